@@ -1,7 +1,15 @@
 #!/usr/bin/env python3
 """bench.py -- stereo pairs/s of the MI355X matcher on BASELINE.json's headline workload.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the headline line (value, ms_per_step, the timed region's steady state
+when it has one).  Everything else below -- value_repeats, the further steady-state region, the event pass (roofline, kernels,
+valu_roofline), single_pair_no_events, pcie_inclusive and with it vs_baseline, other_workloads, cpu_baseline -- runs only under
+--full (vs_baseline is null without it).  --dump-outputs DIR: after the timed steps, rank 0 writes the three result planes of the
+last step (horizontal disparity, vertical disparity, confidence; float32) as DIR/{disparity_x,disparity_y,confidence}.npy -- whole
+when all three fit in 64 MB, else the same fixed, seeded sample of pixels from each (16 MP: 4 Mi pixels, 48 MB); the inputs are
+seeded, so two builds run with the same arguments can be compared output for output.
 
 One "step" = one synthetic 16 MP (4928x3264) stereo pair through the full-resolution 14-level
 pyramid path (BASELINE.json configs[2], the configuration `metric` is quoted on), inputs already
@@ -61,6 +69,9 @@ BYTES_PER_PIXEL = {"k_cost": BYTES_PER_PIXEL_ITER, "k_smooth": 24.0, "k_box": 24
 REFERENCE_PAIRS_PER_S = {"full16mp": 0.1, "fovea16mp": 1.0 / 3.0}  # BASELINE.md section 1 (README.md:15-16): wall clock around one blocking call, copies included
 DEFAULT_BATCH = {"full16mp": 8, "fovea16mp": 8, "1080p": 16}
 PROFILE_TAG = "r06"
+DUMP_BYTES_MAX = 64 << 20     # --dump-outputs: all three planes together
+DUMP_SAMPLE_PIXELS = 1 << 22  # ... and per plane when they are larger (3 x 16 MiB)
+DUMP_SEED = 20251015
 
 WORKLOADS = {
     "full16mp": dict(W=4928, H=3264, mode="full", desc="16MP (4928x3264) stereo pair, full-res 14-level pyramid"),
@@ -193,6 +204,25 @@ def steady_window(call_sizes, slots: int):
     return sum(call_sizes[:ok[0] + 1]) - 1, sum(call_sizes[:ok[-1] + 1]) - 1
 
 
+def dump_outputs(path: str, out) -> None:
+    """--dump-outputs: `out` is one step's result on the device, (3, H, W) or (3, F, fovH, fovW) float32 = horizontal disparity, vertical
+    disparity, confidence.  Written whole when it fits DUMP_BYTES_MAX, else the same seeded sample of DUMP_SAMPLE_PIXELS pixels of each plane
+    (sorted flat indices; the sample depends only on the plane size)."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    planes = out.reshape(3, -1)
+    if out.numel() * out.element_size() <= DUMP_BYTES_MAX:
+        host = out.cpu().numpy()
+    else:
+        rng = np.random.Generator(np.random.PCG64(DUMP_SEED))
+        idx = np.sort(rng.choice(planes.shape[1], DUMP_SAMPLE_PIXELS, replace=False))
+        host = planes[:, torch.from_numpy(idx).to(out.device)].cpu().numpy()
+    for name, a in zip(("disparity_x", "disparity_y", "confidence"), host):
+        np.save(os.path.join(path, f"{name}.npy"), np.ascontiguousarray(a, dtype=np.float32))
+    log(f"outputs of the last timed step: {path}/{{disparity_x,disparity_y,confidence}}.npy, {tuple(host.shape[1:])} each")
+
+
 def spawn_ranks(args) -> int:
     """`--gpus N` without a launcher: start one rank per GPU the way the driver does, from a process that has not touched
     the GPU, and hand back the child's exit code."""
@@ -227,9 +257,18 @@ def main():
                     "have a steady window (-1 = max(steps, 48 x batch, 12 x slots x batch); 0 = no further region: steady_state null)")
     ap.add_argument("--other-steps", type=int, default=64, help="pairs of each leg of `other_workloads` (fovea16mp, 1080p; the default full16mp run on one GPU only; 0 = skip)")
     ap.add_argument("--no-events", action="store_true", help="same as --profile-pairs 0 --no-service --repeats 0 --single-pairs 0 --steady-steps 0 --other-steps 0 (bare throughput line)")
+    ap.add_argument("--full", action="store_true", help="also run every leg beyond the headline figure (value_repeats, the further steady-state region, the event "
+                    "pass, single_pair_no_events, pcie_inclusive and vs_baseline, other_workloads, cpu_baseline), as the options above set them; without "
+                    "it the run is the bare throughput line of --no-events --no-cpu-baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write the result planes of the last one as DIR/<name>.npy (float32, "
+                    "64 MB at most: a fixed, seeded sample of pixels when the planes are larger)")
     args = ap.parse_args()
-    if args.no_events:
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.no_events or not args.full:
         args.profile_pairs, args.no_service, args.repeats, args.single_pairs, args.steady_steps, args.other_steps = 0, True, 0, 0, 0, 0
+    if not args.full:
+        args.no_cpu_baseline = True
     if args.gpus > 1 and "RANK" not in os.environ and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args))
     # stdout carries exactly one line, the JSON result: whatever libraries print on file descriptor 1 on the way
@@ -359,6 +398,8 @@ def main():
     if B > 1:   # ... and enough pairs, untimed, that every slot has run a full-size call: whatever a first batched call sets up is not the workload
         run(2 * slots * B)
     dt = timed(args.steps)
+    if rank == 0 and args.dump_outputs:   # before anything else reuses the ring: step k wrote ring[k % cap] (fovea-shard: ring[k % slots])
+        dump_outputs(args.dump_outputs, ring[(args.steps - 1) % (slots if mode == "fovea-shard" else cap)])
     work = n_gpus if mode != "fovea-shard" else 1
     value = work * args.steps / dt
     timed_calls = call_sizes_of(done)

@@ -4,7 +4,7 @@
 Run from the repo root in the build container:  python tests/golden/make_golden.py
 
 What pins what:
-  * blur_gold.npz  -- expected outputs come from the REFERENCE's own
+  * blur_gold.npz, blur_live_gold.npz  -- expected outputs come from the REFERENCE's own
     convolutionRowCPU / convolutionColumnCPU (oracle/_ref/libgold.so, compiled by
     oracle/Makefile from /root/reference/src/gpu_matcher/convolutionSeparable_gold.cpp where
     it lies).  This is the only executable piece of the reference in this image.
@@ -57,6 +57,26 @@ def blur_gold():
     print("blur_gold: ones row ->", r[0, :3])
 
 
+def blur_live_gold():
+    """The cases of tests/test_oracle_kat.py::test_blur_matches_live_reference_when_present (PCG64(11), values up to 1000, odd
+    sizes), with the reference's own row and column outputs, so that the test runs where oracle/_ref/libgold.so cannot be built."""
+    gold = orc.gold_lib()
+    if gold is None:
+        print("oracle/_ref/libgold.so missing: keeping existing blur_live_gold.npz")
+        return
+    rng = np.random.Generator(np.random.PCG64(11))
+    taps = orc.gauss_taps()
+    cases = {"taps": taps}
+    for H, W in [(17, 23), (2, 2), (40, 131)]:
+        src = rng.random((H, W), dtype=np.float32) * 1000
+        row = np.empty_like(src)
+        col = np.empty_like(src)
+        gold.convolutionRowCPU(fp(row), fp(src), fp(taps), W, H, 2)
+        gold.convolutionColumnCPU(fp(col), fp(row), fp(taps), W, H, 2)
+        cases[f"{W}x{H}_src"], cases[f"{W}x{H}_row"], cases[f"{W}x{H}_col"] = src, row, col
+    np.savez_compressed(os.path.join(OUT, "blur_live_gold.npz"), **cases)
+
+
 def full(W, H, levels, seed):
     L, R, dx, dy = synth.make_pair(W, H, seed)
     out = orc.match_full(L, R, levels)
@@ -96,6 +116,7 @@ def fovea(W, H, levels, F, seed):
 
 if __name__ == "__main__":
     blur_gold()
+    blur_live_gold()
     full(64, 48, 5, synth.BASE_SEED + 100)
     full(160, 120, 8, synth.BASE_SEED + 101)
     stage(96, 72, synth.BASE_SEED + 102)

@@ -81,3 +81,27 @@ def test_the_line_compares_like_with_like_and_carries_the_other_configs():
         assert key in src, key
     assert 'for name in ("fovea16mp", "1080p"):' in src
     assert bench.REFERENCE_PAIRS_PER_S == {"full16mp": 0.1, "fovea16mp": 1.0 / 3.0} and bench.DEFAULT_BATCH["1080p"] == 16
+
+
+def test_dump_outputs_whole_or_a_fixed_sample(tmp_path):
+    """--dump-outputs: the three planes as float32 .npy files, whole when they fit in 64 MB, else the same seeded sample of pixels of each
+    (16 MP: 4 Mi of 16 Mi pixels, 48 MB), identical from run to run."""
+    import numpy as np
+    import torch
+    small = torch.arange(3 * 7 * 40 * 50, dtype=torch.float32).reshape(3, 7, 40, 50)     # a foveated stack's shape
+    bench.dump_outputs(str(tmp_path / "small"), small)
+    for i, name in enumerate(("disparity_x", "disparity_y", "confidence")):
+        a = np.load(tmp_path / "small" / f"{name}.npy")
+        assert a.dtype == np.float32 and np.array_equal(a, small[i].numpy())
+    W, H = 4928, 3264
+    big = (torch.arange(3 * W * H, dtype=torch.int64) % 65521).to(torch.float32).reshape(3, H, W)
+    bench.dump_outputs(str(tmp_path / "a"), big)
+    bench.dump_outputs(str(tmp_path / "b"), big)
+    flat, total = big.reshape(3, -1).numpy(), 0
+    idx = np.sort(np.random.Generator(np.random.PCG64(bench.DUMP_SEED)).choice(W * H, bench.DUMP_SAMPLE_PIXELS, replace=False))
+    for i, name in enumerate(("disparity_x", "disparity_y", "confidence")):
+        a, b = np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy")
+        assert a.dtype == np.float32 and a.shape == (bench.DUMP_SAMPLE_PIXELS,) and np.array_equal(a, b)
+        assert np.array_equal(a, flat[i][idx])
+        total += a.nbytes
+    assert total <= bench.DUMP_BYTES_MAX == 64 << 20

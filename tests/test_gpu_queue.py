@@ -495,7 +495,7 @@ def test_bench_line_keys(lib):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ)
     env.pop("UGSM_DEV", None)     # the product as a user runs it
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--repeats", "0", "--profile-pairs", "1",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--repeats", "0", "--profile-pairs", "1",
                         "--single-pairs", "6", "--other-steps", "32"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -515,6 +515,43 @@ def test_bench_line_keys(lib):
     sp = d["single_pair_no_events"]
     assert 0.9 < sp["on_the_timed_context"]["vs_one_slot_context"] < 1.1, sp      # (reported exactly in the line; 11.6 % apart before round 6)
     assert "roofline" in d and d["roofline"]["kernel"] == "k_cost_march" and 0.1 < d["roofline"]["frac"] < 1.0
+
+
+def test_bench_plain_line_and_dumped_outputs(lib, oracle_16mp_b, tmp_path):
+    """A plain bench.py run (no --full): the headline line and nothing that needs runs of its own; --dump-outputs writes the last timed step's
+    planes -- at 16 MP bench.dump_outputs' seeded sample of pixels -- equal bit for bit to the oracle's answer for that step's pair (step 19
+    of 20: bench.py's second pair)."""
+    import json
+    import os
+    import subprocess
+    import sys
+    import bench
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    env.pop("UGSM_DEV", None)
+    out = tmp_path / "out"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--dump-outputs", str(out)],
+                       env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["metric"] == "stereo pairs/sec at 16MP full-res pyramid" and d["unit"] == "pairs/s" and d["dtype"] == "f32" and d["higher_is_better"] is True
+    assert d["steps"] == 20 and d["warmup"] == 5 and d["calls_formed_by_the_library"] == [4, 5, 7, 4]
+    assert abs(d["value"] * d["ms_per_step"] - 1e3) < 1e-6
+    assert d["vs_baseline"] is None and d["value_repeats"] == [] and d["steady_state"]["value"] is None
+    for key in ("cpu_baseline", "other_workloads", "pcie_inclusive", "single_pair_no_events", "event_pass", "roofline", "kernels"):
+        assert key not in d, key
+    W, H = oracle_16mp_b["W"], oracle_16mp_b["H"]
+    idx = np.sort(np.random.Generator(np.random.PCG64(bench.DUMP_SEED)).choice(W * H, bench.DUMP_SAMPLE_PIXELS, replace=False))
+    ref = oracle_16mp_b["full"].reshape(3, -1)
+    total = 0
+    for i, name in enumerate(("disparity_x", "disparity_y", "confidence")):
+        a = np.load(out / f"{name}.npy")
+        assert a.dtype == np.float32 and a.shape == (bench.DUMP_SAMPLE_PIXELS,), (name, a.dtype, a.shape)
+        assert_bit_equal(a, ref[i, idx], name)
+        total += a.nbytes
+    assert total <= 64 << 20
 
 
 def test_queue_from_plain_c(lib, tmp_path):

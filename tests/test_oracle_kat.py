@@ -99,19 +99,25 @@ def test_blur_matches_reference_gold(orc):
 
 
 def test_blur_matches_live_reference_when_present(orc):
+    """The zero-padded blur against the reference's convolutionRowCPU/ColumnCPU on random images of odd sizes: against their outputs
+    stored in tests/golden/blur_live_gold.npz (make_golden.py) always, and against oracle/_ref/libgold.so itself where it was built."""
+    g = load_golden("blur_live_gold.npz")
     gold = orc.gold_lib()
-    if gold is None:
-        pytest.skip("oracle/_ref/libgold.so not built (no /root/reference here)")
     f32p = C.POINTER(C.c_float)
     rng = np.random.Generator(np.random.PCG64(11))
     taps = orc.gauss_taps()
+    assert_bit_equal(taps, g["taps"], "taps")
     for H, W in [(17, 23), (2, 2), (40, 131)]:
         src = rng.random((H, W), dtype=np.float32) * 1000
-        row = np.empty_like(src)
-        col = np.empty_like(src)
-        gold.convolutionRowCPU(row.ctypes.data_as(f32p), src.ctypes.data_as(f32p), taps.ctypes.data_as(f32p), W, H, 2)
-        gold.convolutionColumnCPU(col.ctypes.data_as(f32p), row.ctypes.data_as(f32p), taps.ctypes.data_as(f32p), W, H, 2)
-        assert_bit_equal(orc.conv(src, taps, "zero"), col, f"{W}x{H}")
+        assert_bit_equal(src, g[f"{W}x{H}_src"], f"{W}x{H} input")
+        assert_bit_equal(orc.conv(src, taps, "zero"), g[f"{W}x{H}_col"], f"{W}x{H}")
+        if gold is not None:
+            row = np.empty_like(src)
+            col = np.empty_like(src)
+            gold.convolutionRowCPU(row.ctypes.data_as(f32p), src.ctypes.data_as(f32p), taps.ctypes.data_as(f32p), W, H, 2)
+            gold.convolutionColumnCPU(col.ctypes.data_as(f32p), row.ctypes.data_as(f32p), taps.ctypes.data_as(f32p), W, H, 2)
+            assert_bit_equal(row, g[f"{W}x{H}_row"], f"{W}x{H} stored row")
+            assert_bit_equal(col, g[f"{W}x{H}_col"], f"{W}x{H} stored col")
 
 
 def test_clamp_conv_constant_field(orc):
