@@ -30,7 +30,9 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-#define UGSM_ABI_VERSION 6  /* 6: the kernel choices follow what is in flight, not ugsm_config.slots: ugsm_plan_level takes `alone`, ugsm_plan_level_in_frame
+#define UGSM_ABI_VERSION 6  /* 6 (additions, nothing changed): the coloured point cloud -- ugsm_cloud_params, UGSM_CLOUD_PCL32 / UGSM_CLOUD_XYZRGB16,
+                               ugsm_default_cloud_params, ugsm_cloud_points, ugsm_point_cloud, ugsm_point_cloud_fovea
+                               6: the kernel choices follow what is in flight, not ugsm_config.slots: ugsm_plan_level takes `alone`, ugsm_plan_level_in_frame
                                is gone, ugsm_level_plan.latency_policy is .alone; ugsm_enqueue_* returns UGSM_OK once the pair is accepted (a failed
                                CALL is reported through ugsm_completion.status only); the fovea shard carries a status word (a rank that fails still
                                reaches the exchange); march_min_pixels < 0 and march_smooth are libugsm_dev.so's
@@ -419,6 +421,45 @@ int ugsm_fovea_mapping(int W, int H, int src_level, int dest_level, int *left_ma
 int ugsm_triangulate_fovea(ugsm_ctx *ctx, int slot, const float *d_stackx, const float *d_stacky, int fovW,
                            int fovH, int src_level, int left_margin, int upper_margin, float scale,
                            const double *P1, const double *P2, float *d_xyz);
+
+/* Row f-1, the cloud itself: what the node's doReconstructionRGB / doReconstructionRGB_FOV (src/pointcloud/getPointCloud.cpp:675-722,
+ * :615-673) build on the host with one pcl::PointXYZRGB push_back per pixel, built on the device from the planes and the left image.
+ * Order as the reference's: column ii outer, row jj inner (a COLUMN-major cloud from row-major planes), pixel (ii, jj) sampled when
+ * ii % sampling == 0 && jj % sampling == 0; an unorganised cloud (width = count, height = 1).  X, Y, Z are bit for bit what
+ * ugsm_triangulate[_fovea] writes for the pixel; rgb = R << 16 | G << 8 | B of the left image (byte0 << 16 | byte1 << 8 | byte2 of
+ * the rgb8 buffer), alpha 0. */
+#define UGSM_CLOUD_PCL32    0  /* pcl::PointXYZRGB as it lies in memory: x, y, z at 0/4/8, 1.0f at 12, the rgb word at 16, 12 zero bytes; point_step 32 */
+#define UGSM_CLOUD_XYZRGB16 1  /* x, y, z, rgb at 0/4/8/12; point_step 16 (a PointCloud2 with the same four fields) */
+typedef struct ugsm_cloud_params {
+    int sampling;        /* >= 1; getPointCloud.cpp:489 uses 1 */
+    int format;          /* UGSM_CLOUD_* */
+    int compact;         /* 0: every sampled pixel in the reference's order; nonzero: only the kept points, in the same relative order */
+    float min_conf;      /* compact: keep conf >= min_conf (a NaN conf is dropped); -inf with d_conf NULL: no confidence test */
+    float z_min, z_max;  /* compact: keep z_min <= Z <= z_max; a non-finite X, Y or Z is never kept */
+} ugsm_cloud_params;
+/* sampling 1, UGSM_CLOUD_PCL32, compact 0, min_conf -inf, z_min -inf, z_max +inf */
+void ugsm_default_cloud_params(ugsm_cloud_params *p);
+/* points of the dense cloud: ceil(W / sampling) * ceil(H / sampling); -1 on bad arguments.  Host only. */
+long long ugsm_cloud_points(int W, int H, int sampling);
+/* The cloud of the full-resolution match.  d_dispx / d_dispy / d_conf: H*W device planes (planes 0, 1, 2 of ugsm_submit_full's d_out;
+ * d_conf may be NULL when p->min_conf is -inf); d_rgbL: the left image, rgb8, `stride` bytes per row, on the device; P1, P2 as for
+ * ugsm_triangulate (host).  d_points (device, 16-byte aligned) receives the first min(count, cap_points) records and nothing past them;
+ * *d_count (device) the cloud's number of points, even where that exceeds cap_points.  Asynchronous on `slot`'s stream, like
+ * ugsm_triangulate (ordered after a submit on the same slot).  A compact cloud uses a per-slot count buffer that grows on demand
+ * (ugsm_context_device_bytes counts it; UGSM_ERR_NOMEM if it cannot grow) and takes two launches; the output is the same byte for byte
+ * from run to run.  UGSM_ERR_BAD_ARG: a null pointer, W or H < 1, stride < 3W, sampling < 1, an unknown format, a NaN min_conf / z_min /
+ * z_max or z_min > z_max, d_conf NULL with min_conf above -inf, cap_points < 0, a misaligned d_points / d_count, above 2^28 pixels. */
+int ugsm_point_cloud(ugsm_ctx *ctx, int slot, const float *d_dispx, const float *d_dispy, const float *d_conf,
+                     const uint8_t *d_rgbL, int W, int H, int stride, const double *P1, const double *P2,
+                     const ugsm_cloud_params *p, void *d_points, long long cap_points, long long *d_count);
+/* The foveated form: the points of level src_level of the (F*fovH) x fovW stacks (d_stackc may be NULL as d_conf above), mapped
+ * into the full-resolution frame with left_margin / upper_margin / scale (ugsm_fovea_mapping), as ugsm_triangulate_fovea does; the
+ * colour is read from the W x H left image at ((int)x1, (int)y1) of the mapped pixel, clamped to the image (at destination level 0
+ * no fovea level leaves the image at 16 MP, 1080p, 640 x 480 or 160 x 120; the reference would read outside it where one did). */
+int ugsm_point_cloud_fovea(ugsm_ctx *ctx, int slot, const float *d_stackx, const float *d_stacky, const float *d_stackc,
+                           int fovW, int fovH, int src_level, int left_margin, int upper_margin, float scale,
+                           const uint8_t *d_rgbL, int W, int H, int stride, const double *P1, const double *P2,
+                           const ugsm_cloud_params *p, void *d_points, long long cap_points, long long *d_count);
 
 /* Row f-3: MatchGPULib::hierarchicalDisparity (MatchGPULib.cpp:2589-2701, kernel MatchLib.cu:435-462):
  * one full-resolution (dx, dy, conf) field from the foveated stacks -- the coarsest fovea level (the whole

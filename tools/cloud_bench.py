@@ -1,0 +1,149 @@
+#!/usr/bin/env python3
+"""The coloured point cloud on the device (ugsm_point_cloud) -- time, bytes, rate, and the host copy it replaces.
+
+    python tools/cloud_bench.py [--reps 25] [--warmup 5] [--out FILE.json]
+
+For 16 MP (4928 x 3264) and 1080p, each cloud form (dense PCL32, dense 16-byte, compact PCL32 / 16-byte with min_conf 0.5) at sampling
+1 and 2, from the (dx, dy, conf) of a real match of the synthetic pair:
+  - device_ms: the call's device time, median over --reps calls after --warmup, from the library's own in-dispatch events
+    (ugsm_config.profile_events 2: from the first launch's begin to the last launch's end; a compact cloud is two launches);
+  - MB: bytes the call must move, from the shapes and the count -- dx, dy (+ conf when compacting; the count launch reads dx, dy, conf
+    once more) and 3 B of rgb per sampled point read, count x point_step written;
+  - GBps, of_copy: MB / device_ms, and that over the device-to-device copy rate measured here the way bench.py records device_copy_GBps
+    (a streaming elementwise kernel, 1 GiB read + 1 GiB written per pass); floor_ms = MB at that rate, of_floor = floor_ms / device_ms;
+  - d2h_ms: the device-to-host copy of the cloud (count x point_step) into page-locked memory, median of wall-clock copies.
+Today's path, per size: ugsm_triangulate (device_ms as above) and the copy of its three float planes to page-locked memory.
+Prints one JSON line per row and writes them all to --out.
+"""
+import argparse
+import ctypes as C
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+P1 = np.array([[7.3230899280915291e+03, 0., 2.4836974544986647e+03, 0.],
+               [0., 7.3035803715514758e+03, 1.7170248033347561e+03, 0.], [0., 0., 1., 0.]])
+P2 = P1.copy()
+P2[0, 3] = -7.3230899280915291e+03 * 0.12
+
+
+def device_ms(c, call):
+    """One call's device time from the library's events (profile_events 2): reset, call, wait, sum what was harvested."""
+    lib = c.lib
+    c.check(lib.ugsm_reset_kernel_stats(c.handle))
+    call()
+    c.check(lib.ugsm_wait(c.handle, 0))
+    from ug_stereomatcher_amd import _lib
+    st = (_lib.KernelStat * 64)()
+    n = lib.ugsm_get_kernel_stats(c.handle, st, 64)
+    return sum(st[k].total_ms for k in range(min(n, 64)))
+
+
+def median_ms(c, call, reps, warmup):
+    for _ in range(warmup):
+        device_ms(c, call)
+    return float(np.median([device_ms(c, call) for _ in range(reps)]))
+
+
+def host_copy_ms(c, dst, src, nbytes, reps):
+    ts = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        c.check(c.lib.ugsm_copy_to_host(c.handle, dst, src, nbytes))
+        ts.append((time.perf_counter() - t0) * 1e3)
+    return float(np.median(ts))
+
+
+def copy_rate_GBps(torch):
+    a = torch.zeros(1 << 28, dtype=torch.float32, device="cuda")
+    b = torch.empty_like(a)
+    for _ in range(3):
+        torch.add(a, 1.0, out=b)
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(8):
+        torch.add(a, 1.0, out=b)
+    e1.record()
+    torch.cuda.synchronize()
+    r = 8 * 2 * a.numel() * 4 / (e0.elapsed_time(e1) * 1e-3) / 1e9
+    del a, b
+    torch.cuda.empty_cache()
+    return r
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=25)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--sizes", default="4928x3264,1920x1080")
+    ap.add_argument("--out")
+    args = ap.parse_args()
+    from ug_stereomatcher_amd import _lib, synth
+    import torch
+    rows = []
+
+    def emit(r):
+        rows.append(r)
+        print(json.dumps(r), flush=True)
+
+    copy = copy_rate_GBps(torch)
+    emit({"what": "device_copy", "GBps": round(copy, 1)})
+    p1, p2 = (np.ascontiguousarray(m, np.float64).reshape(12) for m in (P1, P2))
+    dp = C.POINTER(C.c_double)
+    for size in args.sizes.split(","):
+        W, H = (int(v) for v in size.split("x"))
+        L, R, _, _ = synth.make_pair(W, H, synth.BASE_SEED + 2)
+        with _lib.Context(levels=14, profile_events=2) as c:
+            pL, pR = c.to_device(L), c.to_device(R)
+            d_out = c.alloc(3 * W * H * 4)
+            c.check(c.lib.ugsm_submit_full(c.handle, 0, pL, pR, W, H, L.strides[0], d_out))
+            c.check(c.lib.ugsm_wait(c.handle, 0))
+            plane = W * H * 4
+            d_dx, d_dy, d_conf = d_out, d_out + plane, d_out + 2 * plane
+            d_pts, d_cnt = c.alloc(W * H * 32), c.alloc(8)
+            host = c.host_array((W * H * 32,), np.uint8)
+            h_addr = host.ctypes.data
+            # today's path: X, Y, Z planes, then the three planes to the host
+            d_xyz = c.alloc(3 * plane)
+            tri = lambda: c.check(c.lib.ugsm_triangulate(c.handle, 0, d_dx, d_dy, W, H, p1.ctypes.data_as(dp), p2.ctypes.data_as(dp), d_xyz))
+            t_tri = median_ms(c, tri, args.reps, args.warmup)
+            t_planes = host_copy_ms(c, h_addr, d_xyz, 3 * plane, max(5, args.reps // 3))
+            mb = (8 + 12) * W * H / 1e6
+            emit({"what": "planes_today", "size": size, "device_ms": round(t_tri, 4), "MB": round(mb, 1), "GBps": round(mb / t_tri, 1),
+                  "d2h_MB": round(3 * plane / 1e6, 1), "d2h_ms": round(t_planes, 3), "total_ms": round(t_tri + t_planes, 3)})
+            c.free(d_xyz)
+            for s in (1, 2):
+                for name, fmt, compact in (("dense_pcl32", 0, False), ("dense_xyzrgb16", 1, False), ("compact_pcl32", 0, True),
+                                           ("compact_xyzrgb16", 1, True)):
+                    prm = _lib.cloud_params(sampling=s, format=fmt, compact=compact, min_conf=0.5 if compact else None)
+                    npts = _lib.cloud_points(W, H, s)
+                    call = lambda: c.check(c.lib.ugsm_point_cloud(c.handle, 0, d_dx, d_dy, d_conf, pL, W, H, L.strides[0], p1.ctypes.data_as(dp),
+                                                                  p2.ctypes.data_as(dp), C.byref(prm), d_pts, npts, d_cnt))
+                    t = median_ms(c, call, args.reps, args.warmup)
+                    count = int(c.to_host(d_cnt, (1,), np.int64)[0])
+                    step = 32 if fmt == 0 else 16
+                    read = npts * ((8 + 4) + (8 + 4 + 3) if compact else 8 + 3)
+                    mb = (read + count * step) / 1e6
+                    floor = mb / 1e3 / copy * 1e3  # ms
+                    t_d2h = host_copy_ms(c, h_addr, d_pts, count * step, max(5, args.reps // 3)) if count else 0.0
+                    emit({"what": name, "size": size, "sampling": s, "points": npts, "count": count, "device_ms": round(t, 4),
+                          "MB": round(mb, 1), "GBps": round(mb / t, 1), "of_copy": round(mb / t / copy, 3), "floor_ms": round(floor, 4),
+                          "of_floor": round(floor / t, 3), "d2h_MB": round(count * step / 1e6, 1), "d2h_ms": round(t_d2h, 3),
+                          "total_ms": round(t + t_d2h, 3)})
+            for p in (pL, pR, d_out, d_pts, d_cnt):
+                c.free(p)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(rows, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()

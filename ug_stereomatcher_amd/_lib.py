@@ -50,9 +50,21 @@ EXPORTS = [
     # ... and RCCL inside the library
     "ugsm_shard_unique_id", "ugsm_shard_init", "ugsm_shard_init_all", "ugsm_shard_rank", "ugsm_shard_count_ranks", "ugsm_submit_fovea_shard", "ugsm_shard_set_timeout",
     "ugsm_shard_gather", "ugsm_shard_finalize", "ugsm_context_device_bytes",
+    # row f-1: the coloured point cloud
+    "ugsm_default_cloud_params", "ugsm_cloud_points", "ugsm_point_cloud", "ugsm_point_cloud_fovea",
 ]
 # ... and what include/ugsm_dev.h adds (libugsm_dev.so only)
 DEV_EXPORTS = ["ugsm_stage_poly_probe", "ugsm_stage_div3_probe", "ugsm_stage_div_probe"]
+
+
+UGSM_CLOUD_PCL32 = 0     # pcl::PointXYZRGB in memory: x, y, z, 1.0f, rgb word, 12 zero bytes (32 B)
+UGSM_CLOUD_XYZRGB16 = 1  # x, y, z, rgb word (16 B)
+# the records as numpy structured dtypes (explicit offsets; rgb is the packed R << 16 | G << 8 | B word)
+CLOUD_PCL32 = np.dtype({"names": ["x", "y", "z", "w", "rgb"], "formats": [np.float32, np.float32, np.float32, np.float32, np.uint32],
+                        "offsets": [0, 4, 8, 12, 16], "itemsize": 32})
+CLOUD_XYZRGB16 = np.dtype({"names": ["x", "y", "z", "rgb"], "formats": [np.float32, np.float32, np.float32, np.uint32],
+                           "offsets": [0, 4, 8, 12], "itemsize": 16})
+CLOUD_DTYPES = {UGSM_CLOUD_PCL32: CLOUD_PCL32, UGSM_CLOUD_XYZRGB16: CLOUD_XYZRGB16}
 
 
 class UgsmError(RuntimeError):
@@ -67,6 +79,12 @@ class Config(C.Structure):
                 ("kernel_path", C.c_int), ("profile_events", C.c_int), ("march_min_pixels", C.c_int), ("march_np", C.c_int),
                 ("march_rows", C.c_int), ("march_smooth", C.c_int), ("early_exit_threshold", C.c_float), ("small_max_pixels", C.c_int),
                 ("lr_check_threshold", C.c_float), ("streams", C.c_int), ("batch", C.c_int), ("stream_priority", C.c_int)]
+
+
+class CloudParams(C.Structure):
+    """ugsm_cloud_params (include/ugsm.h)."""
+    _fields_ = [("sampling", C.c_int), ("format", C.c_int), ("compact", C.c_int), ("min_conf", C.c_float), ("z_min", C.c_float),
+                ("z_max", C.c_float)]
 
 
 class LevelPlan(C.Structure):
@@ -260,6 +278,14 @@ def load(dev: bool = False):
     lib.ugsm_shard_set_timeout.argtypes = [vp, C.c_longlong]
     lib.ugsm_shard_gather.argtypes = [vp, i, vp, C.c_longlong, vp, i]
     lib.ugsm_shard_finalize.argtypes = [vp]
+    lib.ugsm_default_cloud_params.argtypes = [C.POINTER(CloudParams)]
+    lib.ugsm_default_cloud_params.restype = None
+    lib.ugsm_cloud_points.argtypes = [i, i, i]
+    lib.ugsm_cloud_points.restype = C.c_longlong
+    dpp = C.POINTER(C.c_double)
+    lib.ugsm_point_cloud.argtypes = [vp, i, vp, vp, vp, vp, i, i, i, dpp, dpp, C.POINTER(CloudParams), vp, C.c_longlong, vp]
+    lib.ugsm_point_cloud_fovea.argtypes = [vp, i, vp, vp, vp, i, i, i, i, i, C.c_float, vp, i, i, i, dpp, dpp, C.POINTER(CloudParams), vp,
+                                           C.c_longlong, vp]
     if bool(lib.ugsm_is_dev_library()) != bool(dev):
         raise UgsmError(UGSM_ERR_STATE, f"{path} is not the {'development' if dev else 'product'} build")
     _libs[dev] = lib
@@ -307,6 +333,23 @@ def fovea_dims(W: int, H: int, levels: int = 14, fovea_levels: int = 7):
 
 def pixel_iterations(W: int, H: int, levels: int = 14, fovea_levels: int = 0) -> int:
     return int(load().ugsm_pixel_iterations(W, H, levels, fovea_levels))
+
+
+def cloud_params(sampling: int = 1, format: int = UGSM_CLOUD_PCL32, compact: bool = False, min_conf: float | None = None,
+                 z_min: float | None = None, z_max: float | None = None) -> CloudParams:
+    """ugsm_cloud_params from ugsm_default_cloud_params with the named fields changed (None: the default)."""
+    p = CloudParams()
+    load().ugsm_default_cloud_params(C.byref(p))
+    p.sampling, p.format, p.compact = int(sampling), int(format), int(bool(compact))
+    for name, v in (("min_conf", min_conf), ("z_min", z_min), ("z_max", z_max)):
+        if v is not None:
+            setattr(p, name, float(v))
+    return p
+
+
+def cloud_points(W: int, H: int, sampling: int = 1) -> int:
+    """Points of the dense cloud, ceil(W / s) * ceil(H / s); -1 on bad arguments."""
+    return int(load().ugsm_cloud_points(W, H, sampling))
 
 
 # ---- context -----------------------------------------------------------------------------
@@ -416,6 +459,37 @@ class Context:
         self.check(self.lib.ugsm_triangulate_fovea(self._h, slot, d_stackx, d_stacky, fovW, fovH, src_level, left, upper,
                                                    C.c_float(float(scale)), p1.ctypes.data_as(dp), p2.ctypes.data_as(dp), d_xyz))
         self.check(self.lib.ugsm_wait(self._h, slot))
+
+    def point_cloud(self, d_dispx: int, d_dispy: int, d_conf, d_rgbL: int, W: int, H: int, stride: int, P1, P2, params: CloudParams,
+                    d_points: int, cap_points: int, d_count: int, slot: int = 0) -> int:
+        """Row f-1, the coloured cloud (getPointCloud.cpp doReconstructionRGB, :675-722) into d_points; waits on the slot and returns the
+        cloud's number of points (which may exceed cap_points: only the first cap_points records are written)."""
+        p1 = np.ascontiguousarray(P1, np.float64).reshape(12)
+        p2 = np.ascontiguousarray(P2, np.float64).reshape(12)
+        dp = C.POINTER(C.c_double)
+        self.check(self.lib.ugsm_point_cloud(self._h, slot, d_dispx, d_dispy, d_conf, d_rgbL, W, H, stride, p1.ctypes.data_as(dp),
+                                             p2.ctypes.data_as(dp), C.byref(params), d_points, int(cap_points), d_count))
+        self.check(self.lib.ugsm_wait(self._h, slot))
+        return int(self.to_host(d_count, (1,), np.int64)[0])
+
+    def point_cloud_fovea(self, d_stackx: int, d_stacky: int, d_stackc, fovW: int, fovH: int, src_level: int, left: int, upper: int, scale,
+                          d_rgbL: int, W: int, H: int, stride: int, P1, P2, params: CloudParams, d_points: int, cap_points: int, d_count: int,
+                          slot: int = 0) -> int:
+        """Row f-1, the foveated cloud (doReconstructionRGB_FOV, :615-673) of level src_level of the stacks; waits, returns the count."""
+        p1 = np.ascontiguousarray(P1, np.float64).reshape(12)
+        p2 = np.ascontiguousarray(P2, np.float64).reshape(12)
+        dp = C.POINTER(C.c_double)
+        self.check(self.lib.ugsm_point_cloud_fovea(self._h, slot, d_stackx, d_stacky, d_stackc, fovW, fovH, src_level, left, upper,
+                                                   C.c_float(float(scale)), d_rgbL, W, H, stride, p1.ctypes.data_as(dp), p2.ctypes.data_as(dp),
+                                                   C.byref(params), d_points, int(cap_points), d_count))
+        self.check(self.lib.ugsm_wait(self._h, slot))
+        return int(self.to_host(d_count, (1,), np.int64)[0])
+
+    def cloud_to_host(self, d_points: int, count: int, format: int = UGSM_CLOUD_PCL32) -> np.ndarray:
+        """The first `count` records at d_points as a structured array of CLOUD_PCL32 or CLOUD_XYZRGB16."""
+        if int(count) == 0:
+            return np.empty(0, CLOUD_DTYPES[format])
+        return self.to_host(d_points, (int(count),), CLOUD_DTYPES[format])
 
     def reconstruct_full(self, d_stackH: int, d_stackV: int, d_stackC: int, W: int, H: int, d_out3: int, off_x: int = 0, off_y: int = 0,
                          slot: int = 0):

@@ -2,7 +2,8 @@
 //
 // k_seed (a level's starting field where the next level's K-cost does not seed itself), k_copy_view (the fovea / pyramid stacks),
 // k_rgb_planes (level 0 of a pyramid of fewer than three levels: BASELINE configs[0]), k_lr_check (the opt-in LR-consistency check),
-// k_triangulate[_fovea], k_upsample_paste (row f-3), k_wdiff_* (row f-4).  All HBM- or launch-bound.
+// k_triangulate[_fovea] (the X, Y, Z planes and, as other forms of the same kernels, the coloured point cloud),
+// k_upsample_paste (row f-3), k_wdiff_* (row f-4).  All HBM- or launch-bound.
 // Citations: /root/reference/src/gpu_matcher/<file>:<line> unless a path is given.
 #include "ugsm_device.hpp"
 #include "ugsm_launch.hpp"
@@ -168,9 +169,15 @@ __device__ __forceinline__ void tri_point(float x1, float y1, float x2, float y2
     Z = ZUp / divisor;
 }
 
+// The forms of k_triangulate / k_triangulate_fovea (template parameter): the X, Y, Z planes, and the two launches of the point cloud
+// (below).  The plane form keeps its own parameter list, so its code is what it was before the cloud forms came.
+enum TriForm : int { kTriPlanes = 0, kTriCloudCount = 1, kTriCloud = 2 };
+
+template <int Form>
 __global__ __launch_bounds__(256) void k_triangulate(const float *__restrict__ dispx, const float *__restrict__ dispy, int W, int H, Proj P1q, Proj P2q,
                                                      float *__restrict__ xyz)
 {
+    static_assert(Form == kTriPlanes, "the plane form");
     const int xx = blockIdx.x * blockDim.x + threadIdx.x;
     const int yy = blockIdx.y;
     if (xx >= W) return;
@@ -190,10 +197,12 @@ __global__ __launch_bounds__(256) void k_triangulate(const float *__restrict__ d
 // get3DPoint, foveated branch (getPointCloud.cpp:892-903): level src_level of the (F*fovH) x fovW stacks, pixel
 // coordinates mapped into the full-resolution frame by mapXcoord / mapYcoord (:387-421).  Those take an int, so the
 // right-image coordinate xx + disparity is truncated toward zero before scaling -- kept as in the reference.
+template <int Form>
 __global__ __launch_bounds__(256) void k_triangulate_fovea(const float *__restrict__ stackx, const float *__restrict__ stacky, int fovW, int fovH,
                                                            int src_level, int left_margin, int upper_margin, float scale, Proj P1q, Proj P2q,
                                                            float *__restrict__ xyz)
 {
+    static_assert(Form == kTriPlanes, "the plane form");
     const int xx = blockIdx.x * blockDim.x + threadIdx.x;
     const int yy = blockIdx.y;
     if (xx >= fovW) return;
@@ -216,7 +225,8 @@ void launch_triangulate(hipStream_t st, const float *dispx, const float *dispy, 
 {
     Proj a, b;
     for (int k = 0; k < 12; k++) { a.m[k] = P1[k]; b.m[k] = P2[k]; }
-    UGSM_LAUNCH(k_triangulate, dim3((W + 255) / 256, H), dim3(256), 0, st, dispx, dispy, W, H, a, b, xyz);
+    void (*const kern)(const float *, const float *, int, int, Proj, Proj, float *) = k_triangulate<kTriPlanes>;
+    UGSM_LAUNCH(kern, dim3((W + 255) / 256, H), dim3(256), 0, st, dispx, dispy, W, H, a, b, xyz);
 }
 
 void launch_triangulate_fovea(hipStream_t st, const float *stackx, const float *stacky, int fovW, int fovH, int src_level, int left_margin,
@@ -224,8 +234,182 @@ void launch_triangulate_fovea(hipStream_t st, const float *stackx, const float *
 {
     Proj a, b;
     for (int k = 0; k < 12; k++) { a.m[k] = P1[k]; b.m[k] = P2[k]; }
-    UGSM_LAUNCH(k_triangulate_fovea, dim3((fovW + 255) / 256, fovH), dim3(256), 0, st, stackx, stacky, fovW, fovH, src_level, left_margin,
+    void (*const kern)(const float *, const float *, int, int, int, int, int, float, Proj, Proj, float *) = k_triangulate_fovea<kTriPlanes>;
+    UGSM_LAUNCH(kern, dim3((fovW + 255) / 256, fovH), dim3(256), 0, st, stackx, stacky, fovW, fovH, src_level, left_margin,
                        upper_margin, scale, a, b, xyz);
+}
+
+// =========================================================================================
+// SURVEY 8f row f-1, second half: the coloured point cloud, getPointCloud.cpp doReconstructionRGB (:675-722) and
+// doReconstructionRGB_FOV (:615-673) -- the node's scalar double loop over the pixels with one push_back per pixel.
+// Column ii is the outer loop and row jj the inner one, so the cloud is COLUMN-major while the planes are row-major: record
+// (ci, cj) of the sampled grid (ii = ci * s, jj = cj * s) is record ci * hc + cj of the dense cloud.  X, Y, Z are tri_point's, from
+// the same operands as the plane form computes them (bit-identical); the colour word is R << 16 | G << 8 | B of the left image
+// (the node's BGR8 copy, :225, packed at :703-714), i.e. byte0 << 16 | byte1 << 8 | byte2 of the rgb8 buffer, alpha 0.
+//
+// One workgroup per tile of kCloudTC sampled columns x kCloudTR sampled rows, three phases:
+//   A  evaluate: lane (t mod 32) = column, so every read is a row-coalesced run (4-byte dx, dy, conf; rgb bytes); the record
+//      (x, y, z, rgb word) goes to LDS at [column][row] and whether it is kept to a byte array;
+//   B  one wave per column, lane = row: a ballot of the kept flags gives every kept row its rank in the column's run (dense: every
+//      row inside the grid is kept, so the ranks are the rows), and `src` the row of each rank;
+//   C  every column's run of the tile is one contiguous block of the output, written with whole 16-byte stores, one wave instruction
+//      covering 1 KB of it: 32 records of 32 B (PCL32) or 64 of 16 B (XYZRGB16).
+// Compact clouds take two launches.  The count form (kTriCloudCount) runs A and B and writes each column's kept count per chunk of
+// kCloudTR rows, and adds it to the column's and the strip's (the tile column's) totals with integer atomics: order-independent sums,
+// deterministic.  The cloud form (kTriCloud) derives each run's first record from those counts -- the strips to its left, the strip's
+// columns to its left, the chunks above it -- and re-evaluates its tile (tri_point is cheap beside a second pass over the output).
+// No workgroup waits for another inside a launch.  Records at or past cap are not written; `count` gets the cloud's size.
+// =========================================================================================
+constexpr int kCloudTC = 32;             // sampled columns per tile
+constexpr int kCloudTR = 64;             // sampled rows per tile = lanes of a wave (phase B)
+constexpr int kCloudPad = kCloudTR + 1;  // records per column in LDS: column c starts 4c banks further on (phase A stores 32 columns at once)
+
+// one sampled point: its record (x, y, z, rgb word as float bits) and whether a compact cloud keeps it
+template <bool Fovea, bool Colour>
+__device__ __forceinline__ bool cloud_point(const CloudArgs &a, const Proj &P1q, const Proj &P2q, int ii, int jj, float4 &rec)
+{
+    const size_t at = (size_t)jj * a.pw + ii;
+    float x1, y1, x2, y2;
+    int cx, cy;
+    if (Fovea) {  // as k_triangulate_fovea; the colour from the full-resolution image at ((int)mapXcoord(ii), (int)mapYcoord(jj)) (:630-640)
+        x1 = (float)a.left_margin + (float)ii * a.scale;
+        y1 = (float)a.upper_margin + (float)jj * a.scale;
+        const int sx = (int)(ii + a.dx[at]);
+        const int sy = (int)(jj + a.dy[at]);
+        x2 = (float)a.left_margin + (float)sx * a.scale;
+        y2 = (float)a.upper_margin + (float)sy * a.scale;
+        // clamped to the image (the reference reads whatever lies there): at destination level 0 no fovea level's window leaves the
+        // image at 16 MP, 1080p, 640 x 480 or 160 x 120, so the clamp only acts on margins a caller pushes past the edge
+        cx = min(max((int)x1, 0), a.W - 1);
+        cy = min(max((int)y1, 0), a.H - 1);
+    } else {      // as k_triangulate
+        x1 = ii;
+        y1 = jj;
+        x2 = ii + a.dx[at];
+        y2 = jj + a.dy[at];
+        cx = ii;
+        cy = jj;
+    }
+    float X, Y, Z;
+    tri_point(x1, y1, x2, y2, P1q.m, P2q.m, X, Y, Z);
+    if (Colour) {
+        const uint8_t *p = a.rgb + (size_t)cy * a.stride + 3 * (size_t)cx;
+        const unsigned word = (unsigned)p[0] << 16 | (unsigned)p[1] << 8 | (unsigned)p[2];
+        rec = make_float4(X, Y, Z, __uint_as_float(word));
+    }
+    if (!a.compact) return true;
+    bool keep = __builtin_isfinite(X) && __builtin_isfinite(Y) && __builtin_isfinite(Z) && Z >= a.z_min && Z <= a.z_max;
+    if (a.conf) keep = keep && a.conf[at] >= a.min_conf;  // (a NaN confidence fails the comparison)
+    return keep;
+}
+
+template <bool Fovea, int Form>
+__device__ __forceinline__ void cloud_tile(const CloudArgs &a, const Proj &P1q, const Proj &P2q)
+{
+    __shared__ float4 rec[kCloudTC * kCloudPad];
+    __shared__ unsigned char kept[kCloudTC * kCloudTR];
+    __shared__ unsigned char src[kCloudTC * kCloudTR];
+    __shared__ int nrec[kCloudTC];
+    __shared__ unsigned pre[kCloudTC + 1];  // compact: [c] the run's first record less the strip's, [kCloudTC] the strip's first record
+    const int t = threadIdx.x, tx = blockIdx.x, ty = blockIdx.y;
+    const int c0 = tx * kCloudTC, r0 = ty * kCloudTR;
+    const int c = t & (kCloudTC - 1), ci = c0 + c;
+    unsigned *const col_tot = a.cnt + (size_t)a.wc * a.nchunk, *const strip_tot = col_tot + a.wc;  // (compact only)
+    if (Form == kTriCloud && a.compact && t <= kCloudTC) pre[t] = 0;
+    // A: evaluate the tile
+    for (int r = t / kCloudTC; r < kCloudTR; r += 256 / kCloudTC) {
+        const int cj = r0 + r;
+        bool k = false;
+        if (ci < a.wc && cj < a.hc) {
+            float4 v;
+            k = cloud_point<Fovea, Form == kTriCloud>(a, P1q, P2q, ci * a.s, cj * a.s, v);
+            if (Form == kTriCloud) rec[c * kCloudPad + r] = v;
+        }
+        kept[c * kCloudTR + r] = k;
+    }
+    __syncthreads();
+    if (Form == kTriCloud && a.compact) {  // the runs' offsets: integer sums of the count launch's results
+        unsigned v = 0, w = 0;
+        for (int k = t; k < tx; k += 256) v += strip_tot[k];               // strips to the left
+        if (ci < a.wc) {
+            for (int k = t / kCloudTC; k < ty; k += 256 / kCloudTC) w += a.cnt[(size_t)ci * a.nchunk + k];  // chunks above
+            for (int k = t / kCloudTC; k < c; k += 256 / kCloudTC) w += col_tot[c0 + k];                    // the strip's columns to the left
+        }
+        if (v) atomicAdd(&pre[kCloudTC], v);
+        if (w) atomicAdd(&pre[c], w);
+    }
+    // B: each column's kept rows, ranked
+    const int lane = t & 63;
+    for (int cc = t >> 6; cc < kCloudTC; cc += 4) {
+        const bool k = kept[cc * kCloudTR + lane] != 0;
+        const unsigned long long m = __builtin_amdgcn_ballot_w64(k);
+        if (Form == kTriCloud && k) src[cc * kCloudTR + __builtin_popcountll(m & ((1ull << lane) - 1))] = (unsigned char)lane;
+        if (lane == 0) {
+            const int n = __builtin_popcountll(m);
+            nrec[cc] = n;
+            if (Form == kTriCloudCount && c0 + cc < a.wc) {
+                a.cnt[(size_t)(c0 + cc) * a.nchunk + ty] = (unsigned)n;
+                if (n) {
+                    atomicAdd(&col_tot[c0 + cc], (unsigned)n);
+                    atomicAdd(&strip_tot[tx], (unsigned)n);
+                }
+            }
+        }
+    }
+    if (Form == kTriCloudCount) return;
+    __syncthreads();
+    // the cloud's size: one workgroup writes it
+    if (t == 0 && ty == 0 && tx == (a.compact ? (int)gridDim.x - 1 : 0))
+        *a.count = a.compact ? (long long)pre[kCloudTC] + strip_tot[tx] : (long long)a.wc * a.hc;
+    // C: every column's run, contiguous
+    if (a.format == 0) {  // UGSM_CLOUD_PCL32: (x, y, z, 1.0f) and (rgb, 0, 0, 0), 32 B per record
+        float4 *out = reinterpret_cast<float4 *>(a.points);
+        for (int q = t; q < kCloudTC * 2 * kCloudTR; q += 256) {
+            const int cc = q / (2 * kCloudTR), j = (q >> 1) & (kCloudTR - 1), half = q & 1;
+            if (j >= nrec[cc]) continue;
+            const long long o = (a.compact ? (long long)pre[kCloudTC] + pre[cc] : (long long)(c0 + cc) * a.hc + r0) + j;
+            if (o >= a.cap) continue;
+            const float4 v = rec[cc * kCloudPad + src[cc * kCloudTR + j]];
+            out[2 * o + half] = half ? make_float4(v.w, 0.0f, 0.0f, 0.0f) : make_float4(v.x, v.y, v.z, 1.0f);
+        }
+    } else {              // UGSM_CLOUD_XYZRGB16: (x, y, z, rgb), 16 B per record
+        float4 *out = reinterpret_cast<float4 *>(a.points);
+        for (int q = t; q < kCloudTC * kCloudTR; q += 256) {
+            const int cc = q / kCloudTR, j = q & (kCloudTR - 1);
+            if (j >= nrec[cc]) continue;
+            const long long o = (a.compact ? (long long)pre[kCloudTC] + pre[cc] : (long long)(c0 + cc) * a.hc + r0) + j;
+            if (o >= a.cap) continue;
+            out[o] = rec[cc * kCloudPad + src[cc * kCloudTR + j]];
+        }
+    }
+}
+
+template <int Form>
+__global__ __launch_bounds__(256) void k_triangulate(CloudArgs a, Proj P1q, Proj P2q)
+{
+    static_assert(Form == kTriCloudCount || Form == kTriCloud, "the cloud forms");
+    cloud_tile<false, Form>(a, P1q, P2q);
+}
+template <int Form>
+__global__ __launch_bounds__(256) void k_triangulate_fovea(CloudArgs a, Proj P1q, Proj P2q)
+{
+    static_assert(Form == kTriCloudCount || Form == kTriCloud, "the cloud forms");
+    cloud_tile<true, Form>(a, P1q, P2q);
+}
+
+int cloud_strips(int wc) { return (wc + kCloudTC - 1) / kCloudTC; }
+int cloud_chunks(int hc) { return (hc + kCloudTR - 1) / kCloudTR; }
+
+void launch_point_cloud(hipStream_t st, const CloudArgs &args, bool fovea, const double *P1, const double *P2)
+{
+    Proj a, b;
+    for (int k = 0; k < 12; k++) { a.m[k] = P1[k]; b.m[k] = P2[k]; }
+    const dim3 grid(cloud_strips(args.wc), args.nchunk);
+    using Kern = void (*)(CloudArgs, Proj, Proj);
+    const Kern count = fovea ? (Kern)k_triangulate_fovea<kTriCloudCount> : (Kern)k_triangulate<kTriCloudCount>;
+    const Kern cloud = fovea ? (Kern)k_triangulate_fovea<kTriCloud> : (Kern)k_triangulate<kTriCloud>;
+    if (args.compact) UGSM_LAUNCH(count, grid, dim3(256), 0, st, args, a, b);
+    UGSM_LAUNCH(cloud, grid, dim3(256), 0, st, args, a, b);
 }
 
 // =========================================================================================

@@ -67,6 +67,27 @@ void launch_lr_check(hipStream_t st, float *left3, const float *right3, int W, i
 void launch_triangulate(hipStream_t st, const float *dispx, const float *dispy, int W, int H, const double *P1, const double *P2, float *xyz);
 void launch_triangulate_fovea(hipStream_t st, const float *stackx, const float *stacky, int fovW, int fovH, int src_level, int left_margin,
                               int upper_margin, float scale, const double *P1, const double *P2, float *xyz);
+// SURVEY 8f row f-1, the coloured point cloud (ugsm_point_cloud[_fovea]): the forms kTriCloudCount / kTriCloud of k_triangulate[_fovea].
+// The sampled grid is wc x hc points (point (ci, cj) = pixel (ci * s, cj * s) of the planes); tiles of 32 columns x 64 rows of it.
+struct CloudArgs {
+    const float *dx, *dy, *conf;  // pw x ph row-major planes (the fovea form: level src_level of the stacks); conf may be null
+    int pw, ph;
+    const uint8_t *rgb;           // the left image, rgb8, W x H, `stride` bytes per row
+    int W, H, stride;
+    int s, wc, hc, nchunk;        // sampling; the sampled grid; cloud_chunks(hc)
+    int format, compact;          // UGSM_CLOUD_PCL32 (0) / UGSM_CLOUD_XYZRGB16 (1); compact: only the points that pass the filter
+    float min_conf, z_min, z_max;
+    int left_margin, upper_margin;  // the fovea form: mapXcoord / mapYcoord (ugsm_fovea_mapping)
+    float scale;
+    unsigned *cnt;  // compact: wc * nchunk counts, wc column totals, cloud_strips(wc) strip totals; the totals zeroed before the launch
+    void *points;   // 16-byte aligned
+    long long cap;
+    long long *count;
+};
+int cloud_strips(int wc);
+int cloud_chunks(int hc);
+// compact: a count launch, then the cloud launch; dense: the cloud launch
+void launch_point_cloud(hipStream_t st, const CloudArgs &args, bool fovea, const double *P1, const double *P2);
 void launch_upsample_paste(hipStream_t st, const float *src3, int W, int H, float *dst3, int W2, int H2, const float *fovH_, const float *fovV_,
                            const float *fovC_, int fovW, int fovH, int org_x, int org_y);
 // S_dx, S_dy, C of weightedDifference (MatchGPULib.cpp:1336-1437) into out3; rowsum = 3*H doubles of scratch

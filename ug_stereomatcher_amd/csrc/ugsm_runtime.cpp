@@ -103,6 +103,8 @@ struct Slot {
     double *wd_rows = nullptr;      // row f-4 scratch: 3 doubles per row + 3 totals
     size_t wd_cap = 0;
     double *wd_host = nullptr;      // page-locked, 3 doubles
+    unsigned *cloud_cnt = nullptr;  // row f-1 cloud, compact: per (column, chunk) counts + column and strip totals (CloudArgs.cnt)
+    size_t cloud_cap = 0;
     int iters_run[UGSM_MAX_LEVELS];
     unsigned *range_bad = nullptr;  // device word: 0 while every pyramid value of the pair in this slot passed range_ok (ugsm_exact.hpp)
     float *hout = nullptr;  // device staging for host-API outputs
@@ -1674,6 +1676,7 @@ void ugsm_destroy(ugsm_ctx *ctx)
             if (e) (void)hipEventDestroy(e);
         if (s.Apyr) (void)hipFree(s.Apyr);
         if (s.lr) (void)hipFree(s.lr);
+        if (s.cloud_cnt) (void)hipFree(s.cloud_cnt);
         if (s.lr_host) (void)hipHostFree(s.lr_host);
         if (s.st2 && s.owns_st2) (void)hipStreamDestroy(s.st2);
         if (s.st && s.owns_st) (void)hipStreamDestroy(s.st);
@@ -2310,6 +2313,127 @@ int ugsm_triangulate_fovea(ugsm_ctx *ctx, int slot, const float *d_stackx, const
     }
     HIPCHK(ctx, hipGetLastError());
     return UGSM_OK;
+}
+
+// ---- row f-1, the coloured point cloud (getPointCloud.cpp doReconstructionRGB[_FOV], :615-722) ----------------------------------------
+
+void ugsm_default_cloud_params(ugsm_cloud_params *p)
+{
+    if (!p) return;
+    p->sampling = 1;
+    p->format = UGSM_CLOUD_PCL32;
+    p->compact = 0;
+    p->min_conf = -INFINITY;
+    p->z_min = -INFINITY;
+    p->z_max = INFINITY;
+}
+
+long long ugsm_cloud_points(int W, int H, int sampling)
+{
+    if (W < 1 || H < 1 || sampling < 1) return -1;
+    return (long long)((W + sampling - 1) / sampling) * ((H + sampling - 1) / sampling);
+}
+
+namespace {
+
+// the checks both entry points share (no device needed); pw x ph: the planes the points come from
+int cloud_args_ok(const float *dx, const float *dy, const float *conf, const uint8_t *rgb, int W, int H, int stride, int pw, int ph,
+                  const double *P1, const double *P2, const ugsm_cloud_params *p, const void *points, long long cap, const long long *count)
+{
+    if (!dx || !dy || !rgb || !P1 || !P2 || !p || !points || !count) return UGSM_ERR_BAD_ARG;
+    if (W < 1 || H < 1 || pw < 1 || ph < 1 || (long long)W * H > kMaxPixels || (long long)pw * ph > kMaxPixels) return UGSM_ERR_BAD_ARG;
+    if ((long long)stride < 3LL * W || p->sampling < 1 || (p->format != UGSM_CLOUD_PCL32 && p->format != UGSM_CLOUD_XYZRGB16)) return UGSM_ERR_BAD_ARG;
+    if (std::isnan(p->min_conf) || std::isnan(p->z_min) || std::isnan(p->z_max) || p->z_min > p->z_max) return UGSM_ERR_BAD_ARG;
+    if (!conf && p->min_conf > -INFINITY) return UGSM_ERR_BAD_ARG;  // (a confidence test without a confidence plane)
+    if (cap < 0 || ((uintptr_t)points & 15) || ((uintptr_t)count & 7)) return UGSM_ERR_BAD_ARG;
+    return UGSM_OK;
+}
+
+int point_cloud(ugsm_ctx *ctx, int slot, CloudArgs &a, bool fovea, const double *P1, const double *P2)
+{
+    Slot *s;
+    UCHK(get_slot(ctx, slot, &s));
+    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
+    a.wc = (a.pw + a.s - 1) / a.s;
+    a.hc = (a.ph + a.s - 1) / a.s;
+    a.nchunk = cloud_chunks(a.hc);
+    a.cnt = nullptr;
+    if (a.compact) {
+        const size_t totals = (size_t)a.wc + (size_t)cloud_strips(a.wc), need = (size_t)a.wc * a.nchunk + totals;
+        if (need > s->cloud_cap) HIPCHK(ctx, hipStreamSynchronize(s->st));  // (the buffer being replaced may still be read by an earlier cloud)
+        UCHK(grow(ctx, s->cloud_cnt, s->cloud_cap, need));
+        a.cnt = s->cloud_cnt;
+        HIPCHK(ctx, hipMemsetAsync(a.cnt + (size_t)a.wc * a.nchunk, 0, totals * sizeof(unsigned), s->st));
+    }
+    {
+        Timer t(ctx, s, slot, KC_MISC, (double)a.wc * a.hc);
+        launch_point_cloud(s->st, a, fovea, P1, P2);
+    }
+    HIPCHK(ctx, hipGetLastError());
+    return UGSM_OK;
+}
+
+}  // namespace
+
+int ugsm_point_cloud(ugsm_ctx *ctx, int slot, const float *d_dispx, const float *d_dispy, const float *d_conf, const uint8_t *d_rgbL, int W, int H,
+                     int stride, const double *P1, const double *P2, const ugsm_cloud_params *p, void *d_points, long long cap_points,
+                     long long *d_count)
+{
+    if (!ctx) return UGSM_ERR_BAD_ARG;
+    UCHK(cloud_args_ok(d_dispx, d_dispy, d_conf, d_rgbL, W, H, stride, W, H, P1, P2, p, d_points, cap_points, d_count));
+    CloudArgs a{};
+    a.dx = d_dispx;
+    a.dy = d_dispy;
+    a.conf = p->compact ? d_conf : nullptr;
+    a.pw = W;
+    a.ph = H;
+    a.rgb = d_rgbL;
+    a.W = W;
+    a.H = H;
+    a.stride = stride;
+    a.s = p->sampling;
+    a.format = p->format;
+    a.compact = p->compact != 0;
+    a.min_conf = p->min_conf;
+    a.z_min = p->z_min;
+    a.z_max = p->z_max;
+    a.points = d_points;
+    a.cap = cap_points;
+    a.count = d_count;
+    return point_cloud(ctx, slot, a, false, P1, P2);
+}
+
+int ugsm_point_cloud_fovea(ugsm_ctx *ctx, int slot, const float *d_stackx, const float *d_stacky, const float *d_stackc, int fovW, int fovH,
+                           int src_level, int left_margin, int upper_margin, float scale, const uint8_t *d_rgbL, int W, int H, int stride,
+                           const double *P1, const double *P2, const ugsm_cloud_params *p, void *d_points, long long cap_points, long long *d_count)
+{
+    if (!ctx) return UGSM_ERR_BAD_ARG;
+    UCHK(cloud_args_ok(d_stackx, d_stacky, d_stackc, d_rgbL, W, H, stride, fovW, fovH, P1, P2, p, d_points, cap_points, d_count));
+    if (src_level < 0 || src_level >= UGSM_MAX_LEVELS || !std::isfinite(scale)) return UGSM_ERR_BAD_ARG;
+    const size_t lvl = (size_t)src_level * fovW * fovH;  // level src_level of the stacks
+    CloudArgs a{};
+    a.dx = d_stackx + lvl;
+    a.dy = d_stacky + lvl;
+    a.conf = (p->compact && d_stackc) ? d_stackc + lvl : nullptr;
+    a.pw = fovW;
+    a.ph = fovH;
+    a.rgb = d_rgbL;
+    a.W = W;
+    a.H = H;
+    a.stride = stride;
+    a.s = p->sampling;
+    a.format = p->format;
+    a.compact = p->compact != 0;
+    a.min_conf = p->min_conf;
+    a.z_min = p->z_min;
+    a.z_max = p->z_max;
+    a.left_margin = left_margin;
+    a.upper_margin = upper_margin;
+    a.scale = scale;
+    a.points = d_points;
+    a.cap = cap_points;
+    a.count = d_count;
+    return point_cloud(ctx, slot, a, true, P1, P2);
 }
 
 // hierarchicalDisparity, MatchGPULib.cpp:2589-2701
