@@ -78,10 +78,13 @@ typedef struct ugsm_config {
     int slots;
     int kernel_path;
     int profile_events; /* slot 0 times its launches with HIP events carried in the dispatch (the kernel's own begin and end): 1 = the cost kernel only, 2 = every kernel class */
-    int march_min_pixels; /* levels of at least this many pixels run K-cost as the marching kernel (one wave per strip of
-                             columns, no LDS); 0 = default threshold (0.4 Mpx per launch; in effect 3 Mpx: the channel-parallel form
-                             k_cost_march4 takes the levels below first); < 0 = never: round 1's LDS-tiled k_cost_split everywhere --
-                             libugsm_dev.so only since ABI 6 (libugsm.so answers UGSM_ERR_BAD_ARG) */
+    int march_min_pixels; /* at least this many pixels march; levels no other form covers march too.  K-cost as the marching
+                             kernel (one wave per strip of columns, no LDS) for the levels of at least this many pixels per launch,
+                             and for every level that neither k_cost_march4 nor the coarse-level latency form takes (with this
+                             threshold above k_cost_march4's 3 Mpx, say); 0 = default threshold (0.4 Mpx per launch; in effect 3 Mpx:
+                             the channel-parallel form k_cost_march4 takes the levels below first); < 0 = never: round 1's LDS-tiled
+                             k_cost_split takes the levels no other form covers -- libugsm_dev.so only since ABI 6 (libugsm.so
+                             answers UGSM_ERR_BAD_ARG) */
     int march_np;         /* ignored since ABI 3 (kept for layout): the two-pixels-per-lane development form of the marching kernel
                              is no longer in the library (tools/kbench.hip instantiates it) */
     int march_rows;       /* tuning / tests: strip height of the marching kernel (0 = automatic) */
@@ -159,13 +162,14 @@ long long ugsm_pixel_iterations(int W, int H, int levels, int fovea_levels);
  * heights that fill whole rounds of workgroups, the right pyramid and the A planes on a side stream -- an idle neighbour slot's stream,
  * borrowed for the call; a one-stream context has one stream more for it); a call that shares the
  * chip gets every launch doing little redundant work (latency kernels up to 50 k pixels only, on 18 x 18 tiles; one stream).
- * cost_kernel / smooth_kernel: 0 = LDS-tiled (k_smooth_fused; as a cost kernel: k_cost_split, libugsm_dev.so only), 1 = marching
+ * cost_kernel / smooth_kernel: 0 = LDS-tiled (k_smooth_fused; as a cost kernel: k_cost_split, libugsm_dev.so with march_min_pixels < 0 only), 1 = marching
  * (k_cost_march), 2 = coarse-level latency form (k_cost_small / k_smooth_small), 3 = one kernel per reference stage (kernel_path 1),
  * 4 (cost_kernel only) = channel-parallel marching form (k_cost_march4);
  * smooth_rh: region height of k_smooth_small (18, 24 or 32; else 0); strip_rows: rows per strip of the marching K-cost (else 0);
  * seed_fused: 1 if the level's seeding rides on its first K-cost launch; smooth_tile_rows: height of k_smooth_fused's 112-column
  * tile where that tile is used (else 0).  With cfg->batch > 1 the plan is that of a call of cfg->batch pairs (ugsm_submit_*_batch): every
- * threshold is compared with what the LAUNCH holds, pairs_per_launch x the level. */
+ * threshold is compared with what the LAUNCH holds, pairs_per_launch x the level.  A configuration that ugsm_create would refuse (after the
+ * same development overrides) has no plan: UGSM_ERR_BAD_ARG. */
 typedef struct ugsm_level_plan {
     int cost_kernel, smooth_kernel, smooth_rh, strip_rows, seed_fused, smooth_tile_rows, alone;
     int pairs_per_launch;  /* ABI 4: cfg->batch where a call of that many pairs runs this level as one launch for all of them, else 1 */

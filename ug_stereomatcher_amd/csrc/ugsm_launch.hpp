@@ -95,7 +95,8 @@ void launch_weighted_difference(hipStream_t st, const float *newd3, const float 
 
 // ---- libugsm_dev.so only (UGSM_DEV_LIB; csrc/dev/): kernel_path 1 (one kernel per reference stage), round 1's LDS-tiled K-cost
 // (ugsm_config.march_min_pixels < 0) and the probe kernels.  The product build has no-op stand-ins so that the runtime reads the same;
-// ugsm_create refuses the configurations that would reach them and the probe entry points are not compiled in.
+// ugsm_create refuses the configurations that would reach them, the kernel-choice policy gives every other level a shipped K-cost form
+// (run_level answers UGSM_ERR_STATE rather than reach launch_cost_fused here) and the probe entry points are not compiled in.
 #ifdef UGSM_DEV_LIB
 constexpr bool kDevLib = true;
 void launch_blur_decimate_ref(hipStream_t st, const float *src3, int W, int H, float *dst3, int W2, int H2, float sf);

@@ -772,7 +772,7 @@ bool use_march4(const ugsm_ctx *ctx, int W, int H, bool alone, int pairs = 1)
     if (ctx->march4_hi >= 0) return ctx->march4_hi > 0 && px >= ctx->march4_lo && px <= ctx->march4_hi;  // (development override)
     return px > small_max_px(ctx->cfg, alone) && px <= kMarch4MaxPixels;
 }
-bool use_march(const ugsm_ctx *ctx, int W, int H, int pairs = 1)  // (ugsm_config.march_min_pixels moves the threshold: tests run every level through it)
+bool march_by_size(const ugsm_ctx *ctx, int W, int H, int pairs = 1)  // (ugsm_config.march_min_pixels moves the threshold: tests run every level through it)
 {
     const int thr = ctx->cfg.march_min_pixels;
     return thr >= 0 && (long long)W * H * pairs >= (thr > 0 ? thr : kMarchMinPixels);
@@ -785,16 +785,30 @@ int march_rows_arg(const ugsm_ctx *ctx) { return ctx->cfg.march_rows > 0 ? ctx->
 int small_rh(const ugsm_ctx *ctx, int W, int H, bool alone, int pairs = 1)
 {
     const long long px = (long long)W * H * pairs;
-    if (ctx->cfg.small_max_pixels < 0 || ctx->cfg.kernel_path == 1 || px > small_max_px(ctx->cfg, alone) || use_march(ctx, W, H, pairs)) return 0;
+    if (ctx->cfg.small_max_pixels < 0 || ctx->cfg.kernel_path == 1 || px > small_max_px(ctx->cfg, alone) || march_by_size(ctx, W, H, pairs)) return 0;
     if (ctx->small_rh_force) return ctx->small_rh_force;
     return !alone ? 32 : (px <= 36000 ? 18 : (px <= 80000 ? 24 : 32));
+}
+bool use_small_cost(const ugsm_ctx *ctx, int W, int H, bool alone, int pairs = 1)
+{
+    return (ctx->small_mask & 1) && small_rh(ctx, W, H, alone, pairs) != 0;
+}
+// k_cost_march: the levels of at least march_min_pixels per launch, and every level that no other form covers -- it is the one shipped form
+// with no size limit and a batch index.  With the default thresholds the other forms cover every size below kMarch4MaxPixels by
+// themselves; the fallback takes what a configuration leaves uncovered (march_min_pixels above k_cost_march4's reach, small_max_pixels < 0
+// with k_cost_march4 off, the development switches).  Only march_min_pixels < 0 (libugsm_dev.so) leaves such levels to round 1's
+// LDS-tiled k_cost_split.
+bool use_march(const ugsm_ctx *ctx, int W, int H, bool alone, int pairs = 1)
+{
+    if (ctx->cfg.kernel_path == 1 || ctx->cfg.march_min_pixels < 0) return false;
+    return march_by_size(ctx, W, H, pairs) || (!use_march4(ctx, W, H, alone, pairs) && !use_small_cost(ctx, W, H, alone, pairs));
 }
 
 // Seeding (subsampleDisp, MatchGPULib.cpp:1526-1590) rides on the level's first K-cost launch when that is a marching kernel: the seeded field is
 // never written.  Not with the early exit (the field before the first iteration is compared against), not on the one-stage-per-kernel path.
 bool fuse_seed(const ugsm_ctx *ctx, int W, int H, bool alone, int pairs = 1)
 {
-    return ctx->fuse_seed && ctx->cfg.kernel_path != 1 && !(ctx->cfg.early_exit_threshold > 0.0f) && (use_march(ctx, W, H, pairs) || use_march4(ctx, W, H, alone, pairs));
+    return ctx->fuse_seed && ctx->cfg.kernel_path != 1 && !(ctx->cfg.early_exit_threshold > 0.0f) && (use_march(ctx, W, H, alone, pairs) || use_march4(ctx, W, H, alone, pairs));
 }
 
 // k_smooth_fused's tile: > 0 = the 112-column tile at this height -- a call ALONE picks the height that fills whole rounds of workgroups
@@ -908,6 +922,13 @@ int run_level(ugsm_ctx *ctx, Slot &s, int si, const Img3 *Lv, const Img3 *Rv, in
     int ran = 0;
     const int pairs = launch_pairs(ctx, s, W, H);
     const bool batched = pairs > 1;
+    const bool march4 = !ref && use_march4(ctx, W, H, s.alone, pairs);
+    const bool march = !ref && use_march(ctx, W, H, s.alone, pairs);
+    const bool small = !ref && use_small_cost(ctx, W, H, s.alone, pairs);
+    if (!ref && !march4 && !march && !small && !kDevLib) {  // (use_march gives every such level to k_cost_march: launch_cost_fused is a no-op here)
+        ctx->err = "no K-cost kernel of libugsm.so covers this level (kernel-choice policy)";
+        return UGSM_ERR_STATE;
+    }
     const float *const A3 = A_pre ? A_pre : s.A;  // (pair k's A at + k * lvl_stride)
     if (!A_pre) {   // A = G_clamp * L^2 does not depend on the iteration: once per level.
         for_groups(s.nb, batched, [&](Grp g) {
@@ -920,10 +941,7 @@ int run_level(ugsm_ctx *ctx, Slot &s, int si, const Img3 *Lv, const Img3 *Rv, in
             }
         });
     }
-    const bool march4 = !ref && use_march4(ctx, W, H, s.alone, pairs);
-    const bool march = !ref && use_march(ctx, W, H, pairs);
-    const bool small = !ref && (ctx->small_mask & 1) && small_rh(ctx, W, H, s.alone, pairs) != 0;
-    // (k_cost_split, the LDS-tiled form a level falls back to when the marching kernels are switched off, has no batch index: pair by pair)
+    // (k_cost_split -- libugsm_dev.so, march_min_pixels < 0: the levels no other form covers -- has no batch index: pair by pair)
     const bool cost_batched = batched && (march4 || march || small);
     for (int m = m_from; m <= m_to; m++) {
         const int blend = !(is_top && m == 1);  // MatchGPULib.cpp:2223
@@ -1529,6 +1547,19 @@ const char *ugsm_status_string(int st)
     }
 }
 
+// The configurations a context can have, asked after the development overrides (apply_dev_env) by ugsm_create and ugsm_plan_level alike:
+// no plan is reported for a configuration that no context can be created with.
+static int check_config(const ugsm_config &cfg)
+{
+    if (cfg.levels < 1 || cfg.levels > UGSM_MAX_LEVELS || cfg.slots < 1 || cfg.slots > 64 || cfg.kernel_path < 0 ||
+        cfg.kernel_path > 1 || cfg.fovea_levels < 0 || cfg.fovea_levels > cfg.levels || !(cfg.lr_check_threshold >= 0.0f) || cfg.streams < 0 ||
+        cfg.batch < 0 || cfg.batch > UGSM_MAX_BATCH || cfg.stream_priority < 0 || cfg.stream_priority > 3)
+        return UGSM_ERR_BAD_ARG;
+    if (cfg.kernel_path == 1 && !kDevLib) return UGSM_ERR_BAD_ARG;       // the one-kernel-per-stage path lives in libugsm_dev.so
+    if (cfg.march_min_pixels < 0 && !kDevLib) return UGSM_ERR_BAD_ARG;  // ... and so does round 1's LDS-tiled K-cost
+    return UGSM_OK;
+}
+
 int ugsm_create(const ugsm_config *cfg_in, ugsm_ctx **out)
 {
     if (!out) return UGSM_ERR_BAD_ARG;
@@ -1549,12 +1580,7 @@ int ugsm_create(const ugsm_config *cfg_in, ugsm_ctx **out)
         const float g[3] = {lit[0] / sum, lit[1] / sum, lit[2] / sum}, k[3] = {UGSM_G0, UGSM_G1, UGSM_G2};
         if (memcmp(g, k, sizeof g) != 0) return UGSM_ERR_STATE;
     }
-    if (cfg.levels < 1 || cfg.levels > UGSM_MAX_LEVELS || cfg.slots < 1 || cfg.slots > 64 || cfg.kernel_path < 0 ||
-        cfg.kernel_path > 1 || cfg.fovea_levels < 0 || cfg.fovea_levels > cfg.levels || !(cfg.lr_check_threshold >= 0.0f) || cfg.streams < 0 ||
-        cfg.batch < 0 || cfg.batch > UGSM_MAX_BATCH || cfg.stream_priority < 0 || cfg.stream_priority > 3)
-        return UGSM_ERR_BAD_ARG;
-    if (cfg.kernel_path == 1 && !kDevLib) return UGSM_ERR_BAD_ARG;       // the one-kernel-per-stage path lives in libugsm_dev.so
-    if (cfg.march_min_pixels < 0 && !kDevLib) return UGSM_ERR_BAD_ARG;  // ... and so does round 1's LDS-tiled K-cost
+    UCHK(check_config(cfg));
     static_assert(UGSM_MAX_BATCH == kMaxBatch, "include/ugsm.h and ugsm_launch.hpp disagree on the batch size");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return UGSM_ERR_NO_DEVICE;
@@ -1706,6 +1732,7 @@ int ugsm_plan_level(const ugsm_config *cfg_in, int alone, int W, int H, ugsm_lev
         apply_dev_env(probe.cfg, knobs, false);
         set_policy(&probe, knobs);
     }
+    UCHK(check_config(probe.cfg));  // (what ugsm_create refuses has no plan)
     memset(out, 0, sizeof *out);
     if (probe.cfg.kernel_path == 1) {
         out->cost_kernel = out->smooth_kernel = 3;
@@ -1719,9 +1746,9 @@ int ugsm_plan_level(const ugsm_config *cfg_in, int alone, int W, int H, ugsm_lev
     out->alone = al ? 1 : 0;
     const int pairs = (nb > 1 && batch_level(&probe, W, H)) ? nb : 1;
     const bool march4 = use_march4(&probe, W, H, al, pairs);  // (asked first, as in run_level)
-    const bool march = use_march(&probe, W, H, pairs);
+    const bool march = use_march(&probe, W, H, al, pairs);
     const int rh = small_rh(&probe, W, H, al, pairs);
-    out->cost_kernel = march4 ? 4 : (march ? 1 : ((rh && (probe.small_mask & 1)) ? 2 : 0));
+    out->cost_kernel = march4 ? 4 : (march ? 1 : (use_small_cost(&probe, W, H, al, pairs) ? 2 : 0));
     out->smooth_kernel = (rh && (probe.small_mask & 2)) ? 2 : 0;
     out->smooth_rh = (probe.small_mask & 2) ? rh : 0;
     out->strip_rows = march4 ? march4_strip_rows(W, H, pairs)
