@@ -31,7 +31,8 @@ extern "C" {
 #endif
 
 #define UGSM_ABI_VERSION 6  /* 6 (additions, nothing changed): the coloured point cloud -- ugsm_cloud_params, UGSM_CLOUD_PCL32 / UGSM_CLOUD_XYZRGB16,
-                               ugsm_default_cloud_params, ugsm_cloud_points, ugsm_point_cloud, ugsm_point_cloud_fovea
+                               ugsm_default_cloud_params, ugsm_cloud_points, ugsm_point_cloud, ugsm_point_cloud_fovea; the resized cloud --
+                               ugsm_resized_cloud_points, ugsm_point_cloud_resized, ugsm_point_cloud_resized_fovea
                                6: the kernel choices follow what is in flight, not ugsm_config.slots: ugsm_plan_level takes `alone`, ugsm_plan_level_in_frame
                                is gone, ugsm_level_plan.latency_policy is .alone; ugsm_enqueue_* returns UGSM_OK once the pair is accepted (a failed
                                CALL is reported through ugsm_completion.status only); the fovea shard carries a status word (a rank that fails still
@@ -464,6 +465,36 @@ int ugsm_point_cloud_fovea(ugsm_ctx *ctx, int slot, const float *d_stackx, const
                            int fovW, int fovH, int src_level, int left_margin, int upper_margin, float scale,
                            const uint8_t *d_rgbL, int W, int H, int stride, const double *P1, const double *P2,
                            const ugsm_cloud_params *p, void *d_points, long long cap_points, long long *d_count);
+
+/* Row f-1, the resized cloud: what the node publishes on output_pointcloud_resized, doReconstruction_resized /
+ * doReconstructionFOV_resized (getPointCloud.cpp:724-800, :802-884).  The Z plane resized with cv::resize(..., INTER_CUBIC) to
+ * dw x dh = (int)((float)pw * factor) x (int)((float)ph * factor) (pw x ph: W x H, or fovW x fovH), then one point per pixel (ii, jj)
+ * of the resized map, column ii outer and row jj inner: X, Y are ugsm_triangulate[_fovea]'s at xx = (int)((float)ii / factor),
+ * yy = (int)((float)jj / factor) (IEEE float division), Z the resized map's (ii, jj), the colour the left image's at (xx, yy).
+ * The reference's registration is kept: X, Y sit at (int)(ii / f) while the cubic's centre lies near ii / f + (1 / f - 1) / 2.
+ * INTER_CUBIC on CV_32F is OpenCV's generic path (resizeGeneric_, HResizeCubic / VResizeCubic), restated in float:
+ *   scale = 1. / ((double)dw / pw); fx = (float)((dx + 0.5) * scale - 0.5); sx = floor(fx); fx -= sx  (rows the same with dy);
+ *   A = -0.75f; c0 = ((A*(x+1) - 5*A)*(x+1) + 8*A)*(x+1) - 4*A, c1 = ((A+2)*x - (A+3))*x*x + 1,
+ *   c2 = ((A+2)*(1-x) - (A+3))*(1-x)*(1-x) + 1, c3 = 1.f - c0 - c1 - c2;
+ *   taps sx-1 .. sx+2 and sy-1 .. sy+2 clamped to the plane; each source row S[sx-1]*c0 + S[sx]*c1 + S[sx+1]*c2 + S[sx+2]*c3 left to
+ *   right, from +0.0f on the columns with sx < 1 or sx + 2 >= pw; then ((R0*b0 + R1*b1) + R2*b2) + R3*b3; no fused multiply-add;
+ *   NaN and inf propagate (a zero coefficient times inf is NaN).  When the size does not change (factor 1) cv::resize copies, and Z
+ *   is the pixel's own.  Builds of OpenCV that take IPP or a fused vertical pass may differ in the last bit.
+ * Otherwise as ugsm_point_cloud[_fovea]: asynchronous on `slot`'s stream, the same records, cap_points and *d_count, and compaction
+ * (finite X, Y and resized Z, z_min <= Z <= z_max, conf(xx, yy) >= min_conf).  UGSM_ERR_BAD_ARG as there, and also: p->sampling other
+ * than 1 (the resized cloud has none), a factor that is not finite and in (0, 1] or leaves a side 0, colour_mapped not 0 or 1. */
+/* points of the resized cloud: (int)((float)W * factor) * (int)((float)H * factor); -1 when factor is not in (0, 1] or a side truncates to 0 */
+long long ugsm_resized_cloud_points(int W, int H, float factor);
+int ugsm_point_cloud_resized(ugsm_ctx *ctx, int slot, const float *d_dispx, const float *d_dispy, const float *d_conf,
+                             const uint8_t *d_rgbL, int W, int H, int stride, const double *P1, const double *P2, float factor,
+                             const ugsm_cloud_params *p, void *d_points, long long cap_points, long long *d_count);
+/* The foveated form, on level src_level of the stacks.  colour_mapped 0: the colour at (xx, yy) of the W x H image, unmapped -- the
+ * reference's own reading (:864-867), from the image's top-left corner; 1: at the mapped pixel, as ugsm_point_cloud_fovea reads it.
+ * Either is clamped to the image. */
+int ugsm_point_cloud_resized_fovea(ugsm_ctx *ctx, int slot, const float *d_stackx, const float *d_stacky, const float *d_stackc,
+                                   int fovW, int fovH, int src_level, int left_margin, int upper_margin, float scale,
+                                   const uint8_t *d_rgbL, int W, int H, int stride, const double *P1, const double *P2, float factor,
+                                   int colour_mapped, const ugsm_cloud_params *p, void *d_points, long long cap_points, long long *d_count);
 
 /* Row f-3: MatchGPULib::hierarchicalDisparity (MatchGPULib.cpp:2589-2701, kernel MatchLib.cu:435-462):
  * one full-resolution (dx, dy, conf) field from the foveated stacks -- the coarsest fovea level (the whole

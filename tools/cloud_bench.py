@@ -14,6 +14,13 @@ For 16 MP (4928 x 3264) and 1080p, each cloud form (dense PCL32, dense 16-byte, 
   - d2h_ms: the device-to-host copy of the cloud (count x point_step) into page-locked memory, median of wall-clock copies.
 Today's path, per size: ugsm_triangulate (device_ms as above) and the copy of its three float planes to page-locked memory.
 Prints one JSON line per row and writes them all to --out.
+
+    python tools/cloud_bench.py --resized [--out profiles/cloud_resized_bench.json]
+
+The resized cloud (ugsm_point_cloud_resized[_fovea]) instead: per size, today's path as above, then dense PCL32 and compact PCL32
+(min_conf 0.5) at f = 0.2 and 0.5, and at 16 MP the fovea stack's level 0 at f = 0.2 (dense PCL32, the reference's colour).  MB: dx, dy
+read once (8 B per pixel of the planes: every row is touched, by a tap or by yy; the compact form's count launch reads them again, and
+conf once per point), the rgb rows the points read (dh rows of 3 W bytes), count x 32 written.
 """
 import argparse
 import ctypes as C
@@ -78,11 +85,74 @@ def copy_rate_GBps(torch):
     return r
 
 
+def resized_rows(args, emit, copy, p1, p2, dp):
+    from ug_stereomatcher_amd import _lib, synth
+    P1p, P2p = p1.ctypes.data_as(dp), p2.ctypes.data_as(dp)
+
+    def row(c, name, call, pw, ph, W, f, npts, compact, d_pts, d_cnt, h_addr, **extra):
+        t = median_ms(c, call, args.reps, args.warmup)
+        count = int(c.to_host(d_cnt, (1,), np.int64)[0])
+        dh = int(np.float32(ph) * np.float32(f))
+        read = 8 * pw * ph + dh * 3 * W + ((8 * pw * ph + 4 * npts) + 4 * npts if compact else 0)
+        mb = (read + count * 32) / 1e6
+        floor = mb / 1e3 / copy * 1e3
+        t_d2h = host_copy_ms(c, h_addr, d_pts, count * 32, max(5, args.reps // 3)) if count else 0.0
+        emit(dict({"what": name, "factor": f, "points": npts, "count": count, "device_ms": round(t, 4), "MB": round(mb, 1),
+                   "GBps": round(mb / t, 1), "floor_ms": round(floor, 4), "of_floor": round(floor / t, 3), "d2h_MB": round(count * 32 / 1e6, 2),
+                   "d2h_ms": round(t_d2h, 3), "total_ms": round(t + t_d2h, 3)}, **extra))
+
+    for size in args.sizes.split(","):
+        W, H = (int(v) for v in size.split("x"))
+        L, R, _, _ = synth.make_pair(W, H, synth.BASE_SEED + 2)
+        with _lib.Context(levels=14, profile_events=2) as c:
+            pL, pR = c.to_device(L), c.to_device(R)
+            plane = W * H * 4
+            d_out, d_xyz = c.alloc(3 * plane), c.alloc(3 * plane)
+            c.check(c.lib.ugsm_submit_full(c.handle, 0, pL, pR, W, H, L.strides[0], d_out))
+            c.check(c.lib.ugsm_wait(c.handle, 0))
+            d_dx, d_dy, d_conf = d_out, d_out + plane, d_out + 2 * plane
+            cap = _lib.resized_cloud_points(W, H, 0.5)
+            d_pts, d_cnt = c.alloc(cap * 32), c.alloc(8)
+            host = c.host_array((3 * plane,), np.uint8)
+            h_addr = host.ctypes.data
+            # today's path: the X, Y, Z planes, then the three planes to the host (where the resize would run)
+            tri = lambda: c.check(c.lib.ugsm_triangulate(c.handle, 0, d_dx, d_dy, W, H, P1p, P2p, d_xyz))
+            t_tri = median_ms(c, tri, args.reps, args.warmup)
+            t_planes = host_copy_ms(c, h_addr, d_xyz, 3 * plane, max(5, args.reps // 3))
+            mb = (8 + 12) * W * H / 1e6
+            emit({"what": "planes_today", "size": size, "device_ms": round(t_tri, 4), "MB": round(mb, 1), "GBps": round(mb / t_tri, 1),
+                  "d2h_MB": round(3 * plane / 1e6, 1), "d2h_ms": round(t_planes, 3), "total_ms": round(t_tri + t_planes, 3)})
+            for f in (0.2, 0.5):
+                npts = _lib.resized_cloud_points(W, H, f)
+                for name, compact in (("resized_dense_pcl32", False), ("resized_compact_pcl32", True)):
+                    prm = _lib.cloud_params(compact=compact, min_conf=0.5 if compact else None)
+                    call = lambda: c.check(c.lib.ugsm_point_cloud_resized(c.handle, 0, d_dx, d_dy, d_conf, pL, W, H, L.strides[0], P1p, P2p,
+                                                                          C.c_float(f), C.byref(prm), d_pts, npts, d_cnt))
+                    row(c, name, call, W, H, W, f, npts, compact, d_pts, d_cnt, h_addr, size=size)
+            if (W, H) == (4928, 3264):   # the fovea stack's level 0 (ugsm_fovea_mapping's margins)
+                fw, fh = _lib.fovea_dims(W, H, 14, 7)
+                d_stack = c.alloc(3 * 7 * fw * fh * 4)
+                c.check(c.lib.ugsm_submit_foveated(c.handle, 0, pL, pR, W, H, L.strides[0], 0, 0, d_stack, None, None))
+                c.check(c.lib.ugsm_wait(c.handle, 0))
+                lvl = 7 * fw * fh * 4
+                left, upper, scale = _lib.fovea_mapping(W, H, 0)
+                npts = _lib.resized_cloud_points(fw, fh, 0.2)
+                prm = _lib.cloud_params()
+                call = lambda: c.check(c.lib.ugsm_point_cloud_resized_fovea(c.handle, 0, d_stack, d_stack + lvl, d_stack + 2 * lvl, fw, fh, 0,
+                                                                            left, upper, C.c_float(scale), pL, W, H, L.strides[0], P1p, P2p,
+                                                                            C.c_float(0.2), 0, C.byref(prm), d_pts, npts, d_cnt))
+                row(c, "resized_fovea_dense_pcl32", call, fw, fh, fw, 0.2, npts, False, d_pts, d_cnt, h_addr, size=f"{fw}x{fh} level 0")
+                c.free(d_stack)
+            for p in (pL, pR, d_out, d_xyz, d_pts, d_cnt):
+                c.free(p)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=25)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--sizes", default="4928x3264,1920x1080")
+    ap.add_argument("--resized", action="store_true", help="the resized cloud's rows instead")
     ap.add_argument("--out")
     args = ap.parse_args()
     from ug_stereomatcher_amd import _lib, synth
@@ -97,7 +167,12 @@ def main():
     emit({"what": "device_copy", "GBps": round(copy, 1)})
     p1, p2 = (np.ascontiguousarray(m, np.float64).reshape(12) for m in (P1, P2))
     dp = C.POINTER(C.c_double)
-    for size in args.sizes.split(","):
+    if args.resized:
+        resized_rows(args, emit, copy, p1, p2, dp)
+        sizes = []
+    else:
+        sizes = args.sizes.split(",")
+    for size in sizes:
         W, H = (int(v) for v in size.split("x"))
         L, R, _, _ = synth.make_pair(W, H, synth.BASE_SEED + 2)
         with _lib.Context(levels=14, profile_events=2) as c:

@@ -52,6 +52,8 @@ EXPORTS = [
     "ugsm_shard_gather", "ugsm_shard_finalize", "ugsm_context_device_bytes",
     # row f-1: the coloured point cloud
     "ugsm_default_cloud_params", "ugsm_cloud_points", "ugsm_point_cloud", "ugsm_point_cloud_fovea",
+    # ... and the resized cloud
+    "ugsm_resized_cloud_points", "ugsm_point_cloud_resized", "ugsm_point_cloud_resized_fovea",
 ]
 # ... and what include/ugsm_dev.h adds (libugsm_dev.so only)
 DEV_EXPORTS = ["ugsm_stage_poly_probe", "ugsm_stage_div3_probe", "ugsm_stage_div_probe"]
@@ -286,6 +288,11 @@ def load(dev: bool = False):
     lib.ugsm_point_cloud.argtypes = [vp, i, vp, vp, vp, vp, i, i, i, dpp, dpp, C.POINTER(CloudParams), vp, C.c_longlong, vp]
     lib.ugsm_point_cloud_fovea.argtypes = [vp, i, vp, vp, vp, i, i, i, i, i, C.c_float, vp, i, i, i, dpp, dpp, C.POINTER(CloudParams), vp,
                                            C.c_longlong, vp]
+    lib.ugsm_resized_cloud_points.argtypes = [i, i, C.c_float]
+    lib.ugsm_resized_cloud_points.restype = C.c_longlong
+    lib.ugsm_point_cloud_resized.argtypes = [vp, i, vp, vp, vp, vp, i, i, i, dpp, dpp, C.c_float, C.POINTER(CloudParams), vp, C.c_longlong, vp]
+    lib.ugsm_point_cloud_resized_fovea.argtypes = [vp, i, vp, vp, vp, i, i, i, i, i, C.c_float, vp, i, i, i, dpp, dpp, C.c_float, i,
+                                                   C.POINTER(CloudParams), vp, C.c_longlong, vp]
     if bool(lib.ugsm_is_dev_library()) != bool(dev):
         raise UgsmError(UGSM_ERR_STATE, f"{path} is not the {'development' if dev else 'product'} build")
     _libs[dev] = lib
@@ -350,6 +357,11 @@ def cloud_params(sampling: int = 1, format: int = UGSM_CLOUD_PCL32, compact: boo
 def cloud_points(W: int, H: int, sampling: int = 1) -> int:
     """Points of the dense cloud, ceil(W / s) * ceil(H / s); -1 on bad arguments."""
     return int(load().ugsm_cloud_points(W, H, sampling))
+
+
+def resized_cloud_points(W: int, H: int, factor: float) -> int:
+    """Points of the resized cloud, (int)((float)W * f) * (int)((float)H * f) with f a float32; -1 on bad arguments."""
+    return int(load().ugsm_resized_cloud_points(W, H, C.c_float(float(factor))))
 
 
 # ---- context -----------------------------------------------------------------------------
@@ -482,6 +494,34 @@ class Context:
         self.check(self.lib.ugsm_point_cloud_fovea(self._h, slot, d_stackx, d_stacky, d_stackc, fovW, fovH, src_level, left, upper,
                                                    C.c_float(float(scale)), d_rgbL, W, H, stride, p1.ctypes.data_as(dp), p2.ctypes.data_as(dp),
                                                    C.byref(params), d_points, int(cap_points), d_count))
+        self.check(self.lib.ugsm_wait(self._h, slot))
+        return int(self.to_host(d_count, (1,), np.int64)[0])
+
+    def point_cloud_resized(self, d_dispx: int, d_dispy: int, d_conf, d_rgbL: int, W: int, H: int, stride: int, P1, P2, factor: float,
+                            params: CloudParams, d_points: int, cap_points: int, d_count: int, slot: int = 0) -> int:
+        """Row f-1, the resized cloud (getPointCloud.cpp doReconstruction_resized, :724-800): the Z plane cubic-resized by `factor` (a
+        float32), X, Y and colour at ((int)(ii / f), (int)(jj / f)); waits on the slot and returns the cloud's number of points."""
+        p1 = np.ascontiguousarray(P1, np.float64).reshape(12)
+        p2 = np.ascontiguousarray(P2, np.float64).reshape(12)
+        dp = C.POINTER(C.c_double)
+        self.check(self.lib.ugsm_point_cloud_resized(self._h, slot, d_dispx, d_dispy, d_conf, d_rgbL, W, H, stride, p1.ctypes.data_as(dp),
+                                                     p2.ctypes.data_as(dp), C.c_float(float(factor)), C.byref(params), d_points,
+                                                     int(cap_points), d_count))
+        self.check(self.lib.ugsm_wait(self._h, slot))
+        return int(self.to_host(d_count, (1,), np.int64)[0])
+
+    def point_cloud_resized_fovea(self, d_stackx: int, d_stacky: int, d_stackc, fovW: int, fovH: int, src_level: int, left: int, upper: int,
+                                  scale, d_rgbL: int, W: int, H: int, stride: int, P1, P2, factor: float, params: CloudParams, d_points: int,
+                                  cap_points: int, d_count: int, colour_mapped: bool = False, slot: int = 0) -> int:
+        """Row f-1, the resized foveated cloud (doReconstructionFOV_resized, :802-884) of level src_level of the stacks; the colour at the
+        unmapped (xx, yy) as the reference reads it, or at the mapped pixel with colour_mapped.  Waits, returns the count."""
+        p1 = np.ascontiguousarray(P1, np.float64).reshape(12)
+        p2 = np.ascontiguousarray(P2, np.float64).reshape(12)
+        dp = C.POINTER(C.c_double)
+        self.check(self.lib.ugsm_point_cloud_resized_fovea(self._h, slot, d_stackx, d_stacky, d_stackc, fovW, fovH, src_level, left, upper,
+                                                           C.c_float(float(scale)), d_rgbL, W, H, stride, p1.ctypes.data_as(dp),
+                                                           p2.ctypes.data_as(dp), C.c_float(float(factor)), int(bool(colour_mapped)),
+                                                           C.byref(params), d_points, int(cap_points), d_count))
         self.check(self.lib.ugsm_wait(self._h, slot))
         return int(self.to_host(d_count, (1,), np.int64)[0])
 

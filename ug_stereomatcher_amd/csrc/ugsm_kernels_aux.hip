@@ -169,9 +169,10 @@ __device__ __forceinline__ void tri_point(float x1, float y1, float x2, float y2
     Z = ZUp / divisor;
 }
 
-// The forms of k_triangulate / k_triangulate_fovea (template parameter): the X, Y, Z planes, and the two launches of the point cloud
-// (below).  The plane form keeps its own parameter list, so its code is what it was before the cloud forms came.
-enum TriForm : int { kTriPlanes = 0, kTriCloudCount = 1, kTriCloud = 2 };
+// The forms of k_triangulate / k_triangulate_fovea (template parameter): the X, Y, Z planes, the two launches of the point cloud and
+// the two of the resized cloud (below).  The plane form keeps its own parameter list, so its code is what it was before the cloud forms
+// came.
+enum TriForm : int { kTriPlanes = 0, kTriCloudCount = 1, kTriCloud = 2, kTriResizedCount = 3, kTriResized = 4 };
 
 template <int Form>
 __global__ __launch_bounds__(256) void k_triangulate(const float *__restrict__ dispx, const float *__restrict__ dispy, int W, int H, Proj P1q, Proj P2q,
@@ -264,6 +265,54 @@ constexpr int kCloudTC = 32;             // sampled columns per tile
 constexpr int kCloudTR = 64;             // sampled rows per tile = lanes of a wave (phase B)
 constexpr int kCloudPad = kCloudTR + 1;  // records per column in LDS: column c starts 4c banks further on (phase A stores 32 columns at once)
 
+// X, Y, Z of pixel (ii, jj) of the planes, from the same operands as the plane forms (bit-identical to them); (x1, y1) the pixel in the
+// full-resolution frame.  The resized forms' producer.  (cloud_point below keeps its own statement of the same operands: routed through
+// this function, the point cloud forms compile to different instruction streams, and tools/isa_dump.py --diff holds them unchanged.)
+template <bool Fovea>
+__device__ __forceinline__ void tri_at(const CloudArgs &a, const Proj &P1q, const Proj &P2q, int ii, int jj, float &x1, float &y1, float &X,
+                                       float &Y, float &Z)
+{
+    const size_t at = (size_t)jj * a.pw + ii;
+    float x2, y2;
+    if (Fovea) {  // as k_triangulate_fovea
+        x1 = (float)a.left_margin + (float)ii * a.scale;
+        y1 = (float)a.upper_margin + (float)jj * a.scale;
+        const int sx = (int)(ii + a.dx[at]);
+        const int sy = (int)(jj + a.dy[at]);
+        x2 = (float)a.left_margin + (float)sx * a.scale;
+        y2 = (float)a.upper_margin + (float)sy * a.scale;
+    } else {      // as k_triangulate
+        x1 = ii;
+        y1 = jj;
+        x2 = ii + a.dx[at];
+        y2 = jj + a.dy[at];
+    }
+    tri_point(x1, y1, x2, y2, P1q.m, P2q.m, X, Y, Z);
+}
+
+// the colour word of full-resolution pixel (cx, cy); the foveated forms clamp it to the image (the reference reads whatever lies there):
+// at destination level 0 no fovea level's window leaves the image at 16 MP, 1080p, 640 x 480 or 160 x 120, so the clamp only acts on
+// margins a caller pushes past the edge
+template <bool Clamp>
+__device__ __forceinline__ unsigned colour_at(const CloudArgs &a, int cx, int cy)
+{
+    if (Clamp) {
+        cx = min(max(cx, 0), a.W - 1);
+        cy = min(max(cy, 0), a.H - 1);
+    }
+    const uint8_t *p = a.rgb + (size_t)cy * a.stride + 3 * (size_t)cx;
+    return (unsigned)p[0] << 16 | (unsigned)p[1] << 8 | (unsigned)p[2];
+}
+
+// whether a compact cloud keeps a point of pixel `at` of the planes
+__device__ __forceinline__ bool cloud_keep(const CloudArgs &a, size_t at, float X, float Y, float Z)
+{
+    if (!a.compact) return true;
+    bool keep = __builtin_isfinite(X) && __builtin_isfinite(Y) && __builtin_isfinite(Z) && Z >= a.z_min && Z <= a.z_max;
+    if (a.conf) keep = keep && a.conf[at] >= a.min_conf;  // (a NaN confidence fails the comparison)
+    return keep;
+}
+
 // one sampled point: its record (x, y, z, rgb word as float bits) and whether a compact cloud keeps it
 template <bool Fovea, bool Colour>
 __device__ __forceinline__ bool cloud_point(const CloudArgs &a, const Proj &P1q, const Proj &P2q, int ii, int jj, float4 &rec)
@@ -303,8 +352,74 @@ __device__ __forceinline__ bool cloud_point(const CloudArgs &a, const Proj &P1q,
     return keep;
 }
 
+// SURVEY 8f row f-1, the resized cloud: getPointCloud.cpp doReconstruction_resized (:724-800) / doReconstructionFOV_resized (:802-884),
+// cv::resize(range_map, res, Size(pw * f, ph * f), 0, 0, INTER_CUBIC) of the Z plane, then one point per pixel (ii, jj) of the resized
+// map, in the same column-major order.  The Z plane is never written: each point evaluates the 16 Z of its 4 x 4 footprint with tri_at
+// (the plane form's Z, bit for bit) and resizes them in OpenCV's float order (resizeGeneric_ with HResizeCubic / VResizeCubic on CV_32F):
+//   taps   fx = (float)((dx + 0.5) * scale_x - 0.5) with scale_x = 1. / ((double)dw / pw) in double, sx = floor(fx), fx -= sx in float;
+//          columns sx-1 .. sx+2 and rows sy-1 .. sy+2 clamped to the plane (replicate border);
+//   coeffs interpolateCubic, A = -0.75f, in float; c3 = 1 - c0 - c1 - c2;
+//   sums   each source row ((S0*c0 + S1*c1) + S2*c2) + S3*c3 left to right, from +0.0f on the border columns (sx < 1 or sx + 2 >= pw:
+//          HResizeCubic's clamped loop accumulates from 0, which only turns a -0.0f sum into +0.0f); then ((R0*b0 + R1*b1) + R2*b2) + R3*b3;
+//          every product rounded on its own (the library builds with -ffp-contract=off).  NaN and inf propagate (0 * inf is NaN).
+//   same   cv::resize copies the plane when the size does not change (factor 1), so there Z is the pixel's own Z.
+// X, Y are get3DPoint's at xx = (int)((float)ii / f), yy = (int)((float)jj / f) (IEEE float division) -- the reference's registration:
+// the cubic's centre lies near ii / f + (1 / f - 1) / 2, two pixels further on at f = 0.2, and it is kept.  The colour is the left
+// image's at (xx, yy); the foveated form reads it there too, in the full image's top-left corner (:864-867), unless colour_mapped asks
+// for the mapped pixel as ugsm_point_cloud_fovea reads it.  A compact cloud tests X, Y, the resized Z and conf(xx, yy).
+__device__ __forceinline__ void cubic_tap(int d, double scale, int n, int &s, float c[4], bool &border)
+{
+    float f = (float)((d + 0.5) * scale - 0.5);
+    s = (int)floorf(f);
+    f -= (float)s;
+    const float A = -0.75f;
+    c[0] = ((A * (f + 1) - 5 * A) * (f + 1) + 8 * A) * (f + 1) - 4 * A;
+    c[1] = ((A + 2) * f - (A + 3)) * f * f + 1;
+    c[2] = ((A + 2) * (1 - f) - (A + 3)) * (1 - f) * (1 - f) + 1;
+    c[3] = 1.f - c[0] - c[1] - c[2];
+    border = s < 1 || s + 2 >= n;
+}
+
+template <bool Fovea, bool Colour>
+__device__ __forceinline__ bool resized_point(const CloudArgs &a, const CloudResize &rz, const Proj &P1q, const Proj &P2q, int ii, int jj,
+                                              float4 &rec)
+{
+    // (ii < (int)(pw * f) keeps ii / f below pw; the clamp never acts)
+    const int xx = min((int)((float)ii / rz.factor), a.pw - 1);
+    const int yy = min((int)((float)jj / rz.factor), a.ph - 1);
+    float x1, y1, X, Y, Z;
+    tri_at<Fovea>(a, P1q, P2q, xx, yy, x1, y1, X, Y, Z);
+    if (!rz.same_size) {
+        int sx, sy;
+        float cx[4], cy[4];
+        bool border, unused;
+        cubic_tap(ii, rz.scale_x, a.pw, sx, cx, border);
+        cubic_tap(jj, rz.scale_y, a.ph, sy, cy, unused);
+        float v = 0.0f;
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+            const int ty = min(max(sy - 1 + r, 0), a.ph - 1);
+            float s[4];
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                float u1, u2, u3, u4;
+                tri_at<Fovea>(a, P1q, P2q, min(max(sx - 1 + k, 0), a.pw - 1), ty, u1, u2, u3, u4, s[k]);
+            }
+            const float p0 = s[0] * cx[0];
+            const float h = (((border ? 0.0f + p0 : p0) + s[1] * cx[1]) + s[2] * cx[2]) + s[3] * cx[3];
+            v = r == 0 ? h * cy[0] : v + h * cy[r];
+        }
+        Z = v;
+    }
+    if (Colour) {
+        const bool mapped = Fovea && rz.colour_mapped;
+        rec = make_float4(X, Y, Z, __uint_as_float(mapped ? colour_at<Fovea>(a, (int)x1, (int)y1) : colour_at<Fovea>(a, xx, yy)));
+    }
+    return cloud_keep(a, (size_t)yy * a.pw + xx, X, Y, Z);
+}
+
 template <bool Fovea, int Form>
-__device__ __forceinline__ void cloud_tile(const CloudArgs &a, const Proj &P1q, const Proj &P2q)
+__device__ __forceinline__ void cloud_tile(const CloudArgs &a, const CloudResize &rz, const Proj &P1q, const Proj &P2q)
 {
     __shared__ float4 rec[kCloudTC * kCloudPad];
     __shared__ unsigned char kept[kCloudTC * kCloudTR];
@@ -315,20 +430,24 @@ __device__ __forceinline__ void cloud_tile(const CloudArgs &a, const Proj &P1q, 
     const int c0 = tx * kCloudTC, r0 = ty * kCloudTR;
     const int c = t & (kCloudTC - 1), ci = c0 + c;
     unsigned *const col_tot = a.cnt + (size_t)a.wc * a.nchunk, *const strip_tot = col_tot + a.wc;  // (compact only)
-    if (Form == kTriCloud && a.compact && t <= kCloudTC) pre[t] = 0;
+    constexpr bool Write = Form == kTriCloud || Form == kTriResized, Count = !Write;  // the cloud launch / the count launch
+    if (Write && a.compact && t <= kCloudTC) pre[t] = 0;
     // A: evaluate the tile
     for (int r = t / kCloudTC; r < kCloudTR; r += 256 / kCloudTC) {
         const int cj = r0 + r;
         bool k = false;
         if (ci < a.wc && cj < a.hc) {
             float4 v;
-            k = cloud_point<Fovea, Form == kTriCloud>(a, P1q, P2q, ci * a.s, cj * a.s, v);
-            if (Form == kTriCloud) rec[c * kCloudPad + r] = v;
+            if constexpr (Form == kTriResizedCount || Form == kTriResized)
+                k = resized_point<Fovea, Write>(a, rz, P1q, P2q, ci, cj, v);
+            else
+                k = cloud_point<Fovea, Write>(a, P1q, P2q, ci * a.s, cj * a.s, v);
+            if (Write) rec[c * kCloudPad + r] = v;
         }
         kept[c * kCloudTR + r] = k;
     }
     __syncthreads();
-    if (Form == kTriCloud && a.compact) {  // the runs' offsets: integer sums of the count launch's results
+    if (Write && a.compact) {  // the runs' offsets: integer sums of the count launch's results
         unsigned v = 0, w = 0;
         for (int k = t; k < tx; k += 256) v += strip_tot[k];               // strips to the left
         if (ci < a.wc) {
@@ -343,11 +462,11 @@ __device__ __forceinline__ void cloud_tile(const CloudArgs &a, const Proj &P1q, 
     for (int cc = t >> 6; cc < kCloudTC; cc += 4) {
         const bool k = kept[cc * kCloudTR + lane] != 0;
         const unsigned long long m = __builtin_amdgcn_ballot_w64(k);
-        if (Form == kTriCloud && k) src[cc * kCloudTR + __builtin_popcountll(m & ((1ull << lane) - 1))] = (unsigned char)lane;
+        if (Write && k) src[cc * kCloudTR + __builtin_popcountll(m & ((1ull << lane) - 1))] = (unsigned char)lane;
         if (lane == 0) {
             const int n = __builtin_popcountll(m);
             nrec[cc] = n;
-            if (Form == kTriCloudCount && c0 + cc < a.wc) {
+            if (Count && c0 + cc < a.wc) {
                 a.cnt[(size_t)(c0 + cc) * a.nchunk + ty] = (unsigned)n;
                 if (n) {
                     atomicAdd(&col_tot[c0 + cc], (unsigned)n);
@@ -356,7 +475,7 @@ __device__ __forceinline__ void cloud_tile(const CloudArgs &a, const Proj &P1q, 
             }
         }
     }
-    if (Form == kTriCloudCount) return;
+    if (Count) return;
     __syncthreads();
     // the cloud's size: one workgroup writes it
     if (t == 0 && ty == 0 && tx == (a.compact ? (int)gridDim.x - 1 : 0))
@@ -388,23 +507,44 @@ template <int Form>
 __global__ __launch_bounds__(256) void k_triangulate(CloudArgs a, Proj P1q, Proj P2q)
 {
     static_assert(Form == kTriCloudCount || Form == kTriCloud, "the cloud forms");
-    cloud_tile<false, Form>(a, P1q, P2q);
+    cloud_tile<false, Form>(a, CloudResize{}, P1q, P2q);
 }
 template <int Form>
 __global__ __launch_bounds__(256) void k_triangulate_fovea(CloudArgs a, Proj P1q, Proj P2q)
 {
     static_assert(Form == kTriCloudCount || Form == kTriCloud, "the cloud forms");
-    cloud_tile<true, Form>(a, P1q, P2q);
+    cloud_tile<true, Form>(a, CloudResize{}, P1q, P2q);
+}
+// (the resized forms take their own argument after the others, so that the cloud forms' arguments lie where they did)
+template <int Form>
+__global__ __launch_bounds__(256) void k_triangulate(CloudArgs a, Proj P1q, Proj P2q, CloudResize rz)
+{
+    static_assert(Form == kTriResizedCount || Form == kTriResized, "the resized cloud forms");
+    cloud_tile<false, Form>(a, rz, P1q, P2q);
+}
+template <int Form>
+__global__ __launch_bounds__(256) void k_triangulate_fovea(CloudArgs a, Proj P1q, Proj P2q, CloudResize rz)
+{
+    static_assert(Form == kTriResizedCount || Form == kTriResized, "the resized cloud forms");
+    cloud_tile<true, Form>(a, rz, P1q, P2q);
 }
 
 int cloud_strips(int wc) { return (wc + kCloudTC - 1) / kCloudTC; }
 int cloud_chunks(int hc) { return (hc + kCloudTR - 1) / kCloudTR; }
 
-void launch_point_cloud(hipStream_t st, const CloudArgs &args, bool fovea, const double *P1, const double *P2)
+void launch_point_cloud(hipStream_t st, const CloudArgs &args, bool fovea, const double *P1, const double *P2, const CloudResize *rz)
 {
     Proj a, b;
     for (int k = 0; k < 12; k++) { a.m[k] = P1[k]; b.m[k] = P2[k]; }
     const dim3 grid(cloud_strips(args.wc), args.nchunk);
+    if (rz) {
+        using Kern = void (*)(CloudArgs, Proj, Proj, CloudResize);
+        const Kern count = fovea ? (Kern)k_triangulate_fovea<kTriResizedCount> : (Kern)k_triangulate<kTriResizedCount>;
+        const Kern cloud = fovea ? (Kern)k_triangulate_fovea<kTriResized> : (Kern)k_triangulate<kTriResized>;
+        if (args.compact) UGSM_LAUNCH(count, grid, dim3(256), 0, st, args, a, b, *rz);
+        UGSM_LAUNCH(cloud, grid, dim3(256), 0, st, args, a, b, *rz);
+        return;
+    }
     using Kern = void (*)(CloudArgs, Proj, Proj);
     const Kern count = fovea ? (Kern)k_triangulate_fovea<kTriCloudCount> : (Kern)k_triangulate<kTriCloudCount>;
     const Kern cloud = fovea ? (Kern)k_triangulate_fovea<kTriCloud> : (Kern)k_triangulate<kTriCloud>;

@@ -84,10 +84,18 @@ struct CloudArgs {
     long long cap;
     long long *count;
 };
+// the resized cloud (ugsm_point_cloud_resized[_fovea]): the forms kTriResizedCount / kTriResized, whose grid is the resized map
+// (CloudArgs.wc x hc = (int)(pw * factor) x (int)(ph * factor), s 1): point (ci, cj) = pixel (ci, cj) of it
+struct CloudResize {
+    double scale_x, scale_y;  // cv::resize's 1. / ((double)wc / pw), 1. / ((double)hc / ph)
+    float factor;
+    int same_size;            // wc == pw && hc == ph: cv::resize copies, Z is the pixel's own
+    int colour_mapped;        // the fovea form: the colour at the mapped pixel (as ugsm_point_cloud_fovea) rather than at (xx, yy)
+};
 int cloud_strips(int wc);
 int cloud_chunks(int hc);
-// compact: a count launch, then the cloud launch; dense: the cloud launch
-void launch_point_cloud(hipStream_t st, const CloudArgs &args, bool fovea, const double *P1, const double *P2);
+// compact: a count launch, then the cloud launch; dense: the cloud launch.  rz: the resized forms
+void launch_point_cloud(hipStream_t st, const CloudArgs &args, bool fovea, const double *P1, const double *P2, const CloudResize *rz = nullptr);
 void launch_upsample_paste(hipStream_t st, const float *src3, int W, int H, float *dst3, int W2, int H2, const float *fovH_, const float *fovV_,
                            const float *fovC_, int fovW, int fovH, int org_x, int org_y);
 // S_dx, S_dy, C of weightedDifference (MatchGPULib.cpp:1336-1437) into out3; rowsum = 3*H doubles of scratch

@@ -2361,11 +2361,21 @@ long long ugsm_cloud_points(int W, int H, int sampling)
     return (long long)((W + sampling - 1) / sampling) * ((H + sampling - 1) / sampling);
 }
 
+long long ugsm_resized_cloud_points(int W, int H, float factor)
+{
+    if (W < 1 || H < 1 || !(factor > 0.0f && factor <= 1.0f)) return -1;
+    const int dw = (int)((float)W * factor), dh = (int)((float)H * factor);  // cv::Size(W * f, H * f): float products, truncated
+    if (dw < 1 || dh < 1) return -1;
+    return (long long)dw * dh;
+}
+
 namespace {
 
-// the checks both entry points share (no device needed); pw x ph: the planes the points come from
+// the checks every entry point shares (no device needed); pw x ph: the planes the points come from; resized: the resized forms, which
+// take no sampling (p->sampling 1) and a factor in (0, 1] that leaves both sides at least 1
 int cloud_args_ok(const float *dx, const float *dy, const float *conf, const uint8_t *rgb, int W, int H, int stride, int pw, int ph,
-                  const double *P1, const double *P2, const ugsm_cloud_params *p, const void *points, long long cap, const long long *count)
+                  const double *P1, const double *P2, const ugsm_cloud_params *p, const void *points, long long cap, const long long *count,
+                  bool resized = false, float factor = 1.0f)
 {
     if (!dx || !dy || !rgb || !P1 || !P2 || !p || !points || !count) return UGSM_ERR_BAD_ARG;
     if (W < 1 || H < 1 || pw < 1 || ph < 1 || (long long)W * H > kMaxPixels || (long long)pw * ph > kMaxPixels) return UGSM_ERR_BAD_ARG;
@@ -2373,16 +2383,60 @@ int cloud_args_ok(const float *dx, const float *dy, const float *conf, const uin
     if (std::isnan(p->min_conf) || std::isnan(p->z_min) || std::isnan(p->z_max) || p->z_min > p->z_max) return UGSM_ERR_BAD_ARG;
     if (!conf && p->min_conf > -INFINITY) return UGSM_ERR_BAD_ARG;  // (a confidence test without a confidence plane)
     if (cap < 0 || ((uintptr_t)points & 15) || ((uintptr_t)count & 7)) return UGSM_ERR_BAD_ARG;
+    if (resized && (p->sampling != 1 || ugsm_resized_cloud_points(pw, ph, factor) < 1)) return UGSM_ERR_BAD_ARG;
     return UGSM_OK;
 }
 
-int point_cloud(ugsm_ctx *ctx, int slot, CloudArgs &a, bool fovea, const double *P1, const double *P2)
+// the CloudArgs of a call whose points come from the pw x ph planes dx, dy, conf (conf is only read by a compact cloud)
+CloudArgs cloud_args(const float *dx, const float *dy, const float *conf, const uint8_t *rgb, int W, int H, int stride, int pw, int ph,
+                     const ugsm_cloud_params *p, void *points, long long cap, long long *count)
+{
+    CloudArgs a{};
+    a.dx = dx;
+    a.dy = dy;
+    a.conf = p->compact ? conf : nullptr;
+    a.pw = pw;
+    a.ph = ph;
+    a.rgb = rgb;
+    a.W = W;
+    a.H = H;
+    a.stride = stride;
+    a.s = p->sampling;
+    a.format = p->format;
+    a.compact = p->compact != 0;
+    a.min_conf = p->min_conf;
+    a.z_min = p->z_min;
+    a.z_max = p->z_max;
+    a.points = points;
+    a.cap = cap;
+    a.count = count;
+    return a;
+}
+
+// the resized map: (int)(pw * factor) x (int)(ph * factor) points and cv::resize's scales (resize.cpp: inv_scale = (double)dsize / ssize,
+// scale = 1. / inv_scale)
+CloudResize resize_args(CloudArgs &a, float factor, int colour_mapped)
+{
+    a.wc = (int)((float)a.pw * factor);
+    a.hc = (int)((float)a.ph * factor);
+    CloudResize rz{};
+    rz.scale_x = 1. / ((double)a.wc / a.pw);
+    rz.scale_y = 1. / ((double)a.hc / a.ph);
+    rz.factor = factor;
+    rz.same_size = a.wc == a.pw && a.hc == a.ph;
+    rz.colour_mapped = colour_mapped;
+    return rz;
+}
+
+int point_cloud(ugsm_ctx *ctx, int slot, CloudArgs &a, bool fovea, const double *P1, const double *P2, const CloudResize *rz = nullptr)
 {
     Slot *s;
     UCHK(get_slot(ctx, slot, &s));
     HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
-    a.wc = (a.pw + a.s - 1) / a.s;
-    a.hc = (a.ph + a.s - 1) / a.s;
+    if (!rz) {  // (the resized forms' grid is resize_args')
+        a.wc = (a.pw + a.s - 1) / a.s;
+        a.hc = (a.ph + a.s - 1) / a.s;
+    }
     a.nchunk = cloud_chunks(a.hc);
     a.cnt = nullptr;
     if (a.compact) {
@@ -2394,9 +2448,23 @@ int point_cloud(ugsm_ctx *ctx, int slot, CloudArgs &a, bool fovea, const double 
     }
     {
         Timer t(ctx, s, slot, KC_MISC, (double)a.wc * a.hc);
-        launch_point_cloud(s->st, a, fovea, P1, P2);
+        launch_point_cloud(s->st, a, fovea, P1, P2, rz);
     }
     HIPCHK(ctx, hipGetLastError());
+    return UGSM_OK;
+}
+
+// the foveated forms' planes (level src_level of the stacks) and mapping (ugsm_fovea_mapping)
+int fovea_cloud_args(CloudArgs &a, const float *stackx, const float *stacky, const float *stackc, int fovW, int fovH, int src_level,
+                     int left_margin, int upper_margin, float scale, const uint8_t *rgb, int W, int H, int stride, const ugsm_cloud_params *p,
+                     void *points, long long cap, long long *count)
+{
+    if (src_level < 0 || src_level >= UGSM_MAX_LEVELS || !std::isfinite(scale)) return UGSM_ERR_BAD_ARG;
+    const size_t lvl = (size_t)src_level * fovW * fovH;
+    a = cloud_args(stackx + lvl, stacky + lvl, stackc ? stackc + lvl : nullptr, rgb, W, H, stride, fovW, fovH, p, points, cap, count);
+    a.left_margin = left_margin;
+    a.upper_margin = upper_margin;
+    a.scale = scale;
     return UGSM_OK;
 }
 
@@ -2408,25 +2476,7 @@ int ugsm_point_cloud(ugsm_ctx *ctx, int slot, const float *d_dispx, const float 
 {
     if (!ctx) return UGSM_ERR_BAD_ARG;
     UCHK(cloud_args_ok(d_dispx, d_dispy, d_conf, d_rgbL, W, H, stride, W, H, P1, P2, p, d_points, cap_points, d_count));
-    CloudArgs a{};
-    a.dx = d_dispx;
-    a.dy = d_dispy;
-    a.conf = p->compact ? d_conf : nullptr;
-    a.pw = W;
-    a.ph = H;
-    a.rgb = d_rgbL;
-    a.W = W;
-    a.H = H;
-    a.stride = stride;
-    a.s = p->sampling;
-    a.format = p->format;
-    a.compact = p->compact != 0;
-    a.min_conf = p->min_conf;
-    a.z_min = p->z_min;
-    a.z_max = p->z_max;
-    a.points = d_points;
-    a.cap = cap_points;
-    a.count = d_count;
+    CloudArgs a = cloud_args(d_dispx, d_dispy, d_conf, d_rgbL, W, H, stride, W, H, p, d_points, cap_points, d_count);
     return point_cloud(ctx, slot, a, false, P1, P2);
 }
 
@@ -2436,31 +2486,38 @@ int ugsm_point_cloud_fovea(ugsm_ctx *ctx, int slot, const float *d_stackx, const
 {
     if (!ctx) return UGSM_ERR_BAD_ARG;
     UCHK(cloud_args_ok(d_stackx, d_stacky, d_stackc, d_rgbL, W, H, stride, fovW, fovH, P1, P2, p, d_points, cap_points, d_count));
-    if (src_level < 0 || src_level >= UGSM_MAX_LEVELS || !std::isfinite(scale)) return UGSM_ERR_BAD_ARG;
-    const size_t lvl = (size_t)src_level * fovW * fovH;  // level src_level of the stacks
-    CloudArgs a{};
-    a.dx = d_stackx + lvl;
-    a.dy = d_stacky + lvl;
-    a.conf = (p->compact && d_stackc) ? d_stackc + lvl : nullptr;
-    a.pw = fovW;
-    a.ph = fovH;
-    a.rgb = d_rgbL;
-    a.W = W;
-    a.H = H;
-    a.stride = stride;
-    a.s = p->sampling;
-    a.format = p->format;
-    a.compact = p->compact != 0;
-    a.min_conf = p->min_conf;
-    a.z_min = p->z_min;
-    a.z_max = p->z_max;
-    a.left_margin = left_margin;
-    a.upper_margin = upper_margin;
-    a.scale = scale;
-    a.points = d_points;
-    a.cap = cap_points;
-    a.count = d_count;
+    CloudArgs a;
+    UCHK(fovea_cloud_args(a, d_stackx, d_stacky, d_stackc, fovW, fovH, src_level, left_margin, upper_margin, scale, d_rgbL, W, H, stride, p,
+                          d_points, cap_points, d_count));
     return point_cloud(ctx, slot, a, true, P1, P2);
+}
+
+// ---- row f-1, the resized cloud (getPointCloud.cpp doReconstruction_resized / doReconstructionFOV_resized, :724-884) ----------------
+
+int ugsm_point_cloud_resized(ugsm_ctx *ctx, int slot, const float *d_dispx, const float *d_dispy, const float *d_conf, const uint8_t *d_rgbL,
+                             int W, int H, int stride, const double *P1, const double *P2, float factor, const ugsm_cloud_params *p,
+                             void *d_points, long long cap_points, long long *d_count)
+{
+    if (!ctx) return UGSM_ERR_BAD_ARG;
+    UCHK(cloud_args_ok(d_dispx, d_dispy, d_conf, d_rgbL, W, H, stride, W, H, P1, P2, p, d_points, cap_points, d_count, true, factor));
+    CloudArgs a = cloud_args(d_dispx, d_dispy, d_conf, d_rgbL, W, H, stride, W, H, p, d_points, cap_points, d_count);
+    const CloudResize rz = resize_args(a, factor, 0);
+    return point_cloud(ctx, slot, a, false, P1, P2, &rz);
+}
+
+int ugsm_point_cloud_resized_fovea(ugsm_ctx *ctx, int slot, const float *d_stackx, const float *d_stacky, const float *d_stackc, int fovW,
+                                   int fovH, int src_level, int left_margin, int upper_margin, float scale, const uint8_t *d_rgbL, int W, int H,
+                                   int stride, const double *P1, const double *P2, float factor, int colour_mapped, const ugsm_cloud_params *p,
+                                   void *d_points, long long cap_points, long long *d_count)
+{
+    if (!ctx) return UGSM_ERR_BAD_ARG;
+    UCHK(cloud_args_ok(d_stackx, d_stacky, d_stackc, d_rgbL, W, H, stride, fovW, fovH, P1, P2, p, d_points, cap_points, d_count, true, factor));
+    if (colour_mapped != 0 && colour_mapped != 1) return UGSM_ERR_BAD_ARG;
+    CloudArgs a;
+    UCHK(fovea_cloud_args(a, d_stackx, d_stacky, d_stackc, fovW, fovH, src_level, left_margin, upper_margin, scale, d_rgbL, W, H, stride, p,
+                          d_points, cap_points, d_count));
+    const CloudResize rz = resize_args(a, factor, colour_mapped);
+    return point_cloud(ctx, slot, a, true, P1, P2, &rz);
 }
 
 // hierarchicalDisparity, MatchGPULib.cpp:2589-2701
