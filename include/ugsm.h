@@ -32,7 +32,9 @@ extern "C" {
 
 #define UGSM_ABI_VERSION 6  /* 6 (additions, nothing changed): the coloured point cloud -- ugsm_cloud_params, UGSM_CLOUD_PCL32 / UGSM_CLOUD_XYZRGB16,
                                ugsm_default_cloud_params, ugsm_cloud_points, ugsm_point_cloud, ugsm_point_cloud_fovea; the resized cloud --
-                               ugsm_resized_cloud_points, ugsm_point_cloud_resized, ugsm_point_cloud_resized_fovea
+                               ugsm_resized_cloud_points, ugsm_point_cloud_resized, ugsm_point_cloud_resized_fovea; the input formats --
+                               UGSM_INPUT_*, ugsm_input_bytes_per_pixel, ugsm_input_format_from_encoding, ugsm_set_input_format,
+                               ugsm_get_input_format
                                6: the kernel choices follow what is in flight, not ugsm_config.slots: ugsm_plan_level takes `alone`, ugsm_plan_level_in_frame
                                is gone, ugsm_level_plan.latency_policy is .alone; ugsm_enqueue_* returns UGSM_OK once the pair is accepted (a failed
                                CALL is reported through ugsm_completion.status only); the fovea shard carries a status word (a rank that fails still
@@ -47,7 +49,7 @@ extern "C" {
 /* status codes */
 #define UGSM_OK                0
 #define UGSM_ERR_BAD_ARG       1  /* null pointer, non-positive size, bad slot/level, image above 2^28 pixels */
-#define UGSM_ERR_SIZE_MISMATCH 2  /* left/right differ, or stride < 3*W (ref: unchecked, MatchGPULib.cpp:315-323) */
+#define UGSM_ERR_SIZE_MISMATCH 2  /* left/right differ, or stride < bytes per pixel * W (ref: unchecked, MatchGPULib.cpp:315-323) */
 #define UGSM_ERR_TOO_SMALL     3  /* a pyramid level would be < 1 px (ref: zero-size malloc, MatchGPULib.cpp:1247) */
 #define UGSM_ERR_NO_DEVICE     4  /* no HIP device / HIP runtime unusable */
 #define UGSM_ERR_DEVICE        5  /* a HIP call failed; see ugsm_last_error */
@@ -177,11 +179,41 @@ typedef struct ugsm_level_plan {
 } ugsm_level_plan;
 int ugsm_plan_level(const ugsm_config *cfg, int alone, int W, int H, ugsm_level_plan *out);
 
+/* ---- input formats: the byte layout of the images every entry point below reads ------------------------------------------------
+ *
+ * The node's image topics carry any encoding cv_bridge converts to rgb8 (UG_GPU_matcher.cpp:143-144,513-514); the library reads five of
+ * them as they are.  A call on an image in format F gives, byte for byte, the result of the rgb8 call on that image converted the way
+ * cv_bridge converts it to rgb8 -- disparities, confidence, fovea stacks, the L / R pyramid stacks, triangulated planes and the cloud's
+ * colour word alike:
+ *   UGSM_INPUT_RGB8   3 bytes per pixel, (b0, b1, b2) -- the default; every call made without ugsm_set_input_format reads this
+ *   UGSM_INPUT_BGR8   3 bytes, R, G, B = (b2, b1, b0)
+ *   UGSM_INPUT_RGBA8  4 bytes, (b0, b1, b2), alpha ignored
+ *   UGSM_INPUT_BGRA8  4 bytes, (b2, b1, b0), alpha ignored
+ *   UGSM_INPUT_MONO8  1 byte, (v, v, v)
+ * `stride` stays bytes per row and must be at least ugsm_input_bytes_per_pixel(F) * W (UGSM_ERR_SIZE_MISMATCH otherwise; the cloud
+ * calls answer UGSM_ERR_BAD_ARG, as for rgb8).  Device pointers need no alignment.
+ * The format is a setting of the context that any call may change, and it is CAPTURED WHEN AN IMAGE IS HANDED OVER: by ugsm_match_*,
+ * ugsm_submit_* (the pyramids, the shard), ugsm_stage_pyramid and the cloud calls when they are made, and by ugsm_enqueue_* for the pair
+ * it enqueues -- the library forms the queue's calls later, each with the format its pairs were enqueued in (pairs of different formats
+ * never share a call). */
+#define UGSM_INPUT_RGB8  0
+#define UGSM_INPUT_BGR8  1
+#define UGSM_INPUT_RGBA8 2
+#define UGSM_INPUT_BGRA8 3
+#define UGSM_INPUT_MONO8 4
+/* 3, 3, 4, 4, 1; -1 for an unknown format.  Host only. */
+int ugsm_input_bytes_per_pixel(int format);
+/* The sensor_msgs encoding names "rgb8", "bgr8", "rgba8", "bgra8", "mono8" -> the format; -1 for any other string and for NULL. */
+int ugsm_input_format_from_encoding(const char *encoding);
+/* UGSM_ERR_BAD_ARG for an unknown format (the format is left as it was).  Takes effect for the images handed over afterwards. */
+int ugsm_set_input_format(ugsm_ctx *ctx, int format);
+int ugsm_get_input_format(const ugsm_ctx *ctx, int *format);
+
 /* ---- the service path: host buffers in, host buffers out ------------------------ */
 
 /* MatchGPULib::match(L, R, 0), MatchGPULib.cpp:303-403, as used by
  * GPU_matcher::disparitySrv (UG_GPU_matcher.cpp:645-658) and mainRoutine (:423-442).
- * rgbL/rgbR: rgb8 rows of `stride` bytes (cv::Mat::step, :318).  dispH/dispV/dispC:
+ * rgbL/rgbR: rgb8 rows of `stride` bytes (cv::Mat::step, :318), or the context's input format (ugsm_set_input_format).  dispH/dispV/dispC:
  * caller-allocated H*W float32 planes (the 32FC1 payloads of dispH/dispV/dispC). */
 int ugsm_match_full(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H,
                     int stride, float *dispH, float *dispV, float *dispC);
@@ -432,7 +464,8 @@ int ugsm_triangulate_fovea(ugsm_ctx *ctx, int slot, const float *d_stackx, const
  * Order as the reference's: column ii outer, row jj inner (a COLUMN-major cloud from row-major planes), pixel (ii, jj) sampled when
  * ii % sampling == 0 && jj % sampling == 0; an unorganised cloud (width = count, height = 1).  X, Y, Z are bit for bit what
  * ugsm_triangulate[_fovea] writes for the pixel; rgb = R << 16 | G << 8 | B of the left image (byte0 << 16 | byte1 << 8 | byte2 of
- * the rgb8 buffer), alpha 0. */
+ * the rgb8 buffer; in another input format, of the pixel's conversion to rgb8: the node's BGR8 copy passes as it is, with
+ * UGSM_INPUT_BGR8), alpha 0. */
 #define UGSM_CLOUD_PCL32    0  /* pcl::PointXYZRGB as it lies in memory: x, y, z at 0/4/8, 1.0f at 12, the rgb word at 16, 12 zero bytes; point_step 32 */
 #define UGSM_CLOUD_XYZRGB16 1  /* x, y, z, rgb at 0/4/8/12; point_step 16 (a PointCloud2 with the same four fields) */
 typedef struct ugsm_cloud_params {
@@ -447,12 +480,12 @@ void ugsm_default_cloud_params(ugsm_cloud_params *p);
 /* points of the dense cloud: ceil(W / sampling) * ceil(H / sampling); -1 on bad arguments.  Host only. */
 long long ugsm_cloud_points(int W, int H, int sampling);
 /* The cloud of the full-resolution match.  d_dispx / d_dispy / d_conf: H*W device planes (planes 0, 1, 2 of ugsm_submit_full's d_out;
- * d_conf may be NULL when p->min_conf is -inf); d_rgbL: the left image, rgb8, `stride` bytes per row, on the device; P1, P2 as for
+ * d_conf may be NULL when p->min_conf is -inf); d_rgbL: the left image, rgb8 (or the input format), `stride` bytes per row, on the device; P1, P2 as for
  * ugsm_triangulate (host).  d_points (device, 16-byte aligned) receives the first min(count, cap_points) records and nothing past them;
  * *d_count (device) the cloud's number of points, even where that exceeds cap_points.  Asynchronous on `slot`'s stream, like
  * ugsm_triangulate (ordered after a submit on the same slot).  A compact cloud uses a per-slot count buffer that grows on demand
  * (ugsm_context_device_bytes counts it; UGSM_ERR_NOMEM if it cannot grow) and takes two launches; the output is the same byte for byte
- * from run to run.  UGSM_ERR_BAD_ARG: a null pointer, W or H < 1, stride < 3W, sampling < 1, an unknown format, a NaN min_conf / z_min /
+ * from run to run.  UGSM_ERR_BAD_ARG: a null pointer, W or H < 1, stride < bytes per pixel * W, sampling < 1, an unknown format, a NaN min_conf / z_min /
  * z_max or z_min > z_max, d_conf NULL with min_conf above -inf, cap_points < 0, a misaligned d_points / d_count, above 2^28 pixels. */
 int ugsm_point_cloud(ugsm_ctx *ctx, int slot, const float *d_dispx, const float *d_dispy, const float *d_conf,
                      const uint8_t *d_rgbL, int W, int H, int stride, const double *P1, const double *P2,

@@ -5,7 +5,8 @@
 // this header: same constructor, same method names, same return layouts (malloc'd float** /
 // float***, freed by the caller exactly as the node already does, :414-418,487-489,636-640,689-691).
 // The image argument is templated on "something with ->image.{rows,cols,step,data}", i.e.
-// cv_bridge::CvImagePtr in the node; the header itself needs neither OpenCV nor ROS.
+// cv_bridge::CvImagePtr in the node, or MatchGPULib::view(msg) of a message the library reads as it
+// is (setInputFormat); the header itself needs neither OpenCV nor ROS.
 #pragma once
 
 #include <cstdint>
@@ -59,6 +60,34 @@ public:
     void setFoveaWidth(int rows) { fovW = rows; }
     void setFoveaHeight(int cols) { fovH = cols; }
     void setFoveated(int fov) { foveatedmatching = fov; }
+
+    // (not in the reference) the byte layout of the images the next calls hand over: UGSM_INPUT_RGB8 (what cv_bridge's toCvCopy(.., RGB8)
+    // gives), or ugsm_input_format_from_encoding(msg.encoding) for a message read in place (view() below).  UGSM_ERR_BAD_ARG for an unknown one.
+    int setInputFormat(int format) { return ugsm_set_input_format(ctx_, format); }
+
+    // (not in the reference) a sensor_msgs::Image -- anything with height, width, step, data and header -- read in place: what the templated
+    // calls below take instead of a cv_bridge copy (->image.{rows,cols,step,data}, ->header).  The message must outlive the call.
+    template <class Header>
+    struct ImageView {
+        struct {
+            int rows, cols;
+            size_t step;
+            const uint8_t *data;
+        } image;
+        Header header;
+        const ImageView *operator->() const { return this; }
+    };
+    template <class Msg>
+    static ImageView<decltype(Msg::header)> view(const Msg &m)
+    {
+        ImageView<decltype(Msg::header)> v;
+        v.image.rows = (int)m.height;
+        v.image.cols = (int)m.width;
+        v.image.step = (size_t)m.step;
+        v.image.data = m.data.data();
+        v.header = m.header;
+        return v;
+    }
 
     // MatchGPULib.cpp:406-426
     template <class ImgPtr>

@@ -1,7 +1,8 @@
 // UG_GPU_matcher_ugsm.cpp -- the UG_matcher_gpu node on top of libugsm (catkin build only; not
 // compiled in the GPU image, which has no ROS).  Same node / topic / service / parameter names and
 // message layouts as /root/reference/src/gpu_matcher/UG_GPU_matcher.cpp (:48-61,:742); the body of
-// each callback is: convert to rgb8 -> one call into the MatchGPULib shim -> wrap the returned
+// each callback is: convert to rgb8 (or, for an encoding the library reads as it is, hand the payload over in place with its input
+// format) -> one call into the MatchGPULib shim -> wrap the returned
 // planes in 32FC1 images.  Written from the reference's interface, not from its source text: one
 // persistent matcher object instead of one per callback, cv::Mat headers over the returned planes
 // instead of per-pixel at<float>() loops, the service path fills the whole fovea stack (U6).
@@ -146,11 +147,31 @@ private:
         free(st);
     }
 
+    // The input format of a pair of messages when the library reads their encoding as it is (rgb8, bgr8, rgba8, bgra8, mono8: the payloads
+    // go to the library in place, no cv_bridge copy); -1: convert with cv_bridge::toCvCopy(.., RGB8) as the reference does
+    static int in_place_format(const sensor_msgs::Image &l, const sensor_msgs::Image &r)
+    {
+        const int fmt = ugsm_input_format_from_encoding(l.encoding.c_str());
+        return (fmt >= 0 && r.encoding == l.encoding) ? fmt : -1;
+    }
+
     bool disparitySrv(ug_stereomatcher::GetDisparitiesGPU::Request &req, ug_stereomatcher::GetDisparitiesGPU::Response &rsp)
     {
+        const int fmt = in_place_format(req.imL, req.imR);
+        if (fmt >= 0) {
+            mgpu_->setInputFormat(fmt);
+            return serve(MatchGPULib::view(req.imL), MatchGPULib::view(req.imR), rsp);
+        }
         cv_bridge::CvImagePtr L, R;
         try { L = cv_bridge::toCvCopy(req.imL, enc::RGB8); R = cv_bridge::toCvCopy(req.imR, enc::RGB8); }
         catch (cv_bridge::Exception &) { ROS_ERROR("Could not convert from '%s' to 'rgb8'.", req.imL.encoding.c_str()); return false; }
+        mgpu_->setInputFormat(UGSM_INPUT_RGB8);
+        return serve(L, R, rsp);
+    }
+
+    template <class Img>
+    bool serve(const Img &L, const Img &R, ug_stereomatcher::GetDisparitiesGPU::Response &rsp)
+    {
         const int fov = foveated();
         mgpu_->setFoveated(fov);
         drain();  // (pipelined topic path: the slots belong to the queue while frames are in flight; publish them first)
@@ -175,9 +196,22 @@ private:
 
     void mainRoutine(const sensor_msgs::ImageConstPtr &imL, const sensor_msgs::ImageConstPtr &imR)
     {
+        const int fmt = in_place_format(*imL, *imR);
+        if (fmt >= 0) {  // (the queue's managed calls copy the payloads before they return: the messages need not outlive the call)
+            mgpu_->setInputFormat(fmt);
+            route(MatchGPULib::view(*imL), MatchGPULib::view(*imR));
+            return;
+        }
         cv_bridge::CvImagePtr L, R;
         try { L = cv_bridge::toCvCopy(imL, enc::RGB8); R = cv_bridge::toCvCopy(imR, enc::RGB8); }
         catch (cv_bridge::Exception &) { ROS_ERROR("Could not convert from '%s' to 'rgb8'.", imL->encoding.c_str()); return; }
+        mgpu_->setInputFormat(UGSM_INPUT_RGB8);
+        route(L, R);
+    }
+
+    template <class Img>
+    void route(const Img &L, const Img &R)
+    {
         const int fov = foveated();
         mgpu_->setFoveated(fov);
         const ros::WallTime t0 = ros::WallTime::now();

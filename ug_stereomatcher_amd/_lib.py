@@ -54,10 +54,20 @@ EXPORTS = [
     "ugsm_default_cloud_params", "ugsm_cloud_points", "ugsm_point_cloud", "ugsm_point_cloud_fovea",
     # ... and the resized cloud
     "ugsm_resized_cloud_points", "ugsm_point_cloud_resized", "ugsm_point_cloud_resized_fovea",
+    # the input formats
+    "ugsm_input_bytes_per_pixel", "ugsm_input_format_from_encoding", "ugsm_set_input_format", "ugsm_get_input_format",
 ]
 # ... and what include/ugsm_dev.h adds (libugsm_dev.so only)
 DEV_EXPORTS = ["ugsm_stage_poly_probe", "ugsm_stage_div3_probe", "ugsm_stage_div_probe"]
 
+
+# input formats (ugsm_set_input_format): the byte layout of the images a context reads; a call on an image in format F gives the rgb8 call's
+# result on its conversion to rgb8 (tests/encode_np.py)
+UGSM_INPUT_RGB8 = 0
+UGSM_INPUT_BGR8 = 1
+UGSM_INPUT_RGBA8 = 2
+UGSM_INPUT_BGRA8 = 3
+UGSM_INPUT_MONO8 = 4
 
 UGSM_CLOUD_PCL32 = 0     # pcl::PointXYZRGB in memory: x, y, z, 1.0f, rgb word, 12 zero bytes (32 B)
 UGSM_CLOUD_XYZRGB16 = 1  # x, y, z, rgb word (16 B)
@@ -280,6 +290,10 @@ def load(dev: bool = False):
     lib.ugsm_shard_set_timeout.argtypes = [vp, C.c_longlong]
     lib.ugsm_shard_gather.argtypes = [vp, i, vp, C.c_longlong, vp, i]
     lib.ugsm_shard_finalize.argtypes = [vp]
+    lib.ugsm_input_bytes_per_pixel.argtypes = [i]
+    lib.ugsm_input_format_from_encoding.argtypes = [C.c_char_p]
+    lib.ugsm_set_input_format.argtypes = [vp, i]
+    lib.ugsm_get_input_format.argtypes = [vp, ip]
     lib.ugsm_default_cloud_params.argtypes = [C.POINTER(CloudParams)]
     lib.ugsm_default_cloud_params.restype = None
     lib.ugsm_cloud_points.argtypes = [i, i, i]
@@ -364,6 +378,18 @@ def resized_cloud_points(W: int, H: int, factor: float) -> int:
     return int(load().ugsm_resized_cloud_points(W, H, C.c_float(float(factor))))
 
 
+def input_bytes_per_pixel(format: int) -> int:
+    """3, 3, 4, 4, 1 for UGSM_INPUT_RGB8 .. UGSM_INPUT_MONO8; -1 for an unknown format."""
+    return int(load().ugsm_input_bytes_per_pixel(int(format)))
+
+
+def input_format_from_encoding(encoding) -> int:
+    """The UGSM_INPUT_* of a sensor_msgs encoding name ("rgb8", "bgr8", "rgba8", "bgra8", "mono8"); -1 for any other (and None)."""
+    if isinstance(encoding, str):
+        encoding = encoding.encode()
+    return int(load().ugsm_input_format_from_encoding(encoding))
+
+
 # ---- context -----------------------------------------------------------------------------
 
 class Context:
@@ -424,6 +450,27 @@ class Context:
     @property
     def handle(self):
         return self._h
+
+    # ---- input format (ugsm_set_input_format): captured by every call that hands an image over --------------------------------------
+    def set_input_format(self, format: int):
+        self.check(self.lib.ugsm_set_input_format(self._h, int(format)))
+
+    @property
+    def input_format(self) -> int:
+        f = C.c_int()
+        self.check(self.lib.ugsm_get_input_format(self._h, C.byref(f)))
+        return f.value
+
+    def check_image(self, a: np.ndarray):
+        """(H, W) uint8 for mono8, (H, W, 3) for rgb8 / bgr8, (H, W, 4) for rgba8 / bgra8, matching the context's input format; rows may be padded
+        (a view of a wider array), pixels must be contiguous.  Returns (W, H, stride)."""
+        bpp = input_bytes_per_pixel(self.input_format)
+        if a.dtype != np.uint8 or not ((a.ndim == 2 and bpp == 1) or (a.ndim == 3 and a.shape[2] == bpp and bpp > 1)):
+            raise UgsmError(UGSM_ERR_SIZE_MISMATCH, f"image of shape {a.shape} and dtype {a.dtype} does not match the input format "
+                                                    f"{self.input_format} ({bpp} bytes per pixel)")
+        if (a.ndim == 3 and a.strides[1:] != (bpp, 1)) or (a.ndim == 2 and a.strides[1] != 1):
+            raise UgsmError(UGSM_ERR_BAD_ARG, "image pixels must be contiguous")
+        return a.shape[1], a.shape[0], a.strides[0]
 
     # device memory through the C-ABI (tests / C hosts); bench.py uses torch tensors instead
     def alloc(self, nbytes: int) -> int:
@@ -578,26 +625,32 @@ class Context:
         self.check(self.lib.ugsm_enqueue_foveated(self._h, d_rgbL, d_rgbR, W, H, stride, int(off[0]), int(off[1]), d_stack, d_pyrL, d_pyrR, tag))
 
     def enqueue_full_host(self, rgbL: np.ndarray, rgbR: np.ndarray, out3: np.ndarray, tag: int):
-        """rgbL / rgbR: page-locked (H, W, 3) uint8 (host_array); out3: page-locked (3, H, W) float32."""
-        H, W = rgbL.shape[:2]
-        self.check(self.lib.ugsm_enqueue_full_host(self._h, rgbL.ctypes.data, rgbR.ctypes.data, W, H, rgbL.strides[0], out3[0].ctypes.data,
+        """rgbL / rgbR: page-locked (H, W, 3) uint8 (host_array; (H, W) or (H, W, 4) in other input formats); out3: page-locked (3, H, W) float32."""
+        W, H, stride = self._pair(rgbL, rgbR)
+        self.check(self.lib.ugsm_enqueue_full_host(self._h, rgbL.ctypes.data, rgbR.ctypes.data, W, H, stride, out3[0].ctypes.data,
                                                    out3[1].ctypes.data, out3[2].ctypes.data, tag))
 
     def enqueue_foveated_host(self, rgbL: np.ndarray, rgbR: np.ndarray, off, stack3: np.ndarray, tag: int, pyrL=None, pyrR=None):
-        H, W = rgbL.shape[:2]
-        self.check(self.lib.ugsm_enqueue_foveated_host(self._h, rgbL.ctypes.data, rgbR.ctypes.data, W, H, rgbL.strides[0], int(off[0]), int(off[1]),
+        W, H, stride = self._pair(rgbL, rgbR)
+        self.check(self.lib.ugsm_enqueue_foveated_host(self._h, rgbL.ctypes.data, rgbR.ctypes.data, W, H, stride, int(off[0]), int(off[1]),
                                                        stack3[0].ctypes.data, stack3[1].ctypes.data, stack3[2].ctypes.data,
                                                        pyrL.ctypes.data if pyrL is not None else None, pyrR.ctypes.data if pyrR is not None else None, tag))
 
     def enqueue_full_managed(self, rgbL: np.ndarray, rgbR: np.ndarray, tag: int):
         """Any host memory: the images are copied before the call returns; the results come back in ugsm_completion.result."""
-        H, W = rgbL.shape[:2]
-        self.check(self.lib.ugsm_enqueue_full_managed(self._h, rgbL.ctypes.data, rgbR.ctypes.data, W, H, rgbL.strides[0], tag))
+        W, H, stride = self._pair(rgbL, rgbR)
+        self.check(self.lib.ugsm_enqueue_full_managed(self._h, rgbL.ctypes.data, rgbR.ctypes.data, W, H, stride, tag))
 
     def enqueue_foveated_managed(self, rgbL: np.ndarray, rgbR: np.ndarray, off, want_pyramids: bool, tag: int):
-        H, W = rgbL.shape[:2]
-        self.check(self.lib.ugsm_enqueue_foveated_managed(self._h, rgbL.ctypes.data, rgbR.ctypes.data, W, H, rgbL.strides[0], int(off[0]), int(off[1]),
+        W, H, stride = self._pair(rgbL, rgbR)
+        self.check(self.lib.ugsm_enqueue_foveated_managed(self._h, rgbL.ctypes.data, rgbR.ctypes.data, W, H, stride, int(off[0]), int(off[1]),
                                                           1 if want_pyramids else 0, tag))
+
+    def _pair(self, rgbL: np.ndarray, rgbR: np.ndarray):
+        g = self.check_image(rgbL)
+        if self.check_image(rgbR) != g:
+            raise UgsmError(UGSM_ERR_SIZE_MISMATCH, "left and right images differ in size or stride")
+        return g
 
     def flush(self):
         self.check(self.lib.ugsm_flush(self._h))

@@ -32,6 +32,55 @@ __device__ __forceinline__ T *shifted(T *p, long long bytes)
 
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
+// The byte layouts of an input image the image-reading kernels are instantiated for: the public formats (ugsm.h UGSM_INPUT_*, same
+// numbers) and, for the two four-byte formats, a form that reads a pixel with one 32-bit load -- the host picks it when the image's base
+// pointer and its stride are 4-byte aligned (a caller's device pointer need not be).  Every layout reads as its conversion to rgb8 would:
+// (R, G, B) = bytes (0, 1, 2) or, swapped, (2, 1, 0); mono8 (v, v, v).
+enum InLayout : int { kInRGB8 = 0, kInBGR8 = 1, kInRGBA8 = 2, kInBGRA8 = 3, kInMono8 = 4, kInRGBA8Word = 5, kInBGRA8Word = 6 };
+// the layout a launch of format fmt (UGSM_INPUT_*) reads with; words: every image of the launch and the stride are 4-byte aligned
+constexpr int input_layout(int fmt, bool words) { return (words && (fmt == kInRGBA8 || fmt == kInBGRA8)) ? fmt + 3 : fmt; }
+template <int L>
+struct InPix {
+    static constexpr int bpp = L == kInMono8 ? 1 : ((L == kInRGB8 || L == kInBGR8) ? 3 : 4);
+    static constexpr bool mono = L == kInMono8;
+    static constexpr bool swap = L == kInBGR8 || L == kInBGRA8 || L == kInBGRA8Word;
+    static constexpr bool word = L == kInRGBA8Word || L == kInBGRA8Word;
+    static constexpr int channels = mono ? 1 : 3;  // distinct planes: mono8's three are one
+    // R, G, B (mono8: v in b[0] only) of the pixel at p
+    __device__ static __forceinline__ void load(const uint8_t *p, unsigned (&b)[3])
+    {
+        if (mono) {
+            b[0] = p[0];
+        } else if (word) {
+            const unsigned w = *reinterpret_cast<const unsigned *>(p);
+            b[0] = swap ? (w >> 16) & 255u : w & 255u;
+            b[1] = (w >> 8) & 255u;
+            b[2] = swap ? w & 255u : (w >> 16) & 255u;
+        } else {
+            b[0] = p[swap ? 2 : 0];
+            b[1] = p[1];
+            b[2] = p[swap ? 0 : 2];
+        }
+    }
+    // the same as floats
+    __device__ static __forceinline__ void loadf(const uint8_t *p, float (&f)[3])
+    {
+        if (mono) {
+            f[0] = (float)p[0];
+        } else if (word) {
+            unsigned b[3];
+            load(p, b);
+            f[0] = (float)b[0];
+            f[1] = (float)b[1];
+            f[2] = (float)b[2];
+        } else {
+            f[0] = (float)p[swap ? 2 : 0];
+            f[1] = (float)p[1];
+            f[2] = (float)p[swap ? 0 : 2];
+        }
+    }
+};
+
 // Default-configured texture reference (MatchLib.cu:56-60): point filter, clamp,
 // unnormalised -> t[clamp(floor(coord))].  NaN -> 0 (never produced; defined so that
 // the kernels and the CPU oracle agree).

@@ -24,7 +24,22 @@ struct CtxHooks {
     // UGSM_OK: go on (wait / query the slot as usual); UGSM_PENDING: (poll) not finished; anything else is returned to the caller once the
     // slot has drained -- a peer rank failed its part of the step, or the step's deadline passed and the communicator was aborted.
     int (*shard_wait)(ugsm_ctx *, int slot, int block) = nullptr;
+    // ugsm_set_input_format: the format of the images the next calls hand over (the queue stores it with each pair and sets it back while
+    // it sends the pair's call)
+    int input_format = UGSM_INPUT_RGB8;
 };
+// ugsm_input_bytes_per_pixel: 3, 3, 4, 4, 1 for UGSM_INPUT_RGB8 .. UGSM_INPUT_MONO8, -1 otherwise
+inline int input_bpp(int format)
+{
+    switch (format) {
+    case UGSM_INPUT_RGB8:
+    case UGSM_INPUT_BGR8: return 3;
+    case UGSM_INPUT_RGBA8:
+    case UGSM_INPUT_BGRA8: return 4;
+    case UGSM_INPUT_MONO8: return 1;
+    default: return -1;
+    }
+}
 CtxHooks &ctx_hooks(ugsm_ctx *ctx);
 const ugsm_config &ctx_config(const ugsm_ctx *ctx);
 // the HIP stream of a slot (a hipStream_t), nullptr for a slot the context does not have; unlike ugsm_slot_stream it leaves the slot's

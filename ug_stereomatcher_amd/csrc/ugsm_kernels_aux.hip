@@ -112,9 +112,35 @@ __global__ void k_rgb_planes(const uint8_t *__restrict__ rgb, int stride, int W,
     planes[2 * n + at] = (float)p[2];
 }
 
-void launch_rgb_planes(hipStream_t st, const uint8_t *rgb, int stride, int W, int H, float *planes)
+// the other input layouts (InLayout, ugsm_device.hpp): each pixel as its conversion to rgb8 reads
+template <int L>
+__global__ void k_rgb_planes(const uint8_t *__restrict__ rgb, int stride, int W, int H, float *__restrict__ planes)
 {
-    UGSM_LAUNCH(k_rgb_planes, grid2(W, H), dim3(256), 0, st, rgb, stride, W, H, planes);
+    int x = blockIdx.x * blockDim.x + threadIdx.x;
+    int y = blockIdx.y;
+    if (x >= W) return;
+    float f[3];
+    InPix<L>::loadf(rgb + (size_t)y * stride + InPix<L>::bpp * x, f);
+    size_t n = (size_t)W * H, at = (size_t)y * W + x;
+    planes[at] = f[0];
+    planes[n + at] = f[InPix<L>::mono ? 0 : 1];
+    planes[2 * n + at] = f[InPix<L>::mono ? 0 : 2];
+}
+
+void launch_rgb_planes(hipStream_t st, const uint8_t *rgb, int stride, int W, int H, float *planes, int fmt)
+{
+    using Kern = void (*)(const uint8_t *, int, int, int, float *);
+    Kern kern = k_rgb_planes;
+    switch (input_layout(fmt, input_words_aligned(rgb, stride, nullptr))) {
+    case kInBGR8: kern = k_rgb_planes<kInBGR8>; break;
+    case kInRGBA8: kern = k_rgb_planes<kInRGBA8>; break;
+    case kInBGRA8: kern = k_rgb_planes<kInBGRA8>; break;
+    case kInMono8: kern = k_rgb_planes<kInMono8>; break;
+    case kInRGBA8Word: kern = k_rgb_planes<kInRGBA8Word>; break;
+    case kInBGRA8Word: kern = k_rgb_planes<kInBGRA8Word>; break;
+    default: break;
+    }
+    UGSM_LAUNCH(kern, grid2(W, H), dim3(256), 0, st, rgb, stride, W, H, planes);
 }
 
 // =========================================================================================
@@ -293,13 +319,39 @@ __device__ __forceinline__ void tri_at(const CloudArgs &a, const Proj &P1q, cons
 // the colour word of full-resolution pixel (cx, cy); the foveated forms clamp it to the image (the reference reads whatever lies there):
 // at destination level 0 no fovea level's window leaves the image at 16 MP, 1080p, 640 x 480 or 160 x 120, so the clamp only acts on
 // margins a caller pushes past the edge
-template <bool Clamp>
-__device__ __forceinline__ unsigned colour_at(const CloudArgs &a, int cx, int cy)
+// The colour word of pixel cx of an image row in any input format (UGSM_INPUT_*; fmt is uniform): R << 16 | G << 8 | B of the pixel's
+// conversion to rgb8.  The forms that take it are instances of their own: the rgb8 forms read as they always did.
+__device__ __forceinline__ unsigned colour_word(const uint8_t *row, int cx, int fmt)
+{
+    switch (fmt) {
+    case kInBGR8: {
+        const uint8_t *p = row + 3 * (size_t)cx;
+        return (unsigned)p[2] << 16 | (unsigned)p[1] << 8 | (unsigned)p[0];
+    }
+    case kInRGBA8: {
+        const uint8_t *p = row + 4 * (size_t)cx;
+        return (unsigned)p[0] << 16 | (unsigned)p[1] << 8 | (unsigned)p[2];
+    }
+    case kInBGRA8: {
+        const uint8_t *p = row + 4 * (size_t)cx;
+        return (unsigned)p[2] << 16 | (unsigned)p[1] << 8 | (unsigned)p[0];
+    }
+    case kInMono8: return (unsigned)row[cx] * 0x010101u;
+    default: {
+        const uint8_t *p = row + 3 * (size_t)cx;
+        return (unsigned)p[0] << 16 | (unsigned)p[1] << 8 | (unsigned)p[2];
+    }
+    }
+}
+
+template <bool Clamp, bool AnyFmt = false>
+__device__ __forceinline__ unsigned colour_at(const CloudArgs &a, int cx, int cy, int fmt = 0)
 {
     if (Clamp) {
         cx = min(max(cx, 0), a.W - 1);
         cy = min(max(cy, 0), a.H - 1);
     }
+    if (AnyFmt) return colour_word(a.rgb + (size_t)cy * a.stride, cx, fmt);
     const uint8_t *p = a.rgb + (size_t)cy * a.stride + 3 * (size_t)cx;
     return (unsigned)p[0] << 16 | (unsigned)p[1] << 8 | (unsigned)p[2];
 }
@@ -314,8 +366,8 @@ __device__ __forceinline__ bool cloud_keep(const CloudArgs &a, size_t at, float 
 }
 
 // one sampled point: its record (x, y, z, rgb word as float bits) and whether a compact cloud keeps it
-template <bool Fovea, bool Colour>
-__device__ __forceinline__ bool cloud_point(const CloudArgs &a, const Proj &P1q, const Proj &P2q, int ii, int jj, float4 &rec)
+template <bool Fovea, bool Colour, bool AnyFmt = false>
+__device__ __forceinline__ bool cloud_point(const CloudArgs &a, const Proj &P1q, const Proj &P2q, int ii, int jj, float4 &rec, int fmt = 0)
 {
     const size_t at = (size_t)jj * a.pw + ii;
     float x1, y1, x2, y2;
@@ -341,7 +393,8 @@ __device__ __forceinline__ bool cloud_point(const CloudArgs &a, const Proj &P1q,
     }
     float X, Y, Z;
     tri_point(x1, y1, x2, y2, P1q.m, P2q.m, X, Y, Z);
-    if (Colour) {
+    if (Colour && AnyFmt) rec = make_float4(X, Y, Z, __uint_as_float(colour_word(a.rgb + (size_t)cy * a.stride, cx, fmt)));
+    if (Colour && !AnyFmt) {
         const uint8_t *p = a.rgb + (size_t)cy * a.stride + 3 * (size_t)cx;
         const unsigned word = (unsigned)p[0] << 16 | (unsigned)p[1] << 8 | (unsigned)p[2];
         rec = make_float4(X, Y, Z, __uint_as_float(word));
@@ -380,9 +433,9 @@ __device__ __forceinline__ void cubic_tap(int d, double scale, int n, int &s, fl
     border = s < 1 || s + 2 >= n;
 }
 
-template <bool Fovea, bool Colour>
+template <bool Fovea, bool Colour, bool AnyFmt = false>
 __device__ __forceinline__ bool resized_point(const CloudArgs &a, const CloudResize &rz, const Proj &P1q, const Proj &P2q, int ii, int jj,
-                                              float4 &rec)
+                                              float4 &rec, int fmt = 0)
 {
     // (ii < (int)(pw * f) keeps ii / f below pw; the clamp never acts)
     const int xx = min((int)((float)ii / rz.factor), a.pw - 1);
@@ -413,13 +466,14 @@ __device__ __forceinline__ bool resized_point(const CloudArgs &a, const CloudRes
     }
     if (Colour) {
         const bool mapped = Fovea && rz.colour_mapped;
-        rec = make_float4(X, Y, Z, __uint_as_float(mapped ? colour_at<Fovea>(a, (int)x1, (int)y1) : colour_at<Fovea>(a, xx, yy)));
+        rec = make_float4(X, Y, Z, __uint_as_float(mapped ? colour_at<Fovea, AnyFmt>(a, (int)x1, (int)y1, fmt) : colour_at<Fovea, AnyFmt>(a, xx, yy, fmt)));
     }
     return cloud_keep(a, (size_t)yy * a.pw + xx, X, Y, Z);
 }
 
-template <bool Fovea, int Form>
-__device__ __forceinline__ void cloud_tile(const CloudArgs &a, const CloudResize &rz, const Proj &P1q, const Proj &P2q)
+// AnyFmt: the colour is read from an image in input format fmt (the rgb8 forms: AnyFmt false, their instruction streams unchanged)
+template <bool Fovea, int Form, bool AnyFmt = false>
+__device__ __forceinline__ void cloud_tile(const CloudArgs &a, const CloudResize &rz, const Proj &P1q, const Proj &P2q, int fmt = 0)
 {
     __shared__ float4 rec[kCloudTC * kCloudPad];
     __shared__ unsigned char kept[kCloudTC * kCloudTR];
@@ -439,9 +493,9 @@ __device__ __forceinline__ void cloud_tile(const CloudArgs &a, const CloudResize
         if (ci < a.wc && cj < a.hc) {
             float4 v;
             if constexpr (Form == kTriResizedCount || Form == kTriResized)
-                k = resized_point<Fovea, Write>(a, rz, P1q, P2q, ci, cj, v);
+                k = resized_point<Fovea, Write, AnyFmt>(a, rz, P1q, P2q, ci, cj, v, fmt);
             else
-                k = cloud_point<Fovea, Write>(a, P1q, P2q, ci * a.s, cj * a.s, v);
+                k = cloud_point<Fovea, Write, AnyFmt>(a, P1q, P2q, ci * a.s, cj * a.s, v, fmt);
             if (Write) rec[c * kCloudPad + r] = v;
         }
         kept[c * kCloudTR + r] = k;
@@ -529,14 +583,42 @@ __global__ __launch_bounds__(256) void k_triangulate_fovea(CloudArgs a, Proj P1q
     cloud_tile<true, Form>(a, rz, P1q, P2q);
 }
 
+// The cloud launches of an image in another input format than rgb8 (fmt, uniform): one instance per cloud form, the colour read with a
+// switch on fmt (the count launches read no colour and are shared)
+template <int Form>
+__global__ __launch_bounds__(256) void k_triangulate(CloudArgs a, Proj P1q, Proj P2q, CloudResize rz, int fmt)
+{
+    static_assert(Form == kTriCloud || Form == kTriResized, "the cloud forms that read colour");
+    cloud_tile<false, Form, true>(a, rz, P1q, P2q, fmt);
+}
+template <int Form>
+__global__ __launch_bounds__(256) void k_triangulate_fovea(CloudArgs a, Proj P1q, Proj P2q, CloudResize rz, int fmt)
+{
+    static_assert(Form == kTriCloud || Form == kTriResized, "the cloud forms that read colour");
+    cloud_tile<true, Form, true>(a, rz, P1q, P2q, fmt);
+}
+
 int cloud_strips(int wc) { return (wc + kCloudTC - 1) / kCloudTC; }
 int cloud_chunks(int hc) { return (hc + kCloudTR - 1) / kCloudTR; }
 
-void launch_point_cloud(hipStream_t st, const CloudArgs &args, bool fovea, const double *P1, const double *P2, const CloudResize *rz)
+void launch_point_cloud(hipStream_t st, const CloudArgs &args, bool fovea, const double *P1, const double *P2, const CloudResize *rz, int fmt)
 {
     Proj a, b;
     for (int k = 0; k < 12; k++) { a.m[k] = P1[k]; b.m[k] = P2[k]; }
     const dim3 grid(cloud_strips(args.wc), args.nchunk);
+    if (fmt != kInRGB8) {
+        using Kern3 = void (*)(CloudArgs, Proj, Proj);
+        using Kern4 = void (*)(CloudArgs, Proj, Proj, CloudResize);
+        using Kern5 = void (*)(CloudArgs, Proj, Proj, CloudResize, int);
+        if (args.compact) {
+            if (rz) UGSM_LAUNCH(fovea ? (Kern4)k_triangulate_fovea<kTriResizedCount> : (Kern4)k_triangulate<kTriResizedCount>, grid, dim3(256), 0, st, args, a, b, *rz);
+            else UGSM_LAUNCH(fovea ? (Kern3)k_triangulate_fovea<kTriCloudCount> : (Kern3)k_triangulate<kTriCloudCount>, grid, dim3(256), 0, st, args, a, b);
+        }
+        const Kern5 cloud = rz ? (fovea ? (Kern5)k_triangulate_fovea<kTriResized> : (Kern5)k_triangulate<kTriResized>)
+                               : (fovea ? (Kern5)k_triangulate_fovea<kTriCloud> : (Kern5)k_triangulate<kTriCloud>);
+        UGSM_LAUNCH(cloud, grid, dim3(256), 0, st, args, a, b, rz ? *rz : CloudResize{}, fmt);
+        return;
+    }
     if (rz) {
         using Kern = void (*)(CloudArgs, Proj, Proj, CloudResize);
         const Kern count = fovea ? (Kern)k_triangulate_fovea<kTriResizedCount> : (Kern)k_triangulate<kTriResizedCount>;

@@ -60,7 +60,7 @@ struct Batch {
 void launch_seed(hipStream_t st, const float *src3, int Ws, int Hs, float *dst3, int Wd, int Hd, int cx, int cy, const Batch *bt = nullptr);
 void launch_copy_view(hipStream_t st, Img3 src, int W, int H, float *dst, size_t dst_plane, int dst_pitch, const Batch *bt = nullptr);
 // rgb8 -> planar float level 0 (MatchGPULib.cpp:332-338) where k_pyr_base does not apply: pyramids of fewer than three levels, kernel_path 1
-void launch_rgb_planes(hipStream_t st, const uint8_t *rgb, int stride, int W, int H, float *planes);
+void launch_rgb_planes(hipStream_t st, const uint8_t *rgb, int stride, int W, int H, float *planes, int fmt = 0);
 // LR-consistency check (north_star; no reference counterpart): zeroes the confidence of left3 where right3 does not point back within tau
 void launch_lr_check(hipStream_t st, float *left3, const float *right3, int W, int H, float tau, unsigned long long *marked);
 // X, Y, Z planes from the full-resolution (dx, dy) and the two 3x4 projection matrices
@@ -72,7 +72,7 @@ void launch_triangulate_fovea(hipStream_t st, const float *stackx, const float *
 struct CloudArgs {
     const float *dx, *dy, *conf;  // pw x ph row-major planes (the fovea form: level src_level of the stacks); conf may be null
     int pw, ph;
-    const uint8_t *rgb;           // the left image, rgb8, W x H, `stride` bytes per row
+    const uint8_t *rgb;           // the left image, W x H, `stride` bytes per row (rgb8, or the format launch_point_cloud is given)
     int W, H, stride;
     int s, wc, hc, nchunk;        // sampling; the sampled grid; cloud_chunks(hc)
     int format, compact;          // UGSM_CLOUD_PCL32 (0) / UGSM_CLOUD_XYZRGB16 (1); compact: only the points that pass the filter
@@ -94,8 +94,9 @@ struct CloudResize {
 };
 int cloud_strips(int wc);
 int cloud_chunks(int hc);
-// compact: a count launch, then the cloud launch; dense: the cloud launch.  rz: the resized forms
-void launch_point_cloud(hipStream_t st, const CloudArgs &args, bool fovea, const double *P1, const double *P2, const CloudResize *rz = nullptr);
+// compact: a count launch, then the cloud launch; dense: the cloud launch.  rz: the resized forms; fmt: the input format of args.rgb (UGSM_INPUT_*)
+void launch_point_cloud(hipStream_t st, const CloudArgs &args, bool fovea, const double *P1, const double *P2, const CloudResize *rz = nullptr,
+                        int fmt = 0);
 void launch_upsample_paste(hipStream_t st, const float *src3, int W, int H, float *dst3, int W2, int H2, const float *fovH_, const float *fovV_,
                            const float *fovC_, int fovW, int fovH, int org_x, int org_y);
 // S_dx, S_dy, C of weightedDifference (MatchGPULib.cpp:1336-1437) into out3; rowsum = 3*H doubles of scratch
@@ -184,8 +185,11 @@ void launch_blur_decimate(hipStream_t st, const float *src3, int W, int H, float
 struct PyrWindow {
     int x0, y0, w, h;
 };
+// every image of the launch (rgb, and rgb + bt->img[b]) and the stride 4-byte aligned: what the word-load layouts need (input_layout)
+bool input_words_aligned(const uint8_t *rgb, int stride, const Batch *bt);
+// fmt: the input format (UGSM_INPUT_*); the four-byte formats take their word-load instances when every image and the stride are 4-byte aligned
 void launch_pyr_base(hipStream_t st, const uint8_t *rgb, int stride, int W, int H, float *lvl0, float *lvl1, int W1, int H1, float *lvl2, int W2,
-                     int H2, unsigned *range_bad, const Batch *bt = nullptr, PyrWindow win = PyrWindow{0, 0, 0, 0});
+                     int H2, unsigned *range_bad, const Batch *bt = nullptr, PyrWindow win = PyrWindow{0, 0, 0, 0}, int fmt = 0);
 void launch_sqblur_clamp(hipStream_t st, Img3 src, int W, int H, float *dst3, const Batch *bt = nullptr);
 
 }  // namespace ugsm

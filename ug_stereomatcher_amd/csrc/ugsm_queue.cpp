@@ -36,16 +36,18 @@ struct Item {
     int mode, mem;
     const uint8_t *L, *R;
     int W, H, stride, off_x, off_y;
+    int fmt;  // the input format the pair was enqueued in (ugsm_set_input_format at the time of its ugsm_enqueue_*)
     float *out[5];  // device: out[0] = d_out / d_stack, out[3], out[4] = d_pyrL / d_pyrR; host: H, V, C planes (+ pyramid stacks)
     uint64_t tag;
     unsigned long long seq;
     int managed;  // index into Queue::pool, or -1
     bool pyr() const { return out[3] != nullptr || out[4] != nullptr; }
-    // pairs of one call: one mode, one kind of memory, one geometry; host calls with pyramid stacks go out alone (the batched host
-    // entry point has none)
+    // pairs of one call: one mode, one kind of memory, one geometry, one input format; host calls with pyramid stacks go out alone (the
+    // batched host entry point has none)
     bool same_kind(const Item &o) const
     {
-        return mode == o.mode && mem == o.mem && W == o.W && H == o.H && stride == o.stride && !(mem != MEM_DEVICE && (pyr() || o.pyr()));
+        return mode == o.mode && mem == o.mem && W == o.W && H == o.H && stride == o.stride && fmt == o.fmt &&
+               !(mem != MEM_DEVICE && (pyr() || o.pyr()));
     }
 };
 
@@ -213,6 +215,9 @@ void dispatch(ugsm_ctx *ctx, Queue *q, int n, int slot, bool more)
     CtxHooks &h = ctx_hooks(ctx);
     h.queue_calling = true;
     h.queue_more = more;
+    // the call reads its images in the format its pairs were enqueued in, whatever the host has set since
+    const int host_fmt = h.input_format;
+    h.input_format = f.fmt;
     int st;
     if (f.mem == MEM_DEVICE) {
         if (f.mode == M_FULL)
@@ -228,6 +233,7 @@ void dispatch(ugsm_ctx *ctx, Queue *q, int n, int slot, bool more)
             st = n == 1 ? ugsm_submit_foveated_host(ctx, slot, L[0], R[0], f.W, f.H, f.stride, ox[0], oy[0], o0[0], o1[0], o2[0], pl[0], pr[0])
                         : ugsm_submit_foveated_batch_host(ctx, slot, n, L, R, f.W, f.H, f.stride, ox, oy, o0, o1, o2);
     }
+    h.input_format = host_fmt;
     h.queue_calling = false;
     h.queue_more = false;
     c.status = st;  // (a call that failed to enqueue: its pairs are reported with this status once the slot has drained, reap / wait_front)
@@ -292,7 +298,8 @@ int check_geometry(ugsm_ctx *ctx, int W, int H, int stride, bool fovea)
     int w[UGSM_MAX_LEVELS], h[UGSM_MAX_LEVELS];
     const int st = ugsm_level_dims(W, H, cfg.levels, w, h);
     if (st != UGSM_OK) return ctx_fail(ctx, st, "ugsm_enqueue_*: bad image size for the context's pyramid");
-    if (stride < 3 * W) return ctx_fail(ctx, UGSM_ERR_SIZE_MISMATCH, "ugsm_enqueue_*: stride < 3 * W");
+    if (stride < input_bpp(ctx_hooks(ctx).input_format) * W)
+        return ctx_fail(ctx, UGSM_ERR_SIZE_MISMATCH, "ugsm_enqueue_*: stride < bytes per pixel of the input format * W");
     if (fovea && cfg.fovea_levels < 2) return ctx_fail(ctx, UGSM_ERR_BAD_ARG, "ugsm_enqueue_foveated*: the context has no fovea levels");
     return UGSM_OK;
 }
@@ -315,6 +322,7 @@ int enqueue(ugsm_ctx *ctx, Item it)
         const int r = room(ctx, q);
         if (r != UGSM_OK) return r;
         it.seq = q->seq + 1;
+        it.fmt = ctx_hooks(ctx).input_format;  // (captured now: the call is formed later)
         q->waiting.push_back(it);
         q->seq = it.seq;
         ctx_hooks(ctx).queue_busy = true;
@@ -376,7 +384,7 @@ int enqueue_managed(ugsm_ctx *ctx, int mode, const uint8_t *rgbL, const uint8_t 
     const ugsm_config &cfg = ctx_config(ctx);
     const int r = room(ctx, q);
     if (r != UGSM_OK) return r;
-    const size_t row = 3 * (size_t)W, img = (row * (size_t)H + 255) & ~(size_t)255;
+    const size_t row = (size_t)input_bpp(ctx_hooks(ctx).input_format) * W, img = (row * (size_t)H + 255) & ~(size_t)255;
     size_t plane, out_floats;
     if (mode == M_FULL) {
         plane = (size_t)W * H;
@@ -394,7 +402,7 @@ int enqueue_managed(ugsm_ctx *ctx, int mode, const uint8_t *rgbL, const uint8_t 
     });
     if (grown != UGSM_OK || idx < 0) return UGSM_ERR_NOMEM;  // (ugsm_host_alloc has set the message)
     Managed &m = q->pool[(size_t)idx];
-    // the images, compacted to rows of 3 W bytes, into the staging buffer: after this the caller's memory is not touched again
+    // the images, compacted to rows of bytes-per-pixel x W bytes, into the staging buffer: after this the caller's memory is not touched again
     for (int side = 0; side < 2; side++) {
         const uint8_t *src = side == 0 ? rgbL : rgbR;
         uint8_t *dst = m.in + side * img;

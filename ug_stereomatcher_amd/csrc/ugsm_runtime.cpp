@@ -670,6 +670,9 @@ Batch make_batch(const Slot &s, Grp g, const Img3 *views = nullptr, const SeedMa
     return b;
 }
 
+// the least stride of a W-pixel row in the context's input format
+int input_row_bytes(const ugsm_ctx *ctx, int W) { return ugsm_input_bytes_per_pixel(ctx->hooks.input_format) * W; }
+
 // CreatePyramidFromImage (MatchGPULib.cpp:1033-1125) for the left OR the right image of every pair of the call: rgb[b] -> pyr + b * pyr_stride.
 // The images of a batch go through every pyramid kernel together (one launch per level for all of them).
 // What a foveated call reads of level 0: every pair's fovea window (the level-0 crop of fovea_geometry); k_pyr_base then stores level 0
@@ -706,12 +709,12 @@ int build_pyramids(ugsm_ctx *ctx, Slot &s, int si, const uint8_t *const *rgb, in
     if (base) {
         Timer t(ctx, &s, si, KC_PYR_BASE, (double)s.W * s.H * nb);
         launch_pyr_base(pst, rgb[0], stride, s.W, s.H, pyr + s.off[0], pyr + s.off[1], s.w[1], s.h[1], pyr + s.off[2], s.w[2], s.h[2], s.range_bad,
-                        nb > 1 ? &bt0 : nullptr, pw);
+                        nb > 1 ? &bt0 : nullptr, pw, ctx->hooks.input_format);
     } else {
         // (pyramids of fewer than three levels, and kernel_path 1: image by image)
         for (int b = 0; b < nb; b++) {
             Timer t(ctx, &s, si, KC_MISC, (double)s.W * s.H);
-            launch_rgb_planes(pst, rgb[b], stride, s.W, s.H, pyr + b * s.pyr_stride + s.off[0]);
+            launch_rgb_planes(pst, rgb[b], stride, s.W, s.H, pyr + b * s.pyr_stride + s.off[0], ctx->hooks.input_format);
         }
     }
     // CreatePyramidFromImage, MatchGPULib.cpp:1063-1106: level 1 from level 0 (sf=(float)SCALE),
@@ -1042,7 +1045,7 @@ int enqueue_pyramids(ugsm_ctx *ctx, Slot &s, int si, const uint8_t *const *d_rgb
     if (!d_rgbL || !d_rgbR || nb < 1 || nb > kMaxBatch) return UGSM_ERR_BAD_ARG;
     for (int b = 0; b < nb; b++)
         if (!d_rgbL[b] || !d_rgbR[b]) return UGSM_ERR_BAD_ARG;
-    if (stride < 3 * W) return UGSM_ERR_SIZE_MISMATCH;
+    if (stride < input_row_bytes(ctx, W)) return UGSM_ERR_SIZE_MISMATCH;
     UCHK(prepare_slot(ctx, s, W, H, nb));
     // the pyramid kernels of the fused path check every value they write (level 0 holds the integers 0..255)
     s.range_known = ctx->cfg.kernel_path != 1 && s.range_bad != nullptr;
@@ -1372,7 +1375,7 @@ int mark_done(ugsm_ctx *ctx, Slot &s)
 int stage_in(ugsm_ctx *ctx, Slot &s, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride)
 {
     if (!rgbL || !rgbR || W < 1 || H < 1) return UGSM_ERR_BAD_ARG;
-    if (stride < 3 * W) return UGSM_ERR_SIZE_MISMATCH;
+    if (stride < input_row_bytes(ctx, W)) return UGSM_ERR_SIZE_MISMATCH;
     const size_t bytes = (size_t)stride * H;
     if (bytes > s.rgb_cap) {
         size_t c = s.rgb_cap;
@@ -1527,6 +1530,32 @@ void ugsm_default_config(ugsm_config *cfg)
 }
 
 int ugsm_abi_version(void) { return UGSM_ABI_VERSION; }
+
+int ugsm_input_bytes_per_pixel(int format) { return input_bpp(format); }
+
+int ugsm_input_format_from_encoding(const char *enc)
+{
+    if (!enc) return -1;
+    static const char *const names[] = {"rgb8", "bgr8", "rgba8", "bgra8", "mono8"};  // sensor_msgs/image_encodings.h, index = UGSM_INPUT_*
+    for (int f = 0; f < 5; f++)
+        if (strcmp(enc, names[f]) == 0) return f;
+    return -1;
+}
+
+int ugsm_set_input_format(ugsm_ctx *ctx, int format)
+{
+    if (!ctx) return UGSM_ERR_BAD_ARG;
+    if (ugsm_input_bytes_per_pixel(format) < 0) return ctx_fail(ctx, UGSM_ERR_BAD_ARG, "ugsm_set_input_format: unknown format");
+    ctx->hooks.input_format = format;
+    return UGSM_OK;
+}
+
+int ugsm_get_input_format(const ugsm_ctx *ctx, int *format)
+{
+    if (!ctx || !format) return UGSM_ERR_BAD_ARG;
+    *format = ctx->hooks.input_format;
+    return UGSM_OK;
+}
 int ugsm_is_dev_library(void) { return kDevLib ? 1 : 0; }
 
 const char *ugsm_status_string(int st)
@@ -2084,7 +2113,7 @@ static int stage_in_batch(ugsm_ctx *ctx, Slot &s, int n, const uint8_t *const *r
                           const uint8_t **dL, const uint8_t **dR)
 {
     if (W < 1 || H < 1) return UGSM_ERR_BAD_ARG;
-    if (stride < 3 * W) return UGSM_ERR_SIZE_MISMATCH;
+    if (stride < input_row_bytes(ctx, W)) return UGSM_ERR_SIZE_MISMATCH;
     const size_t bytes = ((size_t)stride * H + 255) & ~(size_t)255;
     if (bytes * n > s.rgb_cap) {
         size_t c = s.rgb_cap;
@@ -2219,7 +2248,7 @@ int ugsm_stage_pyramid(ugsm_ctx *ctx, const uint8_t *d_rgb, int W, int H, int st
     Slot *s;
     UCHK(get_slot(ctx, 0, &s));
     if (!d_rgb || !d_out3 || level < 0 || level >= ctx->cfg.levels) return UGSM_ERR_BAD_ARG;
-    if (stride < 3 * W) return UGSM_ERR_SIZE_MISMATCH;
+    if (stride < input_row_bytes(ctx, W)) return UGSM_ERR_SIZE_MISMATCH;
     HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
     UCHK(prepare_slot(ctx, *s, W, H));
     UCHK(build_pyramids(ctx, *s, 0, &d_rgb, stride, s->pyrL));
@@ -2373,13 +2402,13 @@ namespace {
 
 // the checks every entry point shares (no device needed); pw x ph: the planes the points come from; resized: the resized forms, which
 // take no sampling (p->sampling 1) and a factor in (0, 1] that leaves both sides at least 1
-int cloud_args_ok(const float *dx, const float *dy, const float *conf, const uint8_t *rgb, int W, int H, int stride, int pw, int ph,
+int cloud_args_ok(const float *dx, const float *dy, const float *conf, const uint8_t *rgb, int W, int H, int stride, int bpp, int pw, int ph,
                   const double *P1, const double *P2, const ugsm_cloud_params *p, const void *points, long long cap, const long long *count,
                   bool resized = false, float factor = 1.0f)
 {
     if (!dx || !dy || !rgb || !P1 || !P2 || !p || !points || !count) return UGSM_ERR_BAD_ARG;
     if (W < 1 || H < 1 || pw < 1 || ph < 1 || (long long)W * H > kMaxPixels || (long long)pw * ph > kMaxPixels) return UGSM_ERR_BAD_ARG;
-    if ((long long)stride < 3LL * W || p->sampling < 1 || (p->format != UGSM_CLOUD_PCL32 && p->format != UGSM_CLOUD_XYZRGB16)) return UGSM_ERR_BAD_ARG;
+    if ((long long)stride < (long long)bpp * W || p->sampling < 1 || (p->format != UGSM_CLOUD_PCL32 && p->format != UGSM_CLOUD_XYZRGB16)) return UGSM_ERR_BAD_ARG;
     if (std::isnan(p->min_conf) || std::isnan(p->z_min) || std::isnan(p->z_max) || p->z_min > p->z_max) return UGSM_ERR_BAD_ARG;
     if (!conf && p->min_conf > -INFINITY) return UGSM_ERR_BAD_ARG;  // (a confidence test without a confidence plane)
     if (cap < 0 || ((uintptr_t)points & 15) || ((uintptr_t)count & 7)) return UGSM_ERR_BAD_ARG;
@@ -2448,7 +2477,7 @@ int point_cloud(ugsm_ctx *ctx, int slot, CloudArgs &a, bool fovea, const double 
     }
     {
         Timer t(ctx, s, slot, KC_MISC, (double)a.wc * a.hc);
-        launch_point_cloud(s->st, a, fovea, P1, P2, rz);
+        launch_point_cloud(s->st, a, fovea, P1, P2, rz, ctx->hooks.input_format);
     }
     HIPCHK(ctx, hipGetLastError());
     return UGSM_OK;
@@ -2475,7 +2504,7 @@ int ugsm_point_cloud(ugsm_ctx *ctx, int slot, const float *d_dispx, const float 
                      long long *d_count)
 {
     if (!ctx) return UGSM_ERR_BAD_ARG;
-    UCHK(cloud_args_ok(d_dispx, d_dispy, d_conf, d_rgbL, W, H, stride, W, H, P1, P2, p, d_points, cap_points, d_count));
+    UCHK(cloud_args_ok(d_dispx, d_dispy, d_conf, d_rgbL, W, H, stride, ugsm_input_bytes_per_pixel(ctx->hooks.input_format), W, H, P1, P2, p, d_points, cap_points, d_count));
     CloudArgs a = cloud_args(d_dispx, d_dispy, d_conf, d_rgbL, W, H, stride, W, H, p, d_points, cap_points, d_count);
     return point_cloud(ctx, slot, a, false, P1, P2);
 }
@@ -2485,7 +2514,7 @@ int ugsm_point_cloud_fovea(ugsm_ctx *ctx, int slot, const float *d_stackx, const
                            const double *P1, const double *P2, const ugsm_cloud_params *p, void *d_points, long long cap_points, long long *d_count)
 {
     if (!ctx) return UGSM_ERR_BAD_ARG;
-    UCHK(cloud_args_ok(d_stackx, d_stacky, d_stackc, d_rgbL, W, H, stride, fovW, fovH, P1, P2, p, d_points, cap_points, d_count));
+    UCHK(cloud_args_ok(d_stackx, d_stacky, d_stackc, d_rgbL, W, H, stride, ugsm_input_bytes_per_pixel(ctx->hooks.input_format), fovW, fovH, P1, P2, p, d_points, cap_points, d_count));
     CloudArgs a;
     UCHK(fovea_cloud_args(a, d_stackx, d_stacky, d_stackc, fovW, fovH, src_level, left_margin, upper_margin, scale, d_rgbL, W, H, stride, p,
                           d_points, cap_points, d_count));
@@ -2499,7 +2528,7 @@ int ugsm_point_cloud_resized(ugsm_ctx *ctx, int slot, const float *d_dispx, cons
                              void *d_points, long long cap_points, long long *d_count)
 {
     if (!ctx) return UGSM_ERR_BAD_ARG;
-    UCHK(cloud_args_ok(d_dispx, d_dispy, d_conf, d_rgbL, W, H, stride, W, H, P1, P2, p, d_points, cap_points, d_count, true, factor));
+    UCHK(cloud_args_ok(d_dispx, d_dispy, d_conf, d_rgbL, W, H, stride, ugsm_input_bytes_per_pixel(ctx->hooks.input_format), W, H, P1, P2, p, d_points, cap_points, d_count, true, factor));
     CloudArgs a = cloud_args(d_dispx, d_dispy, d_conf, d_rgbL, W, H, stride, W, H, p, d_points, cap_points, d_count);
     const CloudResize rz = resize_args(a, factor, 0);
     return point_cloud(ctx, slot, a, false, P1, P2, &rz);
@@ -2511,7 +2540,7 @@ int ugsm_point_cloud_resized_fovea(ugsm_ctx *ctx, int slot, const float *d_stack
                                    void *d_points, long long cap_points, long long *d_count)
 {
     if (!ctx) return UGSM_ERR_BAD_ARG;
-    UCHK(cloud_args_ok(d_stackx, d_stacky, d_stackc, d_rgbL, W, H, stride, fovW, fovH, P1, P2, p, d_points, cap_points, d_count, true, factor));
+    UCHK(cloud_args_ok(d_stackx, d_stacky, d_stackc, d_rgbL, W, H, stride, ugsm_input_bytes_per_pixel(ctx->hooks.input_format), fovW, fovH, P1, P2, p, d_points, cap_points, d_count, true, factor));
     if (colour_mapped != 0 && colour_mapped != 1) return UGSM_ERR_BAD_ARG;
     CloudArgs a;
     UCHK(fovea_cloud_args(a, d_stackx, d_stacky, d_stackc, fovW, fovH, src_level, left_margin, upper_margin, scale, d_rgbL, W, H, stride, p,
