@@ -10,6 +10,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 namespace ugsm {
 
 // MatchGPULib.cpp:761-774 -- {0.0816475, 0.218507, 0.303281, ...} / their f32 sum.
@@ -39,6 +41,20 @@ __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? l
 enum InLayout : int { kInRGB8 = 0, kInBGR8 = 1, kInRGBA8 = 2, kInBGRA8 = 3, kInMono8 = 4, kInRGBA8Word = 5, kInBGRA8Word = 6 };
 // the layout a launch of format fmt (UGSM_INPUT_*) reads with; words: every image of the launch and the stride are 4-byte aligned
 constexpr int input_layout(int fmt, bool words) { return (words && (fmt == kInRGBA8 || fmt == kInBGRA8)) ? fmt + 3 : fmt; }
+// a launcher's one launch body for the layout it reads with: f(std::integral_constant<int, L>()) (host)
+template <class F>
+void with_layout(int layout, F &&f)
+{
+    switch (layout) {
+    case kInBGR8: return f(std::integral_constant<int, kInBGR8>());
+    case kInRGBA8: return f(std::integral_constant<int, kInRGBA8>());
+    case kInBGRA8: return f(std::integral_constant<int, kInBGRA8>());
+    case kInMono8: return f(std::integral_constant<int, kInMono8>());
+    case kInRGBA8Word: return f(std::integral_constant<int, kInRGBA8Word>());
+    case kInBGRA8Word: return f(std::integral_constant<int, kInBGRA8Word>());
+    default: return f(std::integral_constant<int, kInRGB8>());
+    }
+}
 template <int L>
 struct InPix {
     static constexpr int bpp = L == kInMono8 ? 1 : ((L == kInRGB8 || L == kInBGR8) ? 3 : 4);

@@ -99,20 +99,8 @@ void launch_lr_check(hipStream_t st, float *left3, const float *right3, int W, i
 }
 
 // --------------------------------------------------------------------------------------
-// MatchGPULib.cpp:332-338 : rgb8 interleaved -> 3 planar f32
-__global__ void k_rgb_planes(const uint8_t *__restrict__ rgb, int stride, int W, int H, float *__restrict__ planes)
-{
-    int x = blockIdx.x * blockDim.x + threadIdx.x;
-    int y = blockIdx.y;
-    if (x >= W) return;
-    const uint8_t *p = rgb + (size_t)y * stride + 3 * x;
-    size_t n = (size_t)W * H, at = (size_t)y * W + x;
-    planes[at] = (float)p[0];
-    planes[n + at] = (float)p[1];
-    planes[2 * n + at] = (float)p[2];
-}
-
-// the other input layouts (InLayout, ugsm_device.hpp): each pixel as its conversion to rgb8 reads
+// MatchGPULib.cpp:332-338 : rgb8 interleaved -> 3 planar f32; every input layout (InLayout, ugsm_device.hpp) an instance, each pixel read
+// as its conversion to rgb8 reads
 template <int L>
 __global__ void k_rgb_planes(const uint8_t *__restrict__ rgb, int stride, int W, int H, float *__restrict__ planes)
 {
@@ -129,18 +117,9 @@ __global__ void k_rgb_planes(const uint8_t *__restrict__ rgb, int stride, int W,
 
 void launch_rgb_planes(hipStream_t st, const uint8_t *rgb, int stride, int W, int H, float *planes, int fmt)
 {
-    using Kern = void (*)(const uint8_t *, int, int, int, float *);
-    Kern kern = k_rgb_planes;
-    switch (input_layout(fmt, input_words_aligned(rgb, stride, nullptr))) {
-    case kInBGR8: kern = k_rgb_planes<kInBGR8>; break;
-    case kInRGBA8: kern = k_rgb_planes<kInRGBA8>; break;
-    case kInBGRA8: kern = k_rgb_planes<kInBGRA8>; break;
-    case kInMono8: kern = k_rgb_planes<kInMono8>; break;
-    case kInRGBA8Word: kern = k_rgb_planes<kInRGBA8Word>; break;
-    case kInBGRA8Word: kern = k_rgb_planes<kInBGRA8Word>; break;
-    default: break;
-    }
-    UGSM_LAUNCH(kern, grid2(W, H), dim3(256), 0, st, rgb, stride, W, H, planes);
+    with_layout(input_layout(fmt, input_words_aligned(rgb, stride, nullptr)), [&](auto layout) {
+        UGSM_LAUNCH(k_rgb_planes<decltype(layout)::value>, grid2(W, H), dim3(256), 0, st, rgb, stride, W, H, planes);
+    });
 }
 
 // =========================================================================================
@@ -292,8 +271,7 @@ constexpr int kCloudTR = 64;             // sampled rows per tile = lanes of a w
 constexpr int kCloudPad = kCloudTR + 1;  // records per column in LDS: column c starts 4c banks further on (phase A stores 32 columns at once)
 
 // X, Y, Z of pixel (ii, jj) of the planes, from the same operands as the plane forms (bit-identical to them); (x1, y1) the pixel in the
-// full-resolution frame.  The resized forms' producer.  (cloud_point below keeps its own statement of the same operands: routed through
-// this function, the point cloud forms compile to different instruction streams, and tools/isa_dump.py --diff holds them unchanged.)
+// full-resolution frame.
 template <bool Fovea>
 __device__ __forceinline__ void tri_at(const CloudArgs &a, const Proj &P1q, const Proj &P2q, int ii, int jj, float &x1, float &y1, float &X,
                                        float &Y, float &Z)
@@ -316,44 +294,30 @@ __device__ __forceinline__ void tri_at(const CloudArgs &a, const Proj &P1q, cons
     tri_point(x1, y1, x2, y2, P1q.m, P2q.m, X, Y, Z);
 }
 
+// The colour word of pixel cx of an image row in any input format (UGSM_INPUT_*; fmt is uniform): R << 16 | G << 8 | B of the pixel's
+// conversion to rgb8.  The three- and four-byte formats read bytes 0, 1, 2 at fixed offsets (two loads) and select the channel order.
+// Not a switch over the formats: that puts the colour loads and their waits ahead of the arithmetic, and the resized clouds' short
+// launches take up to a sixth longer.
+__device__ __forceinline__ unsigned colour_word(const uint8_t *row, int cx, int fmt)
+{
+    if (fmt == kInMono8) return (unsigned)row[cx] * 0x010101u;
+    const bool swap = fmt == kInBGR8 || fmt == kInBGRA8;
+    const uint8_t *p = row + (size_t)((fmt == kInRGBA8 || fmt == kInBGRA8) ? 4 : 3) * cx;
+    const unsigned c0 = p[0], c1 = p[1], c2 = p[2];
+    return (swap ? c2 : c0) << 16 | c1 << 8 | (swap ? c0 : c2);
+}
+
 // the colour word of full-resolution pixel (cx, cy); the foveated forms clamp it to the image (the reference reads whatever lies there):
 // at destination level 0 no fovea level's window leaves the image at 16 MP, 1080p, 640 x 480 or 160 x 120, so the clamp only acts on
 // margins a caller pushes past the edge
-// The colour word of pixel cx of an image row in any input format (UGSM_INPUT_*; fmt is uniform): R << 16 | G << 8 | B of the pixel's
-// conversion to rgb8.  The forms that take it are instances of their own: the rgb8 forms read as they always did.
-__device__ __forceinline__ unsigned colour_word(const uint8_t *row, int cx, int fmt)
-{
-    switch (fmt) {
-    case kInBGR8: {
-        const uint8_t *p = row + 3 * (size_t)cx;
-        return (unsigned)p[2] << 16 | (unsigned)p[1] << 8 | (unsigned)p[0];
-    }
-    case kInRGBA8: {
-        const uint8_t *p = row + 4 * (size_t)cx;
-        return (unsigned)p[0] << 16 | (unsigned)p[1] << 8 | (unsigned)p[2];
-    }
-    case kInBGRA8: {
-        const uint8_t *p = row + 4 * (size_t)cx;
-        return (unsigned)p[2] << 16 | (unsigned)p[1] << 8 | (unsigned)p[0];
-    }
-    case kInMono8: return (unsigned)row[cx] * 0x010101u;
-    default: {
-        const uint8_t *p = row + 3 * (size_t)cx;
-        return (unsigned)p[0] << 16 | (unsigned)p[1] << 8 | (unsigned)p[2];
-    }
-    }
-}
-
-template <bool Clamp, bool AnyFmt = false>
-__device__ __forceinline__ unsigned colour_at(const CloudArgs &a, int cx, int cy, int fmt = 0)
+template <bool Clamp>
+__device__ __forceinline__ unsigned colour_at(const CloudArgs &a, int cx, int cy)
 {
     if (Clamp) {
         cx = min(max(cx, 0), a.W - 1);
         cy = min(max(cy, 0), a.H - 1);
     }
-    if (AnyFmt) return colour_word(a.rgb + (size_t)cy * a.stride, cx, fmt);
-    const uint8_t *p = a.rgb + (size_t)cy * a.stride + 3 * (size_t)cx;
-    return (unsigned)p[0] << 16 | (unsigned)p[1] << 8 | (unsigned)p[2];
+    return colour_word(a.rgb + (size_t)cy * a.stride, cx, a.fmt);
 }
 
 // whether a compact cloud keeps a point of pixel `at` of the planes
@@ -366,43 +330,16 @@ __device__ __forceinline__ bool cloud_keep(const CloudArgs &a, size_t at, float 
 }
 
 // one sampled point: its record (x, y, z, rgb word as float bits) and whether a compact cloud keeps it
-template <bool Fovea, bool Colour, bool AnyFmt = false>
-__device__ __forceinline__ bool cloud_point(const CloudArgs &a, const Proj &P1q, const Proj &P2q, int ii, int jj, float4 &rec, int fmt = 0)
+template <bool Fovea, bool Colour>
+__device__ __forceinline__ bool cloud_point(const CloudArgs &a, const Proj &P1q, const Proj &P2q, int ii, int jj, float4 &rec)
 {
-    const size_t at = (size_t)jj * a.pw + ii;
-    float x1, y1, x2, y2;
-    int cx, cy;
-    if (Fovea) {  // as k_triangulate_fovea; the colour from the full-resolution image at ((int)mapXcoord(ii), (int)mapYcoord(jj)) (:630-640)
-        x1 = (float)a.left_margin + (float)ii * a.scale;
-        y1 = (float)a.upper_margin + (float)jj * a.scale;
-        const int sx = (int)(ii + a.dx[at]);
-        const int sy = (int)(jj + a.dy[at]);
-        x2 = (float)a.left_margin + (float)sx * a.scale;
-        y2 = (float)a.upper_margin + (float)sy * a.scale;
-        // clamped to the image (the reference reads whatever lies there): at destination level 0 no fovea level's window leaves the
-        // image at 16 MP, 1080p, 640 x 480 or 160 x 120, so the clamp only acts on margins a caller pushes past the edge
-        cx = min(max((int)x1, 0), a.W - 1);
-        cy = min(max((int)y1, 0), a.H - 1);
-    } else {      // as k_triangulate
-        x1 = ii;
-        y1 = jj;
-        x2 = ii + a.dx[at];
-        y2 = jj + a.dy[at];
-        cx = ii;
-        cy = jj;
+    float x1, y1, X, Y, Z;
+    tri_at<Fovea>(a, P1q, P2q, ii, jj, x1, y1, X, Y, Z);
+    if (Colour) {  // the foveated forms: at ((int)mapXcoord(ii), (int)mapYcoord(jj)) of the full-resolution image (:630-640), clamped (colour_at)
+        const int cx = Fovea ? min(max((int)x1, 0), a.W - 1) : ii, cy = Fovea ? min(max((int)y1, 0), a.H - 1) : jj;
+        rec = make_float4(X, Y, Z, __uint_as_float(colour_word(a.rgb + (size_t)cy * a.stride, cx, a.fmt)));
     }
-    float X, Y, Z;
-    tri_point(x1, y1, x2, y2, P1q.m, P2q.m, X, Y, Z);
-    if (Colour && AnyFmt) rec = make_float4(X, Y, Z, __uint_as_float(colour_word(a.rgb + (size_t)cy * a.stride, cx, fmt)));
-    if (Colour && !AnyFmt) {
-        const uint8_t *p = a.rgb + (size_t)cy * a.stride + 3 * (size_t)cx;
-        const unsigned word = (unsigned)p[0] << 16 | (unsigned)p[1] << 8 | (unsigned)p[2];
-        rec = make_float4(X, Y, Z, __uint_as_float(word));
-    }
-    if (!a.compact) return true;
-    bool keep = __builtin_isfinite(X) && __builtin_isfinite(Y) && __builtin_isfinite(Z) && Z >= a.z_min && Z <= a.z_max;
-    if (a.conf) keep = keep && a.conf[at] >= a.min_conf;  // (a NaN confidence fails the comparison)
-    return keep;
+    return cloud_keep(a, (size_t)jj * a.pw + ii, X, Y, Z);
 }
 
 // SURVEY 8f row f-1, the resized cloud: getPointCloud.cpp doReconstruction_resized (:724-800) / doReconstructionFOV_resized (:802-884),
@@ -433,15 +370,18 @@ __device__ __forceinline__ void cubic_tap(int d, double scale, int n, int &s, fl
     border = s < 1 || s + 2 >= n;
 }
 
-template <bool Fovea, bool Colour, bool AnyFmt = false>
+template <bool Fovea, bool Colour>
 __device__ __forceinline__ bool resized_point(const CloudArgs &a, const CloudResize &rz, const Proj &P1q, const Proj &P2q, int ii, int jj,
-                                              float4 &rec, int fmt = 0)
+                                              float4 &rec)
 {
     // (ii < (int)(pw * f) keeps ii / f below pw; the clamp never acts)
     const int xx = min((int)((float)ii / rz.factor), a.pw - 1);
     const int yy = min((int)((float)jj / rz.factor), a.ph - 1);
     float x1, y1, X, Y, Z;
     tri_at<Fovea>(a, P1q, P2q, xx, yy, x1, y1, X, Y, Z);
+    // the colour is read before the taps: its loads go out with the centre pixel's dx, dy, not one round trip after the taps
+    const bool mapped = Fovea && rz.colour_mapped;
+    const unsigned word = Colour ? colour_at<Fovea>(a, mapped ? (int)x1 : xx, mapped ? (int)y1 : yy) : 0u;
     if (!rz.same_size) {
         int sx, sy;
         float cx[4], cy[4];
@@ -464,16 +404,12 @@ __device__ __forceinline__ bool resized_point(const CloudArgs &a, const CloudRes
         }
         Z = v;
     }
-    if (Colour) {
-        const bool mapped = Fovea && rz.colour_mapped;
-        rec = make_float4(X, Y, Z, __uint_as_float(mapped ? colour_at<Fovea, AnyFmt>(a, (int)x1, (int)y1, fmt) : colour_at<Fovea, AnyFmt>(a, xx, yy, fmt)));
-    }
+    if (Colour) rec = make_float4(X, Y, Z, __uint_as_float(word));
     return cloud_keep(a, (size_t)yy * a.pw + xx, X, Y, Z);
 }
 
-// AnyFmt: the colour is read from an image in input format fmt (the rgb8 forms: AnyFmt false, their instruction streams unchanged)
-template <bool Fovea, int Form, bool AnyFmt = false>
-__device__ __forceinline__ void cloud_tile(const CloudArgs &a, const CloudResize &rz, const Proj &P1q, const Proj &P2q, int fmt = 0)
+template <bool Fovea, int Form>
+__device__ __forceinline__ void cloud_tile(const CloudArgs &a, const CloudResize &rz, const Proj &P1q, const Proj &P2q)
 {
     __shared__ float4 rec[kCloudTC * kCloudPad];
     __shared__ unsigned char kept[kCloudTC * kCloudTR];
@@ -493,9 +429,9 @@ __device__ __forceinline__ void cloud_tile(const CloudArgs &a, const CloudResize
         if (ci < a.wc && cj < a.hc) {
             float4 v;
             if constexpr (Form == kTriResizedCount || Form == kTriResized)
-                k = resized_point<Fovea, Write, AnyFmt>(a, rz, P1q, P2q, ci, cj, v, fmt);
+                k = resized_point<Fovea, Write>(a, rz, P1q, P2q, ci, cj, v);
             else
-                k = cloud_point<Fovea, Write, AnyFmt>(a, P1q, P2q, ci * a.s, cj * a.s, v, fmt);
+                k = cloud_point<Fovea, Write>(a, P1q, P2q, ci * a.s, cj * a.s, v);
             if (Write) rec[c * kCloudPad + r] = v;
         }
         kept[c * kCloudTR + r] = k;
@@ -557,81 +493,36 @@ __device__ __forceinline__ void cloud_tile(const CloudArgs &a, const CloudResize
     }
 }
 
-template <int Form>
-__global__ __launch_bounds__(256) void k_triangulate(CloudArgs a, Proj P1q, Proj P2q)
-{
-    static_assert(Form == kTriCloudCount || Form == kTriCloud, "the cloud forms");
-    cloud_tile<false, Form>(a, CloudResize{}, P1q, P2q);
-}
-template <int Form>
-__global__ __launch_bounds__(256) void k_triangulate_fovea(CloudArgs a, Proj P1q, Proj P2q)
-{
-    static_assert(Form == kTriCloudCount || Form == kTriCloud, "the cloud forms");
-    cloud_tile<true, Form>(a, CloudResize{}, P1q, P2q);
-}
-// (the resized forms take their own argument after the others, so that the cloud forms' arguments lie where they did)
+// the cloud forms; rz: the resized forms' (unused by the others)
 template <int Form>
 __global__ __launch_bounds__(256) void k_triangulate(CloudArgs a, Proj P1q, Proj P2q, CloudResize rz)
 {
-    static_assert(Form == kTriResizedCount || Form == kTriResized, "the resized cloud forms");
+    static_assert(Form != kTriPlanes, "the cloud forms");
     cloud_tile<false, Form>(a, rz, P1q, P2q);
 }
 template <int Form>
 __global__ __launch_bounds__(256) void k_triangulate_fovea(CloudArgs a, Proj P1q, Proj P2q, CloudResize rz)
 {
-    static_assert(Form == kTriResizedCount || Form == kTriResized, "the resized cloud forms");
+    static_assert(Form != kTriPlanes, "the cloud forms");
     cloud_tile<true, Form>(a, rz, P1q, P2q);
-}
-
-// The cloud launches of an image in another input format than rgb8 (fmt, uniform): one instance per cloud form, the colour read with a
-// switch on fmt (the count launches read no colour and are shared)
-template <int Form>
-__global__ __launch_bounds__(256) void k_triangulate(CloudArgs a, Proj P1q, Proj P2q, CloudResize rz, int fmt)
-{
-    static_assert(Form == kTriCloud || Form == kTriResized, "the cloud forms that read colour");
-    cloud_tile<false, Form, true>(a, rz, P1q, P2q, fmt);
-}
-template <int Form>
-__global__ __launch_bounds__(256) void k_triangulate_fovea(CloudArgs a, Proj P1q, Proj P2q, CloudResize rz, int fmt)
-{
-    static_assert(Form == kTriCloud || Form == kTriResized, "the cloud forms that read colour");
-    cloud_tile<true, Form, true>(a, rz, P1q, P2q, fmt);
 }
 
 int cloud_strips(int wc) { return (wc + kCloudTC - 1) / kCloudTC; }
 int cloud_chunks(int hc) { return (hc + kCloudTR - 1) / kCloudTR; }
 
-void launch_point_cloud(hipStream_t st, const CloudArgs &args, bool fovea, const double *P1, const double *P2, const CloudResize *rz, int fmt)
+void launch_point_cloud(hipStream_t st, const CloudArgs &args, bool fovea, const double *P1, const double *P2, const CloudResize *rz)
 {
     Proj a, b;
     for (int k = 0; k < 12; k++) { a.m[k] = P1[k]; b.m[k] = P2[k]; }
+    using Kern = void (*)(CloudArgs, Proj, Proj, CloudResize);
+    const Kern count = rz ? (fovea ? (Kern)k_triangulate_fovea<kTriResizedCount> : (Kern)k_triangulate<kTriResizedCount>)
+                          : (fovea ? (Kern)k_triangulate_fovea<kTriCloudCount> : (Kern)k_triangulate<kTriCloudCount>);
+    const Kern cloud = rz ? (fovea ? (Kern)k_triangulate_fovea<kTriResized> : (Kern)k_triangulate<kTriResized>)
+                          : (fovea ? (Kern)k_triangulate_fovea<kTriCloud> : (Kern)k_triangulate<kTriCloud>);
     const dim3 grid(cloud_strips(args.wc), args.nchunk);
-    if (fmt != kInRGB8) {
-        using Kern3 = void (*)(CloudArgs, Proj, Proj);
-        using Kern4 = void (*)(CloudArgs, Proj, Proj, CloudResize);
-        using Kern5 = void (*)(CloudArgs, Proj, Proj, CloudResize, int);
-        if (args.compact) {
-            if (rz) UGSM_LAUNCH(fovea ? (Kern4)k_triangulate_fovea<kTriResizedCount> : (Kern4)k_triangulate<kTriResizedCount>, grid, dim3(256), 0, st, args, a, b, *rz);
-            else UGSM_LAUNCH(fovea ? (Kern3)k_triangulate_fovea<kTriCloudCount> : (Kern3)k_triangulate<kTriCloudCount>, grid, dim3(256), 0, st, args, a, b);
-        }
-        const Kern5 cloud = rz ? (fovea ? (Kern5)k_triangulate_fovea<kTriResized> : (Kern5)k_triangulate<kTriResized>)
-                               : (fovea ? (Kern5)k_triangulate_fovea<kTriCloud> : (Kern5)k_triangulate<kTriCloud>);
-        UGSM_LAUNCH(cloud, grid, dim3(256), 0, st, args, a, b, rz ? *rz : CloudResize{}, fmt);
-        return;
-    }
-    if (rz) {
-        using Kern = void (*)(CloudArgs, Proj, Proj, CloudResize);
-        const Kern count = fovea ? (Kern)k_triangulate_fovea<kTriResizedCount> : (Kern)k_triangulate<kTriResizedCount>;
-        const Kern cloud = fovea ? (Kern)k_triangulate_fovea<kTriResized> : (Kern)k_triangulate<kTriResized>;
-        if (args.compact) UGSM_LAUNCH(count, grid, dim3(256), 0, st, args, a, b, *rz);
-        UGSM_LAUNCH(cloud, grid, dim3(256), 0, st, args, a, b, *rz);
-        return;
-    }
-    using Kern = void (*)(CloudArgs, Proj, Proj);
-    const Kern count = fovea ? (Kern)k_triangulate_fovea<kTriCloudCount> : (Kern)k_triangulate<kTriCloudCount>;
-    const Kern cloud = fovea ? (Kern)k_triangulate_fovea<kTriCloud> : (Kern)k_triangulate<kTriCloud>;
-    if (args.compact) UGSM_LAUNCH(count, grid, dim3(256), 0, st, args, a, b);
-    UGSM_LAUNCH(cloud, grid, dim3(256), 0, st, args, a, b);
+    const CloudResize r = rz ? *rz : CloudResize{};
+    if (args.compact) UGSM_LAUNCH(count, grid, dim3(256), 0, st, args, a, b, r);
+    UGSM_LAUNCH(cloud, grid, dim3(256), 0, st, args, a, b, r);
 }
 
 // =========================================================================================

@@ -240,156 +240,15 @@ __global__ __launch_bounds__(256) void k_sqblur_tiled(Img3 src, int W, int H, fl
 // the 84 candidate columns of the two levels, and a third of the LDS instructions); only the column pass runs at the sampled
 // sites: waves 0-2 own the 52 candidate columns of level 1 (one row phase each), wave 3 the 32 columns of level 2 (two rows at a
 // time), so that an output row segment is written by the lanes of one wave.  Level 0 leaves as 16-byte stores.
+// Every input layout (InLayout, ugsm_device.hpp) is an instance, rgb8 the instance L = kInRGB8: a pixel reads as its conversion to rgb8
+// reads.  The channels are independent all the way, so a mono8 image runs ONE channel's passes and stores that channel to the three planes:
+// bit for bit the rgb8 result of (v, v, v), for a third of the LDS and VALU work.
 constexpr int BTX = 64, BTY = 16, BRW = BTX + 8, BRH = BTY + 4, BC1 = 52, BR1 = 16, BC2 = 32, BR2 = 8;
+template <int L>
 __global__ __launch_bounds__(256) void k_pyr_base(const uint8_t *__restrict__ rgb, int stride, int W, int H, float *__restrict__ lvl0,
                                                   float *__restrict__ lvl1, int W1, int H1, float *__restrict__ lvl2, int W2, int H2,
                                                   unsigned *__restrict__ range_bad, int tiles_x, int n_tiles, Batch bt, PyrWindow win)
 {
-    if (bt.n > 1) {  // this workgroup's image of the batch (blockIdx.y): its rgb8 input, its three levels (one offset: they lie in one pyramid)
-        const int b = (int)blockIdx.y;
-        rgb = shifted(rgb, bt.img[b]);
-        lvl0 = shifted(lvl0, bt.out[b]);
-        lvl1 = shifted(lvl1, bt.out[b]);
-        lvl2 = shifted(lvl2, bt.out[b]);
-        if (range_bad) range_bad += bt.cx[b];  // (the pair the image belongs to)
-        win.x0 = (int)(bt.in[b] & 0xffffffffll);  // (its fovea window's origin rides in the otherwise unused input-field offset)
-        win.y0 = (int)(bt.in[b] >> 32);
-    }
-    __shared__ __attribute__((aligned(16))) float sS[3][BRH * BRW];  // tile + halo 2: region column c at [c], rows 16-byte aligned
-    __shared__ __attribute__((aligned(16))) float sT[3][BRH * BTX];  // row pass of every tile column, every region row
-    __shared__ int sRowSite[BR1 + BR2];  // region row of the sampling site of candidate row ly (level 1, then level 2), -1 = not in this tile
-    const int tid = threadIdx.x;
-    int tile_x, tile_y;
-    xcd_tile(n_tiles, tiles_x, tile_x, tile_y);  // neighbouring tiles share an XCD's L2 (halo lines, partially written output lines)
-    const int x0 = tile_x * BTX, y0 = tile_y * BTY;
-    const float sf1 = (float)1.41421356, sf2 = 2.0f;
-    {   // rgb8 -> float planes of tile + halo 2, zero outside the image (the blur's zero padding, U2/U3)
-        constexpr int RW = BTX + 4;
-        constexpr int NLD = (BRH * RW + 255) / 256;
-        float v[NLD][3];
-#pragma unroll
-        for (int u = 0; u < NLD; u++) {
-            const int it = min(tid + u * 256, BRH * RW - 1);
-            const int r = it / RW, c = it - r * RW;
-            const int gx = x0 - 2 + c, gy = y0 - 2 + r;
-            const bool in = gx >= 0 && gx < W && gy >= 0 && gy < H;
-            const uint8_t *p = rgb + (size_t)min(max(gy, 0), H - 1) * stride + 3 * min(max(gx, 0), W - 1);
-            const float a = (float)p[0], b = (float)p[1], c2 = (float)p[2];
-            v[u][0] = in ? a : 0.0f;
-            v[u][1] = in ? b : 0.0f;
-            v[u][2] = in ? c2 : 0.0f;
-        }
-#pragma unroll
-        for (int u = 0; u < NLD; u++) {
-            const int it = tid + u * 256;
-            if (it < BRH * RW) {
-                const int r = it / RW, c = it - r * RW;
-                sS[0][r * BRW + c] = v[u][0];
-                sS[1][r * BRW + c] = v[u][1];
-                sS[2][r * BRW + c] = v[u][2];
-            }
-        }
-    }
-    // candidate outputs of this tile: columns i = ib + lx, rows j = jb + ly; valid when the sampling site lies in the tile.
-    // Level 1: the sites in a 64-wide tile are at most 46 consecutive i starting 1..3 above ib1 (52 candidates cover a
-    // rounding slip of the float quotient); at most 12 rows, 16 candidates.  Level 2: site = 2i+1, exactly 32 x 8.
-    const int ib1 = max((int)((float)x0 / sf1) - 1, 0), jb1 = max((int)((float)y0 / sf1) - 1, 0);
-    const int ib2 = x0 / 2, jb2 = y0 / 2;
-    if (tid < BR1 + BR2) {
-        const bool o1 = tid < BR1;
-        const int j = (o1 ? jb1 : jb2) + (o1 ? tid : tid - BR1);
-        int site = -1;
-        if (j < (o1 ? H1 : H2)) {
-            const int sy = tex_index(((float)j + 0.5f) * (o1 ? sf1 : sf2), H);
-            if (sy >= y0 && sy < y0 + BTY) site = sy - (y0 - 2);
-        }
-        sRowSite[tid] = site;
-    }
-    __syncthreads();
-    // Foveated calls (win.w > 0) read level 0 only inside the fovea window (CreateFoveatedPyramid crops after a full build,
-    // MatchGPULib.cpp:1128-1190; here the crop is a view, and what no view covers need not exist): the tiles that do not touch the
-    // window skip their level-0 store -- 193 MB of the 338 MB this kernel writes per 16 MP image.  Levels 1 and 2 are written whole:
-    // levels 3 and 4 are made from them.
-    const bool store0 = win.w <= 0 || (x0 < win.x0 + win.w && x0 + BTX > win.x0 && y0 < win.y0 + win.h && y0 + BTY > win.y0);
-    if (store0) {  // level 0: the tile itself; a thread owns 4 consecutive pixels of one row
-        const size_t n = (size_t)W * H;
-        const int r = tid >> 4, c = (tid & 15) * 4;
-        const int gx = x0 + c, gy = y0 + r;
-        if (gy < H && gx < W) {
-            const size_t at = (size_t)gy * W + gx;
-#pragma unroll
-            for (int k = 0; k < 3; k++) {
-                float q[4];
-                ld2(&sS[k][(r + 2) * BRW + c + 2], q);
-                ld2(&sS[k][(r + 2) * BRW + c + 4], q + 2);
-                if ((W & 3) == 0) {  // (then gx + 3 < W, and every plane row starts 16-byte aligned)
-                    *reinterpret_cast<float4 *>(lvl0 + k * n + at) = make_float4(q[0], q[1], q[2], q[3]);
-                } else {
-                    for (int i = 0; i < 4; i++)
-                        if (gx + i < W) lvl0[k * n + at + i] = q[i];
-                }
-            }
-        }
-    }
-    // row pass, dense: tile columns 4q .. 4q+3 of region row r from region columns 4q .. 4q+7 (level-0 values are >= 0: tap5p = tap5
-    // without its "0 +")
-    for (int it = tid; it < 3 * BRH * (BTX / 4); it += 256) {
-        const int k = it / (BRH * (BTX / 4)), rem = it - k * (BRH * (BTX / 4));
-        const int r = rem / (BTX / 4), q = rem - r * (BTX / 4);
-        float p[8], o[4];
-        ld4(&sS[k][r * BRW + 4 * q], p);
-        ld4(&sS[k][r * BRW + 4 * q + 4], p + 4);
-#pragma unroll
-        for (int i = 0; i < 4; i++) o[i] = tap5p(p[i], p[i + 1], p[i + 2], p[i + 3], p[i + 4]);
-        st4(&sT[k][r * BTX + 4 * q], o);
-    }
-    __syncthreads();
-    // column pass at the sampled sites (level 0 holds the integers 0..255: always inside range_ok; levels 1 and 2 are checked)
-    const int wave = tid >> 6, lane = tid & 63;
-    const bool one = wave < 3;
-    static_assert(BC1 <= 64 && 2 * BC2 == 64, "waves 0-2: one level-1 row per step; wave 3: two level-2 rows per step");
-    const int lx = one ? lane : (lane % BC2);
-    const int phase = one ? wave : (lane / BC2), nphase = one ? 3 : 2;
-    const int ci = (one ? ib1 : ib2) + lx;
-    int tcol = -1;  // tile column of this candidate column's sampling site, -1 = not in this tile
-    if ((!one || lane < BC1) && ci < (one ? W1 : W2)) {
-        const int site = tex_index(((float)ci + 0.5f) * (one ? sf1 : sf2), W);
-        if (site >= x0 && site < x0 + BTX) tcol = site - x0;
-    }
-    bool bad = false;
-    if (tcol >= 0) {
-        float *const dst = one ? lvl1 : lvl2;
-        const int Wd = one ? W1 : W2;
-        const size_t nd = (size_t)Wd * (one ? H1 : H2);
-        const int nrow = one ? BR1 : BR2, jb = one ? jb1 : jb2, tb = one ? 0 : BR1;
-        for (int ly = phase; ly < nrow; ly += nphase) {
-            const int cy = sRowSite[tb + ly];
-            if (cy >= 0) {
-                const size_t at = (size_t)(jb + ly) * Wd + ci;
-#pragma unroll
-                for (int k = 0; k < 3; k++) {
-                    const float *p = &sT[k][cy * BTX + tcol];
-                    const float v = tap5p(p[-2 * BTX], p[-BTX], p[0], p[BTX], p[2 * BTX]);
-                    dst[k * nd + at] = v;
-                    bad |= !range_ok(v);
-                }
-            }
-        }
-    }
-    if (bad && range_bad) *range_bad = 1u;
-}
-
-// The other input layouts (InLayout, ugsm_device.hpp): the same kernel, every pixel read as the rgb8 form reads the pixel's conversion to
-// rgb8.  The channels are independent all the way, so a mono8 image runs ONE channel's passes and stores that channel to the three planes:
-// bit for bit the rgb8 result of (v, v, v), for a third of the LDS and VALU work.  (The rgb8 form above keeps its own statement: as this
-// template's instance it compiles to a different, equivalent instruction stream, and tools/isa_dump.py --diff holds it unchanged.  A change
-// to the base pass is made in both copies, and in k_pyr_base_march's two as well: DESIGN.md section 4.4.)
-template <int L>
-__global__ __launch_bounds__(256) void k_pyr_base(const uint8_t *__restrict__ rgb, int stride, int W, int H, float *__restrict__ lvl0,
-                                              float *__restrict__ lvl1, int W1, int H1, float *__restrict__ lvl2, int W2, int H2,
-                                              unsigned *__restrict__ range_bad, int tiles_x, int n_tiles, Batch bt, PyrWindow win)
-{
-    static_assert(L != kInRGB8, "the rgb8 form is the kernel above");
     constexpr int NC = InPix<L>::channels, NP = 3 / NC;  // channels computed; planes each one is stored to
     if (bt.n > 1) {  // this workgroup's image of the batch (blockIdx.y): its rgb8 input, its three levels (one offset: they lie in one pyramid)
         const int b = (int)blockIdx.y;
@@ -546,119 +405,12 @@ __device__ __forceinline__ int pyr_site_index(const int pos, const float sf, con
     }
     return -1;
 }
-template <int HS>
+// Every input layout an instance, as k_pyr_base's (a mono8 lane runs one channel's chains and stores it to the three planes)
+template <int HS, int L>
 __global__ __launch_bounds__(256) void k_pyr_base_march(const uint8_t *__restrict__ rgb, int stride, int W, int H, float *__restrict__ lvl0,
                                                         float *__restrict__ lvl1, int W1, int H1, float *__restrict__ lvl2, int W2, int H2,
                                                         unsigned *__restrict__ range_bad, int strips_x, int n_strips, Batch bt, PyrWindow win)
 {
-    if (bt.n > 1) {  // this workgroup's image of the batch (blockIdx.y)
-        const int b = (int)blockIdx.y;
-        rgb = shifted(rgb, bt.img[b]);
-        lvl0 = shifted(lvl0, bt.out[b]);
-        lvl1 = shifted(lvl1, bt.out[b]);
-        lvl2 = shifted(lvl2, bt.out[b]);
-        if (range_bad) range_bad += bt.cx[b];
-        win.x0 = (int)(bt.in[b] & 0xffffffffll);
-        win.y0 = (int)(bt.in[b] >> 32);
-    }
-    constexpr int VXS = 60;
-    const int wv = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6);
-    if (wv >= n_strips) return;
-    const int sy = wv / strips_x, sx = wv - sy * strips_x;
-    const int lane = threadIdx.x & 63;
-    const int pc = sx * VXS - 2 + lane;        // the column whose pixel this lane holds
-    const int cc = pc - 2;                     // ... and the column whose row-pass window is complete in this lane
-    const int y0 = sy * HS;
-    const int y1 = min(y0 + HS, H);            // centre rows y0 .. y1 - 1
-    const float sf1 = (float)1.41421356, sf2 = 2.0f;
-    const bool cin = pc >= 0 && pc < W;
-    const bool own = lane >= 2 && lane < 2 + VXS && pc < W;  // columns sx * 60 .. + 59: this lane stores their level-0 pixels
-    const bool centre = lane >= 4 && cc < W;   // lanes 4 .. 63 hold the windows of columns sx * 60 .. + 59
-    const int i1 = centre ? pyr_site_index(cc, sf1, W, W1) : -1;
-    const int i2 = (centre && (cc & 1) && (cc >> 1) < W2 && tex_index(((float)(cc >> 1) + 0.5f) * sf2, W) == cc) ? (cc >> 1) : -1;
-    // level 0 is stored where the call reads it: everywhere (win.w <= 0) or in the strips that touch the fovea window
-    const bool store0 = win.w <= 0 || (sx * VXS < win.x0 + win.w && sx * VXS + VXS > win.x0 && y0 < win.y0 + win.h && y1 > win.y0);
-    const size_t n0 = (size_t)W * H, n1 = (size_t)W1 * H1, n2 = (size_t)W2 * H2;
-    const uint8_t *const col = rgb + 3 * (size_t)clampi(pc, 0, W - 1);
-    auto load = [&](const int y, unsigned (&b)[3]) {
-        const uint8_t *p = col + (size_t)clampi(y, 0, H - 1) * stride;
-        b[0] = p[0];
-        b[1] = p[1];
-        b[2] = p[2];
-    };
-    float w[3][5];
-#pragma unroll
-    for (int k = 0; k < 3; k++)
-#pragma unroll
-        for (int u = 0; u < 5; u++) w[k][u] = 0.0f;
-    bool bad = false;
-    unsigned bcur[3], bnx1[3], bnx2[3];
-    load(y0 - 2, bcur);
-    load(y0 - 1, bnx1);
-    // the next level-1 row whose sampling site lies at or below y0, and that site (the sites increase strictly: a row is the site of one j at most)
-    int jn = max((int)((float)y0 / sf1) - 2, 0);
-    int sn = tex_index(((float)jn + 0.5f) * sf1, H);
-    while (sn < y0 && jn < H1) {
-        jn++;
-        sn = tex_index(((float)jn + 0.5f) * sf1, H);
-    }
-    for (int y = y0 - 2; y < y1 + 2; y++) {
-        load(y + 2, bnx2);  // two rows ahead of the arithmetic
-        const bool yin = y >= 0 && y < H;
-        const int cr = y - 2;  // the row whose column window is complete once row y is in
-        // (wave-uniform) is cr a sampling row of level 1 / level 2?
-        int j1 = -1;
-        if (cr >= y0 && cr < y1 && jn < H1 && cr == sn) {
-            j1 = jn;
-            jn++;
-            sn = tex_index(((float)jn + 0.5f) * sf1, H);
-        }
-        const int j2 = (cr >= y0 && cr < y1 && (cr & 1) && (cr >> 1) < H2) ? (cr >> 1) : -1;
-#pragma unroll
-        for (int k = 0; k < 3; k++) {
-            const float v = (cin && yin) ? (float)bcur[k] : 0.0f;  // zero padding (U2/U3)
-            if (store0 && own && y >= y0 && y < y1) lvl0[k * n0 + (size_t)y * W + pc] = v;
-            // row pass (level-0 values are >= 0: tap5p = tap5 without its "0 +"), the partial sum travels one lane to the right per tap
-            const float a0 = v * UGSM_G0, a1 = v * UGSM_G1, a2 = v * UGSM_G2;
-            const float p2 = lane_below(a0) + a1;
-            const float p3 = lane_below(p2) + a2;
-            const float p4 = lane_below(p3) + a1;
-            w[k][0] = w[k][1];
-            w[k][1] = w[k][2];
-            w[k][2] = w[k][3];
-            w[k][3] = w[k][4];
-            w[k][4] = lane_below(p4) + a0;
-        }
-        if (j1 >= 0 || j2 >= 0) {
-#pragma unroll
-            for (int k = 0; k < 3; k++) {
-                const float o = tap5p(w[k][0], w[k][1], w[k][2], w[k][3], w[k][4]);
-                if (j1 >= 0 && i1 >= 0) {
-                    lvl1[k * n1 + (size_t)j1 * W1 + i1] = o;
-                    bad |= !range_ok(o);
-                }
-                if (j2 >= 0 && i2 >= 0) {
-                    lvl2[k * n2 + (size_t)j2 * W2 + i2] = o;
-                    bad |= !range_ok(o);
-                }
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < 3; k++) {
-            bcur[k] = bnx1[k];
-            bnx1[k] = bnx2[k];
-        }
-    }
-    if (bad && range_bad) *range_bad = 1u;
-}
-// The other input layouts, as k_pyr_base's (a mono8 lane runs one channel's chains and stores it to the three planes; the rgb8 form above
-// keeps its own statement for the same reason)
-template <int HS, int L>
-__global__ __launch_bounds__(256) void k_pyr_base_march(const uint8_t *__restrict__ rgb, int stride, int W, int H, float *__restrict__ lvl0,
-                                               float *__restrict__ lvl1, int W1, int H1, float *__restrict__ lvl2, int W2, int H2,
-                                               unsigned *__restrict__ range_bad, int strips_x, int n_strips, Batch bt, PyrWindow win)
-{
-    static_assert(L != kInRGB8, "the rgb8 form is the kernel above");
     constexpr int NC = InPix<L>::channels, NP = 3 / NC;  // channels computed; planes each one is stored to
     if (bt.n > 1) {  // this workgroup's image of the batch (blockIdx.y)
         const int b = (int)blockIdx.y;
@@ -761,23 +513,6 @@ __global__ __launch_bounds__(256) void k_pyr_base_march(const uint8_t *__restric
 }
 int pyr_base_streaming = 1;  // (development: UGSM_PYR_BASE_STREAM=0 -> the LDS-tiled k_pyr_base)
 
-// the other input layouts: the same launches of the layout's instances
-template <int L>
-void launch_pyr_base_as(hipStream_t st, const uint8_t *rgb, int stride, int W, int H, float *lvl0, float *lvl1, int W1, int H1, float *lvl2, int W2,
-                        int H2, unsigned *range_bad, const Batch &B, PyrWindow win)
-{
-    if ((pyr_base_streaming == 1 && win.w > 0) || pyr_base_streaming == 2) {
-        constexpr int HS = 32;
-        const int strips_x = (W + 59) / 60, n_strips = strips_x * ((H + HS - 1) / HS);
-        UGSM_LAUNCH((k_pyr_base_march<HS, L>), dim3((n_strips + 3) / 4, B.n > 1 ? B.n : 1), dim3(256), 0, st, rgb, stride, W, H, lvl0, lvl1, W1, H1, lvl2,
-                    W2, H2, range_bad, strips_x, n_strips, B, win);
-        return;
-    }
-    const int tiles_x = (W + BTX - 1) / BTX, n_tiles = tiles_x * ((H + BTY - 1) / BTY);
-    UGSM_LAUNCH(k_pyr_base<L>, dim3(n_tiles, B.n > 1 ? B.n : 1), dim3(256), 0, st, rgb, stride, W, H, lvl0, lvl1, W1, H1, lvl2, W2, H2, range_bad, tiles_x,
-                n_tiles, B, win);
-}
-
 bool input_words_aligned(const uint8_t *rgb, int stride, const Batch *bt)
 {
     unsigned long long bits = reinterpret_cast<unsigned long long>(rgb) | (unsigned long long)stride;
@@ -792,30 +527,23 @@ void launch_pyr_base(hipStream_t st, const uint8_t *rgb, int stride, int W, int 
     Batch one{};
     one.n = 1;
     const Batch &B = bt ? *bt : one;
-    switch (input_layout(fmt, input_words_aligned(rgb, stride, bt))) {
-    case kInRGB8: break;  // (below, as it always was)
-    case kInBGR8: return launch_pyr_base_as<kInBGR8>(st, rgb, stride, W, H, lvl0, lvl1, W1, H1, lvl2, W2, H2, range_bad, B, win);
-    case kInRGBA8: return launch_pyr_base_as<kInRGBA8>(st, rgb, stride, W, H, lvl0, lvl1, W1, H1, lvl2, W2, H2, range_bad, B, win);
-    case kInBGRA8: return launch_pyr_base_as<kInBGRA8>(st, rgb, stride, W, H, lvl0, lvl1, W1, H1, lvl2, W2, H2, range_bad, B, win);
-    case kInMono8: return launch_pyr_base_as<kInMono8>(st, rgb, stride, W, H, lvl0, lvl1, W1, H1, lvl2, W2, H2, range_bad, B, win);
-    case kInRGBA8Word: return launch_pyr_base_as<kInRGBA8Word>(st, rgb, stride, W, H, lvl0, lvl1, W1, H1, lvl2, W2, H2, range_bad, B, win);
-    case kInBGRA8Word: return launch_pyr_base_as<kInBGRA8Word>(st, rgb, stride, W, H, lvl0, lvl1, W1, H1, lvl2, W2, H2, range_bad, B, win);
-    }
     // Streaming form for the foveated calls only (win.w > 0: level 0 is stored in the window's strips alone).  Where level 0 is written
     // whole -- 193 of 338 MB per 16 MP image -- the tiled kernel's aligned 16-byte stores win: 132 against 151 us per image, 16 MP full mode
     // 183.7 against 179.4 pairs/s; foveated batches 880 -> 903 pairs/s with it (tools/ab.py, same box).  UGSM_PYR_BASE_STREAM=2: everywhere.
-    if ((pyr_base_streaming == 1 && win.w > 0) || pyr_base_streaming == 2) {
-        constexpr int HS = 32;
-        const int strips_x = (W + 59) / 60, n_strips = strips_x * ((H + HS - 1) / HS);
-        void (*const kern)(const uint8_t *, int, int, int, float *, float *, int, int, float *, int, int, unsigned *, int, int, Batch, PyrWindow) =
-            k_pyr_base_march<HS>;
-        UGSM_LAUNCH(kern, dim3((n_strips + 3) / 4, B.n > 1 ? B.n : 1), dim3(256), 0, st, rgb, stride, W, H, lvl0, lvl1, W1, H1, lvl2, W2,
-                           H2, range_bad, strips_x, n_strips, B, win);
-        return;
-    }
-    const int tiles_x = (W + BTX - 1) / BTX, n_tiles = tiles_x * ((H + BTY - 1) / BTY);
-    void (*const kern)(const uint8_t *, int, int, int, float *, float *, int, int, float *, int, int, unsigned *, int, int, Batch, PyrWindow) = k_pyr_base;
-    UGSM_LAUNCH(kern, dim3(n_tiles, B.n > 1 ? B.n : 1), dim3(256), 0, st, rgb, stride, W, H, lvl0, lvl1, W1, H1, lvl2, W2, H2, range_bad, tiles_x, n_tiles, B, win);
+    const bool streaming = (pyr_base_streaming == 1 && win.w > 0) || pyr_base_streaming == 2;
+    with_layout(input_layout(fmt, input_words_aligned(rgb, stride, bt)), [&](auto layout) {
+        constexpr int L = decltype(layout)::value;
+        if (streaming) {
+            constexpr int HS = 32;
+            const int strips_x = (W + 59) / 60, n_strips = strips_x * ((H + HS - 1) / HS);
+            UGSM_LAUNCH((k_pyr_base_march<HS, L>), dim3((n_strips + 3) / 4, B.n > 1 ? B.n : 1), dim3(256), 0, st, rgb, stride, W, H, lvl0, lvl1, W1, H1,
+                        lvl2, W2, H2, range_bad, strips_x, n_strips, B, win);
+        } else {
+            const int tiles_x = (W + BTX - 1) / BTX, n_tiles = tiles_x * ((H + BTY - 1) / BTY);
+            UGSM_LAUNCH(k_pyr_base<L>, dim3(n_tiles, B.n > 1 ? B.n : 1), dim3(256), 0, st, rgb, stride, W, H, lvl0, lvl1, W1, H1, lvl2, W2, H2,
+                        range_bad, tiles_x, n_tiles, B, win);
+        }
+    });
 }
 
 int blur_decimate_streaming = 1;  // (development: UGSM_PYR_STREAM=0 -> the tiled kernel for the factor-2 levels too)

@@ -72,13 +72,14 @@ void launch_triangulate_fovea(hipStream_t st, const float *stackx, const float *
 struct CloudArgs {
     const float *dx, *dy, *conf;  // pw x ph row-major planes (the fovea form: level src_level of the stacks); conf may be null
     int pw, ph;
-    const uint8_t *rgb;           // the left image, W x H, `stride` bytes per row (rgb8, or the format launch_point_cloud is given)
+    const uint8_t *rgb;           // the left image, W x H, `stride` bytes per row, in input format fmt
     int W, H, stride;
     int s, wc, hc, nchunk;        // sampling; the sampled grid; cloud_chunks(hc)
     int format, compact;          // UGSM_CLOUD_PCL32 (0) / UGSM_CLOUD_XYZRGB16 (1); compact: only the points that pass the filter
     float min_conf, z_min, z_max;
     int left_margin, upper_margin;  // the fovea form: mapXcoord / mapYcoord (ugsm_fovea_mapping)
     float scale;
+    int fmt;        // the input format of rgb (UGSM_INPUT_*)
     unsigned *cnt;  // compact: wc * nchunk counts, wc column totals, cloud_strips(wc) strip totals; the totals zeroed before the launch
     void *points;   // 16-byte aligned
     long long cap;
@@ -94,9 +95,8 @@ struct CloudResize {
 };
 int cloud_strips(int wc);
 int cloud_chunks(int hc);
-// compact: a count launch, then the cloud launch; dense: the cloud launch.  rz: the resized forms; fmt: the input format of args.rgb (UGSM_INPUT_*)
-void launch_point_cloud(hipStream_t st, const CloudArgs &args, bool fovea, const double *P1, const double *P2, const CloudResize *rz = nullptr,
-                        int fmt = 0);
+// compact: a count launch, then the cloud launch; dense: the cloud launch.  rz: the resized forms
+void launch_point_cloud(hipStream_t st, const CloudArgs &args, bool fovea, const double *P1, const double *P2, const CloudResize *rz = nullptr);
 void launch_upsample_paste(hipStream_t st, const float *src3, int W, int H, float *dst3, int W2, int H2, const float *fovH_, const float *fovV_,
                            const float *fovC_, int fovW, int fovH, int org_x, int org_y);
 // S_dx, S_dy, C of weightedDifference (MatchGPULib.cpp:1336-1437) into out3; rowsum = 3*H doubles of scratch

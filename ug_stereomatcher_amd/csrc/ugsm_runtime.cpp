@@ -2467,6 +2467,7 @@ int point_cloud(ugsm_ctx *ctx, int slot, CloudArgs &a, bool fovea, const double 
         a.hc = (a.ph + a.s - 1) / a.s;
     }
     a.nchunk = cloud_chunks(a.hc);
+    a.fmt = ctx->hooks.input_format;
     a.cnt = nullptr;
     if (a.compact) {
         const size_t totals = (size_t)a.wc + (size_t)cloud_strips(a.wc), need = (size_t)a.wc * a.nchunk + totals;
@@ -2477,7 +2478,7 @@ int point_cloud(ugsm_ctx *ctx, int slot, CloudArgs &a, bool fovea, const double 
     }
     {
         Timer t(ctx, s, slot, KC_MISC, (double)a.wc * a.hc);
-        launch_point_cloud(s->st, a, fovea, P1, P2, rz, ctx->hooks.input_format);
+        launch_point_cloud(s->st, a, fovea, P1, P2, rz);
     }
     HIPCHK(ctx, hipGetLastError());
     return UGSM_OK;
