@@ -27,6 +27,44 @@ namespace ugsm {
 // What was measured and not kept -- a pipelined form with LDS-DMA prefetch, a marching form, the products v * kappa kept in LDS, the
 // box's row pass fused into the last pass, binary32 Newton quotients, three workgroups per CU: docs/HISTORY.md, profiles/r04_* / r05_kbench_smooth_*.
 constexpr int smooth_pad(int stx) { return stx == 112 ? 0 : 4; }  // floats added to an LDS row (rows stay 16-byte aligned)
+constexpr int kSmoothMaxPasses = 5;  // passes of one launch (the callers split longer iterations)
+// A quad (four consecutive floats of a row) moves as ONE 16-byte global access.  Rows are 16-byte aligned only when the level's width is a
+// multiple of four (16 MP: levels 0 and 1); on the other levels the same access is made at 4-byte alignment (gfx950's global accesses
+// need dword alignment only).  Timed both ways on 16 MP's level 2 (2463 x 1631, tools/kbench mode 5, same box, alternating; five passes /
+// five passes + box, medians of six): 16-byte accesses at 4-byte alignment 48.0 / 57.8 us, four 4-byte accesses per quad 52.7 / 61.2 us,
+// the cell-by-cell phases they replace 50.9 / 61.5 us -- so the quad is one access at any alignment (profiles/r07_kbench_smooth_io.txt).
+typedef float quad_a __attribute__((ext_vector_type(4)));  // (a plain vector type: float4 is a class on the host side of the compile)
+typedef quad_a quad_u __attribute__((aligned(4)));
+typedef __attribute__((address_space(1))) const quad_a gquad_ac;
+typedef __attribute__((address_space(1))) quad_a gquad_a;
+typedef __attribute__((address_space(1))) const quad_u gquad_uc;
+typedef __attribute__((address_space(1))) quad_u gquad_u;
+// One quad at base + off (bytes): scalar base + 32-bit lane offset (ugsm_exact.hpp).  AL: the address is 16-byte aligned.
+template <bool AL>
+__device__ __forceinline__ void ld_quad(const float *base, unsigned off, float (&o)[4])
+{
+    gchar_c *p = (gchar_c *)reinterpret_cast<const char *>(base) + off;
+    quad_a t;
+    if constexpr (AL) t = *(gquad_ac *)p;
+    else t = *(gquad_uc *)p;
+#pragma unroll
+    for (int i = 0; i < 4; i++) o[i] = t[i];
+}
+// ... and out: `cols` (1..4; 4 unless the quad straddles the image's last column, which no 16-byte aligned one does) floats of it
+template <bool AL>
+__device__ __forceinline__ void st_quad(float *base, unsigned off, const float (&q)[4], int cols)
+{
+    gchar *p = (gchar *)reinterpret_cast<char *>(base) + off;
+    if constexpr (AL) {
+        *(gquad_a *)p = quad_a{q[0], q[1], q[2], q[3]};
+    } else if (cols >= 4) {
+        *(gquad_u *)p = quad_a{q[0], q[1], q[2], q[3]};
+    } else {
+#pragma unroll
+        for (int i = 0; i < 3; i++)
+            if (i < cols) *(gfloat *)(p + 4 * i) = q[i];
+    }
+}
 // The passes, the box and the copy-out of ONE tile whose region (tile + halo, clamped onto the image) is in LDS at f0 / f1 / f2.  Every
 // thread of the workgroup calls it; it contains barriers.
 // FIXH: the tile is STY rows high whatever `sty` says -- the height folds into the loop bounds, 2 % faster at level 0 than the
@@ -43,7 +81,11 @@ __device__ __forceinline__ void smooth_tile_body(float *const f0, float *const f
     constexpr int RPW = 64 / QW;             // whole region rows per wave: lane -> (row lane / QW, quad lane % QW), so
                                              // that a quad's west / east neighbours sit in the neighbouring lanes
     constexpr int RG = (NT / 64) * RPW;      // row groups
-    constexpr int MAXR = (LH + RG - 1) / RG; // rows per thread per pass
+    // rows per thread per pass: pass p >= 1 of a launch with halo h <= HY works on sty + 2 (h - p) <= STY + 2 (HY - 1) rows, never on
+    // the whole region (112 x 36: 48 rows = three steps of 16, not the four that LH = 50 asks for: 12 VGPRs and a dead step's compares
+    // less in every pass; level 0, five passes / + box: 172.2 / 200.6 us against 177.1 / 206.6 with four steps, same box)
+    static_assert(HY == kSmoothMaxPasses + 2, "the halo is the pass limit of a launch + 2 rows for the box");
+    constexpr int MAXR = (STY + 2 * (HY - 1) + RG - 1) / RG;
     (void)LH;
     const int LHr = sty + 2 * HY;
     const int tid = threadIdx.x;
@@ -196,6 +238,27 @@ __device__ __forceinline__ void smooth_tile_body(float *const f0, float *const f
         }
     }
 
+    // The box and the copy-out: thread -> (quad column bq of the TILE, rows brg, brg + BRG, ...), so that a wave's lanes hold consecutive
+    // quads of a row.  A quad leaves as one 16-byte store per plane -- aligned when the level's width is a multiple of four (the tile's
+    // first column is one), else at 4-byte alignment (st_quad) --; only the quad that straddles the image's last column goes float by
+    // float.  No per-cell index arithmetic: the offset is one multiply-add per quad-row.
+    constexpr int BQ = STX / 4, BRG = NT / BQ, CMAXR = (STY + BRG - 1) / BRG;
+    const int bq = tid % BQ, brg = tid / BQ;
+    const int bc0 = HX + bq * 4;
+    const bool w4 = (W & 3) == 0;
+    float *const o3b = o3 + n, *const o3c = o3 + 2 * n;
+    auto store_quad = [&](const int gy, const float (&qv)[3][4]) {
+        const int gx = tx0 + bq * 4;
+        if (gx < W && gy < H) {
+            const unsigned off = ((unsigned)gy * (unsigned)W + (unsigned)gx) * 4u;  // (a plane is < 4 GiB)
+            if (w4) {
+                st_quad<true>(o3, off, qv[0], 4); st_quad<true>(o3b, off, qv[1], 4); st_quad<true>(o3c, off, qv[2], 4);
+            } else {
+                const int cols = W - gx;
+                st_quad<false>(o3, off, qv[0], cols); st_quad<false>(o3b, off, qv[1], cols); st_quad<false>(o3c, off, qv[2], cols);
+            }
+        }
+    };
     if (do_box) {
         // refresh the clamped replicas of out-of-image cells within tile+-2 (only edge tiles have any)
         if (tx0 - 2 < 0 || ty0 - 2 < 0 || tx0 + STX + 2 > W || ty0 + sty + 2 > H) {
@@ -210,9 +273,7 @@ __device__ __forceinline__ void smooth_tile_body(float *const f0, float *const f
             __syncthreads();
         }
         // rows (Ta): tile columns, rows tile-2 .. tile+STY+1, rounded to f32, written back in place
-        constexpr int BQ = STX / 4, BRG = NT / BQ, BMAXR = (STY + 4 + BRG - 1) / BRG;
-        const int bq = tid % BQ, brg = tid / BQ;
-        const int bc0 = HX + bq * 4;
+        constexpr int BMAXR = (STY + 4 + BRG - 1) / BRG;
         float bv[BMAXR][3][4];
 #pragma unroll
         for (int u = 0; u < BMAXR; u++) {
@@ -239,10 +300,7 @@ __device__ __forceinline__ void smooth_tile_body(float *const f0, float *const f
             }
         }
         __syncthreads();
-        // columns (Ta) into registers, then back to LDS and out with lanes along the rows: a quad-per-lane
-        // store touches one 16-B piece per lane (4 instructions per 1-KiB row segment); the copy-out below
-        // writes whole contiguous segments
-        constexpr int CMAXR = (STY + BRG - 1) / BRG;
+        // columns (Ta) into registers ...
         float cv[CMAXR][3][4];
 #pragma unroll
         for (int u = 0; u < CMAXR; u++) {
@@ -259,51 +317,22 @@ __device__ __forceinline__ void smooth_tile_body(float *const f0, float *const f
                 }
             }
         }
-        if ((W & 3) == 0) {  // rows are 16-byte aligned: the quads leave as they are (a wave's lanes hold consecutive quads of a row)
+        // ... and out as they are (a wave's lanes hold consecutive quads of a row)
 #pragma unroll
-            for (int u = 0; u < CMAXR; u++) {
-                const int r = HY + brg + u * BRG;
-                const int gx = tx0 + bq * 4, gy = y0 + r;
-                if (brg < BRG && r < HY + sty && gx < W && gy < H) {
-                    const size_t at = (size_t)gy * W + gx;
-#pragma unroll
-                    for (int f = 0; f < 3; f++)
-                        *reinterpret_cast<float4 *>(o3 + f * n + at) = make_float4(cv[u][f][0], cv[u][f][1], cv[u][f][2], cv[u][f][3]);
-                }
-            }
-            return;
+        for (int u = 0; u < CMAXR; u++) {
+            const int r = HY + brg + u * BRG;
+            if (brg < BRG && r < HY + sty) store_quad(y0 + r, cv[u]);
         }
-        __syncthreads();
+    } else {
+        // no box: the tile's quads from LDS (one ds_read_b128 per plane) and out the same way
 #pragma unroll
         for (int u = 0; u < CMAXR; u++) {
             const int r = HY + brg + u * BRG;
             if (brg < BRG && r < HY + sty) {
                 const int at = r * LW + bc0;
-                st4(f0 + at, cv[u][0]); st4(f1 + at, cv[u][1]); st4(f2 + at, cv[u][2]);
-            }
-        }
-        __syncthreads();
-        for (int it = tid; it < STX * sty; it += NT) {
-            const int r = it / STX, c = it - r * STX;
-            const int gx = tx0 + c, gy = ty0 + r;
-            if (gx < W && gy < H) {
-                const size_t at = (size_t)gy * W + gx;
-                const int la = (HY + r) * LW + HX + c;
-                o3[at] = f0[la];
-                o3[n + at] = f1[la];
-                o3[2 * n + at] = f2[la];
-            }
-        }
-    } else {
-        for (int it = tid; it < STX * sty; it += NT) {
-            const int r = it / STX, c = it - r * STX;
-            const int gx = tx0 + c, gy = ty0 + r;
-            if (gx < W && gy < H) {
-                const size_t at = (size_t)gy * W + gx;
-                const int la = (HY + r) * LW + HX + c;
-                o3[at] = f0[la];
-                o3[n + at] = f1[la];
-                o3[2 * n + at] = f2[la];
+                float cv[3][4];
+                ld4(f0 + at, cv[0]); ld4(f1 + at, cv[1]); ld4(f2 + at, cv[2]);
+                store_quad(y0 + r, cv);
             }
         }
     }
@@ -326,8 +355,6 @@ __global__ __launch_bounds__(NT, (NT <= 512 ? NT / 128 : 1)) void k_smooth_fused
     constexpr int RPW = 64 / QW;             // whole region rows per wave: lane -> (row lane / QW, quad lane % QW), so
                                              // that a quad's west / east neighbours sit in the neighbouring lanes
     constexpr int RG = (NT / 64) * RPW;      // row groups
-    constexpr int MAXR = (LH + RG - 1) / RG; // rows per thread per pass
-    (void)QW; (void)RPW; (void)RG; (void)MAXR;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     // A tile is `sty` <= STY rows high (the host picks the height that fills whole rounds of workgroups: smooth_tile_rows);
     // the region is LHr rows, the LDS planes are that long.
@@ -342,10 +369,55 @@ __global__ __launch_bounds__(NT, (NT <= 512 ? NT / 128 : 1)) void k_smooth_fused
     const size_t n = (size_t)W * H;
     const int h = P + (do_box ? 2 : 0);  // halo actually needed
 
-    // ---- load tile + needed halo (clamped onto the image): every global load of the thread is issued
-    // before the first LDS store (a rolled loop waits out one HBM round trip per 512 pixels) ------------
-    {
-        const int r_lo = HY - h, r_hi = LHr - (HY - h);
+    // ---- load tile + needed halo: every global load of the thread is issued before the first LDS store (a rolled loop waits out one
+    // HBM round trip per step) ----------------------------------------------------------------------------------------------------
+    const int r_lo = HY - h, r_hi = LHr - (HY - h);  // the region rows this launch needs
+    // Tile-uniform: the whole width of the region and its needed rows lie inside the image (93 % of a 16 MP level-0 launch).  Such a tile
+    // moves by quads: lane -> quad column, rows dealt over the waves as in the passes, ONE byte offset per thread that advances by RG
+    // rows per step -- no division, no clamp, no select, a third of the load instructions.  The needed rows are loaded at their full
+    // width (the columns outside the needed halo are in the image; nobody reads what the passes make of them); the region rows
+    // outside the needed ones get (0, 0, confidence 1), see below.
+    const bool interior = x0 >= 0 && x0 + RWID <= W && y0 + r_lo >= 0 && y0 + r_hi <= H;
+    if (interior) {
+        constexpr int MAXL = (LH + RG - 1) / RG;
+        static_assert(2 * HY * QW <= NT, "the rows outside the needed ones: one quad per thread");
+        const int lane = tid & 63;
+        const int lq = lane % QW, lrg = (tid >> 6) * RPW + lane / QW;
+        const bool lane_on = lane < RPW * QW;
+        const float *const s3b = s3 + n, *const s3c = s3 + 2 * n;
+        float v[MAXL][3][4];
+        auto load_rows = [&](auto al_tag) {
+            constexpr bool AL = decltype(al_tag)::value;
+            unsigned off = ((unsigned)(y0 + r_lo + lrg) * (unsigned)W + (unsigned)(x0 + lq * 4)) * 4u;  // (a plane is < 4 GiB)
+            const unsigned step = (unsigned)W * (4u * RG);
+#pragma unroll
+            for (int u = 0; u < MAXL; u++) {
+                if (lane_on && r_lo + lrg + u * RG < r_hi) {  // (a wave without a row left branches round the loads: s_cbranch_execz)
+                    ld_quad<AL>(s3, off, v[u][0]); ld_quad<AL>(s3b, off, v[u][1]); ld_quad<AL>(s3c, off, v[u][2]);
+                }
+                off += step;
+            }
+        };
+        // rows are 16-byte aligned when the width is a multiple of four (x0 is one); else the quads are 16-byte accesses at 4-byte
+        // alignment (ld_quad)
+        if ((W & 3) == 0) load_rows(std::true_type{});
+        else load_rows(std::false_type{});
+        if (h < HY && tid < 2 * (HY - h) * QW) {
+            const int k = tid / QW, c = (tid - k * QW) * 4;
+            const int at = (k < HY - h ? k : r_hi + k - (HY - h)) * LW + c;
+            const float zero[4] = {0.0f, 0.0f, 0.0f, 0.0f}, one[4] = {1.0f, 1.0f, 1.0f, 1.0f};
+            st4(f0 + at, zero); st4(f1 + at, zero); st4(f2 + at, one);
+        }
+#pragma unroll
+        for (int u = 0; u < MAXL; u++) {
+            const int r = r_lo + lrg + u * RG;
+            if (lane_on && r < r_hi) {
+                const int at = r * LW + lq * 4;
+                st4(f0 + at, v[u][0]); st4(f1 + at, v[u][1]); st4(f2 + at, v[u][2]);
+            }
+        }
+    } else {
+        // a tile on the image's frame: cell by cell, clamped onto the image
         constexpr int NLD = (LH * RWID + NT - 1) / NT;
         float v[NLD][3];
 #pragma unroll
