@@ -3,7 +3,7 @@
  *
  * libugsm_dev.so is the product's sources plus ug_stereomatcher_amd/csrc/dev/ (csrc/Makefile): everything include/ugsm.h declares, plus what
  * only the tests and the measurement tools need -- kernel_path 1 (one kernel per reference stage: the A/B reference of the fused kernels),
- * ugsm_config.march_min_pixels < 0 (round 1's LDS-tiled K-cost), and the probes below.  A maintainer links libugsm.so.
+ * ugsm_config.march_min_pixels < 0 (round 1's LDS-tiled K-cost), and the probes and the range-word reader below.  A maintainer links libugsm.so.
  */
 #ifndef UGSM_DEV_H
 #define UGSM_DEV_H
@@ -33,6 +33,13 @@ int ugsm_stage_div3_probe(ugsm_ctx *ctx, const float *d_a0, const float *d_a1, c
  * every pyramid value of the pair is 0 or in [2^-12, 2^9]; csrc/ugsm_exact.hpp) on caller-supplied operands:
  * q[i] must equal the IEEE binary32 quotient n[i] / d[i] bit for bit for operands that are 0 or in [2^-62, 2^37]. */
 int ugsm_stage_div_probe(ugsm_ctx *ctx, const float *d_n, const float *d_d, float *d_q, int n);
+
+/* The range words of the first n pairs of the slot's last call, read once everything enqueued on the slot has finished (the call
+ * waits for the slot's stream itself): host_out[b] = 1 when some pyramid value of pair b was outside range_ok (csrc/ugsm_exact.hpp)
+ * and K-cost took the compiler's division for that pair, 0 when every value passed and it took the guarded one.
+ * UGSM_ERR_STATE when the slot holds no words (kernel_path 1, or no call yet), UGSM_ERR_BAD_ARG for n < 1 or n > the pairs of
+ * that call. */
+int ugsm_stage_range_words(ugsm_ctx *ctx, int slot, unsigned *host_out, int n);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop

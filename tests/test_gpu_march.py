@@ -102,9 +102,17 @@ def test_march_equals_tiled_end_to_end(lib, orc, monkeypatch):
         assert_bit_equal(got, exp, f"320x240 full, np={np_lane}")
 
 
-def test_division_in_range_is_ieee(lib):
+def test_division_in_range_is_ieee(lib, orc):
     """K-cost's range-guarded division (csrc/ugsm_exact.hpp: the compiler's division sequence without v_div_scale /
-    v_div_fixup) equals the IEEE binary32 quotient for every operand pair it can meet: 0 or [2^-62, 2^37]."""
+    v_div_fixup) equals the IEEE binary32 quotient for every operand pair it can meet: 0 or [2^-62, 2^37].
+
+    ... and, measured, on the operands an 8-bit image produces when it LEAVES the guarded range: the (N^2, A*B) pairs of the dark
+    640 x 480 pair of tests/dark_np.py at zero disparity (restated on the CPU from the oracle's pyramids; its levels 3-9, the ones with
+    values outside range_ok, give 1.11 M pairs, 762 of them with an operand below 2^-62, down to N^2 = 1.2e-25, A*B = 2.0e-21) all come
+    out as the IEEE quotient too: 0 of them differ, there or at any other of the 14 levels.  So no 8-bit image has been found on which
+    taking the guarded division for an out-of-range pair would change a bit -- the guard's bound is conservative there -- and the
+    end-to-end results cannot tell whether a pyramid kernel missed a value: the word assertions of tests/test_gpu_range_word.py carry
+    that.  Pinned here as measured; range_ok stays as proven."""
     rng = np.random.Generator(np.random.PCG64(41))
     n = 1 << 22
 
@@ -147,6 +155,31 @@ def test_division_in_range_is_ieee(lib):
                 c.free(p)
     assert np.isnan(exp[5 * q + 2048:5 * q + 4096]).all() and (exp[5 * q:5 * q + 2048] == 0).all()
     assert_bit_equal(got, exp, "range-guarded division")
+    # the operands of the dark pair at the levels where its pyramids leave range_ok
+    import dark_np as dk
+    from ug_stereomatcher_amd import synth
+    L, R = dk.dark_pair(*synth.make_pair(640, 480, synth.BASE_SEED + 300)[:2], 77)
+    pl, pr = orc.pyramid(orc.rgb_to_planes(L), 14), orc.pyramid(orc.rgb_to_planes(R), 14)
+    lv = [i for i in range(14) if (~dk.in_range(pl[i])).any() or (~dk.in_range(pr[i])).any()]
+    assert lv and min(lv) >= 3, lv
+    ops = [dk.kcost_operands(orc, pl[i], pr[i]) for i in lv]
+    num, den = np.concatenate([o[0] for o in ops]), np.concatenate([o[1] for o in ops])
+    below = ((num != 0) & (num < np.float32(2.0 ** -62))) | ((den != 0) & (den < np.float32(2.0 ** -62)))
+    print(f"dark pair, levels {lv}: {num.size} operand pairs, {int(below.sum())} with an operand below 2^-62, "
+          f"least N^2 {num[num > 0].min():.3e}, least A*B {den[den > 0].min():.3e}")
+    assert below.sum() > 0, "the dark pair no longer leaves the proven operand range: the recipe or synth changed"
+    with np.errstate(all="ignore"):
+        exp = (num / den).astype(np.float32)
+    with lib.Context(levels=1, dev=True) as c:
+        pn, pd = c.to_device(num), c.to_device(den)
+        pq = c.alloc(4 * num.size)
+        try:
+            c.check(c.lib.ugsm_stage_div_probe(c.handle, pn, pd, pq, num.size))
+            got = c.to_host(pq, (num.size,))
+        finally:
+            for p in (pn, pd, pq):
+                c.free(p)
+    assert_bit_equal(got, exp, "range-guarded division on the dark pair's operands")
 
 
 @pytest.mark.parametrize("np_lane", [1])  # (the two-pixels-per-lane development form is not in libugsm.so: tools/kbench.hip)

@@ -5,7 +5,9 @@ import os
 import sys
 
 import numpy as np
+import pytest
 
+import dark_np as dk
 from conftest import GOLDEN, assert_bit_equal, load_golden
 
 sys.path.insert(0, GOLDEN)
@@ -67,3 +69,58 @@ def test_foveated_320x240(orc):
     g = load_golden("fovea_320x240_l9_f4.npz")
     st = rn.match_foveated(g["L"], g["R"], int(g["levels"]), int(g["F"]))
     assert_bit_equal(st, g["stack"], "foveated stack")
+
+
+# ---- pairs that leave K-cost's guarded-division range (tests/dark_np.py) -------------------------------------------------------------
+# The committed fixtures are [1, 255] texture: no pyramid value of theirs is 0, tiny, or a fringe of black.  The two restatements must
+# also agree where the pyramids hold zeros and values down to 1e-8 -- 0 / 0 correlations, quotients of tiny numbers -- because the GPU
+# tests of the range word (tests/test_gpu_range_word.py) take the C oracle's answer on such pairs as their expectation.
+
+
+def _plain(W, H, seed_off):
+    from ug_stereomatcher_amd import synth
+    return synth.make_pair(W, H, synth.BASE_SEED + seed_off)[:2]
+
+
+@pytest.mark.parametrize("recipe", ["dark noise", "one dim pixel"])
+def test_full_on_pairs_outside_the_guarded_range_160x120(orc, recipe):
+    """C oracle vs numpy restatement, bit for bit, 160 x 120 x 8 levels, on a pair whose pyramids hold values outside range_ok (the
+    premise, asserted: none at levels 0-2, some at a level >= 3; the plain pair has none)."""
+    W, H, lv = 160, 120, 8
+    L, R = _plain(W, H, 611)
+    assert dk.pair_word(orc, L, R, lv)[0] == 0, "the plain pair must stay inside the range"
+    if recipe == "dark noise":
+        L2, R2 = dk.dark_pair(L, R, 5)
+        assert dk.trips(dk.out_of_range_levels(orc, R2, lv))
+    else:
+        L2, R2 = dk.one_dim_pixel(L, 64, 1, (60, 80)), R
+    counts = dk.out_of_range_levels(orc, L2, lv)
+    print(f"{recipe}: out-of-range values per level of L: {counts}")
+    assert dk.trips(counts), counts
+    out = orc.match_full(L2, R2, lv)
+    assert np.isfinite(out).all()
+    assert_bit_equal(rn.match_full(L2, R2, lv), out, f"numpy restatement vs C oracle, {recipe}")
+
+
+@pytest.mark.parametrize("name", ["all 0", "all 255", "constant 7", "L black, R textured", "L textured, R black"])
+def test_full_on_degenerate_pairs_160x120(orc, name):
+    """Flat and black images: every pyramid value is 0 or a constant in range (word 0), every correlation 0 / 0 or 1; both restatements
+    give the same finite field."""
+    W, H, lv = 160, 120, 8
+    L2, R2 = dk.degenerate_pairs(*_plain(W, H, 612))[name]
+    assert dk.pair_word(orc, L2, R2, lv)[0] == 0
+    out = orc.match_full(L2, R2, lv)
+    assert np.isfinite(out).all()
+    assert_bit_equal(rn.match_full(L2, R2, lv), out, f"numpy restatement vs C oracle, {name}")
+
+
+def test_foveated_on_the_dark_pair_320x240(orc):
+    """The foveated restatement (320 x 240 x 9 levels, F = 4) on the dark-noise pair."""
+    W, H, lv, F = 320, 240, 9, 4
+    L2, R2 = dk.dark_pair(*_plain(W, H, 613), 9)
+    cl, cr = dk.out_of_range_levels(orc, L2, lv), dk.out_of_range_levels(orc, R2, lv)
+    print(f"dark pair, out-of-range values per level: L {cl}, R {cr}")
+    assert dk.trips(cl) and dk.trips(cr)
+    st = orc.match_foveated(L2, R2, lv, F)[0]
+    assert np.isfinite(st).all()
+    assert_bit_equal(rn.match_foveated(L2, R2, lv, F), st, "foveated stack, numpy restatement vs C oracle")

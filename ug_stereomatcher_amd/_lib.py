@@ -58,7 +58,7 @@ EXPORTS = [
     "ugsm_input_bytes_per_pixel", "ugsm_input_format_from_encoding", "ugsm_set_input_format", "ugsm_get_input_format",
 ]
 # ... and what include/ugsm_dev.h adds (libugsm_dev.so only)
-DEV_EXPORTS = ["ugsm_stage_poly_probe", "ugsm_stage_div3_probe", "ugsm_stage_div_probe"]
+DEV_EXPORTS = ["ugsm_stage_poly_probe", "ugsm_stage_div3_probe", "ugsm_stage_div_probe", "ugsm_stage_range_words"]
 
 
 # input formats (ugsm_set_input_format): the byte layout of the images a context reads; a call on an image in format F gives the rgb8 call's
@@ -252,6 +252,7 @@ def load(dev: bool = False):
         lib.ugsm_stage_poly_probe.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i]
         lib.ugsm_stage_div3_probe.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i]
         lib.ugsm_stage_div_probe.argtypes = [vp, vp, vp, vp, i]
+        lib.ugsm_stage_range_words.argtypes = [vp, i, C.POINTER(C.c_uint), i]
     lib.ugsm_stage_weighted_difference.argtypes = [vp, vp, vp, i, i, C.POINTER(C.c_float)]
     lib.ugsm_last_iterations.argtypes = [vp, i, C.POINTER(i)]
     lib.ugsm_stage_lr_check.argtypes = [vp, vp, vp, i, i, C.c_float, C.POINTER(C.c_longlong)]
@@ -717,6 +718,13 @@ class Context:
 
     def shard_finalize(self):
         self.check(self.lib.ugsm_shard_finalize(self._h))
+
+    def range_words(self, slot: int, n: int = 1):
+        """libugsm_dev.so only (include/ugsm_dev.h): the range words of the n pairs of the slot's last call, read after the slot has drained --
+        1 where a pyramid value of the pair was outside range_ok (csrc/ugsm_exact.hpp) and K-cost took the compiler's division."""
+        out = (C.c_uint * n)()
+        self.check(self.lib.ugsm_stage_range_words(self._h, slot, out, n))
+        return [int(v) for v in out]
 
     def device_bytes(self) -> int:
         return int(self.lib.ugsm_context_device_bytes(self._h))

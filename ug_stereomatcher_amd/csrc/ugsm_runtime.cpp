@@ -2668,6 +2668,25 @@ int ugsm_stage_div_probe(ugsm_ctx *ctx, const float *d_n, const float *d_d, floa
     HIPCHK(ctx, hipGetLastError());
     return ugsm_wait(ctx, 0);
 }
+
+// The range words of the slot's last call (Slot::range_bad: zeroed by enqueue_pyramids, set by the pyramid kernels, read by the
+// marching K-cost kernels), for the tests that drive that mechanism through whole calls.  Reads host state and device memory only:
+// the slot does not become busy, nothing is launched.
+int ugsm_stage_range_words(ugsm_ctx *ctx, int slot, unsigned *host_out, int n)
+{
+    Slot *s;
+    UCHK(get_slot(ctx, slot, &s, false));
+    if (!host_out || n < 1 || n > kMaxBatch) return UGSM_ERR_BAD_ARG;
+    if (!s->range_known || !s->range_bad) {
+        ctx->err = "the slot holds no range words (kernel_path 1, or no call has built pyramids on it)";
+        return UGSM_ERR_STATE;
+    }
+    if (n > s->nb) return UGSM_ERR_BAD_ARG;
+    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
+    HIPCHK(ctx, hipStreamSynchronize(s->st));  // (the main stream has joined whatever the call put on the side stream)
+    HIPCHK(ctx, hipMemcpy(host_out, s->range_bad, sizeof(unsigned) * n, hipMemcpyDeviceToHost));
+    return UGSM_OK;
+}
 #endif
 
 #ifdef UGSM_DEV_LIB
