@@ -34,7 +34,8 @@ extern "C" {
                                ugsm_default_cloud_params, ugsm_cloud_points, ugsm_point_cloud, ugsm_point_cloud_fovea; the resized cloud --
                                ugsm_resized_cloud_points, ugsm_point_cloud_resized, ugsm_point_cloud_resized_fovea; the input formats --
                                UGSM_INPUT_*, ugsm_input_bytes_per_pixel, ugsm_input_format_from_encoding, ugsm_set_input_format,
-                               ugsm_get_input_format
+                               ugsm_get_input_format; the merged cloud of the fovea stack -- ugsm_fovea_level_mapping, ugsm_fovea_cloud_points,
+                               ugsm_point_cloud_fovea_all
                                6: the kernel choices follow what is in flight, not ugsm_config.slots: ugsm_plan_level takes `alone`, ugsm_plan_level_in_frame
                                is gone, ugsm_level_plan.latency_policy is .alone; ugsm_enqueue_* returns UGSM_OK once the pair is accepted (a failed
                                CALL is reported through ugsm_completion.status only); the fovea shard carries a status word (a rank that fails still
@@ -498,6 +499,47 @@ int ugsm_point_cloud_fovea(ugsm_ctx *ctx, int slot, const float *d_stackx, const
                            int fovW, int fovH, int src_level, int left_margin, int upper_margin, float scale,
                            const uint8_t *d_rgbL, int W, int H, int stride, const double *P1, const double *P2,
                            const ugsm_cloud_params *p, void *d_points, long long cap_points, long long *d_count);
+
+/* The whole fovea stack as ONE cloud (this build's; the reference builds one level at a time).
+ *
+ * ugsm_fovea_level_mapping is ugsm_fovea_mapping(.., src_level, 0, ..) for any fovea_levels F and for this build's window offsets
+ * (off_x, off_y as given to the match).  With w[], h[] of ugsm_level_dims and k = src_level, 0 <= k < F:
+ *   scale = powf((float)1.41421356237309504880, (float)k);
+ *   left_margin = w[0]/2 - w[F-1-k]/2 + (int)lrint(ex[k] * pow(1.41421356, k)), ex[k] the window's clamped offset from the centre at
+ *   level k (0 at level F-1); upper_margin the same with h, ey and off_y.
+ * For F == 7 and offset (0, 0) the three equal ugsm_fovea_mapping(W, H, k, 0, ..) exactly.  Host only.  UGSM_ERR_BAD_ARG: a null
+ * output, F < 2, F > levels, k outside 0 .. F-1, a size ugsm_level_dims refuses for the stack's
+ * F levels (the levels below the stack do not enter).
+ *
+ * THE COVERAGE RULE.  Pixel (ii, jj) of level k >= 1 has the footprint [x1, x1 + scale_k) x [y1, y1 + scale_k) in the full-resolution
+ * frame, x1 = (float)left_k + (float)ii * scale_k and y1 = (float)upper_k + (float)jj * scale_k (the cloud's own x1, y1).  It is COVERED,
+ * and left out of the merged cloud, when that footprint lies wholly inside level k-1's window:
+ *   x1 >= (float)left_{k-1} && x1 + scale_k <= (float)left_{k-1} + (float)fovW * scale_{k-1}, and the same in y with upper and fovH,
+ * every operation in binary32 and rounded on its own.  Level 0 covers nothing.  A pixel that straddles a window's edge is kept: the
+ * cloud has a one-pixel seam of overlap and never a hole.  Per level the covered columns are one interval and the covered rows another.
+ *
+ * ugsm_fovea_cloud_points: the dense size of the merged cloud -- per level (sampled columns) x (sampled rows) less (sampled covered
+ * columns) x (sampled covered rows), written to per_level[0 .. F-1] when that is not NULL -- or -1 on bad arguments.  Host only.
+ * 16 MP, 14 / 7 levels, centred: 1 005 221 points of the stack's 1 752 135.
+ *
+ * ugsm_point_cloud_fovea_all: levels and fovea_levels are the context's; d_stackx / d_stacky / d_stackc the (F*fovH) x fovW stacks of a
+ * foveated call, off_x / off_y as given to it.  Level 0 comes first, then 1 .. F-1; within a level the order is ugsm_point_cloud_fovea's
+ * (column outer, row inner, the sampled pixels) with the covered pixels left out.  Each record is byte for byte the one
+ * ugsm_point_cloud_fovea writes for that pixel with ugsm_fovea_level_mapping's numbers for its level, in either record format and
+ * any input format.  Dense: every uncovered sampled pixel, *d_count = ugsm_fovea_cloud_points(..).  Compact: the kept points only (the
+ * same test), in the same relative order, the same bytes from run to run.  cap_points, *d_count, the stream and the count buffer as for
+ * ugsm_point_cloud.  d_level_counts (device, 8-byte aligned, F entries; may be NULL) receives each level's number of points in the
+ * cloud, so that a consumer knows where each resolution starts.  One launch (compact: two) for the whole stack.
+ * UGSM_ERR_BAD_ARG as for ugsm_point_cloud_fovea, and also: a context with fovea_levels < 2 (a one-level stack is the full frame:
+ * ugsm_point_cloud), a misaligned d_level_counts. */
+int ugsm_fovea_level_mapping(int W, int H, int levels, int fovea_levels, int off_x, int off_y, int src_level,
+                             int *left_margin, int *upper_margin, float *scale);
+long long ugsm_fovea_cloud_points(int W, int H, int levels, int fovea_levels, int off_x, int off_y, int sampling,
+                                  long long *per_level);
+int ugsm_point_cloud_fovea_all(ugsm_ctx *ctx, int slot, const float *d_stackx, const float *d_stacky, const float *d_stackc,
+                               int W, int H, int off_x, int off_y, const uint8_t *d_rgbL, int stride,
+                               const double *P1, const double *P2, const ugsm_cloud_params *p, void *d_points,
+                               long long cap_points, long long *d_count, long long *d_level_counts);
 
 /* Row f-1, the resized cloud: what the node publishes on output_pointcloud_resized, doReconstruction_resized /
  * doReconstructionFOV_resized (getPointCloud.cpp:724-800, :802-884).  The Z plane resized with cv::resize(..., INTER_CUBIC) to

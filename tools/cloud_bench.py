@@ -21,6 +21,16 @@ The resized cloud (ugsm_point_cloud_resized[_fovea]) instead: per size, today's 
 (min_conf 0.5) at f = 0.2 and 0.5, and at 16 MP the fovea stack's level 0 at f = 0.2 (dense PCL32, the reference's colour).  MB: dx, dy
 read once (8 B per pixel of the planes: every row is touched, by a tap or by yy; the compact form's count launch reads them again, and
 conf once per point), the rgb rows the points read (dh rows of 3 W bytes), count x 32 written.
+
+    python tools/cloud_bench.py --stack [--out profiles/cloud_stack_bench.json]
+
+The merged cloud of the whole fovea stack (ugsm_point_cloud_fovea_all) instead: per size, after one ugsm_submit_foveated on the slot,
+dense PCL32, dense 16-byte and compact PCL32 (min_conf 0.5) as one call, and in the same run the two paths it replaces: the F per-level
+ugsm_point_cloud_fovea calls (each repeat is the F calls together; the covered points are written F times over) and
+ugsm_reconstruct_full followed by the dense ugsm_point_cloud of the W x H field.  device_ms is the median over --reps repeats of the
+summed in-dispatch kernel times of a repeat, device_ms_min / _max their range; wall_ms the median host time from the first call to the
+end of ugsm_wait (launch gaps and the compact forms' memsets included); MB = count x point_step, the bytes a consumer receives; d2h_ms
+their copy to page-locked memory.
 """
 import argparse
 import ctypes as C
@@ -56,6 +66,20 @@ def median_ms(c, call, reps, warmup):
     for _ in range(warmup):
         device_ms(c, call)
     return float(np.median([device_ms(c, call) for _ in range(reps)]))
+
+
+def spread_ms(c, call, reps, warmup):
+    """-> (median, min, max) of the device time of `reps` repeats, and the median wall-clock time of a repeat (call .. end of ugsm_wait)."""
+    for _ in range(warmup):
+        device_ms(c, call)
+    ts = [device_ms(c, call) for _ in range(reps)]
+    ws = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        call()
+        c.check(c.lib.ugsm_wait(c.handle, 0))
+        ws.append((time.perf_counter() - t0) * 1e3)
+    return float(np.median(ts)), float(min(ts)), float(max(ts)), float(np.median(ws))
 
 
 def host_copy_ms(c, dst, src, nbytes, reps):
@@ -147,12 +171,78 @@ def resized_rows(args, emit, copy, p1, p2, dp):
                 c.free(p)
 
 
+def stack_rows(args, emit, p1, p2, dp):
+    from ug_stereomatcher_amd import _lib, synth
+    P1p, P2p = p1.ctypes.data_as(dp), p2.ctypes.data_as(dp)
+    levels, F = 14, 7
+    forms = (("dense_pcl32", 0, False), ("dense_xyzrgb16", 1, False), ("compact_pcl32", 0, True))
+    for size in args.sizes.split(","):
+        W, H = (int(v) for v in size.split("x"))
+        L, R, _, _ = synth.make_pair(W, H, synth.BASE_SEED + 2)
+        fw, fh = _lib.fovea_dims(W, H, levels, F)
+        with _lib.Context(levels=levels, fovea_levels=F, profile_events=2) as c:
+            lib, h = c.lib, c.handle
+            pL, pR = c.to_device(L), c.to_device(R)
+            lvl = F * fw * fh * 4
+            d_stack = c.alloc(3 * lvl)
+            c.check(lib.ugsm_submit_foveated(h, 0, pL, pR, W, H, L.strides[0], 0, 0, d_stack, None, None))
+            c.check(lib.ugsm_wait(h, 0))
+            sx, sy, sc = d_stack, d_stack + lvl, d_stack + 2 * lvl
+            plane = W * H * 4
+            d_full = c.alloc(3 * plane)
+            d_pts, d_cnt, d_lvl = c.alloc(W * H * 32), c.alloc(8 * F), c.alloc(8 * F)
+            host = c.host_array((W * H * 32,), np.uint8)
+            maps = [_lib.fovea_level_mapping(W, H, levels, F, k) for k in range(F)]
+            copies = max(5, args.reps // 3)
+
+            def row(what, call, count, step, **extra):
+                t, lo, hi, wall = spread_ms(c, call, args.reps, args.warmup)
+                n = count()
+                t_d2h = host_copy_ms(c, host.ctypes.data, d_pts, n * step, copies) if n else 0.0
+                emit(dict({"what": what, "size": size, "count": n, "device_ms": round(t, 4), "device_ms_min": round(lo, 4),
+                           "device_ms_max": round(hi, 4), "wall_ms": round(wall, 4), "MB": round(n * step / 1e6, 2), "d2h_ms": round(t_d2h, 3),
+                           "total_ms": round(t + t_d2h, 3)}, **extra))
+
+            for name, fmt, compact in forms:
+                prm = _lib.cloud_params(format=fmt, compact=compact, min_conf=0.5 if compact else None)
+                step = 32 if fmt == 0 else 16
+                merged = lambda: c.check(lib.ugsm_point_cloud_fovea_all(h, 0, sx, sy, sc, W, H, 0, 0, pL, L.strides[0], P1p, P2p, C.byref(prm),
+                                                                        d_pts, W * H, d_cnt, d_lvl))
+                row("stack_" + name, merged, lambda: int(c.to_host(d_cnt, (1,), np.int64)[0]), step, launches=2 if compact else 1)
+                # the F per-level calls, each level's cloud behind the one before (a compact cloud needs each count back first: not timed)
+                counts = []
+                for k in range(F):
+                    c.check(lib.ugsm_point_cloud_fovea(h, 0, sx, sy, sc, fw, fh, k, maps[k][0], maps[k][1], C.c_float(maps[k][2]), pL, W, H,
+                                                       L.strides[0], P1p, P2p, C.byref(prm), d_pts, fw * fh, d_cnt + 8 * k))
+                c.check(lib.ugsm_wait(h, 0))
+                counts = c.to_host(d_cnt, (F,), np.int64).tolist()
+                first = np.concatenate([[0], np.cumsum(counts)]).tolist()
+
+                def per_level():
+                    for k in range(F):
+                        c.check(lib.ugsm_point_cloud_fovea(h, 0, sx, sy, sc, fw, fh, k, maps[k][0], maps[k][1], C.c_float(maps[k][2]), pL, W, H,
+                                                           L.strides[0], P1p, P2p, C.byref(prm), d_pts + first[k] * step, fw * fh, d_cnt + 8 * k))
+                row("per_level_" + name, per_level, lambda: int(sum(counts)), step, launches=F * (2 if compact else 1))
+            # the dense field: hierarchicalDisparity's upsampled planes, then the cloud of every pixel
+            prm = _lib.cloud_params()
+
+            def dense_path():
+                c.check(lib.ugsm_reconstruct_full(h, 0, sx, sy, sc, W, H, 0, 0, d_full))
+                c.check(lib.ugsm_point_cloud(h, 0, d_full, d_full + plane, d_full + 2 * plane, pL, W, H, L.strides[0], P1p, P2p, C.byref(prm),
+                                             d_pts, W * H, d_cnt))
+            row("reconstruct_full_then_dense_pcl32", dense_path, lambda: int(c.to_host(d_cnt, (1,), np.int64)[0]), 32, launches=F,
+                planes_MB=round(3 * plane / 1e6, 1))
+            for p in (pL, pR, d_stack, d_full, d_pts, d_cnt, d_lvl):
+                c.free(p)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=25)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--sizes", default="4928x3264,1920x1080")
     ap.add_argument("--resized", action="store_true", help="the resized cloud's rows instead")
+    ap.add_argument("--stack", action="store_true", help="the merged cloud of the fovea stack and the two paths it replaces instead")
     ap.add_argument("--out")
     args = ap.parse_args()
     from ug_stereomatcher_amd import _lib, synth
@@ -169,6 +259,9 @@ def main():
     dp = C.POINTER(C.c_double)
     if args.resized:
         resized_rows(args, emit, copy, p1, p2, dp)
+        sizes = []
+    elif args.stack:
+        stack_rows(args, emit, p1, p2, dp)
         sizes = []
     else:
         sizes = args.sizes.split(",")

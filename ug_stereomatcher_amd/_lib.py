@@ -54,6 +54,8 @@ EXPORTS = [
     "ugsm_default_cloud_params", "ugsm_cloud_points", "ugsm_point_cloud", "ugsm_point_cloud_fovea",
     # ... and the resized cloud
     "ugsm_resized_cloud_points", "ugsm_point_cloud_resized", "ugsm_point_cloud_resized_fovea",
+    # ... and the merged cloud of the whole fovea stack
+    "ugsm_fovea_level_mapping", "ugsm_fovea_cloud_points", "ugsm_point_cloud_fovea_all",
     # the input formats
     "ugsm_input_bytes_per_pixel", "ugsm_input_format_from_encoding", "ugsm_set_input_format", "ugsm_get_input_format",
 ]
@@ -308,6 +310,10 @@ def load(dev: bool = False):
     lib.ugsm_point_cloud_resized.argtypes = [vp, i, vp, vp, vp, vp, i, i, i, dpp, dpp, C.c_float, C.POINTER(CloudParams), vp, C.c_longlong, vp]
     lib.ugsm_point_cloud_resized_fovea.argtypes = [vp, i, vp, vp, vp, i, i, i, i, i, C.c_float, vp, i, i, i, dpp, dpp, C.c_float, i,
                                                    C.POINTER(CloudParams), vp, C.c_longlong, vp]
+    lib.ugsm_fovea_level_mapping.argtypes = [i, i, i, i, i, i, i, C.POINTER(i), C.POINTER(i), C.POINTER(C.c_float)]
+    lib.ugsm_fovea_cloud_points.argtypes = [i, i, i, i, i, i, i, C.POINTER(C.c_longlong)]
+    lib.ugsm_fovea_cloud_points.restype = C.c_longlong
+    lib.ugsm_point_cloud_fovea_all.argtypes = [vp, i, vp, vp, vp, i, i, i, i, vp, i, dpp, dpp, C.POINTER(CloudParams), vp, C.c_longlong, vp, vp]
     if bool(lib.ugsm_is_dev_library()) != bool(dev):
         raise UgsmError(UGSM_ERR_STATE, f"{path} is not the {'development' if dev else 'product'} build")
     _libs[dev] = lib
@@ -377,6 +383,23 @@ def cloud_points(W: int, H: int, sampling: int = 1) -> int:
 def resized_cloud_points(W: int, H: int, factor: float) -> int:
     """Points of the resized cloud, (int)((float)W * f) * (int)((float)H * f) with f a float32; -1 on bad arguments."""
     return int(load().ugsm_resized_cloud_points(W, H, C.c_float(float(factor))))
+
+
+def fovea_level_mapping(W: int, H: int, levels: int, fovea_levels: int, src_level: int, off=(0, 0)):
+    """ugsm_fovea_mapping(.., src_level, 0) for any fovea_levels and window offset -> (left_margin, upper_margin, scale); host only."""
+    l, u, sc = C.c_int(), C.c_int(), C.c_float()
+    st = load().ugsm_fovea_level_mapping(W, H, levels, fovea_levels, int(off[0]), int(off[1]), src_level, C.byref(l), C.byref(u), C.byref(sc))
+    if st:
+        raise UgsmError(st, "ugsm_fovea_level_mapping")
+    return l.value, u.value, np.float32(sc.value)
+
+
+def fovea_cloud_points(W: int, H: int, levels: int = 14, fovea_levels: int = 7, off=(0, 0), sampling: int = 1, per_level: bool = False):
+    """Points of the dense merged cloud of the fovea stack (ugsm_point_cloud_fovea_all), -1 on bad arguments; with per_level, also the
+    list of each level's points."""
+    per = (C.c_longlong * UGSM_MAX_LEVELS)()
+    n = int(load().ugsm_fovea_cloud_points(W, H, levels, fovea_levels, int(off[0]), int(off[1]), sampling, per))
+    return (n, list(per[:fovea_levels]) if n >= 0 else []) if per_level else n
 
 
 def input_bytes_per_pixel(format: int) -> int:
@@ -544,6 +567,22 @@ class Context:
                                                    C.byref(params), d_points, int(cap_points), d_count))
         self.check(self.lib.ugsm_wait(self._h, slot))
         return int(self.to_host(d_count, (1,), np.int64)[0])
+
+    def point_cloud_fovea_all(self, d_stackx: int, d_stacky: int, d_stackc, W: int, H: int, off, d_rgbL: int, stride: int, P1, P2,
+                              params: CloudParams, d_points: int, cap_points: int, d_count: int, d_level_counts=None, slot: int = 0):
+        """The whole fovea stack as one cloud (ugsm_point_cloud_fovea_all): level 0, then 1 .. F-1 without the pixels the finer level
+        covers; waits on the slot and returns the count, or (count, per-level counts) when d_level_counts is given."""
+        p1 = np.ascontiguousarray(P1, np.float64).reshape(12)
+        p2 = np.ascontiguousarray(P2, np.float64).reshape(12)
+        dp = C.POINTER(C.c_double)
+        self.check(self.lib.ugsm_point_cloud_fovea_all(self._h, slot, d_stackx, d_stacky, d_stackc, W, H, int(off[0]), int(off[1]), d_rgbL,
+                                                       stride, p1.ctypes.data_as(dp), p2.ctypes.data_as(dp), C.byref(params), d_points,
+                                                       int(cap_points), d_count, d_level_counts))
+        self.check(self.lib.ugsm_wait(self._h, slot))
+        n = int(self.to_host(d_count, (1,), np.int64)[0])
+        if d_level_counts is None:
+            return n
+        return n, self.to_host(d_level_counts, (self.cfg.fovea_levels,), np.int64).tolist()
 
     def point_cloud_resized(self, d_dispx: int, d_dispy: int, d_conf, d_rgbL: int, W: int, H: int, stride: int, P1, P2, factor: float,
                             params: CloudParams, d_points: int, cap_points: int, d_count: int, slot: int = 0) -> int:

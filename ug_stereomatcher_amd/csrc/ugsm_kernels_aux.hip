@@ -175,9 +175,9 @@ __device__ __forceinline__ void tri_point(float x1, float y1, float x2, float y2
 }
 
 // The forms of k_triangulate / k_triangulate_fovea (template parameter): the X, Y, Z planes, the two launches of the point cloud and
-// the two of the resized cloud (below).  The plane form keeps its own parameter list, so its code is what it was before the cloud forms
-// came.
-enum TriForm : int { kTriPlanes = 0, kTriCloudCount = 1, kTriCloud = 2, kTriResizedCount = 3, kTriResized = 4 };
+// the two of the resized cloud and the two of the fovea stack's merged cloud (below).  The plane form keeps its own parameter list, so
+// its code is what it was before the cloud forms came.
+enum TriForm : int { kTriPlanes = 0, kTriCloudCount = 1, kTriCloud = 2, kTriResizedCount = 3, kTriResized = 4, kTriStackCount = 5, kTriStack = 6 };
 
 template <int Form>
 __global__ __launch_bounds__(256) void k_triangulate(const float *__restrict__ dispx, const float *__restrict__ dispy, int W, int H, Proj P1q, Proj P2q,
@@ -408,25 +408,54 @@ __device__ __forceinline__ bool resized_point(const CloudArgs &a, const CloudRes
     return cloud_keep(a, (size_t)yy * a.pw + xx, X, Y, Z);
 }
 
-template <bool Fovea, int Form>
-__device__ __forceinline__ void cloud_tile(const CloudArgs &a, const CloudResize &rz, const Proj &P1q, const Proj &P2q)
+// The merged cloud of the whole fovea stack (ugsm_point_cloud_fovea_all; kTriStackCount / kTriStack): the same tile over F * strips
+// virtual strips, level = strip / strips.  `a` holds the workgroup's level already (its planes and mapping: k_triangulate_fovea, the
+// overload on the table), lv is that level's row of the table.  A covered point (sampled column in [cx0, cx1) and row in [cy0, cy1): its footprint lies wholly inside
+// the finer level's window) is marked not kept before any load is issued for it, so phase B ranks the rest and phase C writes them as one
+// run per column; a tile wholly inside the rectangle returns at once.  Dense offsets are closed-form: the level's first record, the
+// columns before this one x hc less ny for each covered one among them, the rows above less the covered ones.  Compact: the two-launch
+// scheme over the F * wc virtual columns and F * strips virtual strips.
+__device__ __forceinline__ long long stack_dense_run(const CloudArgs &a, const CloudLevel &lv, int ci, int r0)
 {
+    const int ncx = lv.cx1 - lv.cx0, ny = lv.cy1 - lv.cy0;
+    const bool in = ci >= lv.cx0 && ci < lv.cx1;
+    return lv.first + (long long)ci * a.hc - (long long)ny * min(max(ci - lv.cx0, 0), ncx) + r0 - (in ? min(max(r0 - lv.cy0, 0), ny) : 0);
+}
+
+template <bool Fovea, int Form>
+__device__ __forceinline__ void cloud_tile(const CloudArgs &a, const CloudResize &rz, const Proj &P1q, const Proj &P2q, const CloudStack *sk = nullptr,
+                                           int level = 0)
+{
+    constexpr bool Stack = Form == kTriStackCount || Form == kTriStack;
     __shared__ float4 rec[kCloudTC * kCloudPad];
     __shared__ unsigned char kept[kCloudTC * kCloudTR];
     __shared__ unsigned char src[kCloudTC * kCloudTR];
     __shared__ int nrec[kCloudTC];
     __shared__ unsigned pre[kCloudTC + 1];  // compact: [c] the run's first record less the strip's, [kCloudTC] the strip's first record
+    // tx: the strip among all of the launch (the stack forms: F * strips virtual strips); c0: its first column in its level, v0: among
+    // the launch's columns (the stack forms: level * wc + c0, the F * wc virtual columns)
     const int t = threadIdx.x, tx = blockIdx.x, ty = blockIdx.y;
-    const int c0 = tx * kCloudTC, r0 = ty * kCloudTR;
+    const int c0 = (Stack ? tx - level * sk->strips : tx) * kCloudTC, r0 = ty * kCloudTR;
     const int c = t & (kCloudTC - 1), ci = c0 + c;
-    unsigned *const col_tot = a.cnt + (size_t)a.wc * a.nchunk, *const strip_tot = col_tot + a.wc;  // (compact only)
-    constexpr bool Write = Form == kTriCloud || Form == kTriResized, Count = !Write;  // the cloud launch / the count launch
+    const int v0 = Stack ? level * a.wc + c0 : c0, wv = Stack ? sk->F * a.wc : a.wc;
+    unsigned *const col_tot = a.cnt + (size_t)wv * a.nchunk, *const strip_tot = col_tot + wv;  // (compact only)
+    constexpr bool Write = Form == kTriCloud || Form == kTriResized || Form == kTriStack, Count = !Write;  // the cloud launch / the count launch
+    if constexpr (Stack) {  // a tile wholly covered has nothing to evaluate (the workgroup that writes the size stays)
+        const CloudLevel &lv = sk->lv[level];
+        if (c0 >= lv.cx0 && min(c0 + kCloudTC, a.wc) <= lv.cx1 && r0 >= lv.cy0 && min(r0 + kCloudTR, a.hc) <= lv.cy1 &&
+            !(ty == 0 && tx == (a.compact ? (int)gridDim.x - 1 : 0))) {
+            if (Count && t < kCloudTC && c0 + t < a.wc) a.cnt[(size_t)(v0 + t) * a.nchunk + ty] = 0;
+            return;
+        }
+    }
     if (Write && a.compact && t <= kCloudTC) pre[t] = 0;
     // A: evaluate the tile
     for (int r = t / kCloudTC; r < kCloudTR; r += 256 / kCloudTC) {
         const int cj = r0 + r;
         bool k = false;
-        if (ci < a.wc && cj < a.hc) {
+        bool covered = false;
+        if constexpr (Stack) covered = ci >= sk->lv[level].cx0 && ci < sk->lv[level].cx1 && cj >= sk->lv[level].cy0 && cj < sk->lv[level].cy1;
+        if (ci < a.wc && cj < a.hc && !covered) {
             float4 v;
             if constexpr (Form == kTriResizedCount || Form == kTriResized)
                 k = resized_point<Fovea, Write>(a, rz, P1q, P2q, ci, cj, v);
@@ -441,8 +470,8 @@ __device__ __forceinline__ void cloud_tile(const CloudArgs &a, const CloudResize
         unsigned v = 0, w = 0;
         for (int k = t; k < tx; k += 256) v += strip_tot[k];               // strips to the left
         if (ci < a.wc) {
-            for (int k = t / kCloudTC; k < ty; k += 256 / kCloudTC) w += a.cnt[(size_t)ci * a.nchunk + k];  // chunks above
-            for (int k = t / kCloudTC; k < c; k += 256 / kCloudTC) w += col_tot[c0 + k];                    // the strip's columns to the left
+            for (int k = t / kCloudTC; k < ty; k += 256 / kCloudTC) w += a.cnt[(size_t)(v0 + c) * a.nchunk + k];  // chunks above
+            for (int k = t / kCloudTC; k < c; k += 256 / kCloudTC) w += col_tot[v0 + k];                          // the strip's columns to the left
         }
         if (v) atomicAdd(&pre[kCloudTC], v);
         if (w) atomicAdd(&pre[c], w);
@@ -457,9 +486,9 @@ __device__ __forceinline__ void cloud_tile(const CloudArgs &a, const CloudResize
             const int n = __builtin_popcountll(m);
             nrec[cc] = n;
             if (Count && c0 + cc < a.wc) {
-                a.cnt[(size_t)(c0 + cc) * a.nchunk + ty] = (unsigned)n;
+                a.cnt[(size_t)(v0 + cc) * a.nchunk + ty] = (unsigned)n;
                 if (n) {
-                    atomicAdd(&col_tot[c0 + cc], (unsigned)n);
+                    atomicAdd(&col_tot[v0 + cc], (unsigned)n);
                     atomicAdd(&strip_tot[tx], (unsigned)n);
                 }
             }
@@ -468,7 +497,25 @@ __device__ __forceinline__ void cloud_tile(const CloudArgs &a, const CloudResize
     if (Count) return;
     __syncthreads();
     // the cloud's size: one workgroup writes it
-    if (t == 0 && ty == 0 && tx == (a.compact ? (int)gridDim.x - 1 : 0))
+    if constexpr (Stack) {  // ... and each level's share of it: the strip totals summed per level (eight lanes a level), or the table's
+        if (ty == 0 && tx == (a.compact ? (int)gridDim.x - 1 : 0)) {
+            const CloudLevel &last = sk->lv[sk->F - 1];
+            if (t == 0) *a.count = a.compact ? (long long)pre[kCloudTC] + strip_tot[tx] : last.first + last.points;
+            if (sk->level_counts && a.compact) {
+                static_assert(kCloudMaxLevels * 8 <= 256, "eight lanes per level");
+                const int l = t >> 3;
+                unsigned n = 0;
+                if (l < sk->F)
+                    for (int k = t & 7; k < sk->strips; k += 8) n += strip_tot[l * sk->strips + k];
+                n += __shfl_xor(n, 1);
+                n += __shfl_xor(n, 2);
+                n += __shfl_xor(n, 4);
+                if (l < sk->F && (t & 7) == 0) sk->level_counts[l] = (long long)n;
+            } else if (sk->level_counts && t == 0) {
+                for (int l = 0; l < sk->F; l++) sk->level_counts[l] = sk->lv[l].points;
+            }
+        }
+    } else if (t == 0 && ty == 0 && tx == (a.compact ? (int)gridDim.x - 1 : 0))
         *a.count = a.compact ? (long long)pre[kCloudTC] + strip_tot[tx] : (long long)a.wc * a.hc;
     // C: every column's run, contiguous
     if (a.format == 0) {  // UGSM_CLOUD_PCL32: (x, y, z, 1.0f) and (rgb, 0, 0, 0), 32 B per record
@@ -476,7 +523,8 @@ __device__ __forceinline__ void cloud_tile(const CloudArgs &a, const CloudResize
         for (int q = t; q < kCloudTC * 2 * kCloudTR; q += 256) {
             const int cc = q / (2 * kCloudTR), j = (q >> 1) & (kCloudTR - 1), half = q & 1;
             if (j >= nrec[cc]) continue;
-            const long long o = (a.compact ? (long long)pre[kCloudTC] + pre[cc] : (long long)(c0 + cc) * a.hc + r0) + j;
+            const long long o = (a.compact ? (long long)pre[kCloudTC] + pre[cc]
+                                           : (Stack ? stack_dense_run(a, sk->lv[level], c0 + cc, r0) : (long long)(c0 + cc) * a.hc + r0)) + j;
             if (o >= a.cap) continue;
             const float4 v = rec[cc * kCloudPad + src[cc * kCloudTR + j]];
             out[2 * o + half] = half ? make_float4(v.w, 0.0f, 0.0f, 0.0f) : make_float4(v.x, v.y, v.z, 1.0f);
@@ -486,7 +534,8 @@ __device__ __forceinline__ void cloud_tile(const CloudArgs &a, const CloudResize
         for (int q = t; q < kCloudTC * kCloudTR; q += 256) {
             const int cc = q / kCloudTR, j = q & (kCloudTR - 1);
             if (j >= nrec[cc]) continue;
-            const long long o = (a.compact ? (long long)pre[kCloudTC] + pre[cc] : (long long)(c0 + cc) * a.hc + r0) + j;
+            const long long o = (a.compact ? (long long)pre[kCloudTC] + pre[cc]
+                                           : (Stack ? stack_dense_run(a, sk->lv[level], c0 + cc, r0) : (long long)(c0 + cc) * a.hc + r0)) + j;
             if (o >= a.cap) continue;
             out[o] = rec[cc * kCloudPad + src[cc * kCloudTR + j]];
         }
@@ -507,6 +556,23 @@ __global__ __launch_bounds__(256) void k_triangulate_fovea(CloudArgs a, Proj P1q
     cloud_tile<true, Form>(a, rz, P1q, P2q);
 }
 
+// the merged cloud of the fovea stack (an overload on the table): the workgroup's level from its strip, that level's planes and mapping
+// into its copy of the arguments
+template <int Form>
+__global__ __launch_bounds__(256) void k_triangulate_fovea(CloudArgs a, Proj P1q, Proj P2q, CloudStack sk)
+{
+    static_assert(Form == kTriStackCount || Form == kTriStack, "the stack forms");
+    const int level = blockIdx.x / sk.strips;
+    const CloudLevel &lv = sk.lv[level];
+    a.dx += lv.plane;
+    a.dy += lv.plane;
+    if (a.conf) a.conf += lv.plane;
+    a.left_margin = lv.left_margin;
+    a.upper_margin = lv.upper_margin;
+    a.scale = lv.scale;
+    cloud_tile<true, Form>(a, CloudResize{}, P1q, P2q, &sk, level);
+}
+
 int cloud_strips(int wc) { return (wc + kCloudTC - 1) / kCloudTC; }
 int cloud_chunks(int hc) { return (hc + kCloudTR - 1) / kCloudTR; }
 
@@ -523,6 +589,17 @@ void launch_point_cloud(hipStream_t st, const CloudArgs &args, bool fovea, const
     const CloudResize r = rz ? *rz : CloudResize{};
     if (args.compact) UGSM_LAUNCH(count, grid, dim3(256), 0, st, args, a, b, r);
     UGSM_LAUNCH(cloud, grid, dim3(256), 0, st, args, a, b, r);
+}
+
+void launch_point_cloud_stack(hipStream_t st, const CloudArgs &args, const CloudStack &sk, const double *P1, const double *P2)
+{
+    Proj a, b;
+    for (int k = 0; k < 12; k++) { a.m[k] = P1[k]; b.m[k] = P2[k]; }
+    const dim3 grid(sk.F * sk.strips, args.nchunk);
+    using Kern = void (*)(CloudArgs, Proj, Proj, CloudStack);
+    const Kern count = k_triangulate_fovea<kTriStackCount>, cloud = k_triangulate_fovea<kTriStack>;
+    if (args.compact) UGSM_LAUNCH(count, grid, dim3(256), 0, st, args, a, b, sk);
+    UGSM_LAUNCH(cloud, grid, dim3(256), 0, st, args, a, b, sk);
 }
 
 // =========================================================================================

@@ -93,10 +93,31 @@ struct CloudResize {
     int same_size;            // wc == pw && hc == ph: cv::resize copies, Z is the pixel's own
     int colour_mapped;        // the fovea form: the colour at the mapped pixel (as ugsm_point_cloud_fovea) rather than at (xx, yy)
 };
+// the merged cloud of the whole fovea stack (ugsm_point_cloud_fovea_all): the forms kTriStackCount / kTriStack, whose grid runs over
+// F * cloud_strips(wc) strips (level = strip / strips).  CloudArgs.dx / dy / conf are the stacks (level 0's planes); a workgroup takes its
+// level's planes, mapping and covered rectangle from its row of the table.  A pixel of level k >= 1 whose footprint lies wholly inside
+// level k-1's window is covered and left out (include/ugsm.h); the rule is separable and monotone, so the host hands over one interval
+// of sampled columns and one of sampled rows per level.
+struct CloudLevel {
+    long long plane;   // the level's planes inside the stacks, in floats
+    long long first;   // dense: the level's first record
+    long long points;  // dense: the level's records, wc * hc - (cx1 - cx0) * (cy1 - cy0)
+    int left_margin, upper_margin;  // ugsm_fovea_level_mapping
+    float scale;
+    int cx0, cx1, cy0, cy1;  // the covered sampled columns [cx0, cx1) and rows [cy0, cy1); nothing covered: all 0
+};
+constexpr int kCloudMaxLevels = 32;  // = UGSM_MAX_LEVELS (include/ugsm.h)
+struct CloudStack {
+    int F, strips;             // fovea levels; cloud_strips(wc)
+    long long *level_counts;   // F entries, may be null
+    CloudLevel lv[kCloudMaxLevels];
+};
 int cloud_strips(int wc);
 int cloud_chunks(int hc);
 // compact: a count launch, then the cloud launch; dense: the cloud launch.  rz: the resized forms
 void launch_point_cloud(hipStream_t st, const CloudArgs &args, bool fovea, const double *P1, const double *P2, const CloudResize *rz = nullptr);
+// the same for the merged cloud of the stack; args.cnt (compact): (F * wc) * nchunk counts, F * wc column totals, F * strips strip totals
+void launch_point_cloud_stack(hipStream_t st, const CloudArgs &args, const CloudStack &sk, const double *P1, const double *P2);
 void launch_upsample_paste(hipStream_t st, const float *src3, int W, int H, float *dst3, int W2, int H2, const float *fovH_, const float *fovV_,
                            const float *fovC_, int fovW, int fovH, int org_x, int org_y);
 // S_dx, S_dy, C of weightedDifference (MatchGPULib.cpp:1336-1437) into out3; rowsum = 3*H doubles of scratch

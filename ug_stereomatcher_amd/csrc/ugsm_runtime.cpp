@@ -2356,6 +2356,101 @@ int ugsm_fovea_mapping(int W, int H, int src_level, int dest_level, int *left_ma
     return UGSM_OK;
 }
 
+namespace {
+
+// ugsm_fovea_level_mapping for every level of the stack: the reference's centred margins for any fovea_levels (its `scaled` is
+// F-1-k), moved by this build's window offset -- level k's clamped offset ex[k] (fovea_geometry), in level-0 pixels
+int fovea_level_mappings(int W, int H, int levels, int F, int off_x, int off_y, int *fw, int *fh, int *left, int *upper, float *scale)
+{
+    int w[UGSM_MAX_LEVELS], h[UGSM_MAX_LEVELS];
+    if (F < 2 || F > levels || levels > UGSM_MAX_LEVELS) return UGSM_ERR_BAD_ARG;
+    UCHK(level_dims(W, H, F, w, h));  // (only the stack's F levels enter: a cloud of a given stack does not ask whether the coarse levels below it exist)
+    FoveaGeom g;
+    fovea_geometry(w, h, F, off_x, off_y, g);
+    *fw = g.fw;
+    *fh = g.fh;
+    for (int k = 0; k < F; k++) {
+        const int ex = k < F - 1 ? g.ox[k] - (w[k] / 2 - g.fw / 2) : 0, ey = k < F - 1 ? g.oy[k] - (h[k] / 2 - g.fh / 2) : 0;
+        left[k] = w[0] / 2 - w[F - 1 - k] / 2 + (int)lrint(ex * pow(kScale, k));
+        upper[k] = h[0] / 2 - h[F - 1 - k] / 2 + (int)lrint(ey * pow(kScale, k));
+        scale[k] = powf((float)1.41421356237309504880, (float)k);  // as ugsm_fovea_mapping for destination level 0
+    }
+    return UGSM_OK;
+}
+
+// The coverage rule along one axis (include/ugsm.h): pixel i of level k, at x1 = (float)m + (float)i * sc, is covered when
+// x1 >= (float)m_fine && x1 + sc <= (float)m_fine + (float)n * sc_fine, every operation in binary32.  Monotone in i, so the covered
+// pixels are one interval [i0, i1); of the sampled grid (pixel = index * s) that is [c0, c1).
+void covered_interval(int n, int m, float sc, int m_fine, float sc_fine, int s, int *c0, int *c1)
+{
+    const float lo = (float)m_fine, hi = (float)m_fine + (float)n * sc_fine;
+    int i0 = n, i1 = n;
+    for (int i = 0; i < n; i++) {
+        const float x1 = (float)m + (float)i * sc;
+        const bool in = x1 >= lo && x1 + sc <= hi;
+        if (in && i0 == n) i0 = i;
+        if (!in && i0 < n) { i1 = i; break; }
+    }
+    *c0 = (i0 + s - 1) / s;
+    *c1 = (i1 + s - 1) / s;
+    if (*c1 < *c0) *c1 = *c0;
+}
+
+// the table of the merged cloud's kernel: each level's planes, mapping, covered rectangle and dense records
+int cloud_stack_table(int W, int H, int levels, int F, int off_x, int off_y, int sampling, CloudStack &sk, int *fw_out, int *fh_out)
+{
+    int left[UGSM_MAX_LEVELS], upper[UGSM_MAX_LEVELS], fw, fh;
+    float scale[UGSM_MAX_LEVELS];
+    if (sampling < 1) return UGSM_ERR_BAD_ARG;
+    UCHK(fovea_level_mappings(W, H, levels, F, off_x, off_y, &fw, &fh, left, upper, scale));
+    const int wc = (fw + sampling - 1) / sampling, hc = (fh + sampling - 1) / sampling;
+    sk = CloudStack{};
+    sk.F = F;
+    sk.strips = cloud_strips(wc);
+    long long first = 0;
+    for (int k = 0; k < F; k++) {
+        CloudLevel &lv = sk.lv[k];
+        lv.plane = (long long)k * fw * fh;
+        lv.left_margin = left[k];
+        lv.upper_margin = upper[k];
+        lv.scale = scale[k];
+        if (k > 0) {
+            covered_interval(fw, left[k], scale[k], left[k - 1], scale[k - 1], sampling, &lv.cx0, &lv.cx1);
+            covered_interval(fh, upper[k], scale[k], upper[k - 1], scale[k - 1], sampling, &lv.cy0, &lv.cy1);
+            if (lv.cx0 == lv.cx1 || lv.cy0 == lv.cy1) lv.cx0 = lv.cx1 = lv.cy0 = lv.cy1 = 0;
+        }
+        lv.first = first;
+        lv.points = (long long)wc * hc - (long long)(lv.cx1 - lv.cx0) * (lv.cy1 - lv.cy0);
+        first += lv.points;
+    }
+    if (fw_out) *fw_out = fw;
+    if (fh_out) *fh_out = fh;
+    return UGSM_OK;
+}
+
+}  // namespace
+
+int ugsm_fovea_level_mapping(int W, int H, int levels, int fovea_levels, int off_x, int off_y, int src_level, int *left_margin,
+                             int *upper_margin, float *scale)
+{
+    if (!left_margin || !upper_margin || !scale || src_level < 0 || src_level >= fovea_levels) return UGSM_ERR_BAD_ARG;
+    int left[UGSM_MAX_LEVELS], upper[UGSM_MAX_LEVELS], fw, fh;
+    float sc[UGSM_MAX_LEVELS];
+    if (fovea_level_mappings(W, H, levels, fovea_levels, off_x, off_y, &fw, &fh, left, upper, sc) != UGSM_OK) return UGSM_ERR_BAD_ARG;
+    *left_margin = left[src_level];
+    *upper_margin = upper[src_level];
+    *scale = sc[src_level];
+    return UGSM_OK;
+}
+
+long long ugsm_fovea_cloud_points(int W, int H, int levels, int fovea_levels, int off_x, int off_y, int sampling, long long *per_level)
+{
+    CloudStack sk;
+    if (cloud_stack_table(W, H, levels, fovea_levels, off_x, off_y, sampling, sk, nullptr, nullptr) != UGSM_OK) return -1;
+    for (int k = 0; per_level && k < fovea_levels; k++) per_level[k] = sk.lv[k].points;
+    return sk.lv[fovea_levels - 1].first + sk.lv[fovea_levels - 1].points;
+}
+
 int ugsm_triangulate_fovea(ugsm_ctx *ctx, int slot, const float *d_stackx, const float *d_stacky, int fovW, int fovH, int src_level,
                            int left_margin, int upper_margin, float scale, const double *P1, const double *P2, float *d_xyz)
 {
@@ -2520,6 +2615,41 @@ int ugsm_point_cloud_fovea(ugsm_ctx *ctx, int slot, const float *d_stackx, const
     UCHK(fovea_cloud_args(a, d_stackx, d_stacky, d_stackc, fovW, fovH, src_level, left_margin, upper_margin, scale, d_rgbL, W, H, stride, p,
                           d_points, cap_points, d_count));
     return point_cloud(ctx, slot, a, true, P1, P2);
+}
+
+// The whole stack as one cloud: level 0, then 1 .. F-1, each without the points the finer level already covers (cloud_stack_table)
+int ugsm_point_cloud_fovea_all(ugsm_ctx *ctx, int slot, const float *d_stackx, const float *d_stacky, const float *d_stackc, int W, int H,
+                               int off_x, int off_y, const uint8_t *d_rgbL, int stride, const double *P1, const double *P2,
+                               const ugsm_cloud_params *p, void *d_points, long long cap_points, long long *d_count, long long *d_level_counts)
+{
+    if (!ctx || !p || ((uintptr_t)d_level_counts & 7)) return UGSM_ERR_BAD_ARG;
+    CloudStack sk;
+    int fw, fh;
+    UCHK(cloud_stack_table(W, H, ctx->cfg.levels, ctx->cfg.fovea_levels, off_x, off_y, p->sampling, sk, &fw, &fh));
+    UCHK(cloud_args_ok(d_stackx, d_stacky, d_stackc, d_rgbL, W, H, stride, ugsm_input_bytes_per_pixel(ctx->hooks.input_format), fw, fh, P1, P2, p, d_points, cap_points, d_count));
+    sk.level_counts = d_level_counts;
+    CloudArgs a = cloud_args(d_stackx, d_stacky, d_stackc, d_rgbL, W, H, stride, fw, fh, p, d_points, cap_points, d_count);
+    Slot *s;
+    UCHK(get_slot(ctx, slot, &s));
+    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
+    a.wc = (a.pw + a.s - 1) / a.s;
+    a.hc = (a.ph + a.s - 1) / a.s;
+    a.nchunk = cloud_chunks(a.hc);
+    a.fmt = ctx->hooks.input_format;
+    a.cnt = nullptr;
+    if (a.compact) {  // as point_cloud, over the F * wc virtual columns and F * strips virtual strips
+        const size_t cols = (size_t)sk.F * a.wc, totals = cols + (size_t)sk.F * sk.strips, need = cols * a.nchunk + totals;
+        if (need > s->cloud_cap) HIPCHK(ctx, hipStreamSynchronize(s->st));
+        UCHK(grow(ctx, s->cloud_cnt, s->cloud_cap, need));
+        a.cnt = s->cloud_cnt;
+        HIPCHK(ctx, hipMemsetAsync(a.cnt + cols * a.nchunk, 0, totals * sizeof(unsigned), s->st));
+    }
+    {
+        Timer t(ctx, s, slot, KC_MISC, (double)sk.F * a.wc * a.hc);
+        launch_point_cloud_stack(s->st, a, sk, P1, P2);
+    }
+    HIPCHK(ctx, hipGetLastError());
+    return UGSM_OK;
 }
 
 // ---- row f-1, the resized cloud (getPointCloud.cpp doReconstruction_resized / doReconstructionFOV_resized, :724-884) ----------------
