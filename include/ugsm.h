@@ -35,7 +35,8 @@ extern "C" {
                                ugsm_resized_cloud_points, ugsm_point_cloud_resized, ugsm_point_cloud_resized_fovea; the input formats --
                                UGSM_INPUT_*, ugsm_input_bytes_per_pixel, ugsm_input_format_from_encoding, ugsm_set_input_format,
                                ugsm_get_input_format; the merged cloud of the fovea stack -- ugsm_fovea_level_mapping, ugsm_fovea_cloud_points,
-                               ugsm_point_cloud_fovea_all
+                               ugsm_point_cloud_fovea_all; the LR check of the foveated calls -- UGSM_LR_FULL / UGSM_LR_FOVEATED, ugsm_set_lr_check,
+                               ugsm_get_lr_check, ugsm_last_lr_marked_levels
                                6: the kernel choices follow what is in flight, not ugsm_config.slots: ugsm_plan_level takes `alone`, ugsm_plan_level_in_frame
                                is gone, ugsm_level_plan.latency_policy is .alone; ugsm_enqueue_* returns UGSM_OK once the pair is accepted (a failed
                                CALL is reported through ugsm_completion.status only); the fovea shard carries a status word (a rank that fails still
@@ -106,7 +107,8 @@ typedef struct ugsm_config {
                              full mode only (ugsm_match_full / ugsm_submit_full), the pair is matched a second time with the images
                              exchanged, and the confidence of every left pixel whose match (x + dx, y + dy) in the right-to-left
                              field does not point back within this many pixels, in x or in y, is set to 0 (dx, dy unchanged).
-                             Doubles the matching work of a call. */
+                             Doubles the matching work of a call.  The foveated calls take the check through ugsm_set_lr_check
+                             (below), which also changes or switches off the threshold of a live context. */
     int streams;          /* HIP streams the slots' work is dealt onto; 0 (default) = one per slot.  With fewer streams than slots, slot i
                              enqueues on the stream of slot i % streams: several pairs QUEUED per stream.  The chip runs four hardware
                              queues well and no more, so a throughput host uses streams = 4 and slots = 8: a
@@ -209,6 +211,40 @@ int ugsm_input_format_from_encoding(const char *encoding);
 /* UGSM_ERR_BAD_ARG for an unknown format (the format is left as it was).  Takes effect for the images handed over afterwards. */
 int ugsm_set_input_format(ugsm_ctx *ctx, int format);
 int ugsm_get_input_format(const ugsm_ctx *ctx, int *format);
+
+/* ---- the LR check: which calls apply it ------------------------------------------------------------------------------------------
+ *
+ * The check is a setting of the context: a threshold tau and the set of calls that apply it.  ugsm_create leaves a context at
+ * (ugsm_config.lr_check_threshold, UGSM_LR_FULL): the full-mode calls check, the foveated calls do not, as in every earlier ABI.
+ *   UGSM_LR_FULL      ugsm_match_full, ugsm_submit_full[_host|_batch|_batch_host] and the full-mode queue: the pair is matched a second time
+ *                     with the images exchanged (ugsm_config.lr_check_threshold above); batches run pair by pair
+ *   UGSM_LR_FOVEATED  ugsm_match_foveated, ugsm_match_foveated_full, ugsm_submit_foveated[_host], ugsm_submit_foveated_batch[_host] and,
+ *                     through those, ugsm_enqueue_foveated[_host|_managed]
+ * THE FOVEATED CHECK.  Let S be the stack of the call and B the stack of the same call with the two images exchanged -- the same offsets,
+ * the same context: bit for bit what ugsm_submit_foveated(R, L, ..) returns.  The windows of L and R sit at the same coordinates, so level
+ * k of S and level k of B live on one fovW x fovH grid, and each level k = 0 .. F-1 by itself is checked as ugsm_stage_lr_check checks a
+ * fovW x fovH field: with sx = tex_index((ix + 0.5f) + dx, fovW) and sy likewise, both clamped to the window, the confidence of pixel
+ * (ix, iy) becomes 0 where !(|dx + B.dx[sy][sx]| <= tau) or the same fails in y.  stackH, stackV and the pyramid stacks are untouched; B never
+ * leaves the library; the check runs after the last level and never feeds back into the matching.  tau is in pixels OF THE LEVEL it is applied
+ * to (a pixel of level k spans 1.41^k pixels of the image); a threshold per level is not offered.  ugsm_match_foveated_full reconstructs
+ * from the checked stack: the zeros travel through the levels like any confidence.  A compact cloud (ugsm_point_cloud_fovea[_all],
+ * min_conf > 0) of a checked stack leaves the marked pixels out.
+ * What it costs: the right-to-left match is one more pair of the same call -- the same two pyramids, built once, with the L and R views
+ * exchanged -- so a checked call of n pairs runs 2 n pairs through the levels in lockstep (as ugsm_submit_foveated_batch does, in launches of
+ * at most UGSM_MAX_BATCH; the cost kernel alone takes one launch per direction), one launch checks the whole stack, and B lives in
+ * 3 (F + 1) fovW fovH floats per pair of the slot (24 MB at 16 MP, counted by ugsm_context_device_bytes).  Measured on one MI355X: a
+ * checked blocking call takes 1.73 x the plain one at 16 MP and 1.55 x at 1080p, where a second match would make it 2 x.
+ * NOT checked, whatever the setting: ugsm_submit_fovea_coarse / _fine, ugsm_submit_fovea_shard and the ugsm_stage_* entry points.
+ *
+ * ugsm_set_lr_check: UGSM_ERR_BAD_ARG for !(tau >= 0) (the rule of ugsm_create) and for modes outside 0 .. 3; tau == 0 or modes == 0 switch
+ * the check off, modes without UGSM_LR_FULL switch the full-mode check off (ugsm_last_lr_marked is then -1 after a full-mode call).
+ * UGSM_LR_FOVEATED on a context with early_exit_threshold > 0 or kernel_path 1: UGSM_ERR_BAD_ARG -- those contexts run every level pair by
+ * pair and have no batch dimension to carry the second direction in.  The setting is CAPTURED WHEN A SLOT-LEVEL CALL IS MADE; while pairs
+ * enqueued with ugsm_enqueue_* are outstanding it cannot change (UGSM_ERR_STATE): set it before the first enqueue. */
+#define UGSM_LR_FULL     1
+#define UGSM_LR_FOVEATED 2
+int ugsm_set_lr_check(ugsm_ctx *ctx, float tau, int modes);
+int ugsm_get_lr_check(const ugsm_ctx *ctx, float *tau, int *modes);
 
 /* ---- the service path: host buffers in, host buffers out ------------------------ */
 
@@ -605,8 +641,12 @@ int ugsm_stage_weighted_difference(ugsm_ctx *ctx, const float *d_new3, const flo
  * d_left3's confidence where d_right3 does not point back within tau; *marked (host, may be NULL) = number of pixels marked. */
 int ugsm_stage_lr_check(ugsm_ctx *ctx, float *d_left3, const float *d_right3, int W, int H, float tau, long long *marked);
 /* Pixels the LR check of the last full-mode call on `slot` marked (-1: the call ran without the check; a batched call, which such a
- * context runs pair by pair: of its last pair).  Valid after ugsm_wait. */
+ * context runs pair by pair: of its last pair).  After a checked foveated call (UGSM_LR_FOVEATED): the sum over the levels of the call's
+ * last pair.  Valid after ugsm_wait. */
 long long ugsm_last_lr_marked(ugsm_ctx *ctx, int slot);
+/* The same level by level, for pair `pair` of the last call on `slot`: per_level[0 .. fovea_levels).  UGSM_ERR_STATE if that call ran
+ * without the foveated check, UGSM_ERR_BAD_ARG for a bad slot or pair or a null pointer.  Valid after ugsm_wait. */
+int ugsm_last_lr_marked_levels(ugsm_ctx *ctx, int slot, int pair, long long *per_level);
 /* Iterations each level of the last call on `slot` actually ran (early_exit_threshold > 0 can stop a level early);
  * per_level[UGSM_MAX_LEVELS], -1 for levels not run.  ugsm_stage_iterate records its count at index 0. */
 int ugsm_last_iterations(ugsm_ctx *ctx, int slot, int *per_level);

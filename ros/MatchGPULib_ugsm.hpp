@@ -32,11 +32,15 @@ public:
     {
         ugsm_config cfg;
         ugsm_default_config(&cfg);
+        int lr_modes = -1;  // "-lrmodes=N" not given: the context's default, (lr_check_threshold, UGSM_LR_FULL)
         for (int i = 1; i < argc; i++) {
             if (argv[i] && std::strncmp(argv[i], "-device=", 8) == 0) cfg.device = std::atoi(argv[i] + 8);
             // not in the reference: "-lrcheck=TAU" switches the optional LR-consistency check on (ugsm_config.lr_check_threshold;
             // full mode only; off by default, and the results are the reference's only while it is off)
             if (argv[i] && std::strncmp(argv[i], "-lrcheck=", 9) == 0) cfg.lr_check_threshold = (float)std::atof(argv[i] + 9);
+            // ... and "-lrmodes=N" names the calls that apply it (UGSM_LR_FULL = 1, UGSM_LR_FOVEATED = 2, both = 3; ugsm_set_lr_check):
+            // with 2 or 3 the foveated stacks are checked level by level, both directions in one lockstep call.  Without it: full mode only
+            if (argv[i] && std::strncmp(argv[i], "-lrmodes=", 9) == 0) lr_modes = std::atoi(argv[i] + 9);
             // not in the reference: "-inflight=N" sizes the context for the pipelined calls below (N pairs outstanding in the library's
             // queue: min(N, 4) slots, ceil(N / slots) pairs per call at most); 1 = the reference's one blocking call at a time
             if (argv[i] && std::strncmp(argv[i], "-inflight=", 10) == 0) frames_in_flight = std::atoi(argv[i] + 10);
@@ -49,6 +53,13 @@ public:
         cfg.fovea_levels = foveatelevel;
         const int st = ugsm_create(&cfg, &ctx_);
         if (st != UGSM_OK) throw std::runtime_error(std::string("ugsm_create: ") + ugsm_status_string(st));
+        if (lr_modes >= 0) {
+            const int sl = ugsm_set_lr_check(ctx_, cfg.lr_check_threshold, lr_modes);
+            if (sl != UGSM_OK) {
+                ugsm_destroy(ctx_);
+                throw std::runtime_error(std::string("ugsm_set_lr_check (-lrmodes): ") + ugsm_status_string(sl));
+            }
+        }
     }
     ~MatchGPULib() { ugsm_destroy(ctx_); }
     MatchGPULib(const MatchGPULib &) = delete;
@@ -64,6 +75,9 @@ public:
     // (not in the reference) the byte layout of the images the next calls hand over: UGSM_INPUT_RGB8 (what cv_bridge's toCvCopy(.., RGB8)
     // gives), or ugsm_input_format_from_encoding(msg.encoding) for a message read in place (view() below).  UGSM_ERR_BAD_ARG for an unknown one.
     int setInputFormat(int format) { return ugsm_set_input_format(ctx_, format); }
+    // (not in the reference) the LR check of a live node: the threshold (0 = off) and the calls that apply it (UGSM_LR_FULL | UGSM_LR_FOVEATED).
+    // UGSM_ERR_STATE while pipelined pairs are outstanding.
+    int setLRCheck(float tau, int modes) { return ugsm_set_lr_check(ctx_, tau, modes); }
 
     // (not in the reference) a sensor_msgs::Image -- anything with height, width, step, data and header -- read in place: what the templated
     // calls below take instead of a cv_bridge copy (->image.{rows,cols,step,data}, ->header).  The message must outlive the call.

@@ -1,0 +1,154 @@
+#!/usr/bin/env python3
+"""What the LR check of the foveated calls costs (ugsm_set_lr_check, UGSM_LR_FOVEATED) -- on ONE box, in one session.
+
+    python tools/lr_bench.py [--parent-tree DIR] [--rounds 3] [--out profiles/lr_fovea_bench.json]
+
+At 16 MP (4928 x 3264) and 1080p, 14 / 7 levels, images resident on the device, events off, every measurement a child process of its own
+(one context per process, as tools/ab.py), the configurations of a group taking turns round by round, every child's value kept:
+  (a) one blocking plain foveated call: ugsm_submit_foveated + ugsm_wait on a one-slot context, the median wall-clock time of --reps calls
+      after --warmup -- on this build, and on a build of the parent commit when --parent-tree names a tree that holds one
+      (DIR/ug_stereomatcher_amd with its libugsm.so; the child then imports that package instead of this one);
+  (b) the same call with the check on;
+  (c) a queue burst of --burst foveated pairs on four slots with batches of eight, as bench.py --workload fovea16mp forms it
+      (ugsm_enqueue_foveated, polling, drain), plain and checked, in pairs per second.
+`spread` is the range (max - min) of the (a) children of this build; the acceptance of the change that added the check is written beside
+the numbers: (a) on this build within the spread of (a) on the parent, and (b) below 2 x (a) by more than the spread -- two plain calls
+are what running the second direction after the first would cost before the check itself.
+"""
+import argparse
+import json
+import os
+import statistics
+import subprocess
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SIZES = {"16mp": (4928, 3264), "1080p": (1920, 1080)}
+LEVELS, F = 14, 7
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--parent-tree", default=None, help="a checkout of the parent commit with its libraries built")
+ap.add_argument("--rounds", type=int, default=3)
+ap.add_argument("--reps", type=int, default=40)
+ap.add_argument("--warmup", type=int, default=8)
+ap.add_argument("--burst", type=int, default=96)
+ap.add_argument("--tau", type=float, default=1.0)
+ap.add_argument("--sizes", nargs="*", default=list(SIZES))
+ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "lr_fovea_bench.json"))
+ap.add_argument("--child", choices=["call", "burst"], help="(internal) measure in this process, print one JSON line")
+ap.add_argument("--tree", default=ROOT, help="(internal) the tree whose package the child loads")
+ap.add_argument("--checked", type=int, default=0, help="(internal)")
+ap.add_argument("--size", default="16mp", help="(internal)")
+args = ap.parse_args()
+
+
+def child():
+    sys.path.insert(0, args.tree)
+    import numpy as np
+    from ug_stereomatcher_amd import _lib, synth
+    assert os.path.dirname(os.path.abspath(_lib.__file__)) == os.path.join(os.path.abspath(args.tree), "ug_stereomatcher_amd")
+    W, H = SIZES[args.size]
+    fw, fh = _lib.fovea_dims(W, H, LEVELS, F)
+    L, R = synth.make_pair(W, H, synth.BASE_SEED + 2)[:2]
+    nbytes = 3 * F * fh * fw * 4
+    if args.child == "call":
+        with _lib.Context(levels=LEVELS, fovea_levels=F, slots=1) as c:
+            if args.checked:
+                c.set_lr_check(args.tau, _lib.UGSM_LR_FOVEATED)
+            dL, dR, dS = c.to_device(L), c.to_device(R), c.alloc(nbytes)
+            ts = []
+            for k in range(args.warmup + args.reps):
+                t0 = time.perf_counter()
+                c.check(c.lib.ugsm_submit_foveated(c.handle, 0, dL, dR, W, H, 3 * W, 0, 0, dS, None, None))
+                c.check(c.lib.ugsm_wait(c.handle, 0))
+                ts.append((time.perf_counter() - t0) * 1e3)
+            ts = ts[args.warmup:]
+            marked = int(c.lib.ugsm_last_lr_marked(c.handle, 0))
+            out = dict(ms=statistics.median(ts), ms_min=min(ts), ms_max=max(ts), marked=marked, device_bytes=c.device_bytes())
+    else:
+        slots, B = 4, 8
+        with _lib.Context(levels=LEVELS, fovea_levels=F, slots=slots, batch=B) as c:
+            if args.checked:
+                c.set_lr_check(args.tau, _lib.UGSM_LR_FOVEATED)
+            dL, dR = c.to_device(L), c.to_device(R)
+            cap = (slots + 1) * B
+            ring = [c.alloc(nbytes) for _ in range(cap)]
+
+            def run(m):
+                sizes, last = [], None
+                for k in range(m):
+                    c.enqueue_foveated(dL, dR, W, H, 3 * W, (0, 0), ring[k % cap], k)
+                    while True:
+                        d = c.next_done(False)
+                        if d is None:
+                            break
+                        if d.call_index != last:
+                            sizes.append(d.call_pairs)
+                            last = d.call_index
+                for d in c.drain():
+                    if d.call_index != last:
+                        sizes.append(d.call_pairs)
+                        last = d.call_index
+                return sizes
+            run(2 * slots * B)
+            t0 = time.perf_counter()
+            sizes = run(args.burst)
+            dt = time.perf_counter() - t0
+            out = dict(pairs_per_s=args.burst / dt, calls=sizes, device_bytes=c.device_bytes())
+    print("LRBENCH " + json.dumps(out), flush=True)
+
+
+def measure(kind, size, tree, checked):
+    cmd = [sys.executable, os.path.abspath(__file__), "--child", kind, "--size", size, "--tree", tree, "--checked", str(int(checked)),
+           "--reps", str(args.reps), "--warmup", str(args.warmup), "--burst", str(args.burst), "--tau", str(args.tau)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=240)
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("LRBENCH ")]
+    if r.returncode != 0 or not lines:
+        raise SystemExit(f"child failed ({r.returncode}): {' '.join(cmd)}\n{r.stdout[-2000:]}\n{r.stderr[-2000:]}")
+    return json.loads(lines[-1][8:])
+
+
+def main():
+    parent = os.path.abspath(args.parent_tree) if args.parent_tree else None
+    if parent and not os.path.exists(os.path.join(parent, "ug_stereomatcher_amd", "libugsm.so")):
+        raise SystemExit(f"{parent}: no built ug_stereomatcher_amd/libugsm.so")
+    result = dict(tool="tools/lr_bench.py", levels=LEVELS, fovea_levels=F, tau=args.tau, rounds=args.rounds, reps=args.reps, burst=args.burst,
+                  parent_measured=bool(parent), sizes={})
+    for size in args.sizes:
+        calls = {"a_this": (ROOT, 0), "b_checked": (ROOT, 1)}
+        if parent:
+            calls["a_parent"] = (parent, 0)
+        bursts = {"c_plain": 0, "c_checked": 1}
+        kept = {k: [] for k in list(calls) + list(bursts)}
+        for rnd in range(args.rounds):
+            names = list(calls)
+            for name in (names if rnd % 2 == 0 else names[::-1]):     # alternating order
+                tree, checked = calls[name]
+                kept[name].append(measure("call", size, tree, checked))
+                print(size, name, kept[name][-1], flush=True)
+            names = list(bursts)
+            for name in (names if rnd % 2 == 0 else names[::-1]):
+                kept[name].append(measure("burst", size, ROOT, bursts[name]))
+                print(size, name, kept[name][-1], flush=True)
+        med = {k: statistics.median(v["ms"] for v in kept[k]) for k in calls}
+        a_vals = [v["ms"] for v in kept["a_this"]]
+        spread = max(a_vals) - min(a_vals)
+        rate = {k: statistics.median(v["pairs_per_s"] for v in kept[k]) for k in bursts}
+        row = dict(W=SIZES[size][0], H=SIZES[size][1], children=kept, a_ms=med["a_this"], b_ms=med["b_checked"], spread_ms=spread,
+                   b_over_a=med["b_checked"] / med["a_this"], c_plain_pairs_per_s=rate["c_plain"], c_checked_pairs_per_s=rate["c_checked"],
+                   c_plain_over_checked=rate["c_plain"] / rate["c_checked"],
+                   b_below_two_a_by_more_than_spread=bool(2 * med["a_this"] - med["b_checked"] > spread))
+        if parent:
+            pv = [v["ms"] for v in kept["a_parent"]]
+            row.update(a_parent_ms=med["a_parent"], a_parent_spread_ms=max(pv) - min(pv),
+                       a_equals_parent_within_spread=bool(abs(med["a_this"] - med["a_parent"]) <= max(spread, max(pv) - min(pv))))
+        result["sizes"][size] = row
+        print(json.dumps({k: v for k, v in row.items() if k != "children"}), flush=True)
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    json.dump(result, open(args.out, "w"), indent=1, sort_keys=True)
+    print(f"wrote {args.out}")
+
+
+if __name__ == "__main__":
+    child() if args.child else main()

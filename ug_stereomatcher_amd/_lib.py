@@ -58,6 +58,8 @@ EXPORTS = [
     "ugsm_fovea_level_mapping", "ugsm_fovea_cloud_points", "ugsm_point_cloud_fovea_all",
     # the input formats
     "ugsm_input_bytes_per_pixel", "ugsm_input_format_from_encoding", "ugsm_set_input_format", "ugsm_get_input_format",
+    # the LR check of the foveated calls
+    "ugsm_set_lr_check", "ugsm_get_lr_check", "ugsm_last_lr_marked_levels",
 ]
 # ... and what include/ugsm_dev.h adds (libugsm_dev.so only)
 DEV_EXPORTS = ["ugsm_stage_poly_probe", "ugsm_stage_div3_probe", "ugsm_stage_div_probe", "ugsm_stage_range_words"]
@@ -70,6 +72,10 @@ UGSM_INPUT_BGR8 = 1
 UGSM_INPUT_RGBA8 = 2
 UGSM_INPUT_BGRA8 = 3
 UGSM_INPUT_MONO8 = 4
+
+# which calls apply the LR check (ugsm_set_lr_check); ugsm_create leaves a context at (lr_check_threshold, UGSM_LR_FULL)
+UGSM_LR_FULL = 1
+UGSM_LR_FOVEATED = 2
 
 UGSM_CLOUD_PCL32 = 0     # pcl::PointXYZRGB in memory: x, y, z, 1.0f, rgb word, 12 zero bytes (32 B)
 UGSM_CLOUD_XYZRGB16 = 1  # x, y, z, rgb word (16 B)
@@ -260,6 +266,9 @@ def load(dev: bool = False):
     lib.ugsm_stage_lr_check.argtypes = [vp, vp, vp, i, i, C.c_float, C.POINTER(C.c_longlong)]
     lib.ugsm_last_lr_marked.argtypes = [vp, i]
     lib.ugsm_last_lr_marked.restype = C.c_longlong
+    lib.ugsm_set_lr_check.argtypes = [vp, C.c_float, i]
+    lib.ugsm_get_lr_check.argtypes = [vp, C.POINTER(C.c_float), ip]
+    lib.ugsm_last_lr_marked_levels.argtypes = [vp, i, i, C.POINTER(C.c_longlong)]
     lib.ugsm_slot_stream.argtypes = [vp, i, C.POINTER(vp)]
     lib.ugsm_get_kernel_stats.argtypes = [vp, C.POINTER(KernelStat), i]
     lib.ugsm_reset_kernel_stats.argtypes = [vp]
@@ -484,6 +493,26 @@ class Context:
         f = C.c_int()
         self.check(self.lib.ugsm_get_input_format(self._h, C.byref(f)))
         return f.value
+
+    # ---- the LR check (ugsm_set_lr_check): captured by every slot-level call; fixed while the queue holds pairs ----------------------------
+    def set_lr_check(self, tau: float, modes: int = UGSM_LR_FULL | UGSM_LR_FOVEATED):
+        self.check(self.lib.ugsm_set_lr_check(self._h, float(tau), int(modes)))
+
+    @property
+    def lr_check(self):
+        """(tau, modes)"""
+        tau, modes = C.c_float(), C.c_int()
+        self.check(self.lib.ugsm_get_lr_check(self._h, C.byref(tau), C.byref(modes)))
+        return tau.value, modes.value
+
+    def last_lr_marked(self, slot: int = 0) -> int:
+        return int(self.lib.ugsm_last_lr_marked(self._h, slot))
+
+    def last_lr_marked_levels(self, slot: int = 0, pair: int = 0):
+        """Pixels the foveated check marked on each level (0 = finest first) of pair `pair` of the last call on `slot`."""
+        out = (C.c_longlong * UGSM_MAX_LEVELS)()
+        self.check(self.lib.ugsm_last_lr_marked_levels(self._h, slot, pair, out))
+        return [int(v) for v in out[:self.cfg.fovea_levels]]
 
     def check_image(self, a: np.ndarray):
         """(H, W) uint8 for mono8, (H, W, 3) for rgb8 / bgr8, (H, W, 4) for rgba8 / bgra8, matching the context's input format; rows may be padded

@@ -97,6 +97,34 @@ void launch_lr_check(hipStream_t st, float *left3, const float *right3, int W, i
 {
     UGSM_LAUNCH(k_lr_check, grid2(W, H), dim3(256), 0, st, left3, right3, W, H, tau, marked);
 }
+// The stack form: the same rule on every level of the fovea stacks of ls.n pairs (LrStack, ugsm_launch.hpp), blockIdx.z = pair x F + level.
+// The two stacks of a pair have one layout, so a level's dx, dy and conf planes lie F, 2 F levels apart in either.  One count word per
+// (pair, level): whole numbers, so the order of the waves' additions never shows.
+__global__ __launch_bounds__(256) void k_lr_check(float *__restrict__ stack0, const float *__restrict__ back0, int fovW, int fovH, float tau,
+                                                  unsigned long long *__restrict__ marked, LrStack ls)
+{
+    const int ix = blockIdx.x * blockDim.x + threadIdx.x, iy = blockIdx.y;
+    const int b = blockIdx.z / ls.F, k = blockIdx.z - b * ls.F;
+    const size_t n = (size_t)fovW * fovH, pl = (size_t)ls.F * n;  // a level's plane; a plane of the stack
+    float *const fwd = shifted(stack0, ls.fwd[b]) + (size_t)k * n;
+    const float *const back = shifted(back0, ls.back[b]) + (size_t)k * n;
+    bool bad = false;
+    if (ix < fovW) {
+        const size_t at = (size_t)iy * fovW + ix;
+        const float dxl = fwd[at], dyl = fwd[pl + at];
+        const int sx = tex_index(((float)ix + 0.5f) + dxl, fovW), sy = tex_index(((float)iy + 0.5f) + dyl, fovH);
+        const size_t rt = (size_t)sy * fovW + sx;
+        const float ex = fabsf(dxl + back[rt]), ey = fabsf(dyl + back[pl + rt]);
+        bad = !(ex <= tau) || !(ey <= tau);
+        if (bad) fwd[2 * pl + at] = 0.0f;
+    }
+    const unsigned long long m = __builtin_amdgcn_ballot_w64(bad);
+    if ((threadIdx.x & 63) == 0 && m) atomicAdd(marked + blockIdx.z, (unsigned long long)__builtin_popcountll(m));
+}
+void launch_lr_check(hipStream_t st, float *stack0, const float *back0, int fovW, int fovH, float tau, unsigned long long *marked, const LrStack &ls)
+{
+    UGSM_LAUNCH(k_lr_check, grid2(fovW, fovH, ls.n * ls.F), dim3(256), 0, st, stack0, back0, fovW, fovH, tau, marked, ls);
+}
 
 // --------------------------------------------------------------------------------------
 // MatchGPULib.cpp:332-338 : rgb8 interleaved -> 3 planar f32; every input layout (InLayout, ugsm_device.hpp) an instance, each pixel read

@@ -63,6 +63,15 @@ void launch_copy_view(hipStream_t st, Img3 src, int W, int H, float *dst, size_t
 void launch_rgb_planes(hipStream_t st, const uint8_t *rgb, int stride, int W, int H, float *planes, int fmt = 0);
 // LR-consistency check (north_star; no reference counterpart): zeroes the confidence of left3 where right3 does not point back within tau
 void launch_lr_check(hipStream_t st, float *left3, const float *right3, int W, int H, float tau, unsigned long long *marked);
+// The stack form (a checked foveated call, ugsm_set_lr_check): every level of the fovea stacks of n pairs in ONE launch, grid.z = pair x F +
+// level.  A stack is 3 x (F fovH) x fovW floats (plane p of level k at (p F + k) fovW fovH); level k of pair b's left-to-right stack
+// (stack0 + fwd[b] bytes: the caller's buffer) is checked against level k of its right-to-left stack (back0 + back[b] bytes: the slot's)
+// by the rule above, on the level's own fovW x fovH grid.  marked[b * F + k] counts the pixels marked (zeroed by the caller).
+struct LrStack {
+    int n, F;
+    long long fwd[kMaxBatch], back[kMaxBatch];
+};
+void launch_lr_check(hipStream_t st, float *stack0, const float *back0, int fovW, int fovH, float tau, unsigned long long *marked, const LrStack &ls);
 // X, Y, Z planes from the full-resolution (dx, dy) and the two 3x4 projection matrices
 void launch_triangulate(hipStream_t st, const float *dispx, const float *dispy, int W, int H, const double *P1, const double *P2, float *xyz);
 void launch_triangulate_fovea(hipStream_t st, const float *stackx, const float *stacky, int fovW, int fovH, int src_level, int left_margin,

@@ -66,6 +66,10 @@ struct Slot {
     // pair b's pyramids at pyrL / pyrR + b * pyr_stride, its level buffers (A, d0, d1) at + b * lvl_stride, its range word at range_bad + b.
     int nb = 1;
     size_t pyr_stride = 0, lvl_stride = 0;  // floats
+    // A checked foveated call (ugsm_set_lr_check, UGSM_LR_FOVEATED) matches both directions in lockstep: while its levels run, nb = 2 nreal
+    // VIRTUAL pairs -- virtual pair nreal + b is pair b with the L and R views exchanged (pair_pyr) -- and lvl_stride is the room of one
+    // fovea field, so that both directions' fields lie in the level buffers the slot holds.  Everywhere else nreal == nb.
+    int nreal = 1;
     float *A = nullptr, *Rw = nullptr, *B = nullptr, *d0 = nullptr, *d1 = nullptr;
     // Side stream of the slot (round 3): the right image's upload and pyramid, and then A = G_clamp * L^2 of every full-frame level
     // (MatchGPULib.cpp:1866-1875, once per level), run there beside the left pyramid and the coarse levels' iterations -- launches
@@ -90,8 +94,9 @@ struct Slot {
     hipEvent_t ev_in = nullptr, ev_L = nullptr, ev_R = nullptr, ev_A[UGSM_MAX_LEVELS] = {};
     float *lr = nullptr;     // LR check: the right-to-left field of level 0 (3 planes) + one 8-byte counter behind it
     size_t lr_cap = 0;
-    unsigned long long *lr_host = nullptr;  // page-locked copy of the counter
+    unsigned long long *lr_host = nullptr;  // page-locked copies: word 0 the full-mode counter, then one word per (pair, level) of a checked foveated call
     bool lr_ran = false;
+    int lr_fov_pairs = 0, lr_fov_F = 0;  // the last call on the slot ran the foveated check on this many pairs of this many levels (0: it did not)
     float *Apyr = nullptr;   // A of level i at Apyr + off[i] (same layout as the pyramids)
     size_t apyr_cap = 0;
     int a_from = -1;         // levels a_from .. top have their A in Apyr (ev_A recorded); -1: none (A is computed in line)
@@ -218,6 +223,8 @@ struct ugsm_ctx {
     int smooth_big_min = 0;  // development override: levels of at least this many pixels run k_smooth_fused on its 112-column tile (0 = by the mode)
     int smooth_rows = 0;  // height of k_smooth_fused's 112-column tile: 0 = by policy (smooth_rows_for), > 0 fixed, -1 / -2 = the latency / throughput rule
     long long batch_max_px = 0;  // development override of kBatchMaxPixels (batch_level): levels up to this size go through a batched call as one launch; < 0 = none
+    float lr_tau = 0.0f;  // the LR check (ugsm_set_lr_check; ugsm_create: ugsm_config.lr_check_threshold, UGSM_LR_FULL): the threshold ...
+    int lr_modes = 0;     // ... and the calls that apply it (UGSM_LR_*)
     CtxHooks hooks;  // the queue (ugsm_queue.cpp) and the RCCL shard (ugsm_shard.cpp): layers over the slot API
     long long dev_bytes = 0;    // device memory held by the slots' growable buffers (grow); ugsm_context_device_bytes
     std::unordered_map<const void *, size_t> dev_allocs;  // ... buffer by buffer, so that every release is accounted whatever path it takes
@@ -434,7 +441,7 @@ int prepare_slot(ugsm_ctx *ctx, Slot &s, int W, int H, int nb = 1)
     s.W = W;
     s.H = H;
     s.levels = levels;
-    s.nb = nb;
+    s.nb = s.nreal = nb;
     for (int i = 0; i < UGSM_MAX_LEVELS; i++) s.iters_run[i] = -1;
     s.have_pyr = false;
     s.have_coarse = false;
@@ -642,12 +649,20 @@ void set_policy(ugsm_ctx *c, const DevKnobs &k)
 struct Grp {
     int b0, n;
 };
-// f(Grp) for the whole batch in one launch (`batched`) or pair by pair
+// pairs per launch of a batched level of a call of nb pairs: all of them; the 2 x 9 .. 2 x 16 virtual pairs of a checked foveated call
+// (Slot::nreal) in launches of equal size, none above kMaxBatch (what a Batch holds)
+int group_pairs(int nb)
+{
+    const int launches = (nb + kMaxBatch - 1) / kMaxBatch;
+    return (nb + launches - 1) / launches;
+}
+// f(Grp) for the whole batch in one launch (`batched`; group_pairs(nb) pairs each where one launch cannot hold them) or pair by pair
 template <class F>
 void for_groups(int nb, bool batched, F &&f)
 {
     if (batched && nb > 1) {
-        f(Grp{0, nb});
+        const int per = group_pairs(nb);
+        for (int b0 = 0; b0 < nb; b0 += per) f(Grp{b0, std::min(per, nb - b0)});
         return;
     }
     for (int b = 0; b < nb; b++) f(Grp{b, 1});
@@ -761,7 +776,7 @@ bool batch_level(const ugsm_ctx *ctx, int W, int H)
     return (long long)W * H <= thr;
 }
 // pairs a launch of a W x H level of the call in `s` holds
-int launch_pairs(const ugsm_ctx *ctx, const Slot &s, int W, int H) { return (s.nb > 1 && batch_level(ctx, W, H)) ? s.nb : 1; }
+int launch_pairs(const ugsm_ctx *ctx, const Slot &s, int W, int H) { return (s.nb > 1 && batch_level(ctx, W, H)) ? group_pairs(s.nb) : 1; }
 
 int small_max_px(const ugsm_config &cfg, bool alone)
 {
@@ -946,6 +961,13 @@ int run_level(ugsm_ctx *ctx, Slot &s, int si, const Img3 *Lv, const Img3 *Rv, in
     }
     // (k_cost_split -- libugsm_dev.so, march_min_pixels < 0: the levels no other form covers -- has no batch index: pair by pair)
     const bool cost_batched = batched && (march4 || march || small);
+    // K-cost moves a pair's L and R views by ONE offset (Batch::img), which serves the pairs of one direction only -- pair b's views lie
+    // b pyramids behind pair 0's in both images, virtual pair nreal + b's do so with the images exchanged -- so where a checked foveated
+    // call (Slot::nreal) runs, a K-cost launch holds the pairs of one direction: two launches where every other kernel of the level has one.
+    auto cost_groups = [&](auto &&f) {
+        if (s.nb == s.nreal) return for_groups(s.nb, cost_batched, f);
+        for (int dir = 0; dir < 2; dir++) for_groups(s.nreal, cost_batched, [&](Grp g) { f(Grp{g.b0 + dir * s.nreal, g.n}); });
+    };
     for (int m = m_from; m <= m_to; m++) {
         const int blend = !(is_top && m == 1);  // MatchGPULib.cpp:2223
         if (ref) {
@@ -961,7 +983,7 @@ int run_level(ugsm_ctx *ctx, Slot &s, int si, const Img3 *Lv, const Img3 *Rv, in
             launch_cost_ref(s.st, Lv[0], s.Rw, A3, s.B, cur, other, W, H, thr[m - 1], blend, (m == m_to) ? dbg8 : nullptr);
         } else {
             const bool seeded = seed && m == m_from;
-            for_groups(s.nb, cost_batched, [&](Grp g) {
+            cost_groups([&](Grp g) {
                 Timer t(ctx, &s, si, march4 ? KC_COST_MARCH4 : (march ? KC_COST_MARCH : (small ? KC_COST_SMALL : KC_COST)), px * g.n);
                 const size_t fo = g.b0 * s.lvl_stride;
                 const Img3 L = Lv[g.b0], R = Rv[g.b0];
@@ -1009,6 +1031,18 @@ Img3 level_view(const Slot &s, const float *pyr, int lev, int ox, int oy)
 void full_views(const Slot &s, const float *pyr, int lev, Img3 *out)
 {
     for (int b = 0; b < s.nb; b++) out[b] = level_view(s, pyr + b * s.pyr_stride, lev, 0, 0);
+}
+
+// The pyramid that pair v of the call matches as its left (side 0) or right (side 1) image.  The virtual pairs nreal .. 2 nreal - 1 of a
+// checked foveated call are the pairs 0 .. nreal - 1 with the two exchanged: the right-to-left match reads the same two pyramids.
+const float *pair_pyr(const Slot &s, int side, int v)
+{
+    const bool back = v >= s.nreal;
+    return ((side == 0) != back ? s.pyrL : s.pyrR) + (size_t)(back ? v - s.nreal : v) * s.pyr_stride;
+}
+void side_views(const Slot &s, int side, int lev, Img3 *out)
+{
+    for (int v = 0; v < s.nb; v++) out[v] = level_view(s, pair_pyr(s, side, v), lev, 0, 0);
 }
 
 // Whether this call may use the slot's side stream: single pairs that have the chip to themselves (with four pairs in flight eight
@@ -1152,17 +1186,28 @@ int enqueue_full(ugsm_ctx *ctx, Slot &s, int si, float *const *d_out, bool swap 
 }
 int enqueue_full(ugsm_ctx *ctx, Slot &s, int si, float *d_out, bool swap = false) { return enqueue_full(ctx, s, si, &d_out, swap); }
 
-// Full mode with the optional LR-consistency check (ugsm_config.lr_check_threshold; no reference counterpart): the match, the match
+// The LR check's setting (ugsm_set_lr_check): which calls apply it, and the page-locked words its counts come back in
+bool lr_full_on(const ugsm_ctx *ctx) { return ctx->lr_tau > 0.0f && (ctx->lr_modes & UGSM_LR_FULL); }
+bool lr_fovea_on(const ugsm_ctx *ctx) { return ctx->lr_tau > 0.0f && (ctx->lr_modes & UGSM_LR_FOVEATED); }
+constexpr size_t kLrHostWords = 1 + (size_t)kMaxBatch * UGSM_MAX_LEVELS;
+int lr_host_ready(ugsm_ctx *ctx, Slot &s)
+{
+    if (!s.lr_host) HIPCHK(ctx, hipHostMalloc((void **)&s.lr_host, kLrHostWords * sizeof(unsigned long long), hipHostMallocDefault));
+    return UGSM_OK;
+}
+
+// Full mode with the optional LR-consistency check (ugsm_set_lr_check / ugsm_config.lr_check_threshold; no reference counterpart): the match, the match
 // with the images exchanged into the slot's own buffer, then one kernel that zeroes the inconsistent confidences of d_out.  (Single pairs.)
 int enqueue_full_lr(ugsm_ctx *ctx, Slot &s, int si, float *d_out)
 {
     s.lr_ran = false;
+    s.lr_fov_pairs = 0;
     UCHK(enqueue_full(ctx, s, si, d_out));
-    const float tau = ctx->cfg.lr_check_threshold;
-    if (!(tau > 0.0f)) return UGSM_OK;
+    const float tau = ctx->lr_tau;
+    if (!lr_full_on(ctx)) return UGSM_OK;
     const size_t n3 = 3 * (size_t)s.W * s.H;
     UCHK(grow(ctx, s.lr, s.lr_cap, n3 + 4));
-    if (!s.lr_host) HIPCHK(ctx, hipHostMalloc((void **)&s.lr_host, sizeof(unsigned long long), hipHostMallocDefault));
+    UCHK(lr_host_ready(ctx, s));
     unsigned long long *cnt = reinterpret_cast<unsigned long long *>(s.lr + ((n3 + 1) & ~(size_t)1));  // (8-byte aligned)
     HIPCHK(ctx, hipMemsetAsync(cnt, 0, sizeof *cnt, s.st));
     UCHK(enqueue_full(ctx, s, si, s.lr, true));
@@ -1197,14 +1242,14 @@ int enqueue_fovea_coarse(ugsm_ctx *ctx, Slot &s, int si, float *const *d_state)
     const int top = levels - 1;
     for (int b = 0; b < nb; b++)
         HIPCHK(ctx, hipMemsetAsync(cur + b * s.lvl_stride, 0, sizeof(float) * 3 * (size_t)s.w[top] * s.h[top], s.st));
-    SeedMap sm[kMaxBatch];
-    Img3 Lv[kMaxBatch], Rv[kMaxBatch];
+    SeedMap sm[2 * kMaxBatch];  // (a checked call: two virtual pairs per pair, Slot::nreal)
+    Img3 Lv[2 * kMaxBatch], Rv[2 * kMaxBatch];
     bool seeded = false;
     for (int i = top; i >= F - 1; i--) {
         s.cur_level = i;
         const int mi = level_iterations(i);
-        full_views(s, s.pyrL, i, Lv);
-        full_views(s, s.pyrR, i, Rv);
+        side_views(s, 0, i, Lv);
+        side_views(s, 1, i, Rv);
         UCHK(run_level(ctx, s, si, Lv, Rv, s.w[i], s.h[i], mi, level_smooth(i), i == top, 1, mi, cur, other, nullptr, nullptr, seeded ? sm : nullptr,
                        nb > 1 ? nullptr : level_A(ctx, s, i)));
         seeded = false;
@@ -1227,9 +1272,10 @@ int enqueue_fovea_coarse(ugsm_ctx *ctx, Slot &s, int si, float *const *d_state)
     if (nb == 1) {
         HIPCHK(ctx, hipMemcpyAsync(d_state[0], cur, sizeof(float) * 3 * fn, hipMemcpyDeviceToDevice, s.st));
     } else {
-        const Grp g{0, nb};
-        const Batch bt = copy_batch(s, g, nullptr, d_state, 0);
-        launch_copy_view(s.st, Img3{cur, s.w[F - 1], fn}, s.w[F - 1], s.h[F - 1], d_state[0], fn, s.w[F - 1], &bt);
+        for_groups(nb, true, [&](Grp g) {
+            const Batch bt = copy_batch(s, g, nullptr, d_state, 0);
+            launch_copy_view(s.st, Img3{cur + g.b0 * s.lvl_stride, s.w[F - 1], fn}, s.w[F - 1], s.h[F - 1], d_state[g.b0], fn, s.w[F - 1], &bt);
+        });
     }
     s.have_coarse = nb == 1;
     return UGSM_OK;
@@ -1237,13 +1283,14 @@ int enqueue_fovea_coarse(ugsm_ctx *ctx, Slot &s, int si, float *const *d_state)
 int enqueue_fovea_coarse(ugsm_ctx *ctx, Slot &s, int si, float *d_state) { return enqueue_fovea_coarse(ctx, s, si, &d_state); }
 
 // The fine phase for the s.nb pairs of the call: per-pair states, window offsets and destinations (d_pyrL / d_pyrR may be null, and so may
-// their entries).
+// their entries).  A checked call (Slot::nreal) brings s.nb = 2 nreal states, offsets and stacks -- a virtual pair has its pair's offsets -- and
+// nreal pyramid-stack destinations: the pyramid stacks are the real pairs'.
 int enqueue_fovea_fine(ugsm_ctx *ctx, Slot &s, int si, const float *const *d_state, const int *off_x, const int *off_y, float *const *d_stack,
                        float *const *d_pyrL, float *const *d_pyrR)
 {
     const int levels = s.levels, F = ctx->cfg.fovea_levels, nb = s.nb;
     if (F < 2 || F > levels) return UGSM_ERR_BAD_ARG;
-    FoveaGeom g[kMaxBatch];
+    FoveaGeom g[2 * kMaxBatch];
     for (int b = 0; b < nb; b++) fovea_geometry(s.w, s.h, F, off_x[b], off_y[b], g[b]);
     const int fw = g[0].fw, fh = g[0].fh;
     const size_t fn = (size_t)fw * fh;
@@ -1252,24 +1299,24 @@ int enqueue_fovea_fine(ugsm_ctx *ctx, Slot &s, int si, const float *const *d_sta
     for (int b = 0; b < nb; b++)
         HIPCHK(ctx, hipMemcpyAsync(cur + b * s.lvl_stride, d_state[b], sizeof(float) * 3 * fn, hipMemcpyDeviceToDevice, s.st));
     // a stack row block / a pyramid-stack block for every pair: one launch for the batch
-    auto copy_out = [&](const Img3 *views, const float *field, float *const *dsts, size_t dst_off, size_t dst_plane) {
-        for_groups(nb, np > 1, [&](Grp gr) {
+    auto copy_out = [&](int pairs, const Img3 *views, const float *field, float *const *dsts, size_t dst_off, size_t dst_plane) {
+        for_groups(pairs, np > 1, [&](Grp gr) {
             const Batch bt = copy_batch(s, gr, views, dsts, dst_off);
             const Img3 src = views ? views[gr.b0] : Img3{field + gr.b0 * s.lvl_stride, fw, fn};
             launch_copy_view(s.st, src, fw, fh, dsts[gr.b0] + dst_off, dst_plane, fw, gr.n > 1 ? &bt : nullptr);
         });
     };
     // stack row block F-1 = the whole level F-1 (UG_GPU_matcher.cpp:293-303)
-    copy_out(nullptr, cur, d_stack, (size_t)(F - 1) * fn, (size_t)F * fn);
-    SeedMap sm[kMaxBatch];
-    Img3 Lv[kMaxBatch], Rv[kMaxBatch];
+    copy_out(nb, nullptr, cur, d_stack, (size_t)(F - 1) * fn, (size_t)F * fn);
+    SeedMap sm[2 * kMaxBatch];
+    Img3 Lv[2 * kMaxBatch], Rv[2 * kMaxBatch];
     for (int i = F - 2; i >= 0; i--) {
         s.cur_level = i;
         // foveatedsubsampleDisp, MatchGPULib.cpp:1595-1655
         for (int b = 0; b < nb; b++) {
             sm[b] = SeedMap{fw, fh, g[b].cx[i], g[b].cy[i]};
-            Lv[b] = level_view(s, s.pyrL + b * s.pyr_stride, i, g[b].ox[i], g[b].oy[i]);
-            Rv[b] = level_view(s, s.pyrR + b * s.pyr_stride, i, g[b].ox[i], g[b].oy[i]);
+            Lv[b] = level_view(s, pair_pyr(s, 0, b), i, g[b].ox[i], g[b].oy[i]);
+            Rv[b] = level_view(s, pair_pyr(s, 1, b), i, g[b].ox[i], g[b].oy[i]);
         }
         const bool seeded = fuse_seed(ctx, fw, fh, s.alone, np);
         if (!seeded) {
@@ -1282,28 +1329,29 @@ int enqueue_fovea_fine(ugsm_ctx *ctx, Slot &s, int si, const float *const *d_sta
         }
         const int mi = level_iterations(i);
         UCHK(run_level(ctx, s, si, Lv, Rv, fw, fh, mi, level_smooth(i), false, 1, mi, cur, other, nullptr, nullptr, seeded ? sm : nullptr));
-        copy_out(nullptr, cur, d_stack, (size_t)i * fn, (size_t)F * fn);
+        copy_out(nb, nullptr, cur, d_stack, (size_t)i * fn, (size_t)F * fn);
     }
     // pyramid stacks as the node publishes them (UG_GPU_matcher.cpp:203-213): [level][channel][row]
     for (int side = 0; side < 2; side++) {
         float *const *dsts = side == 0 ? d_pyrL : d_pyrR;
         if (!dsts) continue;
+        const int nr = s.nreal;
         bool all = true, any = false;
-        for (int b = 0; b < nb; b++) {
+        for (int b = 0; b < nr; b++) {
             all = all && dsts[b] != nullptr;
             any = any || dsts[b] != nullptr;
         }
         if (!any) continue;
         const float *pyr = side == 0 ? s.pyrL : s.pyrR;
         for (int k = 0; k < F; k++) {
-            for (int b = 0; b < nb; b++) {
+            for (int b = 0; b < nr; b++) {
                 const int ox = (k < F - 1) ? g[b].ox[k] : 0, oy = (k < F - 1) ? g[b].oy[k] : 0;
                 Lv[b] = level_view(s, pyr + b * s.pyr_stride, k, ox, oy);
             }
             if (all) {
-                copy_out(Lv, nullptr, dsts, (size_t)k * 3 * fn, fn);
+                copy_out(nr, Lv, nullptr, dsts, (size_t)k * 3 * fn, fn);
             } else {
-                for (int b = 0; b < nb; b++)
+                for (int b = 0; b < nr; b++)
                     if (dsts[b]) launch_copy_view(s.st, Lv[b], fw, fh, dsts[b] + (size_t)k * 3 * fn, fn, fw);
             }
         }
@@ -1314,6 +1362,80 @@ int enqueue_fovea_fine(ugsm_ctx *ctx, Slot &s, int si, const float *const *d_sta
 int enqueue_fovea_fine(ugsm_ctx *ctx, Slot &s, int si, const float *d_state, int off_x, int off_y, float *d_stack, float *d_pyrL, float *d_pyrR)
 {
     return enqueue_fovea_fine(ctx, s, si, &d_state, &off_x, &off_y, &d_stack, d_pyrL ? &d_pyrL : nullptr, d_pyrR ? &d_pyrR : nullptr);
+}
+
+// One foveated call of n pairs on device buffers: the pyramids, the coarse levels, the fine levels into the pairs' stacks.  state: n buffers
+// of 3 fovW fovH floats for level F-1's field between the two phases; d_pyrL / d_pyrR as for enqueue_fovea_fine.
+// With the foveated LR check on (ugsm_set_lr_check) the call matches both directions in lockstep and checks the stacks against each other:
+//   - the pyramids are built once; virtual pair n + b reads pair b's with the L and R views exchanged (pair_pyr), through pair b's windows and
+//     seed maps, under pair b's range word (it covers both images' pyramids: build_pyramids reports either image into range_bad[pair]);
+//     every kernel of a level takes the 2 n pairs in one launch except K-cost, which takes each direction in one (run_level);
+//   - every field of a foveated call is at most fovW x fovH, so the 2 n fields lie in the slot's level buffers at a stride of one such field
+//     (n pairs hold n x 3 W H floats per buffer and need 2 n x 3 fovW fovH, fovW fovH <= W H / 2 for every F >= 2: it fits, for F = 2 just);
+//   - what does NOT fit there for F = 2 is the right-to-left STACK, which has to outlive the fine levels: A, d0 and d1 are then full.  It goes,
+//     with the right-to-left state, into the slot's LR buffer (Slot::lr, what the full-mode check keeps its second field in): 3 (F + 1)
+//     fovW fovH floats per pair, 24 MB at 16 MP beside the pair's 1.35 GB, counted by ugsm_context_device_bytes;
+//   - one launch checks every level of every pair's stack (k_lr_check's stack form) after the last level, so nothing feeds back into the
+//     matching; the counts come back with one copy on the slot's stream.
+int enqueue_foveated(ugsm_ctx *ctx, Slot &s, int si, int n, const uint8_t *const *d_rgbL, const uint8_t *const *d_rgbR, int W, int H, int stride,
+                     const int *off_x, const int *off_y, float *const *state, float *const *d_stack, float *const *d_pyrL, float *const *d_pyrR)
+{
+    const int F = ctx->cfg.fovea_levels;
+    s.lr_ran = false;
+    s.lr_fov_pairs = 0;
+    FoveaWin win;
+    UCHK(fovea_windows(ctx, W, H, n, off_x, off_y, win));
+    if (!lr_fovea_on(ctx)) {
+        // (a single pair alone on the chip gets level F-1 .. top's A planes from the side stream; a batch computes A in line)
+        UCHK(enqueue_pyramids(ctx, s, si, d_rgbL, d_rgbR, n, W, H, stride, n == 1 ? F - 1 : -1, &win));
+        UCHK(enqueue_fovea_coarse(ctx, s, si, state));
+        return enqueue_fovea_fine(ctx, s, si, state, off_x, off_y, d_stack, d_pyrL, d_pyrR);
+    }
+    UCHK(enqueue_pyramids(ctx, s, si, d_rgbL, d_rgbR, n, W, H, stride, -1, &win));
+    const int fw = s.w[F - 1], fh = s.h[F - 1];
+    const size_t fn = (size_t)fw * fh, stackf = 3 * (size_t)F * fn;
+    const size_t field = (3 * fn + 63) & ~(size_t)63;           // a virtual pair's room in A, d0, d1
+    const size_t per = (stackf + 3 * fn + 63) & ~(size_t)63;    // a pair's room in the LR buffer: [right-to-left stack][right-to-left state]
+    UCHK(ensure_level_bufs(ctx, s, 2 * (size_t)n * field));     // (holds already: see above)
+    UCHK(grow(ctx, s.lr, s.lr_cap, (size_t)n * per + 2 * (size_t)n * F));
+    UCHK(lr_host_ready(ctx, s));
+    unsigned long long *const cnt = reinterpret_cast<unsigned long long *>(s.lr + (size_t)n * per);  // one word per (pair, level)
+    if (s.range_known) HIPCHK(ctx, hipMemcpyAsync(s.range_bad + n, s.range_bad, sizeof(unsigned) * n, hipMemcpyDeviceToDevice, s.st));
+    int vox[2 * kMaxBatch], voy[2 * kMaxBatch];
+    float *vstate[2 * kMaxBatch], *vstack[2 * kMaxBatch];
+    for (int b = 0; b < n; b++) {
+        vox[b] = vox[n + b] = off_x[b];
+        voy[b] = voy[n + b] = off_y[b];
+        vstate[b] = state[b];
+        vstack[b] = d_stack[b];
+        vstack[n + b] = s.lr + (size_t)b * per;
+        vstate[n + b] = vstack[n + b] + stackf;
+    }
+    const size_t real_stride = s.lvl_stride;
+    s.nb = 2 * n;
+    s.lvl_stride = field;
+    int st = enqueue_fovea_coarse(ctx, s, si, vstate);
+    if (st == UGSM_OK) st = enqueue_fovea_fine(ctx, s, si, vstate, vox, voy, vstack, d_pyrL, d_pyrR);
+    s.nb = n;
+    s.lvl_stride = real_stride;
+    UCHK(st);
+    HIPCHK(ctx, hipMemsetAsync(cnt, 0, sizeof *cnt * n * F, s.st));
+    LrStack ls{};
+    ls.n = n;
+    ls.F = F;
+    for (int b = 0; b < n; b++) {
+        ls.fwd[b] = byte_diff(d_stack[b], d_stack[0]);
+        ls.back[b] = (long long)((size_t)b * per * sizeof(float));
+    }
+    {
+        Timer t(ctx, &s, si, KC_MISC, (double)fn * F * n);
+        launch_lr_check(s.st, d_stack[0], s.lr, fw, fh, ctx->lr_tau, cnt, ls);
+    }
+    HIPCHK(ctx, hipMemcpyAsync(s.lr_host + 1, cnt, sizeof *cnt * n * F, hipMemcpyDeviceToHost, s.st));
+    HIPCHK(ctx, hipGetLastError());
+    s.lr_fov_pairs = n;
+    s.lr_fov_F = F;
+    return UGSM_OK;
 }
 
 // Has everything enqueued on the slot finished?  (Never blocks; a slot found idle stops counting as busy.)
@@ -1617,6 +1739,8 @@ int ugsm_create(const ugsm_config *cfg_in, ugsm_ctx **out)
     if (hipSetDevice(cfg.device) != hipSuccess) return UGSM_ERR_NO_DEVICE;
     ugsm_ctx *ctx = new ugsm_ctx();
     ctx->cfg = cfg;
+    ctx->lr_tau = cfg.lr_check_threshold;
+    ctx->lr_modes = UGSM_LR_FULL;
     set_policy(ctx, knobs);
     if (dev_env_on() && getenv("UGSM_MEM_LIMIT_MB")) ctx->mem_limit = atoll(getenv("UGSM_MEM_LIMIT_MB")) << 20;
     // The side stream pays when a pair is alone on the chip (115.6 against 113.9 pairs/s at 16 MP: the right pyramid and the A planes run
@@ -1649,7 +1773,7 @@ int ugsm_create(const ugsm_config *cfg_in, ugsm_ctx **out)
         const char pc = knobs.stream_prio[0] ? (si < (int)strlen(knobs.stream_prio) ? knobs.stream_prio[si] : 'n') : by_cfg;
         const int prio = pc == 'h' ? prio_greatest : (pc == 'l' ? prio_least : 0);
         bool ok = (!s.owns_st || hipStreamCreateWithPriority(&s.st, hipStreamNonBlocking, prio) == hipSuccess) &&
-                  hipMalloc((void **)&s.range_bad, 64) == hipSuccess && hipEventCreateWithFlags(&s.ev_done, hipEventDisableTiming) == hipSuccess;
+                  hipMalloc((void **)&s.range_bad, 2 * kMaxBatch * sizeof(unsigned)) == hipSuccess && hipEventCreateWithFlags(&s.ev_done, hipEventDisableTiming) == hipSuccess;
         s.prio = prio;
         for (hipEvent_t *e : {&s.ev_in, &s.ev_L, &s.ev_R}) ok = ok && hipEventCreateWithFlags(e, hipEventDisableTiming) == hipSuccess;
         for (int i = 0; i < cfg.levels; i++) ok = ok && hipEventCreateWithFlags(&s.ev_A[i], hipEventDisableTiming) == hipSuccess;
@@ -1868,15 +1992,14 @@ int ugsm_submit_foveated(ugsm_ctx *ctx, int slot, const uint8_t *d_rgbL, const u
     HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
     const int F = ctx->cfg.fovea_levels;
     if (F < 2) return UGSM_ERR_BAD_ARG;
-    FoveaWin win;
-    UCHK(fovea_windows(ctx, W, H, 1, &off_x, &off_y, win));
-    UCHK(enqueue_pyramids(ctx, *s, slot, d_rgbL, d_rgbR, W, H, stride, F - 1, &win));
     // level F-1's state is parked in the (otherwise idle) A buffer's tail? No: use a dedicated spot
     // at the end of d_stack's level F-1 block is not 3-plane contiguous, so stage through hout.
-    const size_t fn3 = 3 * (size_t)s->w[F - 1] * s->h[F - 1];
+    int fw, fh;
+    UCHK(ugsm_fovea_dims(W, H, ctx->cfg.levels, F, &fw, &fh));
+    const size_t fn3 = 3 * (size_t)fw * fh;
     UCHK(grow(ctx, s->hout, s->hout_cap, std::max(fn3, s->hout_cap)));
-    UCHK(enqueue_fovea_coarse(ctx, *s, slot, s->hout));
-    UCHK(enqueue_fovea_fine(ctx, *s, slot, s->hout, off_x, off_y, d_stack, d_pyrL, d_pyrR));
+    UCHK(enqueue_foveated(ctx, *s, slot, 1, &d_rgbL, &d_rgbR, W, H, stride, &off_x, &off_y, &s->hout, &d_stack, d_pyrL ? &d_pyrL : nullptr,
+                          d_pyrR ? &d_pyrR : nullptr));
     return mark_done(ctx, *s);
 }
 
@@ -1884,8 +2007,11 @@ int ugsm_submit_foveated(ugsm_ctx *ctx, int slot, const uint8_t *d_rgbL, const u
 // Contexts whose options need a host round trip per iteration, a second match, or the one-kernel-per-stage path: pair by pair.
 static bool batch_runs_pair_by_pair(const ugsm_ctx *ctx)
 {
-    return ctx->cfg.kernel_path == 1 || ctx->cfg.early_exit_threshold > 0.0f || ctx->cfg.lr_check_threshold > 0.0f;
+    return ctx->cfg.kernel_path == 1 || ctx->cfg.early_exit_threshold > 0.0f || lr_full_on(ctx);
 }
+// ... and the foveated batches: the foveated check runs in lockstep (enqueue_foveated; ugsm_set_lr_check refuses it to the contexts of the first
+// two kinds).  A context with the full-mode check alone sends its foveated batches through pair by pair as it always has.
+static bool fovea_batch_runs_pair_by_pair(const ugsm_ctx *ctx) { return batch_runs_pair_by_pair(ctx) && !lr_fovea_on(ctx); }
 
 int ugsm_submit_full_batch(ugsm_ctx *ctx, int slot, int n, const uint8_t *const *d_rgbL, const uint8_t *const *d_rgbR, int W, int H, int stride,
                            float *const *d_out)
@@ -1905,6 +2031,7 @@ int ugsm_submit_full_batch(ugsm_ctx *ctx, int slot, int n, const uint8_t *const 
     }
     UCHK(enqueue_pyramids(ctx, *s, slot, d_rgbL, d_rgbR, n, W, H, stride));
     s->lr_ran = false;
+    s->lr_fov_pairs = 0;
     UCHK(enqueue_full(ctx, *s, slot, d_out));
     return mark_done(ctx, *s);
 }
@@ -1928,21 +2055,15 @@ int ugsm_submit_foveated_batch(ugsm_ctx *ctx, int slot, int n, const uint8_t *co
     UCHK(grow(ctx, s->hout, s->hout_cap, std::max(fn3 * n, s->hout_cap)));
     FoveaWin win;
     UCHK(fovea_windows(ctx, W, H, n, ox, oy, win));
-    if (n == 1 || batch_runs_pair_by_pair(ctx)) {
-        for (int b = 0; b < n; b++) {
-            FoveaWin w1;
-            UCHK(fovea_windows(ctx, W, H, 1, ox + b, oy + b, w1));
-            UCHK(enqueue_pyramids(ctx, *s, slot, d_rgbL[b], d_rgbR[b], W, H, stride, F - 1, &w1));
-            UCHK(enqueue_fovea_coarse(ctx, *s, slot, s->hout));
-            UCHK(enqueue_fovea_fine(ctx, *s, slot, s->hout, ox[b], oy[b], d_stack[b], d_pyrL ? d_pyrL[b] : nullptr, d_pyrR ? d_pyrR[b] : nullptr));
-        }
+    if (n == 1 || fovea_batch_runs_pair_by_pair(ctx)) {
+        for (int b = 0; b < n; b++)
+            UCHK(enqueue_foveated(ctx, *s, slot, 1, d_rgbL + b, d_rgbR + b, W, H, stride, ox + b, oy + b, &s->hout, d_stack + b,
+                                  (d_pyrL && d_pyrL[b]) ? d_pyrL + b : nullptr, (d_pyrR && d_pyrR[b]) ? d_pyrR + b : nullptr));
         return mark_done(ctx, *s);
     }
     float *state[UGSM_MAX_BATCH];
     for (int b = 0; b < n; b++) state[b] = s->hout + b * fn3;
-    UCHK(enqueue_pyramids(ctx, *s, slot, d_rgbL, d_rgbR, n, W, H, stride, -1, &win));
-    UCHK(enqueue_fovea_coarse(ctx, *s, slot, state));
-    UCHK(enqueue_fovea_fine(ctx, *s, slot, state, ox, oy, d_stack, d_pyrL, d_pyrR));
+    UCHK(enqueue_foveated(ctx, *s, slot, n, d_rgbL, d_rgbR, W, H, stride, ox, oy, state, d_stack, d_pyrL, d_pyrR));
     return mark_done(ctx, *s);
 }
 
@@ -2075,11 +2196,8 @@ static int match_foveated_on_slot(ugsm_ctx *ctx, int slot, const uint8_t *rgbL, 
     float *d_state = s->hout, *d_stack = d_state + 3 * fn;
     float *d_pl = pyrL ? d_stack + 3 * stackn : nullptr;
     float *d_pr = pyrR ? d_stack + 3 * stackn + (pyrL ? 3 * stackn : 0) : nullptr;
-    FoveaWin win;
-    UCHK(fovea_windows(ctx, W, H, 1, &off_x, &off_y, win));
-    UCHK(enqueue_pyramids(ctx, *s, slot, s->rgbL, s->rgbR, W, H, stride, F - 1, &win));
-    UCHK(enqueue_fovea_coarse(ctx, *s, slot, d_state));
-    UCHK(enqueue_fovea_fine(ctx, *s, slot, d_state, off_x, off_y, d_stack, d_pl, d_pr));
+    const uint8_t *const dL = s->rgbL, *const dR = s->rgbR;
+    UCHK(enqueue_foveated(ctx, *s, slot, 1, &dL, &dR, W, H, stride, &off_x, &off_y, &d_state, &d_stack, d_pl ? &d_pl : nullptr, d_pr ? &d_pr : nullptr));
     HIPCHK(ctx, hipMemcpyAsync(stackH, d_stack, stackn * sizeof(float), hipMemcpyDeviceToHost, s->st));
     HIPCHK(ctx, hipMemcpyAsync(stackV, d_stack + stackn, stackn * sizeof(float), hipMemcpyDeviceToHost, s->st));
     HIPCHK(ctx, hipMemcpyAsync(stackC, d_stack + 2 * stackn, stackn * sizeof(float), hipMemcpyDeviceToHost, s->st));
@@ -2153,6 +2271,7 @@ int ugsm_submit_full_batch_host(ugsm_ctx *ctx, int slot, int n, const uint8_t *c
     for (int b = 0; b < n; b++) out[b] = s->hout + b * per;
     UCHK(enqueue_pyramids(ctx, *s, slot, dL, dR, n, W, H, stride));
     s->lr_ran = false;
+    s->lr_fov_pairs = 0;
     UCHK(enqueue_full(ctx, *s, slot, out));
     for (int b = 0; b < n; b++) {
         float *const dst[3] = {dispH[b], dispV[b], dispC[b]};
@@ -2177,7 +2296,7 @@ int ugsm_submit_foveated_batch_host(ugsm_ctx *ctx, int slot, int n, const uint8_
     }
     int zeros[UGSM_MAX_BATCH] = {0};
     const int *ox = off_x ? off_x : zeros, *oy = off_y ? off_y : zeros;
-    if (n == 1 || batch_runs_pair_by_pair(ctx)) {
+    if (n == 1 || fovea_batch_runs_pair_by_pair(ctx)) {
         for (int b = 0; b < n; b++)
             UCHK(match_foveated_on_slot(ctx, slot, rgbL[b], rgbR[b], W, H, stride, ox[b], oy[b], stackH[b], stackV[b], stackC[b], nullptr, nullptr, false));
         return UGSM_OK;
@@ -2194,11 +2313,7 @@ int ugsm_submit_foveated_batch_host(ugsm_ctx *ctx, int slot, int n, const uint8_
         state[b] = s->hout + b * st_per;
         stack[b] = s->hout + n * st_per + b * sk_per;
     }
-    FoveaWin win;
-    UCHK(fovea_windows(ctx, W, H, n, ox, oy, win));
-    UCHK(enqueue_pyramids(ctx, *s, slot, dL, dR, n, W, H, stride, -1, &win));
-    UCHK(enqueue_fovea_coarse(ctx, *s, slot, state));
-    UCHK(enqueue_fovea_fine(ctx, *s, slot, state, ox, oy, stack, nullptr, nullptr));
+    UCHK(enqueue_foveated(ctx, *s, slot, n, dL, dR, W, H, stride, ox, oy, state, stack, nullptr, nullptr));
     for (int b = 0; b < n; b++) {
         HIPCHK(ctx, hipMemcpyAsync(stackH[b], stack[b], stackn * sizeof(float), hipMemcpyDeviceToHost, s->st));
         HIPCHK(ctx, hipMemcpyAsync(stackV[b], stack[b] + stackn, stackn * sizeof(float), hipMemcpyDeviceToHost, s->st));
@@ -2223,11 +2338,8 @@ static int match_foveated_full_on_slot0(ugsm_ctx *ctx, const uint8_t *rgbL, cons
     const size_t fn = (size_t)fw * fh, stackn = (size_t)F * fn, n = (size_t)W * H;
     UCHK(grow(ctx, s->hout, s->hout_cap, 3 * fn + 3 * stackn + 3 * n));  // [state][stack][full field]
     float *d_state = s->hout, *d_stack = d_state + 3 * fn, *d_full = d_stack + 3 * stackn;
-    FoveaWin win;
-    UCHK(fovea_windows(ctx, W, H, 1, &off_x, &off_y, win));
-    UCHK(enqueue_pyramids(ctx, *s, 0, s->rgbL, s->rgbR, W, H, stride, F - 1, &win));
-    UCHK(enqueue_fovea_coarse(ctx, *s, 0, d_state));
-    UCHK(enqueue_fovea_fine(ctx, *s, 0, d_state, off_x, off_y, d_stack, nullptr, nullptr));
+    const uint8_t *const dL = s->rgbL, *const dR = s->rgbR;
+    UCHK(enqueue_foveated(ctx, *s, 0, 1, &dL, &dR, W, H, stride, &off_x, &off_y, &d_state, &d_stack, nullptr, nullptr));
     UCHK(ugsm_reconstruct_full(ctx, 0, d_stack, d_stack + stackn, d_stack + 2 * stackn, W, H, off_x, off_y, d_full));
     float *const dst[3] = {outH, outV, outC};
     prefault_planes(ctx, dst, n);
@@ -2282,7 +2394,7 @@ int ugsm_stage_iterate(ugsm_ctx *ctx, const float *d_L3, const float *d_R3, floa
         launch_range_scan(s->st, d_L3, 3 * n, s->range_bad);
         launch_range_scan(s->st, d_R3, 3 * n, s->range_bad);
     }
-    s->nb = 1;
+    s->nb = s->nreal = 1;
     const Img3 Lv{d_L3, W, n}, Rv{d_R3, W, n};
     UCHK(run_level(ctx, *s, 0, &Lv, &Rv, W, H, mi, S, is_top != 0, m_from, m_to, cur, other, d_dbg8));
     HIPCHK(ctx, hipMemcpyAsync(d_d3, cur, lvl * sizeof(float), hipMemcpyDeviceToDevice, s->st));
@@ -2313,7 +2425,7 @@ int ugsm_stage_smooth(ugsm_ctx *ctx, float *d_d3, int W, int H, int passes, int 
     UCHK(ensure_level_bufs(ctx, *s, lvl));
     float *a = s->d0, *b = s->d1;
     HIPCHK(ctx, hipMemcpyAsync(a, d_d3, lvl * sizeof(float), hipMemcpyDeviceToDevice, s->st));
-    s->nb = 1;
+    s->nb = s->nreal = 1;
     UCHK(enqueue_smooth(ctx, *s, 0, a, b, W, H, passes, do_box != 0));
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipMemcpyAsync(d_d3, a, lvl * sizeof(float), hipMemcpyDeviceToDevice, s->st));
@@ -2750,7 +2862,7 @@ int ugsm_stage_lr_check(ugsm_ctx *ctx, float *d_left3, const float *d_right3, in
     if (!d_left3 || !d_right3 || W < 1 || H < 1 || H > 65535 || (long long)W * H > kMaxPixels || !(tau >= 0.0f)) return UGSM_ERR_BAD_ARG;
     HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
     UCHK(grow(ctx, s->lr, s->lr_cap, std::max<size_t>(s->lr_cap, 8)));
-    if (!s->lr_host) HIPCHK(ctx, hipHostMalloc((void **)&s->lr_host, sizeof(unsigned long long), hipHostMallocDefault));
+    UCHK(lr_host_ready(ctx, *s));
     unsigned long long *cnt = reinterpret_cast<unsigned long long *>(s->lr);
     HIPCHK(ctx, hipStreamSynchronize(s->st));  // (the counter shares the slot's LR buffer)
     HIPCHK(ctx, hipMemsetAsync(cnt, 0, sizeof *cnt, s->st));
@@ -2766,7 +2878,44 @@ long long ugsm_last_lr_marked(ugsm_ctx *ctx, int slot)
 {
     Slot *s;
     if (get_slot(ctx, slot, &s, false) != UGSM_OK) return -1;
+    if (s->lr_fov_pairs > 0 && s->lr_host) {  // a checked foveated call: the levels of its last pair
+        long long sum = 0;
+        for (int k = 0; k < s->lr_fov_F; k++) sum += (long long)s->lr_host[1 + (size_t)(s->lr_fov_pairs - 1) * s->lr_fov_F + k];
+        return sum;
+    }
     return (s->lr_ran && s->lr_host) ? (long long)*s->lr_host : -1;
+}
+
+int ugsm_last_lr_marked_levels(ugsm_ctx *ctx, int slot, int pair, long long *per_level)
+{
+    Slot *s;
+    UCHK(get_slot(ctx, slot, &s, false));  // (reads host state only: the slot does not become busy)
+    if (!per_level) return UGSM_ERR_BAD_ARG;
+    if (s->lr_fov_pairs < 1 || !s->lr_host) return ctx_fail(ctx, UGSM_ERR_STATE, "the last call on the slot ran without the foveated LR check");
+    if (pair < 0 || pair >= s->lr_fov_pairs) return UGSM_ERR_BAD_ARG;
+    for (int k = 0; k < s->lr_fov_F; k++) per_level[k] = (long long)s->lr_host[1 + (size_t)pair * s->lr_fov_F + k];
+    return UGSM_OK;
+}
+
+int ugsm_set_lr_check(ugsm_ctx *ctx, float tau, int modes)
+{
+    if (!ctx || !(tau >= 0.0f) || modes < 0 || modes > (UGSM_LR_FULL | UGSM_LR_FOVEATED)) return UGSM_ERR_BAD_ARG;
+    if (ctx->hooks.queue_busy)
+        return ctx_fail(ctx, UGSM_ERR_STATE, "pairs enqueued with ugsm_enqueue_* are outstanding: the LR check is a setting of the calls the queue forms");
+    // (these contexts run every level pair by pair -- run_level -- and have no batch dimension to carry the second direction in)
+    if ((modes & UGSM_LR_FOVEATED) && (ctx->cfg.early_exit_threshold > 0.0f || ctx->cfg.kernel_path == 1))
+        return ctx_fail(ctx, UGSM_ERR_BAD_ARG, "UGSM_LR_FOVEATED: not with early_exit_threshold > 0 or kernel_path 1");
+    ctx->lr_tau = tau;
+    ctx->lr_modes = modes;
+    return UGSM_OK;
+}
+
+int ugsm_get_lr_check(const ugsm_ctx *ctx, float *tau, int *modes)
+{
+    if (!ctx || !tau || !modes) return UGSM_ERR_BAD_ARG;
+    *tau = ctx->lr_tau;
+    *modes = ctx->lr_modes;
+    return UGSM_OK;
 }
 
 int ugsm_slot_stream(ugsm_ctx *ctx, int slot, void **hip_stream)
