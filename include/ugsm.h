@@ -412,7 +412,8 @@ int ugsm_queue_plan(const ugsm_config *cfg, int n_pairs, int *sizes, int cap);
  * top..F-1 on the full frame; d_state receives level F-1's (dx,dy,conf),
  * 3*fovH*fovW floats -- the 3 MB object broadcast over RCCL.  fine: levels
  * F-2..0 for the window at (off_x, off_y) from a (possibly received) d_state;
- * needs the pair's WHOLE pyramids in the slot, i.e. ugsm_submit_pyramids first (UGSM_ERR_STATE otherwise).  The one-shot foveated
+ * needs the pair's WHOLE pyramids in the slot, i.e. ugsm_submit_pyramids first (UGSM_ERR_STATE otherwise; a full-mode call leaves none
+ * behind: it reads level 0 from the images themselves and may not store it).  The one-shot foveated
  * calls (ugsm_match_foveated, ugsm_submit_foveated[_batch|_host]) know their windows when they build the pyramids and store level 0
  * only inside them (CreateFoveatedPyramid crops after a full build, MatchGPULib.cpp:1128-1190; here 193 MB per 16 MP image are never
  * written), so their pyramids do NOT serve a later ugsm_submit_fovea_fine at another offset. */

@@ -41,6 +41,18 @@ int ugsm_stage_div_probe(ugsm_ctx *ctx, const float *d_n, const float *d_d, floa
  * that call. */
 int ugsm_stage_range_words(ugsm_ctx *ctx, int slot, unsigned *host_out, int n);
 
+/* 1 when the last call on the slot read level 0 of the pyramid from the images themselves (full-mode calls on rgb8 images whose level 0 is
+ * matched by k_cost_march: the float level 0 is then never stored), 0 when it materialised it; minus the status (-UGSM_ERR_BAD_ARG) for a bad slot.  Host state
+ * only: nothing is launched and the slot does not become busy.  The two paths give the same bits, so only this tells which one ran. */
+int ugsm_stage_level0_direct(ugsm_ctx *ctx, int slot);
+
+/* The stage-level iterate call of ugsm.h with the two images given as rgb8 (rows `stride` bytes apart) instead of float planes: the level is matched
+ * the way a full-mode call matches level 0, which it reads from the images themselves -- the 8-bit instances of K-cost and of A = G * L^2 --
+ * but from the caller's field d_d3, so that chosen disparities reach the clamped byte gather.  For contexts whose kernel choice gives the
+ * level to k_cost_march (march_min_pixels = 1, at most 150 000 pixels); UGSM_ERR_STATE otherwise, UGSM_ERR_BAD_ARG for another input format. */
+int ugsm_stage_iterate_rgb8(ugsm_ctx *ctx, const uint8_t *d_rgbL, const uint8_t *d_rgbR, int stride, float *d_d3, int W, int H,
+                            int mi, int S, int is_top, int m_from, int m_to);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

@@ -106,9 +106,14 @@ if __name__ == "__main__":
     if sys.argv[1] == "--diff":
         a, b = json.load(open(sys.argv[2])), json.load(open(sys.argv[3]))
         dm = demangle(sorted(set(a) | set(b)))
-        for s in sorted(set(a) - set(b)):
+        gone, new = sorted(set(a) - set(b)), sorted(set(b) - set(a))
+        for s in gone:  # (a kernel that became a template instance, or moved namespace: another symbol, the same instruction stream)
+            for t in new:
+                if a[s]["sha"] == b[t]["sha"]:
+                    print(f"renamed  {dm[s]}\n      -> {dm[t]}: identical ({a[s]['n']} instructions, vgpr {b[t].get('vgpr_count')})")
+        for s in gone:
             print("removed ", dm[s])
-        for s in sorted(set(b) - set(a)):
+        for s in new:
             print("added   ", dm[s])
         ch = [s for s in sorted(set(a) & set(b)) if a[s]["sha"] != b[s]["sha"]]
         for s in ch:

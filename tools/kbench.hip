@@ -15,6 +15,7 @@
 //   14  k_cost_march4 against k_cost_march / k_cost_split / k_cost_small: bits + timing over strip heights
 //   15  tile heights of the 112-column K-smooth tile: bits against 36 rows, timing
 //   18  two kernels on two streams: alone and side by side
+//   20  level 0 from the 8-bit image: K-cost and A on the float planes against their rgb8 instances -- bits, then timing, alternating
 #define UGSM_DEV_LIB 1  // (the launch header's declarations of the dev kernels)
 #include "../ug_stereomatcher_amd/csrc/ugsm_kernels_aux.hip"
 #include "../ug_stereomatcher_amd/csrc/ugsm_kernels_pyr.hip"
@@ -263,6 +264,49 @@ int main(int argc, char **argv)
             printf("  K-cost march4 + K-smooth  %.1f (%.1f)  -> %.2f of the sum\n", s4, m4 + sm, s4 / (m4 + sm));
             printf("  K-cost march  + K-cost    %.1f (%.1f)  -> %.2f\n", cc, 2 * c, cc / (2 * c));
             printf("  K-smooth      + K-smooth  %.1f (%.1f)  -> %.2f\n", ss, 2 * sm, ss / (2 * sm));
+        }
+    } else if (mode == 20) {
+        // the planes of level 0 hold the integers 0 .. 255 (KBENCH_DATA of tools/kbench_real.py; the random planes are rounded down here):
+        // the rgb8 images they are the conversion of, rows 3 W + 5 bytes apart and one byte off their allocations
+        for (size_t i = 0; i < 3 * n; i++) { hL[i] = floorf(hL[i]); hR[i] = floorf(hR[i]); }
+        CK(hipMemcpy(L, hL.data(), 12 * n, hipMemcpyHostToDevice)); CK(hipMemcpy(R, hR.data(), 12 * n, hipMemcpyHostToDevice));
+        const int stride = 3 * W + 5;
+        std::vector<uint8_t> b8((size_t)stride * H + 1);
+        uint8_t *imgs[2];
+        for (int side = 0; side < 2; side++) {
+            const std::vector<float> &src = side ? hR : hL;
+            for (int y = 0; y < H; y++)
+                for (int x = 0; x < W; x++)
+                    for (int k = 0; k < 3; k++) b8[1 + (size_t)y * stride + 3 * x + k] = (uint8_t)src[k * n + (size_t)y * W + x];
+            CK(hipMalloc(&imgs[side], b8.size())); CK(hipMemcpy(imgs[side], b8.data(), b8.size(), hipMemcpyHostToDevice));
+        }
+        const Img3 bL = byte_view(imgs[0] + 1, stride), bR = byte_view(imgs[1] + 1, stride);
+        launch_sqblur_clamp(st, iL, W, H, o);
+        launch_sqblur_clamp(st, bL, W, H, o2, nullptr, kInRGB8);
+        cmp("k_sqblur_tiled<rgb8> vs the float planes");
+        launch_sqblur_clamp(st, iL, W, H, A);
+        auto march8 = [&](float *dst) { launch_cost_march(st, bL, bR, A, d, dst, W, H, 0.55f, 1, 0, rb, nullptr, kInRGB8); };
+        CK(hipMemset(o, 0xff, 12 * n)); CK(hipMemset(o2, 0xee, 12 * n));
+        march(o);
+        march8(o2);
+        cmp("k_cost_march<rgb8> vs the float planes");
+        for (int round = 0; round < 6; round++) {
+            timeit("k_cost_march float planes", [&]() { march(o); });
+            timeit("k_cost_march rgb8 image", [&]() { march8(o2); });
+        }
+        for (int round = 0; round < 3; round++) {
+            timeit("k_sqblur_tiled float planes", [&]() { launch_sqblur_clamp(st, iL, W, H, o); });
+            timeit("k_sqblur_tiled rgb8 image", [&]() { launch_sqblur_clamp(st, bL, W, H, o2, nullptr, kInRGB8); });
+        }
+        uint8_t *rgb = imgs[0] + 1;
+        const int W1 = (int)(W / 1.41421356), H1 = (int)(H / 1.41421356), W2 = W / 2, H2 = H / 2;
+        for (int round = 0; round < 3; round++) {  // the pyramid pass: all three levels (tiled), levels 1 and 2 only (streaming, and tiled)
+            timeit("k_pyr_base, level 0 stored", [&]() { launch_pyr_base(st, rgb, stride, W, H, L, o, W1, H1, o2, W2, H2, rb); });
+            pyr_base_streaming = 1;
+            timeit("k_pyr_base_march, no level 0", [&]() { launch_pyr_base(st, rgb, stride, W, H, L, o, W1, H1, o2, W2, H2, rb, nullptr, kPyrNoLevel0); });
+            pyr_base_streaming = 0;
+            timeit("k_pyr_base (tiled), no level 0", [&]() { launch_pyr_base(st, rgb, stride, W, H, L, o, W1, H1, o2, W2, H2, rb, nullptr, kPyrNoLevel0); });
+            pyr_base_streaming = 1;
         }
     } else {
         timeit("k_cost_march", [&]() { march(o); });

@@ -62,7 +62,7 @@ EXPORTS = [
     "ugsm_set_lr_check", "ugsm_get_lr_check", "ugsm_last_lr_marked_levels",
 ]
 # ... and what include/ugsm_dev.h adds (libugsm_dev.so only)
-DEV_EXPORTS = ["ugsm_stage_poly_probe", "ugsm_stage_div3_probe", "ugsm_stage_div_probe", "ugsm_stage_range_words"]
+DEV_EXPORTS = ["ugsm_stage_poly_probe", "ugsm_stage_div3_probe", "ugsm_stage_div_probe", "ugsm_stage_range_words", "ugsm_stage_iterate_rgb8", "ugsm_stage_level0_direct"]
 
 
 # input formats (ugsm_set_input_format): the byte layout of the images a context reads; a call on an image in format F gives the rgb8 call's
@@ -261,6 +261,8 @@ def load(dev: bool = False):
         lib.ugsm_stage_div3_probe.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i]
         lib.ugsm_stage_div_probe.argtypes = [vp, vp, vp, vp, i]
         lib.ugsm_stage_range_words.argtypes = [vp, i, C.POINTER(C.c_uint), i]
+        lib.ugsm_stage_level0_direct.argtypes = [vp, i]
+        lib.ugsm_stage_iterate_rgb8.argtypes = [vp, vp, vp, i, vp, i, i, i, i, i, i, i]
     lib.ugsm_stage_weighted_difference.argtypes = [vp, vp, vp, i, i, C.POINTER(C.c_float)]
     lib.ugsm_last_iterations.argtypes = [vp, i, C.POINTER(i)]
     lib.ugsm_stage_lr_check.argtypes = [vp, vp, vp, i, i, C.c_float, C.POINTER(C.c_longlong)]

@@ -40,6 +40,9 @@ __device__ __forceinline__ gchar_c *uniform_base(const float *p)
 }
 __device__ __forceinline__ float ld_at(gchar_c *base, unsigned off) { return *(gfloat_c *)(base + off); }
 __device__ __forceinline__ void st_at(gchar_c *base, unsigned off, float v) { *(gfloat *)((gchar *)base + off) = v; }
+// byte k (a constant: the load's immediate offset) of the pixel at base + off of an interleaved 8-bit image, zero-extended
+typedef __attribute__((address_space(1))) const unsigned char guchar_c;
+__device__ __forceinline__ unsigned ld_u8_at(gchar_c *base, unsigned off, int k) { return *((guchar_c *)(base + off) + k); }
 
 __device__ __forceinline__ void ld4(const float *p, float *o)
 {

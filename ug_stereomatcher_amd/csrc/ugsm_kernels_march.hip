@@ -27,6 +27,8 @@
 // profiles/r05_kbench_march_issue.txt.
 #include "ugsm_exact.hpp"
 #include "ugsm_launch.hpp"
+#include <cstdio>
+#include <cstdlib>
 #include <type_traits>
 
 namespace ugsm {
@@ -127,26 +129,46 @@ __device__ __forceinline__ int tex_index_nb(const float coord, const float nm1)
     return (int)__builtin_amdgcn_fmed3f(floorf(coord), 0.0f, nm1);
 }
 
-// what the load pipeline holds for one row r: (dx,dy)(r+1), the gathered R'(r), L(r-1), A(r-3) and the strip's own (dx,dy,conf)(r-3)
+// what the load pipeline holds for one row r: (dx,dy)(r+1), the gathered R'(r), L(r-1), A(r-3) and the strip's own (dx,dy,conf)(r-3).
+// PixT: what a load of an image value returns -- the float of a pyramid plane, or the byte of the camera image (level 0 of a full-mode call:
+// cost_march_body's IN), which becomes its float where the value is consumed: a conversion at the load would wait for it and end the prefetch.
+template <class PixT>
 struct MarchRow {
     float dx[NP], dy[NP];
-    float R[3][NP], L[3][NP], A[3][NP], O[3][NP];
+    PixT R[3][NP], L[3][NP];
+    float A[3][NP], O[3][NP];
 };
+__device__ __forceinline__ float pix_value(const float v) { return v; }
+__device__ __forceinline__ float pix_value(const unsigned v) { return (float)v; }  // (exact: 0 .. 255, the number the float plane held)
 
 // SEED: d3 is the coarser level's field (sm.Ws x sm.Hs) and this is the level's first iteration: every (dx, dy, conf) the
 // iteration reads is subsampleDispKernel's value (MatchLib.cu:372-401, k_seed in ugsm_kernels_ref.hip) formed on the fly,
 // SCALE * coarse[floor((x + cx + .5f) * sf), floor((y + cy + .5f) * sf)] with the product in binary64 -- the seeded field is never
 // written to memory (at 16 MP: 290 MB and a 95 us launch per level saved for ~3 % more arithmetic in this one iteration).
-template <bool EDGE, bool FAST, bool SEED = false>
+//
+// IN: kInPlanes -- L and R are the float planes of a pyramid level; kInRGB8 -- level 0 of a full-mode call, read from the camera images
+// themselves: L.p / R.p point at the interleaved rgb8 image, L.pitch / R.pitch are its row stride in BYTES.  One uniform base per image, the
+// lanes' 32-bit byte offsets row * stride + 3 * x, and the three channels are three byte loads at immediate offsets 0, 1, 2; a byte converts
+// to exactly the float the plane held, so the two forms give the same bits.
+template <bool EDGE, bool FAST, bool SEED = false, int IN = kInPlanes>
 __device__ __forceinline__ void cost_march_body(const Img3 &L, const Img3 &R, const float *__restrict__ A3, const float *__restrict__ d3,
                                                 float *__restrict__ nd3, const int W, const int H, const float thr, const int blend,
                                                 const int X0, const int xs, const int xe, const int ys, const int ye, const SeedMap sm = SeedMap{0, 0, 0, 0})
 {
+    constexpr bool U8 = IN != kInPlanes;
+    static_assert(IN == kInPlanes || IN == kInRGB8, "the float planes, or the rgb8 image");
+    constexpr int BPP = U8 ? 3 : 4;  // bytes between horizontally neighbouring values of an image row
+    using PixT = std::conditional_t<U8, unsigned, float>;
     const int lane = threadIdx.x & 63;
     const size_t n = (size_t)W * H;
     const size_t nD = SEED ? (size_t)sm.Ws * sm.Hs : n;  // plane size of the field d3 points at
-    gchar_c *const Lb[3] = {uniform_base(L.p), uniform_base(L.p + L.plane), uniform_base(L.p + 2 * L.plane)};
-    gchar_c *const Rb[3] = {uniform_base(R.p), uniform_base(R.p + R.plane), uniform_base(R.p + 2 * R.plane)};
+    gchar_c *const Lb[3] = {uniform_base(L.p), uniform_base(L.p + (U8 ? 0 : L.plane)), uniform_base(L.p + (U8 ? 0 : 2 * L.plane))};
+    gchar_c *const Rb[3] = {uniform_base(R.p), uniform_base(R.p + (U8 ? 0 : R.plane)), uniform_base(R.p + (U8 ? 0 : 2 * R.plane))};
+    // channel k of a pixel: plane k of the float form; byte k of the 8-bit form
+    auto ld_pix = [&](gchar_c *const (&base)[3], const int k, const unsigned off) -> PixT {
+        if constexpr (U8) return ld_u8_at(base[0], off, k);
+        else return ld_at(base[k], off);
+    };
     gchar_c *const Ab[3] = {uniform_base(A3), uniform_base(A3 + n), uniform_base(A3 + 2 * n)};
     gchar_c *const Db[3] = {uniform_base(d3), uniform_base(d3 + nD), uniform_base(d3 + 2 * nD)};
     gchar_c *const Nb[3] = {uniform_base(nd3), uniform_base(nd3 + n), uniform_base(nd3 + 2 * n)};
@@ -156,6 +178,7 @@ __device__ __forceinline__ void cost_march_body(const Img3 &L, const Img3 &R, co
     constexpr int SKEW = March::SKEW;
     int px[NP], po[NP];
     unsigned coff[NP], coffo[NP];  // byte offsets of the (clamped) columns px / po inside a row
+    unsigned coffL[NP];            // ... and of column px inside a row of L and R (the 8-bit form: BPP bytes per pixel)
     float xc[NP];                  // warp x coordinate of the (clamped) pixel centre
     bool cin[NP], stv[NP];
 #pragma unroll
@@ -165,6 +188,7 @@ __device__ __forceinline__ void cost_march_body(const Img3 &L, const Img3 &R, co
         const int pc = EDGE ? clampi(px[j], 0, W - 1) : px[j];
         cin[j] = !EDGE || (px[j] >= 0 && px[j] < W);
         coff[j] = (unsigned)pc * 4u;
+        coffL[j] = U8 ? (unsigned)pc * (unsigned)BPP : coff[j];
         coffo[j] = (unsigned)(EDGE || SKEW ? clampi(po[j], 0, W - 1) : po[j]) * 4u;
         xc[j] = (float)pc + 0.5f;
         stv[j] = po[j] >= xs && po[j] < xe;
@@ -182,7 +206,7 @@ __device__ __forceinline__ void cost_march_body(const Img3 &L, const Img3 &R, co
         if constexpr (SEED) return (float)(UGSM_SCALE * (double)v);
         else return v;
     };
-    const unsigned pitchW = (unsigned)W * 4u, pitchL = (unsigned)L.pitch * 4u;
+    const unsigned pitchW = (unsigned)W * 4u, pitchL = (unsigned)L.pitch * (U8 ? 1u : 4u);
     const float wm1 = (float)(W - 1), hm1 = (float)(H - 1);
     // rows are clamped (scalar ops) only in the strips that touch the frame: an interior strip keeps six rows clear of it (`interior`,
     // k_cost_march)
@@ -210,22 +234,24 @@ __device__ __forceinline__ void cost_march_body(const Img3 &L, const Img3 &R, co
         ld_row(Db[1], off, dy);
     };
     // warpAbyB (MatchLib.cu:510-515): R'[x,y] = tex(R, x + 0.5 + dx, y + 0.5 + dy) at the clamped pixel
-    auto gather = [&](const int r, const float (&dx)[NP], const float (&dy)[NP], float (&o)[3][NP]) {
+    auto gather = [&](const int r, const float (&dx)[NP], const float (&dy)[NP], PixT (&o)[3][NP]) {
         const float yc = (float)rowc(r) + 0.5f;
 #pragma unroll
         for (int j = 0; j < NP; j++) {
             const int sx = tex_index_nb(xc[j] + seedv(dx[j]), wm1);
             const int sy = tex_index_nb(yc + seedv(dy[j]), hm1);
-            const unsigned off = (__umul24((unsigned)sy, (unsigned)R.pitch) + (unsigned)sx) * 4u;
+            const unsigned off = U8 ? __umul24((unsigned)sy, (unsigned)R.pitch) + (unsigned)sx * (unsigned)BPP
+                                    : (__umul24((unsigned)sy, (unsigned)R.pitch) + (unsigned)sx) * 4u;
 #pragma unroll
-            for (int k = 0; k < 3; k++) o[k][j] = ld_at(Rb[k], off);
+            for (int k = 0; k < 3; k++) o[k][j] = ld_pix(Rb, k, off);
         }
     };
-    auto load_L = [&](const int r, float (&o)[3][NP]) {
-        unsigned off[NP];
-        row_off(r, pitchL, off);
+    auto load_L = [&](const int r, PixT (&o)[3][NP]) {
+        const unsigned ro = (unsigned)rowc(r) * pitchL;
 #pragma unroll
-        for (int k = 0; k < 3; k++) ld_row(Lb[k], off, o[k]);
+        for (int k = 0; k < 3; k++)
+#pragma unroll
+            for (int j = 0; j < NP; j++) o[k][j] = ld_pix(Lb, k, ro + coffL[j]);
     };
     auto load_AO = [&](const int r, float (&a)[3][NP], float (&od)[3][NP]) {
         unsigned off[NP];
@@ -259,7 +285,7 @@ __device__ __forceinline__ void cost_march_body(const Img3 &L, const Img3 &R, co
     // One row step.  `cur` holds row r's loads (issued during the previous step); the next row's loads are issued into
     // `nxt` before the arithmetic.  The two sets swap roles from step to step (the row loop is unrolled by two), so a
     // loaded register is never copied: a copy would have to wait for its load and would end the prefetch.
-    auto step = [&](const int r, MarchRow &cur, MarchRow &nxt) {
+    auto step = [&](const int r, MarchRow<PixT> &cur, MarchRow<PixT> &nxt) {
         load_d(r + 2, nxt.dx, nxt.dy);
         gather(r + 1, cur.dx, cur.dy, nxt.R);
         load_L(r, nxt.L);
@@ -276,7 +302,7 @@ __device__ __forceinline__ void cost_march_body(const Img3 &L, const Img3 &R, co
             float rc[NP], sq[NP], hb[NP], bnew[NP];
 #pragma unroll
             for (int j = 0; j < NP; j++) {
-                rc[j] = cur.R[k][j];
+                rc[j] = pix_value(cur.R[k][j]);
                 sq[j] = rc[j] * rc[j];  // Square, MatchLib.cu:569-570
             }
             if (!do_prod) {  // (the strip's first rows: only B is due)
@@ -287,7 +313,7 @@ __device__ __forceinline__ void cost_march_body(const Img3 &L, const Img3 &R, co
             if (do_prod) {
                 float l[NP], p[5][NP], Nv[5][NP];
 #pragma unroll
-                for (int j = 0; j < NP; j++) l[j] = (cin[j] && yin) ? cur.L[k][j] : 0.0f;
+                for (int j = 0; j < NP; j++) l[j] = (cin[j] && yin) ? pix_value(cur.L[k][j]) : 0.0f;
 #pragma unroll
                 for (int j = 0; j < NP; j++) {  // CompareMove, MatchLib.cu:622-624
                     p[0][j] = l[j] * nbr<-1>(Rm1[k]);  // shift (-1, 0)
@@ -361,7 +387,7 @@ __device__ __forceinline__ void cost_march_body(const Img3 &L, const Img3 &R, co
     // ---- prologue of the load pipeline, then the row loop (two steps per trip) ---------------------------------
     int r = ys - 3;
     const int r_end = ye + 2;  // last R' row any output of the strip needs
-    MarchRow P0, P1;
+    MarchRow<PixT> P0, P1;
     {
         float d0x[NP], d0y[NP];
         load_d(r, d0x, d0y);
@@ -421,6 +447,10 @@ __device__ __forceinline__ bool march_strip_cls(const StripClasses &sc, const in
     return ys < H;
 }
 // grid: one wave (64 threads) per strip of March::VX columns x Hs rows; strips dealt to the XCDs as contiguous bands
+// IN (cost_march_body): the float planes of a level, or level 0 of a full-mode call read from the 8-bit images.  In a batched launch of the
+// latter the two images of pair b lie at offsets of their own: L at bt.img[b], R at (bt.cy[b] << 32 | bt.cx[b]) -- the seed-crop origins are
+// zero in full mode, and their fields carry it.
+template <int IN>
 __global__ __launch_bounds__(64 * MARCH_WPB, kMarchWaves) void k_cost_march(Img3 L, Img3 R, const float *__restrict__ A3, const float *__restrict__ d3,
                                                                       float *__restrict__ nd3, int W, int H, float thr, int blend, int strips_x,
                                                                       int n_strips, int Hs, const unsigned *__restrict__ range_bad, SeedMap sm, StripClasses sc,
@@ -429,13 +459,13 @@ __global__ __launch_bounds__(64 * MARCH_WPB, kMarchWaves) void k_cost_march(Img3
     if (bt.n > 1) {  // this workgroup's pair of the batch (blockIdx.y)
         const int b = (int)blockIdx.y;
         L.p = shifted(L.p, bt.img[b]);
-        R.p = shifted(R.p, bt.img[b]);
+        R.p = shifted(R.p, IN == kInPlanes ? bt.img[b] : (long long)(((unsigned long long)(unsigned)bt.cy[b] << 32) | (unsigned)bt.cx[b]));
         A3 = shifted(A3, bt.in[b]);
         d3 = shifted(d3, bt.in[b]);
         nd3 = shifted(nd3, bt.out[b]);
         if (range_bad) range_bad += b;
-        sm.cx = bt.cx[b];
-        sm.cy = bt.cy[b];
+        sm.cx = IN == kInPlanes ? bt.cx[b] : 0;
+        sm.cy = IN == kInPlanes ? bt.cy[b] : 0;
     }
     int sx, sy, ys, ye;
     if (sc.ncls > 1) {  // (kernel-uniform) strips by age class; n_strips = strips per class group count x strips_x is passed as Hs = groups
@@ -454,20 +484,20 @@ __global__ __launch_bounds__(64 * MARCH_WPB, kMarchWaves) void k_cost_march(Img3
     const bool fast = range_bad != nullptr && __builtin_amdgcn_readfirstlane((int)*range_bad) == 0;
     if (sm.Ws > 0) {  // first iteration of a level, seeded from the coarser level's field (kernel-uniform)
         if (fast) {
-            if (interior) cost_march_body<false, true, true>(L, R, A3, d3, nd3, W, H, thr, blend, X0, xs, xe, ys, ye, sm);
-            else cost_march_body<true, true, true>(L, R, A3, d3, nd3, W, H, thr, blend, X0, xs, xe, ys, ye, sm);
+            if (interior) cost_march_body<false, true, true, IN>(L, R, A3, d3, nd3, W, H, thr, blend, X0, xs, xe, ys, ye, sm);
+            else cost_march_body<true, true, true, IN>(L, R, A3, d3, nd3, W, H, thr, blend, X0, xs, xe, ys, ye, sm);
         } else {
-            if (interior) cost_march_body<false, false, true>(L, R, A3, d3, nd3, W, H, thr, blend, X0, xs, xe, ys, ye, sm);
-            else cost_march_body<true, false, true>(L, R, A3, d3, nd3, W, H, thr, blend, X0, xs, xe, ys, ye, sm);
+            if (interior) cost_march_body<false, false, true, IN>(L, R, A3, d3, nd3, W, H, thr, blend, X0, xs, xe, ys, ye, sm);
+            else cost_march_body<true, false, true, IN>(L, R, A3, d3, nd3, W, H, thr, blend, X0, xs, xe, ys, ye, sm);
         }
         return;
     }
     if (fast) {
-        if (interior) cost_march_body<false, true>(L, R, A3, d3, nd3, W, H, thr, blend, X0, xs, xe, ys, ye);
-        else cost_march_body<true, true>(L, R, A3, d3, nd3, W, H, thr, blend, X0, xs, xe, ys, ye);
+        if (interior) cost_march_body<false, true, false, IN>(L, R, A3, d3, nd3, W, H, thr, blend, X0, xs, xe, ys, ye);
+        else cost_march_body<true, true, false, IN>(L, R, A3, d3, nd3, W, H, thr, blend, X0, xs, xe, ys, ye);
     } else {
-        if (interior) cost_march_body<false, false>(L, R, A3, d3, nd3, W, H, thr, blend, X0, xs, xe, ys, ye);
-        else cost_march_body<true, false>(L, R, A3, d3, nd3, W, H, thr, blend, X0, xs, xe, ys, ye);
+        if (interior) cost_march_body<false, false, false, IN>(L, R, A3, d3, nd3, W, H, thr, blend, X0, xs, xe, ys, ye);
+        else cost_march_body<true, false, false, IN>(L, R, A3, d3, nd3, W, H, thr, blend, X0, xs, xe, ys, ye);
     }
 }
 
@@ -508,7 +538,7 @@ int march_strip_rows(int W, int H, int throughput, int pairs)
 // the finished first waves leave behind are taken by the other pairs' kernels anyway.
 int march_age_permille[2] = {470, 340};
 static void launch_cost_march_t(hipStream_t st, Img3 L, Img3 R, const float *A3, const float *d3, float *nd3, int W, int H, float thr, int blend,
-                                int rows, const unsigned *range_bad, SeedMap sm = SeedMap{0, 0, 0, 0}, const Batch *bt = nullptr)
+                                int rows, const unsigned *range_bad, SeedMap sm = SeedMap{0, 0, 0, 0}, const Batch *bt = nullptr, int in = kInPlanes)
 {
     Batch one{};
     one.n = 1;
@@ -539,19 +569,28 @@ static void launch_cost_march_t(hipStream_t st, Img3 L, Img3 R, const float *A3,
             n_strips = 3 * strips_x * Hs;
         }
     }
-    UGSM_LAUNCH(k_cost_march, dim3(n_blocks, pairs), dim3(64 * MARCH_WPB), 0, st, L, R, A3, d3, nd3, W, H, thr, blend, strips_x, n_strips, Hs, range_bad, sm, sc, B);
+    // (in: kInPlanes, or kInRGB8 -- the one 8-bit layout K-cost is instantiated for; the callers materialise level 0 for the others and never
+    // pass another value: run_level checks.  Launching the float form on a byte view would read far outside the image.)
+    if (in != kInPlanes && in != kInRGB8) {
+        fprintf(stderr, "ugsm: launch_cost_march: no instance for input form %d\n", in);
+        abort();
+    }
+    if (in == kInRGB8)
+        UGSM_LAUNCH(k_cost_march<kInRGB8>, dim3(n_blocks, pairs), dim3(64 * MARCH_WPB), 0, st, L, R, A3, d3, nd3, W, H, thr, blend, strips_x, n_strips, Hs, range_bad, sm, sc, B);
+    else
+        UGSM_LAUNCH(k_cost_march<kInPlanes>, dim3(n_blocks, pairs), dim3(64 * MARCH_WPB), 0, st, L, R, A3, d3, nd3, W, H, thr, blend, strips_x, n_strips, Hs, range_bad, sm, sc, B);
 }
 
 void launch_cost_march_seeded(hipStream_t st, Img3 L, Img3 R, const float *A3, const float *coarse3, SeedMap sm, float *nd3, int W, int H, float thr,
-                              int blend, int rows, const unsigned *range_bad, const Batch *bt)
+                              int blend, int rows, const unsigned *range_bad, const Batch *bt, int in)
 {
-    launch_cost_march_t(st, L, R, A3, coarse3, nd3, W, H, thr, blend, rows, range_bad, sm, bt);
+    launch_cost_march_t(st, L, R, A3, coarse3, nd3, W, H, thr, blend, rows, range_bad, sm, bt, in);
 }
 
 void launch_cost_march(hipStream_t st, Img3 L, Img3 R, const float *A3, const float *d3, float *nd3, int W, int H, float thr, int blend, int rows,
-                       const unsigned *range_bad, const Batch *bt)
+                       const unsigned *range_bad, const Batch *bt, int in)
 {
-    launch_cost_march_t(st, L, R, A3, d3, nd3, W, H, thr, blend, rows, range_bad, SeedMap{0, 0, 0, 0}, bt);
+    launch_cost_march_t(st, L, R, A3, d3, nd3, W, H, thr, blend, rows, range_bad, SeedMap{0, 0, 0, 0}, bt, in);
 }
 
 }  // namespace ugsm

@@ -7,6 +7,8 @@
 #include "ugsm_exact.hpp"
 #include "ugsm_launch.hpp"
 #include <algorithm>
+#include <cstdio>
+#include <cstdlib>
 
 namespace ugsm {
 
@@ -151,6 +153,9 @@ __global__ __launch_bounds__(256) void k_blur_decimate2(const float *__restrict_
 
 // A = colconv_clamp(rowconv_clamp(L^2)) (Square + convolutionRows/ColumnsKernelT, MatchLib.cu:556-578,
 // 1461-1565), once per level: it does not depend on the iteration.  64x16 tile, region +2 clamped.
+// IN: kInPlanes -- src is the level's float planes; kInRGB8 -- level 0 of a full-mode call, which is never stored: src is a byte_view
+// (ugsm_launch.hpp) of the image itself and the tile load converts its bytes, the same values the float planes would hold.
+template <int IN>
 __global__ __launch_bounds__(256) void k_sqblur_tiled(Img3 src, int W, int H, float *__restrict__ dst3, int tiles_x, int n_tiles, Batch bt)
 {
     if (bt.n > 1) {  // this workgroup's pair of the batch (blockIdx.y)
@@ -176,9 +181,15 @@ __global__ __launch_bounds__(256) void k_sqblur_tiled(Img3 src, int W, int H, fl
         for (int u = 0; u < NLD; u++) {
             const int it = min(tid + u * 256, RH * LW - 1);
             const int r = it / LW, c = it - r * LW;
-            const size_t at = (size_t)clampi(y0 + r - 2, 0, H - 1) * src.pitch + clampi(x0 + c - 2, 0, W - 1);
+            if constexpr (IN == kInPlanes) {
+                const size_t at = (size_t)clampi(y0 + r - 2, 0, H - 1) * src.pitch + clampi(x0 + c - 2, 0, W - 1);
 #pragma unroll
-            for (int k = 0; k < 3; k++) v[u][k] = src.p[k * src.plane + at];
+                for (int k = 0; k < 3; k++) v[u][k] = src.p[k * src.plane + at];
+            } else {
+                const int gy = clampi(y0 + r - 2, 0, H - 1), gx = clampi(x0 + c - 2, 0, W - 1);
+                static_assert(InPix<IN>::channels == 3, "loadf fills the three channels");
+                InPix<IN>::loadf(reinterpret_cast<const uint8_t *>(src.p) + (size_t)gy * src.pitch + InPix<IN>::bpp * gx, v[u]);
+            }
         }
 #pragma unroll
         for (int u = 0; u < NLD; u++) {
@@ -527,7 +538,8 @@ void launch_pyr_base(hipStream_t st, const uint8_t *rgb, int stride, int W, int 
     Batch one{};
     one.n = 1;
     const Batch &B = bt ? *bt : one;
-    // Streaming form for the foveated calls only (win.w > 0: level 0 is stored in the window's strips alone).  Where level 0 is written
+    // Streaming form wherever level 0 is not written whole (win.w > 0: foveated calls store it in their window's strips alone, full-mode calls
+    // that read level 0 from the images -- kPyrNoLevel0 -- not at all; profiles/r08_trace_level0.md).  Where level 0 is written
     // whole -- 193 of 338 MB per 16 MP image -- the tiled kernel's aligned 16-byte stores win: 132 against 151 us per image, 16 MP full mode
     // 183.7 against 179.4 pairs/s; foveated batches 880 -> 903 pairs/s with it (tools/ab.py, same box).  UGSM_PYR_BASE_STREAM=2: everywhere.
     const bool streaming = (pyr_base_streaming == 1 && win.w > 0) || pyr_base_streaming == 2;
@@ -571,13 +583,20 @@ void launch_blur_decimate(hipStream_t st, const float *src3, int W, int H, float
     UGSM_LAUNCH(k_blur_decimate_tiled, dim3(n_tiles, images, 3), dim3(256), 0, st, src3, W, H, dst3, W2, H2, sf, range_bad, tiles_x, n_tiles, B);
 }
 
-void launch_sqblur_clamp(hipStream_t st, Img3 src, int W, int H, float *dst3, const Batch *bt)
+void launch_sqblur_clamp(hipStream_t st, Img3 src, int W, int H, float *dst3, const Batch *bt, int in)
 {
     Batch one{};
     one.n = 1;
     const Batch &B = bt ? *bt : one;
     const int tiles_x = (W + PTX - 1) / PTX, n_tiles = tiles_x * ((H + PTY - 1) / PTY);
-    UGSM_LAUNCH(k_sqblur_tiled, dim3(n_tiles, B.n > 1 ? B.n : 1), dim3(256), 0, st, src, W, H, dst3, tiles_x, n_tiles, B);
+    // (in: kInPlanes, or kInRGB8 -- the one 8-bit layout the level-0 kernels are instantiated for; the callers materialise level 0 for the others
+    // and never pass another value)
+    if (in != kInPlanes && in != kInRGB8) {
+        fprintf(stderr, "ugsm: launch_sqblur_clamp: no instance for input form %d\n", in);
+        abort();
+    }
+    if (in == kInRGB8) UGSM_LAUNCH(k_sqblur_tiled<kInRGB8>, dim3(n_tiles, B.n > 1 ? B.n : 1), dim3(256), 0, st, src, W, H, dst3, tiles_x, n_tiles, B);
+    else UGSM_LAUNCH(k_sqblur_tiled<kInPlanes>, dim3(n_tiles, B.n > 1 ? B.n : 1), dim3(256), 0, st, src, W, H, dst3, tiles_x, n_tiles, B);
 }
 
 // range_bad[0] = 1 if any of the `count` floats at p is outside range_ok (ugsm_exact.hpp); the caller zeroes the word first.

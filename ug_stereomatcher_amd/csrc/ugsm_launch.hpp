@@ -36,6 +36,12 @@ struct Img3 {
     int pitch;
     size_t plane;
 };
+// Level 0 of a full-mode call is the camera image itself: (float) of its bytes, never stored.  The kernels that read level 0 take the image
+// in an Img3 -- p the interleaved 8-bit image, pitch its row stride in BYTES, plane unused -- together with its InLayout (`in`).
+// K-cost and K-sq are templates on that input form: kInPlanes -- the float planes of a pyramid level -- or kInRGB8 (InLayout, ugsm_device.hpp: 0),
+// the one 8-bit layout they are instantiated for.  The launchers take it as `in` and refuse any other value.
+constexpr int kInPlanes = -1;
+inline Img3 byte_view(const uint8_t *image, int stride) { return Img3{reinterpret_cast<const float *>(image), stride, 0}; }
 
 // Where a level's first iteration finds its starting field when the seeding is fused into K-cost: the coarser level's
 // (dx, dy, conf), Ws x Hs, sampled as subsampleDispKernel does (MatchLib.cu:372-401) with the fovea crop offset (cx, cy).
@@ -165,11 +171,16 @@ inline void launch_cost_fused(hipStream_t, Img3, Img3, const float *, const floa
 // ---- K-cost ----------------------------------------------------------------------------------
 // One iteration's warp + cost + parabola + update as a marching kernel (ugsm_kernels_march.hip): one wave per strip of columns, no LDS.
 // rows = strip height (> 0 fixed; 0 / -1 / -2 / -3: launch_cost_march_t's modes).
+// in: kInPlanes -- L and R are float planes; kInRGB8 -- byte_view()s of the rgb8 images (level 0 of a full-mode call).  A batched launch of the
+// latter carries pair b's R image offset in bt->cx[b] (low word) and bt->cy[b] (high word): the two images of a pair are unrelated pointers and
+// Batch::img holds one offset.  Those fields are the seed-crop origins of the float form, so the rgb8 form takes every origin as ZERO -- true of
+// full mode, its only user; run_level refuses anything else.  (A field of its own would move the kernel arguments behind Batch in every kernel
+// that takes one -- k_pyr_base's window among them -- for one launch per pair.)
 void launch_cost_march(hipStream_t st, Img3 L, Img3 R, const float *A3, const float *d3, float *nd3, int W, int H, float thr, int blend, int rows,
-                       const unsigned *range_bad, const Batch *bt = nullptr);
+                       const unsigned *range_bad, const Batch *bt = nullptr, int in = kInPlanes);
 // First iteration of a level with the seeding fused in: coarse3 = the coarser level's field (never materialised at this level's size)
 void launch_cost_march_seeded(hipStream_t st, Img3 L, Img3 R, const float *A3, const float *coarse3, SeedMap sm, float *nd3, int W, int H, float thr,
-                              int blend, int rows, const unsigned *range_bad, const Batch *bt = nullptr);
+                              int blend, int rows, const unsigned *range_bad, const Batch *bt = nullptr, int in = kInPlanes);
 // strips by age class (ugsm_kernels_march.hip): share (per mille) of a strip group's rows for the first / second wave of a SIMD; {0, 0} = uniform
 extern int march_age_permille[2];
 // strip height the marching K-cost picks for a W x H level; host only
@@ -215,11 +226,15 @@ void launch_blur_decimate(hipStream_t st, const float *src3, int W, int H, float
 struct PyrWindow {
     int x0, y0, w, h;
 };
+// ... and the empty window: no tile or strip touches it, so level 0 is not stored at all.  Full-mode calls whose level-0 kernels read the image
+// itself (byte_view) build their pyramids with it; levels 1 and 2 come out of the same pass as ever.  (Batched: every origin 0.)
+constexpr PyrWindow kPyrNoLevel0{0, 0, 1, 0};
 // every image of the launch (rgb, and rgb + bt->img[b]) and the stride 4-byte aligned: what the word-load layouts need (input_layout)
 bool input_words_aligned(const uint8_t *rgb, int stride, const Batch *bt);
 // fmt: the input format (UGSM_INPUT_*); the four-byte formats take their word-load instances when every image and the stride are 4-byte aligned
 void launch_pyr_base(hipStream_t st, const uint8_t *rgb, int stride, int W, int H, float *lvl0, float *lvl1, int W1, int H1, float *lvl2, int W2,
                      int H2, unsigned *range_bad, const Batch *bt = nullptr, PyrWindow win = PyrWindow{0, 0, 0, 0}, int fmt = 0);
-void launch_sqblur_clamp(hipStream_t st, Img3 src, int W, int H, float *dst3, const Batch *bt = nullptr);
+// in: kInPlanes -- src is the level's float planes; kInRGB8 -- a byte_view() of the rgb8 image (level 0)
+void launch_sqblur_clamp(hipStream_t st, Img3 src, int W, int H, float *dst3, const Batch *bt = nullptr, int in = kInPlanes);
 
 }  // namespace ugsm

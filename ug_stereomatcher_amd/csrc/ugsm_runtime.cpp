@@ -123,6 +123,12 @@ struct Slot {
     size_t nomem_tot = 0;
     long long nomem_epoch = 0;
     bool have_pyr = false;
+    // Level 0 of the call in flight is read from the images themselves (level0_direct: full-mode calls) -- the pyramids hold levels 1 and up,
+    // and the level-0 launches (A, K-cost) take byte views of img0L / img0R[pair], rows img0_stride bytes apart.  The images are the caller's
+    // device buffers or the slot's uploads: valid until the call is reported either way (include/ugsm.h).
+    bool direct0 = false;
+    const uint8_t *img0L[kMaxBatch] = {}, *img0R[kMaxBatch] = {};
+    int img0_stride = 0;
     bool have_coarse = false;
     bool range_known = false;
     int cur_level = kNoLevel;  // pyramid level the launches being enqueued belong to (statistics only)  // range_bad describes the images the next run_level works on
@@ -218,6 +224,7 @@ struct ugsm_ctx {
     int two_streams = 0;  // a call alone forks onto a side stream (every context; UGSM_TWO_STREAMS=0 under UGSM_DEV=1: never)
     int march4_lo = -1, march4_hi = -1;  // development override of k_cost_march4's pixel range (use_march4; -1 = by the mode; 0, 0 = never)
     int force_alone = -1;  // development override of call_alone(): 1 = every call is taken to be alone on the chip, 0 = none is
+    int level0_float = 0;  // development override (UGSM_LEVEL0_FLOAT=1): full-mode calls store the float level 0 too and read that (level0_direct)
     int streams = 1;      // streams the slots' work is dealt onto: slot i enqueues on the stream of slot i % streams (ugsm_config.streams)
     int march_mode = 0;   // strip heights of k_cost_march when cfg.march_rows == 0 (launch_cost_march's `rows`: 0, -1, -2, -3)
     int smooth_big_min = 0;  // development override: levels of at least this many pixels run k_smooth_fused on its 112-column tile (0 = by the mode)
@@ -561,6 +568,7 @@ struct DevKnobs {
     int smooth_big_min = 0;  // UGSM_SMOOTH_BIG_MIN: pixel count from which K-smooth uses the 112-column tile (default 2^19)
     int smooth_rows = 0;     // UGSM_SMOOTH_ROWS: tile height of the large levels' K-smooth (1..39), -1 / -2 = the latency / throughput rule whatever the slots
     int march4_lo = -1, march4_hi = -1;  // UGSM_MARCH4=lo,hi: pixel range of k_cost_march4 (0,0 = never; default: march4_default_range)
+    int level0_float = 0;    // UGSM_LEVEL0_FLOAT=1: full-mode calls materialise the float level 0 as foveated calls and ugsm_submit_pyramids do
 };
 bool dev_env_on()
 {
@@ -588,6 +596,7 @@ void apply_dev_env(ugsm_config &cfg, DevKnobs &k, bool set_globals)
     geti("UGSM_TWO_STREAMS", k.two_streams);
     geti("UGSM_SMOOTH_ROWS", k.smooth_rows);
     geti("UGSM_MARCH_MODE", k.march_mode);
+    geti("UGSM_LEVEL0_FLOAT", k.level0_float);
     if (const char *e = getenv("UGSM_STREAM_PRIO")) snprintf(k.stream_prio, sizeof k.stream_prio, "%s", e);
     if (const char *e = getenv("UGSM_SIDE_PRIO")) k.side_prio = e[0];
     if (const char *e = getenv("UGSM_ALONE")) k.force_alone = e[0] == '1' ? 1 : (e[0] == '0' ? 0 : -1);
@@ -641,6 +650,7 @@ void set_policy(ugsm_ctx *c, const DevKnobs &k)
     c->march4_hi = k.march4_hi;
     c->force_alone = k.force_alone;
     c->batch_max_px = k.batch_max_px;
+    c->level0_float = k.level0_float;
 }
 
 // ---- stages ----------------------------------------------------------------------------
@@ -696,7 +706,9 @@ struct FoveaWin {
     int w = 0, h = 0;
     int x0[kMaxBatch], y0[kMaxBatch];
 };
-int build_pyramids(ugsm_ctx *ctx, Slot &s, int si, const uint8_t *const *rgb, int stride, float *pyr, hipStream_t stream = nullptr, const FoveaWin *win = nullptr)
+// skip0 (full-mode calls whose level-0 kernels read the images: Slot::direct0): level 0 is not stored at all.
+int build_pyramids(ugsm_ctx *ctx, Slot &s, int si, const uint8_t *const *rgb, int stride, float *pyr, hipStream_t stream = nullptr, const FoveaWin *win = nullptr,
+                   bool skip0 = false)
 {
     const hipStream_t pst = stream ? stream : s.st;  // (launches on the side stream are not bracketed by events: Timer records on s.st)
     const int levels = s.levels, nb = s.nb;
@@ -711,9 +723,13 @@ int build_pyramids(ugsm_ctx *ctx, Slot &s, int si, const uint8_t *const *rgb, in
         bt.cx[j] = j;
     }
     Batch bt0 = bt;  // k_pyr_base: the input-field offsets carry the pairs' window origins instead
-    if (win)
-        for (int j = 0; j < nb; j++) bt0.in[j] = ((long long)win->y0[j] << 32) | (unsigned)win->x0[j];
-    const PyrWindow pw = win ? PyrWindow{win->x0[0], win->y0[0], win->w, win->h} : PyrWindow{0, 0, 0, 0};
+    if (win || skip0)
+        for (int j = 0; j < nb; j++) bt0.in[j] = win ? ((long long)win->y0[j] << 32) | (unsigned)win->x0[j] : 0;
+    const PyrWindow pw = win ? PyrWindow{win->x0[0], win->y0[0], win->w, win->h} : (skip0 ? kPyrNoLevel0 : PyrWindow{0, 0, 0, 0});
+    if (skip0 && (win || !base)) {  // (level0_direct asks for neither)
+        ctx->err = "pyramids without level 0 are built by k_pyr_base for full-mode calls only";
+        return UGSM_ERR_STATE;
+    }
     const Batch *const pb = nb > 1 ? &bt : nullptr;
     // One full-mode pair alone on the chip: the streaming factor-2 kernel's many short workgroups on the side stream get
     // in the way of the main stream's latency-bound launches -- 112.3 pairs/s with it on every level, 114.4 with it on the launches of
@@ -916,9 +932,11 @@ int weighted_difference(ugsm_ctx *ctx, Slot &s, const float *newd3, const float 
 // starting field through the seeding map instead of from a materialised seeded field.
 // A_pre (optional, single pairs only): A = G_clamp * L^2 of this level, already computed (on the slot's side stream; the caller has made
 // the main stream wait for it); otherwise it is computed here, into s.A.
+// in (kInPlanes, or kInRGB8: level 0 of a call with Slot::direct0): Lv / Rv are byte views of the pairs' images; the level runs k_cost_march
+// (level0_direct has seen to it) and any seed map has its origin at 0.
 int run_level(ugsm_ctx *ctx, Slot &s, int si, const Img3 *Lv, const Img3 *Rv, int W, int H, int mi, int S, bool is_top, int m_from,
               int m_to, float *&cur, float *&other, float *dbg8, float *const *final_out = nullptr, const SeedMap *seed = nullptr,
-              const float *A_pre = nullptr)
+              const float *A_pre = nullptr, int in = kInPlanes)
 {
     const bool ref = ctx->cfg.kernel_path == 1;
     const double px = (double)W * H;
@@ -943,6 +961,17 @@ int run_level(ugsm_ctx *ctx, Slot &s, int si, const Img3 *Lv, const Img3 *Rv, in
     const bool march4 = !ref && use_march4(ctx, W, H, s.alone, pairs);
     const bool march = !ref && use_march(ctx, W, H, s.alone, pairs);
     const bool small = !ref && use_small_cost(ctx, W, H, s.alone, pairs);
+    if (in != kInPlanes) {  // byte views: what level0_direct promised must hold here, and the seed-crop origins -- whose Batch fields carry the R offsets -- are 0
+        bool origins0 = true;
+        for (int b = 0; seed && b < s.nb; b++) origins0 = origins0 && seed[b].cx == 0 && seed[b].cy == 0;
+        if (in != kInRGB8 || march4 || !march || early || s.nb != s.nreal || !origins0) {
+            ctx->err = in != kInRGB8 ? "level 0 from the image: no kernel instance for this input form"
+                       : !origins0   ? "level 0 from the image: a seed map with a crop origin (the rgb8 K-cost instance serves full mode only)"
+                                     : "level 0 from the image needs the level matched by k_cost_march (kernel-choice policy: march_min_pixels, k_cost_march4's range), "
+                                       "single-direction pairs and no early exit";
+            return UGSM_ERR_STATE;
+        }
+    }
     if (!ref && !march4 && !march && !small && !kDevLib) {  // (use_march gives every such level to k_cost_march: launch_cost_fused is a no-op here)
         ctx->err = "no K-cost kernel of libugsm.so covers this level (kernel-choice policy)";
         return UGSM_ERR_STATE;
@@ -955,7 +984,7 @@ int run_level(ugsm_ctx *ctx, Slot &s, int si, const Img3 *Lv, const Img3 *Rv, in
                 launch_sqblur_clamp_ref(s.st, Lv[g.b0], W, H, s.A);
             } else {
                 const Batch bt = make_batch(s, g, Lv);
-                launch_sqblur_clamp(s.st, Lv[g.b0], W, H, s.A + g.b0 * s.lvl_stride, g.n > 1 ? &bt : nullptr);
+                launch_sqblur_clamp(s.st, Lv[g.b0], W, H, s.A + g.b0 * s.lvl_stride, g.n > 1 ? &bt : nullptr, in);
             }
         });
     }
@@ -987,14 +1016,20 @@ int run_level(ugsm_ctx *ctx, Slot &s, int si, const Img3 *Lv, const Img3 *Rv, in
                 Timer t(ctx, &s, si, march4 ? KC_COST_MARCH4 : (march ? KC_COST_MARCH : (small ? KC_COST_SMALL : KC_COST)), px * g.n);
                 const size_t fo = g.b0 * s.lvl_stride;
                 const Img3 L = Lv[g.b0], R = Rv[g.b0];
-                const Batch bt = make_batch(s, g, Lv, seeded ? seed : nullptr);
+                Batch bt = make_batch(s, g, Lv, seeded ? seed : nullptr);
+                if (in != kInPlanes)  // (byte views: the R image of a pair has an offset of its own, carried where the seed-crop origins -- 0 here -- ride)
+                    for (int j = 0; j < g.n; j++) {
+                        const long long d = byte_diff(Rv[g.b0 + j].p, Rv[g.b0].p);
+                        bt.cx[j] = (int)(unsigned)(d & 0xffffffffll);
+                        bt.cy[j] = (int)(d >> 32);
+                    }
                 const Batch *pb = g.n > 1 ? &bt : nullptr;
                 const unsigned *rb = s.range_known ? s.range_bad + g.b0 : nullptr;
                 if (march4)
                     launch_cost_march4(s.st, L, R, A3 + fo, cur + fo, other + fo, W, H, thr[m - 1], blend, 0, rb, seeded ? seed[g.b0] : SeedMap{0, 0, 0, 0}, pb);
                 else if (march && seeded)
-                    launch_cost_march_seeded(s.st, L, R, A3 + fo, cur + fo, seed[g.b0], other + fo, W, H, thr[m - 1], blend, march_rows_arg(ctx), rb, pb);
-                else if (march) launch_cost_march(s.st, L, R, A3 + fo, cur + fo, other + fo, W, H, thr[m - 1], blend, march_rows_arg(ctx), rb, pb);
+                    launch_cost_march_seeded(s.st, L, R, A3 + fo, cur + fo, seed[g.b0], other + fo, W, H, thr[m - 1], blend, march_rows_arg(ctx), rb, pb, in);
+                else if (march) launch_cost_march(s.st, L, R, A3 + fo, cur + fo, other + fo, W, H, thr[m - 1], blend, march_rows_arg(ctx), rb, pb, in);
                 else if (small) launch_cost_small(s.st, L, R, A3 + fo, cur + fo, other + fo, W, H, thr[m - 1], blend, pb);
                 else launch_cost_fused(s.st, L, R, A3 + fo, cur + fo, other + fo, W, H, thr[m - 1], blend);
             });
@@ -1045,6 +1080,21 @@ void side_views(const Slot &s, int side, int lev, Img3 *out)
     for (int v = 0; v < s.nb; v++) out[v] = level_view(s, pair_pyr(s, side, v), lev, 0, 0);
 }
 
+// Level 0 of the pyramid is (float) of each byte of the image: it holds nothing the image does not, and at 16 MP storing it is 193 of the 338 MB
+// the pyramid pass writes per image.  A full-mode call therefore leaves it unwritten and its level-0 launches -- A = G_clamp * L^2 and K-cost,
+// which run last -- read the image itself: the caller's device buffer, which stays valid and untouched until the call is reported
+// (include/ugsm.h), or the slot's own upload.  Where: the fused path's k_pyr_base (three levels or more), level 0 matched by k_cost_march (the
+// one K-cost form with an 8-bit instance: the levels that large), rgb8 images (the other layouts keep the float level 0: eight more K-cost
+// bodies per layout for formats no measured workload uses), no early exit (it runs pair by pair through other buffers).  Everything
+// that hands the pyramids on -- ugsm_submit_pyramids, the foveated calls, the stage entry points -- stores level 0 as ever.
+bool level0_direct(const ugsm_ctx *ctx, const Slot &s)
+{
+    if (ctx->level0_float || ctx->cfg.kernel_path == 1 || ctx->cfg.early_exit_threshold > 0.0f || s.levels < 3) return false;
+    if (ctx->hooks.input_format != kInRGB8) return false;
+    const int pairs = launch_pairs(ctx, s, s.W, s.H);
+    return !use_march4(ctx, s.W, s.H, s.alone, pairs) && use_march(ctx, s.W, s.H, s.alone, pairs);
+}
+
 // Whether this call may use the slot's side stream: single pairs that have the chip to themselves (with four pairs in flight eight
 // streams on the four hardware queues serialise what one stream per pair lets overlap: -13 %), the fused path, no event brackets (the
 // statistics belong to one stream).
@@ -1063,7 +1113,8 @@ int enqueue_side_A(ugsm_ctx *ctx, Slot &s, int a_from)
     s.forked = true;
     HIPCHK(ctx, hipStreamWaitEvent(s.st2, s.ev_L, 0));
     for (int i = s.levels - 1; i >= a_from; i--) {  // coarsest first: that is the order the levels need them in
-        launch_sqblur_clamp(s.st2, level_view(s, s.pyrL, i, 0, 0), s.w[i], s.h[i], s.Apyr + s.off[i]);
+        if (i == 0 && s.direct0) launch_sqblur_clamp(s.st2, byte_view(s.img0L[0], s.img0_stride), s.w[0], s.h[0], s.Apyr + s.off[0], nullptr, kInRGB8);
+        else launch_sqblur_clamp(s.st2, level_view(s, s.pyrL, i, 0, 0), s.w[i], s.h[i], s.Apyr + s.off[i]);
         HIPCHK(ctx, hipEventRecord(s.ev_A[i], s.st2));
     }
     s.a_from = a_from;
@@ -1073,8 +1124,9 @@ int enqueue_side_A(ugsm_ctx *ctx, Slot &s, int a_from)
 // The pyramids of every pair of the call (s.nb = nb pairs; rgbL / rgbR: nb device pointers).
 // a_from: the levels a_from .. top get their A = G_clamp * L^2 precomputed on the side stream (full mode: 0; foveated: F-1, the
 // fine levels work on crops whose A is clamped at the crop's own border and is computed in line); < 0: none.
+// full: the call is a full-mode match and nothing else reads these pyramids -- level 0 is then read from the images where level0_direct allows.
 int enqueue_pyramids(ugsm_ctx *ctx, Slot &s, int si, const uint8_t *const *d_rgbL, const uint8_t *const *d_rgbR, int nb, int W, int H, int stride, int a_from = -1,
-                     const FoveaWin *win = nullptr)
+                     const FoveaWin *win = nullptr, bool full = false)
 {
     if (!d_rgbL || !d_rgbR || nb < 1 || nb > kMaxBatch) return UGSM_ERR_BAD_ARG;
     for (int b = 0; b < nb; b++)
@@ -1088,29 +1140,38 @@ int enqueue_pyramids(ugsm_ctx *ctx, Slot &s, int si, const uint8_t *const *d_rgb
     // statistics belong to one stream).  Otherwise fork: R's pyramid and the A planes on the side stream.
     const bool fork = side_stream_ok(ctx, s);
     s.a_from = -1;
+    const bool direct0 = full && !win && level0_direct(ctx, s);
+    s.direct0 = direct0;
+    if (direct0) {
+        for (int b = 0; b < nb; b++) {
+            s.img0L[b] = d_rgbL[b];
+            s.img0R[b] = d_rgbR[b];
+        }
+        s.img0_stride = stride;
+    }
     if (!fork) {
-        UCHK(build_pyramids(ctx, s, si, d_rgbL, stride, s.pyrL, nullptr, win));
-        UCHK(build_pyramids(ctx, s, si, d_rgbR, stride, s.pyrR, nullptr, win));
-        s.have_pyr = nb == 1 && !win;  // (the fovea-shard entry points work on single pairs, and on whole pyramids)
+        UCHK(build_pyramids(ctx, s, si, d_rgbL, stride, s.pyrL, nullptr, win, direct0));
+        UCHK(build_pyramids(ctx, s, si, d_rgbR, stride, s.pyrR, nullptr, win, direct0));
+        s.have_pyr = nb == 1 && !win && !direct0;  // (the fovea-shard entry points work on single pairs, and on whole pyramids)
         return UGSM_OK;
     }
     // the side stream starts after everything enqueued on this slot so far (the previous pair still reads pyrR and Apyr)
     HIPCHK(ctx, hipEventRecord(s.ev_in, s.st));
     s.forked = true;
     HIPCHK(ctx, hipStreamWaitEvent(s.st2, s.ev_in, 0));
-    UCHK(build_pyramids(ctx, s, si, d_rgbR, stride, s.pyrR, s.st2, win));
+    UCHK(build_pyramids(ctx, s, si, d_rgbR, stride, s.pyrR, s.st2, win, direct0));
     HIPCHK(ctx, hipEventRecord(s.ev_R, s.st2));
-    UCHK(build_pyramids(ctx, s, si, d_rgbL, stride, s.pyrL, nullptr, win));
+    UCHK(build_pyramids(ctx, s, si, d_rgbL, stride, s.pyrL, nullptr, win, direct0));
     if (a_from >= 0) UCHK(enqueue_side_A(ctx, s, a_from));
     HIPCHK(ctx, hipStreamWaitEvent(s.st, s.ev_R, 0));
     HIPCHK(ctx, hipGetLastError());
-    s.have_pyr = !win;
+    s.have_pyr = !win && !direct0;
     return UGSM_OK;
 }
 int enqueue_pyramids(ugsm_ctx *ctx, Slot &s, int si, const uint8_t *d_rgbL, const uint8_t *d_rgbR, int W, int H, int stride, int a_from = -1,
-                     const FoveaWin *win = nullptr)
+                     const FoveaWin *win = nullptr, bool full = false)
 {
-    return enqueue_pyramids(ctx, s, si, &d_rgbL, &d_rgbR, 1, W, H, stride, a_from, win);
+    return enqueue_pyramids(ctx, s, si, &d_rgbL, &d_rgbR, 1, W, H, stride, a_from, win, full);
 }
 
 // the windows of a foveated call's pairs (n offsets), for enqueue_pyramids
@@ -1159,10 +1220,18 @@ int enqueue_full(ugsm_ctx *ctx, Slot &s, int si, float *const *d_out, bool swap 
         const int mi = level_iterations(i);
         // the finest level's last smoothing launch writes the caller's buffer directly (no 193 MB device copy at 16 MP)
         const bool direct = i == 0 && ctx->cfg.kernel_path != 1 && level_smooth(0) > 0 && !(ctx->cfg.early_exit_threshold > 0.0f);
-        full_views(s, pL, i, Lv);
-        full_views(s, pR, i, Rv);
+        const bool bytes0 = i == 0 && s.direct0;  // level 0 was not stored: the images themselves
+        if (bytes0) {
+            for (int b = 0; b < nb; b++) {
+                Lv[b] = byte_view(swap ? s.img0R[b] : s.img0L[b], s.img0_stride);
+                Rv[b] = byte_view(swap ? s.img0L[b] : s.img0R[b], s.img0_stride);
+            }
+        } else {
+            full_views(s, pL, i, Lv);
+            full_views(s, pR, i, Rv);
+        }
         UCHK(run_level(ctx, s, si, Lv, Rv, s.w[i], s.h[i], mi, level_smooth(i), i == top, 1, mi, cur, other, nullptr, direct ? d_out : nullptr,
-                       seeded ? sm : nullptr, (swap || nb > 1) ? nullptr : level_A(ctx, s, i)));
+                       seeded ? sm : nullptr, (swap || nb > 1) ? nullptr : level_A(ctx, s, i), bytes0 ? kInRGB8 : kInPlanes));
         if (direct) return UGSM_OK;
         seeded = false;
         if (i > 0) {
@@ -1955,7 +2024,7 @@ int ugsm_submit_full(ugsm_ctx *ctx, int slot, const uint8_t *d_rgbL, const uint8
     UCHK(get_slot(ctx, slot, &s));
     if (!d_out) return UGSM_ERR_BAD_ARG;
     HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
-    UCHK(enqueue_pyramids(ctx, *s, slot, d_rgbL, d_rgbR, W, H, stride, 0));
+    UCHK(enqueue_pyramids(ctx, *s, slot, d_rgbL, d_rgbR, W, H, stride, 0, nullptr, true));
     UCHK(enqueue_full_lr(ctx, *s, slot, d_out));
     return mark_done(ctx, *s);
 }
@@ -2024,12 +2093,12 @@ int ugsm_submit_full_batch(ugsm_ctx *ctx, int slot, int n, const uint8_t *const 
     HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
     if (n == 1 || batch_runs_pair_by_pair(ctx)) {
         for (int b = 0; b < n; b++) {
-            UCHK(enqueue_pyramids(ctx, *s, slot, d_rgbL[b], d_rgbR[b], W, H, stride, 0));
+            UCHK(enqueue_pyramids(ctx, *s, slot, d_rgbL[b], d_rgbR[b], W, H, stride, 0, nullptr, true));
             UCHK(enqueue_full_lr(ctx, *s, slot, d_out[b]));
         }
         return mark_done(ctx, *s);
     }
-    UCHK(enqueue_pyramids(ctx, *s, slot, d_rgbL, d_rgbR, n, W, H, stride));
+    UCHK(enqueue_pyramids(ctx, *s, slot, d_rgbL, d_rgbR, n, W, H, stride, -1, nullptr, true));
     s->lr_ran = false;
     s->lr_fov_pairs = 0;
     UCHK(enqueue_full(ctx, *s, slot, d_out));
@@ -2147,7 +2216,7 @@ static int match_full_on_slot(ugsm_ctx *ctx, int slot, const uint8_t *rgbL, cons
     UCHK(stage_in(ctx, *s, rgbL, rgbR, W, H, stride));
     const size_t n = (size_t)W * H;
     UCHK(grow(ctx, s->hout, s->hout_cap, 3 * n));
-    UCHK(enqueue_pyramids(ctx, *s, slot, s->rgbL, s->rgbR, W, H, stride, 0));
+    UCHK(enqueue_pyramids(ctx, *s, slot, s->rgbL, s->rgbR, W, H, stride, 0, nullptr, true));
     UCHK(enqueue_full_lr(ctx, *s, slot, s->hout));
     float *const dst[3] = {dispH, dispV, dispC};
     if (sync) prefault_planes(ctx, dst, n);  // the GPU is busy for the next ~10 ms: touch the caller's result pages meanwhile
@@ -2269,7 +2338,7 @@ int ugsm_submit_full_batch_host(ugsm_ctx *ctx, int slot, int n, const uint8_t *c
     UCHK(grow(ctx, s->hout, s->hout_cap, std::max(per * n, s->hout_cap)));
     float *out[UGSM_MAX_BATCH];
     for (int b = 0; b < n; b++) out[b] = s->hout + b * per;
-    UCHK(enqueue_pyramids(ctx, *s, slot, dL, dR, n, W, H, stride));
+    UCHK(enqueue_pyramids(ctx, *s, slot, dL, dR, n, W, H, stride, -1, nullptr, true));
     s->lr_ran = false;
     s->lr_fov_pairs = 0;
     UCHK(enqueue_full(ctx, *s, slot, out));
@@ -2965,6 +3034,44 @@ int ugsm_stage_range_words(ugsm_ctx *ctx, int slot, unsigned *host_out, int n)
     HIPCHK(ctx, hipStreamSynchronize(s->st));  // (the main stream has joined whatever the call put on the side stream)
     HIPCHK(ctx, hipMemcpy(host_out, s->range_bad, sizeof(unsigned) * n, hipMemcpyDeviceToHost));
     return UGSM_OK;
+}
+
+// Whether the last call on the slot read level 0 from the images (Slot::direct0) -- batched and queue-formed calls included, which leave no other
+// trace of it: the results are the same bits either way.  Host state only.
+int ugsm_stage_level0_direct(ugsm_ctx *ctx, int slot)
+{
+    Slot *s;
+    const int st = get_slot(ctx, slot, &s, false);
+    if (st != UGSM_OK) return -st;
+    return s->direct0 ? 1 : 0;
+}
+
+// ugsm_stage_iterate with the two images given as rgb8 instead of float planes: the level runs the way level 0 of a full-mode call runs
+// (Slot::direct0) -- A and K-cost through their 8-bit instances, on byte views of the images -- but from the caller's field, so that a test
+// can send disparities of its own choosing through the clamped byte gather.
+int ugsm_stage_iterate_rgb8(ugsm_ctx *ctx, const uint8_t *d_rgbL, const uint8_t *d_rgbR, int stride, float *d_d3, int W, int H, int mi, int S, int is_top,
+                            int m_from, int m_to)
+{
+    Slot *s;
+    UCHK(get_slot(ctx, 0, &s));
+    if (!d_rgbL || !d_rgbR || !d_d3 || W < 1 || H < 1 || mi < 1 || m_from < 1 || m_to > mi || S < 0) return UGSM_ERR_BAD_ARG;
+    if ((long long)W * H > kMaxPixels || ctx->cfg.kernel_path == 1 || ctx->hooks.input_format != kInRGB8) return UGSM_ERR_BAD_ARG;
+    if (stride < 3 * W) return UGSM_ERR_SIZE_MISMATCH;
+    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
+    const size_t lvl = 3 * (size_t)W * H;
+    UCHK(ensure_level_bufs(ctx, *s, lvl));
+    float *cur = s->d0, *other = s->d1;
+    HIPCHK(ctx, hipMemcpyAsync(cur, d_d3, lvl * sizeof(float), hipMemcpyDeviceToDevice, s->st));
+    s->have_pyr = false;
+    s->have_coarse = false;
+    s->range_known = true;  // (the integers 0 .. 255: always inside range_ok)
+    HIPCHK(ctx, hipMemsetAsync(s->range_bad, 0, sizeof(unsigned), s->st));
+    s->nb = s->nreal = 1;
+    s->direct0 = false;  // (no call of the slot's: ugsm_stage_level0_direct)
+    const Img3 Lv = byte_view(d_rgbL, stride), Rv = byte_view(d_rgbR, stride);
+    UCHK(run_level(ctx, *s, 0, &Lv, &Rv, W, H, mi, S, is_top != 0, m_from, m_to, cur, other, nullptr, nullptr, nullptr, nullptr, kInRGB8));
+    HIPCHK(ctx, hipMemcpyAsync(d_d3, cur, lvl * sizeof(float), hipMemcpyDeviceToDevice, s->st));
+    return ugsm_wait(ctx, 0);
 }
 #endif
 
