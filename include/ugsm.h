@@ -608,6 +608,65 @@ int ugsm_point_cloud_resized_fovea(ugsm_ctx *ctx, int slot, const float *d_stack
                                    const uint8_t *d_rgbL, int W, int H, int stride, const double *P1, const double *P2, float factor,
                                    int colour_mapped, const ugsm_cloud_params *p, void *d_points, long long cap_points, long long *d_count);
 
+/* ---- the cloud from the queue: enqueue a pair, get its cloud back ------------------------------------------------------------------
+ *
+ * The slot-level cloud calls above answer UGSM_ERR_STATE while enqueued pairs are outstanding, and a managed pair never shows its device
+ * planes.  These forms of ugsm_enqueue_* carry the cloud with the pair: the call the pair goes out in runs the match, then the clouds of
+ * all its pairs on the same slot stream -- ONE launch for the call (compact: two), the pair an index of the grid, each pair's arguments
+ * read from a table in device memory.  (Where the matcher itself goes pair by pair -- calls of one pair, contexts with the full-mode LR
+ * check or early exit -- and where one pair's cloud evaluates more than 9 M sampled points, the size above which the matcher's own levels
+ * go pair by pair (a 16 MP full-mode cloud at sampling 1), the clouds are launched pair by pair too.)
+ *   The full-mode cloud is, byte for byte, what ugsm_point_cloud writes for that pair's planes and left image with the same params, P1,
+ * P2 and input format; the foveated cloud what ugsm_point_cloud_fovea_all writes for the pair's stack and its off_x, off_y -- however
+ * the queue grouped the pairs.  The colour words follow the input format captured at enqueue; with the LR check on, a compact cloud
+ * with min_conf > 0 leaves the marked pixels out, in either mode.
+ *   The spec is copied when the pair is enqueued.  Pairs of one call now also share a byte-equal spec (P1, P2, params, want_planes): a
+ * pair with another spec, or without a cloud, ends the group exactly as a pair of another kind does.
+ *   UGSM_ERR_BAD_ARG, nothing enqueued: everything ugsm_enqueue_full / ugsm_enqueue_foveated and the slot-level cloud calls reject (a null
+ * spec, sampling < 1, an unknown format, a NaN min_conf / z_min / z_max or z_min > z_max, cap_points < 0, a misaligned d_points /
+ * d_count / d_level_counts), max_points < 0, and the foveated forms on a context with fovea_levels < 2.
+ *   Device forms: d_out / d_stack receive the pair's result as with ugsm_enqueue_full / ugsm_enqueue_foveated; d_points, cap_points,
+ * *d_count and d_level_counts (may be NULL) behave as in the slot-level calls -- the count may exceed the cap, nothing is written past
+ * min(count, cap) records.  Every buffer stays valid and untouched until the pair's tag has been reported.
+ *   Managed forms: any host memory in (copied before the call returns), a library-owned page-locked cloud out, fetched with
+ * ugsm_done_cloud after the ugsm_next_done that reported the pair.  want_planes 0: the result planes are NOT downloaded -- they stay in
+ * the slot's device buffers, where the cloud reads them -- and ugsm_completion.result[] is NULL; nonzero: they are lent as by
+ * ugsm_enqueue_*_managed.  The cloud's size is only known on the device, so a managed call completes in two steps: its counts come down
+ * with the call; when the library notices the slot idle it reads them and enqueues one device-to-host copy (the copy engine, not a
+ * kernel) of stored x point_step bytes per pair on the slot's stream, and the pairs are reported when that has drained.  The slot stays
+ * busy in between; order of reporting and "a completion means every buffer of the pair, cloud buffers included, is no longer in use" are
+ * unchanged, and a failed call's pairs are reported with the call's status after the slot has drained, as ever.
+ *   Memory of the managed forms: per slot, pairs x cap x point_step bytes of device cloud (cap = max_points, or the dense size when that is
+ * 0), grown on demand and counted by ugsm_context_device_bytes -- a call that cannot get them is reported with UGSM_ERR_NOMEM; per managed
+ * buffer, page-locked staging that grows to the largest `stored` seen, never to the dense size up front (dense PCL32 at 16 MP is 514 MB
+ * per pair, and (slots + 1) x batch pairs may be outstanding).
+ *   Out of scope: the page-locked _host kind, the resized cloud and the single-level fovea cloud have no queue form. */
+typedef struct ugsm_queue_cloud {
+    double P1[12], P2[12];     /* as ugsm_point_cloud: row-major 3x4, copied at enqueue */
+    ugsm_cloud_params params;  /* sampling, format, compact, min_conf, z_min, z_max */
+    long long max_points;      /* managed: cap of the library-owned cloud; 0 = the dense size */
+    int want_planes;           /* managed: also lend the result planes through ugsm_completion.result (0: they are not downloaded) */
+    int reserved;              /* 0 */
+} ugsm_queue_cloud;
+int ugsm_enqueue_full_cloud(ugsm_ctx *ctx, const uint8_t *d_rgbL, const uint8_t *d_rgbR, int W, int H, int stride, float *d_out,
+                            const ugsm_queue_cloud *spec, void *d_points, long long cap_points, long long *d_count, uint64_t tag);
+int ugsm_enqueue_foveated_cloud(ugsm_ctx *ctx, const uint8_t *d_rgbL, const uint8_t *d_rgbR, int W, int H, int stride, int off_x, int off_y,
+                                float *d_stack, const ugsm_queue_cloud *spec, void *d_points, long long cap_points, long long *d_count,
+                                long long *d_level_counts, uint64_t tag);
+int ugsm_enqueue_full_cloud_managed(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride,
+                                    const ugsm_queue_cloud *spec, uint64_t tag);
+int ugsm_enqueue_foveated_cloud_managed(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, int off_x,
+                                        int off_y, const ugsm_queue_cloud *spec, uint64_t tag);
+typedef struct ugsm_cloud_result {
+    void *points;             /* page-locked, point_step bytes per record, valid until the NEXT ugsm_next_done on this context */
+    long long count, stored;  /* the cloud's size; records at `points` = min(count, cap) */
+    int point_step, levels;   /* 32 or 16; fovea_levels for a foveated pair, else 0 */
+    long long level_counts[UGSM_MAX_LEVELS];
+} ugsm_cloud_result;
+/* The cloud of the pair the last ugsm_next_done reported.  UGSM_ERR_STATE if that pair carried no managed cloud, if its call failed, or if
+ * nothing has been reported yet. */
+int ugsm_done_cloud(ugsm_ctx *ctx, ugsm_cloud_result *out);
+
 /* Row f-3: MatchGPULib::hierarchicalDisparity (MatchGPULib.cpp:2589-2701, kernel MatchLib.cu:435-462):
  * one full-resolution (dx, dy, conf) field from the foveated stacks -- the coarsest fovea level (the whole
  * frame) upsampled level by level (x SCALE, every channel), each finer fovea pasted at its window.

@@ -171,7 +171,7 @@ public:
         const int W = L->image.cols, H = L->image.rows;
         if (R->image.cols != W || R->image.rows != H) return UGSM_ERR_SIZE_MISMATCH;
         int st = ugsm_enqueue_full_managed(ctx_, L->image.data, R->image.data, W, H, (int)L->image.step, tag);
-        if (st == UGSM_OK) { kinds_[tag] = Kind{false, false, W, H}; st = ugsm_flush(ctx_); }
+        if (st == UGSM_OK) { kinds_[tag] = Kind{false, false, W, H, false}; st = ugsm_flush(ctx_); }
         return report(st);
     }
     template <class ImgPtr>
@@ -181,7 +181,29 @@ public:
         if (R->image.cols != W || R->image.rows != H) return UGSM_ERR_SIZE_MISMATCH;
         if (ugsm_fovea_dims(W, H, 14, foveatelevel, &fovW, &fovH) != UGSM_OK) return UGSM_ERR_BAD_ARG;
         int st = ugsm_enqueue_foveated_managed(ctx_, L->image.data, R->image.data, W, H, (int)L->image.step, 0, 0, want_pyramids ? 1 : 0, tag);
-        if (st == UGSM_OK) { kinds_[tag] = Kind{true, want_pyramids, W, H}; st = ugsm_flush(ctx_); }
+        if (st == UGSM_OK) { kinds_[tag] = Kind{true, want_pyramids, W, H, false}; st = ugsm_flush(ctx_); }
+        return report(st);
+    }
+    // ... and with the pair's coloured cloud (include/ugsm.h, "the cloud from the queue"): the cloud of doReconstructionRGB /
+    // doReconstructionRGB_FOV made on the device behind the match and lent through nextDone's Done::cloud.  spec: P1, P2, the cloud's
+    // parameters, max_points, and want_planes -- 0: the result planes are not downloaded at all (Done::planes stay null).
+    template <class ImgPtr>
+    int enqueueMatchCloud(ImgPtr L, ImgPtr R, const ugsm_queue_cloud &spec, uint64_t tag)
+    {
+        const int W = L->image.cols, H = L->image.rows;
+        if (R->image.cols != W || R->image.rows != H) return UGSM_ERR_SIZE_MISMATCH;
+        int st = ugsm_enqueue_full_cloud_managed(ctx_, L->image.data, R->image.data, W, H, (int)L->image.step, &spec, tag);
+        if (st == UGSM_OK) { kinds_[tag] = Kind{false, false, W, H, true}; st = ugsm_flush(ctx_); }
+        return report(st);
+    }
+    template <class ImgPtr>
+    int enqueueStackCloud(ImgPtr L, ImgPtr R, const ugsm_queue_cloud &spec, uint64_t tag)
+    {
+        const int W = L->image.cols, H = L->image.rows;
+        if (R->image.cols != W || R->image.rows != H) return UGSM_ERR_SIZE_MISMATCH;
+        if (ugsm_fovea_dims(W, H, 14, foveatelevel, &fovW, &fovH) != UGSM_OK) return UGSM_ERR_BAD_ARG;
+        int st = ugsm_enqueue_foveated_cloud_managed(ctx_, L->image.data, R->image.data, W, H, (int)L->image.step, 0, 0, &spec, tag);
+        if (st == UGSM_OK) { kinds_[tag] = Kind{true, false, W, H, true}; st = ugsm_flush(ctx_); }
         return report(st);
     }
     int outstanding() const { return (int)kinds_.size(); }
@@ -194,6 +216,8 @@ public:
         bool foveated, pyramids;
         int rows, cols;  // of the image
         float *planes[5];
+        bool has_cloud;           // the pair was enqueued with enqueueMatchCloud / enqueueStackCloud and its call succeeded: ...
+        ugsm_cloud_result cloud;  // ... its cloud (ugsm_done_cloud): page-locked records of the library, valid until the next nextDone
     };
     // true: *out filled -- the oldest pair has been REPORTED and no longer counts as outstanding; out->status says how its call went (a
     // failed call: logged to stderr, planes null; the caller drops whatever it keeps under the tag).  false: nothing outstanding, or
@@ -207,12 +231,14 @@ public:
         kinds_.erase(c.tag);
         out->tag = c.tag; out->status = report(c.status); out->foveated = k.foveated; out->pyramids = k.pyramids; out->rows = k.H; out->cols = k.W;
         for (int i = 0; i < 5; i++) out->planes[i] = c.status == UGSM_OK ? c.result[i] : nullptr;
+        out->cloud = ugsm_cloud_result();
+        out->has_cloud = k.cloud && c.status == UGSM_OK && report(ugsm_done_cloud(ctx_, &out->cloud)) == UGSM_OK;
         return true;
     }
 
 private:
     ugsm_ctx *ctx_;
-    struct Kind { bool foveated, pyramids; int W, H; };
+    struct Kind { bool foveated, pyramids; int W, H; bool cloud; };
     std::map<uint64_t, Kind> kinds_;
     int report(int st)
     {

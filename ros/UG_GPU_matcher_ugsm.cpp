@@ -12,12 +12,21 @@
 // ugsm_enqueue_*_managed through the shim's enqueueMatch / enqueueStack) and publishes results as they complete, in arrival order, a
 // frame or n - 1 later; the callback blocks only while n pairs are outstanding, and a 1 ms wall timer publishes what finishes between
 // frames.  16 MP full mode, one MI355X: 67-70 pairs/s blocking, ~160 pairs/s with frames in flight (bench.py, pcie_inclusive).
+//
+// Not in the reference either: the parameter `publish_cloud` (default 0).  With it on, and frames_in_flight > 1, the topic path enqueues the
+// cloud forms (ugsm_enqueue_*_cloud_managed through enqueueMatchCloud / enqueueStackCloud) and publishes every frame's coloured cloud --
+// doReconstructionRGB's, or the merged cloud of the fovea stack -- on output_pointcloud as a sensor_msgs::PointCloud2 filled from
+// ugsm_done_cloud, as INTEGRATION.md section 7 shows.  cloud_P1 / cloud_P2: the two 3x4 projection matrices, row-major, 12 numbers each (required);
+// cloud_sampling, cloud_format (0 PCL32, 1 XYZRGB16), cloud_compact, cloud_min_conf, cloud_z_min, cloud_z_max: ugsm_cloud_params;
+// cloud_max_points: the cap (0 = the dense size); cloud_only = 1: the planes are neither downloaded nor published.
 #include <cv_bridge/cv_bridge.h>
 #include <image_transport/image_transport.h>
 #include <image_transport/subscriber_filter.h>
 #include <message_filters/sync_policies/approximate_time.h>
 #include <message_filters/synchronizer.h>
+#include <ros/param.h>
 #include <ros/ros.h>
+#include <sensor_msgs/PointCloud2.h>
 #include <sensor_msgs/image_encodings.h>
 #include <stereo_msgs/DisparityImage.h>
 #include <ug_stereomatcher/GetDisparitiesGPU.h>
@@ -54,6 +63,33 @@ public:
             stack_pub_[t] = nh_.advertise<foveatedstack>(t, 1);
         for (const char *t : {"output_disparityH", "output_disparityV", "output_disparityC"})
             disp_pub_[t] = nh_.advertise<stereo_msgs::DisparityImage>(t, 1);
+        nh_.getParam("publish_cloud", publish_cloud_);
+        if (publish_cloud_ && frames_in_flight_ > 1) {
+            std::vector<double> p1, p2;
+            if (!ros::param::get("~cloud_P1", p1) || !ros::param::get("~cloud_P2", p2) || p1.size() != 12 || p2.size() != 12) {
+                ROS_ERROR("publish_cloud needs cloud_P1 and cloud_P2 (12 numbers each): no cloud is published");
+                publish_cloud_ = 0;
+            } else {
+                std::memset(&cloud_spec_, 0, sizeof cloud_spec_);
+                for (int k = 0; k < 12; k++) { cloud_spec_.P1[k] = p1[k]; cloud_spec_.P2[k] = p2[k]; }
+                ugsm_default_cloud_params(&cloud_spec_.params);
+                int cloud_only = 0, max_points = 0;
+                double v;
+                nh_.getParam("cloud_sampling", cloud_spec_.params.sampling);
+                nh_.getParam("cloud_format", cloud_spec_.params.format);
+                nh_.getParam("cloud_compact", cloud_spec_.params.compact);
+                if (ros::param::get("~cloud_min_conf", v)) cloud_spec_.params.min_conf = (float)v;
+                if (ros::param::get("~cloud_z_min", v)) cloud_spec_.params.z_min = (float)v;
+                if (ros::param::get("~cloud_z_max", v)) cloud_spec_.params.z_max = (float)v;
+                nh_.getParam("cloud_max_points", max_points);
+                nh_.getParam("cloud_only", cloud_only);
+                cloud_spec_.max_points = max_points;
+                cloud_spec_.want_planes = cloud_only ? 0 : 1;
+                cloud_pub_ = nh_.advertise<sensor_msgs::PointCloud2>("output_pointcloud", 1);
+            }
+        } else {
+            publish_cloud_ = 0;  // (the blocking path has no cloud: getPointCloud's node, or INTEGRATION.md section 7's slot-level calls)
+        }
         srv_ = nh_.advertiseService("get_disparities_srv", &GPU_matcher::disparitySrv, this);
         sync_.registerCallback(boost::bind(&GPU_matcher::mainRoutine, this, _1, _2));
     }
@@ -68,6 +104,9 @@ private:
     std::map<std::string, ros::Publisher> stack_pub_, disp_pub_;
     std::unique_ptr<MatchGPULib> mgpu_;
     int frames_in_flight_ = 1;
+    int publish_cloud_ = 0;
+    ugsm_queue_cloud cloud_spec_;
+    ros::Publisher cloud_pub_;
     std::string inflight_arg_;
     ros::WallTimer poll_timer_;
     struct InFlight { std_msgs::Header hl, hr; };
@@ -107,6 +146,30 @@ private:
         s.im_width = imW; s.im_height = imH; s.roi_width = fw; s.roi_height = fh; s.num_levels = F;
         return s;
     }
+    // the frame's cloud as an unorganised PointCloud2: one copy out of the library's page-locked records
+    static sensor_msgs::PointCloud2 cloud_msg(const ugsm_cloud_result &c, bool dense, const std_msgs::Header &h)
+    {
+        sensor_msgs::PointCloud2 msg;
+        msg.header = h;
+        msg.height = 1;
+        msg.width = (uint32_t)c.stored;
+        msg.is_bigendian = false;
+        msg.is_dense = dense;
+        msg.point_step = (uint32_t)c.point_step;
+        msg.row_step = msg.point_step * msg.width;
+        const char *names[4] = {"x", "y", "z", "rgb"};
+        const uint32_t offsets[4] = {0, 4, 8, c.point_step == 32 ? 16u : 12u};
+        msg.fields.resize(4);
+        for (int k = 0; k < 4; k++) {
+            msg.fields[k].name = names[k];
+            msg.fields[k].offset = offsets[k];
+            msg.fields[k].datatype = sensor_msgs::PointField::FLOAT32;  // rgb: the packed word, read as a float (PCL's convention)
+            msg.fields[k].count = 1;
+        }
+        msg.data.resize((size_t)c.point_step * (size_t)c.stored);
+        if (c.stored > 0) std::memcpy(msg.data.data(), c.points, msg.data.size());
+        return msg;
+    }
     // publishes the oldest finished frame; false if there is none (block == false: or it has not finished)
     bool publishNext(bool block)
     {
@@ -118,6 +181,8 @@ private:
             ROS_ERROR("ugsm: frame %llu dropped: %s", (unsigned long long)d.tag, ugsm_status_string(d.status));
             return true;
         }
+        if (d.has_cloud) cloud_pub_.publish(cloud_msg(d.cloud, cloud_spec_.params.compact != 0, f.hl));
+        if (!d.planes[0]) return true;  // (a cloud pair enqueued without its planes: cloud_only)
         if (d.foveated) {
             const int fh = mgpu_->getFoveaHeight();
             if (d.pyramids) {
@@ -221,7 +286,9 @@ private:
             const uint64_t tag = next_tag_++;
             if (fov == 1) mgpu_->initStack(L, R);
             // (a status other than UGSM_OK = the pair was REJECTED and nothing is outstanding under the tag: include/ugsm.h, ugsm_enqueue_*)
-            const int st = fov == 1 ? mgpu_->enqueueStack(L, R, true, tag) : mgpu_->enqueueMatch(L, R, tag);
+            // (the cloud forms carry no pyramid stacks: with publish_cloud the foveated path publishes the H, V, C stacks and the cloud)
+            const int st = publish_cloud_ ? (fov == 1 ? mgpu_->enqueueStackCloud(L, R, cloud_spec_, tag) : mgpu_->enqueueMatchCloud(L, R, cloud_spec_, tag))
+                                          : (fov == 1 ? mgpu_->enqueueStack(L, R, true, tag) : mgpu_->enqueueMatch(L, R, tag));
             if (st != UGSM_OK) { ROS_ERROR("ugsm enqueue failed: %s", ugsm_status_string(st)); return; }
             in_flight_[tag] = InFlight{L->header, R->header};
             while (publishNext(false)) {}

@@ -4,7 +4,8 @@
  *
  * Seven synthetic frames go through ugsm_enqueue_full_managed (any host memory in, library-owned planes out) with three frames in
  * flight; every result is compared with the blocking ugsm_match_full of the same frame (the reference node's call,
- * UG_GPU_matcher.cpp:423), byte for byte.  Prints "QUEUE_EXAMPLE_OK" on success; tests/test_gpu_queue.py runs it on the GPU box. */
+ * UG_GPU_matcher.cpp:423), byte for byte.  Then one frame goes through ugsm_enqueue_full_cloud_managed: its coloured cloud comes back from
+ * ugsm_done_cloud and its planes, asked for with want_planes, are compared as well.  Prints "QUEUE_EXAMPLE_OK" on success; tests/test_gpu_queue.py runs it on the GPU box. */
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -76,6 +77,28 @@ int main(void)
             if (block) break;
         }
         if (st != UGSM_OK && st != UGSM_PENDING && st != UGSM_EMPTY) { printf("next_done: %s: %s\n", ugsm_status_string(st), ugsm_last_error(ctx)); return 1; }
+    }
+    {   /* the same frame loop with the frame's cloud: enqueue, fetch the completion, then the cloud that belongs to it */
+        ugsm_queue_cloud spec;
+        ugsm_cloud_result cloud;
+        memset(&spec, 0, sizeof spec);
+        spec.P1[0] = spec.P1[5] = 700.0;  /* a rectified rig: f = 700 px, principal point at the centre, baseline 0.1 */
+        spec.P1[2] = W / 2.0;
+        spec.P1[6] = H / 2.0;
+        spec.P1[10] = 1.0;
+        memcpy(spec.P2, spec.P1, sizeof spec.P2);
+        spec.P2[3] = -70.0;
+        ugsm_default_cloud_params(&spec.params);  /* sampling 1, PCL32, dense */
+        spec.want_planes = 1;
+        make_frame(0, l, r);
+        st = ugsm_enqueue_full_cloud_managed(ctx, l, r, W, H, 3 * W, &spec, (uint64_t)FRAMES);
+        if (st == UGSM_OK) st = ugsm_next_done(ctx, &c, 1);
+        if (st == UGSM_OK) st = c.status;
+        if (st == UGSM_OK) st = ugsm_done_cloud(ctx, &cloud);
+        if (st != UGSM_OK) { printf("cloud pair: %s: %s\n", ugsm_status_string(st), ugsm_last_error(ctx)); return 1; }
+        if ((int)c.tag != FRAMES || cloud.count != ugsm_cloud_points(W, H, 1) || cloud.stored != cloud.count || cloud.point_step != 32 || !cloud.points) bad++;
+        for (int p = 0; p < 3; p++) bad += memcmp(c.result[p], expect + (size_t)p * px, px * sizeof(float)) != 0;
+        printf("cloud pair: %lld points of %d bytes\n", cloud.count, cloud.point_step);
     }
     printf("%d frames, %d in flight, %d library calls, %lld bytes of device memory: %s\n", reported, IN_FLIGHT, calls_seen, ugsm_context_device_bytes(ctx),
            bad ? "DIFFER" : "identical to the blocking calls");

@@ -31,6 +31,16 @@ ugsm_reconstruct_full followed by the dense ugsm_point_cloud of the W x H field.
 summed in-dispatch kernel times of a repeat, device_ms_min / _max their range; wall_ms the median host time from the first call to the
 end of ugsm_wait (launch gaps and the compact forms' memsets included); MB = count x point_step, the bytes a consumer receives; d2h_ms
 their copy to page-locked memory.
+
+    python tools/cloud_bench.py --queue [--pairs 64] [--out profiles/queue_cloud_bench.json]
+
+The cloud from the queue (ugsm_enqueue_*_cloud_managed, ugsm_done_cloud) instead: 16 MP, four slots, calls of up to eight pairs, managed
+kind (any host memory in, library-owned results out), --pairs pairs after a warm-up burst, full mode and the foveated stack.  Legs, pairs/s
+(median of five bursts after two warm-up bursts; every burst's figure is kept): planes only (ugsm_enqueue_*_managed), cloud only (XYZRGB16, sampling 2, dense),
+cloud only (XYZRGB16, sampling 1, compact: min_conf = the median confidence of the first pair), cloud plus planes (the dense cloud with
+want_planes).  Then the device time (profile_events 2: the in-dispatch events of the launches) of ONE batched cloud launch for a call of
+eight pairs against eight single-pair ugsm_point_cloud / ugsm_point_cloud_fovea_all launches on planes of the same size, for the 16 MP
+stack and for 1080p full mode, dense and compact PCL32.  --leg NAME runs one leg only (each GPU step under a time limit of its own).
 """
 import argparse
 import ctypes as C
@@ -236,6 +246,117 @@ def stack_rows(args, emit, p1, p2, dp):
                 c.free(p)
 
 
+QUEUE_LEGS = ("planes", "cloud_dense_s2", "cloud_compact_s1", "cloud_dense_s2_planes")
+
+
+def queue_rows(args, emit, p1, p2):
+    from ug_stereomatcher_amd import _lib, synth
+    W, H, levels, F = 4928, 3264, 14, 7
+    pairs = [synth.make_pair(W, H, synth.BASE_SEED + 2 + 16 * k)[:2] for k in range(2)]
+    xyz16 = _lib.UGSM_CLOUD_XYZRGB16
+    legs = [l for l in QUEUE_LEGS if args.leg in (None, l)]
+    for fovea in (False, True):
+        if args.mode not in (None, "foveated" if fovea else "full"):
+            continue
+        # the compact leg's threshold: the median confidence of the first pair (slot-level match)
+        with _lib.Context(levels=levels, fovea_levels=F) as c:
+            L, R = pairs[0]
+            pL, pR = c.to_device(L), c.to_device(R)
+            fw, fh = _lib.fovea_dims(W, H, levels, F) if fovea else (W, H)
+            plane = (F if fovea else 1) * fw * fh
+            d_out = c.alloc(3 * plane * 4)
+            if fovea:
+                c.check(c.lib.ugsm_submit_foveated(c.handle, 0, pL, pR, W, H, L.strides[0], 0, 0, d_out, None, None))
+            else:
+                c.check(c.lib.ugsm_submit_full(c.handle, 0, pL, pR, W, H, L.strides[0], d_out))
+            c.check(c.lib.ugsm_wait(c.handle, 0))
+            med = float(np.median(c.to_host(d_out + 2 * plane * 4, (plane,), np.float32)))
+        specs = {"cloud_dense_s2": _lib.queue_cloud(p1, p2, _lib.cloud_params(sampling=2, format=xyz16)),
+                 "cloud_compact_s1": _lib.queue_cloud(p1, p2, _lib.cloud_params(format=xyz16, compact=True, min_conf=med)),
+                 "cloud_dense_s2_planes": _lib.queue_cloud(p1, p2, _lib.cloud_params(sampling=2, format=xyz16), want_planes=True)}
+        for leg in legs:
+            with _lib.Context(levels=levels, fovea_levels=F, slots=4, batch=8) as c:
+                spec = specs.get(leg)
+
+                def burst(n):
+                    out, sent, t0 = 0, 0, time.perf_counter()
+                    cloud_mb = 0.0
+                    while out < n:
+                        while sent < n and sent - out < 32:
+                            L, R = pairs[sent % len(pairs)]
+                            if spec is None:
+                                (c.enqueue_foveated_managed(L, R, (0, 0), False, sent) if fovea else c.enqueue_full_managed(L, R, sent))
+                            else:
+                                (c.enqueue_foveated_cloud_managed(L, R, (0, 0), spec, sent) if fovea else c.enqueue_full_cloud_managed(L, R, spec, sent))
+                            sent += 1
+                        d = c.next_done(sent == n or sent - out >= 32)
+                        while d is not None:
+                            if spec is not None:
+                                rec, cnt, _ = c.done_cloud()
+                                cloud_mb = rec.nbytes / 1e6
+                            out += 1
+                            d = c.next_done(False) if out < n else None
+                    return n / (time.perf_counter() - t0), cloud_mb
+
+                for _ in range(2):   # warm-up: every slot's buffers, the managed staging at its final size
+                    burst(args.pairs)
+                rates = [burst(args.pairs) for _ in range(5)]
+                emit({"what": "queue_" + leg, "mode": "foveated" if fovea else "full", "size": f"{W}x{H}", "pairs": args.pairs, "slots": 4, "batch": 8,
+                      "pairs_per_s": round(float(np.median([r[0] for r in rates])), 2), "bursts_pairs_per_s": [round(r[0], 2) for r in rates],
+                      "cloud_MB_per_pair": round(rates[-1][1], 2), "min_conf": round(med, 4) if leg == "cloud_compact_s1" else None,
+                      "device_bytes": int(c.lib.ugsm_context_device_bytes(c.handle))})
+
+
+def queue_launch_rows(args, emit, p1, p2, dp):
+    """One batched cloud launch for eight pairs against eight single-pair launches, device time from the in-dispatch events."""
+    from ug_stereomatcher_amd import _lib, synth
+    P1p, P2p = p1.ctypes.data_as(dp), p2.ctypes.data_as(dp)
+    n = 8
+
+    def misc_ms(c):   # (the cloud launches are the only ones of a context without the LR check that the statistics file under "misc")
+        return sum(r["total_ms"] for r in c.kernel_stats() if r["name"] == "misc")
+
+    for fovea, W, H in ((True, 4928, 3264), (False, 1920, 1080)):
+        levels, F = 14, 7
+        L, R = synth.make_pair(W, H, synth.BASE_SEED + 2)[:2]
+        fw, fh = _lib.fovea_dims(W, H, levels, F) if fovea else (W, H)
+        plane = (F if fovea else 1) * fw * fh
+        for name, compact in (("dense_pcl32", False), ("compact_pcl32", True)):
+            prm = _lib.cloud_params(compact=compact, min_conf=0.5 if compact else None)
+            cap = _lib.fovea_cloud_points(W, H, levels, F) if fovea else _lib.cloud_points(W, H, 1)
+            with _lib.Context(levels=levels, fovea_levels=F, slots=1, batch=n, profile_events=2) as c:
+                pL, pR = c.to_device(L), c.to_device(R)
+                outs = [c.alloc(3 * plane * 4) for _ in range(n)]
+                pts = [c.alloc(cap * 32) for _ in range(n)]
+                cnts = [c.alloc(8) for _ in range(n)]
+                spec = _lib.queue_cloud(p1, p2, prm)
+                batched, single = [], []
+                for rep_ in range(args.warmup + args.reps):
+                    c.reset_kernel_stats()
+                    for b in range(n):
+                        if fovea:
+                            c.enqueue_foveated_cloud(pL, pR, W, H, L.strides[0], (0, 0), outs[b], spec, pts[b], cap, cnts[b], b)
+                        else:
+                            c.enqueue_full_cloud(pL, pR, W, H, L.strides[0], outs[b], spec, pts[b], cap, cnts[b], b)
+                    done = c.drain()
+                    assert len(done) == n and all(d.call_pairs == n for d in done)
+                    batched.append(misc_ms(c))
+                    c.reset_kernel_stats()
+                    for b in range(n):
+                        sx, sy, sc = outs[b], outs[b] + plane * 4, outs[b] + 2 * plane * 4
+                        if fovea:
+                            c.check(c.lib.ugsm_point_cloud_fovea_all(c.handle, 0, sx, sy, sc, W, H, 0, 0, pL, L.strides[0], P1p, P2p, C.byref(prm), pts[b], cap,
+                                                                     cnts[b], None))
+                        else:
+                            c.check(c.lib.ugsm_point_cloud(c.handle, 0, sx, sy, sc, pL, W, H, L.strides[0], P1p, P2p, C.byref(prm), pts[b], cap, cnts[b]))
+                    c.check(c.lib.ugsm_wait(c.handle, 0))
+                    single.append(misc_ms(c))
+                b_, s_ = batched[args.warmup:], single[args.warmup:]
+                emit({"what": "queue_cloud_launch_" + name, "mode": "foveated stack" if fovea else "full", "size": f"{W}x{H}", "pairs": n,
+                      "batched_device_ms": round(float(np.median(b_)), 4), "batched_min": round(min(b_), 4), "batched_max": round(max(b_), 4),
+                      "single_x8_device_ms": round(float(np.median(s_)), 4), "single_min": round(min(s_), 4), "single_max": round(max(s_), 4)})
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=25)
@@ -243,6 +364,10 @@ def main():
     ap.add_argument("--sizes", default="4928x3264,1920x1080")
     ap.add_argument("--resized", action="store_true", help="the resized cloud's rows instead")
     ap.add_argument("--stack", action="store_true", help="the merged cloud of the fovea stack and the two paths it replaces instead")
+    ap.add_argument("--queue", action="store_true", help="the cloud from the queue: pairs/s of the managed legs and the batched launch's device time")
+    ap.add_argument("--pairs", type=int, default=64, help="--queue: pairs per timed burst")
+    ap.add_argument("--leg", choices=QUEUE_LEGS + ("launch",), help="--queue: this leg only")
+    ap.add_argument("--mode", choices=("full", "foveated"), help="--queue: this mode only")
     ap.add_argument("--out")
     args = ap.parse_args()
     from ug_stereomatcher_amd import _lib, synth
@@ -253,10 +378,24 @@ def main():
         rows.append(r)
         print(json.dumps(r), flush=True)
 
-    copy = copy_rate_GBps(torch)
-    emit({"what": "device_copy", "GBps": round(copy, 1)})
     p1, p2 = (np.ascontiguousarray(m, np.float64).reshape(12) for m in (P1, P2))
     dp = C.POINTER(C.c_double)
+    if args.queue:
+        if args.leg != "launch":
+            queue_rows(args, emit, p1, p2)
+        if args.leg == "launch" or (args.leg is None and args.mode is None):
+            queue_launch_rows(args, emit, p1, p2, dp)
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            old = []
+            if os.path.exists(args.out) and (args.leg or args.mode):   # legs run one by one add to the file
+                with open(args.out) as f:
+                    old = json.load(f)
+            with open(args.out, "w") as f:
+                json.dump(old + rows, f, indent=1)
+        return
+    copy = copy_rate_GBps(torch)
+    emit({"what": "device_copy", "GBps": round(copy, 1)})
     if args.resized:
         resized_rows(args, emit, copy, p1, p2, dp)
         sizes = []

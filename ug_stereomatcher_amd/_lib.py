@@ -60,6 +60,8 @@ EXPORTS = [
     "ugsm_input_bytes_per_pixel", "ugsm_input_format_from_encoding", "ugsm_set_input_format", "ugsm_get_input_format",
     # the LR check of the foveated calls
     "ugsm_set_lr_check", "ugsm_get_lr_check", "ugsm_last_lr_marked_levels",
+    # the cloud from the queue
+    "ugsm_enqueue_full_cloud", "ugsm_enqueue_foveated_cloud", "ugsm_enqueue_full_cloud_managed", "ugsm_enqueue_foveated_cloud_managed", "ugsm_done_cloud",
 ]
 # ... and what include/ugsm_dev.h adds (libugsm_dev.so only)
 DEV_EXPORTS = ["ugsm_stage_poly_probe", "ugsm_stage_div3_probe", "ugsm_stage_div_probe", "ugsm_stage_range_words", "ugsm_stage_iterate_rgb8", "ugsm_stage_level0_direct"]
@@ -105,6 +107,29 @@ class CloudParams(C.Structure):
     """ugsm_cloud_params (include/ugsm.h)."""
     _fields_ = [("sampling", C.c_int), ("format", C.c_int), ("compact", C.c_int), ("min_conf", C.c_float), ("z_min", C.c_float),
                 ("z_max", C.c_float)]
+
+
+class QueueCloud(C.Structure):
+    """ugsm_queue_cloud (include/ugsm.h): the cloud job a pair is enqueued with."""
+    _fields_ = [("P1", C.c_double * 12), ("P2", C.c_double * 12), ("params", CloudParams), ("max_points", C.c_longlong), ("want_planes", C.c_int),
+                ("reserved", C.c_int)]
+
+
+class CloudResult(C.Structure):
+    """ugsm_cloud_result (include/ugsm.h): what ugsm_done_cloud reports."""
+    _fields_ = [("points", C.c_void_p), ("count", C.c_longlong), ("stored", C.c_longlong), ("point_step", C.c_int), ("levels", C.c_int),
+                ("level_counts", C.c_longlong * UGSM_MAX_LEVELS)]
+
+
+def queue_cloud(P1, P2, params: CloudParams, max_points: int = 0, want_planes: bool = False) -> QueueCloud:
+    """A ugsm_queue_cloud from two 3x4 projection matrices and the cloud's parameters."""
+    q = QueueCloud()
+    q.P1[:] = np.ascontiguousarray(P1, np.float64).reshape(12).tolist()
+    q.P2[:] = np.ascontiguousarray(P2, np.float64).reshape(12).tolist()
+    C.memmove(C.byref(q.params), C.byref(params), C.sizeof(CloudParams))
+    q.max_points = int(max_points)
+    q.want_planes = 1 if want_planes else 0
+    return q
 
 
 class LevelPlan(C.Structure):
@@ -291,6 +316,11 @@ def load(dev: bool = False):
     lib.ugsm_enqueue_foveated_host.argtypes = [vp, vp, vp, i, i, i, i, i, vp, vp, vp, vp, vp, u64]
     lib.ugsm_enqueue_full_managed.argtypes = [vp, vp, vp, i, i, i, u64]
     lib.ugsm_enqueue_foveated_managed.argtypes = [vp, vp, vp, i, i, i, i, i, i, u64]
+    lib.ugsm_enqueue_full_cloud.argtypes = [vp, vp, vp, i, i, i, vp, C.POINTER(QueueCloud), vp, C.c_longlong, vp, u64]
+    lib.ugsm_enqueue_foveated_cloud.argtypes = [vp, vp, vp, i, i, i, i, i, vp, C.POINTER(QueueCloud), vp, C.c_longlong, vp, vp, u64]
+    lib.ugsm_enqueue_full_cloud_managed.argtypes = [vp, vp, vp, i, i, i, C.POINTER(QueueCloud), u64]
+    lib.ugsm_enqueue_foveated_cloud_managed.argtypes = [vp, vp, vp, i, i, i, i, i, C.POINTER(QueueCloud), u64]
+    lib.ugsm_done_cloud.argtypes = [vp, C.POINTER(CloudResult)]
     lib.ugsm_flush.argtypes = [vp]
     lib.ugsm_next_done.argtypes = [vp, C.POINTER(Completion), i]
     lib.ugsm_queue_depth.argtypes = [vp, ip, ip, ip]
@@ -716,6 +746,39 @@ class Context:
         W, H, stride = self._pair(rgbL, rgbR)
         self.check(self.lib.ugsm_enqueue_foveated_managed(self._h, rgbL.ctypes.data, rgbR.ctypes.data, W, H, stride, int(off[0]), int(off[1]),
                                                           1 if want_pyramids else 0, tag))
+
+    # ... with the pair's cloud (ugsm_enqueue_*_cloud*): spec is a QueueCloud (queue_cloud())
+    def enqueue_full_cloud(self, d_rgbL: int, d_rgbR: int, W: int, H: int, stride: int, d_out: int, spec: QueueCloud, d_points: int, cap_points: int,
+                           d_count: int, tag: int):
+        self.check(self.lib.ugsm_enqueue_full_cloud(self._h, d_rgbL, d_rgbR, W, H, stride, d_out, C.byref(spec), d_points, int(cap_points), d_count, tag))
+
+    def enqueue_foveated_cloud(self, d_rgbL: int, d_rgbR: int, W: int, H: int, stride: int, off, d_stack: int, spec: QueueCloud, d_points: int,
+                               cap_points: int, d_count: int, tag: int, d_level_counts=None):
+        self.check(self.lib.ugsm_enqueue_foveated_cloud(self._h, d_rgbL, d_rgbR, W, H, stride, int(off[0]), int(off[1]), d_stack, C.byref(spec), d_points,
+                                                        int(cap_points), d_count, d_level_counts, tag))
+
+    def enqueue_full_cloud_managed(self, rgbL: np.ndarray, rgbR: np.ndarray, spec: QueueCloud, tag: int):
+        """Any host memory in; the cloud comes back through done_cloud() after the next_done() that reports the pair."""
+        W, H, stride = self._pair(rgbL, rgbR)
+        self.check(self.lib.ugsm_enqueue_full_cloud_managed(self._h, rgbL.ctypes.data, rgbR.ctypes.data, W, H, stride, C.byref(spec), tag))
+
+    def enqueue_foveated_cloud_managed(self, rgbL: np.ndarray, rgbR: np.ndarray, off, spec: QueueCloud, tag: int):
+        W, H, stride = self._pair(rgbL, rgbR)
+        self.check(self.lib.ugsm_enqueue_foveated_cloud_managed(self._h, rgbL.ctypes.data, rgbR.ctypes.data, W, H, stride, int(off[0]), int(off[1]),
+                                                                C.byref(spec), tag))
+
+    def done_cloud(self):
+        """The managed cloud of the pair the last next_done() reported: (records, count, level_counts).  records is a numpy view of the library's
+        page-locked staging (CLOUD_PCL32 or CLOUD_XYZRGB16, `stored` of them), valid until the next next_done() on the context: copy what is to be kept."""
+        r = CloudResult()
+        self.check(self.lib.ugsm_done_cloud(self._h, C.byref(r)))
+        dt = CLOUD_PCL32 if r.point_step == 32 else CLOUD_XYZRGB16
+        if r.stored > 0:
+            buf = (C.c_char * (int(r.stored) * r.point_step)).from_address(r.points)
+            rec = np.frombuffer(buf, dtype=dt)
+        else:
+            rec = np.empty(0, dt)
+        return rec, int(r.count), [int(r.level_counts[k]) for k in range(r.levels)]
 
     def _pair(self, rgbL: np.ndarray, rgbR: np.ndarray):
         g = self.check_image(rgbL)

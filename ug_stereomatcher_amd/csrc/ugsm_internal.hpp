@@ -11,8 +11,31 @@
 
 namespace ugsm {
 
+// A call of n pairs with a cloud each (ugsm_enqueue_*_cloud*), as the queue hands it to the runtime through CtxHooks::cloud_submit.
+struct CloudJob {
+    const uint8_t *L, *R;  // device kind: the device images; managed: the page-locked staging
+    int off_x, off_y;
+    float *out;            // device kind: d_out / d_stack
+    float *planes[3];      // managed with want_planes: the page-locked planes the pair's result goes to
+    void *points;          // device kind: d_points, cap_points, d_count, d_level_counts
+    long long cap;
+    long long *count, *level_counts;
+};
+struct CloudCall {
+    int fovea, managed, n, W, H, stride;
+    const ugsm_queue_cloud *spec;  // the call's (every pair's) spec
+    CloudJob job[UGSM_MAX_BATCH];
+};
+
 // State the layers hang on a context; the runtime owns the storage and calls the `free` hooks from ugsm_destroy (before the slots go).
 struct CtxHooks {
+    // The queue's way to the cloud work (set by ugsm_create; nullptr in a runtime that has none: tests/fake_runtime.cpp).  cloud_submit:
+    // the match of the call's pairs as ugsm_submit_*_batch[_host] enqueues it, then their clouds, on the slot's stream; a managed call's counts
+    // come down to page-locked words behind them.  cloud_finish (managed calls, once the slot has been seen idle after cloud_submit): reads
+    // the counts into res[0 .. n), asks `staging(user, pair, bytes)` for page-locked memory of stored x point_step bytes per pair (nullptr: out
+    // of memory) and enqueues the device-to-host copies on the slot's stream: the slot is busy again until they have drained.
+    int (*cloud_submit)(ugsm_ctx *, int slot, const CloudCall *call) = nullptr;
+    int (*cloud_finish)(ugsm_ctx *, int slot, int n, ugsm_cloud_result *res, void *(*staging)(void *user, int pair, long long bytes), void *user) = nullptr;
     void *queue = nullptr;
     void (*queue_free)(ugsm_ctx *, void *) = nullptr;
     void *shard = nullptr;

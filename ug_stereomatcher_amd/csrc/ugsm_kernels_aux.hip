@@ -601,6 +601,33 @@ __global__ __launch_bounds__(256) void k_triangulate_fovea(CloudArgs a, Proj P1q
     cloud_tile<true, Form>(a, CloudResize{}, P1q, P2q, &sk, level);
 }
 
+// The same forms for the pairs of a queue call in one launch (overloads on the table): blockIdx.z = the pair, whose row of the table in
+// device memory is what the single-pair forms take as kernel arguments.  The tile is cloud_tile, untouched: blockIdx.x, blockIdx.y and
+// gridDim.x are the single-pair launch's.
+template <int Form>
+__global__ __launch_bounds__(256) void k_triangulate(const CloudPair *__restrict__ table, Proj P1q, Proj P2q)
+{
+    static_assert(Form == kTriCloudCount || Form == kTriCloud, "the cloud forms of a call's pairs");
+    const CloudArgs a = table[blockIdx.z].a;
+    cloud_tile<false, Form>(a, CloudResize{}, P1q, P2q);
+}
+template <int Form>
+__global__ __launch_bounds__(256) void k_triangulate_fovea(const CloudPair *__restrict__ table, Proj P1q, Proj P2q)
+{
+    static_assert(Form == kTriStackCount || Form == kTriStack, "the stack forms of a call's pairs");
+    const CloudPair &row = table[blockIdx.z];
+    CloudArgs a = row.a;
+    const int level = blockIdx.x / row.sk.strips;
+    const CloudLevel &lv = row.sk.lv[level];
+    a.dx += lv.plane;
+    a.dy += lv.plane;
+    if (a.conf) a.conf += lv.plane;
+    a.left_margin = lv.left_margin;
+    a.upper_margin = lv.upper_margin;
+    a.scale = lv.scale;
+    cloud_tile<true, Form>(a, CloudResize{}, P1q, P2q, &row.sk, level);
+}
+
 int cloud_strips(int wc) { return (wc + kCloudTC - 1) / kCloudTC; }
 int cloud_chunks(int hc) { return (hc + kCloudTR - 1) / kCloudTR; }
 
@@ -628,6 +655,18 @@ void launch_point_cloud_stack(hipStream_t st, const CloudArgs &args, const Cloud
     const Kern count = k_triangulate_fovea<kTriStackCount>, cloud = k_triangulate_fovea<kTriStack>;
     if (args.compact) UGSM_LAUNCH(count, grid, dim3(256), 0, st, args, a, b, sk);
     UGSM_LAUNCH(cloud, grid, dim3(256), 0, st, args, a, b, sk);
+}
+
+void launch_point_cloud_batch(hipStream_t st, const CloudPair *d_table, int n, const CloudPair &shape, bool stack, const double *P1, const double *P2)
+{
+    Proj a, b;
+    for (int k = 0; k < 12; k++) { a.m[k] = P1[k]; b.m[k] = P2[k]; }
+    using Kern = void (*)(const CloudPair *, Proj, Proj);
+    const Kern count = stack ? (Kern)k_triangulate_fovea<kTriStackCount> : (Kern)k_triangulate<kTriCloudCount>;
+    const Kern cloud = stack ? (Kern)k_triangulate_fovea<kTriStack> : (Kern)k_triangulate<kTriCloud>;
+    const dim3 grid(stack ? shape.sk.F * shape.sk.strips : cloud_strips(shape.a.wc), shape.a.nchunk, n);
+    if (shape.a.compact) UGSM_LAUNCH(count, grid, dim3(256), 0, st, d_table, a, b);
+    UGSM_LAUNCH(cloud, grid, dim3(256), 0, st, d_table, a, b);
 }
 
 // =========================================================================================

@@ -133,6 +133,16 @@ int cloud_chunks(int hc);
 void launch_point_cloud(hipStream_t st, const CloudArgs &args, bool fovea, const double *P1, const double *P2, const CloudResize *rz = nullptr);
 // the same for the merged cloud of the stack; args.cnt (compact): (F * wc) * nchunk counts, F * wc column totals, F * strips strip totals
 void launch_point_cloud_stack(hipStream_t st, const CloudArgs &args, const CloudStack &sk, const double *P1, const double *P2);
+// The clouds of the n pairs of a queue call in ONE launch (compact: two), the pair = blockIdx.z: overloads of the same forms that read their
+// pair's row of a table in DEVICE memory instead of kernel arguments (sixteen CloudStacks do not fit there).  Every row holds the pair's
+// whole CloudArgs -- its planes or stack, image, its own region of the count buffer (zeroed before the launch), points, cap and count --
+// and, for the stack forms, its own CloudStack: windows at different offsets have different margins and covered rectangles.  The pairs
+// share everything that shapes the grid (pw, ph, s, compact; F and strips), which `shape` (a host copy of any row) gives.
+struct CloudPair {
+    CloudArgs a;
+    CloudStack sk;
+};
+void launch_point_cloud_batch(hipStream_t st, const CloudPair *d_table, int n, const CloudPair &shape, bool stack, const double *P1, const double *P2);
 void launch_upsample_paste(hipStream_t st, const float *src3, int W, int H, float *dst3, int W2, int H2, const float *fovH_, const float *fovV_,
                            const float *fovC_, int fovW, int fovH, int org_x, int org_y);
 // S_dx, S_dy, C of weightedDifference (MatchGPULib.cpp:1336-1437) into out3; rowsum = 3*H doubles of scratch

@@ -4,12 +4,15 @@
 // slots in rotation and reports completions in enqueue order.  This is the host logic that produced the throughput figures of rounds 3
 // and 4 from inside bench.py (plan_calls / run / submit), moved behind the C-ABI so that the C++ node's topic path
 // (/root/reference/src/gpu_matcher/UG_GPU_matcher.cpp:126-185,414-494 -- one blocking match() per callback of a single-threaded
-// ros::spin, :749-752) gets the same pipeline from three calls.  Written against the public slot-level entry points only.
+// ros::spin, :749-752) gets the same pipeline from three calls.  Written against the public slot-level entry points only -- and, for the
+// pairs that carry a cloud (ugsm_enqueue_*_cloud*), two function pointers of CtxHooks that the runtime sets in ugsm_create: no symbol of
+// the runtime's cloud work is named here, so the file still links against a runtime that has none (tests/fake_runtime.cpp).
 #include "ugsm_internal.hpp"
 
 #include <time.h>  // (no HIP header: the queue makes no HIP call -- tests/test_queue_host.py builds this file with g++ against a fake runtime)
 
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <deque>
 #include <new>
@@ -23,12 +26,15 @@ namespace {
 enum Mode { M_FULL = 0, M_FOVEA = 1 };
 enum Mem { MEM_DEVICE = 0, MEM_PINNED = 1, MEM_MANAGED = 2 };
 
-// page-locked staging of one managed pair: both images in, the result planes out
+// page-locked staging of one managed pair: both images in, the result planes out, the cloud out (ugsm_enqueue_*_cloud_managed: grown to
+// the largest cloud a pair in this buffer has stored, when the pair's count is known -- never to the dense size up front)
 struct Managed {
     uint8_t *in = nullptr;
     size_t in_cap = 0;
     float *out = nullptr;
     size_t out_cap = 0;  // floats
+    char *cloud = nullptr;
+    size_t cloud_cap = 0;  // bytes
     bool busy = false;
 };
 
@@ -41,13 +47,19 @@ struct Item {
     uint64_t tag;
     unsigned long long seq;
     int managed;  // index into Queue::pool, or -1
+    // the cloud job of a pair enqueued with ugsm_enqueue_*_cloud*: the spec as it was at enqueue, and the device kind's cloud buffers
+    bool has_cloud;
+    ugsm_queue_cloud spec;
+    void *points;
+    long long cap;
+    long long *count, *level_counts;
     bool pyr() const { return out[3] != nullptr || out[4] != nullptr; }
     // pairs of one call: one mode, one kind of memory, one geometry, one input format; host calls with pyramid stacks go out alone (the
-    // batched host entry point has none)
+    // batched host entry point has none); all with a cloud, of one byte-equal spec, or all without
     bool same_kind(const Item &o) const
     {
         return mode == o.mode && mem == o.mem && W == o.W && H == o.H && stride == o.stride && fmt == o.fmt &&
-               !(mem != MEM_DEVICE && (pyr() || o.pyr()));
+               !(mem != MEM_DEVICE && (pyr() || o.pyr())) && has_cloud == o.has_cloud && (!has_cloud || memcmp(&spec, &o.spec, sizeof spec) == 0);
     }
 };
 
@@ -56,11 +68,19 @@ struct Call {
     long long index = 0;
     std::vector<Item> items;
     size_t reported = 0;  // pairs already moved to the done list (retire_front can be resumed after an allocation failure)
+    // A managed cloud call completes in two steps (the size of a compact cloud is only known on the device).  phase 0: the match, the clouds
+    // and the download of their counts are on the slot's stream; when the slot is seen idle the finish hook reads the counts and enqueues
+    // the clouds' device-to-host copies there -- phase 1, the slot busy again; the call is retired when that has drained.  (A call whose
+    // submit failed, or whose slot reported an error, has no second step.)  Every other call is in phase 1 from the start.
+    int phase = 1;
+    std::vector<ugsm_cloud_result> clouds;  // managed cloud calls: what ugsm_done_cloud reports for each pair
 };
 
 struct Done {
     ugsm_completion c;
     int managed;  // the managed buffer the completion lends, or -1
+    bool has_cloud;  // a managed cloud pair of a call that succeeded: ...
+    ugsm_cloud_result cloud;  // ... what ugsm_done_cloud reports after this completion
 };
 
 struct Queue {
@@ -69,6 +89,8 @@ struct Queue {
     std::deque<Done> done;               // retired, not yet fetched
     std::vector<Managed> pool;
     std::vector<int> lent;               // managed buffers the last ugsm_next_done lent to the host
+    bool last_has_cloud = false;         // the pair the last ugsm_next_done reported carried a managed cloud: ...
+    ugsm_cloud_result last_cloud{};      // ... this one (ugsm_done_cloud)
     unsigned long long seq = 0, flush_upto = 0;
     bool round_restarts = false;  // a flush has closed the burst: the next pair enqueued opens a new staggered round
     long long calls = 0, calls_since_idle = 0;
@@ -97,6 +119,7 @@ void queue_free(ugsm_ctx *ctx, void *p)
     for (Managed &m : q->pool) {
         if (m.in) (void)ugsm_host_free(ctx, m.in);
         if (m.out) (void)ugsm_host_free(ctx, m.out);
+        if (m.cloud) (void)ugsm_host_free(ctx, m.cloud);
     }
     delete q;
 }
@@ -105,9 +128,16 @@ Queue *queue_of(ugsm_ctx *ctx)
 {
     CtxHooks &h = ctx_hooks(ctx);
     if (!h.queue) {
-        Queue *q = new (std::nothrow) Queue();
-        if (!q) return nullptr;
-        q->slot_busy.assign((size_t)ctx_config(ctx).slots, 0);
+        // (nothing is thrown from here: ugsm_enqueue_*_managed and ugsm_queue_depth ask outside a no_throw body, and the members' own
+        // constructors allocate)
+        Queue *q = nullptr;
+        try {
+            q = new Queue();
+            q->slot_busy.assign((size_t)ctx_config(ctx).slots, 0);
+        } catch (...) {
+            delete q;
+            return nullptr;
+        }
         h.queue = q;
         h.queue_free = queue_free;
     }
@@ -132,10 +162,54 @@ void retire_front(ugsm_ctx *ctx, Queue *q)
         d.done_ns = t;
         if (it.mem == MEM_MANAGED)
             for (int k = 0; k < 5; k++) d.result[k] = it.out[k];
-        q->done.push_back(Done{d, it.managed});
+        const bool cloud = it.has_cloud && it.mem == MEM_MANAGED && c.status == UGSM_OK && c.reported < c.clouds.size();
+        q->done.push_back(Done{d, it.managed, cloud, cloud ? c.clouds[c.reported] : ugsm_cloud_result{}});
     }
     q->slot_busy[(size_t)c.slot] = 0;
     q->flight.pop_front();
+}
+
+// page-locked room for the cloud of pair `pair` of the call being finished (CtxHooks::cloud_finish asks once the pair's count is known)
+struct StagingFor {
+    ugsm_ctx *ctx;
+    Queue *q;
+    Call *c;
+};
+void *cloud_staging(void *user, int pair, long long bytes)
+{
+    StagingFor *u = static_cast<StagingFor *>(user);
+    if (pair < 0 || (size_t)pair >= u->c->items.size() || bytes < 0) return nullptr;
+    const int idx = u->c->items[(size_t)pair].managed;
+    if (idx < 0) return nullptr;
+    Managed &m = u->q->pool[(size_t)idx];
+    if (m.cloud_cap < (size_t)bytes) {
+        if (m.cloud) (void)ugsm_host_free(u->ctx, m.cloud);
+        m.cloud = nullptr;
+        m.cloud_cap = 0;
+        void *p = nullptr;
+        if (ugsm_host_alloc(u->ctx, &p, bytes) != UGSM_OK) return nullptr;
+        m.cloud = static_cast<char *>(p);
+        m.cloud_cap = (size_t)bytes;
+    }
+    return m.cloud;
+}
+
+// The slot of a managed cloud call in phase 0 has drained (st: what ugsm_poll / ugsm_wait answered): the finish hook -- once per call -- puts
+// the clouds' copies on the slot's stream.  A call that failed has nothing to fetch; whatever the hook did enqueue before it failed is
+// drained like any other work before the pairs are reported.
+void cloud_second_step(ugsm_ctx *ctx, Queue *q, Call &c, int st)
+{
+    c.phase = 1;
+    if (st != UGSM_OK && c.status == UGSM_OK) c.status = st;
+    if (c.status != UGSM_OK) return;
+    CtxHooks &h = ctx_hooks(ctx);
+    StagingFor user{ctx, q, &c};
+    h.queue_calling = true;
+    h.queue_more = true;  // (copies only: the slot does not become a call that has the chip to itself)
+    const int fst = h.cloud_finish ? h.cloud_finish(ctx, c.slot, (int)c.items.size(), c.clouds.data(), cloud_staging, &user) : UGSM_ERR_STATE;
+    h.queue_calling = false;
+    h.queue_more = false;
+    if (fst != UGSM_OK) c.status = fst;
 }
 
 // Retires every call at the front of the flight list that has finished (never blocks).  A call whose submit FAILED is drained like any
@@ -144,8 +218,16 @@ void retire_front(ugsm_ctx *ctx, Queue *q)
 // buffer the library lends next -- are free.  The submit's status is the one reported.
 int reap(ugsm_ctx *ctx, Queue *q)
 {
+    // managed cloud calls whose first step has drained start their second, wherever they are in the flight list: a later call's clouds
+    // come down while the calls before it are still matching
+    for (Call &c : q->flight) {
+        if (c.phase != 0) continue;
+        const int st = ugsm_poll(ctx, c.slot);
+        if (st != UGSM_PENDING) cloud_second_step(ctx, q, c, st);
+    }
     while (!q->flight.empty()) {
         Call &c = q->flight.front();
+        if (c.phase == 0) break;
         const int st = ugsm_poll(ctx, c.slot);
         if (st == UGSM_PENDING) break;
         if (st != UGSM_OK && c.status == UGSM_OK) c.status = st;
@@ -158,6 +240,7 @@ int reap(ugsm_ctx *ctx, Queue *q)
 void wait_front(ugsm_ctx *ctx, Queue *q)
 {
     Call &c = q->flight.front();
+    if (c.phase == 0) cloud_second_step(ctx, q, c, ugsm_wait(ctx, c.slot));
     const int st = ugsm_wait(ctx, c.slot);
     if (st != UGSM_OK && c.status == UGSM_OK) c.status = st;
     retire_front(ctx, q);
@@ -187,6 +270,7 @@ void dispatch(ugsm_ctx *ctx, Queue *q, int n, int slot, bool more)
     Call &c = q->flight.back();
     try {
         c.items.assign(q->waiting.begin(), q->waiting.begin() + n);
+        if (c.items[0].has_cloud && c.items[0].mem == MEM_MANAGED) c.clouds.resize((size_t)n);
     } catch (...) {
         q->flight.pop_back();
         throw;  // (to the entry point's no_throw; the pairs still wait)
@@ -219,7 +303,23 @@ void dispatch(ugsm_ctx *ctx, Queue *q, int n, int slot, bool more)
     const int host_fmt = h.input_format;
     h.input_format = f.fmt;
     int st;
-    if (f.mem == MEM_DEVICE) {
+    if (f.has_cloud) {  // the match and the clouds of the call's pairs: the runtime's hook
+        CloudCall cc{};
+        cc.fovea = f.mode == M_FOVEA;
+        cc.managed = f.mem == MEM_MANAGED;
+        cc.n = n;
+        cc.W = f.W;
+        cc.H = f.H;
+        cc.stride = f.stride;
+        cc.spec = &f.spec;
+        for (int b = 0; b < n; b++) {
+            const Item &it = c.items[(size_t)b];
+            cc.job[b] = CloudJob{it.L, it.R, it.off_x, it.off_y, cc.managed ? nullptr : it.out[0], {nullptr, nullptr, nullptr}, it.points, it.cap, it.count, it.level_counts};
+            for (int k = 0; k < 3 && cc.managed; k++) cc.job[b].planes[k] = it.out[k];
+        }
+        st = h.cloud_submit ? h.cloud_submit(ctx, slot, &cc) : UGSM_ERR_STATE;
+        if (cc.managed) c.phase = 0;  // (a failed submit too: cloud_second_step sees the status once the slot has drained)
+    } else if (f.mem == MEM_DEVICE) {
         if (f.mode == M_FULL)
             st = n == 1 ? ugsm_submit_full(ctx, slot, L[0], R[0], f.W, f.H, f.stride, o0[0]) : ugsm_submit_full_batch(ctx, slot, n, L, R, f.W, f.H, f.stride, o0);
         else
@@ -372,13 +472,47 @@ int managed_get(ugsm_ctx *ctx, Queue *q, size_t in_bytes, size_t out_floats)
     return idx;
 }
 
+// What every ugsm_enqueue_*_cloud* checks of its spec and, the device kind, of its cloud buffers: the slot-level cloud calls' own checks
+// (cloud_args_ok, ugsm_runtime.cpp), made when the pair is enqueued so that a bad pair is rejected and never reported
+int check_cloud(ugsm_ctx *ctx, const ugsm_queue_cloud *spec, int W, int H, bool device, const void *points, long long cap, const long long *count,
+                const long long *level_counts)
+{
+    if (!spec) return ctx_fail(ctx, UGSM_ERR_BAD_ARG, "ugsm_enqueue_*_cloud*: null spec");
+    const ugsm_cloud_params &p = spec->params;
+    if (W < 1 || H < 1 || (long long)W * H > (1LL << 28)) return ctx_fail(ctx, UGSM_ERR_BAD_ARG, "ugsm_enqueue_*_cloud*: bad image size");
+    if (p.sampling < 1 || (p.format != UGSM_CLOUD_PCL32 && p.format != UGSM_CLOUD_XYZRGB16))
+        return ctx_fail(ctx, UGSM_ERR_BAD_ARG, "ugsm_enqueue_*_cloud*: sampling < 1 or an unknown record format");
+    if (std::isnan(p.min_conf) || std::isnan(p.z_min) || std::isnan(p.z_max) || p.z_min > p.z_max)
+        return ctx_fail(ctx, UGSM_ERR_BAD_ARG, "ugsm_enqueue_*_cloud*: a NaN min_conf / z_min / z_max, or z_min > z_max");
+    if (spec->max_points < 0) return ctx_fail(ctx, UGSM_ERR_BAD_ARG, "ugsm_enqueue_*_cloud*: max_points < 0");
+    if (device && (!points || !count || cap < 0 || ((uintptr_t)points & 15) || ((uintptr_t)count & 7) || ((uintptr_t)level_counts & 7)))
+        return ctx_fail(ctx, UGSM_ERR_BAD_ARG, "ugsm_enqueue_*_cloud: a null or misaligned cloud buffer, or cap_points < 0");
+    if (!ctx_hooks(ctx).cloud_submit || !ctx_hooks(ctx).cloud_finish) return ctx_fail(ctx, UGSM_ERR_STATE, "ugsm_enqueue_*_cloud*: this runtime makes no clouds");
+    return UGSM_OK;
+}
+void set_cloud(Item &it, const ugsm_queue_cloud *spec, void *points, long long cap, long long *count, long long *level_counts)
+{
+    it.has_cloud = true;
+    it.spec = *spec;  // (copied now: the call is formed later)
+    it.spec.reserved = 0;
+    it.points = points;
+    it.cap = cap;
+    it.count = count;
+    it.level_counts = level_counts;
+}
+
 int enqueue_managed(ugsm_ctx *ctx, int mode, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, int off_x, int off_y, int want_pyr,
-                    uint64_t tag)
+                    uint64_t tag, const ugsm_queue_cloud *spec = nullptr, bool cloud = false)
 {
     if (!ctx) return UGSM_ERR_BAD_ARG;
     if (!rgbL || !rgbR) return ctx_fail(ctx, UGSM_ERR_BAD_ARG, "ugsm_enqueue_*_managed: null image");
     const int g = check_geometry(ctx, W, H, stride, mode == M_FOVEA);
     if (g != UGSM_OK) return g;
+    if (cloud) {
+        const int cs = check_cloud(ctx, spec, W, H, false, nullptr, 0, nullptr, nullptr);
+        if (cs != UGSM_OK) return cs;
+    }
+    const bool planes = !cloud || spec->want_planes != 0;  // (a cloud pair that does not want its planes has no room for them)
     Queue *q = queue_of(ctx);
     if (!q) return ctx_fail(ctx, UGSM_ERR_NOMEM, "ugsm_enqueue_*: out of host memory");
     const ugsm_config &cfg = ctx_config(ctx);
@@ -388,12 +522,12 @@ int enqueue_managed(ugsm_ctx *ctx, int mode, const uint8_t *rgbL, const uint8_t 
     size_t plane, out_floats;
     if (mode == M_FULL) {
         plane = (size_t)W * H;
-        out_floats = 3 * plane;
+        out_floats = planes ? 3 * plane : 0;
     } else {
         int fw = 0, fh = 0;
         (void)ugsm_fovea_dims(W, H, cfg.levels, cfg.fovea_levels, &fw, &fh);
         plane = (size_t)cfg.fovea_levels * fw * fh;
-        out_floats = 3 * plane + (want_pyr ? 6 * plane : 0);
+        out_floats = (planes ? 3 * plane : 0) + (want_pyr ? 6 * plane : 0);
     }
     int idx = -1;
     const int grown = no_throw(ctx, "ugsm_enqueue_*_managed: out of host memory", [&]() -> int {
@@ -422,13 +556,14 @@ int enqueue_managed(ugsm_ctx *ctx, int mode, const uint8_t *rgbL, const uint8_t 
     it.stride = (int)row;
     it.off_x = off_x;
     it.off_y = off_y;
-    it.out[0] = m.out;
-    it.out[1] = m.out + plane;
-    it.out[2] = m.out + 2 * plane;
+    it.out[0] = planes ? m.out : nullptr;
+    it.out[1] = planes ? m.out + plane : nullptr;
+    it.out[2] = planes ? m.out + 2 * plane : nullptr;
     it.out[3] = (mode == M_FOVEA && want_pyr) ? m.out + 3 * plane : nullptr;
     it.out[4] = (mode == M_FOVEA && want_pyr) ? m.out + 6 * plane : nullptr;
     it.tag = tag;
     it.managed = idx;
+    if (cloud) set_cloud(it, spec, nullptr, 0, nullptr, nullptr);
     const int st = enqueue(ctx, it);
     if (st != UGSM_OK) q->pool[(size_t)idx].busy = false;  // (rejected: the staging buffer is free again)
     return st;
@@ -466,6 +601,8 @@ int next_done(ugsm_ctx *ctx, ugsm_completion *out, int block)
     const int m = q->done.front().managed;
     if (m >= 0) q->lent.push_back(m);  // (before the completion leaves the list: a push_back that throws loses nothing)
     *out = q->done.front().c;
+    q->last_has_cloud = q->done.front().has_cloud;
+    q->last_cloud = q->done.front().cloud;
     q->done.pop_front();
     // (pairs that waited for room may go out now; the slot-level entry points open up again once nothing is outstanding)
     pump(ctx, q, false);
@@ -618,6 +755,79 @@ int ugsm_enqueue_foveated_managed(ugsm_ctx *ctx, const uint8_t *rgbL, const uint
                                   uint64_t tag)
 {
     return enqueue_managed(ctx, M_FOVEA, rgbL, rgbR, W, H, stride, off_x, off_y, want_pyramids, tag);
+}
+
+int ugsm_enqueue_full_cloud(ugsm_ctx *ctx, const uint8_t *d_rgbL, const uint8_t *d_rgbR, int W, int H, int stride, float *d_out,
+                            const ugsm_queue_cloud *spec, void *d_points, long long cap_points, long long *d_count, uint64_t tag)
+{
+    if (!ctx) return UGSM_ERR_BAD_ARG;
+    if (!d_rgbL || !d_rgbR || !d_out) return ctx_fail(ctx, UGSM_ERR_BAD_ARG, "ugsm_enqueue_full_cloud: null buffer");
+    const int g = check_geometry(ctx, W, H, stride, false);
+    if (g != UGSM_OK) return g;
+    const int cs = check_cloud(ctx, spec, W, H, true, d_points, cap_points, d_count, nullptr);
+    if (cs != UGSM_OK) return cs;
+    Item it{};
+    it.mode = M_FULL;
+    it.mem = MEM_DEVICE;
+    it.L = d_rgbL;
+    it.R = d_rgbR;
+    it.W = W;
+    it.H = H;
+    it.stride = stride;
+    it.out[0] = d_out;
+    it.tag = tag;
+    it.managed = -1;
+    set_cloud(it, spec, d_points, cap_points, d_count, nullptr);
+    return enqueue(ctx, it);
+}
+
+int ugsm_enqueue_foveated_cloud(ugsm_ctx *ctx, const uint8_t *d_rgbL, const uint8_t *d_rgbR, int W, int H, int stride, int off_x, int off_y,
+                                float *d_stack, const ugsm_queue_cloud *spec, void *d_points, long long cap_points, long long *d_count,
+                                long long *d_level_counts, uint64_t tag)
+{
+    if (!ctx) return UGSM_ERR_BAD_ARG;
+    if (!d_rgbL || !d_rgbR || !d_stack) return ctx_fail(ctx, UGSM_ERR_BAD_ARG, "ugsm_enqueue_foveated_cloud: null buffer");
+    const int g = check_geometry(ctx, W, H, stride, true);
+    if (g != UGSM_OK) return g;
+    const int cs = check_cloud(ctx, spec, W, H, true, d_points, cap_points, d_count, d_level_counts);
+    if (cs != UGSM_OK) return cs;
+    Item it{};
+    it.mode = M_FOVEA;
+    it.mem = MEM_DEVICE;
+    it.L = d_rgbL;
+    it.R = d_rgbR;
+    it.W = W;
+    it.H = H;
+    it.stride = stride;
+    it.off_x = off_x;
+    it.off_y = off_y;
+    it.out[0] = d_stack;
+    it.tag = tag;
+    it.managed = -1;
+    set_cloud(it, spec, d_points, cap_points, d_count, d_level_counts);
+    return enqueue(ctx, it);
+}
+
+int ugsm_enqueue_full_cloud_managed(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, const ugsm_queue_cloud *spec,
+                                    uint64_t tag)
+{
+    return enqueue_managed(ctx, M_FULL, rgbL, rgbR, W, H, stride, 0, 0, 0, tag, spec, true);
+}
+
+int ugsm_enqueue_foveated_cloud_managed(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, int off_x, int off_y,
+                                        const ugsm_queue_cloud *spec, uint64_t tag)
+{
+    return enqueue_managed(ctx, M_FOVEA, rgbL, rgbR, W, H, stride, off_x, off_y, 0, tag, spec, true);
+}
+
+int ugsm_done_cloud(ugsm_ctx *ctx, ugsm_cloud_result *out)
+{
+    if (!ctx || !out) return UGSM_ERR_BAD_ARG;
+    Queue *q = queue_of(ctx);
+    if (!q) return ctx_fail(ctx, UGSM_ERR_NOMEM, "ugsm_done_cloud: out of host memory");
+    if (!q->last_has_cloud) return ctx_fail(ctx, UGSM_ERR_STATE, "ugsm_done_cloud: the last pair ugsm_next_done reported carried no managed cloud");
+    *out = q->last_cloud;
+    return UGSM_OK;
 }
 
 int ugsm_flush(ugsm_ctx *ctx)

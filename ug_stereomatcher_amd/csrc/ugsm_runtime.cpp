@@ -110,6 +110,18 @@ struct Slot {
     double *wd_host = nullptr;      // page-locked, 3 doubles
     unsigned *cloud_cnt = nullptr;  // row f-1 cloud, compact: per (column, chunk) counts + column and strip totals (CloudArgs.cnt)
     size_t cloud_cap = 0;
+    // The queue's cloud calls (queue_cloud_submit / queue_cloud_finish): the table of the call's batched cloud launch -- in device memory, and
+    // the page-locked copy it is uploaded from on the slot's stream (rewritten only by the slot's next call, i.e. after this one has finished);
+    // managed calls: the device clouds of the pairs (pair b at cq_pts + b * cq_stride bytes, cq_cap[b] records of cq_step bytes), their count
+    // words (kCqWords per pair: the count, then the level counts) and the page-locked words those come down to with the call
+    CloudPair *cq_tab = nullptr, *cq_tab_h = nullptr;
+    size_t cq_tab_cap = 0;
+    char *cq_pts = nullptr;
+    size_t cq_pts_cap = 0, cq_stride = 0;
+    long long *cq_words = nullptr, *cq_words_h = nullptr;
+    size_t cq_words_cap = 0;
+    long long cq_cap[kMaxBatch] = {};
+    int cq_n = 0, cq_step = 0, cq_levels = 0;  // the managed cloud call in flight: pairs, bytes per record, fovea levels (0: full mode)
     int iters_run[UGSM_MAX_LEVELS];
     unsigned *range_bad = nullptr;  // device word: 0 while every pyramid value of the pair in this slot passed range_ok (ugsm_exact.hpp)
     float *hout = nullptr;  // device staging for host-API outputs
@@ -1780,6 +1792,9 @@ static int check_config(const ugsm_config &cfg)
     return UGSM_OK;
 }
 
+static int queue_cloud_submit(ugsm_ctx *ctx, int slot, const CloudCall *call);
+static int queue_cloud_finish(ugsm_ctx *ctx, int slot, int n, ugsm_cloud_result *res, void *(*staging)(void *, int, long long), void *user);
+
 int ugsm_create(const ugsm_config *cfg_in, ugsm_ctx **out)
 {
     if (!out) return UGSM_ERR_BAD_ARG;
@@ -1810,6 +1825,8 @@ int ugsm_create(const ugsm_config *cfg_in, ugsm_ctx **out)
     ctx->cfg = cfg;
     ctx->lr_tau = cfg.lr_check_threshold;
     ctx->lr_modes = UGSM_LR_FULL;
+    ctx->hooks.cloud_submit = queue_cloud_submit;  // (the queue's way to the cloud work: ugsm_internal.hpp)
+    ctx->hooks.cloud_finish = queue_cloud_finish;
     set_policy(ctx, knobs);
     if (dev_env_on() && getenv("UGSM_MEM_LIMIT_MB")) ctx->mem_limit = atoll(getenv("UGSM_MEM_LIMIT_MB")) << 20;
     // The side stream pays when a pair is alone on the chip (115.6 against 113.9 pairs/s at 16 MP: the right pyramid and the A planes run
@@ -1925,6 +1942,10 @@ void ugsm_destroy(ugsm_ctx *ctx)
         if (s.Apyr) (void)hipFree(s.Apyr);
         if (s.lr) (void)hipFree(s.lr);
         if (s.cloud_cnt) (void)hipFree(s.cloud_cnt);
+        for (void *p : {(void *)s.cq_tab, (void *)s.cq_pts, (void *)s.cq_words})
+            if (p) (void)hipFree(p);
+        if (s.cq_tab_h) (void)hipHostFree(s.cq_tab_h);
+        if (s.cq_words_h) (void)hipHostFree(s.cq_words_h);
         if (s.lr_host) (void)hipHostFree(s.lr_host);
         if (s.st2 && s.owns_st2) (void)hipStreamDestroy(s.st2);
         if (s.st && s.owns_st) (void)hipStreamDestroy(s.st);
@@ -2859,6 +2880,216 @@ int ugsm_point_cloud_resized_fovea(ugsm_ctx *ctx, int slot, const float *d_stack
                           d_points, cap_points, d_count));
     const CloudResize rz = resize_args(a, factor, colour_mapped);
     return point_cloud(ctx, slot, a, true, P1, P2, &rz);
+}
+
+// ---- the cloud from the queue (ugsm_enqueue_*_cloud*): a call of n pairs and their clouds -------------------------------------------
+// The match goes onto the slot's stream as the batch entry points above put it there (the same helpers in the same order, so the planes are
+// the same bits); the clouds follow on the same stream.  A call the matcher runs in lockstep gets ONE cloud launch for its pairs (compact:
+// two; launch_point_cloud_batch), from a table uploaded on the stream ahead of it.  A call the matcher runs pair by pair (one pair; the
+// full-mode LR check, early exit) gets pair b's cloud behind pair b's match: a managed call of that kind reuses the slot's image and plane
+// buffers for every pair.  So does a call whose pairs each evaluate more than kBatchMaxPixels sampled points -- the size above which the
+// matcher's own levels go pair by pair, because one pair's launch fills the chip many times over and a batch index buys nothing.
+namespace {
+constexpr size_t kCqWords = 1 + UGSM_MAX_LEVELS;  // a managed pair's count words: the count, the level counts
+
+int queue_cloud_launch(ugsm_ctx *ctx, Slot &s, int si, int b0, int n, bool stack, const ugsm_queue_cloud *spec)
+{
+    const CloudPair &shape = s.cq_tab_h[b0];
+    {
+        Timer t(ctx, &s, si, KC_MISC, (double)n * (stack ? shape.sk.F : 1) * shape.a.wc * shape.a.hc);
+        launch_point_cloud_batch(s.st, s.cq_tab + b0, n, shape, stack, spec->P1, spec->P2);
+    }
+    HIPCHK(ctx, hipGetLastError());
+    return UGSM_OK;
+}
+}  // namespace
+
+static int queue_cloud_submit(ugsm_ctx *ctx, int slot, const CloudCall *call)
+{
+    Slot *s;
+    UCHK(get_slot(ctx, slot, &s));
+    if (!call || !call->spec || call->n < 1 || call->n > UGSM_MAX_BATCH) return UGSM_ERR_BAD_ARG;
+    const ugsm_queue_cloud &spec = *call->spec;
+    const ugsm_cloud_params &p = spec.params;
+    const int n = call->n, W = call->W, H = call->H, stride = call->stride, F = ctx->cfg.fovea_levels;
+    const bool fovea = call->fovea != 0, managed = call->managed != 0, planes = managed && spec.want_planes != 0;
+    if (fovea && F < 2) return UGSM_ERR_BAD_ARG;
+    if (W < 1 || H < 1) return UGSM_ERR_BAD_ARG;
+    if (stride < input_row_bytes(ctx, W)) return UGSM_ERR_SIZE_MISMATCH;
+    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
+    s->cq_n = 0;
+    const bool by_pair = n == 1 || (fovea ? fovea_batch_runs_pair_by_pair(ctx) : batch_runs_pair_by_pair(ctx));
+    int fw = W, fh = H;
+    if (fovea) UCHK(ugsm_fovea_dims(W, H, ctx->cfg.levels, F, &fw, &fh));
+    const size_t px = (size_t)W * H, fn = (size_t)fw * fh, stackn = (size_t)F * fn;
+    const size_t plane = fovea ? stackn : px;  // floats per result plane: the pair's result is three of them
+    const int step = p.format == UGSM_CLOUD_PCL32 ? 32 : 16;
+
+    // 1. where every pair's images, state and result lie on the device
+    const uint8_t *dL[UGSM_MAX_BATCH], *dR[UGSM_MAX_BATCH];
+    float *state[UGSM_MAX_BATCH], *res[UGSM_MAX_BATCH];
+    const size_t st_per = fovea ? ((3 * fn + 63) & ~(size_t)63) : 0, res_per = (3 * plane + 63) & ~(size_t)63;
+    if (managed) {
+        // the slot's uploads and hout: [states][results], one of each for a call that runs pair by pair, n otherwise
+        const int copies = by_pair ? 1 : n;
+        const size_t img = ((size_t)stride * H + 255) & ~(size_t)255;
+        if (img * copies > s->rgb_cap) {
+            size_t c = s->rgb_cap;
+            UCHK(grow(ctx, s->rgbL, c, img * copies));
+            UCHK(grow(ctx, s->rgbR, s->rgb_cap, img * copies));
+        }
+        UCHK(grow(ctx, s->hout, s->hout_cap, std::max(copies * (st_per + res_per), s->hout_cap)));
+        for (int b = 0; b < n; b++) {
+            const int k = by_pair ? 0 : b;
+            dL[b] = s->rgbL + k * img;
+            dR[b] = s->rgbR + k * img;
+            state[b] = s->hout + k * st_per;
+            res[b] = s->hout + copies * st_per + k * res_per;
+        }
+    } else {
+        UCHK(grow(ctx, s->hout, s->hout_cap, std::max(st_per * n, s->hout_cap)));
+        for (int b = 0; b < n; b++) {
+            if (!call->job[b].L || !call->job[b].R || !call->job[b].out) return UGSM_ERR_BAD_ARG;
+            dL[b] = call->job[b].L;
+            dR[b] = call->job[b].R;
+            state[b] = s->hout + (by_pair ? 0 : b * st_per);
+            res[b] = call->job[b].out;
+        }
+    }
+
+    // 2. the table: every pair's cloud arguments
+    if ((size_t)n > s->cq_tab_cap) {
+        if (s->cq_tab_h) HIPCHK(ctx, hipHostFree(s->cq_tab_h));
+        s->cq_tab_h = nullptr;
+        UCHK(grow(ctx, s->cq_tab, s->cq_tab_cap, (size_t)kMaxBatch));
+        HIPCHK(ctx, hipHostMalloc((void **)&s->cq_tab_h, kMaxBatch * sizeof(CloudPair), hipHostMallocDefault));
+    }
+    CloudStack sk[UGSM_MAX_BATCH];
+    long long dense[UGSM_MAX_BATCH], max_cap = 0;
+    for (int b = 0; b < n; b++) {
+        if (fovea) {
+            int w2, h2;
+            UCHK(cloud_stack_table(W, H, ctx->cfg.levels, F, call->job[b].off_x, call->job[b].off_y, p.sampling, sk[b], &w2, &h2));
+            dense[b] = sk[b].lv[F - 1].first + sk[b].lv[F - 1].points;
+        } else {
+            dense[b] = ugsm_cloud_points(W, H, p.sampling);
+        }
+        s->cq_cap[b] = managed ? (spec.max_points > 0 ? std::min(spec.max_points, dense[b]) : dense[b]) : call->job[b].cap;
+        max_cap = std::max(max_cap, s->cq_cap[b]);
+    }
+    if (managed) {
+        s->cq_stride = (size_t)max_cap * step;
+        UCHK(grow(ctx, s->cq_pts, s->cq_pts_cap, std::max(s->cq_stride * n, (size_t)16)));
+        UCHK(grow(ctx, s->cq_words, s->cq_words_cap, kMaxBatch * kCqWords));
+        if (!s->cq_words_h) HIPCHK(ctx, hipHostMalloc((void **)&s->cq_words_h, kMaxBatch * kCqWords * sizeof(long long), hipHostMallocDefault));
+    }
+    const int wc = (fw + p.sampling - 1) / p.sampling, hc = (fh + p.sampling - 1) / p.sampling, nchunk = cloud_chunks(hc);
+    const size_t cols = (size_t)(fovea ? F : 1) * wc, totals = cols + (size_t)(fovea ? F : 1) * cloud_strips(wc), cnt_per = cols * nchunk + totals;
+    if (p.compact) UCHK(grow(ctx, s->cloud_cnt, s->cloud_cap, cnt_per * n));
+    for (int b = 0; b < n; b++) {
+        const CloudJob &j = call->job[b];
+        void *points = managed ? (void *)(s->cq_pts + b * s->cq_stride) : j.points;
+        long long *count = managed ? s->cq_words + b * kCqWords : j.count;
+        long long *levels = managed ? s->cq_words + b * kCqWords + 1 : j.level_counts;
+        UCHK(cloud_args_ok(res[b], res[b] + plane, res[b] + 2 * plane, dL[b], W, H, stride, ugsm_input_bytes_per_pixel(ctx->hooks.input_format), fw, fh,
+                           spec.P1, spec.P2, &p, points, s->cq_cap[b], count));
+        if ((uintptr_t)levels & 7) return UGSM_ERR_BAD_ARG;
+        CloudPair &row = s->cq_tab_h[b];
+        row = CloudPair{};
+        row.a = cloud_args(res[b], res[b] + plane, res[b] + 2 * plane, dL[b], W, H, stride, fw, fh, &p, points, s->cq_cap[b], count);
+        row.a.wc = wc;
+        row.a.hc = hc;
+        row.a.nchunk = nchunk;
+        row.a.fmt = ctx->hooks.input_format;
+        row.a.cnt = p.compact ? s->cloud_cnt + b * cnt_per : nullptr;
+        if (fovea) {
+            row.sk = sk[b];
+            row.sk.level_counts = levels;
+        }
+    }
+    HIPCHK(ctx, hipMemcpyAsync(s->cq_tab, s->cq_tab_h, n * sizeof(CloudPair), hipMemcpyHostToDevice, s->st));
+    if (p.compact) HIPCHK(ctx, hipMemsetAsync(s->cloud_cnt, 0, cnt_per * n * sizeof(unsigned), s->st));  // (the totals of every pair's region)
+
+    // 3. the match, and the clouds behind it
+    const size_t img_bytes = (size_t)stride * H;
+    auto download = [&](int b) -> int {  // a managed pair's planes, where they are wanted
+        if (!planes) return UGSM_OK;
+        for (int k = 0; k < 3; k++)
+            HIPCHK(ctx, hipMemcpyAsync(call->job[b].planes[k], res[b] + k * plane, plane * sizeof(float), hipMemcpyDeviceToHost, s->st));
+        return UGSM_OK;
+    };
+    const bool cloud_by_pair = by_pair || !batch_level(ctx, (fovea ? F : 1) * wc, hc);  // (a pair's sampled points against kBatchMaxPixels)
+    if (by_pair) {
+        for (int b = 0; b < n; b++) {
+            if (managed) UCHK(stage_in(ctx, *s, call->job[b].L, call->job[b].R, W, H, stride));
+            if (fovea) {
+                UCHK(enqueue_foveated(ctx, *s, slot, 1, dL + b, dR + b, W, H, stride, &call->job[b].off_x, &call->job[b].off_y, state + b, res + b, nullptr, nullptr));
+            } else {
+                UCHK(enqueue_pyramids(ctx, *s, slot, dL[b], dR[b], W, H, stride, 0, nullptr, true));
+                UCHK(enqueue_full_lr(ctx, *s, slot, res[b]));
+            }
+            UCHK(download(b));
+            UCHK(queue_cloud_launch(ctx, *s, slot, b, 1, fovea, &spec));
+        }
+    } else {
+        if (managed)
+            for (int b = 0; b < n; b++) {
+                HIPCHK(ctx, hipMemcpyAsync(const_cast<uint8_t *>(dL[b]), call->job[b].L, img_bytes, hipMemcpyHostToDevice, s->st));
+                HIPCHK(ctx, hipMemcpyAsync(const_cast<uint8_t *>(dR[b]), call->job[b].R, img_bytes, hipMemcpyHostToDevice, s->st));
+            }
+        if (fovea) {
+            int ox[UGSM_MAX_BATCH], oy[UGSM_MAX_BATCH];
+            for (int b = 0; b < n; b++) {
+                ox[b] = call->job[b].off_x;
+                oy[b] = call->job[b].off_y;
+            }
+            UCHK(enqueue_foveated(ctx, *s, slot, n, dL, dR, W, H, stride, ox, oy, state, res, nullptr, nullptr));
+        } else {
+            UCHK(enqueue_pyramids(ctx, *s, slot, dL, dR, n, W, H, stride, -1, nullptr, true));
+            s->lr_ran = false;
+            s->lr_fov_pairs = 0;
+            UCHK(enqueue_full(ctx, *s, slot, res));
+        }
+        for (int b = 0; b < n; b++) UCHK(download(b));
+        if (cloud_by_pair)
+            for (int b = 0; b < n; b++) UCHK(queue_cloud_launch(ctx, *s, slot, b, 1, fovea, &spec));
+        else
+            UCHK(queue_cloud_launch(ctx, *s, slot, 0, n, fovea, &spec));
+    }
+    if (managed) {
+        HIPCHK(ctx, hipMemcpyAsync(s->cq_words_h, s->cq_words, n * kCqWords * sizeof(long long), hipMemcpyDeviceToHost, s->st));
+        s->cq_n = n;
+        s->cq_step = step;
+        s->cq_levels = fovea ? F : 0;
+    }
+    return mark_done(ctx, *s);
+}
+
+static int queue_cloud_finish(ugsm_ctx *ctx, int slot, int n, ugsm_cloud_result *res, void *(*staging)(void *, int, long long), void *user)
+{
+    Slot *s;
+    UCHK(get_slot(ctx, slot, &s));
+    if (!res || !staging || n < 1 || n != s->cq_n) return ctx_fail(ctx, UGSM_ERR_STATE, "the slot holds no managed cloud call of that many pairs");
+    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
+    for (int b = 0; b < n; b++) {
+        const long long *w = s->cq_words_h + b * kCqWords;
+        ugsm_cloud_result &r = res[b];
+        r = ugsm_cloud_result{};
+        r.count = w[0];
+        r.stored = std::min(w[0], s->cq_cap[b]);
+        r.point_step = s->cq_step;
+        r.levels = s->cq_levels;
+        for (int l = 0; l < s->cq_levels; l++) r.level_counts[l] = w[1 + l];
+    }
+    s->cq_n = 0;
+    for (int b = 0; b < n; b++) {
+        if (res[b].stored < 1) continue;
+        const long long bytes = res[b].stored * s->cq_step;
+        res[b].points = staging(user, b, bytes);
+        if (!res[b].points) return ctx_fail(ctx, UGSM_ERR_NOMEM, "no page-locked memory for a pair's cloud");
+        HIPCHK(ctx, hipMemcpyAsync(res[b].points, s->cq_pts + b * s->cq_stride, (size_t)bytes, hipMemcpyDeviceToHost, s->st));
+    }
+    return mark_done(ctx, *s);
 }
 
 // hierarchicalDisparity, MatchGPULib.cpp:2589-2701
