@@ -314,6 +314,33 @@ int ugsm_submit_full_batch_host(ugsm_ctx *ctx, int slot, int n, const uint8_t *c
 int ugsm_submit_foveated_batch_host(ugsm_ctx *ctx, int slot, int n, const uint8_t *const *rgbL, const uint8_t *const *rgbR,
                                     int W, int H, int stride, const int *off_x, const int *off_y, float *const *stackH,
                                     float *const *stackV, float *const *stackC);
+/* ---- several fovea windows on ONE pair ------------------------------------------------------------------------------------------------
+ *
+ * A host that looks at n places of one frame (1 <= n <= UGSM_MAX_BATCH) needs the pyramids and the coarse phase -- levels top .. F-1, which
+ * do not depend on the window -- once, and the fine levels F-2 .. 0 of its n windows: those run in lockstep, as the pairs of
+ * ugsm_submit_foveated_batch do, every kernel of a level one launch for all n windows.  Level 0 is stored inside the windows alone.
+ *   off_x / off_y  n window offsets (NULL = all centred).  Offsets that clamp at the frame, duplicates and overlapping windows are allowed.
+ *   d_stack        HOST array of n DEVICE stacks, each 3 x (F*fovH) x fovW as ugsm_submit_foveated writes it.
+ * The matching contract: stack k is, bit for bit, what ugsm_submit_foveated(ctx, slot, d_rgbL, d_rgbR, .., off_x[k], off_y[k], d_stack[k],
+ * NULL, NULL) writes -- for any n, in any input format (ugsm_set_input_format, captured at the call); row block F-1 of every stack is the same
+ * whole-frame level.  With n == 1 the call IS ugsm_submit_foveated without pyramid stacks.
+ * Status: null arrays or entries, n outside 1 .. UGSM_MAX_BATCH, fovea_levels < 2: UGSM_ERR_BAD_ARG; the size errors of ugsm_submit_foveated
+ * as there; pairs outstanding in the queue: UGSM_ERR_STATE; UGSM_LR_FOVEATED set on the context: UGSM_ERR_STATE (the checked multi-window
+ * call is not built).  All of these before anything is enqueued.
+ * Memory: one pair's slot, plus level buffers that hold n fields of 3 fovW fovH floats -- more than a one-pair slot has once n > 2^(F-1); they
+ * grow on demand (counted by ugsm_context_device_bytes), and a call whose buffers cannot grow answers UGSM_ERR_NOMEM.
+ * After the call the slot holds no whole pyramids: ugsm_submit_fovea_fine on it answers UGSM_ERR_STATE, as after any one-shot foveated call.
+ * Contexts with early_exit_threshold set, and kernel_path 1, still build the pyramids and run the coarse phase once; their n fine phases run
+ * one after the other.  Same results.
+ * NOT built: pyramid stacks from this call; a queue form (ugsm_enqueue_*); the page-locked _host kind; the LR check; a merged cloud of
+ * several stacks (call ugsm_point_cloud_fovea_all per stack).
+ * Asynchronous on `slot`. */
+int ugsm_submit_foveated_multi(ugsm_ctx *ctx, int slot, const uint8_t *d_rgbL, const uint8_t *d_rgbR, int W, int H, int stride,
+                               int n, const int *off_x, const int *off_y, float *const *d_stack);
+/* Blocking, any host memory in, host stacks out (HOST arrays of n pointers each), as ugsm_match_foveated; no pyramid stacks. */
+int ugsm_match_foveated_multi(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride,
+                              int n, const int *off_x, const int *off_y, float *const *stackH, float *const *stackV,
+                              float *const *stackC);
 int ugsm_wait(ugsm_ctx *ctx, int slot);
 /* ugsm_wait on every slot, in order; every slot is waited for whatever the ones before it answered, the first failure is the one returned. */
 int ugsm_wait_all(ugsm_ctx *ctx);
@@ -674,6 +701,15 @@ int ugsm_done_cloud(ugsm_ctx *ctx, ugsm_cloud_result *out);
  * off_x/off_y as passed to ugsm_match_foveated.  Asynchronous on `slot`; ugsm_wait(ctx, slot) to finish. */
 int ugsm_reconstruct_full(ugsm_ctx *ctx, int slot, const float *d_stackH, const float *d_stackV,
                           const float *d_stackC, int W, int H, int off_x, int off_y, float *d_out3);
+
+/* hierarchicalDisparity over the n stacks of ugsm_submit_foveated_multi (HOST array of n DEVICE stacks; off_x / off_y as passed there, NULL =
+ * centred): one full-resolution (dx, dy, conf) field.  Start from row block F-1 of stack 0; for level = F-1 .. 1 do the step of
+ * ugsm_reconstruct_full from level to level-1 with this window test: a pixel of level-1 inside window k takes stack k's value -- where
+ * several windows hold it, the HIGHEST k -- and a pixel inside no window takes the upsample, all three channels scaled.  A pasted pixel never
+ * computes the upsample.  n == 1: bit for bit ugsm_reconstruct_full.  fovea_levels < 2, n outside 1 .. UGSM_MAX_BATCH, null entries:
+ * UGSM_ERR_BAD_ARG.  Asynchronous on `slot`. */
+int ugsm_reconstruct_full_multi(ugsm_ctx *ctx, int slot, int n, const float *const *d_stack, int W, int H,
+                                const int *off_x, const int *off_y, float *d_out3);
 
 /* ---- stage-level entry points (tests only; device pointers; synchronous) -------- */
 /* (the probes of the kernels' exact arithmetic shortcuts -- ugsm_stage_poly_probe, ugsm_stage_div3_probe, ugsm_stage_div_probe -- are

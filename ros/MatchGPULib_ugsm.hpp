@@ -130,6 +130,32 @@ public:
     template <class ImgPtr>
     float ***matchStack(ImgPtr L, ImgPtr R) { return stack(L, R, nullptr, nullptr); }
 
+    // Several windows of one pair (not in the reference; include/ugsm.h, "several fovea windows on ONE pair"): matchStack for the n offsets
+    // (1 <= n <= UGSM_MAX_BATCH) in one call -- pyramids and the coarse levels once, the windows' fine levels in lockstep.  out[k]: the
+    // disparity[level][3][fovH*fovW] matchStack returns for (off_x[k], off_y[k]), malloc'd the same way.  False on failure (nothing allocated).
+    template <class ImgPtr>
+    bool matchStackMulti(ImgPtr L, ImgPtr R, int n, const int *off_x, const int *off_y, float ****out)
+    {
+        const int W = L->image.cols, H = L->image.rows, F = foveatelevel;
+        if (!out || n < 1 || n > UGSM_MAX_BATCH || R->image.cols != W || R->image.rows != H) return false;
+        if (ugsm_fovea_dims(W, H, 14, F, &fovW, &fovH) != UGSM_OK) return false;
+        const size_t fn = (size_t)fovW * fovH, sn = fn * F;
+        float *sh = (float *)std::malloc((size_t)n * 3 * sn * sizeof(float));
+        float *ph[UGSM_MAX_BATCH], *pv[UGSM_MAX_BATCH], *pc[UGSM_MAX_BATCH];
+        for (int k = 0; k < n; k++) { ph[k] = sh + (size_t)k * 3 * sn; pv[k] = ph[k] + sn; pc[k] = pv[k] + sn; }
+        const int st = ugsm_match_foveated_multi(ctx_, L->image.data, R->image.data, W, H, (int)L->image.step, n, off_x, off_y, ph, pv, pc);
+        if (st != UGSM_OK) { report(st); std::free(sh); return false; }
+        for (int k = 0; k < n; k++) {
+            out[k] = (float ***)std::malloc(F * sizeof(float **));
+            for (int l = 0; l < F; l++) {
+                out[k][l] = alloc_planes(3, fn);
+                for (int c = 0; c < 3; c++) std::memcpy(out[k][l][c], ph[k] + c * sn + l * fn, fn * sizeof(float));
+            }
+        }
+        std::free(sh);
+        return true;
+    }
+
     // MatchGPULib.cpp:534-700.  leftFov/rightFov: caller-allocated [14][3][fovH*fovW] as in
     // UG_GPU_matcher.cpp:169-179; levels < foveatelevel are filled.
     template <class ImgPtr>

@@ -67,6 +67,25 @@ int main(int argc, char **argv)
             free(blocking);
             if (bad || got != 5) return 8;
         }
+        // matchStackMulti: three windows of the pair in one call; the centred one is matchStack's, and level F-1 is the same in all
+        {
+            const int ox[3] = {40, 0, -5000}, oy[3] = {-25, 0, 5000};
+            float ***multi[3];
+            if (!m.matchStackMulti(L, R, 3, ox, oy, multi)) return 9;
+            const int F = m.getFoveateLevel();
+            const size_t fb = sizeof(float) * m.getFoveaWidth() * m.getFoveaHeight();
+            size_t bad = 0;
+            for (int k = 0; k < F; k++)
+                for (int c = 0; c < 3; c++) bad += std::memcmp(multi[1][k][c], st[k][c], fb) != 0;
+            for (int w = 0; w < 3; w++)
+                for (int c = 0; c < 3; c++) bad += std::memcmp(multi[w][F - 1][c], st[F - 1][c], fb) != 0;
+            std::printf("matchStackMulti (3 windows) vs matchStack: %s\n", bad ? "DIFFER" : "identical");
+            for (int w = 0; w < 3; w++) {
+                for (int k = 0; k < F; k++) { for (int i = 0; i < 3; i++) free(multi[w][k][i]); free(multi[w][k]); }
+                free(multi[w]);
+            }
+            if (bad) return 10;
+        }
         for (int k = 0; k < m.getFoveateLevel(); k++) { for (int i = 0; i < 3; i++) free(st[k][i]); free(st[k]); }
         free(st);
     } catch (const std::exception &e) {

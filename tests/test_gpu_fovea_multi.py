@@ -1,0 +1,427 @@
+"""Several fovea windows on ONE pair: ugsm_submit_foveated_multi, ugsm_match_foveated_multi, ugsm_reconstruct_full_multi.
+
+Pyramids and the coarse phase run once, the windows' fine levels in lockstep; stack k must be, bit for bit, what ugsm_submit_foveated writes
+for offset k -- so what the CPU oracle's match_foveated returns for it -- for any n, in any input format, on every kernel form, with windows
+that clamp at the frame, repeat and overlap.  The reconstruction over the stacks is compared with tests/reconstruct_multi_np.py, which
+tests/test_fovea_multi_host.py pins to the oracle."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import encode_np as en
+import reconstruct_multi_np as rm
+from conftest import assert_bit_equal
+
+pytestmark = pytest.mark.gpu
+
+# (0,0), an off-centre one, two that clamp at the frame, a duplicate, two that overlap the first ones, then a scatter
+OFFS = [(0, 0), (-170, 90), (5000, -5000), (-5000, 5000), (0, 0), (-150, 70), (20, 10)] + [(37 * j - 160, 120 - 29 * j) for j in range(9)]
+
+
+@pytest.fixture(scope="module")
+def lib():
+    import __graft_entry__ as ge
+    ge.build_library()
+    from ug_stereomatcher_amd import _lib
+    return _lib
+
+
+_PAIRS, _ANSWERS = {}, {}
+
+
+def _pair(W, H, patch=True):
+    """One pair per size, the left image with a zero patch (0/0 -> NaN correlations), as some pairs of test_gpu_batch.py::_pairs."""
+    if (W, H) not in _PAIRS:
+        from ug_stereomatcher_amd import synth
+        L, R, _, _ = synth.make_pair(W, H, synth.BASE_SEED + 4100 + W)
+        if patch:
+            L = L.copy()
+            L[H // 5:H // 5 + 24, W // 4:W // 4 + 40] = 0
+        _PAIRS[(W, H)] = (L, R)
+    return _PAIRS[(W, H)]
+
+
+def _answer(orc, L, R, lv, F, off, key=None):
+    """The oracle's stack for one window, computed once per (pair, configuration, offset) and shared."""
+    k = (key or id(L), L.shape, lv, F, tuple(off))
+    if k not in _ANSWERS:
+        _ANSWERS[k] = orc.match_foveated(L, R, lv, F, off[0], off[1])[0]
+        _ANSWERS[k].setflags(write=False)
+    return _ANSWERS[k]
+
+
+def _multi(c, lib, dL, dR, W, H, stride, lv, F, offs, slot=0, wait=True):
+    fw, fh = lib.fovea_dims(W, H, lv, F)
+    dS = [c.alloc(3 * F * fh * fw * 4) for _ in offs]
+    c.submit_foveated_multi(slot, dL, dR, W, H, stride, offs, dS)
+
+    def fetch():
+        try:
+            return [c.to_host(p, (3, F, fh, fw)) for p in dS]
+        finally:
+            for p in dS:
+                c.free(p)
+    if not wait:
+        return fetch
+    c.check(c.lib.ugsm_wait(c.handle, slot))
+    return fetch()
+
+
+def _run(c, lib, L, R, lv, F, offs, slot=0):
+    H, W = L.shape[:2]
+    dL, dR = c.to_device(L), c.to_device(R)
+    try:
+        return _multi(c, lib, dL, dR, W, H, L.strides[0], lv, F, offs, slot)
+    finally:
+        c.free(dL)
+        c.free(dR)
+
+
+def _single(c, lib, dL, dR, W, H, stride, lv, F, off, slot=0):
+    fw, fh = lib.fovea_dims(W, H, lv, F)
+    dS = c.alloc(3 * F * fh * fw * 4)
+    try:
+        c.check(c.lib.ugsm_submit_foveated(c.handle, slot, dL, dR, W, H, stride, off[0], off[1], dS, None, None))
+        c.check(c.lib.ugsm_wait(c.handle, slot))
+        return c.to_host(dS, (3, F, fh, fw))
+    finally:
+        c.free(dS)
+
+
+# ---- 1. against the oracle -------------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("W,H,lv,F,n", [(640, 480, 10, 4, 1), (640, 480, 10, 4, 2), (640, 480, 10, 4, 5), (640, 480, 10, 4, 16),
+                                        (333, 251, 8, 2, 5),     # the level buffers must grow past a one-pair slot (n > 2^(F-1))
+                                        (200, 150, 5, 5, 3),     # the coarse phase is the top level alone
+                                        (584, 190, 2, 2, 2)])    # no k_pyr_base: level 0 is stored whole
+def test_every_stack_vs_oracle(lib, orc, W, H, lv, F, n):
+    L, R = _pair(W, H)
+    offs = OFFS[:n]
+    with lib.Context(levels=lv, fovea_levels=F) as c:
+        got = _run(c, lib, L, R, lv, F, offs)
+    for k, off in enumerate(offs):
+        assert_bit_equal(got[k], _answer(orc, L, R, lv, F, off), f"{W}x{H} levels {lv} F {F}, {n} windows, window {k} at {off}")
+    for k in range(1, n):
+        assert_bit_equal(got[k][:, F - 1], got[0][:, F - 1], "row block F-1 is the same whole-frame level in every stack")
+
+
+# ---- 2. every kernel form on the fine levels -------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("force", ["march", "march4", "shared", "no_fused_seed", "alone"])
+def test_every_kernel_form_on_the_fine_levels(lib, orc, monkeypatch, force):
+    env = {"march": {"UGSM_MARCH_MIN_PIXELS": "1"}, "march4": {"UGSM_MARCH4": "1,2000000000"}, "shared": {"UGSM_ALONE": "0"},
+           "no_fused_seed": {"UGSM_FUSE_SEED": "0"}, "alone": {"UGSM_ALONE": "1"}}[force]
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    W, H, lv, F = 1000, 700, 11, 4
+    offs = [(0, 0), (120, -80), (-300, 200)]
+    L, R = _pair(W, H)
+    with lib.Context(levels=lv, fovea_levels=F) as c:
+        got = _run(c, lib, L, R, lv, F, offs)
+    for k, off in enumerate(offs):
+        assert_bit_equal(got[k], _answer(orc, L, R, lv, F, off), f"{force}, window {k} at {off}")
+
+
+# ---- 3. input formats --------------------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("fmt", [en.BGR8, en.RGBA8, en.BGRA8, en.MONO8], ids=["bgr8", "rgba8", "bgra8", "mono8"])
+def test_input_formats(lib, orc, fmt):
+    """The window kernel's instance per layout: aligned buffers (the four-byte formats' word loads) and, for those formats, a device pointer
+    one byte past an allocation with an odd stride (their byte loads).  Expected: the oracle on the image converted to rgb8."""
+    W, H, lv, F = 333, 251, 8, 3
+    offs = [(0, 0), (-90, 60), (5000, 5000)]
+    L, R = _pair(W, H)
+    a, b = en.encode(L, fmt), en.encode(R, fmt)
+    cL, cR = en.to_rgb8(a, fmt), en.to_rgb8(b, fmt)
+    exp = [_answer(orc, cL, cR, lv, F, off, key=("fmt", fmt)) for off in offs]
+    with lib.Context(levels=lv, fovea_levels=F) as c:
+        c.set_input_format(fmt)
+        for pad, shift in [(0, 0)] + ([(5, 1)] if en.BPP[fmt] == 4 else []):
+            rows = [en.padded(x, pad) for x in (a, b)]
+            stride = rows[0].shape[1]
+            assert pad == 0 or stride % 2 == 1
+            dev = []
+            for r in rows:
+                raw = np.zeros(r.nbytes + 64, np.uint8)
+                raw[shift:shift + r.nbytes] = r.reshape(-1)
+                dev.append(c.to_device(raw))
+            try:
+                got = _multi(c, lib, dev[0] + shift, dev[1] + shift, W, H, stride, lv, F, offs)
+            finally:
+                for p in dev:
+                    c.free(p)
+            for k, off in enumerate(offs):
+                assert_bit_equal(got[k], exp[k], f"{en.NAMES[fmt]}, pad {pad}, shift {shift}, window {k} at {off}")
+
+
+# ---- 4. the slot afterwards ----------------------------------------------------------------------------------------------------------------
+
+def test_the_slot_afterwards(lib, orc):
+    W, H, lv, F = 333, 251, 8, 2
+    L, R = _pair(W, H)
+    fw, fh = lib.fovea_dims(W, H, lv, F)
+    with lib.Context(levels=lv, fovea_levels=F) as c:
+        dL, dR = c.to_device(L), c.to_device(R)
+        st = _single(c, lib, dL, dR, W, H, 3 * W, lv, F, (0, 0))        # the slot as a one-pair call leaves it
+        assert_bit_equal(st, _answer(orc, L, R, lv, F, (0, 0)), "single call first")
+        before = c.device_bytes()
+        got = _multi(c, lib, dL, dR, W, H, 3 * W, lv, F, OFFS[:5])      # n = 5 > 2^(F-1): the level buffers grow
+        for k, off in enumerate(OFFS[:5]):
+            assert_bit_equal(got[k], _answer(orc, L, R, lv, F, off), f"n = 5, window {k}")
+        assert c.device_bytes() >= before
+        assert c.device_bytes() >= before + 3 * (5 * 3 * fw * fh - 3 * W * H) * 4, "A, d0 and d1 each hold five fields now"
+        # ugsm_submit_fovea_fine: the slot holds no whole pyramids
+        dS = c.alloc(3 * F * fh * fw * 4)
+        dT = c.alloc(3 * fh * fw * 4)
+        assert c.lib.ugsm_submit_fovea_fine(c.handle, 0, dT, 0, 0, dS) == lib.UGSM_ERR_STATE
+        # a single foveated call at another offset, a full-mode call, a second multi call with fewer windows
+        assert_bit_equal(_single(c, lib, dL, dR, W, H, 3 * W, lv, F, (40, -33)), _answer(orc, L, R, lv, F, (40, -33)), "single call afterwards")
+        dO = c.alloc(3 * W * H * 4)
+        c.check(c.lib.ugsm_submit_full(c.handle, 0, dL, dR, W, H, 3 * W, dO))
+        c.check(c.lib.ugsm_wait(c.handle, 0))
+        if ("full", W, H, lv) not in _ANSWERS:
+            _ANSWERS[("full", W, H, lv)] = orc.match_full(L, R, lv)
+        assert_bit_equal(c.to_host(dO, (3, H, W)), _ANSWERS[("full", W, H, lv)], "full-mode call afterwards")
+        got = _multi(c, lib, dL, dR, W, H, 3 * W, lv, F, OFFS[1:3])
+        for k, off in enumerate(OFFS[1:3]):
+            assert_bit_equal(got[k], _answer(orc, L, R, lv, F, off), f"second multi call, window {k}")
+        for p in (dL, dR, dS, dT, dO):
+            c.free(p)
+
+
+def test_level_buffers_that_cannot_grow(lib, orc, monkeypatch):
+    """F = 2: sixteen fields of 452 x 339 need 3 x 29 MB of level buffers where one 640 x 480 pair's slot holds 3 x 3.7 MB.  Under the
+    development limit UGSM_MEM_LIMIT_MB (the branch a failed hipMalloc takes) the call answers UGSM_ERR_NOMEM before anything is enqueued,
+    keeps no half-grown buffer, and the slot serves the next call."""
+    W, H, lv, F = 640, 480, 10, 2
+    L, R = _pair(W, H)
+    fw, fh = lib.fovea_dims(W, H, lv, F)
+    monkeypatch.setenv("UGSM_MEM_LIMIT_MB", "60")
+    with lib.Context(levels=lv, fovea_levels=F) as c:
+        dL, dR = c.to_device(L), c.to_device(R)
+        got = _multi(c, lib, dL, dR, W, H, 3 * W, lv, F, OFFS[:2])         # n = 2 = 2^(F-1): one pair's buffers hold it
+        for k, off in enumerate(OFFS[:2]):
+            assert_bit_equal(got[k], _answer(orc, L, R, lv, F, off), f"before, window {k}")
+        held = c.device_bytes()
+        assert held < 60e6, held
+        dS = c.alloc(3 * F * fh * fw * 4)
+        many = (C.c_void_p * 16)(*([dS] * 16))
+        st = c.lib.ugsm_submit_foveated_multi(c.handle, 0, dL, dR, W, H, 3 * W, 16, None, None, many)
+        assert st == lib.UGSM_ERR_NOMEM, st
+        assert b"hipMalloc" in c.lib.ugsm_last_error(c.handle)
+        assert c.device_bytes() < held, "the level buffers were given back whole"
+        c.check(c.lib.ugsm_wait(c.handle, 0))
+        got = _multi(c, lib, dL, dR, W, H, 3 * W, lv, F, OFFS[:2])
+        for k, off in enumerate(OFFS[:2]):
+            assert_bit_equal(got[k], _answer(orc, L, R, lv, F, off), f"after the refused call, window {k}")
+        for p in (dL, dR, dS):
+            c.free(p)
+
+
+# ---- 5. level 0 only where a window lies -----------------------------------------------------------------------------------------------------
+
+def test_level0_is_stored_in_the_windows_alone(lib):
+    """Read from the launch statistics (profile_events = 2 brackets every launch of slot 0 by kernel class and pyramid level; pixel_launches
+    is what the runtime says the launch covers).  Level 0 can be stored by three launches: k_pyr_base (recorded with W H pixels per image
+    whatever its window -- its window argument is what the runtime's build_pyramids passes, kPyrNoLevel0 here, the form
+    tests/test_gpu_level0_direct.py covers), k_rgb_planes whole (class "misc" at level 0) and the window kernel (class k_level0_windows).
+    So: one k_level0_windows launch of 2 n fovW fovH pixels, no "misc" launch at level 0, and k_pyr_base's two launches (one per image) --
+    no further class at level 0 but the matching kernels."""
+    W, H, lv, F, n = 333, 251, 8, 3, 3
+    L, R = _pair(W, H)
+    fw, fh = lib.fovea_dims(W, H, lv, F)
+    with lib.Context(levels=lv, fovea_levels=F, profile_events=2) as c:
+        for calls in (1, 2):
+            c.reset_kernel_stats()
+            for _ in range(calls):
+                _run(c, lib, L, R, lv, F, OFFS[:n])
+            st = c.kernel_stats()
+            win = [s for s in st if s["name"] == "k_level0_windows"]
+            assert len(win) == 1 and win[0]["level"] == 0 and win[0]["launches"] == calls
+            assert win[0]["pixel_launches"] == calls * 2 * n * fw * fh
+            assert not [s for s in st if s["name"] == "misc" and s["level"] == 0], "k_rgb_planes stored level 0 whole"
+            base = [s for s in st if s["name"] == "k_pyr_base"]
+            assert len(base) == 1 and base[0]["launches"] == 2 * calls
+            stores0 = {s["name"] for s in st if s["level"] == 0} - {"k_level0_windows", "k_pyr_base"}
+            assert all(name.startswith(("k_cost", "k_smooth", "k_sqblur", "k_seed")) for name in stores0), stores0
+    with lib.Context(levels=2, fovea_levels=2, profile_events=2) as c:      # no k_pyr_base: level 0 whole, no window launch
+        _run(c, lib, *_pair(584, 190), 2, 2, OFFS[:2])
+        assert not [s for s in c.kernel_stats() if s["name"] == "k_level0_windows"]
+
+
+# ---- 6. two slots in flight ------------------------------------------------------------------------------------------------------------------
+
+def test_two_slots_in_flight(lib, orc):
+    """Slot 1's call sees slot 0 busy: the not-alone kernel choices, no side stream."""
+    W, H, lv, F = 640, 480, 10, 4
+    L, R = _pair(W, H)
+    sets = [OFFS[:3], OFFS[3:7]]
+    with lib.Context(levels=lv, fovea_levels=F, slots=2) as c:
+        dL, dR = c.to_device(L), c.to_device(R)
+        fetch = [_multi(c, lib, dL, dR, W, H, 3 * W, lv, F, sets[s], slot=s, wait=False) for s in range(2)]
+        c.check(c.lib.ugsm_wait_all(c.handle))
+        for s in range(2):
+            for k, st in enumerate(fetch[s]()):
+                assert_bit_equal(st, _answer(orc, L, R, lv, F, sets[s][k]), f"slot {s}, window {k}")
+        c.free(dL)
+        c.free(dR)
+
+
+# ---- 7. the blocking form --------------------------------------------------------------------------------------------------------------------
+
+def test_the_blocking_form_from_pageable_memory(lib, orc):
+    W, H, lv, F = 640, 480, 10, 4
+    L, R = _pair(W, H)
+    offs = OFFS[:5]
+    with lib.Context(levels=lv, fovea_levels=F) as c:
+        host = c.match_foveated_multi(L, R, offs)
+        dev = _run(c, lib, L, R, lv, F, offs)
+    for k, off in enumerate(offs):
+        assert_bit_equal(host[k], dev[k], f"blocking form vs device form, window {k}")
+        assert_bit_equal(host[k], _answer(orc, L, R, lv, F, off), f"blocking form vs oracle, window {k}")
+
+
+# ---- 8. contexts that run pair by pair -----------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("kind", ["early_exit", "kernel_path_1"])
+def test_contexts_that_run_window_by_window(lib, kind):
+    W, H, lv, F = 640, 480, 10, 4
+    L, R = _pair(W, H)
+    offs = OFFS[:3]
+    cfg = dict(early_exit_threshold=0.02) if kind == "early_exit" else dict(kernel_path=1, dev=True)
+    with lib.Context(levels=lv, fovea_levels=F, **cfg) as c:
+        dL, dR = c.to_device(L), c.to_device(R)
+        got = _multi(c, lib, dL, dR, W, H, 3 * W, lv, F, offs)
+        for k, off in enumerate(offs):
+            assert_bit_equal(got[k], _single(c, lib, dL, dR, W, H, 3 * W, lv, F, off), f"{kind}: window {k} vs the single call")
+        c.free(dL)
+        c.free(dR)
+
+
+# ---- 9. reconstruction -------------------------------------------------------------------------------------------------------------------------
+
+def _reconstruct(c, stacks, W, H, offs):
+    dS = [c.to_device(s) for s in stacks]
+    dO = c.alloc(3 * W * H * 4)
+    try:
+        c.reconstruct_full_multi(dS, W, H, dO, offs)
+        return c.to_host(dO, (3, H, W))
+    finally:
+        for p in dS + [dO]:
+            c.free(p)
+
+
+@pytest.mark.parametrize("W,H,lv,F", [(640, 480, 10, 4), (333, 251, 8, 3)])
+def test_reconstruction_vs_the_numpy_restatement(lib, orc, W, H, lv, F):
+    """Four windows of one size: 2 repeats 0 (so it lies wholly inside it, and must win all of it), 1 overlaps both partly, 3 clamps at the
+    frame.  Synthetic stacks with NaN and inf; row block F-1 differs between the stacks on purpose: stack 0's is the one that counts."""
+    offs = [(0, 0), (60, -40), (0, 0), (-5000, 5000)]
+    fw, fh = lib.fovea_dims(W, H, lv, F)
+    rng = np.random.Generator(np.random.PCG64(31 * W + F))
+    stacks = [rm.random_stack(rng, F, fh, fw) for _ in offs]
+    with lib.Context(levels=lv, fovea_levels=F) as c:
+        got = _reconstruct(c, stacks, W, H, offs)
+        assert_bit_equal(got, rm.reconstruct_multi(orc, stacks, W, H, lv, offs), f"{W}x{H}: four windows")
+        # n = 1: ugsm_reconstruct_full on the same stack
+        one = _reconstruct(c, stacks[1:2], W, H, offs[1:2])
+        dS, dO = c.to_device(stacks[1]), c.alloc(3 * W * H * 4)
+        pl = F * fh * fw * 4
+        c.reconstruct_full(dS, dS + pl, dS + 2 * pl, W, H, dO, offs[1][0], offs[1][1])
+        assert_bit_equal(one, c.to_host(dO, (3, H, W)), "n = 1 vs ugsm_reconstruct_full")
+        assert_bit_equal(one, orc.reconstruct_full(stacks[1], W, H, lv, offs[1][0], offs[1][1]), "n = 1 vs the oracle")
+        c.free(dS)
+        c.free(dO)
+
+
+def test_reconstruction_end_to_end(lib, orc):
+    W, H, lv, F = 640, 480, 10, 4
+    L, R = _pair(W, H)
+    offs = OFFS[:2]
+    with lib.Context(levels=lv, fovea_levels=F) as c:
+        stacks = _run(c, lib, L, R, lv, F, offs)
+        out = _reconstruct(c, stacks, W, H, offs)
+    fw, fh, ox, oy, _, _ = orc.fovea_geometry(W, H, lv, F, offs[1][0], offs[1][1])
+    assert_bit_equal(out[:, oy[0]:oy[0] + fh, ox[0]:ox[0] + fw], stacks[1][:, 0], "inside window 1's level-0 rectangle: stack 1's level 0")
+    assert_bit_equal(out, rm.reconstruct_multi(orc, stacks, W, H, lv, offs), "the whole field")
+
+
+# ---- 10. refusals -------------------------------------------------------------------------------------------------------------------------------
+
+def test_refusals_leave_a_working_context(lib, orc):
+    W, H, lv, F = 333, 251, 8, 3
+    L, R = _pair(W, H)
+    fw, fh = lib.fovea_dims(W, H, lv, F)
+    offs = OFFS[:2]
+
+    def works(c, dL, dR):
+        got = _multi(c, lib, dL, dR, W, H, 3 * W, lv, F, offs)
+        for k, off in enumerate(offs):
+            assert_bit_equal(got[k], _answer(orc, L, R, lv, F, off), f"after a refusal, window {k}")
+
+    with lib.Context(levels=lv, fovea_levels=F, slots=2) as c:
+        dL, dR = c.to_device(L), c.to_device(R)
+        dS = c.alloc(3 * F * fh * fw * 4)
+        many = (C.c_void_p * 17)(*([dS] * 17))
+        call = lambda n, ptrs: c.lib.ugsm_submit_foveated_multi(c.handle, 0, dL, dR, W, H, 3 * W, n, None, None, ptrs)
+        assert call(0, many) == lib.UGSM_ERR_BAD_ARG
+        works(c, dL, dR)
+        assert call(17, many) == lib.UGSM_ERR_BAD_ARG
+        works(c, dL, dR)
+        assert call(2, (C.c_void_p * 2)(dS, None)) == lib.UGSM_ERR_BAD_ARG
+        works(c, dL, dR)
+        assert call(2, None) == lib.UGSM_ERR_BAD_ARG
+        assert c.lib.ugsm_submit_foveated_multi(c.handle, 0, dL, dR, W, H, W, 1, None, None, many) == lib.UGSM_ERR_SIZE_MISMATCH
+        works(c, dL, dR)
+        # the foveated LR check is a setting the multi call does not serve
+        c.set_lr_check(1.0, lib.UGSM_LR_FOVEATED)
+        assert call(2, many) == lib.UGSM_ERR_STATE
+        hp = (C.c_void_p * 2)(dS, dS)
+        assert c.lib.ugsm_match_foveated_multi(c.handle, L.ctypes.data, R.ctypes.data, W, H, 3 * W, 2, None, None, hp, hp, hp) == lib.UGSM_ERR_STATE
+        c.set_lr_check(0.0, 0)
+        works(c, dL, dR)
+        # a pair outstanding in the queue: the slots are the queue's
+        c.enqueue_foveated(dL, dR, W, H, 3 * W, (0, 0), dS, 7)
+        assert call(2, many) == lib.UGSM_ERR_STATE
+        assert c.lib.ugsm_reconstruct_full_multi(c.handle, 0, 1, many, W, H, None, None, dS) == lib.UGSM_ERR_STATE
+        done = c.drain()
+        assert [int(d.tag) for d in done] == [7] and done[0].status == 0
+        assert_bit_equal(c.to_host(dS, (3, F, fh, fw)), _answer(orc, L, R, lv, F, (0, 0)), "the queued pair")
+        works(c, dL, dR)
+        # the reconstruction's own refusals
+        assert c.lib.ugsm_reconstruct_full_multi(c.handle, 0, 0, many, W, H, None, None, dS) == lib.UGSM_ERR_BAD_ARG
+        assert c.lib.ugsm_reconstruct_full_multi(c.handle, 0, 17, many, W, H, None, None, dS) == lib.UGSM_ERR_BAD_ARG
+        assert c.lib.ugsm_reconstruct_full_multi(c.handle, 0, 2, (C.c_void_p * 2)(dS, None), W, H, None, None, dS) == lib.UGSM_ERR_BAD_ARG
+        for p in (dL, dR, dS):
+            c.free(p)
+    with lib.Context(levels=lv, fovea_levels=1) as c:     # F = 1: there is no fovea
+        dL, dR = c.to_device(L), c.to_device(R)
+        dO = c.alloc(3 * W * H * 4)
+        one = (C.c_void_p * 1)(dO)
+        assert c.lib.ugsm_submit_foveated_multi(c.handle, 0, dL, dR, W, H, 3 * W, 1, None, None, one) == lib.UGSM_ERR_BAD_ARG
+        assert c.lib.ugsm_reconstruct_full_multi(c.handle, 0, 1, one, W, H, None, None, dO) == lib.UGSM_ERR_BAD_ARG
+        c.check(c.lib.ugsm_submit_full(c.handle, 0, dL, dR, W, H, 3 * W, dO))
+        c.check(c.lib.ugsm_wait(c.handle, 0))
+        if ("full", W, H, lv) not in _ANSWERS:
+            _ANSWERS[("full", W, H, lv)] = orc.match_full(L, R, lv)
+        assert_bit_equal(c.to_host(dO, (3, H, W)), _ANSWERS[("full", W, H, lv)], "a full-mode call after the refusals")
+        for p in (dL, dR, dO):
+            c.free(p)
+
+
+# ---- 11. the shim ---------------------------------------------------------------------------------------------------------------------------------
+
+def test_match_gpu_lib_match_stack_multi(lib, orc):
+    """MatchGPULib.matchStackMulti: one [level][dx|dy|conf] stack per window, each what matchStack returns for its offset."""
+    from ug_stereomatcher_amd.match_gpu_lib import MatchGPULib
+    W, H, lv, F = 640, 480, 10, 4
+    L, R = _pair(W, H)
+    m = MatchGPULib(3, ["node", "x", str(F)], levels=lv)
+    try:
+        got = m.matchStackMulti(L, R, OFFS[:3])
+        assert (m.getFoveaWidth(), m.getFoveaHeight()) == lib.fovea_dims(W, H, lv, F)
+        for k, off in enumerate(OFFS[:3]):
+            assert_bit_equal(got[k], _answer(orc, L, R, lv, F, off).transpose(1, 0, 2, 3), f"matchStackMulti, window {k}")
+        assert_bit_equal(got[1], m.matchStack(L, R, OFFS[1][0], OFFS[1][1]), "matchStackMulti vs matchStack")
+    finally:
+        m.close()

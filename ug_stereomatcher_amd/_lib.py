@@ -39,6 +39,7 @@ EXPORTS = [
     "ugsm_last_error", "ugsm_level_dims", "ugsm_level_iterations", "ugsm_level_smooth_passes",
     "ugsm_threshold_schedule", "ugsm_fovea_dims", "ugsm_pixel_iterations", "ugsm_plan_level", "ugsm_match_full", "ugsm_submit_full_host", "ugsm_submit_foveated_host",
     "ugsm_match_foveated", "ugsm_match_foveated_full", "ugsm_submit_full", "ugsm_submit_foveated", "ugsm_submit_full_batch", "ugsm_submit_foveated_batch", "ugsm_submit_full_batch_host", "ugsm_submit_foveated_batch_host",
+    "ugsm_submit_foveated_multi", "ugsm_match_foveated_multi", "ugsm_reconstruct_full_multi",
     "ugsm_wait", "ugsm_wait_all",
     "ugsm_submit_pyramids", "ugsm_submit_fovea_coarse", "ugsm_submit_fovea_fine", "ugsm_triangulate", "ugsm_fovea_mapping", "ugsm_triangulate_fovea", "ugsm_reconstruct_full", "ugsm_stage_pyramid",
     "ugsm_stage_iterate", "ugsm_stage_seed", "ugsm_stage_smooth", "ugsm_stage_weighted_difference", "ugsm_last_iterations", "ugsm_get_kernel_stats",
@@ -268,6 +269,9 @@ def load(dev: bool = False):
     lib.ugsm_submit_foveated_batch.argtypes = [vp, i, i, pp, pp, i, i, i, ip, ip, pp, pp, pp]
     lib.ugsm_submit_full_batch_host.argtypes = [vp, i, i, pp, pp, i, i, i, pp, pp, pp]
     lib.ugsm_submit_foveated_batch_host.argtypes = [vp, i, i, pp, pp, i, i, i, ip, ip, pp, pp, pp]
+    lib.ugsm_submit_foveated_multi.argtypes = [vp, i, vp, vp, i, i, i, i, ip, ip, pp]
+    lib.ugsm_match_foveated_multi.argtypes = [vp, vp, vp, i, i, i, i, ip, ip, pp, pp, pp]
+    lib.ugsm_reconstruct_full_multi.argtypes = [vp, i, i, pp, i, i, ip, ip, vp]
     lib.ugsm_wait.argtypes = [vp, i]
     lib.ugsm_wait_all.argtypes = [vp]
     lib.ugsm_submit_pyramids.argtypes = [vp, i, vp, vp, i, i, i]
@@ -717,6 +721,42 @@ class Context:
         self.check(self.lib.ugsm_submit_foveated_batch_host(self._h, slot, n, self._ptrs([a.ctypes.data for a in rgbL]), self._ptrs([a.ctypes.data for a in rgbR]),
                                                             W, H, stride, ox, oy, self._ptrs([t[0].ctypes.data for t in stacks]),
                                                             self._ptrs([t[1].ctypes.data for t in stacks]), self._ptrs([t[2].ctypes.data for t in stacks])))
+
+    # ---- several fovea windows on ONE pair (ugsm_*_multi): pyramids and the coarse phase once, the windows' fine levels in lockstep -----
+    @staticmethod
+    def _offsets(offsets, n):
+        if offsets is None:
+            return None, None
+        return (C.c_int * n)(*[int(o[0]) for o in offsets]), (C.c_int * n)(*[int(o[1]) for o in offsets])
+
+    def submit_foveated_multi(self, slot: int, d_rgbL: int, d_rgbR: int, W: int, H: int, stride: int, offsets, d_stack):
+        """d_stack: one device stack per window, each 3 x (F * fovH) x fovW; offsets: one (off_x, off_y) per window, or None (all centred)."""
+        n = len(d_stack)
+        ox, oy = self._offsets(offsets, n)
+        self.check(self.lib.ugsm_submit_foveated_multi(self._h, slot, d_rgbL, d_rgbR, W, H, stride, n, ox, oy, self._ptrs(d_stack)))
+
+    def match_foveated_multi(self, L: np.ndarray, R: np.ndarray, offsets):
+        """Blocking, from any host memory: the (3, F, fovH, fovW) stacks of the windows at `offsets`, one array per window."""
+        W, H, stride = self.check_image(L)
+        if self.check_image(R) != (W, H, stride):
+            raise UgsmError(UGSM_ERR_SIZE_MISMATCH, "the two images differ in size or stride")
+        n = len(offsets)
+        if n < 1:
+            raise UgsmError(UGSM_ERR_BAD_ARG, "no window")
+        fw, fh = fovea_dims(W, H, self.cfg.levels, self.cfg.fovea_levels)
+        stacks = [np.empty((3, self.cfg.fovea_levels, fh, fw), np.float32) for _ in range(n)]
+        ox, oy = self._offsets(offsets, n)
+        self.check(self.lib.ugsm_match_foveated_multi(self._h, L.ctypes.data, R.ctypes.data, W, H, stride, n, ox, oy,
+                                                      self._ptrs([t[0].ctypes.data for t in stacks]), self._ptrs([t[1].ctypes.data for t in stacks]),
+                                                      self._ptrs([t[2].ctypes.data for t in stacks])))
+        return stacks
+
+    def reconstruct_full_multi(self, d_stack, W: int, H: int, d_out3: int, offsets=None, slot: int = 0):
+        """Row f-3 over the stacks of several windows of one pair: where windows overlap the highest index wins.  Waits."""
+        n = len(d_stack)
+        ox, oy = self._offsets(offsets, n)
+        self.check(self.lib.ugsm_reconstruct_full_multi(self._h, slot, n, self._ptrs(d_stack), W, H, ox, oy, d_out3))
+        self.check(self.lib.ugsm_wait(self._h, slot))
 
     # ---- the queue (ugsm_enqueue_* / ugsm_flush / ugsm_next_done): the library owns the slots ----------------------------------------
     def enqueue_full(self, d_rgbL: int, d_rgbR: int, W: int, H: int, stride: int, d_out: int, tag: int):

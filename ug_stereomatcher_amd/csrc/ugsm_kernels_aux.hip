@@ -1,9 +1,10 @@
 // ugsm_kernels_aux.hip -- the plain per-pixel kernels around the matcher proper.
 //
 // k_seed (a level's starting field where the next level's K-cost does not seed itself), k_copy_view (the fovea / pyramid stacks),
-// k_rgb_planes (level 0 of a pyramid of fewer than three levels: BASELINE configs[0]), k_lr_check (the opt-in LR-consistency check),
+// k_rgb_planes (level 0 of a pyramid of fewer than three levels: BASELINE configs[0]; its window form: level 0 inside the windows of a
+// multi-window foveated call), k_lr_check (the opt-in LR-consistency check),
 // k_triangulate[_fovea] (the X, Y, Z planes and, as other forms of the same kernels, the coloured point cloud),
-// k_upsample_paste (row f-3), k_wdiff_* (row f-4).  All HBM- or launch-bound.
+// k_upsample_paste (row f-3; and its form over the stacks of several windows), k_wdiff_* (row f-4).  All HBM- or launch-bound.
 // Citations: /root/reference/src/gpu_matcher/<file>:<line> unless a path is given.
 #include "ugsm_device.hpp"
 #include "ugsm_launch.hpp"
@@ -148,6 +149,42 @@ void launch_rgb_planes(hipStream_t st, const uint8_t *rgb, int stride, int W, in
     with_layout(input_layout(fmt, input_words_aligned(rgb, stride, nullptr)), [&](auto layout) {
         UGSM_LAUNCH(k_rgb_planes<decltype(layout)::value>, grid2(W, H), dim3(256), 0, st, rgb, stride, W, H, planes);
     });
+}
+
+// The window form (k_level0_windows in the statistics; ugsm_submit_foveated_multi): level 0 of BOTH images of one pair, inside the win.n
+// fovea windows (Level0Windows, ugsm_launch.hpp) and nowhere else -- the pyramid pass of such a call stores no level 0 (kPyrNoLevel0).
+// blockIdx.z = 2 x window + image side; a thread converts one pixel as above.  Overlapping windows write equal values: no ordering.
+template <int L>
+__global__ void k_rgb_planes(const uint8_t *__restrict__ rgbL, const uint8_t *__restrict__ rgbR, int stride, int W, int H, float *__restrict__ planesL,
+                             float *__restrict__ planesR, Level0Windows win)
+{
+    const int k = blockIdx.z >> 1, side = blockIdx.z & 1;
+    const int fx = blockIdx.x * blockDim.x + threadIdx.x;
+    const int x = win.x0[k] + fx, y = win.y0[k] + (int)blockIdx.y;
+    if (fx >= win.w || x >= W || y >= H) return;  // (the windows lie inside the frame: fovea_geometry; the launcher refuses others)
+    const uint8_t *const rgb = side ? rgbR : rgbL;
+    float *const planes = side ? planesR : planesL;
+    float f[3];
+    InPix<L>::loadf(rgb + (size_t)y * stride + InPix<L>::bpp * x, f);
+    const size_t n = (size_t)W * H, at = (size_t)y * W + x;
+    planes[at] = f[0];
+    planes[n + at] = f[InPix<L>::mono ? 0 : 1];
+    planes[2 * n + at] = f[InPix<L>::mono ? 0 : 2];
+}
+
+bool launch_level0_windows(hipStream_t st, const uint8_t *rgbL, const uint8_t *rgbR, int stride, int W, int H, float *planesL, float *planesR,
+                           const Level0Windows &win, int fmt)
+{
+    if (win.n < 1 || win.n > kMaxBatch || win.w < 1 || win.h < 1) return false;
+    for (int k = 0; k < win.n; k++)
+        if (win.x0[k] < 0 || win.y0[k] < 0 || win.x0[k] + win.w > W || win.y0[k] + win.h > H) return false;
+    const bool words = input_words_aligned(rgbL, stride, nullptr) && input_words_aligned(rgbR, stride, nullptr);
+    using Kern = void (*)(const uint8_t *, const uint8_t *, int, int, int, float *, float *, Level0Windows);
+    with_layout(input_layout(fmt, words), [&](auto layout) {
+        const Kern kern = k_rgb_planes<decltype(layout)::value>;
+        UGSM_LAUNCH(kern, grid2(win.w, win.h, 2 * win.n), dim3(256), 0, st, rgbL, rgbR, stride, W, H, planesL, planesR, win);
+    });
+    return true;
 }
 
 // =========================================================================================
@@ -703,6 +740,43 @@ void launch_upsample_paste(hipStream_t st, const float *src3, int W, int H, floa
 {
     UGSM_LAUNCH(k_upsample_paste, dim3((W2 + 255) / 256, H2), dim3(256), 0, st, src3, W, H, dst3, W2, H2, fovH_, fovV_, fovC_, fovW, fovH,
                        org_x, org_y);
+}
+
+// The same step over the stacks of pw.n windows of one pair (ugsm_reconstruct_full_multi; PasteWindows, ugsm_launch.hpp): a pixel inside
+// window k takes stack k's value -- the HIGHEST such k where windows overlap, found by a loop over the uniform table -- and a pixel inside
+// none computes the upsample.  fov0: this level's dx plane in stack 0; its dy and conf planes lie fov_plane, 2 fov_plane floats behind.
+// pw.n == 1: the kernel above, operation for operation.
+__global__ __launch_bounds__(256) void k_upsample_paste(const float *__restrict__ src3, int W, int H, float *__restrict__ dst3, int W2, int H2,
+                                                        const float *__restrict__ fov0, size_t fov_plane, int fovW, int fovH, PasteWindows pw)
+{
+    const int ix = blockIdx.x * blockDim.x + threadIdx.x;
+    const int iy = blockIdx.y;
+    if (ix >= W2) return;
+    const float s = (float)1.41421356;
+    const size_t n = (size_t)W * H, n2 = (size_t)W2 * H2, at2 = (size_t)iy * W2 + ix;
+    int k = -1;
+    for (int j = 0; j < pw.n; j++) {
+        const int fx = ix - pw.org_x[j], fy = iy - pw.org_y[j];
+        if (fx >= 0 && fx < fovW && fy >= 0 && fy < fovH) k = j;
+    }
+    if (k >= 0) {
+        const float *const fov = shifted(fov0, pw.stack[k]);
+        const size_t fa = (size_t)(iy - pw.org_y[k]) * fovW + (ix - pw.org_x[k]);
+        dst3[at2] = fov[fa];
+        dst3[n2 + at2] = fov[fov_plane + fa];
+        dst3[2 * n2 + at2] = fov[2 * fov_plane + fa];
+    } else {
+        const size_t at = (size_t)tex_index(((float)iy + 0.5f) / s, H) * W + tex_index(((float)ix + 0.5f) / s, W);
+        dst3[at2] = s * src3[at];
+        dst3[n2 + at2] = s * src3[n + at];
+        dst3[2 * n2 + at2] = s * src3[2 * n + at];
+    }
+}
+
+void launch_upsample_paste_multi(hipStream_t st, const float *src3, int W, int H, float *dst3, int W2, int H2, const float *fov0, size_t fov_plane,
+                                 int fovW, int fovH, const PasteWindows &pw)
+{
+    UGSM_LAUNCH(k_upsample_paste, dim3((W2 + 255) / 256, H2), dim3(256), 0, st, src3, W, H, dst3, W2, H2, fov0, fov_plane, fovW, fovH, pw);
 }
 
 // =========================================================================================

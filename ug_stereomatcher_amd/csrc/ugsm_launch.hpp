@@ -67,6 +67,16 @@ void launch_seed(hipStream_t st, const float *src3, int Ws, int Hs, float *dst3,
 void launch_copy_view(hipStream_t st, Img3 src, int W, int H, float *dst, size_t dst_plane, int dst_pitch, const Batch *bt = nullptr);
 // rgb8 -> planar float level 0 (MatchGPULib.cpp:332-338) where k_pyr_base does not apply: pyramids of fewer than three levels, kernel_path 1
 void launch_rgb_planes(hipStream_t st, const uint8_t *rgb, int stride, int W, int H, float *planes, int fmt = 0);
+// Level 0 of one pair inside n fovea windows of w x h level-0 pixels at (x0[k], y0[k]) -- the window form of k_rgb_planes, one launch for both
+// images (ugsm_submit_foveated_multi: the pyramid pass stores no level 0 there, kPyrNoLevel0).  planesL / planesR: the two level-0 planes
+// (W x H each).  The four-byte formats take their word loads when both images and the stride are 4-byte aligned.  False (nothing launched): a
+// window that leaves the frame.
+struct Level0Windows {
+    int n, w, h;
+    int x0[kMaxBatch], y0[kMaxBatch];
+};
+bool launch_level0_windows(hipStream_t st, const uint8_t *rgbL, const uint8_t *rgbR, int stride, int W, int H, float *planesL, float *planesR,
+                           const Level0Windows &win, int fmt = 0);
 // LR-consistency check (north_star; no reference counterpart): zeroes the confidence of left3 where right3 does not point back within tau
 void launch_lr_check(hipStream_t st, float *left3, const float *right3, int W, int H, float tau, unsigned long long *marked);
 // The stack form (a checked foveated call, ugsm_set_lr_check): every level of the fovea stacks of n pairs in ONE launch, grid.z = pair x F +
@@ -145,6 +155,15 @@ struct CloudPair {
 void launch_point_cloud_batch(hipStream_t st, const CloudPair *d_table, int n, const CloudPair &shape, bool stack, const double *P1, const double *P2);
 void launch_upsample_paste(hipStream_t st, const float *src3, int W, int H, float *dst3, int W2, int H2, const float *fovH_, const float *fovV_,
                            const float *fovC_, int fovW, int fovH, int org_x, int org_y);
+// The same step with the fovea of n stacks of one pair (ugsm_reconstruct_full_multi): window k's crop origin at this level, and its stack's
+// distance from stack 0 in BYTES.  fov0: this level's dx plane in stack 0; dy and conf lie fov_plane, 2 fov_plane floats behind it.
+struct PasteWindows {
+    int n;
+    int org_x[kMaxBatch], org_y[kMaxBatch];
+    long long stack[kMaxBatch];
+};
+void launch_upsample_paste_multi(hipStream_t st, const float *src3, int W, int H, float *dst3, int W2, int H2, const float *fov0, size_t fov_plane,
+                                 int fovW, int fovH, const PasteWindows &pw);
 // S_dx, S_dy, C of weightedDifference (MatchGPULib.cpp:1336-1437) into out3; rowsum = 3*H doubles of scratch
 void launch_weighted_difference(hipStream_t st, const float *newd3, const float *oldd3, int W, int H, double *rowsum, double *out3);
 

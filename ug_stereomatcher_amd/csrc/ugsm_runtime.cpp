@@ -37,11 +37,12 @@ namespace {
 
 constexpr double kScale = 1.41421356;  // MatchLib_common.h:15
 
-enum KClass { KC_COST = 0, KC_SMOOTH, KC_SQBLUR, KC_PYR, KC_SEED, KC_WARP, KC_BOX, KC_MISC, KC_COST_MARCH, KC_PYR_BASE, KC_COST_SMALL, KC_SMOOTH_SMALL, KC_COST_MARCH4, KC_COUNT };
+enum KClass { KC_COST = 0, KC_SMOOTH, KC_SQBLUR, KC_PYR, KC_SEED, KC_WARP, KC_BOX, KC_MISC, KC_COST_MARCH, KC_PYR_BASE, KC_COST_SMALL, KC_SMOOTH_SMALL, KC_COST_MARCH4,
+              KC_LEVEL0_WIN, KC_COUNT };
 const char *kClassName[2][KC_COUNT] = {
     {"k_cost_split", "k_smooth_fused", "k_sqblur_tiled", "k_blur_decimate_tiled", "k_seed", "-", "-", "misc", "k_cost_march", "k_pyr_base", "k_cost_small",
-     "k_smooth_small", "k_cost_march4"},
-    {"k_cost_ref", "k_smooth_pass", "k_sqblur_clamp", "k_blur_decimate", "k_seed", "k_warp", "k_box", "misc", "-", "-", "-", "-", "-"}};
+     "k_smooth_small", "k_cost_march4", "k_level0_windows"},
+    {"k_cost_ref", "k_smooth_pass", "k_sqblur_clamp", "k_blur_decimate", "k_seed", "k_warp", "k_box", "misc", "-", "-", "-", "-", "-", "-"}};
 constexpr int kNoLevel = UGSM_MAX_LEVELS;  // stats cell of launches that belong to no pyramid level
 struct StatCell {
     long long launches = 0;
@@ -70,6 +71,9 @@ struct Slot {
     // VIRTUAL pairs -- virtual pair nreal + b is pair b with the L and R views exchanged (pair_pyr) -- and lvl_stride is the room of one
     // fovea field, so that both directions' fields lie in the level buffers the slot holds.  Everywhere else nreal == nb.
     int nreal = 1;
+    // The fine phase of ugsm_submit_foveated_multi: the nb fields are nb WINDOWS OF ONE PAIR -- every virtual pair reads pair 0's two pyramids,
+    // unswapped (pair_pyr), under pair 0's range word (copied to the others' entries); lvl_stride is one fovea field there as well.
+    bool one_pair = false;
     float *A = nullptr, *Rw = nullptr, *B = nullptr, *d0 = nullptr, *d1 = nullptr;
     // Side stream of the slot (round 3): the right image's upload and pyramid, and then A = G_clamp * L^2 of every full-frame level
     // (MatchGPULib.cpp:1866-1875, once per level), run there beside the left pyramid and the coarse levels' iterations -- launches
@@ -461,6 +465,7 @@ int prepare_slot(ugsm_ctx *ctx, Slot &s, int W, int H, int nb = 1)
     s.H = H;
     s.levels = levels;
     s.nb = s.nreal = nb;
+    s.one_pair = false;
     for (int i = 0; i < UGSM_MAX_LEVELS; i++) s.iters_run[i] = -1;
     s.have_pyr = false;
     s.have_coarse = false;
@@ -714,9 +719,13 @@ int input_row_bytes(const ugsm_ctx *ctx, int W) { return ugsm_input_bytes_per_pi
 // The images of a batch go through every pyramid kernel together (one launch per level for all of them).
 // What a foveated call reads of level 0: every pair's fovea window (the level-0 crop of fovea_geometry); k_pyr_base then stores level 0
 // only where a window lies.  Full-mode calls and ugsm_submit_pyramids (window not known yet) pass none.
+// later (ugsm_submit_foveated_multi: several windows on one pair): k_pyr_base stores no level 0 at all (kPyrNoLevel0); the caller writes it
+// inside the windows afterwards with one launch of its own (enqueue_level0_windows).  Where k_pyr_base does not build the pyramid, level 0 is
+// stored whole as ever.
 struct FoveaWin {
     int w = 0, h = 0;
     int x0[kMaxBatch], y0[kMaxBatch];
+    bool later = false;
 };
 // skip0 (full-mode calls whose level-0 kernels read the images: Slot::direct0): level 0 is not stored at all.
 int build_pyramids(ugsm_ctx *ctx, Slot &s, int si, const uint8_t *const *rgb, int stride, float *pyr, hipStream_t stream = nullptr, const FoveaWin *win = nullptr,
@@ -737,9 +746,10 @@ int build_pyramids(ugsm_ctx *ctx, Slot &s, int si, const uint8_t *const *rgb, in
     Batch bt0 = bt;  // k_pyr_base: the input-field offsets carry the pairs' window origins instead
     if (win || skip0)
         for (int j = 0; j < nb; j++) bt0.in[j] = win ? ((long long)win->y0[j] << 32) | (unsigned)win->x0[j] : 0;
-    const PyrWindow pw = win ? PyrWindow{win->x0[0], win->y0[0], win->w, win->h} : (skip0 ? kPyrNoLevel0 : PyrWindow{0, 0, 0, 0});
-    if (skip0 && (win || !base)) {  // (level0_direct asks for neither)
-        ctx->err = "pyramids without level 0 are built by k_pyr_base for full-mode calls only";
+    const bool later = win && win->later;
+    const PyrWindow pw = later ? kPyrNoLevel0 : (win ? PyrWindow{win->x0[0], win->y0[0], win->w, win->h} : (skip0 ? kPyrNoLevel0 : PyrWindow{0, 0, 0, 0}));
+    if ((skip0 && (win || !base)) || (later && nb != 1)) {  // (level0_direct asks for neither; the windows of ONE pair come later)
+        ctx->err = "pyramids without level 0 are built by k_pyr_base for full-mode calls, and for the one pair of a multi-window call";
         return UGSM_ERR_STATE;
     }
     const Batch *const pb = nb > 1 ? &bt : nullptr;
@@ -1081,9 +1091,11 @@ void full_views(const Slot &s, const float *pyr, int lev, Img3 *out)
 }
 
 // The pyramid that pair v of the call matches as its left (side 0) or right (side 1) image.  The virtual pairs nreal .. 2 nreal - 1 of a
-// checked foveated call are the pairs 0 .. nreal - 1 with the two exchanged: the right-to-left match reads the same two pyramids.
+// checked foveated call are the pairs 0 .. nreal - 1 with the two exchanged: the right-to-left match reads the same two pyramids.  The
+// virtual pairs of a multi-window call (Slot::one_pair) are windows of pair 0: every one reads its pyramids as they are.
 const float *pair_pyr(const Slot &s, int side, int v)
 {
+    if (s.one_pair) return side == 0 ? s.pyrL : s.pyrR;  // (n windows of one pair: ugsm_submit_foveated_multi)
     const bool back = v >= s.nreal;
     return ((side == 0) != back ? s.pyrL : s.pyrR) + (size_t)(back ? v - s.nreal : v) * s.pyr_stride;
 }
@@ -1517,6 +1529,78 @@ int enqueue_foveated(ugsm_ctx *ctx, Slot &s, int si, int n, const uint8_t *const
     s.lr_fov_pairs = n;
     s.lr_fov_F = F;
     return UGSM_OK;
+}
+
+// n fovea windows on ONE pair (ugsm_submit_foveated_multi): what does not depend on the window runs once, the rest in lockstep.
+//   - the pyramids of one pair, as a lone foveated call builds them (side stream and A planes of levels F-1 .. top included), but with no
+//     level 0 (FoveaWin::later); one launch then writes level 0 of both images inside the n windows (k_rgb_planes' window form).  Pyramids
+//     that k_pyr_base does not build (fewer than three levels, kernel_path 1) hold level 0 whole and skip that launch;
+//   - the coarse phase once, its field into `state`;
+//   - the fine phase with s.nb = n virtual pairs that all read pair 0's pyramids (Slot::one_pair, pair_pyr), start from the one state and
+//     run under pair 0's range word; their fields lie in the level buffers at a stride of one fovea field, as a checked call's do.  The
+//     caller has made the buffers hold n such fields (n x 3 fovW fovH floats exceed one pair's 3 W H as soon as n > 2^(F-1));
+//   - contexts that run pair by pair (early exit, kernel_path 1) and n == 1: the fine phase window after window, nb = 1.
+// Afterwards the slot holds no whole pyramids (have_pyr, have_coarse false) and its nb, nreal and lvl_stride are one pair's again.
+int enqueue_foveated_multi(ugsm_ctx *ctx, Slot &s, int si, const uint8_t *d_rgbL, const uint8_t *d_rgbR, int W, int H, int stride, int n,
+                           const int *off_x, const int *off_y, float *state, float *const *d_stack)
+{
+    const int F = ctx->cfg.fovea_levels;
+    s.lr_ran = false;
+    s.lr_fov_pairs = 0;
+    FoveaWin win;
+    UCHK(fovea_windows(ctx, W, H, n, off_x, off_y, win));
+    win.later = true;
+    UCHK(enqueue_pyramids(ctx, s, si, d_rgbL, d_rgbR, W, H, stride, F - 1, &win));
+    if (ctx->cfg.kernel_path != 1 && s.levels >= 3) {  // (k_pyr_base built them: as `base` in build_pyramids)
+        Level0Windows lw{};
+        lw.n = n;
+        lw.w = win.w;
+        lw.h = win.h;
+        for (int k = 0; k < n; k++) {
+            lw.x0[k] = win.x0[k];
+            lw.y0[k] = win.y0[k];
+        }
+        s.cur_level = 0;
+        bool ok;
+        {
+            Timer t(ctx, &s, si, KC_LEVEL0_WIN, 2.0 * n * win.w * win.h);
+            ok = launch_level0_windows(s.st, d_rgbL, d_rgbR, stride, s.W, s.H, s.pyrL + s.off[0], s.pyrR + s.off[0], lw, ctx->hooks.input_format);
+        }
+        s.cur_level = kNoLevel;
+        if (!ok) {
+            ctx->err = "a fovea window leaves the frame";
+            return UGSM_ERR_STATE;
+        }
+        HIPCHK(ctx, hipGetLastError());
+    }
+    int st = enqueue_fovea_coarse(ctx, s, si, state);
+    if (st == UGSM_OK) {
+        if (n == 1 || ctx->cfg.kernel_path == 1 || ctx->cfg.early_exit_threshold > 0.0f) {
+            for (int k = 0; k < n && st == UGSM_OK; k++) st = enqueue_fovea_fine(ctx, s, si, state, off_x[k], off_y[k], d_stack[k], nullptr, nullptr);
+        } else {
+            const size_t field = (3 * (size_t)win.w * win.h + 63) & ~(size_t)63;
+            if ((size_t)n * field > s.lvl_cap) {
+                ctx->err = "the level buffers do not hold the windows' fields";
+                return UGSM_ERR_STATE;
+            }
+            // pair 0's range word for every virtual pair: entries 1 .. n-1, doubling what is already there
+            for (int c = 1; s.range_known && c < n; c *= 2)
+                HIPCHK(ctx, hipMemcpyAsync(s.range_bad + c, s.range_bad, sizeof(unsigned) * std::min(c, n - c), hipMemcpyDeviceToDevice, s.st));
+            const float *vstate[kMaxBatch];
+            for (int k = 0; k < n; k++) vstate[k] = state;
+            const size_t real_stride = s.lvl_stride;
+            s.nb = s.nreal = n;
+            s.lvl_stride = field;
+            s.one_pair = true;
+            st = enqueue_fovea_fine(ctx, s, si, vstate, off_x, off_y, d_stack, nullptr, nullptr);
+            s.nb = s.nreal = 1;
+            s.lvl_stride = real_stride;
+            s.one_pair = false;
+        }
+    }
+    s.have_pyr = false;
+    s.have_coarse = false;
+    return st;
 }
 
 // Has everything enqueued on the slot finished?  (Never blocks; a slot found idle stops counting as busy.)
@@ -2157,6 +2241,46 @@ int ugsm_submit_foveated_batch(ugsm_ctx *ctx, int slot, int n, const uint8_t *co
     return mark_done(ctx, *s);
 }
 
+// ---- n windows on one pair ----------------------------------------------------------------------------------------------------
+// What ugsm_submit_foveated_multi and ugsm_match_foveated_multi refuse before anything is enqueued; the windows' field size on success.
+static int multi_check(ugsm_ctx *ctx, int n, int W, int H, int stride, const int *&off_x, const int *&off_y, const int *zeros, int *fw, int *fh)
+{
+    const int F = ctx->cfg.fovea_levels;
+    if (n < 1 || n > UGSM_MAX_BATCH || F < 2) return UGSM_ERR_BAD_ARG;
+    if (!off_x) off_x = zeros;
+    if (!off_y) off_y = zeros;
+    if (lr_fovea_on(ctx)) return ctx_fail(ctx, UGSM_ERR_STATE, "the foveated LR check is on: the checked multi-window call is not built (ugsm_set_lr_check)");
+    UCHK(ugsm_fovea_dims(W, H, ctx->cfg.levels, F, fw, fh));
+    if (stride < input_row_bytes(ctx, W)) return UGSM_ERR_SIZE_MISMATCH;
+    return UGSM_OK;
+}
+// the level buffers for n fields of fw x fh in lockstep (contexts that run window by window need one pair's alone)
+static int multi_level_bufs(ugsm_ctx *ctx, Slot &s, int n, int W, int H, int fw, int fh)
+{
+    if (n == 1 || ctx->cfg.kernel_path == 1 || ctx->cfg.early_exit_threshold > 0.0f) return UGSM_OK;
+    const size_t field = (3 * (size_t)fw * fh + 63) & ~(size_t)63;
+    return ensure_level_bufs(ctx, s, std::max((size_t)n * field, 3 * (size_t)W * H));
+}
+
+int ugsm_submit_foveated_multi(ugsm_ctx *ctx, int slot, const uint8_t *d_rgbL, const uint8_t *d_rgbR, int W, int H, int stride, int n,
+                               const int *off_x, const int *off_y, float *const *d_stack)
+{
+    Slot *s;
+    UCHK(get_slot(ctx, slot, &s));
+    if (!d_rgbL || !d_rgbR || !d_stack) return UGSM_ERR_BAD_ARG;
+    for (int k = 0; k < n && k < UGSM_MAX_BATCH; k++)
+        if (!d_stack[k]) return UGSM_ERR_BAD_ARG;
+    const int zeros[UGSM_MAX_BATCH] = {0};
+    int fw, fh;
+    UCHK(multi_check(ctx, n, W, H, stride, off_x, off_y, zeros, &fw, &fh));
+    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
+    UCHK(multi_level_bufs(ctx, *s, n, W, H, fw, fh));
+    const size_t fn3 = 3 * (size_t)fw * fh;  // level F-1's state, staged in the slot's hout as ugsm_submit_foveated stages it
+    UCHK(grow(ctx, s->hout, s->hout_cap, std::max(fn3, s->hout_cap)));
+    UCHK(enqueue_foveated_multi(ctx, *s, slot, d_rgbL, d_rgbR, W, H, stride, n, off_x, off_y, s->hout, d_stack));
+    return mark_done(ctx, *s);
+}
+
 int ugsm_wait(ugsm_ctx *ctx, int slot)
 {
     Slot *s;
@@ -2301,6 +2425,39 @@ int ugsm_match_foveated(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR,
                         int off_y, float *stackH, float *stackV, float *stackC, float *pyrL, float *pyrR)
 {
     return drained(ctx, 0, match_foveated_on_slot(ctx, 0, rgbL, rgbR, W, H, stride, off_x, off_y, stackH, stackV, stackC, pyrL, pyrR, true));
+}
+
+static int match_foveated_multi_on_slot0(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, int n, const int *off_x,
+                                         const int *off_y, float *const *stackH, float *const *stackV, float *const *stackC)
+{
+    Slot *s;
+    UCHK(get_slot(ctx, 0, &s));
+    if (!rgbL || !rgbR || !stackH || !stackV || !stackC) return UGSM_ERR_BAD_ARG;
+    for (int k = 0; k < n && k < UGSM_MAX_BATCH; k++)
+        if (!stackH[k] || !stackV[k] || !stackC[k]) return UGSM_ERR_BAD_ARG;
+    const int zeros[UGSM_MAX_BATCH] = {0};
+    int fw, fh;
+    UCHK(multi_check(ctx, n, W, H, stride, off_x, off_y, zeros, &fw, &fh));
+    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
+    UCHK(multi_level_bufs(ctx, *s, n, W, H, fw, fh));
+    const size_t fn = (size_t)fw * fh, stackn = (size_t)ctx->cfg.fovea_levels * fn;
+    UCHK(grow(ctx, s->hout, s->hout_cap, 3 * fn + (size_t)n * 3 * stackn));  // [state 3 fn][n stacks of 3 stackn]
+    UCHK(stage_in(ctx, *s, rgbL, rgbR, W, H, stride));
+    float *d_stack[UGSM_MAX_BATCH];
+    for (int k = 0; k < n; k++) d_stack[k] = s->hout + 3 * fn + (size_t)k * 3 * stackn;
+    UCHK(enqueue_foveated_multi(ctx, *s, 0, s->rgbL, s->rgbR, W, H, stride, n, off_x, off_y, s->hout, d_stack));
+    for (int k = 0; k < n; k++) {
+        float *const dst[3] = {stackH[k], stackV[k], stackC[k]};
+        for (int c = 0; c < 3; c++) HIPCHK(ctx, hipMemcpyAsync(dst[c], d_stack[k] + c * stackn, stackn * sizeof(float), hipMemcpyDeviceToHost, s->st));
+    }
+    s->forked = false;  // (enqueued whole, as mark_done)
+    return ugsm_wait(ctx, 0);
+}
+
+int ugsm_match_foveated_multi(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, int n, const int *off_x,
+                              const int *off_y, float *const *stackH, float *const *stackV, float *const *stackC)
+{
+    return drained(ctx, 0, match_foveated_multi_on_slot0(ctx, rgbL, rgbR, W, H, stride, n, off_x, off_y, stackH, stackV, stackC));
 }
 
 int ugsm_submit_foveated_host(ugsm_ctx *ctx, int slot, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, int off_x,
@@ -3126,6 +3283,46 @@ int ugsm_reconstruct_full(ugsm_ctx *ctx, int slot, const float *d_stackH, const 
         Timer t(ctx, s, slot, KC_MISC, (double)w[level - 1] * h[level - 1]);
         launch_upsample_paste(s->st, cur, w[level], h[level], dst, w[level - 1], h[level - 1], d_stackH + (size_t)(level - 1) * fl,
                               d_stackV + (size_t)(level - 1) * fl, d_stackC + (size_t)(level - 1) * fl, g.fw, g.fh, g.ox[level - 1], g.oy[level - 1]);
+        std::swap(cur, other);
+    }
+    HIPCHK(ctx, hipGetLastError());
+    return UGSM_OK;
+}
+
+// hierarchicalDisparity over the stacks of n windows of one pair: the steps of ugsm_reconstruct_full, every one pasting all the windows
+int ugsm_reconstruct_full_multi(ugsm_ctx *ctx, int slot, int n, const float *const *d_stack, int W, int H, const int *off_x, const int *off_y,
+                                float *d_out3)
+{
+    Slot *s;
+    UCHK(get_slot(ctx, slot, &s));
+    if (!d_stack || !d_out3 || n < 1 || n > UGSM_MAX_BATCH) return UGSM_ERR_BAD_ARG;
+    for (int k = 0; k < n; k++)
+        if (!d_stack[k]) return UGSM_ERR_BAD_ARG;
+    const int levels = ctx->cfg.levels, F = ctx->cfg.fovea_levels;
+    int w[UGSM_MAX_LEVELS], h[UGSM_MAX_LEVELS];
+    UCHK(level_dims(W, H, levels, w, h));
+    if (F < 2 || F > levels) return UGSM_ERR_BAD_ARG;
+    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
+    FoveaGeom g[UGSM_MAX_BATCH];
+    for (int k = 0; k < n; k++) fovea_geometry(w, h, F, off_x ? off_x[k] : 0, off_y ? off_y[k] : 0, g[k]);
+    const size_t fl = (size_t)g[0].fw * g[0].fh;
+    UCHK(ensure_level_bufs(ctx, *s, 3 * (size_t)w[1] * h[1]));
+    // level F-1 (whole frame; the same in every stack) as a 3-plane field, from stack 0
+    float *cur = s->d0, *other = s->d1;
+    for (int c = 0; c < 3; c++)
+        HIPCHK(ctx, hipMemcpyAsync(cur + c * fl, d_stack[0] + ((size_t)c * F + (F - 1)) * fl, fl * sizeof(float), hipMemcpyDeviceToDevice, s->st));
+    for (int level = F - 1; level > 0; level--) {
+        float *dst = (level == 1) ? d_out3 : other;
+        PasteWindows pw{};
+        pw.n = n;
+        for (int k = 0; k < n; k++) {
+            pw.org_x[k] = g[k].ox[level - 1];
+            pw.org_y[k] = g[k].oy[level - 1];
+            pw.stack[k] = byte_diff(d_stack[k], d_stack[0]);
+        }
+        Timer t(ctx, s, slot, KC_MISC, (double)w[level - 1] * h[level - 1]);
+        launch_upsample_paste_multi(s->st, cur, w[level], h[level], dst, w[level - 1], h[level - 1], d_stack[0] + (size_t)(level - 1) * fl, (size_t)F * fl,
+                                    g[0].fw, g[0].fh, pw);
         std::swap(cur, other);
     }
     HIPCHK(ctx, hipGetLastError());
