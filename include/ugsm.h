@@ -36,7 +36,8 @@ extern "C" {
                                UGSM_INPUT_*, ugsm_input_bytes_per_pixel, ugsm_input_format_from_encoding, ugsm_set_input_format,
                                ugsm_get_input_format; the merged cloud of the fovea stack -- ugsm_fovea_level_mapping, ugsm_fovea_cloud_points,
                                ugsm_point_cloud_fovea_all; the LR check of the foveated calls -- UGSM_LR_FULL / UGSM_LR_FOVEATED, ugsm_set_lr_check,
-                               ugsm_get_lr_check, ugsm_last_lr_marked_levels
+                               ugsm_get_lr_check, ugsm_last_lr_marked_levels; the merged cloud of several windows' stacks --
+                               ugsm_fovea_multi_cloud_points, ugsm_point_cloud_fovea_multi
                                6: the kernel choices follow what is in flight, not ugsm_config.slots: ugsm_plan_level takes `alone`, ugsm_plan_level_in_frame
                                is gone, ugsm_level_plan.latency_policy is .alone; ugsm_enqueue_* returns UGSM_OK once the pair is accepted (a failed
                                CALL is reported through ugsm_completion.status only); the fovea shard carries a status word (a rank that fails still
@@ -332,8 +333,8 @@ int ugsm_submit_foveated_batch_host(ugsm_ctx *ctx, int slot, int n, const uint8_
  * After the call the slot holds no whole pyramids: ugsm_submit_fovea_fine on it answers UGSM_ERR_STATE, as after any one-shot foveated call.
  * Contexts with early_exit_threshold set, and kernel_path 1, still build the pyramids and run the coarse phase once; their n fine phases run
  * one after the other.  Same results.
- * NOT built: pyramid stacks from this call; a queue form (ugsm_enqueue_*); the page-locked _host kind; the LR check; a merged cloud of
- * several stacks (call ugsm_point_cloud_fovea_all per stack).
+ * NOT built: pyramid stacks from this call; a queue form (ugsm_enqueue_*); the page-locked _host kind; the LR check.  The merged cloud of
+ * the n stacks is ugsm_point_cloud_fovea_multi (below, with the other clouds).
  * Asynchronous on `slot`. */
 int ugsm_submit_foveated_multi(ugsm_ctx *ctx, int slot, const uint8_t *d_rgbL, const uint8_t *d_rgbR, int W, int H, int stride,
                                int n, const int *off_x, const int *off_y, float *const *d_stack);
@@ -604,6 +605,53 @@ int ugsm_point_cloud_fovea_all(ugsm_ctx *ctx, int slot, const float *d_stackx, c
                                int W, int H, int off_x, int off_y, const uint8_t *d_rgbL, int stride,
                                const double *P1, const double *P2, const ugsm_cloud_params *p, void *d_points,
                                long long cap_points, long long *d_count, long long *d_level_counts);
+
+/* The stacks of SEVERAL WINDOWS of one pair as ONE cloud (this build's): what follows ugsm_submit_foveated_multi as
+ * ugsm_point_cloud_fovea_all follows ugsm_submit_foveated.
+ *
+ * Inputs: n stacks, 1 <= n <= UGSM_MAX_BATCH, each laid out as ugsm_submit_foveated_multi writes it -- 3 x (F*fovH) x fovW, planes dx, dy,
+ * conf -- and the off_x[j], off_y[j] given to that call (NULL = all centred).  left[j][k], upper[j][k], scale_k: ugsm_fovea_level_mapping's
+ * numbers for level k and window j's offset; at k = F-1 the margins are 0 for every window.
+ *
+ * ENTRIES.  The cloud is a sequence of E = (F-1)*n + 1 entries, level-major: entry e = k*n + j is level k of window j for k = 0 .. F-2 and
+ * j = 0 .. n-1; the last entry e = (F-1)*n is the whole-frame level F-1, read from stack 0 alone (row block F-1 is the same field in every
+ * stack by the matching contract, so it is emitted once).  Within an entry the order is ugsm_point_cloud_fovea's (the sampled pixels,
+ * column outer, row inner), and each record is byte for byte the one ugsm_point_cloud_fovea writes for that pixel of that stack with the
+ * entry's mapping, in either record format and any input format.
+ *
+ * THE RULE ACROSS WINDOWS.  Pixel (ii, jj) of entry (j, k) lies at x1 = (float)left[j][k] + (float)ii * scale_k,
+ * y1 = (float)upper[j][k] + (float)jj * scale_k (the cloud's own x1, y1).  inside(i, m) holds when
+ *   x1 >= (float)left[i][m] && x1 + scale_k <= (float)left[i][m] + (float)fovW * scale_m, and the same in y with upper and fovH,
+ * every operation in binary32 and rounded on its own.  The pixel is LEFT OUT when
+ *   (a) k >= 1 and inside(i, k-1) for some window i in 0 .. n-1, its own included: a finer level of any window covers it; or
+ *   (b) k <= F-2 and inside(i, k) for some i > j: the same level of a higher-numbered window holds it (the highest index wins, as in
+ *       ugsm_reconstruct_full_multi).
+ * A pixel that straddles an edge is kept: the cloud has seams of overlap and never a hole.  (b) is stated in the mapped frame, not on the
+ * level's integer grid: left[j][k] rounds each window's offset on its own, and the integer-grid form leaves slivers uncovered.  With
+ * n == 1, (b) is empty and (a) is the coverage rule above: the call is byte for byte ugsm_point_cloud_fovea_all, the count and the
+ * per-level counts included.  Per entry the left-out set is a union of at most 2n-1 rectangles of the sampled grid.
+ *
+ * ugsm_fovea_multi_cloud_points: the dense size of the merged cloud; per_entry (may be NULL) receives the E entry sizes; -1 on bad
+ * arguments.  Host only.
+ *
+ * ugsm_point_cloud_fovea_multi: levels and fovea_levels are the context's.  d_stack is a HOST array of n DEVICE stacks, as
+ * ugsm_reconstruct_full_multi takes it; a stack's confidence plane is its third plane, read only by a compact cloud with min_conf above
+ * -inf.  Dense: every sampled pixel the rule keeps, *d_count = ugsm_fovea_multi_cloud_points(..).  Compact: the ugsm_cloud_params test
+ * applied after the rule, the relative order kept, the same bytes from run to run.  cap_points, *d_count and the count buffer as for
+ * ugsm_point_cloud_fovea_all (the buffer grows on demand, counted by ugsm_context_device_bytes; UGSM_ERR_NOMEM if it cannot).
+ * d_entry_counts (device, 8-byte aligned, E entries; may be NULL) receives each entry's number of points in the cloud.  One launch
+ * (compact: two) for all entries.  Asynchronous on `slot`'s stream -- so ordered behind a ugsm_submit_foveated_multi on the same slot --
+ * and the call itself does not wait for the stream unless one of its buffers has to grow.
+ * UGSM_ERR_BAD_ARG, before any device work: everything ugsm_point_cloud_fovea_all refuses, n outside 1 .. UGSM_MAX_BATCH, a null array or
+ * entry, a misaligned d_entry_counts.  UGSM_ERR_STATE: pairs enqueued with ugsm_enqueue_* are outstanding.
+ * NOT built: a queue or managed form of this call; the resized cloud of several stacks; the LR check of the multi-window call; the ros/
+ * shim does not call it. */
+long long ugsm_fovea_multi_cloud_points(int W, int H, int levels, int fovea_levels, int n, const int *off_x, const int *off_y,
+                                        int sampling, long long *per_entry);
+int ugsm_point_cloud_fovea_multi(ugsm_ctx *ctx, int slot, int n, const float *const *d_stack, int W, int H,
+                                 const int *off_x, const int *off_y, const uint8_t *d_rgbL, int stride,
+                                 const double *P1, const double *P2, const ugsm_cloud_params *p, void *d_points,
+                                 long long cap_points, long long *d_count, long long *d_entry_counts);
 
 /* Row f-1, the resized cloud: what the node publishes on output_pointcloud_resized, doReconstruction_resized /
  * doReconstructionFOV_resized (getPointCloud.cpp:724-800, :802-884).  The Z plane resized with cv::resize(..., INTER_CUBIC) to

@@ -41,6 +41,19 @@ cloud only (XYZRGB16, sampling 1, compact: min_conf = the median confidence of t
 want_planes).  Then the device time (profile_events 2: the in-dispatch events of the launches) of ONE batched cloud launch for a call of
 eight pairs against eight single-pair ugsm_point_cloud / ugsm_point_cloud_fovea_all launches on planes of the same size, for the 16 MP
 stack and for 1080p full mode, dense and compact PCL32.  --leg NAME runs one leg only (each GPU step under a time limit of its own).
+
+    python tools/cloud_bench.py --multi [--parent-tree DIR] [--rounds 3] [--out profiles/cloud_multi_bench.json]
+
+The merged cloud of several windows of one pair (ugsm_point_cloud_fovea_multi) instead: 16 MP and 1080p at 14 / 7 levels, n = 2, 4, 8
+windows at two offset sets -- spread over the frame (little overlap) and clustered round the centre (heavy overlap) -- after one
+ugsm_submit_foveated_multi on the slot.  Per case: one merged call, dense PCL32 and compact XYZRGB16 (min_conf 0.5), and the n
+ugsm_point_cloud_fovea_all calls it replaces (each repeat is the n calls together, cloud behind cloud in one buffer): device_ms (the summed
+in-dispatch kernel times of a repeat, median over --reps repeats after --warmup), wall_ms (first call .. end of ugsm_wait: launch gaps,
+the table's upload and the compact forms' memsets included) and the records written.  Every measurement runs in a child process of its
+own (one context per process), as tools/lr_bench.py does it: this build's child and -- when --parent-tree names a checkout of the parent
+commit with its libraries built -- the parent's child, which times the n calls there, take turns round by round in alternating order;
+every child's value is kept, `spread` is the range between a configuration's own children.  Written beside the numbers: whether the
+merged call takes no longer than the n calls on the parent commit, beyond the spread between those calls' own repeats.
 """
 import argparse
 import ctypes as C
@@ -52,7 +65,7 @@ import time
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+sys.path.insert(0, ROOT)   # (a --multi child puts its --tree in front of it)
 
 P1 = np.array([[7.3230899280915291e+03, 0., 2.4836974544986647e+03, 0.],
                [0., 7.3035803715514758e+03, 1.7170248033347561e+03, 0.], [0., 0., 1., 0.]])
@@ -357,6 +370,137 @@ def queue_launch_rows(args, emit, p1, p2, dp):
                       "single_x8_device_ms": round(float(np.median(s_)), 4), "single_min": round(min(s_), 4), "single_max": round(max(s_), 4)})
 
 
+MULTI_FORMS = (("dense_pcl32", 0, False), ("compact_xyzrgb16", 1, True))
+
+
+def multi_offsets(kind, n, W, H, fw, fh):
+    """n window offsets: 'spread' -- a grid over the frame, the level-0 windows far apart; 'clustered' -- the same grid an eighth of a
+    window apart round the centre."""
+    nx, ny = {2: (2, 1), 4: (2, 2), 8: (4, 2)}[n]
+    dx, dy = (int(0.8 * W / nx), int(0.8 * H / ny)) if kind == "spread" else (fw // 8, fh // 8)
+    return [(int((i - (nx - 1) / 2) * dx), int((j - (ny - 1) / 2) * dy)) for j in range(ny) for i in range(nx)]
+
+
+def multi_child(args):
+    """One size in this process, every case: prints one line "MULTIBENCH <json list of rows>"."""
+    sys.path.insert(0, args.tree)
+    from ug_stereomatcher_amd import _lib, synth
+    assert os.path.dirname(os.path.abspath(_lib.__file__)) == os.path.join(os.path.abspath(args.tree), "ug_stereomatcher_amd")
+    p1, p2 = (np.ascontiguousarray(m, np.float64).reshape(12) for m in (P1, P2))
+    dp = C.POINTER(C.c_double)
+    P1p, P2p = p1.ctypes.data_as(dp), p2.ctypes.data_as(dp)
+    levels, F = 14, 7
+    W, H = (int(v) for v in args.size.split("x"))
+    merged_too = hasattr(_lib.Context, "point_cloud_fovea_multi")
+    L, R, _, _ = synth.make_pair(W, H, synth.BASE_SEED + 2)
+    fw, fh = _lib.fovea_dims(W, H, levels, F)
+    lvl = F * fw * fh * 4
+    rows = []
+    with _lib.Context(levels=levels, fovea_levels=F, profile_events=2) as c:
+        lib, h = c.lib, c.handle
+        pL, pR = c.to_device(L), c.to_device(R)
+        stacks = [c.alloc(3 * lvl) for _ in range(8)]
+        d_pts, d_cnt = c.alloc(8 * F * fw * fh * 32), c.alloc(8 * 8)
+        for n in (2, 4, 8):
+            for kind in ("spread", "clustered"):
+                offs = multi_offsets(kind, n, W, H, fw, fh)
+                c.submit_foveated_multi(0, pL, pR, W, H, L.strides[0], offs, stacks[:n])
+                c.check(lib.ugsm_wait(h, 0))
+                ox, oy = c._offsets(offs, n)
+                ptrs = c._ptrs(stacks[:n])
+                for name, fmt, compact in MULTI_FORMS:
+                    prm = _lib.cloud_params(format=fmt, compact=compact, min_conf=0.5 if compact else None)
+                    step = 32 if fmt == 0 else 16
+                    row = {"size": args.size, "n": n, "offsets": kind, "form": name}
+                    if merged_too:
+                        cap = _lib.fovea_multi_cloud_points(W, H, levels, F, offs)
+                        merged = lambda: c.check(lib.ugsm_point_cloud_fovea_multi(h, 0, n, ptrs, W, H, ox, oy, pL, L.strides[0], P1p, P2p, C.byref(prm),
+                                                                                  d_pts, cap, d_cnt, None))
+                        t, lo, hi, wall = spread_ms(c, merged, args.reps, args.warmup)
+                        row.update(merged_device_ms=t, merged_device_ms_min=lo, merged_device_ms_max=hi, merged_wall_ms=wall,
+                                   merged_records=int(c.to_host(d_cnt, (1,), np.int64)[0]), merged_launches=2 if compact else 1)
+                    # the n calls it replaces, each stack's cloud behind the one before (a compact cloud needs each count back first: not timed)
+                    caps = [_lib.fovea_cloud_points(W, H, levels, F, o) for o in offs]
+                    one = lambda k, at: c.check(lib.ugsm_point_cloud_fovea_all(h, 0, stacks[k], stacks[k] + lvl, stacks[k] + 2 * lvl, W, H, offs[k][0],
+                                                                               offs[k][1], pL, L.strides[0], P1p, P2p, C.byref(prm),
+                                                                               d_pts + at * step, caps[k], d_cnt + 8 * k, None))
+                    for k in range(n):
+                        one(k, 0)
+                    c.check(lib.ugsm_wait(h, 0))
+                    counts = c.to_host(d_cnt, (n,), np.int64).tolist()
+                    first = np.concatenate([[0], np.cumsum(counts)]).tolist()
+
+                    def per_stack():
+                        for k in range(n):
+                            one(k, first[k])
+                    t, lo, hi, wall = spread_ms(c, per_stack, args.reps, args.warmup)
+                    row.update(per_stack_device_ms=t, per_stack_device_ms_min=lo, per_stack_device_ms_max=hi, per_stack_wall_ms=wall,
+                               per_stack_records=int(sum(counts)), per_stack_launches=n * (2 if compact else 1))
+                    rows.append(row)
+        for p in [pL, pR, d_pts, d_cnt] + stacks:
+            c.free(p)
+    print("MULTIBENCH " + json.dumps(rows), flush=True)
+
+
+def multi_main(args):
+    import statistics
+    import subprocess
+    parent = os.path.abspath(args.parent_tree) if args.parent_tree else None
+    if parent and not os.path.exists(os.path.join(parent, "ug_stereomatcher_amd", "libugsm.so")):
+        raise SystemExit(f"{parent}: no built ug_stereomatcher_amd/libugsm.so")
+    trees = {"this": ROOT}
+    if parent:
+        trees["parent"] = parent
+
+    def measure(tree, size):
+        cmd = [sys.executable, os.path.abspath(__file__), "--multi", "--child", "--tree", tree, "--size", size, "--reps", str(args.reps),
+               "--warmup", str(args.warmup)]
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=420)
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("MULTIBENCH ")]
+        if r.returncode != 0 or not lines:
+            raise SystemExit(f"child failed ({r.returncode}): {' '.join(cmd)}\n{r.stdout[-2000:]}\n{r.stderr[-2000:]}")
+        return json.loads(lines[-1][11:])
+
+    result = dict(tool="tools/cloud_bench.py --multi", levels=14, fovea_levels=7, rounds=args.rounds, reps=args.reps, warmup=args.warmup,
+                  parent_measured=bool(parent), cases=[])
+    for size in args.sizes.split(","):
+        kept = {name: [] for name in trees}
+        for rnd in range(args.rounds):
+            names = list(trees)
+            for name in (names if rnd % 2 == 0 else names[::-1]):     # alternating order
+                kept[name].append(measure(trees[name], size))
+                print(size, name, "round", rnd, flush=True)
+        for k, first in enumerate(kept["this"][0]):
+            med = lambda name, key: statistics.median(ch[k][key] for ch in kept[name])
+            rng = lambda name, key: max(ch[k][key] for ch in kept[name]) - min(ch[k][key] for ch in kept[name])
+            case = {key: first[key] for key in ("size", "n", "offsets", "form", "merged_records", "per_stack_records", "merged_launches",
+                                                "per_stack_launches")}
+            for key in ("merged_device_ms", "merged_wall_ms", "per_stack_device_ms", "per_stack_wall_ms"):
+                case[key] = round(med("this", key), 4)
+                case[key + "_children"] = [round(ch[k][key], 4) for ch in kept["this"]]
+                case[key + "_spread"] = round(rng("this", key), 4)
+            case["records_ratio"] = round(first["merged_records"] / first["per_stack_records"], 3)
+            if parent:
+                for key in ("per_stack_device_ms", "per_stack_wall_ms"):
+                    case["parent_" + key] = round(med("parent", key), 4)
+                    case["parent_" + key + "_children"] = [round(ch[k][key], 4) for ch in kept["parent"]]
+                    case["parent_" + key + "_spread"] = round(rng("parent", key), 4)
+                # (the spread of the parent's calls: between its children, and inside a child between its own repeats, whichever is larger)
+                inside = max(ch[k]["per_stack_device_ms_max"] - ch[k]["per_stack_device_ms_min"] for ch in kept["parent"])
+                case["parent_per_stack_device_ms_repeat_range"] = round(inside, 4)
+                case["merged_no_longer_than_parent_calls_device"] = bool(
+                    case["merged_device_ms"] <= case["parent_per_stack_device_ms"] + max(case["parent_per_stack_device_ms_spread"], inside))
+                case["merged_no_longer_than_parent_calls_wall"] = bool(
+                    case["merged_wall_ms"] <= case["parent_per_stack_wall_ms"] + case["parent_per_stack_wall_ms_spread"])
+            result["cases"].append(case)
+            print(json.dumps({a: b for a, b in case.items() if not a.endswith("_children")}), flush=True)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(result, f, indent=1, sort_keys=True)
+        print(f"wrote {args.out}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=25)
@@ -368,8 +512,16 @@ def main():
     ap.add_argument("--pairs", type=int, default=64, help="--queue: pairs per timed burst")
     ap.add_argument("--leg", choices=QUEUE_LEGS + ("launch",), help="--queue: this leg only")
     ap.add_argument("--mode", choices=("full", "foveated"), help="--queue: this mode only")
+    ap.add_argument("--multi", action="store_true", help="the merged cloud of several windows of one pair and the per-stack calls it replaces instead")
+    ap.add_argument("--parent-tree", default=None, help="--multi: a checkout of the parent commit with its libraries built")
+    ap.add_argument("--rounds", type=int, default=3, help="--multi: children per configuration")
+    ap.add_argument("--child", action="store_true", help="(internal) --multi: measure in this process")
+    ap.add_argument("--tree", default=ROOT, help="(internal) the tree whose package the child loads")
+    ap.add_argument("--size", default="4928x3264", help="(internal)")
     ap.add_argument("--out")
     args = ap.parse_args()
+    if args.multi:
+        return multi_child(args) if args.child else multi_main(args)
     from ug_stereomatcher_amd import _lib, synth
     import torch
     rows = []

@@ -57,6 +57,8 @@ EXPORTS = [
     "ugsm_resized_cloud_points", "ugsm_point_cloud_resized", "ugsm_point_cloud_resized_fovea",
     # ... and the merged cloud of the whole fovea stack
     "ugsm_fovea_level_mapping", "ugsm_fovea_cloud_points", "ugsm_point_cloud_fovea_all",
+    # ... and of the stacks of several windows of one pair
+    "ugsm_fovea_multi_cloud_points", "ugsm_point_cloud_fovea_multi",
     # the input formats
     "ugsm_input_bytes_per_pixel", "ugsm_input_format_from_encoding", "ugsm_set_input_format", "ugsm_get_input_format",
     # the LR check of the foveated calls
@@ -359,6 +361,9 @@ def load(dev: bool = False):
     lib.ugsm_fovea_cloud_points.argtypes = [i, i, i, i, i, i, i, C.POINTER(C.c_longlong)]
     lib.ugsm_fovea_cloud_points.restype = C.c_longlong
     lib.ugsm_point_cloud_fovea_all.argtypes = [vp, i, vp, vp, vp, i, i, i, i, vp, i, dpp, dpp, C.POINTER(CloudParams), vp, C.c_longlong, vp, vp]
+    lib.ugsm_fovea_multi_cloud_points.argtypes = [i, i, i, i, i, ip, ip, i, C.POINTER(C.c_longlong)]
+    lib.ugsm_fovea_multi_cloud_points.restype = C.c_longlong
+    lib.ugsm_point_cloud_fovea_multi.argtypes = [vp, i, i, pp, i, i, ip, ip, vp, i, dpp, dpp, C.POINTER(CloudParams), vp, C.c_longlong, vp, vp]
     if bool(lib.ugsm_is_dev_library()) != bool(dev):
         raise UgsmError(UGSM_ERR_STATE, f"{path} is not the {'development' if dev else 'product'} build")
     _libs[dev] = lib
@@ -445,6 +450,17 @@ def fovea_cloud_points(W: int, H: int, levels: int = 14, fovea_levels: int = 7, 
     per = (C.c_longlong * UGSM_MAX_LEVELS)()
     n = int(load().ugsm_fovea_cloud_points(W, H, levels, fovea_levels, int(off[0]), int(off[1]), sampling, per))
     return (n, list(per[:fovea_levels]) if n >= 0 else []) if per_level else n
+
+
+def fovea_multi_cloud_points(W: int, H: int, levels: int, fovea_levels: int, offsets, sampling: int = 1, per_entry: bool = False):
+    """Points of the dense merged cloud of the stacks of len(offsets) windows of one pair (ugsm_point_cloud_fovea_multi), -1 on bad
+    arguments; with per_entry, also the list of each entry's points, level-major: (fovea_levels - 1) * len(offsets) + 1 entries."""
+    n = len(offsets)
+    E = max((fovea_levels - 1) * n + 1, 1)
+    per = (C.c_longlong * E)()
+    ox, oy = (C.c_int * n)(*[int(o[0]) for o in offsets]), (C.c_int * n)(*[int(o[1]) for o in offsets])
+    total = int(load().ugsm_fovea_multi_cloud_points(W, H, levels, fovea_levels, n, ox, oy, sampling, per))
+    return (total, list(per[:E]) if total >= 0 else []) if per_entry else total
 
 
 def input_bytes_per_pixel(format: int) -> int:
@@ -648,6 +664,26 @@ class Context:
         if d_level_counts is None:
             return n
         return n, self.to_host(d_level_counts, (self.cfg.fovea_levels,), np.int64).tolist()
+
+    def point_cloud_fovea_multi(self, d_stacks, W: int, H: int, offsets, d_rgbL: int, stride: int, P1, P2, params: CloudParams, d_points: int,
+                                cap_points: int, d_count: int, d_entry_counts=None, slot: int = 0):
+        """The stacks of several windows of one pair as one cloud (ugsm_point_cloud_fovea_multi): the entries level-major, each without
+        the pixels a finer level of any window or the same level of a higher-numbered window holds.  d_stacks: one device stack per window;
+        offsets: one (off_x, off_y) per window, or None (all centred).  Waits on the slot and returns the count, or (count, per-entry
+        counts) when d_entry_counts is given."""
+        n = len(d_stacks)
+        ox, oy = self._offsets(offsets, n)
+        p1 = np.ascontiguousarray(P1, np.float64).reshape(12)
+        p2 = np.ascontiguousarray(P2, np.float64).reshape(12)
+        dp = C.POINTER(C.c_double)
+        self.check(self.lib.ugsm_point_cloud_fovea_multi(self._h, slot, n, self._ptrs(d_stacks), W, H, ox, oy, d_rgbL, stride,
+                                                         p1.ctypes.data_as(dp), p2.ctypes.data_as(dp), C.byref(params), d_points,
+                                                         int(cap_points), d_count, d_entry_counts))
+        self.check(self.lib.ugsm_wait(self._h, slot))
+        count = int(self.to_host(d_count, (1,), np.int64)[0])
+        if d_entry_counts is None:
+            return count
+        return count, self.to_host(d_entry_counts, ((self.cfg.fovea_levels - 1) * n + 1,), np.int64).tolist()
 
     def point_cloud_resized(self, d_dispx: int, d_dispy: int, d_conf, d_rgbL: int, W: int, H: int, stride: int, P1, P2, factor: float,
                             params: CloudParams, d_points: int, cap_points: int, d_count: int, slot: int = 0) -> int:

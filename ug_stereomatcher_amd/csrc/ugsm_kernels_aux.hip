@@ -240,9 +240,12 @@ __device__ __forceinline__ void tri_point(float x1, float y1, float x2, float y2
 }
 
 // The forms of k_triangulate / k_triangulate_fovea (template parameter): the X, Y, Z planes, the two launches of the point cloud and
-// the two of the resized cloud and the two of the fovea stack's merged cloud (below).  The plane form keeps its own parameter list, so
-// its code is what it was before the cloud forms came.
-enum TriForm : int { kTriPlanes = 0, kTriCloudCount = 1, kTriCloud = 2, kTriResizedCount = 3, kTriResized = 4, kTriStackCount = 5, kTriStack = 6 };
+// the two of the resized cloud, the two of the fovea stack's merged cloud and the two of the merged cloud of several windows' stacks
+// (below).  The plane form keeps its own parameter list, so its code is what it was before the cloud forms came.
+enum TriForm : int {
+    kTriPlanes = 0, kTriCloudCount = 1, kTriCloud = 2, kTriResizedCount = 3, kTriResized = 4, kTriStackCount = 5, kTriStack = 6,
+    kTriMultiCount = 7, kTriMulti = 8
+};
 
 template <int Form>
 __global__ __launch_bounds__(256) void k_triangulate(const float *__restrict__ dispx, const float *__restrict__ dispy, int W, int H, Proj P1q, Proj P2q,
@@ -487,11 +490,35 @@ __device__ __forceinline__ long long stack_dense_run(const CloudArgs &a, const C
     return lv.first + (long long)ci * a.hc - (long long)ny * min(max(ci - lv.cx0, 0), ncx) + r0 - (in ? min(max(r0 - lv.cy0, 0), ny) : 0);
 }
 
+// The merged cloud of several windows' stacks (ugsm_point_cloud_fovea_multi; kTriMultiCount / kTriMulti): the same tile over E * strips
+// virtual strips, entry = strip / strips, E = (F-1) n + 1 entries (level-major: entry k n + j = level k of window j; the last = level F-1
+// of stack 0).  What an entry leaves out is a UNION of rectangles of its sampled grid (CloudEntry), so the kernel (k_triangulate_fovea,
+// the overload on CloudMulti) reduces the entry's list to what the tile needs before the tile runs, 32 lanes = the tile's columns:
+//   omask[c]  the left-out rows of column c inside the tile, one bit per row: phase A marks those not kept before any load;
+//   run[c]    dense: the first record of column c's run in this tile -- the entry's first record, the records of the columns before it
+//             (the host's segments: between two neighbouring rectangle edges every column keeps the same number of rows) and the kept
+//             rows above the tile (the row masks of the chunks above, popcounted).  No workgroup waits for another.
+// Compact: the two-launch scheme over the E * wc virtual columns and E * strips virtual strips.
+struct MultiTile {
+    const unsigned long long *omask;
+    const long long *run;
+};
+
+// bits [lo, hi) of a tile's 64 rows
+__device__ __forceinline__ unsigned long long row_bits(int lo, int hi)
+{
+    lo = max(lo, 0);
+    hi = min(hi, kCloudTR);
+    if (hi <= lo) return 0ull;
+    return (hi == kCloudTR ? ~0ull : (1ull << hi) - 1) & ~((1ull << lo) - 1);
+}
+
 template <bool Fovea, int Form>
 __device__ __forceinline__ void cloud_tile(const CloudArgs &a, const CloudResize &rz, const Proj &P1q, const Proj &P2q, const CloudStack *sk = nullptr,
-                                           int level = 0)
+                                           int level = 0, const CloudMulti *mu = nullptr, const MultiTile *mt = nullptr)
 {
     constexpr bool Stack = Form == kTriStackCount || Form == kTriStack;
+    constexpr bool Multi = Form == kTriMultiCount || Form == kTriMulti;  // (level: the entry; its early return is the kernel's)
     __shared__ float4 rec[kCloudTC * kCloudPad];
     __shared__ unsigned char kept[kCloudTC * kCloudTR];
     __shared__ unsigned char src[kCloudTC * kCloudTR];
@@ -500,11 +527,11 @@ __device__ __forceinline__ void cloud_tile(const CloudArgs &a, const CloudResize
     // tx: the strip among all of the launch (the stack forms: F * strips virtual strips); c0: its first column in its level, v0: among
     // the launch's columns (the stack forms: level * wc + c0, the F * wc virtual columns)
     const int t = threadIdx.x, tx = blockIdx.x, ty = blockIdx.y;
-    const int c0 = (Stack ? tx - level * sk->strips : tx) * kCloudTC, r0 = ty * kCloudTR;
+    const int c0 = (Stack ? tx - level * sk->strips : Multi ? tx - level * ((a.wc + kCloudTC - 1) / kCloudTC) : tx) * kCloudTC, r0 = ty * kCloudTR;
     const int c = t & (kCloudTC - 1), ci = c0 + c;
-    const int v0 = Stack ? level * a.wc + c0 : c0, wv = Stack ? sk->F * a.wc : a.wc;
+    const int v0 = Stack || Multi ? level * a.wc + c0 : c0, wv = Stack ? sk->F * a.wc : Multi ? mu->E * a.wc : a.wc;
     unsigned *const col_tot = a.cnt + (size_t)wv * a.nchunk, *const strip_tot = col_tot + wv;  // (compact only)
-    constexpr bool Write = Form == kTriCloud || Form == kTriResized || Form == kTriStack, Count = !Write;  // the cloud launch / the count launch
+    constexpr bool Write = Form == kTriCloud || Form == kTriResized || Form == kTriStack || Form == kTriMulti, Count = !Write;  // the cloud launch / the count launch
     if constexpr (Stack) {  // a tile wholly covered has nothing to evaluate (the workgroup that writes the size stays)
         const CloudLevel &lv = sk->lv[level];
         if (c0 >= lv.cx0 && min(c0 + kCloudTC, a.wc) <= lv.cx1 && r0 >= lv.cy0 && min(r0 + kCloudTR, a.hc) <= lv.cy1 &&
@@ -520,6 +547,7 @@ __device__ __forceinline__ void cloud_tile(const CloudArgs &a, const CloudResize
         bool k = false;
         bool covered = false;
         if constexpr (Stack) covered = ci >= sk->lv[level].cx0 && ci < sk->lv[level].cx1 && cj >= sk->lv[level].cy0 && cj < sk->lv[level].cy1;
+        if constexpr (Multi) covered = (mt->omask[c] >> r) & 1;
         if (ci < a.wc && cj < a.hc && !covered) {
             float4 v;
             if constexpr (Form == kTriResizedCount || Form == kTriResized)
@@ -580,6 +608,21 @@ __device__ __forceinline__ void cloud_tile(const CloudArgs &a, const CloudResize
                 for (int l = 0; l < sk->F; l++) sk->level_counts[l] = sk->lv[l].points;
             }
         }
+    } else if constexpr (Multi) {  // ... and each entry's share: E may pass what eight lanes a level were sized for, so a lane loops over entries
+        if (ty == 0 && tx == (a.compact ? (int)gridDim.x - 1 : 0)) {
+            if (t == 0) *a.count = a.compact ? (long long)pre[kCloudTC] + strip_tot[tx] : mu->total;
+            if (mu->entry_counts) {
+                const int strips = (a.wc + kCloudTC - 1) / kCloudTC;
+                for (int e = t; e < mu->E; e += 256) {
+                    long long n = mu->table[e].points;
+                    if (a.compact) {
+                        n = 0;
+                        for (int k = 0; k < strips; k++) n += strip_tot[e * strips + k];
+                    }
+                    mu->entry_counts[e] = n;
+                }
+            }
+        }
     } else if (t == 0 && ty == 0 && tx == (a.compact ? (int)gridDim.x - 1 : 0))
         *a.count = a.compact ? (long long)pre[kCloudTC] + strip_tot[tx] : (long long)a.wc * a.hc;
     // C: every column's run, contiguous
@@ -589,7 +632,7 @@ __device__ __forceinline__ void cloud_tile(const CloudArgs &a, const CloudResize
             const int cc = q / (2 * kCloudTR), j = (q >> 1) & (kCloudTR - 1), half = q & 1;
             if (j >= nrec[cc]) continue;
             const long long o = (a.compact ? (long long)pre[kCloudTC] + pre[cc]
-                                           : (Stack ? stack_dense_run(a, sk->lv[level], c0 + cc, r0) : (long long)(c0 + cc) * a.hc + r0)) + j;
+                                           : (Multi ? mt->run[cc] : Stack ? stack_dense_run(a, sk->lv[level], c0 + cc, r0) : (long long)(c0 + cc) * a.hc + r0)) + j;
             if (o >= a.cap) continue;
             const float4 v = rec[cc * kCloudPad + src[cc * kCloudTR + j]];
             out[2 * o + half] = half ? make_float4(v.w, 0.0f, 0.0f, 0.0f) : make_float4(v.x, v.y, v.z, 1.0f);
@@ -600,7 +643,7 @@ __device__ __forceinline__ void cloud_tile(const CloudArgs &a, const CloudResize
             const int cc = q / kCloudTR, j = q & (kCloudTR - 1);
             if (j >= nrec[cc]) continue;
             const long long o = (a.compact ? (long long)pre[kCloudTC] + pre[cc]
-                                           : (Stack ? stack_dense_run(a, sk->lv[level], c0 + cc, r0) : (long long)(c0 + cc) * a.hc + r0)) + j;
+                                           : (Multi ? mt->run[cc] : Stack ? stack_dense_run(a, sk->lv[level], c0 + cc, r0) : (long long)(c0 + cc) * a.hc + r0)) + j;
             if (o >= a.cap) continue;
             out[o] = rec[cc * kCloudPad + src[cc * kCloudTR + j]];
         }
@@ -665,6 +708,70 @@ __global__ __launch_bounds__(256) void k_triangulate_fovea(const CloudPair *__re
     cloud_tile<true, Form>(a, CloudResize{}, P1q, P2q, &row.sk, level);
 }
 
+// The merged cloud of several windows' stacks: the workgroup's entry from its strip; the entry's row of the table in device memory gives its
+// planes and mapping into the workgroup's copy of the arguments; its rectangle list is read from the table ONCE, a lane a rectangle, into
+// LDS, and reduced from there to the tile's row masks and dense run starts (MultiTile, above cloud_tile).  A tile wholly inside one
+// rectangle returns at once (the workgroup that writes the size stays).
+template <int Form>
+__global__ __launch_bounds__(256) void k_triangulate_fovea(CloudArgs a, Proj P1q, Proj P2q, CloudMulti mu)
+{
+    static_assert(Form == kTriMultiCount || Form == kTriMulti, "the forms of several windows' stacks");
+    __shared__ unsigned long long omask[kCloudTC];
+    __shared__ long long run[kCloudTC];
+    __shared__ CloudRect rects[kCloudMaxRects];
+    const int t = threadIdx.x, tx = blockIdx.x, ty = blockIdx.y;
+    const int strips = (a.wc + kCloudTC - 1) / kCloudTC;
+    const int e = tx / strips;
+    const CloudEntry &en = mu.table[e];
+    const int nrect = min(en.nrect, kCloudMaxRects), nseg = min(en.nseg, kCloudMaxSegs);
+    const int c0 = (tx - e * strips) * kCloudTC, r0 = ty * kCloudTR;
+    const int c1 = min(c0 + kCloudTC, a.wc), r1 = min(r0 + kCloudTR, a.hc);
+    if (t < nrect) rects[t] = en.rect[t];
+    __syncthreads();
+    bool whole = false;
+    for (int i = 0; i < nrect; i++) {
+        const CloudRect q = rects[i];
+        whole = whole || (c0 >= q.cx0 && c1 <= q.cx1 && r0 >= q.cy0 && r1 <= q.cy1);
+    }
+    if (whole && !(ty == 0 && tx == (a.compact ? (int)gridDim.x - 1 : 0))) {
+        if (Form == kTriMultiCount && t < kCloudTC && c0 + t < a.wc) a.cnt[(size_t)(e * a.wc + c0 + t) * a.nchunk + ty] = 0;
+        return;
+    }
+    if (t < kCloudTC) {
+        const int ci = c0 + t;
+        unsigned long long m = 0;
+        for (int i = 0; i < nrect; i++) {
+            const CloudRect q = rects[i];
+            if (ci >= q.cx0 && ci < q.cx1) m |= row_bits(q.cy0 - r0, q.cy1 - r0);
+        }
+        omask[t] = m;
+        if (Form == kTriMulti && !a.compact) {
+            int above = 0;  // the left-out rows of this column above the tile
+            for (int ch = 0; ch < ty; ch++) {
+                unsigned long long u = 0;
+                for (int i = 0; i < nrect; i++) {
+                    const CloudRect q = rects[i];
+                    if (ci >= q.cx0 && ci < q.cx1) u |= row_bits(q.cy0 - ch * kCloudTR, q.cy1 - ch * kCloudTR);
+                }
+                above += __builtin_popcountll(u);
+            }
+            int sg = 0;     // the column's segment: the last one that starts at or before it
+            for (int i = 1; i < nseg; i++)
+                if (en.seg_x[i] <= ci) sg = i;
+            run[t] = en.first + (long long)en.seg_first[sg] + (long long)(ci - en.seg_x[sg]) * en.seg_rows[sg] + (r0 - above);
+        }
+    }
+    __syncthreads();
+    a.dx = en.dx;
+    a.dy = en.dy;
+    a.conf = a.compact ? en.conf : nullptr;
+    a.left_margin = en.left_margin;
+    a.upper_margin = en.upper_margin;
+    a.scale = en.scale;
+    const MultiTile mt{omask, run};
+    cloud_tile<true, Form>(a, CloudResize{}, P1q, P2q, nullptr, e, &mu, &mt);
+}
+
 int cloud_strips(int wc) { return (wc + kCloudTC - 1) / kCloudTC; }
 int cloud_chunks(int hc) { return (hc + kCloudTR - 1) / kCloudTR; }
 
@@ -692,6 +799,17 @@ void launch_point_cloud_stack(hipStream_t st, const CloudArgs &args, const Cloud
     const Kern count = k_triangulate_fovea<kTriStackCount>, cloud = k_triangulate_fovea<kTriStack>;
     if (args.compact) UGSM_LAUNCH(count, grid, dim3(256), 0, st, args, a, b, sk);
     UGSM_LAUNCH(cloud, grid, dim3(256), 0, st, args, a, b, sk);
+}
+
+void launch_point_cloud_multi(hipStream_t st, const CloudArgs &args, const CloudMulti &mu, const double *P1, const double *P2)
+{
+    Proj a, b;
+    for (int k = 0; k < 12; k++) { a.m[k] = P1[k]; b.m[k] = P2[k]; }
+    const dim3 grid(mu.E * cloud_strips(args.wc), args.nchunk);
+    using Kern = void (*)(CloudArgs, Proj, Proj, CloudMulti);
+    const Kern count = k_triangulate_fovea<kTriMultiCount>, cloud = k_triangulate_fovea<kTriMulti>;
+    if (args.compact) UGSM_LAUNCH(count, grid, dim3(256), 0, st, args, a, b, mu);
+    UGSM_LAUNCH(cloud, grid, dim3(256), 0, st, args, a, b, mu);
 }
 
 void launch_point_cloud_batch(hipStream_t st, const CloudPair *d_table, int n, const CloudPair &shape, bool stack, const double *P1, const double *P2)

@@ -153,6 +153,36 @@ struct CloudPair {
     CloudStack sk;
 };
 void launch_point_cloud_batch(hipStream_t st, const CloudPair *d_table, int n, const CloudPair &shape, bool stack, const double *P1, const double *P2);
+// The merged cloud of the stacks of n windows of ONE pair (ugsm_point_cloud_fovea_multi): the forms kTriMultiCount / kTriMulti, whose grid
+// runs over E * cloud_strips(wc) strips, E = (F-1) n + 1 entries (entry = strip / strips).  A workgroup takes its entry's row of a table
+// in DEVICE memory (E reaches 97 and a row holds up to 31 rectangles: no room among the kernel arguments): the entry's planes and mapping,
+// the rectangles of its sampled grid that the rule across windows leaves out (include/ugsm.h; a union, so they may overlap), and what the
+// dense offsets need -- the entry's first record, and the columns cut into segments at the rectangles' edges: inside a segment every
+// column keeps the same number of rows, so a column's first record is its segment's plus a product.
+constexpr int kCloudMaxRects = 2 * kMaxBatch - 1;     // n windows' finer levels + the n - 1 higher-numbered windows' same level
+constexpr int kCloudMaxSegs = 2 * kCloudMaxRects + 1;
+struct CloudRect {
+    int cx0, cx1, cy0, cy1;  // the sampled columns [cx0, cx1) and rows [cy0, cy1); never empty
+};
+struct CloudEntry {
+    const float *dx, *dy, *conf;    // the entry's level of its stack
+    int left_margin, upper_margin;  // ugsm_fovea_level_mapping for the entry's window
+    float scale;
+    int nrect, nseg;
+    long long first, points;        // dense: the entry's first record and its records
+    CloudRect rect[kCloudMaxRects];
+    int seg_x[kCloudMaxSegs];           // segment g = the columns from seg_x[g] up to the next segment's (the last: up to wc)
+    int seg_rows[kCloudMaxSegs];        // the rows each of its columns keeps
+    unsigned seg_first[kCloudMaxSegs];  // the entry's records before its first column
+};
+struct CloudMulti {
+    const CloudEntry *table;  // device memory, E rows
+    int E;
+    long long total;          // dense: the cloud's size
+    long long *entry_counts;  // E entries, may be null
+};
+// args.dx / dy / conf are not read (the table's are); args.cnt (compact): (E * wc) * nchunk counts, E * wc column totals, E * strips strip totals
+void launch_point_cloud_multi(hipStream_t st, const CloudArgs &args, const CloudMulti &mu, const double *P1, const double *P2);
 void launch_upsample_paste(hipStream_t st, const float *src3, int W, int H, float *dst3, int W2, int H2, const float *fovH_, const float *fovV_,
                            const float *fovC_, int fovW, int fovH, int org_x, int org_y);
 // The same step with the fovea of n stacks of one pair (ugsm_reconstruct_full_multi): window k's crop origin at this level, and its stack's

@@ -126,6 +126,16 @@ struct Slot {
     size_t cq_words_cap = 0;
     long long cq_cap[kMaxBatch] = {};
     int cq_n = 0, cq_step = 0, cq_levels = 0;  // the managed cloud call in flight: pairs, bytes per record, fovea levels (0: full mode)
+    // The merged cloud of several windows (ugsm_point_cloud_fovea_multi): its table of entries in device memory, and the page-locked copies
+    // it is uploaded from on the slot's stream.  The call does not wait for the stream, so a copy may still be read by an earlier call's
+    // upload when the next call is made: kMcRing copies take turns, each with an event behind its upload, and a call waits only for the
+    // UPLOAD of the call kMcRing before it.
+    static constexpr int kMcRing = 4;
+    CloudEntry *mc_tab = nullptr, *mc_tab_h = nullptr;
+    size_t mc_tab_cap = 0, mc_tab_h_rows = 0;  // rows of the device table; rows of each page-locked copy
+    hipEvent_t mc_ev[kMcRing] = {};
+    bool mc_ev_set[kMcRing] = {};
+    int mc_next = 0;
     int iters_run[UGSM_MAX_LEVELS];
     unsigned *range_bad = nullptr;  // device word: 0 while every pyramid value of the pair in this slot passed range_ok (ugsm_exact.hpp)
     float *hout = nullptr;  // device staging for host-API outputs
@@ -2029,6 +2039,10 @@ void ugsm_destroy(ugsm_ctx *ctx)
         for (void *p : {(void *)s.cq_tab, (void *)s.cq_pts, (void *)s.cq_words})
             if (p) (void)hipFree(p);
         if (s.cq_tab_h) (void)hipHostFree(s.cq_tab_h);
+        if (s.mc_tab) (void)hipFree(s.mc_tab);
+        if (s.mc_tab_h) (void)hipHostFree(s.mc_tab_h);
+        for (hipEvent_t e : s.mc_ev)
+            if (e) (void)hipEventDestroy(e);
         if (s.cq_words_h) (void)hipHostFree(s.cq_words_h);
         if (s.lr_host) (void)hipHostFree(s.lr_host);
         if (s.st2 && s.owns_st2) (void)hipStreamDestroy(s.st2);
@@ -2739,17 +2753,25 @@ int fovea_level_mappings(int W, int H, int levels, int F, int off_x, int off_y, 
 
 // The coverage rule along one axis (include/ugsm.h): pixel i of level k, at x1 = (float)m + (float)i * sc, is covered when
 // x1 >= (float)m_fine && x1 + sc <= (float)m_fine + (float)n * sc_fine, every operation in binary32.  Monotone in i, so the covered
-// pixels are one interval [i0, i1); of the sampled grid (pixel = index * s) that is [c0, c1).
+// pixels are one interval [i0, i1); of the sampled grid (pixel = index * s) that is [c0, c1).  x1 never falls as i grows (i is exact in
+// binary32, and a rounded product and a rounded sum keep the order of their operands), so the first test turns true once and the second
+// false once: two bisections, the same interval a scan over the pixels finds (the merged cloud of several windows asks for up to 31
+// rectangles for each of up to 97 entries per call).
 void covered_interval(int n, int m, float sc, int m_fine, float sc_fine, int s, int *c0, int *c1)
 {
     const float lo = (float)m_fine, hi = (float)m_fine + (float)n * sc_fine;
-    int i0 = n, i1 = n;
-    for (int i = 0; i < n; i++) {
-        const float x1 = (float)m + (float)i * sc;
-        const bool in = x1 >= lo && x1 + sc <= hi;
-        if (in && i0 == n) i0 = i;
-        if (!in && i0 < n) { i1 = i; break; }
-    }
+    auto first = [&](int from, auto test) {  // the first i in [from, n) that passes a test which stays passed; n: none
+        int a = from, b = n;
+        while (a < b) {
+            const int mid = a + (b - a) / 2;
+            if (test((float)m + (float)mid * sc)) b = mid;
+            else a = mid + 1;
+        }
+        return a;
+    };
+    int i0 = first(0, [&](float x1) { return x1 >= lo; });
+    int i1 = first(i0, [&](float x1) { return !(x1 + sc <= hi); });
+    if (i1 <= i0) i0 = i1 = n;  // (nothing covered)
     *c0 = (i0 + s - 1) / s;
     *c1 = (i1 + s - 1) / s;
     if (*c1 < *c0) *c1 = *c0;
@@ -2787,7 +2809,93 @@ int cloud_stack_table(int W, int H, int levels, int F, int off_x, int off_y, int
     return UGSM_OK;
 }
 
+// ---- the merged cloud of several windows of one pair (ugsm_point_cloud_fovea_multi; the rule across windows: include/ugsm.h) ----------
+struct MultiCloud {
+    int n, F, E, fw, fh, wc, hc, s;
+    int left[UGSM_MAX_BATCH][UGSM_MAX_LEVELS], upper[UGSM_MAX_BATCH][UGSM_MAX_LEVELS];
+    float scale[UGSM_MAX_LEVELS];
+};
+
+int cloud_multi_geometry(int W, int H, int levels, int F, int n, const int *off_x, const int *off_y, int sampling, MultiCloud &g)
+{
+    if (n < 1 || n > UGSM_MAX_BATCH || sampling < 1) return UGSM_ERR_BAD_ARG;
+    for (int j = 0; j < n; j++)
+        UCHK(fovea_level_mappings(W, H, levels, F, off_x ? off_x[j] : 0, off_y ? off_y[j] : 0, &g.fw, &g.fh, g.left[j], g.upper[j], g.scale));
+    g.n = n;
+    g.F = F;
+    g.E = (F - 1) * n + 1;
+    g.s = sampling;
+    g.wc = (g.fw + sampling - 1) / sampling;
+    g.hc = (g.fh + sampling - 1) / sampling;
+    return UGSM_OK;
+}
+
+// Entry e's row of the kernel's table, its planes apart: the mapping, the rectangles the entry leaves out -- (a) inside level k-1 of any
+// window, (b) inside level k of a higher-numbered window; each a column interval times a row interval (covered_interval) -- the column
+// segments between the rectangles' edges, and the entry's dense records.  `first`: the records of the entries before it.
+void cloud_multi_entry(const MultiCloud &g, int e, long long first, CloudEntry &en)
+{
+    const int k = e / g.n, j = e - k * g.n;  // (the last entry: level F-1 of window 0)
+    en = CloudEntry{};
+    en.left_margin = g.left[j][k];
+    en.upper_margin = g.upper[j][k];
+    en.scale = g.scale[k];
+    auto add = [&](int i, int m) {
+        CloudRect q;
+        covered_interval(g.fw, g.left[j][k], g.scale[k], g.left[i][m], g.scale[m], g.s, &q.cx0, &q.cx1);
+        covered_interval(g.fh, g.upper[j][k], g.scale[k], g.upper[i][m], g.scale[m], g.s, &q.cy0, &q.cy1);
+        if (q.cx0 < q.cx1 && q.cy0 < q.cy1 && en.nrect < kCloudMaxRects) en.rect[en.nrect++] = q;
+    };
+    if (k >= 1)
+        for (int i = 0; i < g.n; i++) add(i, k - 1);
+    if (k <= g.F - 2)
+        for (int i = j + 1; i < g.n; i++) add(i, k);
+    // the segments: between two neighbouring edges the same rectangles hold every column, so every column keeps the same number of rows
+    int xs[kCloudMaxSegs + 1], nx = 0;
+    xs[nx++] = 0;
+    for (int i = 0; i < en.nrect; i++)
+        for (int x : {en.rect[i].cx0, en.rect[i].cx1})
+            if (x > 0 && x < g.wc) xs[nx++] = x;
+    std::sort(xs, xs + nx);
+    nx = (int)(std::unique(xs, xs + nx) - xs);
+    long long records = 0;
+    for (int sg = 0; sg < nx; sg++) {
+        std::pair<int, int> rows[kCloudMaxRects];
+        int nr = 0;
+        for (int i = 0; i < en.nrect; i++)
+            if (en.rect[i].cx0 <= xs[sg] && xs[sg] < en.rect[i].cx1) rows[nr++] = {en.rect[i].cy0, en.rect[i].cy1};
+        std::sort(rows, rows + nr);
+        int out = 0, reach = 0;  // the length of the union of the row intervals
+        for (int i = 0; i < nr; i++) {
+            out += std::max(rows[i].second - std::max(rows[i].first, reach), 0);
+            reach = std::max(reach, rows[i].second);
+        }
+        en.seg_x[sg] = xs[sg];
+        en.seg_rows[sg] = g.hc - out;
+        en.seg_first[sg] = (unsigned)records;
+        records += (long long)((sg + 1 < nx ? xs[sg + 1] : g.wc) - xs[sg]) * (g.hc - out);
+    }
+    en.nseg = nx;
+    en.first = first;
+    en.points = records;
+}
+
 }  // namespace
+
+long long ugsm_fovea_multi_cloud_points(int W, int H, int levels, int fovea_levels, int n, const int *off_x, const int *off_y, int sampling,
+                                        long long *per_entry)
+{
+    MultiCloud g;
+    if (cloud_multi_geometry(W, H, levels, fovea_levels, n, off_x, off_y, sampling, g) != UGSM_OK) return -1;
+    long long total = 0;
+    for (int e = 0; e < g.E; e++) {
+        CloudEntry en;
+        cloud_multi_entry(g, e, total, en);
+        if (per_entry) per_entry[e] = en.points;
+        total += en.points;
+    }
+    return total;
+}
 
 int ugsm_fovea_level_mapping(int W, int H, int levels, int fovea_levels, int off_x, int off_y, int src_level, int *left_margin,
                              int *upper_margin, float *scale)
@@ -3006,6 +3114,82 @@ int ugsm_point_cloud_fovea_all(ugsm_ctx *ctx, int slot, const float *d_stackx, c
     {
         Timer t(ctx, s, slot, KC_MISC, (double)sk.F * a.wc * a.hc);
         launch_point_cloud_stack(s->st, a, sk, P1, P2);
+    }
+    HIPCHK(ctx, hipGetLastError());
+    return UGSM_OK;
+}
+
+// The stacks of n windows of one pair as one cloud: the entries level-major, each without what the rule across windows leaves out
+// (cloud_multi_entry).  The table goes up on the slot's stream from a page-locked copy; nothing here waits for the stream unless a
+// buffer has to grow.
+int ugsm_point_cloud_fovea_multi(ugsm_ctx *ctx, int slot, int n, const float *const *d_stack, int W, int H, const int *off_x, const int *off_y,
+                                 const uint8_t *d_rgbL, int stride, const double *P1, const double *P2, const ugsm_cloud_params *p, void *d_points,
+                                 long long cap_points, long long *d_count, long long *d_entry_counts)
+{
+    if (!ctx || !p || !d_stack || n < 1 || n > UGSM_MAX_BATCH || ((uintptr_t)d_entry_counts & 7)) return UGSM_ERR_BAD_ARG;
+    for (int j = 0; j < n; j++)
+        if (!d_stack[j]) return UGSM_ERR_BAD_ARG;
+    MultiCloud g;
+    const int F = ctx->cfg.fovea_levels;
+    UCHK(cloud_multi_geometry(W, H, ctx->cfg.levels, F, n, off_x, off_y, p->sampling, g));
+    const size_t fn = (size_t)g.fw * g.fh, plane = (size_t)F * fn;
+    UCHK(cloud_args_ok(d_stack[0], d_stack[0] + plane, d_stack[0] + 2 * plane, d_rgbL, W, H, stride, ugsm_input_bytes_per_pixel(ctx->hooks.input_format), g.fw,
+                       g.fh, P1, P2, p, d_points, cap_points, d_count));
+    CloudArgs a = cloud_args(nullptr, nullptr, nullptr, d_rgbL, W, H, stride, g.fw, g.fh, p, d_points, cap_points, d_count);
+    Slot *s;
+    UCHK(get_slot(ctx, slot, &s));
+    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
+    a.wc = g.wc;
+    a.hc = g.hc;
+    a.nchunk = cloud_chunks(a.hc);
+    a.fmt = ctx->hooks.input_format;
+    a.cnt = nullptr;
+    const int E = g.E, strips = cloud_strips(a.wc);
+    if ((size_t)E > s->mc_tab_cap || (size_t)E > s->mc_tab_h_rows) {  // (an earlier call's kernels may still read the table, its upload the copies)
+        HIPCHK(ctx, hipStreamSynchronize(s->st));
+        UCHK(grow(ctx, s->mc_tab, s->mc_tab_cap, (size_t)E));
+        if ((size_t)E > s->mc_tab_h_rows) {
+            if (s->mc_tab_h) HIPCHK(ctx, hipHostFree(s->mc_tab_h));
+            s->mc_tab_h = nullptr;
+            s->mc_tab_h_rows = 0;
+            HIPCHK(ctx, hipHostMalloc((void **)&s->mc_tab_h, (size_t)Slot::kMcRing * E * sizeof(CloudEntry), hipHostMallocDefault));
+            s->mc_tab_h_rows = (size_t)E;
+            for (bool &set : s->mc_ev_set) set = false;
+        }
+    }
+    if (a.compact) {  // as point_cloud, over the E * wc virtual columns and E * strips virtual strips
+        const size_t cols = (size_t)E * a.wc, totals = cols + (size_t)E * strips, need = cols * a.nchunk + totals;
+        if (need > s->cloud_cap) HIPCHK(ctx, hipStreamSynchronize(s->st));
+        UCHK(grow(ctx, s->cloud_cnt, s->cloud_cap, need));
+        a.cnt = s->cloud_cnt;
+        HIPCHK(ctx, hipMemsetAsync(a.cnt + cols * a.nchunk, 0, totals * sizeof(unsigned), s->st));
+    }
+    const int turn = s->mc_next;
+    s->mc_next = (turn + 1) % Slot::kMcRing;
+    if (!s->mc_ev[turn]) HIPCHK(ctx, hipEventCreateWithFlags(&s->mc_ev[turn], hipEventDisableTiming));
+    if (s->mc_ev_set[turn]) HIPCHK(ctx, hipEventSynchronize(s->mc_ev[turn]));  // (the upload of the call kMcRing back: long done)
+    CloudEntry *const rows = s->mc_tab_h + (size_t)turn * s->mc_tab_h_rows;
+    const bool use_conf = a.compact && p->min_conf > -INFINITY;  // (the confidence planes are read by nothing else)
+    long long total = 0;
+    for (int e = 0; e < E; e++) {
+        cloud_multi_entry(g, e, total, rows[e]);
+        const int k = e / n, j = e - k * n;
+        rows[e].dx = d_stack[j] + (size_t)k * fn;
+        rows[e].dy = rows[e].dx + plane;
+        rows[e].conf = use_conf ? rows[e].dx + 2 * plane : nullptr;
+        total += rows[e].points;
+    }
+    HIPCHK(ctx, hipMemcpyAsync(s->mc_tab, rows, (size_t)E * sizeof(CloudEntry), hipMemcpyHostToDevice, s->st));
+    HIPCHK(ctx, hipEventRecord(s->mc_ev[turn], s->st));
+    s->mc_ev_set[turn] = true;
+    CloudMulti mu{};
+    mu.table = s->mc_tab;
+    mu.E = E;
+    mu.total = total;
+    mu.entry_counts = d_entry_counts;
+    {
+        Timer t(ctx, s, slot, KC_MISC, (double)E * a.wc * a.hc);
+        launch_point_cloud_multi(s->st, a, mu, P1, P2);
     }
     HIPCHK(ctx, hipGetLastError());
     return UGSM_OK;
