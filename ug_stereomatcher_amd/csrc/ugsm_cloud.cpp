@@ -1,0 +1,699 @@
+// ugsm_cloud.cpp -- row f-1 of the runtime: triangulation and the coloured point clouds (getPointCloud.cpp), on the slots of ugsm_runtime.cpp.
+// The fovea forms' geometry and the coverage rule of the merged clouds (host only), the slot-level entry points behind one preamble
+// (cloud_begin), and the queue's cloud calls (CtxHooks::cloud_submit / cloud_finish).  Every form's kernel is cloud_tile (ugsm_kernels_aux.hip).
+#include "ugsm_slot.hpp"
+
+#include <algorithm>
+#include <cmath>
+
+using namespace ugsm;
+
+namespace {
+
+// one launch (or a count launch and the cloud's) in the statistics' bracket, and what it reports
+template <class F>
+int timed_launch(ugsm_ctx *ctx, Slot *s, int slot, double points, F &&launch)
+{
+    {
+        Timer t(ctx, s, slot, KC_MISC, points);
+        launch();
+    }
+    HIPCHK(ctx, hipGetLastError());
+    return UGSM_OK;
+}
+
+// ugsm_fovea_level_mapping for every level of the stack: the reference's centred margins for any fovea_levels (its `scaled` is
+// F-1-k), moved by this build's window offset -- level k's clamped offset ex[k] (fovea_geometry), in level-0 pixels
+int fovea_level_mappings(int W, int H, int levels, int F, int off_x, int off_y, int *fw, int *fh, int *left, int *upper, float *scale)
+{
+    int w[UGSM_MAX_LEVELS], h[UGSM_MAX_LEVELS];
+    if (F < 2 || F > levels || levels > UGSM_MAX_LEVELS) return UGSM_ERR_BAD_ARG;
+    UCHK(level_dims(W, H, F, w, h));  // (only the stack's F levels enter: a cloud of a given stack does not ask whether the coarse levels below it exist)
+    FoveaGeom g;
+    fovea_geometry(w, h, F, off_x, off_y, g);
+    *fw = g.fw;
+    *fh = g.fh;
+    for (int k = 0; k < F; k++) {
+        const int ex = k < F - 1 ? g.ox[k] - (w[k] / 2 - g.fw / 2) : 0, ey = k < F - 1 ? g.oy[k] - (h[k] / 2 - g.fh / 2) : 0;
+        left[k] = w[0] / 2 - w[F - 1 - k] / 2 + (int)lrint(ex * pow(kScale, k));
+        upper[k] = h[0] / 2 - h[F - 1 - k] / 2 + (int)lrint(ey * pow(kScale, k));
+        scale[k] = powf((float)1.41421356237309504880, (float)k);  // as ugsm_fovea_mapping for destination level 0
+    }
+    return UGSM_OK;
+}
+
+// The coverage rule along one axis (include/ugsm.h): pixel i of level k, at x1 = (float)m + (float)i * sc, is covered when
+// x1 >= (float)m_fine && x1 + sc <= (float)m_fine + (float)n * sc_fine, every operation in binary32.  Monotone in i, so the covered
+// pixels are one interval [i0, i1); of the sampled grid (pixel = index * s) that is [c0, c1).  x1 never falls as i grows (i is exact in
+// binary32, and a rounded product and a rounded sum keep the order of their operands), so the first test turns true once and the second
+// false once: two bisections, the same interval a scan over the pixels finds (the merged cloud of several windows asks for up to 31
+// rectangles for each of up to 97 entries per call).
+void covered_interval(int n, int m, float sc, int m_fine, float sc_fine, int s, int *c0, int *c1)
+{
+    const float lo = (float)m_fine, hi = (float)m_fine + (float)n * sc_fine;
+    auto first = [&](int from, auto test) {  // the first i in [from, n) that passes a test which stays passed; n: none
+        int a = from, b = n;
+        while (a < b) {
+            const int mid = a + (b - a) / 2;
+            if (test((float)m + (float)mid * sc)) b = mid;
+            else a = mid + 1;
+        }
+        return a;
+    };
+    int i0 = first(0, [&](float x1) { return x1 >= lo; });
+    int i1 = first(i0, [&](float x1) { return !(x1 + sc <= hi); });
+    if (i1 <= i0) i0 = i1 = n;  // (nothing covered)
+    *c0 = (i0 + s - 1) / s;
+    *c1 = (i1 + s - 1) / s;
+    if (*c1 < *c0) *c1 = *c0;
+}
+
+// ---- the merged cloud of several windows of one pair (ugsm_point_cloud_fovea_multi; the rule across windows: include/ugsm.h) ----------
+struct MultiCloud {
+    int n, F, E, fw, fh, wc, hc, s;
+    int left[UGSM_MAX_BATCH][UGSM_MAX_LEVELS], upper[UGSM_MAX_BATCH][UGSM_MAX_LEVELS];
+    float scale[UGSM_MAX_LEVELS];
+};
+
+int cloud_multi_geometry(int W, int H, int levels, int F, int n, const int *off_x, const int *off_y, int sampling, MultiCloud &g)
+{
+    if (n < 1 || n > UGSM_MAX_BATCH || sampling < 1) return UGSM_ERR_BAD_ARG;
+    for (int j = 0; j < n; j++)
+        UCHK(fovea_level_mappings(W, H, levels, F, off_x ? off_x[j] : 0, off_y ? off_y[j] : 0, &g.fw, &g.fh, g.left[j], g.upper[j], g.scale));
+    g.n = n;
+    g.F = F;
+    g.E = (F - 1) * n + 1;
+    g.s = sampling;
+    g.wc = (g.fw + sampling - 1) / sampling;
+    g.hc = (g.fh + sampling - 1) / sampling;
+    return UGSM_OK;
+}
+
+// Entry e's row of the kernel's table, its planes apart: the mapping, the rectangles the entry leaves out -- (a) inside level k-1 of any
+// window, (b) inside level k of a higher-numbered window; each a column interval times a row interval (covered_interval) -- the column
+// segments between the rectangles' edges, and the entry's dense records.  `first`: the records of the entries before it.
+void cloud_multi_entry(const MultiCloud &g, int e, long long first, CloudEntry &en)
+{
+    const int k = e / g.n, j = e - k * g.n;  // (the last entry: level F-1 of window 0)
+    en = CloudEntry{};
+    en.left_margin = g.left[j][k];
+    en.upper_margin = g.upper[j][k];
+    en.scale = g.scale[k];
+    auto add = [&](int i, int m) {
+        CloudRect q;
+        covered_interval(g.fw, g.left[j][k], g.scale[k], g.left[i][m], g.scale[m], g.s, &q.cx0, &q.cx1);
+        covered_interval(g.fh, g.upper[j][k], g.scale[k], g.upper[i][m], g.scale[m], g.s, &q.cy0, &q.cy1);
+        if (q.cx0 < q.cx1 && q.cy0 < q.cy1 && en.nrect < kCloudMaxRects) en.rect[en.nrect++] = q;
+    };
+    if (k >= 1)
+        for (int i = 0; i < g.n; i++) add(i, k - 1);
+    if (k <= g.F - 2)
+        for (int i = j + 1; i < g.n; i++) add(i, k);
+    // the segments: between two neighbouring edges the same rectangles hold every column, so every column keeps the same number of rows
+    int xs[kCloudMaxSegs + 1], nx = 0;
+    xs[nx++] = 0;
+    for (int i = 0; i < en.nrect; i++)
+        for (int x : {en.rect[i].cx0, en.rect[i].cx1})
+            if (x > 0 && x < g.wc) xs[nx++] = x;
+    std::sort(xs, xs + nx);
+    nx = (int)(std::unique(xs, xs + nx) - xs);
+    long long records = 0;
+    for (int sg = 0; sg < nx; sg++) {
+        std::pair<int, int> rows[kCloudMaxRects];
+        int nr = 0;
+        for (int i = 0; i < en.nrect; i++)
+            if (en.rect[i].cx0 <= xs[sg] && xs[sg] < en.rect[i].cx1) rows[nr++] = {en.rect[i].cy0, en.rect[i].cy1};
+        std::sort(rows, rows + nr);
+        int out = 0, reach = 0;  // the length of the union of the row intervals
+        for (int i = 0; i < nr; i++) {
+            out += std::max(rows[i].second - std::max(rows[i].first, reach), 0);
+            reach = std::max(reach, rows[i].second);
+        }
+        en.seg_x[sg] = xs[sg];
+        en.seg_rows[sg] = g.hc - out;
+        en.seg_first[sg] = (unsigned)records;
+        records += (long long)((sg + 1 < nx ? xs[sg + 1] : g.wc) - xs[sg]) * (g.hc - out);
+    }
+    en.nseg = nx;
+    en.first = first;
+    en.points = records;
+}
+
+// The table of the whole stack's cloud (ugsm_point_cloud_fovea_all): each level's planes, mapping, covered rectangle and dense records.  It is
+// the merged cloud of ONE window: entry k is level k, and what it leaves out is at most one rectangle -- the part inside level k-1.
+int cloud_stack_table(int W, int H, int levels, int F, int off_x, int off_y, int sampling, CloudStack &sk, int *fw_out, int *fh_out)
+{
+    MultiCloud g;
+    UCHK(cloud_multi_geometry(W, H, levels, F, 1, &off_x, &off_y, sampling, g));
+    sk = CloudStack{};
+    sk.F = F;
+    sk.strips = cloud_strips(g.wc);
+    long long first = 0;
+    for (int k = 0; k < F; k++) {
+        CloudEntry en;
+        cloud_multi_entry(g, k, first, en);
+        CloudLevel &lv = sk.lv[k];
+        lv.plane = (long long)k * g.fw * g.fh;
+        lv.left_margin = en.left_margin;
+        lv.upper_margin = en.upper_margin;
+        lv.scale = en.scale;
+        const CloudRect out = en.nrect ? en.rect[0] : CloudRect{};
+        lv.cx0 = out.cx0;
+        lv.cx1 = out.cx1;
+        lv.cy0 = out.cy0;
+        lv.cy1 = out.cy1;
+        lv.first = first;
+        lv.points = en.points;
+        first += en.points;
+    }
+    if (fw_out) *fw_out = g.fw;
+    if (fh_out) *fh_out = g.fh;
+    return UGSM_OK;
+}
+
+// the checks every entry point shares (no device needed); pw x ph: the planes the points come from; resized: the resized forms, which
+// take no sampling (p->sampling 1) and a factor in (0, 1] that leaves both sides at least 1
+int cloud_args_ok(const ugsm_ctx *ctx, const float *dx, const float *dy, const float *conf, const uint8_t *rgb, int W, int H, int stride, int pw,
+                  int ph, const double *P1, const double *P2, const ugsm_cloud_params *p, const void *points, long long cap, const long long *count,
+                  bool resized = false, float factor = 1.0f)
+{
+    if (!ctx || !dx || !dy || !rgb || !P1 || !P2 || !p || !points || !count) return UGSM_ERR_BAD_ARG;
+    if (W < 1 || H < 1 || pw < 1 || ph < 1 || (long long)W * H > kMaxPixels || (long long)pw * ph > kMaxPixels) return UGSM_ERR_BAD_ARG;
+    if (stride < input_row_bytes(ctx, W) || p->sampling < 1 || (p->format != UGSM_CLOUD_PCL32 && p->format != UGSM_CLOUD_XYZRGB16)) return UGSM_ERR_BAD_ARG;
+    if (std::isnan(p->min_conf) || std::isnan(p->z_min) || std::isnan(p->z_max) || p->z_min > p->z_max) return UGSM_ERR_BAD_ARG;
+    if (!conf && p->min_conf > -INFINITY) return UGSM_ERR_BAD_ARG;  // (a confidence test without a confidence plane)
+    if (cap < 0 || ((uintptr_t)points & 15) || ((uintptr_t)count & 7)) return UGSM_ERR_BAD_ARG;
+    if (resized && (p->sampling != 1 || ugsm_resized_cloud_points(pw, ph, factor) < 1)) return UGSM_ERR_BAD_ARG;
+    return UGSM_OK;
+}
+
+// the CloudArgs of a call whose points come from the pw x ph planes dx, dy, conf (conf is only read by a compact cloud)
+CloudArgs cloud_args(const float *dx, const float *dy, const float *conf, const uint8_t *rgb, int W, int H, int stride, int pw, int ph,
+                     const ugsm_cloud_params *p, void *points, long long cap, long long *count)
+{
+    CloudArgs a{};
+    a.dx = dx;
+    a.dy = dy;
+    a.conf = p->compact ? conf : nullptr;
+    a.pw = pw;
+    a.ph = ph;
+    a.rgb = rgb;
+    a.W = W;
+    a.H = H;
+    a.stride = stride;
+    a.s = p->sampling;
+    a.format = p->format;
+    a.compact = p->compact != 0;
+    a.min_conf = p->min_conf;
+    a.z_min = p->z_min;
+    a.z_max = p->z_max;
+    a.points = points;
+    a.cap = cap;
+    a.count = count;
+    return a;
+}
+
+// the resized map: (int)(pw * factor) x (int)(ph * factor) points and cv::resize's scales (resize.cpp: inv_scale = (double)dsize / ssize,
+// scale = 1. / inv_scale)
+CloudResize resize_args(CloudArgs &a, float factor, int colour_mapped)
+{
+    a.wc = (int)((float)a.pw * factor);
+    a.hc = (int)((float)a.ph * factor);
+    CloudResize rz{};
+    rz.scale_x = 1. / ((double)a.wc / a.pw);
+    rz.scale_y = 1. / ((double)a.hc / a.ph);
+    rz.factor = factor;
+    rz.same_size = a.wc == a.pw && a.hc == a.ph;
+    rz.colour_mapped = colour_mapped;
+    return rz;
+}
+
+// The words of a compact cloud's count buffer (CloudArgs.cnt) over `entries` virtual grids of wc columns -- the levels of a stack, the entries
+// of a merged cloud: the entries' (column, chunk) counts, then their column totals and strip totals.
+size_t cloud_cnt_words(int entries, int wc, int nchunk) { return (size_t)entries * ((size_t)wc * nchunk + wc + cloud_strips(wc)); }
+
+// What every slot-level cloud does before its launch: it takes the slot and sets the device, fills in the sampled grid (unless the resized
+// forms have: resize_args), its chunks and the input format and, for a compact cloud, makes the slot's count buffer hold `entries`
+// virtual grids and zeroes their totals on the slot's stream.  table_rows (the merged cloud of several windows): before that, room for so
+// many rows in the device table and in the page-locked copies it goes up from.
+int cloud_begin(ugsm_ctx *ctx, int slot, CloudArgs &a, int entries, Slot **out, size_t table_rows = 0)
+{
+    UCHK(get_slot(ctx, slot, out));
+    Slot &s = **out;
+    SlotCloud &c = s.cloud;
+    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
+    if (!a.wc) {  // (the resized forms' grid is resize_args')
+        a.wc = (a.pw + a.s - 1) / a.s;
+        a.hc = (a.ph + a.s - 1) / a.s;
+    }
+    a.nchunk = cloud_chunks(a.hc);
+    a.fmt = ctx->hooks.input_format;
+    a.cnt = nullptr;
+    if (table_rows > c.mc_tab_cap || table_rows > c.mc_tab_h_rows) {  // (an earlier call's kernels may still read the table, its upload the copies)
+        HIPCHK(ctx, hipStreamSynchronize(s.st));
+        UCHK(grow(ctx, c.mc_tab, c.mc_tab_cap, table_rows));
+        if (table_rows > c.mc_tab_h_rows) {
+            if (c.mc_tab_h) HIPCHK(ctx, hipHostFree(c.mc_tab_h));
+            c.mc_tab_h = nullptr;
+            c.mc_tab_h_rows = 0;
+            HIPCHK(ctx, hipHostMalloc((void **)&c.mc_tab_h, SlotCloud::kMcRing * table_rows * sizeof(CloudEntry), hipHostMallocDefault));
+            c.mc_tab_h_rows = table_rows;
+            for (bool &set : c.mc_ev_set) set = false;
+        }
+    }
+    if (!a.compact) return UGSM_OK;
+    const size_t counts = (size_t)entries * a.wc * a.nchunk, need = cloud_cnt_words(entries, a.wc, a.nchunk);
+    if (need > c.cnt_cap) HIPCHK(ctx, hipStreamSynchronize(s.st));  // (the buffer being replaced may still be read by an earlier cloud)
+    UCHK(grow(ctx, c.cnt, c.cnt_cap, need));
+    a.cnt = c.cnt;
+    HIPCHK(ctx, hipMemsetAsync(a.cnt + counts, 0, (need - counts) * sizeof(unsigned), s.st));  // (the totals)
+    return UGSM_OK;
+}
+
+int point_cloud(ugsm_ctx *ctx, int slot, CloudArgs &a, bool fovea, const double *P1, const double *P2, const CloudResize *rz = nullptr)
+{
+    Slot *s;
+    UCHK(cloud_begin(ctx, slot, a, 1, &s));
+    return timed_launch(ctx, s, slot, (double)a.wc * a.hc, [&] { launch_point_cloud(s->st, a, fovea, P1, P2, rz); });
+}
+
+// the foveated forms' planes (level src_level of the stacks) and mapping (ugsm_fovea_mapping)
+int fovea_cloud_args(CloudArgs &a, const float *stackx, const float *stacky, const float *stackc, int fovW, int fovH, int src_level,
+                     int left_margin, int upper_margin, float scale, const uint8_t *rgb, int W, int H, int stride, const ugsm_cloud_params *p,
+                     void *points, long long cap, long long *count)
+{
+    if (src_level < 0 || src_level >= UGSM_MAX_LEVELS || !std::isfinite(scale)) return UGSM_ERR_BAD_ARG;
+    const size_t lvl = (size_t)src_level * fovW * fovH;
+    a = cloud_args(stackx + lvl, stacky + lvl, stackc ? stackc + lvl : nullptr, rgb, W, H, stride, fovW, fovH, p, points, cap, count);
+    a.left_margin = left_margin;
+    a.upper_margin = upper_margin;
+    a.scale = scale;
+    return UGSM_OK;
+}
+
+constexpr size_t kCqWords = 1 + UGSM_MAX_LEVELS;  // a managed pair's count words: the count, the level counts
+
+int queue_cloud_launch(ugsm_ctx *ctx, Slot &s, int si, int b0, int n, bool stack, const ugsm_queue_cloud *spec)
+{
+    const CloudPair &shape = s.cloud.cq_tab_h[b0];
+    return timed_launch(ctx, &s, si, (double)n * (stack ? shape.sk.F : 1) * shape.a.wc * shape.a.hc,
+                        [&] { launch_point_cloud_batch(s.st, s.cloud.cq_tab + b0, n, shape, stack, spec->P1, spec->P2); });
+}
+
+}  // namespace
+
+extern "C" {
+
+int ugsm_triangulate(ugsm_ctx *ctx, int slot, const float *d_dispx, const float *d_dispy, int W, int H, const double *P1, const double *P2,
+                     float *d_xyz)
+{
+    Slot *s;
+    UCHK(get_slot(ctx, slot, &s));
+    if (!d_dispx || !d_dispy || !P1 || !P2 || !d_xyz || W < 1 || H < 1) return UGSM_ERR_BAD_ARG;
+    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
+    return timed_launch(ctx, s, slot, (double)W * H, [&] { launch_triangulate(s->st, d_dispx, d_dispy, W, H, P1, P2, d_xyz); });
+}
+
+// CdynamicCalibration::left_marginOf_in / upper_marginOf_in / mapXcoord (getPointCloud.cpp:387-484)
+int ugsm_fovea_mapping(int W, int H, int src_level, int dest_level, int *left_margin, int *upper_margin, float *scale)
+{
+    if (!left_margin || !upper_margin || !scale || W < 1 || H < 1) return UGSM_ERR_BAD_ARG;
+    int scaled = 6 - src_level;  // :435 (the reference hard-codes its 7 fovea levels here)
+    if (src_level < dest_level) scaled = src_level + dest_level;
+    if (scaled < 0 || scaled >= 15 || dest_level < 0 || dest_level >= 15 || src_level < 0) return UGSM_ERR_BAD_ARG;
+    int w[16], h[16];
+    w[0] = W;
+    h[0] = H;
+    for (int i = 0; i < 14; i++) {  // :441-443
+        w[i + 1] = (int)(w[i] / kScale);
+        h[i + 1] = (int)(h[i] / kScale);
+    }
+    *left_margin = w[dest_level] / 2 - w[scaled] / 2;
+    *upper_margin = h[dest_level] / 2 - h[scaled] / 2;
+    const float root = (src_level < dest_level) ? (float)0.70710678118654752440 : (float)1.41421356237309504880;
+    *scale = powf(root, (float)std::abs(src_level - dest_level));  // pow(float, float), :397
+    return UGSM_OK;
+}
+
+long long ugsm_fovea_multi_cloud_points(int W, int H, int levels, int fovea_levels, int n, const int *off_x, const int *off_y, int sampling,
+                                        long long *per_entry)
+{
+    MultiCloud g;
+    if (cloud_multi_geometry(W, H, levels, fovea_levels, n, off_x, off_y, sampling, g) != UGSM_OK) return -1;
+    long long total = 0;
+    for (int e = 0; e < g.E; e++) {
+        CloudEntry en;
+        cloud_multi_entry(g, e, total, en);
+        if (per_entry) per_entry[e] = en.points;
+        total += en.points;
+    }
+    return total;
+}
+
+int ugsm_fovea_level_mapping(int W, int H, int levels, int fovea_levels, int off_x, int off_y, int src_level, int *left_margin,
+                             int *upper_margin, float *scale)
+{
+    if (!left_margin || !upper_margin || !scale || src_level < 0 || src_level >= fovea_levels) return UGSM_ERR_BAD_ARG;
+    int left[UGSM_MAX_LEVELS], upper[UGSM_MAX_LEVELS], fw, fh;
+    float sc[UGSM_MAX_LEVELS];
+    if (fovea_level_mappings(W, H, levels, fovea_levels, off_x, off_y, &fw, &fh, left, upper, sc) != UGSM_OK) return UGSM_ERR_BAD_ARG;
+    *left_margin = left[src_level];
+    *upper_margin = upper[src_level];
+    *scale = sc[src_level];
+    return UGSM_OK;
+}
+
+long long ugsm_fovea_cloud_points(int W, int H, int levels, int fovea_levels, int off_x, int off_y, int sampling, long long *per_level)
+{
+    return ugsm_fovea_multi_cloud_points(W, H, levels, fovea_levels, 1, &off_x, &off_y, sampling, per_level);  // (one window: entry k is level k)
+}
+
+int ugsm_triangulate_fovea(ugsm_ctx *ctx, int slot, const float *d_stackx, const float *d_stacky, int fovW, int fovH, int src_level,
+                           int left_margin, int upper_margin, float scale, const double *P1, const double *P2, float *d_xyz)
+{
+    Slot *s;
+    UCHK(get_slot(ctx, slot, &s));
+    if (!d_stackx || !d_stacky || !P1 || !P2 || !d_xyz || fovW < 1 || fovH < 1 || src_level < 0) return UGSM_ERR_BAD_ARG;
+    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
+    return timed_launch(ctx, s, slot, (double)fovW * fovH,
+                        [&] { launch_triangulate_fovea(s->st, d_stackx, d_stacky, fovW, fovH, src_level, left_margin, upper_margin, scale, P1, P2, d_xyz); });
+}
+
+// ---- row f-1, the coloured point cloud (getPointCloud.cpp doReconstructionRGB[_FOV], :615-722) ----------------------------------------
+
+void ugsm_default_cloud_params(ugsm_cloud_params *p)
+{
+    if (!p) return;
+    p->sampling = 1;
+    p->format = UGSM_CLOUD_PCL32;
+    p->compact = 0;
+    p->min_conf = -INFINITY;
+    p->z_min = -INFINITY;
+    p->z_max = INFINITY;
+}
+
+long long ugsm_cloud_points(int W, int H, int sampling)
+{
+    if (W < 1 || H < 1 || sampling < 1) return -1;
+    return (long long)((W + sampling - 1) / sampling) * ((H + sampling - 1) / sampling);
+}
+
+long long ugsm_resized_cloud_points(int W, int H, float factor)
+{
+    if (W < 1 || H < 1 || !(factor > 0.0f && factor <= 1.0f)) return -1;
+    const int dw = (int)((float)W * factor), dh = (int)((float)H * factor);  // cv::Size(W * f, H * f): float products, truncated
+    if (dw < 1 || dh < 1) return -1;
+    return (long long)dw * dh;
+}
+
+int ugsm_point_cloud(ugsm_ctx *ctx, int slot, const float *d_dispx, const float *d_dispy, const float *d_conf, const uint8_t *d_rgbL, int W, int H,
+                     int stride, const double *P1, const double *P2, const ugsm_cloud_params *p, void *d_points, long long cap_points,
+                     long long *d_count)
+{
+    UCHK(cloud_args_ok(ctx, d_dispx, d_dispy, d_conf, d_rgbL, W, H, stride, W, H, P1, P2, p, d_points, cap_points, d_count));
+    CloudArgs a = cloud_args(d_dispx, d_dispy, d_conf, d_rgbL, W, H, stride, W, H, p, d_points, cap_points, d_count);
+    return point_cloud(ctx, slot, a, false, P1, P2);
+}
+
+int ugsm_point_cloud_fovea(ugsm_ctx *ctx, int slot, const float *d_stackx, const float *d_stacky, const float *d_stackc, int fovW, int fovH,
+                           int src_level, int left_margin, int upper_margin, float scale, const uint8_t *d_rgbL, int W, int H, int stride,
+                           const double *P1, const double *P2, const ugsm_cloud_params *p, void *d_points, long long cap_points, long long *d_count)
+{
+    UCHK(cloud_args_ok(ctx, d_stackx, d_stacky, d_stackc, d_rgbL, W, H, stride, fovW, fovH, P1, P2, p, d_points, cap_points, d_count));
+    CloudArgs a;
+    UCHK(fovea_cloud_args(a, d_stackx, d_stacky, d_stackc, fovW, fovH, src_level, left_margin, upper_margin, scale, d_rgbL, W, H, stride, p,
+                          d_points, cap_points, d_count));
+    return point_cloud(ctx, slot, a, true, P1, P2);
+}
+
+// The whole stack as one cloud: level 0, then 1 .. F-1, each without the points the finer level already covers (cloud_stack_table)
+int ugsm_point_cloud_fovea_all(ugsm_ctx *ctx, int slot, const float *d_stackx, const float *d_stacky, const float *d_stackc, int W, int H,
+                               int off_x, int off_y, const uint8_t *d_rgbL, int stride, const double *P1, const double *P2,
+                               const ugsm_cloud_params *p, void *d_points, long long cap_points, long long *d_count, long long *d_level_counts)
+{
+    if (!ctx || !p || ((uintptr_t)d_level_counts & 7)) return UGSM_ERR_BAD_ARG;
+    CloudStack sk;
+    int fw, fh;
+    UCHK(cloud_stack_table(W, H, ctx->cfg.levels, ctx->cfg.fovea_levels, off_x, off_y, p->sampling, sk, &fw, &fh));
+    UCHK(cloud_args_ok(ctx, d_stackx, d_stacky, d_stackc, d_rgbL, W, H, stride, fw, fh, P1, P2, p, d_points, cap_points, d_count));
+    sk.level_counts = d_level_counts;
+    CloudArgs a = cloud_args(d_stackx, d_stacky, d_stackc, d_rgbL, W, H, stride, fw, fh, p, d_points, cap_points, d_count);
+    Slot *s;
+    UCHK(cloud_begin(ctx, slot, a, sk.F, &s));
+    return timed_launch(ctx, s, slot, (double)sk.F * a.wc * a.hc, [&] { launch_point_cloud_stack(s->st, a, sk, P1, P2); });
+}
+
+// The stacks of n windows of one pair as one cloud: the entries level-major, each without what the rule across windows leaves out
+// (cloud_multi_entry).  The table goes up on the slot's stream from a page-locked copy; nothing here waits for the stream unless a
+// buffer has to grow.
+int ugsm_point_cloud_fovea_multi(ugsm_ctx *ctx, int slot, int n, const float *const *d_stack, int W, int H, const int *off_x, const int *off_y,
+                                 const uint8_t *d_rgbL, int stride, const double *P1, const double *P2, const ugsm_cloud_params *p, void *d_points,
+                                 long long cap_points, long long *d_count, long long *d_entry_counts)
+{
+    if (!ctx || !p || !d_stack || n < 1 || n > UGSM_MAX_BATCH || ((uintptr_t)d_entry_counts & 7)) return UGSM_ERR_BAD_ARG;
+    for (int j = 0; j < n; j++)
+        if (!d_stack[j]) return UGSM_ERR_BAD_ARG;
+    MultiCloud g;
+    const int F = ctx->cfg.fovea_levels;
+    UCHK(cloud_multi_geometry(W, H, ctx->cfg.levels, F, n, off_x, off_y, p->sampling, g));
+    const size_t fn = (size_t)g.fw * g.fh, plane = (size_t)F * fn;
+    UCHK(cloud_args_ok(ctx, d_stack[0], d_stack[0] + plane, d_stack[0] + 2 * plane, d_rgbL, W, H, stride, g.fw, g.fh, P1, P2, p, d_points, cap_points, d_count));
+    CloudArgs a = cloud_args(nullptr, nullptr, nullptr, d_rgbL, W, H, stride, g.fw, g.fh, p, d_points, cap_points, d_count);
+    Slot *s;
+    const int E = g.E;
+    UCHK(cloud_begin(ctx, slot, a, E, &s, (size_t)E));
+    SlotCloud &c = s->cloud;
+    const int turn = c.mc_next;
+    c.mc_next = (turn + 1) % SlotCloud::kMcRing;
+    if (!c.mc_ev[turn]) HIPCHK(ctx, hipEventCreateWithFlags(&c.mc_ev[turn], hipEventDisableTiming));
+    if (c.mc_ev_set[turn]) HIPCHK(ctx, hipEventSynchronize(c.mc_ev[turn]));  // (the upload of the call kMcRing back: long done)
+    CloudEntry *const rows = c.mc_tab_h + (size_t)turn * c.mc_tab_h_rows;
+    const bool use_conf = a.compact && p->min_conf > -INFINITY;  // (the confidence planes are read by nothing else)
+    long long total = 0;
+    for (int e = 0; e < E; e++) {
+        cloud_multi_entry(g, e, total, rows[e]);
+        const int k = e / n, j = e - k * n;
+        rows[e].dx = d_stack[j] + (size_t)k * fn;
+        rows[e].dy = rows[e].dx + plane;
+        rows[e].conf = use_conf ? rows[e].dx + 2 * plane : nullptr;
+        total += rows[e].points;
+    }
+    HIPCHK(ctx, hipMemcpyAsync(c.mc_tab, rows, (size_t)E * sizeof(CloudEntry), hipMemcpyHostToDevice, s->st));
+    HIPCHK(ctx, hipEventRecord(c.mc_ev[turn], s->st));
+    c.mc_ev_set[turn] = true;
+    const CloudMulti mu{c.mc_tab, E, total, d_entry_counts};
+    return timed_launch(ctx, s, slot, (double)E * a.wc * a.hc, [&] { launch_point_cloud_multi(s->st, a, mu, P1, P2); });
+}
+
+// ---- row f-1, the resized cloud (getPointCloud.cpp doReconstruction_resized / doReconstructionFOV_resized, :724-884) ----------------
+
+int ugsm_point_cloud_resized(ugsm_ctx *ctx, int slot, const float *d_dispx, const float *d_dispy, const float *d_conf, const uint8_t *d_rgbL,
+                             int W, int H, int stride, const double *P1, const double *P2, float factor, const ugsm_cloud_params *p,
+                             void *d_points, long long cap_points, long long *d_count)
+{
+    UCHK(cloud_args_ok(ctx, d_dispx, d_dispy, d_conf, d_rgbL, W, H, stride, W, H, P1, P2, p, d_points, cap_points, d_count, true, factor));
+    CloudArgs a = cloud_args(d_dispx, d_dispy, d_conf, d_rgbL, W, H, stride, W, H, p, d_points, cap_points, d_count);
+    const CloudResize rz = resize_args(a, factor, 0);
+    return point_cloud(ctx, slot, a, false, P1, P2, &rz);
+}
+
+int ugsm_point_cloud_resized_fovea(ugsm_ctx *ctx, int slot, const float *d_stackx, const float *d_stacky, const float *d_stackc, int fovW,
+                                   int fovH, int src_level, int left_margin, int upper_margin, float scale, const uint8_t *d_rgbL, int W, int H,
+                                   int stride, const double *P1, const double *P2, float factor, int colour_mapped, const ugsm_cloud_params *p,
+                                   void *d_points, long long cap_points, long long *d_count)
+{
+    UCHK(cloud_args_ok(ctx, d_stackx, d_stacky, d_stackc, d_rgbL, W, H, stride, fovW, fovH, P1, P2, p, d_points, cap_points, d_count, true, factor));
+    if (colour_mapped != 0 && colour_mapped != 1) return UGSM_ERR_BAD_ARG;
+    CloudArgs a;
+    UCHK(fovea_cloud_args(a, d_stackx, d_stacky, d_stackc, fovW, fovH, src_level, left_margin, upper_margin, scale, d_rgbL, W, H, stride, p,
+                          d_points, cap_points, d_count));
+    const CloudResize rz = resize_args(a, factor, colour_mapped);
+    return point_cloud(ctx, slot, a, true, P1, P2, &rz);
+}
+
+}  // extern "C"
+
+// ---- the cloud from the queue (ugsm_enqueue_*_cloud*): a call of n pairs and their clouds -------------------------------------------
+// The match goes onto the slot's stream as the batch entry points above put it there (the same helpers in the same order, so the planes are
+// the same bits); the clouds follow on the same stream.  A call the matcher runs in lockstep gets ONE cloud launch for its pairs (compact:
+// two; launch_point_cloud_batch), from a table uploaded on the stream ahead of it.  A call the matcher runs pair by pair (one pair; the
+// full-mode LR check, early exit) gets pair b's cloud behind pair b's match: a managed call of that kind reuses the slot's image and plane
+// buffers for every pair.  So does a call whose pairs each evaluate more than kBatchMaxPixels sampled points -- the size above which the
+// matcher's own levels go pair by pair, because one pair's launch fills the chip many times over and a batch index buys nothing.
+int ugsm::queue_cloud_submit(ugsm_ctx *ctx, int slot, const CloudCall *call)
+{
+    Slot *s;
+    UCHK(get_slot(ctx, slot, &s));
+    SlotCloud &c = s->cloud;
+    if (!call || !call->spec || call->n < 1 || call->n > UGSM_MAX_BATCH) return UGSM_ERR_BAD_ARG;
+    const ugsm_queue_cloud &spec = *call->spec;
+    const ugsm_cloud_params &p = spec.params;
+    const int n = call->n, W = call->W, H = call->H, stride = call->stride, F = ctx->cfg.fovea_levels;
+    const bool fovea = call->fovea != 0, managed = call->managed != 0, planes = managed && spec.want_planes != 0;
+    if (fovea && F < 2) return UGSM_ERR_BAD_ARG;
+    if (W < 1 || H < 1) return UGSM_ERR_BAD_ARG;
+    if (stride < input_row_bytes(ctx, W)) return UGSM_ERR_SIZE_MISMATCH;
+    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
+    c.cq_n = 0;
+    const bool by_pair = n == 1 || (fovea ? fovea_batch_runs_pair_by_pair(ctx) : batch_runs_pair_by_pair(ctx));
+    int fw = W, fh = H;
+    if (fovea) UCHK(ugsm_fovea_dims(W, H, ctx->cfg.levels, F, &fw, &fh));
+    const size_t px = (size_t)W * H, fn = (size_t)fw * fh, stackn = (size_t)F * fn;
+    const size_t plane = fovea ? stackn : px;  // floats per result plane: the pair's result is three of them
+    const int step = p.format == UGSM_CLOUD_PCL32 ? 32 : 16;
+
+    // 1. where every pair's images, state and result lie on the device
+    const uint8_t *dL[UGSM_MAX_BATCH], *dR[UGSM_MAX_BATCH];
+    float *state[UGSM_MAX_BATCH], *res[UGSM_MAX_BATCH];
+    const size_t st_per = fovea ? ((3 * fn + 63) & ~(size_t)63) : 0, res_per = (3 * plane + 63) & ~(size_t)63;
+    if (managed) {
+        // the slot's uploads and hout: [states][results], one of each for a call that runs pair by pair, n otherwise
+        const int copies = by_pair ? 1 : n;
+        const size_t img = ((size_t)stride * H + 255) & ~(size_t)255;
+        if (img * copies > s->rgb_cap) {
+            size_t c = s->rgb_cap;
+            UCHK(grow(ctx, s->rgbL, c, img * copies));
+            UCHK(grow(ctx, s->rgbR, s->rgb_cap, img * copies));
+        }
+        UCHK(grow(ctx, s->hout, s->hout_cap, std::max(copies * (st_per + res_per), s->hout_cap)));
+        for (int b = 0; b < n; b++) {
+            const int k = by_pair ? 0 : b;
+            dL[b] = s->rgbL + k * img;
+            dR[b] = s->rgbR + k * img;
+            state[b] = s->hout + k * st_per;
+            res[b] = s->hout + copies * st_per + k * res_per;
+        }
+    } else {
+        UCHK(grow(ctx, s->hout, s->hout_cap, std::max(st_per * n, s->hout_cap)));
+        for (int b = 0; b < n; b++) {
+            if (!call->job[b].L || !call->job[b].R || !call->job[b].out) return UGSM_ERR_BAD_ARG;
+            dL[b] = call->job[b].L;
+            dR[b] = call->job[b].R;
+            state[b] = s->hout + (by_pair ? 0 : b * st_per);
+            res[b] = call->job[b].out;
+        }
+    }
+
+    // 2. the table: every pair's cloud arguments
+    if ((size_t)n > c.cq_tab_cap) {
+        if (c.cq_tab_h) HIPCHK(ctx, hipHostFree(c.cq_tab_h));
+        c.cq_tab_h = nullptr;
+        UCHK(grow(ctx, c.cq_tab, c.cq_tab_cap, (size_t)kMaxBatch));
+        HIPCHK(ctx, hipHostMalloc((void **)&c.cq_tab_h, kMaxBatch * sizeof(CloudPair), hipHostMallocDefault));
+    }
+    CloudStack sk[UGSM_MAX_BATCH];
+    long long dense[UGSM_MAX_BATCH], max_cap = 0;
+    int ox[UGSM_MAX_BATCH], oy[UGSM_MAX_BATCH];  // (foveated calls: the pairs' window offsets)
+    for (int b = 0; b < n; b++) {
+        ox[b] = call->job[b].off_x;
+        oy[b] = call->job[b].off_y;
+        if (fovea) {
+            UCHK(cloud_stack_table(W, H, ctx->cfg.levels, F, ox[b], oy[b], p.sampling, sk[b], nullptr, nullptr));
+            dense[b] = sk[b].lv[F - 1].first + sk[b].lv[F - 1].points;
+        } else {
+            dense[b] = ugsm_cloud_points(W, H, p.sampling);
+        }
+        c.cq_cap[b] = managed ? (spec.max_points > 0 ? std::min(spec.max_points, dense[b]) : dense[b]) : call->job[b].cap;
+        max_cap = std::max(max_cap, c.cq_cap[b]);
+    }
+    if (managed) {
+        c.cq_stride = (size_t)max_cap * step;
+        UCHK(grow(ctx, c.cq_pts, c.cq_pts_cap, std::max(c.cq_stride * n, (size_t)16)));
+        UCHK(grow(ctx, c.cq_words, c.cq_words_cap, kMaxBatch * kCqWords));
+        if (!c.cq_words_h) HIPCHK(ctx, hipHostMalloc((void **)&c.cq_words_h, kMaxBatch * kCqWords * sizeof(long long), hipHostMallocDefault));
+    }
+    const int wc = (fw + p.sampling - 1) / p.sampling, hc = (fh + p.sampling - 1) / p.sampling, nchunk = cloud_chunks(hc);
+    const size_t cnt_per = cloud_cnt_words(fovea ? F : 1, wc, nchunk);  // a pair's region of the count buffer
+    if (p.compact) UCHK(grow(ctx, c.cnt, c.cnt_cap, cnt_per * n));
+    for (int b = 0; b < n; b++) {
+        const CloudJob &j = call->job[b];
+        void *points = managed ? (void *)(c.cq_pts + b * c.cq_stride) : j.points;
+        long long *count = managed ? c.cq_words + b * kCqWords : j.count;
+        long long *levels = managed ? c.cq_words + b * kCqWords + 1 : j.level_counts;
+        UCHK(cloud_args_ok(ctx, res[b], res[b] + plane, res[b] + 2 * plane, dL[b], W, H, stride, fw, fh, spec.P1, spec.P2, &p, points, c.cq_cap[b], count));
+        if ((uintptr_t)levels & 7) return UGSM_ERR_BAD_ARG;
+        CloudPair &row = c.cq_tab_h[b];
+        row = CloudPair{};
+        row.a = cloud_args(res[b], res[b] + plane, res[b] + 2 * plane, dL[b], W, H, stride, fw, fh, &p, points, c.cq_cap[b], count);
+        row.a.wc = wc;
+        row.a.hc = hc;
+        row.a.nchunk = nchunk;
+        row.a.fmt = ctx->hooks.input_format;
+        row.a.cnt = p.compact ? c.cnt + b * cnt_per : nullptr;
+        if (fovea) {
+            row.sk = sk[b];
+            row.sk.level_counts = levels;
+        }
+    }
+    HIPCHK(ctx, hipMemcpyAsync(c.cq_tab, c.cq_tab_h, n * sizeof(CloudPair), hipMemcpyHostToDevice, s->st));
+    if (p.compact) HIPCHK(ctx, hipMemsetAsync(c.cnt, 0, cnt_per * n * sizeof(unsigned), s->st));  // (the totals of every pair's region)
+
+    // 3. the match, and the clouds behind it
+    const size_t img_bytes = (size_t)stride * H;
+    auto download = [&](int b) -> int {  // a managed pair's planes, where they are wanted
+        if (!planes) return UGSM_OK;
+        for (int k = 0; k < 3; k++)
+            HIPCHK(ctx, hipMemcpyAsync(call->job[b].planes[k], res[b] + k * plane, plane * sizeof(float), hipMemcpyDeviceToHost, s->st));
+        return UGSM_OK;
+    };
+    auto match = [&](int b, int k) {  // pairs b .. b + k - 1 of the call: one of them, or all in lockstep
+        return fovea ? enqueue_match_foveated(ctx, *s, slot, k, dL + b, dR + b, W, H, stride, ox + b, oy + b, state + b, res + b, nullptr, nullptr)
+                     : enqueue_match_full(ctx, *s, slot, k, dL + b, dR + b, W, H, stride, res + b);
+    };
+    const bool cloud_by_pair = by_pair || !batch_level(ctx, (fovea ? F : 1) * wc, hc);  // (a pair's sampled points against kBatchMaxPixels)
+    if (by_pair) {
+        for (int b = 0; b < n; b++) {
+            if (managed) UCHK(stage_in(ctx, *s, call->job[b].L, call->job[b].R, W, H, stride));
+            UCHK(match(b, 1));
+            UCHK(download(b));
+            UCHK(queue_cloud_launch(ctx, *s, slot, b, 1, fovea, &spec));
+        }
+    } else {
+        if (managed)
+            for (int b = 0; b < n; b++) {
+                HIPCHK(ctx, hipMemcpyAsync(const_cast<uint8_t *>(dL[b]), call->job[b].L, img_bytes, hipMemcpyHostToDevice, s->st));
+                HIPCHK(ctx, hipMemcpyAsync(const_cast<uint8_t *>(dR[b]), call->job[b].R, img_bytes, hipMemcpyHostToDevice, s->st));
+            }
+        UCHK(match(0, n));
+        for (int b = 0; b < n; b++) UCHK(download(b));
+        if (cloud_by_pair)
+            for (int b = 0; b < n; b++) UCHK(queue_cloud_launch(ctx, *s, slot, b, 1, fovea, &spec));
+        else
+            UCHK(queue_cloud_launch(ctx, *s, slot, 0, n, fovea, &spec));
+    }
+    if (managed) {
+        HIPCHK(ctx, hipMemcpyAsync(c.cq_words_h, c.cq_words, n * kCqWords * sizeof(long long), hipMemcpyDeviceToHost, s->st));
+        c.cq_n = n;
+        c.cq_step = step;
+        c.cq_levels = fovea ? F : 0;
+    }
+    return mark_done(ctx, *s);
+}
+
+int ugsm::queue_cloud_finish(ugsm_ctx *ctx, int slot, int n, ugsm_cloud_result *res, void *(*staging)(void *, int, long long), void *user)
+{
+    Slot *s;
+    UCHK(get_slot(ctx, slot, &s));
+    SlotCloud &c = s->cloud;
+    if (!res || !staging || n < 1 || n != c.cq_n) return ctx_fail(ctx, UGSM_ERR_STATE, "the slot holds no managed cloud call of that many pairs");
+    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
+    for (int b = 0; b < n; b++) {
+        const long long *w = c.cq_words_h + b * kCqWords;
+        ugsm_cloud_result &r = res[b];
+        r = ugsm_cloud_result{};
+        r.count = w[0];
+        r.stored = std::min(w[0], c.cq_cap[b]);
+        r.point_step = c.cq_step;
+        r.levels = c.cq_levels;
+        for (int l = 0; l < c.cq_levels; l++) r.level_counts[l] = w[1 + l];
+    }
+    c.cq_n = 0;
+    for (int b = 0; b < n; b++) {
+        if (res[b].stored < 1) continue;
+        const long long bytes = res[b].stored * c.cq_step;
+        res[b].points = staging(user, b, bytes);
+        if (!res[b].points) return ctx_fail(ctx, UGSM_ERR_NOMEM, "no page-locked memory for a pair's cloud");
+        HIPCHK(ctx, hipMemcpyAsync(res[b].points, c.cq_pts + b * c.cq_stride, (size_t)bytes, hipMemcpyDeviceToHost, s->st));
+    }
+    return mark_done(ctx, *s);
+}

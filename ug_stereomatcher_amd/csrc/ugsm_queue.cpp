@@ -473,7 +473,7 @@ int managed_get(ugsm_ctx *ctx, Queue *q, size_t in_bytes, size_t out_floats)
 }
 
 // What every ugsm_enqueue_*_cloud* checks of its spec and, the device kind, of its cloud buffers: the slot-level cloud calls' own checks
-// (cloud_args_ok, ugsm_runtime.cpp), made when the pair is enqueued so that a bad pair is rejected and never reported
+// (cloud_args_ok, ugsm_cloud.cpp), made when the pair is enqueued so that a bad pair is rejected and never reported
 int check_cloud(ugsm_ctx *ctx, const ugsm_queue_cloud *spec, int W, int H, bool device, const void *points, long long cap, const long long *count,
                 const long long *level_counts)
 {

@@ -1,4 +1,5 @@
-// ugsm_runtime.cpp -- host runtime + C-ABI of libugsm.so.
+// ugsm_runtime.cpp -- host runtime + C-ABI of libugsm.so: the context, the slots and the matcher.  (The point clouds -- row f-1, from
+// ugsm_triangulate to the queue's cloud calls -- are ugsm_cloud.cpp; what the two share is ugsm_slot.hpp.)
 //
 // Replaces the host orchestration of /root/reference/src/gpu_matcher/MatchGPULib.cpp:
 // a persistent context owns every device buffer (the reference mallocs/frees ~23 buffers
@@ -11,157 +12,28 @@
 #include "../../include/ugsm_dev.h"
 #endif
 #include "ugsm_device.hpp"
-#include "ugsm_internal.hpp"
-#include "ugsm_launch.hpp"
-
-#include <hip/hip_runtime.h>
+#include "ugsm_slot.hpp"
 
 #include <algorithm>
 #include <cmath>
-#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <condition_variable>
 #include <functional>
-#include <memory>
 #include <mutex>
-#include <string>
 #include <system_error>
 #include <thread>
-#include <unordered_map>
-#include <vector>
 
 using namespace ugsm;
 
 namespace {
-
-constexpr double kScale = 1.41421356;  // MatchLib_common.h:15
-
-enum KClass { KC_COST = 0, KC_SMOOTH, KC_SQBLUR, KC_PYR, KC_SEED, KC_WARP, KC_BOX, KC_MISC, KC_COST_MARCH, KC_PYR_BASE, KC_COST_SMALL, KC_SMOOTH_SMALL, KC_COST_MARCH4,
-              KC_LEVEL0_WIN, KC_COUNT };
 const char *kClassName[2][KC_COUNT] = {
     {"k_cost_split", "k_smooth_fused", "k_sqblur_tiled", "k_blur_decimate_tiled", "k_seed", "-", "-", "misc", "k_cost_march", "k_pyr_base", "k_cost_small",
      "k_smooth_small", "k_cost_march4", "k_level0_windows"},
     {"k_cost_ref", "k_smooth_pass", "k_sqblur_clamp", "k_blur_decimate", "k_seed", "k_warp", "k_box", "misc", "-", "-", "-", "-", "-", "-"}};
-constexpr int kNoLevel = UGSM_MAX_LEVELS;  // stats cell of launches that belong to no pyramid level
-struct StatCell {
-    long long launches = 0;
-    double total_ms = 0, pixel_launches = 0;
-};
+}  // namespace
 
-struct EvRec {
-    int kclass;
-    int level;
-    double pixels;
-    hipEvent_t a, b;
-};
-
-struct Slot {
-    hipStream_t st = nullptr;
-    int W = 0, H = 0, levels = 0;
-    int w[UGSM_MAX_LEVELS], h[UGSM_MAX_LEVELS];
-    size_t off[UGSM_MAX_LEVELS];  // float offset of level i inside pyrL/pyrR
-    float *pyrL = nullptr, *pyrR = nullptr;
-    size_t pyr_cap = 0;  // floats
-    // Batch (round 4): the call in flight matches `nb` pairs of one size in lockstep.  Every per-pair buffer of the slot holds nb copies:
-    // pair b's pyramids at pyrL / pyrR + b * pyr_stride, its level buffers (A, d0, d1) at + b * lvl_stride, its range word at range_bad + b.
-    int nb = 1;
-    size_t pyr_stride = 0, lvl_stride = 0;  // floats
-    // A checked foveated call (ugsm_set_lr_check, UGSM_LR_FOVEATED) matches both directions in lockstep: while its levels run, nb = 2 nreal
-    // VIRTUAL pairs -- virtual pair nreal + b is pair b with the L and R views exchanged (pair_pyr) -- and lvl_stride is the room of one
-    // fovea field, so that both directions' fields lie in the level buffers the slot holds.  Everywhere else nreal == nb.
-    int nreal = 1;
-    // The fine phase of ugsm_submit_foveated_multi: the nb fields are nb WINDOWS OF ONE PAIR -- every virtual pair reads pair 0's two pyramids,
-    // unswapped (pair_pyr), under pair 0's range word (copied to the others' entries); lvl_stride is one fovea field there as well.
-    bool one_pair = false;
-    float *A = nullptr, *Rw = nullptr, *B = nullptr, *d0 = nullptr, *d1 = nullptr;
-    // Side stream of the slot (round 3): the right image's upload and pyramid, and then A = G_clamp * L^2 of every full-frame level
-    // (MatchGPULib.cpp:1866-1875, once per level), run there beside the left pyramid and the coarse levels' iterations -- launches
-    // that last microseconds and depend on nothing but the left pyramid.  The main stream joins it through events: ev_R before the
-    // first level, ev_A[i] before level i's first K-cost launch, so a wait on the main stream still covers everything.
-    // WHICH stream that is (round 6): a call uses a side stream only when it has the chip to itself (`alone`), i.e. when every other slot
-    // is idle -- so with two or more streams in the context the side stream of a slot is A NEIGHBOUR SLOT'S OWN STREAM, borrowed for the call:
-    // a context holds no stream that calls in flight leave idle, and a lone call's two streams sit on two hardware queues whatever way HIP
-    // deals streams onto queues.  A context with one stream gets one stream more (owns_st2).
-    hipStream_t st2 = nullptr;
-    bool owns_st2 = false;
-    // set where a call puts work on st2, cleared where a ugsm_submit_* returns success (every piece of that work has then been joined by
-    // the main stream).  Still set at ugsm_wait / ugsm_poll = the submit failed part-way: the side stream is waited for as well, so that a
-    // reported call never leaves work behind that reads the caller's images.
-    bool forked = false;
-    int prio = 0;                  // HIP priority of `st` (a side stream of the slot's own is created in the same pool)
-    bool owns_st = true;           // false: `st` is the stream of slot (index % streams): several slots queue their pairs on one stream
-    hipEvent_t ev_done = nullptr;  // recorded at the end of every ugsm_submit_*: what ugsm_wait waits for when the stream is shared
-    bool done_recorded = false;
-    bool busy = false;   // a call has been enqueued here and neither ugsm_wait nor ugsm_poll has seen it finish (get_slot / slot_idle)
-    bool alone = true;   // the call in flight had the chip to itself when it was submitted (call_alone): what the kernel choices follow
-    hipEvent_t ev_in = nullptr, ev_L = nullptr, ev_R = nullptr, ev_A[UGSM_MAX_LEVELS] = {};
-    float *lr = nullptr;     // LR check: the right-to-left field of level 0 (3 planes) + one 8-byte counter behind it
-    size_t lr_cap = 0;
-    unsigned long long *lr_host = nullptr;  // page-locked copies: word 0 the full-mode counter, then one word per (pair, level) of a checked foveated call
-    bool lr_ran = false;
-    int lr_fov_pairs = 0, lr_fov_F = 0;  // the last call on the slot ran the foveated check on this many pairs of this many levels (0: it did not)
-    float *Apyr = nullptr;   // A of level i at Apyr + off[i] (same layout as the pyramids)
-    size_t apyr_cap = 0;
-    int a_from = -1;         // levels a_from .. top have their A in Apyr (ev_A recorded); -1: none (A is computed in line)
-    size_t lvl_cap = 0;  // floats per 3-plane level buffer
-    uint8_t *rgbL = nullptr, *rgbR = nullptr;
-    size_t rgb_cap = 0;
-    float *d2 = nullptr;            // third (dx,dy,conf) buffer: only with early_exit_threshold > 0 (the previous iteration's field must survive)
-    size_t d2_cap = 0;
-    double *wd_rows = nullptr;      // row f-4 scratch: 3 doubles per row + 3 totals
-    size_t wd_cap = 0;
-    double *wd_host = nullptr;      // page-locked, 3 doubles
-    unsigned *cloud_cnt = nullptr;  // row f-1 cloud, compact: per (column, chunk) counts + column and strip totals (CloudArgs.cnt)
-    size_t cloud_cap = 0;
-    // The queue's cloud calls (queue_cloud_submit / queue_cloud_finish): the table of the call's batched cloud launch -- in device memory, and
-    // the page-locked copy it is uploaded from on the slot's stream (rewritten only by the slot's next call, i.e. after this one has finished);
-    // managed calls: the device clouds of the pairs (pair b at cq_pts + b * cq_stride bytes, cq_cap[b] records of cq_step bytes), their count
-    // words (kCqWords per pair: the count, then the level counts) and the page-locked words those come down to with the call
-    CloudPair *cq_tab = nullptr, *cq_tab_h = nullptr;
-    size_t cq_tab_cap = 0;
-    char *cq_pts = nullptr;
-    size_t cq_pts_cap = 0, cq_stride = 0;
-    long long *cq_words = nullptr, *cq_words_h = nullptr;
-    size_t cq_words_cap = 0;
-    long long cq_cap[kMaxBatch] = {};
-    int cq_n = 0, cq_step = 0, cq_levels = 0;  // the managed cloud call in flight: pairs, bytes per record, fovea levels (0: full mode)
-    // The merged cloud of several windows (ugsm_point_cloud_fovea_multi): its table of entries in device memory, and the page-locked copies
-    // it is uploaded from on the slot's stream.  The call does not wait for the stream, so a copy may still be read by an earlier call's
-    // upload when the next call is made: kMcRing copies take turns, each with an event behind its upload, and a call waits only for the
-    // UPLOAD of the call kMcRing before it.
-    static constexpr int kMcRing = 4;
-    CloudEntry *mc_tab = nullptr, *mc_tab_h = nullptr;
-    size_t mc_tab_cap = 0, mc_tab_h_rows = 0;  // rows of the device table; rows of each page-locked copy
-    hipEvent_t mc_ev[kMcRing] = {};
-    bool mc_ev_set[kMcRing] = {};
-    int mc_next = 0;
-    int iters_run[UGSM_MAX_LEVELS];
-    unsigned *range_bad = nullptr;  // device word: 0 while every pyramid value of the pair in this slot passed range_ok (ugsm_exact.hpp)
-    float *hout = nullptr;  // device staging for host-API outputs
-    size_t hout_cap = 0;
-    float *hpin = nullptr;  // page-locked host staging for host-API outputs that land in pageable caller memory
-    size_t hpin_cap = 0;
-    hipEvent_t out_ev[12] = {};  // one per piece of the pageable copy-out (copy_out_planes)
-    // out of memory for the configured batch (prepare_slot): the capacity that failed, for which geometry, and the context's release
-    // count then -- the attempt is not repeated until something has been released or a call needs that much
-    int nomem_pairs = 0;
-    size_t nomem_tot = 0;
-    long long nomem_epoch = 0;
-    bool have_pyr = false;
-    // Level 0 of the call in flight is read from the images themselves (level0_direct: full-mode calls) -- the pyramids hold levels 1 and up,
-    // and the level-0 launches (A, K-cost) take byte views of img0L / img0R[pair], rows img0_stride bytes apart.  The images are the caller's
-    // device buffers or the slot's uploads: valid until the call is reported either way (include/ugsm.h).
-    bool direct0 = false;
-    const uint8_t *img0L[kMaxBatch] = {}, *img0R[kMaxBatch] = {};
-    int img0_stride = 0;
-    bool have_coarse = false;
-    bool range_known = false;
-    int cur_level = kNoLevel;  // pyramid level the launches being enqueued belong to (statistics only)  // range_bad describes the images the next run_level works on
-    std::vector<EvRec> pending;
-    std::vector<hipEvent_t> pool;
-};
-
+namespace ugsm {
 // A persistent team of host threads for the service path's page touching and staging copies (the first version
 // created ~29 std::threads per call; a failed creation -- EAGAIN under a thread or cgroup limit -- threw through an extern "C"
 // entry point with joinable threads on the stack, i.e. std::terminate in the caller's process).  Workers are created once, on the
@@ -238,35 +110,6 @@ private:
     bool stop_ = false;
 };
 
-}  // namespace
-
-struct ugsm_ctx {
-    std::unique_ptr<HostTeam> team;  // service path only; created on first use (host_team below)
-    ugsm_config cfg;
-    std::vector<Slot> slots;
-    std::string err;
-    StatCell cells[KC_COUNT][UGSM_MAX_LEVELS + 1];
-    int fuse_seed = 1, small_mask = 3, small_rh_force = 0;  // development overrides (apply_dev_env); the defaults are the product
-    int two_streams = 0;  // a call alone forks onto a side stream (every context; UGSM_TWO_STREAMS=0 under UGSM_DEV=1: never)
-    int march4_lo = -1, march4_hi = -1;  // development override of k_cost_march4's pixel range (use_march4; -1 = by the mode; 0, 0 = never)
-    int force_alone = -1;  // development override of call_alone(): 1 = every call is taken to be alone on the chip, 0 = none is
-    int level0_float = 0;  // development override (UGSM_LEVEL0_FLOAT=1): full-mode calls store the float level 0 too and read that (level0_direct)
-    int streams = 1;      // streams the slots' work is dealt onto: slot i enqueues on the stream of slot i % streams (ugsm_config.streams)
-    int march_mode = 0;   // strip heights of k_cost_march when cfg.march_rows == 0 (launch_cost_march's `rows`: 0, -1, -2, -3)
-    int smooth_big_min = 0;  // development override: levels of at least this many pixels run k_smooth_fused on its 112-column tile (0 = by the mode)
-    int smooth_rows = 0;  // height of k_smooth_fused's 112-column tile: 0 = by policy (smooth_rows_for), > 0 fixed, -1 / -2 = the latency / throughput rule
-    long long batch_max_px = 0;  // development override of kBatchMaxPixels (batch_level): levels up to this size go through a batched call as one launch; < 0 = none
-    float lr_tau = 0.0f;  // the LR check (ugsm_set_lr_check; ugsm_create: ugsm_config.lr_check_threshold, UGSM_LR_FULL): the threshold ...
-    int lr_modes = 0;     // ... and the calls that apply it (UGSM_LR_*)
-    CtxHooks hooks;  // the queue (ugsm_queue.cpp) and the RCCL shard (ugsm_shard.cpp): layers over the slot API
-    long long dev_bytes = 0;    // device memory held by the slots' growable buffers (grow); ugsm_context_device_bytes
-    std::unordered_map<const void *, size_t> dev_allocs;  // ... buffer by buffer, so that every release is accounted whatever path it takes
-    long long release_epoch = 0;  // counts the releases of tracked device buffers (untrack): "memory may have come free since"
-    bool counted_live = false;  // this context counts in g_live_contexts (ugsm_create got as far as handing it out)
-    long long mem_limit = 0;    // development (UGSM_MEM_LIMIT_MB under UGSM_DEV=1): grow refuses to go past it -- the UGSM_ERR_NOMEM path without exhausting a GPU
-};
-
-namespace ugsm {
 CtxHooks &ctx_hooks(ugsm_ctx *ctx) { return ctx->hooks; }
 const ugsm_config &ctx_config(const ugsm_ctx *ctx) { return ctx->cfg; }
 void *ctx_slot_stream(ugsm_ctx *ctx, int slot) { return (ctx && slot >= 0 && slot < (int)ctx->slots.size()) ? (void *)ctx->slots[(size_t)slot].st : nullptr; }
@@ -275,28 +118,6 @@ int ctx_fail(ugsm_ctx *ctx, int status, const char *what)
     if (ctx && what) ctx->err = what;
     return status;
 }
-}  // namespace ugsm
-
-namespace {
-
-#define HIPCHK(ctx, call)                                                                             \
-    do {                                                                                              \
-        hipError_t e__ = (call);                                                                      \
-        if (e__ != hipSuccess) {                                                                      \
-            char b__[512];                                                                            \
-            snprintf(b__, sizeof b__, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e__), __FILE__, __LINE__); \
-            (ctx)->err = b__;                                                                         \
-            return UGSM_ERR_DEVICE;                                                                   \
-        }                                                                                             \
-    } while (0)
-
-#define UCHK(call)                       \
-    do {                                 \
-        int r__ = (call);                \
-        if (r__ != UGSM_OK) return r__;  \
-    } while (0)
-
-constexpr long long kMaxPixels = 1LL << 28;  // 268 Mpx: 4 B x pixels of one plane stays below 2^31
 
 int level_dims(int W, int H, int levels, int *w, int *h)
 {
@@ -331,12 +152,6 @@ void threshold_schedule(int mi, float *out)
     }
 }
 
-struct FoveaGeom {
-    int fw, fh, Wup, Hup;
-    int ox[UGSM_MAX_LEVELS], oy[UGSM_MAX_LEVELS];  // crop origin at level lev < F-1
-    int cx[UGSM_MAX_LEVELS], cy[UGSM_MAX_LEVELS];  // seed-crop origin for transition lev+1 -> lev
-};
-
 // Reference (off = 0): MatchGPULib.cpp:1143-1146,1173-1176 (pyramid crop) and :1612-1615 (seed crop).
 // The offset generalisation is this build's (DESIGN.md "Fovea windows").
 void fovea_geometry(const int *w, const int *h, int F, int off_x, int off_y, FoveaGeom &g)
@@ -366,42 +181,13 @@ void fovea_geometry(const int *w, const int *h, int F, int off_x, int off_y, Fov
     }
 }
 
+}  // namespace ugsm
+
+ugsm_ctx::~ugsm_ctx() = default;
+
+namespace {
+
 // ---- buffers ---------------------------------------------------------------------------
-
-void untrack(ugsm_ctx *ctx, const void *p)
-{
-    auto it = ctx->dev_allocs.find(p);
-    if (it == ctx->dev_allocs.end()) return;
-    ctx->dev_bytes -= (long long)it->second;
-    ctx->dev_allocs.erase(it);
-    ctx->release_epoch++;
-}
-
-template <class T>
-int grow(ugsm_ctx *ctx, T *&p, size_t &cap, size_t need)
-{
-    if (need <= cap) return UGSM_OK;
-    if (p) {
-        untrack(ctx, p);
-        HIPCHK(ctx, hipFree(p));
-    }
-    p = nullptr;
-    cap = 0;
-    hipError_t e = (ctx->mem_limit > 0 && ctx->dev_bytes + (long long)(need * sizeof(T)) > ctx->mem_limit) ? hipErrorOutOfMemory
-                                                                                                          : hipMalloc((void **)&p, need * sizeof(T));
-    if (e != hipSuccess) {
-        (void)hipGetLastError();  // (the failed allocation must not poison the next launch check)
-        char b[256];
-        snprintf(b, sizeof b, "hipMalloc of %zu bytes failed: %s (the context holds %lld bytes)", need * sizeof(T), hipGetErrorString(e), ctx->dev_bytes);
-        ctx->err = b;
-        p = nullptr;
-        return UGSM_ERR_NOMEM;
-    }
-    cap = need;
-    ctx->dev_bytes += (long long)(need * sizeof(T));
-    ctx->dev_allocs[p] = need * sizeof(T);
-    return UGSM_OK;
-}
 
 // (dx,dy,conf) ping-pong, A = G*L^2 and (kernel_path 1 only) R' and B: 3-plane buffers sized
 // for the largest level seen.
@@ -519,48 +305,7 @@ int prepare_slot(ugsm_ctx *ctx, Slot &s, int W, int H, int nb = 1)
     return st;
 }
 
-// ---- event bookkeeping -----------------------------------------------------------------
-
-struct Timer {
-    ugsm_ctx *ctx;
-    Slot *s;
-    bool on;
-    EvRec rec;
-    LaunchProbe probe;
-    Timer(ugsm_ctx *c, Slot *sl, int slot_idx, int kclass, double pixels) : ctx(c), s(sl)
-    {
-        // 1: only the dominant (cost) kernel is bracketed -- two events per launch are not free (a 16 MP pair
-        // has ~750 launches; bracketing all of them costs slot 0 about 20 %); 2: every kernel class
-        const bool cost_class = kclass == KC_COST || kclass == KC_COST_MARCH || kclass == KC_COST_SMALL || kclass == KC_COST_MARCH4;
-        on = slot_idx == 0 && (c->cfg.profile_events >= 2 || (c->cfg.profile_events == 1 && cost_class));
-        if (!on) return;
-        rec.kclass = kclass;
-        rec.level = sl->cur_level;
-        rec.pixels = pixels;
-        for (hipEvent_t *e : {&rec.a, &rec.b}) {
-            if (!s->pool.empty()) {
-                *e = s->pool.back();
-                s->pool.pop_back();
-            } else if (hipEventCreate(e) != hipSuccess) {
-                on = false;
-                return;
-            }
-        }
-        probe = LaunchProbe{rec.a, rec.b, 0};  // the bracket's launch carries the two events in its dispatch (ugsm_launch.hpp)
-        g_probe = &probe;
-    }
-    ~Timer()
-    {
-        if (!on) return;
-        g_probe = nullptr;
-        if (probe.n == 0) {  // (nothing was launched inside the bracket)
-            s->pool.push_back(rec.a);
-            s->pool.push_back(rec.b);
-            return;
-        }
-        s->pending.push_back(rec);
-    }
-};
+// ---- event bookkeeping (Timer: ugsm_slot.hpp) --------------------------------------------
 
 void harvest(ugsm_ctx *ctx, Slot &s)
 {
@@ -722,9 +467,6 @@ Batch make_batch(const Slot &s, Grp g, const Img3 *views = nullptr, const SeedMa
     return b;
 }
 
-// the least stride of a W-pixel row in the context's input format
-int input_row_bytes(const ugsm_ctx *ctx, int W) { return ugsm_input_bytes_per_pixel(ctx->hooks.input_format) * W; }
-
 // CreatePyramidFromImage (MatchGPULib.cpp:1033-1125) for the left OR the right image of every pair of the call: rgb[b] -> pyr + b * pyr_stride.
 // The images of a batch go through every pyramid kernel together (one launch per level for all of them).
 // What a foveated call reads of level 0: every pair's fovea window (the level-0 crop of fovea_geometry); k_pyr_base then stores level 0
@@ -818,11 +560,13 @@ constexpr int kMarch4MaxPixels = 3000000;       // above them k_cost_march4 (fou
 constexpr int kMarchMinPixels = 400000;         // k_cost_march from here -- asked after k_cost_march4, so in effect above its range
 constexpr int kSmoothBigMinPixels = 1 << 19;    // k_smooth_fused's 112-column tile from here (1.39 x the tile in halo work, against 1.8 x for 64 x 32)
 
-bool batch_level(const ugsm_ctx *ctx, int W, int H)
+}  // namespace
+bool ugsm::batch_level(const ugsm_ctx *ctx, int W, int H)
 {
     const long long thr = ctx->batch_max_px > 0 ? ctx->batch_max_px : (ctx->batch_max_px < 0 ? 0 : kBatchMaxPixels);
     return (long long)W * H <= thr;
 }
+namespace {
 // pairs a launch of a W x H level of the call in `s` holds
 int launch_pairs(const ugsm_ctx *ctx, const Slot &s, int W, int H) { return (s.nb > 1 && batch_level(ctx, W, H)) ? group_pairs(s.nb) : 1; }
 
@@ -1467,6 +1211,7 @@ int enqueue_fovea_fine(ugsm_ctx *ctx, Slot &s, int si, const float *d_state, int
     return enqueue_fovea_fine(ctx, s, si, &d_state, &off_x, &off_y, &d_stack, d_pyrL ? &d_pyrL : nullptr, d_pyrR ? &d_pyrR : nullptr);
 }
 
+}  // namespace
 // One foveated call of n pairs on device buffers: the pyramids, the coarse levels, the fine levels into the pairs' stacks.  state: n buffers
 // of 3 fovW fovH floats for level F-1's field between the two phases; d_pyrL / d_pyrR as for enqueue_fovea_fine.
 // With the foveated LR check on (ugsm_set_lr_check) the call matches both directions in lockstep and checks the stacks against each other:
@@ -1480,8 +1225,8 @@ int enqueue_fovea_fine(ugsm_ctx *ctx, Slot &s, int si, const float *d_state, int
 //     fovW fovH floats per pair, 24 MB at 16 MP beside the pair's 1.35 GB, counted by ugsm_context_device_bytes;
 //   - one launch checks every level of every pair's stack (k_lr_check's stack form) after the last level, so nothing feeds back into the
 //     matching; the counts come back with one copy on the slot's stream.
-int enqueue_foveated(ugsm_ctx *ctx, Slot &s, int si, int n, const uint8_t *const *d_rgbL, const uint8_t *const *d_rgbR, int W, int H, int stride,
-                     const int *off_x, const int *off_y, float *const *state, float *const *d_stack, float *const *d_pyrL, float *const *d_pyrR)
+int ugsm::enqueue_match_foveated(ugsm_ctx *ctx, Slot &s, int si, int n, const uint8_t *const *d_rgbL, const uint8_t *const *d_rgbR, int W, int H, int stride,
+                                 const int *off_x, const int *off_y, float *const *state, float *const *d_stack, float *const *d_pyrL, float *const *d_pyrR)
 {
     const int F = ctx->cfg.fovea_levels;
     s.lr_ran = false;
@@ -1540,6 +1285,22 @@ int enqueue_foveated(ugsm_ctx *ctx, Slot &s, int si, int n, const uint8_t *const
     s.lr_fov_F = F;
     return UGSM_OK;
 }
+
+// One full-mode call of n pairs on device buffers.  One pair: its pyramids (A planes from the side stream where the call is alone), the match
+// and the LR check where it is on; several: the pyramids and the levels of all of them in lockstep (no check: batch_runs_pair_by_pair).
+int ugsm::enqueue_match_full(ugsm_ctx *ctx, Slot &s, int si, int n, const uint8_t *const *d_rgbL, const uint8_t *const *d_rgbR, int W, int H, int stride,
+                             float *const *d_out)
+{
+    if (n == 1) {
+        UCHK(enqueue_pyramids(ctx, s, si, d_rgbL, d_rgbR, 1, W, H, stride, 0, nullptr, true));
+        return enqueue_full_lr(ctx, s, si, d_out[0]);
+    }
+    UCHK(enqueue_pyramids(ctx, s, si, d_rgbL, d_rgbR, n, W, H, stride, -1, nullptr, true));
+    s.lr_ran = false;
+    s.lr_fov_pairs = 0;
+    return enqueue_full(ctx, s, si, d_out);
+}
+namespace {
 
 // n fovea windows on ONE pair (ugsm_submit_foveated_multi): what does not depend on the window runs once, the rest in lockstep.
 //   - the pyramids of one pair, as a lone foveated call builds them (side stream and A planes of levels F-1 .. top included), but with no
@@ -1638,7 +1399,8 @@ bool call_alone(ugsm_ctx *ctx, int slot)
     return true;
 }
 
-int get_slot(ugsm_ctx *ctx, int slot, Slot **out, bool enqueues = true)
+}  // namespace
+int ugsm::get_slot(ugsm_ctx *ctx, int slot, Slot **out, bool enqueues)
 {
     if (!ctx) return UGSM_ERR_BAD_ARG;
     if (slot < 0 || slot >= (int)ctx->slots.size()) {
@@ -1660,7 +1422,7 @@ int get_slot(ugsm_ctx *ctx, int slot, Slot **out, bool enqueues = true)
 
 // End of a ugsm_submit_*: the slot's completion mark.  With several slots on one stream (ugsm_config.streams < slots) ugsm_wait waits for
 // this event, not for the pairs other slots have queued behind it on the same stream.
-int mark_done(ugsm_ctx *ctx, Slot &s)
+int ugsm::mark_done(ugsm_ctx *ctx, Slot &s)
 {
     s.forked = false;  // (the call was enqueued whole: the main stream waits for everything it put on the side stream)
     if (ctx->streams >= (int)ctx->slots.size()) return UGSM_OK;
@@ -1669,7 +1431,7 @@ int mark_done(ugsm_ctx *ctx, Slot &s)
     return UGSM_OK;
 }
 
-int stage_in(ugsm_ctx *ctx, Slot &s, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride)
+int ugsm::stage_in(ugsm_ctx *ctx, Slot &s, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride)
 {
     if (!rgbL || !rgbR || W < 1 || H < 1) return UGSM_ERR_BAD_ARG;
     if (stride < input_row_bytes(ctx, W)) return UGSM_ERR_SIZE_MISMATCH;
@@ -1692,6 +1454,7 @@ int stage_in(ugsm_ctx *ctx, Slot &s, const uint8_t *rgbL, const uint8_t *rgbR, i
     }
     return UGSM_OK;
 }
+namespace {
 
 // Result planes into caller memory.  Page-locked destinations (ugsm_host_alloc, or memory the caller registered) take the
 // device-to-host copies directly.  Pageable ones go through a page-locked staging buffer and a team of host threads: the
@@ -1807,6 +1570,11 @@ namespace ugsm {
 void ctx_host_copy(ugsm_ctx *ctx, void *dst, const void *src, size_t bytes) { team_copy(ctx, dst, src, bytes); }
 bool host_pinned(const void *p) { return is_pinned(p); }
 bool dev_env() { return dev_env_on(); }
+// Contexts whose options need a host round trip per iteration, a second match, or the one-kernel-per-stage path run their batches pair by pair.
+bool batch_runs_pair_by_pair(const ugsm_ctx *ctx) { return ctx->cfg.kernel_path == 1 || ctx->cfg.early_exit_threshold > 0.0f || lr_full_on(ctx); }
+// ... and the foveated batches: the foveated check runs in lockstep (enqueue_match_foveated; ugsm_set_lr_check refuses it to the contexts of the
+// first two kinds).  A context with the full-mode check alone sends its foveated batches through pair by pair as it always has.
+bool fovea_batch_runs_pair_by_pair(const ugsm_ctx *ctx) { return batch_runs_pair_by_pair(ctx) && !lr_fovea_on(ctx); }
 }  // namespace ugsm
 
 // =========================================================================================
@@ -1885,9 +1653,6 @@ static int check_config(const ugsm_config &cfg)
     if (cfg.march_min_pixels < 0 && !kDevLib) return UGSM_ERR_BAD_ARG;  // ... and so does round 1's LDS-tiled K-cost
     return UGSM_OK;
 }
-
-static int queue_cloud_submit(ugsm_ctx *ctx, int slot, const CloudCall *call);
-static int queue_cloud_finish(ugsm_ctx *ctx, int slot, int n, ugsm_cloud_result *res, void *(*staging)(void *, int, long long), void *user);
 
 int ugsm_create(const ugsm_config *cfg_in, ugsm_ctx **out)
 {
@@ -2035,15 +1800,7 @@ void ugsm_destroy(ugsm_ctx *ctx)
             if (e) (void)hipEventDestroy(e);
         if (s.Apyr) (void)hipFree(s.Apyr);
         if (s.lr) (void)hipFree(s.lr);
-        if (s.cloud_cnt) (void)hipFree(s.cloud_cnt);
-        for (void *p : {(void *)s.cq_tab, (void *)s.cq_pts, (void *)s.cq_words})
-            if (p) (void)hipFree(p);
-        if (s.cq_tab_h) (void)hipHostFree(s.cq_tab_h);
-        if (s.mc_tab) (void)hipFree(s.mc_tab);
-        if (s.mc_tab_h) (void)hipHostFree(s.mc_tab_h);
-        for (hipEvent_t e : s.mc_ev)
-            if (e) (void)hipEventDestroy(e);
-        if (s.cq_words_h) (void)hipHostFree(s.cq_words_h);
+        s.cloud.release();
         if (s.lr_host) (void)hipHostFree(s.lr_host);
         if (s.st2 && s.owns_st2) (void)hipStreamDestroy(s.st2);
         if (s.st && s.owns_st) (void)hipStreamDestroy(s.st);
@@ -2186,21 +1943,12 @@ int ugsm_submit_foveated(ugsm_ctx *ctx, int slot, const uint8_t *d_rgbL, const u
     UCHK(ugsm_fovea_dims(W, H, ctx->cfg.levels, F, &fw, &fh));
     const size_t fn3 = 3 * (size_t)fw * fh;
     UCHK(grow(ctx, s->hout, s->hout_cap, std::max(fn3, s->hout_cap)));
-    UCHK(enqueue_foveated(ctx, *s, slot, 1, &d_rgbL, &d_rgbR, W, H, stride, &off_x, &off_y, &s->hout, &d_stack, d_pyrL ? &d_pyrL : nullptr,
+    UCHK(enqueue_match_foveated(ctx, *s, slot, 1, &d_rgbL, &d_rgbR, W, H, stride, &off_x, &off_y, &s->hout, &d_stack, d_pyrL ? &d_pyrL : nullptr,
                           d_pyrR ? &d_pyrR : nullptr));
     return mark_done(ctx, *s);
 }
 
 // ---- B pairs per call ---------------------------------------------------------------------------------------------------------
-// Contexts whose options need a host round trip per iteration, a second match, or the one-kernel-per-stage path: pair by pair.
-static bool batch_runs_pair_by_pair(const ugsm_ctx *ctx)
-{
-    return ctx->cfg.kernel_path == 1 || ctx->cfg.early_exit_threshold > 0.0f || lr_full_on(ctx);
-}
-// ... and the foveated batches: the foveated check runs in lockstep (enqueue_foveated; ugsm_set_lr_check refuses it to the contexts of the first
-// two kinds).  A context with the full-mode check alone sends its foveated batches through pair by pair as it always has.
-static bool fovea_batch_runs_pair_by_pair(const ugsm_ctx *ctx) { return batch_runs_pair_by_pair(ctx) && !lr_fovea_on(ctx); }
-
 int ugsm_submit_full_batch(ugsm_ctx *ctx, int slot, int n, const uint8_t *const *d_rgbL, const uint8_t *const *d_rgbR, int W, int H, int stride,
                            float *const *d_out)
 {
@@ -2210,17 +1958,8 @@ int ugsm_submit_full_batch(ugsm_ctx *ctx, int slot, int n, const uint8_t *const 
     for (int b = 0; b < n; b++)
         if (!d_rgbL[b] || !d_rgbR[b] || !d_out[b]) return UGSM_ERR_BAD_ARG;
     HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
-    if (n == 1 || batch_runs_pair_by_pair(ctx)) {
-        for (int b = 0; b < n; b++) {
-            UCHK(enqueue_pyramids(ctx, *s, slot, d_rgbL[b], d_rgbR[b], W, H, stride, 0, nullptr, true));
-            UCHK(enqueue_full_lr(ctx, *s, slot, d_out[b]));
-        }
-        return mark_done(ctx, *s);
-    }
-    UCHK(enqueue_pyramids(ctx, *s, slot, d_rgbL, d_rgbR, n, W, H, stride, -1, nullptr, true));
-    s->lr_ran = false;
-    s->lr_fov_pairs = 0;
-    UCHK(enqueue_full(ctx, *s, slot, d_out));
+    const int per = batch_runs_pair_by_pair(ctx) ? 1 : n;  // pairs per match: one by one, or all in lockstep
+    for (int b = 0; b < n; b += per) UCHK(enqueue_match_full(ctx, *s, slot, per, d_rgbL + b, d_rgbR + b, W, H, stride, d_out + b));
     return mark_done(ctx, *s);
 }
 
@@ -2241,17 +1980,15 @@ int ugsm_submit_foveated_batch(ugsm_ctx *ctx, int slot, int n, const uint8_t *co
     UCHK(ugsm_fovea_dims(W, H, ctx->cfg.levels, F, &fw, &fh));
     const size_t fn3 = (3 * (size_t)fw * fh + 63) & ~(size_t)63;  // level F-1's state of every pair, staged in the slot's hout
     UCHK(grow(ctx, s->hout, s->hout_cap, std::max(fn3 * n, s->hout_cap)));
-    FoveaWin win;
-    UCHK(fovea_windows(ctx, W, H, n, ox, oy, win));
     if (n == 1 || fovea_batch_runs_pair_by_pair(ctx)) {
         for (int b = 0; b < n; b++)
-            UCHK(enqueue_foveated(ctx, *s, slot, 1, d_rgbL + b, d_rgbR + b, W, H, stride, ox + b, oy + b, &s->hout, d_stack + b,
+            UCHK(enqueue_match_foveated(ctx, *s, slot, 1, d_rgbL + b, d_rgbR + b, W, H, stride, ox + b, oy + b, &s->hout, d_stack + b,
                                   (d_pyrL && d_pyrL[b]) ? d_pyrL + b : nullptr, (d_pyrR && d_pyrR[b]) ? d_pyrR + b : nullptr));
         return mark_done(ctx, *s);
     }
     float *state[UGSM_MAX_BATCH];
     for (int b = 0; b < n; b++) state[b] = s->hout + b * fn3;
-    UCHK(enqueue_foveated(ctx, *s, slot, n, d_rgbL, d_rgbR, W, H, stride, ox, oy, state, d_stack, d_pyrL, d_pyrR));
+    UCHK(enqueue_match_foveated(ctx, *s, slot, n, d_rgbL, d_rgbR, W, H, stride, ox, oy, state, d_stack, d_pyrL, d_pyrR));
     return mark_done(ctx, *s);
 }
 
@@ -2425,7 +2162,7 @@ static int match_foveated_on_slot(ugsm_ctx *ctx, int slot, const uint8_t *rgbL, 
     float *d_pl = pyrL ? d_stack + 3 * stackn : nullptr;
     float *d_pr = pyrR ? d_stack + 3 * stackn + (pyrL ? 3 * stackn : 0) : nullptr;
     const uint8_t *const dL = s->rgbL, *const dR = s->rgbR;
-    UCHK(enqueue_foveated(ctx, *s, slot, 1, &dL, &dR, W, H, stride, &off_x, &off_y, &d_state, &d_stack, d_pl ? &d_pl : nullptr, d_pr ? &d_pr : nullptr));
+    UCHK(enqueue_match_foveated(ctx, *s, slot, 1, &dL, &dR, W, H, stride, &off_x, &off_y, &d_state, &d_stack, d_pl ? &d_pl : nullptr, d_pr ? &d_pr : nullptr));
     HIPCHK(ctx, hipMemcpyAsync(stackH, d_stack, stackn * sizeof(float), hipMemcpyDeviceToHost, s->st));
     HIPCHK(ctx, hipMemcpyAsync(stackV, d_stack + stackn, stackn * sizeof(float), hipMemcpyDeviceToHost, s->st));
     HIPCHK(ctx, hipMemcpyAsync(stackC, d_stack + 2 * stackn, stackn * sizeof(float), hipMemcpyDeviceToHost, s->st));
@@ -2530,10 +2267,7 @@ int ugsm_submit_full_batch_host(ugsm_ctx *ctx, int slot, int n, const uint8_t *c
     UCHK(grow(ctx, s->hout, s->hout_cap, std::max(per * n, s->hout_cap)));
     float *out[UGSM_MAX_BATCH];
     for (int b = 0; b < n; b++) out[b] = s->hout + b * per;
-    UCHK(enqueue_pyramids(ctx, *s, slot, dL, dR, n, W, H, stride, -1, nullptr, true));
-    s->lr_ran = false;
-    s->lr_fov_pairs = 0;
-    UCHK(enqueue_full(ctx, *s, slot, out));
+    UCHK(enqueue_match_full(ctx, *s, slot, n, dL, dR, W, H, stride, out));
     for (int b = 0; b < n; b++) {
         float *const dst[3] = {dispH[b], dispV[b], dispC[b]};
         UCHK(copy_out_planes(ctx, *s, out[b], px, dst));  // (page-locked destinations: three asynchronous copies)
@@ -2574,7 +2308,7 @@ int ugsm_submit_foveated_batch_host(ugsm_ctx *ctx, int slot, int n, const uint8_
         state[b] = s->hout + b * st_per;
         stack[b] = s->hout + n * st_per + b * sk_per;
     }
-    UCHK(enqueue_foveated(ctx, *s, slot, n, dL, dR, W, H, stride, ox, oy, state, stack, nullptr, nullptr));
+    UCHK(enqueue_match_foveated(ctx, *s, slot, n, dL, dR, W, H, stride, ox, oy, state, stack, nullptr, nullptr));
     for (int b = 0; b < n; b++) {
         HIPCHK(ctx, hipMemcpyAsync(stackH[b], stack[b], stackn * sizeof(float), hipMemcpyDeviceToHost, s->st));
         HIPCHK(ctx, hipMemcpyAsync(stackV[b], stack[b] + stackn, stackn * sizeof(float), hipMemcpyDeviceToHost, s->st));
@@ -2600,7 +2334,7 @@ static int match_foveated_full_on_slot0(ugsm_ctx *ctx, const uint8_t *rgbL, cons
     UCHK(grow(ctx, s->hout, s->hout_cap, 3 * fn + 3 * stackn + 3 * n));  // [state][stack][full field]
     float *d_state = s->hout, *d_stack = d_state + 3 * fn, *d_full = d_stack + 3 * stackn;
     const uint8_t *const dL = s->rgbL, *const dR = s->rgbR;
-    UCHK(enqueue_foveated(ctx, *s, 0, 1, &dL, &dR, W, H, stride, &off_x, &off_y, &d_state, &d_stack, nullptr, nullptr));
+    UCHK(enqueue_match_foveated(ctx, *s, 0, 1, &dL, &dR, W, H, stride, &off_x, &off_y, &d_state, &d_stack, nullptr, nullptr));
     UCHK(ugsm_reconstruct_full(ctx, 0, d_stack, d_stack + stackn, d_stack + 2 * stackn, W, H, off_x, off_y, d_full));
     float *const dst[3] = {outH, outV, outC};
     prefault_planes(ctx, dst, n);
@@ -2691,746 +2425,6 @@ int ugsm_stage_smooth(ugsm_ctx *ctx, float *d_d3, int W, int H, int passes, int 
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipMemcpyAsync(d_d3, a, lvl * sizeof(float), hipMemcpyDeviceToDevice, s->st));
     return ugsm_wait(ctx, 0);
-}
-
-int ugsm_triangulate(ugsm_ctx *ctx, int slot, const float *d_dispx, const float *d_dispy, int W, int H, const double *P1, const double *P2,
-                     float *d_xyz)
-{
-    Slot *s;
-    UCHK(get_slot(ctx, slot, &s));
-    if (!d_dispx || !d_dispy || !P1 || !P2 || !d_xyz || W < 1 || H < 1) return UGSM_ERR_BAD_ARG;
-    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
-    {
-        Timer t(ctx, s, slot, KC_MISC, (double)W * H);
-        launch_triangulate(s->st, d_dispx, d_dispy, W, H, P1, P2, d_xyz);
-    }
-    HIPCHK(ctx, hipGetLastError());
-    return UGSM_OK;
-}
-
-// CdynamicCalibration::left_marginOf_in / upper_marginOf_in / mapXcoord (getPointCloud.cpp:387-484)
-int ugsm_fovea_mapping(int W, int H, int src_level, int dest_level, int *left_margin, int *upper_margin, float *scale)
-{
-    if (!left_margin || !upper_margin || !scale || W < 1 || H < 1) return UGSM_ERR_BAD_ARG;
-    int scaled = 6 - src_level;  // :435 (the reference hard-codes its 7 fovea levels here)
-    if (src_level < dest_level) scaled = src_level + dest_level;
-    if (scaled < 0 || scaled >= 15 || dest_level < 0 || dest_level >= 15 || src_level < 0) return UGSM_ERR_BAD_ARG;
-    int w[16], h[16];
-    w[0] = W;
-    h[0] = H;
-    for (int i = 0; i < 14; i++) {  // :441-443
-        w[i + 1] = (int)(w[i] / kScale);
-        h[i + 1] = (int)(h[i] / kScale);
-    }
-    *left_margin = w[dest_level] / 2 - w[scaled] / 2;
-    *upper_margin = h[dest_level] / 2 - h[scaled] / 2;
-    const float root = (src_level < dest_level) ? (float)0.70710678118654752440 : (float)1.41421356237309504880;
-    *scale = powf(root, (float)std::abs(src_level - dest_level));  // pow(float, float), :397
-    return UGSM_OK;
-}
-
-namespace {
-
-// ugsm_fovea_level_mapping for every level of the stack: the reference's centred margins for any fovea_levels (its `scaled` is
-// F-1-k), moved by this build's window offset -- level k's clamped offset ex[k] (fovea_geometry), in level-0 pixels
-int fovea_level_mappings(int W, int H, int levels, int F, int off_x, int off_y, int *fw, int *fh, int *left, int *upper, float *scale)
-{
-    int w[UGSM_MAX_LEVELS], h[UGSM_MAX_LEVELS];
-    if (F < 2 || F > levels || levels > UGSM_MAX_LEVELS) return UGSM_ERR_BAD_ARG;
-    UCHK(level_dims(W, H, F, w, h));  // (only the stack's F levels enter: a cloud of a given stack does not ask whether the coarse levels below it exist)
-    FoveaGeom g;
-    fovea_geometry(w, h, F, off_x, off_y, g);
-    *fw = g.fw;
-    *fh = g.fh;
-    for (int k = 0; k < F; k++) {
-        const int ex = k < F - 1 ? g.ox[k] - (w[k] / 2 - g.fw / 2) : 0, ey = k < F - 1 ? g.oy[k] - (h[k] / 2 - g.fh / 2) : 0;
-        left[k] = w[0] / 2 - w[F - 1 - k] / 2 + (int)lrint(ex * pow(kScale, k));
-        upper[k] = h[0] / 2 - h[F - 1 - k] / 2 + (int)lrint(ey * pow(kScale, k));
-        scale[k] = powf((float)1.41421356237309504880, (float)k);  // as ugsm_fovea_mapping for destination level 0
-    }
-    return UGSM_OK;
-}
-
-// The coverage rule along one axis (include/ugsm.h): pixel i of level k, at x1 = (float)m + (float)i * sc, is covered when
-// x1 >= (float)m_fine && x1 + sc <= (float)m_fine + (float)n * sc_fine, every operation in binary32.  Monotone in i, so the covered
-// pixels are one interval [i0, i1); of the sampled grid (pixel = index * s) that is [c0, c1).  x1 never falls as i grows (i is exact in
-// binary32, and a rounded product and a rounded sum keep the order of their operands), so the first test turns true once and the second
-// false once: two bisections, the same interval a scan over the pixels finds (the merged cloud of several windows asks for up to 31
-// rectangles for each of up to 97 entries per call).
-void covered_interval(int n, int m, float sc, int m_fine, float sc_fine, int s, int *c0, int *c1)
-{
-    const float lo = (float)m_fine, hi = (float)m_fine + (float)n * sc_fine;
-    auto first = [&](int from, auto test) {  // the first i in [from, n) that passes a test which stays passed; n: none
-        int a = from, b = n;
-        while (a < b) {
-            const int mid = a + (b - a) / 2;
-            if (test((float)m + (float)mid * sc)) b = mid;
-            else a = mid + 1;
-        }
-        return a;
-    };
-    int i0 = first(0, [&](float x1) { return x1 >= lo; });
-    int i1 = first(i0, [&](float x1) { return !(x1 + sc <= hi); });
-    if (i1 <= i0) i0 = i1 = n;  // (nothing covered)
-    *c0 = (i0 + s - 1) / s;
-    *c1 = (i1 + s - 1) / s;
-    if (*c1 < *c0) *c1 = *c0;
-}
-
-// the table of the merged cloud's kernel: each level's planes, mapping, covered rectangle and dense records
-int cloud_stack_table(int W, int H, int levels, int F, int off_x, int off_y, int sampling, CloudStack &sk, int *fw_out, int *fh_out)
-{
-    int left[UGSM_MAX_LEVELS], upper[UGSM_MAX_LEVELS], fw, fh;
-    float scale[UGSM_MAX_LEVELS];
-    if (sampling < 1) return UGSM_ERR_BAD_ARG;
-    UCHK(fovea_level_mappings(W, H, levels, F, off_x, off_y, &fw, &fh, left, upper, scale));
-    const int wc = (fw + sampling - 1) / sampling, hc = (fh + sampling - 1) / sampling;
-    sk = CloudStack{};
-    sk.F = F;
-    sk.strips = cloud_strips(wc);
-    long long first = 0;
-    for (int k = 0; k < F; k++) {
-        CloudLevel &lv = sk.lv[k];
-        lv.plane = (long long)k * fw * fh;
-        lv.left_margin = left[k];
-        lv.upper_margin = upper[k];
-        lv.scale = scale[k];
-        if (k > 0) {
-            covered_interval(fw, left[k], scale[k], left[k - 1], scale[k - 1], sampling, &lv.cx0, &lv.cx1);
-            covered_interval(fh, upper[k], scale[k], upper[k - 1], scale[k - 1], sampling, &lv.cy0, &lv.cy1);
-            if (lv.cx0 == lv.cx1 || lv.cy0 == lv.cy1) lv.cx0 = lv.cx1 = lv.cy0 = lv.cy1 = 0;
-        }
-        lv.first = first;
-        lv.points = (long long)wc * hc - (long long)(lv.cx1 - lv.cx0) * (lv.cy1 - lv.cy0);
-        first += lv.points;
-    }
-    if (fw_out) *fw_out = fw;
-    if (fh_out) *fh_out = fh;
-    return UGSM_OK;
-}
-
-// ---- the merged cloud of several windows of one pair (ugsm_point_cloud_fovea_multi; the rule across windows: include/ugsm.h) ----------
-struct MultiCloud {
-    int n, F, E, fw, fh, wc, hc, s;
-    int left[UGSM_MAX_BATCH][UGSM_MAX_LEVELS], upper[UGSM_MAX_BATCH][UGSM_MAX_LEVELS];
-    float scale[UGSM_MAX_LEVELS];
-};
-
-int cloud_multi_geometry(int W, int H, int levels, int F, int n, const int *off_x, const int *off_y, int sampling, MultiCloud &g)
-{
-    if (n < 1 || n > UGSM_MAX_BATCH || sampling < 1) return UGSM_ERR_BAD_ARG;
-    for (int j = 0; j < n; j++)
-        UCHK(fovea_level_mappings(W, H, levels, F, off_x ? off_x[j] : 0, off_y ? off_y[j] : 0, &g.fw, &g.fh, g.left[j], g.upper[j], g.scale));
-    g.n = n;
-    g.F = F;
-    g.E = (F - 1) * n + 1;
-    g.s = sampling;
-    g.wc = (g.fw + sampling - 1) / sampling;
-    g.hc = (g.fh + sampling - 1) / sampling;
-    return UGSM_OK;
-}
-
-// Entry e's row of the kernel's table, its planes apart: the mapping, the rectangles the entry leaves out -- (a) inside level k-1 of any
-// window, (b) inside level k of a higher-numbered window; each a column interval times a row interval (covered_interval) -- the column
-// segments between the rectangles' edges, and the entry's dense records.  `first`: the records of the entries before it.
-void cloud_multi_entry(const MultiCloud &g, int e, long long first, CloudEntry &en)
-{
-    const int k = e / g.n, j = e - k * g.n;  // (the last entry: level F-1 of window 0)
-    en = CloudEntry{};
-    en.left_margin = g.left[j][k];
-    en.upper_margin = g.upper[j][k];
-    en.scale = g.scale[k];
-    auto add = [&](int i, int m) {
-        CloudRect q;
-        covered_interval(g.fw, g.left[j][k], g.scale[k], g.left[i][m], g.scale[m], g.s, &q.cx0, &q.cx1);
-        covered_interval(g.fh, g.upper[j][k], g.scale[k], g.upper[i][m], g.scale[m], g.s, &q.cy0, &q.cy1);
-        if (q.cx0 < q.cx1 && q.cy0 < q.cy1 && en.nrect < kCloudMaxRects) en.rect[en.nrect++] = q;
-    };
-    if (k >= 1)
-        for (int i = 0; i < g.n; i++) add(i, k - 1);
-    if (k <= g.F - 2)
-        for (int i = j + 1; i < g.n; i++) add(i, k);
-    // the segments: between two neighbouring edges the same rectangles hold every column, so every column keeps the same number of rows
-    int xs[kCloudMaxSegs + 1], nx = 0;
-    xs[nx++] = 0;
-    for (int i = 0; i < en.nrect; i++)
-        for (int x : {en.rect[i].cx0, en.rect[i].cx1})
-            if (x > 0 && x < g.wc) xs[nx++] = x;
-    std::sort(xs, xs + nx);
-    nx = (int)(std::unique(xs, xs + nx) - xs);
-    long long records = 0;
-    for (int sg = 0; sg < nx; sg++) {
-        std::pair<int, int> rows[kCloudMaxRects];
-        int nr = 0;
-        for (int i = 0; i < en.nrect; i++)
-            if (en.rect[i].cx0 <= xs[sg] && xs[sg] < en.rect[i].cx1) rows[nr++] = {en.rect[i].cy0, en.rect[i].cy1};
-        std::sort(rows, rows + nr);
-        int out = 0, reach = 0;  // the length of the union of the row intervals
-        for (int i = 0; i < nr; i++) {
-            out += std::max(rows[i].second - std::max(rows[i].first, reach), 0);
-            reach = std::max(reach, rows[i].second);
-        }
-        en.seg_x[sg] = xs[sg];
-        en.seg_rows[sg] = g.hc - out;
-        en.seg_first[sg] = (unsigned)records;
-        records += (long long)((sg + 1 < nx ? xs[sg + 1] : g.wc) - xs[sg]) * (g.hc - out);
-    }
-    en.nseg = nx;
-    en.first = first;
-    en.points = records;
-}
-
-}  // namespace
-
-long long ugsm_fovea_multi_cloud_points(int W, int H, int levels, int fovea_levels, int n, const int *off_x, const int *off_y, int sampling,
-                                        long long *per_entry)
-{
-    MultiCloud g;
-    if (cloud_multi_geometry(W, H, levels, fovea_levels, n, off_x, off_y, sampling, g) != UGSM_OK) return -1;
-    long long total = 0;
-    for (int e = 0; e < g.E; e++) {
-        CloudEntry en;
-        cloud_multi_entry(g, e, total, en);
-        if (per_entry) per_entry[e] = en.points;
-        total += en.points;
-    }
-    return total;
-}
-
-int ugsm_fovea_level_mapping(int W, int H, int levels, int fovea_levels, int off_x, int off_y, int src_level, int *left_margin,
-                             int *upper_margin, float *scale)
-{
-    if (!left_margin || !upper_margin || !scale || src_level < 0 || src_level >= fovea_levels) return UGSM_ERR_BAD_ARG;
-    int left[UGSM_MAX_LEVELS], upper[UGSM_MAX_LEVELS], fw, fh;
-    float sc[UGSM_MAX_LEVELS];
-    if (fovea_level_mappings(W, H, levels, fovea_levels, off_x, off_y, &fw, &fh, left, upper, sc) != UGSM_OK) return UGSM_ERR_BAD_ARG;
-    *left_margin = left[src_level];
-    *upper_margin = upper[src_level];
-    *scale = sc[src_level];
-    return UGSM_OK;
-}
-
-long long ugsm_fovea_cloud_points(int W, int H, int levels, int fovea_levels, int off_x, int off_y, int sampling, long long *per_level)
-{
-    CloudStack sk;
-    if (cloud_stack_table(W, H, levels, fovea_levels, off_x, off_y, sampling, sk, nullptr, nullptr) != UGSM_OK) return -1;
-    for (int k = 0; per_level && k < fovea_levels; k++) per_level[k] = sk.lv[k].points;
-    return sk.lv[fovea_levels - 1].first + sk.lv[fovea_levels - 1].points;
-}
-
-int ugsm_triangulate_fovea(ugsm_ctx *ctx, int slot, const float *d_stackx, const float *d_stacky, int fovW, int fovH, int src_level,
-                           int left_margin, int upper_margin, float scale, const double *P1, const double *P2, float *d_xyz)
-{
-    Slot *s;
-    UCHK(get_slot(ctx, slot, &s));
-    if (!d_stackx || !d_stacky || !P1 || !P2 || !d_xyz || fovW < 1 || fovH < 1 || src_level < 0) return UGSM_ERR_BAD_ARG;
-    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
-    {
-        Timer t(ctx, s, slot, KC_MISC, (double)fovW * fovH);
-        launch_triangulate_fovea(s->st, d_stackx, d_stacky, fovW, fovH, src_level, left_margin, upper_margin, scale, P1, P2, d_xyz);
-    }
-    HIPCHK(ctx, hipGetLastError());
-    return UGSM_OK;
-}
-
-// ---- row f-1, the coloured point cloud (getPointCloud.cpp doReconstructionRGB[_FOV], :615-722) ----------------------------------------
-
-void ugsm_default_cloud_params(ugsm_cloud_params *p)
-{
-    if (!p) return;
-    p->sampling = 1;
-    p->format = UGSM_CLOUD_PCL32;
-    p->compact = 0;
-    p->min_conf = -INFINITY;
-    p->z_min = -INFINITY;
-    p->z_max = INFINITY;
-}
-
-long long ugsm_cloud_points(int W, int H, int sampling)
-{
-    if (W < 1 || H < 1 || sampling < 1) return -1;
-    return (long long)((W + sampling - 1) / sampling) * ((H + sampling - 1) / sampling);
-}
-
-long long ugsm_resized_cloud_points(int W, int H, float factor)
-{
-    if (W < 1 || H < 1 || !(factor > 0.0f && factor <= 1.0f)) return -1;
-    const int dw = (int)((float)W * factor), dh = (int)((float)H * factor);  // cv::Size(W * f, H * f): float products, truncated
-    if (dw < 1 || dh < 1) return -1;
-    return (long long)dw * dh;
-}
-
-namespace {
-
-// the checks every entry point shares (no device needed); pw x ph: the planes the points come from; resized: the resized forms, which
-// take no sampling (p->sampling 1) and a factor in (0, 1] that leaves both sides at least 1
-int cloud_args_ok(const float *dx, const float *dy, const float *conf, const uint8_t *rgb, int W, int H, int stride, int bpp, int pw, int ph,
-                  const double *P1, const double *P2, const ugsm_cloud_params *p, const void *points, long long cap, const long long *count,
-                  bool resized = false, float factor = 1.0f)
-{
-    if (!dx || !dy || !rgb || !P1 || !P2 || !p || !points || !count) return UGSM_ERR_BAD_ARG;
-    if (W < 1 || H < 1 || pw < 1 || ph < 1 || (long long)W * H > kMaxPixels || (long long)pw * ph > kMaxPixels) return UGSM_ERR_BAD_ARG;
-    if ((long long)stride < (long long)bpp * W || p->sampling < 1 || (p->format != UGSM_CLOUD_PCL32 && p->format != UGSM_CLOUD_XYZRGB16)) return UGSM_ERR_BAD_ARG;
-    if (std::isnan(p->min_conf) || std::isnan(p->z_min) || std::isnan(p->z_max) || p->z_min > p->z_max) return UGSM_ERR_BAD_ARG;
-    if (!conf && p->min_conf > -INFINITY) return UGSM_ERR_BAD_ARG;  // (a confidence test without a confidence plane)
-    if (cap < 0 || ((uintptr_t)points & 15) || ((uintptr_t)count & 7)) return UGSM_ERR_BAD_ARG;
-    if (resized && (p->sampling != 1 || ugsm_resized_cloud_points(pw, ph, factor) < 1)) return UGSM_ERR_BAD_ARG;
-    return UGSM_OK;
-}
-
-// the CloudArgs of a call whose points come from the pw x ph planes dx, dy, conf (conf is only read by a compact cloud)
-CloudArgs cloud_args(const float *dx, const float *dy, const float *conf, const uint8_t *rgb, int W, int H, int stride, int pw, int ph,
-                     const ugsm_cloud_params *p, void *points, long long cap, long long *count)
-{
-    CloudArgs a{};
-    a.dx = dx;
-    a.dy = dy;
-    a.conf = p->compact ? conf : nullptr;
-    a.pw = pw;
-    a.ph = ph;
-    a.rgb = rgb;
-    a.W = W;
-    a.H = H;
-    a.stride = stride;
-    a.s = p->sampling;
-    a.format = p->format;
-    a.compact = p->compact != 0;
-    a.min_conf = p->min_conf;
-    a.z_min = p->z_min;
-    a.z_max = p->z_max;
-    a.points = points;
-    a.cap = cap;
-    a.count = count;
-    return a;
-}
-
-// the resized map: (int)(pw * factor) x (int)(ph * factor) points and cv::resize's scales (resize.cpp: inv_scale = (double)dsize / ssize,
-// scale = 1. / inv_scale)
-CloudResize resize_args(CloudArgs &a, float factor, int colour_mapped)
-{
-    a.wc = (int)((float)a.pw * factor);
-    a.hc = (int)((float)a.ph * factor);
-    CloudResize rz{};
-    rz.scale_x = 1. / ((double)a.wc / a.pw);
-    rz.scale_y = 1. / ((double)a.hc / a.ph);
-    rz.factor = factor;
-    rz.same_size = a.wc == a.pw && a.hc == a.ph;
-    rz.colour_mapped = colour_mapped;
-    return rz;
-}
-
-int point_cloud(ugsm_ctx *ctx, int slot, CloudArgs &a, bool fovea, const double *P1, const double *P2, const CloudResize *rz = nullptr)
-{
-    Slot *s;
-    UCHK(get_slot(ctx, slot, &s));
-    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
-    if (!rz) {  // (the resized forms' grid is resize_args')
-        a.wc = (a.pw + a.s - 1) / a.s;
-        a.hc = (a.ph + a.s - 1) / a.s;
-    }
-    a.nchunk = cloud_chunks(a.hc);
-    a.fmt = ctx->hooks.input_format;
-    a.cnt = nullptr;
-    if (a.compact) {
-        const size_t totals = (size_t)a.wc + (size_t)cloud_strips(a.wc), need = (size_t)a.wc * a.nchunk + totals;
-        if (need > s->cloud_cap) HIPCHK(ctx, hipStreamSynchronize(s->st));  // (the buffer being replaced may still be read by an earlier cloud)
-        UCHK(grow(ctx, s->cloud_cnt, s->cloud_cap, need));
-        a.cnt = s->cloud_cnt;
-        HIPCHK(ctx, hipMemsetAsync(a.cnt + (size_t)a.wc * a.nchunk, 0, totals * sizeof(unsigned), s->st));
-    }
-    {
-        Timer t(ctx, s, slot, KC_MISC, (double)a.wc * a.hc);
-        launch_point_cloud(s->st, a, fovea, P1, P2, rz);
-    }
-    HIPCHK(ctx, hipGetLastError());
-    return UGSM_OK;
-}
-
-// the foveated forms' planes (level src_level of the stacks) and mapping (ugsm_fovea_mapping)
-int fovea_cloud_args(CloudArgs &a, const float *stackx, const float *stacky, const float *stackc, int fovW, int fovH, int src_level,
-                     int left_margin, int upper_margin, float scale, const uint8_t *rgb, int W, int H, int stride, const ugsm_cloud_params *p,
-                     void *points, long long cap, long long *count)
-{
-    if (src_level < 0 || src_level >= UGSM_MAX_LEVELS || !std::isfinite(scale)) return UGSM_ERR_BAD_ARG;
-    const size_t lvl = (size_t)src_level * fovW * fovH;
-    a = cloud_args(stackx + lvl, stacky + lvl, stackc ? stackc + lvl : nullptr, rgb, W, H, stride, fovW, fovH, p, points, cap, count);
-    a.left_margin = left_margin;
-    a.upper_margin = upper_margin;
-    a.scale = scale;
-    return UGSM_OK;
-}
-
-}  // namespace
-
-int ugsm_point_cloud(ugsm_ctx *ctx, int slot, const float *d_dispx, const float *d_dispy, const float *d_conf, const uint8_t *d_rgbL, int W, int H,
-                     int stride, const double *P1, const double *P2, const ugsm_cloud_params *p, void *d_points, long long cap_points,
-                     long long *d_count)
-{
-    if (!ctx) return UGSM_ERR_BAD_ARG;
-    UCHK(cloud_args_ok(d_dispx, d_dispy, d_conf, d_rgbL, W, H, stride, ugsm_input_bytes_per_pixel(ctx->hooks.input_format), W, H, P1, P2, p, d_points, cap_points, d_count));
-    CloudArgs a = cloud_args(d_dispx, d_dispy, d_conf, d_rgbL, W, H, stride, W, H, p, d_points, cap_points, d_count);
-    return point_cloud(ctx, slot, a, false, P1, P2);
-}
-
-int ugsm_point_cloud_fovea(ugsm_ctx *ctx, int slot, const float *d_stackx, const float *d_stacky, const float *d_stackc, int fovW, int fovH,
-                           int src_level, int left_margin, int upper_margin, float scale, const uint8_t *d_rgbL, int W, int H, int stride,
-                           const double *P1, const double *P2, const ugsm_cloud_params *p, void *d_points, long long cap_points, long long *d_count)
-{
-    if (!ctx) return UGSM_ERR_BAD_ARG;
-    UCHK(cloud_args_ok(d_stackx, d_stacky, d_stackc, d_rgbL, W, H, stride, ugsm_input_bytes_per_pixel(ctx->hooks.input_format), fovW, fovH, P1, P2, p, d_points, cap_points, d_count));
-    CloudArgs a;
-    UCHK(fovea_cloud_args(a, d_stackx, d_stacky, d_stackc, fovW, fovH, src_level, left_margin, upper_margin, scale, d_rgbL, W, H, stride, p,
-                          d_points, cap_points, d_count));
-    return point_cloud(ctx, slot, a, true, P1, P2);
-}
-
-// The whole stack as one cloud: level 0, then 1 .. F-1, each without the points the finer level already covers (cloud_stack_table)
-int ugsm_point_cloud_fovea_all(ugsm_ctx *ctx, int slot, const float *d_stackx, const float *d_stacky, const float *d_stackc, int W, int H,
-                               int off_x, int off_y, const uint8_t *d_rgbL, int stride, const double *P1, const double *P2,
-                               const ugsm_cloud_params *p, void *d_points, long long cap_points, long long *d_count, long long *d_level_counts)
-{
-    if (!ctx || !p || ((uintptr_t)d_level_counts & 7)) return UGSM_ERR_BAD_ARG;
-    CloudStack sk;
-    int fw, fh;
-    UCHK(cloud_stack_table(W, H, ctx->cfg.levels, ctx->cfg.fovea_levels, off_x, off_y, p->sampling, sk, &fw, &fh));
-    UCHK(cloud_args_ok(d_stackx, d_stacky, d_stackc, d_rgbL, W, H, stride, ugsm_input_bytes_per_pixel(ctx->hooks.input_format), fw, fh, P1, P2, p, d_points, cap_points, d_count));
-    sk.level_counts = d_level_counts;
-    CloudArgs a = cloud_args(d_stackx, d_stacky, d_stackc, d_rgbL, W, H, stride, fw, fh, p, d_points, cap_points, d_count);
-    Slot *s;
-    UCHK(get_slot(ctx, slot, &s));
-    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
-    a.wc = (a.pw + a.s - 1) / a.s;
-    a.hc = (a.ph + a.s - 1) / a.s;
-    a.nchunk = cloud_chunks(a.hc);
-    a.fmt = ctx->hooks.input_format;
-    a.cnt = nullptr;
-    if (a.compact) {  // as point_cloud, over the F * wc virtual columns and F * strips virtual strips
-        const size_t cols = (size_t)sk.F * a.wc, totals = cols + (size_t)sk.F * sk.strips, need = cols * a.nchunk + totals;
-        if (need > s->cloud_cap) HIPCHK(ctx, hipStreamSynchronize(s->st));
-        UCHK(grow(ctx, s->cloud_cnt, s->cloud_cap, need));
-        a.cnt = s->cloud_cnt;
-        HIPCHK(ctx, hipMemsetAsync(a.cnt + cols * a.nchunk, 0, totals * sizeof(unsigned), s->st));
-    }
-    {
-        Timer t(ctx, s, slot, KC_MISC, (double)sk.F * a.wc * a.hc);
-        launch_point_cloud_stack(s->st, a, sk, P1, P2);
-    }
-    HIPCHK(ctx, hipGetLastError());
-    return UGSM_OK;
-}
-
-// The stacks of n windows of one pair as one cloud: the entries level-major, each without what the rule across windows leaves out
-// (cloud_multi_entry).  The table goes up on the slot's stream from a page-locked copy; nothing here waits for the stream unless a
-// buffer has to grow.
-int ugsm_point_cloud_fovea_multi(ugsm_ctx *ctx, int slot, int n, const float *const *d_stack, int W, int H, const int *off_x, const int *off_y,
-                                 const uint8_t *d_rgbL, int stride, const double *P1, const double *P2, const ugsm_cloud_params *p, void *d_points,
-                                 long long cap_points, long long *d_count, long long *d_entry_counts)
-{
-    if (!ctx || !p || !d_stack || n < 1 || n > UGSM_MAX_BATCH || ((uintptr_t)d_entry_counts & 7)) return UGSM_ERR_BAD_ARG;
-    for (int j = 0; j < n; j++)
-        if (!d_stack[j]) return UGSM_ERR_BAD_ARG;
-    MultiCloud g;
-    const int F = ctx->cfg.fovea_levels;
-    UCHK(cloud_multi_geometry(W, H, ctx->cfg.levels, F, n, off_x, off_y, p->sampling, g));
-    const size_t fn = (size_t)g.fw * g.fh, plane = (size_t)F * fn;
-    UCHK(cloud_args_ok(d_stack[0], d_stack[0] + plane, d_stack[0] + 2 * plane, d_rgbL, W, H, stride, ugsm_input_bytes_per_pixel(ctx->hooks.input_format), g.fw,
-                       g.fh, P1, P2, p, d_points, cap_points, d_count));
-    CloudArgs a = cloud_args(nullptr, nullptr, nullptr, d_rgbL, W, H, stride, g.fw, g.fh, p, d_points, cap_points, d_count);
-    Slot *s;
-    UCHK(get_slot(ctx, slot, &s));
-    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
-    a.wc = g.wc;
-    a.hc = g.hc;
-    a.nchunk = cloud_chunks(a.hc);
-    a.fmt = ctx->hooks.input_format;
-    a.cnt = nullptr;
-    const int E = g.E, strips = cloud_strips(a.wc);
-    if ((size_t)E > s->mc_tab_cap || (size_t)E > s->mc_tab_h_rows) {  // (an earlier call's kernels may still read the table, its upload the copies)
-        HIPCHK(ctx, hipStreamSynchronize(s->st));
-        UCHK(grow(ctx, s->mc_tab, s->mc_tab_cap, (size_t)E));
-        if ((size_t)E > s->mc_tab_h_rows) {
-            if (s->mc_tab_h) HIPCHK(ctx, hipHostFree(s->mc_tab_h));
-            s->mc_tab_h = nullptr;
-            s->mc_tab_h_rows = 0;
-            HIPCHK(ctx, hipHostMalloc((void **)&s->mc_tab_h, (size_t)Slot::kMcRing * E * sizeof(CloudEntry), hipHostMallocDefault));
-            s->mc_tab_h_rows = (size_t)E;
-            for (bool &set : s->mc_ev_set) set = false;
-        }
-    }
-    if (a.compact) {  // as point_cloud, over the E * wc virtual columns and E * strips virtual strips
-        const size_t cols = (size_t)E * a.wc, totals = cols + (size_t)E * strips, need = cols * a.nchunk + totals;
-        if (need > s->cloud_cap) HIPCHK(ctx, hipStreamSynchronize(s->st));
-        UCHK(grow(ctx, s->cloud_cnt, s->cloud_cap, need));
-        a.cnt = s->cloud_cnt;
-        HIPCHK(ctx, hipMemsetAsync(a.cnt + cols * a.nchunk, 0, totals * sizeof(unsigned), s->st));
-    }
-    const int turn = s->mc_next;
-    s->mc_next = (turn + 1) % Slot::kMcRing;
-    if (!s->mc_ev[turn]) HIPCHK(ctx, hipEventCreateWithFlags(&s->mc_ev[turn], hipEventDisableTiming));
-    if (s->mc_ev_set[turn]) HIPCHK(ctx, hipEventSynchronize(s->mc_ev[turn]));  // (the upload of the call kMcRing back: long done)
-    CloudEntry *const rows = s->mc_tab_h + (size_t)turn * s->mc_tab_h_rows;
-    const bool use_conf = a.compact && p->min_conf > -INFINITY;  // (the confidence planes are read by nothing else)
-    long long total = 0;
-    for (int e = 0; e < E; e++) {
-        cloud_multi_entry(g, e, total, rows[e]);
-        const int k = e / n, j = e - k * n;
-        rows[e].dx = d_stack[j] + (size_t)k * fn;
-        rows[e].dy = rows[e].dx + plane;
-        rows[e].conf = use_conf ? rows[e].dx + 2 * plane : nullptr;
-        total += rows[e].points;
-    }
-    HIPCHK(ctx, hipMemcpyAsync(s->mc_tab, rows, (size_t)E * sizeof(CloudEntry), hipMemcpyHostToDevice, s->st));
-    HIPCHK(ctx, hipEventRecord(s->mc_ev[turn], s->st));
-    s->mc_ev_set[turn] = true;
-    CloudMulti mu{};
-    mu.table = s->mc_tab;
-    mu.E = E;
-    mu.total = total;
-    mu.entry_counts = d_entry_counts;
-    {
-        Timer t(ctx, s, slot, KC_MISC, (double)E * a.wc * a.hc);
-        launch_point_cloud_multi(s->st, a, mu, P1, P2);
-    }
-    HIPCHK(ctx, hipGetLastError());
-    return UGSM_OK;
-}
-
-// ---- row f-1, the resized cloud (getPointCloud.cpp doReconstruction_resized / doReconstructionFOV_resized, :724-884) ----------------
-
-int ugsm_point_cloud_resized(ugsm_ctx *ctx, int slot, const float *d_dispx, const float *d_dispy, const float *d_conf, const uint8_t *d_rgbL,
-                             int W, int H, int stride, const double *P1, const double *P2, float factor, const ugsm_cloud_params *p,
-                             void *d_points, long long cap_points, long long *d_count)
-{
-    if (!ctx) return UGSM_ERR_BAD_ARG;
-    UCHK(cloud_args_ok(d_dispx, d_dispy, d_conf, d_rgbL, W, H, stride, ugsm_input_bytes_per_pixel(ctx->hooks.input_format), W, H, P1, P2, p, d_points, cap_points, d_count, true, factor));
-    CloudArgs a = cloud_args(d_dispx, d_dispy, d_conf, d_rgbL, W, H, stride, W, H, p, d_points, cap_points, d_count);
-    const CloudResize rz = resize_args(a, factor, 0);
-    return point_cloud(ctx, slot, a, false, P1, P2, &rz);
-}
-
-int ugsm_point_cloud_resized_fovea(ugsm_ctx *ctx, int slot, const float *d_stackx, const float *d_stacky, const float *d_stackc, int fovW,
-                                   int fovH, int src_level, int left_margin, int upper_margin, float scale, const uint8_t *d_rgbL, int W, int H,
-                                   int stride, const double *P1, const double *P2, float factor, int colour_mapped, const ugsm_cloud_params *p,
-                                   void *d_points, long long cap_points, long long *d_count)
-{
-    if (!ctx) return UGSM_ERR_BAD_ARG;
-    UCHK(cloud_args_ok(d_stackx, d_stacky, d_stackc, d_rgbL, W, H, stride, ugsm_input_bytes_per_pixel(ctx->hooks.input_format), fovW, fovH, P1, P2, p, d_points, cap_points, d_count, true, factor));
-    if (colour_mapped != 0 && colour_mapped != 1) return UGSM_ERR_BAD_ARG;
-    CloudArgs a;
-    UCHK(fovea_cloud_args(a, d_stackx, d_stacky, d_stackc, fovW, fovH, src_level, left_margin, upper_margin, scale, d_rgbL, W, H, stride, p,
-                          d_points, cap_points, d_count));
-    const CloudResize rz = resize_args(a, factor, colour_mapped);
-    return point_cloud(ctx, slot, a, true, P1, P2, &rz);
-}
-
-// ---- the cloud from the queue (ugsm_enqueue_*_cloud*): a call of n pairs and their clouds -------------------------------------------
-// The match goes onto the slot's stream as the batch entry points above put it there (the same helpers in the same order, so the planes are
-// the same bits); the clouds follow on the same stream.  A call the matcher runs in lockstep gets ONE cloud launch for its pairs (compact:
-// two; launch_point_cloud_batch), from a table uploaded on the stream ahead of it.  A call the matcher runs pair by pair (one pair; the
-// full-mode LR check, early exit) gets pair b's cloud behind pair b's match: a managed call of that kind reuses the slot's image and plane
-// buffers for every pair.  So does a call whose pairs each evaluate more than kBatchMaxPixels sampled points -- the size above which the
-// matcher's own levels go pair by pair, because one pair's launch fills the chip many times over and a batch index buys nothing.
-namespace {
-constexpr size_t kCqWords = 1 + UGSM_MAX_LEVELS;  // a managed pair's count words: the count, the level counts
-
-int queue_cloud_launch(ugsm_ctx *ctx, Slot &s, int si, int b0, int n, bool stack, const ugsm_queue_cloud *spec)
-{
-    const CloudPair &shape = s.cq_tab_h[b0];
-    {
-        Timer t(ctx, &s, si, KC_MISC, (double)n * (stack ? shape.sk.F : 1) * shape.a.wc * shape.a.hc);
-        launch_point_cloud_batch(s.st, s.cq_tab + b0, n, shape, stack, spec->P1, spec->P2);
-    }
-    HIPCHK(ctx, hipGetLastError());
-    return UGSM_OK;
-}
-}  // namespace
-
-static int queue_cloud_submit(ugsm_ctx *ctx, int slot, const CloudCall *call)
-{
-    Slot *s;
-    UCHK(get_slot(ctx, slot, &s));
-    if (!call || !call->spec || call->n < 1 || call->n > UGSM_MAX_BATCH) return UGSM_ERR_BAD_ARG;
-    const ugsm_queue_cloud &spec = *call->spec;
-    const ugsm_cloud_params &p = spec.params;
-    const int n = call->n, W = call->W, H = call->H, stride = call->stride, F = ctx->cfg.fovea_levels;
-    const bool fovea = call->fovea != 0, managed = call->managed != 0, planes = managed && spec.want_planes != 0;
-    if (fovea && F < 2) return UGSM_ERR_BAD_ARG;
-    if (W < 1 || H < 1) return UGSM_ERR_BAD_ARG;
-    if (stride < input_row_bytes(ctx, W)) return UGSM_ERR_SIZE_MISMATCH;
-    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
-    s->cq_n = 0;
-    const bool by_pair = n == 1 || (fovea ? fovea_batch_runs_pair_by_pair(ctx) : batch_runs_pair_by_pair(ctx));
-    int fw = W, fh = H;
-    if (fovea) UCHK(ugsm_fovea_dims(W, H, ctx->cfg.levels, F, &fw, &fh));
-    const size_t px = (size_t)W * H, fn = (size_t)fw * fh, stackn = (size_t)F * fn;
-    const size_t plane = fovea ? stackn : px;  // floats per result plane: the pair's result is three of them
-    const int step = p.format == UGSM_CLOUD_PCL32 ? 32 : 16;
-
-    // 1. where every pair's images, state and result lie on the device
-    const uint8_t *dL[UGSM_MAX_BATCH], *dR[UGSM_MAX_BATCH];
-    float *state[UGSM_MAX_BATCH], *res[UGSM_MAX_BATCH];
-    const size_t st_per = fovea ? ((3 * fn + 63) & ~(size_t)63) : 0, res_per = (3 * plane + 63) & ~(size_t)63;
-    if (managed) {
-        // the slot's uploads and hout: [states][results], one of each for a call that runs pair by pair, n otherwise
-        const int copies = by_pair ? 1 : n;
-        const size_t img = ((size_t)stride * H + 255) & ~(size_t)255;
-        if (img * copies > s->rgb_cap) {
-            size_t c = s->rgb_cap;
-            UCHK(grow(ctx, s->rgbL, c, img * copies));
-            UCHK(grow(ctx, s->rgbR, s->rgb_cap, img * copies));
-        }
-        UCHK(grow(ctx, s->hout, s->hout_cap, std::max(copies * (st_per + res_per), s->hout_cap)));
-        for (int b = 0; b < n; b++) {
-            const int k = by_pair ? 0 : b;
-            dL[b] = s->rgbL + k * img;
-            dR[b] = s->rgbR + k * img;
-            state[b] = s->hout + k * st_per;
-            res[b] = s->hout + copies * st_per + k * res_per;
-        }
-    } else {
-        UCHK(grow(ctx, s->hout, s->hout_cap, std::max(st_per * n, s->hout_cap)));
-        for (int b = 0; b < n; b++) {
-            if (!call->job[b].L || !call->job[b].R || !call->job[b].out) return UGSM_ERR_BAD_ARG;
-            dL[b] = call->job[b].L;
-            dR[b] = call->job[b].R;
-            state[b] = s->hout + (by_pair ? 0 : b * st_per);
-            res[b] = call->job[b].out;
-        }
-    }
-
-    // 2. the table: every pair's cloud arguments
-    if ((size_t)n > s->cq_tab_cap) {
-        if (s->cq_tab_h) HIPCHK(ctx, hipHostFree(s->cq_tab_h));
-        s->cq_tab_h = nullptr;
-        UCHK(grow(ctx, s->cq_tab, s->cq_tab_cap, (size_t)kMaxBatch));
-        HIPCHK(ctx, hipHostMalloc((void **)&s->cq_tab_h, kMaxBatch * sizeof(CloudPair), hipHostMallocDefault));
-    }
-    CloudStack sk[UGSM_MAX_BATCH];
-    long long dense[UGSM_MAX_BATCH], max_cap = 0;
-    for (int b = 0; b < n; b++) {
-        if (fovea) {
-            int w2, h2;
-            UCHK(cloud_stack_table(W, H, ctx->cfg.levels, F, call->job[b].off_x, call->job[b].off_y, p.sampling, sk[b], &w2, &h2));
-            dense[b] = sk[b].lv[F - 1].first + sk[b].lv[F - 1].points;
-        } else {
-            dense[b] = ugsm_cloud_points(W, H, p.sampling);
-        }
-        s->cq_cap[b] = managed ? (spec.max_points > 0 ? std::min(spec.max_points, dense[b]) : dense[b]) : call->job[b].cap;
-        max_cap = std::max(max_cap, s->cq_cap[b]);
-    }
-    if (managed) {
-        s->cq_stride = (size_t)max_cap * step;
-        UCHK(grow(ctx, s->cq_pts, s->cq_pts_cap, std::max(s->cq_stride * n, (size_t)16)));
-        UCHK(grow(ctx, s->cq_words, s->cq_words_cap, kMaxBatch * kCqWords));
-        if (!s->cq_words_h) HIPCHK(ctx, hipHostMalloc((void **)&s->cq_words_h, kMaxBatch * kCqWords * sizeof(long long), hipHostMallocDefault));
-    }
-    const int wc = (fw + p.sampling - 1) / p.sampling, hc = (fh + p.sampling - 1) / p.sampling, nchunk = cloud_chunks(hc);
-    const size_t cols = (size_t)(fovea ? F : 1) * wc, totals = cols + (size_t)(fovea ? F : 1) * cloud_strips(wc), cnt_per = cols * nchunk + totals;
-    if (p.compact) UCHK(grow(ctx, s->cloud_cnt, s->cloud_cap, cnt_per * n));
-    for (int b = 0; b < n; b++) {
-        const CloudJob &j = call->job[b];
-        void *points = managed ? (void *)(s->cq_pts + b * s->cq_stride) : j.points;
-        long long *count = managed ? s->cq_words + b * kCqWords : j.count;
-        long long *levels = managed ? s->cq_words + b * kCqWords + 1 : j.level_counts;
-        UCHK(cloud_args_ok(res[b], res[b] + plane, res[b] + 2 * plane, dL[b], W, H, stride, ugsm_input_bytes_per_pixel(ctx->hooks.input_format), fw, fh,
-                           spec.P1, spec.P2, &p, points, s->cq_cap[b], count));
-        if ((uintptr_t)levels & 7) return UGSM_ERR_BAD_ARG;
-        CloudPair &row = s->cq_tab_h[b];
-        row = CloudPair{};
-        row.a = cloud_args(res[b], res[b] + plane, res[b] + 2 * plane, dL[b], W, H, stride, fw, fh, &p, points, s->cq_cap[b], count);
-        row.a.wc = wc;
-        row.a.hc = hc;
-        row.a.nchunk = nchunk;
-        row.a.fmt = ctx->hooks.input_format;
-        row.a.cnt = p.compact ? s->cloud_cnt + b * cnt_per : nullptr;
-        if (fovea) {
-            row.sk = sk[b];
-            row.sk.level_counts = levels;
-        }
-    }
-    HIPCHK(ctx, hipMemcpyAsync(s->cq_tab, s->cq_tab_h, n * sizeof(CloudPair), hipMemcpyHostToDevice, s->st));
-    if (p.compact) HIPCHK(ctx, hipMemsetAsync(s->cloud_cnt, 0, cnt_per * n * sizeof(unsigned), s->st));  // (the totals of every pair's region)
-
-    // 3. the match, and the clouds behind it
-    const size_t img_bytes = (size_t)stride * H;
-    auto download = [&](int b) -> int {  // a managed pair's planes, where they are wanted
-        if (!planes) return UGSM_OK;
-        for (int k = 0; k < 3; k++)
-            HIPCHK(ctx, hipMemcpyAsync(call->job[b].planes[k], res[b] + k * plane, plane * sizeof(float), hipMemcpyDeviceToHost, s->st));
-        return UGSM_OK;
-    };
-    const bool cloud_by_pair = by_pair || !batch_level(ctx, (fovea ? F : 1) * wc, hc);  // (a pair's sampled points against kBatchMaxPixels)
-    if (by_pair) {
-        for (int b = 0; b < n; b++) {
-            if (managed) UCHK(stage_in(ctx, *s, call->job[b].L, call->job[b].R, W, H, stride));
-            if (fovea) {
-                UCHK(enqueue_foveated(ctx, *s, slot, 1, dL + b, dR + b, W, H, stride, &call->job[b].off_x, &call->job[b].off_y, state + b, res + b, nullptr, nullptr));
-            } else {
-                UCHK(enqueue_pyramids(ctx, *s, slot, dL[b], dR[b], W, H, stride, 0, nullptr, true));
-                UCHK(enqueue_full_lr(ctx, *s, slot, res[b]));
-            }
-            UCHK(download(b));
-            UCHK(queue_cloud_launch(ctx, *s, slot, b, 1, fovea, &spec));
-        }
-    } else {
-        if (managed)
-            for (int b = 0; b < n; b++) {
-                HIPCHK(ctx, hipMemcpyAsync(const_cast<uint8_t *>(dL[b]), call->job[b].L, img_bytes, hipMemcpyHostToDevice, s->st));
-                HIPCHK(ctx, hipMemcpyAsync(const_cast<uint8_t *>(dR[b]), call->job[b].R, img_bytes, hipMemcpyHostToDevice, s->st));
-            }
-        if (fovea) {
-            int ox[UGSM_MAX_BATCH], oy[UGSM_MAX_BATCH];
-            for (int b = 0; b < n; b++) {
-                ox[b] = call->job[b].off_x;
-                oy[b] = call->job[b].off_y;
-            }
-            UCHK(enqueue_foveated(ctx, *s, slot, n, dL, dR, W, H, stride, ox, oy, state, res, nullptr, nullptr));
-        } else {
-            UCHK(enqueue_pyramids(ctx, *s, slot, dL, dR, n, W, H, stride, -1, nullptr, true));
-            s->lr_ran = false;
-            s->lr_fov_pairs = 0;
-            UCHK(enqueue_full(ctx, *s, slot, res));
-        }
-        for (int b = 0; b < n; b++) UCHK(download(b));
-        if (cloud_by_pair)
-            for (int b = 0; b < n; b++) UCHK(queue_cloud_launch(ctx, *s, slot, b, 1, fovea, &spec));
-        else
-            UCHK(queue_cloud_launch(ctx, *s, slot, 0, n, fovea, &spec));
-    }
-    if (managed) {
-        HIPCHK(ctx, hipMemcpyAsync(s->cq_words_h, s->cq_words, n * kCqWords * sizeof(long long), hipMemcpyDeviceToHost, s->st));
-        s->cq_n = n;
-        s->cq_step = step;
-        s->cq_levels = fovea ? F : 0;
-    }
-    return mark_done(ctx, *s);
-}
-
-static int queue_cloud_finish(ugsm_ctx *ctx, int slot, int n, ugsm_cloud_result *res, void *(*staging)(void *, int, long long), void *user)
-{
-    Slot *s;
-    UCHK(get_slot(ctx, slot, &s));
-    if (!res || !staging || n < 1 || n != s->cq_n) return ctx_fail(ctx, UGSM_ERR_STATE, "the slot holds no managed cloud call of that many pairs");
-    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
-    for (int b = 0; b < n; b++) {
-        const long long *w = s->cq_words_h + b * kCqWords;
-        ugsm_cloud_result &r = res[b];
-        r = ugsm_cloud_result{};
-        r.count = w[0];
-        r.stored = std::min(w[0], s->cq_cap[b]);
-        r.point_step = s->cq_step;
-        r.levels = s->cq_levels;
-        for (int l = 0; l < s->cq_levels; l++) r.level_counts[l] = w[1 + l];
-    }
-    s->cq_n = 0;
-    for (int b = 0; b < n; b++) {
-        if (res[b].stored < 1) continue;
-        const long long bytes = res[b].stored * s->cq_step;
-        res[b].points = staging(user, b, bytes);
-        if (!res[b].points) return ctx_fail(ctx, UGSM_ERR_NOMEM, "no page-locked memory for a pair's cloud");
-        HIPCHK(ctx, hipMemcpyAsync(res[b].points, s->cq_pts + b * s->cq_stride, (size_t)bytes, hipMemcpyDeviceToHost, s->st));
-    }
-    return mark_done(ctx, *s);
 }
 
 // hierarchicalDisparity, MatchGPULib.cpp:2589-2701
