@@ -15,6 +15,8 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = os.path.join(_HERE, "libugsm_oracle.so")
 _GOLD = os.path.join(_HERE, "_ref", "libgold.so")
+_MATCHLIB = os.path.join(_HERE, "_ref", "libmatchlib_cpu.so")
+_REFERENCE = "/root/reference"
 
 _f32p = C.POINTER(C.c_float)
 _u8p = C.POINTER(C.c_uint8)
@@ -22,13 +24,19 @@ _i32p = C.POINTER(C.c_int)
 
 
 def build(force: bool = False) -> None:
-    """Compile the oracle (and oracle/_ref when /root/reference is present)."""
+    """Compile the oracle and, when the reference checkout is present, whichever of oracle/_ref/libgold.so (the reference's CPU
+    convolution) and oracle/_ref/libmatchlib_cpu.so (the reference's stage file MatchLib.cu, run on the CPU through oracle/ref_cpu/)
+    is missing or older than what it is built from."""
     src = os.path.join(_HERE, "ugsm_oracle.c")
     stale = (not os.path.exists(_LIB)) or os.path.getmtime(_LIB) < os.path.getmtime(src)
     if force or stale:
         subprocess.check_call(["make", "-s", "-C", _HERE, "all"])
-    if os.path.isdir("/root/reference") and (force or not os.path.exists(_GOLD)):
-        subprocess.check_call(["make", "-s", "-C", _HERE, "ref"])
+    if os.path.isdir(_REFERENCE):
+        if force or not os.path.exists(_GOLD):
+            subprocess.check_call(["make", "-s", "-C", _HERE, "ref-gold"])
+        shim = [os.path.join(_HERE, "ref_cpu", f) for f in ("cuda_runtime.h", "helper_cuda.h", "shim_exports.cpp", "launch_rewrite.py")]
+        if force or not os.path.exists(_MATCHLIB) or any(os.path.getmtime(f) > os.path.getmtime(_MATCHLIB) for f in shim):
+            subprocess.check_call(["make", "-s", "-C", _HERE, "ref-matchlib"])
 
 
 _lib = None
@@ -48,6 +56,19 @@ def gold_lib():
     if not os.path.exists(_GOLD):
         return None
     return C.CDLL(_GOLD)
+
+
+_matchlib = None
+
+
+def matchlib_cpu():
+    """The reference's own stage functions (MatchLib.cu compiled for the CPU, oracle/_ref), or None where it was not built."""
+    global _matchlib
+    if _matchlib is None:
+        if not os.path.exists(_MATCHLIB):
+            return None
+        _matchlib = C.CDLL(_MATCHLIB)
+    return _matchlib
 
 
 def _fp(a):

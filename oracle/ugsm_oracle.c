@@ -1,9 +1,11 @@
 /*
  * ugsm_oracle.c -- CPU restatement of gerac83/ug_stereomatcher's pyramidal matcher.
  *
- * TEST INFRASTRUCTURE ONLY (see ugsm_oracle.h).  "parity unpinned" by the reference
- * except for the zero-padded blur, which is pinned against the reference's own
- * convolutionSeparable_gold.cpp (oracle/_ref/libgold.so).
+ * TEST INFRASTRUCTURE ONLY (see ugsm_oracle.h).  The arithmetic of every stage is pinned
+ * against the reference's own MatchLib.cu run on the CPU (oracle/_ref/libmatchlib_cpu.so,
+ * oracle/ref_cpu/, tests/test_ref_pin_host.py) and the zero-padded blur also against its
+ * convolutionSeparable_gold.cpp (oracle/_ref/libgold.so); the host's orchestration
+ * (MatchGPULib.cpp, unbuildable) is restated here unpinned.
  *
  * Every function cites the reference file:line it restates (paths relative to
  * /root/reference/src/gpu_matcher/).  Written from the behaviour of that code, not

@@ -7,7 +7,11 @@ What pins what:
   * blur_gold.npz, blur_live_gold.npz  -- expected outputs come from the REFERENCE's own
     convolutionRowCPU / convolutionColumnCPU (oracle/_ref/libgold.so, compiled by
     oracle/Makefile from /root/reference/src/gpu_matcher/convolutionSeparable_gold.cpp where
-    it lies).  This is the only executable piece of the reference in this image.
+    it lies).
+  * ref_stages.npz  -- expected outputs come from the REFERENCE's own stage functions, MatchLib.cu
+    compiled for the CPU (oracle/_ref/libmatchlib_cpu.so through oracle/ref_cpu/), composed by
+    tests/ref_stages.py in the order of MatchGPULib.cpp: two iterations of a level at three sizes,
+    pyramid levels, seeds, smoothing passes.  Inputs: uint8 images and float seed fields.
   * every other file -- inputs from ug_stereomatcher_amd.synth, expected outputs from the
     CPU restatement (oracle/).  The reference has no tests or golden data for these
     ("parity unpinned"): the fixtures freeze the restatement so that an accidental change
@@ -22,6 +26,8 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import ref_stages as rs  # noqa: E402
 from oracle import oracle as orc  # noqa: E402
 from ug_stereomatcher_amd import synth  # noqa: E402
 
@@ -77,6 +83,19 @@ def blur_live_gold():
     np.savez_compressed(os.path.join(OUT, "blur_live_gold.npz"), **cases)
 
 
+def ref_stages():
+    """tests/golden/ref_stages.npz: the inputs of tests/ref_stages.py and what the reference's own stage code gives for them
+    (tests/test_ref_pin_host.py, tests/test_gpu_ref_pin.py).  Q and (dx', dy', kappa) for the smallest case only."""
+    ref = rs.load(orc)
+    if ref is None:
+        print("oracle/_ref/libmatchlib_cpu.so missing: keeping existing ref_stages.npz")
+        return
+    inp = rs.fixture_inputs()
+    out = rs.live_fixture_outputs(ref, inp, orc.threshold_schedule(rs.MI), orc.level_dims)
+    np.savez_compressed(os.path.join(OUT, "ref_stages.npz"), **inp, **out)
+    print("ref_stages:", len(inp), "inputs,", len(out), "outputs")
+
+
 def full(W, H, levels, seed):
     L, R, dx, dy = synth.make_pair(W, H, seed)
     out = orc.match_full(L, R, levels)
@@ -115,8 +134,10 @@ def fovea(W, H, levels, F, seed):
 
 
 if __name__ == "__main__":
+    orc.build()
     blur_gold()
     blur_live_gold()
+    ref_stages()
     full(64, 48, 5, synth.BASE_SEED + 100)
     full(160, 120, 8, synth.BASE_SEED + 101)
     stage(96, 72, synth.BASE_SEED + 102)

@@ -6,8 +6,9 @@ reading of the reference; the reference holds no fixtures, so a shared misreadin
 the algorithm again by a different route -- whole-array numpy operations in float32 with explicit float64 promotions,
 written from /root/reference/src/gpu_matcher/{MatchLib.cu, MatchGPULib.cpp} (line numbers cited per function) and
 SURVEY.md Appendix A, without looking at the C oracle's loops -- and tests/test_oracle_np.py checks the C oracle against
-it BIT FOR BIT on the committed fixtures.  Two restatements agreeing does not pin the reference's binary (nothing can,
-here), but a slip of the pen in either one now shows.
+it BIT FOR BIT on the committed fixtures.  Two restatements agreeing does not pin the reference; the stage arithmetic of both is
+pinned separately, to MatchLib.cu itself run on the CPU (tests/test_ref_pin_host.py), and the agreement covers the host-side
+orchestration that pin cannot reach.
 
 numpy never contracts a*b+c, every ufunc on float32 arrays rounds to float32, and float32 / float32 is the correctly
 rounded quotient: the same float contract as oracle/ (DESIGN.md section 3).
@@ -182,9 +183,11 @@ def smooth_pass(d):
     return np.stack(out)
 
 
-def iterate_level(L, R, d, i, is_top, m_from=1, m_to=None):
+def iterate_level(L, R, d, i, is_top, m_from=1, m_to=None, mi=None, S=None, want_dbg=False):
+    """Iterations m_from..m_to of level i; mi / S override the level's own iteration and pass counts.  With want_dbg also the five Q
+    planes and (dx', dy', kappa) of the last iteration."""
     g = gauss_taps()
-    mi, S = iterations(i), smooth_passes(i)
+    mi, S = (iterations(i) if mi is None else mi), (smooth_passes(i) if S is None else S)
     thr = thresholds(mi)
     _, H, W = L.shape
     xs = np.arange(W, dtype=F32) + F32(0.5)
@@ -217,10 +220,11 @@ def iterate_level(L, R, d, i, is_top, m_from=1, m_to=None):
         if not (is_top and m == 1):
             kap = clamp01((0.75 * cf.astype(F64) + 0.25 * kap.astype(F64)).astype(F32))  # TrueConfidence, old = texSrc
         nd = np.stack([(dx + ddx).astype(F32), (dy + ddy).astype(F32), kap])
+        dbg = (np.stack(Q), nd)
         for _ in range(S):
             nd = smooth_pass(nd)
         d = np.stack([blur(p, BOX, "clamp") for p in nd])
-    return d
+    return (d,) + dbg if want_dbg else d
 
 
 def seed(src, W2, H2):

@@ -1,6 +1,8 @@
 """The C oracle against the independent numpy restatement (tests/golden/restate_np.py), bit for bit, on the committed
-fixtures.  Neither is the reference (which cannot be built or run here and holds no fixtures): two restatements written by
-different routes agreeing is what stands in for a pin -- see the header of restate_np.py."""
+fixtures.  Neither is the reference.  The arithmetic of every stage of both IS held to the reference's own stage code, MatchLib.cu
+run on the CPU (oracle/ref_cpu/, tests/test_ref_pin_host.py, tests/golden/ref_stages.npz: DESIGN.md section 3); what the two
+restatements agreeing still stands in for is everything that pin does not reach -- the host's orchestration (the order of the
+calls, the level schedule, the pyramid and fovea drivers: MatchGPULib.cpp cannot be built) and whole matches on whole images."""
 import os
 import sys
 
