@@ -220,7 +220,8 @@ int ugsm_get_input_format(const ugsm_ctx *ctx, int *format);
  *   UGSM_LR_FULL      ugsm_match_full, ugsm_submit_full[_host|_batch|_batch_host] and the full-mode queue: the pair is matched a second time
  *                     with the images exchanged (ugsm_config.lr_check_threshold above); batches run pair by pair
  *   UGSM_LR_FOVEATED  ugsm_match_foveated, ugsm_match_foveated_full, ugsm_submit_foveated[_host], ugsm_submit_foveated_batch[_host] and,
- *                     through those, ugsm_enqueue_foveated[_host|_managed]
+ *                     through those, ugsm_enqueue_foveated[_host|_managed].  (The multi-window call takes its check per call, not from
+ *                     this setting: ugsm_submit_foveated_multi_checked.)
  * THE FOVEATED CHECK.  Let S be the stack of the call and B the stack of the same call with the two images exchanged -- the same offsets,
  * the same context: bit for bit what ugsm_submit_foveated(R, L, ..) returns.  The windows of L and R sit at the same coordinates, so level
  * k of S and level k of B live on one fovW x fovH grid, and each level k = 0 .. F-1 by itself is checked as ugsm_stage_lr_check checks a
@@ -327,14 +328,14 @@ int ugsm_submit_foveated_batch_host(ugsm_ctx *ctx, int slot, int n, const uint8_
  * whole-frame level.  With n == 1 the call IS ugsm_submit_foveated without pyramid stacks.
  * Status: null arrays or entries, n outside 1 .. UGSM_MAX_BATCH, fovea_levels < 2: UGSM_ERR_BAD_ARG; the size errors of ugsm_submit_foveated
  * as there; pairs outstanding in the queue: UGSM_ERR_STATE; UGSM_LR_FOVEATED set on the context: UGSM_ERR_STATE (the checked multi-window
- * call is not built).  All of these before anything is enqueued.
+ * call is an entry point of its own, ugsm_submit_foveated_multi_checked below).  All of these before anything is enqueued.
  * Memory: one pair's slot, plus level buffers that hold n fields of 3 fovW fovH floats -- more than a one-pair slot has once n > 2^(F-1); they
  * grow on demand (counted by ugsm_context_device_bytes), and a call whose buffers cannot grow answers UGSM_ERR_NOMEM.
  * After the call the slot holds no whole pyramids: ugsm_submit_fovea_fine on it answers UGSM_ERR_STATE, as after any one-shot foveated call.
  * Contexts with early_exit_threshold set, and kernel_path 1, still build the pyramids and run the coarse phase once; their n fine phases run
  * one after the other.  Same results.
- * NOT built: pyramid stacks from this call; a queue form (ugsm_enqueue_*); the page-locked _host kind; the LR check.  The merged cloud of
- * the n stacks is ugsm_point_cloud_fovea_multi (below, with the other clouds).
+ * NOT built: pyramid stacks from this call; a queue form (ugsm_enqueue_*); the page-locked _host kind.  The merged cloud of the n stacks is
+ * ugsm_point_cloud_fovea_multi (below, with the other clouds).
  * Asynchronous on `slot`. */
 int ugsm_submit_foveated_multi(ugsm_ctx *ctx, int slot, const uint8_t *d_rgbL, const uint8_t *d_rgbR, int W, int H, int stride,
                                int n, const int *off_x, const int *off_y, float *const *d_stack);
@@ -342,6 +343,27 @@ int ugsm_submit_foveated_multi(ugsm_ctx *ctx, int slot, const uint8_t *d_rgbL, c
 int ugsm_match_foveated_multi(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride,
                               int n, const int *off_x, const int *off_y, float *const *stackH, float *const *stackV,
                               float *const *stackC);
+/* The CHECKED multi-window call: both directions of the n windows in one lockstep call, the n stacks checked against their right-to-left twins.
+ * tau (> 0, in pixels of the level it is applied to) is an argument of the call: the call neither reads nor changes what ugsm_set_lr_check
+ * holds, and runs the same with UGSM_LR_FOVEATED set or not.
+ * The contract: stack k is, bit for bit, what ugsm_submit_foveated(ctx, slot, d_rgbL, d_rgbR, .., off_x[k], off_y[k], d_stack[k], NULL, NULL)
+ * writes on a context with ugsm_set_lr_check(ctx, tau, UGSM_LR_FOVEATED) -- stackH and stackV those of the unchecked call, stackC of level j
+ * zeroed where the rule of "THE FOVEATED CHECK" fails against the stack of the exchanged pair at the same offset; row block F-1 the same
+ * checked whole-frame level in every stack -- for any n in 1 .. UGSM_MAX_BATCH, any input format captured at the call, and offsets that clamp,
+ * repeat or overlap.  The pyramids are built once and the coarse phase runs once for the two directions; the right-to-left stacks never leave
+ * the library (the slot's LR buffer, counted by ugsm_context_device_bytes; the level buffers hold 2 n fovea fields and grow on demand).
+ * Counts: ugsm_last_lr_marked_levels(ctx, slot, k, per_level) answers for window k (pair >= n: UGSM_ERR_BAD_ARG); ugsm_last_lr_marked the
+ * levels of window n-1.  After a plain ugsm_submit_foveated_multi on the slot both answer as after any unchecked call.
+ * Status, all before anything is enqueued: !(tau > 0), NaN included: UGSM_ERR_BAD_ARG; contexts with early_exit_threshold > 0 or kernel_path 1:
+ * UGSM_ERR_BAD_ARG (ugsm_set_lr_check's rule: they have no batch dimension); every refusal of ugsm_submit_foveated_multi as it stands there but
+ * the one about UGSM_LR_FOVEATED; a buffer that cannot grow: UGSM_ERR_NOMEM, the context usable afterwards.
+ * NOT built: a queue form; the page-locked _host kind; pyramid stacks. */
+int ugsm_submit_foveated_multi_checked(ugsm_ctx *ctx, int slot, const uint8_t *d_rgbL, const uint8_t *d_rgbR, int W, int H, int stride,
+                                       int n, const int *off_x, const int *off_y, float *const *d_stack, float tau);
+/* Blocking, any host memory in, host stacks out, as ugsm_match_foveated_multi. */
+int ugsm_match_foveated_multi_checked(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride,
+                                      int n, const int *off_x, const int *off_y, float *const *stackH, float *const *stackV,
+                                      float *const *stackC, float tau);
 int ugsm_wait(ugsm_ctx *ctx, int slot);
 /* ugsm_wait on every slot, in order; every slot is waited for whatever the ones before it answered, the first failure is the one returned. */
 int ugsm_wait_all(ugsm_ctx *ctx);
@@ -644,8 +666,8 @@ int ugsm_point_cloud_fovea_all(ugsm_ctx *ctx, int slot, const float *d_stackx, c
  * and the call itself does not wait for the stream unless one of its buffers has to grow.
  * UGSM_ERR_BAD_ARG, before any device work: everything ugsm_point_cloud_fovea_all refuses, n outside 1 .. UGSM_MAX_BATCH, a null array or
  * entry, a misaligned d_entry_counts.  UGSM_ERR_STATE: pairs enqueued with ugsm_enqueue_* are outstanding.
- * NOT built: a queue or managed form of this call; the resized cloud of several stacks; the LR check of the multi-window call; the ros/
- * shim does not call it. */
+ * The stacks of ugsm_submit_foveated_multi_checked go in as any others: a compact cloud with min_conf > 0 leaves the marked pixels out.
+ * NOT built: a queue or managed form of this call; the resized cloud of several stacks; the ros/ shim does not call it. */
 long long ugsm_fovea_multi_cloud_points(int W, int H, int levels, int fovea_levels, int n, const int *off_x, const int *off_y,
                                         int sampling, long long *per_entry);
 int ugsm_point_cloud_fovea_multi(ugsm_ctx *ctx, int slot, int n, const float *const *d_stack, int W, int H,

@@ -133,8 +133,9 @@ public:
     // Several windows of one pair (not in the reference; include/ugsm.h, "several fovea windows on ONE pair"): matchStack for the n offsets
     // (1 <= n <= UGSM_MAX_BATCH) in one call -- pyramids and the coarse levels once, the windows' fine levels in lockstep.  out[k]: the
     // disparity[level][3][fovH*fovW] matchStack returns for (off_x[k], off_y[k]), malloc'd the same way.  False on failure (nothing allocated).
+    // tau > 0: the checked call (ugsm_match_foveated_multi_checked) -- stack k is matchStack's at offset k under setLRCheck(tau, 2).
     template <class ImgPtr>
-    bool matchStackMulti(ImgPtr L, ImgPtr R, int n, const int *off_x, const int *off_y, float ****out)
+    bool matchStackMulti(ImgPtr L, ImgPtr R, int n, const int *off_x, const int *off_y, float ****out, float tau = 0.0f)
     {
         const int W = L->image.cols, H = L->image.rows, F = foveatelevel;
         if (!out || n < 1 || n > UGSM_MAX_BATCH || R->image.cols != W || R->image.rows != H) return false;
@@ -143,7 +144,8 @@ public:
         float *sh = (float *)std::malloc((size_t)n * 3 * sn * sizeof(float));
         float *ph[UGSM_MAX_BATCH], *pv[UGSM_MAX_BATCH], *pc[UGSM_MAX_BATCH];
         for (int k = 0; k < n; k++) { ph[k] = sh + (size_t)k * 3 * sn; pv[k] = ph[k] + sn; pc[k] = pv[k] + sn; }
-        const int st = ugsm_match_foveated_multi(ctx_, L->image.data, R->image.data, W, H, (int)L->image.step, n, off_x, off_y, ph, pv, pc);
+        const int st = tau > 0.0f ? ugsm_match_foveated_multi_checked(ctx_, L->image.data, R->image.data, W, H, (int)L->image.step, n, off_x, off_y, ph, pv, pc, tau)
+                                  : ugsm_match_foveated_multi(ctx_, L->image.data, R->image.data, W, H, (int)L->image.step, n, off_x, off_y, ph, pv, pc);
         if (st != UGSM_OK) { report(st); std::free(sh); return false; }
         for (int k = 0; k < n; k++) {
             out[k] = (float ***)std::malloc(F * sizeof(float **));

@@ -86,6 +86,30 @@ int main(int argc, char **argv)
             }
             if (bad) return 10;
         }
+        // matchStackMulti with a tau: the centred window is matchStack's under setLRCheck(tau, 2), and the context's setting stays off
+        {
+            const int ox[3] = {40, 0, -5000}, oy[3] = {-25, 0, 5000};
+            float ***multi[3];
+            if (!m.matchStackMulti(L, R, 3, ox, oy, multi, 1.0f)) return 11;
+            if (m.setLRCheck(1.0f, 2) != UGSM_OK) return 12;
+            float ***chk = m.matchStack(L, R);
+            if (m.setLRCheck(0.0f, 0) != UGSM_OK || !chk) return 13;
+            const int F = m.getFoveateLevel();
+            const size_t fb = sizeof(float) * m.getFoveaWidth() * m.getFoveaHeight();
+            size_t bad = 0, zeroed = 0;
+            for (int k = 0; k < F; k++) {
+                for (int c = 0; c < 3; c++) bad += std::memcmp(multi[1][k][c], chk[k][c], fb) != 0;
+                zeroed += std::memcmp(chk[k][2], st[k][2], fb) != 0;
+            }
+            std::printf("matchStackMulti (3 windows, tau 1) vs checked matchStack: %s; levels the check changed: %zu\n", bad ? "DIFFER" : "identical", zeroed);
+            for (int w = 0; w < 3; w++) {
+                for (int k = 0; k < F; k++) { for (int i = 0; i < 3; i++) free(multi[w][k][i]); free(multi[w][k]); }
+                free(multi[w]);
+            }
+            for (int k = 0; k < F; k++) { for (int i = 0; i < 3; i++) free(chk[k][i]); free(chk[k]); }
+            free(chk);
+            if (bad) return 14;
+        }
         for (int k = 0; k < m.getFoveateLevel(); k++) { for (int i = 0; i < 3; i++) free(st[k][i]); free(st[k]); }
         free(st);
     } catch (const std::exception &e) {

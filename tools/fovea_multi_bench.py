@@ -18,6 +18,17 @@ over the children of one configuration: what two runs of the same code differ by
 Also timed at 16 MP: ugsm_reconstruct_full_multi for n = 1 against ugsm_reconstruct_full, and for n = 8.
 Reported beside the numbers: (d) at n = 1 against one ugsm_submit_foveated on the parent (within the spread?), and (d) against the best of
 (a), (b), (c) for every n >= 2 (faster by more than the spread?).
+
+    python tools/fovea_multi_bench.py --checked [--parent-tree DIR] [--out profiles/fovea_multi_checked_bench.json]
+
+The same protocol for the CHECKED multi-window call (ugsm_submit_foveated_multi_checked, tau = 1):
+  (a)  n sequential checked ugsm_submit_foveated calls (ugsm_set_lr_check(1, UGSM_LR_FOVEATED));     on the parent
+  (b)  a checked ugsm_submit_foveated_batch with the pair given n times;                             on the parent
+  (c)  the plain ugsm_submit_foveated_multi;                                                         on the parent
+  (d)  ugsm_submit_foveated_multi_checked;                                                           on this build
+  (c') the plain ugsm_submit_foveated_multi.                                                         on this build
+Reported: whether (d) takes no longer than the better of (a) and (b) beyond the spread (the larger range between the children of (d) and of
+that candidate), whether (c') equals (c) within the spread of the two, the ratio (d) / (c'), and the memory of (d) against (b).
 """
 import argparse
 import json
@@ -42,11 +53,15 @@ ap.add_argument("--reps", type=int, default=20)
 ap.add_argument("--warmup", type=int, default=4)
 ap.add_argument("--sizes", nargs="*", default=list(SIZES))
 ap.add_argument("--child-timeout", type=int, default=240, help="seconds a child may take (timeout -k 10)")
-ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "fovea_multi_bench.json"))
+ap.add_argument("--checked", action="store_true", help="measure the checked multi-window call (tau = 1) against its alternatives")
+ap.add_argument("--out", default=None, help="default: profiles/fovea_multi_bench.json, with --checked profiles/fovea_multi_checked_bench.json")
 ap.add_argument("--child", choices=["old", "new"], help="(internal) measure in this process, print one JSON line")
 ap.add_argument("--tree", default=ROOT, help="(internal) the tree whose package the child loads")
 ap.add_argument("--size", default="16mp", help="(internal)")
 args = ap.parse_args()
+if args.out is None:
+    args.out = os.path.join(ROOT, "profiles", "fovea_multi_checked_bench.json" if args.checked else "fovea_multi_bench.json")
+TAU = 1.0
 
 
 def offsets(W, H, n):
@@ -62,7 +77,66 @@ def timed(fn):
     return statistics.median(ts[args.warmup:])
 
 
+def child_checked():
+    """The --checked child: (a), (b), (c) on the tree of `old`; (d), (c') on the tree of `new`."""
+    sys.path.insert(0, args.tree)
+    from ug_stereomatcher_amd import _lib, synth
+    assert os.path.dirname(os.path.abspath(_lib.__file__)) == os.path.join(os.path.abspath(args.tree), "ug_stereomatcher_amd")
+    W, H = SIZES[args.size]
+    fw, fh = _lib.fovea_dims(W, H, LEVELS, F)
+    L, R = synth.make_pair(W, H, synth.BASE_SEED + 2)[:2]
+    nbytes = 3 * F * fh * fw * 4
+    out = {}
+    with _lib.Context(levels=LEVELS, fovea_levels=F, slots=1) as c:
+        dL, dR = c.to_device(L), c.to_device(R)
+        dS = [c.alloc(nbytes) for _ in range(max(NS))]
+        wait = lambda: c.check(c.lib.ugsm_wait(c.handle, 0))
+        for n in NS:
+            offs = offsets(W, H, n)
+
+            def plain():
+                c.submit_foveated_multi(0, dL, dR, W, H, 3 * W, offs, dS[:n])
+                wait()
+            if args.child == "old":
+                def a():
+                    for k, (ox, oy) in enumerate(offs):
+                        c.check(c.lib.ugsm_submit_foveated(c.handle, 0, dL, dR, W, H, 3 * W, ox, oy, dS[k], None, None))
+                        wait()
+                out[f"c_{n}"] = timed(plain)
+                c.set_lr_check(TAU, _lib.UGSM_LR_FOVEATED)
+                out[f"a_{n}"] = timed(a)
+                c.set_lr_check(0.0, 0)
+            else:
+                def d():
+                    c.submit_foveated_multi_checked(0, dL, dR, W, H, 3 * W, offs, dS[:n], TAU)
+                    wait()
+                out[f"cp_{n}"] = timed(plain)
+                out[f"d_{n}"] = timed(d)
+                out[f"device_bytes_d_{n}"] = c.device_bytes()
+    if args.child == "old":     # (b): a context created for n pairs holds n slots' worth of memory
+        for n in NS:
+            try:
+                with _lib.Context(levels=LEVELS, fovea_levels=F, slots=1, batch=n) as c:
+                    c.set_lr_check(TAU, _lib.UGSM_LR_FOVEATED)
+                    dL, dR = c.to_device(L), c.to_device(R)
+                    dS = [c.alloc(nbytes) for _ in range(n)]
+                    offs = offsets(W, H, n)
+
+                    def b():
+                        c.submit_foveated_batch(0, [dL] * n, [dR] * n, W, H, 3 * W, offs, dS)
+                        c.check(c.lib.ugsm_wait(c.handle, 0))
+                    out[f"b_{n}"] = timed(b)
+                    out[f"device_bytes_b_{n}"] = c.device_bytes()
+            except _lib.UgsmError as e:
+                if e.status != _lib.UGSM_ERR_NOMEM:
+                    raise
+                out[f"b_{n}"] = None
+    print("MULTIBENCH " + json.dumps(out), flush=True)
+
+
 def child():
+    if args.checked:
+        return child_checked()
     sys.path.insert(0, args.tree)
     from ug_stereomatcher_amd import _lib, synth
     assert os.path.dirname(os.path.abspath(_lib.__file__)) == os.path.join(os.path.abspath(args.tree), "ug_stereomatcher_amd")
@@ -137,7 +211,7 @@ def child():
 
 def measure(kind, size, tree):
     cmd = ["timeout", "-k", "10", str(args.child_timeout), sys.executable, os.path.abspath(__file__), "--child", kind, "--size", size, "--tree", tree,
-           "--reps", str(args.reps), "--warmup", str(args.warmup)]
+           "--reps", str(args.reps), "--warmup", str(args.warmup)] + (["--checked"] if args.checked else [])
     r = subprocess.run(cmd, capture_output=True, text=True)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("MULTIBENCH ")]
     if r.returncode != 0 or not lines:     # (a child that failed, faulted or ran into its limit: nothing more is started)
@@ -149,8 +223,10 @@ def main():
     parent = os.path.abspath(args.parent_tree) if args.parent_tree else None
     if parent and not os.path.exists(os.path.join(parent, "ug_stereomatcher_amd", "libugsm.so")):
         raise SystemExit(f"{parent}: no built ug_stereomatcher_amd/libugsm.so")
-    result = dict(tool="tools/fovea_multi_bench.py", levels=LEVELS, fovea_levels=F, rounds=args.rounds, reps=args.reps, warmup=args.warmup,
-                  parent_measured=bool(parent), windows=NS, sizes={})
+    result = dict(tool="tools/fovea_multi_bench.py" + (" --checked" if args.checked else ""), levels=LEVELS, fovea_levels=F, rounds=args.rounds,
+                  reps=args.reps, warmup=args.warmup, parent_measured=bool(parent), windows=NS, sizes={})
+    if args.checked:
+        result["tau"] = TAU
     for size in args.sizes:
         W, H = SIZES[size]
         turns = [("old", parent or ROOT), ("new", ROOT)]
@@ -164,6 +240,24 @@ def main():
             vals = [v[key] for v in kept[kind] if v.get(key) is not None]
             return (statistics.median(vals), max(vals) - min(vals)) if vals else (None, None)
         row = dict(W=W, H=H, offsets=offsets(W, H, max(NS)), children=kept, n={})
+        if args.checked:
+            for n in NS:
+                cell = {}
+                for kind, cand in (("old", "a"), ("old", "b"), ("old", "c"), ("new", "d"), ("new", "cp")):
+                    cell[f"{cand}_ms"], cell[f"{cand}_spread_ms"] = stat(kind, f"{cand}_{n}")
+                others = {k: cell[f"{k}_ms"] for k in "ab" if cell[f"{k}_ms"] is not None}
+                best = min(others, key=others.get)
+                spread = max(cell["d_spread_ms"], cell[f"{best}_spread_ms"])
+                cell.update(best_other=best, best_other_ms=others[best], d_over_best=cell["d_ms"] / others[best], spread_ms=spread,
+                            d_over_cp=cell["d_ms"] / cell["cp_ms"],
+                            d_no_slower_than_best_beyond_spread=bool(cell["d_ms"] - others[best] <= spread),
+                            d_faster_than_best_by_more_than_spread=bool(others[best] - cell["d_ms"] > spread),
+                            cp_equals_c_within_spread=bool(abs(cell["cp_ms"] - cell["c_ms"]) <= max(cell["cp_spread_ms"], cell["c_spread_ms"])),
+                            device_bytes_d=stat("new", f"device_bytes_d_{n}")[0], device_bytes_b=stat("old", f"device_bytes_b_{n}")[0])
+                row["n"][str(n)] = cell
+            result["sizes"][size] = row
+            print(json.dumps({k: v for k, v in row.items() if k != "children"}), flush=True)
+            continue
         single, single_spread = stat("old", "a_1")
         for n in NS:
             cell = {}

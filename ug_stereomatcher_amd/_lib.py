@@ -65,6 +65,8 @@ EXPORTS = [
     "ugsm_set_lr_check", "ugsm_get_lr_check", "ugsm_last_lr_marked_levels",
     # the cloud from the queue
     "ugsm_enqueue_full_cloud", "ugsm_enqueue_foveated_cloud", "ugsm_enqueue_full_cloud_managed", "ugsm_enqueue_foveated_cloud_managed", "ugsm_done_cloud",
+    # the checked multi-window call
+    "ugsm_submit_foveated_multi_checked", "ugsm_match_foveated_multi_checked",
 ]
 # ... and what include/ugsm_dev.h adds (libugsm_dev.so only)
 DEV_EXPORTS = ["ugsm_stage_poly_probe", "ugsm_stage_div3_probe", "ugsm_stage_div_probe", "ugsm_stage_range_words", "ugsm_stage_iterate_rgb8", "ugsm_stage_level0_direct"]
@@ -274,6 +276,8 @@ def load(dev: bool = False):
     lib.ugsm_submit_foveated_multi.argtypes = [vp, i, vp, vp, i, i, i, i, ip, ip, pp]
     lib.ugsm_match_foveated_multi.argtypes = [vp, vp, vp, i, i, i, i, ip, ip, pp, pp, pp]
     lib.ugsm_reconstruct_full_multi.argtypes = [vp, i, i, pp, i, i, ip, ip, vp]
+    lib.ugsm_submit_foveated_multi_checked.argtypes = [vp, i, vp, vp, i, i, i, i, ip, ip, pp, C.c_float]
+    lib.ugsm_match_foveated_multi_checked.argtypes = [vp, vp, vp, i, i, i, i, ip, ip, pp, pp, pp, C.c_float]
     lib.ugsm_wait.argtypes = [vp, i]
     lib.ugsm_wait_all.argtypes = [vp]
     lib.ugsm_submit_pyramids.argtypes = [vp, i, vp, vp, i, i, i]
@@ -771,8 +775,16 @@ class Context:
         ox, oy = self._offsets(offsets, n)
         self.check(self.lib.ugsm_submit_foveated_multi(self._h, slot, d_rgbL, d_rgbR, W, H, stride, n, ox, oy, self._ptrs(d_stack)))
 
-    def match_foveated_multi(self, L: np.ndarray, R: np.ndarray, offsets):
-        """Blocking, from any host memory: the (3, F, fovH, fovW) stacks of the windows at `offsets`, one array per window."""
+    def submit_foveated_multi_checked(self, slot: int, d_rgbL: int, d_rgbR: int, W: int, H: int, stride: int, offsets, d_stack, tau: float):
+        """submit_foveated_multi with the foveated LR check at threshold tau (> 0; the call's own, not the context's setting): both directions
+        in lockstep, stackC zeroed where the match does not point back.  last_lr_marked_levels(slot, k) answers for window k."""
+        n = len(d_stack)
+        ox, oy = self._offsets(offsets, n)
+        self.check(self.lib.ugsm_submit_foveated_multi_checked(self._h, slot, d_rgbL, d_rgbR, W, H, stride, n, ox, oy, self._ptrs(d_stack), tau))
+
+    def match_foveated_multi(self, L: np.ndarray, R: np.ndarray, offsets, tau=None):
+        """Blocking, from any host memory: the (3, F, fovH, fovW) stacks of the windows at `offsets`, one array per window.  tau (> 0): the
+        checked call (ugsm_match_foveated_multi_checked)."""
         W, H, stride = self.check_image(L)
         if self.check_image(R) != (W, H, stride):
             raise UgsmError(UGSM_ERR_SIZE_MISMATCH, "the two images differ in size or stride")
@@ -782,10 +794,15 @@ class Context:
         fw, fh = fovea_dims(W, H, self.cfg.levels, self.cfg.fovea_levels)
         stacks = [np.empty((3, self.cfg.fovea_levels, fh, fw), np.float32) for _ in range(n)]
         ox, oy = self._offsets(offsets, n)
-        self.check(self.lib.ugsm_match_foveated_multi(self._h, L.ctypes.data, R.ctypes.data, W, H, stride, n, ox, oy,
-                                                      self._ptrs([t[0].ctypes.data for t in stacks]), self._ptrs([t[1].ctypes.data for t in stacks]),
-                                                      self._ptrs([t[2].ctypes.data for t in stacks])))
+        planes = [self._ptrs([t[c].ctypes.data for t in stacks]) for c in range(3)]
+        if tau is None:
+            self.check(self.lib.ugsm_match_foveated_multi(self._h, L.ctypes.data, R.ctypes.data, W, H, stride, n, ox, oy, *planes))
+        else:
+            self.check(self.lib.ugsm_match_foveated_multi_checked(self._h, L.ctypes.data, R.ctypes.data, W, H, stride, n, ox, oy, *planes, tau))
         return stacks
+
+    def match_foveated_multi_checked(self, L: np.ndarray, R: np.ndarray, offsets, tau: float):
+        return self.match_foveated_multi(L, R, offsets, tau)
 
     def reconstruct_full_multi(self, d_stack, W: int, H: int, d_out3: int, offsets=None, slot: int = 0):
         """Row f-3 over the stacks of several windows of one pair: where windows overlap the highest index wins.  Waits."""

@@ -846,11 +846,12 @@ void full_views(const Slot &s, const float *pyr, int lev, Img3 *out)
 
 // The pyramid that pair v of the call matches as its left (side 0) or right (side 1) image.  The virtual pairs nreal .. 2 nreal - 1 of a
 // checked foveated call are the pairs 0 .. nreal - 1 with the two exchanged: the right-to-left match reads the same two pyramids.  The
-// virtual pairs of a multi-window call (Slot::one_pair) are windows of pair 0: every one reads its pyramids as they are.
+// virtual pairs of a multi-window call (Slot::one_pair) are windows of pair 0: every one reads its pyramids as they are -- and, in the checked
+// multi-window call, the virtual pairs nreal .. 2 nreal - 1 read them with the two exchanged.
 const float *pair_pyr(const Slot &s, int side, int v)
 {
-    if (s.one_pair) return side == 0 ? s.pyrL : s.pyrR;  // (n windows of one pair: ugsm_submit_foveated_multi)
     const bool back = v >= s.nreal;
+    if (s.one_pair) return (side == 0) != back ? s.pyrL : s.pyrR;  // (n windows of one pair: ugsm_submit_foveated_multi[_checked])
     return ((side == 0) != back ? s.pyrL : s.pyrR) + (size_t)(back ? v - s.nreal : v) * s.pyr_stride;
 }
 void side_views(const Slot &s, int side, int lev, Img3 *out)
@@ -1302,26 +1303,9 @@ int ugsm::enqueue_match_full(ugsm_ctx *ctx, Slot &s, int si, int n, const uint8_
 }
 namespace {
 
-// n fovea windows on ONE pair (ugsm_submit_foveated_multi): what does not depend on the window runs once, the rest in lockstep.
-//   - the pyramids of one pair, as a lone foveated call builds them (side stream and A planes of levels F-1 .. top included), but with no
-//     level 0 (FoveaWin::later); one launch then writes level 0 of both images inside the n windows (k_rgb_planes' window form).  Pyramids
-//     that k_pyr_base does not build (fewer than three levels, kernel_path 1) hold level 0 whole and skip that launch;
-//   - the coarse phase once, its field into `state`;
-//   - the fine phase with s.nb = n virtual pairs that all read pair 0's pyramids (Slot::one_pair, pair_pyr), start from the one state and
-//     run under pair 0's range word; their fields lie in the level buffers at a stride of one fovea field, as a checked call's do.  The
-//     caller has made the buffers hold n such fields (n x 3 fovW fovH floats exceed one pair's 3 W H as soon as n > 2^(F-1));
-//   - contexts that run pair by pair (early exit, kernel_path 1) and n == 1: the fine phase window after window, nb = 1.
-// Afterwards the slot holds no whole pyramids (have_pyr, have_coarse false) and its nb, nreal and lvl_stride are one pair's again.
-int enqueue_foveated_multi(ugsm_ctx *ctx, Slot &s, int si, const uint8_t *d_rgbL, const uint8_t *d_rgbR, int W, int H, int stride, int n,
-                           const int *off_x, const int *off_y, float *state, float *const *d_stack)
+// Level 0 of both images inside the n windows of a multi-window call (k_pyr_base stored none: FoveaWin::later), one launch.
+int enqueue_level0_windows(ugsm_ctx *ctx, Slot &s, int si, const uint8_t *d_rgbL, const uint8_t *d_rgbR, int stride, int n, const FoveaWin &win)
 {
-    const int F = ctx->cfg.fovea_levels;
-    s.lr_ran = false;
-    s.lr_fov_pairs = 0;
-    FoveaWin win;
-    UCHK(fovea_windows(ctx, W, H, n, off_x, off_y, win));
-    win.later = true;
-    UCHK(enqueue_pyramids(ctx, s, si, d_rgbL, d_rgbR, W, H, stride, F - 1, &win));
     if (ctx->cfg.kernel_path != 1 && s.levels >= 3) {  // (k_pyr_base built them: as `base` in build_pyramids)
         Level0Windows lw{};
         lw.n = n;
@@ -1344,6 +1328,30 @@ int enqueue_foveated_multi(ugsm_ctx *ctx, Slot &s, int si, const uint8_t *d_rgbL
         }
         HIPCHK(ctx, hipGetLastError());
     }
+    return UGSM_OK;
+}
+
+// n fovea windows on ONE pair (ugsm_submit_foveated_multi): what does not depend on the window runs once, the rest in lockstep.
+//   - the pyramids of one pair, as a lone foveated call builds them (side stream and A planes of levels F-1 .. top included), but with no
+//     level 0 (FoveaWin::later); one launch then writes level 0 of both images inside the n windows (k_rgb_planes' window form).  Pyramids
+//     that k_pyr_base does not build (fewer than three levels, kernel_path 1) hold level 0 whole and skip that launch;
+//   - the coarse phase once, its field into `state`;
+//   - the fine phase with s.nb = n virtual pairs that all read pair 0's pyramids (Slot::one_pair, pair_pyr), start from the one state and
+//     run under pair 0's range word; their fields lie in the level buffers at a stride of one fovea field, as a checked call's do.  The
+//     caller has made the buffers hold n such fields (n x 3 fovW fovH floats exceed one pair's 3 W H as soon as n > 2^(F-1));
+//   - contexts that run pair by pair (early exit, kernel_path 1) and n == 1: the fine phase window after window, nb = 1.
+// Afterwards the slot holds no whole pyramids (have_pyr, have_coarse false) and its nb, nreal and lvl_stride are one pair's again.
+int enqueue_foveated_multi(ugsm_ctx *ctx, Slot &s, int si, const uint8_t *d_rgbL, const uint8_t *d_rgbR, int W, int H, int stride, int n,
+                           const int *off_x, const int *off_y, float *state, float *const *d_stack)
+{
+    const int F = ctx->cfg.fovea_levels;
+    s.lr_ran = false;
+    s.lr_fov_pairs = 0;
+    FoveaWin win;
+    UCHK(fovea_windows(ctx, W, H, n, off_x, off_y, win));
+    win.later = true;
+    UCHK(enqueue_pyramids(ctx, s, si, d_rgbL, d_rgbR, W, H, stride, F - 1, &win));
+    UCHK(enqueue_level0_windows(ctx, s, si, d_rgbL, d_rgbR, stride, n, win));
     int st = enqueue_fovea_coarse(ctx, s, si, state);
     if (st == UGSM_OK) {
         if (n == 1 || ctx->cfg.kernel_path == 1 || ctx->cfg.early_exit_threshold > 0.0f) {
@@ -1372,6 +1380,104 @@ int enqueue_foveated_multi(ugsm_ctx *ctx, Slot &s, int si, const uint8_t *d_rgbL
     s.have_pyr = false;
     s.have_coarse = false;
     return st;
+}
+
+// The room the checked multi-window call takes in the slot's LR buffer, in floats: n right-to-left stacks, the right-to-left level-F-1 state,
+// then one 8-byte count word per (window, level).
+struct MultiLrRoom {
+    size_t per, state, cnt, total;
+};
+MultiLrRoom multi_lr_room(int n, int F, int fw, int fh)
+{
+    const size_t fn = (size_t)fw * fh;
+    MultiLrRoom r;
+    r.per = (3 * (size_t)F * fn + 63) & ~(size_t)63;
+    r.state = (size_t)n * r.per;
+    r.cnt = r.state + ((3 * fn + 63) & ~(size_t)63);  // (a multiple of 64 floats: 8-byte aligned)
+    r.total = r.cnt + 2 * (size_t)n * F;
+    return r;
+}
+
+// ugsm_submit_foveated_multi_checked: n windows of one pair, both directions in lockstep, the n stacks checked against their right-to-left twins.
+// enqueue_foveated_multi and the checked enqueue_match_foveated composed:
+//   - one pair's pyramids with no level 0 and the one k_level0_windows launch, as the plain multi call (no A planes from the side stream: the
+//     coarse phase runs on two virtual pairs and computes A in line, as every batch does).  The right-to-left direction reads the same two
+//     pyramids, so nothing more is stored;
+//   - pair 0's range word into the entries 1 .. 2 n - 1;
+//   - the coarse phase once for the two directions: nb = 2, nreal = 1 (virtual pair 1 = pair 0 exchanged, pair_pyr), level F-1's two fields into
+//     `state` and into the LR buffer;
+//   - the fine phase with nb = 2 n, nreal = n, Slot::one_pair: entry k is window k left-to-right from the first state, entry n + k window k
+//     right-to-left from the second, its stack in the LR buffer.  K-cost runs one launch per direction and level (cost_groups); more than
+//     kMaxBatch entries go through launches of equal size (group_pairs);
+//   - one launch of k_lr_check's stack form over the n (window, level) entries with the call's own tau, the counts back with one copy.
+// The caller has made the level buffers hold 2 n fovea fields and the LR buffer multi_lr_room(..).total floats.
+int enqueue_foveated_multi_checked(ugsm_ctx *ctx, Slot &s, int si, const uint8_t *d_rgbL, const uint8_t *d_rgbR, int W, int H, int stride, int n,
+                                   const int *off_x, const int *off_y, float *state, float *const *d_stack, float tau)
+{
+    const int F = ctx->cfg.fovea_levels;
+    s.lr_ran = false;
+    s.lr_fov_pairs = 0;
+    FoveaWin win;
+    UCHK(fovea_windows(ctx, W, H, n, off_x, off_y, win));
+    win.later = true;
+    UCHK(enqueue_pyramids(ctx, s, si, d_rgbL, d_rgbR, W, H, stride, -1, &win));
+    UCHK(enqueue_level0_windows(ctx, s, si, d_rgbL, d_rgbR, stride, n, win));
+    const int fw = win.w, fh = win.h;
+    const size_t fn = (size_t)fw * fh;
+    const size_t field = (3 * fn + 63) & ~(size_t)63;
+    const MultiLrRoom room = multi_lr_room(n, F, fw, fh);
+    if (2 * (size_t)n * field > s.lvl_cap || room.total > s.lr_cap || !s.lr_host) {
+        ctx->err = "the slot's buffers do not hold the checked windows' fields";
+        return UGSM_ERR_STATE;
+    }
+    unsigned long long *const cnt = reinterpret_cast<unsigned long long *>(s.lr + room.cnt);
+    for (int c = 1; s.range_known && c < 2 * n; c *= 2)
+        HIPCHK(ctx, hipMemcpyAsync(s.range_bad + c, s.range_bad, sizeof(unsigned) * std::min(c, 2 * n - c), hipMemcpyDeviceToDevice, s.st));
+    int vox[2 * kMaxBatch], voy[2 * kMaxBatch];
+    float *vstate[2 * kMaxBatch], *vstack[2 * kMaxBatch];
+    for (int k = 0; k < n; k++) {
+        vox[k] = vox[n + k] = off_x[k];
+        voy[k] = voy[n + k] = off_y[k];
+        vstate[k] = state;
+        vstate[n + k] = s.lr + room.state;
+        vstack[k] = d_stack[k];
+        vstack[n + k] = s.lr + (size_t)k * room.per;
+    }
+    float *const cstate[2] = {state, s.lr + room.state};
+    const size_t real_stride = s.lvl_stride;
+    s.lvl_stride = field;
+    s.nb = 2;
+    s.nreal = 1;
+    int st = enqueue_fovea_coarse(ctx, s, si, cstate);
+    if (st == UGSM_OK) {
+        s.nb = 2 * n;
+        s.nreal = n;
+        s.one_pair = true;
+        st = enqueue_fovea_fine(ctx, s, si, vstate, vox, voy, vstack, nullptr, nullptr);
+    }
+    s.nb = s.nreal = 1;
+    s.lvl_stride = real_stride;
+    s.one_pair = false;
+    s.have_pyr = false;
+    s.have_coarse = false;
+    UCHK(st);
+    HIPCHK(ctx, hipMemsetAsync(cnt, 0, sizeof *cnt * n * F, s.st));
+    LrStack ls{};
+    ls.n = n;
+    ls.F = F;
+    for (int k = 0; k < n; k++) {
+        ls.fwd[k] = byte_diff(d_stack[k], d_stack[0]);
+        ls.back[k] = (long long)((size_t)k * room.per * sizeof(float));
+    }
+    {
+        Timer t(ctx, &s, si, KC_MISC, (double)fn * F * n);
+        launch_lr_check(s.st, d_stack[0], s.lr, fw, fh, tau, cnt, ls);
+    }
+    HIPCHK(ctx, hipMemcpyAsync(s.lr_host + 1, cnt, sizeof *cnt * n * F, hipMemcpyDeviceToHost, s.st));
+    HIPCHK(ctx, hipGetLastError());
+    s.lr_fov_pairs = n;
+    s.lr_fov_F = F;
+    return UGSM_OK;
 }
 
 // Has everything enqueued on the slot finished?  (Never blocks; a slot found idle stops counting as busy.)
@@ -1994,13 +2100,20 @@ int ugsm_submit_foveated_batch(ugsm_ctx *ctx, int slot, int n, const uint8_t *co
 
 // ---- n windows on one pair ----------------------------------------------------------------------------------------------------
 // What ugsm_submit_foveated_multi and ugsm_match_foveated_multi refuse before anything is enqueued; the windows' field size on success.
-static int multi_check(ugsm_ctx *ctx, int n, int W, int H, int stride, const int *&off_x, const int *&off_y, const int *zeros, int *fw, int *fh)
+// tau: null = the plain call; else the checked call's threshold (ugsm_submit_foveated_multi_checked), which has refusals of its own and does
+// not look at the context's setting.
+static int multi_check(ugsm_ctx *ctx, int n, int W, int H, int stride, const int *&off_x, const int *&off_y, const int *zeros, int *fw, int *fh,
+                       const float *tau = nullptr)
 {
     const int F = ctx->cfg.fovea_levels;
     if (n < 1 || n > UGSM_MAX_BATCH || F < 2) return UGSM_ERR_BAD_ARG;
     if (!off_x) off_x = zeros;
     if (!off_y) off_y = zeros;
-    if (lr_fovea_on(ctx)) return ctx_fail(ctx, UGSM_ERR_STATE, "the foveated LR check is on: the checked multi-window call is not built (ugsm_set_lr_check)");
+    if (tau && !(*tau > 0.0f)) return ctx_fail(ctx, UGSM_ERR_BAD_ARG, "the checked multi-window call needs tau > 0");
+    // (ugsm_set_lr_check's rule: these contexts run every level pair by pair and have no batch dimension to carry the second direction in)
+    if (tau && (ctx->cfg.early_exit_threshold > 0.0f || ctx->cfg.kernel_path == 1))
+        return ctx_fail(ctx, UGSM_ERR_BAD_ARG, "the checked multi-window call: not with early_exit_threshold > 0 or kernel_path 1");
+    if (!tau && lr_fovea_on(ctx)) return ctx_fail(ctx, UGSM_ERR_STATE, "the foveated LR check is on: the checked multi-window call is ugsm_submit_foveated_multi_checked (ugsm_set_lr_check)");
     UCHK(ugsm_fovea_dims(W, H, ctx->cfg.levels, F, fw, fh));
     if (stride < input_row_bytes(ctx, W)) return UGSM_ERR_SIZE_MISMATCH;
     return UGSM_OK;
@@ -2011,6 +2124,34 @@ static int multi_level_bufs(ugsm_ctx *ctx, Slot &s, int n, int W, int H, int fw,
     if (n == 1 || ctx->cfg.kernel_path == 1 || ctx->cfg.early_exit_threshold > 0.0f) return UGSM_OK;
     const size_t field = (3 * (size_t)fw * fh + 63) & ~(size_t)63;
     return ensure_level_bufs(ctx, s, std::max((size_t)n * field, 3 * (size_t)W * H));
+}
+
+// ... and of the checked call: 2 n fields in the level buffers, the right-to-left stacks, state and count words in the LR buffer
+static int multi_checked_bufs(ugsm_ctx *ctx, Slot &s, int n, int W, int H, int fw, int fh)
+{
+    const size_t field = (3 * (size_t)fw * fh + 63) & ~(size_t)63;
+    UCHK(ensure_level_bufs(ctx, s, std::max(2 * (size_t)n * field, 3 * (size_t)W * H)));
+    UCHK(grow(ctx, s.lr, s.lr_cap, multi_lr_room(n, ctx->cfg.fovea_levels, fw, fh).total));
+    return lr_host_ready(ctx, s);
+}
+
+int ugsm_submit_foveated_multi_checked(ugsm_ctx *ctx, int slot, const uint8_t *d_rgbL, const uint8_t *d_rgbR, int W, int H, int stride, int n,
+                                       const int *off_x, const int *off_y, float *const *d_stack, float tau)
+{
+    Slot *s;
+    UCHK(get_slot(ctx, slot, &s));
+    if (!d_rgbL || !d_rgbR || !d_stack) return UGSM_ERR_BAD_ARG;
+    for (int k = 0; k < n && k < UGSM_MAX_BATCH; k++)
+        if (!d_stack[k]) return UGSM_ERR_BAD_ARG;
+    const int zeros[UGSM_MAX_BATCH] = {0};
+    int fw, fh;
+    UCHK(multi_check(ctx, n, W, H, stride, off_x, off_y, zeros, &fw, &fh, &tau));
+    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
+    UCHK(multi_checked_bufs(ctx, *s, n, W, H, fw, fh));
+    const size_t fn3 = 3 * (size_t)fw * fh;  // the left-to-right level-F-1 state, staged in the slot's hout
+    UCHK(grow(ctx, s->hout, s->hout_cap, std::max(fn3, s->hout_cap)));
+    UCHK(enqueue_foveated_multi_checked(ctx, *s, slot, d_rgbL, d_rgbR, W, H, stride, n, off_x, off_y, s->hout, d_stack, tau));
+    return mark_done(ctx, *s);
 }
 
 int ugsm_submit_foveated_multi(ugsm_ctx *ctx, int slot, const uint8_t *d_rgbL, const uint8_t *d_rgbR, int W, int H, int stride, int n,
@@ -2178,8 +2319,9 @@ int ugsm_match_foveated(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR,
     return drained(ctx, 0, match_foveated_on_slot(ctx, 0, rgbL, rgbR, W, H, stride, off_x, off_y, stackH, stackV, stackC, pyrL, pyrR, true));
 }
 
+// (tau: null = the plain call, else the checked one's threshold)
 static int match_foveated_multi_on_slot0(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, int n, const int *off_x,
-                                         const int *off_y, float *const *stackH, float *const *stackV, float *const *stackC)
+                                         const int *off_y, float *const *stackH, float *const *stackV, float *const *stackC, const float *tau = nullptr)
 {
     Slot *s;
     UCHK(get_slot(ctx, 0, &s));
@@ -2188,15 +2330,16 @@ static int match_foveated_multi_on_slot0(ugsm_ctx *ctx, const uint8_t *rgbL, con
         if (!stackH[k] || !stackV[k] || !stackC[k]) return UGSM_ERR_BAD_ARG;
     const int zeros[UGSM_MAX_BATCH] = {0};
     int fw, fh;
-    UCHK(multi_check(ctx, n, W, H, stride, off_x, off_y, zeros, &fw, &fh));
+    UCHK(multi_check(ctx, n, W, H, stride, off_x, off_y, zeros, &fw, &fh, tau));
     HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
-    UCHK(multi_level_bufs(ctx, *s, n, W, H, fw, fh));
+    UCHK(tau ? multi_checked_bufs(ctx, *s, n, W, H, fw, fh) : multi_level_bufs(ctx, *s, n, W, H, fw, fh));
     const size_t fn = (size_t)fw * fh, stackn = (size_t)ctx->cfg.fovea_levels * fn;
     UCHK(grow(ctx, s->hout, s->hout_cap, 3 * fn + (size_t)n * 3 * stackn));  // [state 3 fn][n stacks of 3 stackn]
     UCHK(stage_in(ctx, *s, rgbL, rgbR, W, H, stride));
     float *d_stack[UGSM_MAX_BATCH];
     for (int k = 0; k < n; k++) d_stack[k] = s->hout + 3 * fn + (size_t)k * 3 * stackn;
-    UCHK(enqueue_foveated_multi(ctx, *s, 0, s->rgbL, s->rgbR, W, H, stride, n, off_x, off_y, s->hout, d_stack));
+    if (tau) UCHK(enqueue_foveated_multi_checked(ctx, *s, 0, s->rgbL, s->rgbR, W, H, stride, n, off_x, off_y, s->hout, d_stack, *tau));
+    else UCHK(enqueue_foveated_multi(ctx, *s, 0, s->rgbL, s->rgbR, W, H, stride, n, off_x, off_y, s->hout, d_stack));
     for (int k = 0; k < n; k++) {
         float *const dst[3] = {stackH[k], stackV[k], stackC[k]};
         for (int c = 0; c < 3; c++) HIPCHK(ctx, hipMemcpyAsync(dst[c], d_stack[k] + c * stackn, stackn * sizeof(float), hipMemcpyDeviceToHost, s->st));
@@ -2209,6 +2352,12 @@ int ugsm_match_foveated_multi(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t 
                               const int *off_y, float *const *stackH, float *const *stackV, float *const *stackC)
 {
     return drained(ctx, 0, match_foveated_multi_on_slot0(ctx, rgbL, rgbR, W, H, stride, n, off_x, off_y, stackH, stackV, stackC));
+}
+
+int ugsm_match_foveated_multi_checked(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, int n, const int *off_x,
+                                      const int *off_y, float *const *stackH, float *const *stackV, float *const *stackC, float tau)
+{
+    return drained(ctx, 0, match_foveated_multi_on_slot0(ctx, rgbL, rgbR, W, H, stride, n, off_x, off_y, stackH, stackV, stackC, &tau));
 }
 
 int ugsm_submit_foveated_host(ugsm_ctx *ctx, int slot, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, int off_x,

@@ -83,6 +83,7 @@ struct Slot {
     int nreal = 1;
     // The fine phase of ugsm_submit_foveated_multi: the nb fields are nb WINDOWS OF ONE PAIR -- every virtual pair reads pair 0's two pyramids,
     // unswapped (pair_pyr), under pair 0's range word (copied to the others' entries); lvl_stride is one fovea field there as well.
+    // ugsm_submit_foveated_multi_checked runs both at once: nb = 2 nreal, entry nreal + k is window k with the two pyramids exchanged.
     bool one_pair = false;
     float *A = nullptr, *Rw = nullptr, *B = nullptr, *d0 = nullptr, *d1 = nullptr;
     // Side stream of the slot (round 3): the right image's upload and pyramid, and then A = G_clamp * L^2 of every full-frame level

@@ -149,15 +149,16 @@ class MatchGPULib:
         return self._stack(cv_ptrL, cv_ptrR, False, off_x, off_y)[0]
 
     # -- several windows of one pair (not in the reference; include/ugsm.h, "several fovea windows on ONE pair") --
-    def matchStackMulti(self, cv_ptrL, cv_ptrR, offsets):
+    def matchStackMulti(self, cv_ptrL, cv_ptrR, offsets, tau=None):
         """matchStack for every (off_x, off_y) of `offsets` (1 .. 16) in one call -- pyramids and the coarse levels once, the windows' fine
-        levels in lockstep.  Returns one float32 (foveatelevel, 3, fovH, fovW) per window, each what matchStack returns for its offset."""
+        levels in lockstep.  Returns one float32 (foveatelevel, 3, fovH, fovW) per window, each what matchStack returns for its offset.
+        tau (> 0): the checked call -- both directions in lockstep, each stack what matchStack returns under setLRCheck(tau, 2)."""
         L, R = _as_rgb8(cv_ptrL), _as_rgb8(cv_ptrR)
         if L.shape != R.shape or L.strides[0] != R.strides[0]:
             raise UgsmError(_lib.UGSM_ERR_SIZE_MISMATCH, "left/right images differ in size")
         rows, cols = L.shape[:2]
         self.fovW, self.fovH = _lib.fovea_dims(cols, rows, self._levels, self.foveatelevel)
-        stacks = self._ctx.match_foveated_multi(L, R, [(int(x), int(y)) for x, y in offsets])
+        stacks = self._ctx.match_foveated_multi(L, R, [(int(x), int(y)) for x, y in offsets], tau)
         return [np.ascontiguousarray(st.transpose(1, 0, 2, 3)) for st in stacks]
 
     # -- matchStackPyramid, MatchGPULib.cpp:534-700 --
