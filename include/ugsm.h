@@ -37,7 +37,9 @@ extern "C" {
                                ugsm_get_input_format; the merged cloud of the fovea stack -- ugsm_fovea_level_mapping, ugsm_fovea_cloud_points,
                                ugsm_point_cloud_fovea_all; the LR check of the foveated calls -- UGSM_LR_FULL / UGSM_LR_FOVEATED, ugsm_set_lr_check,
                                ugsm_get_lr_check, ugsm_last_lr_marked_levels; the merged cloud of several windows' stacks --
-                               ugsm_fovea_multi_cloud_points, ugsm_point_cloud_fovea_multi
+                               ugsm_fovea_multi_cloud_points, ugsm_point_cloud_fovea_multi; the warped right image and the photometric residual of a
+                               match -- ugsm_warp_planes, ugsm_warp_right, ugsm_warp_right_fovea, ugsm_photometric_residual,
+                               ugsm_photometric_residual_fovea
                                6: the kernel choices follow what is in flight, not ugsm_config.slots: ugsm_plan_level takes `alone`, ugsm_plan_level_in_frame
                                is gone, ugsm_level_plan.latency_policy is .alone; ugsm_enqueue_* returns UGSM_OK once the pair is accepted (a failed
                                CALL is reported through ugsm_completion.status only); the fovea shard carries a status word (a rank that fails still
@@ -780,6 +782,57 @@ int ugsm_reconstruct_full(ugsm_ctx *ctx, int slot, const float *d_stackH, const 
  * UGSM_ERR_BAD_ARG.  Asynchronous on `slot`. */
 int ugsm_reconstruct_full_multi(ugsm_ctx *ctx, int slot, int n, const float *const *d_stack, int W, int H,
                                 const int *off_x, const int *off_y, float *d_out3);
+
+/* ---- the warped right image and the photometric residual of a match ----------------------------------------------------------------
+ *
+ * MatchGPULib::warpRightImage (MatchGPULib.h:40, MatchGPULib.cpp:1445-1518, stage `warp` / kernel warpAbyB, MatchLib.cu:499-549) on device
+ * memory, and the number that goes with the picture: whether, without ground truth, the right image lands on the left one under a field.
+ *
+ * THE WARP.  For a W x H plane src and fields dx, dy of the same size
+ *   warp(src, dx, dy)[iy][ix] = src[ tex(((float)iy + 0.5f) + dy[iy][ix], H) ][ tex(((float)ix + 0.5f) + dx[iy][ix], W) ]
+ * with tex(f, n) the matcher's texture index: floor(f); !(floor >= 0), NaN included, gives 0; floor > n-1 gives n-1.  The sums are binary32,
+ * each rounded on its own; the fetched value is stored as it is, with no arithmetic on it.  For finite and for wild disparities (NaN, +-inf,
+ * +-3e38, +-2^31, denormals) this is, bit for bit, the reference's `warp` with texSrc = src, texdispx = dx, texdispy = dy, and the matcher's
+ * own fetch of the right image inside an iteration.
+ *
+ * THE RESIDUAL.  Left planes L_c, right planes R_c (c = 0, 1, 2), fields dx, dy and weights conf (NULL: every weight is 1.0f).  With
+ * R'_c = warp(R_c, dx, dy), the per-pixel term is t = fabsf(L_c - R'_c) in float, then t = t * conf in float; S_c = sum(t) per channel and
+ * C = sum(conf).  The four sums are binary64, in the fixed order of weightedDifference as this build defines it (row f-4,
+ * ugsm_stage_weighted_difference): within a row, lane l = x mod 64 adds its columns left to right from 0.0, and the 64 lane sums are then
+ * added in lane order from 0.0; the row sums go the same way over y mod 64.  So (float)(S_a / C) is what ugsm_stage_weighted_difference
+ * returns for the fields (L_a, L_b, conf) and (R'_a, R'_b, .).  No float atomics anywhere: the same bytes come out from run to run.  The
+ * device writes S_0, S_1, S_2, C as four doubles; the host forms S_c / C, and C == 0 is the host's business.  A mono8 context: S_0 = S_1 = S_2.
+ *
+ * All five calls are asynchronous on `slot`'s stream, like ugsm_triangulate -- so ordered behind a ugsm_submit_* on the same slot -- and
+ * make no host synchronisation unless a scratch buffer has to grow.  The residual's row sums (4 doubles per row and level) live in a
+ * per-slot scratch that grows on demand, counted by ugsm_context_device_bytes; UGSM_ERR_NOMEM if it cannot grow, and the context stays
+ * usable.  The images are read in the context's input format, captured at the call (ugsm_set_input_format).
+ * UGSM_ERR_STATE while pairs enqueued with ugsm_enqueue_* are outstanding.  UGSM_ERR_BAD_ARG, before any device work: a null pointer
+ * (d_conf / d_stackc excepted), W or H < 1, H above 65535, more than 2^28 pixels, stride < bytes per pixel * W, channels outside 1 .. 96, a
+ * bad slot, d_dst == d_src or d_warp == d_pyrR (the warp is not in place), a d_sums that is not 8-byte aligned, the fovea forms on a
+ * context with fovea_levels < 2.
+ * NOT built: a per-pixel residual map; a byte-image (rgb8) output of the warp; queue / managed forms; the stacks of several windows in one
+ * call (call the stack form once per window); a residual that feeds back into the confidence. */
+/* planes in, planes out: MatchGPULib::warpRightImage on device memory.  channels planes of W x H floats, one (dx, dy) for all of them */
+int ugsm_warp_planes(ugsm_ctx *ctx, int slot, const float *d_src, int channels, int W, int H,
+                     const float *d_dispx, const float *d_dispy, float *d_dst);
+/* the right IMAGE as it is on the device (the context's input format) -> three float planes R', G', B' of the warped image, 3 x H x W
+ * floats; mono8: three equal planes.  No float copy of the image is made first. */
+int ugsm_warp_right(ugsm_ctx *ctx, int slot, const uint8_t *d_rgbR, int W, int H, int stride,
+                    const float *d_dispx, const float *d_dispy, float *d_warp3);
+/* every level of a fovea stack in ONE launch: level k of d_pyrR ((F*3*fovH) x fovW floats, rows [level][channel][row], as
+ * ugsm_submit_foveated writes it) warped by level k of d_stackx / d_stacky ((F*fovH) x fovW), clamped to the fovW x fovH window as the
+ * matcher's own fetch is; d_warp is laid out as d_pyrR.  F is the context's fovea_levels. */
+int ugsm_warp_right_fovea(ugsm_ctx *ctx, int slot, const float *d_pyrR, const float *d_stackx, const float *d_stacky,
+                          int fovW, int fovH, float *d_warp);
+/* the residual of a full-resolution field, straight from the two images (no warped image is stored); d_conf may be NULL; d_sums4: 4
+ * doubles on the device, 8-byte aligned: S_0, S_1, S_2, C */
+int ugsm_photometric_residual(ugsm_ctx *ctx, int slot, const uint8_t *d_rgbL, const uint8_t *d_rgbR, int W, int H, int stride,
+                              const float *d_dispx, const float *d_dispy, const float *d_conf, double *d_sums4);
+/* the same per level of a stack, one launch for the rows of all levels and one for the totals; d_stackc may be NULL; d_sums: F x 4
+ * doubles, [level][S_0, S_1, S_2, C] */
+int ugsm_photometric_residual_fovea(ugsm_ctx *ctx, int slot, const float *d_pyrL, const float *d_pyrR, const float *d_stackx,
+                                    const float *d_stacky, const float *d_stackc, int fovW, int fovH, double *d_sums);
 
 /* ---- stage-level entry points (tests only; device pointers; synchronous) -------- */
 /* (the probes of the kernels' exact arithmetic shortcuts -- ugsm_stage_poly_probe, ugsm_stage_div3_probe, ugsm_stage_div_probe -- are

@@ -189,6 +189,28 @@ public:
         return fin;
     }
 
+    // MatchGPULib.cpp:1445-1518.  right[j] = imageW*imageH floats for j < channels, disparity[0] / disparity[1] the horizontal / vertical
+    // field.  Returns `channels` malloc'd planes: right[j] fetched where the matcher fetches it under the field (include/ugsm.h, "the warp").
+    float **warpRightImage(float **right, float **disparity, int channels, int imageW, int imageH)
+    {
+        if (!right || !disparity || channels < 1 || imageW < 1 || imageH < 1) return nullptr;
+        const size_t n = (size_t)imageW * imageH;
+        void *d_src = nullptr, *d_disp = nullptr, *d_dst = nullptr;
+        float **out = alloc_planes(channels, n);
+        int st = ugsm_dev_alloc(ctx_, &d_src, (long long)(channels * n * sizeof(float)));
+        if (st == UGSM_OK) st = ugsm_dev_alloc(ctx_, &d_disp, (long long)(2 * n * sizeof(float)));
+        if (st == UGSM_OK) st = ugsm_dev_alloc(ctx_, &d_dst, (long long)(channels * n * sizeof(float)));
+        for (int j = 0; j < channels && st == UGSM_OK; j++) st = ugsm_copy_to_device(ctx_, (float *)d_src + j * n, right[j], (long long)(n * sizeof(float)));
+        for (int k = 0; k < 2 && st == UGSM_OK; k++) st = ugsm_copy_to_device(ctx_, (float *)d_disp + k * n, disparity[k], (long long)(n * sizeof(float)));
+        if (st == UGSM_OK) st = ugsm_warp_planes(ctx_, 0, (float *)d_src, channels, imageW, imageH, (float *)d_disp, (float *)d_disp + n, (float *)d_dst);
+        if (st == UGSM_OK) st = ugsm_wait(ctx_, 0);
+        for (int j = 0; j < channels && st == UGSM_OK; j++) st = ugsm_copy_to_host(ctx_, out[j], (float *)d_dst + j * n, (long long)(n * sizeof(float)));
+        for (void *p : {d_src, d_disp, d_dst})
+            if (p) ugsm_dev_free(ctx_, p);
+        if (st != UGSM_OK) return fail(out, channels, st);
+        return out;
+    }
+
     // ---- the pipelined twin of match / matchStack / matchStackPyramid (not in the reference): include/ugsm.h, "the queue" ------------
     // The images are copied into page-locked staging memory of the library before the call returns (the cv_bridge image may be freed);
     // the result comes out of nextDone, in arrival order.  Every call flushes: a frame starts at once if a slot is free, and under load

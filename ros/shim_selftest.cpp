@@ -110,6 +110,26 @@ int main(int argc, char **argv)
             free(chk);
             if (bad) return 14;
         }
+        // warpRightImage (MatchGPULib.cpp:1445-1518): the right image is the left one moved by two pixels, so under dx = 2, dy = 0 it lands
+        // on the left image wherever the fetch stays inside the frame (columns 0 .. W-3)
+        {
+            const size_t n = (size_t)W * H;
+            std::vector<float> planes(3 * n), left(3 * n), field(2 * n, 0.0f);
+            for (size_t i = 0; i < n; i++) {
+                field[i] = 2.0f;
+                for (int c = 0; c < 3; c++) { planes[c * n + i] = r[3 * i + c]; left[c * n + i] = l[3 * i + c]; }
+            }
+            float *right[3] = {planes.data(), planes.data() + n, planes.data() + 2 * n}, *disp[2] = {field.data(), field.data() + n};
+            float **warped = m.warpRightImage(right, disp, 3, W, H);
+            if (!warped) return 15;
+            size_t bad = 0;
+            for (int c = 0; c < 3; c++)
+                for (int y = 0; y < H; y++) bad += std::memcmp(warped[c] + (size_t)y * W, left.data() + c * n + (size_t)y * W, sizeof(float) * (W - 2)) != 0;
+            std::printf("warpRightImage by dx = 2 vs the left image: %s\n", bad ? "DIFFER" : "identical");
+            for (int c = 0; c < 3; c++) free(warped[c]);
+            free(warped);
+            if (bad) return 16;
+        }
         for (int k = 0; k < m.getFoveateLevel(); k++) { for (int i = 0; i < 3; i++) free(st[k][i]); free(st[k]); }
         free(st);
     } catch (const std::exception &e) {

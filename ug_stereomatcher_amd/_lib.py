@@ -67,6 +67,8 @@ EXPORTS = [
     "ugsm_enqueue_full_cloud", "ugsm_enqueue_foveated_cloud", "ugsm_enqueue_full_cloud_managed", "ugsm_enqueue_foveated_cloud_managed", "ugsm_done_cloud",
     # the checked multi-window call
     "ugsm_submit_foveated_multi_checked", "ugsm_match_foveated_multi_checked",
+    # the warped right image and the photometric residual of a match
+    "ugsm_warp_planes", "ugsm_warp_right", "ugsm_warp_right_fovea", "ugsm_photometric_residual", "ugsm_photometric_residual_fovea",
 ]
 # ... and what include/ugsm_dev.h adds (libugsm_dev.so only)
 DEV_EXPORTS = ["ugsm_stage_poly_probe", "ugsm_stage_div3_probe", "ugsm_stage_div_probe", "ugsm_stage_range_words", "ugsm_stage_iterate_rgb8", "ugsm_stage_level0_direct"]
@@ -368,6 +370,11 @@ def load(dev: bool = False):
     lib.ugsm_fovea_multi_cloud_points.argtypes = [i, i, i, i, i, ip, ip, i, C.POINTER(C.c_longlong)]
     lib.ugsm_fovea_multi_cloud_points.restype = C.c_longlong
     lib.ugsm_point_cloud_fovea_multi.argtypes = [vp, i, i, pp, i, i, ip, ip, vp, i, dpp, dpp, C.POINTER(CloudParams), vp, C.c_longlong, vp, vp]
+    lib.ugsm_warp_planes.argtypes = [vp, i, vp, i, i, i, vp, vp, vp]
+    lib.ugsm_warp_right.argtypes = [vp, i, vp, i, i, i, vp, vp, vp]
+    lib.ugsm_warp_right_fovea.argtypes = [vp, i, vp, vp, vp, i, i, vp]
+    lib.ugsm_photometric_residual.argtypes = [vp, i, vp, vp, i, i, i, vp, vp, vp, vp]
+    lib.ugsm_photometric_residual_fovea.argtypes = [vp, i, vp, vp, vp, vp, vp, i, i, vp]
     if bool(lib.ugsm_is_dev_library()) != bool(dev):
         raise UgsmError(UGSM_ERR_STATE, f"{path} is not the {'development' if dev else 'product'} build")
     _libs[dev] = lib
@@ -517,6 +524,9 @@ class Context:
             for p in getattr(self, "_pinned", []):
                 self.lib.ugsm_host_free(self._h, p)
             self._pinned = []
+            if getattr(self, "_res_sums", None) is not None:
+                self.lib.ugsm_dev_free(self._h, self._res_sums)
+                self._res_sums = None
             self.lib.ugsm_destroy(self._h)
             self._h = None
 
@@ -716,6 +726,52 @@ class Context:
                                                            C.byref(params), d_points, int(cap_points), d_count))
         self.check(self.lib.ugsm_wait(self._h, slot))
         return int(self.to_host(d_count, (1,), np.int64)[0])
+
+    # ---- the warped right image and the photometric residual of a match (include/ugsm.h) -----------------------------------------------
+    def warp_planes(self, d_src: int, channels: int, W: int, H: int, d_dispx: int, d_dispy: int, d_dst: int, slot: int = 0, wait: bool = True):
+        """MatchGPULib::warpRightImage on device memory: `channels` float planes of W x H warped by one (dx, dy) into d_dst."""
+        self.check(self.lib.ugsm_warp_planes(self._h, slot, d_src, channels, W, H, d_dispx, d_dispy, d_dst))
+        if wait:
+            self.check(self.lib.ugsm_wait(self._h, slot))
+
+    def warp_right(self, d_rgbR: int, W: int, H: int, stride: int, d_dispx: int, d_dispy: int, d_warp3: int, slot: int = 0, wait: bool = True):
+        """The right image (the context's input format) warped into three float planes at d_warp3; wait=False leaves it on the slot's stream."""
+        self.check(self.lib.ugsm_warp_right(self._h, slot, d_rgbR, W, H, stride, d_dispx, d_dispy, d_warp3))
+        if wait:
+            self.check(self.lib.ugsm_wait(self._h, slot))
+
+    def warp_right_fovea(self, d_pyrR: int, d_stackx: int, d_stacky: int, fovW: int, fovH: int, d_warp: int, slot: int = 0, wait: bool = True):
+        """Every level of the right fovea pyramid stack warped by its level of the disparity stacks, one launch; d_warp laid out as d_pyrR."""
+        self.check(self.lib.ugsm_warp_right_fovea(self._h, slot, d_pyrR, d_stackx, d_stacky, fovW, fovH, d_warp))
+        if wait:
+            self.check(self.lib.ugsm_wait(self._h, slot))
+
+    def _residual_sums(self, levels: int, slot: int):
+        """The doubles the last residual on `slot` wrote -> (S / C as float32[levels][3], C[levels]); the raw sums stay in last_residual_sums."""
+        self.check(self.lib.ugsm_wait(self._h, slot))
+        raw = self.to_host(self._res_sums, (levels, 4), np.float64)
+        self.last_residual_sums = raw
+        with np.errstate(all="ignore"):
+            q = (raw[:, :3] / raw[:, 3:4]).astype(np.float32)
+        return q, raw[:, 3].copy()
+
+    def _residual_buffer(self):
+        if getattr(self, "_res_sums", None) is None:
+            self._res_sums = self.alloc(UGSM_MAX_LEVELS * 4 * 8)   # (freed by close())
+        return self._res_sums
+
+    def photometric_residual(self, d_rgbL: int, d_rgbR: int, W: int, H: int, stride: int, d_dispx: int, d_dispy: int, d_conf=None, slot: int = 0):
+        """sum(|L_c - warp(R_c)| * conf) / sum(conf) per channel, straight from the two images: (float32[3], C); the four raw doubles
+        S_0, S_1, S_2, C are kept in last_residual_sums[0].  d_conf None: every weight 1."""
+        self.check(self.lib.ugsm_photometric_residual(self._h, slot, d_rgbL, d_rgbR, W, H, stride, d_dispx, d_dispy, d_conf, self._residual_buffer()))
+        q, c = self._residual_sums(1, slot)
+        return q[0], float(c[0])
+
+    def photometric_residual_fovea(self, d_pyrL: int, d_pyrR: int, d_stackx: int, d_stacky: int, d_stackc, fovW: int, fovH: int, slot: int = 0):
+        """The same per level of a fovea stack: (float32[F][3], C[F]); the raw doubles [level][S_0, S_1, S_2, C] in last_residual_sums."""
+        self.check(self.lib.ugsm_photometric_residual_fovea(self._h, slot, d_pyrL, d_pyrR, d_stackx, d_stacky, d_stackc, fovW, fovH,
+                                                            self._residual_buffer()))
+        return self._residual_sums(self.cfg.fovea_levels, slot)
 
     def cloud_to_host(self, d_points: int, count: int, format: int = UGSM_CLOUD_PCL32) -> np.ndarray:
         """The first `count` records at d_points as a structured array of CLOUD_PCL32 or CLOUD_XYZRGB16."""

@@ -196,6 +196,30 @@ void launch_upsample_paste_multi(hipStream_t st, const float *src3, int W, int H
                                  int fovW, int fovH, const PasteWindows &pw);
 // S_dx, S_dy, C of weightedDifference (MatchGPULib.cpp:1336-1437) into out3; rowsum = 3*H doubles of scratch
 void launch_weighted_difference(hipStream_t st, const float *newd3, const float *oldd3, int W, int H, double *rowsum, double *out3);
+// MatchGPULib::warpRightImage (MatchGPULib.cpp:1445-1518, kernel warpAbyB MatchLib.cu:499-549) -- the warp form of k_rgb_planes:
+//   dst[iy][ix] = src[tex_index(((float)iy + 0.5f) + dy[iy][ix], H)][tex_index(((float)ix + 0.5f) + dx[iy][ix], W)], the value stored as fetched.
+// in == kInPlanes: src is `planes` float planes of W x H, dst as many, the grid's z the plane; plane z is warped by field z / per_field of
+// dx / dy (fields W x H apart): per_field = planes for one field for all of them, 3 for a fovea stack (z = 3 x level + channel).
+// in == an input format (UGSM_INPUT_*): src is the 8-bit image (`stride` bytes a row), planes == 3: a thread fetches its pixel once and
+// stores the three (the four-byte formats take their word loads where the image and the stride are 4-byte aligned).
+struct WarpArgs {
+    const void *src;
+    int stride, W, H, planes, per_field;
+    const float *dx, *dy;
+    float *dst;
+};
+void launch_warp(hipStream_t st, const WarpArgs &a, int in);
+// The photometric residual of a match -- forms of k_wdiff_rows / k_wdiff_total: per channel c, t = fabsf(L_c - warp(R_c)) in float, t = t * conf in
+// float, S_c = sum(t), C = sum(conf) (conf null: 1.0f), binary64 sums in row f-4's fixed order.  in == kInPlanes: L and R are `levels` levels of
+// [channel][row] float planes (a fovea pyramid stack), dx / dy / conf as many levels of W x H; an input format (UGSM_INPUT_*): the two 8-bit images, levels == 1.
+// rowsum: levels x H x 4 doubles of scratch; sums: levels x 4 doubles [S0, S1, S2, C].  Two launches for all levels.
+struct ResidualArgs {
+    const void *L, *R;
+    int stride, W, H, levels;
+    const float *dx, *dy, *conf;
+    double *rowsum;
+};
+void launch_residual(hipStream_t st, const ResidualArgs &a, int in, double *sums);
 
 // ---- libugsm_dev.so only (UGSM_DEV_LIB; csrc/dev/): kernel_path 1 (one kernel per reference stage), round 1's LDS-tiled K-cost
 // (ugsm_config.march_min_pixels < 0) and the probe kernels.  The product build has no-op stand-ins so that the runtime reads the same;

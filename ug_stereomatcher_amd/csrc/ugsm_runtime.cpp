@@ -1894,7 +1894,7 @@ void ugsm_destroy(ugsm_ctx *ctx)
         harvest(ctx, s);
         for (hipEvent_t e : s.pool) (void)hipEventDestroy(e);
         for (void *p : {(void *)s.pyrL, (void *)s.pyrR, (void *)s.A, (void *)s.Rw, (void *)s.B, (void *)s.d0, (void *)s.d1,
-                        (void *)s.rgbL, (void *)s.rgbR, (void *)s.hout, (void *)s.range_bad, (void *)s.d2, (void *)s.wd_rows})
+                        (void *)s.rgbL, (void *)s.rgbR, (void *)s.hout, (void *)s.range_bad, (void *)s.d2, (void *)s.wd_rows, (void *)s.res_rows})
             if (p) (void)hipFree(p);
         if (s.wd_host) (void)hipHostFree(s.wd_host);
         if (s.hpin) (void)hipHostFree(s.hpin);

@@ -1,4 +1,5 @@
-// ugsm_slot.hpp -- the runtime's own state, for its translation units (ugsm_runtime.cpp: the matcher; ugsm_cloud.cpp: the clouds): the
+// ugsm_slot.hpp -- the runtime's own state, for its translation units (ugsm_runtime.cpp: the matcher; ugsm_cloud.cpp: the clouds;
+// ugsm_warp.cpp: the warped right image and the photometric residual): the
 // slot, the context, the checks and the few helpers of ugsm_runtime.cpp that the cloud layer enqueues through.  Nothing here is exported.
 // (The layers above the slot API -- queue, shard -- and the tests' fake runtimes compile against ugsm_internal.hpp, which needs no HIP.)
 #pragma once
@@ -124,6 +125,8 @@ struct Slot {
     size_t wd_cap = 0;
     double *wd_host = nullptr;      // page-locked, 3 doubles
     SlotCloud cloud;                // row f-1, the clouds
+    double *res_rows = nullptr;     // the photometric residual (ugsm_warp.cpp): 4 doubles per row and level, grown on demand (grow: counted)
+    size_t res_cap = 0;
     int iters_run[UGSM_MAX_LEVELS];
     unsigned *range_bad = nullptr;  // device word: 0 while every pyramid value of the pair in this slot passed range_ok (ugsm_exact.hpp)
     float *hout = nullptr;  // device staging for host-API outputs

@@ -125,6 +125,22 @@ class MatchGPULib:
             for p in ps + [pout]:
                 c.free(p)
 
+    # -- warpRightImage, MatchGPULib.cpp:1445-1518 --
+    def warpRightImage(self, right, disparity, channels: int, imageW: int, imageH: int) -> np.ndarray:
+        """right: `channels` float planes of imageH x imageW; disparity[0] / disparity[1]: the horizontal / vertical field.  Returns the
+        warped planes, float32 (channels, imageH, imageW): out[j][y][x] = right[j] at the texel the matcher fetches for (x, y)."""
+        src = np.ascontiguousarray(np.asarray(right, np.float32)[:channels]).reshape(channels, imageH, imageW)
+        dx = np.ascontiguousarray(np.asarray(disparity[0], np.float32)).reshape(imageH, imageW)
+        dy = np.ascontiguousarray(np.asarray(disparity[1], np.float32)).reshape(imageH, imageW)
+        c = self._ctx
+        ps = [c.to_device(src), c.to_device(dx), c.to_device(dy), c.alloc(src.nbytes)]
+        try:
+            c.warp_planes(ps[0], channels, imageW, imageH, ps[1], ps[2], ps[3])
+            return c.to_host(ps[3], (channels, imageH, imageW))
+        finally:
+            for p in ps:
+                c.free(p)
+
     def _stack(self, cv_ptrL, cv_ptrR, want_pyr: bool, off_x: int = 0, off_y: int = 0):
         L, R = _as_rgb8(cv_ptrL), _as_rgb8(cv_ptrR)
         if L.shape != R.shape or L.strides[0] != R.strides[0]:
