@@ -16,7 +16,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = os.path.join(_HERE, "libugsm_oracle.so")
 _GOLD = os.path.join(_HERE, "_ref", "libgold.so")
 _MATCHLIB = os.path.join(_HERE, "_ref", "libmatchlib_cpu.so")
-_REFERENCE = "/root/reference"
+_DRIVER = os.path.join(_HERE, "_ref", "ref_driver")
+_REFERENCE = os.environ.get("REF", "/root/reference")  # as oracle/Makefile: REF ?= /root/reference
 
 _f32p = C.POINTER(C.c_float)
 _u8p = C.POINTER(C.c_uint8)
@@ -25,8 +26,9 @@ _i32p = C.POINTER(C.c_int)
 
 def build(force: bool = False) -> None:
     """Compile the oracle and, when the reference checkout is present, whichever of oracle/_ref/libgold.so (the reference's CPU
-    convolution) and oracle/_ref/libmatchlib_cpu.so (the reference's stage file MatchLib.cu, run on the CPU through oracle/ref_cpu/)
-    is missing or older than what it is built from."""
+    convolution), oracle/_ref/libmatchlib_cpu.so (the reference's stage file MatchLib.cu, run on the CPU through oracle/ref_cpu/) and
+    oracle/_ref/ref_driver (its host driver MatchGPULib.cpp on top of both, behind oracle/ref_cpu/ref_driver.cpp) is missing or older
+    than what it is built from."""
     src = os.path.join(_HERE, "ugsm_oracle.c")
     stale = (not os.path.exists(_LIB)) or os.path.getmtime(_LIB) < os.path.getmtime(src)
     if force or stale:
@@ -37,6 +39,11 @@ def build(force: bool = False) -> None:
         shim = [os.path.join(_HERE, "ref_cpu", f) for f in ("cuda_runtime.h", "helper_cuda.h", "shim_exports.cpp", "launch_rewrite.py")]
         if force or not os.path.exists(_MATCHLIB) or any(os.path.getmtime(f) > os.path.getmtime(_MATCHLIB) for f in shim):
             subprocess.check_call(["make", "-s", "-C", _HERE, "ref-matchlib"])
+        host = [os.path.join(_HERE, "ref_cpu", f) for f in ("cuda_runtime.h", "helper_cuda.h", "helper_functions.h", "cv.h", "highgui.h",
+                                                            os.path.join("cv_bridge", "cv_bridge.h"), "host_alloc.h", "host_rewrite.py",
+                                                            "launch_rewrite.py", "smem_canvas.cpp", "ref_driver.cpp")]
+        if force or not os.path.exists(_DRIVER) or any(os.path.getmtime(f) > os.path.getmtime(_DRIVER) for f in host):
+            subprocess.check_call(["make", "-s", "-C", _HERE, "ref-driver"])
 
 
 _lib = None

@@ -1,6 +1,7 @@
 /*
  * cuda_runtime.h -- a CPU stand-in for the slice of the CUDA runtime that the reference's stage file
- * (src/gpu_matcher/MatchLib.cu) uses, so that g++ can compile that file unchanged into oracle/_ref/libmatchlib_cpu.so.
+ * (src/gpu_matcher/MatchLib.cu) and its host driver (src/gpu_matcher/MatchGPULib.cpp) use, so that g++ can compile the first
+ * unchanged into oracle/_ref/libmatchlib_cpu.so and both into oracle/_ref/ref_driver.
  *
  * TEST INFRASTRUCTURE ONLY.  Written from CUDA's documented semantics (CUDA C Programming Guide: execution model,
  * "Texture Fetching" appendix, "Mathematical Functions" appendix), not from any NVIDIA header and not from the reference.
@@ -8,7 +9,15 @@
  *   __global__ / __device__ / __constant__   nothing: kernels are plain functions, constant memory is a plain global
  *   __shared__                               `static`: one block runs at a time, so the per-block array is one static
  *   threadIdx / blockIdx / blockDim / gridDim  thread-local, set by cpu_launch for every emulated thread
- *   cudaArray                                {float *data; int w, h} over caller-owned memory (cpu_array_wrap, shim_exports.cpp)
+ *   cudaArray                                {float *data; int w, h; bool owned}: over caller-owned memory (cpu_array_wrap,
+ *                                            shim_exports.cpp) or, from cudaMallocArray, owning w * h texels of its own: a copy
+ *                                            into it is a snapshot, later stores to the source do not reach the texture
+ *   cudaMalloc / cudaMallocHost / cudaFree*  device memory is host memory; every new byte is filled (cpu_alloc below)
+ *   cudaMemcpy                               memmove of `count` bytes, whatever the kind (one address space)
+ *   cudaMemcpyToArray                        `count` bytes, row after row without padding, from byte wOffset of row hOffset on;
+ *                                            a copy that would pass the array's end is cudaErrorInvalidValue and copies nothing
+ *   cudaDeviceSynchronize / cudaDeviceReset  nothing runs asynchronously and there is no device state: cudaSuccess
+ *   cudaMemGetInfo                           a fixed 1 GiB free of 1 GiB (the driver only prints it)
  *   texture<float, 2, cudaReadModeElementType>  a binding to a cudaArray; a texture reference whose filterMode, addressMode and
  *                                            normalized fields are never set is point sampled, clamp addressed and takes
  *                                            unnormalised coordinates: tex2D(t, x, y) = T[clamp(floor(y))][clamp(floor(x))]
@@ -52,13 +61,77 @@ inline thread_local dim3 blockDim;
 inline thread_local dim3 gridDim;
 
 typedef int cudaError_t;
-enum { cudaSuccess = 0 };
+enum { cudaSuccess = 0, cudaErrorInvalidValue = 1 };
 enum cudaTextureReadMode { cudaReadModeElementType = 0 };
+enum cudaMemcpyKind { cudaMemcpyHostToHost = 0, cudaMemcpyHostToDevice = 1, cudaMemcpyDeviceToHost = 2, cudaMemcpyDeviceToDevice = 3 };
 
 struct cudaArray {
     float *data;
     int w, h;
+    bool owned = false;
 };
+
+struct cudaChannelFormatDesc {
+    int bits;
+};
+template <class T>
+inline cudaChannelFormatDesc cudaCreateChannelDesc() { return {(int)(8 * sizeof(T))}; }
+
+/* ---- memory ----------------------------------------------------------------------------------------------------------- */
+
+/* New memory is uninitialised in CUDA and in C.  Here every new 32-bit word holds the value of the environment variable named
+ * (hexadecimal), zero where it is unset: UGSM_REF_HOST_FILL for malloc (host_alloc.h) and cudaMallocHost, UGSM_REF_DEVICE_FILL for
+ * cudaMalloc and cudaMallocArray.  A result that changes with the fill was read before it was written. */
+inline void *cpu_alloc(size_t bytes, const char *fill_env)
+{
+    const char *e = std::getenv(fill_env);
+    const uint32_t word = e ? (uint32_t)std::strtoul(e, nullptr, 16) : 0u;
+    const size_t n = (bytes + 3) / 4;
+    uint32_t *p = (uint32_t *)std::malloc(n ? n * 4 : 4);
+    for (size_t i = 0; p && i < n; i++) p[i] = word;
+    return p;
+}
+
+template <class T>
+inline cudaError_t cudaMalloc(T **p, size_t bytes) { return (*p = (T *)cpu_alloc(bytes, "UGSM_REF_DEVICE_FILL")) ? cudaSuccess : cudaErrorInvalidValue; }
+template <class T>
+inline cudaError_t cudaMallocHost(T **p, size_t bytes) { return (*p = (T *)cpu_alloc(bytes, "UGSM_REF_HOST_FILL")) ? cudaSuccess : cudaErrorInvalidValue; }
+inline cudaError_t cudaFree(void *p) { std::free(p); return cudaSuccess; }
+inline cudaError_t cudaFreeHost(void *p) { std::free(p); return cudaSuccess; }
+
+inline cudaError_t cudaMallocArray(cudaArray **a, const cudaChannelFormatDesc *desc, size_t w, size_t h)
+{
+    if (!desc || desc->bits != 32 || w == 0 || h == 0) return cudaErrorInvalidValue;
+    *a = new cudaArray{(float *)cpu_alloc(w * h * sizeof(float), "UGSM_REF_DEVICE_FILL"), (int)w, (int)h, true};
+    return cudaSuccess;
+}
+inline cudaError_t cudaFreeArray(cudaArray *a)
+{
+    if (a && a->owned) std::free(a->data);
+    delete a;
+    return cudaSuccess;
+}
+
+inline cudaError_t cudaMemcpy(void *dst, const void *src, size_t count, cudaMemcpyKind)
+{
+    std::memmove(dst, src, count);
+    return cudaSuccess;
+}
+inline cudaError_t cudaMemcpyToArray(cudaArray *a, size_t wOffset, size_t hOffset, const void *src, size_t count, cudaMemcpyKind)
+{
+    const size_t row = (size_t)a->w * sizeof(float), size = row * (size_t)a->h, at = hOffset * row + wOffset;
+    if (wOffset >= row || at > size || count > size - at) return cudaErrorInvalidValue;
+    std::memmove((char *)a->data + at, src, count);
+    return cudaSuccess;
+}
+
+inline cudaError_t cudaDeviceSynchronize() { return cudaSuccess; }
+inline cudaError_t cudaDeviceReset() { return cudaSuccess; }
+inline cudaError_t cudaMemGetInfo(size_t *free_bytes, size_t *total_bytes)
+{
+    *free_bytes = *total_bytes = (size_t)1 << 30;
+    return cudaSuccess;
+}
 
 template <class T, int dims, cudaTextureReadMode mode>
 struct texture {

@@ -3,7 +3,8 @@
  * oracle/_ref/libmatchlib_cpu.so next to the reference's stage file.  TEST INFRASTRUCTURE ONLY.
  *
  * cpu_array_wrap / cpu_array_free: the reference's stage functions take cudaArray pointers; the tests wrap numpy memory.
- * shim_*: the stand-in's own semantics, so that tests/test_ref_pin_host.py can check them directly.
+ * shim_*: the stand-in's own semantics, so that tests/test_ref_pin_host.py (device side) and tests/test_ref_driver_host.py (the host
+ * calls that the driver's result rests on) can check them directly.
  */
 #include "cuda_runtime.h"
 
@@ -58,5 +59,68 @@ static void barrier_probe_kernel(int *out)
 void shim_barrier_probe(int *out, int gx, int gy, int bx, int by)
 {
     cpu_launch_sync(dim3(gx, gy), dim3(bx, by), [&] { barrier_probe_kernel(out); });
+}
+
+/* ---- the host calls ------------------------------------------------------------------------------------------------------------ */
+
+/* An array from cudaMallocArray owns its texels.  The image goes host -> device buffer -> array (device to device), then the buffer is
+ * overwritten, as matchlevel overwrites the buffer a texture was copied from: out[] = the texels fetched after that, out2[] = after a
+ * second copy from the overwritten buffer.  Returns the OR of every status. */
+int shim_array_snapshot(const float *src, int w, int h, float *out, float *out2)
+{
+    const size_t bytes = (size_t)w * h * sizeof(float);
+    cudaChannelFormatDesc desc = cudaCreateChannelDesc<float>();
+    cudaArray *a = nullptr;
+    float *buf = nullptr;
+    int st = cudaMallocArray(&a, &desc, w, h) | cudaMalloc((void **)&buf, bytes);
+    st |= cudaMemcpy(buf, src, bytes, cudaMemcpyHostToDevice);
+    st |= cudaMemcpyToArray(a, 0, 0, buf, bytes, cudaMemcpyDeviceToDevice);
+    for (int i = 0; i < w * h; i++) buf[i] = -buf[i] - 1.0f;
+    cudaBindTextureToArray(probe_tex, a);
+    for (int y = 0; y < h; y++)
+        for (int x = 0; x < w; x++) out[y * w + x] = tex2D(probe_tex, x + 0.5f, y + 0.5f);
+    st |= cudaMemcpyToArray(a, 0, 0, buf, bytes, cudaMemcpyDeviceToDevice);
+    for (int y = 0; y < h; y++)
+        for (int x = 0; x < w; x++) out2[y * w + x] = tex2D(probe_tex, x + 0.5f, y + 0.5f);
+    cudaUnbindTexture(probe_tex);
+    st |= cudaFreeArray(a) | cudaFree(buf);
+    return st;
+}
+
+/* cudaMemcpyToArray of `count` bytes at byte wOffset of row hOffset into a fresh w x h array: the status, and the array's texels in out[] */
+int shim_memcpy_to_array(const float *src, int w, int h, int wOffset, int hOffset, int count, float *out)
+{
+    cudaChannelFormatDesc desc = cudaCreateChannelDesc<float>();
+    cudaArray *a = nullptr;
+    if (cudaMallocArray(&a, &desc, w, h) != cudaSuccess) return -1;
+    const int st = cudaMemcpyToArray(a, wOffset, hOffset, src, count, cudaMemcpyHostToDevice);
+    std::memcpy(out, a->data, (size_t)w * h * sizeof(float));
+    cudaFreeArray(a);
+    return st;
+}
+
+/* cudaMemcpy, device to device, between two ranges of one buffer that overlap: buf[to .. to + n) = the old buf[from .. from + n) */
+int shim_memcpy_overlap(float *buf, int from, int to, int n)
+{
+    return cudaMemcpy(buf + to, buf + from, (size_t)n * sizeof(float), cudaMemcpyDeviceToDevice);
+}
+
+/* the first and the last word of fresh memory of `bytes` bytes: 0 cudaMalloc, 1 cudaMallocHost, 2 cudaMallocArray (bytes / 4 texels wide) */
+int shim_fresh_words(int kind, int bytes, unsigned *first, unsigned *last)
+{
+    const size_t n = (size_t)bytes / 4;
+    if (kind == 2) {
+        cudaChannelFormatDesc desc = cudaCreateChannelDesc<float>();
+        cudaArray *a = nullptr;
+        if (cudaMallocArray(&a, &desc, n, 1) != cudaSuccess) return -1;
+        std::memcpy(first, a->data, 4);
+        std::memcpy(last, a->data + n - 1, 4);
+        return cudaFreeArray(a);
+    }
+    unsigned *p = nullptr;
+    if ((kind ? cudaMallocHost((void **)&p, bytes) : cudaMalloc((void **)&p, bytes)) != cudaSuccess) return -1;
+    *first = p[0];
+    *last = p[n - 1];
+    return kind ? cudaFreeHost(p) : cudaFree(p);
 }
 }

@@ -4,8 +4,9 @@
  * TEST INFRASTRUCTURE ONLY (see ugsm_oracle.h).  The arithmetic of every stage is pinned
  * against the reference's own MatchLib.cu run on the CPU (oracle/_ref/libmatchlib_cpu.so,
  * oracle/ref_cpu/, tests/test_ref_pin_host.py) and the zero-padded blur also against its
- * convolutionSeparable_gold.cpp (oracle/_ref/libgold.so); the host's orchestration
- * (MatchGPULib.cpp, unbuildable) is restated here unpinned.
+ * convolutionSeparable_gold.cpp (oracle/_ref/libgold.so); the host's orchestration is
+ * pinned against the reference's own MatchGPULib.cpp run on the CPU (oracle/_ref/ref_driver,
+ * tests/test_ref_driver_host.py, tests/golden/ref_driver_*.npz), whole calls at three sizes.
  *
  * Every function cites the reference file:line it restates (paths relative to
  * /root/reference/src/gpu_matcher/).  Written from the behaviour of that code, not

@@ -6,12 +6,14 @@
  * cpu_baseline leg and __graft_entry__.smoke() use it, as the checker.
  *
  * PARITY PIN STATUS: the reference ships no tests, golden vectors or CPU matcher
- * (SURVEY.md section 4 / 8c), and its CUDA path cannot be built here.  The only
- * reference fragment that compiles in this image is convolutionSeparable_gold.cpp
- * (oracle/_ref/libgold.so, built by oracle/Makefile from /root/reference in place);
- * the zero-padded blur of this oracle is pinned against it.  Everything else is
- * "parity unpinned" by the reference: pinned only by known-answer tests derived
- * from the reference source and by this restatement's own golden fixtures.
+ * (SURVEY.md section 4 / 8c), and its CUDA path cannot be built here as it ships.
+ * Its sources compile for the CPU where they lie (oracle/Makefile ref, oracle/ref_cpu/):
+ * convolutionSeparable_gold.cpp pins the zero-padded blur of this oracle, MatchLib.cu the
+ * arithmetic of every stage, and MatchGPULib.cpp on top of both (oracle/_ref/ref_driver)
+ * whole calls -- full mode, the fovea stack, the reconstruction, the pyramid -- at three
+ * sizes.  What the reference has no counterpart to (off-centre windows,
+ * batches, the LR check, clouds) is pinned only by known-answer tests and by this
+ * restatement's own golden fixtures.
  *
  * Arithmetic contract (see DESIGN.md "Float contract"): IEEE-754 binary32 with the
  * reference's float->double promotions mirrored, no FMA contraction

@@ -2,9 +2,11 @@
 arrays -- test infrastructure, shared by tests/test_ref_pin_host.py and tests/golden/make_golden.py.
 
 Every method is one extern "C" function of MatchLib.cu with the argument roles that MatchGPULib.cpp gives it (file:line cited per method).
-iterate() and pyramid() compose those calls in the order of the reference's host code.  The composition is THIS file's code: the host class
-(MatchGPULib.cpp) needs OpenCV and cannot be built, so the order of the calls, the buffers that alias, the taps (MatchGPULib.cpp:761-774,
-344-348) and the threshold schedule (:2299-2306) are restated here and pin nothing.  What is pinned is the arithmetic of every stage.
+iterate() and pyramid() compose those calls in the order of the reference's host code.  The composition is THIS file's code: the order of
+the calls, the buffers that alias, the taps (MatchGPULib.cpp:761-774, 344-348) and the threshold schedule (:2299-2306) are restated here
+from the cited lines, so what THIS file pins is the arithmetic of every stage.  The host's own ordering is pinned elsewhere: the host class
+itself runs on the CPU as oracle/_ref/ref_driver (oracle/ref_cpu/ref_driver.cpp, tests/ref_driver.py), whole calls of it are frozen in
+tests/golden/ref_driver_*.npz, and the oracle -- whose steps this file's composition equals bit for bit -- is held to those.
 
 The two shared-memory convolutions are only defined by the reference where the width is a multiple of 128 and the height a multiple of 64
 (elsewhere their unguarded loads read the next row or past the buffer and their stores race).  smem_rows / smem_cols

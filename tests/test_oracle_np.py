@@ -1,8 +1,8 @@
 """The C oracle against the independent numpy restatement (tests/golden/restate_np.py), bit for bit, on the committed
 fixtures.  Neither is the reference.  The arithmetic of every stage of both IS held to the reference's own stage code, MatchLib.cu
 run on the CPU (oracle/ref_cpu/, tests/test_ref_pin_host.py, tests/golden/ref_stages.npz: DESIGN.md section 3); what the two
-restatements agreeing still stands in for is everything that pin does not reach -- the host's orchestration (the order of the
-calls, the level schedule, the pyramid and fovea drivers: MatchGPULib.cpp cannot be built) and whole matches on whole images."""
+restatements agreeing still stands in for is what neither that pin nor the pin of whole calls to the reference's host driver
+(tests/test_ref_driver_host.py: fourteen levels at three sizes) reaches -- other sizes and level counts, off-centre windows."""
 import os
 import sys
 

@@ -6,8 +6,8 @@ inputs and its output compared with the matching step of oracle/ugsm_oracle.c an
 skip and tests/golden/ref_stages.npz -- what that library gave for stored inputs (tests/golden/make_golden.py) -- carries the pin.
 
 What this pins is the ARITHMETIC of every stage.  The order of the calls, the buffers that alias, the taps and the threshold schedule belong to
-the host class (MatchGPULib.cpp), which needs OpenCV and cannot be built: tests/ref_stages.py restates them from the cited lines, and a misreading
-of the host's ordering that oracle, restatement and driver share would still pass.  Out of scope: weightedDifferenceGPU / reduceGPU (early exit is
+the host class (MatchGPULib.cpp): tests/ref_stages.py restates them from the cited lines, and a misreading of the host's ordering that oracle,
+restatement and that composition share would still pass HERE.  tests/test_ref_driver_host.py closes that: the host class itself, run on the CPU.  Out of scope: weightedDifferenceGPU / reduceGPU (early exit is
 off in the reference and the project sums in double on purpose).  NaN texture coordinates are never given to the library.
 """
 import ctypes as C
