@@ -260,8 +260,7 @@ int prepare_slot(ugsm_ctx *ctx, Slot &s, int W, int H, int nb = 1)
     s.W = W;
     s.H = H;
     s.levels = levels;
-    s.nb = s.nreal = nb;
-    s.one_pair = false;
+    s.nb = nb;
     for (int i = 0; i < UGSM_MAX_LEVELS; i++) s.iters_run[i] = -1;
     s.have_pyr = false;
     s.have_coarse = false;
@@ -431,8 +430,28 @@ void set_policy(ugsm_ctx *c, const DevKnobs &k)
 struct Grp {
     int b0, n;
 };
-// pairs per launch of a batched level of a call of nb pairs: all of them; the 2 x 9 .. 2 x 16 virtual pairs of a checked foveated call
-// (Slot::nreal) in launches of equal size, none above kMaxBatch (what a Batch holds)
+// The lockstep layout of a call's levels: how many fields run together, which pyramids each reads and where its fields lie.  A value that the
+// call's sequence makes once and hands down; the slot keeps only what belongs to its real pairs (Slot::nb, Slot::lvl_stride).
+struct Shape {
+    int nb;         // the entries that run in lockstep
+    int nreal;      // entries nreal .. nb - 1 are the entries 0 .. nreal - 1 with the L and R views exchanged (pair_pyr); nreal == nb: none are
+    bool one_pair;  // every entry reads pair 0's pyramids: the entries are windows of one pair
+    size_t stride;  // floats between consecutive entries' fields in A, d0 and d1
+    // the slot's real pairs, each at its own full-frame room
+    static Shape pairs(const Slot &s) { return {s.nb, s.nb, false, s.lvl_stride}; }
+    // both directions of n pairs / n windows of one pair / both directions of n windows of one pair: every field is at most a fovea field, `field`
+    // floats of room each (fovea_field_room), so that they all lie in the level buffers the slot holds
+    static Shape both_directions(int n, size_t field) { return {2 * n, n, false, field}; }
+    static Shape windows(int n, size_t field) { return {n, n, true, field}; }
+    static Shape windows_both_directions(int n, size_t field) { return {2 * n, n, true, field}; }
+    // the coarse phase of the checked multi-window call: the one pair and its exchanged twin
+    static Shape coarse_both_directions(size_t field) { return both_directions(1, field); }
+};
+// the room of one fovea field (3 planes of fw x fh) in the level buffers, in the LR buffer and in hout: a multiple of 64 floats
+size_t fovea_field_room(int fw, int fh) { return (3 * (size_t)fw * fh + 63) & ~(size_t)63; }
+
+// entries per launch of a batched level of a call of nb entries: all of them; the 2 x 9 .. 2 x 16 entries of a checked foveated call
+// in launches of equal size, none above kMaxBatch (what a Batch holds)
 int group_pairs(int nb)
 {
     const int launches = (nb + kMaxBatch - 1) / kMaxBatch;
@@ -450,15 +469,15 @@ void for_groups(int nb, bool batched, F &&f)
     for (int b = 0; b < nb; b++) f(Grp{b, 1});
 }
 inline long long byte_diff(const void *a, const void *b) { return (long long)(reinterpret_cast<intptr_t>(a) - reinterpret_cast<intptr_t>(b)); }
-// The Batch argument of a group's launch.  Inputs and outputs are the slot's level buffers (pair b at + b * lvl_stride) unless
+// The Batch argument of a group's launch.  Inputs and outputs are the slot's level buffers (entry b at + b * sh.stride) unless
 // `outs` names per-pair destinations (the callers' buffers); `views`: the L / R views of the pairs (fovea windows sit at different
 // places); `seeds`: their seed-crop origins.  All arrays are indexed by the pair's number in the batch.
-Batch make_batch(const Slot &s, Grp g, const Img3 *views = nullptr, const SeedMap *seeds = nullptr, float *const *outs = nullptr)
+Batch make_batch(const Shape &sh, Grp g, const Img3 *views = nullptr, const SeedMap *seeds = nullptr, float *const *outs = nullptr)
 {
     Batch b{};
     b.n = g.n;
     for (int j = 0; j < g.n; j++) {
-        b.in[j] = (long long)(j * s.lvl_stride * sizeof(float));
+        b.in[j] = (long long)(j * sh.stride * sizeof(float));
         b.out[j] = outs ? byte_diff(outs[g.b0 + j], outs[g.b0]) : b.in[j];
         b.img[j] = views ? byte_diff(views[g.b0 + j].p, views[g.b0].p) : 0;
         b.cx[j] = seeds ? seeds[g.b0 + j].cx : 0;
@@ -567,8 +586,8 @@ bool ugsm::batch_level(const ugsm_ctx *ctx, int W, int H)
     return (long long)W * H <= thr;
 }
 namespace {
-// pairs a launch of a W x H level of the call in `s` holds
-int launch_pairs(const ugsm_ctx *ctx, const Slot &s, int W, int H) { return (s.nb > 1 && batch_level(ctx, W, H)) ? group_pairs(s.nb) : 1; }
+// entries a launch of a W x H level of a call of this shape holds
+int launch_pairs(const ugsm_ctx *ctx, const Shape &sh, int W, int H) { return (sh.nb > 1 && batch_level(ctx, W, H)) ? group_pairs(sh.nb) : 1; }
 
 int small_max_px(const ugsm_config &cfg, bool alone)
 {
@@ -636,10 +655,10 @@ int smooth_class_for(int W, int H, int pairs)
     return pairs <= 1 ? 0 : (((long long)W * H * pairs >= smooth_mid_min_pixels && W >= 48 && H >= 24) ? 2 : 1);
 }
 
-// S Jacobi passes + the 3x3 box (MatchGPULib.cpp:2257-2412) for every pair of the call.  On return `a` holds the
-// result and `b` is scratch (base pointers: pair k's buffers lie at + k * lvl_stride).
+// S Jacobi passes + the 3x3 box (MatchGPULib.cpp:2257-2412) for every entry of the call.  On return `a` holds the
+// result and `b` is scratch (base pointers: entry k's buffers lie at + k * sh.stride).
 // final_out (optional, fused path): per-pair destinations; the last launch writes there instead of into `b`, and `a` is then not meaningful.
-int enqueue_smooth(ugsm_ctx *ctx, Slot &s, int si, float *&a, float *&b, int W, int H, int S, bool do_box, float *const *final_out = nullptr)
+int enqueue_smooth(ugsm_ctx *ctx, Slot &s, int si, const Shape &sh, float *&a, float *&b, int W, int H, int S, bool do_box, float *const *final_out = nullptr)
 {
     const double px = (double)W * H;
     if (ctx->cfg.kernel_path == 1) {  // (never batched)
@@ -654,7 +673,7 @@ int enqueue_smooth(ugsm_ctx *ctx, Slot &s, int si, float *&a, float *&b, int W, 
             std::swap(a, b);
         }
     } else {
-        const int pairs = launch_pairs(ctx, s, W, H);
+        const int pairs = launch_pairs(ctx, sh, W, H);
         int left = S;
         do {
             int p = std::min(left, 5);
@@ -663,11 +682,11 @@ int enqueue_smooth(ugsm_ctx *ctx, Slot &s, int si, float *&a, float *&b, int W, 
             const int rh = (ctx->small_mask & 2) ? small_rh(ctx, W, H, s.alone, pairs) : 0;
             const bool box_now = do_box && left == 0;
             const bool to_final = left == 0 && final_out;
-            for_groups(s.nb, pairs > 1, [&](Grp g) {
+            for_groups(sh.nb, pairs > 1, [&](Grp g) {
                 Timer t(ctx, &s, si, rh ? KC_SMOOTH_SMALL : KC_SMOOTH, px * g.n);
-                const float *src = a + g.b0 * s.lvl_stride;
-                float *dst = to_final ? final_out[g.b0] : b + g.b0 * s.lvl_stride;
-                const Batch bt = make_batch(s, g, nullptr, nullptr, to_final ? final_out : nullptr);
+                const float *src = a + g.b0 * sh.stride;
+                float *dst = to_final ? final_out[g.b0] : b + g.b0 * sh.stride;
+                const Batch bt = make_batch(sh, g, nullptr, nullptr, to_final ? final_out : nullptr);
                 const Batch *pb = g.n > 1 ? &bt : nullptr;
                 if (rh) launch_smooth_small(s.st, src, dst, W, H, p, box_now, rh, pb);
                 else launch_smooth_fused(s.st, src, dst, W, H, p, box_now, smooth_rows_for(ctx, W, H, s.alone, g.n), pb, smooth_class_for(W, H, g.n));
@@ -699,18 +718,18 @@ int weighted_difference(ugsm_ctx *ctx, Slot &s, const float *newd3, const float 
     return UGSM_OK;
 }
 
-// matchlevel (MatchGPULib.cpp:1662-2489), iterations m_from..m_to, for every pair of the call (s.nb; in lockstep).  Lv / Rv: the pairs'
-// views of the level (s.nb entries).  cur holds (dx,dy,conf) on entry and on exit; other is scratch of the same size (base pointers:
-// pair k's fields lie at + k * lvl_stride).
+// matchlevel (MatchGPULib.cpp:1662-2489), iterations m_from..m_to, for every entry of the call (sh.nb; in lockstep).  Lv / Rv: the entries'
+// views of the level (sh.nb of them).  cur holds (dx,dy,conf) on entry and on exit; other is scratch of the same size (base pointers:
+// entry k's fields lie at + k * sh.stride).
 // final_out (optional, fused path only): per-pair destinations where the last iteration leaves its result instead of the ping-pong buffer
 // (saves the device-to-device copy of the finished level); cur/other are then not meaningful afterwards.
-// seed (optional, see fuse_seed; s.nb entries): `cur` holds the COARSER level's field (seed->Ws x seed->Hs) and iteration m_from reads its
+// seed (optional, see fuse_seed; sh.nb entries): `cur` holds the COARSER level's field (seed->Ws x seed->Hs) and iteration m_from reads its
 // starting field through the seeding map instead of from a materialised seeded field.
 // A_pre (optional, single pairs only): A = G_clamp * L^2 of this level, already computed (on the slot's side stream; the caller has made
 // the main stream wait for it); otherwise it is computed here, into s.A.
 // in (kInPlanes, or kInRGB8: level 0 of a call with Slot::direct0): Lv / Rv are byte views of the pairs' images; the level runs k_cost_march
 // (level0_direct has seen to it) and any seed map has its origin at 0.
-int run_level(ugsm_ctx *ctx, Slot &s, int si, const Img3 *Lv, const Img3 *Rv, int W, int H, int mi, int S, bool is_top, int m_from,
+int run_level(ugsm_ctx *ctx, Slot &s, int si, const Shape &sh, const Img3 *Lv, const Img3 *Rv, int W, int H, int mi, int S, bool is_top, int m_from,
               int m_to, float *&cur, float *&other, float *dbg8, float *const *final_out = nullptr, const SeedMap *seed = nullptr,
               const float *A_pre = nullptr, int in = kInPlanes)
 {
@@ -722,7 +741,7 @@ int run_level(ugsm_ctx *ctx, Slot &s, int si, const Img3 *Lv, const Img3 *Rv, in
     // previous iteration's field has to survive the smoothing ping-pong, hence a third buffer.
     const float eps = ctx->cfg.early_exit_threshold;
     const bool early = eps > 0.0f;
-    if ((early || ref) && s.nb != 1) return UGSM_ERR_STATE;  // (the batch entry points run such contexts pair by pair)
+    if ((early || ref) && sh.nb != 1) return UGSM_ERR_STATE;  // (the batch entry points run such contexts pair by pair)
     float *third = nullptr;
     if (early) {
         const size_t lvl = 3 * (size_t)W * H;
@@ -732,15 +751,15 @@ int run_level(ugsm_ctx *ctx, Slot &s, int si, const Img3 *Lv, const Img3 *Rv, in
         final_out = nullptr;
     }
     int ran = 0;
-    const int pairs = launch_pairs(ctx, s, W, H);
+    const int pairs = launch_pairs(ctx, sh, W, H);
     const bool batched = pairs > 1;
     const bool march4 = !ref && use_march4(ctx, W, H, s.alone, pairs);
     const bool march = !ref && use_march(ctx, W, H, s.alone, pairs);
     const bool small = !ref && use_small_cost(ctx, W, H, s.alone, pairs);
     if (in != kInPlanes) {  // byte views: what level0_direct promised must hold here, and the seed-crop origins -- whose Batch fields carry the R offsets -- are 0
         bool origins0 = true;
-        for (int b = 0; seed && b < s.nb; b++) origins0 = origins0 && seed[b].cx == 0 && seed[b].cy == 0;
-        if (in != kInRGB8 || march4 || !march || early || s.nb != s.nreal || !origins0) {
+        for (int b = 0; seed && b < sh.nb; b++) origins0 = origins0 && seed[b].cx == 0 && seed[b].cy == 0;
+        if (in != kInRGB8 || march4 || !march || early || sh.nb != sh.nreal || !origins0) {
             ctx->err = in != kInRGB8 ? "level 0 from the image: no kernel instance for this input form"
                        : !origins0   ? "level 0 from the image: a seed map with a crop origin (the rgb8 K-cost instance serves full mode only)"
                                      : "level 0 from the image needs the level matched by k_cost_march (kernel-choice policy: march_min_pixels, k_cost_march4's range), "
@@ -752,26 +771,26 @@ int run_level(ugsm_ctx *ctx, Slot &s, int si, const Img3 *Lv, const Img3 *Rv, in
         ctx->err = "no K-cost kernel of libugsm.so covers this level (kernel-choice policy)";
         return UGSM_ERR_STATE;
     }
-    const float *const A3 = A_pre ? A_pre : s.A;  // (pair k's A at + k * lvl_stride)
+    const float *const A3 = A_pre ? A_pre : s.A;  // (entry k's A at + k * sh.stride)
     if (!A_pre) {   // A = G_clamp * L^2 does not depend on the iteration: once per level.
-        for_groups(s.nb, batched, [&](Grp g) {
+        for_groups(sh.nb, batched, [&](Grp g) {
             Timer t(ctx, &s, si, KC_SQBLUR, px * g.n);
             if (ref) {
                 launch_sqblur_clamp_ref(s.st, Lv[g.b0], W, H, s.A);
             } else {
-                const Batch bt = make_batch(s, g, Lv);
-                launch_sqblur_clamp(s.st, Lv[g.b0], W, H, s.A + g.b0 * s.lvl_stride, g.n > 1 ? &bt : nullptr, in);
+                const Batch bt = make_batch(sh, g, Lv);
+                launch_sqblur_clamp(s.st, Lv[g.b0], W, H, s.A + g.b0 * sh.stride, g.n > 1 ? &bt : nullptr, in);
             }
         });
     }
     // (k_cost_split -- libugsm_dev.so, march_min_pixels < 0: the levels no other form covers -- has no batch index: pair by pair)
     const bool cost_batched = batched && (march4 || march || small);
-    // K-cost moves a pair's L and R views by ONE offset (Batch::img), which serves the pairs of one direction only -- pair b's views lie
-    // b pyramids behind pair 0's in both images, virtual pair nreal + b's do so with the images exchanged -- so where a checked foveated
-    // call (Slot::nreal) runs, a K-cost launch holds the pairs of one direction: two launches where every other kernel of the level has one.
+    // K-cost moves an entry's L and R views by ONE offset (Batch::img), which serves the entries of one direction only -- entry b's views lie
+    // b pyramids behind entry 0's in both images, entry nreal + b's do so with the images exchanged -- so where a shape holds both
+    // directions (nreal < nb), a K-cost launch holds the entries of one: two launches where every other kernel of the level has one.
     auto cost_groups = [&](auto &&f) {
-        if (s.nb == s.nreal) return for_groups(s.nb, cost_batched, f);
-        for (int dir = 0; dir < 2; dir++) for_groups(s.nreal, cost_batched, [&](Grp g) { f(Grp{g.b0 + dir * s.nreal, g.n}); });
+        if (sh.nb == sh.nreal) return for_groups(sh.nb, cost_batched, f);
+        for (int dir = 0; dir < 2; dir++) for_groups(sh.nreal, cost_batched, [&](Grp g) { f(Grp{g.b0 + dir * sh.nreal, g.n}); });
     };
     for (int m = m_from; m <= m_to; m++) {
         const int blend = !(is_top && m == 1);  // MatchGPULib.cpp:2223
@@ -790,9 +809,9 @@ int run_level(ugsm_ctx *ctx, Slot &s, int si, const Img3 *Lv, const Img3 *Rv, in
             const bool seeded = seed && m == m_from;
             cost_groups([&](Grp g) {
                 Timer t(ctx, &s, si, march4 ? KC_COST_MARCH4 : (march ? KC_COST_MARCH : (small ? KC_COST_SMALL : KC_COST)), px * g.n);
-                const size_t fo = g.b0 * s.lvl_stride;
+                const size_t fo = g.b0 * sh.stride;
                 const Img3 L = Lv[g.b0], R = Rv[g.b0];
-                Batch bt = make_batch(s, g, Lv, seeded ? seed : nullptr);
+                Batch bt = make_batch(sh, g, Lv, seeded ? seed : nullptr);
                 if (in != kInPlanes)  // (byte views: the R image of a pair has an offset of its own, carried where the seed-crop origins -- 0 here -- ride)
                     for (int j = 0; j < g.n; j++) {
                         const long long d = byte_diff(Rv[g.b0 + j].p, Rv[g.b0].p);
@@ -813,7 +832,7 @@ int run_level(ugsm_ctx *ctx, Slot &s, int si, const Img3 *Lv, const Img3 *Rv, in
         ran = m;
         if (early) {
             float *a = other, *b = third;  // cur (the field before this iteration) stays untouched
-            UCHK(enqueue_smooth(ctx, s, si, a, b, W, H, S, true, nullptr));
+            UCHK(enqueue_smooth(ctx, s, si, sh, a, b, W, H, S, true, nullptr));
             float dif[2] = {0.0f, 0.0f};
             if (m < m_to) UCHK(weighted_difference(ctx, s, a, cur, W, H, dif));
             float *old = cur;
@@ -824,7 +843,7 @@ int run_level(ugsm_ctx *ctx, Slot &s, int si, const Img3 *Lv, const Img3 *Rv, in
             continue;
         }
         float *a = other, *b = cur;
-        UCHK(enqueue_smooth(ctx, s, si, a, b, W, H, S, true, (m == m_to && !ref) ? final_out : nullptr));
+        UCHK(enqueue_smooth(ctx, s, si, sh, a, b, W, H, S, true, (m == m_to && !ref) ? final_out : nullptr));
         if (m == m_to && !ref && final_out) break;
         cur = a;
         other = b;
@@ -838,25 +857,25 @@ Img3 level_view(const Slot &s, const float *pyr, int lev, int ox, int oy)
 {
     return Img3{pyr + s.off[lev] + (size_t)oy * s.w[lev] + ox, s.w[lev], (size_t)s.w[lev] * s.h[lev]};
 }
-// the full-frame views of level `lev` for every pair of the call
-void full_views(const Slot &s, const float *pyr, int lev, Img3 *out)
+// the full-frame views of level `lev` for every entry of the call (a shape of real pairs)
+void full_views(const Slot &s, const Shape &sh, const float *pyr, int lev, Img3 *out)
 {
-    for (int b = 0; b < s.nb; b++) out[b] = level_view(s, pyr + b * s.pyr_stride, lev, 0, 0);
+    for (int b = 0; b < sh.nb; b++) out[b] = level_view(s, pyr + b * s.pyr_stride, lev, 0, 0);
 }
 
-// The pyramid that pair v of the call matches as its left (side 0) or right (side 1) image.  The virtual pairs nreal .. 2 nreal - 1 of a
-// checked foveated call are the pairs 0 .. nreal - 1 with the two exchanged: the right-to-left match reads the same two pyramids.  The
-// virtual pairs of a multi-window call (Slot::one_pair) are windows of pair 0: every one reads its pyramids as they are -- and, in the checked
-// multi-window call, the virtual pairs nreal .. 2 nreal - 1 read them with the two exchanged.
-const float *pair_pyr(const Slot &s, int side, int v)
+// The pyramid that entry v of the call matches as its left (side 0) or right (side 1) image.  The entries nreal .. nb - 1 of a shape that
+// holds both directions are the entries 0 .. nreal - 1 with the two exchanged: the right-to-left match reads the same two pyramids.  The
+// entries of a multi-window call (Shape::one_pair) are windows of pair 0: every one reads its pyramids as they are -- and, in the checked
+// multi-window call, the entries nreal .. nb - 1 read them with the two exchanged.
+const float *pair_pyr(const Slot &s, const Shape &sh, int side, int v)
 {
-    const bool back = v >= s.nreal;
-    if (s.one_pair) return (side == 0) != back ? s.pyrL : s.pyrR;  // (n windows of one pair: ugsm_submit_foveated_multi[_checked])
-    return ((side == 0) != back ? s.pyrL : s.pyrR) + (size_t)(back ? v - s.nreal : v) * s.pyr_stride;
+    const bool back = v >= sh.nreal;
+    if (sh.one_pair) return (side == 0) != back ? s.pyrL : s.pyrR;  // (n windows of one pair: ugsm_submit_foveated_multi[_checked])
+    return ((side == 0) != back ? s.pyrL : s.pyrR) + (size_t)(back ? v - sh.nreal : v) * s.pyr_stride;
 }
-void side_views(const Slot &s, int side, int lev, Img3 *out)
+void side_views(const Slot &s, const Shape &sh, int side, int lev, Img3 *out)
 {
-    for (int v = 0; v < s.nb; v++) out[v] = level_view(s, pair_pyr(s, side, v), lev, 0, 0);
+    for (int v = 0; v < sh.nb; v++) out[v] = level_view(s, pair_pyr(s, sh, side, v), lev, 0, 0);
 }
 
 // Level 0 of the pyramid is (float) of each byte of the image: it holds nothing the image does not, and at 16 MP storing it is 193 of the 338 MB
@@ -870,7 +889,7 @@ bool level0_direct(const ugsm_ctx *ctx, const Slot &s)
 {
     if (ctx->level0_float || ctx->cfg.kernel_path == 1 || ctx->cfg.early_exit_threshold > 0.0f || s.levels < 3) return false;
     if (ctx->hooks.input_format != kInRGB8) return false;
-    const int pairs = launch_pairs(ctx, s, s.W, s.H);
+    const int pairs = launch_pairs(ctx, Shape::pairs(s), s.W, s.H);
     return !use_march4(ctx, s.W, s.H, s.alone, pairs) && use_march(ctx, s.W, s.H, s.alone, pairs);
 }
 
@@ -980,56 +999,79 @@ const float *level_A(ugsm_ctx *ctx, Slot &s, int i)
     return s.Apyr + s.off[i];
 }
 
-// matching() with foveatedmatching==0, MatchGPULib.cpp:1196-1318, for the s.nb pairs of the call; d_out: their result buffers.
+// Level `lev` + 1's fields (Ws x Hs, in `cur`) handed to level `lev` (W x H): subsampleDisp, MatchGPULib.cpp:1526-1590, and
+// foveatedsubsampleDisp, :1595-1655.  Fills the entries' seed maps; where level `lev`'s first K-cost launch reads `cur` through them (fuse_seed)
+// that is all: true.  Otherwise launch_seed writes the seeded fields into `other` and the two swap: false.
+// g: the entries' fovea geometries, whose seed-crop origins of level `lev` apply; null (the full-frame levels): origin 0.
+bool hand_seed(ugsm_ctx *ctx, Slot &s, int si, const Shape &sh, int Ws, int Hs, int W, int H, const FoveaGeom *g, int lev, SeedMap *sm, float *&cur,
+               float *&other)
+{
+    for (int b = 0; b < sh.nb; b++) sm[b] = SeedMap{Ws, Hs, g ? g[b].cx[lev] : 0, g ? g[b].cy[lev] : 0};
+    const int np = launch_pairs(ctx, sh, W, H);
+    if (fuse_seed(ctx, W, H, s.alone, np)) return true;
+    for_groups(sh.nb, np > 1, [&](Grp gr) {
+        Timer t(ctx, &s, si, KC_SEED, (double)W * H * gr.n);
+        const Batch bt = make_batch(sh, gr, nullptr, sm);
+        launch_seed(s.st, cur + gr.b0 * sh.stride, Ws, Hs, other + gr.b0 * sh.stride, W, H, sm[gr.b0].cx, sm[gr.b0].cy, gr.n > 1 ? &bt : nullptr);
+    });
+    std::swap(cur, other);
+    return false;
+}
+
+// The full-frame levels top .. `last` of a call, coarse to fine from the zero seed, for the entries of `sh`: the loop of matching(),
+// MatchGPULib.cpp:1196-1318.  What differs between its callers comes in:
+// views(i, Lv, Rv): fills the entries' views of level i and returns their form (run_level's `in`);
+// side_A: a level's A is taken from the side stream where it was precomputed there (level_A);
+// direct_out (optional): the entries' result buffers, which level 0's last smoothing launch writes itself where it can (no 193 MB device
+// copy at 16 MP): `field` is then null.  Otherwise `field` is the level buffer that holds level `last`'s fields, for the caller's copy.
+template <class Views>
+int enqueue_descent(ugsm_ctx *ctx, Slot &s, int si, const Shape &sh, int last, Views &&views, bool side_A, float *const *direct_out, float *&field)
+{
+    float *cur = s.d0, *other = s.d1;
+    const int top = s.levels - 1;
+    for (int b = 0; b < sh.nb; b++)  // U1: zero seed
+        HIPCHK(ctx, hipMemsetAsync(cur + b * sh.stride, 0, sizeof(float) * 3 * (size_t)s.w[top] * s.h[top], s.st));
+    SeedMap sm[2 * kMaxBatch];  // (a shape of both directions: two entries per pair)
+    Img3 Lv[2 * kMaxBatch], Rv[2 * kMaxBatch];
+    bool seeded = false;
+    field = nullptr;
+    for (int i = top; i >= last; i--) {
+        s.cur_level = i;
+        const int mi = level_iterations(i);
+        const bool direct = direct_out && i == 0 && ctx->cfg.kernel_path != 1 && level_smooth(0) > 0 && !(ctx->cfg.early_exit_threshold > 0.0f);
+        const int in = views(i, Lv, Rv);
+        UCHK(run_level(ctx, s, si, sh, Lv, Rv, s.w[i], s.h[i], mi, level_smooth(i), i == top, 1, mi, cur, other, nullptr, direct ? direct_out : nullptr,
+                       seeded ? sm : nullptr, side_A ? level_A(ctx, s, i) : nullptr, in));
+        if (direct) return UGSM_OK;
+        seeded = i > last && hand_seed(ctx, s, si, sh, s.w[i], s.h[i], s.w[i - 1], s.h[i - 1], nullptr, 0, sm, cur, other);
+    }
+    field = cur;
+    return UGSM_OK;
+}
+
+// matching() with foveatedmatching==0, for the s.nb pairs of the call; d_out: their result buffers.
 // swap: the images exchanged (the right-to-left match of the LR check): the right pyramid is the "left" image; A is then computed
 // in line (the side stream's A planes belong to the left image).
 int enqueue_full(ugsm_ctx *ctx, Slot &s, int si, float *const *d_out, bool swap = false)
 {
-    const int levels = s.levels, nb = s.nb;
+    const Shape sh = Shape::pairs(s);
     const float *const pL = swap ? s.pyrR : s.pyrL, *const pR = swap ? s.pyrL : s.pyrR;
-    float *cur = s.d0, *other = s.d1;
-    const int top = levels - 1;
-    for (int b = 0; b < nb; b++)  // U1: zero seed
-        HIPCHK(ctx, hipMemsetAsync(cur + b * s.lvl_stride, 0, sizeof(float) * 3 * (size_t)s.w[top] * s.h[top], s.st));
-    SeedMap sm[kMaxBatch];
-    Img3 Lv[kMaxBatch], Rv[kMaxBatch];
-    bool seeded = false;
-    for (int i = top; i >= 0; i--) {
-        s.cur_level = i;
-        const int mi = level_iterations(i);
-        // the finest level's last smoothing launch writes the caller's buffer directly (no 193 MB device copy at 16 MP)
-        const bool direct = i == 0 && ctx->cfg.kernel_path != 1 && level_smooth(0) > 0 && !(ctx->cfg.early_exit_threshold > 0.0f);
-        const bool bytes0 = i == 0 && s.direct0;  // level 0 was not stored: the images themselves
-        if (bytes0) {
-            for (int b = 0; b < nb; b++) {
+    auto views = [&](int i, Img3 *Lv, Img3 *Rv) -> int {
+        if (i == 0 && s.direct0) {  // level 0 was not stored: the images themselves
+            for (int b = 0; b < sh.nb; b++) {
                 Lv[b] = byte_view(swap ? s.img0R[b] : s.img0L[b], s.img0_stride);
                 Rv[b] = byte_view(swap ? s.img0L[b] : s.img0R[b], s.img0_stride);
             }
-        } else {
-            full_views(s, pL, i, Lv);
-            full_views(s, pR, i, Rv);
+            return kInRGB8;
         }
-        UCHK(run_level(ctx, s, si, Lv, Rv, s.w[i], s.h[i], mi, level_smooth(i), i == top, 1, mi, cur, other, nullptr, direct ? d_out : nullptr,
-                       seeded ? sm : nullptr, (swap || nb > 1) ? nullptr : level_A(ctx, s, i), bytes0 ? kInRGB8 : kInPlanes));
-        if (direct) return UGSM_OK;
-        seeded = false;
-        if (i > 0) {
-            const int np = launch_pairs(ctx, s, s.w[i - 1], s.h[i - 1]);
-            if (fuse_seed(ctx, s.w[i - 1], s.h[i - 1], s.alone, np)) {  // the next level's first K-cost launch reads `cur` through the seeding map
-                for (int b = 0; b < nb; b++) sm[b] = SeedMap{s.w[i], s.h[i], 0, 0};
-                seeded = true;
-            } else {
-                for_groups(nb, np > 1, [&](Grp g) {
-                    Timer t(ctx, &s, si, KC_SEED, (double)s.w[i - 1] * s.h[i - 1] * g.n);
-                    const Batch bt = make_batch(s, g);
-                    launch_seed(s.st, cur + g.b0 * s.lvl_stride, s.w[i], s.h[i], other + g.b0 * s.lvl_stride, s.w[i - 1], s.h[i - 1], 0, 0, g.n > 1 ? &bt : nullptr);
-                });
-                std::swap(cur, other);
-            }
-        }
-    }
-    for (int b = 0; b < nb; b++)
-        HIPCHK(ctx, hipMemcpyAsync(d_out[b], cur + b * s.lvl_stride, sizeof(float) * 3 * (size_t)s.W * s.H, hipMemcpyDeviceToDevice, s.st));
+        full_views(s, sh, pL, i, Lv);
+        full_views(s, sh, pR, i, Rv);
+        return kInPlanes;
+    };
+    float *field;
+    UCHK(enqueue_descent(ctx, s, si, sh, 0, views, !swap && sh.nb == 1, d_out, field));
+    for (int b = 0; field && b < sh.nb; b++)
+        HIPCHK(ctx, hipMemcpyAsync(d_out[b], field + b * sh.stride, sizeof(float) * 3 * (size_t)s.W * s.H, hipMemcpyDeviceToDevice, s.st));
     return UGSM_OK;
 }
 int enqueue_full(ugsm_ctx *ctx, Slot &s, int si, float *d_out, bool swap = false) { return enqueue_full(ctx, s, si, &d_out, swap); }
@@ -1069,88 +1111,64 @@ int enqueue_full_lr(ugsm_ctx *ctx, Slot &s, int si, float *d_out)
     return UGSM_OK;
 }
 
-// a batched plane copy: pair j of group g from src0 + j * lvl_stride (a level buffer) or from its view, to its own destination
-Batch copy_batch(const Slot &s, Grp g, const Img3 *views, float *const *dsts, size_t dst_off)
+// a batched plane copy: entry j of group g from src0 + j * sh.stride (a level buffer) or from its view, to its own destination
+Batch copy_batch(const Shape &sh, Grp g, const Img3 *views, float *const *dsts, size_t dst_off)
 {
     Batch b{};
     b.n = g.n;
     for (int j = 0; j < g.n; j++) {
-        b.img[j] = views ? byte_diff(views[g.b0 + j].p, views[g.b0].p) : (long long)(j * s.lvl_stride * sizeof(float));
+        b.img[j] = views ? byte_diff(views[g.b0 + j].p, views[g.b0].p) : (long long)(j * sh.stride * sizeof(float));
         b.out[j] = byte_diff(dsts[g.b0 + j] + dst_off, dsts[g.b0] + dst_off);
     }
     return b;
 }
 
-// matching() with foveatedmatching==1 (MatchGPULib.cpp:1230-1294), split at level F-1; d_state: one buffer per pair of the call.
-int enqueue_fovea_coarse(ugsm_ctx *ctx, Slot &s, int si, float *const *d_state)
+// matching() with foveatedmatching==1 (MatchGPULib.cpp:1230-1294), split at level F-1; d_state: one buffer per entry of the call.
+int enqueue_fovea_coarse(ugsm_ctx *ctx, Slot &s, int si, const Shape &sh, float *const *d_state)
 {
-    const int levels = s.levels, F = ctx->cfg.fovea_levels, nb = s.nb;
-    if (F < 2 || F > levels) return UGSM_ERR_BAD_ARG;
-    float *cur = s.d0, *other = s.d1;
-    const int top = levels - 1;
-    for (int b = 0; b < nb; b++)
-        HIPCHK(ctx, hipMemsetAsync(cur + b * s.lvl_stride, 0, sizeof(float) * 3 * (size_t)s.w[top] * s.h[top], s.st));
-    SeedMap sm[2 * kMaxBatch];  // (a checked call: two virtual pairs per pair, Slot::nreal)
-    Img3 Lv[2 * kMaxBatch], Rv[2 * kMaxBatch];
-    bool seeded = false;
-    for (int i = top; i >= F - 1; i--) {
-        s.cur_level = i;
-        const int mi = level_iterations(i);
-        side_views(s, 0, i, Lv);
-        side_views(s, 1, i, Rv);
-        UCHK(run_level(ctx, s, si, Lv, Rv, s.w[i], s.h[i], mi, level_smooth(i), i == top, 1, mi, cur, other, nullptr, nullptr, seeded ? sm : nullptr,
-                       nb > 1 ? nullptr : level_A(ctx, s, i)));
-        seeded = false;
-        if (i > F - 1) {
-            const int np = launch_pairs(ctx, s, s.w[i - 1], s.h[i - 1]);
-            if (fuse_seed(ctx, s.w[i - 1], s.h[i - 1], s.alone, np)) {
-                for (int b = 0; b < nb; b++) sm[b] = SeedMap{s.w[i], s.h[i], 0, 0};
-                seeded = true;
-            } else {
-                for_groups(nb, np > 1, [&](Grp g) {
-                    Timer t(ctx, &s, si, KC_SEED, (double)s.w[i - 1] * s.h[i - 1] * g.n);
-                    const Batch bt = make_batch(s, g);
-                    launch_seed(s.st, cur + g.b0 * s.lvl_stride, s.w[i], s.h[i], other + g.b0 * s.lvl_stride, s.w[i - 1], s.h[i - 1], 0, 0, g.n > 1 ? &bt : nullptr);
-                });
-                std::swap(cur, other);
-            }
-        }
-    }
+    const int F = ctx->cfg.fovea_levels;
+    if (F < 2 || F > s.levels) return UGSM_ERR_BAD_ARG;
+    auto views = [&](int i, Img3 *Lv, Img3 *Rv) -> int {
+        side_views(s, sh, 0, i, Lv);
+        side_views(s, sh, 1, i, Rv);
+        return kInPlanes;
+    };
+    float *cur;
+    UCHK(enqueue_descent(ctx, s, si, sh, F - 1, views, sh.nb == 1, nullptr, cur));
     const size_t fn = (size_t)s.w[F - 1] * s.h[F - 1];
-    if (nb == 1) {
+    if (sh.nb == 1) {
         HIPCHK(ctx, hipMemcpyAsync(d_state[0], cur, sizeof(float) * 3 * fn, hipMemcpyDeviceToDevice, s.st));
     } else {
-        for_groups(nb, true, [&](Grp g) {
-            const Batch bt = copy_batch(s, g, nullptr, d_state, 0);
-            launch_copy_view(s.st, Img3{cur + g.b0 * s.lvl_stride, s.w[F - 1], fn}, s.w[F - 1], s.h[F - 1], d_state[g.b0], fn, s.w[F - 1], &bt);
+        for_groups(sh.nb, true, [&](Grp g) {
+            const Batch bt = copy_batch(sh, g, nullptr, d_state, 0);
+            launch_copy_view(s.st, Img3{cur + g.b0 * sh.stride, s.w[F - 1], fn}, s.w[F - 1], s.h[F - 1], d_state[g.b0], fn, s.w[F - 1], &bt);
         });
     }
-    s.have_coarse = nb == 1;
+    s.have_coarse = sh.nb == 1;
     return UGSM_OK;
 }
-int enqueue_fovea_coarse(ugsm_ctx *ctx, Slot &s, int si, float *d_state) { return enqueue_fovea_coarse(ctx, s, si, &d_state); }
 
-// The fine phase for the s.nb pairs of the call: per-pair states, window offsets and destinations (d_pyrL / d_pyrR may be null, and so may
-// their entries).  A checked call (Slot::nreal) brings s.nb = 2 nreal states, offsets and stacks -- a virtual pair has its pair's offsets -- and
-// nreal pyramid-stack destinations: the pyramid stacks are the real pairs'.
-int enqueue_fovea_fine(ugsm_ctx *ctx, Slot &s, int si, const float *const *d_state, const int *off_x, const int *off_y, float *const *d_stack,
-                       float *const *d_pyrL, float *const *d_pyrR)
+// The fine phase for the sh.nb entries of the call: per-entry states and stacks (sh.nb of each), and sh.nreal window offsets and pyramid-stack
+// destinations (d_pyrL / d_pyrR may be null, and so may their entries): an exchanged entry of a shape of both directions has its twin's window,
+// and the pyramid stacks are the real pairs'.
+int enqueue_fovea_fine(ugsm_ctx *ctx, Slot &s, int si, const Shape &sh, const float *const *d_state, const int *off_x, const int *off_y,
+                       float *const *d_stack, float *const *d_pyrL, float *const *d_pyrR)
 {
-    const int levels = s.levels, F = ctx->cfg.fovea_levels, nb = s.nb;
+    const int levels = s.levels, F = ctx->cfg.fovea_levels, nb = sh.nb;
     if (F < 2 || F > levels) return UGSM_ERR_BAD_ARG;
     FoveaGeom g[2 * kMaxBatch];
-    for (int b = 0; b < nb; b++) fovea_geometry(s.w, s.h, F, off_x[b], off_y[b], g[b]);
+    for (int b = 0; b < nb; b++) fovea_geometry(s.w, s.h, F, off_x[b % sh.nreal], off_y[b % sh.nreal], g[b]);
     const int fw = g[0].fw, fh = g[0].fh;
     const size_t fn = (size_t)fw * fh;
-    const int np = launch_pairs(ctx, s, fw, fh);  // (every level of the fine phase is a window of this size)
+    const int np = launch_pairs(ctx, sh, fw, fh);  // (every level of the fine phase is a window of this size)
     float *cur = s.d0, *other = s.d1;
     for (int b = 0; b < nb; b++)
-        HIPCHK(ctx, hipMemcpyAsync(cur + b * s.lvl_stride, d_state[b], sizeof(float) * 3 * fn, hipMemcpyDeviceToDevice, s.st));
-    // a stack row block / a pyramid-stack block for every pair: one launch for the batch
+        HIPCHK(ctx, hipMemcpyAsync(cur + b * sh.stride, d_state[b], sizeof(float) * 3 * fn, hipMemcpyDeviceToDevice, s.st));
+    // a stack row block / a pyramid-stack block for every entry: one launch for the batch
     auto copy_out = [&](int pairs, const Img3 *views, const float *field, float *const *dsts, size_t dst_off, size_t dst_plane) {
         for_groups(pairs, np > 1, [&](Grp gr) {
-            const Batch bt = copy_batch(s, gr, views, dsts, dst_off);
-            const Img3 src = views ? views[gr.b0] : Img3{field + gr.b0 * s.lvl_stride, fw, fn};
+            const Batch bt = copy_batch(sh, gr, views, dsts, dst_off);
+            const Img3 src = views ? views[gr.b0] : Img3{field + gr.b0 * sh.stride, fw, fn};
             launch_copy_view(s.st, src, fw, fh, dsts[gr.b0] + dst_off, dst_plane, fw, gr.n > 1 ? &bt : nullptr);
         });
     };
@@ -1160,30 +1178,20 @@ int enqueue_fovea_fine(ugsm_ctx *ctx, Slot &s, int si, const float *const *d_sta
     Img3 Lv[2 * kMaxBatch], Rv[2 * kMaxBatch];
     for (int i = F - 2; i >= 0; i--) {
         s.cur_level = i;
-        // foveatedsubsampleDisp, MatchGPULib.cpp:1595-1655
         for (int b = 0; b < nb; b++) {
-            sm[b] = SeedMap{fw, fh, g[b].cx[i], g[b].cy[i]};
-            Lv[b] = level_view(s, pair_pyr(s, 0, b), i, g[b].ox[i], g[b].oy[i]);
-            Rv[b] = level_view(s, pair_pyr(s, 1, b), i, g[b].ox[i], g[b].oy[i]);
+            Lv[b] = level_view(s, pair_pyr(s, sh, 0, b), i, g[b].ox[i], g[b].oy[i]);
+            Rv[b] = level_view(s, pair_pyr(s, sh, 1, b), i, g[b].ox[i], g[b].oy[i]);
         }
-        const bool seeded = fuse_seed(ctx, fw, fh, s.alone, np);
-        if (!seeded) {
-            for_groups(nb, np > 1, [&](Grp gr) {
-                Timer t(ctx, &s, si, KC_SEED, (double)fn * gr.n);
-                const Batch bt = make_batch(s, gr, nullptr, sm);
-                launch_seed(s.st, cur + gr.b0 * s.lvl_stride, fw, fh, other + gr.b0 * s.lvl_stride, fw, fh, sm[gr.b0].cx, sm[gr.b0].cy, gr.n > 1 ? &bt : nullptr);
-            });
-            std::swap(cur, other);
-        }
+        const bool seeded = hand_seed(ctx, s, si, sh, fw, fh, fw, fh, g, i, sm, cur, other);
         const int mi = level_iterations(i);
-        UCHK(run_level(ctx, s, si, Lv, Rv, fw, fh, mi, level_smooth(i), false, 1, mi, cur, other, nullptr, nullptr, seeded ? sm : nullptr));
+        UCHK(run_level(ctx, s, si, sh, Lv, Rv, fw, fh, mi, level_smooth(i), false, 1, mi, cur, other, nullptr, nullptr, seeded ? sm : nullptr));
         copy_out(nb, nullptr, cur, d_stack, (size_t)i * fn, (size_t)F * fn);
     }
     // pyramid stacks as the node publishes them (UG_GPU_matcher.cpp:203-213): [level][channel][row]
     for (int side = 0; side < 2; side++) {
         float *const *dsts = side == 0 ? d_pyrL : d_pyrR;
         if (!dsts) continue;
-        const int nr = s.nreal;
+        const int nr = sh.nreal;
         bool all = true, any = false;
         for (int b = 0; b < nr; b++) {
             all = all && dsts[b] != nullptr;
@@ -1207,25 +1215,77 @@ int enqueue_fovea_fine(ugsm_ctx *ctx, Slot &s, int si, const float *const *d_sta
     HIPCHK(ctx, hipGetLastError());
     return UGSM_OK;
 }
+
+// pair 0's range word into the entries 1 .. m - 1 (windows of one pair run under its word), doubling what is already there
+int spread_range_word(ugsm_ctx *ctx, Slot &s, int m)
+{
+    for (int c = 1; s.range_known && c < m; c *= 2)
+        HIPCHK(ctx, hipMemcpyAsync(s.range_bad + c, s.range_bad, sizeof(unsigned) * std::min(c, m - c), hipMemcpyDeviceToDevice, s.st));
+    return UGSM_OK;
+}
+
+// The room a checked foveated call takes in the slot's LR buffer, in floats.  Entry k's right-to-left stack lies at k * per; the count words (one
+// of 8 bytes per (entry, level); at a multiple of 64 floats: aligned) at cnt.  The right-to-left level-F-1 state: n pairs keep one each behind
+// their stack, at k * per + state; n windows of one pair (one_state) share one behind the last stack, at state.
+struct LrRoom {
+    size_t per, state, cnt, total;
+};
+LrRoom lr_room(int n, int F, int fw, int fh, bool one_state)
+{
+    const size_t stackf = 3 * (size_t)F * fw * fh, field = 3 * (size_t)fw * fh;
+    LrRoom r;
+    r.per = ((one_state ? stackf : stackf + field) + 63) & ~(size_t)63;
+    r.state = one_state ? (size_t)n * r.per : stackf;
+    r.cnt = (size_t)n * r.per + (one_state ? fovea_field_room(fw, fh) : 0);
+    r.total = r.cnt + 2 * (size_t)n * F;
+    return r;
+}
+
+// The tail of a checked foveated call: one launch of k_lr_check's stack form over every level of the n stacks against their right-to-left
+// twins (entry k's at s.lr + k * per) -- after the last level, so nothing feeds back into the matching -- and the counts back with one copy on
+// the slot's stream.
+int enqueue_lr_stack_check(ugsm_ctx *ctx, Slot &s, int si, int n, int F, int fw, int fh, float tau, float *const *d_stack, size_t per,
+                           unsigned long long *cnt)
+{
+    HIPCHK(ctx, hipMemsetAsync(cnt, 0, sizeof *cnt * n * F, s.st));
+    LrStack ls{};
+    ls.n = n;
+    ls.F = F;
+    for (int b = 0; b < n; b++) {
+        ls.fwd[b] = byte_diff(d_stack[b], d_stack[0]);
+        ls.back[b] = (long long)((size_t)b * per * sizeof(float));
+    }
+    {
+        Timer t(ctx, &s, si, KC_MISC, (double)((size_t)fw * fh) * F * n);
+        launch_lr_check(s.st, d_stack[0], s.lr, fw, fh, tau, cnt, ls);
+    }
+    HIPCHK(ctx, hipMemcpyAsync(s.lr_host + 1, cnt, sizeof *cnt * n * F, hipMemcpyDeviceToHost, s.st));
+    HIPCHK(ctx, hipGetLastError());
+    s.lr_fov_pairs = n;
+    s.lr_fov_F = F;
+    return UGSM_OK;
+}
+
+// (single pairs: the stage-wise entry points, and a multi-window call that runs window by window)
+int enqueue_fovea_coarse(ugsm_ctx *ctx, Slot &s, int si, float *d_state) { return enqueue_fovea_coarse(ctx, s, si, Shape::pairs(s), &d_state); }
 int enqueue_fovea_fine(ugsm_ctx *ctx, Slot &s, int si, const float *d_state, int off_x, int off_y, float *d_stack, float *d_pyrL, float *d_pyrR)
 {
-    return enqueue_fovea_fine(ctx, s, si, &d_state, &off_x, &off_y, &d_stack, d_pyrL ? &d_pyrL : nullptr, d_pyrR ? &d_pyrR : nullptr);
+    return enqueue_fovea_fine(ctx, s, si, Shape::pairs(s), &d_state, &off_x, &off_y, &d_stack, d_pyrL ? &d_pyrL : nullptr, d_pyrR ? &d_pyrR : nullptr);
 }
 
 }  // namespace
 // One foveated call of n pairs on device buffers: the pyramids, the coarse levels, the fine levels into the pairs' stacks.  state: n buffers
 // of 3 fovW fovH floats for level F-1's field between the two phases; d_pyrL / d_pyrR as for enqueue_fovea_fine.
 // With the foveated LR check on (ugsm_set_lr_check) the call matches both directions in lockstep and checks the stacks against each other:
-//   - the pyramids are built once; virtual pair n + b reads pair b's with the L and R views exchanged (pair_pyr), through pair b's windows and
-//     seed maps, under pair b's range word (it covers both images' pyramids: build_pyramids reports either image into range_bad[pair]);
-//     every kernel of a level takes the 2 n pairs in one launch except K-cost, which takes each direction in one (run_level);
+//   - the pyramids are built once; entry n + b of the shape reads pair b's with the L and R views exchanged (pair_pyr), through pair b's windows
+//     and seed maps, under pair b's range word (it covers both images' pyramids: build_pyramids reports either image into range_bad[pair]);
+//     every kernel of a level takes the 2 n entries in one launch except K-cost, which takes each direction in one (run_level);
 //   - every field of a foveated call is at most fovW x fovH, so the 2 n fields lie in the slot's level buffers at a stride of one such field
 //     (n pairs hold n x 3 W H floats per buffer and need 2 n x 3 fovW fovH, fovW fovH <= W H / 2 for every F >= 2: it fits, for F = 2 just);
 //   - what does NOT fit there for F = 2 is the right-to-left STACK, which has to outlive the fine levels: A, d0 and d1 are then full.  It goes,
-//     with the right-to-left state, into the slot's LR buffer (Slot::lr, what the full-mode check keeps its second field in): 3 (F + 1)
+//     with the right-to-left state, into the slot's LR buffer (Slot::lr, what the full-mode check keeps its second field in; lr_room): 3 (F + 1)
 //     fovW fovH floats per pair, 24 MB at 16 MP beside the pair's 1.35 GB, counted by ugsm_context_device_bytes;
-//   - one launch checks every level of every pair's stack (k_lr_check's stack form) after the last level, so nothing feeds back into the
-//     matching; the counts come back with one copy on the slot's stream.
+//   - one launch checks every level of every pair's stack after the last level (enqueue_lr_stack_check).
 int ugsm::enqueue_match_foveated(ugsm_ctx *ctx, Slot &s, int si, int n, const uint8_t *const *d_rgbL, const uint8_t *const *d_rgbR, int W, int H, int stride,
                                  const int *off_x, const int *off_y, float *const *state, float *const *d_stack, float *const *d_pyrL, float *const *d_pyrR)
 {
@@ -1237,54 +1297,28 @@ int ugsm::enqueue_match_foveated(ugsm_ctx *ctx, Slot &s, int si, int n, const ui
     if (!lr_fovea_on(ctx)) {
         // (a single pair alone on the chip gets level F-1 .. top's A planes from the side stream; a batch computes A in line)
         UCHK(enqueue_pyramids(ctx, s, si, d_rgbL, d_rgbR, n, W, H, stride, n == 1 ? F - 1 : -1, &win));
-        UCHK(enqueue_fovea_coarse(ctx, s, si, state));
-        return enqueue_fovea_fine(ctx, s, si, state, off_x, off_y, d_stack, d_pyrL, d_pyrR);
+        const Shape sh = Shape::pairs(s);
+        UCHK(enqueue_fovea_coarse(ctx, s, si, sh, state));
+        return enqueue_fovea_fine(ctx, s, si, sh, state, off_x, off_y, d_stack, d_pyrL, d_pyrR);
     }
     UCHK(enqueue_pyramids(ctx, s, si, d_rgbL, d_rgbR, n, W, H, stride, -1, &win));
     const int fw = s.w[F - 1], fh = s.h[F - 1];
-    const size_t fn = (size_t)fw * fh, stackf = 3 * (size_t)F * fn;
-    const size_t field = (3 * fn + 63) & ~(size_t)63;           // a virtual pair's room in A, d0, d1
-    const size_t per = (stackf + 3 * fn + 63) & ~(size_t)63;    // a pair's room in the LR buffer: [right-to-left stack][right-to-left state]
-    UCHK(ensure_level_bufs(ctx, s, 2 * (size_t)n * field));     // (holds already: see above)
-    UCHK(grow(ctx, s.lr, s.lr_cap, (size_t)n * per + 2 * (size_t)n * F));
+    const Shape sh = Shape::both_directions(n, fovea_field_room(fw, fh));
+    const LrRoom room = lr_room(n, F, fw, fh, false);
+    UCHK(ensure_level_bufs(ctx, s, sh.nb * sh.stride));  // (holds already: see above)
+    UCHK(grow(ctx, s.lr, s.lr_cap, room.total));
     UCHK(lr_host_ready(ctx, s));
-    unsigned long long *const cnt = reinterpret_cast<unsigned long long *>(s.lr + (size_t)n * per);  // one word per (pair, level)
     if (s.range_known) HIPCHK(ctx, hipMemcpyAsync(s.range_bad + n, s.range_bad, sizeof(unsigned) * n, hipMemcpyDeviceToDevice, s.st));
-    int vox[2 * kMaxBatch], voy[2 * kMaxBatch];
     float *vstate[2 * kMaxBatch], *vstack[2 * kMaxBatch];
     for (int b = 0; b < n; b++) {
-        vox[b] = vox[n + b] = off_x[b];
-        voy[b] = voy[n + b] = off_y[b];
         vstate[b] = state[b];
         vstack[b] = d_stack[b];
-        vstack[n + b] = s.lr + (size_t)b * per;
-        vstate[n + b] = vstack[n + b] + stackf;
+        vstack[n + b] = s.lr + (size_t)b * room.per;
+        vstate[n + b] = vstack[n + b] + room.state;
     }
-    const size_t real_stride = s.lvl_stride;
-    s.nb = 2 * n;
-    s.lvl_stride = field;
-    int st = enqueue_fovea_coarse(ctx, s, si, vstate);
-    if (st == UGSM_OK) st = enqueue_fovea_fine(ctx, s, si, vstate, vox, voy, vstack, d_pyrL, d_pyrR);
-    s.nb = n;
-    s.lvl_stride = real_stride;
-    UCHK(st);
-    HIPCHK(ctx, hipMemsetAsync(cnt, 0, sizeof *cnt * n * F, s.st));
-    LrStack ls{};
-    ls.n = n;
-    ls.F = F;
-    for (int b = 0; b < n; b++) {
-        ls.fwd[b] = byte_diff(d_stack[b], d_stack[0]);
-        ls.back[b] = (long long)((size_t)b * per * sizeof(float));
-    }
-    {
-        Timer t(ctx, &s, si, KC_MISC, (double)fn * F * n);
-        launch_lr_check(s.st, d_stack[0], s.lr, fw, fh, ctx->lr_tau, cnt, ls);
-    }
-    HIPCHK(ctx, hipMemcpyAsync(s.lr_host + 1, cnt, sizeof *cnt * n * F, hipMemcpyDeviceToHost, s.st));
-    HIPCHK(ctx, hipGetLastError());
-    s.lr_fov_pairs = n;
-    s.lr_fov_F = F;
-    return UGSM_OK;
+    UCHK(enqueue_fovea_coarse(ctx, s, si, sh, vstate));
+    UCHK(enqueue_fovea_fine(ctx, s, si, sh, vstate, off_x, off_y, vstack, d_pyrL, d_pyrR));
+    return enqueue_lr_stack_check(ctx, s, si, n, F, fw, fh, ctx->lr_tau, d_stack, room.per, reinterpret_cast<unsigned long long *>(s.lr + room.cnt));
 }
 
 // One full-mode call of n pairs on device buffers.  One pair: its pyramids (A planes from the side stream where the call is alone), the match
@@ -1336,11 +1370,11 @@ int enqueue_level0_windows(ugsm_ctx *ctx, Slot &s, int si, const uint8_t *d_rgbL
 //     level 0 (FoveaWin::later); one launch then writes level 0 of both images inside the n windows (k_rgb_planes' window form).  Pyramids
 //     that k_pyr_base does not build (fewer than three levels, kernel_path 1) hold level 0 whole and skip that launch;
 //   - the coarse phase once, its field into `state`;
-//   - the fine phase with s.nb = n virtual pairs that all read pair 0's pyramids (Slot::one_pair, pair_pyr), start from the one state and
+//   - the fine phase on a shape of n windows that all read pair 0's pyramids (Shape::one_pair, pair_pyr), start from the one state and
 //     run under pair 0's range word; their fields lie in the level buffers at a stride of one fovea field, as a checked call's do.  The
 //     caller has made the buffers hold n such fields (n x 3 fovW fovH floats exceed one pair's 3 W H as soon as n > 2^(F-1));
-//   - contexts that run pair by pair (early exit, kernel_path 1) and n == 1: the fine phase window after window, nb = 1.
-// Afterwards the slot holds no whole pyramids (have_pyr, have_coarse false) and its nb, nreal and lvl_stride are one pair's again.
+//   - contexts that run pair by pair (early exit, kernel_path 1) and n == 1: the fine phase window after window, as single pairs.
+// Afterwards the slot holds no whole pyramids (have_pyr, have_coarse false).
 int enqueue_foveated_multi(ugsm_ctx *ctx, Slot &s, int si, const uint8_t *d_rgbL, const uint8_t *d_rgbR, int W, int H, int stride, int n,
                            const int *off_x, const int *off_y, float *state, float *const *d_stack)
 {
@@ -1357,24 +1391,15 @@ int enqueue_foveated_multi(ugsm_ctx *ctx, Slot &s, int si, const uint8_t *d_rgbL
         if (n == 1 || ctx->cfg.kernel_path == 1 || ctx->cfg.early_exit_threshold > 0.0f) {
             for (int k = 0; k < n && st == UGSM_OK; k++) st = enqueue_fovea_fine(ctx, s, si, state, off_x[k], off_y[k], d_stack[k], nullptr, nullptr);
         } else {
-            const size_t field = (3 * (size_t)win.w * win.h + 63) & ~(size_t)63;
-            if ((size_t)n * field > s.lvl_cap) {
+            const Shape sh = Shape::windows(n, fovea_field_room(win.w, win.h));
+            if (sh.nb * sh.stride > s.lvl_cap) {
                 ctx->err = "the level buffers do not hold the windows' fields";
                 return UGSM_ERR_STATE;
             }
-            // pair 0's range word for every virtual pair: entries 1 .. n-1, doubling what is already there
-            for (int c = 1; s.range_known && c < n; c *= 2)
-                HIPCHK(ctx, hipMemcpyAsync(s.range_bad + c, s.range_bad, sizeof(unsigned) * std::min(c, n - c), hipMemcpyDeviceToDevice, s.st));
+            UCHK(spread_range_word(ctx, s, n));
             const float *vstate[kMaxBatch];
             for (int k = 0; k < n; k++) vstate[k] = state;
-            const size_t real_stride = s.lvl_stride;
-            s.nb = s.nreal = n;
-            s.lvl_stride = field;
-            s.one_pair = true;
-            st = enqueue_fovea_fine(ctx, s, si, vstate, off_x, off_y, d_stack, nullptr, nullptr);
-            s.nb = s.nreal = 1;
-            s.lvl_stride = real_stride;
-            s.one_pair = false;
+            st = enqueue_fovea_fine(ctx, s, si, sh, vstate, off_x, off_y, d_stack, nullptr, nullptr);
         }
     }
     s.have_pyr = false;
@@ -1382,35 +1407,19 @@ int enqueue_foveated_multi(ugsm_ctx *ctx, Slot &s, int si, const uint8_t *d_rgbL
     return st;
 }
 
-// The room the checked multi-window call takes in the slot's LR buffer, in floats: n right-to-left stacks, the right-to-left level-F-1 state,
-// then one 8-byte count word per (window, level).
-struct MultiLrRoom {
-    size_t per, state, cnt, total;
-};
-MultiLrRoom multi_lr_room(int n, int F, int fw, int fh)
-{
-    const size_t fn = (size_t)fw * fh;
-    MultiLrRoom r;
-    r.per = (3 * (size_t)F * fn + 63) & ~(size_t)63;
-    r.state = (size_t)n * r.per;
-    r.cnt = r.state + ((3 * fn + 63) & ~(size_t)63);  // (a multiple of 64 floats: 8-byte aligned)
-    r.total = r.cnt + 2 * (size_t)n * F;
-    return r;
-}
-
 // ugsm_submit_foveated_multi_checked: n windows of one pair, both directions in lockstep, the n stacks checked against their right-to-left twins.
 // enqueue_foveated_multi and the checked enqueue_match_foveated composed:
 //   - one pair's pyramids with no level 0 and the one k_level0_windows launch, as the plain multi call (no A planes from the side stream: the
-//     coarse phase runs on two virtual pairs and computes A in line, as every batch does).  The right-to-left direction reads the same two
+//     coarse phase runs on two entries and computes A in line, as every batch does).  The right-to-left direction reads the same two
 //     pyramids, so nothing more is stored;
 //   - pair 0's range word into the entries 1 .. 2 n - 1;
-//   - the coarse phase once for the two directions: nb = 2, nreal = 1 (virtual pair 1 = pair 0 exchanged, pair_pyr), level F-1's two fields into
-//     `state` and into the LR buffer;
-//   - the fine phase with nb = 2 n, nreal = n, Slot::one_pair: entry k is window k left-to-right from the first state, entry n + k window k
+//   - the coarse phase once for the two directions (Shape::coarse_both_directions: entry 1 = pair 0 exchanged, pair_pyr), level F-1's two
+//     fields into `state` and into the LR buffer;
+//   - the fine phase on Shape::windows_both_directions: entry k is window k left-to-right from the first state, entry n + k window k
 //     right-to-left from the second, its stack in the LR buffer.  K-cost runs one launch per direction and level (cost_groups); more than
 //     kMaxBatch entries go through launches of equal size (group_pairs);
-//   - one launch of k_lr_check's stack form over the n (window, level) entries with the call's own tau, the counts back with one copy.
-// The caller has made the level buffers hold 2 n fovea fields and the LR buffer multi_lr_room(..).total floats.
+//   - one launch of k_lr_check's stack form over the n (window, level) entries with the call's own tau (enqueue_lr_stack_check).
+// The caller has made the level buffers hold 2 n fovea fields and the LR buffer lr_room(.., true).total floats.
 int enqueue_foveated_multi_checked(ugsm_ctx *ctx, Slot &s, int si, const uint8_t *d_rgbL, const uint8_t *d_rgbR, int W, int H, int stride, int n,
                                    const int *off_x, const int *off_y, float *state, float *const *d_stack, float tau)
 {
@@ -1422,62 +1431,27 @@ int enqueue_foveated_multi_checked(ugsm_ctx *ctx, Slot &s, int si, const uint8_t
     win.later = true;
     UCHK(enqueue_pyramids(ctx, s, si, d_rgbL, d_rgbR, W, H, stride, -1, &win));
     UCHK(enqueue_level0_windows(ctx, s, si, d_rgbL, d_rgbR, stride, n, win));
-    const int fw = win.w, fh = win.h;
-    const size_t fn = (size_t)fw * fh;
-    const size_t field = (3 * fn + 63) & ~(size_t)63;
-    const MultiLrRoom room = multi_lr_room(n, F, fw, fh);
-    if (2 * (size_t)n * field > s.lvl_cap || room.total > s.lr_cap || !s.lr_host) {
+    const size_t field = fovea_field_room(win.w, win.h);
+    const Shape sh = Shape::windows_both_directions(n, field);
+    const LrRoom room = lr_room(n, F, win.w, win.h, true);
+    if (sh.nb * sh.stride > s.lvl_cap || room.total > s.lr_cap || !s.lr_host) {
         ctx->err = "the slot's buffers do not hold the checked windows' fields";
         return UGSM_ERR_STATE;
     }
-    unsigned long long *const cnt = reinterpret_cast<unsigned long long *>(s.lr + room.cnt);
-    for (int c = 1; s.range_known && c < 2 * n; c *= 2)
-        HIPCHK(ctx, hipMemcpyAsync(s.range_bad + c, s.range_bad, sizeof(unsigned) * std::min(c, 2 * n - c), hipMemcpyDeviceToDevice, s.st));
-    int vox[2 * kMaxBatch], voy[2 * kMaxBatch];
+    UCHK(spread_range_word(ctx, s, 2 * n));
     float *vstate[2 * kMaxBatch], *vstack[2 * kMaxBatch];
     for (int k = 0; k < n; k++) {
-        vox[k] = vox[n + k] = off_x[k];
-        voy[k] = voy[n + k] = off_y[k];
         vstate[k] = state;
         vstate[n + k] = s.lr + room.state;
         vstack[k] = d_stack[k];
         vstack[n + k] = s.lr + (size_t)k * room.per;
     }
     float *const cstate[2] = {state, s.lr + room.state};
-    const size_t real_stride = s.lvl_stride;
-    s.lvl_stride = field;
-    s.nb = 2;
-    s.nreal = 1;
-    int st = enqueue_fovea_coarse(ctx, s, si, cstate);
-    if (st == UGSM_OK) {
-        s.nb = 2 * n;
-        s.nreal = n;
-        s.one_pair = true;
-        st = enqueue_fovea_fine(ctx, s, si, vstate, vox, voy, vstack, nullptr, nullptr);
-    }
-    s.nb = s.nreal = 1;
-    s.lvl_stride = real_stride;
-    s.one_pair = false;
     s.have_pyr = false;
     s.have_coarse = false;
-    UCHK(st);
-    HIPCHK(ctx, hipMemsetAsync(cnt, 0, sizeof *cnt * n * F, s.st));
-    LrStack ls{};
-    ls.n = n;
-    ls.F = F;
-    for (int k = 0; k < n; k++) {
-        ls.fwd[k] = byte_diff(d_stack[k], d_stack[0]);
-        ls.back[k] = (long long)((size_t)k * room.per * sizeof(float));
-    }
-    {
-        Timer t(ctx, &s, si, KC_MISC, (double)fn * F * n);
-        launch_lr_check(s.st, d_stack[0], s.lr, fw, fh, tau, cnt, ls);
-    }
-    HIPCHK(ctx, hipMemcpyAsync(s.lr_host + 1, cnt, sizeof *cnt * n * F, hipMemcpyDeviceToHost, s.st));
-    HIPCHK(ctx, hipGetLastError());
-    s.lr_fov_pairs = n;
-    s.lr_fov_F = F;
-    return UGSM_OK;
+    UCHK(enqueue_fovea_coarse(ctx, s, si, Shape::coarse_both_directions(field), cstate));
+    UCHK(enqueue_fovea_fine(ctx, s, si, sh, vstate, off_x, off_y, vstack, nullptr, nullptr));
+    return enqueue_lr_stack_check(ctx, s, si, n, F, win.w, win.h, tau, d_stack, room.per, reinterpret_cast<unsigned long long *>(s.lr + room.cnt));
 }
 
 // Has everything enqueued on the slot finished?  (Never blocks; a slot found idle stops counting as busy.)
@@ -2084,7 +2058,7 @@ int ugsm_submit_foveated_batch(ugsm_ctx *ctx, int slot, int n, const uint8_t *co
     const int *ox = off_x ? off_x : zeros, *oy = off_y ? off_y : zeros;
     int fw, fh;
     UCHK(ugsm_fovea_dims(W, H, ctx->cfg.levels, F, &fw, &fh));
-    const size_t fn3 = (3 * (size_t)fw * fh + 63) & ~(size_t)63;  // level F-1's state of every pair, staged in the slot's hout
+    const size_t fn3 = fovea_field_room(fw, fh);  // level F-1's state of every pair, staged in the slot's hout
     UCHK(grow(ctx, s->hout, s->hout_cap, std::max(fn3 * n, s->hout_cap)));
     if (n == 1 || fovea_batch_runs_pair_by_pair(ctx)) {
         for (int b = 0; b < n; b++)
@@ -2122,55 +2096,48 @@ static int multi_check(ugsm_ctx *ctx, int n, int W, int H, int stride, const int
 static int multi_level_bufs(ugsm_ctx *ctx, Slot &s, int n, int W, int H, int fw, int fh)
 {
     if (n == 1 || ctx->cfg.kernel_path == 1 || ctx->cfg.early_exit_threshold > 0.0f) return UGSM_OK;
-    const size_t field = (3 * (size_t)fw * fh + 63) & ~(size_t)63;
-    return ensure_level_bufs(ctx, s, std::max((size_t)n * field, 3 * (size_t)W * H));
+    return ensure_level_bufs(ctx, s, std::max((size_t)n * fovea_field_room(fw, fh), 3 * (size_t)W * H));
 }
 
 // ... and of the checked call: 2 n fields in the level buffers, the right-to-left stacks, state and count words in the LR buffer
 static int multi_checked_bufs(ugsm_ctx *ctx, Slot &s, int n, int W, int H, int fw, int fh)
 {
-    const size_t field = (3 * (size_t)fw * fh + 63) & ~(size_t)63;
-    UCHK(ensure_level_bufs(ctx, s, std::max(2 * (size_t)n * field, 3 * (size_t)W * H)));
-    UCHK(grow(ctx, s.lr, s.lr_cap, multi_lr_room(n, ctx->cfg.fovea_levels, fw, fh).total));
+    UCHK(ensure_level_bufs(ctx, s, std::max(2 * (size_t)n * fovea_field_room(fw, fh), 3 * (size_t)W * H)));
+    UCHK(grow(ctx, s.lr, s.lr_cap, lr_room(n, ctx->cfg.fovea_levels, fw, fh, true).total));
     return lr_host_ready(ctx, s);
+}
+
+// (tau: null = the plain call, else the checked one's threshold)
+static int submit_foveated_multi(ugsm_ctx *ctx, int slot, const uint8_t *d_rgbL, const uint8_t *d_rgbR, int W, int H, int stride, int n, const int *off_x,
+                                 const int *off_y, float *const *d_stack, const float *tau)
+{
+    Slot *s;
+    UCHK(get_slot(ctx, slot, &s));
+    if (!d_rgbL || !d_rgbR || !d_stack) return UGSM_ERR_BAD_ARG;
+    for (int k = 0; k < n && k < UGSM_MAX_BATCH; k++)
+        if (!d_stack[k]) return UGSM_ERR_BAD_ARG;
+    const int zeros[UGSM_MAX_BATCH] = {0};
+    int fw, fh;
+    UCHK(multi_check(ctx, n, W, H, stride, off_x, off_y, zeros, &fw, &fh, tau));
+    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
+    UCHK(tau ? multi_checked_bufs(ctx, *s, n, W, H, fw, fh) : multi_level_bufs(ctx, *s, n, W, H, fw, fh));
+    const size_t fn3 = 3 * (size_t)fw * fh;  // the (left-to-right) level-F-1 state, staged in the slot's hout as ugsm_submit_foveated stages it
+    UCHK(grow(ctx, s->hout, s->hout_cap, std::max(fn3, s->hout_cap)));
+    if (tau) UCHK(enqueue_foveated_multi_checked(ctx, *s, slot, d_rgbL, d_rgbR, W, H, stride, n, off_x, off_y, s->hout, d_stack, *tau));
+    else UCHK(enqueue_foveated_multi(ctx, *s, slot, d_rgbL, d_rgbR, W, H, stride, n, off_x, off_y, s->hout, d_stack));
+    return mark_done(ctx, *s);
 }
 
 int ugsm_submit_foveated_multi_checked(ugsm_ctx *ctx, int slot, const uint8_t *d_rgbL, const uint8_t *d_rgbR, int W, int H, int stride, int n,
                                        const int *off_x, const int *off_y, float *const *d_stack, float tau)
 {
-    Slot *s;
-    UCHK(get_slot(ctx, slot, &s));
-    if (!d_rgbL || !d_rgbR || !d_stack) return UGSM_ERR_BAD_ARG;
-    for (int k = 0; k < n && k < UGSM_MAX_BATCH; k++)
-        if (!d_stack[k]) return UGSM_ERR_BAD_ARG;
-    const int zeros[UGSM_MAX_BATCH] = {0};
-    int fw, fh;
-    UCHK(multi_check(ctx, n, W, H, stride, off_x, off_y, zeros, &fw, &fh, &tau));
-    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
-    UCHK(multi_checked_bufs(ctx, *s, n, W, H, fw, fh));
-    const size_t fn3 = 3 * (size_t)fw * fh;  // the left-to-right level-F-1 state, staged in the slot's hout
-    UCHK(grow(ctx, s->hout, s->hout_cap, std::max(fn3, s->hout_cap)));
-    UCHK(enqueue_foveated_multi_checked(ctx, *s, slot, d_rgbL, d_rgbR, W, H, stride, n, off_x, off_y, s->hout, d_stack, tau));
-    return mark_done(ctx, *s);
+    return submit_foveated_multi(ctx, slot, d_rgbL, d_rgbR, W, H, stride, n, off_x, off_y, d_stack, &tau);
 }
 
 int ugsm_submit_foveated_multi(ugsm_ctx *ctx, int slot, const uint8_t *d_rgbL, const uint8_t *d_rgbR, int W, int H, int stride, int n,
                                const int *off_x, const int *off_y, float *const *d_stack)
 {
-    Slot *s;
-    UCHK(get_slot(ctx, slot, &s));
-    if (!d_rgbL || !d_rgbR || !d_stack) return UGSM_ERR_BAD_ARG;
-    for (int k = 0; k < n && k < UGSM_MAX_BATCH; k++)
-        if (!d_stack[k]) return UGSM_ERR_BAD_ARG;
-    const int zeros[UGSM_MAX_BATCH] = {0};
-    int fw, fh;
-    UCHK(multi_check(ctx, n, W, H, stride, off_x, off_y, zeros, &fw, &fh));
-    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
-    UCHK(multi_level_bufs(ctx, *s, n, W, H, fw, fh));
-    const size_t fn3 = 3 * (size_t)fw * fh;  // level F-1's state, staged in the slot's hout as ugsm_submit_foveated stages it
-    UCHK(grow(ctx, s->hout, s->hout_cap, std::max(fn3, s->hout_cap)));
-    UCHK(enqueue_foveated_multi(ctx, *s, slot, d_rgbL, d_rgbR, W, H, stride, n, off_x, off_y, s->hout, d_stack));
-    return mark_done(ctx, *s);
+    return submit_foveated_multi(ctx, slot, d_rgbL, d_rgbR, W, H, stride, n, off_x, off_y, d_stack, nullptr);
 }
 
 int ugsm_wait(ugsm_ctx *ctx, int slot)
@@ -2274,6 +2241,14 @@ int ugsm_submit_full_host(ugsm_ctx *ctx, int slot, const uint8_t *rgbL, const ui
     return match_full_on_slot(ctx, slot, rgbL, rgbR, W, H, stride, dispH, dispV, dispC, false);
 }
 
+// a device stack's H, V and C planes (stackn floats each) down into three host buffers, on the slot's stream
+static int download_stack(ugsm_ctx *ctx, Slot &s, const float *d_stack, size_t stackn, float *stackH, float *stackV, float *stackC)
+{
+    float *const dst[3] = {stackH, stackV, stackC};
+    for (int c = 0; c < 3; c++) HIPCHK(ctx, hipMemcpyAsync(dst[c], d_stack + c * stackn, stackn * sizeof(float), hipMemcpyDeviceToHost, s.st));
+    return UGSM_OK;
+}
+
 static int match_foveated_on_slot(ugsm_ctx *ctx, int slot, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, int off_x, int off_y,
                                   float *stackH, float *stackV, float *stackC, float *pyrL, float *pyrR, bool sync)
 {
@@ -2304,9 +2279,7 @@ static int match_foveated_on_slot(ugsm_ctx *ctx, int slot, const uint8_t *rgbL, 
     float *d_pr = pyrR ? d_stack + 3 * stackn + (pyrL ? 3 * stackn : 0) : nullptr;
     const uint8_t *const dL = s->rgbL, *const dR = s->rgbR;
     UCHK(enqueue_match_foveated(ctx, *s, slot, 1, &dL, &dR, W, H, stride, &off_x, &off_y, &d_state, &d_stack, d_pl ? &d_pl : nullptr, d_pr ? &d_pr : nullptr));
-    HIPCHK(ctx, hipMemcpyAsync(stackH, d_stack, stackn * sizeof(float), hipMemcpyDeviceToHost, s->st));
-    HIPCHK(ctx, hipMemcpyAsync(stackV, d_stack + stackn, stackn * sizeof(float), hipMemcpyDeviceToHost, s->st));
-    HIPCHK(ctx, hipMemcpyAsync(stackC, d_stack + 2 * stackn, stackn * sizeof(float), hipMemcpyDeviceToHost, s->st));
+    UCHK(download_stack(ctx, *s, d_stack, stackn, stackH, stackV, stackC));
     if (pyrL) HIPCHK(ctx, hipMemcpyAsync(pyrL, d_pl, 3 * stackn * sizeof(float), hipMemcpyDeviceToHost, s->st));
     if (pyrR) HIPCHK(ctx, hipMemcpyAsync(pyrR, d_pr, 3 * stackn * sizeof(float), hipMemcpyDeviceToHost, s->st));
     if (sync) s->forked = false;  // (enqueued whole, as mark_done)
@@ -2340,10 +2313,7 @@ static int match_foveated_multi_on_slot0(ugsm_ctx *ctx, const uint8_t *rgbL, con
     for (int k = 0; k < n; k++) d_stack[k] = s->hout + 3 * fn + (size_t)k * 3 * stackn;
     if (tau) UCHK(enqueue_foveated_multi_checked(ctx, *s, 0, s->rgbL, s->rgbR, W, H, stride, n, off_x, off_y, s->hout, d_stack, *tau));
     else UCHK(enqueue_foveated_multi(ctx, *s, 0, s->rgbL, s->rgbR, W, H, stride, n, off_x, off_y, s->hout, d_stack));
-    for (int k = 0; k < n; k++) {
-        float *const dst[3] = {stackH[k], stackV[k], stackC[k]};
-        for (int c = 0; c < 3; c++) HIPCHK(ctx, hipMemcpyAsync(dst[c], d_stack[k] + c * stackn, stackn * sizeof(float), hipMemcpyDeviceToHost, s->st));
-    }
+    for (int k = 0; k < n; k++) UCHK(download_stack(ctx, *s, d_stack[k], stackn, stackH[k], stackV[k], stackC[k]));
     s->forked = false;  // (enqueued whole, as mark_done)
     return ugsm_wait(ctx, 0);
 }
@@ -2450,7 +2420,7 @@ int ugsm_submit_foveated_batch_host(ugsm_ctx *ctx, int slot, int n, const uint8_
     const uint8_t *dL[UGSM_MAX_BATCH], *dR[UGSM_MAX_BATCH];
     UCHK(stage_in_batch(ctx, *s, n, rgbL, rgbR, W, H, stride, dL, dR));
     const size_t fn = (size_t)fw * fh, stackn = (size_t)F * fn;
-    const size_t st_per = (3 * fn + 63) & ~(size_t)63, sk_per = (3 * stackn + 63) & ~(size_t)63;  // hout: [states n x st_per][stacks n x sk_per]
+    const size_t st_per = fovea_field_room(fw, fh), sk_per = (3 * stackn + 63) & ~(size_t)63;  // hout: [states n x st_per][stacks n x sk_per]
     UCHK(grow(ctx, s->hout, s->hout_cap, std::max(n * (st_per + sk_per), s->hout_cap)));
     float *state[UGSM_MAX_BATCH], *stack[UGSM_MAX_BATCH];
     for (int b = 0; b < n; b++) {
@@ -2458,11 +2428,7 @@ int ugsm_submit_foveated_batch_host(ugsm_ctx *ctx, int slot, int n, const uint8_
         stack[b] = s->hout + n * st_per + b * sk_per;
     }
     UCHK(enqueue_match_foveated(ctx, *s, slot, n, dL, dR, W, H, stride, ox, oy, state, stack, nullptr, nullptr));
-    for (int b = 0; b < n; b++) {
-        HIPCHK(ctx, hipMemcpyAsync(stackH[b], stack[b], stackn * sizeof(float), hipMemcpyDeviceToHost, s->st));
-        HIPCHK(ctx, hipMemcpyAsync(stackV[b], stack[b] + stackn, stackn * sizeof(float), hipMemcpyDeviceToHost, s->st));
-        HIPCHK(ctx, hipMemcpyAsync(stackC[b], stack[b] + 2 * stackn, stackn * sizeof(float), hipMemcpyDeviceToHost, s->st));
-    }
+    for (int b = 0; b < n; b++) UCHK(download_stack(ctx, *s, stack[b], stackn, stackH[b], stackV[b], stackC[b]));
     return mark_done(ctx, *s);
 }
 
@@ -2538,9 +2504,9 @@ int ugsm_stage_iterate(ugsm_ctx *ctx, const float *d_L3, const float *d_R3, floa
         launch_range_scan(s->st, d_L3, 3 * n, s->range_bad);
         launch_range_scan(s->st, d_R3, 3 * n, s->range_bad);
     }
-    s->nb = s->nreal = 1;
+    s->nb = 1;
     const Img3 Lv{d_L3, W, n}, Rv{d_R3, W, n};
-    UCHK(run_level(ctx, *s, 0, &Lv, &Rv, W, H, mi, S, is_top != 0, m_from, m_to, cur, other, d_dbg8));
+    UCHK(run_level(ctx, *s, 0, Shape::pairs(*s), &Lv, &Rv, W, H, mi, S, is_top != 0, m_from, m_to, cur, other, d_dbg8));
     HIPCHK(ctx, hipMemcpyAsync(d_d3, cur, lvl * sizeof(float), hipMemcpyDeviceToDevice, s->st));
     return ugsm_wait(ctx, 0);
 }
@@ -2569,8 +2535,8 @@ int ugsm_stage_smooth(ugsm_ctx *ctx, float *d_d3, int W, int H, int passes, int 
     UCHK(ensure_level_bufs(ctx, *s, lvl));
     float *a = s->d0, *b = s->d1;
     HIPCHK(ctx, hipMemcpyAsync(a, d_d3, lvl * sizeof(float), hipMemcpyDeviceToDevice, s->st));
-    s->nb = s->nreal = 1;
-    UCHK(enqueue_smooth(ctx, *s, 0, a, b, W, H, passes, do_box != 0));
+    s->nb = 1;
+    UCHK(enqueue_smooth(ctx, *s, 0, Shape::pairs(*s), a, b, W, H, passes, do_box != 0));
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipMemcpyAsync(d_d3, a, lvl * sizeof(float), hipMemcpyDeviceToDevice, s->st));
     return ugsm_wait(ctx, 0);
@@ -2821,10 +2787,10 @@ int ugsm_stage_iterate_rgb8(ugsm_ctx *ctx, const uint8_t *d_rgbL, const uint8_t 
     s->have_coarse = false;
     s->range_known = true;  // (the integers 0 .. 255: always inside range_ok)
     HIPCHK(ctx, hipMemsetAsync(s->range_bad, 0, sizeof(unsigned), s->st));
-    s->nb = s->nreal = 1;
+    s->nb = 1;
     s->direct0 = false;  // (no call of the slot's: ugsm_stage_level0_direct)
     const Img3 Lv = byte_view(d_rgbL, stride), Rv = byte_view(d_rgbR, stride);
-    UCHK(run_level(ctx, *s, 0, &Lv, &Rv, W, H, mi, S, is_top != 0, m_from, m_to, cur, other, nullptr, nullptr, nullptr, nullptr, kInRGB8));
+    UCHK(run_level(ctx, *s, 0, Shape::pairs(*s), &Lv, &Rv, W, H, mi, S, is_top != 0, m_from, m_to, cur, other, nullptr, nullptr, nullptr, nullptr, kInRGB8));
     HIPCHK(ctx, hipMemcpyAsync(d_d3, cur, lvl * sizeof(float), hipMemcpyDeviceToDevice, s->st));
     return ugsm_wait(ctx, 0);
 }

@@ -76,16 +76,12 @@ struct Slot {
     size_t pyr_cap = 0;  // floats
     // Batch (round 4): the call in flight matches `nb` pairs of one size in lockstep.  Every per-pair buffer of the slot holds nb copies:
     // pair b's pyramids at pyrL / pyrR + b * pyr_stride, its level buffers (A, d0, d1) at + b * lvl_stride, its range word at range_bad + b.
+    // nb and the strides describe the call's REAL pairs and are set by prepare_slot alone (the stage entry points, which bring one field of
+    // their own, set nb = 1).  What runs in lockstep while a call's levels are
+    // enqueued -- both directions of a checked foveated call, the windows of a multi-window call, at a stride of one fovea field -- is a value
+    // the call's sequence hands down (Shape, ugsm_runtime.cpp), never written here.
     int nb = 1;
     size_t pyr_stride = 0, lvl_stride = 0;  // floats
-    // A checked foveated call (ugsm_set_lr_check, UGSM_LR_FOVEATED) matches both directions in lockstep: while its levels run, nb = 2 nreal
-    // VIRTUAL pairs -- virtual pair nreal + b is pair b with the L and R views exchanged (pair_pyr) -- and lvl_stride is the room of one
-    // fovea field, so that both directions' fields lie in the level buffers the slot holds.  Everywhere else nreal == nb.
-    int nreal = 1;
-    // The fine phase of ugsm_submit_foveated_multi: the nb fields are nb WINDOWS OF ONE PAIR -- every virtual pair reads pair 0's two pyramids,
-    // unswapped (pair_pyr), under pair 0's range word (copied to the others' entries); lvl_stride is one fovea field there as well.
-    // ugsm_submit_foveated_multi_checked runs both at once: nb = 2 nreal, entry nreal + k is window k with the two pyramids exchanged.
-    bool one_pair = false;
     float *A = nullptr, *Rw = nullptr, *B = nullptr, *d0 = nullptr, *d1 = nullptr;
     // Side stream of the slot (round 3): the right image's upload and pyramid, and then A = G_clamp * L^2 of every full-frame level
     // (MatchGPULib.cpp:1866-1875, once per level), run there beside the left pyramid and the coarse levels' iterations -- launches
