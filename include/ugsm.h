@@ -39,7 +39,8 @@ extern "C" {
                                ugsm_get_lr_check, ugsm_last_lr_marked_levels; the merged cloud of several windows' stacks --
                                ugsm_fovea_multi_cloud_points, ugsm_point_cloud_fovea_multi; the warped right image and the photometric residual of a
                                match -- ugsm_warp_planes, ugsm_warp_right, ugsm_warp_right_fovea, ugsm_photometric_residual,
-                               ugsm_photometric_residual_fovea
+                               ugsm_photometric_residual_fovea; the checked full-mode call -- ugsm_submit_full_checked, ugsm_match_full_checked,
+                               ugsm_last_lr_marked_pair
                                6: the kernel choices follow what is in flight, not ugsm_config.slots: ugsm_plan_level takes `alone`, ugsm_plan_level_in_frame
                                is gone, ugsm_level_plan.latency_policy is .alone; ugsm_enqueue_* returns UGSM_OK once the pair is accepted (a failed
                                CALL is reported through ugsm_completion.status only); the fovea shard carries a status word (a rank that fails still
@@ -220,7 +221,9 @@ int ugsm_get_input_format(const ugsm_ctx *ctx, int *format);
  * The check is a setting of the context: a threshold tau and the set of calls that apply it.  ugsm_create leaves a context at
  * (ugsm_config.lr_check_threshold, UGSM_LR_FULL): the full-mode calls check, the foveated calls do not, as in every earlier ABI.
  *   UGSM_LR_FULL      ugsm_match_full, ugsm_submit_full[_host|_batch|_batch_host] and the full-mode queue: the pair is matched a second time
- *                     with the images exchanged (ugsm_config.lr_check_threshold above); batches run pair by pair
+ *                     with the images exchanged (ugsm_config.lr_check_threshold above); batches run pair by pair.  (Both directions of a
+ *                     full-mode batch in one lockstep call, the right camera's field returned too, tau per call and not from this
+ *                     setting: ugsm_submit_full_checked.)
  *   UGSM_LR_FOVEATED  ugsm_match_foveated, ugsm_match_foveated_full, ugsm_submit_foveated[_host], ugsm_submit_foveated_batch[_host] and,
  *                     through those, ugsm_enqueue_foveated[_host|_managed].  (The multi-window call takes its check per call, not from
  *                     this setting: ugsm_submit_foveated_multi_checked.)
@@ -318,6 +321,36 @@ int ugsm_submit_full_batch_host(ugsm_ctx *ctx, int slot, int n, const uint8_t *c
 int ugsm_submit_foveated_batch_host(ugsm_ctx *ctx, int slot, int n, const uint8_t *const *rgbL, const uint8_t *const *rgbR,
                                     int W, int H, int stride, const int *off_x, const int *off_y, float *const *stackH,
                                     float *const *stackV, float *const *stackC);
+/* The CHECKED full-mode call: both directions of n pairs (1 <= n <= UGSM_MAX_BATCH, all W x H) in one lockstep call, each pair's two fields
+ * checked against each other.  tau (> 0, in pixels) is an argument of the call: the call neither reads nor changes what ugsm_set_lr_check holds.
+ *   d_rgbL, d_rgbR, d_out  HOST arrays of n DEVICE pointers, buffers laid out as for ugsm_submit_full_batch.
+ *   d_back                 the same for the right camera's checked field; may be NULL, and so may any of its entries: that pair's
+ *                          right-to-left field then stays in the slot's LR buffer, as the context's own check keeps it.
+ * The contract, bit for bit: d_out[k] is what ugsm_submit_full(L_k, R_k) writes on a context with ugsm_set_lr_check(ctx, tau, UGSM_LR_FULL),
+ * d_back[k] what that same call writes for (R_k, L_k) -- dx and dy those of the unchecked matches, the confidence zeroed where the rule of
+ * ugsm_stage_lr_check fails against the other direction's UNCHECKED dx and dy (neither check reads a confidence, so the two checks of a
+ * pair do not depend on each other) -- in any input format, captured at the call.
+ * How it runs: the pyramids of the n pairs are built once; the right-to-left match of pair k is one more entry of the same call that reads
+ * pair k's pyramids with the L and R views exchanged, so 2 n full-frame fields run through the levels in lockstep -- every kernel of a level
+ * of at most 9 Mpx one launch for all of them (launches of at most UGSM_MAX_BATCH entries; the cost kernel one launch per direction), larger
+ * levels entry by entry -- level 0's last launch writes straight into d_out[k] and d_back[k], and ONE launch checks both directions of up
+ * to eight pairs (nine to sixteen: two launches).  Cost against the context's own check, which matches the second direction after the first and single pairs only: DESIGN.md section 8.
+ * Counts: ugsm_last_lr_marked_pair(ctx, slot, k, &fwd, &back) answers for pair k; ugsm_last_lr_marked the forward count of pair n-1;
+ * ugsm_last_lr_marked_levels UGSM_ERR_STATE, as after any full-mode call.
+ * Memory: the level buffers hold 2 n full fields -- 3 x 3 W H floats per pair more than the slot of an unchecked batch of n -- and the LR
+ * buffer one field per pair whose d_back entry is NULL; both grow on demand, counted by ugsm_context_device_bytes.
+ * Status, all before anything is enqueued: !(tau > 0), NaN included, null arrays, null entries of d_rgbL / d_rgbR / d_out, n outside
+ * 1 .. UGSM_MAX_BATCH: UGSM_ERR_BAD_ARG; contexts with early_exit_threshold > 0 or kernel_path 1: UGSM_ERR_BAD_ARG (ugsm_set_lr_check's rule for
+ * the lockstep check: they have no batch dimension); the size errors of ugsm_submit_full as there; pairs outstanding in the queue:
+ * UGSM_ERR_STATE; a buffer that cannot grow: UGSM_ERR_NOMEM, the context usable afterwards.
+ * NOT built: a queue form (ugsm_enqueue_*); the page-locked _host kind.
+ * Asynchronous on `slot`. */
+int ugsm_submit_full_checked(ugsm_ctx *ctx, int slot, int n, const uint8_t *const *d_rgbL, const uint8_t *const *d_rgbR,
+                             int W, int H, int stride, float *const *d_out, float *const *d_back, float tau);
+/* Blocking, one pair, any host memory in and out, as ugsm_match_full.  backH / backV / backC (the right camera's checked planes): all three
+ * or none (NULL); anything else is UGSM_ERR_BAD_ARG. */
+int ugsm_match_full_checked(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride,
+                            float *dispH, float *dispV, float *dispC, float *backH, float *backV, float *backC, float tau);
 /* ---- several fovea windows on ONE pair ------------------------------------------------------------------------------------------------
  *
  * A host that looks at n places of one frame (1 <= n <= UGSM_MAX_BATCH) needs the pyramids and the coarse phase -- levels top .. F-1, which
@@ -866,6 +899,10 @@ long long ugsm_last_lr_marked(ugsm_ctx *ctx, int slot);
 /* The same level by level, for pair `pair` of the last call on `slot`: per_level[0 .. fovea_levels).  UGSM_ERR_STATE if that call ran
  * without the foveated check, UGSM_ERR_BAD_ARG for a bad slot or pair or a null pointer.  Valid after ugsm_wait. */
 int ugsm_last_lr_marked_levels(ugsm_ctx *ctx, int slot, int pair, long long *per_level);
+/* Pixels the check of the last ugsm_submit_full_checked / ugsm_match_full_checked on `slot` marked for pair `pair`: *fwd in the left-to-right
+ * field, *back in the right-to-left one (either may be NULL).  UGSM_ERR_STATE if the last call on the slot was another one, UGSM_ERR_BAD_ARG
+ * for a null context, a bad slot or a bad pair.  Valid after ugsm_wait. */
+int ugsm_last_lr_marked_pair(ugsm_ctx *ctx, int slot, int pair, long long *fwd, long long *back);
 /* Iterations each level of the last call on `slot` actually ran (early_exit_threshold > 0 can stop a level early);
  * per_level[UGSM_MAX_LEVELS], -1 for levels not run.  ugsm_stage_iterate records its count at index 0. */
 int ugsm_last_iterations(ugsm_ctx *ctx, int slot, int *per_level);

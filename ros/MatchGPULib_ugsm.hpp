@@ -126,6 +126,28 @@ public:
         return fin;
     }
 
+    // (not in the reference) match(L, R, 0) with the LR check at threshold tau for this call alone (ugsm_match_full_checked: both directions in
+    // one lockstep call; the context's setLRCheck setting is neither read nor changed).  Returns the left camera's checked finDisp and, where
+    // `back` is given, the right camera's in *back, malloc'd the same way.  tau <= 0 or fov != 0: match(L, R, fov), *back = nullptr.
+    template <class ImgPtr>
+    float **match(ImgPtr L, ImgPtr R, int fov, float tau, float ***back = nullptr)
+    {
+        if (back) *back = nullptr;
+        if (fov != 0 || !(tau > 0.0f)) return match(L, R, fov);
+        foveatedmatching = fov;
+        const int W = L->image.cols, H = L->image.rows;
+        if (R->image.cols != W || R->image.rows != H) return nullptr;
+        float **fin = alloc_planes(3, (size_t)W * H), **bk = back ? alloc_planes(3, (size_t)W * H) : nullptr;
+        const int st = ugsm_match_full_checked(ctx_, L->image.data, R->image.data, W, H, (int)L->image.step, fin[0], fin[1], fin[2], bk ? bk[0] : nullptr,
+                                               bk ? bk[1] : nullptr, bk ? bk[2] : nullptr, tau);
+        if (st != UGSM_OK) {
+            if (bk) { for (int c = 0; c < 3; c++) std::free(bk[c]); std::free(bk); }
+            return fail(fin, 3, st);
+        }
+        if (back) *back = bk;
+        return fin;
+    }
+
     // MatchGPULib.cpp:429-531.  Returns disparity[level][3][fovH*fovW] for level < foveatelevel.
     template <class ImgPtr>
     float ***matchStack(ImgPtr L, ImgPtr R) { return stack(L, R, nullptr, nullptr); }

@@ -19,6 +19,9 @@
 // ugsm_done_cloud, as INTEGRATION.md section 7 shows.  cloud_P1 / cloud_P2: the two 3x4 projection matrices, row-major, 12 numbers each (required);
 // cloud_sampling, cloud_format (0 PCL32, 1 XYZRGB16), cloud_compact, cloud_min_conf, cloud_z_min, cloud_z_max: ugsm_cloud_params;
 // cloud_max_points: the cap (0 = the dense size); cloud_only = 1: the planes are neither downloaded nor published.
+//
+// Nor this: the parameter `lr_check_tau` (default 0 = off).  With tau > 0 the blocking full-mode paths (topic and service) run the LR check for the call:
+// both directions in one lockstep call (ugsm_match_full_checked), the confidence plane zeroed where the match does not point back within tau pixels.
 #include <cv_bridge/cv_bridge.h>
 #include <image_transport/image_transport.h>
 #include <image_transport/subscriber_filter.h>
@@ -118,6 +121,13 @@ private:
         int f = 0;
         if (!nh_.getParam("foveated", f)) ROS_WARN("foveated option has not been set. Matcher is on non-foveated mode!");
         return f;
+    }
+    float lr_check_tau()
+    {  // (not in the reference) re-read on every call like `foveated`; > 0: the blocking full-mode matches check left against right in one
+       // lockstep call (the shim's match(L, R, fov, tau): ugsm_match_full_checked) and dispC / output_disparityC carry the checked confidence
+        double tau = 0.0;
+        ros::param::get("~lr_check_tau", tau);
+        return (float)tau;
     }
     static sensor_msgs::Image plane_msg(float *p, int rows, int cols, const std_msgs::Header &h)
     {
@@ -248,7 +258,7 @@ private:
             rsp.fdispC = stack_msg(st, 2, L->header, 0, 0, false);
             free_stack(st, mgpu_->getFoveateLevel());
         } else {
-            float **fin = mgpu_->match(L, R, fov);
+            float **fin = mgpu_->match(L, R, fov, lr_check_tau());  // (tau <= 0: the plain match)
             if (!fin) return false;
             rsp.dispH.image = plane_msg(fin[0], L->image.rows, L->image.cols, L->header); rsp.dispH.header = L->header;
             rsp.dispV.image = plane_msg(fin[1], L->image.rows, L->image.cols, R->header); rsp.dispV.header = R->header;
@@ -324,7 +334,7 @@ private:
             for (int k = 0; k < 14; k++) { for (int c = 0; c < 3; c++) { free(lf[k][c]); free(rf[k][c]); } free(lf[k]); free(rf[k]); }
             free(lf); free(rf);
         } else {
-            float **fin = mgpu_->match(L, R, fov);
+            float **fin = mgpu_->match(L, R, fov, lr_check_tau());  // (tau <= 0: the plain match)
             ROS_INFO("Non Foveated Disparity took %f Seconds", (ros::WallTime::now() - t0).toSec());
             if (!fin) return;
             const char *topics[3] = {"output_disparityH", "output_disparityV", "output_disparityC"};

@@ -130,6 +130,20 @@ int main(int argc, char **argv)
             free(warped);
             if (bad) return 16;
         }
+        // match(L, R, 0, tau): the left camera's field is match(L, R, 0)'s under setLRCheck(tau, 1), the right camera's match(R, L, 0)'s
+        {
+            float **bk = nullptr;
+            float **chk = m.match(L, R, 0, 1.0f, &bk);
+            if (!chk || !bk) return 17;
+            if (m.setLRCheck(1.0f, 1) != UGSM_OK) return 18;
+            float **seq = m.match(L, R, 0), **seqb = m.match(R, L, 0);
+            if (m.setLRCheck(0.0f, 0) != UGSM_OK || !seq || !seqb) return 19;
+            size_t bad = 0;
+            for (int c = 0; c < 3; c++) bad += std::memcmp(chk[c], seq[c], sizeof(float) * W * H) != 0 || std::memcmp(bk[c], seqb[c], sizeof(float) * W * H) != 0;
+            std::printf("match (tau 1, both directions in one call) vs the two checked matches: %s\n", bad ? "DIFFER" : "identical");
+            for (float **p : {chk, bk, seq, seqb}) { for (int c = 0; c < 3; c++) free(p[c]); free(p); }
+            if (bad) return 20;
+        }
         for (int k = 0; k < m.getFoveateLevel(); k++) { for (int i = 0; i < 3; i++) free(st[k][i]); free(st[k]); }
         free(st);
     } catch (const std::exception &e) {

@@ -2,6 +2,7 @@
 """What the LR check of the foveated calls costs (ugsm_set_lr_check, UGSM_LR_FOVEATED) -- on ONE box, in one session.
 
     python tools/lr_bench.py [--parent-tree DIR] [--rounds 3] [--out profiles/lr_fovea_bench.json]
+    python tools/lr_bench.py --full [--parent-tree DIR] [--rounds 3]      # the full-mode calls: full_main below, profiles/lr_full_bench.json
 
 At 16 MP (4928 x 3264) and 1080p, 14 / 7 levels, images resident on the device, events off, every measurement a child process of its own
 (one context per process, as tools/ab.py), the configurations of a group taking turns round by round, every child's value kept:
@@ -36,7 +37,10 @@ ap.add_argument("--burst", type=int, default=96)
 ap.add_argument("--tau", type=float, default=1.0)
 ap.add_argument("--sizes", nargs="*", default=list(SIZES))
 ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "lr_fovea_bench.json"))
-ap.add_argument("--child", choices=["call", "burst"], help="(internal) measure in this process, print one JSON line")
+ap.add_argument("--full", action="store_true", help="the full-mode table (full_main below) instead of the foveated one; writes profiles/lr_full_bench.json")
+ap.add_argument("--form", choices=["plain", "seq", "new"], default="plain", help="(internal, --child full)")
+ap.add_argument("--n", type=int, default=1, help="(internal, --child full) pairs per call")
+ap.add_argument("--child", choices=["call", "burst", "full"], help="(internal) measure in this process, print one JSON line")
 ap.add_argument("--tree", default=ROOT, help="(internal) the tree whose package the child loads")
 ap.add_argument("--checked", type=int, default=0, help="(internal)")
 ap.add_argument("--size", default="16mp", help="(internal)")
@@ -99,9 +103,76 @@ def child():
     print("LRBENCH " + json.dumps(out), flush=True)
 
 
-def measure(kind, size, tree, checked):
+def full_child():
+    """One blocking full-mode call of --n pairs (submit + ugsm_wait on a one-slot context; every pair the same two device images, its own outputs):
+    plain -- ugsm_submit_full / ugsm_submit_full_batch; seq -- the same on a context with lr_check_threshold = tau (the second direction after
+    the first, batches pair by pair); new -- ugsm_submit_full_checked, the right-to-left fields left in the slot as the context's check leaves them."""
+    sys.path.insert(0, args.tree)
+    from ug_stereomatcher_amd import _lib, synth
+    assert os.path.dirname(os.path.abspath(_lib.__file__)) == os.path.join(os.path.abspath(args.tree), "ug_stereomatcher_amd")
+    W, H = SIZES[args.size]
+    n = args.n
+    L, R = synth.make_pair(W, H, synth.BASE_SEED + 2)[:2]
+    with _lib.Context(levels=LEVELS, slots=1, batch=n, lr_check_threshold=args.tau if args.form == "seq" else 0.0) as c:
+        dL, dR = c.to_device(L), c.to_device(R)
+        dO = [c.alloc(3 * W * H * 4) for _ in range(n)]
+        ts = []
+        for k in range(args.warmup + args.reps):
+            t0 = time.perf_counter()
+            if args.form == "new":
+                c.submit_full_checked(0, [dL] * n, [dR] * n, W, H, 3 * W, dO, None, args.tau)
+            elif n == 1:
+                c.check(c.lib.ugsm_submit_full(c.handle, 0, dL, dR, W, H, 3 * W, dO[0]))
+            else:
+                c.submit_full_batch(0, [dL] * n, [dR] * n, W, H, 3 * W, dO)
+            c.check(c.lib.ugsm_wait(c.handle, 0))
+            ts.append((time.perf_counter() - t0) * 1e3)
+        ts = ts[args.warmup:]
+        out = dict(ms=statistics.median(ts), ms_min=min(ts), ms_max=max(ts), marked=int(c.lib.ugsm_last_lr_marked(c.handle, 0)), device_bytes=c.device_bytes())
+    print("LRBENCH " + json.dumps(out), flush=True)
+
+
+def full_main():
+    """--full: what the LR check of a full-mode call costs, at 16 MP and 1080p, 14 levels, every measurement a child process, the configurations
+    taking turns round by round:
+      a_plain    the plain blocking call, n = 1 (this build);
+      b_seq      the checked ugsm_submit_full of the PARENT build (--parent-tree; this build's where none is given: the same code), n = 1: the
+                 sequential form;  b_seq_this: the same on this build, where a parent was measured;
+      c_new_1    ugsm_submit_full_checked, n = 1;  c_new_8: n = 8, against  b_seq_8: the parent's checked ugsm_submit_full_batch of 8.
+    `b_spread_ms` is the range of the b_seq children; no ratio is fixed in advance (DESIGN.md section 8 quotes the table)."""
+    parent = os.path.abspath(args.parent_tree) if args.parent_tree else None
+    if parent and not os.path.exists(os.path.join(parent, "ug_stereomatcher_amd", "libugsm.so")):
+        raise SystemExit(f"{parent}: no built ug_stereomatcher_amd/libugsm.so")
+    old = parent or ROOT
+    result = dict(tool="tools/lr_bench.py --full", levels=LEVELS, tau=args.tau, rounds=args.rounds, reps=args.reps, parent_measured=bool(parent), sizes={})
+    for size in args.sizes:
+        configs = {"a_plain": (ROOT, "plain", 1), "b_seq": (old, "seq", 1), "c_new_1": (ROOT, "new", 1), "b_seq_8": (old, "seq", 8), "c_new_8": (ROOT, "new", 8)}
+        if parent:
+            configs["b_seq_this"] = (ROOT, "seq", 1)
+        kept = {k: [] for k in configs}
+        for rnd in range(args.rounds):
+            names = list(configs)
+            for name in (names if rnd % 2 == 0 else names[::-1]):     # alternating order
+                tree, form, n = configs[name]
+                kept[name].append(measure("full", size, tree, 0, form, n))
+                print(size, name, kept[name][-1], flush=True)
+        med = {k: statistics.median(v["ms"] for v in kept[k]) for k in configs}
+        rng = {k: max(v["ms"] for v in kept[k]) - min(v["ms"] for v in kept[k]) for k in configs}
+        row = dict(W=SIZES[size][0], H=SIZES[size][1], children=kept, median_ms=med, range_ms=rng, b_spread_ms=rng["b_seq"],
+                   b_over_a=med["b_seq"] / med["a_plain"], c1_over_a=med["c_new_1"] / med["a_plain"], c1_over_b=med["c_new_1"] / med["b_seq"],
+                   c8_over_b8=med["c_new_8"] / med["b_seq_8"], c8_ms_per_pair=med["c_new_8"] / 8, b8_ms_per_pair=med["b_seq_8"] / 8,
+                   c1_slower_than_b_by_more_than_spread=bool(med["c_new_1"] - med["b_seq"] > rng["b_seq"]))
+        result["sizes"][size] = row
+        print(json.dumps({k: v for k, v in row.items() if k != "children"}), flush=True)
+    out = args.out if args.out != ap.get_default("out") else os.path.join(ROOT, "profiles", "lr_full_bench.json")
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    json.dump(result, open(out, "w"), indent=1, sort_keys=True)
+    print(f"wrote {out}")
+
+
+def measure(kind, size, tree, checked, form="plain", n=1):
     cmd = [sys.executable, os.path.abspath(__file__), "--child", kind, "--size", size, "--tree", tree, "--checked", str(int(checked)),
-           "--reps", str(args.reps), "--warmup", str(args.warmup), "--burst", str(args.burst), "--tau", str(args.tau)]
+           "--reps", str(args.reps), "--warmup", str(args.warmup), "--burst", str(args.burst), "--tau", str(args.tau), "--form", form, "--n", str(n)]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=240)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("LRBENCH ")]
     if r.returncode != 0 or not lines:
@@ -151,4 +222,9 @@ def main():
 
 
 if __name__ == "__main__":
-    child() if args.child else main()
+    if args.child == "full":
+        full_child()
+    elif args.child:
+        child()
+    else:
+        full_main() if args.full else main()

@@ -69,6 +69,8 @@ EXPORTS = [
     "ugsm_submit_foveated_multi_checked", "ugsm_match_foveated_multi_checked",
     # the warped right image and the photometric residual of a match
     "ugsm_warp_planes", "ugsm_warp_right", "ugsm_warp_right_fovea", "ugsm_photometric_residual", "ugsm_photometric_residual_fovea",
+    # the checked full-mode call
+    "ugsm_submit_full_checked", "ugsm_match_full_checked", "ugsm_last_lr_marked_pair",
 ]
 # ... and what include/ugsm_dev.h adds (libugsm_dev.so only)
 DEV_EXPORTS = ["ugsm_stage_poly_probe", "ugsm_stage_div3_probe", "ugsm_stage_div_probe", "ugsm_stage_range_words", "ugsm_stage_iterate_rgb8", "ugsm_stage_level0_direct"]
@@ -280,6 +282,9 @@ def load(dev: bool = False):
     lib.ugsm_reconstruct_full_multi.argtypes = [vp, i, i, pp, i, i, ip, ip, vp]
     lib.ugsm_submit_foveated_multi_checked.argtypes = [vp, i, vp, vp, i, i, i, i, ip, ip, pp, C.c_float]
     lib.ugsm_match_foveated_multi_checked.argtypes = [vp, vp, vp, i, i, i, i, ip, ip, pp, pp, pp, C.c_float]
+    lib.ugsm_submit_full_checked.argtypes = [vp, i, i, pp, pp, i, i, i, pp, pp, C.c_float]
+    lib.ugsm_match_full_checked.argtypes = [vp, vp, vp, i, i, i, vp, vp, vp, vp, vp, vp, C.c_float]
+    lib.ugsm_last_lr_marked_pair.argtypes = [vp, i, i, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
     lib.ugsm_wait.argtypes = [vp, i]
     lib.ugsm_wait_all.argtypes = [vp]
     lib.ugsm_submit_pyramids.argtypes = [vp, i, vp, vp, i, i, i]
@@ -793,6 +798,34 @@ class Context:
     def submit_full_batch(self, slot: int, d_rgbL, d_rgbR, W: int, H: int, stride: int, d_out):
         n = len(d_rgbL)
         self.check(self.lib.ugsm_submit_full_batch(self._h, slot, n, self._ptrs(d_rgbL), self._ptrs(d_rgbR), W, H, stride, self._ptrs(d_out)))
+
+    def submit_full_checked(self, slot: int, d_rgbL, d_rgbR, W: int, H: int, stride: int, d_out, d_back, tau: float):
+        """Both directions of the pairs in one lockstep call (ugsm_submit_full_checked), each pair's two fields checked against each other at
+        threshold tau (> 0; the call's own, not the context's setting).  d_back: None, or one device pointer (or None) per pair for the right
+        camera's checked field.  last_lr_marked_pair(slot, k) answers for pair k."""
+        n = len(d_rgbL)
+        if len(d_rgbR) != n or len(d_out) != n or (d_back is not None and len(d_back) != n):
+            raise UgsmError(UGSM_ERR_BAD_ARG, "one entry per pair in every list")
+        self.check(self.lib.ugsm_submit_full_checked(self._h, slot, n, self._ptrs(d_rgbL), self._ptrs(d_rgbR), W, H, stride, self._ptrs(d_out),
+                                                     self._ptrs(d_back) if d_back is not None else None, tau))
+
+    def match_full_checked(self, L: np.ndarray, R: np.ndarray, tau: float, back: bool = True):
+        """Blocking, from any host memory (ugsm_match_full_checked): the checked (3, H, W) field of the left camera and, with `back`, that of
+        the right camera (else None)."""
+        W, H, stride = self.check_image(L)
+        if self.check_image(R) != (W, H, stride):
+            raise UgsmError(UGSM_ERR_SIZE_MISMATCH, "the two images differ in size or stride")
+        fwd = np.empty((3, H, W), np.float32)
+        bwd = np.empty((3, H, W), np.float32) if back else None
+        bp = [bwd[c].ctypes.data for c in range(3)] if back else [None] * 3
+        self.check(self.lib.ugsm_match_full_checked(self._h, L.ctypes.data, R.ctypes.data, W, H, stride, *[fwd[c].ctypes.data for c in range(3)], *bp, tau))
+        return fwd, bwd
+
+    def last_lr_marked_pair(self, slot: int = 0, pair: int = 0):
+        """(forward, backward) pixels the check of the last submit_full_checked / match_full_checked on `slot` marked for pair `pair`."""
+        f, b = C.c_longlong(), C.c_longlong()
+        self.check(self.lib.ugsm_last_lr_marked_pair(self._h, slot, pair, C.byref(f), C.byref(b)))
+        return int(f.value), int(b.value)
 
     def submit_foveated_batch(self, slot: int, d_rgbL, d_rgbR, W: int, H: int, stride: int, offsets, d_stack, d_pyrL=None, d_pyrR=None):
         n = len(d_rgbL)

@@ -102,6 +102,11 @@ void launch_lr_check(hipStream_t st, float *left3, const float *right3, int W, i
 // The stack form: the same rule on every level of the fovea stacks of ls.n pairs (LrStack, ugsm_launch.hpp), blockIdx.z = pair x F + level.
 // The two stacks of a pair have one layout, so a level's dx, dy and conf planes lie F, 2 F levels apart in either.  One count word per
 // (pair, level): whole numbers, so the order of the waves' additions never shows.
+// With F = 1 a "stack" is one full-frame field (3 planes of W x H), which is how a checked full-mode call (ugsm_submit_full_checked) checks BOTH
+// directions of its pairs in one launch: entry 2 b is pair b's left-to-right field against its right-to-left one, entry 2 b + 1 the same two
+// exchanged.  That is race-free: a thread reads dx and dy of its own field and of the other one -- planes no thread of the launch writes --
+// and writes only its own field's confidence plane, which no thread reads; so each check sees the other direction's UNCHECKED dx and dy
+// whatever order the workgroups run in, and no byte written through stack0 is read through back0 (the __restrict__ pair holds).
 __global__ __launch_bounds__(256) void k_lr_check(float *__restrict__ stack0, const float *__restrict__ back0, int fovW, int fovH, float tau,
                                                   unsigned long long *__restrict__ marked, LrStack ls)
 {

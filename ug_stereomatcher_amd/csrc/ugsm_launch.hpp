@@ -88,6 +88,8 @@ struct LrStack {
     long long fwd[kMaxBatch], back[kMaxBatch];
 };
 void launch_lr_check(hipStream_t st, float *stack0, const float *back0, int fovW, int fovH, float tau, unsigned long long *marked, const LrStack &ls);
+// (F = 1: a stack is one full-frame field.  A checked full-mode call, ugsm_submit_full_checked, checks both directions of its pairs so: entry
+// 2 b = pair b's left-to-right field against its right-to-left one, entry 2 b + 1 the two exchanged, both pointers relative to one base.)
 // X, Y, Z planes from the full-resolution (dx, dy) and the two 3x4 projection matrices
 void launch_triangulate(hipStream_t st, const float *dispx, const float *dispy, int W, int H, const double *P1, const double *P2, float *xyz);
 void launch_triangulate_fovea(hipStream_t st, const float *stackx, const float *stacky, int fovW, int fovH, int src_level, int left_margin,

@@ -446,6 +446,9 @@ struct Shape {
     static Shape windows_both_directions(int n, size_t field) { return {2 * n, n, true, field}; }
     // the coarse phase of the checked multi-window call: the one pair and its exchanged twin
     static Shape coarse_both_directions(size_t field) { return both_directions(1, field); }
+    // both directions of the slot's real pairs at full frame (ugsm_submit_full_checked): 2 nb entries, each at its own full-frame room -- twice
+    // what the slot holds for its pairs, so the caller has grown the level buffers
+    static Shape full_both_directions(const Slot &s) { return {2 * s.nb, s.nb, false, s.lvl_stride}; }
 };
 // the room of one fovea field (3 planes of fw x fh) in the level buffers, in the LR buffer and in hout: a multiple of 64 floats
 size_t fovea_field_room(int fw, int fh) { return (3 * (size_t)fw * fh + 63) & ~(size_t)63; }
@@ -728,7 +731,8 @@ int weighted_difference(ugsm_ctx *ctx, Slot &s, const float *newd3, const float 
 // A_pre (optional, single pairs only): A = G_clamp * L^2 of this level, already computed (on the slot's side stream; the caller has made
 // the main stream wait for it); otherwise it is computed here, into s.A.
 // in (kInPlanes, or kInRGB8: level 0 of a call with Slot::direct0): Lv / Rv are byte views of the pairs' images; the level runs k_cost_march
-// (level0_direct has seen to it) and any seed map has its origin at 0.
+// (level0_direct has seen to it) and any seed map has its origin at 0.  A shape of both directions may bring them too: a K-cost launch holds
+// the entries of one direction (cost_groups), so one R offset per entry serves it, and A = G * L^2 reads the L view alone.
 int run_level(ugsm_ctx *ctx, Slot &s, int si, const Shape &sh, const Img3 *Lv, const Img3 *Rv, int W, int H, int mi, int S, bool is_top, int m_from,
               int m_to, float *&cur, float *&other, float *dbg8, float *const *final_out = nullptr, const SeedMap *seed = nullptr,
               const float *A_pre = nullptr, int in = kInPlanes)
@@ -759,11 +763,11 @@ int run_level(ugsm_ctx *ctx, Slot &s, int si, const Shape &sh, const Img3 *Lv, c
     if (in != kInPlanes) {  // byte views: what level0_direct promised must hold here, and the seed-crop origins -- whose Batch fields carry the R offsets -- are 0
         bool origins0 = true;
         for (int b = 0; seed && b < sh.nb; b++) origins0 = origins0 && seed[b].cx == 0 && seed[b].cy == 0;
-        if (in != kInRGB8 || march4 || !march || early || sh.nb != sh.nreal || !origins0) {
+        if (in != kInRGB8 || march4 || !march || early || !origins0) {
             ctx->err = in != kInRGB8 ? "level 0 from the image: no kernel instance for this input form"
                        : !origins0   ? "level 0 from the image: a seed map with a crop origin (the rgb8 K-cost instance serves full mode only)"
-                                     : "level 0 from the image needs the level matched by k_cost_march (kernel-choice policy: march_min_pixels, k_cost_march4's range), "
-                                       "single-direction pairs and no early exit";
+                                     : "level 0 from the image needs the level matched by k_cost_march (kernel-choice policy: march_min_pixels, k_cost_march4's range) "
+                                       "and no early exit";
             return UGSM_ERR_STATE;
         }
     }
@@ -885,11 +889,14 @@ void side_views(const Slot &s, const Shape &sh, int side, int lev, Img3 *out)
 // one K-cost form with an 8-bit instance: the levels that large), rgb8 images (the other layouts keep the float level 0: eight more K-cost
 // bodies per layout for formats no measured workload uses), no early exit (it runs pair by pair through other buffers).  Everything
 // that hands the pyramids on -- ugsm_submit_pyramids, the foveated calls, the stage entry points -- stores level 0 as ever.
-bool level0_direct(const ugsm_ctx *ctx, const Slot &s)
+// entries: how many fields the call runs in lockstep (0: the slot's pairs; a checked full-mode call: two per pair) -- what a launch holds decides the kernel.
+bool level0_direct(const ugsm_ctx *ctx, const Slot &s, int entries = 0)
 {
     if (ctx->level0_float || ctx->cfg.kernel_path == 1 || ctx->cfg.early_exit_threshold > 0.0f || s.levels < 3) return false;
     if (ctx->hooks.input_format != kInRGB8) return false;
-    const int pairs = launch_pairs(ctx, Shape::pairs(s), s.W, s.H);
+    Shape sh = Shape::pairs(s);
+    if (entries > 0) sh.nb = entries;
+    const int pairs = launch_pairs(ctx, sh, s.W, s.H);
     return !use_march4(ctx, s.W, s.H, s.alone, pairs) && use_march(ctx, s.W, s.H, s.alone, pairs);
 }
 
@@ -923,8 +930,9 @@ int enqueue_side_A(ugsm_ctx *ctx, Slot &s, int a_from)
 // a_from: the levels a_from .. top get their A = G_clamp * L^2 precomputed on the side stream (full mode: 0; foveated: F-1, the
 // fine levels work on crops whose A is clamped at the crop's own border and is computed in line); < 0: none.
 // full: the call is a full-mode match and nothing else reads these pyramids -- level 0 is then read from the images where level0_direct allows.
+// entries: the fields the call's levels run in lockstep where that is not nb (level0_direct).
 int enqueue_pyramids(ugsm_ctx *ctx, Slot &s, int si, const uint8_t *const *d_rgbL, const uint8_t *const *d_rgbR, int nb, int W, int H, int stride, int a_from = -1,
-                     const FoveaWin *win = nullptr, bool full = false)
+                     const FoveaWin *win = nullptr, bool full = false, int entries = 0)
 {
     if (!d_rgbL || !d_rgbR || nb < 1 || nb > kMaxBatch) return UGSM_ERR_BAD_ARG;
     for (int b = 0; b < nb; b++)
@@ -938,7 +946,7 @@ int enqueue_pyramids(ugsm_ctx *ctx, Slot &s, int si, const uint8_t *const *d_rgb
     // statistics belong to one stream).  Otherwise fork: R's pyramid and the A planes on the side stream.
     const bool fork = side_stream_ok(ctx, s);
     s.a_from = -1;
-    const bool direct0 = full && !win && level0_direct(ctx, s);
+    const bool direct0 = full && !win && level0_direct(ctx, s, entries);
     s.direct0 = direct0;
     if (direct0) {
         for (int b = 0; b < nb; b++) {
@@ -1092,6 +1100,7 @@ int enqueue_full_lr(ugsm_ctx *ctx, Slot &s, int si, float *d_out)
 {
     s.lr_ran = false;
     s.lr_fov_pairs = 0;
+    s.lr_full_pairs = 0;
     UCHK(enqueue_full(ctx, s, si, d_out));
     const float tau = ctx->lr_tau;
     if (!lr_full_on(ctx)) return UGSM_OK;
@@ -1108,6 +1117,84 @@ int enqueue_full_lr(ugsm_ctx *ctx, Slot &s, int si, float *d_out)
     HIPCHK(ctx, hipMemcpyAsync(s.lr_host, cnt, sizeof *cnt, hipMemcpyDeviceToHost, s.st));
     HIPCHK(ctx, hipGetLastError());
     s.lr_ran = true;
+    return UGSM_OK;
+}
+
+// The room a checked full-mode call takes in the slot's LR buffer, in floats: one full field (Slot::lvl_stride: a multiple of 64 floats) for
+// every pair whose right-to-left field the caller does not take, the count words (one of 8 bytes per (pair, direction)) behind them.
+size_t lr_full_room(size_t lvl_stride, int kept, int n) { return (size_t)kept * lvl_stride + 4 * (size_t)n; }
+
+// ugsm_submit_full_checked: both directions of n full-mode pairs in lockstep, each pair's two fields checked against each other.
+//   - the pyramids of the n pairs once, as ugsm_submit_full_batch builds them (a lone pair: the right one on the side stream); level 0 stays
+//     unwritten where level0_direct allows, judged by the 2 n entries a launch of the call holds;
+//   - one descent over 2 n full-frame entries at a stride of one full field: entry n + b is pair b with the L and R views exchanged (pair_pyr;
+//     at level 0 of a direct call: the two images exchanged), under pair b's range word, which covers both of its pyramids.  Every kernel of a
+//     level takes the 2 n entries in one launch except K-cost, one launch per direction (cost_groups); more than kMaxBatch entries go through
+//     launches of equal size (group_pairs); levels above kBatchMaxPixels run entry by entry.  A is computed in line for both directions;
+//   - level 0's last smoothing launch writes the fields where they belong: d_out[b], and d_back[b] or the slot's LR buffer;
+//   - one launch of k_lr_check's stack form (F = 1: a stack of one full field) over the 2 n (pair, direction) checks with the call's own tau
+//     -- two launches from nine pairs on, an LrStack holds kMaxBatch checks -- and the counts back with one copy.
+// The caller has made the level buffers hold 2 n full fields and the LR buffer lr_full_room floats.
+int enqueue_full_checked(ugsm_ctx *ctx, Slot &s, int si, int n, const uint8_t *const *d_rgbL, const uint8_t *const *d_rgbR, int W, int H, int stride,
+                         float *const *d_out, float *const *d_back, float tau)
+{
+    s.lr_ran = false;
+    s.lr_fov_pairs = 0;
+    s.lr_full_pairs = 0;
+    UCHK(enqueue_pyramids(ctx, s, si, d_rgbL, d_rgbR, n, W, H, stride, -1, nullptr, true, 2 * n));
+    const Shape sh = Shape::full_both_directions(s);
+    int kept = 0;
+    float *outs[2 * kMaxBatch];
+    for (int b = 0; b < n; b++) {
+        outs[b] = d_out[b];
+        outs[n + b] = (d_back && d_back[b]) ? d_back[b] : s.lr + (size_t)kept++ * s.lvl_stride;
+    }
+    // (holds already, unless prepare_slot ran out of memory for the configured batch and fell back to this call's n pairs: it then freed what the
+    // caller had grown)
+    UCHK(ensure_level_bufs(ctx, s, sh.nb * sh.stride));
+    if (lr_full_room(s.lvl_stride, kept, n) > s.lr_cap || !s.lr_host) {
+        ctx->err = "the slot's buffers do not hold both directions' fields";
+        return UGSM_ERR_STATE;
+    }
+    if (s.range_known) HIPCHK(ctx, hipMemcpyAsync(s.range_bad + n, s.range_bad, sizeof(unsigned) * n, hipMemcpyDeviceToDevice, s.st));
+    auto views = [&](int i, Img3 *Lv, Img3 *Rv) -> int {
+        if (i == 0 && s.direct0) {  // level 0 was not stored: the images themselves, exchanged for the entries n .. 2 n - 1
+            for (int b = 0; b < n; b++) {
+                Lv[b] = Rv[n + b] = byte_view(s.img0L[b], s.img0_stride);
+                Rv[b] = Lv[n + b] = byte_view(s.img0R[b], s.img0_stride);
+            }
+            return kInRGB8;
+        }
+        side_views(s, sh, 0, i, Lv);
+        side_views(s, sh, 1, i, Rv);
+        return kInPlanes;
+    };
+    float *field;
+    UCHK(enqueue_descent(ctx, s, si, sh, 0, views, false, outs, field));
+    for (int v = 0; field && v < sh.nb; v++)
+        HIPCHK(ctx, hipMemcpyAsync(outs[v], field + v * sh.stride, sizeof(float) * 3 * (size_t)s.W * s.H, hipMemcpyDeviceToDevice, s.st));
+    unsigned long long *cnt = reinterpret_cast<unsigned long long *>(s.lr + (size_t)kept * s.lvl_stride);
+    HIPCHK(ctx, hipMemsetAsync(cnt, 0, sizeof *cnt * 2 * n, s.st));
+    // k_lr_check's stack form with F = 1: a "stack" is then one full field.  Check 2 b is pair b's left-to-right field against its right-to-left
+    // one, check 2 b + 1 the two exchanged; each reads dx and dy of both fields and writes its own field's confidence alone, so both directions
+    // in one launch are race-free and either sees the other's unchecked field.  An LrStack holds kMaxBatch checks: up to eight pairs are one
+    // launch, nine to sixteen two of equal size.
+    for_groups(2 * n, true, [&](Grp g) {
+        LrStack ls{};
+        ls.n = g.n;
+        ls.F = 1;
+        for (int j = 0; j < g.n; j++) {
+            const int b = (g.b0 + j) >> 1, dir = (g.b0 + j) & 1;
+            ls.fwd[j] = byte_diff(outs[dir ? n + b : b], outs[0]);
+            ls.back[j] = byte_diff(outs[dir ? b : n + b], outs[0]);
+        }
+        Timer t(ctx, &s, si, KC_MISC, (double)g.n * s.W * s.H);
+        launch_lr_check(s.st, outs[0], outs[0], s.W, s.H, tau, cnt + g.b0, ls);
+    });
+    HIPCHK(ctx, hipMemcpyAsync(s.lr_host + 1, cnt, sizeof *cnt * 2 * n, hipMemcpyDeviceToHost, s.st));
+    HIPCHK(ctx, hipGetLastError());
+    s.lr_ran = true;
+    s.lr_full_pairs = n;
     return UGSM_OK;
 }
 
@@ -2072,6 +2159,49 @@ int ugsm_submit_foveated_batch(ugsm_ctx *ctx, int slot, int n, const uint8_t *co
     return mark_done(ctx, *s);
 }
 
+// ---- both directions of n full-mode pairs -------------------------------------------------------------------------------------
+// What ugsm_submit_full_checked and ugsm_match_full_checked refuse before anything is enqueued, beyond their null pointers.  The threshold is
+// the call's own: the context's setting (ugsm_set_lr_check) is neither read nor changed.
+static int full_checked_check(ugsm_ctx *ctx, int n, int W, int H, int stride, float tau)
+{
+    if (n < 1 || n > UGSM_MAX_BATCH) return ctx_fail(ctx, UGSM_ERR_BAD_ARG, "the checked full-mode call takes 1 .. UGSM_MAX_BATCH pairs");
+    if (!(tau > 0.0f)) return ctx_fail(ctx, UGSM_ERR_BAD_ARG, "the checked full-mode call needs tau > 0");
+    // (ugsm_set_lr_check's rule: these contexts run every level pair by pair and have no batch dimension to carry the second direction in)
+    if (ctx->cfg.early_exit_threshold > 0.0f || ctx->cfg.kernel_path == 1)
+        return ctx_fail(ctx, UGSM_ERR_BAD_ARG, "the checked full-mode call: not with early_exit_threshold > 0 or kernel_path 1");
+    int w[UGSM_MAX_LEVELS], h[UGSM_MAX_LEVELS];
+    UCHK(level_dims(W, H, ctx->cfg.levels, w, h));
+    if (stride < input_row_bytes(ctx, W)) return UGSM_ERR_SIZE_MISMATCH;
+    return UGSM_OK;
+}
+// ... and its buffers: A, d0 and d1 for 2 n full fields, the LR buffer for the `kept` right-to-left fields the caller does not take and the
+// count words.  A buffer that cannot grow answers UGSM_ERR_NOMEM here, before anything is enqueued (ensure_level_bufs: all or nothing).
+static int full_checked_bufs(ugsm_ctx *ctx, Slot &s, int n, int kept, int W, int H)
+{
+    const size_t field = (3 * (size_t)W * H + 63) & ~(size_t)63;  // (Slot::lvl_stride, as prepare_slot sets it for this size)
+    UCHK(ensure_level_bufs(ctx, s, 2 * (size_t)n * field));
+    UCHK(grow(ctx, s.lr, s.lr_cap, lr_full_room(field, kept, n)));
+    return lr_host_ready(ctx, s);
+}
+
+int ugsm_submit_full_checked(ugsm_ctx *ctx, int slot, int n, const uint8_t *const *d_rgbL, const uint8_t *const *d_rgbR, int W, int H, int stride,
+                             float *const *d_out, float *const *d_back, float tau)
+{
+    Slot *s;
+    UCHK(get_slot(ctx, slot, &s));
+    if (!d_rgbL || !d_rgbR || !d_out) return UGSM_ERR_BAD_ARG;
+    UCHK(full_checked_check(ctx, n, W, H, stride, tau));
+    int kept = 0;
+    for (int b = 0; b < n; b++) {
+        if (!d_rgbL[b] || !d_rgbR[b] || !d_out[b]) return UGSM_ERR_BAD_ARG;
+        kept += !(d_back && d_back[b]);
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
+    UCHK(full_checked_bufs(ctx, *s, n, kept, W, H));
+    UCHK(enqueue_full_checked(ctx, *s, slot, n, d_rgbL, d_rgbR, W, H, stride, d_out, d_back, tau));
+    return mark_done(ctx, *s);
+}
+
 // ---- n windows on one pair ----------------------------------------------------------------------------------------------------
 // What ugsm_submit_foveated_multi and ugsm_match_foveated_multi refuse before anything is enqueued; the windows' field size on success.
 // tau: null = the plain call; else the checked call's threshold (ugsm_submit_foveated_multi_checked), which has refusals of its own and does
@@ -2233,6 +2363,40 @@ int ugsm_match_full(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int
                     float *dispV, float *dispC)
 {
     return drained(ctx, 0, match_full_on_slot(ctx, 0, rgbL, rgbR, W, H, stride, dispH, dispV, dispC, true));
+}
+
+// The checked service call on slot 0: upload, both directions in lockstep, the check, the forward planes (and the backward ones where asked
+// for) into caller memory of any kind.
+static int match_full_checked_on_slot0(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, float *dispH, float *dispV,
+                                       float *dispC, float *backH, float *backV, float *backC, float tau)
+{
+    Slot *s;
+    UCHK(get_slot(ctx, 0, &s));
+    if (!rgbL || !rgbR || !dispH || !dispV || !dispC) return UGSM_ERR_BAD_ARG;
+    const bool back = backH || backV || backC;
+    if (back && !(backH && backV && backC)) return ctx_fail(ctx, UGSM_ERR_BAD_ARG, "backH, backV and backC: all three or none");
+    UCHK(full_checked_check(ctx, 1, W, H, stride, tau));
+    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
+    UCHK(full_checked_bufs(ctx, *s, 1, back ? 0 : 1, W, H));
+    const size_t n = (size_t)W * H, room = (3 * n + 63) & ~(size_t)63;
+    UCHK(grow(ctx, s->hout, s->hout_cap, (back ? 2 : 1) * room));
+    UCHK(stage_in(ctx, *s, rgbL, rgbR, W, H, stride));
+    const uint8_t *const dL = s->rgbL, *const dR = s->rgbR;
+    float *const d_fwd = s->hout, *const d_bwd = back ? s->hout + room : nullptr;
+    UCHK(enqueue_full_checked(ctx, *s, 0, 1, &dL, &dR, W, H, stride, &d_fwd, back ? &d_bwd : nullptr, tau));
+    float *const dst[3] = {dispH, dispV, dispC}, *const bdst[3] = {backH, backV, backC};
+    prefault_planes(ctx, dst, n);
+    if (back) prefault_planes(ctx, bdst, n);
+    UCHK(copy_out_planes(ctx, *s, d_fwd, n, dst));
+    if (back) UCHK(copy_out_planes(ctx, *s, d_bwd, n, bdst));
+    s->forked = false;  // (enqueued whole, as mark_done)
+    return ugsm_wait(ctx, 0);
+}
+
+int ugsm_match_full_checked(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, float *dispH, float *dispV,
+                            float *dispC, float *backH, float *backV, float *backC, float tau)
+{
+    return drained(ctx, 0, match_full_checked_on_slot0(ctx, rgbL, rgbR, W, H, stride, dispH, dispV, dispC, backH, backV, backC, tau));
 }
 
 int ugsm_submit_full_host(ugsm_ctx *ctx, int slot, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, float *dispH,
@@ -2673,7 +2837,19 @@ long long ugsm_last_lr_marked(ugsm_ctx *ctx, int slot)
         for (int k = 0; k < s->lr_fov_F; k++) sum += (long long)s->lr_host[1 + (size_t)(s->lr_fov_pairs - 1) * s->lr_fov_F + k];
         return sum;
     }
+    if (s->lr_ran && s->lr_host && s->lr_full_pairs > 0) return (long long)s->lr_host[1 + 2 * (size_t)(s->lr_full_pairs - 1)];  // ugsm_submit_full_checked: the last pair, forward
     return (s->lr_ran && s->lr_host) ? (long long)*s->lr_host : -1;
+}
+
+int ugsm_last_lr_marked_pair(ugsm_ctx *ctx, int slot, int pair, long long *fwd, long long *back)
+{
+    Slot *s;
+    UCHK(get_slot(ctx, slot, &s, false));  // (reads host state only: the slot does not become busy)
+    if (!s->lr_ran || s->lr_full_pairs < 1 || !s->lr_host) return ctx_fail(ctx, UGSM_ERR_STATE, "the last call on the slot was not ugsm_submit_full_checked");
+    if (pair < 0 || pair >= s->lr_full_pairs) return UGSM_ERR_BAD_ARG;
+    if (fwd) *fwd = (long long)s->lr_host[1 + 2 * (size_t)pair];
+    if (back) *back = (long long)s->lr_host[2 + 2 * (size_t)pair];
+    return UGSM_OK;
 }
 
 int ugsm_last_lr_marked_levels(ugsm_ctx *ctx, int slot, int pair, long long *per_level)

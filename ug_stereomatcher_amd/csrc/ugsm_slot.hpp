@@ -108,6 +108,7 @@ struct Slot {
     size_t lr_cap = 0;
     unsigned long long *lr_host = nullptr;  // page-locked copies: word 0 the full-mode counter, then one word per (pair, level) of a checked foveated call
     bool lr_ran = false;
+    int lr_full_pairs = 0;  // read with lr_ran: the last call was ugsm_submit_full_checked on this many pairs, word 1 + 2 b + direction of lr_host pair b's count (0: word 0)
     int lr_fov_pairs = 0, lr_fov_F = 0;  // the last call on the slot ran the foveated check on this many pairs of this many levels (0: it did not)
     float *Apyr = nullptr;   // A of level i at Apyr + off[i] (same layout as the pyramids)
     size_t apyr_cap = 0;

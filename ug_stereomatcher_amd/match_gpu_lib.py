@@ -91,12 +91,18 @@ class MatchGPULib:
         return 0
 
     # -- match, MatchGPULib.cpp:303-403 --
-    def match(self, cv_ptrL, cv_ptrR, fov: int = 0) -> np.ndarray:
-        """Returns finDisp: float32 (3, rows, cols) = horizontal, vertical disparity and confidence."""
+    def match(self, cv_ptrL, cv_ptrR, fov: int = 0, tau=None):
+        """Returns finDisp: float32 (3, rows, cols) = horizontal, vertical disparity and confidence.
+        tau (> 0, fov == 0; not in the reference): the LR check for this call alone, both directions in one lockstep call
+        (ugsm_match_full_checked) -- returns (finDisp, backDisp): the checked fields of the left and of the right camera."""
         L, R = _as_rgb8(cv_ptrL), _as_rgb8(cv_ptrR)
         if L.shape != R.shape or L.strides[0] != R.strides[0]:
             raise UgsmError(_lib.UGSM_ERR_SIZE_MISMATCH, "left/right images differ in size")
         self.foveatedmatching = fov
+        if tau is not None:
+            if fov != 0:
+                raise UgsmError(_lib.UGSM_ERR_BAD_ARG, "match(.., tau) is the full-mode call: fov must be 0")
+            return self._ctx.match_full_checked(L, R, tau)
         rows, cols = L.shape[:2]
         out = np.empty((3, rows, cols), np.float32)
         c = self._ctx
