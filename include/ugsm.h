@@ -40,7 +40,8 @@ extern "C" {
                                ugsm_fovea_multi_cloud_points, ugsm_point_cloud_fovea_multi; the warped right image and the photometric residual of a
                                match -- ugsm_warp_planes, ugsm_warp_right, ugsm_warp_right_fovea, ugsm_photometric_residual,
                                ugsm_photometric_residual_fovea; the checked full-mode call -- ugsm_submit_full_checked, ugsm_match_full_checked,
-                               ugsm_last_lr_marked_pair
+                               ugsm_last_lr_marked_pair; the seeded full-mode call -- ugsm_submit_full_seeded, ugsm_match_full_seeded,
+                               ugsm_stage_restrict, ugsm_seeded_pixel_iterations
                                6: the kernel choices follow what is in flight, not ugsm_config.slots: ugsm_plan_level takes `alone`, ugsm_plan_level_in_frame
                                is gone, ugsm_level_plan.latency_policy is .alone; ugsm_enqueue_* returns UGSM_OK once the pair is accepted (a failed
                                CALL is reported through ugsm_completion.status only); the fovea shard carries a status word (a rank that fails still
@@ -162,6 +163,8 @@ int ugsm_threshold_schedule(int mi, float *out);
 int ugsm_fovea_dims(int W, int H, int levels, int fovea_levels, int *fovW, int *fovH);
 /* Sum over levels of iterations x pixels; fovea_levels==0 => full-resolution mode */
 long long ugsm_pixel_iterations(int W, int H, int levels, int fovea_levels);
+/* The same for a seeded full-mode call (ugsm_submit_full_seeded): the levels start_level .. 0 only.  -1 for a size or a level that does not exist. */
+long long ugsm_seeded_pixel_iterations(int W, int H, int levels, int start_level);
 
 /* Which kernels a W x H level runs under `cfg` (NULL = defaults), for maintainers and the host tests; results never depend on it.
  * ONE thing besides the level's size decides: whether the call has the chip to itself (`alone` != 0) or shares it with other calls.
@@ -351,6 +354,40 @@ int ugsm_submit_full_checked(ugsm_ctx *ctx, int slot, int n, const uint8_t *cons
  * or none (NULL); anything else is UGSM_ERR_BAD_ARG. */
 int ugsm_match_full_checked(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride,
                             float *dispH, float *dispV, float *dispC, float *backH, float *backV, float *backC, float tau);
+/* The SEEDED full-mode call: n pairs (1 <= n <= UGSM_MAX_BATCH, all W x H) matched from level start_level downwards, each from a prior field of
+ * its own instead of from the zero seed at the top level -- for a host that matched the previous frame and so holds a field better than
+ * anything the coarse levels can produce (a tracker, a video pipeline).  The reference has nothing like it: the build's own definition, as the
+ * LR check is.
+ *   d_rgbL, d_rgbR, d_out  HOST arrays of n DEVICE pointers, buffers laid out as for ugsm_submit_full_batch.
+ *   d_prior                the same for the priors: full-resolution fields (3 planes of W x H: dx, dy, conf), e.g. an earlier call's d_out.
+ *   start_level            0 .. levels - 1: the first level that is matched.
+ * The contract, bit for bit: d_out[k] is the field reached by restricting d_prior[k] to level start_level, running matchlevel on the levels
+ * start_level .. 0 with the usual iteration and smoothing counts and subsampleDisp between them, and never taking the top level's
+ * first-iteration exception: level start_level's first iteration blends the confidence like any other, because a prior has one.
+ * The restriction (ugsm_stage_restrict runs it alone) reads the prior at the sites the image pyramid samples level s's pixels from.  With
+ * k = s / 2: for an even s column x reads column ((x + 1) << k) - 1 -- k steps of the pyramid's sf = 2.0f sampling tex_index((c + .5f) * 2) --;
+ * for an odd s first c1 = ((x + 1) << k) - 1, a level-1 column, then tex_index((c1 + 0.5f) * (float)1.41421356, W), the pyramid's
+ * level-0 -> level-1 sampling; rows likewise.  dx and dy of an odd level become q = (float)((double)v / 1.41421356), the partner of
+ * subsampleDisp's SCALE * v, then q * 2^-k in binary32; of an even level v * 2^-k; the confidence is copied; s = 0 is a copy.
+ * What runs: the pyramid kernels build the levels 0 .. max(start_level, 2) only; one restriction launch fills level start_level's fields where
+ * the zero seed is otherwise set; the levels above run nothing; from level start_level downwards every launch is the full-mode call's -- the n
+ * pairs in lockstep exactly as ugsm_submit_full_batch groups them, level 0 from the images where it does so.  Any input format, captured at
+ * the call.  d_prior[k] == d_out[k] is allowed (the restriction reads before level 0 writes, on the same stream), and a prior that is the
+ * d_out of the call enqueued just before on the same slot needs no wait in between.
+ * NOT the cold call: a seeded call from the top level with a zero prior differs from ugsm_submit_full because of the blend.  A cold start from
+ * level s is a context with levels = s + 1.
+ * Status, all before anything is enqueued: null arrays or null entries, n outside 1 .. UGSM_MAX_BATCH, start_level outside 0 .. levels - 1,
+ * contexts with early_exit_threshold > 0: UGSM_ERR_BAD_ARG; UGSM_LR_FULL in force (ugsm_set_lr_check) or pairs outstanding in the queue:
+ * UGSM_ERR_STATE; the size errors of ugsm_submit_full as there.  kernel_path 1 (libugsm_dev.so) runs the pairs one after the other, as it does
+ * for ugsm_submit_full_batch.  What it saves, measured: DESIGN.md section 8.
+ * NOT built: a queue form (ugsm_enqueue_*); the page-locked _host kind; a seeded checked or foveated call.
+ * Asynchronous on `slot`. */
+int ugsm_submit_full_seeded(ugsm_ctx *ctx, int slot, int n, const uint8_t *const *d_rgbL, const uint8_t *const *d_rgbR,
+                            int W, int H, int stride, const float *const *d_prior, int start_level, float *const *d_out);
+/* Blocking, one pair on slot 0, any host memory in and out, as ugsm_match_full; the prior: three planes of W x H, not the result planes. */
+int ugsm_match_full_seeded(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride,
+                           const float *priorH, const float *priorV, const float *priorC, int start_level,
+                           float *dispH, float *dispV, float *dispC);
 /* ---- several fovea windows on ONE pair ------------------------------------------------------------------------------------------------
  *
  * A host that looks at n places of one frame (1 <= n <= UGSM_MAX_BATCH) needs the pyramids and the coarse phase -- levels top .. F-1, which
@@ -883,6 +920,9 @@ int ugsm_stage_iterate(ugsm_ctx *ctx, const float *d_L3, const float *d_R3, floa
 /* subsampleDisp / foveatedsubsampleDisp, MatchGPULib.cpp:1526-1655 */
 int ugsm_stage_seed(ugsm_ctx *ctx, const float *d_src3, int W, int H, float *d_dst3, int W2, int H2,
                     int Wup, int Hup, int crop_x, int crop_y);
+/* The restriction of the seeded call (ugsm_submit_full_seeded) alone: level `level`'s starting field d_dst3 (3 planes of w x h, the level's
+ * size by ugsm_level_dims with the context's levels) from the full-resolution field d_src3 (3 planes of W x H).  Not in place. */
+int ugsm_stage_restrict(ugsm_ctx *ctx, const float *d_src3, int W, int H, int level, float *d_dst3);
 /* S smoothing passes (+ box if do_box), MatchGPULib.cpp:2257-2412, in place */
 int ugsm_stage_smooth(ugsm_ctx *ctx, float *d_d3, int W, int H, int passes, int do_box);
 

@@ -148,6 +148,21 @@ public:
         return fin;
     }
 
+    // (not in the reference) match(L, R, 0) started at level start_level from `prior` -- a finDisp[3][rows*cols] of the same size, the previous
+    // frame's say -- instead of from the zero seed at the top level (ugsm_match_full_seeded).  Returns a fresh finDisp; the prior stays the caller's.
+    template <class ImgPtr>
+    float **matchSeeded(ImgPtr L, ImgPtr R, float *const *prior, int start_level)
+    {
+        foveatedmatching = 0;
+        const int W = L->image.cols, H = L->image.rows;
+        if (!prior || R->image.cols != W || R->image.rows != H) return nullptr;
+        float **fin = alloc_planes(3, (size_t)W * H);
+        const int st = ugsm_match_full_seeded(ctx_, L->image.data, R->image.data, W, H, (int)L->image.step, prior[0], prior[1], prior[2], start_level,
+                                              fin[0], fin[1], fin[2]);
+        if (st != UGSM_OK) return fail(fin, 3, st);
+        return fin;
+    }
+
     // MatchGPULib.cpp:429-531.  Returns disparity[level][3][fovH*fovW] for level < foveatelevel.
     template <class ImgPtr>
     float ***matchStack(ImgPtr L, ImgPtr R) { return stack(L, R, nullptr, nullptr); }

@@ -22,6 +22,10 @@
 //
 // Nor this: the parameter `lr_check_tau` (default 0 = off).  With tau > 0 the blocking full-mode paths (topic and service) run the LR check for the call:
 // both directions in one lockstep call (ugsm_match_full_checked), the confidence plane zeroed where the match does not point back within tau pixels.
+//
+// Nor this: the parameter `seed_level` (default -1 = off).  With a level s >= 0 the blocking full-mode topic path keeps every frame's result and starts the
+// next frame of the same size at level s from it (the shim's matchSeeded: ugsm_match_full_seeded) instead of from the zero seed at the top level; the
+// first frame, a frame of another size and a frame after a failed call are matched cold.
 #include <cv_bridge/cv_bridge.h>
 #include <image_transport/image_transport.h>
 #include <image_transport/subscriber_filter.h>
@@ -115,6 +119,8 @@ private:
     struct InFlight { std_msgs::Header hl, hr; };
     std::map<uint64_t, InFlight> in_flight_;  // headers of the frames whose results have not been published yet
     uint64_t next_tag_ = 0;
+    float **last_ = nullptr;  // seed_level >= 0: the last full-mode result of the topic path (last_w_ x last_h_), the next frame's prior
+    int last_w_ = 0, last_h_ = 0;
 
     int foveated()
     {  // re-read on every call, default 0 with a warning (reference :96-102)
@@ -128,6 +134,17 @@ private:
         double tau = 0.0;
         ros::param::get("~lr_check_tau", tau);
         return (float)tau;
+    }
+    int seed_level()
+    {  // (not in the reference) re-read on every call like `foveated`; >= 0: the level a frame is started at from the last frame's result
+        int s = -1;
+        nh_.getParam("seed_level", s);
+        return s;
+    }
+    void drop_last()
+    {
+        if (last_) { for (int c = 0; c < 3; c++) free(last_[c]); free(last_); }
+        last_ = nullptr;
     }
     static sensor_msgs::Image plane_msg(float *p, int rows, int cols, const std_msgs::Header &h)
     {
@@ -334,8 +351,12 @@ private:
             for (int k = 0; k < 14; k++) { for (int c = 0; c < 3; c++) { free(lf[k][c]); free(rf[k][c]); } free(lf[k]); free(rf[k]); }
             free(lf); free(rf);
         } else {
-            float **fin = mgpu_->match(L, R, fov, lr_check_tau());  // (tau <= 0: the plain match)
+            const int sl = seed_level();
+            const bool seeded = sl >= 0 && last_ && last_w_ == L->image.cols && last_h_ == L->image.rows;
+            float **fin = seeded ? mgpu_->matchSeeded(L, R, last_, sl)
+                                 : mgpu_->match(L, R, fov, lr_check_tau());  // (tau <= 0: the plain match)
             ROS_INFO("Non Foveated Disparity took %f Seconds", (ros::WallTime::now() - t0).toSec());
+            drop_last();  // (a failed call too: the next frame is matched cold)
             if (!fin) return;
             const char *topics[3] = {"output_disparityH", "output_disparityV", "output_disparityC"};
             for (int i = 0; i < 3; i++) {
@@ -343,8 +364,14 @@ private:
                 d.header = (i == 1) ? R->header : L->header;
                 d.image = plane_msg(fin[i], L->image.rows, L->image.cols, d.header);
                 disp_pub_[topics[i]].publish(d);
-                free(fin[i]);
             }
+            if (sl >= 0) {  // the next frame's prior
+                last_ = fin;
+                last_w_ = L->image.cols;
+                last_h_ = L->image.rows;
+                return;
+            }
+            for (int i = 0; i < 3; i++) free(fin[i]);
             free(fin);
         }
     }

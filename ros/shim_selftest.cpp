@@ -144,6 +144,21 @@ int main(int argc, char **argv)
             for (float **p : {chk, bk, seq, seqb}) { for (int c = 0; c < 3; c++) free(p[c]); free(p); }
             if (bad) return 20;
         }
+        // matchSeeded(L, R, prior, 5): the match started at level 5 from the cold result -- the same field every time, and not the cold one
+        {
+            float **cold = m.match(L, R, 0);
+            if (!cold) return 21;
+            float **s1 = m.matchSeeded(L, R, cold, 5), **s2 = m.matchSeeded(L, R, cold, 5);
+            if (!s1 || !s2 || m.matchSeeded(L, R, cold, 14)) return 22;  // (level 14 does not exist: refused)
+            size_t differ = 0, moved = 0;
+            for (int c = 0; c < 3; c++) {
+                differ += std::memcmp(s1[c], s2[c], sizeof(float) * W * H) != 0;
+                moved += std::memcmp(s1[c], cold[c], sizeof(float) * W * H) != 0;
+            }
+            std::printf("matchSeeded (level 5 from the cold result) twice: %s; planes that differ from the cold match: %zu\n", differ ? "DIFFER" : "identical", moved);
+            for (float **p : {cold, s1, s2}) { for (int c = 0; c < 3; c++) free(p[c]); free(p); }
+            if (differ) return 23;
+        }
         for (int k = 0; k < m.getFoveateLevel(); k++) { for (int i = 0; i < 3; i++) free(st[k][i]); free(st[k]); }
         free(st);
     } catch (const std::exception &e) {

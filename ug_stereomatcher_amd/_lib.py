@@ -71,6 +71,8 @@ EXPORTS = [
     "ugsm_warp_planes", "ugsm_warp_right", "ugsm_warp_right_fovea", "ugsm_photometric_residual", "ugsm_photometric_residual_fovea",
     # the checked full-mode call
     "ugsm_submit_full_checked", "ugsm_match_full_checked", "ugsm_last_lr_marked_pair",
+    # the seeded full-mode call
+    "ugsm_submit_full_seeded", "ugsm_match_full_seeded", "ugsm_stage_restrict", "ugsm_seeded_pixel_iterations",
 ]
 # ... and what include/ugsm_dev.h adds (libugsm_dev.so only)
 DEV_EXPORTS = ["ugsm_stage_poly_probe", "ugsm_stage_div3_probe", "ugsm_stage_div_probe", "ugsm_stage_range_words", "ugsm_stage_iterate_rgb8", "ugsm_stage_level0_direct"]
@@ -285,6 +287,11 @@ def load(dev: bool = False):
     lib.ugsm_submit_full_checked.argtypes = [vp, i, i, pp, pp, i, i, i, pp, pp, C.c_float]
     lib.ugsm_match_full_checked.argtypes = [vp, vp, vp, i, i, i, vp, vp, vp, vp, vp, vp, C.c_float]
     lib.ugsm_last_lr_marked_pair.argtypes = [vp, i, i, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
+    lib.ugsm_submit_full_seeded.argtypes = [vp, i, i, pp, pp, i, i, i, pp, i, pp]
+    lib.ugsm_match_full_seeded.argtypes = [vp, vp, vp, i, i, i, vp, vp, vp, i, vp, vp, vp]
+    lib.ugsm_stage_restrict.argtypes = [vp, vp, i, i, i, vp]
+    lib.ugsm_seeded_pixel_iterations.argtypes = [i, i, i, i]
+    lib.ugsm_seeded_pixel_iterations.restype = C.c_longlong
     lib.ugsm_wait.argtypes = [vp, i]
     lib.ugsm_wait_all.argtypes = [vp]
     lib.ugsm_submit_pyramids.argtypes = [vp, i, vp, vp, i, i, i]
@@ -427,6 +434,11 @@ def fovea_dims(W: int, H: int, levels: int = 14, fovea_levels: int = 7):
 
 def pixel_iterations(W: int, H: int, levels: int = 14, fovea_levels: int = 0) -> int:
     return int(load().ugsm_pixel_iterations(W, H, levels, fovea_levels))
+
+
+def seeded_pixel_iterations(W: int, H: int, levels: int = 14, start_level: int = 0) -> int:
+    """Sum of iterations x pixels over the levels start_level .. 0: what a seeded full-mode call runs (-1: no such size or level)."""
+    return int(load().ugsm_seeded_pixel_iterations(W, H, levels, start_level))
 
 
 def cloud_params(sampling: int = 1, format: int = UGSM_CLOUD_PCL32, compact: bool = False, min_conf: float | None = None,
@@ -826,6 +838,32 @@ class Context:
         f, b = C.c_longlong(), C.c_longlong()
         self.check(self.lib.ugsm_last_lr_marked_pair(self._h, slot, pair, C.byref(f), C.byref(b)))
         return int(f.value), int(b.value)
+
+    def submit_full_seeded(self, slot: int, d_rgbL, d_rgbR, W: int, H: int, stride: int, d_prior, start_level: int, d_out):
+        """The pairs matched from level start_level downwards, each from its full-resolution prior field (ugsm_submit_full_seeded): lists of
+        device pointers, one entry per pair; d_prior[k] may be d_out[k]."""
+        n = len(d_rgbL)
+        if len(d_rgbR) != n or len(d_prior) != n or len(d_out) != n:
+            raise UgsmError(UGSM_ERR_BAD_ARG, "one entry per pair in every list")
+        self.check(self.lib.ugsm_submit_full_seeded(self._h, slot, n, self._ptrs(d_rgbL), self._ptrs(d_rgbR), W, H, stride, self._ptrs(d_prior),
+                                                    int(start_level), self._ptrs(d_out)))
+
+    def match_full_seeded(self, L: np.ndarray, R: np.ndarray, prior: np.ndarray, start_level: int) -> np.ndarray:
+        """Blocking, from any host memory (ugsm_match_full_seeded): the (3, H, W) field reached from level start_level of `prior` (3, H, W)."""
+        W, H, stride = self.check_image(L)
+        if self.check_image(R) != (W, H, stride):
+            raise UgsmError(UGSM_ERR_SIZE_MISMATCH, "the two images differ in size or stride")
+        if tuple(prior.shape) != (3, H, W):
+            raise UgsmError(UGSM_ERR_SIZE_MISMATCH, "the prior is a (3, H, W) field of the images' size")
+        pr = np.ascontiguousarray(prior, np.float32)
+        out = np.empty((3, H, W), np.float32)
+        self.check(self.lib.ugsm_match_full_seeded(self._h, L.ctypes.data, R.ctypes.data, W, H, stride, *[pr[c].ctypes.data for c in range(3)],
+                                                   int(start_level), *[out[c].ctypes.data for c in range(3)]))
+        return out
+
+    def stage_restrict(self, d_src3: int, W: int, H: int, level: int, d_dst3: int):
+        """The seeded call's restriction alone (ugsm_stage_restrict): level `level`'s starting field from a full-resolution one; waits."""
+        self.check(self.lib.ugsm_stage_restrict(self._h, d_src3, W, H, int(level), d_dst3))
 
     def submit_foveated_batch(self, slot: int, d_rgbL, d_rgbR, W: int, H: int, stride: int, offsets, d_stack, d_pyrL=None, d_pyrR=None):
         n = len(d_rgbL)

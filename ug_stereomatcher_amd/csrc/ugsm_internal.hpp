@@ -76,6 +76,12 @@ void ctx_host_copy(ugsm_ctx *ctx, void *dst, const void *src, size_t bytes);
 bool host_pinned(const void *p);
 // UGSM_DEV=1 is set: the process asked for the development switches (UGSM_* environment variables); nothing reads one without it
 bool dev_env();
+// The seeded full-mode call behind its entry points (ugsm_seeded.cpp, which has refused what the call refuses): n pairs enqueued on `slot`
+// from level start_level of their priors; and the blocking call on slot 0, its three prior and result planes in host memory of any kind.
+int seeded_submit(ugsm_ctx *ctx, int slot, int n, const uint8_t *const *d_rgbL, const uint8_t *const *d_rgbR, int W, int H, int stride,
+                  const float *const *d_prior, int start_level, float *const *d_out);
+int seeded_match(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, const float *const prior[3], int start_level,
+                 float *const disp[3]);
 // the stagger of the queue's first round after idle and the size of every later call (ugsm.h, "the queue")
 int queue_target(int batch, int slots, long long calls_since_idle);
 

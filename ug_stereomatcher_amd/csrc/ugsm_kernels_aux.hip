@@ -1,6 +1,7 @@
 // ugsm_kernels_aux.hip -- the plain per-pixel kernels around the matcher proper.
 //
-// k_seed (a level's starting field where the next level's K-cost does not seed itself), k_copy_view (the fovea / pyramid stacks),
+// k_seed (a level's starting field where the next level's K-cost does not seed itself; its restriction form: a level's starting field from a
+// full-resolution prior, the seeded full-mode call), k_copy_view (the fovea / pyramid stacks),
 // k_rgb_planes (level 0 of a pyramid of fewer than three levels: BASELINE configs[0]; its window form: level 0 inside the windows of a
 // multi-window foveated call), k_lr_check (the opt-in LR-consistency check),
 // k_triangulate[_fovea] (the X, Y, Z planes and, as other forms of the same kernels, the coloured point cloud),
@@ -39,6 +40,43 @@ __global__ void k_seed(const float *__restrict__ src3, int Ws, int Hs, float *__
     dst3[(size_t)plane * Wd * Hd + (size_t)iy * Wd + ix] = (float)(UGSM_SCALE * (double)v);
 }
 
+// The restriction form (k_restrict in the statistics; ugsm_submit_full_seeded -- no reference counterpart): level s's
+// starting field (rm.w x rm.h) from a full-resolution field (rm.W x rm.H, planes dx, dy, conf), read at the sites the image pyramid itself
+// samples level s's pixels from.  k = s / 2.  Even s: k steps of the pyramid's sf = 2.0f sampling, tex_index((c + .5f) * 2) -- column x reads
+// column ((x + 1) << k) - 1 of level 0; the closed form carries the first k - 1 steps, the last one keeps its tex_index.  Odd s: the same k
+// steps down to level 1, c1 = ((x + 1) << k) - 1, then level 1's own site in level 0, tex_index((c1 + .5f) * (float)SCALE).  Rows likewise:
+// the source row is one scalar per workgroup.
+// Values: dx and dy of an odd level are q = f32((double)v / SCALE), the partner of k_seed's f32(SCALE * (double)v), then q * 2^-k; of an even
+// level v * 2^-k (rm.scale = 2^-k, exact in binary32); the confidence is copied.  s = 0: a copy.
+// (batched: blockIdx.z = 3 x pair + plane; pair b's full-resolution field at src3 + bt.in[b] bytes)
+__device__ __forceinline__ int restrict_site(const int c, const int k, const int odd, const int n)
+{
+    if (odd) return tex_index(((float)(((c + 1) << k) - 1) + 0.5f) * (float)UGSM_SCALE, n);
+    if (k == 0) return c < n ? c : n - 1;
+    return tex_index(((float)(((c + 1) << (k - 1)) - 1) + 0.5f) * 2.0f, n);
+}
+__global__ void k_seed(const float *__restrict__ src3, RestrictMap rm, float *__restrict__ dst3, Batch bt)
+{
+    const int ix = blockIdx.x * blockDim.x + threadIdx.x;
+    const int iy = blockIdx.y;
+    int plane = blockIdx.z;
+    if (bt.n > 1) {
+        const int b = plane / 3;
+        plane -= 3 * b;
+        src3 = shifted(src3, bt.in[b]);
+        dst3 = shifted(dst3, bt.out[b]);
+    }
+    if (ix >= rm.w) return;
+    const int sy = restrict_site(iy, rm.k, rm.odd, rm.H);
+    const int sx = restrict_site(ix, rm.k, rm.odd, rm.W);
+    float v = src3[(size_t)plane * rm.W * rm.H + (size_t)sy * rm.W + sx];
+    if (plane < 2) {
+        if (rm.odd) v = (float)((double)v / UGSM_SCALE);
+        if (rm.k) v = v * rm.scale;
+    }
+    dst3[(size_t)plane * rm.w * rm.h + (size_t)iy * rm.w + ix] = v;
+}
+
 // fovea-stack / pyramid-stack packing: plain 2-D crop copy of 3 planes
 // (batched: blockIdx.z = 3 x pair + plane)
 __global__ void k_copy_view(Img3 src, int W, int H, float *__restrict__ dst, size_t dst_plane, int dst_pitch, Batch bt)
@@ -62,6 +100,15 @@ void launch_seed(hipStream_t st, const float *src3, int Ws, int Hs, float *dst3,
     one.n = 1;
     const Batch &B = bt ? *bt : one;
     UGSM_LAUNCH(k_seed, grid2(Wd, Hd, 3 * (B.n > 1 ? B.n : 1)), dim3(256), 0, st, src3, Ws, Hs, dst3, Wd, Hd, cx, cy, B);
+}
+void launch_restrict(hipStream_t st, const float *src3, int W, int H, int level, float *dst3, int w, int h, const Batch *bt)
+{
+    Batch one{};
+    one.n = 1;
+    const Batch &B = bt ? *bt : one;
+    const int k = level / 2;
+    const RestrictMap rm{W, H, w, h, k, level & 1, 1.0f / (float)(1 << k)};
+    UGSM_LAUNCH(k_seed, grid2(w, h, 3 * (B.n > 1 ? B.n : 1)), dim3(256), 0, st, src3, rm, dst3, B);
 }
 void launch_copy_view(hipStream_t st, Img3 src, int W, int H, float *dst, size_t dst_plane, int dst_pitch, const Batch *bt)
 {

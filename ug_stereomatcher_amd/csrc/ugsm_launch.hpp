@@ -64,6 +64,13 @@ struct Batch {
 
 // ---- plain per-pixel kernels (ugsm_kernels_aux.hip) ---------------------------------------
 void launch_seed(hipStream_t st, const float *src3, int Ws, int Hs, float *dst3, int Wd, int Hd, int cx, int cy, const Batch *bt = nullptr);
+// The restriction form of k_seed (ugsm_submit_full_seeded): level `level`'s starting field dst3 (w x h, the level's size) from the
+// full-resolution field src3 (W x H).  Batched: pair b reads src3 + bt->in[b] bytes and writes dst3 + bt->out[b] bytes.
+struct RestrictMap {
+    int W, H, w, h, k, odd;  // k = level / 2, odd = level & 1
+    float scale;             // 2^-k
+};
+void launch_restrict(hipStream_t st, const float *src3, int W, int H, int level, float *dst3, int w, int h, const Batch *bt = nullptr);
 void launch_copy_view(hipStream_t st, Img3 src, int W, int H, float *dst, size_t dst_plane, int dst_pitch, const Batch *bt = nullptr);
 // rgb8 -> planar float level 0 (MatchGPULib.cpp:332-338) where k_pyr_base does not apply: pyramids of fewer than three levels, kernel_path 1
 void launch_rgb_planes(hipStream_t st, const uint8_t *rgb, int stride, int W, int H, float *planes, int fmt = 0);

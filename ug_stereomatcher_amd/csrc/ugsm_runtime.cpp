@@ -29,8 +29,8 @@ using namespace ugsm;
 namespace {
 const char *kClassName[2][KC_COUNT] = {
     {"k_cost_split", "k_smooth_fused", "k_sqblur_tiled", "k_blur_decimate_tiled", "k_seed", "-", "-", "misc", "k_cost_march", "k_pyr_base", "k_cost_small",
-     "k_smooth_small", "k_cost_march4", "k_level0_windows"},
-    {"k_cost_ref", "k_smooth_pass", "k_sqblur_clamp", "k_blur_decimate", "k_seed", "k_warp", "k_box", "misc", "-", "-", "-", "-", "-", "-"}};
+     "k_smooth_small", "k_cost_march4", "k_level0_windows", "k_restrict"},
+    {"k_cost_ref", "k_smooth_pass", "k_sqblur_clamp", "k_blur_decimate", "k_seed", "k_warp", "k_box", "misc", "-", "-", "-", "-", "-", "-", "k_restrict"}};
 }  // namespace
 
 namespace ugsm {
@@ -502,11 +502,12 @@ struct FoveaWin {
     bool later = false;
 };
 // skip0 (full-mode calls whose level-0 kernels read the images: Slot::direct0): level 0 is not stored at all.
+// built (a seeded call, which matches no level above its first): only the levels 0 .. built - 1 are produced; 0: all of them.
 int build_pyramids(ugsm_ctx *ctx, Slot &s, int si, const uint8_t *const *rgb, int stride, float *pyr, hipStream_t stream = nullptr, const FoveaWin *win = nullptr,
-                   bool skip0 = false)
+                   bool skip0 = false, int built = 0)
 {
     const hipStream_t pst = stream ? stream : s.st;  // (launches on the side stream are not bracketed by events: Timer records on s.st)
-    const int levels = s.levels, nb = s.nb;
+    const int levels = (built > 0 && built < s.levels) ? built : s.levels, nb = s.nb;
     const bool ref = ctx->cfg.kernel_path == 1;
     // levels 0, 1, 2 in one pass over the rgb8 input (k_pyr_base); the one-stage-per-kernel path keeps the three launches
     const bool base = !ref && levels >= 3;
@@ -909,7 +910,8 @@ bool side_stream_ok(const ugsm_ctx *ctx, const Slot &s)
 }
 // A = G_clamp * L^2 of the full-frame levels a_from .. top on the side stream, beside whatever the main stream does next (the right
 // pyramid's join, the coarse levels' iterations); run_level takes them through level_A, which makes the main stream wait for each.
-int enqueue_side_A(ugsm_ctx *ctx, Slot &s, int a_from)
+// a_top (a seeded call): the first level that is matched, where it is not the top one; < 0: the top level.
+int enqueue_side_A(ugsm_ctx *ctx, Slot &s, int a_from, int a_top = -1)
 {
     if (a_from < 0 || ctx->cfg.early_exit_threshold > 0.0f) return UGSM_OK;
     size_t tot = s.off[s.levels - 1] + 3 * (size_t)s.w[s.levels - 1] * s.h[s.levels - 1];
@@ -917,7 +919,7 @@ int enqueue_side_A(ugsm_ctx *ctx, Slot &s, int a_from)
     HIPCHK(ctx, hipEventRecord(s.ev_L, s.st));  // (the left pyramid is complete on the main stream)
     s.forked = true;
     HIPCHK(ctx, hipStreamWaitEvent(s.st2, s.ev_L, 0));
-    for (int i = s.levels - 1; i >= a_from; i--) {  // coarsest first: that is the order the levels need them in
+    for (int i = a_top >= 0 ? a_top : s.levels - 1; i >= a_from; i--) {  // coarsest first: that is the order the levels need them in
         if (i == 0 && s.direct0) launch_sqblur_clamp(s.st2, byte_view(s.img0L[0], s.img0_stride), s.w[0], s.h[0], s.Apyr + s.off[0], nullptr, kInRGB8);
         else launch_sqblur_clamp(s.st2, level_view(s, s.pyrL, i, 0, 0), s.w[i], s.h[i], s.Apyr + s.off[i]);
         HIPCHK(ctx, hipEventRecord(s.ev_A[i], s.st2));
@@ -931,9 +933,12 @@ int enqueue_side_A(ugsm_ctx *ctx, Slot &s, int a_from)
 // fine levels work on crops whose A is clamped at the crop's own border and is computed in line); < 0: none.
 // full: the call is a full-mode match and nothing else reads these pyramids -- level 0 is then read from the images where level0_direct allows.
 // entries: the fields the call's levels run in lockstep where that is not nb (level0_direct).
+// first (a seeded call; < 0: none): the call matches the levels first .. 0 only: the pyramids hold the levels 0 .. max(first, 2) -- what k_pyr_base
+// makes in its one pass, and the levels up to the first -- so nothing that needs whole pyramids may follow (have_pyr), and A stops at `first`.
 int enqueue_pyramids(ugsm_ctx *ctx, Slot &s, int si, const uint8_t *const *d_rgbL, const uint8_t *const *d_rgbR, int nb, int W, int H, int stride, int a_from = -1,
-                     const FoveaWin *win = nullptr, bool full = false, int entries = 0)
+                     const FoveaWin *win = nullptr, bool full = false, int entries = 0, int first = -1)
 {
+    const int built = first < 0 ? 0 : std::max(first, 2) + 1;
     if (!d_rgbL || !d_rgbR || nb < 1 || nb > kMaxBatch) return UGSM_ERR_BAD_ARG;
     for (int b = 0; b < nb; b++)
         if (!d_rgbL[b] || !d_rgbR[b]) return UGSM_ERR_BAD_ARG;
@@ -956,22 +961,22 @@ int enqueue_pyramids(ugsm_ctx *ctx, Slot &s, int si, const uint8_t *const *d_rgb
         s.img0_stride = stride;
     }
     if (!fork) {
-        UCHK(build_pyramids(ctx, s, si, d_rgbL, stride, s.pyrL, nullptr, win, direct0));
-        UCHK(build_pyramids(ctx, s, si, d_rgbR, stride, s.pyrR, nullptr, win, direct0));
-        s.have_pyr = nb == 1 && !win && !direct0;  // (the fovea-shard entry points work on single pairs, and on whole pyramids)
+        UCHK(build_pyramids(ctx, s, si, d_rgbL, stride, s.pyrL, nullptr, win, direct0, built));
+        UCHK(build_pyramids(ctx, s, si, d_rgbR, stride, s.pyrR, nullptr, win, direct0, built));
+        s.have_pyr = nb == 1 && !win && !direct0 && built == 0;  // (the fovea-shard entry points work on single pairs, and on whole pyramids)
         return UGSM_OK;
     }
     // the side stream starts after everything enqueued on this slot so far (the previous pair still reads pyrR and Apyr)
     HIPCHK(ctx, hipEventRecord(s.ev_in, s.st));
     s.forked = true;
     HIPCHK(ctx, hipStreamWaitEvent(s.st2, s.ev_in, 0));
-    UCHK(build_pyramids(ctx, s, si, d_rgbR, stride, s.pyrR, s.st2, win, direct0));
+    UCHK(build_pyramids(ctx, s, si, d_rgbR, stride, s.pyrR, s.st2, win, direct0, built));
     HIPCHK(ctx, hipEventRecord(s.ev_R, s.st2));
-    UCHK(build_pyramids(ctx, s, si, d_rgbL, stride, s.pyrL, nullptr, win, direct0));
-    if (a_from >= 0) UCHK(enqueue_side_A(ctx, s, a_from));
+    UCHK(build_pyramids(ctx, s, si, d_rgbL, stride, s.pyrL, nullptr, win, direct0, built));
+    if (a_from >= 0) UCHK(enqueue_side_A(ctx, s, a_from, first));
     HIPCHK(ctx, hipStreamWaitEvent(s.st, s.ev_R, 0));
     HIPCHK(ctx, hipGetLastError());
-    s.have_pyr = !win && !direct0;
+    s.have_pyr = !win && !direct0 && built == 0;
     return UGSM_OK;
 }
 int enqueue_pyramids(ugsm_ctx *ctx, Slot &s, int si, const uint8_t *d_rgbL, const uint8_t *d_rgbR, int W, int H, int stride, int a_from = -1,
@@ -1032,23 +1037,43 @@ bool hand_seed(ugsm_ctx *ctx, Slot &s, int si, const Shape &sh, int Ws, int Hs, 
 // side_A: a level's A is taken from the side stream where it was precomputed there (level_A);
 // direct_out (optional): the entries' result buffers, which level 0's last smoothing launch writes itself where it can (no 193 MB device
 // copy at 16 MP): `field` is then null.  Otherwise `field` is the level buffer that holds level `last`'s fields, for the caller's copy.
+// prior (optional; the seeded call, ugsm_submit_full_seeded): the entries' full-resolution fields (s.W x s.H), of which the descent starts at
+// level `first` instead of from the zero seed at the top: the restriction (launch_restrict) fills level `first`'s fields where the zero seed
+// is otherwise set, the levels above run nothing, and level `first` is no top level -- its first iteration blends the confidence like any
+// other, a prior has one.  From there down everything is the same.
 template <class Views>
-int enqueue_descent(ugsm_ctx *ctx, Slot &s, int si, const Shape &sh, int last, Views &&views, bool side_A, float *const *direct_out, float *&field)
+int enqueue_descent(ugsm_ctx *ctx, Slot &s, int si, const Shape &sh, int last, Views &&views, bool side_A, float *const *direct_out, float *&field,
+                    int first = -1, const float *const *prior = nullptr)
 {
     float *cur = s.d0, *other = s.d1;
-    const int top = s.levels - 1;
-    for (int b = 0; b < sh.nb; b++)  // U1: zero seed
-        HIPCHK(ctx, hipMemsetAsync(cur + b * sh.stride, 0, sizeof(float) * 3 * (size_t)s.w[top] * s.h[top], s.st));
+    const int top = s.levels - 1, start = prior ? first : top;
+    if (prior) {
+        if (start < last || start > top) return UGSM_ERR_BAD_ARG;
+        s.cur_level = start;
+        for_groups(sh.nb, launch_pairs(ctx, sh, s.w[start], s.h[start]) > 1, [&](Grp g) {
+            Timer t(ctx, &s, si, KC_RESTRICT, (double)s.w[start] * s.h[start] * g.n);
+            Batch bt{};
+            bt.n = g.n;
+            for (int j = 0; j < g.n; j++) {
+                bt.in[j] = byte_diff(prior[g.b0 + j], prior[g.b0]);
+                bt.out[j] = (long long)(j * sh.stride * sizeof(float));
+            }
+            launch_restrict(s.st, prior[g.b0], s.W, s.H, start, cur + g.b0 * sh.stride, s.w[start], s.h[start], g.n > 1 ? &bt : nullptr);
+        });
+    } else {
+        for (int b = 0; b < sh.nb; b++)  // U1: zero seed
+            HIPCHK(ctx, hipMemsetAsync(cur + b * sh.stride, 0, sizeof(float) * 3 * (size_t)s.w[top] * s.h[top], s.st));
+    }
     SeedMap sm[2 * kMaxBatch];  // (a shape of both directions: two entries per pair)
     Img3 Lv[2 * kMaxBatch], Rv[2 * kMaxBatch];
     bool seeded = false;
     field = nullptr;
-    for (int i = top; i >= last; i--) {
+    for (int i = start; i >= last; i--) {
         s.cur_level = i;
         const int mi = level_iterations(i);
         const bool direct = direct_out && i == 0 && ctx->cfg.kernel_path != 1 && level_smooth(0) > 0 && !(ctx->cfg.early_exit_threshold > 0.0f);
         const int in = views(i, Lv, Rv);
-        UCHK(run_level(ctx, s, si, sh, Lv, Rv, s.w[i], s.h[i], mi, level_smooth(i), i == top, 1, mi, cur, other, nullptr, direct ? direct_out : nullptr,
+        UCHK(run_level(ctx, s, si, sh, Lv, Rv, s.w[i], s.h[i], mi, level_smooth(i), i == top && !prior, 1, mi, cur, other, nullptr, direct ? direct_out : nullptr,
                        seeded ? sm : nullptr, side_A ? level_A(ctx, s, i) : nullptr, in));
         if (direct) return UGSM_OK;
         seeded = i > last && hand_seed(ctx, s, si, sh, s.w[i], s.h[i], s.w[i - 1], s.h[i - 1], nullptr, 0, sm, cur, other);
@@ -1060,7 +1085,8 @@ int enqueue_descent(ugsm_ctx *ctx, Slot &s, int si, const Shape &sh, int last, V
 // matching() with foveatedmatching==0, for the s.nb pairs of the call; d_out: their result buffers.
 // swap: the images exchanged (the right-to-left match of the LR check): the right pyramid is the "left" image; A is then computed
 // in line (the side stream's A planes belong to the left image).
-int enqueue_full(ugsm_ctx *ctx, Slot &s, int si, float *const *d_out, bool swap = false)
+// prior (optional): the seeded call -- the descent starts at level `first` from the pairs' full-resolution priors (enqueue_descent).
+int enqueue_full(ugsm_ctx *ctx, Slot &s, int si, float *const *d_out, bool swap = false, int first = -1, const float *const *prior = nullptr)
 {
     const Shape sh = Shape::pairs(s);
     const float *const pL = swap ? s.pyrR : s.pyrL, *const pR = swap ? s.pyrL : s.pyrR;
@@ -1077,7 +1103,7 @@ int enqueue_full(ugsm_ctx *ctx, Slot &s, int si, float *const *d_out, bool swap 
         return kInPlanes;
     };
     float *field;
-    UCHK(enqueue_descent(ctx, s, si, sh, 0, views, !swap && sh.nb == 1, d_out, field));
+    UCHK(enqueue_descent(ctx, s, si, sh, 0, views, !swap && sh.nb == 1, d_out, field, first, prior));
     for (int b = 0; field && b < sh.nb; b++)
         HIPCHK(ctx, hipMemcpyAsync(d_out[b], field + b * sh.stride, sizeof(float) * 3 * (size_t)s.W * s.H, hipMemcpyDeviceToDevice, s.st));
     return UGSM_OK;
@@ -1421,6 +1447,30 @@ int ugsm::enqueue_match_full(ugsm_ctx *ctx, Slot &s, int si, int n, const uint8_
     s.lr_ran = false;
     s.lr_fov_pairs = 0;
     return enqueue_full(ctx, s, si, d_out);
+}
+
+// The seeded full-mode call (ugsm_submit_full_seeded; its refusals: ugsm_seeded.cpp): n pairs in lockstep from level `start` of their priors.
+// The pyramids stop at level max(start, 2); a lone pair's A planes come from the side stream for the levels start .. 0 as in any full-mode call.
+static int enqueue_match_full_seeded(ugsm_ctx *ctx, Slot &s, int si, int n, const uint8_t *const *d_rgbL, const uint8_t *const *d_rgbR, int W, int H,
+                                     int stride, const float *const *d_prior, int start, float *const *d_out)
+{
+    UCHK(enqueue_pyramids(ctx, s, si, d_rgbL, d_rgbR, n, W, H, stride, n == 1 ? 0 : -1, nullptr, true, 0, start));
+    s.have_coarse = false;
+    s.lr_ran = false;
+    s.lr_fov_pairs = 0;
+    s.lr_full_pairs = 0;
+    return enqueue_full(ctx, s, si, d_out, false, start, d_prior);
+}
+int ugsm::seeded_submit(ugsm_ctx *ctx, int slot, int n, const uint8_t *const *d_rgbL, const uint8_t *const *d_rgbR, int W, int H, int stride,
+                        const float *const *d_prior, int start_level, float *const *d_out)
+{
+    Slot *s;
+    UCHK(get_slot(ctx, slot, &s));
+    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
+    const int per = batch_runs_pair_by_pair(ctx) ? 1 : n;  // (kernel_path 1: the pairs one after the other, as ugsm_submit_full_batch)
+    for (int b = 0; b < n; b += per)
+        UCHK(enqueue_match_full_seeded(ctx, *s, slot, per, d_rgbL + b, d_rgbR + b, W, H, stride, d_prior + b, start_level, d_out + b));
+    return mark_done(ctx, *s);
 }
 namespace {
 
@@ -2399,6 +2449,35 @@ int ugsm_match_full_checked(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *r
     return drained(ctx, 0, match_full_checked_on_slot0(ctx, rgbL, rgbR, W, H, stride, dispH, dispV, dispC, backH, backV, backC, tau));
 }
 
+}  // extern "C"
+// The seeded service call (ugsm_match_full_seeded; its refusals: ugsm_seeded.cpp) on slot 0: images and prior up -- the prior's planes into
+// the slot's result staging, where the call then writes in place: the restriction reads before level 0 writes --, the match, the planes
+// into caller memory of any kind.
+static int seeded_match_on_slot0(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, const float *const prior[3], int start_level,
+                                 float *const disp[3])
+{
+    Slot *s;
+    UCHK(get_slot(ctx, 0, &s));
+    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
+    UCHK(stage_in(ctx, *s, rgbL, rgbR, W, H, stride));
+    const size_t n = (size_t)W * H;
+    UCHK(grow(ctx, s->hout, s->hout_cap, 3 * n));
+    for (int c = 0; c < 3; c++) HIPCHK(ctx, hipMemcpyAsync(s->hout + c * n, prior[c], n * sizeof(float), hipMemcpyHostToDevice, s->st));
+    const uint8_t *const dL = s->rgbL, *const dR = s->rgbR;
+    float *const field = s->hout;
+    UCHK(enqueue_match_full_seeded(ctx, *s, 0, 1, &dL, &dR, W, H, stride, &field, start_level, &field));
+    prefault_planes(ctx, disp, n);
+    UCHK(copy_out_planes(ctx, *s, s->hout, n, disp));
+    s->forked = false;  // (enqueued whole, as mark_done)
+    return ugsm_wait(ctx, 0);
+}
+int ugsm::seeded_match(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, const float *const prior[3], int start_level,
+                       float *const disp[3])
+{
+    return drained(ctx, 0, seeded_match_on_slot0(ctx, rgbL, rgbR, W, H, stride, prior, start_level, disp));
+}
+extern "C" {
+
 int ugsm_submit_full_host(ugsm_ctx *ctx, int slot, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, float *dispH,
                           float *dispV, float *dispC)
 {
@@ -2685,6 +2764,19 @@ int ugsm_stage_seed(ugsm_ctx *ctx, const float *d_src3, int W, int H, float *d_d
     (void)Hup;
     HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
     launch_seed(s->st, d_src3, W, H, d_dst3, W2, H2, crop_x, crop_y);
+    HIPCHK(ctx, hipGetLastError());
+    return ugsm_wait(ctx, 0);
+}
+
+int ugsm_stage_restrict(ugsm_ctx *ctx, const float *d_src3, int W, int H, int level, float *d_dst3)
+{
+    Slot *s;
+    UCHK(get_slot(ctx, 0, &s));
+    if (!d_src3 || !d_dst3 || level < 0 || level >= ctx->cfg.levels) return UGSM_ERR_BAD_ARG;
+    int w[UGSM_MAX_LEVELS], h[UGSM_MAX_LEVELS];
+    UCHK(level_dims(W, H, ctx->cfg.levels, w, h));
+    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
+    launch_restrict(s->st, d_src3, W, H, level, d_dst3, w[level], h[level]);
     HIPCHK(ctx, hipGetLastError());
     return ugsm_wait(ctx, 0);
 }

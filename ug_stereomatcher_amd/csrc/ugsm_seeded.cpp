@@ -1,0 +1,68 @@
+// ugsm_seeded.cpp -- the entry points of the seeded full-mode call (include/ugsm.h: ugsm_submit_full_seeded, ugsm_match_full_seeded,
+// ugsm_seeded_pixel_iterations): what the call refuses, all of it before anything is enqueued, and the call's size.  Written against the
+// public entry points and ugsm_internal.hpp only (no HIP call here, as the queue): the runtime does the enqueueing (ugsm::seeded_submit,
+// ugsm::seeded_match: ugsm_runtime.cpp), and the refusals can be driven on a machine without a GPU (tests/fake_seeded.cpp).
+#include "ugsm_internal.hpp"
+
+using namespace ugsm;
+
+// What both calls refuse beyond their null pointers.
+static int seeded_check(ugsm_ctx *ctx, int n, int W, int H, int stride, int start_level)
+{
+    const ugsm_config &cfg = ctx_config(ctx);
+    const CtxHooks &hooks = ctx_hooks(ctx);
+    if (n < 1 || n > UGSM_MAX_BATCH) return ctx_fail(ctx, UGSM_ERR_BAD_ARG, "the seeded full-mode call takes 1 .. UGSM_MAX_BATCH pairs");
+    if (start_level < 0 || start_level >= cfg.levels) return ctx_fail(ctx, UGSM_ERR_BAD_ARG, "the seeded full-mode call: start_level outside 0 .. levels - 1");
+    // (the early exit compares a level's fields pair by pair through a third buffer and a host round trip: no lockstep, and no use beside a prior)
+    if (cfg.early_exit_threshold > 0.0f) return ctx_fail(ctx, UGSM_ERR_BAD_ARG, "the seeded full-mode call: not with early_exit_threshold > 0");
+    if (hooks.queue_busy && !hooks.queue_calling)
+        return ctx_fail(ctx, UGSM_ERR_STATE, "pairs enqueued with ugsm_enqueue_* are outstanding: the slots belong to the queue until ugsm_next_done has reported them all");
+    float tau = 0.0f;
+    int modes = 0;
+    if (ugsm_get_lr_check(ctx, &tau, &modes) == UGSM_OK && tau > 0.0f && (modes & UGSM_LR_FULL))
+        return ctx_fail(ctx, UGSM_ERR_STATE, "the full-mode LR check is on (ugsm_set_lr_check): there is no seeded checked call");
+    int w[UGSM_MAX_LEVELS], h[UGSM_MAX_LEVELS];
+    const int st = ugsm_level_dims(W, H, cfg.levels, w, h);
+    if (st != UGSM_OK) return st;
+    if (stride < input_bpp(hooks.input_format) * W) return UGSM_ERR_SIZE_MISMATCH;
+    return UGSM_OK;
+}
+
+extern "C" {
+
+int ugsm_submit_full_seeded(ugsm_ctx *ctx, int slot, int n, const uint8_t *const *d_rgbL, const uint8_t *const *d_rgbR, int W, int H, int stride,
+                            const float *const *d_prior, int start_level, float *const *d_out)
+{
+    if (!ctx) return UGSM_ERR_BAD_ARG;
+    if (!d_rgbL || !d_rgbR || !d_prior || !d_out) return ctx_fail(ctx, UGSM_ERR_BAD_ARG, "the seeded full-mode call: a null array");
+    const int st = seeded_check(ctx, n, W, H, stride, start_level);
+    if (st != UGSM_OK) return st;
+    for (int b = 0; b < n; b++)
+        if (!d_rgbL[b] || !d_rgbR[b] || !d_prior[b] || !d_out[b]) return ctx_fail(ctx, UGSM_ERR_BAD_ARG, "the seeded full-mode call: a null entry");
+    return seeded_submit(ctx, slot, n, d_rgbL, d_rgbR, W, H, stride, d_prior, start_level, d_out);
+}
+
+int ugsm_match_full_seeded(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, const float *priorH, const float *priorV,
+                           const float *priorC, int start_level, float *dispH, float *dispV, float *dispC)
+{
+    if (!ctx) return UGSM_ERR_BAD_ARG;
+    if (!rgbL || !rgbR || !priorH || !priorV || !priorC || !dispH || !dispV || !dispC)
+        return ctx_fail(ctx, UGSM_ERR_BAD_ARG, "the seeded full-mode call: a null pointer");
+    const int st = seeded_check(ctx, 1, W, H, stride, start_level);
+    if (st != UGSM_OK) return st;
+    const float *const prior[3] = {priorH, priorV, priorC};
+    float *const disp[3] = {dispH, dispV, dispC};
+    return seeded_match(ctx, rgbL, rgbR, W, H, stride, prior, start_level, disp);
+}
+
+long long ugsm_seeded_pixel_iterations(int W, int H, int levels, int start_level)
+{
+    int w[UGSM_MAX_LEVELS], h[UGSM_MAX_LEVELS];
+    if (levels < 1 || levels > UGSM_MAX_LEVELS || start_level < 0 || start_level >= levels) return -1;
+    if (ugsm_level_dims(W, H, levels, w, h) != UGSM_OK) return -1;
+    long long tot = 0;
+    for (int i = 0; i <= start_level; i++) tot += (long long)w[i] * h[i] * ugsm_level_iterations(i);
+    return tot;
+}
+
+}  // extern "C"

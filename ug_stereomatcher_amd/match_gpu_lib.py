@@ -117,6 +117,15 @@ class MatchGPULib:
                                       out[0].ctypes.data, out[1].ctypes.data, out[2].ctypes.data))
         return out
 
+    def matchSeeded(self, cv_ptrL, cv_ptrR, prior, start_level: int) -> np.ndarray:
+        """(not in the reference) match(L, R, 0) started at level start_level from `prior`, a finDisp of the images' size -- the previous
+        frame's, say -- instead of from the zero seed at the top level (ugsm_match_full_seeded).  Returns finDisp."""
+        L, R = _as_rgb8(cv_ptrL), _as_rgb8(cv_ptrR)
+        if L.shape != R.shape or L.strides[0] != R.strides[0]:
+            raise UgsmError(_lib.UGSM_ERR_SIZE_MISMATCH, "left/right images differ in size")
+        self.foveatedmatching = 0
+        return self._ctx.match_full_seeded(L, R, np.asarray(prior, np.float32), start_level)
+
     # -- hierarchicalDisparity, MatchGPULib.cpp:2589-2701 --
     def hierarchicalDisparity(self, foveated: np.ndarray, widthInit: int, heightInit: int) -> np.ndarray:
         """foveated: (foveatelevel, 3, fovH, fovW) as matchStack returns it -> (3, heightInit, widthInit)."""
