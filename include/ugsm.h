@@ -41,7 +41,8 @@ extern "C" {
                                match -- ugsm_warp_planes, ugsm_warp_right, ugsm_warp_right_fovea, ugsm_photometric_residual,
                                ugsm_photometric_residual_fovea; the checked full-mode call -- ugsm_submit_full_checked, ugsm_match_full_checked,
                                ugsm_last_lr_marked_pair; the seeded full-mode call -- ugsm_submit_full_seeded, ugsm_match_full_seeded,
-                               ugsm_stage_restrict, ugsm_seeded_pixel_iterations
+                               ugsm_stage_restrict, ugsm_seeded_pixel_iterations; the seeded (warm) foveated call -- ugsm_submit_foveated_warm,
+                               ugsm_submit_foveated_warm_field, ugsm_match_foveated_warm, ugsm_stage_warm_stack, ugsm_fovea_warm_pixel_iterations
                                6: the kernel choices follow what is in flight, not ugsm_config.slots: ugsm_plan_level takes `alone`, ugsm_plan_level_in_frame
                                is gone, ugsm_level_plan.latency_policy is .alone; ugsm_enqueue_* returns UGSM_OK once the pair is accepted (a failed
                                CALL is reported through ugsm_completion.status only); the fovea shard carries a status word (a rank that fails still
@@ -165,6 +166,8 @@ int ugsm_fovea_dims(int W, int H, int levels, int fovea_levels, int *fovW, int *
 long long ugsm_pixel_iterations(int W, int H, int levels, int fovea_levels);
 /* The same for a seeded full-mode call (ugsm_submit_full_seeded): the levels start_level .. 0 only.  -1 for a size or a level that does not exist. */
 long long ugsm_seeded_pixel_iterations(int W, int H, int levels, int start_level);
+/* ... and for a warm foveated call (ugsm_submit_foveated_warm): fovW x fovH x the iterations of the levels start_level .. 0.  -1 likewise. */
+long long ugsm_fovea_warm_pixel_iterations(int W, int H, int levels, int fovea_levels, int start_level);
 
 /* Which kernels a W x H level runs under `cfg` (NULL = defaults), for maintainers and the host tests; results never depend on it.
  * ONE thing besides the level's size decides: whether the call has the chip to itself (`alone` != 0) or shares it with other calls.
@@ -380,7 +383,8 @@ int ugsm_match_full_checked(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *r
  * contexts with early_exit_threshold > 0: UGSM_ERR_BAD_ARG; UGSM_LR_FULL in force (ugsm_set_lr_check) or pairs outstanding in the queue:
  * UGSM_ERR_STATE; the size errors of ugsm_submit_full as there.  kernel_path 1 (libugsm_dev.so) runs the pairs one after the other, as it does
  * for ugsm_submit_full_batch.  What it saves, measured: DESIGN.md section 8.
- * NOT built: a queue form (ugsm_enqueue_*); the page-locked _host kind; a seeded checked or foveated call.
+ * NOT built: a queue form (ugsm_enqueue_*); the page-locked _host kind; a seeded checked or foveated call of this kind (the foveated one is
+ * a call of its own, from a prior STACK: ugsm_submit_foveated_warm, below).
  * Asynchronous on `slot`. */
 int ugsm_submit_full_seeded(ugsm_ctx *ctx, int slot, int n, const uint8_t *const *d_rgbL, const uint8_t *const *d_rgbR,
                             int W, int H, int stride, const float *const *d_prior, int start_level, float *const *d_out);
@@ -388,6 +392,56 @@ int ugsm_submit_full_seeded(ugsm_ctx *ctx, int slot, int n, const uint8_t *const
 int ugsm_match_full_seeded(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride,
                            const float *priorH, const float *priorV, const float *priorC, int start_level,
                            float *dispH, float *dispV, float *dispC);
+/* The seeded FOVEATED call -- "warm", against the cold call that starts from the zero seed at the top level: n pairs (1 <= n <= UGSM_MAX_BATCH,
+ * all W x H) matched from FOVEA level start_level downwards, each from a prior fovea STACK of its own, whose window may lie elsewhere than the
+ * new one -- for a tracker, which looks at one place frame after frame and holds the previous frame's stack for it.  Every matched level of a
+ * stack is a fovW x fovH field, so a foveated call is launch-bound throughout and the coarse levels it leaves out are most of its launches.
+ * The build's own definition, as ugsm_submit_full_seeded is.
+ *   d_rgbL, d_rgbR, off_x, off_y, d_stack  as ugsm_submit_foveated_batch takes them (a NULL offset array: centred); no pyramid stacks.
+ *   d_prior_stack              HOST array of n DEVICE pointers: stacks of the d_stack layout, e.g. an earlier call's d_stack.
+ *   prior_off_x, prior_off_y   the offsets those stacks were matched at (NULL: centred).
+ *   start_level                0 .. fovea_levels - 1: the first level that is matched.
+ * The starting fields, from operations this header already defines (so every comparison is bit for bit): with P the full-resolution field
+ * ugsm_reconstruct_full gives for the prior stack at the prior's offsets, and R_k what ugsm_stage_restrict gives for P at level k, the
+ * starting field of level k (start_level <= k <= F-1) is the fovW x fovH crop of R_k at the NEW window's origin at level k (level F-1: the
+ * whole level).  ONE launch computes them pointwise from the stack (ugsm_stage_warm_stack runs it alone): neither P -- twice 193 MB written at
+ * 16 MP -- nor R_k is ever formed.  For a target pixel: its level-0 site (sx, sy) as in ugsm_submit_full_seeded's restriction; then V_0(sx, sy),
+ * where V_{F-1}(x, y) is row block F-1 of the prior at (x, y) and, for l < F-1, V_l(x, y) is row block l at (x - ox_l, y - oy_l) where that
+ * lies inside the prior's window of level l, else (float)1.41421356 * V_{l+1}(tex((x + .5f) / (float)1.41421356), tex((y + .5f) / ...)) --
+ * ugsm_reconstruct_full's step, all three channels scaled, every multiplication rounded on its own --; then the restriction's value transform.
+ * The contract, bit for bit: row blocks start_level + 1 .. F-1 of d_stack[k] receive their starting fields -- the prior carried over to the new
+ * window by ONE rule (no copy-if-the-window-did-not-move branch: inside a finer window of the prior the finer level's value is the better one),
+ * so the result is itself a valid prior and a valid input to ugsm_reconstruct_full and the cloud calls.  Level start_level is matched from its
+ * starting field with its usual iteration and smoothing counts and never takes the top level's first-iteration exception; the levels below
+ * follow exactly as the fine phase of ugsm_submit_foveated runs them (foveatedsubsampleDisp between them, the window views of the new
+ * offsets); start_level = F-1 matches the whole-frame level F-1 first.  Row blocks 0 .. start_level receive the matched fields.  Nothing else
+ * is written.
+ * What runs: the pyramid kernels build the levels 0 .. max(start_level, 2) only, level 0 inside the windows; one starting-field launch per
+ * call (k_restrict_stack in the kernel statistics, at level start_level, n (F - start_level) fovW fovH pixel-launches); no launch at any level
+ * above start_level; from there down every launch is the one ugsm_submit_foveated_batch makes for these n pairs, lockstep grouping included.
+ * Any input format, captured at the call.  A call whose prior is the d_stack of the call enqueued just before on the same slot needs no wait
+ * in between.
+ * WARNING: a chain of warm calls never refreshes the levels above start_level -- they are carried over, resampled, frame after frame.  The host
+ * decides when to run a cold call (ugsm_submit_foveated) again.
+ * Status, all before anything is enqueued: null arrays or null entries, n outside 1 .. UGSM_MAX_BATCH, start_level outside 0 .. F-1,
+ * fovea_levels < 2, contexts with early_exit_threshold > 0, and a prior that overlaps one of the call's d_stack buffers (the call is NOT in
+ * place: the launch that reads the priors writes the stacks; a tracker alternates two stacks, 21 MB each at 16 MP): UGSM_ERR_BAD_ARG;
+ * UGSM_LR_FOVEATED in force (ugsm_set_lr_check) or pairs outstanding in the queue: UGSM_ERR_STATE; the size errors of ugsm_submit_foveated as
+ * there.  kernel_path 1 (libugsm_dev.so) runs the pairs one after the other.  What it saves, measured: DESIGN.md section 8.
+ * NOT built: pyramid stacks from this call (the levels above max(start_level, 2) are not built); a queue or managed form; the page-locked
+ * _host kind; a checked call; a multi-window call; start levels above F-1.
+ * Asynchronous on `slot`. */
+int ugsm_submit_foveated_warm(ugsm_ctx *ctx, int slot, int n, const uint8_t *const *d_rgbL, const uint8_t *const *d_rgbR, int W, int H, int stride,
+                              const int *off_x, const int *off_y, const float *const *d_prior_stack, const int *prior_off_x, const int *prior_off_y,
+                              int start_level, float *const *d_stack);
+/* The same from full-resolution FIELDS (3 planes of W x H each, e.g. a full-mode d_out) -- for the host that matches the whole frame once
+ * and follows windows afterwards: P is the field itself and the descent above has depth zero. */
+int ugsm_submit_foveated_warm_field(ugsm_ctx *ctx, int slot, int n, const uint8_t *const *d_rgbL, const uint8_t *const *d_rgbR, int W, int H, int stride,
+                                    const int *off_x, const int *off_y, const float *const *d_prior_field, int start_level, float *const *d_stack);
+/* Blocking, one pair on slot 0, any host memory in and out, as ugsm_match_foveated; the prior: the three planes of a stack, not the result planes. */
+int ugsm_match_foveated_warm(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, int off_x, int off_y,
+                             const float *priorH, const float *priorV, const float *priorC, int prior_off_x, int prior_off_y, int start_level,
+                             float *stackH, float *stackV, float *stackC);
 /* ---- several fovea windows on ONE pair ------------------------------------------------------------------------------------------------
  *
  * A host that looks at n places of one frame (1 <= n <= UGSM_MAX_BATCH) needs the pyramids and the coarse phase -- levels top .. F-1, which
@@ -923,6 +977,10 @@ int ugsm_stage_seed(ugsm_ctx *ctx, const float *d_src3, int W, int H, float *d_d
 /* The restriction of the seeded call (ugsm_submit_full_seeded) alone: level `level`'s starting field d_dst3 (3 planes of w x h, the level's
  * size by ugsm_level_dims with the context's levels) from the full-resolution field d_src3 (3 planes of W x H).  Not in place. */
 int ugsm_stage_restrict(ugsm_ctx *ctx, const float *d_src3, int W, int H, int level, float *d_dst3);
+/* The starting-field launch of the warm foveated call (ugsm_submit_foveated_warm) alone: row blocks start_level .. F-1 of d_dst_stack from the
+ * stack d_prior_stack matched at (prior_off_x, prior_off_y), for a window at (off_x, off_y); the row blocks below are not written.  Not in place. */
+int ugsm_stage_warm_stack(ugsm_ctx *ctx, const float *d_prior_stack, int W, int H, int prior_off_x, int prior_off_y, int off_x, int off_y,
+                          int start_level, float *d_dst_stack);
 /* S smoothing passes (+ box if do_box), MatchGPULib.cpp:2257-2412, in place */
 int ugsm_stage_smooth(ugsm_ctx *ctx, float *d_d3, int W, int H, int passes, int do_box);
 

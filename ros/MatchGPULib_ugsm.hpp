@@ -167,6 +167,37 @@ public:
     template <class ImgPtr>
     float ***matchStack(ImgPtr L, ImgPtr R) { return stack(L, R, nullptr, nullptr); }
 
+    // (not in the reference) matchStack for the window at off[2] started at fovea level start_level from `prior_stack` -- a
+    // disparity[level][3][fovH*fovW] as matchStack returns it, the previous frame's at the offsets prior_off[2] -- instead of from the zero seed at
+    // the top level (ugsm_match_foveated_warm).  Returns a fresh stack; the levels above start_level are the prior carried over; the prior stays
+    // the caller's.  A chain of these never refreshes the levels above start_level: run matchStack again now and then.
+    template <class ImgPtr>
+    float ***matchStackSeeded(ImgPtr L, ImgPtr R, float **const *prior_stack, const int *prior_off, const int *off, int start_level)
+    {
+        const int W = L->image.cols, H = L->image.rows, F = foveatelevel;
+        if (!prior_stack || !prior_off || !off || R->image.cols != W || R->image.rows != H) return nullptr;
+        if (ugsm_fovea_dims(W, H, 14, F, &fovW, &fovH) != UGSM_OK) return nullptr;
+        const size_t fn = (size_t)fovW * fovH, sn = fn * F;
+        float *in = (float *)std::malloc(3 * sn * sizeof(float)), *sh = (float *)std::malloc(3 * sn * sizeof(float));
+        for (int k = 0; k < F; k++)
+            for (int c = 0; c < 3; c++) std::memcpy(in + c * sn + k * fn, prior_stack[k][c], fn * sizeof(float));
+        const int st = ugsm_match_foveated_warm(ctx_, L->image.data, R->image.data, W, H, (int)L->image.step, off[0], off[1], in, in + sn, in + 2 * sn,
+                                                prior_off[0], prior_off[1], start_level, sh, sh + sn, sh + 2 * sn);
+        float ***disp = nullptr;
+        if (st == UGSM_OK) {
+            disp = (float ***)std::malloc(F * sizeof(float **));
+            for (int k = 0; k < F; k++) {
+                disp[k] = alloc_planes(3, fn);
+                for (int c = 0; c < 3; c++) std::memcpy(disp[k][c], sh + c * sn + k * fn, fn * sizeof(float));
+            }
+        } else {
+            std::fprintf(stderr, "ugsm: %s: %s\n", ugsm_status_string(st), ugsm_last_error(ctx_));
+        }
+        std::free(in);
+        std::free(sh);
+        return disp;
+    }
+
     // Several windows of one pair (not in the reference; include/ugsm.h, "several fovea windows on ONE pair"): matchStack for the n offsets
     // (1 <= n <= UGSM_MAX_BATCH) in one call -- pyramids and the coarse levels once, the windows' fine levels in lockstep.  out[k]: the
     // disparity[level][3][fovH*fovW] matchStack returns for (off_x[k], off_y[k]), malloc'd the same way.  False on failure (nothing allocated).

@@ -159,6 +159,23 @@ int main(int argc, char **argv)
             for (float **p : {cold, s1, s2}) { for (int c = 0; c < 3; c++) free(p[c]); free(p); }
             if (differ) return 23;
         }
+        // matchStackSeeded(L, R, st, {0, 0}, {12, -8}, F - 1): the window moved by a few pixels, started at the top fovea level from the cold stack --
+        // the same stack every time; a start level that does not exist is refused
+        {
+            const int at0[2] = {0, 0}, at1[2] = {12, -8}, sl = m.getFoveateLevel() - 1;
+            float ***w1 = m.matchStackSeeded(L, R, st, at0, at1, sl), ***w2 = m.matchStackSeeded(L, R, st, at0, at1, sl);
+            if (!w1 || !w2 || m.matchStackSeeded(L, R, st, at0, at1, m.getFoveateLevel())) return 24;
+            const size_t fn = (size_t)m.getFoveaWidth() * m.getFoveaHeight();
+            size_t differ = 0;
+            for (int k = 0; k < m.getFoveateLevel(); k++)
+                for (int c = 0; c < 3; c++) differ += std::memcmp(w1[k][c], w2[k][c], sizeof(float) * fn) != 0;
+            std::printf("matchStackSeeded (fovea level %d from the cold stack, window moved) twice: %s\n", sl, differ ? "DIFFER" : "identical");
+            for (float ***p : {w1, w2}) {
+                for (int k = 0; k < m.getFoveateLevel(); k++) { for (int c = 0; c < 3; c++) free(p[k][c]); free(p[k]); }
+                free(p);
+            }
+            if (differ) return 25;
+        }
         for (int k = 0; k < m.getFoveateLevel(); k++) { for (int i = 0; i < 3; i++) free(st[k][i]); free(st[k]); }
         free(st);
     } catch (const std::exception &e) {

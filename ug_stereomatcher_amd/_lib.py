@@ -73,6 +73,8 @@ EXPORTS = [
     "ugsm_submit_full_checked", "ugsm_match_full_checked", "ugsm_last_lr_marked_pair",
     # the seeded full-mode call
     "ugsm_submit_full_seeded", "ugsm_match_full_seeded", "ugsm_stage_restrict", "ugsm_seeded_pixel_iterations",
+    # the seeded (warm) foveated call
+    "ugsm_submit_foveated_warm", "ugsm_submit_foveated_warm_field", "ugsm_match_foveated_warm", "ugsm_stage_warm_stack", "ugsm_fovea_warm_pixel_iterations",
 ]
 # ... and what include/ugsm_dev.h adds (libugsm_dev.so only)
 DEV_EXPORTS = ["ugsm_stage_poly_probe", "ugsm_stage_div3_probe", "ugsm_stage_div_probe", "ugsm_stage_range_words", "ugsm_stage_iterate_rgb8", "ugsm_stage_level0_direct"]
@@ -292,6 +294,13 @@ def load(dev: bool = False):
     lib.ugsm_stage_restrict.argtypes = [vp, vp, i, i, i, vp]
     lib.ugsm_seeded_pixel_iterations.argtypes = [i, i, i, i]
     lib.ugsm_seeded_pixel_iterations.restype = C.c_longlong
+    ip = C.POINTER(C.c_int)
+    lib.ugsm_submit_foveated_warm.argtypes = [vp, i, i, pp, pp, i, i, i, ip, ip, pp, ip, ip, i, pp]
+    lib.ugsm_submit_foveated_warm_field.argtypes = [vp, i, i, pp, pp, i, i, i, ip, ip, pp, i, pp]
+    lib.ugsm_match_foveated_warm.argtypes = [vp, vp, vp, i, i, i, i, i, vp, vp, vp, i, i, i, vp, vp, vp]
+    lib.ugsm_stage_warm_stack.argtypes = [vp, vp, i, i, i, i, i, i, i, vp]
+    lib.ugsm_fovea_warm_pixel_iterations.argtypes = [i, i, i, i, i]
+    lib.ugsm_fovea_warm_pixel_iterations.restype = C.c_longlong
     lib.ugsm_wait.argtypes = [vp, i]
     lib.ugsm_wait_all.argtypes = [vp]
     lib.ugsm_submit_pyramids.argtypes = [vp, i, vp, vp, i, i, i]
@@ -439,6 +448,11 @@ def pixel_iterations(W: int, H: int, levels: int = 14, fovea_levels: int = 0) ->
 def seeded_pixel_iterations(W: int, H: int, levels: int = 14, start_level: int = 0) -> int:
     """Sum of iterations x pixels over the levels start_level .. 0: what a seeded full-mode call runs (-1: no such size or level)."""
     return int(load().ugsm_seeded_pixel_iterations(W, H, levels, start_level))
+
+
+def fovea_warm_pixel_iterations(W: int, H: int, levels: int = 14, fovea_levels: int = 7, start_level: int = 0) -> int:
+    """fovW x fovH x the iterations of the levels start_level .. 0: what a warm foveated call runs (-1: no such size or level)."""
+    return int(load().ugsm_fovea_warm_pixel_iterations(W, H, levels, fovea_levels, start_level))
 
 
 def cloud_params(sampling: int = 1, format: int = UGSM_CLOUD_PCL32, compact: bool = False, min_conf: float | None = None,
@@ -864,6 +878,47 @@ class Context:
     def stage_restrict(self, d_src3: int, W: int, H: int, level: int, d_dst3: int):
         """The seeded call's restriction alone (ugsm_stage_restrict): level `level`'s starting field from a full-resolution one; waits."""
         self.check(self.lib.ugsm_stage_restrict(self._h, d_src3, W, H, int(level), d_dst3))
+
+    def submit_foveated_warm(self, slot: int, d_rgbL, d_rgbR, W: int, H: int, stride: int, offsets, d_prior_stack, prior_offsets, start_level: int,
+                             d_stack):
+        """The pairs matched from fovea level start_level downwards, each from its prior stack matched at prior_offsets[k]
+        (ugsm_submit_foveated_warm): lists of device pointers, one entry per pair; offsets: lists of (x, y), None = centred.  Not in place."""
+        n = len(d_rgbL)
+        if len(d_rgbR) != n or len(d_prior_stack) != n or len(d_stack) != n or any(o is not None and len(o) != n for o in (offsets, prior_offsets)):
+            raise UgsmError(UGSM_ERR_BAD_ARG, "one entry per pair in every list")
+        ox, oy = self._offsets(offsets, n)
+        px, py = self._offsets(prior_offsets, n)
+        self.check(self.lib.ugsm_submit_foveated_warm(self._h, slot, n, self._ptrs(d_rgbL), self._ptrs(d_rgbR), W, H, stride, ox, oy,
+                                                      self._ptrs(d_prior_stack), px, py, int(start_level), self._ptrs(d_stack)))
+
+    def submit_foveated_warm_field(self, slot: int, d_rgbL, d_rgbR, W: int, H: int, stride: int, offsets, d_prior_field, start_level: int, d_stack):
+        """The same from full-resolution prior fields, 3 planes of W x H each (ugsm_submit_foveated_warm_field)."""
+        n = len(d_rgbL)
+        if len(d_rgbR) != n or len(d_prior_field) != n or len(d_stack) != n or (offsets is not None and len(offsets) != n):
+            raise UgsmError(UGSM_ERR_BAD_ARG, "one entry per pair in every list")
+        ox, oy = self._offsets(offsets, n)
+        self.check(self.lib.ugsm_submit_foveated_warm_field(self._h, slot, n, self._ptrs(d_rgbL), self._ptrs(d_rgbR), W, H, stride, ox, oy,
+                                                            self._ptrs(d_prior_field), int(start_level), self._ptrs(d_stack)))
+
+    def match_foveated_warm(self, L: np.ndarray, R: np.ndarray, prior_stack: np.ndarray, prior_off, off, start_level: int) -> np.ndarray:
+        """Blocking, from any host memory (ugsm_match_foveated_warm): the (3, F, fovH, fovW) stack of the window at `off` reached from fovea level
+        start_level of `prior_stack`, a stack of that shape matched at `prior_off`."""
+        W, H, stride = self.check_image(L)
+        if self.check_image(R) != (W, H, stride):
+            raise UgsmError(UGSM_ERR_SIZE_MISMATCH, "the two images differ in size or stride")
+        pr = np.ascontiguousarray(prior_stack, np.float32)
+        if pr.ndim != 4 or pr.shape[0] != 3:
+            raise UgsmError(UGSM_ERR_SIZE_MISMATCH, "the prior is a (3, F, fovH, fovW) stack")
+        out = np.empty(pr.shape, np.float32)
+        self.check(self.lib.ugsm_match_foveated_warm(self._h, L.ctypes.data, R.ctypes.data, W, H, stride, int(off[0]), int(off[1]),
+                                                     *[pr[c].ctypes.data for c in range(3)], int(prior_off[0]), int(prior_off[1]), int(start_level),
+                                                     *[out[c].ctypes.data for c in range(3)]))
+        return out
+
+    def stage_warm_stack(self, d_prior_stack: int, W: int, H: int, prior_off, off, start_level: int, d_dst_stack: int):
+        """The warm foveated call's starting-field launch alone (ugsm_stage_warm_stack): row blocks start_level .. F-1 of d_dst_stack; waits."""
+        self.check(self.lib.ugsm_stage_warm_stack(self._h, d_prior_stack, W, H, int(prior_off[0]), int(prior_off[1]), int(off[0]), int(off[1]),
+                                                  int(start_level), d_dst_stack))
 
     def submit_foveated_batch(self, slot: int, d_rgbL, d_rgbR, W: int, H: int, stride: int, offsets, d_stack, d_pyrL=None, d_pyrR=None):
         n = len(d_rgbL)

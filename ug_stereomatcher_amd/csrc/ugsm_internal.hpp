@@ -82,6 +82,14 @@ int seeded_submit(ugsm_ctx *ctx, int slot, int n, const uint8_t *const *d_rgbL, 
                   const float *const *d_prior, int start_level, float *const *d_out);
 int seeded_match(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, const float *const prior[3], int start_level,
                  float *const disp[3]);
+// The warm foveated call behind its entry points (ugsm_fovea_seeded.cpp, which has refused what the call refuses): n pairs enqueued on `slot`
+// from fovea level start_level of their priors -- stacks with their windows' offsets (null arrays: centred), or, field != 0, full-resolution
+// fields --; and the blocking call on slot 0, its three prior and result stack planes in host memory of any kind.
+int fovea_warm_submit(ugsm_ctx *ctx, int slot, int n, const uint8_t *const *d_rgbL, const uint8_t *const *d_rgbR, int W, int H, int stride, const int *off_x,
+                      const int *off_y, const float *const *d_prior, const int *prior_off_x, const int *prior_off_y, int field, int start_level,
+                      float *const *d_stack);
+int fovea_warm_match(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, int off_x, int off_y, const float *const prior[3],
+                     int prior_off_x, int prior_off_y, int start_level, float *const stack[3]);
 // the stagger of the queue's first round after idle and the size of every later call (ugsm.h, "the queue")
 int queue_target(int batch, int slots, long long calls_since_idle);
 

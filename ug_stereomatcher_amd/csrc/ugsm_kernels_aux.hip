@@ -5,8 +5,8 @@
 // k_rgb_planes (level 0 of a pyramid of fewer than three levels: BASELINE configs[0]; its window form: level 0 inside the windows of a
 // multi-window foveated call), k_lr_check (the opt-in LR-consistency check),
 // k_triangulate[_fovea] (the X, Y, Z planes and, as other forms of the same kernels, the coloured point cloud),
-// k_upsample_paste (row f-3; and its form over the stacks of several windows), k_wdiff_* (row f-4; and, as other forms, the photometric
-// residual of a match), the warp form of k_rgb_planes (MatchGPULib::warpRightImage).  All HBM- or launch-bound.
+// k_upsample_paste (row f-3; its form over the stacks of several windows; and its pointwise form: the starting fields of a warm foveated
+// call from a prior stack), k_wdiff_* (row f-4; and, as other forms, the photometric residual of a match), the warp form of k_rgb_planes (MatchGPULib::warpRightImage).  All HBM- or launch-bound.
 // Citations: /root/reference/src/gpu_matcher/<file>:<line> unless a path is given.
 #include "ugsm_device.hpp"
 #include "ugsm_launch.hpp"
@@ -989,6 +989,106 @@ void launch_upsample_paste_multi(hipStream_t st, const float *src3, int W, int H
                                  int fovW, int fovH, const PasteWindows &pw)
 {
     UGSM_LAUNCH(k_upsample_paste, dim3((W2 + 255) / 256, H2), dim3(256), 0, st, src3, W, H, dst3, W2, H2, fov0, fov_plane, fovW, fovH, pw);
+}
+
+// The pointwise form (k_restrict_stack in the statistics; ugsm_submit_foveated_warm -- no reference counterpart, DESIGN.md section 8;
+// RestrictStack, ugsm_launch.hpp): one thread per pixel of the fw x fh starting field of fovea level k of entry e, blockIdx.z = e x (F - s) +
+// (k - s), all three planes -- they share the descent.  Window pixel (ix, iy) is level-k pixel (ix + nox[k], iy + noy[k]); its level-0 site is
+// restrict_site's; from there the rule of the kernels above is walked from level 0 upwards: level l < F-1 holds the value where the site
+// lies inside the prior's window of that level, otherwise it is s * (level l + 1 at tex_index((c + .5f) / s)), the very expressions above.
+// The walk's level is uniform (the windows' origins and the levels' sizes come from scalar loads); a lane that has found its level stops
+// moving, and the wave leaves the loop when every lane has.  The multiplications by s follow, one per level descended, each rounded on its
+// own; then the restriction's value transform (k_seed's restriction form).  Nothing is read outside the prior: a window test precedes every
+// read of a level below F-1, and tex_index clamps to level F-1's own size.
+template <bool kTable>
+__global__ __launch_bounds__(256) void k_upsample_paste(const float *__restrict__ prior0, float *__restrict__ stack0, float *__restrict__ work0, RestrictStack rs)
+{
+    const int ix = blockIdx.x * blockDim.x + threadIdx.x;
+    const int iy = blockIdx.y;
+    const int nl = rs.F - rs.s;
+    const int e = blockIdx.z / nl, k = rs.s + (int)blockIdx.z - e * nl;
+    const RestrictStackRow &row = kTable ? rs.table[e] : rs.rows[e];
+    if (ix >= rs.fw) return;
+    const float s = (float)1.41421356;
+    const int half = k >> 1, odd = k & 1;
+    int x = restrict_site(ix + row.nox[k], half, odd, rs.W);
+    int y = restrict_site(iy + row.noy[k], half, odd, rs.H);
+    const float *const src = shifted(prior0, row.prior);
+    const size_t fn = (size_t)rs.fw * rs.fh;
+    size_t at, plane;
+    int depth = 0;
+    if (rs.field) {
+        at = (size_t)y * rs.W + x;
+        plane = (size_t)rs.W * rs.H;
+    } else {
+        plane = (size_t)rs.F * fn;
+        bool found = false;
+        at = 0;
+        for (int l = 0; l < rs.F - 1; l++) {
+            const int fx = x - row.pox[l], fy = y - row.poy[l];
+            if (!found && fx >= 0 && fx < rs.fw && fy >= 0 && fy < rs.fh) {
+                found = true;
+                depth = l;
+                at = (size_t)l * fn + (size_t)fy * rs.fw + fx;
+            }
+            if (!found) {
+                x = tex_index(((float)x + 0.5f) / s, rs.w[l + 1]);
+                y = tex_index(((float)y + 0.5f) / s, rs.h[l + 1]);
+            }
+            if (__ballot(!found) == 0) break;
+        }
+        if (!found) {
+            depth = rs.F - 1;
+            at = (size_t)(rs.F - 1) * fn + (size_t)y * rs.fw + x;
+        }
+    }
+    float v0 = src[at], v1 = src[plane + at], v2 = src[2 * plane + at];
+    for (int j = 0; j < depth; j++) {
+        v0 = s * v0;
+        v1 = s * v1;
+        v2 = s * v2;
+    }
+    if (odd) {
+        v0 = (float)((double)v0 / UGSM_SCALE);
+        v1 = (float)((double)v1 / UGSM_SCALE);
+    }
+    if (half) {
+        const float scale = __int_as_float((127 - half) << 23);  // 2^-half
+        v0 = v0 * scale;
+        v1 = v1 * scale;
+    }
+    const size_t o = (size_t)iy * rs.fw + ix;
+    if (work0 && k == rs.s) {
+        float *const dst = shifted(work0, row.work);
+        dst[o] = v0;
+        dst[fn + o] = v1;
+        dst[2 * fn + o] = v2;
+    } else {
+        float *const dst = shifted(stack0, row.dst) + (size_t)k * fn;
+        const size_t stack_plane = (size_t)rs.F * fn;
+        dst[o] = v0;
+        dst[stack_plane + o] = v1;
+        dst[2 * stack_plane + o] = v2;
+    }
+}
+
+bool launch_restrict_stack(hipStream_t st, const float *prior0, float *stack0, float *work0, RestrictStack rs, const RestrictStackRow *rows)
+{
+    if (!rows || rs.n < 1 || rs.n > kMaxBatch || rs.F < 2 || rs.F > kCloudMaxLevels || rs.s < 0 || rs.s >= rs.F) return false;
+    if (rs.fw < 1 || rs.fh < 1 || rs.w[rs.F - 1] != rs.fw || rs.h[rs.F - 1] != rs.fh || rs.w[0] != rs.W || rs.h[0] != rs.H) return false;
+    if (!rs.table && rs.n > kRestrictStackByValue) return false;
+    for (int e = 0; e < rs.n; e++) {
+        const RestrictStackRow &r = rows[e];
+        for (int k = rs.s; k < rs.F; k++)
+            if (r.nox[k] < 0 || r.noy[k] < 0 || r.nox[k] + rs.fw > rs.w[k] || r.noy[k] + rs.fh > rs.h[k]) return false;
+        for (int l = 0; !rs.field && l < rs.F - 1; l++)
+            if (r.pox[l] < 0 || r.poy[l] < 0 || r.pox[l] + rs.fw > rs.w[l] || r.poy[l] + rs.fh > rs.h[l]) return false;
+        if (!rs.table) rs.rows[e] = r;
+    }
+    const dim3 grid((rs.fw + 255) / 256, rs.fh, rs.n * (rs.F - rs.s));
+    if (rs.table) UGSM_LAUNCH(k_upsample_paste<true>, grid, dim3(256), 0, st, prior0, stack0, work0, rs);
+    else UGSM_LAUNCH(k_upsample_paste<false>, grid, dim3(256), 0, st, prior0, stack0, work0, rs);
+    return true;
 }
 
 // =========================================================================================

@@ -203,6 +203,33 @@ struct PasteWindows {
 };
 void launch_upsample_paste_multi(hipStream_t st, const float *src3, int W, int H, float *dst3, int W2, int H2, const float *fov0, size_t fov_plane,
                                  int fovW, int fovH, const PasteWindows &pw);
+// The POINTWISE form of the same kernel (k_restrict_stack in the statistics; the warm foveated call, ugsm_submit_foveated_warm): the starting
+// fields of the fovea levels s .. F-1 of n entries from a prior each, in ONE launch, grid.z = entry x (F - s) + (level - s).  The field of
+// level k is the fw x fh crop, at the NEW window's origin at level k, of the restriction (RestrictMap, above) to level k of the full-resolution
+// field that ugsm_reconstruct_full gives for the prior stack -- computed per target pixel: the pixel's level-0 site, then the paste rule
+// descended from level 0 of the prior stack until a level's window holds the site (level F-1 holds every site), then as many multiplications
+// by (float)1.41421356 as levels were descended.  Neither the full-resolution field nor its restriction is ever formed.
+// A row = one entry: where its prior and its destinations lie (BYTES relative to the launch's pointers) and the two windows' origins.
+// field != 0: the priors are full-resolution fields (3 planes of W x H) and the descent has depth zero; pox / poy are not read.
+// Destinations: level k > s, and level s where work0 is null, go to row block k of the entry's stack (3 planes of F x fh x fw) at stack0 + dst;
+// with work0, level s goes to the 3 dense planes of fw x fh at work0 + work (the level buffer the matching starts in).
+// Up to kRestrictStackByValue rows travel in the kernel arguments (sixteen do not fit there); more are read from `table`, n rows in DEVICE memory.
+struct RestrictStackRow {
+    long long prior, dst, work;
+    int nox[kCloudMaxLevels], noy[kCloudMaxLevels];  // the new window's origin at level k (k = F-1: 0, the whole level)
+    int pox[kCloudMaxLevels], poy[kCloudMaxLevels];  // the prior's window at level l < F-1
+};
+constexpr int kRestrictStackByValue = 2;
+struct RestrictStack {
+    int n, F, s, field;
+    int W, H, fw, fh;
+    int w[kCloudMaxLevels], h[kCloudMaxLevels];  // the sizes of the levels 0 .. F-1 (w[F-1] x h[F-1] = fw x fh)
+    const RestrictStackRow *table;               // null: rows[] below
+    RestrictStackRow rows[kRestrictStackByValue];
+};
+// rows: the n rows in HOST memory -- checked here, and copied into the arguments where rs.table is null (rs.rows is the launcher's to fill).
+// False (nothing launched): a shape the kernel's bounds do not cover (a window that leaves its level, more rows by value than there is room for).
+bool launch_restrict_stack(hipStream_t st, const float *prior0, float *stack0, float *work0, RestrictStack rs, const RestrictStackRow *rows);
 // S_dx, S_dy, C of weightedDifference (MatchGPULib.cpp:1336-1437) into out3; rowsum = 3*H doubles of scratch
 void launch_weighted_difference(hipStream_t st, const float *newd3, const float *oldd3, int W, int H, double *rowsum, double *out3);
 // MatchGPULib::warpRightImage (MatchGPULib.cpp:1445-1518, kernel warpAbyB MatchLib.cu:499-549) -- the warp form of k_rgb_planes:

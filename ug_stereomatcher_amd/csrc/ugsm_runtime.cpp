@@ -29,8 +29,8 @@ using namespace ugsm;
 namespace {
 const char *kClassName[2][KC_COUNT] = {
     {"k_cost_split", "k_smooth_fused", "k_sqblur_tiled", "k_blur_decimate_tiled", "k_seed", "-", "-", "misc", "k_cost_march", "k_pyr_base", "k_cost_small",
-     "k_smooth_small", "k_cost_march4", "k_level0_windows", "k_restrict"},
-    {"k_cost_ref", "k_smooth_pass", "k_sqblur_clamp", "k_blur_decimate", "k_seed", "k_warp", "k_box", "misc", "-", "-", "-", "-", "-", "-", "k_restrict"}};
+     "k_smooth_small", "k_cost_march4", "k_level0_windows", "k_restrict", "k_restrict_stack"},
+    {"k_cost_ref", "k_smooth_pass", "k_sqblur_clamp", "k_blur_decimate", "k_seed", "k_warp", "k_box", "misc", "-", "-", "-", "-", "-", "-", "k_restrict", "k_restrict_stack"}};
 }  // namespace
 
 namespace ugsm {
@@ -1264,18 +1264,22 @@ int enqueue_fovea_coarse(ugsm_ctx *ctx, Slot &s, int si, const Shape &sh, float 
 // The fine phase for the sh.nb entries of the call: per-entry states and stacks (sh.nb of each), and sh.nreal window offsets and pyramid-stack
 // destinations (d_pyrL / d_pyrR may be null, and so may their entries): an exchanged entry of a shape of both directions has its twin's window,
 // and the pyramid stacks are the real pairs'.
+// first (the warm call, ugsm_submit_foveated_warm; < 0: none): the levels first .. 0 only, from starting fields that the caller's launch has
+// put where d_state is otherwise copied to -- s.d0, entry b at + b * sh.stride --: d_state is not read, the row blocks above `first` are the
+// caller's, and level `first` takes no seed.  first == F-1: the whole level F-1 is matched first, as the last level of the coarse phase is but
+// never as a top level (a prior has a confidence), and its block follows.
 int enqueue_fovea_fine(ugsm_ctx *ctx, Slot &s, int si, const Shape &sh, const float *const *d_state, const int *off_x, const int *off_y,
-                       float *const *d_stack, float *const *d_pyrL, float *const *d_pyrR)
+                       float *const *d_stack, float *const *d_pyrL, float *const *d_pyrR, int first = -1)
 {
     const int levels = s.levels, F = ctx->cfg.fovea_levels, nb = sh.nb;
-    if (F < 2 || F > levels) return UGSM_ERR_BAD_ARG;
+    if (F < 2 || F > levels || first >= F) return UGSM_ERR_BAD_ARG;
     FoveaGeom g[2 * kMaxBatch];
     for (int b = 0; b < nb; b++) fovea_geometry(s.w, s.h, F, off_x[b % sh.nreal], off_y[b % sh.nreal], g[b]);
     const int fw = g[0].fw, fh = g[0].fh;
     const size_t fn = (size_t)fw * fh;
     const int np = launch_pairs(ctx, sh, fw, fh);  // (every level of the fine phase is a window of this size)
     float *cur = s.d0, *other = s.d1;
-    for (int b = 0; b < nb; b++)
+    for (int b = 0; first < 0 && b < nb; b++)
         HIPCHK(ctx, hipMemcpyAsync(cur + b * sh.stride, d_state[b], sizeof(float) * 3 * fn, hipMemcpyDeviceToDevice, s.st));
     // a stack row block / a pyramid-stack block for every entry: one launch for the batch
     auto copy_out = [&](int pairs, const Img3 *views, const float *field, float *const *dsts, size_t dst_off, size_t dst_plane) {
@@ -1286,16 +1290,17 @@ int enqueue_fovea_fine(ugsm_ctx *ctx, Slot &s, int si, const Shape &sh, const fl
         });
     };
     // stack row block F-1 = the whole level F-1 (UG_GPU_matcher.cpp:293-303)
-    copy_out(nb, nullptr, cur, d_stack, (size_t)(F - 1) * fn, (size_t)F * fn);
+    if (first < 0) copy_out(nb, nullptr, cur, d_stack, (size_t)(F - 1) * fn, (size_t)F * fn);
     SeedMap sm[2 * kMaxBatch];
     Img3 Lv[2 * kMaxBatch], Rv[2 * kMaxBatch];
-    for (int i = F - 2; i >= 0; i--) {
+    for (int i = first < 0 ? F - 2 : first; i >= 0; i--) {
         s.cur_level = i;
         for (int b = 0; b < nb; b++) {
-            Lv[b] = level_view(s, pair_pyr(s, sh, 0, b), i, g[b].ox[i], g[b].oy[i]);
-            Rv[b] = level_view(s, pair_pyr(s, sh, 1, b), i, g[b].ox[i], g[b].oy[i]);
+            const int ox = i < F - 1 ? g[b].ox[i] : 0, oy = i < F - 1 ? g[b].oy[i] : 0;
+            Lv[b] = level_view(s, pair_pyr(s, sh, 0, b), i, ox, oy);
+            Rv[b] = level_view(s, pair_pyr(s, sh, 1, b), i, ox, oy);
         }
-        const bool seeded = hand_seed(ctx, s, si, sh, fw, fh, fw, fh, g, i, sm, cur, other);
+        const bool seeded = i != first && hand_seed(ctx, s, si, sh, fw, fh, fw, fh, g, i, sm, cur, other);
         const int mi = level_iterations(i);
         UCHK(run_level(ctx, s, si, sh, Lv, Rv, fw, fh, mi, level_smooth(i), false, 1, mi, cur, other, nullptr, nullptr, seeded ? sm : nullptr));
         copy_out(nb, nullptr, cur, d_stack, (size_t)i * fn, (size_t)F * fn);
@@ -1470,6 +1475,108 @@ int ugsm::seeded_submit(ugsm_ctx *ctx, int slot, int n, const uint8_t *const *d_
     const int per = batch_runs_pair_by_pair(ctx) ? 1 : n;  // (kernel_path 1: the pairs one after the other, as ugsm_submit_full_batch)
     for (int b = 0; b < n; b += per)
         UCHK(enqueue_match_full_seeded(ctx, *s, slot, per, d_rgbL + b, d_rgbR + b, W, H, stride, d_prior + b, start_level, d_out + b));
+    return mark_done(ctx, *s);
+}
+namespace {
+// The starting fields of the fovea levels start .. F-1 of n entries from their priors, one launch (launch_restrict_stack): the rows from the
+// two windows' geometries; up to kRestrictStackByValue of them in the launch's arguments, more through the slot's table.  Level `start` goes
+// to `work` (entry b at + b * work_stride floats) where that is given, everything else to the row blocks of d_stack.
+int enqueue_restrict_stack(ugsm_ctx *ctx, Slot &s, int si, int n, const int *w, const int *h, int F, const float *const *prior, const int *poff_x,
+                           const int *poff_y, bool field, const int *off_x, const int *off_y, int start, float *const *d_stack, float *work, size_t work_stride)
+{
+    RestrictStack rs{};
+    rs.n = n;
+    rs.F = F;
+    rs.s = start;
+    rs.field = field ? 1 : 0;
+    rs.W = w[0];
+    rs.H = h[0];
+    rs.fw = w[F - 1];
+    rs.fh = h[F - 1];
+    for (int l = 0; l < F; l++) {
+        rs.w[l] = w[l];
+        rs.h[l] = h[l];
+    }
+    RestrictStackRow local[kRestrictStackByValue], *rows = local;
+    const bool table = n > kRestrictStackByValue;
+    int turn = 0;
+    if (table) {
+        UCHK(grow(ctx, s.warm_tab, s.warm_tab_cap, (size_t)kMaxBatch));
+        if (!s.warm_tab_h) HIPCHK(ctx, hipHostMalloc((void **)&s.warm_tab_h, Slot::kWarmRing * kMaxBatch * sizeof(RestrictStackRow), hipHostMallocDefault));
+        turn = s.warm_next;
+        s.warm_next = (turn + 1) % Slot::kWarmRing;
+        if (!s.warm_ev[turn]) HIPCHK(ctx, hipEventCreateWithFlags(&s.warm_ev[turn], hipEventDisableTiming));
+        if (s.warm_ev_set[turn]) HIPCHK(ctx, hipEventSynchronize(s.warm_ev[turn]));  // (the upload of the call kWarmRing back: long done)
+        rows = s.warm_tab_h + (size_t)turn * kMaxBatch;
+    }
+    for (int b = 0; b < n; b++) {
+        FoveaGeom gn, gp;
+        fovea_geometry(w, h, F, off_x ? off_x[b] : 0, off_y ? off_y[b] : 0, gn);
+        if (!field) fovea_geometry(w, h, F, poff_x ? poff_x[b] : 0, poff_y ? poff_y[b] : 0, gp);
+        RestrictStackRow &r = rows[b];
+        r = RestrictStackRow{};
+        r.prior = byte_diff(prior[b], prior[0]);
+        r.dst = byte_diff(d_stack[b], d_stack[0]);
+        r.work = (long long)(b * work_stride * sizeof(float));
+        for (int l = 0; l < F - 1; l++) {
+            r.nox[l] = gn.ox[l];
+            r.noy[l] = gn.oy[l];
+            r.pox[l] = field ? 0 : gp.ox[l];
+            r.poy[l] = field ? 0 : gp.oy[l];
+        }
+    }
+    if (table) {
+        HIPCHK(ctx, hipMemcpyAsync(s.warm_tab, rows, (size_t)n * sizeof(RestrictStackRow), hipMemcpyHostToDevice, s.st));
+        HIPCHK(ctx, hipEventRecord(s.warm_ev[turn], s.st));
+        s.warm_ev_set[turn] = true;
+        rs.table = s.warm_tab;
+    }
+    s.cur_level = start;
+    bool ok;
+    {
+        Timer t(ctx, &s, si, KC_RESTRICT_STACK, (double)n * (F - start) * rs.fw * rs.fh);
+        ok = launch_restrict_stack(s.st, prior[0], d_stack[0], work, rs, rows);
+    }
+    s.cur_level = kNoLevel;
+    if (!ok) return ctx_fail(ctx, UGSM_ERR_STATE, "the warm foveated call: a window that leaves its level");
+    HIPCHK(ctx, hipGetLastError());
+    return UGSM_OK;
+}
+
+// The warm foveated call (ugsm_submit_foveated_warm[_field]; its refusals: ugsm_fovea_seeded.cpp): n pairs in lockstep from fovea level `start`
+// of their priors.  The pyramids stop at level max(start, 2), level 0 inside the new windows; A is computed in line at every level (level F-1,
+// where it is matched, included: the side stream's A planes serve the coarse phase, which does not run).  One launch writes every starting
+// field: level `start`'s into the level buffer the fine phase starts in, the levels above into the stacks' row blocks.
+int enqueue_match_foveated_warm(ugsm_ctx *ctx, Slot &s, int si, int n, const uint8_t *const *d_rgbL, const uint8_t *const *d_rgbR, int W, int H, int stride,
+                                const int *off_x, const int *off_y, const float *const *d_prior, const int *poff_x, const int *poff_y, bool field, int start,
+                                float *const *d_stack)
+{
+    const int F = ctx->cfg.fovea_levels;
+    FoveaWin win;
+    UCHK(fovea_windows(ctx, W, H, n, off_x, off_y, win));
+    UCHK(enqueue_pyramids(ctx, s, si, d_rgbL, d_rgbR, n, W, H, stride, -1, &win, false, 0, start));
+    s.have_coarse = false;
+    s.lr_ran = false;
+    s.lr_fov_pairs = 0;
+    s.lr_full_pairs = 0;
+    const Shape sh = Shape::pairs(s);
+    UCHK(enqueue_restrict_stack(ctx, s, si, n, s.w, s.h, F, d_prior, poff_x, poff_y, field, off_x, off_y, start, d_stack, s.d0, sh.stride));
+    return enqueue_fovea_fine(ctx, s, si, sh, nullptr, off_x, off_y, d_stack, nullptr, nullptr, start);
+}
+}  // namespace
+int ugsm::fovea_warm_submit(ugsm_ctx *ctx, int slot, int n, const uint8_t *const *d_rgbL, const uint8_t *const *d_rgbR, int W, int H, int stride, const int *off_x,
+                            const int *off_y, const float *const *d_prior, const int *prior_off_x, const int *prior_off_y, int field, int start_level,
+                            float *const *d_stack)
+{
+    Slot *s;
+    UCHK(get_slot(ctx, slot, &s));
+    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
+    const int zeros[UGSM_MAX_BATCH] = {0};
+    const int *ox = off_x ? off_x : zeros, *oy = off_y ? off_y : zeros, *px = prior_off_x ? prior_off_x : zeros, *py = prior_off_y ? prior_off_y : zeros;
+    const int per = (n == 1 || fovea_batch_runs_pair_by_pair(ctx)) ? 1 : n;  // (kernel_path 1: the pairs one after the other, as ugsm_submit_foveated_batch)
+    for (int b = 0; b < n; b += per)
+        UCHK(enqueue_match_foveated_warm(ctx, *s, slot, per, d_rgbL + b, d_rgbR + b, W, H, stride, ox + b, oy + b, d_prior + b, px + b, py + b, field != 0,
+                                         start_level, d_stack + b));
     return mark_done(ctx, *s);
 }
 namespace {
@@ -2019,6 +2126,10 @@ void ugsm_destroy(ugsm_ctx *ctx)
         if (s.lr) (void)hipFree(s.lr);
         s.cloud.release();
         if (s.lr_host) (void)hipHostFree(s.lr_host);
+        if (s.warm_tab) (void)hipFree(s.warm_tab);
+        if (s.warm_tab_h) (void)hipHostFree(s.warm_tab_h);
+        for (hipEvent_t e : s.warm_ev)
+            if (e) (void)hipEventDestroy(e);
         if (s.st2 && s.owns_st2) (void)hipStreamDestroy(s.st2);
         if (s.st && s.owns_st) (void)hipStreamDestroy(s.st);
         if (s.ev_done) (void)hipEventDestroy(s.ev_done);
@@ -2476,6 +2587,33 @@ int ugsm::seeded_match(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, 
 {
     return drained(ctx, 0, seeded_match_on_slot0(ctx, rgbL, rgbR, W, H, stride, prior, start_level, disp));
 }
+// The warm foveated service call (ugsm_match_foveated_warm; its refusals: ugsm_fovea_seeded.cpp) on slot 0: images and the prior stack's three
+// planes up, the match into a second stack beside it in the slot's result staging (the call is not in place), that stack's planes down.
+static int fovea_warm_match_on_slot0(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, int off_x, int off_y,
+                                     const float *const prior[3], int prior_off_x, int prior_off_y, int start_level, float *const stack[3])
+{
+    Slot *s;
+    UCHK(get_slot(ctx, 0, &s));
+    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
+    int fw, fh;
+    UCHK(ugsm_fovea_dims(W, H, ctx->cfg.levels, ctx->cfg.fovea_levels, &fw, &fh));
+    UCHK(stage_in(ctx, *s, rgbL, rgbR, W, H, stride));
+    const size_t stackn = (size_t)ctx->cfg.fovea_levels * fw * fh;
+    UCHK(grow(ctx, s->hout, s->hout_cap, 6 * stackn));  // [prior 3 stackn][stack 3 stackn]
+    for (int c = 0; c < 3; c++) HIPCHK(ctx, hipMemcpyAsync(s->hout + c * stackn, prior[c], stackn * sizeof(float), hipMemcpyHostToDevice, s->st));
+    const uint8_t *const dL = s->rgbL, *const dR = s->rgbR;
+    const float *const d_prior = s->hout;
+    float *const d_stack = s->hout + 3 * stackn;
+    UCHK(enqueue_match_foveated_warm(ctx, *s, 0, 1, &dL, &dR, W, H, stride, &off_x, &off_y, &d_prior, &prior_off_x, &prior_off_y, false, start_level, &d_stack));
+    for (int c = 0; c < 3; c++) HIPCHK(ctx, hipMemcpyAsync(stack[c], d_stack + c * stackn, stackn * sizeof(float), hipMemcpyDeviceToHost, s->st));
+    s->forked = false;  // (enqueued whole, as mark_done)
+    return ugsm_wait(ctx, 0);
+}
+int ugsm::fovea_warm_match(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, int off_x, int off_y, const float *const prior[3],
+                           int prior_off_x, int prior_off_y, int start_level, float *const stack[3])
+{
+    return drained(ctx, 0, fovea_warm_match_on_slot0(ctx, rgbL, rgbR, W, H, stride, off_x, off_y, prior, prior_off_x, prior_off_y, start_level, stack));
+}
 extern "C" {
 
 int ugsm_submit_full_host(ugsm_ctx *ctx, int slot, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, float *dispH,
@@ -2778,6 +2916,20 @@ int ugsm_stage_restrict(ugsm_ctx *ctx, const float *d_src3, int W, int H, int le
     HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
     launch_restrict(s->st, d_src3, W, H, level, d_dst3, w[level], h[level]);
     HIPCHK(ctx, hipGetLastError());
+    return ugsm_wait(ctx, 0);
+}
+
+int ugsm_stage_warm_stack(ugsm_ctx *ctx, const float *d_prior_stack, int W, int H, int prior_off_x, int prior_off_y, int off_x, int off_y, int start_level,
+                          float *d_dst_stack)
+{
+    Slot *s;
+    UCHK(get_slot(ctx, 0, &s));
+    const int F = ctx->cfg.fovea_levels;
+    if (!d_prior_stack || !d_dst_stack || d_prior_stack == d_dst_stack || F < 2 || F > ctx->cfg.levels || start_level < 0 || start_level >= F) return UGSM_ERR_BAD_ARG;
+    int w[UGSM_MAX_LEVELS], h[UGSM_MAX_LEVELS];
+    UCHK(level_dims(W, H, ctx->cfg.levels, w, h));
+    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
+    UCHK(enqueue_restrict_stack(ctx, *s, 0, 1, w, h, F, &d_prior_stack, &prior_off_x, &prior_off_y, false, &off_x, &off_y, start_level, &d_dst_stack, nullptr, 0));
     return ugsm_wait(ctx, 0);
 }
 

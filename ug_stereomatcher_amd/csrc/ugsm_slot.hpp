@@ -17,7 +17,7 @@ namespace ugsm {
 
 constexpr double kScale = 1.41421356;  // MatchLib_common.h:15
 enum KClass { KC_COST = 0, KC_SMOOTH, KC_SQBLUR, KC_PYR, KC_SEED, KC_WARP, KC_BOX, KC_MISC, KC_COST_MARCH, KC_PYR_BASE, KC_COST_SMALL, KC_SMOOTH_SMALL, KC_COST_MARCH4,
-              KC_LEVEL0_WIN, KC_RESTRICT, KC_COUNT };
+              KC_LEVEL0_WIN, KC_RESTRICT, KC_RESTRICT_STACK, KC_COUNT };
 constexpr int kNoLevel = UGSM_MAX_LEVELS;  // stats cell of launches that belong to no pyramid level
 struct StatCell {
     long long launches = 0;
@@ -144,6 +144,15 @@ struct Slot {
     const uint8_t *img0L[kMaxBatch] = {}, *img0R[kMaxBatch] = {};
     int img0_stride = 0;
     bool have_coarse = false;
+    // The warm foveated call (ugsm_submit_foveated_warm) with more entries than travel in its launch's arguments: their rows in device memory
+    // (kMaxBatch of them) and the page-locked copies they are uploaded from on the slot's stream, allocated by the first such call.  The call
+    // does not wait for the stream, so kWarmRing copies take turns, each with an event behind its upload, as SlotCloud::mc_tab_h.
+    static constexpr int kWarmRing = 4;
+    RestrictStackRow *warm_tab = nullptr, *warm_tab_h = nullptr;
+    size_t warm_tab_cap = 0;
+    hipEvent_t warm_ev[kWarmRing] = {};
+    bool warm_ev_set[kWarmRing] = {};
+    int warm_next = 0;
     bool range_known = false;
     int cur_level = kNoLevel;  // pyramid level the launches being enqueued belong to (statistics only)  // range_bad describes the images the next run_level works on
     std::vector<EvRec> pending;

@@ -179,6 +179,23 @@ class MatchGPULib:
         """Returns float32 (foveatelevel, 3, fovH, fovW): [level][dx|dy|conf]."""
         return self._stack(cv_ptrL, cv_ptrR, False, off_x, off_y)[0]
 
+    def matchStackSeeded(self, cv_ptrL, cv_ptrR, prior_stack, prior_off, off, start_level: int) -> np.ndarray:
+        """(not in the reference) matchStack(L, R, *off) started at fovea level start_level from `prior_stack` -- what matchStack returned for
+        the previous frame at the offsets `prior_off`, which may differ from `off` -- instead of from the zero seed at the top level
+        (ugsm_match_foveated_warm).  Returns float32 (foveatelevel, 3, fovH, fovW); the levels above start_level are the prior carried over."""
+        L, R = _as_rgb8(cv_ptrL), _as_rgb8(cv_ptrR)
+        if L.shape != R.shape or L.strides[0] != R.strides[0]:
+            raise UgsmError(_lib.UGSM_ERR_SIZE_MISMATCH, "left/right images differ in size")
+        rows, cols = L.shape[:2]
+        F = self.foveatelevel
+        fw, fh = _lib.fovea_dims(cols, rows, self._levels, F)
+        prior = np.asarray(prior_stack, np.float32)
+        if prior.shape != (F, 3, fh, fw):
+            raise UgsmError(_lib.UGSM_ERR_SIZE_MISMATCH, "the prior is a stack as matchStack returns it: (foveatelevel, 3, fovH, fovW)")
+        self.fovW, self.fovH = fw, fh
+        stack = self._ctx.match_foveated_warm(L, R, np.ascontiguousarray(prior.transpose(1, 0, 2, 3)), prior_off, off, start_level)
+        return np.ascontiguousarray(stack.transpose(1, 0, 2, 3))
+
     # -- several windows of one pair (not in the reference; include/ugsm.h, "several fovea windows on ONE pair") --
     def matchStackMulti(self, cv_ptrL, cv_ptrR, offsets, tau=None):
         """matchStack for every (off_x, off_y) of `offsets` (1 .. 16) in one call -- pyramids and the coarse levels once, the windows' fine
