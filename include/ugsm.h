@@ -42,7 +42,9 @@ extern "C" {
                                ugsm_photometric_residual_fovea; the checked full-mode call -- ugsm_submit_full_checked, ugsm_match_full_checked,
                                ugsm_last_lr_marked_pair; the seeded full-mode call -- ugsm_submit_full_seeded, ugsm_match_full_seeded,
                                ugsm_stage_restrict, ugsm_seeded_pixel_iterations; the seeded (warm) foveated call -- ugsm_submit_foveated_warm,
-                               ugsm_submit_foveated_warm_field, ugsm_match_foveated_warm, ugsm_stage_warm_stack, ugsm_fovea_warm_pixel_iterations
+                               ugsm_submit_foveated_warm_field, ugsm_match_foveated_warm, ugsm_stage_warm_stack, ugsm_fovea_warm_pixel_iterations;
+                               the full-mode call in two halves -- ugsm_submit_full_coarse, ugsm_submit_full_fine, ugsm_match_full_coarse,
+                               ugsm_match_full_fine, ugsm_stage_prolong, ugsm_coarse_pixel_iterations
                                6: the kernel choices follow what is in flight, not ugsm_config.slots: ugsm_plan_level takes `alone`, ugsm_plan_level_in_frame
                                is gone, ugsm_level_plan.latency_policy is .alone; ugsm_enqueue_* returns UGSM_OK once the pair is accepted (a failed
                                CALL is reported through ugsm_completion.status only); the fovea shard carries a status word (a rank that fails still
@@ -166,6 +168,9 @@ int ugsm_fovea_dims(int W, int H, int levels, int fovea_levels, int *fovW, int *
 long long ugsm_pixel_iterations(int W, int H, int levels, int fovea_levels);
 /* The same for a seeded full-mode call (ugsm_submit_full_seeded): the levels start_level .. 0 only.  -1 for a size or a level that does not exist. */
 long long ugsm_seeded_pixel_iterations(int W, int H, int levels, int start_level);
+/* The same for the coarse half of a full-mode call (ugsm_submit_full_coarse): the levels stop_level .. levels - 1 only.  -1 for a size or a level
+ * that does not exist.  For every e >= 1: ugsm_coarse_pixel_iterations(.., e) + ugsm_seeded_pixel_iterations(.., e - 1) is the whole call's. */
+long long ugsm_coarse_pixel_iterations(int W, int H, int levels, int stop_level);
 /* ... and for a warm foveated call (ugsm_submit_foveated_warm): fovW x fovH x the iterations of the levels start_level .. 0.  -1 likewise. */
 long long ugsm_fovea_warm_pixel_iterations(int W, int H, int levels, int fovea_levels, int start_level);
 
@@ -442,6 +447,61 @@ int ugsm_submit_foveated_warm_field(ugsm_ctx *ctx, int slot, int n, const uint8_
 int ugsm_match_foveated_warm(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, int off_x, int off_y,
                              const float *priorH, const float *priorV, const float *priorC, int prior_off_x, int prior_off_y, int start_level,
                              float *stackH, float *stackV, float *stackC);
+/* The full-mode call in TWO HALVES: stop at level e, resume from its field -- for a host that wants a field at reduced resolution from
+ * full-resolution images (a preview, an obstacle map, a fovea controller that decides where to look) and, perhaps later, the full one without
+ * starting again at the top level.  The levels 6 .. 13 hold 8 % of a call's pixel-iterations and most of its launches, the levels 0 and 1
+ * about half of its work.  Below: w[], h[] by ugsm_level_dims, top = levels - 1.
+ * The contract, bit for bit: coarse(e) followed by fine(e) is ugsm_submit_full.
+ *
+ * COARSE.  n pairs (1 <= n <= UGSM_MAX_BATCH, all W x H); d_rgbL, d_rgbR, d_state, d_full: HOST arrays of n DEVICE pointers.
+ *   d_state[k]  receives three planes (dx, dy, conf) of w[e] x h[e], e = stop_level (0 .. top): the field of level e after matchlevel on the
+ *               levels top .. e from the zero seed, subsampleDisp between them, the top level with its first-iteration exception -- what the
+ *               cold call holds in its level buffer when level e has finished.  stop_level = 0 is ugsm_submit_full_batch.
+ *   d_full      may be NULL, and so may any of its entries; where d_full[k] is given it receives three planes of W x H: the PROLONGATION of
+ *               d_state[k], P_0 of
+ *                   P_l[y][x] = (float)(1.41421356 * (double)P_l+1[tex(((float)y + 0.5f) * sf, h[l+1])][tex(((float)x + 0.5f) * sf, w[l+1])])
+ *               for l = e-1 .. 0, with P_e the state, sf = (float)(1 / 1.41421356) and tex the matcher's texture index (floor; NaN or negative:
+ *               0; clamped to n - 1) -- e steps of subsampleDisp without a crop (ugsm_stage_seed).  All three planes are scaled: the reference
+ *               scales the confidence too.  e = 0 is a copy.  Every level's own size takes part: the clamp binds at some levels (for 333
+ *               columns on the steps from the levels 0, 2, 3, 4, 7, 8, 10, 12) and there is no closed form.  A prolonged field is a W x H field
+ *               like any other: for the clouds, the warp, the residual, and for ugsm_submit_full_seeded as a prior.
+ * What runs: the pyramids as ugsm_submit_full_batch builds them; every launch of the levels top .. e is the one that call makes for these n
+ * pairs, lockstep grouping and a lone pair's A planes from the side stream included; no K-cost, K-smooth, A or seed launch at any level below e;
+ * ONE prolongation launch per call for all the pairs with a d_full entry (k_prolong in the kernel statistics, at level e, pairs x W x H
+ * pixel-launches; ugsm_stage_prolong runs it alone), which computes P_0 pointwise -- P_1 .. P_e-1 are never formed.  Any input format, captured
+ * at the call.  Nothing is written past the three planes of either output.
+ *
+ * FINE.  d_state[k]: a field of level e = state_level (1 .. top), three planes of w[e] x h[e]; d_out[k] receives the field reached by
+ * subsampleDisp of the state to level e - 1, then matchlevel on the levels e-1 .. 0 with their usual iteration and smoothing counts and
+ * subsampleDisp between them; no level takes the top level's exception.  With the d_state of ugsm_submit_full_coarse(.., e, ..) for the same
+ * pair on a context of the same `levels`, d_out[k] is bit for bit ugsm_submit_full's result -- for every e, however the n pairs are grouped,
+ * in any input format.  A state from anywhere else (another frame's, another process's, one the host wrote) is allowed: the definition says
+ * what comes out.
+ * What runs: the pyramid kernels build the levels 0 .. max(e - 1, 2) only, as the seeded call's; one device-to-device copy per pair places the
+ * state in the level buffer (at most 3 w[1] h[1] floats); the step to level e - 1 is the cold call's own -- fused into that level's first K-cost
+ * launch where the call fuses it, k_seed otherwise --; from level e - 1 down every launch is the full-mode batch call's, level 0 from the images
+ * where it reads them, its last smoothing launch writing d_out[k].  The state is read before anything of the call is written, on the slot's
+ * stream: a state that is the d_state of a coarse call enqueued just before on the same slot needs no wait in between.
+ *
+ * Status, all before anything is enqueued (a refused call writes nothing): null arrays, null entries of d_rgbL / d_rgbR / d_state / d_out,
+ * n outside 1 .. UGSM_MAX_BATCH, stop_level outside 0 .. top, state_level outside 1 .. top, contexts with early_exit_threshold > 0, a d_full[k]
+ * that overlaps any of the call's states: UGSM_ERR_BAD_ARG; UGSM_LR_FULL in force (ugsm_set_lr_check) or pairs outstanding in the queue:
+ * UGSM_ERR_STATE; the size errors of ugsm_submit_full as there.  kernel_path 1 (libugsm_dev.so) runs the pairs one after the other (and then
+ * one prolongation per pair).  What the halves cost, measured: DESIGN.md section 8, "The call in two halves".
+ * NOT built: a queue or managed form (ugsm_enqueue_*); the page-locked _host kind; a checked or seeded coarse call; the node's use of it;
+ * clouds straight from a level-sized state (prolong it first).
+ * Both asynchronous on `slot`. */
+int ugsm_submit_full_coarse(ugsm_ctx *ctx, int slot, int n, const uint8_t *const *d_rgbL, const uint8_t *const *d_rgbR,
+                            int W, int H, int stride, int stop_level, float *const *d_state, float *const *d_full);
+int ugsm_submit_full_fine(ugsm_ctx *ctx, int slot, int n, const uint8_t *const *d_rgbL, const uint8_t *const *d_rgbR,
+                          int W, int H, int stride, const float *const *d_state, int state_level, float *const *d_out);
+/* Blocking, one pair on slot 0, any host memory in and out, as ugsm_match_full.  state*: planes of w[e] x h[e]; fullH / fullV / fullC (planes
+ * of W x H, the prolongation): all three or none (NULL), anything else is UGSM_ERR_BAD_ARG. */
+int ugsm_match_full_coarse(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, int stop_level,
+                           float *stateH, float *stateV, float *stateC, float *fullH, float *fullV, float *fullC);
+int ugsm_match_full_fine(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride,
+                         const float *stateH, const float *stateV, const float *stateC, int state_level,
+                         float *dispH, float *dispV, float *dispC);
 /* ---- several fovea windows on ONE pair ------------------------------------------------------------------------------------------------
  *
  * A host that looks at n places of one frame (1 <= n <= UGSM_MAX_BATCH) needs the pyramids and the coarse phase -- levels top .. F-1, which
@@ -977,6 +1037,9 @@ int ugsm_stage_seed(ugsm_ctx *ctx, const float *d_src3, int W, int H, float *d_d
 /* The restriction of the seeded call (ugsm_submit_full_seeded) alone: level `level`'s starting field d_dst3 (3 planes of w x h, the level's
  * size by ugsm_level_dims with the context's levels) from the full-resolution field d_src3 (3 planes of W x H).  Not in place. */
 int ugsm_stage_restrict(ugsm_ctx *ctx, const float *d_src3, int W, int H, int level, float *d_dst3);
+/* The prolongation of the coarse half (ugsm_submit_full_coarse) alone: the full-resolution field d_dst3 (3 planes of W x H) from level `level`'s
+ * field d_src3 (3 planes of w x h, the level's size by ugsm_level_dims with the context's levels), one launch.  Not in place. */
+int ugsm_stage_prolong(ugsm_ctx *ctx, const float *d_src3, int W, int H, int level, float *d_dst3);
 /* The starting-field launch of the warm foveated call (ugsm_submit_foveated_warm) alone: row blocks start_level .. F-1 of d_dst_stack from the
  * stack d_prior_stack matched at (prior_off_x, prior_off_y), for a window at (off_x, off_y); the row blocks below are not written.  Not in place. */
 int ugsm_stage_warm_stack(ugsm_ctx *ctx, const float *d_prior_stack, int W, int H, int prior_off_x, int prior_off_y, int off_x, int off_y,

@@ -51,6 +51,7 @@ public:
         if (cfg.batch > 8) cfg.batch = 8;
         if (argc > 2) foveatelevel = std::atoi(argv[2]);
         cfg.fovea_levels = foveatelevel;
+        levels_ = cfg.levels;
         const int st = ugsm_create(&cfg, &ctx_);
         if (st != UGSM_OK) throw std::runtime_error(std::string("ugsm_create: ") + ugsm_status_string(st));
         if (lr_modes >= 0) {
@@ -159,6 +160,41 @@ public:
         float **fin = alloc_planes(3, (size_t)W * H);
         const int st = ugsm_match_full_seeded(ctx_, L->image.data, R->image.data, W, H, (int)L->image.step, prior[0], prior[1], prior[2], start_level,
                                               fin[0], fin[1], fin[2]);
+        if (st != UGSM_OK) return fail(fin, 3, st);
+        return fin;
+    }
+
+    // (not in the reference) match(L, R, 0) in two halves.  matchCoarse stops when level stop_level has finished and returns that level's field,
+    // state[3][h*w] of the level's own size (ugsm_level_dims) -- a field at reduced resolution from the full-resolution images; with `full` it also
+    // hands out the field's prolongation to the images' size, a finDisp (ugsm_match_full_coarse).  matchFine runs the rest from such a state
+    // (ugsm_match_full_fine): with matchCoarse's state of the same pair, match(L, R, 0)'s finDisp bit for bit.  The state stays the caller's.
+    template <class ImgPtr>
+    float **matchCoarse(ImgPtr L, ImgPtr R, int stop_level, float ***full = nullptr)
+    {
+        foveatedmatching = 0;
+        const int W = L->image.cols, H = L->image.rows;
+        int w[UGSM_MAX_LEVELS], h[UGSM_MAX_LEVELS];
+        if (full) *full = nullptr;
+        if (R->image.cols != W || R->image.rows != H || stop_level < 0 || stop_level >= levels_ || ugsm_level_dims(W, H, levels_, w, h) != UGSM_OK) return nullptr;
+        float **state = alloc_planes(3, (size_t)w[stop_level] * h[stop_level]), **fin = full ? alloc_planes(3, (size_t)W * H) : nullptr;
+        const int st = ugsm_match_full_coarse(ctx_, L->image.data, R->image.data, W, H, (int)L->image.step, stop_level, state[0], state[1], state[2],
+                                              fin ? fin[0] : nullptr, fin ? fin[1] : nullptr, fin ? fin[2] : nullptr);
+        if (st != UGSM_OK) {
+            if (fin) { for (int c = 0; c < 3; c++) std::free(fin[c]); std::free(fin); }
+            return fail(state, 3, st);
+        }
+        if (full) *full = fin;
+        return state;
+    }
+    template <class ImgPtr>
+    float **matchFine(ImgPtr L, ImgPtr R, float *const *state, int state_level)
+    {
+        foveatedmatching = 0;
+        const int W = L->image.cols, H = L->image.rows;
+        if (!state || R->image.cols != W || R->image.rows != H) return nullptr;
+        float **fin = alloc_planes(3, (size_t)W * H);
+        const int st = ugsm_match_full_fine(ctx_, L->image.data, R->image.data, W, H, (int)L->image.step, state[0], state[1], state[2], state_level,
+                                            fin[0], fin[1], fin[2]);
         if (st != UGSM_OK) return fail(fin, 3, st);
         return fin;
     }
@@ -356,6 +392,7 @@ public:
 
 private:
     ugsm_ctx *ctx_;
+    int levels_ = 0;  // the context's pyramid levels (matchCoarse / matchFine size a level's field by them)
     struct Kind { bool foveated, pyramids; int W, H; bool cloud; };
     std::map<uint64_t, Kind> kinds_;
     int report(int st)

@@ -159,6 +159,20 @@ int main(int argc, char **argv)
             for (float **p : {cold, s1, s2}) { for (int c = 0; c < 3; c++) free(p[c]); free(p); }
             if (differ) return 23;
         }
+        // matchCoarse(L, R, 5) then matchFine from its state: the cold match bit for bit; the prolongation has the images' size
+        {
+            float **cold = m.match(L, R, 0), **full = nullptr;
+            if (!cold) return 24;
+            float **state = m.matchCoarse(L, R, 5, &full);
+            if (!state || !full || m.matchCoarse(L, R, 14)) return 25;  // (level 14 does not exist: refused)
+            float **fin = m.matchFine(L, R, state, 5);
+            if (!fin || m.matchFine(L, R, state, 0)) return 26;         // (level 0 is no state: refused)
+            size_t differ = 0;
+            for (int c = 0; c < 3; c++) differ += std::memcmp(fin[c], cold[c], sizeof(float) * W * H) != 0;
+            std::printf("matchCoarse (level 5) + matchFine against match: %s\n", differ ? "DIFFER" : "identical");
+            for (float **p : {cold, full, state, fin}) { for (int c = 0; c < 3; c++) free(p[c]); free(p); }
+            if (differ) return 27;
+        }
         // matchStackSeeded(L, R, st, {0, 0}, {12, -8}, F - 1): the window moved by a few pixels, started at the top fovea level from the cold stack --
         // the same stack every time; a start level that does not exist is refused
         {

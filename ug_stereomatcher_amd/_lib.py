@@ -75,6 +75,8 @@ EXPORTS = [
     "ugsm_submit_full_seeded", "ugsm_match_full_seeded", "ugsm_stage_restrict", "ugsm_seeded_pixel_iterations",
     # the seeded (warm) foveated call
     "ugsm_submit_foveated_warm", "ugsm_submit_foveated_warm_field", "ugsm_match_foveated_warm", "ugsm_stage_warm_stack", "ugsm_fovea_warm_pixel_iterations",
+    # the full-mode call in two halves
+    "ugsm_submit_full_coarse", "ugsm_submit_full_fine", "ugsm_match_full_coarse", "ugsm_match_full_fine", "ugsm_stage_prolong", "ugsm_coarse_pixel_iterations",
 ]
 # ... and what include/ugsm_dev.h adds (libugsm_dev.so only)
 DEV_EXPORTS = ["ugsm_stage_poly_probe", "ugsm_stage_div3_probe", "ugsm_stage_div_probe", "ugsm_stage_range_words", "ugsm_stage_iterate_rgb8", "ugsm_stage_level0_direct"]
@@ -301,6 +303,13 @@ def load(dev: bool = False):
     lib.ugsm_stage_warm_stack.argtypes = [vp, vp, i, i, i, i, i, i, i, vp]
     lib.ugsm_fovea_warm_pixel_iterations.argtypes = [i, i, i, i, i]
     lib.ugsm_fovea_warm_pixel_iterations.restype = C.c_longlong
+    lib.ugsm_submit_full_coarse.argtypes = [vp, i, i, pp, pp, i, i, i, i, pp, pp]
+    lib.ugsm_submit_full_fine.argtypes = [vp, i, i, pp, pp, i, i, i, pp, i, pp]
+    lib.ugsm_match_full_coarse.argtypes = [vp, vp, vp, i, i, i, i, vp, vp, vp, vp, vp, vp]
+    lib.ugsm_match_full_fine.argtypes = [vp, vp, vp, i, i, i, vp, vp, vp, i, vp, vp, vp]
+    lib.ugsm_stage_prolong.argtypes = [vp, vp, i, i, i, vp]
+    lib.ugsm_coarse_pixel_iterations.argtypes = [i, i, i, i]
+    lib.ugsm_coarse_pixel_iterations.restype = C.c_longlong
     lib.ugsm_wait.argtypes = [vp, i]
     lib.ugsm_wait_all.argtypes = [vp]
     lib.ugsm_submit_pyramids.argtypes = [vp, i, vp, vp, i, i, i]
@@ -448,6 +457,11 @@ def pixel_iterations(W: int, H: int, levels: int = 14, fovea_levels: int = 0) ->
 def seeded_pixel_iterations(W: int, H: int, levels: int = 14, start_level: int = 0) -> int:
     """Sum of iterations x pixels over the levels start_level .. 0: what a seeded full-mode call runs (-1: no such size or level)."""
     return int(load().ugsm_seeded_pixel_iterations(W, H, levels, start_level))
+
+
+def coarse_pixel_iterations(W: int, H: int, levels: int = 14, stop_level: int = 0) -> int:
+    """Sum of iterations x pixels over the levels stop_level .. levels - 1: what the coarse half of a full-mode call runs (-1: no such size or level)."""
+    return int(load().ugsm_coarse_pixel_iterations(W, H, levels, stop_level))
 
 
 def fovea_warm_pixel_iterations(W: int, H: int, levels: int = 14, fovea_levels: int = 7, start_level: int = 0) -> int:
@@ -919,6 +933,61 @@ class Context:
         """The warm foveated call's starting-field launch alone (ugsm_stage_warm_stack): row blocks start_level .. F-1 of d_dst_stack; waits."""
         self.check(self.lib.ugsm_stage_warm_stack(self._h, d_prior_stack, W, H, int(prior_off[0]), int(prior_off[1]), int(off[0]), int(off[1]),
                                                   int(start_level), d_dst_stack))
+
+    def submit_full_coarse(self, slot: int, d_rgbL, d_rgbR, W: int, H: int, stride: int, stop_level: int, d_state, d_full=None):
+        """The coarse half of a full-mode call (ugsm_submit_full_coarse): the levels top .. stop_level; lists of device pointers, one entry per
+        pair.  d_state[k]: level stop_level's field; d_full (None, or a list whose entries may be None): its prolongation to W x H."""
+        n = len(d_rgbL)
+        if len(d_rgbR) != n or len(d_state) != n or (d_full is not None and len(d_full) != n):
+            raise UgsmError(UGSM_ERR_BAD_ARG, "one entry per pair in every list")
+        self.check(self.lib.ugsm_submit_full_coarse(self._h, slot, n, self._ptrs(d_rgbL), self._ptrs(d_rgbR), W, H, stride, int(stop_level),
+                                                    self._ptrs(d_state), self._ptrs(d_full) if d_full is not None else None))
+
+    def submit_full_fine(self, slot: int, d_rgbL, d_rgbR, W: int, H: int, stride: int, d_state, state_level: int, d_out):
+        """The fine half (ugsm_submit_full_fine): the levels state_level - 1 .. 0 from the pairs' fields of level state_level."""
+        n = len(d_rgbL)
+        if len(d_rgbR) != n or len(d_state) != n or len(d_out) != n:
+            raise UgsmError(UGSM_ERR_BAD_ARG, "one entry per pair in every list")
+        self.check(self.lib.ugsm_submit_full_fine(self._h, slot, n, self._ptrs(d_rgbL), self._ptrs(d_rgbR), W, H, stride, self._ptrs(d_state),
+                                                  int(state_level), self._ptrs(d_out)))
+
+    def stage_prolong(self, d_src3: int, W: int, H: int, level: int, d_dst3: int):
+        """The coarse half's prolongation alone (ugsm_stage_prolong): the W x H field of a field of level `level`; waits."""
+        self.check(self.lib.ugsm_stage_prolong(self._h, d_src3, W, H, int(level), d_dst3))
+
+    def match_full_coarse(self, L: np.ndarray, R: np.ndarray, stop_level: int, want_full: bool = False):
+        """Blocking, from any host memory (ugsm_match_full_coarse): level stop_level's (3, h, w) field; with want_full, (state, its (3, H, W)
+        prolongation)."""
+        W, H, stride = self.check_image(L)
+        if self.check_image(R) != (W, H, stride):
+            raise UgsmError(UGSM_ERR_SIZE_MISMATCH, "the two images differ in size or stride")
+        levels = int(self.cfg.levels)
+        if not 0 <= int(stop_level) < levels:
+            raise UgsmError(UGSM_ERR_BAD_ARG, "stop_level outside 0 .. levels - 1")
+        w, h = level_dims(W, H, levels)
+        state = np.empty((3, h[stop_level], w[stop_level]), np.float32)
+        full = np.empty((3, H, W), np.float32) if want_full else None
+        self.check(self.lib.ugsm_match_full_coarse(self._h, L.ctypes.data, R.ctypes.data, W, H, stride, int(stop_level),
+                                                   *[state[c].ctypes.data for c in range(3)],
+                                                   *[full[c].ctypes.data if want_full else None for c in range(3)]))
+        return (state, full) if want_full else state
+
+    def match_full_fine(self, L: np.ndarray, R: np.ndarray, state: np.ndarray, state_level: int) -> np.ndarray:
+        """Blocking, from any host memory (ugsm_match_full_fine): the (3, H, W) field reached from `state`, a (3, h, w) field of level state_level."""
+        W, H, stride = self.check_image(L)
+        if self.check_image(R) != (W, H, stride):
+            raise UgsmError(UGSM_ERR_SIZE_MISMATCH, "the two images differ in size or stride")
+        levels = int(self.cfg.levels)
+        if not 1 <= int(state_level) < levels:
+            raise UgsmError(UGSM_ERR_BAD_ARG, "state_level outside 1 .. levels - 1")
+        w, h = level_dims(W, H, levels)
+        if tuple(state.shape) != (3, h[state_level], w[state_level]):
+            raise UgsmError(UGSM_ERR_SIZE_MISMATCH, "the state is a (3, h, w) field of level state_level's size")
+        st = np.ascontiguousarray(state, np.float32)
+        out = np.empty((3, H, W), np.float32)
+        self.check(self.lib.ugsm_match_full_fine(self._h, L.ctypes.data, R.ctypes.data, W, H, stride, *[st[c].ctypes.data for c in range(3)],
+                                                 int(state_level), *[out[c].ctypes.data for c in range(3)]))
+        return out
 
     def submit_foveated_batch(self, slot: int, d_rgbL, d_rgbR, W: int, H: int, stride: int, offsets, d_stack, d_pyrL=None, d_pyrR=None):
         n = len(d_rgbL)

@@ -90,6 +90,17 @@ int fovea_warm_submit(ugsm_ctx *ctx, int slot, int n, const uint8_t *const *d_rg
                       float *const *d_stack);
 int fovea_warm_match(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, int off_x, int off_y, const float *const prior[3],
                      int prior_off_x, int prior_off_y, int start_level, float *const stack[3]);
+// The full-mode call in two halves behind its entry points (ugsm_coarse.cpp, which has refused what the calls refuse): n pairs enqueued on
+// `slot` -- the levels top .. stop_level into d_state, prolonged into the d_full entries that are set (d_full may be null); the levels
+// state_level - 1 .. 0 from d_state into d_out --; and the blocking calls on slot 0, their planes in host memory of any kind (full: null for none).
+int coarse_submit(ugsm_ctx *ctx, int slot, int n, const uint8_t *const *d_rgbL, const uint8_t *const *d_rgbR, int W, int H, int stride, int stop_level,
+                  float *const *d_state, float *const *d_full);
+int fine_submit(ugsm_ctx *ctx, int slot, int n, const uint8_t *const *d_rgbL, const uint8_t *const *d_rgbR, int W, int H, int stride,
+                const float *const *d_state, int state_level, float *const *d_out);
+int coarse_match(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, int stop_level, float *const state[3],
+                 float *const full[3]);
+int fine_match(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, const float *const state[3], int state_level,
+               float *const disp[3]);
 // the stagger of the queue's first round after idle and the size of every later call (ugsm.h, "the queue")
 int queue_target(int batch, int slots, long long calls_since_idle);
 

@@ -1,7 +1,8 @@
 // ugsm_kernels_aux.hip -- the plain per-pixel kernels around the matcher proper.
 //
 // k_seed (a level's starting field where the next level's K-cost does not seed itself; its restriction form: a level's starting field from a
-// full-resolution prior, the seeded full-mode call), k_copy_view (the fovea / pyramid stacks),
+// full-resolution prior, the seeded full-mode call), k_copy_view (the fovea / pyramid stacks; its prolongation form: a level's field at
+// full resolution in one launch, the coarse half of a full-mode call),
 // k_rgb_planes (level 0 of a pyramid of fewer than three levels: BASELINE configs[0]; its window form: level 0 inside the windows of a
 // multi-window foveated call), k_lr_check (the opt-in LR-consistency check),
 // k_triangulate[_fovea] (the X, Y, Z planes and, as other forms of the same kernels, the coloured point cloud),
@@ -94,6 +95,68 @@ __global__ void k_copy_view(Img3 src, int W, int H, float *__restrict__ dst, siz
     dst[(size_t)plane * dst_plane + (size_t)iy * dst_pitch + ix] = src.p[(size_t)plane * src.plane + (size_t)iy * src.pitch + ix];
 }
 
+// The prolongation form (k_prolong in the statistics; ugsm_submit_full_coarse, ugsm_stage_prolong -- DESIGN.md section 8): the field of level
+// e (pm.ws x pm.hs) at full resolution (pm.W x pm.H), pointwise.  By definition e steps of k_seed, P_l = k_seed(P_l+1) for l = e-1 .. 0 with
+// no crop; here P_1 .. P_e-1 are never formed: an output pixel walks its column down through the sizes w[1 .. e] -- tex_index(((float)c +
+// 0.5f) * sf, w[l]) at every level, whose clamp binds at some levels and not at others, so no closed form --, its row likewise (one site per
+// workgroup: blockIdx.y alone decides it), gathers the three planes' values there and multiplies each e times by SCALE in binary64, every
+// product rounded to binary32 on its own as the chain rounds it.  e = 0: a copy of a view, like the form above.
+// One thread does the three planes of four pixels, in 4 / V pieces of V consecutive pixels (V = pm.vec: 4, 2 or 1 -- what the rows'
+// alignment allows, prolong_vec), piece c of a workgroup's 1024 columns at (c * 256 + thread) * V: every store instruction of a wave covers
+// consecutive bytes, 16 per lane where V = 4.  The four columns walk down together, a level's size read once for them.  The source is read
+// about 2^e times per value, from L2; the launch is bound by the 3 W H floats it writes.  No LDS, no atomics.
+// (batched: blockIdx.z = pair; pair b's state at src3 + bt.in[b] bytes, its output at dst3 + bt.out[b] bytes -- moved as pointers, not
+// through integers as shifted() does: the accesses stay global ones)
+template <int V>
+__device__ __forceinline__ void prolong_row(const float *__restrict__ srow, const size_t splane, float *__restrict__ drow, const size_t dplane, const ProlongMap &pm)
+{
+    struct alignas(4 * V) Vec {
+        float v[V];
+    };
+    const float sf = (float)(1 / UGSM_SCALE);
+    int x[4], sx[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) sx[k] = x[k] = blockIdx.x * 1024 + ((k / V) * 256 + (int)threadIdx.x) * V + k % V;
+    for (int l = 1; l <= pm.e; l++) {
+        const int n = pm.w[l];
+#pragma unroll
+        for (int k = 0; k < 4; k++) sx[k] = tex_index(((float)sx[k] + 0.5f) * sf, n);
+    }
+#pragma unroll
+    for (int c = 0; c < 4 / V; c++) {
+        if (x[c * V] >= pm.W) return;  // (pm.W is a multiple of V: a piece lies inside the row or outside it)
+        Vec o[3];
+#pragma unroll
+        for (int j = 0; j < V; j++) {
+#pragma unroll
+            for (int p = 0; p < 3; p++) {
+                float v = srow[p * splane + sx[c * V + j]];
+                for (int l = 0; l < pm.e; l++) v = (float)(UGSM_SCALE * (double)v);
+                o[p].v[j] = v;
+            }
+        }
+#pragma unroll
+        for (int p = 0; p < 3; p++) *reinterpret_cast<Vec *>(drow + p * dplane + x[c * V]) = o[p];
+    }
+}
+__global__ __launch_bounds__(256) void k_copy_view(const float *__restrict__ src3, ProlongMap pm, float *__restrict__ dst3, Batch bt)
+{
+    if (bt.n > 1) {
+        src3 = reinterpret_cast<const float *>(reinterpret_cast<const char *>(src3) + bt.in[blockIdx.z]);
+        dst3 = reinterpret_cast<float *>(reinterpret_cast<char *>(dst3) + bt.out[blockIdx.z]);
+    }
+    const float sf = (float)(1 / UGSM_SCALE);
+    const int iy = blockIdx.y;
+    int sy = iy;
+    for (int l = 1; l <= pm.e; l++) sy = tex_index(((float)sy + 0.5f) * sf, pm.h[l]);
+    const size_t splane = (size_t)pm.ws * pm.hs, dplane = (size_t)pm.W * pm.H;
+    const float *srow = src3 + (size_t)sy * pm.ws;
+    float *drow = dst3 + (size_t)iy * pm.W;
+    if (pm.vec == 4) prolong_row<4>(srow, splane, drow, dplane, pm);
+    else if (pm.vec == 2) prolong_row<2>(srow, splane, drow, dplane, pm);
+    else prolong_row<1>(srow, splane, drow, dplane, pm);
+}
+
 void launch_seed(hipStream_t st, const float *src3, int Ws, int Hs, float *dst3, int Wd, int Hd, int cx, int cy, const Batch *bt)
 {
     Batch one{};
@@ -116,6 +179,37 @@ void launch_copy_view(hipStream_t st, Img3 src, int W, int H, float *dst, size_t
     one.n = 1;
     const Batch &B = bt ? *bt : one;
     UGSM_LAUNCH(k_copy_view, grid2(W, H, 3 * (B.n > 1 ? B.n : 1)), dim3(256), 0, st, src, W, H, dst, dst_plane, dst_pitch, B);
+}
+// the widest store every row of every plane of every pair's output is aligned for: 16 bytes, 8, or 4
+static int prolong_vec(const float *dst3, int W, const Batch &B)
+{
+    for (int v = 4; v > 1; v >>= 1) {
+        bool ok = W % v == 0 && reinterpret_cast<uintptr_t>(dst3) % (4 * v) == 0;
+        for (int b = 0; ok && b < B.n; b++) ok = B.out[b] % (4 * v) == 0;
+        if (ok) return v;
+    }
+    return 1;
+}
+bool launch_prolong(hipStream_t st, const float *src3, const int *w, const int *h, int level, float *dst3, const Batch *bt)
+{
+    Batch one{};
+    one.n = 1;
+    const Batch &B = bt ? *bt : one;
+    if (level < 0 || level >= kProlongMaxLevels || B.n > kMaxBatch || w[0] < 1 || h[0] < 1 || h[0] > 65535) return false;
+    ProlongMap pm{};
+    pm.W = w[0];
+    pm.H = h[0];
+    pm.ws = w[level];
+    pm.hs = h[level];
+    pm.e = level;
+    pm.vec = prolong_vec(dst3, w[0], B);
+    for (int l = 0; l <= level; l++) {
+        if (w[l] < 1 || h[l] < 1) return false;  // (tex_index clamps to n - 1: every read lies inside its level)
+        pm.w[l] = w[l];
+        pm.h[l] = h[l];
+    }
+    UGSM_LAUNCH(k_copy_view, dim3((w[0] + 1023) / 1024, h[0], B.n > 1 ? B.n : 1), dim3(256), 0, st, src3, pm, dst3, B);
+    return true;
 }
 // --------------------------------------------------------------------------------------
 // LR-consistency check (BASELINE.json north_star; the reference has none: SURVEY.md 0.4 -- the build's own definition, DESIGN.md

@@ -72,6 +72,17 @@ struct RestrictMap {
 };
 void launch_restrict(hipStream_t st, const float *src3, int W, int H, int level, float *dst3, int w, int h, const Batch *bt = nullptr);
 void launch_copy_view(hipStream_t st, Img3 src, int W, int H, float *dst, size_t dst_plane, int dst_pitch, const Batch *bt = nullptr);
+// The prolongation form of k_copy_view (ugsm_submit_full_coarse, ugsm_stage_prolong): the field src3 of level `level` (3 planes of w[level] x
+// h[level]) at full resolution in dst3 (3 planes of w[0] x h[0]), as `level` steps of k_seed give it, in one launch.  w, h: the sizes of the
+// levels 0 .. level (ugsm_level_dims); every level's own size takes part (its clamp).  Batched: pair b reads src3 + bt->in[b] bytes and
+// writes dst3 + bt->out[b] bytes.  False (nothing launched): a level or a size the kernel's bounds do not cover.
+constexpr int kProlongMaxLevels = 32;  // = UGSM_MAX_LEVELS (include/ugsm.h)
+struct ProlongMap {
+    int W, H, ws, hs;  // the output's size and the state's
+    int e, vec;        // the state's level; pixels per store: 4, 2 or 1, what every row's alignment allows
+    int w[kProlongMaxLevels], h[kProlongMaxLevels];  // the sizes of the levels 0 .. e
+};
+bool launch_prolong(hipStream_t st, const float *src3, const int *w, const int *h, int level, float *dst3, const Batch *bt = nullptr);
 // rgb8 -> planar float level 0 (MatchGPULib.cpp:332-338) where k_pyr_base does not apply: pyramids of fewer than three levels, kernel_path 1
 void launch_rgb_planes(hipStream_t st, const uint8_t *rgb, int stride, int W, int H, float *planes, int fmt = 0);
 // Level 0 of one pair inside n fovea windows of w x h level-0 pixels at (x0[k], y0[k]) -- the window form of k_rgb_planes, one launch for both

@@ -29,8 +29,8 @@ using namespace ugsm;
 namespace {
 const char *kClassName[2][KC_COUNT] = {
     {"k_cost_split", "k_smooth_fused", "k_sqblur_tiled", "k_blur_decimate_tiled", "k_seed", "-", "-", "misc", "k_cost_march", "k_pyr_base", "k_cost_small",
-     "k_smooth_small", "k_cost_march4", "k_level0_windows", "k_restrict", "k_restrict_stack"},
-    {"k_cost_ref", "k_smooth_pass", "k_sqblur_clamp", "k_blur_decimate", "k_seed", "k_warp", "k_box", "misc", "-", "-", "-", "-", "-", "-", "k_restrict", "k_restrict_stack"}};
+     "k_smooth_small", "k_cost_march4", "k_level0_windows", "k_restrict", "k_restrict_stack", "k_prolong"},
+    {"k_cost_ref", "k_smooth_pass", "k_sqblur_clamp", "k_blur_decimate", "k_seed", "k_warp", "k_box", "misc", "-", "-", "-", "-", "-", "-", "k_restrict", "k_restrict_stack", "k_prolong"}};
 }  // namespace
 
 namespace ugsm {
@@ -1041,13 +1041,24 @@ bool hand_seed(ugsm_ctx *ctx, Slot &s, int si, const Shape &sh, int Ws, int Hs, 
 // level `first` instead of from the zero seed at the top: the restriction (launch_restrict) fills level `first`'s fields where the zero seed
 // is otherwise set, the levels above run nothing, and level `first` is no top level -- its first iteration blends the confidence like any
 // other, a prior has one.  From there down everything is the same.
+// state (optional, instead of a prior; the fine half of a full-mode call, ugsm_submit_full_fine): the entries' fields of level `first` + 1, as
+// a descent that stopped there (`last`) left them.  They are placed in the level buffer and handed to level `first` by the cold call's own step
+// (hand_seed); the descent goes on at level `first` as if the levels above had just run.
 template <class Views>
 int enqueue_descent(ugsm_ctx *ctx, Slot &s, int si, const Shape &sh, int last, Views &&views, bool side_A, float *const *direct_out, float *&field,
-                    int first = -1, const float *const *prior = nullptr)
+                    int first = -1, const float *const *prior = nullptr, const float *const *state = nullptr)
 {
     float *cur = s.d0, *other = s.d1;
-    const int top = s.levels - 1, start = prior ? first : top;
-    if (prior) {
+    const int top = s.levels - 1, start = (prior || state) ? first : top;
+    SeedMap sm[2 * kMaxBatch];  // (a shape of both directions: two entries per pair)
+    bool seeded = false;
+    if (state) {
+        if (prior || start < last || start >= top) return UGSM_ERR_BAD_ARG;
+        s.cur_level = start + 1;
+        for (int b = 0; b < sh.nb; b++)
+            HIPCHK(ctx, hipMemcpyAsync(cur + b * sh.stride, state[b], sizeof(float) * 3 * (size_t)s.w[start + 1] * s.h[start + 1], hipMemcpyDeviceToDevice, s.st));
+        seeded = hand_seed(ctx, s, si, sh, s.w[start + 1], s.h[start + 1], s.w[start], s.h[start], nullptr, 0, sm, cur, other);
+    } else if (prior) {
         if (start < last || start > top) return UGSM_ERR_BAD_ARG;
         s.cur_level = start;
         for_groups(sh.nb, launch_pairs(ctx, sh, s.w[start], s.h[start]) > 1, [&](Grp g) {
@@ -1064,9 +1075,7 @@ int enqueue_descent(ugsm_ctx *ctx, Slot &s, int si, const Shape &sh, int last, V
         for (int b = 0; b < sh.nb; b++)  // U1: zero seed
             HIPCHK(ctx, hipMemsetAsync(cur + b * sh.stride, 0, sizeof(float) * 3 * (size_t)s.w[top] * s.h[top], s.st));
     }
-    SeedMap sm[2 * kMaxBatch];  // (a shape of both directions: two entries per pair)
     Img3 Lv[2 * kMaxBatch], Rv[2 * kMaxBatch];
-    bool seeded = false;
     field = nullptr;
     for (int i = start; i >= last; i--) {
         s.cur_level = i;
@@ -1086,7 +1095,9 @@ int enqueue_descent(ugsm_ctx *ctx, Slot &s, int si, const Shape &sh, int last, V
 // swap: the images exchanged (the right-to-left match of the LR check): the right pyramid is the "left" image; A is then computed
 // in line (the side stream's A planes belong to the left image).
 // prior (optional): the seeded call -- the descent starts at level `first` from the pairs' full-resolution priors (enqueue_descent).
-int enqueue_full(ugsm_ctx *ctx, Slot &s, int si, float *const *d_out, bool swap = false, int first = -1, const float *const *prior = nullptr)
+// state (optional, instead): the fine half -- the descent goes on at level `first` from the pairs' fields of level `first` + 1.
+int enqueue_full(ugsm_ctx *ctx, Slot &s, int si, float *const *d_out, bool swap = false, int first = -1, const float *const *prior = nullptr,
+                 const float *const *state = nullptr)
 {
     const Shape sh = Shape::pairs(s);
     const float *const pL = swap ? s.pyrR : s.pyrL, *const pR = swap ? s.pyrL : s.pyrR;
@@ -1103,12 +1114,52 @@ int enqueue_full(ugsm_ctx *ctx, Slot &s, int si, float *const *d_out, bool swap 
         return kInPlanes;
     };
     float *field;
-    UCHK(enqueue_descent(ctx, s, si, sh, 0, views, !swap && sh.nb == 1, d_out, field, first, prior));
+    UCHK(enqueue_descent(ctx, s, si, sh, 0, views, !swap && sh.nb == 1, d_out, field, first, prior, state));
     for (int b = 0; field && b < sh.nb; b++)
         HIPCHK(ctx, hipMemcpyAsync(d_out[b], field + b * sh.stride, sizeof(float) * 3 * (size_t)s.W * s.H, hipMemcpyDeviceToDevice, s.st));
     return UGSM_OK;
 }
 int enqueue_full(ugsm_ctx *ctx, Slot &s, int si, float *d_out, bool swap = false) { return enqueue_full(ctx, s, si, &d_out, swap); }
+
+// The coarse half of a full-mode call (ugsm_submit_full_coarse) for the s.nb pairs of the call: the levels top .. e as enqueue_full runs them,
+// level e's fields into d_state; then, for the pairs with a d_full entry (d_full may be null), their prolongation to full resolution in ONE
+// launch (launch_prolong), read from d_state.  e == 0: the whole call, d_state its result.
+int enqueue_full_coarse(ugsm_ctx *ctx, Slot &s, int si, int e, float *const *d_state, float *const *d_full)
+{
+    const Shape sh = Shape::pairs(s);
+    if (e == 0) {
+        UCHK(enqueue_full(ctx, s, si, d_state));
+    } else {
+        auto views = [&](int i, Img3 *Lv, Img3 *Rv) -> int {
+            full_views(s, sh, s.pyrL, i, Lv);
+            full_views(s, sh, s.pyrR, i, Rv);
+            return kInPlanes;
+        };
+        float *field;
+        UCHK(enqueue_descent(ctx, s, si, sh, e, views, sh.nb == 1, nullptr, field));
+        for (int b = 0; b < sh.nb; b++)
+            HIPCHK(ctx, hipMemcpyAsync(d_state[b], field + b * sh.stride, sizeof(float) * 3 * (size_t)s.w[e] * s.h[e], hipMemcpyDeviceToDevice, s.st));
+    }
+    int asked[kMaxBatch], m = 0;
+    for (int b = 0; d_full && b < sh.nb; b++)
+        if (d_full[b]) asked[m++] = b;
+    if (m == 0) return UGSM_OK;
+    Batch bt{};
+    bt.n = m;
+    for (int j = 0; j < m; j++) {
+        bt.in[j] = byte_diff(d_state[asked[j]], d_state[asked[0]]);
+        bt.out[j] = byte_diff(d_full[asked[j]], d_full[asked[0]]);
+    }
+    s.cur_level = e;
+    bool launched;
+    {
+        Timer t(ctx, &s, si, KC_PROLONG, (double)m * s.W * s.H);
+        launched = launch_prolong(s.st, d_state[asked[0]], s.w, s.h, e, d_full[asked[0]], m > 1 ? &bt : nullptr);
+    }
+    if (!launched) return ctx_fail(ctx, UGSM_ERR_BAD_ARG, "the prolongation: a size its kernel does not cover");
+    HIPCHK(ctx, hipGetLastError());
+    return UGSM_OK;
+}
 
 // The LR check's setting (ugsm_set_lr_check): which calls apply it, and the page-locked words its counts come back in
 bool lr_full_on(const ugsm_ctx *ctx) { return ctx->lr_tau > 0.0f && (ctx->lr_modes & UGSM_LR_FULL); }
@@ -1475,6 +1526,53 @@ int ugsm::seeded_submit(ugsm_ctx *ctx, int slot, int n, const uint8_t *const *d_
     const int per = batch_runs_pair_by_pair(ctx) ? 1 : n;  // (kernel_path 1: the pairs one after the other, as ugsm_submit_full_batch)
     for (int b = 0; b < n; b += per)
         UCHK(enqueue_match_full_seeded(ctx, *s, slot, per, d_rgbL + b, d_rgbR + b, W, H, stride, d_prior + b, start_level, d_out + b));
+    return mark_done(ctx, *s);
+}
+
+// The full-mode call in two halves (ugsm_submit_full_coarse, ugsm_submit_full_fine; their refusals: ugsm_coarse.cpp), n pairs in lockstep.
+// Coarse: the pyramids as ugsm_submit_full_batch builds them -- a lone pair's A planes from the side stream for the levels top .. e only --,
+// the levels top .. e, and the prolongation.  Fine: the pyramids up to level max(e - 1, 2) as the seeded call's, the levels e - 1 .. 0 from the
+// states of level e.
+static int enqueue_match_full_coarse(ugsm_ctx *ctx, Slot &s, int si, int n, const uint8_t *const *d_rgbL, const uint8_t *const *d_rgbR, int W, int H,
+                                     int stride, int e, float *const *d_state, float *const *d_full)
+{
+    UCHK(enqueue_pyramids(ctx, s, si, d_rgbL, d_rgbR, n, W, H, stride, n == 1 ? e : -1, nullptr, true));
+    s.have_coarse = false;
+    s.lr_ran = false;
+    s.lr_fov_pairs = 0;
+    s.lr_full_pairs = 0;
+    return enqueue_full_coarse(ctx, s, si, e, d_state, d_full);
+}
+static int enqueue_match_full_fine(ugsm_ctx *ctx, Slot &s, int si, int n, const uint8_t *const *d_rgbL, const uint8_t *const *d_rgbR, int W, int H,
+                                   int stride, const float *const *d_state, int e, float *const *d_out)
+{
+    UCHK(enqueue_pyramids(ctx, s, si, d_rgbL, d_rgbR, n, W, H, stride, n == 1 ? 0 : -1, nullptr, true, 0, e - 1));
+    s.have_coarse = false;
+    s.lr_ran = false;
+    s.lr_fov_pairs = 0;
+    s.lr_full_pairs = 0;
+    return enqueue_full(ctx, s, si, d_out, false, e - 1, nullptr, d_state);
+}
+int ugsm::coarse_submit(ugsm_ctx *ctx, int slot, int n, const uint8_t *const *d_rgbL, const uint8_t *const *d_rgbR, int W, int H, int stride,
+                        int stop_level, float *const *d_state, float *const *d_full)
+{
+    Slot *s;
+    UCHK(get_slot(ctx, slot, &s));
+    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
+    const int per = batch_runs_pair_by_pair(ctx) ? 1 : n;  // (kernel_path 1: the pairs one after the other, as ugsm_submit_full_batch)
+    for (int b = 0; b < n; b += per)
+        UCHK(enqueue_match_full_coarse(ctx, *s, slot, per, d_rgbL + b, d_rgbR + b, W, H, stride, stop_level, d_state + b, d_full ? d_full + b : nullptr));
+    return mark_done(ctx, *s);
+}
+int ugsm::fine_submit(ugsm_ctx *ctx, int slot, int n, const uint8_t *const *d_rgbL, const uint8_t *const *d_rgbR, int W, int H, int stride,
+                      const float *const *d_state, int state_level, float *const *d_out)
+{
+    Slot *s;
+    UCHK(get_slot(ctx, slot, &s));
+    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
+    const int per = batch_runs_pair_by_pair(ctx) ? 1 : n;
+    for (int b = 0; b < n; b += per)
+        UCHK(enqueue_match_full_fine(ctx, *s, slot, per, d_rgbL + b, d_rgbR + b, W, H, stride, d_state + b, state_level, d_out + b));
     return mark_done(ctx, *s);
 }
 namespace {
@@ -2587,6 +2685,59 @@ int ugsm::seeded_match(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, 
 {
     return drained(ctx, 0, seeded_match_on_slot0(ctx, rgbL, rgbR, W, H, stride, prior, start_level, disp));
 }
+// The two halves as service calls (ugsm_match_full_coarse, ugsm_match_full_fine; their refusals: ugsm_coarse.cpp) on slot 0.  The slot's
+// result staging holds the full-resolution field (the prolongation, or the fine half's result) and, behind it, the state of level e.
+static int coarse_match_on_slot0(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, int e, float *const state[3],
+                                 float *const full[3])
+{
+    Slot *s;
+    UCHK(get_slot(ctx, 0, &s));
+    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
+    int w[UGSM_MAX_LEVELS], h[UGSM_MAX_LEVELS];
+    UCHK(level_dims(W, H, ctx->cfg.levels, w, h));
+    UCHK(stage_in(ctx, *s, rgbL, rgbR, W, H, stride));
+    const size_t n = (size_t)W * H, ne = (size_t)w[e] * h[e], room = full ? ((3 * n + 63) & ~(size_t)63) : 0;
+    UCHK(grow(ctx, s->hout, s->hout_cap, room + 3 * ne));
+    const uint8_t *const dL = s->rgbL, *const dR = s->rgbR;
+    float *const d_state = s->hout + room, *const d_full = full ? s->hout : nullptr;
+    UCHK(enqueue_match_full_coarse(ctx, *s, 0, 1, &dL, &dR, W, H, stride, e, &d_state, &d_full));
+    if (full) prefault_planes(ctx, full, n);
+    UCHK(copy_out_planes(ctx, *s, d_state, ne, state));
+    if (full) UCHK(copy_out_planes(ctx, *s, d_full, n, full));
+    s->forked = false;  // (enqueued whole, as mark_done)
+    return ugsm_wait(ctx, 0);
+}
+int ugsm::coarse_match(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, int stop_level, float *const state[3],
+                       float *const full[3])
+{
+    return drained(ctx, 0, coarse_match_on_slot0(ctx, rgbL, rgbR, W, H, stride, stop_level, state, full));
+}
+static int fine_match_on_slot0(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, const float *const state[3], int e,
+                               float *const disp[3])
+{
+    Slot *s;
+    UCHK(get_slot(ctx, 0, &s));
+    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
+    int w[UGSM_MAX_LEVELS], h[UGSM_MAX_LEVELS];
+    UCHK(level_dims(W, H, ctx->cfg.levels, w, h));
+    UCHK(stage_in(ctx, *s, rgbL, rgbR, W, H, stride));
+    const size_t n = (size_t)W * H, ne = (size_t)w[e] * h[e], room = (3 * n + 63) & ~(size_t)63;
+    UCHK(grow(ctx, s->hout, s->hout_cap, room + 3 * ne));
+    for (int c = 0; c < 3; c++) HIPCHK(ctx, hipMemcpyAsync(s->hout + room + c * ne, state[c], ne * sizeof(float), hipMemcpyHostToDevice, s->st));
+    const uint8_t *const dL = s->rgbL, *const dR = s->rgbR;
+    const float *const d_state = s->hout + room;
+    float *const field = s->hout;
+    UCHK(enqueue_match_full_fine(ctx, *s, 0, 1, &dL, &dR, W, H, stride, &d_state, e, &field));
+    prefault_planes(ctx, disp, n);
+    UCHK(copy_out_planes(ctx, *s, s->hout, n, disp));
+    s->forked = false;  // (enqueued whole, as mark_done)
+    return ugsm_wait(ctx, 0);
+}
+int ugsm::fine_match(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, const float *const state[3], int state_level,
+                     float *const disp[3])
+{
+    return drained(ctx, 0, fine_match_on_slot0(ctx, rgbL, rgbR, W, H, stride, state, state_level, disp));
+}
 // The warm foveated service call (ugsm_match_foveated_warm; its refusals: ugsm_fovea_seeded.cpp) on slot 0: images and the prior stack's three
 // planes up, the match into a second stack beside it in the slot's result staging (the call is not in place), that stack's planes down.
 static int fovea_warm_match_on_slot0(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, int off_x, int off_y,
@@ -2901,7 +3052,10 @@ int ugsm_stage_seed(ugsm_ctx *ctx, const float *d_src3, int W, int H, float *d_d
     (void)Wup;
     (void)Hup;
     HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
-    launch_seed(s->st, d_src3, W, H, d_dst3, W2, H2, crop_x, crop_y);
+    {
+        Timer t(ctx, s, 0, KC_SEED, (double)W2 * H2);  // (profile_events = 2: the launch's own duration in the kernel statistics)
+        launch_seed(s->st, d_src3, W, H, d_dst3, W2, H2, crop_x, crop_y);
+    }
     HIPCHK(ctx, hipGetLastError());
     return ugsm_wait(ctx, 0);
 }
@@ -2915,6 +3069,25 @@ int ugsm_stage_restrict(ugsm_ctx *ctx, const float *d_src3, int W, int H, int le
     UCHK(level_dims(W, H, ctx->cfg.levels, w, h));
     HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
     launch_restrict(s->st, d_src3, W, H, level, d_dst3, w[level], h[level]);
+    HIPCHK(ctx, hipGetLastError());
+    return ugsm_wait(ctx, 0);
+}
+
+int ugsm_stage_prolong(ugsm_ctx *ctx, const float *d_src3, int W, int H, int level, float *d_dst3)
+{
+    Slot *s;
+    UCHK(get_slot(ctx, 0, &s));
+    if (!d_src3 || !d_dst3 || level < 0 || level >= ctx->cfg.levels) return UGSM_ERR_BAD_ARG;
+    int w[UGSM_MAX_LEVELS], h[UGSM_MAX_LEVELS];
+    UCHK(level_dims(W, H, ctx->cfg.levels, w, h));
+    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
+    s->cur_level = level;
+    bool launched;
+    {
+        Timer t(ctx, s, 0, KC_PROLONG, (double)W * H);
+        launched = launch_prolong(s->st, d_src3, w, h, level, d_dst3);
+    }
+    if (!launched) return ctx_fail(ctx, UGSM_ERR_BAD_ARG, "the prolongation: a size its kernel does not cover");
     HIPCHK(ctx, hipGetLastError());
     return ugsm_wait(ctx, 0);
 }

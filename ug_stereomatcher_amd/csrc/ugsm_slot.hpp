@@ -17,7 +17,7 @@ namespace ugsm {
 
 constexpr double kScale = 1.41421356;  // MatchLib_common.h:15
 enum KClass { KC_COST = 0, KC_SMOOTH, KC_SQBLUR, KC_PYR, KC_SEED, KC_WARP, KC_BOX, KC_MISC, KC_COST_MARCH, KC_PYR_BASE, KC_COST_SMALL, KC_SMOOTH_SMALL, KC_COST_MARCH4,
-              KC_LEVEL0_WIN, KC_RESTRICT, KC_RESTRICT_STACK, KC_COUNT };
+              KC_LEVEL0_WIN, KC_RESTRICT, KC_RESTRICT_STACK, KC_PROLONG, KC_COUNT };
 constexpr int kNoLevel = UGSM_MAX_LEVELS;  // stats cell of launches that belong to no pyramid level
 struct StatCell {
     long long launches = 0;

@@ -126,6 +126,24 @@ class MatchGPULib:
         self.foveatedmatching = 0
         return self._ctx.match_full_seeded(L, R, np.asarray(prior, np.float32), start_level)
 
+    def matchCoarse(self, cv_ptrL, cv_ptrR, stop_level: int, want_full: bool = False):
+        """(not in the reference) match(L, R, 0) stopped when level stop_level has finished (ugsm_match_full_coarse): that level's field,
+        (3, h, w) of the level's size; with want_full, (state, its prolongation to the images' size, a finDisp)."""
+        L, R = _as_rgb8(cv_ptrL), _as_rgb8(cv_ptrR)
+        if L.shape != R.shape or L.strides[0] != R.strides[0]:
+            raise UgsmError(_lib.UGSM_ERR_SIZE_MISMATCH, "left/right images differ in size")
+        self.foveatedmatching = 0
+        return self._ctx.match_full_coarse(L, R, stop_level, want_full)
+
+    def matchFine(self, cv_ptrL, cv_ptrR, state, state_level: int) -> np.ndarray:
+        """(not in the reference) the rest of match(L, R, 0) from `state`, the field of level state_level that matchCoarse returned
+        (ugsm_match_full_fine): with the same pair, match(L, R, 0)'s finDisp bit for bit.  Returns finDisp."""
+        L, R = _as_rgb8(cv_ptrL), _as_rgb8(cv_ptrR)
+        if L.shape != R.shape or L.strides[0] != R.strides[0]:
+            raise UgsmError(_lib.UGSM_ERR_SIZE_MISMATCH, "left/right images differ in size")
+        self.foveatedmatching = 0
+        return self._ctx.match_full_fine(L, R, np.asarray(state, np.float32), state_level)
+
     # -- hierarchicalDisparity, MatchGPULib.cpp:2589-2701 --
     def hierarchicalDisparity(self, foveated: np.ndarray, widthInit: int, heightInit: int) -> np.ndarray:
         """foveated: (foveatelevel, 3, fovH, fovW) as matchStack returns it -> (3, heightInit, widthInit)."""
