@@ -13,34 +13,16 @@ using namespace ugsm;
 // back in *we x *he.
 static int halves_check(ugsm_ctx *ctx, int n, int W, int H, int stride, int level, int lowest, const char *bad_level, int *we, int *he)
 {
-    const ugsm_config &cfg = ctx_config(ctx);
-    const CtxHooks &hooks = ctx_hooks(ctx);
-    if (n < 1 || n > UGSM_MAX_BATCH) return ctx_fail(ctx, UGSM_ERR_BAD_ARG, "a full-mode call in two halves takes 1 .. UGSM_MAX_BATCH pairs");
-    if (level < lowest || level >= cfg.levels) return ctx_fail(ctx, UGSM_ERR_BAD_ARG, bad_level);
-    // (the early exit runs pair by pair through a host round trip per iteration: no lockstep, and a level's field then depends on the exit)
-    if (cfg.early_exit_threshold > 0.0f) return ctx_fail(ctx, UGSM_ERR_BAD_ARG, "a full-mode call in two halves: not with early_exit_threshold > 0");
-    if (hooks.queue_busy && !hooks.queue_calling)
-        return ctx_fail(ctx, UGSM_ERR_STATE, "pairs enqueued with ugsm_enqueue_* are outstanding: the slots belong to the queue until ugsm_next_done has reported them all");
-    float tau = 0.0f;
-    int modes = 0;
-    if (ugsm_get_lr_check(ctx, &tau, &modes) == UGSM_OK && tau > 0.0f && (modes & UGSM_LR_FULL))
-        return ctx_fail(ctx, UGSM_ERR_STATE, "the full-mode LR check is on (ugsm_set_lr_check): there is no checked call in two halves");
     int w[UGSM_MAX_LEVELS], h[UGSM_MAX_LEVELS];
-    const int st = ugsm_level_dims(W, H, cfg.levels, w, h);
+    const bool bad = level < lowest || level >= ctx_config(ctx).levels;
+    const int st = refuse_common(ctx, "a full-mode call in two halves", UGSM_LR_FULL, n, bad ? bad_level : nullptr, W, H, stride, w, h);
     if (st != UGSM_OK) return st;
-    if (stride < input_bpp(hooks.input_format) * W) return UGSM_ERR_SIZE_MISMATCH;
     *we = w[level];
     *he = h[level];
     return UGSM_OK;
 }
 static const char kBadStop[] = "ugsm_submit_full_coarse: stop_level outside 0 .. levels - 1";
 static const char kBadState[] = "ugsm_submit_full_fine: state_level outside 1 .. levels - 1";
-
-static bool overlap(const float *a, size_t na, const float *b, size_t nb)
-{
-    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
-    return a0 < b0 + nb * sizeof(float) && b0 < a0 + na * sizeof(float);
-}
 
 extern "C" {
 
@@ -57,7 +39,7 @@ int ugsm_submit_full_coarse(ugsm_ctx *ctx, int slot, int n, const uint8_t *const
     // (the prolongation reads the states while it writes: an output that lies over any pair's state would be read half written)
     for (int b = 0; d_full && b < n; b++)
         for (int k = 0; d_full[b] && k < n; k++)
-            if (overlap(d_full[b], 3 * (size_t)W * H, d_state[k], 3 * (size_t)we * he))
+            if (overlap(d_full[b], sizeof(float) * 3 * (size_t)W * H, d_state[k], sizeof(float) * 3 * (size_t)we * he))
                 return ctx_fail(ctx, UGSM_ERR_BAD_ARG, "ugsm_submit_full_coarse: a d_full entry overlaps a state of the call");
     return coarse_submit(ctx, slot, n, d_rgbL, d_rgbR, W, H, stride, stop_level, d_state, d_full);
 }

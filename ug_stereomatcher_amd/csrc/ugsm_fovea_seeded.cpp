@@ -9,36 +9,21 @@
 
 using namespace ugsm;
 
-// What every form refuses beyond its null pointers; the fovea's size comes back for the overlap test.
+// What every form refuses beyond its null pointers: the shared refusals (refuse_common) around the call's own two, the context's fovea and the
+// start level; the fovea's size comes back for the overlap test.
 static int warm_check(ugsm_ctx *ctx, int n, int W, int H, int stride, int start_level, int *fw, int *fh)
 {
     const ugsm_config &cfg = ctx_config(ctx);
-    const CtxHooks &hooks = ctx_hooks(ctx);
     const int F = cfg.fovea_levels;
-    if (n < 1 || n > UGSM_MAX_BATCH) return ctx_fail(ctx, UGSM_ERR_BAD_ARG, "the warm foveated call takes 1 .. UGSM_MAX_BATCH pairs");
-    if (F < 2 || F > cfg.levels) return ctx_fail(ctx, UGSM_ERR_BAD_ARG, "the warm foveated call needs a context with fovea_levels >= 2");
-    if (start_level < 0 || start_level >= F) return ctx_fail(ctx, UGSM_ERR_BAD_ARG, "the warm foveated call: start_level outside 0 .. fovea_levels - 1");
-    // (the early exit compares a level's fields pair by pair through a third buffer and a host round trip: no lockstep, and no use beside a prior)
-    if (cfg.early_exit_threshold > 0.0f) return ctx_fail(ctx, UGSM_ERR_BAD_ARG, "the warm foveated call: not with early_exit_threshold > 0");
-    if (hooks.queue_busy && !hooks.queue_calling)
-        return ctx_fail(ctx, UGSM_ERR_STATE, "pairs enqueued with ugsm_enqueue_* are outstanding: the slots belong to the queue until ugsm_next_done has reported them all");
-    float tau = 0.0f;
-    int modes = 0;
-    if (ugsm_get_lr_check(ctx, &tau, &modes) == UGSM_OK && tau > 0.0f && (modes & UGSM_LR_FOVEATED))
-        return ctx_fail(ctx, UGSM_ERR_STATE, "the foveated LR check is on (ugsm_set_lr_check): there is no warm checked call");
+    const char *own = (F < 2 || F > cfg.levels)          ? "the warm foveated call needs a context with fovea_levels >= 2"
+                      : (start_level < 0 || start_level >= F) ? "the warm foveated call: start_level outside 0 .. fovea_levels - 1"
+                                                              : nullptr;
     int w[UGSM_MAX_LEVELS], h[UGSM_MAX_LEVELS];
-    int st = ugsm_level_dims(W, H, cfg.levels, w, h);
+    const int st = refuse_common(ctx, "the warm foveated call", UGSM_LR_FOVEATED, n, own, W, H, stride, w, h);
     if (st != UGSM_OK) return st;
-    st = ugsm_fovea_dims(W, H, cfg.levels, F, fw, fh);
-    if (st != UGSM_OK) return st;
-    if (stride < input_bpp(hooks.input_format) * W) return UGSM_ERR_SIZE_MISMATCH;
+    *fw = w[F - 1];  // (ugsm_fovea_dims)
+    *fh = h[F - 1];
     return UGSM_OK;
-}
-
-static bool overlap(const void *a, size_t abytes, const void *b, size_t bbytes)
-{
-    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
-    return x < y + bbytes && y < x + abytes;
 }
 
 // field: the priors are full-resolution fields; else stacks, with their windows' offsets (null arrays: centred)

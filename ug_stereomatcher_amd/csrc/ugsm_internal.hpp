@@ -6,6 +6,8 @@
 #include "../../include/ugsm.h"
 
 #include <stddef.h>
+#include <stdint.h>
+#include <stdio.h>
 
 #include <new>
 
@@ -101,6 +103,39 @@ int coarse_match(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int W,
                  float *const full[3]);
 int fine_match(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, const float *const state[3], int state_level,
                float *const disp[3]);
+// What the seeded call, the two halves and the warm foveated call all refuse beyond their null pointers (ugsm_seeded.cpp, ugsm_coarse.cpp,
+// ugsm_fovea_seeded.cpp), in the one order they have always had: the pair count, the call's own refusal of its level arguments, the early
+// exit, a busy queue, the LR check, a size with no pyramid, a stride too small.
+// what: the call's name for the messages; lr_mode: the UGSM_LR_* bit under which the call has no checked form; own: the message of the call's own
+// refusal (null: its level arguments are fine); the levels' sizes come back in w and h.
+inline int refuse_common(ugsm_ctx *ctx, const char *what, int lr_mode, int n, const char *own, int W, int H, int stride, int *w, int *h)
+{
+    const ugsm_config &cfg = ctx_config(ctx);
+    const CtxHooks &hooks = ctx_hooks(ctx);
+    char msg[200];
+    snprintf(msg, sizeof msg, "%s takes 1 .. UGSM_MAX_BATCH pairs", what);
+    if (n < 1 || n > UGSM_MAX_BATCH) return ctx_fail(ctx, UGSM_ERR_BAD_ARG, msg);
+    if (own) return ctx_fail(ctx, UGSM_ERR_BAD_ARG, own);
+    // (the early exit compares a level's fields pair by pair through a third buffer and a host round trip per iteration: no lockstep, a level's
+    // field then depends on the exit, and it is no use beside a prior)
+    snprintf(msg, sizeof msg, "%s: not with early_exit_threshold > 0", what);
+    if (cfg.early_exit_threshold > 0.0f) return ctx_fail(ctx, UGSM_ERR_BAD_ARG, msg);
+    if (hooks.queue_busy && !hooks.queue_calling)
+        return ctx_fail(ctx, UGSM_ERR_STATE, "pairs enqueued with ugsm_enqueue_* are outstanding: the slots belong to the queue until ugsm_next_done has reported them all");
+    float tau = 0.0f;
+    int modes = 0;
+    snprintf(msg, sizeof msg, "the %s LR check is on (ugsm_set_lr_check): %s has no checked form", lr_mode == UGSM_LR_FULL ? "full-mode" : "foveated", what);
+    if (ugsm_get_lr_check(ctx, &tau, &modes) == UGSM_OK && tau > 0.0f && (modes & lr_mode)) return ctx_fail(ctx, UGSM_ERR_STATE, msg);
+    const int st = ugsm_level_dims(W, H, cfg.levels, w, h);
+    if (st != UGSM_OK) return st;
+    return stride < input_bpp(hooks.input_format) * W ? UGSM_ERR_SIZE_MISMATCH : UGSM_OK;
+}
+// two buffers of abytes and bbytes share a byte
+inline bool overlap(const void *a, size_t abytes, const void *b, size_t bbytes)
+{
+    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+    return x < y + bbytes && y < x + abytes;
+}
 // the stagger of the queue's first round after idle and the size of every later call (ugsm.h, "the queue")
 int queue_target(int batch, int slots, long long calls_since_idle);
 

@@ -263,8 +263,27 @@ int prepare_slot(ugsm_ctx *ctx, Slot &s, int W, int H, int nb = 1)
     s.nb = nb;
     for (int i = 0; i < UGSM_MAX_LEVELS; i++) s.iters_run[i] = -1;
     s.have_pyr = false;
-    s.have_coarse = false;
     s.a_from = -1;
+    // What the slot says about its LAST call is cleared here, where a call that builds pyramids begins -- every ugsm_submit_* / ugsm_match_* that
+    // takes images, ugsm_submit_pyramids, ugsm_stage_pyramid -- so that a call only sets what it does:
+    //   lr_ran        set by enqueue_full_lr and enqueue_full_checked behind their check;
+    //   lr_full_pairs set by enqueue_full_checked alone and read only under lr_ran (ugsm_last_lr_marked, ugsm_last_lr_marked_pair): the calls that
+    //                 used to leave it standing beside lr_ran == false left nothing that could be seen;
+    //   lr_fov_pairs  set by enqueue_lr_stack_check behind a checked foveated call's check;
+    //   have_coarse   set by enqueue_fovea_coarse alone, which runs after the pyramids (nothing reads it today).
+    // Every one of these setters runs after its call's prepare_slot, so nothing a call sets is undone here.  (ugsm_submit_pyramids and
+    // ugsm_stage_pyramid, which set none, used to leave the LR words of the call before them standing: after them ugsm_last_lr_marked* now
+    // answer what include/ugsm.h says of a last call that ran no check.)  Who does not come through here:
+    //   ugsm_submit_fovea_coarse / _fine work on the pyramids of a ugsm_submit_pyramids and touch no LR word, as ever: they run no check
+    //   (include/ugsm.h), and ugsm_last_lr_marked* answer as after that ugsm_submit_pyramids; _coarse sets have_coarse;
+    //   ugsm_stage_iterate[_rgb8] bring planes of their own: they clear have_pyr and have_coarse themselves (a ugsm_submit_fovea_coarse may
+    //   have set it) and touch no LR word; the other ugsm_stage_* calls touch none of the four.
+    // A call refused before its pyramids (a null image, a stride too small, a size with no pyramid) has enqueued nothing and leaves the slot
+    // describing the call before it.
+    s.lr_ran = false;
+    s.lr_full_pairs = 0;
+    s.lr_fov_pairs = 0;
+    s.have_coarse = false;
     const size_t lvl = 3 * (size_t)W * H;
     // (pairs of a batch start on 256-byte boundaries: the kernels' 16-byte accesses stay aligned whatever the level sizes add up to)
     s.pyr_stride = (tot + 63) & ~(size_t)63;
@@ -1031,73 +1050,77 @@ bool hand_seed(ugsm_ctx *ctx, Slot &s, int si, const Shape &sh, int Ws, int Hs, 
     return false;
 }
 
-// The full-frame levels top .. `last` of a call, coarse to fine from the zero seed, for the entries of `sh`: the loop of matching(),
-// MatchGPULib.cpp:1196-1318.  What differs between its callers comes in:
+// The full-frame levels from .. to of a call, coarse to fine, for the entries of `sh`: the loop of matching(), MatchGPULib.cpp:1196-1318.
+// Which levels, and what level `from` starts from, is the call's LevelRange:
+//   Zero (from == top): the zero seed, and level `from` is the top level (its first iteration takes no confidence);
+//   Prior: the restriction of the entries' full-resolution fields (launch_restrict) fills level `from`'s fields where the zero seed is
+//          otherwise set; the levels above run nothing, and level `from` is no top level, whichever it is -- its first iteration blends the
+//          confidence like any other, a prior has one;
+//   State: the entries' fields of level from + 1, placed in the level buffer and handed to level `from` by the cold call's own step
+//          (hand_seed): the descent goes on at level `from` as if the levels above had just run.
+// From there down everything is the same.  What else differs between the callers comes in:
 // views(i, Lv, Rv): fills the entries' views of level i and returns their form (run_level's `in`);
 // side_A: a level's A is taken from the side stream where it was precomputed there (level_A);
 // direct_out (optional): the entries' result buffers, which level 0's last smoothing launch writes itself where it can (no 193 MB device
-// copy at 16 MP): `field` is then null.  Otherwise `field` is the level buffer that holds level `last`'s fields, for the caller's copy.
-// prior (optional; the seeded call, ugsm_submit_full_seeded): the entries' full-resolution fields (s.W x s.H), of which the descent starts at
-// level `first` instead of from the zero seed at the top: the restriction (launch_restrict) fills level `first`'s fields where the zero seed
-// is otherwise set, the levels above run nothing, and level `first` is no top level -- its first iteration blends the confidence like any
-// other, a prior has one.  From there down everything is the same.
-// state (optional, instead of a prior; the fine half of a full-mode call, ugsm_submit_full_fine): the entries' fields of level `first` + 1, as
-// a descent that stopped there (`last`) left them.  They are placed in the level buffer and handed to level `first` by the cold call's own step
-// (hand_seed); the descent goes on at level `first` as if the levels above had just run.
+// copy at 16 MP): `field` is then null.  Otherwise `field` is the level buffer that holds level `to`'s fields, for the caller's copy.
 template <class Views>
-int enqueue_descent(ugsm_ctx *ctx, Slot &s, int si, const Shape &sh, int last, Views &&views, bool side_A, float *const *direct_out, float *&field,
-                    int first = -1, const float *const *prior = nullptr, const float *const *state = nullptr)
+int enqueue_descent(ugsm_ctx *ctx, Slot &s, int si, const Shape &sh, const LevelRange &r, Views &&views, bool side_A, float *const *direct_out, float *&field)
 {
     float *cur = s.d0, *other = s.d1;
-    const int top = s.levels - 1, start = (prior || state) ? first : top;
+    const int from = r.from;
     SeedMap sm[2 * kMaxBatch];  // (a shape of both directions: two entries per pair)
     bool seeded = false;
-    if (state) {
-        if (prior || start < last || start >= top) return UGSM_ERR_BAD_ARG;
-        s.cur_level = start + 1;
+    if (r.start == LevelRange::State) {
+        s.cur_level = from + 1;
         for (int b = 0; b < sh.nb; b++)
-            HIPCHK(ctx, hipMemcpyAsync(cur + b * sh.stride, state[b], sizeof(float) * 3 * (size_t)s.w[start + 1] * s.h[start + 1], hipMemcpyDeviceToDevice, s.st));
-        seeded = hand_seed(ctx, s, si, sh, s.w[start + 1], s.h[start + 1], s.w[start], s.h[start], nullptr, 0, sm, cur, other);
-    } else if (prior) {
-        if (start < last || start > top) return UGSM_ERR_BAD_ARG;
-        s.cur_level = start;
-        for_groups(sh.nb, launch_pairs(ctx, sh, s.w[start], s.h[start]) > 1, [&](Grp g) {
-            Timer t(ctx, &s, si, KC_RESTRICT, (double)s.w[start] * s.h[start] * g.n);
+            HIPCHK(ctx, hipMemcpyAsync(cur + b * sh.stride, r.source[b], sizeof(float) * 3 * (size_t)s.w[from + 1] * s.h[from + 1], hipMemcpyDeviceToDevice, s.st));
+        seeded = hand_seed(ctx, s, si, sh, s.w[from + 1], s.h[from + 1], s.w[from], s.h[from], nullptr, 0, sm, cur, other);
+    } else if (r.start == LevelRange::Prior) {
+        const float *const *prior = r.source;
+        s.cur_level = from;
+        for_groups(sh.nb, launch_pairs(ctx, sh, s.w[from], s.h[from]) > 1, [&](Grp g) {
+            Timer t(ctx, &s, si, KC_RESTRICT, (double)s.w[from] * s.h[from] * g.n);
             Batch bt{};
             bt.n = g.n;
             for (int j = 0; j < g.n; j++) {
                 bt.in[j] = byte_diff(prior[g.b0 + j], prior[g.b0]);
                 bt.out[j] = (long long)(j * sh.stride * sizeof(float));
             }
-            launch_restrict(s.st, prior[g.b0], s.W, s.H, start, cur + g.b0 * sh.stride, s.w[start], s.h[start], g.n > 1 ? &bt : nullptr);
+            launch_restrict(s.st, prior[g.b0], s.W, s.H, from, cur + g.b0 * sh.stride, s.w[from], s.h[from], g.n > 1 ? &bt : nullptr);
         });
     } else {
         for (int b = 0; b < sh.nb; b++)  // U1: zero seed
-            HIPCHK(ctx, hipMemsetAsync(cur + b * sh.stride, 0, sizeof(float) * 3 * (size_t)s.w[top] * s.h[top], s.st));
+            HIPCHK(ctx, hipMemsetAsync(cur + b * sh.stride, 0, sizeof(float) * 3 * (size_t)s.w[from] * s.h[from], s.st));
     }
     Img3 Lv[2 * kMaxBatch], Rv[2 * kMaxBatch];
     field = nullptr;
-    for (int i = start; i >= last; i--) {
+    for (int i = from; i >= r.to; i--) {
         s.cur_level = i;
         const int mi = level_iterations(i);
         const bool direct = direct_out && i == 0 && ctx->cfg.kernel_path != 1 && level_smooth(0) > 0 && !(ctx->cfg.early_exit_threshold > 0.0f);
         const int in = views(i, Lv, Rv);
-        UCHK(run_level(ctx, s, si, sh, Lv, Rv, s.w[i], s.h[i], mi, level_smooth(i), i == top && !prior, 1, mi, cur, other, nullptr, direct ? direct_out : nullptr,
-                       seeded ? sm : nullptr, side_A ? level_A(ctx, s, i) : nullptr, in));
+        UCHK(run_level(ctx, s, si, sh, Lv, Rv, s.w[i], s.h[i], mi, level_smooth(i), i == from && r.start == LevelRange::Zero, 1, mi, cur, other, nullptr,
+                       direct ? direct_out : nullptr, seeded ? sm : nullptr, side_A ? level_A(ctx, s, i) : nullptr, in));
         if (direct) return UGSM_OK;
-        seeded = i > last && hand_seed(ctx, s, si, sh, s.w[i], s.h[i], s.w[i - 1], s.h[i - 1], nullptr, 0, sm, cur, other);
+        seeded = i > r.to && hand_seed(ctx, s, si, sh, s.w[i], s.h[i], s.w[i - 1], s.h[i - 1], nullptr, 0, sm, cur, other);
     }
     field = cur;
     return UGSM_OK;
 }
 
-// matching() with foveatedmatching==0, for the s.nb pairs of the call; d_out: their result buffers.
+// the entries' fields of level `lev`, as a descent left them in `field` (entry v at + v * sh.stride), into their destinations
+int copy_fields(ugsm_ctx *ctx, Slot &s, const Shape &sh, const float *field, int lev, float *const *outs)
+{
+    for (int v = 0; v < sh.nb; v++)
+        HIPCHK(ctx, hipMemcpyAsync(outs[v], field + v * sh.stride, sizeof(float) * 3 * (size_t)s.w[lev] * s.h[lev], hipMemcpyDeviceToDevice, s.st));
+    return UGSM_OK;
+}
+
+// matching() with foveatedmatching==0 over the levels of `r`, for the s.nb pairs of the call; d_out: their buffers for level r.to's fields
+// (level 0: the results, which its last launch writes itself where it can).
 // swap: the images exchanged (the right-to-left match of the LR check): the right pyramid is the "left" image; A is then computed
 // in line (the side stream's A planes belong to the left image).
-// prior (optional): the seeded call -- the descent starts at level `first` from the pairs' full-resolution priors (enqueue_descent).
-// state (optional, instead): the fine half -- the descent goes on at level `first` from the pairs' fields of level `first` + 1.
-int enqueue_full(ugsm_ctx *ctx, Slot &s, int si, float *const *d_out, bool swap = false, int first = -1, const float *const *prior = nullptr,
-                 const float *const *state = nullptr)
+int enqueue_full(ugsm_ctx *ctx, Slot &s, int si, float *const *d_out, const LevelRange &r, bool swap = false)
 {
     const Shape sh = Shape::pairs(s);
     const float *const pL = swap ? s.pyrR : s.pyrL, *const pR = swap ? s.pyrL : s.pyrR;
@@ -1114,34 +1137,16 @@ int enqueue_full(ugsm_ctx *ctx, Slot &s, int si, float *const *d_out, bool swap 
         return kInPlanes;
     };
     float *field;
-    UCHK(enqueue_descent(ctx, s, si, sh, 0, views, !swap && sh.nb == 1, d_out, field, first, prior, state));
-    for (int b = 0; field && b < sh.nb; b++)
-        HIPCHK(ctx, hipMemcpyAsync(d_out[b], field + b * sh.stride, sizeof(float) * 3 * (size_t)s.W * s.H, hipMemcpyDeviceToDevice, s.st));
-    return UGSM_OK;
+    UCHK(enqueue_descent(ctx, s, si, sh, r, views, !swap && sh.nb == 1, d_out, field));
+    return field ? copy_fields(ctx, s, sh, field, r.to, d_out) : UGSM_OK;
 }
-int enqueue_full(ugsm_ctx *ctx, Slot &s, int si, float *d_out, bool swap = false) { return enqueue_full(ctx, s, si, &d_out, swap); }
 
-// The coarse half of a full-mode call (ugsm_submit_full_coarse) for the s.nb pairs of the call: the levels top .. e as enqueue_full runs them,
-// level e's fields into d_state; then, for the pairs with a d_full entry (d_full may be null), their prolongation to full resolution in ONE
-// launch (launch_prolong), read from d_state.  e == 0: the whole call, d_state its result.
-int enqueue_full_coarse(ugsm_ctx *ctx, Slot &s, int si, int e, float *const *d_state, float *const *d_full)
+// The coarse half's prolongation (ugsm_submit_full_coarse): for the pairs with a d_full entry, the full-resolution field of their level-e
+// state in ONE launch (launch_prolong), read from d_state.
+int enqueue_prolong(ugsm_ctx *ctx, Slot &s, int si, int e, float *const *d_state, float *const *d_full)
 {
-    const Shape sh = Shape::pairs(s);
-    if (e == 0) {
-        UCHK(enqueue_full(ctx, s, si, d_state));
-    } else {
-        auto views = [&](int i, Img3 *Lv, Img3 *Rv) -> int {
-            full_views(s, sh, s.pyrL, i, Lv);
-            full_views(s, sh, s.pyrR, i, Rv);
-            return kInPlanes;
-        };
-        float *field;
-        UCHK(enqueue_descent(ctx, s, si, sh, e, views, sh.nb == 1, nullptr, field));
-        for (int b = 0; b < sh.nb; b++)
-            HIPCHK(ctx, hipMemcpyAsync(d_state[b], field + b * sh.stride, sizeof(float) * 3 * (size_t)s.w[e] * s.h[e], hipMemcpyDeviceToDevice, s.st));
-    }
     int asked[kMaxBatch], m = 0;
-    for (int b = 0; d_full && b < sh.nb; b++)
+    for (int b = 0; b < s.nb; b++)
         if (d_full[b]) asked[m++] = b;
     if (m == 0) return UGSM_OK;
     Batch bt{};
@@ -1161,6 +1166,7 @@ int enqueue_full_coarse(ugsm_ctx *ctx, Slot &s, int si, int e, float *const *d_s
     return UGSM_OK;
 }
 
+
 // The LR check's setting (ugsm_set_lr_check): which calls apply it, and the page-locked words its counts come back in
 bool lr_full_on(const ugsm_ctx *ctx) { return ctx->lr_tau > 0.0f && (ctx->lr_modes & UGSM_LR_FULL); }
 bool lr_fovea_on(const ugsm_ctx *ctx) { return ctx->lr_tau > 0.0f && (ctx->lr_modes & UGSM_LR_FOVEATED); }
@@ -1171,22 +1177,18 @@ int lr_host_ready(ugsm_ctx *ctx, Slot &s)
     return UGSM_OK;
 }
 
-// Full mode with the optional LR-consistency check (ugsm_set_lr_check / ugsm_config.lr_check_threshold; no reference counterpart): the match, the match
-// with the images exchanged into the slot's own buffer, then one kernel that zeroes the inconsistent confidences of d_out.  (Single pairs.)
+// The context's LR-consistency check of a full-mode call (ugsm_set_lr_check / ugsm_config.lr_check_threshold; no reference counterpart), behind
+// the match that wrote d_out: the match with the images exchanged into the slot's own buffer, then one kernel that zeroes the inconsistent
+// confidences of d_out.  (Single pairs, whole calls.)
 int enqueue_full_lr(ugsm_ctx *ctx, Slot &s, int si, float *d_out)
 {
-    s.lr_ran = false;
-    s.lr_fov_pairs = 0;
-    s.lr_full_pairs = 0;
-    UCHK(enqueue_full(ctx, s, si, d_out));
     const float tau = ctx->lr_tau;
-    if (!lr_full_on(ctx)) return UGSM_OK;
     const size_t n3 = 3 * (size_t)s.W * s.H;
     UCHK(grow(ctx, s.lr, s.lr_cap, n3 + 4));
     UCHK(lr_host_ready(ctx, s));
     unsigned long long *cnt = reinterpret_cast<unsigned long long *>(s.lr + ((n3 + 1) & ~(size_t)1));  // (8-byte aligned)
     HIPCHK(ctx, hipMemsetAsync(cnt, 0, sizeof *cnt, s.st));
-    UCHK(enqueue_full(ctx, s, si, s.lr, true));
+    UCHK(enqueue_full(ctx, s, si, &s.lr, LevelRange::cold(s.levels), true));
     {
         Timer t(ctx, &s, si, KC_MISC, (double)s.W * s.H);
         launch_lr_check(s.st, d_out, s.lr, s.W, s.H, tau, cnt);
@@ -1215,9 +1217,6 @@ size_t lr_full_room(size_t lvl_stride, int kept, int n) { return (size_t)kept * 
 int enqueue_full_checked(ugsm_ctx *ctx, Slot &s, int si, int n, const uint8_t *const *d_rgbL, const uint8_t *const *d_rgbR, int W, int H, int stride,
                          float *const *d_out, float *const *d_back, float tau)
 {
-    s.lr_ran = false;
-    s.lr_fov_pairs = 0;
-    s.lr_full_pairs = 0;
     UCHK(enqueue_pyramids(ctx, s, si, d_rgbL, d_rgbR, n, W, H, stride, -1, nullptr, true, 2 * n));
     const Shape sh = Shape::full_both_directions(s);
     int kept = 0;
@@ -1247,9 +1246,8 @@ int enqueue_full_checked(ugsm_ctx *ctx, Slot &s, int si, int n, const uint8_t *c
         return kInPlanes;
     };
     float *field;
-    UCHK(enqueue_descent(ctx, s, si, sh, 0, views, false, outs, field));
-    for (int v = 0; field && v < sh.nb; v++)
-        HIPCHK(ctx, hipMemcpyAsync(outs[v], field + v * sh.stride, sizeof(float) * 3 * (size_t)s.W * s.H, hipMemcpyDeviceToDevice, s.st));
+    UCHK(enqueue_descent(ctx, s, si, sh, LevelRange::cold(s.levels), views, false, outs, field));
+    if (field) UCHK(copy_fields(ctx, s, sh, field, 0, outs));
     unsigned long long *cnt = reinterpret_cast<unsigned long long *>(s.lr + (size_t)kept * s.lvl_stride);
     HIPCHK(ctx, hipMemsetAsync(cnt, 0, sizeof *cnt * 2 * n, s.st));
     // k_lr_check's stack form with F = 1: a "stack" is then one full field.  Check 2 b is pair b's left-to-right field against its right-to-left
@@ -1298,7 +1296,7 @@ int enqueue_fovea_coarse(ugsm_ctx *ctx, Slot &s, int si, const Shape &sh, float 
         return kInPlanes;
     };
     float *cur;
-    UCHK(enqueue_descent(ctx, s, si, sh, F - 1, views, sh.nb == 1, nullptr, cur));
+    UCHK(enqueue_descent(ctx, s, si, sh, LevelRange::coarse(s.levels, F - 1), views, sh.nb == 1, nullptr, cur));
     const size_t fn = (size_t)s.w[F - 1] * s.h[F - 1];
     if (sh.nb == 1) {
         HIPCHK(ctx, hipMemcpyAsync(d_state[0], cur, sizeof(float) * 3 * fn, hipMemcpyDeviceToDevice, s.st));
@@ -1459,8 +1457,6 @@ int ugsm::enqueue_match_foveated(ugsm_ctx *ctx, Slot &s, int si, int n, const ui
                                  const int *off_x, const int *off_y, float *const *state, float *const *d_stack, float *const *d_pyrL, float *const *d_pyrR)
 {
     const int F = ctx->cfg.fovea_levels;
-    s.lr_ran = false;
-    s.lr_fov_pairs = 0;
     FoveaWin win;
     UCHK(fovea_windows(ctx, W, H, n, off_x, off_y, win));
     if (!lr_fovea_on(ctx)) {
@@ -1490,90 +1486,70 @@ int ugsm::enqueue_match_foveated(ugsm_ctx *ctx, Slot &s, int si, int n, const ui
     return enqueue_lr_stack_check(ctx, s, si, n, F, fw, fh, ctx->lr_tau, d_stack, room.per, reinterpret_cast<unsigned long long *>(s.lr + room.cnt));
 }
 
-// One full-mode call of n pairs on device buffers.  One pair: its pyramids (A planes from the side stream where the call is alone), the match
-// and the LR check where it is on; several: the pyramids and the levels of all of them in lockstep (no check: batch_runs_pair_by_pair).
+// One full-mode call of n pairs on device buffers over the levels of `given` (null: the cold call), every kind of it -- whole, seeded, either half:
+//   - the pyramids, as far up as the range reaches: a descent that starts below the top (seeded, fine half) builds the levels 0 .. max(from, 2)
+//     only.  A lone pair's A planes come from the side stream, where the call is alone, for the levels the range runs (to .. from); several
+//     pairs compute A in line;
+//   - the levels of all pairs in lockstep, level `to`'s fields into d_out (level 0: written by its last launch where that can be);
+//   - a lone pair's whole call: the context's LR check where it is on (several pairs: no check -- batch_runs_pair_by_pair);
+//   - the coarse half: the prolongation of the fields it was asked for.
 int ugsm::enqueue_match_full(ugsm_ctx *ctx, Slot &s, int si, int n, const uint8_t *const *d_rgbL, const uint8_t *const *d_rgbR, int W, int H, int stride,
-                             float *const *d_out)
+                             float *const *d_out, const LevelRange *given)
 {
-    if (n == 1) {
-        UCHK(enqueue_pyramids(ctx, s, si, d_rgbL, d_rgbR, 1, W, H, stride, 0, nullptr, true));
-        return enqueue_full_lr(ctx, s, si, d_out[0]);
-    }
-    UCHK(enqueue_pyramids(ctx, s, si, d_rgbL, d_rgbR, n, W, H, stride, -1, nullptr, true));
-    s.lr_ran = false;
-    s.lr_fov_pairs = 0;
-    return enqueue_full(ctx, s, si, d_out);
+    const LevelRange r = given ? *given : LevelRange::cold(ctx->cfg.levels);
+    UCHK(enqueue_pyramids(ctx, s, si, d_rgbL, d_rgbR, n, W, H, stride, n == 1 ? r.to : -1, nullptr, true, 0, r.start == LevelRange::Zero ? -1 : r.from));
+    UCHK(enqueue_full(ctx, s, si, d_out, r));
+    if (n == 1 && r.whole() && lr_full_on(ctx)) UCHK(enqueue_full_lr(ctx, s, si, d_out[0]));
+    return r.full ? enqueue_prolong(ctx, s, si, r.to, d_out, r.full) : UGSM_OK;
 }
 
-// The seeded full-mode call (ugsm_submit_full_seeded; its refusals: ugsm_seeded.cpp): n pairs in lockstep from level `start` of their priors.
-// The pyramids stop at level max(start, 2); a lone pair's A planes come from the side stream for the levels start .. 0 as in any full-mode call.
-static int enqueue_match_full_seeded(ugsm_ctx *ctx, Slot &s, int si, int n, const uint8_t *const *d_rgbL, const uint8_t *const *d_rgbR, int W, int H,
-                                     int stride, const float *const *d_prior, int start, float *const *d_out)
+namespace {
+// The frame of a ugsm_submit_* of n pairs on device buffers, whose refusals have been made: the device, body(slot, b, k) for the pairs
+// b .. b + k - 1 -- all n in one (per == n) or one after the other (per == 1: the contexts of batch_runs_pair_by_pair) --, the completion mark.
+template <class Body>
+int submit_pairs(ugsm_ctx *ctx, Slot &s, int n, int per, Body &&body)
 {
-    UCHK(enqueue_pyramids(ctx, s, si, d_rgbL, d_rgbR, n, W, H, stride, n == 1 ? 0 : -1, nullptr, true, 0, start));
-    s.have_coarse = false;
-    s.lr_ran = false;
-    s.lr_fov_pairs = 0;
-    s.lr_full_pairs = 0;
-    return enqueue_full(ctx, s, si, d_out, false, start, d_prior);
+    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
+    for (int b = 0; b < n; b += per) UCHK(body(s, b, per));
+    return mark_done(ctx, s);
 }
+// ... of a call that has nothing to refuse between the slot's own refusals and the device
+template <class Body>
+int submit_pairs(ugsm_ctx *ctx, int slot, int n, int per, Body &&body)
+{
+    Slot *s;
+    UCHK(get_slot(ctx, slot, &s));
+    return submit_pairs(ctx, *s, n, per, body);
+}
+}  // namespace
+
+// The seeded full-mode call (ugsm_submit_full_seeded; its refusals: ugsm_seeded.cpp): n pairs in lockstep from level `start_level` of their priors.
 int ugsm::seeded_submit(ugsm_ctx *ctx, int slot, int n, const uint8_t *const *d_rgbL, const uint8_t *const *d_rgbR, int W, int H, int stride,
                         const float *const *d_prior, int start_level, float *const *d_out)
 {
-    Slot *s;
-    UCHK(get_slot(ctx, slot, &s));
-    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
-    const int per = batch_runs_pair_by_pair(ctx) ? 1 : n;  // (kernel_path 1: the pairs one after the other, as ugsm_submit_full_batch)
-    for (int b = 0; b < n; b += per)
-        UCHK(enqueue_match_full_seeded(ctx, *s, slot, per, d_rgbL + b, d_rgbR + b, W, H, stride, d_prior + b, start_level, d_out + b));
-    return mark_done(ctx, *s);
+    return submit_pairs(ctx, slot, n, batch_runs_pair_by_pair(ctx) ? 1 : n, [&](Slot &s, int b, int k) {
+        const LevelRange r = LevelRange::seeded(start_level, d_prior + b);
+        return enqueue_match_full(ctx, s, slot, k, d_rgbL + b, d_rgbR + b, W, H, stride, d_out + b, &r);
+    });
 }
 
 // The full-mode call in two halves (ugsm_submit_full_coarse, ugsm_submit_full_fine; their refusals: ugsm_coarse.cpp), n pairs in lockstep.
-// Coarse: the pyramids as ugsm_submit_full_batch builds them -- a lone pair's A planes from the side stream for the levels top .. e only --,
-// the levels top .. e, and the prolongation.  Fine: the pyramids up to level max(e - 1, 2) as the seeded call's, the levels e - 1 .. 0 from the
-// states of level e.
-static int enqueue_match_full_coarse(ugsm_ctx *ctx, Slot &s, int si, int n, const uint8_t *const *d_rgbL, const uint8_t *const *d_rgbR, int W, int H,
-                                     int stride, int e, float *const *d_state, float *const *d_full)
-{
-    UCHK(enqueue_pyramids(ctx, s, si, d_rgbL, d_rgbR, n, W, H, stride, n == 1 ? e : -1, nullptr, true));
-    s.have_coarse = false;
-    s.lr_ran = false;
-    s.lr_fov_pairs = 0;
-    s.lr_full_pairs = 0;
-    return enqueue_full_coarse(ctx, s, si, e, d_state, d_full);
-}
-static int enqueue_match_full_fine(ugsm_ctx *ctx, Slot &s, int si, int n, const uint8_t *const *d_rgbL, const uint8_t *const *d_rgbR, int W, int H,
-                                   int stride, const float *const *d_state, int e, float *const *d_out)
-{
-    UCHK(enqueue_pyramids(ctx, s, si, d_rgbL, d_rgbR, n, W, H, stride, n == 1 ? 0 : -1, nullptr, true, 0, e - 1));
-    s.have_coarse = false;
-    s.lr_ran = false;
-    s.lr_fov_pairs = 0;
-    s.lr_full_pairs = 0;
-    return enqueue_full(ctx, s, si, d_out, false, e - 1, nullptr, d_state);
-}
+// Coarse: the levels top .. stop_level into d_state, and the prolongation.  Fine: the levels state_level - 1 .. 0 from the states of state_level.
 int ugsm::coarse_submit(ugsm_ctx *ctx, int slot, int n, const uint8_t *const *d_rgbL, const uint8_t *const *d_rgbR, int W, int H, int stride,
                         int stop_level, float *const *d_state, float *const *d_full)
 {
-    Slot *s;
-    UCHK(get_slot(ctx, slot, &s));
-    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
-    const int per = batch_runs_pair_by_pair(ctx) ? 1 : n;  // (kernel_path 1: the pairs one after the other, as ugsm_submit_full_batch)
-    for (int b = 0; b < n; b += per)
-        UCHK(enqueue_match_full_coarse(ctx, *s, slot, per, d_rgbL + b, d_rgbR + b, W, H, stride, stop_level, d_state + b, d_full ? d_full + b : nullptr));
-    return mark_done(ctx, *s);
+    return submit_pairs(ctx, slot, n, batch_runs_pair_by_pair(ctx) ? 1 : n, [&](Slot &s, int b, int k) {
+        const LevelRange r = LevelRange::coarse(ctx->cfg.levels, stop_level, d_full ? d_full + b : nullptr);
+        return enqueue_match_full(ctx, s, slot, k, d_rgbL + b, d_rgbR + b, W, H, stride, d_state + b, &r);
+    });
 }
 int ugsm::fine_submit(ugsm_ctx *ctx, int slot, int n, const uint8_t *const *d_rgbL, const uint8_t *const *d_rgbR, int W, int H, int stride,
                       const float *const *d_state, int state_level, float *const *d_out)
 {
-    Slot *s;
-    UCHK(get_slot(ctx, slot, &s));
-    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
-    const int per = batch_runs_pair_by_pair(ctx) ? 1 : n;
-    for (int b = 0; b < n; b += per)
-        UCHK(enqueue_match_full_fine(ctx, *s, slot, per, d_rgbL + b, d_rgbR + b, W, H, stride, d_state + b, state_level, d_out + b));
-    return mark_done(ctx, *s);
+    return submit_pairs(ctx, slot, n, batch_runs_pair_by_pair(ctx) ? 1 : n, [&](Slot &s, int b, int k) {
+        const LevelRange r = LevelRange::fine(state_level, d_state + b);
+        return enqueue_match_full(ctx, s, slot, k, d_rgbL + b, d_rgbR + b, W, H, stride, d_out + b, &r);
+    });
 }
 namespace {
 // The starting fields of the fovea levels start .. F-1 of n entries from their priors, one launch (launch_restrict_stack): the rows from the
@@ -1653,10 +1629,6 @@ int enqueue_match_foveated_warm(ugsm_ctx *ctx, Slot &s, int si, int n, const uin
     FoveaWin win;
     UCHK(fovea_windows(ctx, W, H, n, off_x, off_y, win));
     UCHK(enqueue_pyramids(ctx, s, si, d_rgbL, d_rgbR, n, W, H, stride, -1, &win, false, 0, start));
-    s.have_coarse = false;
-    s.lr_ran = false;
-    s.lr_fov_pairs = 0;
-    s.lr_full_pairs = 0;
     const Shape sh = Shape::pairs(s);
     UCHK(enqueue_restrict_stack(ctx, s, si, n, s.w, s.h, F, d_prior, poff_x, poff_y, field, off_x, off_y, start, d_stack, s.d0, sh.stride));
     return enqueue_fovea_fine(ctx, s, si, sh, nullptr, off_x, off_y, d_stack, nullptr, nullptr, start);
@@ -1666,16 +1638,13 @@ int ugsm::fovea_warm_submit(ugsm_ctx *ctx, int slot, int n, const uint8_t *const
                             const int *off_y, const float *const *d_prior, const int *prior_off_x, const int *prior_off_y, int field, int start_level,
                             float *const *d_stack)
 {
-    Slot *s;
-    UCHK(get_slot(ctx, slot, &s));
-    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
     const int zeros[UGSM_MAX_BATCH] = {0};
     const int *ox = off_x ? off_x : zeros, *oy = off_y ? off_y : zeros, *px = prior_off_x ? prior_off_x : zeros, *py = prior_off_y ? prior_off_y : zeros;
     const int per = (n == 1 || fovea_batch_runs_pair_by_pair(ctx)) ? 1 : n;  // (kernel_path 1: the pairs one after the other, as ugsm_submit_foveated_batch)
-    for (int b = 0; b < n; b += per)
-        UCHK(enqueue_match_foveated_warm(ctx, *s, slot, per, d_rgbL + b, d_rgbR + b, W, H, stride, ox + b, oy + b, d_prior + b, px + b, py + b, field != 0,
-                                         start_level, d_stack + b));
-    return mark_done(ctx, *s);
+    return submit_pairs(ctx, slot, n, per, [&](Slot &s, int b, int k) {
+        return enqueue_match_foveated_warm(ctx, s, slot, k, d_rgbL + b, d_rgbR + b, W, H, stride, ox + b, oy + b, d_prior + b, px + b, py + b, field != 0,
+                                           start_level, d_stack + b);
+    });
 }
 namespace {
 
@@ -1721,8 +1690,6 @@ int enqueue_foveated_multi(ugsm_ctx *ctx, Slot &s, int si, const uint8_t *d_rgbL
                            const int *off_x, const int *off_y, float *state, float *const *d_stack)
 {
     const int F = ctx->cfg.fovea_levels;
-    s.lr_ran = false;
-    s.lr_fov_pairs = 0;
     FoveaWin win;
     UCHK(fovea_windows(ctx, W, H, n, off_x, off_y, win));
     win.later = true;
@@ -1766,8 +1733,6 @@ int enqueue_foveated_multi_checked(ugsm_ctx *ctx, Slot &s, int si, const uint8_t
                                    const int *off_x, const int *off_y, float *state, float *const *d_stack, float tau)
 {
     const int F = ctx->cfg.fovea_levels;
-    s.lr_ran = false;
-    s.lr_fov_pairs = 0;
     FoveaWin win;
     UCHK(fovea_windows(ctx, W, H, n, off_x, off_y, win));
     win.later = true;
@@ -1790,7 +1755,6 @@ int enqueue_foveated_multi_checked(ugsm_ctx *ctx, Slot &s, int si, const uint8_t
     }
     float *const cstate[2] = {state, s.lr + room.state};
     s.have_pyr = false;
-    s.have_coarse = false;
     UCHK(enqueue_fovea_coarse(ctx, s, si, Shape::coarse_both_directions(field), cstate));
     UCHK(enqueue_fovea_fine(ctx, s, si, sh, vstate, off_x, off_y, vstack, nullptr, nullptr));
     return enqueue_lr_stack_check(ctx, s, si, n, F, win.w, win.h, tau, d_stack, room.per, reinterpret_cast<unsigned long long *>(s.lr + room.cnt));
@@ -1986,9 +1950,158 @@ int copy_out_planes(ugsm_ctx *ctx, Slot &s, const float *d_src, size_t plane_flo
     return UGSM_OK;
 }
 
+// The counterpart of copy_out_planes for what a call reads besides its images (a prior, a state, a prior stack): three host planes of any kind
+// up into d_dst, on the slot's stream.
+int upload_planes(ugsm_ctx *ctx, Slot &s, float *d_dst, size_t plane_floats, const float *const src[3])
+{
+    for (int c = 0; c < 3; c++) HIPCHK(ctx, hipMemcpyAsync(d_dst + c * plane_floats, src[c], plane_floats * sizeof(float), hipMemcpyHostToDevice, s.st));
+    return UGSM_OK;
+}
+
+// a device stack's H, V and C planes (stackn floats each) down into three host buffers, on the slot's stream
+int download_stack(ugsm_ctx *ctx, Slot &s, const float *d_stack, size_t stackn, float *stackH, float *stackV, float *stackC)
+{
+    float *const dst[3] = {stackH, stackV, stackC};
+    for (int c = 0; c < 3; c++) HIPCHK(ctx, hipMemcpyAsync(dst[c], d_stack + c * stackn, stackn * sizeof(float), hipMemcpyDeviceToHost, s.st));
+    return UGSM_OK;
+}
+
+// what the non-blocking host-memory calls answer to a buffer that is not page-locked
+int not_pinned(ugsm_ctx *ctx, const char *entry)
+{
+    ctx->err = std::string(entry) + ": every host buffer must be page-locked (ugsm_host_alloc, hipHostMalloc or hipHostRegister)";
+    return UGSM_ERR_BAD_ARG;
+}
+
+// A blocking entry point that failed part-way: whatever it did enqueue -- uploads that read the caller's images, on the slot's stream or on
+// the side stream -- has drained before the caller hears of the failure.  "When the call returns the buffers are the caller's again"
+// holds for a failed call too (the reference exit()s instead, MatchGPULib.cpp passim).
+int drained(ugsm_ctx *ctx, int slot, int st)
+{
+    if (st == UGSM_OK || !ctx || slot < 0 || slot >= (int)ctx->slots.size()) return st;
+    const std::string why = ctx->err;
+    (void)ugsm_wait(ctx, slot);
+    ctx->err = why;
+    return st;
+}
+
+// The frame of every call that takes one pair's images from host memory, on a slot.  `sync`: the reference's call -- it returns when the results
+// are in place, in pageable or page-locked memory, and a failure part-way is drained --; otherwise everything is only enqueued and every buffer
+// must be page-locked.  The slot, the device, then what the call brings:
+//   check(slot, hout): the call's own refusals, in the call's own order, and `hout`, the floats of the slot's result staging it needs; a call
+//       that must hear UGSM_ERR_NOMEM before anything is enqueued grows its buffers, the staging included, here;
+//   the images go up into slot.rgbL / rgbR (stage_in), the result staging grows;
+//   match(slot): the uploads of what the call reads besides the images, and the match, into the staging it carves itself;
+//   down(slot): the results into the caller's memory;
+// and the wait, or the completion mark.
+template <class Check, class Match, class Down>
+int host_call(ugsm_ctx *ctx, int slot, bool sync, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, Check &&check, Match &&match,
+              Down &&down)
+{
+    auto enqueue = [&]() -> int {
+        Slot *s;
+        UCHK(get_slot(ctx, slot, &s));
+        HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
+        size_t hout = 0;
+        UCHK(check(*s, hout));
+        UCHK(stage_in(ctx, *s, rgbL, rgbR, W, H, stride));
+        UCHK(grow(ctx, s->hout, s->hout_cap, hout));
+        UCHK(match(*s));
+        UCHK(down(*s));
+        if (!sync) return mark_done(ctx, *s);
+        s->forked = false;  // (enqueued whole, as mark_done)
+        return ugsm_wait(ctx, slot);
+    };
+    return sync ? drained(ctx, slot, enqueue()) : enqueue();
+}
+// ... of a blocking call on slot 0 whose entry point has made every refusal (ugsm_seeded.cpp, ugsm_coarse.cpp, ugsm_fovea_seeded.cpp)
+template <class Match, class Down>
+int host_call(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, size_t hout_floats, Match &&match, Down &&down)
+{
+    auto size = [&](Slot &, size_t &hout) -> int {
+        hout = hout_floats;
+        return UGSM_OK;
+    };
+    return host_call(ctx, 0, true, rgbL, rgbR, W, H, stride, size, match, down);
+}
+
+// a full field's room in the result staging where something lies behind it: a multiple of 64 floats
+size_t field_room(size_t px) { return (3 * px + 63) & ~(size_t)63; }
+
 }  // namespace
 
 namespace ugsm {
+// The seeded service call (ugsm_match_full_seeded) on slot 0: images and prior up -- the prior's planes into the slot's result staging, where
+// the call then writes in place: the restriction reads before level 0 writes --, the match, the planes into caller memory of any kind.
+int seeded_match(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, const float *const prior[3], int start_level,
+                 float *const disp[3])
+{
+    const size_t n = (size_t)W * H;
+    auto match = [&](Slot &s) -> int {
+        UCHK(upload_planes(ctx, s, s.hout, n, prior));
+        const LevelRange r = LevelRange::seeded(start_level, &s.hout);
+        return enqueue_match_full(ctx, s, 0, 1, &s.rgbL, &s.rgbR, W, H, stride, &s.hout, &r);
+    };
+    return host_call(ctx, rgbL, rgbR, W, H, stride, 3 * n, match, [&](Slot &s) -> int {
+        prefault_planes(ctx, disp, n);
+        return copy_out_planes(ctx, s, s.hout, n, disp);
+    });
+}
+
+// The two halves as service calls (ugsm_match_full_coarse, ugsm_match_full_fine) on slot 0.  The slot's result staging holds the
+// full-resolution field (the prolongation, or the fine half's result) and, behind it, the state of level e (whose size the entry point has had).
+int coarse_match(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, int e, float *const state[3], float *const full[3])
+{
+    int w[UGSM_MAX_LEVELS], h[UGSM_MAX_LEVELS];
+    UCHK(level_dims(W, H, ctx->cfg.levels, w, h));  // (holds: the entry point has had level e's size from it)
+    const size_t n = (size_t)W * H, ne = (size_t)w[e] * h[e], room = full ? field_room(n) : 0;
+    auto match = [&](Slot &s) -> int {
+        float *const d_state = s.hout + room, *const d_full = full ? s.hout : nullptr;
+        const LevelRange r = LevelRange::coarse(ctx->cfg.levels, e, &d_full);
+        return enqueue_match_full(ctx, s, 0, 1, &s.rgbL, &s.rgbR, W, H, stride, &d_state, &r);
+    };
+    return host_call(ctx, rgbL, rgbR, W, H, stride, room + 3 * ne, match, [&](Slot &s) -> int {
+        if (full) prefault_planes(ctx, full, n);
+        UCHK(copy_out_planes(ctx, s, s.hout + room, ne, state));
+        return full ? copy_out_planes(ctx, s, s.hout, n, full) : UGSM_OK;
+    });
+}
+int fine_match(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, const float *const state[3], int e, float *const disp[3])
+{
+    int w[UGSM_MAX_LEVELS], h[UGSM_MAX_LEVELS];
+    UCHK(level_dims(W, H, ctx->cfg.levels, w, h));
+    const size_t n = (size_t)W * H, ne = (size_t)w[e] * h[e], room = field_room(n);
+    auto match = [&](Slot &s) -> int {
+        UCHK(upload_planes(ctx, s, s.hout + room, ne, state));
+        const float *const d_state = s.hout + room;
+        const LevelRange r = LevelRange::fine(e, &d_state);
+        return enqueue_match_full(ctx, s, 0, 1, &s.rgbL, &s.rgbR, W, H, stride, &s.hout, &r);
+    };
+    return host_call(ctx, rgbL, rgbR, W, H, stride, room + 3 * ne, match, [&](Slot &s) -> int {
+        prefault_planes(ctx, disp, n);
+        return copy_out_planes(ctx, s, s.hout, n, disp);
+    });
+}
+
+// The warm foveated service call (ugsm_match_foveated_warm) on slot 0: images and the prior stack's three planes up, the match into a second
+// stack beside it in the slot's result staging (the call is not in place: [prior 3 stackn][stack 3 stackn]), that stack's planes down.
+int fovea_warm_match(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, int off_x, int off_y, const float *const prior[3],
+                     int prior_off_x, int prior_off_y, int start_level, float *const stack[3])
+{
+    int fw, fh;
+    UCHK(ugsm_fovea_dims(W, H, ctx->cfg.levels, ctx->cfg.fovea_levels, &fw, &fh));
+    const size_t stackn = (size_t)ctx->cfg.fovea_levels * fw * fh;
+    auto match = [&](Slot &s) -> int {
+        UCHK(upload_planes(ctx, s, s.hout, stackn, prior));
+        const float *const d_prior = s.hout;
+        float *const d_stack = s.hout + 3 * stackn;
+        return enqueue_match_foveated_warm(ctx, s, 0, 1, &s.rgbL, &s.rgbR, W, H, stride, &off_x, &off_y, &d_prior, &prior_off_x, &prior_off_y, false,
+                                           start_level, &d_stack);
+    };
+    return host_call(ctx, rgbL, rgbR, W, H, stride, 6 * stackn, match,
+                     [&](Slot &s) -> int { return download_stack(ctx, s, s.hout + 3 * stackn, stackn, stack[0], stack[1], stack[2]); });
+}
+
 void ctx_host_copy(ugsm_ctx *ctx, void *dst, const void *src, size_t bytes) { team_copy(ctx, dst, src, bytes); }
 bool host_pinned(const void *p) { return is_pinned(p); }
 bool dev_env() { return dev_env_on(); }
@@ -2326,8 +2439,7 @@ int ugsm_submit_full(ugsm_ctx *ctx, int slot, const uint8_t *d_rgbL, const uint8
     UCHK(get_slot(ctx, slot, &s));
     if (!d_out) return UGSM_ERR_BAD_ARG;
     HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
-    UCHK(enqueue_pyramids(ctx, *s, slot, d_rgbL, d_rgbR, W, H, stride, 0, nullptr, true));
-    UCHK(enqueue_full_lr(ctx, *s, slot, d_out));
+    UCHK(enqueue_match_full(ctx, *s, slot, 1, &d_rgbL, &d_rgbR, W, H, stride, &d_out));
     return mark_done(ctx, *s);
 }
 
@@ -2383,10 +2495,8 @@ int ugsm_submit_full_batch(ugsm_ctx *ctx, int slot, int n, const uint8_t *const 
     if (n < 1 || n > UGSM_MAX_BATCH || !d_rgbL || !d_rgbR || !d_out) return UGSM_ERR_BAD_ARG;
     for (int b = 0; b < n; b++)
         if (!d_rgbL[b] || !d_rgbR[b] || !d_out[b]) return UGSM_ERR_BAD_ARG;
-    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
     const int per = batch_runs_pair_by_pair(ctx) ? 1 : n;  // pairs per match: one by one, or all in lockstep
-    for (int b = 0; b < n; b += per) UCHK(enqueue_match_full(ctx, *s, slot, per, d_rgbL + b, d_rgbR + b, W, H, stride, d_out + b));
-    return mark_done(ctx, *s);
+    return submit_pairs(ctx, *s, n, per, [&](Slot &sl, int b, int k) { return enqueue_match_full(ctx, sl, slot, k, d_rgbL + b, d_rgbR + b, W, H, stride, d_out + b); });
 }
 
 int ugsm_submit_foveated_batch(ugsm_ctx *ctx, int slot, int n, const uint8_t *const *d_rgbL, const uint8_t *const *d_rgbR, int W, int H, int stride,
@@ -2581,291 +2691,184 @@ int ugsm_wait_all(ugsm_ctx *ctx)
     return first;
 }
 
-// A blocking entry point that failed part-way: whatever it did enqueue -- uploads that read the caller's images, on the slot's stream or on
-// the side stream -- has drained before the caller hears of the failure.  "When the call returns the buffers are the caller's again"
-// holds for a failed call too (the reference exit()s instead, MatchGPULib.cpp passim).
-static int drained(ugsm_ctx *ctx, int slot, int st)
+// The service call on a slot: upload, pyramids, match, results into caller memory (host_call: `sync` = the reference's call).
+static int match_full_host(ugsm_ctx *ctx, int slot, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, float *dispH, float *dispV,
+                           float *dispC, bool sync)
 {
-    if (st == UGSM_OK || !ctx || slot < 0 || slot >= (int)ctx->slots.size()) return st;
-    const std::string why = ctx->err;
-    (void)ugsm_wait(ctx, slot);
-    ctx->err = why;
-    return st;
-}
-
-// The service call on a slot: upload, pyramids, match, results into caller memory.  `sync` = the reference's call (returns when the
-// planes are in place; pageable or page-locked memory); otherwise everything is only enqueued and every buffer must be page-locked.
-static int match_full_on_slot(ugsm_ctx *ctx, int slot, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, float *dispH,
-                              float *dispV, float *dispC, bool sync)
-{
-    Slot *s;
-    UCHK(get_slot(ctx, slot, &s));
-    if (!dispH || !dispV || !dispC) return UGSM_ERR_BAD_ARG;
-    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
-    if (!sync && !(is_pinned(rgbL) && is_pinned(rgbR) && is_pinned(dispH) && is_pinned(dispV) && is_pinned(dispC))) {
-        ctx->err = "ugsm_submit_full_host: every host buffer must be page-locked (ugsm_host_alloc, hipHostMalloc or hipHostRegister)";
-        return UGSM_ERR_BAD_ARG;
-    }
-    UCHK(stage_in(ctx, *s, rgbL, rgbR, W, H, stride));
-    const size_t n = (size_t)W * H;
-    UCHK(grow(ctx, s->hout, s->hout_cap, 3 * n));
-    UCHK(enqueue_pyramids(ctx, *s, slot, s->rgbL, s->rgbR, W, H, stride, 0, nullptr, true));
-    UCHK(enqueue_full_lr(ctx, *s, slot, s->hout));
     float *const dst[3] = {dispH, dispV, dispC};
-    if (sync) prefault_planes(ctx, dst, n);  // the GPU is busy for the next ~10 ms: touch the caller's result pages meanwhile
-    UCHK(copy_out_planes(ctx, *s, s->hout, n, dst));
-    if (sync) s->forked = false;  // (enqueued whole, as mark_done)
-    return sync ? ugsm_wait(ctx, slot) : mark_done(ctx, *s);
+    const size_t n = (size_t)W * H;
+    auto check = [&](Slot &, size_t &hout) -> int {
+        if (!dispH || !dispV || !dispC) return UGSM_ERR_BAD_ARG;
+        if (!sync && !(is_pinned(rgbL) && is_pinned(rgbR) && is_pinned(dispH) && is_pinned(dispV) && is_pinned(dispC))) return not_pinned(ctx, "ugsm_submit_full_host");
+        hout = 3 * n;
+        return UGSM_OK;
+    };
+    auto match = [&](Slot &s) -> int { return enqueue_match_full(ctx, s, slot, 1, &s.rgbL, &s.rgbR, W, H, stride, &s.hout); };
+    return host_call(ctx, slot, sync, rgbL, rgbR, W, H, stride, check, match, [&](Slot &s) -> int {
+        if (sync) prefault_planes(ctx, dst, n);  // the GPU is busy for the next ~10 ms: touch the caller's result pages meanwhile
+        return copy_out_planes(ctx, s, s.hout, n, dst);
+    });
 }
 
 int ugsm_match_full(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, float *dispH,
                     float *dispV, float *dispC)
 {
-    return drained(ctx, 0, match_full_on_slot(ctx, 0, rgbL, rgbR, W, H, stride, dispH, dispV, dispC, true));
+    return match_full_host(ctx, 0, rgbL, rgbR, W, H, stride, dispH, dispV, dispC, true);
 }
-
-// The checked service call on slot 0: upload, both directions in lockstep, the check, the forward planes (and the backward ones where asked
-// for) into caller memory of any kind.
-static int match_full_checked_on_slot0(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, float *dispH, float *dispV,
-                                       float *dispC, float *backH, float *backV, float *backC, float tau)
-{
-    Slot *s;
-    UCHK(get_slot(ctx, 0, &s));
-    if (!rgbL || !rgbR || !dispH || !dispV || !dispC) return UGSM_ERR_BAD_ARG;
-    const bool back = backH || backV || backC;
-    if (back && !(backH && backV && backC)) return ctx_fail(ctx, UGSM_ERR_BAD_ARG, "backH, backV and backC: all three or none");
-    UCHK(full_checked_check(ctx, 1, W, H, stride, tau));
-    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
-    UCHK(full_checked_bufs(ctx, *s, 1, back ? 0 : 1, W, H));
-    const size_t n = (size_t)W * H, room = (3 * n + 63) & ~(size_t)63;
-    UCHK(grow(ctx, s->hout, s->hout_cap, (back ? 2 : 1) * room));
-    UCHK(stage_in(ctx, *s, rgbL, rgbR, W, H, stride));
-    const uint8_t *const dL = s->rgbL, *const dR = s->rgbR;
-    float *const d_fwd = s->hout, *const d_bwd = back ? s->hout + room : nullptr;
-    UCHK(enqueue_full_checked(ctx, *s, 0, 1, &dL, &dR, W, H, stride, &d_fwd, back ? &d_bwd : nullptr, tau));
-    float *const dst[3] = {dispH, dispV, dispC}, *const bdst[3] = {backH, backV, backC};
-    prefault_planes(ctx, dst, n);
-    if (back) prefault_planes(ctx, bdst, n);
-    UCHK(copy_out_planes(ctx, *s, d_fwd, n, dst));
-    if (back) UCHK(copy_out_planes(ctx, *s, d_bwd, n, bdst));
-    s->forked = false;  // (enqueued whole, as mark_done)
-    return ugsm_wait(ctx, 0);
-}
-
-int ugsm_match_full_checked(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, float *dispH, float *dispV,
-                            float *dispC, float *backH, float *backV, float *backC, float tau)
-{
-    return drained(ctx, 0, match_full_checked_on_slot0(ctx, rgbL, rgbR, W, H, stride, dispH, dispV, dispC, backH, backV, backC, tau));
-}
-
-}  // extern "C"
-// The seeded service call (ugsm_match_full_seeded; its refusals: ugsm_seeded.cpp) on slot 0: images and prior up -- the prior's planes into
-// the slot's result staging, where the call then writes in place: the restriction reads before level 0 writes --, the match, the planes
-// into caller memory of any kind.
-static int seeded_match_on_slot0(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, const float *const prior[3], int start_level,
-                                 float *const disp[3])
-{
-    Slot *s;
-    UCHK(get_slot(ctx, 0, &s));
-    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
-    UCHK(stage_in(ctx, *s, rgbL, rgbR, W, H, stride));
-    const size_t n = (size_t)W * H;
-    UCHK(grow(ctx, s->hout, s->hout_cap, 3 * n));
-    for (int c = 0; c < 3; c++) HIPCHK(ctx, hipMemcpyAsync(s->hout + c * n, prior[c], n * sizeof(float), hipMemcpyHostToDevice, s->st));
-    const uint8_t *const dL = s->rgbL, *const dR = s->rgbR;
-    float *const field = s->hout;
-    UCHK(enqueue_match_full_seeded(ctx, *s, 0, 1, &dL, &dR, W, H, stride, &field, start_level, &field));
-    prefault_planes(ctx, disp, n);
-    UCHK(copy_out_planes(ctx, *s, s->hout, n, disp));
-    s->forked = false;  // (enqueued whole, as mark_done)
-    return ugsm_wait(ctx, 0);
-}
-int ugsm::seeded_match(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, const float *const prior[3], int start_level,
-                       float *const disp[3])
-{
-    return drained(ctx, 0, seeded_match_on_slot0(ctx, rgbL, rgbR, W, H, stride, prior, start_level, disp));
-}
-// The two halves as service calls (ugsm_match_full_coarse, ugsm_match_full_fine; their refusals: ugsm_coarse.cpp) on slot 0.  The slot's
-// result staging holds the full-resolution field (the prolongation, or the fine half's result) and, behind it, the state of level e.
-static int coarse_match_on_slot0(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, int e, float *const state[3],
-                                 float *const full[3])
-{
-    Slot *s;
-    UCHK(get_slot(ctx, 0, &s));
-    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
-    int w[UGSM_MAX_LEVELS], h[UGSM_MAX_LEVELS];
-    UCHK(level_dims(W, H, ctx->cfg.levels, w, h));
-    UCHK(stage_in(ctx, *s, rgbL, rgbR, W, H, stride));
-    const size_t n = (size_t)W * H, ne = (size_t)w[e] * h[e], room = full ? ((3 * n + 63) & ~(size_t)63) : 0;
-    UCHK(grow(ctx, s->hout, s->hout_cap, room + 3 * ne));
-    const uint8_t *const dL = s->rgbL, *const dR = s->rgbR;
-    float *const d_state = s->hout + room, *const d_full = full ? s->hout : nullptr;
-    UCHK(enqueue_match_full_coarse(ctx, *s, 0, 1, &dL, &dR, W, H, stride, e, &d_state, &d_full));
-    if (full) prefault_planes(ctx, full, n);
-    UCHK(copy_out_planes(ctx, *s, d_state, ne, state));
-    if (full) UCHK(copy_out_planes(ctx, *s, d_full, n, full));
-    s->forked = false;  // (enqueued whole, as mark_done)
-    return ugsm_wait(ctx, 0);
-}
-int ugsm::coarse_match(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, int stop_level, float *const state[3],
-                       float *const full[3])
-{
-    return drained(ctx, 0, coarse_match_on_slot0(ctx, rgbL, rgbR, W, H, stride, stop_level, state, full));
-}
-static int fine_match_on_slot0(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, const float *const state[3], int e,
-                               float *const disp[3])
-{
-    Slot *s;
-    UCHK(get_slot(ctx, 0, &s));
-    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
-    int w[UGSM_MAX_LEVELS], h[UGSM_MAX_LEVELS];
-    UCHK(level_dims(W, H, ctx->cfg.levels, w, h));
-    UCHK(stage_in(ctx, *s, rgbL, rgbR, W, H, stride));
-    const size_t n = (size_t)W * H, ne = (size_t)w[e] * h[e], room = (3 * n + 63) & ~(size_t)63;
-    UCHK(grow(ctx, s->hout, s->hout_cap, room + 3 * ne));
-    for (int c = 0; c < 3; c++) HIPCHK(ctx, hipMemcpyAsync(s->hout + room + c * ne, state[c], ne * sizeof(float), hipMemcpyHostToDevice, s->st));
-    const uint8_t *const dL = s->rgbL, *const dR = s->rgbR;
-    const float *const d_state = s->hout + room;
-    float *const field = s->hout;
-    UCHK(enqueue_match_full_fine(ctx, *s, 0, 1, &dL, &dR, W, H, stride, &d_state, e, &field));
-    prefault_planes(ctx, disp, n);
-    UCHK(copy_out_planes(ctx, *s, s->hout, n, disp));
-    s->forked = false;  // (enqueued whole, as mark_done)
-    return ugsm_wait(ctx, 0);
-}
-int ugsm::fine_match(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, const float *const state[3], int state_level,
-                     float *const disp[3])
-{
-    return drained(ctx, 0, fine_match_on_slot0(ctx, rgbL, rgbR, W, H, stride, state, state_level, disp));
-}
-// The warm foveated service call (ugsm_match_foveated_warm; its refusals: ugsm_fovea_seeded.cpp) on slot 0: images and the prior stack's three
-// planes up, the match into a second stack beside it in the slot's result staging (the call is not in place), that stack's planes down.
-static int fovea_warm_match_on_slot0(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, int off_x, int off_y,
-                                     const float *const prior[3], int prior_off_x, int prior_off_y, int start_level, float *const stack[3])
-{
-    Slot *s;
-    UCHK(get_slot(ctx, 0, &s));
-    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
-    int fw, fh;
-    UCHK(ugsm_fovea_dims(W, H, ctx->cfg.levels, ctx->cfg.fovea_levels, &fw, &fh));
-    UCHK(stage_in(ctx, *s, rgbL, rgbR, W, H, stride));
-    const size_t stackn = (size_t)ctx->cfg.fovea_levels * fw * fh;
-    UCHK(grow(ctx, s->hout, s->hout_cap, 6 * stackn));  // [prior 3 stackn][stack 3 stackn]
-    for (int c = 0; c < 3; c++) HIPCHK(ctx, hipMemcpyAsync(s->hout + c * stackn, prior[c], stackn * sizeof(float), hipMemcpyHostToDevice, s->st));
-    const uint8_t *const dL = s->rgbL, *const dR = s->rgbR;
-    const float *const d_prior = s->hout;
-    float *const d_stack = s->hout + 3 * stackn;
-    UCHK(enqueue_match_foveated_warm(ctx, *s, 0, 1, &dL, &dR, W, H, stride, &off_x, &off_y, &d_prior, &prior_off_x, &prior_off_y, false, start_level, &d_stack));
-    for (int c = 0; c < 3; c++) HIPCHK(ctx, hipMemcpyAsync(stack[c], d_stack + c * stackn, stackn * sizeof(float), hipMemcpyDeviceToHost, s->st));
-    s->forked = false;  // (enqueued whole, as mark_done)
-    return ugsm_wait(ctx, 0);
-}
-int ugsm::fovea_warm_match(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, int off_x, int off_y, const float *const prior[3],
-                           int prior_off_x, int prior_off_y, int start_level, float *const stack[3])
-{
-    return drained(ctx, 0, fovea_warm_match_on_slot0(ctx, rgbL, rgbR, W, H, stride, off_x, off_y, prior, prior_off_x, prior_off_y, start_level, stack));
-}
-extern "C" {
 
 int ugsm_submit_full_host(ugsm_ctx *ctx, int slot, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, float *dispH,
                           float *dispV, float *dispC)
 {
-    return match_full_on_slot(ctx, slot, rgbL, rgbR, W, H, stride, dispH, dispV, dispC, false);
+    return match_full_host(ctx, slot, rgbL, rgbR, W, H, stride, dispH, dispV, dispC, false);
 }
 
-// a device stack's H, V and C planes (stackn floats each) down into three host buffers, on the slot's stream
-static int download_stack(ugsm_ctx *ctx, Slot &s, const float *d_stack, size_t stackn, float *stackH, float *stackV, float *stackC)
+// The checked service call on slot 0: upload, both directions in lockstep, the check, the forward planes (and the backward ones where asked
+// for) into caller memory of any kind.  Its buffers, the result staging included, grow before the images go up.
+int ugsm_match_full_checked(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, float *dispH, float *dispV,
+                            float *dispC, float *backH, float *backV, float *backC, float tau)
 {
-    float *const dst[3] = {stackH, stackV, stackC};
-    for (int c = 0; c < 3; c++) HIPCHK(ctx, hipMemcpyAsync(dst[c], d_stack + c * stackn, stackn * sizeof(float), hipMemcpyDeviceToHost, s.st));
-    return UGSM_OK;
+    float *const dst[3] = {dispH, dispV, dispC}, *const bdst[3] = {backH, backV, backC};
+    const bool back = backH || backV || backC;
+    const size_t n = (size_t)W * H, room = field_room(n);
+    auto check = [&](Slot &s, size_t &hout) -> int {
+        if (!rgbL || !rgbR || !dispH || !dispV || !dispC) return UGSM_ERR_BAD_ARG;
+        if (back && !(backH && backV && backC)) return ctx_fail(ctx, UGSM_ERR_BAD_ARG, "backH, backV and backC: all three or none");
+        UCHK(full_checked_check(ctx, 1, W, H, stride, tau));
+        UCHK(full_checked_bufs(ctx, s, 1, back ? 0 : 1, W, H));
+        hout = (back ? 2 : 1) * room;
+        return grow(ctx, s.hout, s.hout_cap, hout);
+    };
+    auto match = [&](Slot &s) -> int {
+        float *const d_fwd = s.hout, *const d_bwd = back ? s.hout + room : nullptr;
+        return enqueue_full_checked(ctx, s, 0, 1, &s.rgbL, &s.rgbR, W, H, stride, &d_fwd, back ? &d_bwd : nullptr, tau);
+    };
+    return host_call(ctx, 0, true, rgbL, rgbR, W, H, stride, check, match, [&](Slot &s) -> int {
+        prefault_planes(ctx, dst, n);
+        if (back) prefault_planes(ctx, bdst, n);
+        UCHK(copy_out_planes(ctx, s, s.hout, n, dst));
+        return back ? copy_out_planes(ctx, s, s.hout + room, n, bdst) : UGSM_OK;
+    });
 }
 
-static int match_foveated_on_slot(ugsm_ctx *ctx, int slot, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, int off_x, int off_y,
-                                  float *stackH, float *stackV, float *stackC, float *pyrL, float *pyrR, bool sync)
+// One foveated pair from host memory.  The slot's result staging: [state 3*fn][stack 3*stackn][pyrL 3*stackn][pyrR 3*stackn], the pyramid
+// stacks where they are asked for.
+static int match_foveated_host(ugsm_ctx *ctx, int slot, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, int off_x, int off_y,
+                               float *stackH, float *stackV, float *stackC, float *pyrL, float *pyrR, bool sync)
 {
-    Slot *s;
-    UCHK(get_slot(ctx, slot, &s));
-    if (!stackH || !stackV || !stackC) return UGSM_ERR_BAD_ARG;
-    const int F = ctx->cfg.fovea_levels;
-    if (F < 2) return UGSM_ERR_BAD_ARG;
-    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
-    if (!sync) {
-        bool pinned = is_pinned(rgbL) && is_pinned(rgbR) && is_pinned(stackH) && is_pinned(stackV) && is_pinned(stackC);
-        if (pyrL) pinned = pinned && is_pinned(pyrL);
-        if (pyrR) pinned = pinned && is_pinned(pyrR);
-        if (!pinned) {
-            ctx->err = "ugsm_submit_foveated_host: every host buffer must be page-locked (ugsm_host_alloc, hipHostMalloc or hipHostRegister)";
-            return UGSM_ERR_BAD_ARG;
-        }
-    }
-    int fw, fh;
-    UCHK(ugsm_fovea_dims(W, H, ctx->cfg.levels, F, &fw, &fh));
-    UCHK(stage_in(ctx, *s, rgbL, rgbR, W, H, stride));
-    const size_t fn = (size_t)fw * fh, stackn = (size_t)F * fn;
-    // layout of hout: [state 3*fn][stack 3*stackn][pyrL 3*stackn][pyrR 3*stackn]
-    const size_t need = 3 * fn + 3 * stackn + (pyrL ? 3 * stackn : 0) + (pyrR ? 3 * stackn : 0);
-    UCHK(grow(ctx, s->hout, s->hout_cap, need));
-    float *d_state = s->hout, *d_stack = d_state + 3 * fn;
-    float *d_pl = pyrL ? d_stack + 3 * stackn : nullptr;
-    float *d_pr = pyrR ? d_stack + 3 * stackn + (pyrL ? 3 * stackn : 0) : nullptr;
-    const uint8_t *const dL = s->rgbL, *const dR = s->rgbR;
-    UCHK(enqueue_match_foveated(ctx, *s, slot, 1, &dL, &dR, W, H, stride, &off_x, &off_y, &d_state, &d_stack, d_pl ? &d_pl : nullptr, d_pr ? &d_pr : nullptr));
-    UCHK(download_stack(ctx, *s, d_stack, stackn, stackH, stackV, stackC));
-    if (pyrL) HIPCHK(ctx, hipMemcpyAsync(pyrL, d_pl, 3 * stackn * sizeof(float), hipMemcpyDeviceToHost, s->st));
-    if (pyrR) HIPCHK(ctx, hipMemcpyAsync(pyrR, d_pr, 3 * stackn * sizeof(float), hipMemcpyDeviceToHost, s->st));
-    if (sync) s->forked = false;  // (enqueued whole, as mark_done)
-    return sync ? ugsm_wait(ctx, slot) : mark_done(ctx, *s);
+    const int F = ctx ? ctx->cfg.fovea_levels : 0;
+    size_t fn = 0, stackn = 0;
+    float *d_stack = nullptr, *d_pl = nullptr, *d_pr = nullptr;
+    auto check = [&](Slot &, size_t &hout) -> int {
+        if (!stackH || !stackV || !stackC || F < 2) return UGSM_ERR_BAD_ARG;
+        if (!sync && !(is_pinned(rgbL) && is_pinned(rgbR) && is_pinned(stackH) && is_pinned(stackV) && is_pinned(stackC) && (!pyrL || is_pinned(pyrL)) &&
+                       (!pyrR || is_pinned(pyrR))))
+            return not_pinned(ctx, "ugsm_submit_foveated_host");
+        int fw, fh;
+        UCHK(ugsm_fovea_dims(W, H, ctx->cfg.levels, F, &fw, &fh));
+        fn = (size_t)fw * fh;
+        stackn = (size_t)F * fn;
+        hout = 3 * fn + 3 * stackn + (pyrL ? 3 * stackn : 0) + (pyrR ? 3 * stackn : 0);
+        return UGSM_OK;
+    };
+    auto match = [&](Slot &s) -> int {
+        float *d_state = s.hout;
+        d_stack = d_state + 3 * fn;
+        d_pl = pyrL ? d_stack + 3 * stackn : nullptr;
+        d_pr = pyrR ? d_stack + 3 * stackn + (pyrL ? 3 * stackn : 0) : nullptr;
+        return enqueue_match_foveated(ctx, s, slot, 1, &s.rgbL, &s.rgbR, W, H, stride, &off_x, &off_y, &d_state, &d_stack, d_pl ? &d_pl : nullptr,
+                                      d_pr ? &d_pr : nullptr);
+    };
+    return host_call(ctx, slot, sync, rgbL, rgbR, W, H, stride, check, match, [&](Slot &s) -> int {
+        UCHK(download_stack(ctx, s, d_stack, stackn, stackH, stackV, stackC));
+        if (pyrL) HIPCHK(ctx, hipMemcpyAsync(pyrL, d_pl, 3 * stackn * sizeof(float), hipMemcpyDeviceToHost, s.st));
+        if (pyrR) HIPCHK(ctx, hipMemcpyAsync(pyrR, d_pr, 3 * stackn * sizeof(float), hipMemcpyDeviceToHost, s.st));
+        return UGSM_OK;
+    });
 }
 
 int ugsm_match_foveated(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, int off_x,
                         int off_y, float *stackH, float *stackV, float *stackC, float *pyrL, float *pyrR)
 {
-    return drained(ctx, 0, match_foveated_on_slot(ctx, 0, rgbL, rgbR, W, H, stride, off_x, off_y, stackH, stackV, stackC, pyrL, pyrR, true));
-}
-
-// (tau: null = the plain call, else the checked one's threshold)
-static int match_foveated_multi_on_slot0(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, int n, const int *off_x,
-                                         const int *off_y, float *const *stackH, float *const *stackV, float *const *stackC, const float *tau = nullptr)
-{
-    Slot *s;
-    UCHK(get_slot(ctx, 0, &s));
-    if (!rgbL || !rgbR || !stackH || !stackV || !stackC) return UGSM_ERR_BAD_ARG;
-    for (int k = 0; k < n && k < UGSM_MAX_BATCH; k++)
-        if (!stackH[k] || !stackV[k] || !stackC[k]) return UGSM_ERR_BAD_ARG;
-    const int zeros[UGSM_MAX_BATCH] = {0};
-    int fw, fh;
-    UCHK(multi_check(ctx, n, W, H, stride, off_x, off_y, zeros, &fw, &fh, tau));
-    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
-    UCHK(tau ? multi_checked_bufs(ctx, *s, n, W, H, fw, fh) : multi_level_bufs(ctx, *s, n, W, H, fw, fh));
-    const size_t fn = (size_t)fw * fh, stackn = (size_t)ctx->cfg.fovea_levels * fn;
-    UCHK(grow(ctx, s->hout, s->hout_cap, 3 * fn + (size_t)n * 3 * stackn));  // [state 3 fn][n stacks of 3 stackn]
-    UCHK(stage_in(ctx, *s, rgbL, rgbR, W, H, stride));
-    float *d_stack[UGSM_MAX_BATCH];
-    for (int k = 0; k < n; k++) d_stack[k] = s->hout + 3 * fn + (size_t)k * 3 * stackn;
-    if (tau) UCHK(enqueue_foveated_multi_checked(ctx, *s, 0, s->rgbL, s->rgbR, W, H, stride, n, off_x, off_y, s->hout, d_stack, *tau));
-    else UCHK(enqueue_foveated_multi(ctx, *s, 0, s->rgbL, s->rgbR, W, H, stride, n, off_x, off_y, s->hout, d_stack));
-    for (int k = 0; k < n; k++) UCHK(download_stack(ctx, *s, d_stack[k], stackn, stackH[k], stackV[k], stackC[k]));
-    s->forked = false;  // (enqueued whole, as mark_done)
-    return ugsm_wait(ctx, 0);
-}
-
-int ugsm_match_foveated_multi(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, int n, const int *off_x,
-                              const int *off_y, float *const *stackH, float *const *stackV, float *const *stackC)
-{
-    return drained(ctx, 0, match_foveated_multi_on_slot0(ctx, rgbL, rgbR, W, H, stride, n, off_x, off_y, stackH, stackV, stackC));
-}
-
-int ugsm_match_foveated_multi_checked(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, int n, const int *off_x,
-                                      const int *off_y, float *const *stackH, float *const *stackV, float *const *stackC, float tau)
-{
-    return drained(ctx, 0, match_foveated_multi_on_slot0(ctx, rgbL, rgbR, W, H, stride, n, off_x, off_y, stackH, stackV, stackC, &tau));
+    return match_foveated_host(ctx, 0, rgbL, rgbR, W, H, stride, off_x, off_y, stackH, stackV, stackC, pyrL, pyrR, true);
 }
 
 int ugsm_submit_foveated_host(ugsm_ctx *ctx, int slot, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, int off_x,
                               int off_y, float *stackH, float *stackV, float *stackC, float *pyrL, float *pyrR)
 {
-    return match_foveated_on_slot(ctx, slot, rgbL, rgbR, W, H, stride, off_x, off_y, stackH, stackV, stackC, pyrL, pyrR, false);
+    return match_foveated_host(ctx, slot, rgbL, rgbR, W, H, stride, off_x, off_y, stackH, stackV, stackC, pyrL, pyrR, false);
+}
+
+// n windows of one pair from host memory, on slot 0 (tau: null = the plain call, else the checked one's threshold).  The slot's result staging:
+// [state 3 fn][n stacks of 3 stackn]; the call's buffers, the staging included, grow before the images go up.
+static int match_foveated_multi_host(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, int n, const int *off_x,
+                                     const int *off_y, float *const *stackH, float *const *stackV, float *const *stackC, const float *tau)
+{
+    const int zeros[UGSM_MAX_BATCH] = {0};
+    size_t stackn = 0;
+    float *d_stack[UGSM_MAX_BATCH];
+    auto check = [&](Slot &s, size_t &hout) -> int {
+        if (!rgbL || !rgbR || !stackH || !stackV || !stackC) return UGSM_ERR_BAD_ARG;
+        for (int k = 0; k < n && k < UGSM_MAX_BATCH; k++)
+            if (!stackH[k] || !stackV[k] || !stackC[k]) return UGSM_ERR_BAD_ARG;
+        int fw, fh;
+        UCHK(multi_check(ctx, n, W, H, stride, off_x, off_y, zeros, &fw, &fh, tau));
+        UCHK(tau ? multi_checked_bufs(ctx, s, n, W, H, fw, fh) : multi_level_bufs(ctx, s, n, W, H, fw, fh));
+        const size_t fn = (size_t)fw * fh;
+        stackn = (size_t)ctx->cfg.fovea_levels * fn;
+        hout = 3 * fn + (size_t)n * 3 * stackn;
+        UCHK(grow(ctx, s.hout, s.hout_cap, hout));
+        for (int k = 0; k < n; k++) d_stack[k] = s.hout + 3 * fn + (size_t)k * 3 * stackn;
+        return UGSM_OK;
+    };
+    auto match = [&](Slot &s) -> int {
+        return tau ? enqueue_foveated_multi_checked(ctx, s, 0, s.rgbL, s.rgbR, W, H, stride, n, off_x, off_y, s.hout, d_stack, *tau)
+                   : enqueue_foveated_multi(ctx, s, 0, s.rgbL, s.rgbR, W, H, stride, n, off_x, off_y, s.hout, d_stack);
+    };
+    return host_call(ctx, 0, true, rgbL, rgbR, W, H, stride, check, match, [&](Slot &s) -> int {
+        for (int k = 0; k < n; k++) UCHK(download_stack(ctx, s, d_stack[k], stackn, stackH[k], stackV[k], stackC[k]));
+        return UGSM_OK;
+    });
+}
+
+int ugsm_match_foveated_multi(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, int n, const int *off_x,
+                              const int *off_y, float *const *stackH, float *const *stackV, float *const *stackC)
+{
+    return match_foveated_multi_host(ctx, rgbL, rgbR, W, H, stride, n, off_x, off_y, stackH, stackV, stackC, nullptr);
+}
+
+int ugsm_match_foveated_multi_checked(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, int n, const int *off_x,
+                                      const int *off_y, float *const *stackH, float *const *stackV, float *const *stackC, float tau)
+{
+    return match_foveated_multi_host(ctx, rgbL, rgbR, W, H, stride, n, off_x, off_y, stackH, stackV, stackC, &tau);
+}
+
+// match(L, R, fov == 1), MatchGPULib.cpp:354-360: foveated matching, then hierarchicalDisparity on the stacks.  The slot's result staging:
+// [state][stack][full field]
+int ugsm_match_foveated_full(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, int off_x, int off_y,
+                             float *outH, float *outV, float *outC)
+{
+    float *const dst[3] = {outH, outV, outC};
+    const int F = ctx ? ctx->cfg.fovea_levels : 0;
+    const size_t n = (size_t)W * H;
+    size_t fn = 0, stackn = 0;
+    auto check = [&](Slot &, size_t &hout) -> int {
+        if (!outH || !outV || !outC || F < 2) return UGSM_ERR_BAD_ARG;
+        int fw, fh;
+        UCHK(ugsm_fovea_dims(W, H, ctx->cfg.levels, F, &fw, &fh));
+        fn = (size_t)fw * fh;
+        stackn = (size_t)F * fn;
+        hout = 3 * fn + 3 * stackn + 3 * n;
+        return UGSM_OK;
+    };
+    auto match = [&](Slot &s) -> int {
+        float *d_state = s.hout, *d_stack = d_state + 3 * fn;
+        UCHK(enqueue_match_foveated(ctx, s, 0, 1, &s.rgbL, &s.rgbR, W, H, stride, &off_x, &off_y, &d_state, &d_stack, nullptr, nullptr));
+        return ugsm_reconstruct_full(ctx, 0, d_stack, d_stack + stackn, d_stack + 2 * stackn, W, H, off_x, off_y, d_stack + 3 * stackn);
+    };
+    return host_call(ctx, 0, true, rgbL, rgbR, W, H, stride, check, match, [&](Slot &s) -> int {
+        prefault_planes(ctx, dst, n);
+        return copy_out_planes(ctx, s, s.hout + 3 * fn + 3 * stackn, n, dst);
+    });
 }
 
 // ---- batches from page-locked host memory (round 4): the uploads of all pairs, ONE batched match, the downloads of all pairs, enqueued on
@@ -2875,6 +2878,14 @@ static bool all_pinned(const void *const *p, int n)
     for (int b = 0; b < n; b++)
         if (!p[b] || !is_pinned(p[b])) return false;
     return true;
+}
+// what both calls refuse behind their null arrays: an image or a result plane, of any pair, that is null or not page-locked
+static int batch_pinned(ugsm_ctx *ctx, const char *entry, int n, const uint8_t *const *rgbL, const uint8_t *const *rgbR, float *const *outH,
+                        float *const *outV, float *const *outC)
+{
+    for (const void *const *p : {(const void *const *)rgbL, (const void *const *)rgbR, (const void *const *)outH, (const void *const *)outV, (const void *const *)outC})
+        if (!all_pinned(p, n)) return not_pinned(ctx, entry);
+    return UGSM_OK;
 }
 static int stage_in_batch(ugsm_ctx *ctx, Slot &s, int n, const uint8_t *const *rgbL, const uint8_t *const *rgbR, int W, int H, int stride,
                           const uint8_t **dL, const uint8_t **dR)
@@ -2903,19 +2914,15 @@ int ugsm_submit_full_batch_host(ugsm_ctx *ctx, int slot, int n, const uint8_t *c
     UCHK(get_slot(ctx, slot, &s));
     if (n < 1 || n > UGSM_MAX_BATCH || !rgbL || !rgbR || !dispH || !dispV || !dispC) return UGSM_ERR_BAD_ARG;
     HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
-    if (!all_pinned((const void *const *)rgbL, n) || !all_pinned((const void *const *)rgbR, n) || !all_pinned((const void *const *)dispH, n) ||
-        !all_pinned((const void *const *)dispV, n) || !all_pinned((const void *const *)dispC, n)) {
-        ctx->err = "ugsm_submit_full_batch_host: every host buffer must be page-locked (ugsm_host_alloc, hipHostMalloc or hipHostRegister)";
-        return UGSM_ERR_BAD_ARG;
-    }
+    UCHK(batch_pinned(ctx, "ugsm_submit_full_batch_host", n, rgbL, rgbR, dispH, dispV, dispC));
     if (n == 1 || batch_runs_pair_by_pair(ctx)) {
-        for (int b = 0; b < n; b++) UCHK(match_full_on_slot(ctx, slot, rgbL[b], rgbR[b], W, H, stride, dispH[b], dispV[b], dispC[b], false));
+        for (int b = 0; b < n; b++) UCHK(match_full_host(ctx, slot, rgbL[b], rgbR[b], W, H, stride, dispH[b], dispV[b], dispC[b], false));
         return UGSM_OK;
     }
     const uint8_t *dL[UGSM_MAX_BATCH], *dR[UGSM_MAX_BATCH];
     UCHK(stage_in_batch(ctx, *s, n, rgbL, rgbR, W, H, stride, dL, dR));
-    const size_t px = (size_t)W * H, per = (3 * px + 63) & ~(size_t)63;
-    UCHK(grow(ctx, s->hout, s->hout_cap, std::max(per * n, s->hout_cap)));
+    const size_t px = (size_t)W * H, per = field_room(px);
+    UCHK(grow(ctx, s->hout, s->hout_cap, per * n));
     float *out[UGSM_MAX_BATCH];
     for (int b = 0; b < n; b++) out[b] = s->hout + b * per;
     UCHK(enqueue_match_full(ctx, *s, slot, n, dL, dR, W, H, stride, out));
@@ -2935,16 +2942,12 @@ int ugsm_submit_foveated_batch_host(ugsm_ctx *ctx, int slot, int n, const uint8_
     const int F = ctx->cfg.fovea_levels;
     if (F < 2) return UGSM_ERR_BAD_ARG;
     HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
-    if (!all_pinned((const void *const *)rgbL, n) || !all_pinned((const void *const *)rgbR, n) || !all_pinned((const void *const *)stackH, n) ||
-        !all_pinned((const void *const *)stackV, n) || !all_pinned((const void *const *)stackC, n)) {
-        ctx->err = "ugsm_submit_foveated_batch_host: every host buffer must be page-locked (ugsm_host_alloc, hipHostMalloc or hipHostRegister)";
-        return UGSM_ERR_BAD_ARG;
-    }
+    UCHK(batch_pinned(ctx, "ugsm_submit_foveated_batch_host", n, rgbL, rgbR, stackH, stackV, stackC));
     int zeros[UGSM_MAX_BATCH] = {0};
     const int *ox = off_x ? off_x : zeros, *oy = off_y ? off_y : zeros;
     if (n == 1 || fovea_batch_runs_pair_by_pair(ctx)) {
         for (int b = 0; b < n; b++)
-            UCHK(match_foveated_on_slot(ctx, slot, rgbL[b], rgbR[b], W, H, stride, ox[b], oy[b], stackH[b], stackV[b], stackC[b], nullptr, nullptr, false));
+            UCHK(match_foveated_host(ctx, slot, rgbL[b], rgbR[b], W, H, stride, ox[b], oy[b], stackH[b], stackV[b], stackC[b], nullptr, nullptr, false));
         return UGSM_OK;
     }
     int fw, fh;
@@ -2953,7 +2956,7 @@ int ugsm_submit_foveated_batch_host(ugsm_ctx *ctx, int slot, int n, const uint8_
     UCHK(stage_in_batch(ctx, *s, n, rgbL, rgbR, W, H, stride, dL, dR));
     const size_t fn = (size_t)fw * fh, stackn = (size_t)F * fn;
     const size_t st_per = fovea_field_room(fw, fh), sk_per = (3 * stackn + 63) & ~(size_t)63;  // hout: [states n x st_per][stacks n x sk_per]
-    UCHK(grow(ctx, s->hout, s->hout_cap, std::max(n * (st_per + sk_per), s->hout_cap)));
+    UCHK(grow(ctx, s->hout, s->hout_cap, n * (st_per + sk_per)));
     float *state[UGSM_MAX_BATCH], *stack[UGSM_MAX_BATCH];
     for (int b = 0; b < n; b++) {
         state[b] = s->hout + b * st_per;
@@ -2962,37 +2965,6 @@ int ugsm_submit_foveated_batch_host(ugsm_ctx *ctx, int slot, int n, const uint8_
     UCHK(enqueue_match_foveated(ctx, *s, slot, n, dL, dR, W, H, stride, ox, oy, state, stack, nullptr, nullptr));
     for (int b = 0; b < n; b++) UCHK(download_stack(ctx, *s, stack[b], stackn, stackH[b], stackV[b], stackC[b]));
     return mark_done(ctx, *s);
-}
-
-// match(L, R, fov == 1), MatchGPULib.cpp:354-360: foveated matching, then hierarchicalDisparity on the stacks
-static int match_foveated_full_on_slot0(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, int off_x, int off_y,
-                                        float *outH, float *outV, float *outC)
-{
-    Slot *s;
-    UCHK(get_slot(ctx, 0, &s));
-    if (!outH || !outV || !outC) return UGSM_ERR_BAD_ARG;
-    const int F = ctx->cfg.fovea_levels;
-    if (F < 2) return UGSM_ERR_BAD_ARG;
-    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
-    int fw, fh;
-    UCHK(ugsm_fovea_dims(W, H, ctx->cfg.levels, F, &fw, &fh));
-    UCHK(stage_in(ctx, *s, rgbL, rgbR, W, H, stride));
-    const size_t fn = (size_t)fw * fh, stackn = (size_t)F * fn, n = (size_t)W * H;
-    UCHK(grow(ctx, s->hout, s->hout_cap, 3 * fn + 3 * stackn + 3 * n));  // [state][stack][full field]
-    float *d_state = s->hout, *d_stack = d_state + 3 * fn, *d_full = d_stack + 3 * stackn;
-    const uint8_t *const dL = s->rgbL, *const dR = s->rgbR;
-    UCHK(enqueue_match_foveated(ctx, *s, 0, 1, &dL, &dR, W, H, stride, &off_x, &off_y, &d_state, &d_stack, nullptr, nullptr));
-    UCHK(ugsm_reconstruct_full(ctx, 0, d_stack, d_stack + stackn, d_stack + 2 * stackn, W, H, off_x, off_y, d_full));
-    float *const dst[3] = {outH, outV, outC};
-    prefault_planes(ctx, dst, n);
-    UCHK(copy_out_planes(ctx, *s, d_full, n, dst));
-    s->forked = false;  // (enqueued whole, as mark_done)
-    return ugsm_wait(ctx, 0);
-}
-int ugsm_match_foveated_full(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, int off_x, int off_y,
-                             float *outH, float *outV, float *outC)
-{
-    return drained(ctx, 0, match_foveated_full_on_slot0(ctx, rgbL, rgbR, W, H, stride, off_x, off_y, outH, outV, outC));
 }
 
 // ---- stage-level ------------------------------------------------------------------------

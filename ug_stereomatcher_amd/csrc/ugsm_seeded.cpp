@@ -6,26 +6,13 @@
 
 using namespace ugsm;
 
-// What both calls refuse beyond their null pointers.
+// What both calls refuse beyond their null pointers: the shared refusals (refuse_common) around the call's own level.
 static int seeded_check(ugsm_ctx *ctx, int n, int W, int H, int stride, int start_level)
 {
-    const ugsm_config &cfg = ctx_config(ctx);
-    const CtxHooks &hooks = ctx_hooks(ctx);
-    if (n < 1 || n > UGSM_MAX_BATCH) return ctx_fail(ctx, UGSM_ERR_BAD_ARG, "the seeded full-mode call takes 1 .. UGSM_MAX_BATCH pairs");
-    if (start_level < 0 || start_level >= cfg.levels) return ctx_fail(ctx, UGSM_ERR_BAD_ARG, "the seeded full-mode call: start_level outside 0 .. levels - 1");
-    // (the early exit compares a level's fields pair by pair through a third buffer and a host round trip: no lockstep, and no use beside a prior)
-    if (cfg.early_exit_threshold > 0.0f) return ctx_fail(ctx, UGSM_ERR_BAD_ARG, "the seeded full-mode call: not with early_exit_threshold > 0");
-    if (hooks.queue_busy && !hooks.queue_calling)
-        return ctx_fail(ctx, UGSM_ERR_STATE, "pairs enqueued with ugsm_enqueue_* are outstanding: the slots belong to the queue until ugsm_next_done has reported them all");
-    float tau = 0.0f;
-    int modes = 0;
-    if (ugsm_get_lr_check(ctx, &tau, &modes) == UGSM_OK && tau > 0.0f && (modes & UGSM_LR_FULL))
-        return ctx_fail(ctx, UGSM_ERR_STATE, "the full-mode LR check is on (ugsm_set_lr_check): there is no seeded checked call");
     int w[UGSM_MAX_LEVELS], h[UGSM_MAX_LEVELS];
-    const int st = ugsm_level_dims(W, H, cfg.levels, w, h);
-    if (st != UGSM_OK) return st;
-    if (stride < input_bpp(hooks.input_format) * W) return UGSM_ERR_SIZE_MISMATCH;
-    return UGSM_OK;
+    const bool bad = start_level < 0 || start_level >= ctx_config(ctx).levels;
+    return refuse_common(ctx, "the seeded full-mode call", UGSM_LR_FULL, n, bad ? "the seeded full-mode call: start_level outside 0 .. levels - 1" : nullptr, W, H,
+                         stride, w, h);
 }
 
 extern "C" {

@@ -303,9 +303,33 @@ bool fovea_batch_runs_pair_by_pair(const ugsm_ctx *ctx);
 int get_slot(ugsm_ctx *ctx, int slot, Slot **out, bool enqueues = true);
 int mark_done(ugsm_ctx *ctx, Slot &s);
 int stage_in(ugsm_ctx *ctx, Slot &s, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride);
-// "Match n pairs on this slot", as every batch entry point and the queue's cloud calls enqueue it: one pair, or n > 1 pairs in lockstep
+// Which full-frame levels a descent runs -- `from` down to `to` -- and what level `from` starts from (enqueue_descent, ugsm_runtime.cpp).  Made by
+// the four makers alone, so a start always comes with its source and its levels: the zero seed with the top level, a prior or a state with the
+// level it belongs to, and never two of them.  The levels themselves are the entry points' to have checked against the pyramid
+// (ugsm_seeded.cpp, ugsm_coarse.cpp: 0 <= to <= from < levels).
+struct LevelRange {
+    enum Start { Zero, Prior, State };
+    const int from, to;
+    const Start start;
+    const float *const *const source;  // the entries' full-resolution priors (Prior) or their fields of level from + 1 (State)
+    float *const *const full;          // the coarse half: where the pairs' level-`to` fields are then prolonged to (null, or null entries: nowhere)
+    // the whole call: every level from the zero seed
+    static LevelRange cold(int levels) { return {levels - 1, 0, Zero, nullptr, nullptr}; }
+    // ugsm_submit_full_seeded: the levels start .. 0 from the pairs' priors
+    static LevelRange seeded(int start, const float *const *prior) { return {start, 0, Prior, prior, nullptr}; }
+    // ugsm_submit_full_coarse, and the coarse phase of a foveated call: the levels top .. e from the zero seed.  e == 0 without `full` IS the cold call
+    static LevelRange coarse(int levels, int e, float *const *full = nullptr) { return {levels - 1, e, Zero, nullptr, full}; }
+    // ugsm_submit_full_fine: the levels e - 1 .. 0 from the pairs' fields of level e
+    static LevelRange fine(int e, const float *const *state) { return {e - 1, 0, State, state, nullptr}; }
+    bool whole() const { return start == Zero && to == 0 && !full; }
+
+  private:
+    LevelRange(int f, int t, Start s, const float *const *src, float *const *fl) : from(f), to(t), start(s), source(src), full(fl) {}
+};
+// "Match n pairs on this slot", as every batch entry point and the queue's cloud calls enqueue it: one pair, or n > 1 pairs in lockstep, over
+// the levels of `range` (null: the cold call) -- level range->to's fields into d_out
 int enqueue_match_full(ugsm_ctx *ctx, Slot &s, int si, int n, const uint8_t *const *d_rgbL, const uint8_t *const *d_rgbR, int W, int H, int stride,
-                       float *const *d_out);
+                       float *const *d_out, const LevelRange *range = nullptr);
 int enqueue_match_foveated(ugsm_ctx *ctx, Slot &s, int si, int n, const uint8_t *const *d_rgbL, const uint8_t *const *d_rgbR, int W, int H, int stride,
                            const int *off_x, const int *off_y, float *const *state, float *const *d_stack, float *const *d_pyrL, float *const *d_pyrR);
 // ---- ... and ugsm_cloud.cpp for ugsm_create: the queue's way to the cloud work (CtxHooks, ugsm_internal.hpp) ----------------------------
