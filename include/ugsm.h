@@ -209,11 +209,17 @@ int ugsm_plan_level(const ugsm_config *cfg, int alone, int W, int H, ugsm_level_
  *   UGSM_INPUT_BGRA8  4 bytes, (b2, b1, b0), alpha ignored
  *   UGSM_INPUT_MONO8  1 byte, (v, v, v)
  * `stride` stays bytes per row and must be at least ugsm_input_bytes_per_pixel(F) * W (UGSM_ERR_SIZE_MISMATCH otherwise; the cloud
- * calls answer UGSM_ERR_BAD_ARG, as for rgb8).  Device pointers need no alignment.
+ * calls answer UGSM_ERR_BAD_ARG, as for rgb8).  Device pointers need no alignment (the images'; the float buffers: the last paragraph).
  * The format is a setting of the context that any call may change, and it is CAPTURED WHEN AN IMAGE IS HANDED OVER: by ugsm_match_*,
  * ugsm_submit_* (the pyramids, the shard), ugsm_stage_pyramid and the cloud calls when they are made, and by ugsm_enqueue_* for the pair
  * it enqueues -- the library forms the queue's calls later, each with the format its pairs were enqueued in (pairs of different formats
- * never share a call). */
+ * never share a call).
+ *
+ * ALIGNMENT OF FLOAT BUFFERS.  Every `float *` device buffer of this header, read or written -- d_out, d_stack, d_pyrL / d_pyrR, d_back,
+ * d_prior, d_state, d_full, d_out3, d_xyz, the disparity, confidence and warp planes, the fields of the ugsm_stage_* entry points -- needs
+ * 4-byte alignment and nothing more: a buffer at base + 4, + 8 or + 12 bytes of an allocation gives the same results bit for bit, and no
+ * call writes outside the floats it is given (tests/test_gpu_caller_buffers.py).  The buffers that need more keep their refusals
+ * (UGSM_ERR_BAD_ARG): d_points 16 bytes, the count words (d_count, d_level_counts, d_entry_counts) and the residual's sums 8 bytes. */
 #define UGSM_INPUT_RGB8  0
 #define UGSM_INPUT_BGR8  1
 #define UGSM_INPUT_RGBA8 2
