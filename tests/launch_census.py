@@ -1,9 +1,10 @@
 """The launch census: which kernels a call launches, level by level and in which groups, and what it writes.
 
-The parity tests prove the bytes of every call mode; nothing in them proves that a change to the code that SEQUENCES a call (ugsm_runtime.cpp:
-run_level, the descent, the fovea phases) did not turn one batched launch into n launches or regroup them.  profile_events = 2 makes
-ugsm_get_kernel_stats report, per (kernel name, level) of slot 0, `launches` and `pixel_launches` -- the latter sums pixels x entries of each
-launch, so it encodes the grouping.  One call at a time on a fresh one-slot context (so that `alone` is deterministic) gives one census:
+The parity tests prove the bytes of every call mode; nothing in them proves that a change to the code that SEQUENCES a call (ugsm_levels.cpp:
+run_level; ugsm_full.cpp: the descent; ugsm_fovea.cpp: the fovea phases) did not turn one batched launch into n launches or regroup them.
+profile_events = 2 makes ugsm_get_kernel_stats report, per (kernel name, level) of slot 0, `launches` and `pixel_launches` -- the latter sums pixels x
+entries of each launch, so it encodes the grouping.  One call at a time on a fresh one-slot context (so that `alone` is deterministic) gives one
+census:
 
     {"launches": [[name, level, launches, pixel_launches], ...] sorted, launches > 0 only,
      "sha256":   [the SHA-256 of each output buffer's bytes, in the order the call was given them]}

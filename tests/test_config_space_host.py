@@ -15,7 +15,7 @@ from ug_stereomatcher_amd import _lib
 
 TILED, MARCH, SMALL, STAGED, MARCH4 = 0, 1, 2, 3, 4
 MARCHING = (MARCH, MARCH4)
-K_BATCH_MAX_PIXELS = 9_000_000          # kBatchMaxPixels (ugsm_runtime.cpp): levels up to here are one launch for all pairs of a batched call
+K_BATCH_MAX_PIXELS = 9_000_000          # kBatchMaxPixels (ugsm_policy.cpp): levels up to here are one launch for all pairs of a batched call
 THRESHOLDS = (50_000, 150_000, 400_000, 3_000_000, K_BATCH_MAX_PIXELS)   # the shared / alone latency reach, the marching default, k_cost_march4's top
 
 MARCH_MIN = (0, 1, 49_999, 50_000, 150_000, 400_000, 3_000_000, 3_000_001, 10**7, 2**28, 2**31 - 1)

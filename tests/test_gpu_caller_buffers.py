@@ -1,7 +1,7 @@
 """Caller-owned float buffers at 4-byte bases between guard bands (include/ugsm.h: "float buffers need 4-byte alignment and nothing more").
 
 Several kernels choose a 16-byte or 8-byte access form from a level's WIDTH alone; a caller's buffer at base + 4, + 8 or + 12 bytes is where
-such a form would meet an address the compiler was told is aligned.  Where that happens today (ugsm_runtime.cpp):
+such a form would meet an address the compiler was told is aligned.  Where that happens today (ugsm_full.cpp, ugsm_levels.cpp):
   * K-smooth's quad store (k_smooth_fused, st_quad<true> when W % 4 == 0): level 0's last launch of a full-mode call writes d_out / d_back /
     d_state of level 0 itself (enqueue_descent's direct_out).  The template instances are compiled one by one, so the full-mode calls run once
     per tile class -- the 112-column tile at its fixed height of 36 rows and at a variable one, 64 x 32, 32 x 16 -- under the switches of

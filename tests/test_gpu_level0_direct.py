@@ -1,4 +1,4 @@
-"""Full-mode calls read level 0 from the 8-bit images themselves (Slot::direct0, ugsm_runtime.cpp: the pyramid pass stores levels 1 and 2 only,
+"""Full-mode calls read level 0 from the 8-bit images themselves (Slot::direct0, ugsm_levels.cpp: the pyramid pass stores levels 1 and 2 only,
 A = G * L^2 and K-cost of level 0 run their 8-bit instances on the image): bit for bit the result of the materialised float level 0
 (UGSM_LEVEL0_FLOAT=1 under UGSM_DEV=1) and of the CPU oracle.
 
@@ -314,7 +314,7 @@ def test_wild_disparities_through_the_byte_gather(lib, orc):
 
 @pytest.mark.parametrize("fmt", en.FORMATS, ids=[en.NAMES[f] for f in en.FORMATS])
 def test_each_input_layout(lib, orc, monkeypatch, fmt):
-    """rgb8 calls read level 0 from the image; the other layouts keep the materialised float level 0 (level0_direct, ugsm_runtime.cpp) -- either
+    """rgb8 calls read level 0 from the image; the other layouts keep the materialised float level 0 (level0_direct, ugsm_policy.cpp) -- either
     way the result is the rgb8 result on the image's conversion to rgb8, under both settings of the development switch."""
     W, H, lv = 157, 101, 8
     L, R = _pair(W, H, 61)

@@ -206,7 +206,7 @@ def test_a_burst_is_staggered_and_hinted(fq):
 
 
 def test_a_flushed_call_with_nothing_behind_it_is_taken_to_be_alone(fq):
-    """The hint the kernel policy reads (call_alone, csrc/ugsm_runtime.cpp): clear for one pair enqueued and flushed (the node's topic path when
+    """The hint the kernel policy reads (call_alone, csrc/ugsm_policy.cpp): clear for one pair enqueued and flushed (the node's topic path when
     frames arrive slower than they are matched), for a partial call sent by a blocking ugsm_next_done, and for the LAST call of a burst;
     set for a call that leaves pairs waiting (here: a pair of another size behind it)."""
     h = Host(fq, 4, 8)

@@ -1,7 +1,7 @@
 // ugsm_coarse.cpp -- the entry points of the full-mode call in two halves (include/ugsm.h: ugsm_submit_full_coarse, ugsm_submit_full_fine,
 // ugsm_match_full_coarse, ugsm_match_full_fine, ugsm_coarse_pixel_iterations): what the calls refuse, all of it before anything is enqueued,
 // and the coarse half's size.  Written against the public entry points and ugsm_internal.hpp only (no HIP call here, as ugsm_seeded.cpp): the
-// runtime does the enqueueing (ugsm::coarse_submit, fine_submit, coarse_match, fine_match: ugsm_runtime.cpp), and the refusals can be driven
+// runtime does the enqueueing (ugsm::coarse_submit, fine_submit: ugsm_full.cpp; coarse_match, fine_match: ugsm_host.cpp), and the refusals can be driven
 // on a machine without a GPU (tests/fake_coarse.cpp).
 #include "ugsm_internal.hpp"
 

@@ -1,7 +1,7 @@
 // ugsm_fovea_seeded.cpp -- the entry points of the seeded (warm) foveated call (include/ugsm.h: ugsm_submit_foveated_warm,
 // ugsm_submit_foveated_warm_field, ugsm_match_foveated_warm, ugsm_fovea_warm_pixel_iterations): what the call refuses, all of it before
 // anything is enqueued, and the call's size.  Written against the public entry points and ugsm_internal.hpp only (no HIP call here, as
-// ugsm_seeded.cpp): the runtime does the enqueueing (ugsm::fovea_warm_submit, ugsm::fovea_warm_match: ugsm_runtime.cpp), and the refusals
+// ugsm_seeded.cpp): the runtime does the enqueueing (ugsm::fovea_warm_submit: ugsm_fovea.cpp; ugsm::fovea_warm_match: ugsm_host.cpp), and the refusals
 // can be driven on a machine without a GPU (tests/fake_fovea_seeded.cpp).
 #include "ugsm_internal.hpp"
 

@@ -261,7 +261,7 @@ int free_slot(const Queue *q)
 
 // One library call for the first n waiting pairs on `slot`.  more: other calls follow this one closely -- pairs wait behind it, or it filled
 // up without a flush (a host that submits faster than the chip matches): the runtime then takes the call to share the chip whatever the
-// other slots are doing at this instant (call_alone, ugsm_runtime.cpp).
+// other slots are doing at this instant (call_alone, ugsm_policy.cpp).
 void dispatch(ugsm_ctx *ctx, Queue *q, int n, int slot, bool more)
 {
     // the call's place in the flight list first: everything that can run out of host memory happens before anything reaches the GPU,

@@ -1,5 +1,7 @@
-// ugsm_runtime.cpp -- host runtime + C-ABI of libugsm.so: the context, the slots and the matcher.  (The point clouds -- row f-1, from
-// ugsm_triangulate to the queue's cloud calls -- are ugsm_cloud.cpp; what the two share is ugsm_slot.hpp.)
+// ugsm_runtime.cpp -- the context of libugsm.so: the slots and their buffers, the slot a call gets and its completion mark, ugsm_create and
+// ugsm_destroy, ugsm_wait and ugsm_poll, the getters and setters, the statistics and the memory helpers.  (Which kernel a level gets:
+// ugsm_policy.cpp.  What a call enqueues: ugsm_levels.cpp, ugsm_full.cpp, ugsm_fovea.cpp.  Caller host memory: ugsm_host.cpp.  The stage-level
+// entry points: ugsm_stages.cpp.  The point clouds: ugsm_cloud.cpp.  What they share: ugsm_slot.hpp.)
 //
 // Replaces the host orchestration of /root/reference/src/gpu_matcher/MatchGPULib.cpp:
 // a persistent context owns every device buffer (the reference mallocs/frees ~23 buffers
@@ -8,9 +10,6 @@
 // HIP stream ("slot") so the launch-bound coarse levels of one pair overlap the
 // bandwidth/VALU-bound fine levels of another.
 #include "../../include/ugsm.h"
-#ifdef UGSM_DEV_LIB
-#include "../../include/ugsm_dev.h"
-#endif
 #include "ugsm_device.hpp"
 #include "ugsm_slot.hpp"
 
@@ -18,11 +17,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
-#include <condition_variable>
-#include <functional>
 #include <mutex>
-#include <system_error>
-#include <thread>
 
 using namespace ugsm;
 
@@ -31,85 +26,31 @@ const char *kClassName[2][KC_COUNT] = {
     {"k_cost_split", "k_smooth_fused", "k_sqblur_tiled", "k_blur_decimate_tiled", "k_seed", "-", "-", "misc", "k_cost_march", "k_pyr_base", "k_cost_small",
      "k_smooth_small", "k_cost_march4", "k_level0_windows", "k_restrict", "k_restrict_stack", "k_prolong"},
     {"k_cost_ref", "k_smooth_pass", "k_sqblur_clamp", "k_blur_decimate", "k_seed", "k_warp", "k_box", "misc", "-", "-", "-", "-", "-", "-", "k_restrict", "k_restrict_stack", "k_prolong"}};
+
+// ---- event bookkeeping (Timer: ugsm_slot.hpp) --------------------------------------------
+
+void harvest(ugsm_ctx *ctx, Slot &s)
+{
+    for (EvRec &r : s.pending) {
+        float ms = 0;
+        if (hipEventElapsedTime(&ms, r.a, r.b) == hipSuccess) {
+            StatCell &c = ctx->cells[r.kclass][r.level];
+            c.launches += 1;
+            c.total_ms += ms;
+            c.pixel_launches += r.pixels;
+        }
+        s.pool.push_back(r.a);
+        s.pool.push_back(r.b);
+    }
+    s.pending.clear();
+}
+
+// ugsm_create applies the process-wide tuning variables only while no other context of the process is alive (apply_dev_env, ugsm_policy.cpp)
+std::mutex g_globals_mutex;
+int g_live_contexts = 0;
 }  // namespace
 
 namespace ugsm {
-// A persistent team of host threads for the service path's page touching and staging copies (the first version
-// created ~29 std::threads per call; a failed creation -- EAGAIN under a thread or cgroup limit -- threw through an extern "C"
-// entry point with joinable threads on the stack, i.e. std::terminate in the caller's process).  Workers are created once, on the
-// first service call; creation failures are caught and the team simply stays smaller (down to the calling thread alone).
-class HostTeam {
-public:
-    explicit HostTeam(unsigned want)
-    {
-        for (unsigned t = 1; t < want; t++) {
-            try {
-                workers_.emplace_back([this, t] { loop(t); });
-            } catch (const std::system_error &) {
-                break;  // no more threads to be had: run with what there is
-            }
-        }
-    }
-    ~HostTeam()
-    {
-        {
-            std::lock_guard<std::mutex> lk(m_);
-            stop_ = true;
-            gen_++;
-        }
-        cv_.notify_all();
-        for (std::thread &t : workers_) t.join();
-    }
-    unsigned size() const { return (unsigned)workers_.size() + 1; }
-    // f(member, members) on every member; the caller is member 0.  Returns when all are done.  f must not throw.
-    void run(const std::function<void(unsigned, unsigned)> &f)
-    {
-        const unsigned n = size();
-        if (n == 1) {
-            f(0, 1);
-            return;
-        }
-        {
-            std::lock_guard<std::mutex> lk(m_);
-            job_ = &f;
-            pending_ = n - 1;
-            gen_++;
-        }
-        cv_.notify_all();
-        f(0, n);
-        std::unique_lock<std::mutex> lk(m_);
-        done_.wait(lk, [this] { return pending_ == 0; });
-        job_ = nullptr;
-    }
-
-private:
-    void loop(unsigned me)
-    {
-        unsigned seen = 0;
-        for (;;) {
-            const std::function<void(unsigned, unsigned)> *job;
-            {
-                std::unique_lock<std::mutex> lk(m_);
-                cv_.wait(lk, [&] { return gen_ != seen; });
-                seen = gen_;
-                if (stop_) return;
-                job = job_;
-            }
-            if (job) (*job)(me, size());
-            {
-                std::lock_guard<std::mutex> lk(m_);
-                if (--pending_ == 0) done_.notify_one();
-            }
-        }
-    }
-    std::vector<std::thread> workers_;
-    std::mutex m_;
-    std::condition_variable cv_, done_;
-    const std::function<void(unsigned, unsigned)> *job_ = nullptr;
-    unsigned gen_ = 0, pending_ = 0;
-    bool stop_ = false;
-};
-
 CtxHooks &ctx_hooks(ugsm_ctx *ctx) { return ctx->hooks; }
 const ugsm_config &ctx_config(const ugsm_ctx *ctx) { return ctx->cfg; }
 void *ctx_slot_stream(ugsm_ctx *ctx, int slot) { return (ctx && slot >= 0 && slot < (int)ctx->slots.size()) ? (void *)ctx->slots[(size_t)slot].st : nullptr; }
@@ -181,12 +122,6 @@ void fovea_geometry(const int *w, const int *h, int F, int off_x, int off_y, Fov
     }
 }
 
-}  // namespace ugsm
-
-ugsm_ctx::~ugsm_ctx() = default;
-
-namespace {
-
 // ---- buffers ---------------------------------------------------------------------------
 
 // (dx,dy,conf) ping-pong, A = G*L^2 and (kernel_path 1 only) R' and B: 3-plane buffers sized
@@ -219,8 +154,16 @@ int ensure_level_bufs(ugsm_ctx *ctx, Slot &s, size_t lvl)
     return UGSM_OK;
 }
 
+// the page-locked words the LR checks' counts come back in
+constexpr size_t kLrHostWords = 1 + (size_t)kMaxBatch * UGSM_MAX_LEVELS;
+int lr_host_ready(ugsm_ctx *ctx, Slot &s)
+{
+    if (!s.lr_host) HIPCHK(ctx, hipHostMalloc((void **)&s.lr_host, kLrHostWords * sizeof(unsigned long long), hipHostMallocDefault));
+    return UGSM_OK;
+}
+
 // the slot's pyramids and level buffers for `cap_pairs` pairs (both pyramids or neither; level buffers all or nothing)
-int alloc_slot_buffers(ugsm_ctx *ctx, Slot &s, int cap_pairs, size_t tot, size_t lvl)
+static int alloc_slot_buffers(ugsm_ctx *ctx, Slot &s, int cap_pairs, size_t tot, size_t lvl)
 {
     const size_t pyr_need = cap_pairs > 1 ? s.pyr_stride * cap_pairs : tot;
     if (pyr_need > s.pyr_cap) {
@@ -244,7 +187,7 @@ int alloc_slot_buffers(ugsm_ctx *ctx, Slot &s, int cap_pairs, size_t tot, size_t
     return ensure_level_bufs(ctx, s, cap_pairs > 1 ? s.lvl_stride * cap_pairs : lvl);
 }
 
-int prepare_slot(ugsm_ctx *ctx, Slot &s, int W, int H, int nb = 1)
+int prepare_slot(ugsm_ctx *ctx, Slot &s, int W, int H, int nb)
 {
     const int levels = ctx->cfg.levels;
     int w[UGSM_MAX_LEVELS], h[UGSM_MAX_LEVELS];
@@ -323,1470 +266,20 @@ int prepare_slot(ugsm_ctx *ctx, Slot &s, int W, int H, int nb = 1)
     return st;
 }
 
-// ---- event bookkeeping (Timer: ugsm_slot.hpp) --------------------------------------------
-
-void harvest(ugsm_ctx *ctx, Slot &s)
+// The configurations a context can have, asked after the development overrides (apply_dev_env) by ugsm_create and ugsm_plan_level alike:
+// no plan is reported for a configuration that no context can be created with.
+int check_config(const ugsm_config &cfg)
 {
-    for (EvRec &r : s.pending) {
-        float ms = 0;
-        if (hipEventElapsedTime(&ms, r.a, r.b) == hipSuccess) {
-            StatCell &c = ctx->cells[r.kclass][r.level];
-            c.launches += 1;
-            c.total_ms += ms;
-            c.pixel_launches += r.pixels;
-        }
-        s.pool.push_back(r.a);
-        s.pool.push_back(r.b);
-    }
-    s.pending.clear();
-}
-
-// ---- development overrides ---------------------------------------------------------------
-// tools/ and tests/ steer the per-level kernel choice through environment variables.  They are read ONLY when UGSM_DEV=1 is set
-// as well, so that a production process never changes behaviour because of a stray variable, and in ONE place, shared by
-// ugsm_create and ugsm_plan_level (which therefore reports what a context created under the same environment launches).
-struct DevKnobs {
-    int fuse_seed = 1;       // UGSM_FUSE_SEED=0: seed every level with its own launch
-    int small_mask = 3;      // UGSM_SMALL_MASK: bit 0 = k_cost_small, bit 1 = k_smooth_small
-    int small_rh_force = 0;  // UGSM_SMALL_RH: region height of k_smooth_small whatever the level size (18, 24 or 32)
-    int force_alone = -1;    // UGSM_ALONE=1 / 0: the kernel choices of a call that has the chip to itself / that shares it, whatever is in flight
-    int two_streams = -1;    // UGSM_TWO_STREAMS=0: no call forks onto a side stream (default 1: a call that is alone does)
-    char side_prio = 0;         // UGSM_SIDE_PRIO=h|n|l|s: a side stream of its own for every slot, at that priority (s: the slot's); default: borrowed (ugsm_create)
-    char stream_prio[65] = "";  // UGSM_STREAM_PRIO: one letter per slot, h / n / l = greatest / default / least stream priority (slot_stream_priority)
-    int march_mode = 0;      // UGSM_MARCH_MODE=0,-1,-2,-3: launch_cost_march's strip-height / age-class mode (default 0: latency heights, strips by age class)
-    long long batch_max_px = 0;  // UGSM_BATCH_MAX_PIXELS: levels up to this many pixels are ONE launch for all pairs of a batched call (default kBatchMaxPixels; < 0: none)
-    int smooth_big_min = 0;  // UGSM_SMOOTH_BIG_MIN: pixel count from which K-smooth uses the 112-column tile (default 2^19)
-    int smooth_rows = 0;     // UGSM_SMOOTH_ROWS: tile height of the large levels' K-smooth (1..39), -1 / -2 = the latency / throughput rule whatever the slots
-    int march4_lo = -1, march4_hi = -1;  // UGSM_MARCH4=lo,hi: pixel range of k_cost_march4 (0,0 = never; default: march4_default_range)
-    int level0_float = 0;    // UGSM_LEVEL0_FLOAT=1: full-mode calls materialise the float level 0 as foveated calls and ugsm_submit_pyramids do
-};
-bool dev_env_on()
-{
-    const char *e = getenv("UGSM_DEV");
-    return e && e[0] == '1';
-}
-// set_globals: also apply the process-wide tuning variables (UGSM_SMOOTH_MID_MIN, UGSM_PYR_STREAM*, UGSM_MARCH_AGE).  They are CREATE-TIME,
-// PROCESS-WIDE settings: ugsm_create applies them only while no other context of the process is alive (g_live_contexts, under
-// g_globals_mutex), so that creating a second context never changes the kernels of a live one, from whatever thread; the
-// host-only ugsm_plan_level never does.
-std::mutex g_globals_mutex;
-int g_live_contexts = 0;
-void apply_dev_env(ugsm_config &cfg, DevKnobs &k, bool set_globals)
-{
-    if (!dev_env_on()) return;
-    auto geti = [](const char *name, int &dst) {
-        if (const char *e = getenv(name)) dst = atoi(e);
-    };
-    geti("UGSM_KERNEL_PATH", cfg.kernel_path);
-    geti("UGSM_MARCH_MIN_PIXELS", cfg.march_min_pixels);
-    geti("UGSM_MARCH_ROWS", cfg.march_rows);
-    geti("UGSM_SMALL_MAX_PIXELS", cfg.small_max_pixels);
-    geti("UGSM_SMALL_MASK", k.small_mask);
-    geti("UGSM_FUSE_SEED", k.fuse_seed);
-    geti("UGSM_TWO_STREAMS", k.two_streams);
-    geti("UGSM_SMOOTH_ROWS", k.smooth_rows);
-    geti("UGSM_MARCH_MODE", k.march_mode);
-    geti("UGSM_LEVEL0_FLOAT", k.level0_float);
-    if (const char *e = getenv("UGSM_STREAM_PRIO")) snprintf(k.stream_prio, sizeof k.stream_prio, "%s", e);
-    if (const char *e = getenv("UGSM_SIDE_PRIO")) k.side_prio = e[0];
-    if (const char *e = getenv("UGSM_ALONE")) k.force_alone = e[0] == '1' ? 1 : (e[0] == '0' ? 0 : -1);
-    geti("UGSM_SMOOTH_BIG_MIN", k.smooth_big_min);
-    if (const char *e = getenv("UGSM_BATCH_MAX_PIXELS")) k.batch_max_px = atoll(e);
-    if (set_globals) {  // the process-wide tuning variables: back to their defaults first, so that a variable a test has removed stops acting
-        smooth_mid_min_pixels = 1 << 18;
-        smooth_lds_extra_bytes = 0;
-        blur_decimate_streaming = 1;
-        pyr_base_streaming = 1;
-        blur_decimate_streaming_min = 0;
-        march_age_permille[0] = 470;
-        march_age_permille[1] = 340;
-        geti("UGSM_SMOOTH_MID_MIN", smooth_mid_min_pixels);
-        geti("UGSM_SMOOTH_LDS_EXTRA", smooth_lds_extra_bytes);
-        geti("UGSM_PYR_STREAM", blur_decimate_streaming);
-        geti("UGSM_PYR_BASE_STREAM", pyr_base_streaming);
-        if (const char *e = getenv("UGSM_PYR_STREAM_MIN")) blur_decimate_streaming_min = atoll(e);
-    }
-    if (const char *e = set_globals ? getenv("UGSM_MARCH_AGE") : nullptr) {
-        int a = 0, b = 0;
-        if (sscanf(e, "%d,%d", &a, &b) == 2 && a >= 0 && b >= 0 && a + b < 1000) {
-            march_age_permille[0] = a;
-            march_age_permille[1] = b;
-        }
-    }
-    if (const char *e = getenv("UGSM_MARCH4")) {
-        int a = 0, b = 0;
-        if (sscanf(e, "%d,%d", &a, &b) == 2 && a >= 0 && b >= a) {
-            k.march4_lo = a;
-            k.march4_hi = b;
-        }
-    }
-    int rh = 0;
-    geti("UGSM_SMALL_RH", rh);
-    if (rh == 18 || rh == 24 || rh == 32) k.small_rh_force = rh;
-}
-
-// The choices of a context that are not in ugsm_config: the development overrides (the defaults are with the policy functions below).
-void set_policy(ugsm_ctx *c, const DevKnobs &k)
-{
-    c->small_mask = k.small_mask;
-    c->fuse_seed = k.fuse_seed;
-    c->small_rh_force = k.small_rh_force;
-    c->smooth_rows = k.smooth_rows;
-    c->smooth_big_min = k.smooth_big_min > 0 ? k.smooth_big_min : 0;
-    // strips by age class, every context: +8 % on a level-0 launch alone on the chip, +1.2 % on a pair alone; with four pairs in
-    // flight it costs 0.4 % (163.2 against 163.7 pairs/s) -- kept on there too, so that a kernel measured alone is the kernel that ran
-    c->march_mode = k.march_mode <= 0 ? k.march_mode : 0;
-    c->march4_lo = k.march4_lo;
-    c->march4_hi = k.march4_hi;
-    c->force_alone = k.force_alone;
-    c->batch_max_px = k.batch_max_px;
-    c->level0_float = k.level0_float;
-}
-
-// ---- stages ----------------------------------------------------------------------------
-
-// The pairs of one launch: b0 .. b0 + n - 1 of the batch in the slot (n = 1: an ordinary launch of pair b0).
-struct Grp {
-    int b0, n;
-};
-// The lockstep layout of a call's levels: how many fields run together, which pyramids each reads and where its fields lie.  A value that the
-// call's sequence makes once and hands down; the slot keeps only what belongs to its real pairs (Slot::nb, Slot::lvl_stride).
-struct Shape {
-    int nb;         // the entries that run in lockstep
-    int nreal;      // entries nreal .. nb - 1 are the entries 0 .. nreal - 1 with the L and R views exchanged (pair_pyr); nreal == nb: none are
-    bool one_pair;  // every entry reads pair 0's pyramids: the entries are windows of one pair
-    size_t stride;  // floats between consecutive entries' fields in A, d0 and d1
-    // the slot's real pairs, each at its own full-frame room
-    static Shape pairs(const Slot &s) { return {s.nb, s.nb, false, s.lvl_stride}; }
-    // both directions of n pairs / n windows of one pair / both directions of n windows of one pair: every field is at most a fovea field, `field`
-    // floats of room each (fovea_field_room), so that they all lie in the level buffers the slot holds
-    static Shape both_directions(int n, size_t field) { return {2 * n, n, false, field}; }
-    static Shape windows(int n, size_t field) { return {n, n, true, field}; }
-    static Shape windows_both_directions(int n, size_t field) { return {2 * n, n, true, field}; }
-    // the coarse phase of the checked multi-window call: the one pair and its exchanged twin
-    static Shape coarse_both_directions(size_t field) { return both_directions(1, field); }
-    // both directions of the slot's real pairs at full frame (ugsm_submit_full_checked): 2 nb entries, each at its own full-frame room -- twice
-    // what the slot holds for its pairs, so the caller has grown the level buffers
-    static Shape full_both_directions(const Slot &s) { return {2 * s.nb, s.nb, false, s.lvl_stride}; }
-};
-// the room of one fovea field (3 planes of fw x fh) in the level buffers, in the LR buffer and in hout: a multiple of 64 floats
-size_t fovea_field_room(int fw, int fh) { return (3 * (size_t)fw * fh + 63) & ~(size_t)63; }
-
-// entries per launch of a batched level of a call of nb entries: all of them; the 2 x 9 .. 2 x 16 entries of a checked foveated call
-// in launches of equal size, none above kMaxBatch (what a Batch holds)
-int group_pairs(int nb)
-{
-    const int launches = (nb + kMaxBatch - 1) / kMaxBatch;
-    return (nb + launches - 1) / launches;
-}
-// f(Grp) for the whole batch in one launch (`batched`; group_pairs(nb) pairs each where one launch cannot hold them) or pair by pair
-template <class F>
-void for_groups(int nb, bool batched, F &&f)
-{
-    if (batched && nb > 1) {
-        const int per = group_pairs(nb);
-        for (int b0 = 0; b0 < nb; b0 += per) f(Grp{b0, std::min(per, nb - b0)});
-        return;
-    }
-    for (int b = 0; b < nb; b++) f(Grp{b, 1});
-}
-inline long long byte_diff(const void *a, const void *b) { return (long long)(reinterpret_cast<intptr_t>(a) - reinterpret_cast<intptr_t>(b)); }
-// The Batch argument of a group's launch.  Inputs and outputs are the slot's level buffers (entry b at + b * sh.stride) unless
-// `outs` names per-pair destinations (the callers' buffers); `views`: the L / R views of the pairs (fovea windows sit at different
-// places); `seeds`: their seed-crop origins.  All arrays are indexed by the pair's number in the batch.
-Batch make_batch(const Shape &sh, Grp g, const Img3 *views = nullptr, const SeedMap *seeds = nullptr, float *const *outs = nullptr)
-{
-    Batch b{};
-    b.n = g.n;
-    for (int j = 0; j < g.n; j++) {
-        b.in[j] = (long long)(j * sh.stride * sizeof(float));
-        b.out[j] = outs ? byte_diff(outs[g.b0 + j], outs[g.b0]) : b.in[j];
-        b.img[j] = views ? byte_diff(views[g.b0 + j].p, views[g.b0].p) : 0;
-        b.cx[j] = seeds ? seeds[g.b0 + j].cx : 0;
-        b.cy[j] = seeds ? seeds[g.b0 + j].cy : 0;
-    }
-    return b;
-}
-
-// CreatePyramidFromImage (MatchGPULib.cpp:1033-1125) for the left OR the right image of every pair of the call: rgb[b] -> pyr + b * pyr_stride.
-// The images of a batch go through every pyramid kernel together (one launch per level for all of them).
-// What a foveated call reads of level 0: every pair's fovea window (the level-0 crop of fovea_geometry); k_pyr_base then stores level 0
-// only where a window lies.  Full-mode calls and ugsm_submit_pyramids (window not known yet) pass none.
-// later (ugsm_submit_foveated_multi: several windows on one pair): k_pyr_base stores no level 0 at all (kPyrNoLevel0); the caller writes it
-// inside the windows afterwards with one launch of its own (enqueue_level0_windows).  Where k_pyr_base does not build the pyramid, level 0 is
-// stored whole as ever.
-struct FoveaWin {
-    int w = 0, h = 0;
-    int x0[kMaxBatch], y0[kMaxBatch];
-    bool later = false;
-};
-// skip0 (full-mode calls whose level-0 kernels read the images: Slot::direct0): level 0 is not stored at all.
-// built (a seeded call, which matches no level above its first): only the levels 0 .. built - 1 are produced; 0: all of them.
-int build_pyramids(ugsm_ctx *ctx, Slot &s, int si, const uint8_t *const *rgb, int stride, float *pyr, hipStream_t stream = nullptr, const FoveaWin *win = nullptr,
-                   bool skip0 = false, int built = 0)
-{
-    const hipStream_t pst = stream ? stream : s.st;  // (launches on the side stream are not bracketed by events: Timer records on s.st)
-    const int levels = (built > 0 && built < s.levels) ? built : s.levels, nb = s.nb;
-    const bool ref = ctx->cfg.kernel_path == 1;
-    // levels 0, 1, 2 in one pass over the rgb8 input (k_pyr_base); the one-stage-per-kernel path keeps the three launches
-    const bool base = !ref && levels >= 3;
-    Batch bt{};  // image j of the launch = pair j: its rgb8 input, its pyramid, its range word
-    bt.n = nb;
-    for (int j = 0; j < nb; j++) {
-        bt.img[j] = byte_diff(rgb[j], rgb[0]);
-        bt.in[j] = bt.out[j] = (long long)(j * s.pyr_stride * sizeof(float));
-        bt.cx[j] = j;
-    }
-    Batch bt0 = bt;  // k_pyr_base: the input-field offsets carry the pairs' window origins instead
-    if (win || skip0)
-        for (int j = 0; j < nb; j++) bt0.in[j] = win ? ((long long)win->y0[j] << 32) | (unsigned)win->x0[j] : 0;
-    const bool later = win && win->later;
-    const PyrWindow pw = later ? kPyrNoLevel0 : (win ? PyrWindow{win->x0[0], win->y0[0], win->w, win->h} : (skip0 ? kPyrNoLevel0 : PyrWindow{0, 0, 0, 0}));
-    if ((skip0 && (win || !base)) || (later && nb != 1)) {  // (level0_direct asks for neither; the windows of ONE pair come later)
-        ctx->err = "pyramids without level 0 are built by k_pyr_base for full-mode calls, and for the one pair of a multi-window call";
-        return UGSM_ERR_STATE;
-    }
-    const Batch *const pb = nb > 1 ? &bt : nullptr;
-    // One full-mode pair alone on the chip: the streaming factor-2 kernel's many short workgroups on the side stream get
-    // in the way of the main stream's latency-bound launches -- 112.3 pairs/s with it on every level, 114.4 with it on the launches of
-    // >= 1.5 M outputs only, 114.1 without it (tools/ab.py, same box); foveated calls and everything with more in flight gain from it
-    // on every level (a lone foveated pair +1.8 %, batches of eight +3.3 %).
-    const long long stream_min = (s.alone && nb == 1 && !win) ? 1500000 : 0;
-    s.cur_level = 0;
-    if (base) {
-        Timer t(ctx, &s, si, KC_PYR_BASE, (double)s.W * s.H * nb);
-        launch_pyr_base(pst, rgb[0], stride, s.W, s.H, pyr + s.off[0], pyr + s.off[1], s.w[1], s.h[1], pyr + s.off[2], s.w[2], s.h[2], s.range_bad,
-                        nb > 1 ? &bt0 : nullptr, pw, ctx->hooks.input_format);
-    } else {
-        // (pyramids of fewer than three levels, and kernel_path 1: image by image)
-        for (int b = 0; b < nb; b++) {
-            Timer t(ctx, &s, si, KC_MISC, (double)s.W * s.H);
-            launch_rgb_planes(pst, rgb[b], stride, s.W, s.H, pyr + b * s.pyr_stride + s.off[0], ctx->hooks.input_format);
-        }
-    }
-    // CreatePyramidFromImage, MatchGPULib.cpp:1063-1106: level 1 from level 0 (sf=(float)SCALE),
-    // level i+2 from level i (sf=2.0f).  Levels are produced in dependency order.
-    for (int i = 0; i < levels; i++) {
-        if (i == 0 && levels > 1 && !base) {
-            s.cur_level = 1;
-            Timer t(ctx, &s, si, KC_PYR, (double)s.w[1] * s.h[1] * nb);
-            float sf = (float)kScale;
-            if (ref) launch_blur_decimate_ref(pst, pyr + s.off[0], s.w[0], s.h[0], pyr + s.off[1], s.w[1], s.h[1], sf);
-            else launch_blur_decimate(pst, pyr + s.off[0], s.w[0], s.h[0], pyr + s.off[1], s.w[1], s.h[1], sf, s.range_bad, pb, stream_min);
-        }
-        if (i + 2 < levels && !(base && i == 0)) {
-            s.cur_level = i + 2;
-            Timer t(ctx, &s, si, KC_PYR, (double)s.w[i + 2] * s.h[i + 2] * nb);
-            float sf = (float)(0.000 + (int)(kScale * kScale + 0.5));  // :1090
-            if (ref) launch_blur_decimate_ref(pst, pyr + s.off[i], s.w[i], s.h[i], pyr + s.off[i + 2], s.w[i + 2], s.h[i + 2], sf);
-            else launch_blur_decimate(pst, pyr + s.off[i], s.w[i], s.h[i], pyr + s.off[i + 2], s.w[i + 2], s.h[i + 2], sf, s.range_bad, pb, stream_min);
-        }
-    }
-    s.cur_level = kNoLevel;
-    HIPCHK(ctx, hipGetLastError());
+    if (cfg.levels < 1 || cfg.levels > UGSM_MAX_LEVELS || cfg.slots < 1 || cfg.slots > 64 || cfg.kernel_path < 0 ||
+        cfg.kernel_path > 1 || cfg.fovea_levels < 0 || cfg.fovea_levels > cfg.levels || !(cfg.lr_check_threshold >= 0.0f) || cfg.streams < 0 ||
+        cfg.batch < 0 || cfg.batch > UGSM_MAX_BATCH || cfg.stream_priority < 0 || cfg.stream_priority > 3)
+        return UGSM_ERR_BAD_ARG;
+    if (cfg.kernel_path == 1 && !kDevLib) return UGSM_ERR_BAD_ARG;       // the one-kernel-per-stage path lives in libugsm_dev.so
+    if (cfg.march_min_pixels < 0 && !kDevLib) return UGSM_ERR_BAD_ARG;  // ... and so does round 1's LDS-tiled K-cost
     return UGSM_OK;
 }
 
-// ---- per-level kernel choices ---------------------------------------------------------------------------------------
-// Which kernel runs a level is decided by the level's size -- compared with what the LAUNCH holds: pairs x W x H, pairs = the batch where
-// the level is batched, else 1 -- and by ONE question: does the call have the chip to itself (Slot::alone; call_alone below)?  A call alone
-// wants every launch SHORT: nothing else fills the CUs a launch leaves idle.  A call that shares the chip wants every launch to do LITTLE
-// REDUNDANT WORK: what it wastes, the others could have used.  Five choices ask the question (marked ALONE below, plus the pyramid's
-// streaming threshold in build_pyramids and the side stream); the rest is six numbers.  The A/B behind each: DESIGN.md section 4.
-// (Rounds 3-5 switched between two whole threshold sets by ugsm_config.slots and the frame size; forced against each other they differ by
-// 0.35 % where bench.py measures, and a lone 16 MP call on a four-slot context lost 11.6 % to the wrong one: VERDICT r05 #1.)
-constexpr long long kBatchMaxPixels = 9000000;  // levels up to here go through a batched call as ONE launch for all its pairs (level 0 of a 16 MP pair: pair by pair)
-constexpr int kSmallMaxPixelsAlone = 150000;    // the coarse levels' latency kernels (ugsm_kernels_small.hip) up to here for a call alone ...
-constexpr int kSmallMaxPixelsShared = 50000;    // ... and up to here on a shared chip (above it k_cost_march4 and the tiled K-smooth redo less)
-constexpr int kMarch4MaxPixels = 3000000;       // above them k_cost_march4 (four waves per strip: wins while a launch lasts as long as one strip) up to here
-constexpr int kMarchMinPixels = 400000;         // k_cost_march from here -- asked after k_cost_march4, so in effect above its range
-constexpr int kSmoothBigMinPixels = 1 << 19;    // k_smooth_fused's 112-column tile from here (1.39 x the tile in halo work, against 1.8 x for 64 x 32)
-
-}  // namespace
-bool ugsm::batch_level(const ugsm_ctx *ctx, int W, int H)
-{
-    const long long thr = ctx->batch_max_px > 0 ? ctx->batch_max_px : (ctx->batch_max_px < 0 ? 0 : kBatchMaxPixels);
-    return (long long)W * H <= thr;
-}
-namespace {
-// entries a launch of a W x H level of a call of this shape holds
-int launch_pairs(const ugsm_ctx *ctx, const Shape &sh, int W, int H) { return (sh.nb > 1 && batch_level(ctx, W, H)) ? group_pairs(sh.nb) : 1; }
-
-int small_max_px(const ugsm_config &cfg, bool alone)
-{
-    if (cfg.small_max_pixels < 0) return 0;
-    return cfg.small_max_pixels > 0 ? cfg.small_max_pixels : (alone ? kSmallMaxPixelsAlone : kSmallMaxPixelsShared);
-}
-bool use_march4(const ugsm_ctx *ctx, int W, int H, bool alone, int pairs = 1)
-{
-    const long long px = (long long)W * H * pairs;
-    if (ctx->cfg.kernel_path == 1) return false;
-    if (ctx->march4_hi >= 0) return ctx->march4_hi > 0 && px >= ctx->march4_lo && px <= ctx->march4_hi;  // (development override)
-    return px > small_max_px(ctx->cfg, alone) && px <= kMarch4MaxPixels;
-}
-bool march_by_size(const ugsm_ctx *ctx, int W, int H, int pairs = 1)  // (ugsm_config.march_min_pixels moves the threshold: tests run every level through it)
-{
-    const int thr = ctx->cfg.march_min_pixels;
-    return thr >= 0 && (long long)W * H * pairs >= (thr > 0 ? thr : kMarchMinPixels);
-}
-int march_rows_arg(const ugsm_ctx *ctx) { return ctx->cfg.march_rows > 0 ? ctx->cfg.march_rows : ctx->march_mode; }
-
-// The latency kernels' K-smooth region height (0 = not a level of theirs).  On a shared chip 18 x 18 tiles (3.2 x the tile in halo work; the
-// 18 x 4 / 18 x 10 tiles redo 8 x / 4.6 x: free on an idle chip, 3.6 % / 9.2 % of the throughput with four pairs in flight); a call ALONE
-// takes the smallest tile that still gives every workgroup a CU of its own, or nearly.
-int small_rh(const ugsm_ctx *ctx, int W, int H, bool alone, int pairs = 1)
-{
-    const long long px = (long long)W * H * pairs;
-    if (ctx->cfg.small_max_pixels < 0 || ctx->cfg.kernel_path == 1 || px > small_max_px(ctx->cfg, alone) || march_by_size(ctx, W, H, pairs)) return 0;
-    if (ctx->small_rh_force) return ctx->small_rh_force;
-    return !alone ? 32 : (px <= 36000 ? 18 : (px <= 80000 ? 24 : 32));
-}
-bool use_small_cost(const ugsm_ctx *ctx, int W, int H, bool alone, int pairs = 1)
-{
-    return (ctx->small_mask & 1) && small_rh(ctx, W, H, alone, pairs) != 0;
-}
-// k_cost_march: the levels of at least march_min_pixels per launch, and every level that no other form covers -- it is the one shipped form
-// with no size limit and a batch index.  With the default thresholds the other forms cover every size below kMarch4MaxPixels by
-// themselves; the fallback takes what a configuration leaves uncovered (march_min_pixels above k_cost_march4's reach, small_max_pixels < 0
-// with k_cost_march4 off, the development switches).  Only march_min_pixels < 0 (libugsm_dev.so) leaves such levels to round 1's
-// LDS-tiled k_cost_split.
-bool use_march(const ugsm_ctx *ctx, int W, int H, bool alone, int pairs = 1)
-{
-    if (ctx->cfg.kernel_path == 1 || ctx->cfg.march_min_pixels < 0) return false;
-    return march_by_size(ctx, W, H, pairs) || (!use_march4(ctx, W, H, alone, pairs) && !use_small_cost(ctx, W, H, alone, pairs));
-}
-
-// Seeding (subsampleDisp, MatchGPULib.cpp:1526-1590) rides on the level's first K-cost launch when that is a marching kernel: the seeded field is
-// never written.  Not with the early exit (the field before the first iteration is compared against), not on the one-stage-per-kernel path.
-bool fuse_seed(const ugsm_ctx *ctx, int W, int H, bool alone, int pairs = 1)
-{
-    return ctx->fuse_seed && ctx->cfg.kernel_path != 1 && !(ctx->cfg.early_exit_threshold > 0.0f) && (use_march(ctx, W, H, alone, pairs) || use_march4(ctx, W, H, alone, pairs));
-}
-
-// k_smooth_fused's tile: > 0 = the 112-column tile at this height -- a call ALONE picks the height that fills whole rounds of workgroups
-// (smooth_tile_rows), else 36 --; 0 = the tile class by the level's size (64 x 32 from 0.26 Mpx, else 32 x 16)
-int smooth_rows_for(const ugsm_ctx *ctx, int W, int H, bool alone, int pairs = 1)
-{
-    if ((long long)W * H * pairs < (ctx->smooth_big_min > 0 ? ctx->smooth_big_min : kSmoothBigMinPixels)) return 0;
-    if (pairs > 1 && W < 100) return 0;  // (a level narrower than the 112-column tile: the smaller tile classes waste fewer lanes)
-    if (ctx->smooth_rows > 0) return std::min(ctx->smooth_rows, kSmoothTileRowsMax);
-    return smooth_tile_rows(W, H, ctx->smooth_rows == -1 ? 1 : (ctx->smooth_rows == -2 ? 0 : (alone ? 1 : 0)), pairs);
-}
-// ... and the tile class of the smaller levels of a batched launch: by what the launch holds
-int smooth_class_for(int W, int H, int pairs)
-{
-    return pairs <= 1 ? 0 : (((long long)W * H * pairs >= smooth_mid_min_pixels && W >= 48 && H >= 24) ? 2 : 1);
-}
-
-// S Jacobi passes + the 3x3 box (MatchGPULib.cpp:2257-2412) for every entry of the call.  On return `a` holds the
-// result and `b` is scratch (base pointers: entry k's buffers lie at + k * sh.stride).
-// final_out (optional, fused path): per-pair destinations; the last launch writes there instead of into `b`, and `a` is then not meaningful.
-int enqueue_smooth(ugsm_ctx *ctx, Slot &s, int si, const Shape &sh, float *&a, float *&b, int W, int H, int S, bool do_box, float *const *final_out = nullptr)
-{
-    const double px = (double)W * H;
-    if (ctx->cfg.kernel_path == 1) {  // (never batched)
-        for (int j = 0; j < S; j++) {
-            Timer t(ctx, &s, si, KC_SMOOTH, px);
-            launch_smooth_pass_ref(s.st, a, b, W, H);
-            std::swap(a, b);
-        }
-        if (do_box) {
-            Timer t(ctx, &s, si, KC_BOX, px);
-            launch_box_ref(s.st, a, b, W, H);
-            std::swap(a, b);
-        }
-    } else {
-        const int pairs = launch_pairs(ctx, sh, W, H);
-        int left = S;
-        do {
-            int p = std::min(left, 5);
-            left -= p;
-            if (p == 0 && !do_box) break;
-            const int rh = (ctx->small_mask & 2) ? small_rh(ctx, W, H, s.alone, pairs) : 0;
-            const bool box_now = do_box && left == 0;
-            const bool to_final = left == 0 && final_out;
-            for_groups(sh.nb, pairs > 1, [&](Grp g) {
-                Timer t(ctx, &s, si, rh ? KC_SMOOTH_SMALL : KC_SMOOTH, px * g.n);
-                const float *src = a + g.b0 * sh.stride;
-                float *dst = to_final ? final_out[g.b0] : b + g.b0 * sh.stride;
-                const Batch bt = make_batch(sh, g, nullptr, nullptr, to_final ? final_out : nullptr);
-                const Batch *pb = g.n > 1 ? &bt : nullptr;
-                if (rh) launch_smooth_small(s.st, src, dst, W, H, p, box_now, rh, pb);
-                else launch_smooth_fused(s.st, src, dst, W, H, p, box_now, smooth_rows_for(ctx, W, H, s.alone, g.n), pb, smooth_class_for(W, H, g.n));
-            });
-            if (!to_final) std::swap(a, b);
-        } while (left > 0);
-    }
-    return UGSM_OK;
-}
-
-// Row f-4 (MatchGPULib.cpp:1323-1437): S_dx / C and S_dy / C of two device fields, synchronously (one host round trip).
-int weighted_difference(ugsm_ctx *ctx, Slot &s, const float *newd3, const float *oldd3, int W, int H, float out2[2])
-{
-    const size_t need = 3 * (size_t)H + 3;
-    if (need > s.wd_cap) {
-        if (s.wd_rows) HIPCHK(ctx, hipFree(s.wd_rows));
-        s.wd_rows = nullptr;
-        s.wd_cap = 0;
-        HIPCHK(ctx, hipMalloc((void **)&s.wd_rows, need * sizeof(double)));
-        s.wd_cap = need;
-    }
-    if (!s.wd_host) HIPCHK(ctx, hipHostMalloc((void **)&s.wd_host, 3 * sizeof(double), hipHostMallocDefault));
-    double *tot = s.wd_rows + 3 * (size_t)H;
-    launch_weighted_difference(s.st, newd3, oldd3, W, H, s.wd_rows, tot);
-    HIPCHK(ctx, hipMemcpyAsync(s.wd_host, tot, 3 * sizeof(double), hipMemcpyDeviceToHost, s.st));
-    HIPCHK(ctx, hipStreamSynchronize(s.st));
-    out2[0] = (float)(s.wd_host[0] / s.wd_host[2]);
-    out2[1] = (float)(s.wd_host[1] / s.wd_host[2]);
-    return UGSM_OK;
-}
-
-// matchlevel (MatchGPULib.cpp:1662-2489), iterations m_from..m_to, for every entry of the call (sh.nb; in lockstep).  Lv / Rv: the entries'
-// views of the level (sh.nb of them).  cur holds (dx,dy,conf) on entry and on exit; other is scratch of the same size (base pointers:
-// entry k's fields lie at + k * sh.stride).
-// final_out (optional, fused path only): per-pair destinations where the last iteration leaves its result instead of the ping-pong buffer
-// (saves the device-to-device copy of the finished level); cur/other are then not meaningful afterwards.
-// seed (optional, see fuse_seed; sh.nb entries): `cur` holds the COARSER level's field (seed->Ws x seed->Hs) and iteration m_from reads its
-// starting field through the seeding map instead of from a materialised seeded field.
-// A_pre (optional, single pairs only): A = G_clamp * L^2 of this level, already computed (on the slot's side stream; the caller has made
-// the main stream wait for it); otherwise it is computed here, into s.A.
-// in (kInPlanes, or kInRGB8: level 0 of a call with Slot::direct0): Lv / Rv are byte views of the pairs' images; the level runs k_cost_march
-// (level0_direct has seen to it) and any seed map has its origin at 0.  A shape of both directions may bring them too: a K-cost launch holds
-// the entries of one direction (cost_groups), so one R offset per entry serves it, and A = G * L^2 reads the L view alone.
-int run_level(ugsm_ctx *ctx, Slot &s, int si, const Shape &sh, const Img3 *Lv, const Img3 *Rv, int W, int H, int mi, int S, bool is_top, int m_from,
-              int m_to, float *&cur, float *&other, float *dbg8, float *const *final_out = nullptr, const SeedMap *seed = nullptr,
-              const float *A_pre = nullptr, int in = kInPlanes)
-{
-    const bool ref = ctx->cfg.kernel_path == 1;
-    const double px = (double)W * H;
-    std::vector<float> thr((size_t)std::max(mi, 1));
-    threshold_schedule(mi, thr.data());
-    // row f-4, opt-in: stop the level when the confidence-weighted mean change of dx and dy falls below the threshold.  The
-    // previous iteration's field has to survive the smoothing ping-pong, hence a third buffer.
-    const float eps = ctx->cfg.early_exit_threshold;
-    const bool early = eps > 0.0f;
-    if ((early || ref) && sh.nb != 1) return UGSM_ERR_STATE;  // (the batch entry points run such contexts pair by pair)
-    float *third = nullptr;
-    if (early) {
-        const size_t lvl = 3 * (size_t)W * H;
-        UCHK(grow(ctx, s.d2, s.d2_cap, std::max(lvl, s.lvl_cap)));
-        // the three field buffers rotate through the levels: the spare one is whichever is neither `cur` nor `other` right now
-        third = (s.d0 != cur && s.d0 != other) ? s.d0 : ((s.d1 != cur && s.d1 != other) ? s.d1 : s.d2);
-        final_out = nullptr;
-    }
-    int ran = 0;
-    const int pairs = launch_pairs(ctx, sh, W, H);
-    const bool batched = pairs > 1;
-    const bool march4 = !ref && use_march4(ctx, W, H, s.alone, pairs);
-    const bool march = !ref && use_march(ctx, W, H, s.alone, pairs);
-    const bool small = !ref && use_small_cost(ctx, W, H, s.alone, pairs);
-    if (in != kInPlanes) {  // byte views: what level0_direct promised must hold here, and the seed-crop origins -- whose Batch fields carry the R offsets -- are 0
-        bool origins0 = true;
-        for (int b = 0; seed && b < sh.nb; b++) origins0 = origins0 && seed[b].cx == 0 && seed[b].cy == 0;
-        if (in != kInRGB8 || march4 || !march || early || !origins0) {
-            ctx->err = in != kInRGB8 ? "level 0 from the image: no kernel instance for this input form"
-                       : !origins0   ? "level 0 from the image: a seed map with a crop origin (the rgb8 K-cost instance serves full mode only)"
-                                     : "level 0 from the image needs the level matched by k_cost_march (kernel-choice policy: march_min_pixels, k_cost_march4's range) "
-                                       "and no early exit";
-            return UGSM_ERR_STATE;
-        }
-    }
-    if (!ref && !march4 && !march && !small && !kDevLib) {  // (use_march gives every such level to k_cost_march: launch_cost_fused is a no-op here)
-        ctx->err = "no K-cost kernel of libugsm.so covers this level (kernel-choice policy)";
-        return UGSM_ERR_STATE;
-    }
-    const float *const A3 = A_pre ? A_pre : s.A;  // (entry k's A at + k * sh.stride)
-    if (!A_pre) {   // A = G_clamp * L^2 does not depend on the iteration: once per level.
-        for_groups(sh.nb, batched, [&](Grp g) {
-            Timer t(ctx, &s, si, KC_SQBLUR, px * g.n);
-            if (ref) {
-                launch_sqblur_clamp_ref(s.st, Lv[g.b0], W, H, s.A);
-            } else {
-                const Batch bt = make_batch(sh, g, Lv);
-                launch_sqblur_clamp(s.st, Lv[g.b0], W, H, s.A + g.b0 * sh.stride, g.n > 1 ? &bt : nullptr, in);
-            }
-        });
-    }
-    // (k_cost_split -- libugsm_dev.so, march_min_pixels < 0: the levels no other form covers -- has no batch index: pair by pair)
-    const bool cost_batched = batched && (march4 || march || small);
-    // K-cost moves an entry's L and R views by ONE offset (Batch::img), which serves the entries of one direction only -- entry b's views lie
-    // b pyramids behind entry 0's in both images, entry nreal + b's do so with the images exchanged -- so where a shape holds both
-    // directions (nreal < nb), a K-cost launch holds the entries of one: two launches where every other kernel of the level has one.
-    auto cost_groups = [&](auto &&f) {
-        if (sh.nb == sh.nreal) return for_groups(sh.nb, cost_batched, f);
-        for (int dir = 0; dir < 2; dir++) for_groups(sh.nreal, cost_batched, [&](Grp g) { f(Grp{g.b0 + dir * sh.nreal, g.n}); });
-    };
-    for (int m = m_from; m <= m_to; m++) {
-        const int blend = !(is_top && m == 1);  // MatchGPULib.cpp:2223
-        if (ref) {
-            {
-                Timer t(ctx, &s, si, KC_WARP, px);
-                launch_warp_ref(s.st, Rv[0], cur, W, H, s.Rw);
-            }
-            {
-                Timer t(ctx, &s, si, KC_SQBLUR, px);
-                launch_sqblur_clamp_ref(s.st, Img3{s.Rw, W, (size_t)W * H}, W, H, s.B);
-            }
-            Timer t(ctx, &s, si, KC_COST, px);
-            launch_cost_ref(s.st, Lv[0], s.Rw, A3, s.B, cur, other, W, H, thr[m - 1], blend, (m == m_to) ? dbg8 : nullptr);
-        } else {
-            const bool seeded = seed && m == m_from;
-            cost_groups([&](Grp g) {
-                Timer t(ctx, &s, si, march4 ? KC_COST_MARCH4 : (march ? KC_COST_MARCH : (small ? KC_COST_SMALL : KC_COST)), px * g.n);
-                const size_t fo = g.b0 * sh.stride;
-                const Img3 L = Lv[g.b0], R = Rv[g.b0];
-                Batch bt = make_batch(sh, g, Lv, seeded ? seed : nullptr);
-                if (in != kInPlanes)  // (byte views: the R image of a pair has an offset of its own, carried where the seed-crop origins -- 0 here -- ride)
-                    for (int j = 0; j < g.n; j++) {
-                        const long long d = byte_diff(Rv[g.b0 + j].p, Rv[g.b0].p);
-                        bt.cx[j] = (int)(unsigned)(d & 0xffffffffll);
-                        bt.cy[j] = (int)(d >> 32);
-                    }
-                const Batch *pb = g.n > 1 ? &bt : nullptr;
-                const unsigned *rb = s.range_known ? s.range_bad + g.b0 : nullptr;
-                if (march4)
-                    launch_cost_march4(s.st, L, R, A3 + fo, cur + fo, other + fo, W, H, thr[m - 1], blend, 0, rb, seeded ? seed[g.b0] : SeedMap{0, 0, 0, 0}, pb);
-                else if (march && seeded)
-                    launch_cost_march_seeded(s.st, L, R, A3 + fo, cur + fo, seed[g.b0], other + fo, W, H, thr[m - 1], blend, march_rows_arg(ctx), rb, pb, in);
-                else if (march) launch_cost_march(s.st, L, R, A3 + fo, cur + fo, other + fo, W, H, thr[m - 1], blend, march_rows_arg(ctx), rb, pb, in);
-                else if (small) launch_cost_small(s.st, L, R, A3 + fo, cur + fo, other + fo, W, H, thr[m - 1], blend, pb);
-                else launch_cost_fused(s.st, L, R, A3 + fo, cur + fo, other + fo, W, H, thr[m - 1], blend);
-            });
-        }
-        ran = m;
-        if (early) {
-            float *a = other, *b = third;  // cur (the field before this iteration) stays untouched
-            UCHK(enqueue_smooth(ctx, s, si, sh, a, b, W, H, S, true, nullptr));
-            float dif[2] = {0.0f, 0.0f};
-            if (m < m_to) UCHK(weighted_difference(ctx, s, a, cur, W, H, dif));
-            float *old = cur;
-            cur = a;  // the new field; b and the old field are the scratch pair of the next iteration
-            other = b;
-            third = old;
-            if (m < m_to && dif[0] < eps && dif[1] < eps) break;  // differenceIterations: both below the threshold
-            continue;
-        }
-        float *a = other, *b = cur;
-        UCHK(enqueue_smooth(ctx, s, si, sh, a, b, W, H, S, true, (m == m_to && !ref) ? final_out : nullptr));
-        if (m == m_to && !ref && final_out) break;
-        cur = a;
-        other = b;
-    }
-    s.iters_run[s.cur_level == kNoLevel ? 0 : s.cur_level] = ran;
-    HIPCHK(ctx, hipGetLastError());
-    return UGSM_OK;
-}
-
-Img3 level_view(const Slot &s, const float *pyr, int lev, int ox, int oy)
-{
-    return Img3{pyr + s.off[lev] + (size_t)oy * s.w[lev] + ox, s.w[lev], (size_t)s.w[lev] * s.h[lev]};
-}
-// the full-frame views of level `lev` for every entry of the call (a shape of real pairs)
-void full_views(const Slot &s, const Shape &sh, const float *pyr, int lev, Img3 *out)
-{
-    for (int b = 0; b < sh.nb; b++) out[b] = level_view(s, pyr + b * s.pyr_stride, lev, 0, 0);
-}
-
-// The pyramid that entry v of the call matches as its left (side 0) or right (side 1) image.  The entries nreal .. nb - 1 of a shape that
-// holds both directions are the entries 0 .. nreal - 1 with the two exchanged: the right-to-left match reads the same two pyramids.  The
-// entries of a multi-window call (Shape::one_pair) are windows of pair 0: every one reads its pyramids as they are -- and, in the checked
-// multi-window call, the entries nreal .. nb - 1 read them with the two exchanged.
-const float *pair_pyr(const Slot &s, const Shape &sh, int side, int v)
-{
-    const bool back = v >= sh.nreal;
-    if (sh.one_pair) return (side == 0) != back ? s.pyrL : s.pyrR;  // (n windows of one pair: ugsm_submit_foveated_multi[_checked])
-    return ((side == 0) != back ? s.pyrL : s.pyrR) + (size_t)(back ? v - sh.nreal : v) * s.pyr_stride;
-}
-void side_views(const Slot &s, const Shape &sh, int side, int lev, Img3 *out)
-{
-    for (int v = 0; v < sh.nb; v++) out[v] = level_view(s, pair_pyr(s, sh, side, v), lev, 0, 0);
-}
-
-// Level 0 of the pyramid is (float) of each byte of the image: it holds nothing the image does not, and at 16 MP storing it is 193 of the 338 MB
-// the pyramid pass writes per image.  A full-mode call therefore leaves it unwritten and its level-0 launches -- A = G_clamp * L^2 and K-cost,
-// which run last -- read the image itself: the caller's device buffer, which stays valid and untouched until the call is reported
-// (include/ugsm.h), or the slot's own upload.  Where: the fused path's k_pyr_base (three levels or more), level 0 matched by k_cost_march (the
-// one K-cost form with an 8-bit instance: the levels that large), rgb8 images (the other layouts keep the float level 0: eight more K-cost
-// bodies per layout for formats no measured workload uses), no early exit (it runs pair by pair through other buffers).  Everything
-// that hands the pyramids on -- ugsm_submit_pyramids, the foveated calls, the stage entry points -- stores level 0 as ever.
-// entries: how many fields the call runs in lockstep (0: the slot's pairs; a checked full-mode call: two per pair) -- what a launch holds decides the kernel.
-bool level0_direct(const ugsm_ctx *ctx, const Slot &s, int entries = 0)
-{
-    if (ctx->level0_float || ctx->cfg.kernel_path == 1 || ctx->cfg.early_exit_threshold > 0.0f || s.levels < 3) return false;
-    if (ctx->hooks.input_format != kInRGB8) return false;
-    Shape sh = Shape::pairs(s);
-    if (entries > 0) sh.nb = entries;
-    const int pairs = launch_pairs(ctx, sh, s.W, s.H);
-    return !use_march4(ctx, s.W, s.H, s.alone, pairs) && use_march(ctx, s.W, s.H, s.alone, pairs);
-}
-
-// Whether this call may use the slot's side stream: single pairs that have the chip to themselves (with four pairs in flight eight
-// streams on the four hardware queues serialise what one stream per pair lets overlap: -13 %), the fused path, no event brackets (the
-// statistics belong to one stream).
-bool side_stream_ok(const ugsm_ctx *ctx, const Slot &s)
-{
-    return s.nb == 1 && s.alone && s.st2 != nullptr && ctx->cfg.kernel_path != 1 && ctx->cfg.profile_events == 0 && ctx->two_streams;
-}
-// A = G_clamp * L^2 of the full-frame levels a_from .. top on the side stream, beside whatever the main stream does next (the right
-// pyramid's join, the coarse levels' iterations); run_level takes them through level_A, which makes the main stream wait for each.
-// a_top (a seeded call): the first level that is matched, where it is not the top one; < 0: the top level.
-int enqueue_side_A(ugsm_ctx *ctx, Slot &s, int a_from, int a_top = -1)
-{
-    if (a_from < 0 || ctx->cfg.early_exit_threshold > 0.0f) return UGSM_OK;
-    size_t tot = s.off[s.levels - 1] + 3 * (size_t)s.w[s.levels - 1] * s.h[s.levels - 1];
-    UCHK(grow(ctx, s.Apyr, s.apyr_cap, tot));
-    HIPCHK(ctx, hipEventRecord(s.ev_L, s.st));  // (the left pyramid is complete on the main stream)
-    s.forked = true;
-    HIPCHK(ctx, hipStreamWaitEvent(s.st2, s.ev_L, 0));
-    for (int i = a_top >= 0 ? a_top : s.levels - 1; i >= a_from; i--) {  // coarsest first: that is the order the levels need them in
-        if (i == 0 && s.direct0) launch_sqblur_clamp(s.st2, byte_view(s.img0L[0], s.img0_stride), s.w[0], s.h[0], s.Apyr + s.off[0], nullptr, kInRGB8);
-        else launch_sqblur_clamp(s.st2, level_view(s, s.pyrL, i, 0, 0), s.w[i], s.h[i], s.Apyr + s.off[i]);
-        HIPCHK(ctx, hipEventRecord(s.ev_A[i], s.st2));
-    }
-    s.a_from = a_from;
-    return UGSM_OK;
-}
-
-// The pyramids of every pair of the call (s.nb = nb pairs; rgbL / rgbR: nb device pointers).
-// a_from: the levels a_from .. top get their A = G_clamp * L^2 precomputed on the side stream (full mode: 0; foveated: F-1, the
-// fine levels work on crops whose A is clamped at the crop's own border and is computed in line); < 0: none.
-// full: the call is a full-mode match and nothing else reads these pyramids -- level 0 is then read from the images where level0_direct allows.
-// entries: the fields the call's levels run in lockstep where that is not nb (level0_direct).
-// first (a seeded call; < 0: none): the call matches the levels first .. 0 only: the pyramids hold the levels 0 .. max(first, 2) -- what k_pyr_base
-// makes in its one pass, and the levels up to the first -- so nothing that needs whole pyramids may follow (have_pyr), and A stops at `first`.
-int enqueue_pyramids(ugsm_ctx *ctx, Slot &s, int si, const uint8_t *const *d_rgbL, const uint8_t *const *d_rgbR, int nb, int W, int H, int stride, int a_from = -1,
-                     const FoveaWin *win = nullptr, bool full = false, int entries = 0, int first = -1)
-{
-    const int built = first < 0 ? 0 : std::max(first, 2) + 1;
-    if (!d_rgbL || !d_rgbR || nb < 1 || nb > kMaxBatch) return UGSM_ERR_BAD_ARG;
-    for (int b = 0; b < nb; b++)
-        if (!d_rgbL[b] || !d_rgbR[b]) return UGSM_ERR_BAD_ARG;
-    if (stride < input_row_bytes(ctx, W)) return UGSM_ERR_SIZE_MISMATCH;
-    UCHK(prepare_slot(ctx, s, W, H, nb));
-    // the pyramid kernels of the fused path check every value they write (level 0 holds the integers 0..255)
-    s.range_known = ctx->cfg.kernel_path != 1 && s.range_bad != nullptr;
-    if (s.range_known) HIPCHK(ctx, hipMemsetAsync(s.range_bad, 0, sizeof(unsigned) * nb, s.st));
-    // One stream, as in rounds 1 and 2: the one-stage-per-kernel path, a batch, and whenever launches are bracketed by events (the
-    // statistics belong to one stream).  Otherwise fork: R's pyramid and the A planes on the side stream.
-    const bool fork = side_stream_ok(ctx, s);
-    s.a_from = -1;
-    const bool direct0 = full && !win && level0_direct(ctx, s, entries);
-    s.direct0 = direct0;
-    if (direct0) {
-        for (int b = 0; b < nb; b++) {
-            s.img0L[b] = d_rgbL[b];
-            s.img0R[b] = d_rgbR[b];
-        }
-        s.img0_stride = stride;
-    }
-    if (!fork) {
-        UCHK(build_pyramids(ctx, s, si, d_rgbL, stride, s.pyrL, nullptr, win, direct0, built));
-        UCHK(build_pyramids(ctx, s, si, d_rgbR, stride, s.pyrR, nullptr, win, direct0, built));
-        s.have_pyr = nb == 1 && !win && !direct0 && built == 0;  // (the fovea-shard entry points work on single pairs, and on whole pyramids)
-        return UGSM_OK;
-    }
-    // the side stream starts after everything enqueued on this slot so far (the previous pair still reads pyrR and Apyr)
-    HIPCHK(ctx, hipEventRecord(s.ev_in, s.st));
-    s.forked = true;
-    HIPCHK(ctx, hipStreamWaitEvent(s.st2, s.ev_in, 0));
-    UCHK(build_pyramids(ctx, s, si, d_rgbR, stride, s.pyrR, s.st2, win, direct0, built));
-    HIPCHK(ctx, hipEventRecord(s.ev_R, s.st2));
-    UCHK(build_pyramids(ctx, s, si, d_rgbL, stride, s.pyrL, nullptr, win, direct0, built));
-    if (a_from >= 0) UCHK(enqueue_side_A(ctx, s, a_from, first));
-    HIPCHK(ctx, hipStreamWaitEvent(s.st, s.ev_R, 0));
-    HIPCHK(ctx, hipGetLastError());
-    s.have_pyr = !win && !direct0 && built == 0;
-    return UGSM_OK;
-}
-int enqueue_pyramids(ugsm_ctx *ctx, Slot &s, int si, const uint8_t *d_rgbL, const uint8_t *d_rgbR, int W, int H, int stride, int a_from = -1,
-                     const FoveaWin *win = nullptr, bool full = false)
-{
-    return enqueue_pyramids(ctx, s, si, &d_rgbL, &d_rgbR, 1, W, H, stride, a_from, win, full);
-}
-
-// the windows of a foveated call's pairs (n offsets), for enqueue_pyramids
-int fovea_windows(const ugsm_ctx *ctx, int W, int H, int n, const int *off_x, const int *off_y, FoveaWin &win)
-{
-    const int F = ctx->cfg.fovea_levels;
-    int w[UGSM_MAX_LEVELS], h[UGSM_MAX_LEVELS];
-    UCHK(level_dims(W, H, ctx->cfg.levels, w, h));
-    if (F < 2 || F > ctx->cfg.levels || n < 1 || n > kMaxBatch) return UGSM_ERR_BAD_ARG;
-    for (int b = 0; b < n; b++) {
-        FoveaGeom g;
-        fovea_geometry(w, h, F, off_x[b], off_y[b], g);
-        win.w = g.fw;
-        win.h = g.fh;
-        win.x0[b] = g.ox[0];
-        win.y0[b] = g.oy[0];
-    }
-    return UGSM_OK;
-}
-
-// A of full-frame level i if it was precomputed on the side stream (the main stream is made to wait for it here), else null
-const float *level_A(ugsm_ctx *ctx, Slot &s, int i)
-{
-    if (s.a_from < 0 || i < s.a_from) return nullptr;
-    if (hipStreamWaitEvent(s.st, s.ev_A[i], 0) != hipSuccess) return nullptr;
-    (void)ctx;
-    return s.Apyr + s.off[i];
-}
-
-// Level `lev` + 1's fields (Ws x Hs, in `cur`) handed to level `lev` (W x H): subsampleDisp, MatchGPULib.cpp:1526-1590, and
-// foveatedsubsampleDisp, :1595-1655.  Fills the entries' seed maps; where level `lev`'s first K-cost launch reads `cur` through them (fuse_seed)
-// that is all: true.  Otherwise launch_seed writes the seeded fields into `other` and the two swap: false.
-// g: the entries' fovea geometries, whose seed-crop origins of level `lev` apply; null (the full-frame levels): origin 0.
-bool hand_seed(ugsm_ctx *ctx, Slot &s, int si, const Shape &sh, int Ws, int Hs, int W, int H, const FoveaGeom *g, int lev, SeedMap *sm, float *&cur,
-               float *&other)
-{
-    for (int b = 0; b < sh.nb; b++) sm[b] = SeedMap{Ws, Hs, g ? g[b].cx[lev] : 0, g ? g[b].cy[lev] : 0};
-    const int np = launch_pairs(ctx, sh, W, H);
-    if (fuse_seed(ctx, W, H, s.alone, np)) return true;
-    for_groups(sh.nb, np > 1, [&](Grp gr) {
-        Timer t(ctx, &s, si, KC_SEED, (double)W * H * gr.n);
-        const Batch bt = make_batch(sh, gr, nullptr, sm);
-        launch_seed(s.st, cur + gr.b0 * sh.stride, Ws, Hs, other + gr.b0 * sh.stride, W, H, sm[gr.b0].cx, sm[gr.b0].cy, gr.n > 1 ? &bt : nullptr);
-    });
-    std::swap(cur, other);
-    return false;
-}
-
-// The full-frame levels from .. to of a call, coarse to fine, for the entries of `sh`: the loop of matching(), MatchGPULib.cpp:1196-1318.
-// Which levels, and what level `from` starts from, is the call's LevelRange:
-//   Zero (from == top): the zero seed, and level `from` is the top level (its first iteration takes no confidence);
-//   Prior: the restriction of the entries' full-resolution fields (launch_restrict) fills level `from`'s fields where the zero seed is
-//          otherwise set; the levels above run nothing, and level `from` is no top level, whichever it is -- its first iteration blends the
-//          confidence like any other, a prior has one;
-//   State: the entries' fields of level from + 1, placed in the level buffer and handed to level `from` by the cold call's own step
-//          (hand_seed): the descent goes on at level `from` as if the levels above had just run.
-// From there down everything is the same.  What else differs between the callers comes in:
-// views(i, Lv, Rv): fills the entries' views of level i and returns their form (run_level's `in`);
-// side_A: a level's A is taken from the side stream where it was precomputed there (level_A);
-// direct_out (optional): the entries' result buffers, which level 0's last smoothing launch writes itself where it can (no 193 MB device
-// copy at 16 MP): `field` is then null.  Otherwise `field` is the level buffer that holds level `to`'s fields, for the caller's copy.
-template <class Views>
-int enqueue_descent(ugsm_ctx *ctx, Slot &s, int si, const Shape &sh, const LevelRange &r, Views &&views, bool side_A, float *const *direct_out, float *&field)
-{
-    float *cur = s.d0, *other = s.d1;
-    const int from = r.from;
-    SeedMap sm[2 * kMaxBatch];  // (a shape of both directions: two entries per pair)
-    bool seeded = false;
-    if (r.start == LevelRange::State) {
-        s.cur_level = from + 1;
-        for (int b = 0; b < sh.nb; b++)
-            HIPCHK(ctx, hipMemcpyAsync(cur + b * sh.stride, r.source[b], sizeof(float) * 3 * (size_t)s.w[from + 1] * s.h[from + 1], hipMemcpyDeviceToDevice, s.st));
-        seeded = hand_seed(ctx, s, si, sh, s.w[from + 1], s.h[from + 1], s.w[from], s.h[from], nullptr, 0, sm, cur, other);
-    } else if (r.start == LevelRange::Prior) {
-        const float *const *prior = r.source;
-        s.cur_level = from;
-        for_groups(sh.nb, launch_pairs(ctx, sh, s.w[from], s.h[from]) > 1, [&](Grp g) {
-            Timer t(ctx, &s, si, KC_RESTRICT, (double)s.w[from] * s.h[from] * g.n);
-            Batch bt{};
-            bt.n = g.n;
-            for (int j = 0; j < g.n; j++) {
-                bt.in[j] = byte_diff(prior[g.b0 + j], prior[g.b0]);
-                bt.out[j] = (long long)(j * sh.stride * sizeof(float));
-            }
-            launch_restrict(s.st, prior[g.b0], s.W, s.H, from, cur + g.b0 * sh.stride, s.w[from], s.h[from], g.n > 1 ? &bt : nullptr);
-        });
-    } else {
-        for (int b = 0; b < sh.nb; b++)  // U1: zero seed
-            HIPCHK(ctx, hipMemsetAsync(cur + b * sh.stride, 0, sizeof(float) * 3 * (size_t)s.w[from] * s.h[from], s.st));
-    }
-    Img3 Lv[2 * kMaxBatch], Rv[2 * kMaxBatch];
-    field = nullptr;
-    for (int i = from; i >= r.to; i--) {
-        s.cur_level = i;
-        const int mi = level_iterations(i);
-        const bool direct = direct_out && i == 0 && ctx->cfg.kernel_path != 1 && level_smooth(0) > 0 && !(ctx->cfg.early_exit_threshold > 0.0f);
-        const int in = views(i, Lv, Rv);
-        UCHK(run_level(ctx, s, si, sh, Lv, Rv, s.w[i], s.h[i], mi, level_smooth(i), i == from && r.start == LevelRange::Zero, 1, mi, cur, other, nullptr,
-                       direct ? direct_out : nullptr, seeded ? sm : nullptr, side_A ? level_A(ctx, s, i) : nullptr, in));
-        if (direct) return UGSM_OK;
-        seeded = i > r.to && hand_seed(ctx, s, si, sh, s.w[i], s.h[i], s.w[i - 1], s.h[i - 1], nullptr, 0, sm, cur, other);
-    }
-    field = cur;
-    return UGSM_OK;
-}
-
-// the entries' fields of level `lev`, as a descent left them in `field` (entry v at + v * sh.stride), into their destinations
-int copy_fields(ugsm_ctx *ctx, Slot &s, const Shape &sh, const float *field, int lev, float *const *outs)
-{
-    for (int v = 0; v < sh.nb; v++)
-        HIPCHK(ctx, hipMemcpyAsync(outs[v], field + v * sh.stride, sizeof(float) * 3 * (size_t)s.w[lev] * s.h[lev], hipMemcpyDeviceToDevice, s.st));
-    return UGSM_OK;
-}
-
-// matching() with foveatedmatching==0 over the levels of `r`, for the s.nb pairs of the call; d_out: their buffers for level r.to's fields
-// (level 0: the results, which its last launch writes itself where it can).
-// swap: the images exchanged (the right-to-left match of the LR check): the right pyramid is the "left" image; A is then computed
-// in line (the side stream's A planes belong to the left image).
-int enqueue_full(ugsm_ctx *ctx, Slot &s, int si, float *const *d_out, const LevelRange &r, bool swap = false)
-{
-    const Shape sh = Shape::pairs(s);
-    const float *const pL = swap ? s.pyrR : s.pyrL, *const pR = swap ? s.pyrL : s.pyrR;
-    auto views = [&](int i, Img3 *Lv, Img3 *Rv) -> int {
-        if (i == 0 && s.direct0) {  // level 0 was not stored: the images themselves
-            for (int b = 0; b < sh.nb; b++) {
-                Lv[b] = byte_view(swap ? s.img0R[b] : s.img0L[b], s.img0_stride);
-                Rv[b] = byte_view(swap ? s.img0L[b] : s.img0R[b], s.img0_stride);
-            }
-            return kInRGB8;
-        }
-        full_views(s, sh, pL, i, Lv);
-        full_views(s, sh, pR, i, Rv);
-        return kInPlanes;
-    };
-    float *field;
-    UCHK(enqueue_descent(ctx, s, si, sh, r, views, !swap && sh.nb == 1, d_out, field));
-    return field ? copy_fields(ctx, s, sh, field, r.to, d_out) : UGSM_OK;
-}
-
-// The coarse half's prolongation (ugsm_submit_full_coarse): for the pairs with a d_full entry, the full-resolution field of their level-e
-// state in ONE launch (launch_prolong), read from d_state.
-int enqueue_prolong(ugsm_ctx *ctx, Slot &s, int si, int e, float *const *d_state, float *const *d_full)
-{
-    int asked[kMaxBatch], m = 0;
-    for (int b = 0; b < s.nb; b++)
-        if (d_full[b]) asked[m++] = b;
-    if (m == 0) return UGSM_OK;
-    Batch bt{};
-    bt.n = m;
-    for (int j = 0; j < m; j++) {
-        bt.in[j] = byte_diff(d_state[asked[j]], d_state[asked[0]]);
-        bt.out[j] = byte_diff(d_full[asked[j]], d_full[asked[0]]);
-    }
-    s.cur_level = e;
-    bool launched;
-    {
-        Timer t(ctx, &s, si, KC_PROLONG, (double)m * s.W * s.H);
-        launched = launch_prolong(s.st, d_state[asked[0]], s.w, s.h, e, d_full[asked[0]], m > 1 ? &bt : nullptr);
-    }
-    if (!launched) return ctx_fail(ctx, UGSM_ERR_BAD_ARG, "the prolongation: a size its kernel does not cover");
-    HIPCHK(ctx, hipGetLastError());
-    return UGSM_OK;
-}
-
-
-// The LR check's setting (ugsm_set_lr_check): which calls apply it, and the page-locked words its counts come back in
-bool lr_full_on(const ugsm_ctx *ctx) { return ctx->lr_tau > 0.0f && (ctx->lr_modes & UGSM_LR_FULL); }
-bool lr_fovea_on(const ugsm_ctx *ctx) { return ctx->lr_tau > 0.0f && (ctx->lr_modes & UGSM_LR_FOVEATED); }
-constexpr size_t kLrHostWords = 1 + (size_t)kMaxBatch * UGSM_MAX_LEVELS;
-int lr_host_ready(ugsm_ctx *ctx, Slot &s)
-{
-    if (!s.lr_host) HIPCHK(ctx, hipHostMalloc((void **)&s.lr_host, kLrHostWords * sizeof(unsigned long long), hipHostMallocDefault));
-    return UGSM_OK;
-}
-
-// The context's LR-consistency check of a full-mode call (ugsm_set_lr_check / ugsm_config.lr_check_threshold; no reference counterpart), behind
-// the match that wrote d_out: the match with the images exchanged into the slot's own buffer, then one kernel that zeroes the inconsistent
-// confidences of d_out.  (Single pairs, whole calls.)
-int enqueue_full_lr(ugsm_ctx *ctx, Slot &s, int si, float *d_out)
-{
-    const float tau = ctx->lr_tau;
-    const size_t n3 = 3 * (size_t)s.W * s.H;
-    UCHK(grow(ctx, s.lr, s.lr_cap, n3 + 4));
-    UCHK(lr_host_ready(ctx, s));
-    unsigned long long *cnt = reinterpret_cast<unsigned long long *>(s.lr + ((n3 + 1) & ~(size_t)1));  // (8-byte aligned)
-    HIPCHK(ctx, hipMemsetAsync(cnt, 0, sizeof *cnt, s.st));
-    UCHK(enqueue_full(ctx, s, si, &s.lr, LevelRange::cold(s.levels), true));
-    {
-        Timer t(ctx, &s, si, KC_MISC, (double)s.W * s.H);
-        launch_lr_check(s.st, d_out, s.lr, s.W, s.H, tau, cnt);
-    }
-    HIPCHK(ctx, hipMemcpyAsync(s.lr_host, cnt, sizeof *cnt, hipMemcpyDeviceToHost, s.st));
-    HIPCHK(ctx, hipGetLastError());
-    s.lr_ran = true;
-    return UGSM_OK;
-}
-
-// The room a checked full-mode call takes in the slot's LR buffer, in floats: one full field (Slot::lvl_stride: a multiple of 64 floats) for
-// every pair whose right-to-left field the caller does not take, the count words (one of 8 bytes per (pair, direction)) behind them.
-size_t lr_full_room(size_t lvl_stride, int kept, int n) { return (size_t)kept * lvl_stride + 4 * (size_t)n; }
-
-// ugsm_submit_full_checked: both directions of n full-mode pairs in lockstep, each pair's two fields checked against each other.
-//   - the pyramids of the n pairs once, as ugsm_submit_full_batch builds them (a lone pair: the right one on the side stream); level 0 stays
-//     unwritten where level0_direct allows, judged by the 2 n entries a launch of the call holds;
-//   - one descent over 2 n full-frame entries at a stride of one full field: entry n + b is pair b with the L and R views exchanged (pair_pyr;
-//     at level 0 of a direct call: the two images exchanged), under pair b's range word, which covers both of its pyramids.  Every kernel of a
-//     level takes the 2 n entries in one launch except K-cost, one launch per direction (cost_groups); more than kMaxBatch entries go through
-//     launches of equal size (group_pairs); levels above kBatchMaxPixels run entry by entry.  A is computed in line for both directions;
-//   - level 0's last smoothing launch writes the fields where they belong: d_out[b], and d_back[b] or the slot's LR buffer;
-//   - one launch of k_lr_check's stack form (F = 1: a stack of one full field) over the 2 n (pair, direction) checks with the call's own tau
-//     -- two launches from nine pairs on, an LrStack holds kMaxBatch checks -- and the counts back with one copy.
-// The caller has made the level buffers hold 2 n full fields and the LR buffer lr_full_room floats.
-int enqueue_full_checked(ugsm_ctx *ctx, Slot &s, int si, int n, const uint8_t *const *d_rgbL, const uint8_t *const *d_rgbR, int W, int H, int stride,
-                         float *const *d_out, float *const *d_back, float tau)
-{
-    UCHK(enqueue_pyramids(ctx, s, si, d_rgbL, d_rgbR, n, W, H, stride, -1, nullptr, true, 2 * n));
-    const Shape sh = Shape::full_both_directions(s);
-    int kept = 0;
-    float *outs[2 * kMaxBatch];
-    for (int b = 0; b < n; b++) {
-        outs[b] = d_out[b];
-        outs[n + b] = (d_back && d_back[b]) ? d_back[b] : s.lr + (size_t)kept++ * s.lvl_stride;
-    }
-    // (holds already, unless prepare_slot ran out of memory for the configured batch and fell back to this call's n pairs: it then freed what the
-    // caller had grown)
-    UCHK(ensure_level_bufs(ctx, s, sh.nb * sh.stride));
-    if (lr_full_room(s.lvl_stride, kept, n) > s.lr_cap || !s.lr_host) {
-        ctx->err = "the slot's buffers do not hold both directions' fields";
-        return UGSM_ERR_STATE;
-    }
-    if (s.range_known) HIPCHK(ctx, hipMemcpyAsync(s.range_bad + n, s.range_bad, sizeof(unsigned) * n, hipMemcpyDeviceToDevice, s.st));
-    auto views = [&](int i, Img3 *Lv, Img3 *Rv) -> int {
-        if (i == 0 && s.direct0) {  // level 0 was not stored: the images themselves, exchanged for the entries n .. 2 n - 1
-            for (int b = 0; b < n; b++) {
-                Lv[b] = Rv[n + b] = byte_view(s.img0L[b], s.img0_stride);
-                Rv[b] = Lv[n + b] = byte_view(s.img0R[b], s.img0_stride);
-            }
-            return kInRGB8;
-        }
-        side_views(s, sh, 0, i, Lv);
-        side_views(s, sh, 1, i, Rv);
-        return kInPlanes;
-    };
-    float *field;
-    UCHK(enqueue_descent(ctx, s, si, sh, LevelRange::cold(s.levels), views, false, outs, field));
-    if (field) UCHK(copy_fields(ctx, s, sh, field, 0, outs));
-    unsigned long long *cnt = reinterpret_cast<unsigned long long *>(s.lr + (size_t)kept * s.lvl_stride);
-    HIPCHK(ctx, hipMemsetAsync(cnt, 0, sizeof *cnt * 2 * n, s.st));
-    // k_lr_check's stack form with F = 1: a "stack" is then one full field.  Check 2 b is pair b's left-to-right field against its right-to-left
-    // one, check 2 b + 1 the two exchanged; each reads dx and dy of both fields and writes its own field's confidence alone, so both directions
-    // in one launch are race-free and either sees the other's unchecked field.  An LrStack holds kMaxBatch checks: up to eight pairs are one
-    // launch, nine to sixteen two of equal size.
-    for_groups(2 * n, true, [&](Grp g) {
-        LrStack ls{};
-        ls.n = g.n;
-        ls.F = 1;
-        for (int j = 0; j < g.n; j++) {
-            const int b = (g.b0 + j) >> 1, dir = (g.b0 + j) & 1;
-            ls.fwd[j] = byte_diff(outs[dir ? n + b : b], outs[0]);
-            ls.back[j] = byte_diff(outs[dir ? b : n + b], outs[0]);
-        }
-        Timer t(ctx, &s, si, KC_MISC, (double)g.n * s.W * s.H);
-        launch_lr_check(s.st, outs[0], outs[0], s.W, s.H, tau, cnt + g.b0, ls);
-    });
-    HIPCHK(ctx, hipMemcpyAsync(s.lr_host + 1, cnt, sizeof *cnt * 2 * n, hipMemcpyDeviceToHost, s.st));
-    HIPCHK(ctx, hipGetLastError());
-    s.lr_ran = true;
-    s.lr_full_pairs = n;
-    return UGSM_OK;
-}
-
-// a batched plane copy: entry j of group g from src0 + j * sh.stride (a level buffer) or from its view, to its own destination
-Batch copy_batch(const Shape &sh, Grp g, const Img3 *views, float *const *dsts, size_t dst_off)
-{
-    Batch b{};
-    b.n = g.n;
-    for (int j = 0; j < g.n; j++) {
-        b.img[j] = views ? byte_diff(views[g.b0 + j].p, views[g.b0].p) : (long long)(j * sh.stride * sizeof(float));
-        b.out[j] = byte_diff(dsts[g.b0 + j] + dst_off, dsts[g.b0] + dst_off);
-    }
-    return b;
-}
-
-// matching() with foveatedmatching==1 (MatchGPULib.cpp:1230-1294), split at level F-1; d_state: one buffer per entry of the call.
-int enqueue_fovea_coarse(ugsm_ctx *ctx, Slot &s, int si, const Shape &sh, float *const *d_state)
-{
-    const int F = ctx->cfg.fovea_levels;
-    if (F < 2 || F > s.levels) return UGSM_ERR_BAD_ARG;
-    auto views = [&](int i, Img3 *Lv, Img3 *Rv) -> int {
-        side_views(s, sh, 0, i, Lv);
-        side_views(s, sh, 1, i, Rv);
-        return kInPlanes;
-    };
-    float *cur;
-    UCHK(enqueue_descent(ctx, s, si, sh, LevelRange::coarse(s.levels, F - 1), views, sh.nb == 1, nullptr, cur));
-    const size_t fn = (size_t)s.w[F - 1] * s.h[F - 1];
-    if (sh.nb == 1) {
-        HIPCHK(ctx, hipMemcpyAsync(d_state[0], cur, sizeof(float) * 3 * fn, hipMemcpyDeviceToDevice, s.st));
-    } else {
-        for_groups(sh.nb, true, [&](Grp g) {
-            const Batch bt = copy_batch(sh, g, nullptr, d_state, 0);
-            launch_copy_view(s.st, Img3{cur + g.b0 * sh.stride, s.w[F - 1], fn}, s.w[F - 1], s.h[F - 1], d_state[g.b0], fn, s.w[F - 1], &bt);
-        });
-    }
-    s.have_coarse = sh.nb == 1;
-    return UGSM_OK;
-}
-
-// The fine phase for the sh.nb entries of the call: per-entry states and stacks (sh.nb of each), and sh.nreal window offsets and pyramid-stack
-// destinations (d_pyrL / d_pyrR may be null, and so may their entries): an exchanged entry of a shape of both directions has its twin's window,
-// and the pyramid stacks are the real pairs'.
-// first (the warm call, ugsm_submit_foveated_warm; < 0: none): the levels first .. 0 only, from starting fields that the caller's launch has
-// put where d_state is otherwise copied to -- s.d0, entry b at + b * sh.stride --: d_state is not read, the row blocks above `first` are the
-// caller's, and level `first` takes no seed.  first == F-1: the whole level F-1 is matched first, as the last level of the coarse phase is but
-// never as a top level (a prior has a confidence), and its block follows.
-int enqueue_fovea_fine(ugsm_ctx *ctx, Slot &s, int si, const Shape &sh, const float *const *d_state, const int *off_x, const int *off_y,
-                       float *const *d_stack, float *const *d_pyrL, float *const *d_pyrR, int first = -1)
-{
-    const int levels = s.levels, F = ctx->cfg.fovea_levels, nb = sh.nb;
-    if (F < 2 || F > levels || first >= F) return UGSM_ERR_BAD_ARG;
-    FoveaGeom g[2 * kMaxBatch];
-    for (int b = 0; b < nb; b++) fovea_geometry(s.w, s.h, F, off_x[b % sh.nreal], off_y[b % sh.nreal], g[b]);
-    const int fw = g[0].fw, fh = g[0].fh;
-    const size_t fn = (size_t)fw * fh;
-    const int np = launch_pairs(ctx, sh, fw, fh);  // (every level of the fine phase is a window of this size)
-    float *cur = s.d0, *other = s.d1;
-    for (int b = 0; first < 0 && b < nb; b++)
-        HIPCHK(ctx, hipMemcpyAsync(cur + b * sh.stride, d_state[b], sizeof(float) * 3 * fn, hipMemcpyDeviceToDevice, s.st));
-    // a stack row block / a pyramid-stack block for every entry: one launch for the batch
-    auto copy_out = [&](int pairs, const Img3 *views, const float *field, float *const *dsts, size_t dst_off, size_t dst_plane) {
-        for_groups(pairs, np > 1, [&](Grp gr) {
-            const Batch bt = copy_batch(sh, gr, views, dsts, dst_off);
-            const Img3 src = views ? views[gr.b0] : Img3{field + gr.b0 * sh.stride, fw, fn};
-            launch_copy_view(s.st, src, fw, fh, dsts[gr.b0] + dst_off, dst_plane, fw, gr.n > 1 ? &bt : nullptr);
-        });
-    };
-    // stack row block F-1 = the whole level F-1 (UG_GPU_matcher.cpp:293-303)
-    if (first < 0) copy_out(nb, nullptr, cur, d_stack, (size_t)(F - 1) * fn, (size_t)F * fn);
-    SeedMap sm[2 * kMaxBatch];
-    Img3 Lv[2 * kMaxBatch], Rv[2 * kMaxBatch];
-    for (int i = first < 0 ? F - 2 : first; i >= 0; i--) {
-        s.cur_level = i;
-        for (int b = 0; b < nb; b++) {
-            const int ox = i < F - 1 ? g[b].ox[i] : 0, oy = i < F - 1 ? g[b].oy[i] : 0;
-            Lv[b] = level_view(s, pair_pyr(s, sh, 0, b), i, ox, oy);
-            Rv[b] = level_view(s, pair_pyr(s, sh, 1, b), i, ox, oy);
-        }
-        const bool seeded = i != first && hand_seed(ctx, s, si, sh, fw, fh, fw, fh, g, i, sm, cur, other);
-        const int mi = level_iterations(i);
-        UCHK(run_level(ctx, s, si, sh, Lv, Rv, fw, fh, mi, level_smooth(i), false, 1, mi, cur, other, nullptr, nullptr, seeded ? sm : nullptr));
-        copy_out(nb, nullptr, cur, d_stack, (size_t)i * fn, (size_t)F * fn);
-    }
-    // pyramid stacks as the node publishes them (UG_GPU_matcher.cpp:203-213): [level][channel][row]
-    for (int side = 0; side < 2; side++) {
-        float *const *dsts = side == 0 ? d_pyrL : d_pyrR;
-        if (!dsts) continue;
-        const int nr = sh.nreal;
-        bool all = true, any = false;
-        for (int b = 0; b < nr; b++) {
-            all = all && dsts[b] != nullptr;
-            any = any || dsts[b] != nullptr;
-        }
-        if (!any) continue;
-        const float *pyr = side == 0 ? s.pyrL : s.pyrR;
-        for (int k = 0; k < F; k++) {
-            for (int b = 0; b < nr; b++) {
-                const int ox = (k < F - 1) ? g[b].ox[k] : 0, oy = (k < F - 1) ? g[b].oy[k] : 0;
-                Lv[b] = level_view(s, pyr + b * s.pyr_stride, k, ox, oy);
-            }
-            if (all) {
-                copy_out(nr, Lv, nullptr, dsts, (size_t)k * 3 * fn, fn);
-            } else {
-                for (int b = 0; b < nr; b++)
-                    if (dsts[b]) launch_copy_view(s.st, Lv[b], fw, fh, dsts[b] + (size_t)k * 3 * fn, fn, fw);
-            }
-        }
-    }
-    HIPCHK(ctx, hipGetLastError());
-    return UGSM_OK;
-}
-
-// pair 0's range word into the entries 1 .. m - 1 (windows of one pair run under its word), doubling what is already there
-int spread_range_word(ugsm_ctx *ctx, Slot &s, int m)
-{
-    for (int c = 1; s.range_known && c < m; c *= 2)
-        HIPCHK(ctx, hipMemcpyAsync(s.range_bad + c, s.range_bad, sizeof(unsigned) * std::min(c, m - c), hipMemcpyDeviceToDevice, s.st));
-    return UGSM_OK;
-}
-
-// The room a checked foveated call takes in the slot's LR buffer, in floats.  Entry k's right-to-left stack lies at k * per; the count words (one
-// of 8 bytes per (entry, level); at a multiple of 64 floats: aligned) at cnt.  The right-to-left level-F-1 state: n pairs keep one each behind
-// their stack, at k * per + state; n windows of one pair (one_state) share one behind the last stack, at state.
-struct LrRoom {
-    size_t per, state, cnt, total;
-};
-LrRoom lr_room(int n, int F, int fw, int fh, bool one_state)
-{
-    const size_t stackf = 3 * (size_t)F * fw * fh, field = 3 * (size_t)fw * fh;
-    LrRoom r;
-    r.per = ((one_state ? stackf : stackf + field) + 63) & ~(size_t)63;
-    r.state = one_state ? (size_t)n * r.per : stackf;
-    r.cnt = (size_t)n * r.per + (one_state ? fovea_field_room(fw, fh) : 0);
-    r.total = r.cnt + 2 * (size_t)n * F;
-    return r;
-}
-
-// The tail of a checked foveated call: one launch of k_lr_check's stack form over every level of the n stacks against their right-to-left
-// twins (entry k's at s.lr + k * per) -- after the last level, so nothing feeds back into the matching -- and the counts back with one copy on
-// the slot's stream.
-int enqueue_lr_stack_check(ugsm_ctx *ctx, Slot &s, int si, int n, int F, int fw, int fh, float tau, float *const *d_stack, size_t per,
-                           unsigned long long *cnt)
-{
-    HIPCHK(ctx, hipMemsetAsync(cnt, 0, sizeof *cnt * n * F, s.st));
-    LrStack ls{};
-    ls.n = n;
-    ls.F = F;
-    for (int b = 0; b < n; b++) {
-        ls.fwd[b] = byte_diff(d_stack[b], d_stack[0]);
-        ls.back[b] = (long long)((size_t)b * per * sizeof(float));
-    }
-    {
-        Timer t(ctx, &s, si, KC_MISC, (double)((size_t)fw * fh) * F * n);
-        launch_lr_check(s.st, d_stack[0], s.lr, fw, fh, tau, cnt, ls);
-    }
-    HIPCHK(ctx, hipMemcpyAsync(s.lr_host + 1, cnt, sizeof *cnt * n * F, hipMemcpyDeviceToHost, s.st));
-    HIPCHK(ctx, hipGetLastError());
-    s.lr_fov_pairs = n;
-    s.lr_fov_F = F;
-    return UGSM_OK;
-}
-
-// (single pairs: the stage-wise entry points, and a multi-window call that runs window by window)
-int enqueue_fovea_coarse(ugsm_ctx *ctx, Slot &s, int si, float *d_state) { return enqueue_fovea_coarse(ctx, s, si, Shape::pairs(s), &d_state); }
-int enqueue_fovea_fine(ugsm_ctx *ctx, Slot &s, int si, const float *d_state, int off_x, int off_y, float *d_stack, float *d_pyrL, float *d_pyrR)
-{
-    return enqueue_fovea_fine(ctx, s, si, Shape::pairs(s), &d_state, &off_x, &off_y, &d_stack, d_pyrL ? &d_pyrL : nullptr, d_pyrR ? &d_pyrR : nullptr);
-}
-
-}  // namespace
-// One foveated call of n pairs on device buffers: the pyramids, the coarse levels, the fine levels into the pairs' stacks.  state: n buffers
-// of 3 fovW fovH floats for level F-1's field between the two phases; d_pyrL / d_pyrR as for enqueue_fovea_fine.
-// With the foveated LR check on (ugsm_set_lr_check) the call matches both directions in lockstep and checks the stacks against each other:
-//   - the pyramids are built once; entry n + b of the shape reads pair b's with the L and R views exchanged (pair_pyr), through pair b's windows
-//     and seed maps, under pair b's range word (it covers both images' pyramids: build_pyramids reports either image into range_bad[pair]);
-//     every kernel of a level takes the 2 n entries in one launch except K-cost, which takes each direction in one (run_level);
-//   - every field of a foveated call is at most fovW x fovH, so the 2 n fields lie in the slot's level buffers at a stride of one such field
-//     (n pairs hold n x 3 W H floats per buffer and need 2 n x 3 fovW fovH, fovW fovH <= W H / 2 for every F >= 2: it fits, for F = 2 just);
-//   - what does NOT fit there for F = 2 is the right-to-left STACK, which has to outlive the fine levels: A, d0 and d1 are then full.  It goes,
-//     with the right-to-left state, into the slot's LR buffer (Slot::lr, what the full-mode check keeps its second field in; lr_room): 3 (F + 1)
-//     fovW fovH floats per pair, 24 MB at 16 MP beside the pair's 1.35 GB, counted by ugsm_context_device_bytes;
-//   - one launch checks every level of every pair's stack after the last level (enqueue_lr_stack_check).
-int ugsm::enqueue_match_foveated(ugsm_ctx *ctx, Slot &s, int si, int n, const uint8_t *const *d_rgbL, const uint8_t *const *d_rgbR, int W, int H, int stride,
-                                 const int *off_x, const int *off_y, float *const *state, float *const *d_stack, float *const *d_pyrL, float *const *d_pyrR)
-{
-    const int F = ctx->cfg.fovea_levels;
-    FoveaWin win;
-    UCHK(fovea_windows(ctx, W, H, n, off_x, off_y, win));
-    if (!lr_fovea_on(ctx)) {
-        // (a single pair alone on the chip gets level F-1 .. top's A planes from the side stream; a batch computes A in line)
-        UCHK(enqueue_pyramids(ctx, s, si, d_rgbL, d_rgbR, n, W, H, stride, n == 1 ? F - 1 : -1, &win));
-        const Shape sh = Shape::pairs(s);
-        UCHK(enqueue_fovea_coarse(ctx, s, si, sh, state));
-        return enqueue_fovea_fine(ctx, s, si, sh, state, off_x, off_y, d_stack, d_pyrL, d_pyrR);
-    }
-    UCHK(enqueue_pyramids(ctx, s, si, d_rgbL, d_rgbR, n, W, H, stride, -1, &win));
-    const int fw = s.w[F - 1], fh = s.h[F - 1];
-    const Shape sh = Shape::both_directions(n, fovea_field_room(fw, fh));
-    const LrRoom room = lr_room(n, F, fw, fh, false);
-    UCHK(ensure_level_bufs(ctx, s, sh.nb * sh.stride));  // (holds already: see above)
-    UCHK(grow(ctx, s.lr, s.lr_cap, room.total));
-    UCHK(lr_host_ready(ctx, s));
-    if (s.range_known) HIPCHK(ctx, hipMemcpyAsync(s.range_bad + n, s.range_bad, sizeof(unsigned) * n, hipMemcpyDeviceToDevice, s.st));
-    float *vstate[2 * kMaxBatch], *vstack[2 * kMaxBatch];
-    for (int b = 0; b < n; b++) {
-        vstate[b] = state[b];
-        vstack[b] = d_stack[b];
-        vstack[n + b] = s.lr + (size_t)b * room.per;
-        vstate[n + b] = vstack[n + b] + room.state;
-    }
-    UCHK(enqueue_fovea_coarse(ctx, s, si, sh, vstate));
-    UCHK(enqueue_fovea_fine(ctx, s, si, sh, vstate, off_x, off_y, vstack, d_pyrL, d_pyrR));
-    return enqueue_lr_stack_check(ctx, s, si, n, F, fw, fh, ctx->lr_tau, d_stack, room.per, reinterpret_cast<unsigned long long *>(s.lr + room.cnt));
-}
-
-// One full-mode call of n pairs on device buffers over the levels of `given` (null: the cold call), every kind of it -- whole, seeded, either half:
-//   - the pyramids, as far up as the range reaches: a descent that starts below the top (seeded, fine half) builds the levels 0 .. max(from, 2)
-//     only.  A lone pair's A planes come from the side stream, where the call is alone, for the levels the range runs (to .. from); several
-//     pairs compute A in line;
-//   - the levels of all pairs in lockstep, level `to`'s fields into d_out (level 0: written by its last launch where that can be);
-//   - a lone pair's whole call: the context's LR check where it is on (several pairs: no check -- batch_runs_pair_by_pair);
-//   - the coarse half: the prolongation of the fields it was asked for.
-int ugsm::enqueue_match_full(ugsm_ctx *ctx, Slot &s, int si, int n, const uint8_t *const *d_rgbL, const uint8_t *const *d_rgbR, int W, int H, int stride,
-                             float *const *d_out, const LevelRange *given)
-{
-    const LevelRange r = given ? *given : LevelRange::cold(ctx->cfg.levels);
-    UCHK(enqueue_pyramids(ctx, s, si, d_rgbL, d_rgbR, n, W, H, stride, n == 1 ? r.to : -1, nullptr, true, 0, r.start == LevelRange::Zero ? -1 : r.from));
-    UCHK(enqueue_full(ctx, s, si, d_out, r));
-    if (n == 1 && r.whole() && lr_full_on(ctx)) UCHK(enqueue_full_lr(ctx, s, si, d_out[0]));
-    return r.full ? enqueue_prolong(ctx, s, si, r.to, d_out, r.full) : UGSM_OK;
-}
-
-namespace {
-// The frame of a ugsm_submit_* of n pairs on device buffers, whose refusals have been made: the device, body(slot, b, k) for the pairs
-// b .. b + k - 1 -- all n in one (per == n) or one after the other (per == 1: the contexts of batch_runs_pair_by_pair) --, the completion mark.
-template <class Body>
-int submit_pairs(ugsm_ctx *ctx, Slot &s, int n, int per, Body &&body)
-{
-    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
-    for (int b = 0; b < n; b += per) UCHK(body(s, b, per));
-    return mark_done(ctx, s);
-}
-// ... of a call that has nothing to refuse between the slot's own refusals and the device
-template <class Body>
-int submit_pairs(ugsm_ctx *ctx, int slot, int n, int per, Body &&body)
-{
-    Slot *s;
-    UCHK(get_slot(ctx, slot, &s));
-    return submit_pairs(ctx, *s, n, per, body);
-}
-}  // namespace
-
-// The seeded full-mode call (ugsm_submit_full_seeded; its refusals: ugsm_seeded.cpp): n pairs in lockstep from level `start_level` of their priors.
-int ugsm::seeded_submit(ugsm_ctx *ctx, int slot, int n, const uint8_t *const *d_rgbL, const uint8_t *const *d_rgbR, int W, int H, int stride,
-                        const float *const *d_prior, int start_level, float *const *d_out)
-{
-    return submit_pairs(ctx, slot, n, batch_runs_pair_by_pair(ctx) ? 1 : n, [&](Slot &s, int b, int k) {
-        const LevelRange r = LevelRange::seeded(start_level, d_prior + b);
-        return enqueue_match_full(ctx, s, slot, k, d_rgbL + b, d_rgbR + b, W, H, stride, d_out + b, &r);
-    });
-}
-
-// The full-mode call in two halves (ugsm_submit_full_coarse, ugsm_submit_full_fine; their refusals: ugsm_coarse.cpp), n pairs in lockstep.
-// Coarse: the levels top .. stop_level into d_state, and the prolongation.  Fine: the levels state_level - 1 .. 0 from the states of state_level.
-int ugsm::coarse_submit(ugsm_ctx *ctx, int slot, int n, const uint8_t *const *d_rgbL, const uint8_t *const *d_rgbR, int W, int H, int stride,
-                        int stop_level, float *const *d_state, float *const *d_full)
-{
-    return submit_pairs(ctx, slot, n, batch_runs_pair_by_pair(ctx) ? 1 : n, [&](Slot &s, int b, int k) {
-        const LevelRange r = LevelRange::coarse(ctx->cfg.levels, stop_level, d_full ? d_full + b : nullptr);
-        return enqueue_match_full(ctx, s, slot, k, d_rgbL + b, d_rgbR + b, W, H, stride, d_state + b, &r);
-    });
-}
-int ugsm::fine_submit(ugsm_ctx *ctx, int slot, int n, const uint8_t *const *d_rgbL, const uint8_t *const *d_rgbR, int W, int H, int stride,
-                      const float *const *d_state, int state_level, float *const *d_out)
-{
-    return submit_pairs(ctx, slot, n, batch_runs_pair_by_pair(ctx) ? 1 : n, [&](Slot &s, int b, int k) {
-        const LevelRange r = LevelRange::fine(state_level, d_state + b);
-        return enqueue_match_full(ctx, s, slot, k, d_rgbL + b, d_rgbR + b, W, H, stride, d_out + b, &r);
-    });
-}
-namespace {
-// The starting fields of the fovea levels start .. F-1 of n entries from their priors, one launch (launch_restrict_stack): the rows from the
-// two windows' geometries; up to kRestrictStackByValue of them in the launch's arguments, more through the slot's table.  Level `start` goes
-// to `work` (entry b at + b * work_stride floats) where that is given, everything else to the row blocks of d_stack.
-int enqueue_restrict_stack(ugsm_ctx *ctx, Slot &s, int si, int n, const int *w, const int *h, int F, const float *const *prior, const int *poff_x,
-                           const int *poff_y, bool field, const int *off_x, const int *off_y, int start, float *const *d_stack, float *work, size_t work_stride)
-{
-    RestrictStack rs{};
-    rs.n = n;
-    rs.F = F;
-    rs.s = start;
-    rs.field = field ? 1 : 0;
-    rs.W = w[0];
-    rs.H = h[0];
-    rs.fw = w[F - 1];
-    rs.fh = h[F - 1];
-    for (int l = 0; l < F; l++) {
-        rs.w[l] = w[l];
-        rs.h[l] = h[l];
-    }
-    RestrictStackRow local[kRestrictStackByValue], *rows = local;
-    const bool table = n > kRestrictStackByValue;
-    int turn = 0;
-    if (table) {
-        UCHK(grow(ctx, s.warm_tab, s.warm_tab_cap, (size_t)kMaxBatch));
-        if (!s.warm_tab_h) HIPCHK(ctx, hipHostMalloc((void **)&s.warm_tab_h, Slot::kWarmRing * kMaxBatch * sizeof(RestrictStackRow), hipHostMallocDefault));
-        turn = s.warm_next;
-        s.warm_next = (turn + 1) % Slot::kWarmRing;
-        if (!s.warm_ev[turn]) HIPCHK(ctx, hipEventCreateWithFlags(&s.warm_ev[turn], hipEventDisableTiming));
-        if (s.warm_ev_set[turn]) HIPCHK(ctx, hipEventSynchronize(s.warm_ev[turn]));  // (the upload of the call kWarmRing back: long done)
-        rows = s.warm_tab_h + (size_t)turn * kMaxBatch;
-    }
-    for (int b = 0; b < n; b++) {
-        FoveaGeom gn, gp;
-        fovea_geometry(w, h, F, off_x ? off_x[b] : 0, off_y ? off_y[b] : 0, gn);
-        if (!field) fovea_geometry(w, h, F, poff_x ? poff_x[b] : 0, poff_y ? poff_y[b] : 0, gp);
-        RestrictStackRow &r = rows[b];
-        r = RestrictStackRow{};
-        r.prior = byte_diff(prior[b], prior[0]);
-        r.dst = byte_diff(d_stack[b], d_stack[0]);
-        r.work = (long long)(b * work_stride * sizeof(float));
-        for (int l = 0; l < F - 1; l++) {
-            r.nox[l] = gn.ox[l];
-            r.noy[l] = gn.oy[l];
-            r.pox[l] = field ? 0 : gp.ox[l];
-            r.poy[l] = field ? 0 : gp.oy[l];
-        }
-    }
-    if (table) {
-        HIPCHK(ctx, hipMemcpyAsync(s.warm_tab, rows, (size_t)n * sizeof(RestrictStackRow), hipMemcpyHostToDevice, s.st));
-        HIPCHK(ctx, hipEventRecord(s.warm_ev[turn], s.st));
-        s.warm_ev_set[turn] = true;
-        rs.table = s.warm_tab;
-    }
-    s.cur_level = start;
-    bool ok;
-    {
-        Timer t(ctx, &s, si, KC_RESTRICT_STACK, (double)n * (F - start) * rs.fw * rs.fh);
-        ok = launch_restrict_stack(s.st, prior[0], d_stack[0], work, rs, rows);
-    }
-    s.cur_level = kNoLevel;
-    if (!ok) return ctx_fail(ctx, UGSM_ERR_STATE, "the warm foveated call: a window that leaves its level");
-    HIPCHK(ctx, hipGetLastError());
-    return UGSM_OK;
-}
-
-// The warm foveated call (ugsm_submit_foveated_warm[_field]; its refusals: ugsm_fovea_seeded.cpp): n pairs in lockstep from fovea level `start`
-// of their priors.  The pyramids stop at level max(start, 2), level 0 inside the new windows; A is computed in line at every level (level F-1,
-// where it is matched, included: the side stream's A planes serve the coarse phase, which does not run).  One launch writes every starting
-// field: level `start`'s into the level buffer the fine phase starts in, the levels above into the stacks' row blocks.
-int enqueue_match_foveated_warm(ugsm_ctx *ctx, Slot &s, int si, int n, const uint8_t *const *d_rgbL, const uint8_t *const *d_rgbR, int W, int H, int stride,
-                                const int *off_x, const int *off_y, const float *const *d_prior, const int *poff_x, const int *poff_y, bool field, int start,
-                                float *const *d_stack)
-{
-    const int F = ctx->cfg.fovea_levels;
-    FoveaWin win;
-    UCHK(fovea_windows(ctx, W, H, n, off_x, off_y, win));
-    UCHK(enqueue_pyramids(ctx, s, si, d_rgbL, d_rgbR, n, W, H, stride, -1, &win, false, 0, start));
-    const Shape sh = Shape::pairs(s);
-    UCHK(enqueue_restrict_stack(ctx, s, si, n, s.w, s.h, F, d_prior, poff_x, poff_y, field, off_x, off_y, start, d_stack, s.d0, sh.stride));
-    return enqueue_fovea_fine(ctx, s, si, sh, nullptr, off_x, off_y, d_stack, nullptr, nullptr, start);
-}
-}  // namespace
-int ugsm::fovea_warm_submit(ugsm_ctx *ctx, int slot, int n, const uint8_t *const *d_rgbL, const uint8_t *const *d_rgbR, int W, int H, int stride, const int *off_x,
-                            const int *off_y, const float *const *d_prior, const int *prior_off_x, const int *prior_off_y, int field, int start_level,
-                            float *const *d_stack)
-{
-    const int zeros[UGSM_MAX_BATCH] = {0};
-    const int *ox = off_x ? off_x : zeros, *oy = off_y ? off_y : zeros, *px = prior_off_x ? prior_off_x : zeros, *py = prior_off_y ? prior_off_y : zeros;
-    const int per = (n == 1 || fovea_batch_runs_pair_by_pair(ctx)) ? 1 : n;  // (kernel_path 1: the pairs one after the other, as ugsm_submit_foveated_batch)
-    return submit_pairs(ctx, slot, n, per, [&](Slot &s, int b, int k) {
-        return enqueue_match_foveated_warm(ctx, s, slot, k, d_rgbL + b, d_rgbR + b, W, H, stride, ox + b, oy + b, d_prior + b, px + b, py + b, field != 0,
-                                           start_level, d_stack + b);
-    });
-}
-namespace {
-
-// Level 0 of both images inside the n windows of a multi-window call (k_pyr_base stored none: FoveaWin::later), one launch.
-int enqueue_level0_windows(ugsm_ctx *ctx, Slot &s, int si, const uint8_t *d_rgbL, const uint8_t *d_rgbR, int stride, int n, const FoveaWin &win)
-{
-    if (ctx->cfg.kernel_path != 1 && s.levels >= 3) {  // (k_pyr_base built them: as `base` in build_pyramids)
-        Level0Windows lw{};
-        lw.n = n;
-        lw.w = win.w;
-        lw.h = win.h;
-        for (int k = 0; k < n; k++) {
-            lw.x0[k] = win.x0[k];
-            lw.y0[k] = win.y0[k];
-        }
-        s.cur_level = 0;
-        bool ok;
-        {
-            Timer t(ctx, &s, si, KC_LEVEL0_WIN, 2.0 * n * win.w * win.h);
-            ok = launch_level0_windows(s.st, d_rgbL, d_rgbR, stride, s.W, s.H, s.pyrL + s.off[0], s.pyrR + s.off[0], lw, ctx->hooks.input_format);
-        }
-        s.cur_level = kNoLevel;
-        if (!ok) {
-            ctx->err = "a fovea window leaves the frame";
-            return UGSM_ERR_STATE;
-        }
-        HIPCHK(ctx, hipGetLastError());
-    }
-    return UGSM_OK;
-}
-
-// n fovea windows on ONE pair (ugsm_submit_foveated_multi): what does not depend on the window runs once, the rest in lockstep.
-//   - the pyramids of one pair, as a lone foveated call builds them (side stream and A planes of levels F-1 .. top included), but with no
-//     level 0 (FoveaWin::later); one launch then writes level 0 of both images inside the n windows (k_rgb_planes' window form).  Pyramids
-//     that k_pyr_base does not build (fewer than three levels, kernel_path 1) hold level 0 whole and skip that launch;
-//   - the coarse phase once, its field into `state`;
-//   - the fine phase on a shape of n windows that all read pair 0's pyramids (Shape::one_pair, pair_pyr), start from the one state and
-//     run under pair 0's range word; their fields lie in the level buffers at a stride of one fovea field, as a checked call's do.  The
-//     caller has made the buffers hold n such fields (n x 3 fovW fovH floats exceed one pair's 3 W H as soon as n > 2^(F-1));
-//   - contexts that run pair by pair (early exit, kernel_path 1) and n == 1: the fine phase window after window, as single pairs.
-// Afterwards the slot holds no whole pyramids (have_pyr, have_coarse false).
-int enqueue_foveated_multi(ugsm_ctx *ctx, Slot &s, int si, const uint8_t *d_rgbL, const uint8_t *d_rgbR, int W, int H, int stride, int n,
-                           const int *off_x, const int *off_y, float *state, float *const *d_stack)
-{
-    const int F = ctx->cfg.fovea_levels;
-    FoveaWin win;
-    UCHK(fovea_windows(ctx, W, H, n, off_x, off_y, win));
-    win.later = true;
-    UCHK(enqueue_pyramids(ctx, s, si, d_rgbL, d_rgbR, W, H, stride, F - 1, &win));
-    UCHK(enqueue_level0_windows(ctx, s, si, d_rgbL, d_rgbR, stride, n, win));
-    int st = enqueue_fovea_coarse(ctx, s, si, state);
-    if (st == UGSM_OK) {
-        if (n == 1 || ctx->cfg.kernel_path == 1 || ctx->cfg.early_exit_threshold > 0.0f) {
-            for (int k = 0; k < n && st == UGSM_OK; k++) st = enqueue_fovea_fine(ctx, s, si, state, off_x[k], off_y[k], d_stack[k], nullptr, nullptr);
-        } else {
-            const Shape sh = Shape::windows(n, fovea_field_room(win.w, win.h));
-            if (sh.nb * sh.stride > s.lvl_cap) {
-                ctx->err = "the level buffers do not hold the windows' fields";
-                return UGSM_ERR_STATE;
-            }
-            UCHK(spread_range_word(ctx, s, n));
-            const float *vstate[kMaxBatch];
-            for (int k = 0; k < n; k++) vstate[k] = state;
-            st = enqueue_fovea_fine(ctx, s, si, sh, vstate, off_x, off_y, d_stack, nullptr, nullptr);
-        }
-    }
-    s.have_pyr = false;
-    s.have_coarse = false;
-    return st;
-}
-
-// ugsm_submit_foveated_multi_checked: n windows of one pair, both directions in lockstep, the n stacks checked against their right-to-left twins.
-// enqueue_foveated_multi and the checked enqueue_match_foveated composed:
-//   - one pair's pyramids with no level 0 and the one k_level0_windows launch, as the plain multi call (no A planes from the side stream: the
-//     coarse phase runs on two entries and computes A in line, as every batch does).  The right-to-left direction reads the same two
-//     pyramids, so nothing more is stored;
-//   - pair 0's range word into the entries 1 .. 2 n - 1;
-//   - the coarse phase once for the two directions (Shape::coarse_both_directions: entry 1 = pair 0 exchanged, pair_pyr), level F-1's two
-//     fields into `state` and into the LR buffer;
-//   - the fine phase on Shape::windows_both_directions: entry k is window k left-to-right from the first state, entry n + k window k
-//     right-to-left from the second, its stack in the LR buffer.  K-cost runs one launch per direction and level (cost_groups); more than
-//     kMaxBatch entries go through launches of equal size (group_pairs);
-//   - one launch of k_lr_check's stack form over the n (window, level) entries with the call's own tau (enqueue_lr_stack_check).
-// The caller has made the level buffers hold 2 n fovea fields and the LR buffer lr_room(.., true).total floats.
-int enqueue_foveated_multi_checked(ugsm_ctx *ctx, Slot &s, int si, const uint8_t *d_rgbL, const uint8_t *d_rgbR, int W, int H, int stride, int n,
-                                   const int *off_x, const int *off_y, float *state, float *const *d_stack, float tau)
-{
-    const int F = ctx->cfg.fovea_levels;
-    FoveaWin win;
-    UCHK(fovea_windows(ctx, W, H, n, off_x, off_y, win));
-    win.later = true;
-    UCHK(enqueue_pyramids(ctx, s, si, d_rgbL, d_rgbR, W, H, stride, -1, &win));
-    UCHK(enqueue_level0_windows(ctx, s, si, d_rgbL, d_rgbR, stride, n, win));
-    const size_t field = fovea_field_room(win.w, win.h);
-    const Shape sh = Shape::windows_both_directions(n, field);
-    const LrRoom room = lr_room(n, F, win.w, win.h, true);
-    if (sh.nb * sh.stride > s.lvl_cap || room.total > s.lr_cap || !s.lr_host) {
-        ctx->err = "the slot's buffers do not hold the checked windows' fields";
-        return UGSM_ERR_STATE;
-    }
-    UCHK(spread_range_word(ctx, s, 2 * n));
-    float *vstate[2 * kMaxBatch], *vstack[2 * kMaxBatch];
-    for (int k = 0; k < n; k++) {
-        vstate[k] = state;
-        vstate[n + k] = s.lr + room.state;
-        vstack[k] = d_stack[k];
-        vstack[n + k] = s.lr + (size_t)k * room.per;
-    }
-    float *const cstate[2] = {state, s.lr + room.state};
-    s.have_pyr = false;
-    UCHK(enqueue_fovea_coarse(ctx, s, si, Shape::coarse_both_directions(field), cstate));
-    UCHK(enqueue_fovea_fine(ctx, s, si, sh, vstate, off_x, off_y, vstack, nullptr, nullptr));
-    return enqueue_lr_stack_check(ctx, s, si, n, F, win.w, win.h, tau, d_stack, room.per, reinterpret_cast<unsigned long long *>(s.lr + room.cnt));
-}
-
-// Has everything enqueued on the slot finished?  (Never blocks; a slot found idle stops counting as busy.)
-bool slot_idle(Slot &s)
-{
-    if (!s.busy) return true;
-    const hipError_t e = s.done_recorded ? hipEventQuery(s.ev_done) : hipStreamQuery(s.st);
-    if (e == hipErrorNotReady) return false;
-    if (e != hipSuccess) (void)hipGetLastError();  // (the slot's own ugsm_wait / ugsm_poll reports it)
-    s.busy = false;
-    return true;
-}
-// Does the call about to be enqueued on `slot` have the chip to itself?  It does when nothing is unfinished on any other slot of the
-// context and the dispatcher has not said that more calls follow (the queue, ugsm_queue.cpp: pairs wait behind this call, or a call
-// filled up by itself -- a host that submits faster than the chip matches).  The blocking entry points (ugsm_match_*: the node's service
-// call, UG_GPU_matcher.cpp:497-694, and its one-at-a-time topic path, :126-185) are therefore alone whatever ugsm_config.slots says; a
-// burst through the slot API is alone for its first call only.  What is in flight decides -- not how many slots the context was created
-// with.
-bool call_alone(ugsm_ctx *ctx, int slot)
-{
-    if (ctx->force_alone >= 0) return ctx->force_alone == 1;
-    if (ctx->hooks.queue_calling && ctx->hooks.queue_more) return false;
-    for (int i = 0; i < (int)ctx->slots.size(); i++)
-        if (i != slot && !slot_idle(ctx->slots[i])) return false;
-    return true;
-}
-
-}  // namespace
-int ugsm::get_slot(ugsm_ctx *ctx, int slot, Slot **out, bool enqueues)
+int get_slot(ugsm_ctx *ctx, int slot, Slot **out, bool enqueues)
 {
     if (!ctx) return UGSM_ERR_BAD_ARG;
     if (slot < 0 || slot >= (int)ctx->slots.size()) {
@@ -1808,7 +301,7 @@ int ugsm::get_slot(ugsm_ctx *ctx, int slot, Slot **out, bool enqueues)
 
 // End of a ugsm_submit_*: the slot's completion mark.  With several slots on one stream (ugsm_config.streams < slots) ugsm_wait waits for
 // this event, not for the pairs other slots have queued behind it on the same stream.
-int ugsm::mark_done(ugsm_ctx *ctx, Slot &s)
+int mark_done(ugsm_ctx *ctx, Slot &s)
 {
     s.forked = false;  // (the call was enqueued whole: the main stream waits for everything it put on the side stream)
     if (ctx->streams >= (int)ctx->slots.size()) return UGSM_OK;
@@ -1817,299 +310,6 @@ int ugsm::mark_done(ugsm_ctx *ctx, Slot &s)
     return UGSM_OK;
 }
 
-int ugsm::stage_in(ugsm_ctx *ctx, Slot &s, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride)
-{
-    if (!rgbL || !rgbR || W < 1 || H < 1) return UGSM_ERR_BAD_ARG;
-    if (stride < input_row_bytes(ctx, W)) return UGSM_ERR_SIZE_MISMATCH;
-    const size_t bytes = (size_t)stride * H;
-    if (bytes > s.rgb_cap) {
-        size_t c = s.rgb_cap;
-        UCHK(grow(ctx, s.rgbL, c, bytes));
-        UCHK(grow(ctx, s.rgbR, s.rgb_cap, bytes));
-    }
-    HIPCHK(ctx, hipMemcpyAsync(s.rgbL, rgbL, bytes, hipMemcpyHostToDevice, s.st));
-    // the right image goes up on the side stream, where its pyramid is built: the transfer (0.9 ms at 16 MP) then runs under the
-    // left pyramid instead of in front of it.  The side stream first waits for what the slot did before.
-    if (s.alone && s.st2 && ctx->cfg.kernel_path != 1 && ctx->cfg.profile_events == 0 && ctx->two_streams) {  // (single pairs: as side_stream_ok)
-        HIPCHK(ctx, hipEventRecord(s.ev_in, s.st));
-        s.forked = true;
-        HIPCHK(ctx, hipStreamWaitEvent(s.st2, s.ev_in, 0));
-        HIPCHK(ctx, hipMemcpyAsync(s.rgbR, rgbR, bytes, hipMemcpyHostToDevice, s.st2));
-    } else {
-        HIPCHK(ctx, hipMemcpyAsync(s.rgbR, rgbR, bytes, hipMemcpyHostToDevice, s.st));
-    }
-    return UGSM_OK;
-}
-namespace {
-
-// Result planes into caller memory.  Page-locked destinations (ugsm_host_alloc, or memory the caller registered) take the
-// device-to-host copies directly.  Pageable ones go through a page-locked staging buffer and a team of host threads: the
-// reference node allocates fresh result planes for every call (UG_GPU_matcher.cpp:414-418), and the first touch of 193 MB of
-// fresh pages by the single copy thread of a pageable hipMemcpy costs more than the whole match (30.7 ms against 16.6 ms per
-// 16 MP pair); spread over the team, and with plane k+1's transfer running under plane k's copy, it costs ~2 ms.
-bool is_pinned(const void *p)
-{
-    hipPointerAttribute_t a;
-    if (hipPointerGetAttributes(&a, p) != hipSuccess) {
-        (void)hipGetLastError();  // an ordinary malloc'd pointer is "invalid value" to the runtime: clear the sticky error
-        return false;
-    }
-    return a.type == hipMemoryTypeHost;
-}
-
-// The context's host team (UGSM_COPY_THREADS members, default min(8, hardware threads); 1 = the calling thread only).  Never throws.
-HostTeam *host_team(ugsm_ctx *ctx)
-{
-    if (!ctx->team) {
-        const char *e = getenv("UGSM_COPY_THREADS");
-        unsigned n = e ? (unsigned)atoi(e) : std::min(8u, std::max(1u, std::thread::hardware_concurrency()));
-        n = std::min(std::max(1u, n), 64u);
-        try {
-            ctx->team.reset(new HostTeam(n));
-        } catch (...) {  // (allocation failure of the team object itself)
-            return nullptr;
-        }
-    }
-    return ctx->team.get();
-}
-
-constexpr size_t kTeamMinBytes = 1u << 22;  // below 4 MB a single memcpy / page walk is faster than waking the team
-
-void team_copy(ugsm_ctx *ctx, void *dst, const void *src, size_t bytes)
-{
-    HostTeam *team = bytes >= kTeamMinBytes ? host_team(ctx) : nullptr;
-    if (!team || team->size() == 1) {
-        memcpy(dst, src, bytes);
-        return;
-    }
-    team->run([=](unsigned t, unsigned n) {
-        const size_t chunk = ((bytes / n) + 4095) & ~(size_t)4095;
-        const size_t off = (size_t)t * chunk;
-        if (off < bytes) memcpy((char *)dst + off, (const char *)src + off, std::min(chunk, bytes - off));
-    });
-}
-
-// First touch of the caller's (possibly fresh) result pages by the host team WHILE the GPU is still matching: every page of
-// dst[0..2] gets one byte written (the planes are overwritten in full afterwards), so the page faults are off the critical path.
-void prefault_planes(ugsm_ctx *ctx, float *const dst[3], size_t plane_floats)
-{
-    const size_t pb = plane_floats * sizeof(float);
-    if (pb < kTeamMinBytes) return;  // (a small call: the copy itself touches the pages)
-    if (is_pinned(dst[0]) && is_pinned(dst[1]) && is_pinned(dst[2])) return;
-    auto touch = [=](unsigned t, unsigned n) {
-        for (int k = 0; k < 3; k++) {
-            volatile char *p = (volatile char *)dst[k];
-            const size_t lo = pb * t / n, hi = pb * (t + 1) / n;
-            for (size_t o = (lo + 4095) & ~(size_t)4095; o < hi; o += 4096) p[o] = 0;
-            if (t == 0 && pb) p[0] = 0;
-        }
-    };
-    HostTeam *team = host_team(ctx);
-    if (team) team->run(touch);
-    else touch(0, 1);
-}
-
-int copy_out_planes(ugsm_ctx *ctx, Slot &s, const float *d_src, size_t plane_floats, float *const dst[3])
-{
-    const size_t pb = plane_floats * sizeof(float);
-    if (is_pinned(dst[0]) && is_pinned(dst[1]) && is_pinned(dst[2])) {
-        for (int k = 0; k < 3; k++) HIPCHK(ctx, hipMemcpyAsync(dst[k], d_src + k * plane_floats, pb, hipMemcpyDeviceToHost, s.st));
-        return UGSM_OK;
-    }
-    if (3 * plane_floats > s.hpin_cap) {
-        if (s.hpin) HIPCHK(ctx, hipHostFree(s.hpin));
-        s.hpin = nullptr;
-        s.hpin_cap = 0;
-        HIPCHK(ctx, hipHostMalloc((void **)&s.hpin, 3 * pb, hipHostMallocDefault));
-        s.hpin_cap = 3 * plane_floats;
-    }
-    // Every plane in PIECES: a piece's copy into the caller's pages runs under the next piece's transfer, so what is left exposed behind
-    // the last transfer is one piece's copy, not one plane's (a quarter plane at 16 MP: 0.25 ms instead of 1 ms).
-    const int pieces = pb >= 4 * kTeamMinBytes ? 4 : 1;
-    const size_t pf = ((plane_floats + pieces - 1) / pieces + 1023) & ~(size_t)1023;  // floats per piece (4 KiB multiples)
-    auto piece = [&](int i, size_t &off, size_t &len) {
-        const int k = i / pieces, c = i - k * pieces;
-        const size_t lo = std::min((size_t)c * pf, plane_floats), hi = std::min(lo + pf, plane_floats);
-        off = (size_t)k * plane_floats + lo;
-        len = hi - lo;
-        return k;
-    };
-    for (int i = 0; i < 3 * pieces; i++) {
-        size_t off, len;
-        piece(i, off, len);
-        if (!s.out_ev[i]) HIPCHK(ctx, hipEventCreateWithFlags(&s.out_ev[i], hipEventDisableTiming));
-        if (len) HIPCHK(ctx, hipMemcpyAsync(s.hpin + off, d_src + off, len * sizeof(float), hipMemcpyDeviceToHost, s.st));
-        HIPCHK(ctx, hipEventRecord(s.out_ev[i], s.st));
-    }
-    for (int i = 0; i < 3 * pieces; i++) {
-        size_t off, len;
-        const int k = piece(i, off, len);
-        HIPCHK(ctx, hipEventSynchronize(s.out_ev[i]));
-        if (len) team_copy(ctx, (char *)dst[k] + (off - (size_t)k * plane_floats) * sizeof(float), s.hpin + off, len * sizeof(float));
-    }
-    return UGSM_OK;
-}
-
-// The counterpart of copy_out_planes for what a call reads besides its images (a prior, a state, a prior stack): three host planes of any kind
-// up into d_dst, on the slot's stream.
-int upload_planes(ugsm_ctx *ctx, Slot &s, float *d_dst, size_t plane_floats, const float *const src[3])
-{
-    for (int c = 0; c < 3; c++) HIPCHK(ctx, hipMemcpyAsync(d_dst + c * plane_floats, src[c], plane_floats * sizeof(float), hipMemcpyHostToDevice, s.st));
-    return UGSM_OK;
-}
-
-// a device stack's H, V and C planes (stackn floats each) down into three host buffers, on the slot's stream
-int download_stack(ugsm_ctx *ctx, Slot &s, const float *d_stack, size_t stackn, float *stackH, float *stackV, float *stackC)
-{
-    float *const dst[3] = {stackH, stackV, stackC};
-    for (int c = 0; c < 3; c++) HIPCHK(ctx, hipMemcpyAsync(dst[c], d_stack + c * stackn, stackn * sizeof(float), hipMemcpyDeviceToHost, s.st));
-    return UGSM_OK;
-}
-
-// what the non-blocking host-memory calls answer to a buffer that is not page-locked
-int not_pinned(ugsm_ctx *ctx, const char *entry)
-{
-    ctx->err = std::string(entry) + ": every host buffer must be page-locked (ugsm_host_alloc, hipHostMalloc or hipHostRegister)";
-    return UGSM_ERR_BAD_ARG;
-}
-
-// A blocking entry point that failed part-way: whatever it did enqueue -- uploads that read the caller's images, on the slot's stream or on
-// the side stream -- has drained before the caller hears of the failure.  "When the call returns the buffers are the caller's again"
-// holds for a failed call too (the reference exit()s instead, MatchGPULib.cpp passim).
-int drained(ugsm_ctx *ctx, int slot, int st)
-{
-    if (st == UGSM_OK || !ctx || slot < 0 || slot >= (int)ctx->slots.size()) return st;
-    const std::string why = ctx->err;
-    (void)ugsm_wait(ctx, slot);
-    ctx->err = why;
-    return st;
-}
-
-// The frame of every call that takes one pair's images from host memory, on a slot.  `sync`: the reference's call -- it returns when the results
-// are in place, in pageable or page-locked memory, and a failure part-way is drained --; otherwise everything is only enqueued and every buffer
-// must be page-locked.  The slot, the device, then what the call brings:
-//   check(slot, hout): the call's own refusals, in the call's own order, and `hout`, the floats of the slot's result staging it needs; a call
-//       that must hear UGSM_ERR_NOMEM before anything is enqueued grows its buffers, the staging included, here;
-//   the images go up into slot.rgbL / rgbR (stage_in), the result staging grows;
-//   match(slot): the uploads of what the call reads besides the images, and the match, into the staging it carves itself;
-//   down(slot): the results into the caller's memory;
-// and the wait, or the completion mark.
-template <class Check, class Match, class Down>
-int host_call(ugsm_ctx *ctx, int slot, bool sync, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, Check &&check, Match &&match,
-              Down &&down)
-{
-    auto enqueue = [&]() -> int {
-        Slot *s;
-        UCHK(get_slot(ctx, slot, &s));
-        HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
-        size_t hout = 0;
-        UCHK(check(*s, hout));
-        UCHK(stage_in(ctx, *s, rgbL, rgbR, W, H, stride));
-        UCHK(grow(ctx, s->hout, s->hout_cap, hout));
-        UCHK(match(*s));
-        UCHK(down(*s));
-        if (!sync) return mark_done(ctx, *s);
-        s->forked = false;  // (enqueued whole, as mark_done)
-        return ugsm_wait(ctx, slot);
-    };
-    return sync ? drained(ctx, slot, enqueue()) : enqueue();
-}
-// ... of a blocking call on slot 0 whose entry point has made every refusal (ugsm_seeded.cpp, ugsm_coarse.cpp, ugsm_fovea_seeded.cpp)
-template <class Match, class Down>
-int host_call(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, size_t hout_floats, Match &&match, Down &&down)
-{
-    auto size = [&](Slot &, size_t &hout) -> int {
-        hout = hout_floats;
-        return UGSM_OK;
-    };
-    return host_call(ctx, 0, true, rgbL, rgbR, W, H, stride, size, match, down);
-}
-
-// a full field's room in the result staging where something lies behind it: a multiple of 64 floats
-size_t field_room(size_t px) { return (3 * px + 63) & ~(size_t)63; }
-
-}  // namespace
-
-namespace ugsm {
-// The seeded service call (ugsm_match_full_seeded) on slot 0: images and prior up -- the prior's planes into the slot's result staging, where
-// the call then writes in place: the restriction reads before level 0 writes --, the match, the planes into caller memory of any kind.
-int seeded_match(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, const float *const prior[3], int start_level,
-                 float *const disp[3])
-{
-    const size_t n = (size_t)W * H;
-    auto match = [&](Slot &s) -> int {
-        UCHK(upload_planes(ctx, s, s.hout, n, prior));
-        const LevelRange r = LevelRange::seeded(start_level, &s.hout);
-        return enqueue_match_full(ctx, s, 0, 1, &s.rgbL, &s.rgbR, W, H, stride, &s.hout, &r);
-    };
-    return host_call(ctx, rgbL, rgbR, W, H, stride, 3 * n, match, [&](Slot &s) -> int {
-        prefault_planes(ctx, disp, n);
-        return copy_out_planes(ctx, s, s.hout, n, disp);
-    });
-}
-
-// The two halves as service calls (ugsm_match_full_coarse, ugsm_match_full_fine) on slot 0.  The slot's result staging holds the
-// full-resolution field (the prolongation, or the fine half's result) and, behind it, the state of level e (whose size the entry point has had).
-int coarse_match(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, int e, float *const state[3], float *const full[3])
-{
-    int w[UGSM_MAX_LEVELS], h[UGSM_MAX_LEVELS];
-    UCHK(level_dims(W, H, ctx->cfg.levels, w, h));  // (holds: the entry point has had level e's size from it)
-    const size_t n = (size_t)W * H, ne = (size_t)w[e] * h[e], room = full ? field_room(n) : 0;
-    auto match = [&](Slot &s) -> int {
-        float *const d_state = s.hout + room, *const d_full = full ? s.hout : nullptr;
-        const LevelRange r = LevelRange::coarse(ctx->cfg.levels, e, &d_full);
-        return enqueue_match_full(ctx, s, 0, 1, &s.rgbL, &s.rgbR, W, H, stride, &d_state, &r);
-    };
-    return host_call(ctx, rgbL, rgbR, W, H, stride, room + 3 * ne, match, [&](Slot &s) -> int {
-        if (full) prefault_planes(ctx, full, n);
-        UCHK(copy_out_planes(ctx, s, s.hout + room, ne, state));
-        return full ? copy_out_planes(ctx, s, s.hout, n, full) : UGSM_OK;
-    });
-}
-int fine_match(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, const float *const state[3], int e, float *const disp[3])
-{
-    int w[UGSM_MAX_LEVELS], h[UGSM_MAX_LEVELS];
-    UCHK(level_dims(W, H, ctx->cfg.levels, w, h));
-    const size_t n = (size_t)W * H, ne = (size_t)w[e] * h[e], room = field_room(n);
-    auto match = [&](Slot &s) -> int {
-        UCHK(upload_planes(ctx, s, s.hout + room, ne, state));
-        const float *const d_state = s.hout + room;
-        const LevelRange r = LevelRange::fine(e, &d_state);
-        return enqueue_match_full(ctx, s, 0, 1, &s.rgbL, &s.rgbR, W, H, stride, &s.hout, &r);
-    };
-    return host_call(ctx, rgbL, rgbR, W, H, stride, room + 3 * ne, match, [&](Slot &s) -> int {
-        prefault_planes(ctx, disp, n);
-        return copy_out_planes(ctx, s, s.hout, n, disp);
-    });
-}
-
-// The warm foveated service call (ugsm_match_foveated_warm) on slot 0: images and the prior stack's three planes up, the match into a second
-// stack beside it in the slot's result staging (the call is not in place: [prior 3 stackn][stack 3 stackn]), that stack's planes down.
-int fovea_warm_match(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, int off_x, int off_y, const float *const prior[3],
-                     int prior_off_x, int prior_off_y, int start_level, float *const stack[3])
-{
-    int fw, fh;
-    UCHK(ugsm_fovea_dims(W, H, ctx->cfg.levels, ctx->cfg.fovea_levels, &fw, &fh));
-    const size_t stackn = (size_t)ctx->cfg.fovea_levels * fw * fh;
-    auto match = [&](Slot &s) -> int {
-        UCHK(upload_planes(ctx, s, s.hout, stackn, prior));
-        const float *const d_prior = s.hout;
-        float *const d_stack = s.hout + 3 * stackn;
-        return enqueue_match_foveated_warm(ctx, s, 0, 1, &s.rgbL, &s.rgbR, W, H, stride, &off_x, &off_y, &d_prior, &prior_off_x, &prior_off_y, false,
-                                           start_level, &d_stack);
-    };
-    return host_call(ctx, rgbL, rgbR, W, H, stride, 6 * stackn, match,
-                     [&](Slot &s) -> int { return download_stack(ctx, s, s.hout + 3 * stackn, stackn, stack[0], stack[1], stack[2]); });
-}
-
-void ctx_host_copy(ugsm_ctx *ctx, void *dst, const void *src, size_t bytes) { team_copy(ctx, dst, src, bytes); }
-bool host_pinned(const void *p) { return is_pinned(p); }
-bool dev_env() { return dev_env_on(); }
-// Contexts whose options need a host round trip per iteration, a second match, or the one-kernel-per-stage path run their batches pair by pair.
-bool batch_runs_pair_by_pair(const ugsm_ctx *ctx) { return ctx->cfg.kernel_path == 1 || ctx->cfg.early_exit_threshold > 0.0f || lr_full_on(ctx); }
-// ... and the foveated batches: the foveated check runs in lockstep (enqueue_match_foveated; ugsm_set_lr_check refuses it to the contexts of the
-// first two kinds).  A context with the full-mode check alone sends its foveated batches through pair by pair as it always has.
-bool fovea_batch_runs_pair_by_pair(const ugsm_ctx *ctx) { return batch_runs_pair_by_pair(ctx) && !lr_fovea_on(ctx); }
 }  // namespace ugsm
 
 // =========================================================================================
@@ -2176,19 +376,6 @@ const char *ugsm_status_string(int st)
     }
 }
 
-// The configurations a context can have, asked after the development overrides (apply_dev_env) by ugsm_create and ugsm_plan_level alike:
-// no plan is reported for a configuration that no context can be created with.
-static int check_config(const ugsm_config &cfg)
-{
-    if (cfg.levels < 1 || cfg.levels > UGSM_MAX_LEVELS || cfg.slots < 1 || cfg.slots > 64 || cfg.kernel_path < 0 ||
-        cfg.kernel_path > 1 || cfg.fovea_levels < 0 || cfg.fovea_levels > cfg.levels || !(cfg.lr_check_threshold >= 0.0f) || cfg.streams < 0 ||
-        cfg.batch < 0 || cfg.batch > UGSM_MAX_BATCH || cfg.stream_priority < 0 || cfg.stream_priority > 3)
-        return UGSM_ERR_BAD_ARG;
-    if (cfg.kernel_path == 1 && !kDevLib) return UGSM_ERR_BAD_ARG;       // the one-kernel-per-stage path lives in libugsm_dev.so
-    if (cfg.march_min_pixels < 0 && !kDevLib) return UGSM_ERR_BAD_ARG;  // ... and so does round 1's LDS-tiled K-cost
-    return UGSM_OK;
-}
-
 int ugsm_create(const ugsm_config *cfg_in, ugsm_ctx **out)
 {
     if (!out) return UGSM_ERR_BAD_ARG;
@@ -2222,7 +409,7 @@ int ugsm_create(const ugsm_config *cfg_in, ugsm_ctx **out)
     ctx->hooks.cloud_submit = queue_cloud_submit;  // (the queue's way to the cloud work: ugsm_internal.hpp)
     ctx->hooks.cloud_finish = queue_cloud_finish;
     set_policy(ctx, knobs);
-    if (dev_env_on() && getenv("UGSM_MEM_LIMIT_MB")) ctx->mem_limit = atoll(getenv("UGSM_MEM_LIMIT_MB")) << 20;
+    if (dev_env() && getenv("UGSM_MEM_LIMIT_MB")) ctx->mem_limit = atoll(getenv("UGSM_MEM_LIMIT_MB")) << 20;
     // The side stream pays when a pair is alone on the chip (115.6 against 113.9 pairs/s at 16 MP: the right pyramid and the A planes run
     // beside the left pyramid and the coarse levels; profiles/r06_ab_alone.txt).  With four pairs in flight USING theirs it loses 13 % (136
     // against 157 pairs/s): eight streams on the four hardware queues serialise kernels that one stream per pair lets overlap.  So every
@@ -2358,43 +545,6 @@ int ugsm_level_dims(int W, int H, int levels, int *w, int *h)
 int ugsm_level_iterations(int level) { return level < 0 ? 0 : level_iterations(level); }
 int ugsm_level_smooth_passes(int level) { return level < 0 ? 0 : level_smooth(level); }
 
-int ugsm_plan_level(const ugsm_config *cfg_in, int alone, int W, int H, ugsm_level_plan *out)
-{
-    if (!out || W < 1 || H < 1) return UGSM_ERR_BAD_ARG;
-    ugsm_ctx probe;  // host-only: the same policy functions the launch path calls, on a context that owns no device state
-    if (cfg_in) probe.cfg = *cfg_in;
-    else ugsm_default_config(&probe.cfg);
-    {   // ... under the same development overrides ugsm_create would apply in this process (none unless UGSM_DEV=1)
-        DevKnobs knobs;
-        apply_dev_env(probe.cfg, knobs, false);
-        set_policy(&probe, knobs);
-    }
-    UCHK(check_config(probe.cfg));  // (what ugsm_create refuses has no plan)
-    memset(out, 0, sizeof *out);
-    if (probe.cfg.kernel_path == 1) {
-        out->cost_kernel = out->smooth_kernel = 3;
-        out->pairs_per_launch = 1;
-        return UGSM_OK;
-    }
-    // a context created for batches (ugsm_config.batch) is asked about a call of that many pairs: a level of at most kBatchMaxPixels is one
-    // launch for all of them, and the thresholds are compared with what the launch holds
-    const int nb = std::min(std::max(probe.cfg.batch, 1), kMaxBatch);
-    const bool al = probe.force_alone >= 0 ? probe.force_alone == 1 : alone != 0;
-    out->alone = al ? 1 : 0;
-    const int pairs = (nb > 1 && batch_level(&probe, W, H)) ? nb : 1;
-    const bool march4 = use_march4(&probe, W, H, al, pairs);  // (asked first, as in run_level)
-    const bool march = use_march(&probe, W, H, al, pairs);
-    const int rh = small_rh(&probe, W, H, al, pairs);
-    out->cost_kernel = march4 ? 4 : (march ? 1 : (use_small_cost(&probe, W, H, al, pairs) ? 2 : 0));
-    out->smooth_kernel = (rh && (probe.small_mask & 2)) ? 2 : 0;
-    out->smooth_rh = (probe.small_mask & 2) ? rh : 0;
-    out->strip_rows = march4 ? march4_strip_rows(W, H, pairs)
-                             : (march ? (probe.cfg.march_rows > 0 ? probe.cfg.march_rows : march_strip_rows(W, H, probe.march_mode <= -2, pairs)) : 0);
-    out->seed_fused = fuse_seed(&probe, W, H, al, pairs) ? 1 : 0;
-    out->smooth_tile_rows = out->smooth_kernel == 0 ? smooth_rows_for(&probe, W, H, al, pairs) : 0;
-    out->pairs_per_launch = pairs;
-    return UGSM_OK;
-}
 int ugsm_threshold_schedule(int mi, float *out)
 {
     if (mi < 1 || !out) return UGSM_ERR_BAD_ARG;
@@ -2420,223 +570,6 @@ long long ugsm_pixel_iterations(int W, int H, int levels, int F)
         tot += px * level_iterations(i);
     }
     return tot;
-}
-
-int ugsm_submit_pyramids(ugsm_ctx *ctx, int slot, const uint8_t *d_rgbL, const uint8_t *d_rgbR, int W, int H, int stride)
-{
-    Slot *s;
-    UCHK(get_slot(ctx, slot, &s));
-    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
-    // (no A planes here: the ranks of a fovea shard that only run the fine phase never use them; a coarse phase that follows computes
-    // them on the side stream itself -- ADVICE r03)
-    UCHK(enqueue_pyramids(ctx, *s, slot, d_rgbL, d_rgbR, W, H, stride, -1));
-    return mark_done(ctx, *s);
-}
-
-int ugsm_submit_full(ugsm_ctx *ctx, int slot, const uint8_t *d_rgbL, const uint8_t *d_rgbR, int W, int H, int stride, float *d_out)
-{
-    Slot *s;
-    UCHK(get_slot(ctx, slot, &s));
-    if (!d_out) return UGSM_ERR_BAD_ARG;
-    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
-    UCHK(enqueue_match_full(ctx, *s, slot, 1, &d_rgbL, &d_rgbR, W, H, stride, &d_out));
-    return mark_done(ctx, *s);
-}
-
-int ugsm_submit_fovea_coarse(ugsm_ctx *ctx, int slot, float *d_state)
-{
-    Slot *s;
-    UCHK(get_slot(ctx, slot, &s));
-    if (!d_state) return UGSM_ERR_BAD_ARG;
-    if (!s->have_pyr) return UGSM_ERR_STATE;
-    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
-    if (s->a_from < 0 && side_stream_ok(ctx, *s) && ctx->cfg.fovea_levels >= 2) UCHK(enqueue_side_A(ctx, *s, ctx->cfg.fovea_levels - 1));
-    UCHK(enqueue_fovea_coarse(ctx, *s, slot, d_state));
-    return mark_done(ctx, *s);
-}
-
-int ugsm_submit_fovea_fine(ugsm_ctx *ctx, int slot, const float *d_state, int off_x, int off_y, float *d_stack)
-{
-    Slot *s;
-    UCHK(get_slot(ctx, slot, &s));
-    if (!d_state || !d_stack) return UGSM_ERR_BAD_ARG;
-    if (!s->have_pyr) return UGSM_ERR_STATE;
-    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
-    UCHK(enqueue_fovea_fine(ctx, *s, slot, d_state, off_x, off_y, d_stack, nullptr, nullptr));
-    return mark_done(ctx, *s);
-}
-
-int ugsm_submit_foveated(ugsm_ctx *ctx, int slot, const uint8_t *d_rgbL, const uint8_t *d_rgbR, int W, int H, int stride,
-                         int off_x, int off_y, float *d_stack, float *d_pyrL, float *d_pyrR)
-{
-    Slot *s;
-    UCHK(get_slot(ctx, slot, &s));
-    if (!d_stack) return UGSM_ERR_BAD_ARG;
-    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
-    const int F = ctx->cfg.fovea_levels;
-    if (F < 2) return UGSM_ERR_BAD_ARG;
-    // level F-1's state is parked in the (otherwise idle) A buffer's tail? No: use a dedicated spot
-    // at the end of d_stack's level F-1 block is not 3-plane contiguous, so stage through hout.
-    int fw, fh;
-    UCHK(ugsm_fovea_dims(W, H, ctx->cfg.levels, F, &fw, &fh));
-    const size_t fn3 = 3 * (size_t)fw * fh;
-    UCHK(grow(ctx, s->hout, s->hout_cap, std::max(fn3, s->hout_cap)));
-    UCHK(enqueue_match_foveated(ctx, *s, slot, 1, &d_rgbL, &d_rgbR, W, H, stride, &off_x, &off_y, &s->hout, &d_stack, d_pyrL ? &d_pyrL : nullptr,
-                          d_pyrR ? &d_pyrR : nullptr));
-    return mark_done(ctx, *s);
-}
-
-// ---- B pairs per call ---------------------------------------------------------------------------------------------------------
-int ugsm_submit_full_batch(ugsm_ctx *ctx, int slot, int n, const uint8_t *const *d_rgbL, const uint8_t *const *d_rgbR, int W, int H, int stride,
-                           float *const *d_out)
-{
-    Slot *s;
-    UCHK(get_slot(ctx, slot, &s));
-    if (n < 1 || n > UGSM_MAX_BATCH || !d_rgbL || !d_rgbR || !d_out) return UGSM_ERR_BAD_ARG;
-    for (int b = 0; b < n; b++)
-        if (!d_rgbL[b] || !d_rgbR[b] || !d_out[b]) return UGSM_ERR_BAD_ARG;
-    const int per = batch_runs_pair_by_pair(ctx) ? 1 : n;  // pairs per match: one by one, or all in lockstep
-    return submit_pairs(ctx, *s, n, per, [&](Slot &sl, int b, int k) { return enqueue_match_full(ctx, sl, slot, k, d_rgbL + b, d_rgbR + b, W, H, stride, d_out + b); });
-}
-
-int ugsm_submit_foveated_batch(ugsm_ctx *ctx, int slot, int n, const uint8_t *const *d_rgbL, const uint8_t *const *d_rgbR, int W, int H, int stride,
-                               const int *off_x, const int *off_y, float *const *d_stack, float *const *d_pyrL, float *const *d_pyrR)
-{
-    Slot *s;
-    UCHK(get_slot(ctx, slot, &s));
-    if (n < 1 || n > UGSM_MAX_BATCH || !d_rgbL || !d_rgbR || !d_stack) return UGSM_ERR_BAD_ARG;
-    for (int b = 0; b < n; b++)
-        if (!d_rgbL[b] || !d_rgbR[b] || !d_stack[b]) return UGSM_ERR_BAD_ARG;
-    const int F = ctx->cfg.fovea_levels;
-    if (F < 2) return UGSM_ERR_BAD_ARG;
-    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
-    int zeros[UGSM_MAX_BATCH] = {0};
-    const int *ox = off_x ? off_x : zeros, *oy = off_y ? off_y : zeros;
-    int fw, fh;
-    UCHK(ugsm_fovea_dims(W, H, ctx->cfg.levels, F, &fw, &fh));
-    const size_t fn3 = fovea_field_room(fw, fh);  // level F-1's state of every pair, staged in the slot's hout
-    UCHK(grow(ctx, s->hout, s->hout_cap, std::max(fn3 * n, s->hout_cap)));
-    if (n == 1 || fovea_batch_runs_pair_by_pair(ctx)) {
-        for (int b = 0; b < n; b++)
-            UCHK(enqueue_match_foveated(ctx, *s, slot, 1, d_rgbL + b, d_rgbR + b, W, H, stride, ox + b, oy + b, &s->hout, d_stack + b,
-                                  (d_pyrL && d_pyrL[b]) ? d_pyrL + b : nullptr, (d_pyrR && d_pyrR[b]) ? d_pyrR + b : nullptr));
-        return mark_done(ctx, *s);
-    }
-    float *state[UGSM_MAX_BATCH];
-    for (int b = 0; b < n; b++) state[b] = s->hout + b * fn3;
-    UCHK(enqueue_match_foveated(ctx, *s, slot, n, d_rgbL, d_rgbR, W, H, stride, ox, oy, state, d_stack, d_pyrL, d_pyrR));
-    return mark_done(ctx, *s);
-}
-
-// ---- both directions of n full-mode pairs -------------------------------------------------------------------------------------
-// What ugsm_submit_full_checked and ugsm_match_full_checked refuse before anything is enqueued, beyond their null pointers.  The threshold is
-// the call's own: the context's setting (ugsm_set_lr_check) is neither read nor changed.
-static int full_checked_check(ugsm_ctx *ctx, int n, int W, int H, int stride, float tau)
-{
-    if (n < 1 || n > UGSM_MAX_BATCH) return ctx_fail(ctx, UGSM_ERR_BAD_ARG, "the checked full-mode call takes 1 .. UGSM_MAX_BATCH pairs");
-    if (!(tau > 0.0f)) return ctx_fail(ctx, UGSM_ERR_BAD_ARG, "the checked full-mode call needs tau > 0");
-    // (ugsm_set_lr_check's rule: these contexts run every level pair by pair and have no batch dimension to carry the second direction in)
-    if (ctx->cfg.early_exit_threshold > 0.0f || ctx->cfg.kernel_path == 1)
-        return ctx_fail(ctx, UGSM_ERR_BAD_ARG, "the checked full-mode call: not with early_exit_threshold > 0 or kernel_path 1");
-    int w[UGSM_MAX_LEVELS], h[UGSM_MAX_LEVELS];
-    UCHK(level_dims(W, H, ctx->cfg.levels, w, h));
-    if (stride < input_row_bytes(ctx, W)) return UGSM_ERR_SIZE_MISMATCH;
-    return UGSM_OK;
-}
-// ... and its buffers: A, d0 and d1 for 2 n full fields, the LR buffer for the `kept` right-to-left fields the caller does not take and the
-// count words.  A buffer that cannot grow answers UGSM_ERR_NOMEM here, before anything is enqueued (ensure_level_bufs: all or nothing).
-static int full_checked_bufs(ugsm_ctx *ctx, Slot &s, int n, int kept, int W, int H)
-{
-    const size_t field = (3 * (size_t)W * H + 63) & ~(size_t)63;  // (Slot::lvl_stride, as prepare_slot sets it for this size)
-    UCHK(ensure_level_bufs(ctx, s, 2 * (size_t)n * field));
-    UCHK(grow(ctx, s.lr, s.lr_cap, lr_full_room(field, kept, n)));
-    return lr_host_ready(ctx, s);
-}
-
-int ugsm_submit_full_checked(ugsm_ctx *ctx, int slot, int n, const uint8_t *const *d_rgbL, const uint8_t *const *d_rgbR, int W, int H, int stride,
-                             float *const *d_out, float *const *d_back, float tau)
-{
-    Slot *s;
-    UCHK(get_slot(ctx, slot, &s));
-    if (!d_rgbL || !d_rgbR || !d_out) return UGSM_ERR_BAD_ARG;
-    UCHK(full_checked_check(ctx, n, W, H, stride, tau));
-    int kept = 0;
-    for (int b = 0; b < n; b++) {
-        if (!d_rgbL[b] || !d_rgbR[b] || !d_out[b]) return UGSM_ERR_BAD_ARG;
-        kept += !(d_back && d_back[b]);
-    }
-    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
-    UCHK(full_checked_bufs(ctx, *s, n, kept, W, H));
-    UCHK(enqueue_full_checked(ctx, *s, slot, n, d_rgbL, d_rgbR, W, H, stride, d_out, d_back, tau));
-    return mark_done(ctx, *s);
-}
-
-// ---- n windows on one pair ----------------------------------------------------------------------------------------------------
-// What ugsm_submit_foveated_multi and ugsm_match_foveated_multi refuse before anything is enqueued; the windows' field size on success.
-// tau: null = the plain call; else the checked call's threshold (ugsm_submit_foveated_multi_checked), which has refusals of its own and does
-// not look at the context's setting.
-static int multi_check(ugsm_ctx *ctx, int n, int W, int H, int stride, const int *&off_x, const int *&off_y, const int *zeros, int *fw, int *fh,
-                       const float *tau = nullptr)
-{
-    const int F = ctx->cfg.fovea_levels;
-    if (n < 1 || n > UGSM_MAX_BATCH || F < 2) return UGSM_ERR_BAD_ARG;
-    if (!off_x) off_x = zeros;
-    if (!off_y) off_y = zeros;
-    if (tau && !(*tau > 0.0f)) return ctx_fail(ctx, UGSM_ERR_BAD_ARG, "the checked multi-window call needs tau > 0");
-    // (ugsm_set_lr_check's rule: these contexts run every level pair by pair and have no batch dimension to carry the second direction in)
-    if (tau && (ctx->cfg.early_exit_threshold > 0.0f || ctx->cfg.kernel_path == 1))
-        return ctx_fail(ctx, UGSM_ERR_BAD_ARG, "the checked multi-window call: not with early_exit_threshold > 0 or kernel_path 1");
-    if (!tau && lr_fovea_on(ctx)) return ctx_fail(ctx, UGSM_ERR_STATE, "the foveated LR check is on: the checked multi-window call is ugsm_submit_foveated_multi_checked (ugsm_set_lr_check)");
-    UCHK(ugsm_fovea_dims(W, H, ctx->cfg.levels, F, fw, fh));
-    if (stride < input_row_bytes(ctx, W)) return UGSM_ERR_SIZE_MISMATCH;
-    return UGSM_OK;
-}
-// the level buffers for n fields of fw x fh in lockstep (contexts that run window by window need one pair's alone)
-static int multi_level_bufs(ugsm_ctx *ctx, Slot &s, int n, int W, int H, int fw, int fh)
-{
-    if (n == 1 || ctx->cfg.kernel_path == 1 || ctx->cfg.early_exit_threshold > 0.0f) return UGSM_OK;
-    return ensure_level_bufs(ctx, s, std::max((size_t)n * fovea_field_room(fw, fh), 3 * (size_t)W * H));
-}
-
-// ... and of the checked call: 2 n fields in the level buffers, the right-to-left stacks, state and count words in the LR buffer
-static int multi_checked_bufs(ugsm_ctx *ctx, Slot &s, int n, int W, int H, int fw, int fh)
-{
-    UCHK(ensure_level_bufs(ctx, s, std::max(2 * (size_t)n * fovea_field_room(fw, fh), 3 * (size_t)W * H)));
-    UCHK(grow(ctx, s.lr, s.lr_cap, lr_room(n, ctx->cfg.fovea_levels, fw, fh, true).total));
-    return lr_host_ready(ctx, s);
-}
-
-// (tau: null = the plain call, else the checked one's threshold)
-static int submit_foveated_multi(ugsm_ctx *ctx, int slot, const uint8_t *d_rgbL, const uint8_t *d_rgbR, int W, int H, int stride, int n, const int *off_x,
-                                 const int *off_y, float *const *d_stack, const float *tau)
-{
-    Slot *s;
-    UCHK(get_slot(ctx, slot, &s));
-    if (!d_rgbL || !d_rgbR || !d_stack) return UGSM_ERR_BAD_ARG;
-    for (int k = 0; k < n && k < UGSM_MAX_BATCH; k++)
-        if (!d_stack[k]) return UGSM_ERR_BAD_ARG;
-    const int zeros[UGSM_MAX_BATCH] = {0};
-    int fw, fh;
-    UCHK(multi_check(ctx, n, W, H, stride, off_x, off_y, zeros, &fw, &fh, tau));
-    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
-    UCHK(tau ? multi_checked_bufs(ctx, *s, n, W, H, fw, fh) : multi_level_bufs(ctx, *s, n, W, H, fw, fh));
-    const size_t fn3 = 3 * (size_t)fw * fh;  // the (left-to-right) level-F-1 state, staged in the slot's hout as ugsm_submit_foveated stages it
-    UCHK(grow(ctx, s->hout, s->hout_cap, std::max(fn3, s->hout_cap)));
-    if (tau) UCHK(enqueue_foveated_multi_checked(ctx, *s, slot, d_rgbL, d_rgbR, W, H, stride, n, off_x, off_y, s->hout, d_stack, *tau));
-    else UCHK(enqueue_foveated_multi(ctx, *s, slot, d_rgbL, d_rgbR, W, H, stride, n, off_x, off_y, s->hout, d_stack));
-    return mark_done(ctx, *s);
-}
-
-int ugsm_submit_foveated_multi_checked(ugsm_ctx *ctx, int slot, const uint8_t *d_rgbL, const uint8_t *d_rgbR, int W, int H, int stride, int n,
-                                       const int *off_x, const int *off_y, float *const *d_stack, float tau)
-{
-    return submit_foveated_multi(ctx, slot, d_rgbL, d_rgbR, W, H, stride, n, off_x, off_y, d_stack, &tau);
-}
-
-int ugsm_submit_foveated_multi(ugsm_ctx *ctx, int slot, const uint8_t *d_rgbL, const uint8_t *d_rgbR, int W, int H, int stride, int n,
-                               const int *off_x, const int *off_y, float *const *d_stack)
-{
-    return submit_foveated_multi(ctx, slot, d_rgbL, d_rgbR, W, H, stride, n, off_x, off_y, d_stack, nullptr);
 }
 
 int ugsm_wait(ugsm_ctx *ctx, int slot)
@@ -2689,532 +622,6 @@ int ugsm_wait_all(ugsm_ctx *ctx)
     }
     if (first != UGSM_OK) ctx->err = why;
     return first;
-}
-
-// The service call on a slot: upload, pyramids, match, results into caller memory (host_call: `sync` = the reference's call).
-static int match_full_host(ugsm_ctx *ctx, int slot, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, float *dispH, float *dispV,
-                           float *dispC, bool sync)
-{
-    float *const dst[3] = {dispH, dispV, dispC};
-    const size_t n = (size_t)W * H;
-    auto check = [&](Slot &, size_t &hout) -> int {
-        if (!dispH || !dispV || !dispC) return UGSM_ERR_BAD_ARG;
-        if (!sync && !(is_pinned(rgbL) && is_pinned(rgbR) && is_pinned(dispH) && is_pinned(dispV) && is_pinned(dispC))) return not_pinned(ctx, "ugsm_submit_full_host");
-        hout = 3 * n;
-        return UGSM_OK;
-    };
-    auto match = [&](Slot &s) -> int { return enqueue_match_full(ctx, s, slot, 1, &s.rgbL, &s.rgbR, W, H, stride, &s.hout); };
-    return host_call(ctx, slot, sync, rgbL, rgbR, W, H, stride, check, match, [&](Slot &s) -> int {
-        if (sync) prefault_planes(ctx, dst, n);  // the GPU is busy for the next ~10 ms: touch the caller's result pages meanwhile
-        return copy_out_planes(ctx, s, s.hout, n, dst);
-    });
-}
-
-int ugsm_match_full(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, float *dispH,
-                    float *dispV, float *dispC)
-{
-    return match_full_host(ctx, 0, rgbL, rgbR, W, H, stride, dispH, dispV, dispC, true);
-}
-
-int ugsm_submit_full_host(ugsm_ctx *ctx, int slot, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, float *dispH,
-                          float *dispV, float *dispC)
-{
-    return match_full_host(ctx, slot, rgbL, rgbR, W, H, stride, dispH, dispV, dispC, false);
-}
-
-// The checked service call on slot 0: upload, both directions in lockstep, the check, the forward planes (and the backward ones where asked
-// for) into caller memory of any kind.  Its buffers, the result staging included, grow before the images go up.
-int ugsm_match_full_checked(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, float *dispH, float *dispV,
-                            float *dispC, float *backH, float *backV, float *backC, float tau)
-{
-    float *const dst[3] = {dispH, dispV, dispC}, *const bdst[3] = {backH, backV, backC};
-    const bool back = backH || backV || backC;
-    const size_t n = (size_t)W * H, room = field_room(n);
-    auto check = [&](Slot &s, size_t &hout) -> int {
-        if (!rgbL || !rgbR || !dispH || !dispV || !dispC) return UGSM_ERR_BAD_ARG;
-        if (back && !(backH && backV && backC)) return ctx_fail(ctx, UGSM_ERR_BAD_ARG, "backH, backV and backC: all three or none");
-        UCHK(full_checked_check(ctx, 1, W, H, stride, tau));
-        UCHK(full_checked_bufs(ctx, s, 1, back ? 0 : 1, W, H));
-        hout = (back ? 2 : 1) * room;
-        return grow(ctx, s.hout, s.hout_cap, hout);
-    };
-    auto match = [&](Slot &s) -> int {
-        float *const d_fwd = s.hout, *const d_bwd = back ? s.hout + room : nullptr;
-        return enqueue_full_checked(ctx, s, 0, 1, &s.rgbL, &s.rgbR, W, H, stride, &d_fwd, back ? &d_bwd : nullptr, tau);
-    };
-    return host_call(ctx, 0, true, rgbL, rgbR, W, H, stride, check, match, [&](Slot &s) -> int {
-        prefault_planes(ctx, dst, n);
-        if (back) prefault_planes(ctx, bdst, n);
-        UCHK(copy_out_planes(ctx, s, s.hout, n, dst));
-        return back ? copy_out_planes(ctx, s, s.hout + room, n, bdst) : UGSM_OK;
-    });
-}
-
-// One foveated pair from host memory.  The slot's result staging: [state 3*fn][stack 3*stackn][pyrL 3*stackn][pyrR 3*stackn], the pyramid
-// stacks where they are asked for.
-static int match_foveated_host(ugsm_ctx *ctx, int slot, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, int off_x, int off_y,
-                               float *stackH, float *stackV, float *stackC, float *pyrL, float *pyrR, bool sync)
-{
-    const int F = ctx ? ctx->cfg.fovea_levels : 0;
-    size_t fn = 0, stackn = 0;
-    float *d_stack = nullptr, *d_pl = nullptr, *d_pr = nullptr;
-    auto check = [&](Slot &, size_t &hout) -> int {
-        if (!stackH || !stackV || !stackC || F < 2) return UGSM_ERR_BAD_ARG;
-        if (!sync && !(is_pinned(rgbL) && is_pinned(rgbR) && is_pinned(stackH) && is_pinned(stackV) && is_pinned(stackC) && (!pyrL || is_pinned(pyrL)) &&
-                       (!pyrR || is_pinned(pyrR))))
-            return not_pinned(ctx, "ugsm_submit_foveated_host");
-        int fw, fh;
-        UCHK(ugsm_fovea_dims(W, H, ctx->cfg.levels, F, &fw, &fh));
-        fn = (size_t)fw * fh;
-        stackn = (size_t)F * fn;
-        hout = 3 * fn + 3 * stackn + (pyrL ? 3 * stackn : 0) + (pyrR ? 3 * stackn : 0);
-        return UGSM_OK;
-    };
-    auto match = [&](Slot &s) -> int {
-        float *d_state = s.hout;
-        d_stack = d_state + 3 * fn;
-        d_pl = pyrL ? d_stack + 3 * stackn : nullptr;
-        d_pr = pyrR ? d_stack + 3 * stackn + (pyrL ? 3 * stackn : 0) : nullptr;
-        return enqueue_match_foveated(ctx, s, slot, 1, &s.rgbL, &s.rgbR, W, H, stride, &off_x, &off_y, &d_state, &d_stack, d_pl ? &d_pl : nullptr,
-                                      d_pr ? &d_pr : nullptr);
-    };
-    return host_call(ctx, slot, sync, rgbL, rgbR, W, H, stride, check, match, [&](Slot &s) -> int {
-        UCHK(download_stack(ctx, s, d_stack, stackn, stackH, stackV, stackC));
-        if (pyrL) HIPCHK(ctx, hipMemcpyAsync(pyrL, d_pl, 3 * stackn * sizeof(float), hipMemcpyDeviceToHost, s.st));
-        if (pyrR) HIPCHK(ctx, hipMemcpyAsync(pyrR, d_pr, 3 * stackn * sizeof(float), hipMemcpyDeviceToHost, s.st));
-        return UGSM_OK;
-    });
-}
-
-int ugsm_match_foveated(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, int off_x,
-                        int off_y, float *stackH, float *stackV, float *stackC, float *pyrL, float *pyrR)
-{
-    return match_foveated_host(ctx, 0, rgbL, rgbR, W, H, stride, off_x, off_y, stackH, stackV, stackC, pyrL, pyrR, true);
-}
-
-int ugsm_submit_foveated_host(ugsm_ctx *ctx, int slot, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, int off_x,
-                              int off_y, float *stackH, float *stackV, float *stackC, float *pyrL, float *pyrR)
-{
-    return match_foveated_host(ctx, slot, rgbL, rgbR, W, H, stride, off_x, off_y, stackH, stackV, stackC, pyrL, pyrR, false);
-}
-
-// n windows of one pair from host memory, on slot 0 (tau: null = the plain call, else the checked one's threshold).  The slot's result staging:
-// [state 3 fn][n stacks of 3 stackn]; the call's buffers, the staging included, grow before the images go up.
-static int match_foveated_multi_host(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, int n, const int *off_x,
-                                     const int *off_y, float *const *stackH, float *const *stackV, float *const *stackC, const float *tau)
-{
-    const int zeros[UGSM_MAX_BATCH] = {0};
-    size_t stackn = 0;
-    float *d_stack[UGSM_MAX_BATCH];
-    auto check = [&](Slot &s, size_t &hout) -> int {
-        if (!rgbL || !rgbR || !stackH || !stackV || !stackC) return UGSM_ERR_BAD_ARG;
-        for (int k = 0; k < n && k < UGSM_MAX_BATCH; k++)
-            if (!stackH[k] || !stackV[k] || !stackC[k]) return UGSM_ERR_BAD_ARG;
-        int fw, fh;
-        UCHK(multi_check(ctx, n, W, H, stride, off_x, off_y, zeros, &fw, &fh, tau));
-        UCHK(tau ? multi_checked_bufs(ctx, s, n, W, H, fw, fh) : multi_level_bufs(ctx, s, n, W, H, fw, fh));
-        const size_t fn = (size_t)fw * fh;
-        stackn = (size_t)ctx->cfg.fovea_levels * fn;
-        hout = 3 * fn + (size_t)n * 3 * stackn;
-        UCHK(grow(ctx, s.hout, s.hout_cap, hout));
-        for (int k = 0; k < n; k++) d_stack[k] = s.hout + 3 * fn + (size_t)k * 3 * stackn;
-        return UGSM_OK;
-    };
-    auto match = [&](Slot &s) -> int {
-        return tau ? enqueue_foveated_multi_checked(ctx, s, 0, s.rgbL, s.rgbR, W, H, stride, n, off_x, off_y, s.hout, d_stack, *tau)
-                   : enqueue_foveated_multi(ctx, s, 0, s.rgbL, s.rgbR, W, H, stride, n, off_x, off_y, s.hout, d_stack);
-    };
-    return host_call(ctx, 0, true, rgbL, rgbR, W, H, stride, check, match, [&](Slot &s) -> int {
-        for (int k = 0; k < n; k++) UCHK(download_stack(ctx, s, d_stack[k], stackn, stackH[k], stackV[k], stackC[k]));
-        return UGSM_OK;
-    });
-}
-
-int ugsm_match_foveated_multi(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, int n, const int *off_x,
-                              const int *off_y, float *const *stackH, float *const *stackV, float *const *stackC)
-{
-    return match_foveated_multi_host(ctx, rgbL, rgbR, W, H, stride, n, off_x, off_y, stackH, stackV, stackC, nullptr);
-}
-
-int ugsm_match_foveated_multi_checked(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, int n, const int *off_x,
-                                      const int *off_y, float *const *stackH, float *const *stackV, float *const *stackC, float tau)
-{
-    return match_foveated_multi_host(ctx, rgbL, rgbR, W, H, stride, n, off_x, off_y, stackH, stackV, stackC, &tau);
-}
-
-// match(L, R, fov == 1), MatchGPULib.cpp:354-360: foveated matching, then hierarchicalDisparity on the stacks.  The slot's result staging:
-// [state][stack][full field]
-int ugsm_match_foveated_full(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, int off_x, int off_y,
-                             float *outH, float *outV, float *outC)
-{
-    float *const dst[3] = {outH, outV, outC};
-    const int F = ctx ? ctx->cfg.fovea_levels : 0;
-    const size_t n = (size_t)W * H;
-    size_t fn = 0, stackn = 0;
-    auto check = [&](Slot &, size_t &hout) -> int {
-        if (!outH || !outV || !outC || F < 2) return UGSM_ERR_BAD_ARG;
-        int fw, fh;
-        UCHK(ugsm_fovea_dims(W, H, ctx->cfg.levels, F, &fw, &fh));
-        fn = (size_t)fw * fh;
-        stackn = (size_t)F * fn;
-        hout = 3 * fn + 3 * stackn + 3 * n;
-        return UGSM_OK;
-    };
-    auto match = [&](Slot &s) -> int {
-        float *d_state = s.hout, *d_stack = d_state + 3 * fn;
-        UCHK(enqueue_match_foveated(ctx, s, 0, 1, &s.rgbL, &s.rgbR, W, H, stride, &off_x, &off_y, &d_state, &d_stack, nullptr, nullptr));
-        return ugsm_reconstruct_full(ctx, 0, d_stack, d_stack + stackn, d_stack + 2 * stackn, W, H, off_x, off_y, d_stack + 3 * stackn);
-    };
-    return host_call(ctx, 0, true, rgbL, rgbR, W, H, stride, check, match, [&](Slot &s) -> int {
-        prefault_planes(ctx, dst, n);
-        return copy_out_planes(ctx, s, s.hout + 3 * fn + 3 * stackn, n, dst);
-    });
-}
-
-// ---- batches from page-locked host memory (round 4): the uploads of all pairs, ONE batched match, the downloads of all pairs, enqueued on
-// the slot's stream.  The images are staged in the slot (pair b at rgbL / rgbR + b * image bytes), the results in hout.
-static bool all_pinned(const void *const *p, int n)
-{
-    for (int b = 0; b < n; b++)
-        if (!p[b] || !is_pinned(p[b])) return false;
-    return true;
-}
-// what both calls refuse behind their null arrays: an image or a result plane, of any pair, that is null or not page-locked
-static int batch_pinned(ugsm_ctx *ctx, const char *entry, int n, const uint8_t *const *rgbL, const uint8_t *const *rgbR, float *const *outH,
-                        float *const *outV, float *const *outC)
-{
-    for (const void *const *p : {(const void *const *)rgbL, (const void *const *)rgbR, (const void *const *)outH, (const void *const *)outV, (const void *const *)outC})
-        if (!all_pinned(p, n)) return not_pinned(ctx, entry);
-    return UGSM_OK;
-}
-static int stage_in_batch(ugsm_ctx *ctx, Slot &s, int n, const uint8_t *const *rgbL, const uint8_t *const *rgbR, int W, int H, int stride,
-                          const uint8_t **dL, const uint8_t **dR)
-{
-    if (W < 1 || H < 1) return UGSM_ERR_BAD_ARG;
-    if (stride < input_row_bytes(ctx, W)) return UGSM_ERR_SIZE_MISMATCH;
-    const size_t bytes = ((size_t)stride * H + 255) & ~(size_t)255;
-    if (bytes * n > s.rgb_cap) {
-        size_t c = s.rgb_cap;
-        UCHK(grow(ctx, s.rgbL, c, bytes * n));
-        UCHK(grow(ctx, s.rgbR, s.rgb_cap, bytes * n));
-    }
-    for (int b = 0; b < n; b++) {
-        dL[b] = s.rgbL + b * bytes;
-        dR[b] = s.rgbR + b * bytes;
-        HIPCHK(ctx, hipMemcpyAsync(s.rgbL + b * bytes, rgbL[b], (size_t)stride * H, hipMemcpyHostToDevice, s.st));
-        HIPCHK(ctx, hipMemcpyAsync(s.rgbR + b * bytes, rgbR[b], (size_t)stride * H, hipMemcpyHostToDevice, s.st));
-    }
-    return UGSM_OK;
-}
-
-int ugsm_submit_full_batch_host(ugsm_ctx *ctx, int slot, int n, const uint8_t *const *rgbL, const uint8_t *const *rgbR, int W, int H, int stride,
-                                float *const *dispH, float *const *dispV, float *const *dispC)
-{
-    Slot *s;
-    UCHK(get_slot(ctx, slot, &s));
-    if (n < 1 || n > UGSM_MAX_BATCH || !rgbL || !rgbR || !dispH || !dispV || !dispC) return UGSM_ERR_BAD_ARG;
-    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
-    UCHK(batch_pinned(ctx, "ugsm_submit_full_batch_host", n, rgbL, rgbR, dispH, dispV, dispC));
-    if (n == 1 || batch_runs_pair_by_pair(ctx)) {
-        for (int b = 0; b < n; b++) UCHK(match_full_host(ctx, slot, rgbL[b], rgbR[b], W, H, stride, dispH[b], dispV[b], dispC[b], false));
-        return UGSM_OK;
-    }
-    const uint8_t *dL[UGSM_MAX_BATCH], *dR[UGSM_MAX_BATCH];
-    UCHK(stage_in_batch(ctx, *s, n, rgbL, rgbR, W, H, stride, dL, dR));
-    const size_t px = (size_t)W * H, per = field_room(px);
-    UCHK(grow(ctx, s->hout, s->hout_cap, per * n));
-    float *out[UGSM_MAX_BATCH];
-    for (int b = 0; b < n; b++) out[b] = s->hout + b * per;
-    UCHK(enqueue_match_full(ctx, *s, slot, n, dL, dR, W, H, stride, out));
-    for (int b = 0; b < n; b++) {
-        float *const dst[3] = {dispH[b], dispV[b], dispC[b]};
-        UCHK(copy_out_planes(ctx, *s, out[b], px, dst));  // (page-locked destinations: three asynchronous copies)
-    }
-    return mark_done(ctx, *s);
-}
-
-int ugsm_submit_foveated_batch_host(ugsm_ctx *ctx, int slot, int n, const uint8_t *const *rgbL, const uint8_t *const *rgbR, int W, int H, int stride,
-                                    const int *off_x, const int *off_y, float *const *stackH, float *const *stackV, float *const *stackC)
-{
-    Slot *s;
-    UCHK(get_slot(ctx, slot, &s));
-    if (n < 1 || n > UGSM_MAX_BATCH || !rgbL || !rgbR || !stackH || !stackV || !stackC) return UGSM_ERR_BAD_ARG;
-    const int F = ctx->cfg.fovea_levels;
-    if (F < 2) return UGSM_ERR_BAD_ARG;
-    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
-    UCHK(batch_pinned(ctx, "ugsm_submit_foveated_batch_host", n, rgbL, rgbR, stackH, stackV, stackC));
-    int zeros[UGSM_MAX_BATCH] = {0};
-    const int *ox = off_x ? off_x : zeros, *oy = off_y ? off_y : zeros;
-    if (n == 1 || fovea_batch_runs_pair_by_pair(ctx)) {
-        for (int b = 0; b < n; b++)
-            UCHK(match_foveated_host(ctx, slot, rgbL[b], rgbR[b], W, H, stride, ox[b], oy[b], stackH[b], stackV[b], stackC[b], nullptr, nullptr, false));
-        return UGSM_OK;
-    }
-    int fw, fh;
-    UCHK(ugsm_fovea_dims(W, H, ctx->cfg.levels, F, &fw, &fh));
-    const uint8_t *dL[UGSM_MAX_BATCH], *dR[UGSM_MAX_BATCH];
-    UCHK(stage_in_batch(ctx, *s, n, rgbL, rgbR, W, H, stride, dL, dR));
-    const size_t fn = (size_t)fw * fh, stackn = (size_t)F * fn;
-    const size_t st_per = fovea_field_room(fw, fh), sk_per = (3 * stackn + 63) & ~(size_t)63;  // hout: [states n x st_per][stacks n x sk_per]
-    UCHK(grow(ctx, s->hout, s->hout_cap, n * (st_per + sk_per)));
-    float *state[UGSM_MAX_BATCH], *stack[UGSM_MAX_BATCH];
-    for (int b = 0; b < n; b++) {
-        state[b] = s->hout + b * st_per;
-        stack[b] = s->hout + n * st_per + b * sk_per;
-    }
-    UCHK(enqueue_match_foveated(ctx, *s, slot, n, dL, dR, W, H, stride, ox, oy, state, stack, nullptr, nullptr));
-    for (int b = 0; b < n; b++) UCHK(download_stack(ctx, *s, stack[b], stackn, stackH[b], stackV[b], stackC[b]));
-    return mark_done(ctx, *s);
-}
-
-// ---- stage-level ------------------------------------------------------------------------
-
-int ugsm_stage_pyramid(ugsm_ctx *ctx, const uint8_t *d_rgb, int W, int H, int stride, int level, float *d_out3)
-{
-    Slot *s;
-    UCHK(get_slot(ctx, 0, &s));
-    if (!d_rgb || !d_out3 || level < 0 || level >= ctx->cfg.levels) return UGSM_ERR_BAD_ARG;
-    if (stride < input_row_bytes(ctx, W)) return UGSM_ERR_SIZE_MISMATCH;
-    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
-    UCHK(prepare_slot(ctx, *s, W, H));
-    UCHK(build_pyramids(ctx, *s, 0, &d_rgb, stride, s->pyrL));
-    HIPCHK(ctx, hipMemcpyAsync(d_out3, s->pyrL + s->off[level], sizeof(float) * 3 * (size_t)s->w[level] * s->h[level],
-                               hipMemcpyDeviceToDevice, s->st));
-    return ugsm_wait(ctx, 0);
-}
-
-int ugsm_stage_iterate(ugsm_ctx *ctx, const float *d_L3, const float *d_R3, float *d_d3, int W, int H, int mi, int S,
-                       int is_top, int m_from, int m_to, float *d_dbg8)
-{
-    Slot *s;
-    UCHK(get_slot(ctx, 0, &s));
-    if (!d_L3 || !d_R3 || !d_d3 || W < 1 || H < 1 || mi < 1 || m_from < 1 || m_to > mi || S < 0) return UGSM_ERR_BAD_ARG;
-    if ((long long)W * H > kMaxPixels) return UGSM_ERR_BAD_ARG;
-    if (d_dbg8 && ctx->cfg.kernel_path != 1) return UGSM_ERR_BAD_ARG;
-    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
-    // level buffers sized for this image; the pyramid buffers are not needed here
-    const size_t lvl = 3 * (size_t)W * H;
-    UCHK(ensure_level_bufs(ctx, *s, lvl));
-    float *cur = s->d0, *other = s->d1;
-    HIPCHK(ctx, hipMemcpyAsync(cur, d_d3, lvl * sizeof(float), hipMemcpyDeviceToDevice, s->st));
-    const size_t n = (size_t)W * H;
-    // the planes arrive ready-made: check their range here (the pyramid kernels do it for the matcher proper).  The slot's range
-    // word then describes THESE planes, no longer the slot's pyramids: a fovea phase submitted afterwards must rebuild them first
-    s->have_pyr = false;
-    s->have_coarse = false;
-    s->range_known = ctx->cfg.kernel_path != 1;
-    if (s->range_known) {
-        HIPCHK(ctx, hipMemsetAsync(s->range_bad, 0, sizeof(unsigned), s->st));
-        launch_range_scan(s->st, d_L3, 3 * n, s->range_bad);
-        launch_range_scan(s->st, d_R3, 3 * n, s->range_bad);
-    }
-    s->nb = 1;
-    const Img3 Lv{d_L3, W, n}, Rv{d_R3, W, n};
-    UCHK(run_level(ctx, *s, 0, Shape::pairs(*s), &Lv, &Rv, W, H, mi, S, is_top != 0, m_from, m_to, cur, other, d_dbg8));
-    HIPCHK(ctx, hipMemcpyAsync(d_d3, cur, lvl * sizeof(float), hipMemcpyDeviceToDevice, s->st));
-    return ugsm_wait(ctx, 0);
-}
-
-int ugsm_stage_seed(ugsm_ctx *ctx, const float *d_src3, int W, int H, float *d_dst3, int W2, int H2, int Wup, int Hup,
-                    int crop_x, int crop_y)
-{
-    Slot *s;
-    UCHK(get_slot(ctx, 0, &s));
-    if (!d_src3 || !d_dst3 || W < 1 || H < 1 || W2 < 1 || H2 < 1) return UGSM_ERR_BAD_ARG;
-    (void)Wup;
-    (void)Hup;
-    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
-    {
-        Timer t(ctx, s, 0, KC_SEED, (double)W2 * H2);  // (profile_events = 2: the launch's own duration in the kernel statistics)
-        launch_seed(s->st, d_src3, W, H, d_dst3, W2, H2, crop_x, crop_y);
-    }
-    HIPCHK(ctx, hipGetLastError());
-    return ugsm_wait(ctx, 0);
-}
-
-int ugsm_stage_restrict(ugsm_ctx *ctx, const float *d_src3, int W, int H, int level, float *d_dst3)
-{
-    Slot *s;
-    UCHK(get_slot(ctx, 0, &s));
-    if (!d_src3 || !d_dst3 || level < 0 || level >= ctx->cfg.levels) return UGSM_ERR_BAD_ARG;
-    int w[UGSM_MAX_LEVELS], h[UGSM_MAX_LEVELS];
-    UCHK(level_dims(W, H, ctx->cfg.levels, w, h));
-    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
-    launch_restrict(s->st, d_src3, W, H, level, d_dst3, w[level], h[level]);
-    HIPCHK(ctx, hipGetLastError());
-    return ugsm_wait(ctx, 0);
-}
-
-int ugsm_stage_prolong(ugsm_ctx *ctx, const float *d_src3, int W, int H, int level, float *d_dst3)
-{
-    Slot *s;
-    UCHK(get_slot(ctx, 0, &s));
-    if (!d_src3 || !d_dst3 || level < 0 || level >= ctx->cfg.levels) return UGSM_ERR_BAD_ARG;
-    int w[UGSM_MAX_LEVELS], h[UGSM_MAX_LEVELS];
-    UCHK(level_dims(W, H, ctx->cfg.levels, w, h));
-    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
-    s->cur_level = level;
-    bool launched;
-    {
-        Timer t(ctx, s, 0, KC_PROLONG, (double)W * H);
-        launched = launch_prolong(s->st, d_src3, w, h, level, d_dst3);
-    }
-    if (!launched) return ctx_fail(ctx, UGSM_ERR_BAD_ARG, "the prolongation: a size its kernel does not cover");
-    HIPCHK(ctx, hipGetLastError());
-    return ugsm_wait(ctx, 0);
-}
-
-int ugsm_stage_warm_stack(ugsm_ctx *ctx, const float *d_prior_stack, int W, int H, int prior_off_x, int prior_off_y, int off_x, int off_y, int start_level,
-                          float *d_dst_stack)
-{
-    Slot *s;
-    UCHK(get_slot(ctx, 0, &s));
-    const int F = ctx->cfg.fovea_levels;
-    if (!d_prior_stack || !d_dst_stack || d_prior_stack == d_dst_stack || F < 2 || F > ctx->cfg.levels || start_level < 0 || start_level >= F) return UGSM_ERR_BAD_ARG;
-    int w[UGSM_MAX_LEVELS], h[UGSM_MAX_LEVELS];
-    UCHK(level_dims(W, H, ctx->cfg.levels, w, h));
-    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
-    UCHK(enqueue_restrict_stack(ctx, *s, 0, 1, w, h, F, &d_prior_stack, &prior_off_x, &prior_off_y, false, &off_x, &off_y, start_level, &d_dst_stack, nullptr, 0));
-    return ugsm_wait(ctx, 0);
-}
-
-int ugsm_stage_smooth(ugsm_ctx *ctx, float *d_d3, int W, int H, int passes, int do_box)
-{
-    Slot *s;
-    UCHK(get_slot(ctx, 0, &s));
-    if (!d_d3 || W < 1 || H < 1 || passes < 0 || (long long)W * H > kMaxPixels) return UGSM_ERR_BAD_ARG;
-    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
-    const size_t lvl = 3 * (size_t)W * H;
-    UCHK(ensure_level_bufs(ctx, *s, lvl));
-    float *a = s->d0, *b = s->d1;
-    HIPCHK(ctx, hipMemcpyAsync(a, d_d3, lvl * sizeof(float), hipMemcpyDeviceToDevice, s->st));
-    s->nb = 1;
-    UCHK(enqueue_smooth(ctx, *s, 0, Shape::pairs(*s), a, b, W, H, passes, do_box != 0));
-    HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipMemcpyAsync(d_d3, a, lvl * sizeof(float), hipMemcpyDeviceToDevice, s->st));
-    return ugsm_wait(ctx, 0);
-}
-
-// hierarchicalDisparity, MatchGPULib.cpp:2589-2701
-int ugsm_reconstruct_full(ugsm_ctx *ctx, int slot, const float *d_stackH, const float *d_stackV, const float *d_stackC, int W, int H,
-                          int off_x, int off_y, float *d_out3)
-{
-    Slot *s;
-    UCHK(get_slot(ctx, slot, &s));
-    if (!d_stackH || !d_stackV || !d_stackC || !d_out3) return UGSM_ERR_BAD_ARG;
-    const int levels = ctx->cfg.levels, F = ctx->cfg.fovea_levels;
-    int w[UGSM_MAX_LEVELS], h[UGSM_MAX_LEVELS];
-    UCHK(level_dims(W, H, levels, w, h));
-    if (F < 1 || F > levels) return UGSM_ERR_BAD_ARG;
-    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
-    FoveaGeom g;
-    if (F >= 2) fovea_geometry(w, h, F, off_x, off_y, g);
-    else { g.fw = w[0]; g.fh = h[0]; }
-    const size_t fl = (size_t)g.fw * g.fh;
-    if (F == 1) {  // the stack is the full frame already
-        const float *src[3] = {d_stackH, d_stackV, d_stackC};
-        for (int c = 0; c < 3; c++) HIPCHK(ctx, hipMemcpyAsync(d_out3 + c * fl, src[c], fl * sizeof(float), hipMemcpyDeviceToDevice, s->st));
-        return UGSM_OK;
-    }
-    UCHK(ensure_level_bufs(ctx, *s, 3 * (size_t)w[1] * h[1]));
-    // level F-1 (whole frame) as a 3-plane field
-    float *cur = s->d0, *other = s->d1;
-    {
-        const float *src[3] = {d_stackH, d_stackV, d_stackC};
-        for (int c = 0; c < 3; c++)
-            HIPCHK(ctx, hipMemcpyAsync(cur + c * fl, src[c] + (size_t)(F - 1) * fl, fl * sizeof(float), hipMemcpyDeviceToDevice, s->st));
-    }
-    for (int level = F - 1; level > 0; level--) {
-        float *dst = (level == 1) ? d_out3 : other;
-        Timer t(ctx, s, slot, KC_MISC, (double)w[level - 1] * h[level - 1]);
-        launch_upsample_paste(s->st, cur, w[level], h[level], dst, w[level - 1], h[level - 1], d_stackH + (size_t)(level - 1) * fl,
-                              d_stackV + (size_t)(level - 1) * fl, d_stackC + (size_t)(level - 1) * fl, g.fw, g.fh, g.ox[level - 1], g.oy[level - 1]);
-        std::swap(cur, other);
-    }
-    HIPCHK(ctx, hipGetLastError());
-    return UGSM_OK;
-}
-
-// hierarchicalDisparity over the stacks of n windows of one pair: the steps of ugsm_reconstruct_full, every one pasting all the windows
-int ugsm_reconstruct_full_multi(ugsm_ctx *ctx, int slot, int n, const float *const *d_stack, int W, int H, const int *off_x, const int *off_y,
-                                float *d_out3)
-{
-    Slot *s;
-    UCHK(get_slot(ctx, slot, &s));
-    if (!d_stack || !d_out3 || n < 1 || n > UGSM_MAX_BATCH) return UGSM_ERR_BAD_ARG;
-    for (int k = 0; k < n; k++)
-        if (!d_stack[k]) return UGSM_ERR_BAD_ARG;
-    const int levels = ctx->cfg.levels, F = ctx->cfg.fovea_levels;
-    int w[UGSM_MAX_LEVELS], h[UGSM_MAX_LEVELS];
-    UCHK(level_dims(W, H, levels, w, h));
-    if (F < 2 || F > levels) return UGSM_ERR_BAD_ARG;
-    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
-    FoveaGeom g[UGSM_MAX_BATCH];
-    for (int k = 0; k < n; k++) fovea_geometry(w, h, F, off_x ? off_x[k] : 0, off_y ? off_y[k] : 0, g[k]);
-    const size_t fl = (size_t)g[0].fw * g[0].fh;
-    UCHK(ensure_level_bufs(ctx, *s, 3 * (size_t)w[1] * h[1]));
-    // level F-1 (whole frame; the same in every stack) as a 3-plane field, from stack 0
-    float *cur = s->d0, *other = s->d1;
-    for (int c = 0; c < 3; c++)
-        HIPCHK(ctx, hipMemcpyAsync(cur + c * fl, d_stack[0] + ((size_t)c * F + (F - 1)) * fl, fl * sizeof(float), hipMemcpyDeviceToDevice, s->st));
-    for (int level = F - 1; level > 0; level--) {
-        float *dst = (level == 1) ? d_out3 : other;
-        PasteWindows pw{};
-        pw.n = n;
-        for (int k = 0; k < n; k++) {
-            pw.org_x[k] = g[k].ox[level - 1];
-            pw.org_y[k] = g[k].oy[level - 1];
-            pw.stack[k] = byte_diff(d_stack[k], d_stack[0]);
-        }
-        Timer t(ctx, s, slot, KC_MISC, (double)w[level - 1] * h[level - 1]);
-        launch_upsample_paste_multi(s->st, cur, w[level], h[level], dst, w[level - 1], h[level - 1], d_stack[0] + (size_t)(level - 1) * fl, (size_t)F * fl,
-                                    g[0].fw, g[0].fh, pw);
-        std::swap(cur, other);
-    }
-    HIPCHK(ctx, hipGetLastError());
-    return UGSM_OK;
-}
-
-#ifdef UGSM_DEV_LIB
-int ugsm_stage_poly_probe(ugsm_ctx *ctx, const float *d_c, const float *d_l, const float *d_r, const float *d_thr, float *d_delta,
-                          float *d_corr, float *d_third, int n)
-{
-    Slot *s;
-    UCHK(get_slot(ctx, 0, &s));
-    if (!d_c || !d_l || !d_r || !d_thr || !d_delta || !d_corr || !d_third || n < 1) return UGSM_ERR_BAD_ARG;
-    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
-    launch_poly_probe(s->st, d_c, d_l, d_r, d_thr, d_delta, d_corr, d_third, n);
-    HIPCHK(ctx, hipGetLastError());
-    return ugsm_wait(ctx, 0);
-}
-#endif
-
-int ugsm_stage_weighted_difference(ugsm_ctx *ctx, const float *d_new3, const float *d_old3, int W, int H, float *out2)
-{
-    Slot *s;
-    UCHK(get_slot(ctx, 0, &s));
-    if (!d_new3 || !d_old3 || !out2 || W < 1 || H < 1 || H > 65535 || (long long)W * H > kMaxPixels) return UGSM_ERR_BAD_ARG;
-    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
-    return weighted_difference(ctx, *s, d_new3, d_old3, W, H, out2);
-}
-
-int ugsm_stage_lr_check(ugsm_ctx *ctx, float *d_left3, const float *d_right3, int W, int H, float tau, long long *marked)
-{
-    Slot *s;
-    UCHK(get_slot(ctx, 0, &s));
-    if (!d_left3 || !d_right3 || W < 1 || H < 1 || H > 65535 || (long long)W * H > kMaxPixels || !(tau >= 0.0f)) return UGSM_ERR_BAD_ARG;
-    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
-    UCHK(grow(ctx, s->lr, s->lr_cap, std::max<size_t>(s->lr_cap, 8)));
-    UCHK(lr_host_ready(ctx, *s));
-    unsigned long long *cnt = reinterpret_cast<unsigned long long *>(s->lr);
-    HIPCHK(ctx, hipStreamSynchronize(s->st));  // (the counter shares the slot's LR buffer)
-    HIPCHK(ctx, hipMemsetAsync(cnt, 0, sizeof *cnt, s->st));
-    launch_lr_check(s->st, d_left3, d_right3, W, H, tau, cnt);
-    HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipMemcpyAsync(s->lr_host, cnt, sizeof *cnt, hipMemcpyDeviceToHost, s->st));
-    UCHK(ugsm_wait(ctx, 0));
-    if (marked) *marked = (long long)*s->lr_host;
-    return UGSM_OK;
 }
 
 long long ugsm_last_lr_marked(ugsm_ctx *ctx, int slot)
@@ -3290,90 +697,6 @@ int ugsm_last_iterations(ugsm_ctx *ctx, int slot, int *per_level)
     for (int i = 0; i < UGSM_MAX_LEVELS; i++) per_level[i] = s->iters_run[i];
     return UGSM_OK;
 }
-
-#ifdef UGSM_DEV_LIB
-int ugsm_stage_div_probe(ugsm_ctx *ctx, const float *d_n, const float *d_d, float *d_q, int n)
-{
-    Slot *s;
-    UCHK(get_slot(ctx, 0, &s));
-    if (!d_n || !d_d || !d_q || n < 1) return UGSM_ERR_BAD_ARG;
-    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
-    launch_div_probe(s->st, d_n, d_d, d_q, n);
-    HIPCHK(ctx, hipGetLastError());
-    return ugsm_wait(ctx, 0);
-}
-
-// The range words of the slot's last call (Slot::range_bad: zeroed by enqueue_pyramids, set by the pyramid kernels, read by the
-// marching K-cost kernels), for the tests that drive that mechanism through whole calls.  Reads host state and device memory only:
-// the slot does not become busy, nothing is launched.
-int ugsm_stage_range_words(ugsm_ctx *ctx, int slot, unsigned *host_out, int n)
-{
-    Slot *s;
-    UCHK(get_slot(ctx, slot, &s, false));
-    if (!host_out || n < 1 || n > kMaxBatch) return UGSM_ERR_BAD_ARG;
-    if (!s->range_known || !s->range_bad) {
-        ctx->err = "the slot holds no range words (kernel_path 1, or no call has built pyramids on it)";
-        return UGSM_ERR_STATE;
-    }
-    if (n > s->nb) return UGSM_ERR_BAD_ARG;
-    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
-    HIPCHK(ctx, hipStreamSynchronize(s->st));  // (the main stream has joined whatever the call put on the side stream)
-    HIPCHK(ctx, hipMemcpy(host_out, s->range_bad, sizeof(unsigned) * n, hipMemcpyDeviceToHost));
-    return UGSM_OK;
-}
-
-// Whether the last call on the slot read level 0 from the images (Slot::direct0) -- batched and queue-formed calls included, which leave no other
-// trace of it: the results are the same bits either way.  Host state only.
-int ugsm_stage_level0_direct(ugsm_ctx *ctx, int slot)
-{
-    Slot *s;
-    const int st = get_slot(ctx, slot, &s, false);
-    if (st != UGSM_OK) return -st;
-    return s->direct0 ? 1 : 0;
-}
-
-// ugsm_stage_iterate with the two images given as rgb8 instead of float planes: the level runs the way level 0 of a full-mode call runs
-// (Slot::direct0) -- A and K-cost through their 8-bit instances, on byte views of the images -- but from the caller's field, so that a test
-// can send disparities of its own choosing through the clamped byte gather.
-int ugsm_stage_iterate_rgb8(ugsm_ctx *ctx, const uint8_t *d_rgbL, const uint8_t *d_rgbR, int stride, float *d_d3, int W, int H, int mi, int S, int is_top,
-                            int m_from, int m_to)
-{
-    Slot *s;
-    UCHK(get_slot(ctx, 0, &s));
-    if (!d_rgbL || !d_rgbR || !d_d3 || W < 1 || H < 1 || mi < 1 || m_from < 1 || m_to > mi || S < 0) return UGSM_ERR_BAD_ARG;
-    if ((long long)W * H > kMaxPixels || ctx->cfg.kernel_path == 1 || ctx->hooks.input_format != kInRGB8) return UGSM_ERR_BAD_ARG;
-    if (stride < 3 * W) return UGSM_ERR_SIZE_MISMATCH;
-    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
-    const size_t lvl = 3 * (size_t)W * H;
-    UCHK(ensure_level_bufs(ctx, *s, lvl));
-    float *cur = s->d0, *other = s->d1;
-    HIPCHK(ctx, hipMemcpyAsync(cur, d_d3, lvl * sizeof(float), hipMemcpyDeviceToDevice, s->st));
-    s->have_pyr = false;
-    s->have_coarse = false;
-    s->range_known = true;  // (the integers 0 .. 255: always inside range_ok)
-    HIPCHK(ctx, hipMemsetAsync(s->range_bad, 0, sizeof(unsigned), s->st));
-    s->nb = 1;
-    s->direct0 = false;  // (no call of the slot's: ugsm_stage_level0_direct)
-    const Img3 Lv = byte_view(d_rgbL, stride), Rv = byte_view(d_rgbR, stride);
-    UCHK(run_level(ctx, *s, 0, Shape::pairs(*s), &Lv, &Rv, W, H, mi, S, is_top != 0, m_from, m_to, cur, other, nullptr, nullptr, nullptr, nullptr, kInRGB8));
-    HIPCHK(ctx, hipMemcpyAsync(d_d3, cur, lvl * sizeof(float), hipMemcpyDeviceToDevice, s->st));
-    return ugsm_wait(ctx, 0);
-}
-#endif
-
-#ifdef UGSM_DEV_LIB
-int ugsm_stage_div3_probe(ugsm_ctx *ctx, const float *d_a0, const float *d_a1, const float *d_a2, const float *d_s, float *d_q0, float *d_q1,
-                          float *d_q2, int n)
-{
-    Slot *s;
-    UCHK(get_slot(ctx, 0, &s));
-    if (!d_a0 || !d_a1 || !d_a2 || !d_s || !d_q0 || !d_q1 || !d_q2 || n < 1) return UGSM_ERR_BAD_ARG;
-    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
-    launch_div3_probe(s->st, d_a0, d_a1, d_a2, d_s, d_q0, d_q1, d_q2, n);
-    HIPCHK(ctx, hipGetLastError());
-    return ugsm_wait(ctx, 0);
-}
-#endif
 
 // ---- instrumentation / memory helpers ---------------------------------------------------
 

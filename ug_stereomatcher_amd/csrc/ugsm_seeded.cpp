@@ -1,7 +1,7 @@
 // ugsm_seeded.cpp -- the entry points of the seeded full-mode call (include/ugsm.h: ugsm_submit_full_seeded, ugsm_match_full_seeded,
 // ugsm_seeded_pixel_iterations): what the call refuses, all of it before anything is enqueued, and the call's size.  Written against the
-// public entry points and ugsm_internal.hpp only (no HIP call here, as the queue): the runtime does the enqueueing (ugsm::seeded_submit,
-// ugsm::seeded_match: ugsm_runtime.cpp), and the refusals can be driven on a machine without a GPU (tests/fake_seeded.cpp).
+// public entry points and ugsm_internal.hpp only (no HIP call here, as the queue): the runtime does the enqueueing (ugsm::seeded_submit:
+// ugsm_full.cpp; ugsm::seeded_match: ugsm_host.cpp), and the refusals can be driven on a machine without a GPU (tests/fake_seeded.cpp).
 #include "ugsm_internal.hpp"
 
 using namespace ugsm;

@@ -1,12 +1,20 @@
-// ugsm_slot.hpp -- the runtime's own state, for its translation units (ugsm_runtime.cpp: the matcher; ugsm_cloud.cpp: the clouds;
-// ugsm_warp.cpp: the warped right image and the photometric residual): the
-// slot, the context, the checks and the few helpers of ugsm_runtime.cpp that the cloud layer enqueues through.  Nothing here is exported.
+// ugsm_slot.hpp -- the runtime's own state, for its translation units: the slot, the context, the checks, the vocabulary of a call's
+// sequence, and what one of these files defines for another.  Nothing here is exported.
+//   ugsm_runtime.cpp  the context: slots and their buffers, ugsm_create / ugsm_destroy, ugsm_wait / ugsm_poll, getters, statistics
+//   ugsm_policy.cpp   which kernel and which stream a level gets; the development overrides; ugsm_plan_level
+//   ugsm_levels.cpp   the work of one level: pyramids, A, K-cost and K-smooth (run_level), the seed hand-over
+//   ugsm_full.cpp     the full-frame descent and the calls made of it (whole, checked, seeded, the two halves); a foveated call's coarse phase
+//   ugsm_fovea.cpp    the foveated calls: fine phase, checked, warm, several windows on one pair; hierarchicalDisparity
+//   ugsm_host.cpp     everything that touches caller host memory: the host team, staging, the blocking service calls
+//   ugsm_stages.cpp   the stage-level entry points (tests only)
+//   ugsm_cloud.cpp    the clouds;  ugsm_warp.cpp  the warped right image and the photometric residual
 // (The layers above the slot API -- queue, shard -- and the tests' fake runtimes compile against ugsm_internal.hpp, which needs no HIP.)
 #pragma once
 
 #include "ugsm_internal.hpp"
 #include "ugsm_launch.hpp"
 
+#include <algorithm>
 #include <cstdio>
 #include <memory>
 #include <string>
@@ -79,7 +87,7 @@ struct Slot {
     // nb and the strides describe the call's REAL pairs and are set by prepare_slot alone (the stage entry points, which bring one field of
     // their own, set nb = 1).  What runs in lockstep while a call's levels are
     // enqueued -- both directions of a checked foveated call, the windows of a multi-window call, at a stride of one fovea field -- is a value
-    // the call's sequence hands down (Shape, ugsm_runtime.cpp), never written here.
+    // the call's sequence hands down (Shape, below), never written here.
     int nb = 1;
     size_t pyr_stride = 0, lvl_stride = 0;  // floats
     float *A = nullptr, *Rw = nullptr, *B = nullptr, *d0 = nullptr, *d1 = nullptr;
@@ -153,12 +161,12 @@ struct Slot {
     hipEvent_t warm_ev[kWarmRing] = {};
     bool warm_ev_set[kWarmRing] = {};
     int warm_next = 0;
-    bool range_known = false;
-    int cur_level = kNoLevel;  // pyramid level the launches being enqueued belong to (statistics only)  // range_bad describes the images the next run_level works on
+    bool range_known = false;  // range_bad describes the images the next run_level works on
+    int cur_level = kNoLevel;  // pyramid level the launches being enqueued belong to (statistics only)
     std::vector<EvRec> pending;
     std::vector<hipEvent_t> pool;
 };
-class HostTeam;  // (ugsm_runtime.cpp)
+class HostTeam;  // (ugsm_host.cpp)
 
 }  // namespace ugsm
 
@@ -186,7 +194,8 @@ struct ugsm_ctx {
     long long release_epoch = 0;  // counts the releases of tracked device buffers (untrack): "memory may have come free since"
     bool counted_live = false;  // this context counts in g_live_contexts (ugsm_create got as far as handing it out)
     long long mem_limit = 0;    // development (UGSM_MEM_LIMIT_MB under UGSM_DEV=1): grow refuses to go past it -- the UGSM_ERR_NOMEM path without exhausting a GPU
-    ~ugsm_ctx();  // (ugsm_runtime.cpp: where HostTeam is whole)
+    ugsm_ctx();
+    ~ugsm_ctx();  // (both in ugsm_host.cpp: where HostTeam is whole)
 };
 
 #define HIPCHK(ctx, call)                                                                             \
@@ -292,18 +301,62 @@ struct Timer {
     }
 };
 
-// ---- what ugsm_runtime.cpp defines for ugsm_cloud.cpp ------------------------------------------------------------------
-int level_dims(int W, int H, int levels, int *w, int *h);
-void fovea_geometry(const int *w, const int *h, int F, int off_x, int off_y, FoveaGeom &g);
-// the least stride of a W-pixel row in the context's input format
-inline int input_row_bytes(const ugsm_ctx *ctx, int W) { return input_bpp(ctx->hooks.input_format) * W; }
-bool batch_level(const ugsm_ctx *ctx, int W, int H);
-bool batch_runs_pair_by_pair(const ugsm_ctx *ctx);
-bool fovea_batch_runs_pair_by_pair(const ugsm_ctx *ctx);
-int get_slot(ugsm_ctx *ctx, int slot, Slot **out, bool enqueues = true);
-int mark_done(ugsm_ctx *ctx, Slot &s);
-int stage_in(ugsm_ctx *ctx, Slot &s, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride);
-// Which full-frame levels a descent runs -- `from` down to `to` -- and what level `from` starts from (enqueue_descent, ugsm_runtime.cpp).  Made by
+// ---- the vocabulary of a call's sequence (ugsm_levels.cpp, ugsm_full.cpp, ugsm_fovea.cpp, ugsm_stages.cpp) --------------------------------
+// The pairs of one launch: b0 .. b0 + n - 1 of the batch in the slot (n = 1: an ordinary launch of pair b0).
+struct Grp {
+    int b0, n;
+};
+// The lockstep layout of a call's levels: how many fields run together, which pyramids each reads and where its fields lie.  A value that the
+// call's sequence makes once and hands down; the slot keeps only what belongs to its real pairs (Slot::nb, Slot::lvl_stride).
+struct Shape {
+    int nb;         // the entries that run in lockstep
+    int nreal;      // entries nreal .. nb - 1 are the entries 0 .. nreal - 1 with the L and R views exchanged (pair_pyr); nreal == nb: none are
+    bool one_pair;  // every entry reads pair 0's pyramids: the entries are windows of one pair
+    size_t stride;  // floats between consecutive entries' fields in A, d0 and d1
+    // the slot's real pairs, each at its own full-frame room
+    static Shape pairs(const Slot &s) { return {s.nb, s.nb, false, s.lvl_stride}; }
+    // both directions of n pairs / n windows of one pair / both directions of n windows of one pair: every field is at most a fovea field, `field`
+    // floats of room each (field_room), so that they all lie in the level buffers the slot holds
+    static Shape both_directions(int n, size_t field) { return {2 * n, n, false, field}; }
+    static Shape windows(int n, size_t field) { return {n, n, true, field}; }
+    static Shape windows_both_directions(int n, size_t field) { return {2 * n, n, true, field}; }
+    // the coarse phase of the checked multi-window call: the one pair and its exchanged twin
+    static Shape coarse_both_directions(size_t field) { return both_directions(1, field); }
+    // both directions of the slot's real pairs at full frame (ugsm_submit_full_checked): 2 nb entries, each at its own full-frame room -- twice
+    // what the slot holds for its pairs, so the caller has grown the level buffers
+    static Shape full_both_directions(const Slot &s) { return {2 * s.nb, s.nb, false, s.lvl_stride}; }
+};
+
+// the room of one field of px pixels (3 planes) where something lies behind it -- in the level buffers, in the LR buffer, in hout: a multiple of 64 floats
+inline size_t field_room(size_t px) { return (3 * px + 63) & ~(size_t)63; }
+
+int group_pairs(int nb);  // (ugsm_policy.cpp)
+// f(Grp) for the whole batch in one launch (`batched`; group_pairs(nb) pairs each where one launch cannot hold them) or pair by pair
+template <class F>
+void for_groups(int nb, bool batched, F &&f)
+{
+    if (batched && nb > 1) {
+        const int per = group_pairs(nb);
+        for (int b0 = 0; b0 < nb; b0 += per) f(Grp{b0, std::min(per, nb - b0)});
+        return;
+    }
+    for (int b = 0; b < nb; b++) f(Grp{b, 1});
+}
+inline long long byte_diff(const void *a, const void *b) { return (long long)(reinterpret_cast<intptr_t>(a) - reinterpret_cast<intptr_t>(b)); }
+
+// The windows of a foveated call's pairs, for build_pyramids (ugsm_levels.cpp).
+// What a foveated call reads of level 0: every pair's fovea window (the level-0 crop of fovea_geometry); k_pyr_base then stores level 0
+// only where a window lies.  Full-mode calls and ugsm_submit_pyramids (window not known yet) pass none.
+// later (ugsm_submit_foveated_multi: several windows on one pair): k_pyr_base stores no level 0 at all (kPyrNoLevel0); the caller writes it
+// inside the windows afterwards with one launch of its own (enqueue_level0_windows).  Where k_pyr_base does not build the pyramid, level 0 is
+// stored whole as ever.
+struct FoveaWin {
+    int w = 0, h = 0;
+    int x0[kMaxBatch], y0[kMaxBatch];
+    bool later = false;
+};
+
+// Which full-frame levels a descent runs -- `from` down to `to` -- and what level `from` starts from (enqueue_descent, ugsm_full.cpp).  Made by
 // the four makers alone, so a start always comes with its source and its levels: the zero seed with the top level, a prior or a state with the
 // level it belongs to, and never two of them.  The levels themselves are the entry points' to have checked against the pyramid
 // (ugsm_seeded.cpp, ugsm_coarse.cpp: 0 <= to <= from < levels).
@@ -326,13 +379,129 @@ struct LevelRange {
   private:
     LevelRange(int f, int t, Start s, const float *const *src, float *const *fl) : from(f), to(t), start(s), source(src), full(fl) {}
 };
+
+// ---- ugsm_runtime.cpp: the context ---------------------------------------------------------------------------------------------------
+int level_dims(int W, int H, int levels, int *w, int *h);
+int level_iterations(int i);
+int level_smooth(int i);
+void threshold_schedule(int mi, float *out);
+void fovea_geometry(const int *w, const int *h, int F, int off_x, int off_y, FoveaGeom &g);
+// the least stride of a W-pixel row in the context's input format
+inline int input_row_bytes(const ugsm_ctx *ctx, int W) { return input_bpp(ctx->hooks.input_format) * W; }
+int ensure_level_bufs(ugsm_ctx *ctx, Slot &s, size_t lvl);
+int lr_host_ready(ugsm_ctx *ctx, Slot &s);
+int prepare_slot(ugsm_ctx *ctx, Slot &s, int W, int H, int nb = 1);
+int check_config(const ugsm_config &cfg);
+int get_slot(ugsm_ctx *ctx, int slot, Slot **out, bool enqueues = true);
+int mark_done(ugsm_ctx *ctx, Slot &s);
+
+// The frame of a ugsm_submit_* of n pairs on device buffers, whose refusals have been made: the device, body(slot, b, k) for the pairs
+// b .. b + k - 1 -- all n in one (per == n) or one after the other (per == 1: the contexts of batch_runs_pair_by_pair) --, the completion mark.
+template <class Body>
+int submit_pairs(ugsm_ctx *ctx, Slot &s, int n, int per, Body &&body)
+{
+    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
+    for (int b = 0; b < n; b += per) UCHK(body(s, b, per));
+    return mark_done(ctx, s);
+}
+// ... of a call that has nothing to refuse between the slot's own refusals and the device
+template <class Body>
+int submit_pairs(ugsm_ctx *ctx, int slot, int n, int per, Body &&body)
+{
+    Slot *s;
+    UCHK(get_slot(ctx, slot, &s));
+    return submit_pairs(ctx, *s, n, per, body);
+}
+
+// ---- ugsm_policy.cpp: which kernel and which stream a level gets ------------------------------------------------------------------------
+// The development overrides, as apply_dev_env reads them for ugsm_create and ugsm_plan_level (the defaults are the product)
+struct DevKnobs {
+    int fuse_seed = 1;       // UGSM_FUSE_SEED=0: seed every level with its own launch
+    int small_mask = 3;      // UGSM_SMALL_MASK: bit 0 = k_cost_small, bit 1 = k_smooth_small
+    int small_rh_force = 0;  // UGSM_SMALL_RH: region height of k_smooth_small whatever the level size (18, 24 or 32)
+    int force_alone = -1;    // UGSM_ALONE=1 / 0: the kernel choices of a call that has the chip to itself / that shares it, whatever is in flight
+    int two_streams = -1;    // UGSM_TWO_STREAMS=0: no call forks onto a side stream (default 1: a call that is alone does)
+    char side_prio = 0;         // UGSM_SIDE_PRIO=h|n|l|s: a side stream of its own for every slot, at that priority (s: the slot's); default: borrowed (ugsm_create)
+    char stream_prio[65] = "";  // UGSM_STREAM_PRIO: one letter per slot, h / n / l = greatest / default / least stream priority (slot_stream_priority)
+    int march_mode = 0;      // UGSM_MARCH_MODE=0,-1,-2,-3: launch_cost_march's strip-height / age-class mode (default 0: latency heights, strips by age class)
+    long long batch_max_px = 0;  // UGSM_BATCH_MAX_PIXELS: levels up to this many pixels are ONE launch for all pairs of a batched call (default kBatchMaxPixels; < 0: none)
+    int smooth_big_min = 0;  // UGSM_SMOOTH_BIG_MIN: pixel count from which K-smooth uses the 112-column tile (default 2^19)
+    int smooth_rows = 0;     // UGSM_SMOOTH_ROWS: tile height of the large levels' K-smooth (1..39), -1 / -2 = the latency / throughput rule whatever the slots
+    int march4_lo = -1, march4_hi = -1;  // UGSM_MARCH4=lo,hi: pixel range of k_cost_march4 (0,0 = never; default: march4_default_range)
+    int level0_float = 0;    // UGSM_LEVEL0_FLOAT=1: full-mode calls materialise the float level 0 as foveated calls and ugsm_submit_pyramids do
+};
+void apply_dev_env(ugsm_config &cfg, DevKnobs &k, bool set_globals);
+void set_policy(ugsm_ctx *c, const DevKnobs &k);
+bool batch_level(const ugsm_ctx *ctx, int W, int H);
+int launch_pairs(const ugsm_ctx *ctx, const Shape &sh, int W, int H);
+bool use_march4(const ugsm_ctx *ctx, int W, int H, bool alone, int pairs = 1);
+int march_rows_arg(const ugsm_ctx *ctx);
+int small_rh(const ugsm_ctx *ctx, int W, int H, bool alone, int pairs = 1);
+bool use_small_cost(const ugsm_ctx *ctx, int W, int H, bool alone, int pairs = 1);
+bool use_march(const ugsm_ctx *ctx, int W, int H, bool alone, int pairs = 1);
+bool fuse_seed(const ugsm_ctx *ctx, int W, int H, bool alone, int pairs = 1);
+int smooth_rows_for(const ugsm_ctx *ctx, int W, int H, bool alone, int pairs = 1);
+int smooth_class_for(int W, int H, int pairs);
+bool level0_direct(const ugsm_ctx *ctx, const Slot &s, int entries = 0);
+long long pyramid_stream_min(const Slot &s, bool windowed);
+bool side_stream_ok(const ugsm_ctx *ctx, const Slot &s);
+bool call_alone(ugsm_ctx *ctx, int slot);
+bool lr_full_on(const ugsm_ctx *ctx);
+bool lr_fovea_on(const ugsm_ctx *ctx);
+bool batch_runs_pair_by_pair(const ugsm_ctx *ctx);
+bool fovea_batch_runs_pair_by_pair(const ugsm_ctx *ctx);
+
+// ---- ugsm_levels.cpp: the work of one level (the comments are with the definitions) --------------------------------------------------------
+Batch copy_batch(const Shape &sh, Grp g, const Img3 *views, float *const *dsts, size_t dst_off);
+int build_pyramids(ugsm_ctx *ctx, Slot &s, int si, const uint8_t *const *rgb, int stride, float *pyr, hipStream_t stream = nullptr, const FoveaWin *win = nullptr,
+                   bool skip0 = false, int built = 0);
+int enqueue_smooth(ugsm_ctx *ctx, Slot &s, int si, const Shape &sh, float *&a, float *&b, int W, int H, int S, bool do_box, float *const *final_out = nullptr);
+int weighted_difference(ugsm_ctx *ctx, Slot &s, const float *newd3, const float *oldd3, int W, int H, float out2[2]);
+int run_level(ugsm_ctx *ctx, Slot &s, int si, const Shape &sh, const Img3 *Lv, const Img3 *Rv, int W, int H, int mi, int S, bool is_top, int m_from,
+              int m_to, float *&cur, float *&other, float *dbg8, float *const *final_out = nullptr, const SeedMap *seed = nullptr,
+              const float *A_pre = nullptr, int in = kInPlanes);
+Img3 level_view(const Slot &s, const float *pyr, int lev, int ox, int oy);
+const float *pair_pyr(const Slot &s, const Shape &sh, int side, int v);
+int enqueue_side_A(ugsm_ctx *ctx, Slot &s, int a_from, int a_top = -1);
+int enqueue_pyramids(ugsm_ctx *ctx, Slot &s, int si, const uint8_t *const *d_rgbL, const uint8_t *const *d_rgbR, int nb, int W, int H, int stride, int a_from = -1,
+                     const FoveaWin *win = nullptr, bool full = false, int entries = 0, int first = -1);
+int enqueue_pyramids(ugsm_ctx *ctx, Slot &s, int si, const uint8_t *d_rgbL, const uint8_t *d_rgbR, int W, int H, int stride, int a_from = -1,
+                     const FoveaWin *win = nullptr, bool full = false);
+bool hand_seed(ugsm_ctx *ctx, Slot &s, int si, const Shape &sh, int Ws, int Hs, int W, int H, const FoveaGeom *g, int lev, SeedMap *sm, float *&cur,
+               float *&other);
+
+// ---- ugsm_full.cpp: the full-frame calls, and a foveated call's coarse phase ----------------------------------------------------------------
 // "Match n pairs on this slot", as every batch entry point and the queue's cloud calls enqueue it: one pair, or n > 1 pairs in lockstep, over
 // the levels of `range` (null: the cold call) -- level range->to's fields into d_out
 int enqueue_match_full(ugsm_ctx *ctx, Slot &s, int si, int n, const uint8_t *const *d_rgbL, const uint8_t *const *d_rgbR, int W, int H, int stride,
                        float *const *d_out, const LevelRange *range = nullptr);
+int enqueue_full_checked(ugsm_ctx *ctx, Slot &s, int si, int n, const uint8_t *const *d_rgbL, const uint8_t *const *d_rgbR, int W, int H, int stride,
+                         float *const *d_out, float *const *d_back, float tau);
+int full_checked_check(ugsm_ctx *ctx, int n, int W, int H, int stride, float tau);
+int full_checked_bufs(ugsm_ctx *ctx, Slot &s, int n, int kept, int W, int H);
+int enqueue_fovea_coarse(ugsm_ctx *ctx, Slot &s, int si, const Shape &sh, float *const *d_state);
+
+// ---- ugsm_fovea.cpp: the foveated calls ------------------------------------------------------------------------------------------------
 int enqueue_match_foveated(ugsm_ctx *ctx, Slot &s, int si, int n, const uint8_t *const *d_rgbL, const uint8_t *const *d_rgbR, int W, int H, int stride,
                            const int *off_x, const int *off_y, float *const *state, float *const *d_stack, float *const *d_pyrL, float *const *d_pyrR);
-// ---- ... and ugsm_cloud.cpp for ugsm_create: the queue's way to the cloud work (CtxHooks, ugsm_internal.hpp) ----------------------------
+int enqueue_match_foveated_warm(ugsm_ctx *ctx, Slot &s, int si, int n, const uint8_t *const *d_rgbL, const uint8_t *const *d_rgbR, int W, int H, int stride,
+                                const int *off_x, const int *off_y, const float *const *d_prior, const int *poff_x, const int *poff_y, bool field, int start,
+                                float *const *d_stack);
+int enqueue_restrict_stack(ugsm_ctx *ctx, Slot &s, int si, int n, const int *w, const int *h, int F, const float *const *prior, const int *poff_x,
+                           const int *poff_y, bool field, const int *off_x, const int *off_y, int start, float *const *d_stack, float *work, size_t work_stride);
+int enqueue_foveated_multi(ugsm_ctx *ctx, Slot &s, int si, const uint8_t *d_rgbL, const uint8_t *d_rgbR, int W, int H, int stride, int n,
+                           const int *off_x, const int *off_y, float *state, float *const *d_stack);
+int enqueue_foveated_multi_checked(ugsm_ctx *ctx, Slot &s, int si, const uint8_t *d_rgbL, const uint8_t *d_rgbR, int W, int H, int stride, int n,
+                                   const int *off_x, const int *off_y, float *state, float *const *d_stack, float tau);
+int multi_check(ugsm_ctx *ctx, int n, int W, int H, int stride, const int *&off_x, const int *&off_y, const int *zeros, int *fw, int *fh,
+                const float *tau = nullptr);
+int multi_level_bufs(ugsm_ctx *ctx, Slot &s, int n, int W, int H, int fw, int fh);
+int multi_checked_bufs(ugsm_ctx *ctx, Slot &s, int n, int W, int H, int fw, int fh);
+
+// ---- ugsm_host.cpp: caller host memory ------------------------------------------------------------------------------------------------
+int stage_in(ugsm_ctx *ctx, Slot &s, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride);
+
+// ---- ugsm_cloud.cpp, for ugsm_create: the queue's way to the cloud work (CtxHooks, ugsm_internal.hpp) ----------------------------
 int queue_cloud_submit(ugsm_ctx *ctx, int slot, const CloudCall *call);
 int queue_cloud_finish(ugsm_ctx *ctx, int slot, int n, ugsm_cloud_result *res, void *(*staging)(void *, int, long long), void *user);
 
