@@ -9,6 +9,20 @@ import pytest
 
 from conftest import ROOT
 
+# the k_* symbol set of the shipped library and the shipped .hip files, exactly
+PRODUCT_KERNELS = {"k_cost_march", "k_cost_march4", "k_cost_small", "k_smooth_small", "k_smooth_fused", "k_pyr_base", "k_pyr_base_march", "k_blur_decimate2",
+                   "k_blur_decimate_tiled", "k_sqblur_tiled", "k_range_scan", "k_seed", "k_copy_view", "k_lr_check", "k_rgb_planes", "k_triangulate",
+                   "k_triangulate_fovea", "k_upsample_paste", "k_wdiff_rows", "k_wdiff_total",
+                   "k_restrict", "k_prolong", "k_level0_windows", "k_warp_right", "k_residual_rows", "k_residual_total", "k_upsample_paste_multi",
+                   "k_restrict_stack", "k_cloud", "k_cloud_fovea", "k_cloud_stack", "k_cloud_pairs", "k_cloud_stack_pairs", "k_cloud_multi"}
+SHIPPED_HIP = ["ugsm_kernels_aux.hip", "ugsm_kernels_cloud.hip", "ugsm_kernels_fields.hip", "ugsm_kernels_march.hip", "ugsm_kernels_march4.hip",
+               "ugsm_kernels_pyr.hip", "ugsm_kernels_small.hip", "ugsm_kernels_smooth.hip", "ugsm_kernels_warp.hip"]
+
+
+def library_kernels(path):   # the kernels' mangled names: _ZN4ugsm<len>k_name...
+    blob = open(path, "rb").read()
+    return set(name[:int(n)].decode() for n, name in re.findall(rb"_ZN4ugsm(\d+)(k_[a-z_0-9]+)", blob))
+
 
 @pytest.fixture(scope="module")
 def lib():
@@ -57,20 +71,36 @@ def test_product_library_holds_no_development_kernel(lib):
     """the one-kernel-per-stage path, round 1's LDS-tiled K-cost and the probe kernels are csrc/dev/ and in
     libugsm_dev.so only; the library a maintainer links carries only kernels a configuration of include/ugsm.h can launch, and the measured
     negatives of rounds 2-5 (k_smooth_march, k_smooth_pipe, k_iter_small, the one-thread-per-quad k_cost_fused) are in neither."""
-    def kernels(path):   # the kernels' mangled names: _ZN4ugsm<len>k_name...
-        blob = open(path, "rb").read()
-        return set(name[:int(n)].decode() for n, name in re.findall(rb"_ZN4ugsm(\d+)(k_[a-z_0-9]+)", blob))
-    prod, dev = kernels(lib.LIB_PATH), kernels(lib.DEV_LIB_PATH)
+    prod, dev = library_kernels(lib.LIB_PATH), library_kernels(lib.DEV_LIB_PATH)
     banned = {"k_cost_split", "k_poly_probe", "k_div3_probe", "k_div_probe", "k_cost_ref", "k_warp", "k_smooth_pass", "k_box", "k_sqblur_clamp", "k_blur_decimate"}
     gone = {"k_smooth_march", "k_smooth_pipe", "k_iter_small", "k_cost_fused"}
     assert not (prod & (banned | gone)), sorted(prod & (banned | gone))
     assert banned <= dev, sorted(banned - dev)
     assert not (dev & gone), sorted(dev & gone)
-    product_kernels = {"k_cost_march", "k_cost_march4", "k_cost_small", "k_smooth_small", "k_smooth_fused", "k_pyr_base", "k_pyr_base_march", "k_blur_decimate2",
-                       "k_blur_decimate_tiled", "k_sqblur_tiled", "k_range_scan", "k_seed", "k_copy_view", "k_lr_check", "k_rgb_planes", "k_triangulate",
-                       "k_triangulate_fovea", "k_upsample_paste", "k_wdiff_rows", "k_wdiff_total"}
-    assert prod == product_kernels, sorted(prod ^ product_kernels)          # the k_* symbol set of the shipped library, exactly
-    assert dev == product_kernels | banned, sorted(dev ^ (product_kernels | banned))
+    assert prod == PRODUCT_KERNELS, sorted(prod ^ PRODUCT_KERNELS)          # the k_* symbol set of the shipped library, exactly
+    assert dev == PRODUCT_KERNELS | banned, sorted(dev ^ (PRODUCT_KERNELS | banned))
+
+
+def test_a_kernel_name_is_one_operation(lib):
+    """The pins above keep development kernels out of the product; they do not ban a new name or a new file.  A new operation gets a kernel
+    of its own name -- equal to its class in the kernel statistics where it has one -- not an overload of a kernel that does something else:
+    over the shipped .hip files every __global__ name is defined in one file, and once, but for k_lr_check's two forms (one operation on a
+    field and on a stack, tests/test_lr_fovea_host.py); and every kernel class of the statistics names a kernel of the library."""
+    csrc = os.path.join(ROOT, "ug_stereomatcher_amd", "csrc")
+    where = {}
+    for f in SHIPPED_HIP:
+        for name in re.findall(r"__global__[^\n]*\bvoid (k_[a-z_0-9]+)\(", open(os.path.join(csrc, f)).read()):
+            where.setdefault(name, []).append(f)
+    assert set(where) == PRODUCT_KERNELS, sorted(set(where) ^ PRODUCT_KERNELS)
+    assert all(len(set(fs)) == 1 for fs in where.values()), {k: fs for k, fs in where.items() if len(set(fs)) > 1}
+    assert {k: len(fs) for k, fs in where.items() if len(fs) > 1} == {"k_lr_check": 2}
+    runtime = open(os.path.join(csrc, "ugsm_runtime.cpp")).read()
+    classes = re.findall(r'"([^"]+)"', re.search(r"kClassName\[2\]\[KC_COUNT\] = \{\s*\{(.*?)\}", runtime, re.S).group(1))
+    named = [c for c in classes if c.startswith("k_") and c != "k_cost_split"]   # (k_cost_split: libugsm_dev.so's, banned above)
+    assert len(named) >= 12 and "k_restrict_stack" in named
+    prod = library_kernels(lib.LIB_PATH)
+    for c in named:
+        assert any(k.startswith(c) for k in prod), c
 
 
 def test_product_kernel_sources_hold_no_development_switch():
@@ -78,7 +108,7 @@ def test_product_kernel_sources_hold_no_development_switch():
     is those same files plus csrc/dev/."""
     csrc = os.path.join(ROOT, "ug_stereomatcher_amd", "csrc")
     files = sorted(f for f in os.listdir(csrc) if f.endswith(".hip"))
-    assert files == ["ugsm_kernels_aux.hip", "ugsm_kernels_march.hip", "ugsm_kernels_march4.hip", "ugsm_kernels_pyr.hip", "ugsm_kernels_small.hip", "ugsm_kernels_smooth.hip"]
+    assert files == SHIPPED_HIP
     for f in files:
         src = open(os.path.join(csrc, f)).read()
         assert not re.search(r"^\s*#\s*(if|ifdef|ifndef|elif|else|endif)\b", src, re.M), f

@@ -367,18 +367,19 @@ def test_the_shim_compiles_with_the_two_methods(tmp_path):
     assert "m.matchCoarse(L, R, 5" in open(os.path.join(ROOT, "ros", "shim_selftest.cpp")).read()
 
 
-def test_the_prolongation_is_a_form_of_k_copy_view_and_a_class_of_the_statistics():
-    """The shipped library's kernel names are pinned (tests/test_abi_host.py), and so is the number of k_seed's forms (tests/test_seeded_host.py):
-    the prolongation is a second form of k_copy_view -- level 0's prolongation is a copy -- and `k_prolong` is its class in the kernel
-    statistics.  No LDS, no atomics, no preprocessor conditional in the kernel file."""
+def test_the_prolongation_is_k_prolong_and_a_class_of_the_statistics():
+    """The prolongation is a kernel of its own name, k_prolong (ugsm_kernels_fields.hip), which is also its class in the kernel statistics;
+    k_copy_view (ugsm_kernels_aux.hip) is the one operation of that name.  No LDS, no atomics, no preprocessor conditional in the kernel file."""
     csrc = os.path.join(ROOT, "ug_stereomatcher_amd", "csrc")
+    fields = open(os.path.join(csrc, "ugsm_kernels_fields.hip")).read()
     aux = open(os.path.join(csrc, "ugsm_kernels_aux.hip")).read()
-    assert len(re.findall(r"__global__[^\n]*\bvoid k_copy_view\(", aux)) == 2
-    assert "ProlongMap pm" in aux and "bool launch_prolong(" in aux
-    body = aux.split("void prolong_row(", 1)[1].split("void launch_seed(", 1)[0]
-    assert "ProlongMap pm" in body
+    assert len(re.findall(r"__global__[^\n]*\bvoid k_prolong\(", fields)) == 1
+    assert len(re.findall(r"__global__[^\n]*\bvoid k_copy_view\(", aux)) == 1 and aux.count("k_copy_view(") == 1
+    assert "ProlongMap pm" in fields and "bool launch_prolong(" in fields
+    body = fields.split("void prolong_row(", 1)[1].split("bool launch_prolong(", 1)[0]
+    assert "ProlongMap pm" in body and "void k_prolong(" in body
     assert "__shared__" not in body and "atomic" not in body
-    assert not re.search(r"^\s*#\s*(if|ifdef|ifndef|elif|else|endif)\b", aux, re.M)
+    assert not re.search(r"^\s*#\s*(if|ifdef|ifndef|elif|else|endif)\b", fields + aux, re.M)
     assert '"k_prolong"' in open(os.path.join(csrc, "ugsm_runtime.cpp")).read()
     assert "ugsm_coarse.cpp" in open(os.path.join(csrc, "Makefile")).read()
 

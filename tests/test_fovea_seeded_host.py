@@ -326,15 +326,16 @@ def test_the_shim_selftest_compiles(tmp_path):
                            "-o", str(tmp_path / "shim_selftest.o")])
 
 
-def test_the_starting_fields_are_a_form_of_k_upsample_paste_and_a_class_of_the_statistics():
-    """The shipped library's kernel names are pinned (tests/test_abi_host.py): the starting-field kernel is the pointwise form of k_upsample_paste,
-    whose rule it descends, and `k_restrict_stack` is its class in the kernel statistics.  No atomics in it."""
+def test_the_starting_fields_are_k_restrict_stack_and_a_class_of_the_statistics():
+    """The starting-field kernel is a kernel of its own name, k_restrict_stack, beside k_upsample_paste (ugsm_kernels_fields.hip), whose rule it
+    descends; the name is also its class in the kernel statistics, and k_upsample_paste is the one operation of that name.  No atomics in it."""
     csrc = os.path.join(ROOT, "ug_stereomatcher_amd", "csrc")
-    aux = open(os.path.join(csrc, "ugsm_kernels_aux.hip")).read()
-    assert len(re.findall(r"__global__[^\n]*\bvoid k_upsample_paste\(", aux)) == 3
-    body = aux.split("RestrictStack rs)\n{", 1)[1].split("\n}\n", 1)[0]
+    fields = open(os.path.join(csrc, "ugsm_kernels_fields.hip")).read()
+    assert len(re.findall(r"__global__[^\n]*\bvoid k_restrict_stack\(", fields)) == 1
+    assert len(re.findall(r"__global__[^\n]*\bvoid k_upsample_paste\(", fields)) == 1 and fields.count("k_upsample_paste(") == 1
+    body = fields.split("RestrictStack rs)\n{", 1)[1].split("\n}\n", 1)[0]
     assert "restrict_site(" in body and "tex_index(" in body and "atomic" not in body
-    assert "bool launch_restrict_stack(" in aux
+    assert "bool launch_restrict_stack(" in fields
     assert '"k_restrict_stack"' in open(os.path.join(csrc, "ugsm_runtime.cpp")).read()
 
 

@@ -312,13 +312,15 @@ def test_the_shim_selftest_and_the_node_compile(lib, tmp_path):
     assert r.returncode == 0, r.stderr
 
 
-def test_the_restriction_is_a_form_of_k_seed_and_a_class_of_the_statistics():
-    """The shipped library's kernel names are pinned (tests/test_abi_host.py): the restriction is a second form of k_seed, as the window form of
-    k_rgb_planes is, and `k_restrict` is its class in the kernel statistics."""
+def test_the_restriction_is_k_restrict_and_a_class_of_the_statistics():
+    """The restriction is a kernel of its own name, k_restrict (ugsm_kernels_fields.hip), which is also its class in the kernel statistics;
+    k_seed (ugsm_kernels_aux.hip) is the one operation of that name."""
     csrc = os.path.join(ROOT, "ug_stereomatcher_amd", "csrc")
+    fields = open(os.path.join(csrc, "ugsm_kernels_fields.hip")).read()
     aux = open(os.path.join(csrc, "ugsm_kernels_aux.hip")).read()
-    assert len(re.findall(r"__global__[^\n]*\bvoid k_seed\(", aux)) == 2
-    assert "RestrictMap rm" in aux and "void launch_restrict(" in aux
+    assert len(re.findall(r"__global__[^\n]*\bvoid k_restrict\(", fields)) == 1
+    assert len(re.findall(r"__global__[^\n]*\bvoid k_seed\(", aux)) == 1 and aux.count("k_seed(") == 1
+    assert "RestrictMap rm" in fields and "void launch_restrict(" in fields
     assert '"k_restrict"' in open(os.path.join(csrc, "ugsm_runtime.cpp")).read()
 
 

@@ -1,5 +1,5 @@
-import sys, time, numpy as np
-sys.path.insert(0, '/root/repo')
+import os, sys, time, numpy as np
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from ug_stereomatcher_amd import _lib, synth
 W, H = 4928, 3264

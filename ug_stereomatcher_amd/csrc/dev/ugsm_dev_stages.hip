@@ -9,9 +9,6 @@
 
 namespace ugsm {
 
-static inline dim3 grid2(int W, int H, int z = 1) { return dim3((W + 255) / 256, H, z); }
-
-
 // --------------------------------------------------------------------------------------
 // MatchGPULib.cpp:1071-1096 + MatchLib.cu:71-156,195-278,311-339.
 // dst[x,y] = blur(src)[floor((x+.5f)*sf), floor((y+.5f)*sf)], blur = zero-padded row conv

@@ -1,6 +1,6 @@
 // ugsm_cloud.cpp -- row f-1 of the runtime: triangulation and the coloured point clouds (getPointCloud.cpp), on the slots of ugsm_runtime.cpp.
 // The fovea forms' geometry and the coverage rule of the merged clouds (host only), the slot-level entry points behind one preamble
-// (cloud_begin), and the queue's cloud calls (CtxHooks::cloud_submit / cloud_finish).  Every form's kernel is cloud_tile (ugsm_kernels_aux.hip).
+// (cloud_begin), and the queue's cloud calls (CtxHooks::cloud_submit / cloud_finish).  Every cloud kernel is cloud_tile (ugsm_kernels_cloud.hip).
 #include "ugsm_slot.hpp"
 
 #include <algorithm>

@@ -34,6 +34,9 @@ __device__ __forceinline__ T *shifted(T *p, long long bytes)
 
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
+// the grid of the one-thread-per-pixel kernels: 256 columns a workgroup, a row each (host)
+static inline dim3 grid2(int W, int H, int z = 1) { return dim3((W + 255) / 256, H, z); }
+
 // The byte layouts of an input image the image-reading kernels are instantiated for: the public formats (ugsm.h UGSM_INPUT_*, same
 // numbers) and, for the two four-byte formats, a form that reads a pixel with one 32-bit load -- the host picks it when the image's base
 // pointer and its stride are 4-byte aligned (a caller's device pointer need not be).  Every layout reads as its conversion to rgb8 would:

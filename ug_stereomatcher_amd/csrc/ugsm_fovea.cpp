@@ -330,7 +330,7 @@ static int enqueue_level0_windows(ugsm_ctx *ctx, Slot &s, int si, const uint8_t 
 
 // n fovea windows on ONE pair (ugsm_submit_foveated_multi): what does not depend on the window runs once, the rest in lockstep.
 //   - the pyramids of one pair, as a lone foveated call builds them (side stream and A planes of levels F-1 .. top included), but with no
-//     level 0 (FoveaWin::later); one launch then writes level 0 of both images inside the n windows (k_rgb_planes' window form).  Pyramids
+//     level 0 (FoveaWin::later); one launch then writes level 0 of both images inside the n windows (k_level0_windows).  Pyramids
 //     that k_pyr_base does not build (fewer than three levels, kernel_path 1) hold level 0 whole and skip that launch;
 //   - the coarse phase once, its field into `state`;
 //   - the fine phase on a shape of n windows that all read pair 0's pyramids (Shape::one_pair, pair_pyr), start from the one state and

@@ -62,9 +62,9 @@ struct Batch {
     long long out[kMaxBatch];  // pair b's output: nd3 / o3 / dst (a slot buffer, or the caller's)
 };
 
-// ---- plain per-pixel kernels (ugsm_kernels_aux.hip) ---------------------------------------
+// ---- plain per-pixel kernels (ugsm_kernels_aux.hip, _fields.hip, _cloud.hip, _warp.hip) ----
 void launch_seed(hipStream_t st, const float *src3, int Ws, int Hs, float *dst3, int Wd, int Hd, int cx, int cy, const Batch *bt = nullptr);
-// The restriction form of k_seed (ugsm_submit_full_seeded): level `level`'s starting field dst3 (w x h, the level's size) from the
+// The restriction, k_restrict (ugsm_submit_full_seeded): level `level`'s starting field dst3 (w x h, the level's size) from the
 // full-resolution field src3 (W x H).  Batched: pair b reads src3 + bt->in[b] bytes and writes dst3 + bt->out[b] bytes.
 struct RestrictMap {
     int W, H, w, h, k, odd;  // k = level / 2, odd = level & 1
@@ -72,7 +72,7 @@ struct RestrictMap {
 };
 void launch_restrict(hipStream_t st, const float *src3, int W, int H, int level, float *dst3, int w, int h, const Batch *bt = nullptr);
 void launch_copy_view(hipStream_t st, Img3 src, int W, int H, float *dst, size_t dst_plane, int dst_pitch, const Batch *bt = nullptr);
-// The prolongation form of k_copy_view (ugsm_submit_full_coarse, ugsm_stage_prolong): the field src3 of level `level` (3 planes of w[level] x
+// The prolongation, k_prolong (ugsm_submit_full_coarse, ugsm_stage_prolong): the field src3 of level `level` (3 planes of w[level] x
 // h[level]) at full resolution in dst3 (3 planes of w[0] x h[0]), as `level` steps of k_seed give it, in one launch.  w, h: the sizes of the
 // levels 0 .. level (ugsm_level_dims); every level's own size takes part (its clamp).  Batched: pair b reads src3 + bt->in[b] bytes and
 // writes dst3 + bt->out[b] bytes.  False (nothing launched): a level or a size the kernel's bounds do not cover.
@@ -85,7 +85,7 @@ struct ProlongMap {
 bool launch_prolong(hipStream_t st, const float *src3, const int *w, const int *h, int level, float *dst3, const Batch *bt = nullptr);
 // rgb8 -> planar float level 0 (MatchGPULib.cpp:332-338) where k_pyr_base does not apply: pyramids of fewer than three levels, kernel_path 1
 void launch_rgb_planes(hipStream_t st, const uint8_t *rgb, int stride, int W, int H, float *planes, int fmt = 0);
-// Level 0 of one pair inside n fovea windows of w x h level-0 pixels at (x0[k], y0[k]) -- the window form of k_rgb_planes, one launch for both
+// Level 0 of one pair inside n fovea windows of w x h level-0 pixels at (x0[k], y0[k]) -- k_level0_windows, one launch for both
 // images (ugsm_submit_foveated_multi: the pyramid pass stores no level 0 there, kPyrNoLevel0).  planesL / planesR: the two level-0 planes
 // (W x H each).  The four-byte formats take their word loads when both images and the stride are 4-byte aligned.  False (nothing launched): a
 // window that leaves the frame.
@@ -112,7 +112,7 @@ void launch_lr_check(hipStream_t st, float *stack0, const float *back0, int fovW
 void launch_triangulate(hipStream_t st, const float *dispx, const float *dispy, int W, int H, const double *P1, const double *P2, float *xyz);
 void launch_triangulate_fovea(hipStream_t st, const float *stackx, const float *stacky, int fovW, int fovH, int src_level, int left_margin,
                               int upper_margin, float scale, const double *P1, const double *P2, float *xyz);
-// SURVEY 8f row f-1, the coloured point cloud (ugsm_point_cloud[_fovea]): the forms kTriCloudCount / kTriCloud of k_triangulate[_fovea].
+// SURVEY 8f row f-1, the coloured point cloud (ugsm_point_cloud[_fovea]): k_cloud[_fovea]<kTriCloudCount / kTriCloud>.
 // The sampled grid is wc x hc points (point (ci, cj) = pixel (ci * s, cj * s) of the planes); tiles of 32 columns x 64 rows of it.
 struct CloudArgs {
     const float *dx, *dy, *conf;  // pw x ph row-major planes (the fovea form: level src_level of the stacks); conf may be null
@@ -130,7 +130,7 @@ struct CloudArgs {
     long long cap;
     long long *count;
 };
-// the resized cloud (ugsm_point_cloud_resized[_fovea]): the forms kTriResizedCount / kTriResized, whose grid is the resized map
+// the resized cloud (ugsm_point_cloud_resized[_fovea]): k_cloud[_fovea]<kTriResizedCount / kTriResized>, whose grid is the resized map
 // (CloudArgs.wc x hc = (int)(pw * factor) x (int)(ph * factor), s 1): point (ci, cj) = pixel (ci, cj) of it
 struct CloudResize {
     double scale_x, scale_y;  // cv::resize's 1. / ((double)wc / pw), 1. / ((double)hc / ph)
@@ -138,7 +138,7 @@ struct CloudResize {
     int same_size;            // wc == pw && hc == ph: cv::resize copies, Z is the pixel's own
     int colour_mapped;        // the fovea form: the colour at the mapped pixel (as ugsm_point_cloud_fovea) rather than at (xx, yy)
 };
-// the merged cloud of the whole fovea stack (ugsm_point_cloud_fovea_all): the forms kTriStackCount / kTriStack, whose grid runs over
+// the merged cloud of the whole fovea stack (ugsm_point_cloud_fovea_all): k_cloud_stack<kTriStackCount / kTriStack>, whose grid runs over
 // F * cloud_strips(wc) strips (level = strip / strips).  CloudArgs.dx / dy / conf are the stacks (level 0's planes); a workgroup takes its
 // level's planes, mapping and covered rectangle from its row of the table.  A pixel of level k >= 1 whose footprint lies wholly inside
 // level k-1's window is covered and left out (include/ugsm.h); the rule is separable and monotone, so the host hands over one interval
@@ -163,17 +163,17 @@ int cloud_chunks(int hc);
 void launch_point_cloud(hipStream_t st, const CloudArgs &args, bool fovea, const double *P1, const double *P2, const CloudResize *rz = nullptr);
 // the same for the merged cloud of the stack; args.cnt (compact): (F * wc) * nchunk counts, F * wc column totals, F * strips strip totals
 void launch_point_cloud_stack(hipStream_t st, const CloudArgs &args, const CloudStack &sk, const double *P1, const double *P2);
-// The clouds of the n pairs of a queue call in ONE launch (compact: two), the pair = blockIdx.z: overloads of the same forms that read their
+// The clouds of the n pairs of a queue call in ONE launch (compact: two), the pair = blockIdx.z: k_cloud_pairs / k_cloud_stack_pairs read their
 // pair's row of a table in DEVICE memory instead of kernel arguments (sixteen CloudStacks do not fit there).  Every row holds the pair's
 // whole CloudArgs -- its planes or stack, image, its own region of the count buffer (zeroed before the launch), points, cap and count --
-// and, for the stack forms, its own CloudStack: windows at different offsets have different margins and covered rectangles.  The pairs
+// and, for k_cloud_stack_pairs, its own CloudStack: windows at different offsets have different margins and covered rectangles.  The pairs
 // share everything that shapes the grid (pw, ph, s, compact; F and strips), which `shape` (a host copy of any row) gives.
 struct CloudPair {
     CloudArgs a;
     CloudStack sk;
 };
 void launch_point_cloud_batch(hipStream_t st, const CloudPair *d_table, int n, const CloudPair &shape, bool stack, const double *P1, const double *P2);
-// The merged cloud of the stacks of n windows of ONE pair (ugsm_point_cloud_fovea_multi): the forms kTriMultiCount / kTriMulti, whose grid
+// The merged cloud of the stacks of n windows of ONE pair (ugsm_point_cloud_fovea_multi): k_cloud_multi<kTriMultiCount / kTriMulti>, whose grid
 // runs over E * cloud_strips(wc) strips, E = (F-1) n + 1 entries (entry = strip / strips).  A workgroup takes its entry's row of a table
 // in DEVICE memory (E reaches 97 and a row holds up to 31 rectangles: no room among the kernel arguments): the entry's planes and mapping,
 // the rectangles of its sampled grid that the rule across windows leaves out (include/ugsm.h; a union, so they may overlap), and what the
@@ -214,7 +214,7 @@ struct PasteWindows {
 };
 void launch_upsample_paste_multi(hipStream_t st, const float *src3, int W, int H, float *dst3, int W2, int H2, const float *fov0, size_t fov_plane,
                                  int fovW, int fovH, const PasteWindows &pw);
-// The POINTWISE form of the same kernel (k_restrict_stack in the statistics; the warm foveated call, ugsm_submit_foveated_warm): the starting
+// The same rule POINTWISE, k_restrict_stack (the warm foveated call, ugsm_submit_foveated_warm): the starting
 // fields of the fovea levels s .. F-1 of n entries from a prior each, in ONE launch, grid.z = entry x (F - s) + (level - s).  The field of
 // level k is the fw x fh crop, at the NEW window's origin at level k, of the restriction (RestrictMap, above) to level k of the full-resolution
 // field that ugsm_reconstruct_full gives for the prior stack -- computed per target pixel: the pixel's level-0 site, then the paste rule
@@ -243,7 +243,7 @@ struct RestrictStack {
 bool launch_restrict_stack(hipStream_t st, const float *prior0, float *stack0, float *work0, RestrictStack rs, const RestrictStackRow *rows);
 // S_dx, S_dy, C of weightedDifference (MatchGPULib.cpp:1336-1437) into out3; rowsum = 3*H doubles of scratch
 void launch_weighted_difference(hipStream_t st, const float *newd3, const float *oldd3, int W, int H, double *rowsum, double *out3);
-// MatchGPULib::warpRightImage (MatchGPULib.cpp:1445-1518, kernel warpAbyB MatchLib.cu:499-549) -- the warp form of k_rgb_planes:
+// MatchGPULib::warpRightImage (MatchGPULib.cpp:1445-1518, kernel warpAbyB MatchLib.cu:499-549) -- k_warp_right:
 //   dst[iy][ix] = src[tex_index(((float)iy + 0.5f) + dy[iy][ix], H)][tex_index(((float)ix + 0.5f) + dx[iy][ix], W)], the value stored as fetched.
 // in == kInPlanes: src is `planes` float planes of W x H, dst as many, the grid's z the plane; plane z is warped by field z / per_field of
 // dx / dy (fields W x H apart): per_field = planes for one field for all of them, 3 for a fovea stack (z = 3 x level + channel).
@@ -256,7 +256,7 @@ struct WarpArgs {
     float *dst;
 };
 void launch_warp(hipStream_t st, const WarpArgs &a, int in);
-// The photometric residual of a match -- forms of k_wdiff_rows / k_wdiff_total: per channel c, t = fabsf(L_c - warp(R_c)) in float, t = t * conf in
+// The photometric residual of a match -- k_residual_rows / k_residual_total: per channel c, t = fabsf(L_c - warp(R_c)) in float, t = t * conf in
 // float, S_c = sum(t), C = sum(conf) (conf null: 1.0f), binary64 sums in row f-4's fixed order.  in == kInPlanes: L and R are `levels` levels of
 // [channel][row] float planes (a fovea pyramid stack), dx / dy / conf as many levels of W x H; an input format (UGSM_INPUT_*): the two 8-bit images, levels == 1.
 // rowsum: levels x H x 4 doubles of scratch; sums: levels x 4 doubles [S0, S1, S2, C].  Two launches for all levels.

@@ -1,7 +1,7 @@
 // ugsm_warp.cpp -- the warped right image (MatchGPULib::warpRightImage, MatchGPULib.cpp:1445-1518) and the photometric residual of a match
 // (row f-4's rule, weightedDifference :1336-1437, on a left plane and the warped right plane), on the slots of ugsm_runtime.cpp.  Five
-// slot-level entry points behind one preamble (warp_begin); the kernels are the warp form of k_rgb_planes and the residual forms of
-// k_wdiff_rows / k_wdiff_total (ugsm_kernels_aux.hip).  Definitions: include/ugsm.h.
+// slot-level entry points behind one preamble (warp_begin); the kernels are k_warp_right and k_residual_rows /
+// k_residual_total (ugsm_kernels_warp.hip).  Definitions: include/ugsm.h.
 #include "ugsm_slot.hpp"
 
 using namespace ugsm;
