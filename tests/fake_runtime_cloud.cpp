@@ -13,6 +13,7 @@ struct FakeCloud {
     int fovea, managed, n, finishes, step;
     ugsm_queue_cloud spec;
     const uint8_t *L[UGSM_MAX_BATCH];
+    CloudJob job[UGSM_MAX_BATCH];  // as handed over (W, H, stride and the format in force are in the call's own record: ugsm_fake_call_args)
 };
 struct FakeCloudState {
     ugsm_ctx *ctx;
@@ -30,8 +31,9 @@ static FakeCloudState *state_of(const ugsm_ctx *ctx)
 static int fake_cloud_submit(ugsm_ctx *ctx, int slot, const CloudCall *call)
 {
     FakeCloudState *fs = state_of(ctx);
-    const uint8_t *L[UGSM_MAX_BATCH];
-    for (int b = 0; b < call->n; b++) L[b] = call->job[b].L;
+    const uint8_t *L[UGSM_MAX_BATCH], *R[UGSM_MAX_BATCH];
+    int ox[UGSM_MAX_BATCH], oy[UGSM_MAX_BATCH];
+    float *out[UGSM_MAX_BATCH];
     FakeCloud fc{};
     fc.call = (long long)ctx->calls.size();
     fc.fovea = call->fovea;
@@ -39,9 +41,17 @@ static int fake_cloud_submit(ugsm_ctx *ctx, int slot, const CloudCall *call)
     fc.n = call->n;
     fc.step = call->spec->params.format == UGSM_CLOUD_PCL32 ? 32 : 16;
     fc.spec = *call->spec;
-    for (int b = 0; b < call->n; b++) fc.L[b] = L[b];
+    for (int b = 0; b < call->n; b++) {
+        const CloudJob &j = fc.job[b] = call->job[b];
+        fc.L[b] = L[b] = j.L;
+        R[b] = j.R;
+        ox[b] = j.off_x;
+        oy[b] = j.off_y;
+        out[b] = call->managed ? j.planes[0] : j.out;
+    }
     fs->clouds.push_back(fc);  // (may throw, like the recorder's own push_back: the runtime ran out of memory before anything ran)
-    const int st = submit(ctx, slot, call->n, call->fovea, call->managed ? 1 : 0, L);
+    const int st = submit(ctx, slot, SubmitArgs{E_CLOUD | (call->fovea ? E_FOVEA : 0) | (call->managed ? E_HOST : 0), call->n, call->W, call->H, call->stride,
+                                                L, R, ox, oy, {out, nullptr, nullptr, nullptr, nullptr}});
     if (ctx->calls.size() != (size_t)fc.call + 1) fs->clouds.pop_back();
     return st;
 }
@@ -136,6 +146,27 @@ int ugsm_fake_cloud_call(const ugsm_ctx *c, long long k, int *out8, double *p1_0
             const int v[8] = {f.fovea, f.managed, f.n, f.finishes, f.spec.want_planes, f.spec.params.sampling, f.spec.params.format, f.spec.params.compact};
             memcpy(out8, v, sizeof v);
             *p1_0 = f.spec.P1[0];
+            return 0;
+        }
+    return -1;
+}
+// the CloudJob of every pair of cloud call k, twelve words per pair: L, R, off_x, off_y, out, planes[0 .. 2], points, cap, count, level_counts;
+// *reserved: the recorded spec's `reserved`; -1 if call k was no cloud call
+int ugsm_fake_cloud_jobs(const ugsm_ctx *c, long long k, long long *jobs, int *reserved)
+{
+    const FakeCloudState *fs = state_of(c);
+    if (!fs) return -1;
+    for (const FakeCloud &f : fs->clouds)
+        if (f.call == k) {
+            for (int b = 0; b < f.n; b++) {
+                const CloudJob &j = f.job[b];
+                const void *p[] = {j.L, j.R, nullptr, nullptr, j.out, j.planes[0], j.planes[1], j.planes[2], j.points, nullptr, j.count, j.level_counts};
+                for (int i = 0; i < 12; i++) jobs[12 * b + i] = (long long)(uintptr_t)p[i];
+                jobs[12 * b + 2] = j.off_x;
+                jobs[12 * b + 3] = j.off_y;
+                jobs[12 * b + 9] = j.cap;
+            }
+            *reserved = f.spec.reserved;
             return 0;
         }
     return -1;

@@ -10,7 +10,9 @@ What the header promises and this file checks:
   * ugsm_done_cloud gives the cloud of the pair just reported and UGSM_ERR_STATE otherwise; the staging is not handed on before the next
     ugsm_next_done;
   * a failed submit or finish hook reports every pair of the call once with that status; host allocation failures lose no pair;
-  * bad arguments are rejected and leave the queue as it was;
+  * bad arguments are rejected and leave the queue as it was -- for all ten ugsm_enqueue_*, every refusal with its status, its exact
+    message and its place in the order of the refusals;
+  * the hook receives every CloudJob field of every pair as it was enqueued, and the spec with `reserved` cleared;
   * the queue has no link-time dependency on the cloud work: it still builds and loads (RTLD_NOW) against tests/fake_runtime.cpp."""
 import ctypes as C
 import os
@@ -69,12 +71,20 @@ def fq(tmp_path_factory):
     lib.ugsm_fake_calls.restype = ll
     lib.ugsm_fake_call.argtypes = [vp, ll, C.POINTER(i * 7), C.POINTER(vp * 16)]
     lib.ugsm_fake_cloud_call.argtypes = [vp, ll, C.POINTER(i * 8), C.POINTER(C.c_double)]
+    lib.ugsm_fake_call_args.argtypes = [vp, ll, C.POINTER(ll * 7), C.POINTER(ll * (9 * 16))]
+    lib.ugsm_fake_cloud_jobs.argtypes = [vp, ll, C.POINTER(ll * (12 * 16)), C.POINTER(i)]
+    lib.ugsm_fake_unpinned.argtypes = [vp]
+    lib.ugsm_fake_unpinned.restype = None
     lib.ugsm_fake_violations.argtypes = [vp]
     lib.ugsm_fake_fail_alloc_after.argtypes = [ll]
     lib.ugsm_fake_fail_alloc_after.restype = None
     lib.ugsm_fake_allocs.restype = ll
     lib.ugsm_enqueue_full.argtypes = [vp, vp, vp, i, i, i, vp, u64]
+    lib.ugsm_enqueue_foveated.argtypes = [vp, vp, vp, i, i, i, i, i, vp, vp, vp, u64]
+    lib.ugsm_enqueue_full_host.argtypes = [vp, vp, vp, i, i, i, vp, vp, vp, u64]
+    lib.ugsm_enqueue_foveated_host.argtypes = [vp, vp, vp, i, i, i, i, i, vp, vp, vp, vp, vp, u64]
     lib.ugsm_enqueue_full_managed.argtypes = [vp, vp, vp, i, i, i, u64]
+    lib.ugsm_enqueue_foveated_managed.argtypes = [vp, vp, vp, i, i, i, i, i, i, u64]
     lib.ugsm_enqueue_full_cloud.argtypes = [vp, vp, vp, i, i, i, vp, qc, vp, ll, vp, u64]
     lib.ugsm_enqueue_foveated_cloud.argtypes = [vp, vp, vp, i, i, i, i, i, vp, qc, vp, ll, vp, vp, u64]
     lib.ugsm_enqueue_full_cloud_managed.argtypes = [vp, vp, vp, i, i, i, qc, u64]
@@ -464,3 +474,251 @@ def test_the_queue_still_links_against_the_plain_fake(tmp_path):
     lib = C.CDLL(so, mode=os.RTLD_NOW)
     for name in ("ugsm_enqueue_full_cloud", "ugsm_enqueue_foveated_cloud", "ugsm_enqueue_full_cloud_managed", "ugsm_enqueue_foveated_cloud_managed", "ugsm_done_cloud"):
         assert hasattr(lib, name), name
+
+
+# ---- what a cloud call carries: every CloudJob field of every pair ---------------------------------------------------------------------
+def _cloud_jobs(fq, ctx, k):
+    head, pairs, jobs, reserved = (C.c_longlong * 7)(), (C.c_longlong * (9 * 16))(), (C.c_longlong * (12 * 16))(), C.c_int(-1)
+    assert fq.ugsm_fake_call_args(ctx, k, C.byref(head), C.byref(pairs)) == 0
+    assert fq.ugsm_fake_cloud_jobs(ctx, k, C.byref(jobs), C.byref(reserved)) == 0
+    rec = dict(zip(("entry", "W", "H", "stride", "fmt", "pyr_arrays", "n"), head))
+    rec["reserved"] = reserved.value
+    rec["jobs"] = [list(jobs[12 * b:12 * b + 12]) for b in range(rec["n"])]
+    return rec
+
+
+def test_cloud_marshalling(fq):
+    """Every cloud call the hook receives carries exactly what its pairs were enqueued with -- every CloudJob field, in enqueue order, the
+    call's size and stride, the spec with `reserved` cleared -- for the four cloud kinds in calls of one pair and of several; a managed
+    pair's images, planes and completion are its staging buffer's carve-up."""
+    ctx = fq.ugsm_fake_create_cloud(2, 3, 8, 4, 1)
+    want, images, done, staged = {}, {}, [], {}
+    W, H = 64, 32
+
+    def enqueue(kind, want_planes=0):
+        tag = len(want)
+        sp = spec(want_planes=want_planes, max_points=50)
+        sp.reserved = 7
+        p = BASE + 4096 * tag
+        L, R, out, points, count, lc = p, p + 64, p + 128, p + 256, p + 512, p + 768
+        ox, oy, cap = 3 + tag, 1000 + tag, 5000 + tag
+        fovea, managed = kind in ("fcloud", "mfcloud"), kind in ("mcloud", "mfcloud")
+        w = dict(kind=kind, fovea=fovea, managed=managed, want_planes=want_planes, stride=3 * W + 8, ox=ox if fovea else 0, oy=oy if fovea else 0)
+        if kind == "cloud":
+            st = fq.ugsm_enqueue_full_cloud(ctx, L, R, W, H, 3 * W + 8, out, C.byref(sp), points, cap, count, tag)
+            w["job"] = [L, R, 0, 0, out, 0, 0, 0, points, cap, count, 0]
+        elif kind == "fcloud":
+            st = fq.ugsm_enqueue_foveated_cloud(ctx, L, R, W, H, 3 * W + 8, ox, oy, out, C.byref(sp), points, cap, count, lc, tag)
+            w["job"] = [L, R, ox, oy, out, 0, 0, 0, points, cap, count, lc]
+        else:
+            img = np.random.RandomState(tag).randint(0, 256, (2, H, 3 * W + 8)).astype(np.uint8)
+            img[0].reshape(-1)[:4].view(np.uint32)[0] = tag                 # (the fake takes the cloud's count from the left image's first word)
+            images[tag] = [img[s][:, :3 * W].tobytes() for s in range(2)]
+            w["stride"] = 3 * W
+            if kind == "mcloud":
+                st = fq.ugsm_enqueue_full_cloud_managed(ctx, img[0].ctypes.data, img[1].ctypes.data, W, H, 3 * W + 8, C.byref(sp), tag)
+            else:
+                st = fq.ugsm_enqueue_foveated_cloud_managed(ctx, img[0].ctypes.data, img[1].ctypes.data, W, H, 3 * W + 8, ox, oy, C.byref(sp), tag)
+            img[:] = 0
+        sp.reserved, sp.want_planes = 9, 1 - want_planes                   # (the spec was copied at enqueue)
+        assert st == OK, (kind, st, fq.ugsm_last_error(ctx))
+        want[tag] = w
+
+    def drain():
+        while True:
+            c = Completion()
+            st = fq.ugsm_next_done(ctx, C.byref(c), 1)
+            if st == EMPTY:
+                return
+            assert st == OK and c.status == OK, (st, c.status)
+            tag, k = int(c.tag), int(c.call_index)
+            b = sum(1 for _, kk, _ in done if kk == k)
+            done.append((tag, k, [C.cast(c.result[j], C.c_void_p).value or 0 for j in range(5)]))
+            if want[tag]["managed"]:                                       # the staging is lent until the next ugsm_next_done: look now
+                job = _cloud_jobs(fq, ctx, k)["jobs"][b]
+                staged[tag] = [C.string_at(job[0], 3 * W * H), C.string_at(job[1], 3 * W * H)]
+
+    try:
+        # (the first call after idle or a flush takes two pairs, the later ones three)
+        enqueue("cloud"), enqueue("cloud"), enqueue("cloud"), enqueue("fcloud"), enqueue("fcloud"), enqueue("fcloud"), drain()
+        enqueue("fcloud"), drain()
+        enqueue("mcloud", 1), enqueue("mcloud", 1), enqueue("mcloud", 1), enqueue("mcloud", 0), enqueue("mcloud", 0)
+        enqueue("mfcloud", 1), enqueue("mfcloud", 1), enqueue("mfcloud", 1), drain()
+        enqueue("mfcloud", 0), drain()
+        assert fq.ugsm_fake_violations(ctx) == 0
+        assert [t for t, _, _ in done] == list(range(len(want)))
+        ncalls = fq.ugsm_fake_calls(ctx)
+        assert sorted({k for _, k, _ in done}) == list(range(ncalls))
+        seen = set()
+        for k in range(ncalls):
+            rec = _cloud_jobs(fq, ctx, k)
+            tags = [t for t, kk, _ in done if kk == k]
+            results = [r for _, kk, r in done if kk == k]
+            n, w0 = rec["n"], want[tags[0]]
+            assert n == len(tags) and tags == list(range(tags[0], tags[0] + n)), (k, rec, tags)
+            assert rec["entry"] == 8 + (2 if w0["fovea"] else 0) + (4 if w0["managed"] else 0), (k, rec)
+            assert (rec["W"], rec["H"], rec["stride"], rec["fmt"], rec["reserved"]) == (W, H, w0["stride"], 0, 0), (k, rec)
+            v, p1 = (C.c_int * 8)(), C.c_double()
+            assert fq.ugsm_fake_cloud_call(ctx, k, C.byref(v), C.byref(p1)) == 0
+            assert (v[0], v[1], v[2], v[4]) == (int(w0["fovea"]), int(w0["managed"]), n, w0["want_planes"]), (k, list(v))
+            for t, job, res in zip(tags, rec["jobs"], results):
+                w = want[t]
+                assert (w["kind"], w["want_planes"]) == (w0["kind"], w0["want_planes"])
+                if not w["managed"]:
+                    assert job == w["job"], (k, t, job, w["job"])
+                    assert res == [0] * 5
+                else:
+                    img = (3 * W * H + 255) & ~255
+                    plane = (4 * (W // 8) * (H // 8) if w["fovea"] else W * H) * 4
+                    L = job[0]
+                    planes = [res[0], res[0] + plane, res[0] + 2 * plane] if w["want_planes"] else [0, 0, 0]
+                    assert L and bool(res[0]) == bool(w["want_planes"])
+                    assert job == [L, L + img, w["ox"], w["oy"], 0] + planes + [0, 0, 0, 0], (k, t, job)
+                    assert res == planes + [0, 0], (t, res)
+                    assert staged[t] == images[t], (k, t)
+                seen.add((w["kind"], n > 1))
+        assert seen == {(kind, many) for kind in ("cloud", "fcloud", "mcloud", "mfcloud") for many in (False, True)}, seen
+    finally:
+        fq.ugsm_fake_destroy_cloud(ctx)
+
+
+# ---- the refusals of all ten entry points, in their order ---------------------------------------------------------------------------------
+SIZE_MISMATCH = 2
+M_NULL = "ugsm_enqueue_%s: null buffer"
+M_NULL_MANAGED = "ugsm_enqueue_*_managed: null image"
+M_SIZE = "ugsm_enqueue_*: bad image size for the context's pyramid"
+M_STRIDE = "ugsm_enqueue_*: stride < bytes per pixel of the input format * W"
+M_FOVEA = "ugsm_enqueue_foveated*: the context has no fovea levels"
+M_PINNED = ("ugsm_enqueue_%s: every host buffer must be page-locked (ugsm_host_alloc, hipHostMalloc or hipHostRegister); "
+            "ugsm_enqueue_%s_managed takes any memory")
+M_SPEC = "ugsm_enqueue_*_cloud*: null spec"
+M_SAMPLING = "ugsm_enqueue_*_cloud*: sampling < 1 or an unknown record format"
+M_NAN = "ugsm_enqueue_*_cloud*: a NaN min_conf / z_min / z_max, or z_min > z_max"
+M_MAX_POINTS = "ugsm_enqueue_*_cloud*: max_points < 0"
+M_BUFFERS = "ugsm_enqueue_*_cloud: a null or misaligned cloud buffer, or cap_points < 0"
+M_NO_CLOUDS = "ugsm_enqueue_*_cloud*: this runtime makes no clouds"
+M_FULL = ("ugsm_enqueue_*: (slots + 1) x batch pairs are outstanding and completions wait to be fetched: "
+          "call ugsm_next_done first")
+
+# name -> (the call, the result pointers it requires)
+ENTRY_POINTS = {
+    "full": (lambda q, c, a: q.ugsm_enqueue_full(c, a.L, a.R, a.W, a.H, a.stride, a.o0, a.tag), ["o0"]),
+    "foveated": (lambda q, c, a: q.ugsm_enqueue_foveated(c, a.L, a.R, a.W, a.H, a.stride, a.ox, a.oy, a.o0, a.pl, a.pr, a.tag), ["o0"]),
+    "full_host": (lambda q, c, a: q.ugsm_enqueue_full_host(c, a.L, a.R, a.W, a.H, a.stride, a.o0, a.o1, a.o2, a.tag), ["o0", "o1", "o2"]),
+    "foveated_host": (lambda q, c, a: q.ugsm_enqueue_foveated_host(c, a.L, a.R, a.W, a.H, a.stride, a.ox, a.oy, a.o0, a.o1, a.o2, a.pl, a.pr, a.tag),
+                      ["o0", "o1", "o2"]),
+    "full_managed": (lambda q, c, a: q.ugsm_enqueue_full_managed(c, a.L, a.R, a.W, a.H, a.stride, a.tag), []),
+    "foveated_managed": (lambda q, c, a: q.ugsm_enqueue_foveated_managed(c, a.L, a.R, a.W, a.H, a.stride, a.ox, a.oy, 1, a.tag), []),
+    "full_cloud": (lambda q, c, a: q.ugsm_enqueue_full_cloud(c, a.L, a.R, a.W, a.H, a.stride, a.o0, a.spec, a.points, a.cap, a.count, a.tag), ["o0"]),
+    "foveated_cloud": (lambda q, c, a: q.ugsm_enqueue_foveated_cloud(c, a.L, a.R, a.W, a.H, a.stride, a.ox, a.oy, a.o0, a.spec, a.points, a.cap, a.count,
+                                                                    a.lc, a.tag), ["o0"]),
+    "full_cloud_managed": (lambda q, c, a: q.ugsm_enqueue_full_cloud_managed(c, a.L, a.R, a.W, a.H, a.stride, a.spec, a.tag), []),
+    "foveated_cloud_managed": (lambda q, c, a: q.ugsm_enqueue_foveated_cloud_managed(c, a.L, a.R, a.W, a.H, a.stride, a.ox, a.oy, a.spec, a.tag), []),
+}
+
+
+def refusals(name):
+    """(what, context, arguments that differ from a good call, status, message) for entry point `name`, several refusals at once where the
+    order between them is to be pinned: the one named first in `what` wins."""
+    fovea, managed, cloud = "foveated" in name, name.endswith("managed"), "cloud" in name
+    host, device_cloud = name.endswith("host"), cloud and not managed
+    null = M_NULL_MANAGED if managed else M_NULL % name
+    small, tiny = dict(stride=3 * 64 - 1), dict(W=8)
+    out = [("null left image", "good", dict(L=None), BAD_ARG, null), ("null right image", "good", dict(R=None), BAD_ARG, null),
+           ("null image, then size", "good", dict(R=None, **tiny), BAD_ARG, null),
+           ("size", "good", tiny, BAD_ARG, M_SIZE), ("size, then stride", "good", dict(W=8, stride=1), BAD_ARG, M_SIZE),
+           ("stride", "good", small, SIZE_MISMATCH, M_STRIDE), ("stride, then full queue", "full", small, SIZE_MISMATCH, M_STRIDE),
+           ("full queue", "full", {}, STATE, M_FULL)]
+    for r in ENTRY_POINTS[name][1]:
+        out += [("null result " + r, "good", {r: None}, BAD_ARG, null), ("null result %s, then size" % r, "good", dict(tiny, **{r: None}), BAD_ARG, null)]
+    if fovea:
+        out += [("stride, then no fovea levels", "no fovea", small, SIZE_MISMATCH, M_STRIDE), ("no fovea levels", "no fovea", {}, BAD_ARG, M_FOVEA)]
+    if host:
+        pinned = M_PINNED % (name, name[:-5])
+        out += [("not page-locked: " + r, "good", dict(unpinned=r), BAD_ARG, pinned) for r in ["L", "R"] + ENTRY_POINTS[name][1]]
+        out += [("stride, then not page-locked", "good", dict(small, unpinned="L"), SIZE_MISMATCH, M_STRIDE),
+                ("not page-locked, then full queue", "full", dict(unpinned="o1"), BAD_ARG, pinned)]
+        if fovea:
+            out += [("not page-locked: " + r, "good", {r: BASE + 8192, "unpinned": r}, BAD_ARG, pinned) for r in ("pl", "pr")]
+            out += [("no fovea levels, then not page-locked", "no fovea", dict(unpinned="L"), BAD_ARG, M_FOVEA)]
+    if cloud:
+        nan = float("nan")
+        out += [("stride, then null spec", "good", dict(small, spec=None), SIZE_MISMATCH, M_STRIDE),
+                ("null spec", "good", dict(spec=None), BAD_ARG, M_SPEC), ("null spec, then no cloud hooks", "no hooks", dict(spec=None), BAD_ARG, M_SPEC),
+                ("sampling 0", "good", dict(spec=spec(sampling=0)), BAD_ARG, M_SAMPLING),
+                ("sampling 0, then NaN", "good", dict(spec=spec(sampling=0, min_conf=nan)), BAD_ARG, M_SAMPLING),
+                ("NaN, then max_points", "good", dict(spec=spec(z=(nan, 1.0), max_points=-1)), BAD_ARG, M_NAN),
+                ("max_points, then no cloud hooks", "no hooks", dict(spec=spec(max_points=-1)), BAD_ARG, M_MAX_POINTS),
+                ("no cloud hooks", "no hooks", {}, STATE, M_NO_CLOUDS), ("no cloud hooks, then full queue", "no hooks, full", {}, STATE, M_NO_CLOUDS),
+                ("null spec, then full queue", "full", dict(spec=None), BAD_ARG, M_SPEC)]
+        if fovea:
+            out += [("no fovea levels, then null spec", "no fovea", dict(spec=None), BAD_ARG, M_FOVEA)]
+    if device_cloud:
+        out += [("misaligned d_points", "good", dict(points=BASE + 8), BAD_ARG, M_BUFFERS), ("null d_count", "good", dict(count=None), BAD_ARG, M_BUFFERS),
+                ("sampling 0, then misaligned d_points", "good", dict(spec=spec(sampling=0), points=BASE + 8), BAD_ARG, M_SAMPLING),
+                ("max_points, then misaligned d_points", "good", dict(spec=spec(max_points=-1), points=BASE + 8), BAD_ARG, M_MAX_POINTS),
+                ("misaligned d_points, then no cloud hooks", "no hooks", dict(points=BASE + 8), BAD_ARG, M_BUFFERS),
+                ("misaligned d_points, then full queue", "full", dict(points=BASE + 8), BAD_ARG, M_BUFFERS)]
+    return out
+
+
+@pytest.mark.parametrize("name", list(ENTRY_POINTS))
+def test_every_entry_point_refuses_in_order_with_its_message(fq, name):
+    """Each refusal of each ugsm_enqueue_*: its status, the exact text of ugsm_last_error, which of two refusals that apply at once wins,
+    and that nothing was enqueued -- the queue is as deep as before, and what it reports in the end are the pairs that were accepted."""
+    import types
+    call = ENTRY_POINTS[name][0]
+    images = np.zeros((2, 32, 3 * 64), np.uint8)      # (real memory: the managed kinds read their images once a pair is accepted)
+
+    def arguments(**over):
+        a = types.SimpleNamespace(L=images[0].ctypes.data, R=images[1].ctypes.data, W=64, H=32, stride=3 * 64, ox=1, oy=2, o0=BASE + 128, o1=BASE + 192,
+                                  o2=BASE + 256, pl=None, pr=None, spec=spec(), points=BASE + 1024, cap=10, count=BASE + 2048, lc=BASE + 3072, tag=77)
+        unpinned = over.pop("unpinned", None)
+        vars(a).update(over)
+        a.spec = C.byref(a.spec) if a.spec is not None else None
+        return a, getattr(a, unpinned) if unpinned else None
+
+    def depth(ctx):
+        w, f, u = C.c_int(), C.c_int(), C.c_int()
+        assert fq.ugsm_queue_depth(ctx, C.byref(w), C.byref(f), C.byref(u)) == OK
+        return w.value, f.value, u.value
+
+    def context(kind):
+        full = kind.endswith("full")
+        ctx = fq.ugsm_fake_create_cloud(1 if full else 2, 1 if full else 3, 8, 1 if kind == "no fovea" else 4, 0 if kind.startswith("no hooks") else 1)
+        assert ctx
+        for tag in range(2 if full else 0):           # (slots + 1) x batch = 2 pairs outstanding: one finished and not fetched, one in flight
+            assert fq.ugsm_enqueue_full(ctx, BASE, BASE + 64, 64, 32, 3 * 64, BASE + 128, tag) == OK
+        return ctx
+
+    assert call(fq, None, arguments()[0]) == BAD_ARG                                     # no context: no message either
+    ctxs = {}
+    try:
+        for what, kind, over, status, message in refusals(name):
+            ctx = ctxs[kind] = ctxs.get(kind) or context(kind)
+            a, unpinned = arguments(**over)
+            before, allocs = depth(ctx), fq.ugsm_fake_allocs()
+            fq.ugsm_fake_unpinned(unpinned)
+            st = call(fq, ctx, a)
+            fq.ugsm_fake_unpinned(None)
+            assert (st, fq.ugsm_last_error(ctx).decode()) == (status, message), (name, what)
+            assert depth(ctx) == before, (name, what)
+            if kind.endswith("full"):
+                assert fq.ugsm_fake_allocs() == allocs, (name, what)                      # refused before any staging was made or filled
+        for kind, ctx in ctxs.items():                                                    # never reported: only the pairs that filled the queue are
+            tags = []
+            while True:
+                c = Completion()
+                st = fq.ugsm_next_done(ctx, C.byref(c), 1)
+                if st == EMPTY:
+                    break
+                assert st == OK
+                tags.append(int(c.tag))
+            assert tags == ([0, 1] if kind.endswith("full") else []), (name, kind, tags)
+        a, _ = arguments()
+        assert call(fq, ctxs["good"], a) == OK, (name, fq.ugsm_last_error(ctxs["good"]))       # the good call of the table is one
+        c = Completion()
+        assert fq.ugsm_next_done(ctxs["good"], C.byref(c), 1) == OK and c.tag == 77 and c.status == OK
+    finally:
+        for ctx in ctxs.values():
+            fq.ugsm_fake_destroy_cloud(ctx)

@@ -10,7 +10,9 @@ The queue is host logic written against the public slot-level entry points; what
   * the `more` hint (CtxHooks::queue_more) that makes the runtime take a call to share the chip: set when pairs wait behind the call or
     the call filled up by itself, clear for a flushed call with nothing behind it;
   * nothing is thrown across the C-ABI: with the Nth host allocation failing, entry points answer UGSM_ERR_NOMEM and the first rule
-    still holds.
+    still holds;
+  * a call carries exactly the arguments its pairs were enqueued with, at the right slot-level entry point (test_marshalling: the fake
+    records everything a ugsm_submit_* stand-in is handed; the cloud kinds and every refusal of the ten entry points: test_queue_cloud_host.py).
 The reference has no counterpart (one blocking match() per callback, UG_GPU_matcher.cpp:126-185, 749-752)."""
 import ctypes as C
 import os
@@ -33,7 +35,8 @@ class Completion(C.Structure):
 def fq(tmp_path_factory):
     out = str(tmp_path_factory.mktemp("fakeq") / "libugsm_queue_fake.so")
     cmd = ["g++", "-std=c++17", "-O1", "-g", "-fPIC", "-shared", "-fvisibility=hidden",
-           os.path.join(ROOT, "tests", "fake_runtime.cpp"), os.path.join(ROOT, "ug_stereomatcher_amd", "csrc", "ugsm_queue.cpp"),
+           os.path.join(ROOT, "tests", "fake_runtime.cpp"), os.path.join(ROOT, "tests", "fake_input_format.cpp"),
+           os.path.join(ROOT, "ug_stereomatcher_amd", "csrc", "ugsm_queue.cpp"),
            "-Wl,--version-script=" + os.path.join(ROOT, "ug_stereomatcher_amd", "csrc", "ugsm.map"), "-o", out]
     r = subprocess.run(cmd, capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -49,6 +52,9 @@ def fq(tmp_path_factory):
     lib.ugsm_fake_calls.argtypes = [vp]
     lib.ugsm_fake_calls.restype = ll
     lib.ugsm_fake_call.argtypes = [vp, ll, C.POINTER(i * 7), C.POINTER(vp * 16)]
+    lib.ugsm_fake_call_args.argtypes = [vp, ll, C.POINTER(ll * 7), C.POINTER(ll * (9 * 16))]
+    lib.ugsm_fake_set_input_format.argtypes = [vp, i]
+    lib.ugsm_fake_get_input_format.argtypes = [vp]
     lib.ugsm_fake_violations.argtypes = [vp]
     lib.ugsm_fake_fail_alloc_after.argtypes = [ll]
     lib.ugsm_fake_fail_alloc_after.restype = None
@@ -56,7 +62,9 @@ def fq(tmp_path_factory):
     lib.ugsm_enqueue_full.argtypes = [vp, vp, vp, i, i, i, vp, u64]
     lib.ugsm_enqueue_foveated.argtypes = [vp, vp, vp, i, i, i, i, i, vp, vp, vp, u64]
     lib.ugsm_enqueue_full_host.argtypes = [vp, vp, vp, i, i, i, vp, vp, vp, u64]
+    lib.ugsm_enqueue_foveated_host.argtypes = [vp, vp, vp, i, i, i, i, i, vp, vp, vp, vp, vp, u64]
     lib.ugsm_enqueue_full_managed.argtypes = [vp, vp, vp, i, i, i, u64]
+    lib.ugsm_enqueue_foveated_managed.argtypes = [vp, vp, vp, i, i, i, i, i, i, u64]
     lib.ugsm_flush.argtypes = [vp]
     lib.ugsm_next_done.argtypes = [vp, C.POINTER(Completion), i]
     lib.ugsm_queue_depth.argtypes = [vp, C.POINTER(i), C.POINTER(i), C.POINTER(i)]
@@ -312,3 +320,168 @@ def test_host_allocation_failures_lose_no_pair(fq):
         finally:
             h.close()
     assert refused > 3, (refused, fetch_failed)     # (the faults do land: some in an enqueue, which then refuses its pair)
+
+
+# ---- what a call carries: every argument of every pair ---------------------------------------------------------------------------------
+E_BATCH, E_FOVEA, E_HOST = 1, 2, 4          # which ugsm_submit_* stand-in a call went to (tests/fake_runtime.cpp)
+RGB8, RGBA8, MONO8 = 0, 2, 4
+BPP = {RGB8: 3, RGBA8: 4, MONO8: 1}
+FOVEA_LEVELS = 4
+
+
+class Marshal:
+    """A host whose every pointer argument and offset is distinct per pair; keeps what each pair was enqueued with and, for the managed
+    kinds, what its staging held when the pair was reported."""
+
+    def __init__(self, lib):
+        self.lib = lib
+        self.ctx = lib.ugsm_fake_create(2, 3, 8, FOVEA_LEVELS)
+        assert self.ctx
+        self.fmt = RGB8
+        self.want, self.images, self.done, self.staged = {}, {}, [], {}
+
+    def close(self):
+        self.lib.ugsm_fake_destroy(self.ctx)
+
+    def set_format(self, fmt):
+        assert self.lib.ugsm_fake_set_input_format(self.ctx, fmt) == OK
+        self.fmt = fmt
+
+    def enqueue(self, kind, pyr="", size=(64, 32), stride=None):
+        """kind: full, fovea, full_host, fovea_host, full_managed, fovea_managed; pyr: which pyramid stacks the pair asks for ("", "L", "LR")."""
+        lib, ctx, tag = self.lib, self.ctx, len(self.want)
+        W, H = size
+        row = BPP[self.fmt] * W
+        stride = row + 8 if stride is None else stride
+        p = BASE + 4096 * tag
+        L, R, o0, o1, o2 = (p + 64 * k for k in range(5))
+        pl, pr = (p + 320 if "L" in pyr else None), (p + 384 if "R" in pyr else None)
+        ox, oy = 3 + tag, 1000 + tag
+        w = dict(kind=kind, pyr=pyr, fovea=kind.startswith("fovea"), host=not kind in ("full", "fovea"), managed=kind.endswith("managed"),
+                 W=W, H=H, stride=stride, fmt=self.fmt, L=L, R=R, ox=0, oy=0)
+        if w["fovea"]:
+            w["ox"], w["oy"] = ox, oy
+        if kind == "full":
+            st, w["out"] = lib.ugsm_enqueue_full(ctx, L, R, W, H, stride, o0, tag), [o0, 0, 0, 0, 0]
+        elif kind == "fovea":
+            st, w["out"] = lib.ugsm_enqueue_foveated(ctx, L, R, W, H, stride, ox, oy, o0, pl, pr, tag), [o0, 0, 0, pl or 0, pr or 0]
+        elif kind == "full_host":
+            st, w["out"] = lib.ugsm_enqueue_full_host(ctx, L, R, W, H, stride, o0, o1, o2, tag), [o0, o1, o2, 0, 0]
+        elif kind == "fovea_host":
+            st = lib.ugsm_enqueue_foveated_host(ctx, L, R, W, H, stride, ox, oy, o0, o1, o2, pl, pr, tag)
+            w["out"] = [o0, o1, o2, pl or 0, pr or 0]
+        else:
+            img = np.random.RandomState(tag).randint(0, 256, (2, H, stride)).astype(np.uint8)   # any memory: the library copies the images
+            self.images[tag] = [img[s][:, :row].tobytes() for s in range(2)]                    # ... compacted to rows of bytes per pixel x W
+            w["stride"] = row
+            if kind == "full_managed":
+                assert pyr == ""
+                st = lib.ugsm_enqueue_full_managed(ctx, img[0].ctypes.data, img[1].ctypes.data, W, H, stride, tag)
+            else:
+                assert pyr in ("", "LR")
+                st = lib.ugsm_enqueue_foveated_managed(ctx, img[0].ctypes.data, img[1].ctypes.data, W, H, stride, ox, oy, 1 if pyr else 0, tag)
+            img[:] = 0                                                                          # (the caller's memory is not read again)
+        assert st == OK, (kind, st, lib.ugsm_last_error(ctx))
+        self.want[tag] = w
+        return tag
+
+    def args(self, k):
+        head, pairs = (C.c_longlong * 7)(), (C.c_longlong * (9 * 16))()
+        assert self.lib.ugsm_fake_call_args(self.ctx, k, C.byref(head), C.byref(pairs)) == 0, k
+        rec = dict(zip(("entry", "W", "H", "stride", "fmt", "pyr_arrays", "n"), head))
+        rec["pairs"] = [dict(L=pairs[9 * b], R=pairs[9 * b + 1], ox=pairs[9 * b + 2], oy=pairs[9 * b + 3], out=list(pairs[9 * b + 4:9 * b + 9]))
+                        for b in range(rec["n"])]
+        return rec
+
+    def drain(self):
+        while True:
+            c = Completion()
+            st = self.lib.ugsm_next_done(self.ctx, C.byref(c), 1)
+            if st == EMPTY:
+                return
+            assert st == OK and c.status == OK, (st, c.status)
+            tag, k = int(c.tag), int(c.call_index)
+            b = sum(1 for _, kk, _ in self.done if kk == k)          # the pair's place in its call: pairs are reported in enqueue order
+            self.done.append((tag, k, [C.cast(c.result[j], C.c_void_p).value or 0 for j in range(5)]))
+            w = self.want[tag]
+            if w["managed"]:                                         # the staging is lent until the next ugsm_next_done: look now
+                pr = self.args(k)["pairs"][b]
+                nbytes = w["stride"] * w["H"]
+                self.staged[tag] = [C.string_at(pr["L"], nbytes), C.string_at(pr["R"], nbytes)]
+
+
+def test_marshalling(fq):
+    """Every recorded call carries exactly the arguments its pairs were enqueued with, in enqueue order, at the right one of the eight
+    ugsm_submit_* entry points: two slots, calls of up to three, every non-cloud kind in calls of one pair and of several, kind changes in
+    the backlog, host pairs with pyramid stacks going out alone, strides larger than a row, a format change between two enqueues."""
+    m = Marshal(fq)
+    try:
+        # (the first call after idle or a flush takes two pairs, the later ones three: ugsm_queue_plan)
+        m.enqueue("full"), m.enqueue("full")                                        # a call of two
+        m.enqueue("full"), m.enqueue("fovea")                                       # another kind behind it: the full pair goes out alone
+        m.enqueue("fovea"), m.enqueue("fovea", "LR")                                # three foveated pairs, one with pyramids
+        m.drain()
+        m.enqueue("fovea", "L"), m.drain()                                          # one pair, its left pyramid only
+        m.enqueue("fovea"), m.enqueue("fovea")                                      # two without: no pyramid arrays
+        m.enqueue("fovea"), m.drain()
+        m.enqueue("full_host"), m.enqueue("full_host")
+        m.enqueue("full_host"), m.enqueue("fovea_host")
+        m.enqueue("fovea_host"), m.enqueue("fovea_host", "L")                       # pyramid stacks: ends the group and goes out alone
+        m.drain()
+        m.enqueue("fovea_host", "LR"), m.enqueue("fovea_host"), m.drain()
+        m.enqueue("full_managed"), m.enqueue("full_managed", stride=3 * 64)          # (one with rows that need no compaction)
+        m.enqueue("full_managed"), m.drain()
+        m.enqueue("fovea_managed"), m.enqueue("fovea_managed")
+        m.enqueue("fovea_managed", "LR")
+        m.enqueue("fovea_managed"), m.drain()
+        m.enqueue("full", size=(64, 32), stride=4 * 64 + 8), m.enqueue("full", size=(128, 64)), m.drain()   # another size
+        a = m.enqueue("full", stride=4 * 64 + 8)
+        m.set_format(RGBA8)
+        b = m.enqueue("full", stride=4 * 64 + 8)                                    # differs from `a` in nothing but the format
+        c = m.enqueue("full_managed")
+        m.set_format(MONO8)                                                         # what the host sets later does not reach pairs already enqueued
+        m.drain()
+        assert fq.ugsm_fake_get_input_format(m.ctx) == MONO8
+        assert fq.ugsm_fake_violations(m.ctx) == 0
+
+        want = m.want
+        assert [t for t, _, _ in m.done] == list(range(len(want)))                  # exactly once, in enqueue order
+        ncalls = fq.ugsm_fake_calls(m.ctx)
+        assert sorted({k for _, k, _ in m.done}) == list(range(ncalls))
+        seen = set()
+        for k in range(ncalls):
+            rec = m.args(k)
+            tags = [t for t, kk, _ in m.done if kk == k]
+            results = [r for _, kk, r in m.done if kk == k]
+            n, w0 = rec["n"], want[tags[0]]
+            assert n == len(tags) and tags == list(range(tags[0], tags[0] + n)), (k, rec, tags)
+            assert rec["entry"] == (E_FOVEA if w0["fovea"] else 0) + (E_HOST if w0["host"] else 0) + (E_BATCH if n > 1 else 0), (k, rec, w0)
+            assert rec["pyr_arrays"] == (1 if rec["entry"] == E_FOVEA + E_BATCH and any(want[t]["pyr"] for t in tags) else 0), (k, rec)
+            for t, got, res in zip(tags, rec["pairs"], results):
+                w = want[t]
+                assert (rec["W"], rec["H"], rec["stride"], rec["fmt"]) == (w["W"], w["H"], w["stride"], w["fmt"]), (k, t, rec, w)
+                assert (got["ox"], got["oy"]) == (w["ox"], w["oy"]), (k, t, got, w)
+                if not w["managed"]:
+                    assert (got["L"], got["R"], got["out"]) == (w["L"], w["R"], w["out"]), (k, t, got, w)
+                    assert res == [0] * 5, (t, res)
+                else:
+                    # the staging buffer's carve-up: both images, 256-byte aligned; three planes, then the two pyramid stacks of three planes each
+                    img = (w["stride"] * w["H"] + 255) & ~255
+                    plane = (FOVEA_LEVELS * (w["W"] // 8) * (w["H"] // 8) if w["fovea"] else w["W"] * w["H"]) * 4
+                    o0 = got["out"][0]
+                    assert got["L"] and o0 and got["R"] == got["L"] + img, (k, t, got)
+                    assert got["out"] == [o0, o0 + plane, o0 + 2 * plane, o0 + 3 * plane if w["pyr"] else 0, o0 + 6 * plane if w["pyr"] else 0], (k, t, got)
+                    assert res == got["out"], (t, res, got)
+                    assert m.staged[t] == m.images[t], (k, t)
+                seen.add((w["kind"], w["pyr"], n > 1))
+            if w0["managed"]:
+                assert len({g["L"] for g in rec["pairs"]}) == n and len({g["out"][0] for g in rec["pairs"]}) == n      # a buffer per pair
+        # the format each of the last three pairs was enqueued in, alone in its call
+        assert [(want[t]["fmt"], sum(1 for _, kk, _ in m.done if kk == m.done[t][1])) for t in (a, b, c)] == [(RGB8, 1), (RGBA8, 1), (RGBA8, 1)]
+        both = lambda kind, pyr="": {(kind, pyr, False), (kind, pyr, True)}
+        need = (both("full") | both("fovea") | {("fovea", "LR", True), ("fovea", "L", False)} | both("full_host") | both("fovea_host")
+                | {("fovea_host", "L", False), ("fovea_host", "LR", False)} | both("full_managed") | both("fovea_managed") | {("fovea_managed", "LR", False)})
+        assert seen == need, (sorted(seen ^ need))
+        assert {m.args(k)["entry"] for k in range(ncalls)} == set(range(8))         # all eight entry points
+    finally:
+        m.close()

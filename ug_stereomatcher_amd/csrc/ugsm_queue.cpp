@@ -26,33 +26,34 @@ namespace {
 enum Mode { M_FULL = 0, M_FOVEA = 1 };
 enum Mem { MEM_DEVICE = 0, MEM_PINNED = 1, MEM_MANAGED = 2 };
 
+struct Pinned {  // page-locked memory the queue owns (pinned_room)
+    void *p = nullptr;
+    size_t bytes = 0;
+};
 // page-locked staging of one managed pair: both images in, the result planes out, the cloud out (ugsm_enqueue_*_cloud_managed: grown to
 // the largest cloud a pair in this buffer has stored, when the pair's count is known -- never to the dense size up front)
 struct Managed {
-    uint8_t *in = nullptr;
-    size_t in_cap = 0;
-    float *out = nullptr;
-    size_t out_cap = 0;  // floats
-    char *cloud = nullptr;
-    size_t cloud_cap = 0;  // bytes
+    Pinned in, out, cloud;
     bool busy = false;
 };
 
+// One pair, as its entry point states it -- the leading members, in the order an entry point lists them -- and as the queue keeps it.
 struct Item {
     int mode, mem;
-    const uint8_t *L, *R;
+    const uint8_t *L, *R;  // (a managed pair: the caller's images until the pair is accepted, its staging from then on: stage_managed)
     int W, H, stride, off_x, off_y;
-    int fmt;  // the input format the pair was enqueued in (ugsm_set_input_format at the time of its ugsm_enqueue_*)
     float *out[5];  // device: out[0] = d_out / d_stack, out[3], out[4] = d_pyrL / d_pyrR; host: H, V, C planes (+ pyramid stacks)
     uint64_t tag;
-    unsigned long long seq;
-    int managed;  // index into Queue::pool, or -1
-    // the cloud job of a pair enqueued with ugsm_enqueue_*_cloud*: the spec as it was at enqueue, and the device kind's cloud buffers
-    bool has_cloud;
-    ugsm_queue_cloud spec;
-    void *points;
-    long long cap;
-    long long *count, *level_counts;
+    bool want_pyr = false;  // a managed foveated pair asks for its pyramid stacks
+    // the cloud job of a pair enqueued with ugsm_enqueue_*_cloud*: the device kind's cloud buffers, and the spec as it was at enqueue
+    bool has_cloud = false;
+    void *points = nullptr;
+    long long cap = 0;
+    long long *count = nullptr, *level_counts = nullptr;
+    ugsm_queue_cloud spec{};
+    int fmt = 0;  // the input format the pair was enqueued in (ugsm_set_input_format at the time of its ugsm_enqueue_*)
+    unsigned long long seq = 0;
+    int managed = -1;  // index into Queue::pool, or -1
     bool pyr() const { return out[3] != nullptr || out[4] != nullptr; }
     // pairs of one call: one mode, one kind of memory, one geometry, one input format; host calls with pyramid stacks go out alone (the
     // batched host entry point has none); all with a cloud, of one byte-equal spec, or all without
@@ -116,19 +117,30 @@ int batch_of(const ugsm_config &cfg) { return std::min(std::max(cfg.batch, 1), U
 void queue_free(ugsm_ctx *ctx, void *p)
 {
     Queue *q = static_cast<Queue *>(p);
-    for (Managed &m : q->pool) {
-        if (m.in) (void)ugsm_host_free(ctx, m.in);
-        if (m.out) (void)ugsm_host_free(ctx, m.out);
-        if (m.cloud) (void)ugsm_host_free(ctx, m.cloud);
-    }
+    for (Managed &m : q->pool)
+        for (Pinned *b : {&m.in, &m.out, &m.cloud})
+            if (b->p) (void)ugsm_host_free(ctx, b->p);
     delete q;
+}
+
+// at least `bytes` of page-locked memory in b; the old contents are not kept.  false: out of memory -- b is empty and ugsm_host_alloc has
+// set the message
+bool pinned_room(ugsm_ctx *ctx, Pinned &b, size_t bytes)
+{
+    if (b.bytes >= bytes) return true;
+    if (b.p) (void)ugsm_host_free(ctx, b.p);
+    b = Pinned{};
+    void *p = nullptr;
+    if (ugsm_host_alloc(ctx, &p, (long long)bytes) != UGSM_OK) return false;
+    b = Pinned{p, bytes};
+    return true;
 }
 
 Queue *queue_of(ugsm_ctx *ctx)
 {
     CtxHooks &h = ctx_hooks(ctx);
     if (!h.queue) {
-        // (nothing is thrown from here: ugsm_enqueue_*_managed and ugsm_queue_depth ask outside a no_throw body, and the members' own
+        // (nothing is thrown from here: ugsm_enqueue_* and ugsm_queue_depth ask outside a no_throw body, and the members' own
         // constructors allocate)
         Queue *q = nullptr;
         try {
@@ -181,17 +193,8 @@ void *cloud_staging(void *user, int pair, long long bytes)
     if (pair < 0 || (size_t)pair >= u->c->items.size() || bytes < 0) return nullptr;
     const int idx = u->c->items[(size_t)pair].managed;
     if (idx < 0) return nullptr;
-    Managed &m = u->q->pool[(size_t)idx];
-    if (m.cloud_cap < (size_t)bytes) {
-        if (m.cloud) (void)ugsm_host_free(u->ctx, m.cloud);
-        m.cloud = nullptr;
-        m.cloud_cap = 0;
-        void *p = nullptr;
-        if (ugsm_host_alloc(u->ctx, &p, bytes) != UGSM_OK) return nullptr;
-        m.cloud = static_cast<char *>(p);
-        m.cloud_cap = (size_t)bytes;
-    }
-    return m.cloud;
+    Pinned &cloud = u->q->pool[(size_t)idx].cloud;
+    return pinned_room(u->ctx, cloud, (size_t)bytes) ? cloud.p : nullptr;
 }
 
 // The slot of a managed cloud call in phase 0 has drained (st: what ugsm_poll / ugsm_wait answered): the finish hook -- once per call -- puts
@@ -216,7 +219,7 @@ void cloud_second_step(ugsm_ctx *ctx, Queue *q, Call &c, int st)
 // other before its pairs are reported: a submit can fail after work has gone onto the slot's stream (out of memory for the staging of a
 // later phase, a launch error mid-call), and a completion tells the host that its input and result buffers -- or the managed staging
 // buffer the library lends next -- are free.  The submit's status is the one reported.
-int reap(ugsm_ctx *ctx, Queue *q)
+void reap(ugsm_ctx *ctx, Queue *q)
 {
     // managed cloud calls whose first step has drained start their second, wherever they are in the flight list: a later call's clouds
     // come down while the calls before it are still matching
@@ -233,7 +236,6 @@ int reap(ugsm_ctx *ctx, Queue *q)
         if (st != UGSM_OK && c.status == UGSM_OK) c.status = st;
         retire_front(ctx, q);
     }
-    return UGSM_OK;
 }
 
 // blocks until the oldest call in flight has finished (or, its submit having failed, until what it did enqueue has drained), and retires it
@@ -259,6 +261,22 @@ int free_slot(const Queue *q)
     return -1;
 }
 
+// the pairs of a call, as columns: what the ugsm_submit_*_batch entry points take
+struct Columns {
+    const uint8_t *L[UGSM_MAX_BATCH], *R[UGSM_MAX_BATCH];
+    int off_x[UGSM_MAX_BATCH], off_y[UGSM_MAX_BATCH];
+    float *out[5][UGSM_MAX_BATCH];  // (Item::out, transposed)
+    bool any_pyr = false;
+};
+
+// a pair's part of the call the cloud hook takes: a managed pair has its planes where a device pair has its d_out / d_stack
+CloudJob cloud_job(const Item &it)
+{
+    float *const none = nullptr;
+    if (it.mem == MEM_MANAGED) return CloudJob{it.L, it.R, it.off_x, it.off_y, none, {it.out[0], it.out[1], it.out[2]}, it.points, it.cap, it.count, it.level_counts};
+    return CloudJob{it.L, it.R, it.off_x, it.off_y, it.out[0], {none, none, none}, it.points, it.cap, it.count, it.level_counts};
+}
+
 // One library call for the first n waiting pairs on `slot`.  more: other calls follow this one closely -- pairs wait behind it, or it filled
 // up without a flush (a host that submits faster than the chip matches): the runtime then takes the call to share the chip whatever the
 // other slots are doing at this instant (call_alone, ugsm_policy.cpp).
@@ -279,23 +297,20 @@ void dispatch(ugsm_ctx *ctx, Queue *q, int n, int slot, bool more)
     c.index = q->calls++;
     q->waiting.erase(q->waiting.begin(), q->waiting.begin() + n);
     const Item &f = c.items[0];
-    const uint8_t *L[UGSM_MAX_BATCH], *R[UGSM_MAX_BATCH];
-    float *o0[UGSM_MAX_BATCH], *o1[UGSM_MAX_BATCH], *o2[UGSM_MAX_BATCH], *pl[UGSM_MAX_BATCH], *pr[UGSM_MAX_BATCH];
-    int ox[UGSM_MAX_BATCH], oy[UGSM_MAX_BATCH];
-    bool any_pyr = false;
+    const bool fovea = f.mode == M_FOVEA, host = f.mem != MEM_DEVICE;
+    Columns p;
+    CloudCall cc{fovea, f.mem == MEM_MANAGED, n, f.W, f.H, f.stride, &f.spec, {}};  // (sent only if the pairs carry a cloud)
     for (int b = 0; b < n; b++) {
         const Item &it = c.items[(size_t)b];
-        L[b] = it.L;
-        R[b] = it.R;
-        o0[b] = it.out[0];
-        o1[b] = it.out[1];
-        o2[b] = it.out[2];
-        pl[b] = it.out[3];
-        pr[b] = it.out[4];
-        ox[b] = it.off_x;
-        oy[b] = it.off_y;
-        any_pyr = any_pyr || it.pyr();
+        p.L[b] = it.L;
+        p.R[b] = it.R;
+        p.off_x[b] = it.off_x;
+        p.off_y[b] = it.off_y;
+        for (int k = 0; k < 5; k++) p.out[k][b] = it.out[k];
+        p.any_pyr = p.any_pyr || it.pyr();
+        if (f.has_cloud) cc.job[b] = cloud_job(it);
     }
+    float *const *o0 = p.out[0], *const *o1 = p.out[1], *const *o2 = p.out[2], *const *pl = p.out[3], *const *pr = p.out[4];
     CtxHooks &h = ctx_hooks(ctx);
     h.queue_calling = true;
     h.queue_more = more;
@@ -304,34 +319,20 @@ void dispatch(ugsm_ctx *ctx, Queue *q, int n, int slot, bool more)
     h.input_format = f.fmt;
     int st;
     if (f.has_cloud) {  // the match and the clouds of the call's pairs: the runtime's hook
-        CloudCall cc{};
-        cc.fovea = f.mode == M_FOVEA;
-        cc.managed = f.mem == MEM_MANAGED;
-        cc.n = n;
-        cc.W = f.W;
-        cc.H = f.H;
-        cc.stride = f.stride;
-        cc.spec = &f.spec;
-        for (int b = 0; b < n; b++) {
-            const Item &it = c.items[(size_t)b];
-            cc.job[b] = CloudJob{it.L, it.R, it.off_x, it.off_y, cc.managed ? nullptr : it.out[0], {nullptr, nullptr, nullptr}, it.points, it.cap, it.count, it.level_counts};
-            for (int k = 0; k < 3 && cc.managed; k++) cc.job[b].planes[k] = it.out[k];
-        }
         st = h.cloud_submit ? h.cloud_submit(ctx, slot, &cc) : UGSM_ERR_STATE;
         if (cc.managed) c.phase = 0;  // (a failed submit too: cloud_second_step sees the status once the slot has drained)
-    } else if (f.mem == MEM_DEVICE) {
-        if (f.mode == M_FULL)
-            st = n == 1 ? ugsm_submit_full(ctx, slot, L[0], R[0], f.W, f.H, f.stride, o0[0]) : ugsm_submit_full_batch(ctx, slot, n, L, R, f.W, f.H, f.stride, o0);
-        else
-            st = n == 1 ? ugsm_submit_foveated(ctx, slot, L[0], R[0], f.W, f.H, f.stride, ox[0], oy[0], o0[0], pl[0], pr[0])
-                        : ugsm_submit_foveated_batch(ctx, slot, n, L, R, f.W, f.H, f.stride, ox, oy, o0, any_pyr ? pl : nullptr, any_pyr ? pr : nullptr);
+    } else if (!fovea && !host) {
+        st = n == 1 ? ugsm_submit_full(ctx, slot, p.L[0], p.R[0], f.W, f.H, f.stride, o0[0]) : ugsm_submit_full_batch(ctx, slot, n, p.L, p.R, f.W, f.H, f.stride, o0);
+    } else if (fovea && !host) {
+        st = n == 1 ? ugsm_submit_foveated(ctx, slot, p.L[0], p.R[0], f.W, f.H, f.stride, p.off_x[0], p.off_y[0], o0[0], pl[0], pr[0])
+                    : ugsm_submit_foveated_batch(ctx, slot, n, p.L, p.R, f.W, f.H, f.stride, p.off_x, p.off_y, o0, p.any_pyr ? pl : nullptr,
+                                                 p.any_pyr ? pr : nullptr);
+    } else if (!fovea) {
+        st = n == 1 ? ugsm_submit_full_host(ctx, slot, p.L[0], p.R[0], f.W, f.H, f.stride, o0[0], o1[0], o2[0])
+                    : ugsm_submit_full_batch_host(ctx, slot, n, p.L, p.R, f.W, f.H, f.stride, o0, o1, o2);
     } else {
-        if (f.mode == M_FULL)
-            st = n == 1 ? ugsm_submit_full_host(ctx, slot, L[0], R[0], f.W, f.H, f.stride, o0[0], o1[0], o2[0])
-                        : ugsm_submit_full_batch_host(ctx, slot, n, L, R, f.W, f.H, f.stride, o0, o1, o2);
-        else
-            st = n == 1 ? ugsm_submit_foveated_host(ctx, slot, L[0], R[0], f.W, f.H, f.stride, ox[0], oy[0], o0[0], o1[0], o2[0], pl[0], pr[0])
-                        : ugsm_submit_foveated_batch_host(ctx, slot, n, L, R, f.W, f.H, f.stride, ox, oy, o0, o1, o2);
+        st = n == 1 ? ugsm_submit_foveated_host(ctx, slot, p.L[0], p.R[0], f.W, f.H, f.stride, p.off_x[0], p.off_y[0], o0[0], o1[0], o2[0], pl[0], pr[0])
+                    : ugsm_submit_foveated_batch_host(ctx, slot, n, p.L, p.R, f.W, f.H, f.stride, p.off_x, p.off_y, o0, o1, o2);
     }
     h.input_format = host_fmt;
     h.queue_calling = false;
@@ -414,69 +415,69 @@ int room(ugsm_ctx *ctx, const Queue *q)
     return ctx_fail(ctx, UGSM_ERR_STATE, "ugsm_enqueue_*: (slots + 1) x batch pairs are outstanding and completions wait to be fetched: call ugsm_next_done first");
 }
 
-int enqueue(ugsm_ctx *ctx, Item it)
-{
-    return no_throw(ctx, "ugsm_enqueue_*: out of host memory", [&]() -> int {
-        Queue *q = queue_of(ctx);
-        if (!q) return ctx_fail(ctx, UGSM_ERR_NOMEM, "ugsm_enqueue_*: out of host memory");
-        const int r = room(ctx, q);
-        if (r != UGSM_OK) return r;
-        it.seq = q->seq + 1;
-        it.fmt = ctx_hooks(ctx).input_format;  // (captured now: the call is formed later)
-        q->waiting.push_back(it);
-        q->seq = it.seq;
-        ctx_hooks(ctx).queue_busy = true;
-        // the pair is accepted; whatever happens to its call comes out of ugsm_next_done -- and a pump that ran out of host memory leaves
-        // the pairs waiting for the next entry point's pump: that is not a rejection either
-        (void)no_throw(ctx, "ugsm_enqueue_*: out of host memory", [&]() -> int {
-            pump(ctx, q, true);
-            return UGSM_OK;
-        });
-        update_busy(ctx, q);
-        return UGSM_OK;
-    });
-}
-
-// a managed buffer with room for `in_bytes` of images and `out_floats` of results
+// a managed buffer with room for `in_bytes` of images and `out_floats` of results; -1: out of memory (ugsm_host_alloc has set the message)
 int managed_get(ugsm_ctx *ctx, Queue *q, size_t in_bytes, size_t out_floats)
 {
+    const size_t out_bytes = out_floats * sizeof(float);
     int idx = -1;
     for (size_t k = 0; k < q->pool.size(); k++)
-        if (!q->pool[k].busy && (idx < 0 || (q->pool[k].in_cap >= in_bytes && q->pool[k].out_cap >= out_floats))) idx = (int)k;
+        if (!q->pool[k].busy && (idx < 0 || (q->pool[k].in.bytes >= in_bytes && q->pool[k].out.bytes >= out_bytes))) idx = (int)k;
     if (idx < 0) {
         q->pool.emplace_back();
         idx = (int)q->pool.size() - 1;
     }
     Managed &m = q->pool[(size_t)idx];
-    if (m.in_cap < in_bytes) {
-        if (m.in) (void)ugsm_host_free(ctx, m.in);
-        m.in = nullptr;
-        m.in_cap = 0;
-        void *p = nullptr;
-        const int st = ugsm_host_alloc(ctx, &p, (long long)in_bytes);
-        if (st != UGSM_OK) return -1;
-        m.in = static_cast<uint8_t *>(p);
-        m.in_cap = in_bytes;
-    }
-    if (m.out_cap < out_floats) {
-        if (m.out) (void)ugsm_host_free(ctx, m.out);
-        m.out = nullptr;
-        m.out_cap = 0;
-        void *p = nullptr;
-        const int st = ugsm_host_alloc(ctx, &p, (long long)(out_floats * sizeof(float)));
-        if (st != UGSM_OK) return -1;
-        m.out = static_cast<float *>(p);
-        m.out_cap = out_floats;
-    }
+    if (!pinned_room(ctx, m.in, in_bytes) || !pinned_room(ctx, m.out, out_bytes)) return -1;
     m.busy = true;
     return idx;
 }
 
+// What is a managed pair's own, once the queue has room for it: a staging buffer, the images into it -- compacted to rows of bytes-per-pixel
+// x W bytes; after this the caller's memory is not touched again -- and the pair's images and results carved from it.
+int stage_managed(ugsm_ctx *ctx, Queue *q, Item &it)
+{
+    const ugsm_config &cfg = ctx_config(ctx);
+    const bool planes = !it.has_cloud || it.spec.want_planes != 0;  // (a cloud pair that does not want its planes has no room for them)
+    const bool pyr = it.mode == M_FOVEA && it.want_pyr;
+    const size_t row = (size_t)input_bpp(ctx_hooks(ctx).input_format) * it.W, img = (row * (size_t)it.H + 255) & ~(size_t)255;
+    size_t plane = (size_t)it.W * it.H;
+    if (it.mode == M_FOVEA) {
+        int fw = 0, fh = 0;
+        (void)ugsm_fovea_dims(it.W, it.H, cfg.levels, cfg.fovea_levels, &fw, &fh);
+        plane = (size_t)cfg.fovea_levels * fw * fh;
+    }
+    int idx = -1;
+    const int grown = no_throw(ctx, "ugsm_enqueue_*_managed: out of host memory", [&]() -> int {
+        idx = managed_get(ctx, q, 2 * img, (planes ? 3 * plane : 0) + (pyr ? 6 * plane : 0));
+        return UGSM_OK;
+    });
+    if (grown != UGSM_OK || idx < 0) return UGSM_ERR_NOMEM;  // (ugsm_host_alloc has set the message)
+    uint8_t *in = static_cast<uint8_t *>(q->pool[(size_t)idx].in.p);
+    float *out = static_cast<float *>(q->pool[(size_t)idx].out.p);
+    for (int side = 0; side < 2; side++) {
+        const uint8_t *src = side == 0 ? it.L : it.R;
+        uint8_t *dst = in + side * img;
+        if ((size_t)it.stride == row) {
+            ctx_host_copy(ctx, dst, src, row * (size_t)it.H);
+        } else {
+            for (int y = 0; y < it.H; y++) memcpy(dst + (size_t)y * row, src + (size_t)y * it.stride, row);
+        }
+    }
+    it.L = in;
+    it.R = in + img;
+    it.stride = (int)row;
+    for (int k = 0; k < 3; k++) it.out[k] = planes ? out + k * plane : nullptr;
+    it.out[3] = pyr ? out + 3 * plane : nullptr;
+    it.out[4] = pyr ? out + 6 * plane : nullptr;
+    it.managed = idx;
+    return UGSM_OK;
+}
+
 // What every ugsm_enqueue_*_cloud* checks of its spec and, the device kind, of its cloud buffers: the slot-level cloud calls' own checks
 // (cloud_args_ok, ugsm_cloud.cpp), made when the pair is enqueued so that a bad pair is rejected and never reported
-int check_cloud(ugsm_ctx *ctx, const ugsm_queue_cloud *spec, int W, int H, bool device, const void *points, long long cap, const long long *count,
-                const long long *level_counts)
+int check_cloud(ugsm_ctx *ctx, const ugsm_queue_cloud *spec, const Item &it)
 {
+    const int W = it.W, H = it.H;
     if (!spec) return ctx_fail(ctx, UGSM_ERR_BAD_ARG, "ugsm_enqueue_*_cloud*: null spec");
     const ugsm_cloud_params &p = spec->params;
     if (W < 1 || H < 1 || (long long)W * H > (1LL << 28)) return ctx_fail(ctx, UGSM_ERR_BAD_ARG, "ugsm_enqueue_*_cloud*: bad image size");
@@ -485,87 +486,76 @@ int check_cloud(ugsm_ctx *ctx, const ugsm_queue_cloud *spec, int W, int H, bool 
     if (std::isnan(p.min_conf) || std::isnan(p.z_min) || std::isnan(p.z_max) || p.z_min > p.z_max)
         return ctx_fail(ctx, UGSM_ERR_BAD_ARG, "ugsm_enqueue_*_cloud*: a NaN min_conf / z_min / z_max, or z_min > z_max");
     if (spec->max_points < 0) return ctx_fail(ctx, UGSM_ERR_BAD_ARG, "ugsm_enqueue_*_cloud*: max_points < 0");
-    if (device && (!points || !count || cap < 0 || ((uintptr_t)points & 15) || ((uintptr_t)count & 7) || ((uintptr_t)level_counts & 7)))
+    if (it.mem == MEM_DEVICE && (!it.points || !it.count || it.cap < 0 || ((uintptr_t)it.points & 15) || ((uintptr_t)it.count & 7) || ((uintptr_t)it.level_counts & 7)))
         return ctx_fail(ctx, UGSM_ERR_BAD_ARG, "ugsm_enqueue_*_cloud: a null or misaligned cloud buffer, or cap_points < 0");
     if (!ctx_hooks(ctx).cloud_submit || !ctx_hooks(ctx).cloud_finish) return ctx_fail(ctx, UGSM_ERR_STATE, "ugsm_enqueue_*_cloud*: this runtime makes no clouds");
     return UGSM_OK;
 }
-void set_cloud(Item &it, const ugsm_queue_cloud *spec, void *points, long long cap, long long *count, long long *level_counts)
+Item with_cloud(Item it, void *points = nullptr, long long cap = 0, long long *count = nullptr, long long *level_counts = nullptr)
 {
     it.has_cloud = true;
-    it.spec = *spec;  // (copied now: the call is formed later)
-    it.spec.reserved = 0;
     it.points = points;
     it.cap = cap;
     it.count = count;
     it.level_counts = level_counts;
+    return it;
 }
 
-int enqueue_managed(ugsm_ctx *ctx, int mode, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, int off_x, int off_y, int want_pyr,
-                    uint64_t tag, const ugsm_queue_cloud *spec = nullptr, bool cloud = false)
+const char kNoMem[] = "ugsm_enqueue_*: out of host memory";
+
+// The one way in.  `it`: the pair as its entry point `name` states it; required: how many of its leading result pointers must be set; spec:
+// the cloud spec of a pair made with_cloud.  The refusals in the order every entry point has had them -- a refused pair is never reported --,
+// then the pair is accepted: whatever happens to its call comes out of ugsm_next_done.
+int enqueue_pair(ugsm_ctx *ctx, const char *name, Item it, int required, const ugsm_queue_cloud *spec = nullptr)
 {
     if (!ctx) return UGSM_ERR_BAD_ARG;
-    if (!rgbL || !rgbR) return ctx_fail(ctx, UGSM_ERR_BAD_ARG, "ugsm_enqueue_*_managed: null image");
-    const int g = check_geometry(ctx, W, H, stride, mode == M_FOVEA);
+    char msg[256];
+    bool null = !it.L || !it.R;
+    for (int k = 0; k < required; k++) null = null || !it.out[k];
+    if (null) {
+        snprintf(msg, sizeof msg, "%s: null buffer", name);
+        return ctx_fail(ctx, UGSM_ERR_BAD_ARG, it.mem == MEM_MANAGED ? "ugsm_enqueue_*_managed: null image" : msg);
+    }
+    const int g = check_geometry(ctx, it.W, it.H, it.stride, it.mode == M_FOVEA);
     if (g != UGSM_OK) return g;
-    if (cloud) {
-        const int cs = check_cloud(ctx, spec, W, H, false, nullptr, 0, nullptr, nullptr);
-        if (cs != UGSM_OK) return cs;
-    }
-    const bool planes = !cloud || spec->want_planes != 0;  // (a cloud pair that does not want its planes has no room for them)
-    Queue *q = queue_of(ctx);
-    if (!q) return ctx_fail(ctx, UGSM_ERR_NOMEM, "ugsm_enqueue_*: out of host memory");
-    const ugsm_config &cfg = ctx_config(ctx);
-    const int r = room(ctx, q);
-    if (r != UGSM_OK) return r;
-    const size_t row = (size_t)input_bpp(ctx_hooks(ctx).input_format) * W, img = (row * (size_t)H + 255) & ~(size_t)255;
-    size_t plane, out_floats;
-    if (mode == M_FULL) {
-        plane = (size_t)W * H;
-        out_floats = planes ? 3 * plane : 0;
-    } else {
-        int fw = 0, fh = 0;
-        (void)ugsm_fovea_dims(W, H, cfg.levels, cfg.fovea_levels, &fw, &fh);
-        plane = (size_t)cfg.fovea_levels * fw * fh;
-        out_floats = (planes ? 3 * plane : 0) + (want_pyr ? 6 * plane : 0);
-    }
-    int idx = -1;
-    const int grown = no_throw(ctx, "ugsm_enqueue_*_managed: out of host memory", [&]() -> int {
-        idx = managed_get(ctx, q, 2 * img, out_floats);
-        return UGSM_OK;
-    });
-    if (grown != UGSM_OK || idx < 0) return UGSM_ERR_NOMEM;  // (ugsm_host_alloc has set the message)
-    Managed &m = q->pool[(size_t)idx];
-    // the images, compacted to rows of bytes-per-pixel x W bytes, into the staging buffer: after this the caller's memory is not touched again
-    for (int side = 0; side < 2; side++) {
-        const uint8_t *src = side == 0 ? rgbL : rgbR;
-        uint8_t *dst = m.in + side * img;
-        if ((size_t)stride == row) {
-            ctx_host_copy(ctx, dst, src, row * (size_t)H);
-        } else {
-            for (int y = 0; y < H; y++) memcpy(dst + (size_t)y * row, src + (size_t)y * stride, row);
+    if (it.mem == MEM_PINNED) {
+        bool pinned = host_pinned(it.L) && host_pinned(it.R);
+        for (float *o : it.out) pinned = pinned && (!o || host_pinned(o));
+        if (!pinned) {
+            snprintf(msg, sizeof msg, "%s: every host buffer must be page-locked (ugsm_host_alloc, hipHostMalloc or hipHostRegister); ugsm_enqueue_%s_managed takes any memory",
+                     name, it.mode == M_FULL ? "full" : "foveated");
+            return ctx_fail(ctx, UGSM_ERR_BAD_ARG, msg);
         }
     }
-    Item it{};
-    it.mode = mode;
-    it.mem = MEM_MANAGED;
-    it.L = m.in;
-    it.R = m.in + img;
-    it.W = W;
-    it.H = H;
-    it.stride = (int)row;
-    it.off_x = off_x;
-    it.off_y = off_y;
-    it.out[0] = planes ? m.out : nullptr;
-    it.out[1] = planes ? m.out + plane : nullptr;
-    it.out[2] = planes ? m.out + 2 * plane : nullptr;
-    it.out[3] = (mode == M_FOVEA && want_pyr) ? m.out + 3 * plane : nullptr;
-    it.out[4] = (mode == M_FOVEA && want_pyr) ? m.out + 6 * plane : nullptr;
-    it.tag = tag;
-    it.managed = idx;
-    if (cloud) set_cloud(it, spec, nullptr, 0, nullptr, nullptr);
-    const int st = enqueue(ctx, it);
-    if (st != UGSM_OK) q->pool[(size_t)idx].busy = false;  // (rejected: the staging buffer is free again)
+    if (it.has_cloud) {
+        const int cs = check_cloud(ctx, spec, it);
+        if (cs != UGSM_OK) return cs;
+        it.spec = *spec;  // (copied now: the call is formed later)
+        it.spec.reserved = 0;
+    }
+    Queue *q = queue_of(ctx);
+    if (!q) return ctx_fail(ctx, UGSM_ERR_NOMEM, kNoMem);
+    const int r = room(ctx, q);
+    if (r != UGSM_OK) return r;
+    if (it.mem == MEM_MANAGED) {  // (only now: a pair the queue refuses is not copied)
+        const int ms = stage_managed(ctx, q, it);
+        if (ms != UGSM_OK) return ms;
+    }
+    const int st = no_throw(ctx, kNoMem, [&]() -> int {
+        it.seq = q->seq + 1;
+        it.fmt = ctx_hooks(ctx).input_format;  // (captured now: the call is formed later)
+        q->waiting.push_back(it);
+        q->seq = it.seq;
+        ctx_hooks(ctx).queue_busy = true;
+        // a pump that ran out of host memory leaves the pairs waiting for the next entry point's pump: that is not a rejection
+        (void)no_throw(ctx, kNoMem, [&]() -> int {
+            pump(ctx, q, true);
+            return UGSM_OK;
+        });
+        update_busy(ctx, q);
+        return UGSM_OK;
+    });
+    if (st != UGSM_OK && it.managed >= 0) q->pool[(size_t)it.managed].busy = false;  // (rejected: the staging buffer is free again)
     return st;
 }
 
@@ -644,180 +634,67 @@ int ugsm_queue_plan(const ugsm_config *cfg_in, int n_pairs, int *sizes, int cap)
 
 int ugsm_enqueue_full(ugsm_ctx *ctx, const uint8_t *d_rgbL, const uint8_t *d_rgbR, int W, int H, int stride, float *d_out, uint64_t tag)
 {
-    if (!ctx) return UGSM_ERR_BAD_ARG;
-    if (!d_rgbL || !d_rgbR || !d_out) return ctx_fail(ctx, UGSM_ERR_BAD_ARG, "ugsm_enqueue_full: null buffer");
-    const int g = check_geometry(ctx, W, H, stride, false);
-    if (g != UGSM_OK) return g;
-    Item it{};
-    it.mode = M_FULL;
-    it.mem = MEM_DEVICE;
-    it.L = d_rgbL;
-    it.R = d_rgbR;
-    it.W = W;
-    it.H = H;
-    it.stride = stride;
-    it.out[0] = d_out;
-    it.tag = tag;
-    it.managed = -1;
-    return enqueue(ctx, it);
+    return enqueue_pair(ctx, "ugsm_enqueue_full", Item{M_FULL, MEM_DEVICE, d_rgbL, d_rgbR, W, H, stride, 0, 0, {d_out}, tag}, 1);
 }
 
 int ugsm_enqueue_foveated(ugsm_ctx *ctx, const uint8_t *d_rgbL, const uint8_t *d_rgbR, int W, int H, int stride, int off_x, int off_y, float *d_stack,
                           float *d_pyrL, float *d_pyrR, uint64_t tag)
 {
-    if (!ctx) return UGSM_ERR_BAD_ARG;
-    if (!d_rgbL || !d_rgbR || !d_stack) return ctx_fail(ctx, UGSM_ERR_BAD_ARG, "ugsm_enqueue_foveated: null buffer");
-    const int g = check_geometry(ctx, W, H, stride, true);
-    if (g != UGSM_OK) return g;
-    Item it{};
-    it.mode = M_FOVEA;
-    it.mem = MEM_DEVICE;
-    it.L = d_rgbL;
-    it.R = d_rgbR;
-    it.W = W;
-    it.H = H;
-    it.stride = stride;
-    it.off_x = off_x;
-    it.off_y = off_y;
-    it.out[0] = d_stack;
-    it.out[3] = d_pyrL;
-    it.out[4] = d_pyrR;
-    it.tag = tag;
-    it.managed = -1;
-    return enqueue(ctx, it);
+    const Item it{M_FOVEA, MEM_DEVICE, d_rgbL, d_rgbR, W, H, stride, off_x, off_y, {d_stack, nullptr, nullptr, d_pyrL, d_pyrR}, tag};
+    return enqueue_pair(ctx, "ugsm_enqueue_foveated", it, 1);
 }
 
 int ugsm_enqueue_full_host(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, float *dispH, float *dispV, float *dispC,
                            uint64_t tag)
 {
-    if (!ctx) return UGSM_ERR_BAD_ARG;
-    if (!rgbL || !rgbR || !dispH || !dispV || !dispC) return ctx_fail(ctx, UGSM_ERR_BAD_ARG, "ugsm_enqueue_full_host: null buffer");
-    const int g = check_geometry(ctx, W, H, stride, false);
-    if (g != UGSM_OK) return g;
-    if (!(host_pinned(rgbL) && host_pinned(rgbR) && host_pinned(dispH) && host_pinned(dispV) && host_pinned(dispC)))
-        return ctx_fail(ctx, UGSM_ERR_BAD_ARG, "ugsm_enqueue_full_host: every host buffer must be page-locked (ugsm_host_alloc, hipHostMalloc or hipHostRegister); "
-                                               "ugsm_enqueue_full_managed takes any memory");
-    Item it{};
-    it.mode = M_FULL;
-    it.mem = MEM_PINNED;
-    it.L = rgbL;
-    it.R = rgbR;
-    it.W = W;
-    it.H = H;
-    it.stride = stride;
-    it.out[0] = dispH;
-    it.out[1] = dispV;
-    it.out[2] = dispC;
-    it.tag = tag;
-    it.managed = -1;
-    return enqueue(ctx, it);
+    return enqueue_pair(ctx, "ugsm_enqueue_full_host", Item{M_FULL, MEM_PINNED, rgbL, rgbR, W, H, stride, 0, 0, {dispH, dispV, dispC}, tag}, 3);
 }
 
 int ugsm_enqueue_foveated_host(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, int off_x, int off_y, float *stackH,
                                float *stackV, float *stackC, float *pyrL, float *pyrR, uint64_t tag)
 {
-    if (!ctx) return UGSM_ERR_BAD_ARG;
-    if (!rgbL || !rgbR || !stackH || !stackV || !stackC) return ctx_fail(ctx, UGSM_ERR_BAD_ARG, "ugsm_enqueue_foveated_host: null buffer");
-    const int g = check_geometry(ctx, W, H, stride, true);
-    if (g != UGSM_OK) return g;
-    bool pinned = host_pinned(rgbL) && host_pinned(rgbR) && host_pinned(stackH) && host_pinned(stackV) && host_pinned(stackC);
-    if (pyrL) pinned = pinned && host_pinned(pyrL);
-    if (pyrR) pinned = pinned && host_pinned(pyrR);
-    if (!pinned)
-        return ctx_fail(ctx, UGSM_ERR_BAD_ARG, "ugsm_enqueue_foveated_host: every host buffer must be page-locked (ugsm_host_alloc, hipHostMalloc or hipHostRegister); "
-                                               "ugsm_enqueue_foveated_managed takes any memory");
-    Item it{};
-    it.mode = M_FOVEA;
-    it.mem = MEM_PINNED;
-    it.L = rgbL;
-    it.R = rgbR;
-    it.W = W;
-    it.H = H;
-    it.stride = stride;
-    it.off_x = off_x;
-    it.off_y = off_y;
-    it.out[0] = stackH;
-    it.out[1] = stackV;
-    it.out[2] = stackC;
-    it.out[3] = pyrL;
-    it.out[4] = pyrR;
-    it.tag = tag;
-    it.managed = -1;
-    return enqueue(ctx, it);
+    const Item it{M_FOVEA, MEM_PINNED, rgbL, rgbR, W, H, stride, off_x, off_y, {stackH, stackV, stackC, pyrL, pyrR}, tag};
+    return enqueue_pair(ctx, "ugsm_enqueue_foveated_host", it, 3);
 }
 
 int ugsm_enqueue_full_managed(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, uint64_t tag)
 {
-    return enqueue_managed(ctx, M_FULL, rgbL, rgbR, W, H, stride, 0, 0, 0, tag);
+    return enqueue_pair(ctx, "ugsm_enqueue_full_managed", Item{M_FULL, MEM_MANAGED, rgbL, rgbR, W, H, stride, 0, 0, {}, tag}, 0);
 }
 
 int ugsm_enqueue_foveated_managed(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, int off_x, int off_y, int want_pyramids,
                                   uint64_t tag)
 {
-    return enqueue_managed(ctx, M_FOVEA, rgbL, rgbR, W, H, stride, off_x, off_y, want_pyramids, tag);
+    const Item it{M_FOVEA, MEM_MANAGED, rgbL, rgbR, W, H, stride, off_x, off_y, {}, tag, want_pyramids != 0};
+    return enqueue_pair(ctx, "ugsm_enqueue_foveated_managed", it, 0);
 }
 
 int ugsm_enqueue_full_cloud(ugsm_ctx *ctx, const uint8_t *d_rgbL, const uint8_t *d_rgbR, int W, int H, int stride, float *d_out,
                             const ugsm_queue_cloud *spec, void *d_points, long long cap_points, long long *d_count, uint64_t tag)
 {
-    if (!ctx) return UGSM_ERR_BAD_ARG;
-    if (!d_rgbL || !d_rgbR || !d_out) return ctx_fail(ctx, UGSM_ERR_BAD_ARG, "ugsm_enqueue_full_cloud: null buffer");
-    const int g = check_geometry(ctx, W, H, stride, false);
-    if (g != UGSM_OK) return g;
-    const int cs = check_cloud(ctx, spec, W, H, true, d_points, cap_points, d_count, nullptr);
-    if (cs != UGSM_OK) return cs;
-    Item it{};
-    it.mode = M_FULL;
-    it.mem = MEM_DEVICE;
-    it.L = d_rgbL;
-    it.R = d_rgbR;
-    it.W = W;
-    it.H = H;
-    it.stride = stride;
-    it.out[0] = d_out;
-    it.tag = tag;
-    it.managed = -1;
-    set_cloud(it, spec, d_points, cap_points, d_count, nullptr);
-    return enqueue(ctx, it);
+    const Item it{M_FULL, MEM_DEVICE, d_rgbL, d_rgbR, W, H, stride, 0, 0, {d_out}, tag};
+    return enqueue_pair(ctx, "ugsm_enqueue_full_cloud", with_cloud(it, d_points, cap_points, d_count), 1, spec);
 }
 
 int ugsm_enqueue_foveated_cloud(ugsm_ctx *ctx, const uint8_t *d_rgbL, const uint8_t *d_rgbR, int W, int H, int stride, int off_x, int off_y,
                                 float *d_stack, const ugsm_queue_cloud *spec, void *d_points, long long cap_points, long long *d_count,
                                 long long *d_level_counts, uint64_t tag)
 {
-    if (!ctx) return UGSM_ERR_BAD_ARG;
-    if (!d_rgbL || !d_rgbR || !d_stack) return ctx_fail(ctx, UGSM_ERR_BAD_ARG, "ugsm_enqueue_foveated_cloud: null buffer");
-    const int g = check_geometry(ctx, W, H, stride, true);
-    if (g != UGSM_OK) return g;
-    const int cs = check_cloud(ctx, spec, W, H, true, d_points, cap_points, d_count, d_level_counts);
-    if (cs != UGSM_OK) return cs;
-    Item it{};
-    it.mode = M_FOVEA;
-    it.mem = MEM_DEVICE;
-    it.L = d_rgbL;
-    it.R = d_rgbR;
-    it.W = W;
-    it.H = H;
-    it.stride = stride;
-    it.off_x = off_x;
-    it.off_y = off_y;
-    it.out[0] = d_stack;
-    it.tag = tag;
-    it.managed = -1;
-    set_cloud(it, spec, d_points, cap_points, d_count, d_level_counts);
-    return enqueue(ctx, it);
+    const Item it{M_FOVEA, MEM_DEVICE, d_rgbL, d_rgbR, W, H, stride, off_x, off_y, {d_stack}, tag};
+    return enqueue_pair(ctx, "ugsm_enqueue_foveated_cloud", with_cloud(it, d_points, cap_points, d_count, d_level_counts), 1, spec);
 }
 
 int ugsm_enqueue_full_cloud_managed(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, const ugsm_queue_cloud *spec,
                                     uint64_t tag)
 {
-    return enqueue_managed(ctx, M_FULL, rgbL, rgbR, W, H, stride, 0, 0, 0, tag, spec, true);
+    return enqueue_pair(ctx, "ugsm_enqueue_full_cloud_managed", with_cloud(Item{M_FULL, MEM_MANAGED, rgbL, rgbR, W, H, stride, 0, 0, {}, tag}), 0, spec);
 }
 
 int ugsm_enqueue_foveated_cloud_managed(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, int off_x, int off_y,
                                         const ugsm_queue_cloud *spec, uint64_t tag)
 {
-    return enqueue_managed(ctx, M_FOVEA, rgbL, rgbR, W, H, stride, off_x, off_y, 0, tag, spec, true);
+    const Item it{M_FOVEA, MEM_MANAGED, rgbL, rgbR, W, H, stride, off_x, off_y, {}, tag};
+    return enqueue_pair(ctx, "ugsm_enqueue_foveated_cloud_managed", with_cloud(it), 0, spec);
 }
 
 int ugsm_done_cloud(ugsm_ctx *ctx, ugsm_cloud_result *out)
