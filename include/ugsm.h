@@ -44,7 +44,9 @@ extern "C" {
                                ugsm_stage_restrict, ugsm_seeded_pixel_iterations; the seeded (warm) foveated call -- ugsm_submit_foveated_warm,
                                ugsm_submit_foveated_warm_field, ugsm_match_foveated_warm, ugsm_stage_warm_stack, ugsm_fovea_warm_pixel_iterations;
                                the full-mode call in two halves -- ugsm_submit_full_coarse, ugsm_submit_full_fine, ugsm_match_full_coarse,
-                               ugsm_match_full_fine, ugsm_stage_prolong, ugsm_coarse_pixel_iterations
+                               ugsm_match_full_fine, ugsm_stage_prolong, ugsm_coarse_pixel_iterations; checked full-mode pairs through the queue --
+                               ugsm_submit_full_checked_host, ugsm_enqueue_full_checked, ugsm_enqueue_full_checked_managed,
+                               ugsm_enqueue_full_checked_cloud, ugsm_enqueue_full_checked_cloud_managed, ugsm_checked_result, ugsm_done_checked
                                6: the kernel choices follow what is in flight, not ugsm_config.slots: ugsm_plan_level takes `alone`, ugsm_plan_level_in_frame
                                is gone, ugsm_level_plan.latency_policy is .alone; ugsm_enqueue_* returns UGSM_OK once the pair is accepted (a failed
                                CALL is reported through ugsm_completion.status only); the fovea shard carries a status word (a rank that fails still
@@ -360,10 +362,21 @@ int ugsm_submit_foveated_batch_host(ugsm_ctx *ctx, int slot, int n, const uint8_
  * 1 .. UGSM_MAX_BATCH: UGSM_ERR_BAD_ARG; contexts with early_exit_threshold > 0 or kernel_path 1: UGSM_ERR_BAD_ARG (ugsm_set_lr_check's rule for
  * the lockstep check: they have no batch dimension); the size errors of ugsm_submit_full as there; pairs outstanding in the queue:
  * UGSM_ERR_STATE; a buffer that cannot grow: UGSM_ERR_NOMEM, the context usable afterwards.
- * NOT built: a queue form (ugsm_enqueue_*); the page-locked _host kind.
+ * The queue form: ugsm_enqueue_full_checked[_managed | _cloud | _cloud_managed], below ("checked pairs through the queue"); from page-locked
+ * memory: ugsm_submit_full_checked_host.
+ * NOT built: a seeded or coarse / fine checked call; of the queue form, the page-locked _host kind (device and managed pairs only).
  * Asynchronous on `slot`. */
 int ugsm_submit_full_checked(ugsm_ctx *ctx, int slot, int n, const uint8_t *const *d_rgbL, const uint8_t *const *d_rgbR,
                              int W, int H, int stride, float *const *d_out, float *const *d_back, float tau);
+/* The same call from page-locked host memory, in and out, as ugsm_submit_full_batch_host: the images of the n pairs go up, both directions run
+ * in lockstep, the checked forward planes come down into dispH / dispV / dispC [k], and the right camera's checked planes into backH / backV /
+ * backC [k] for the pairs that ask for them -- the three arrays NULL (no pair asks), or all three given with, per pair, all three entries set
+ * or all three NULL; anything else is UGSM_ERR_BAD_ARG.  Every buffer page-locked, else UGSM_ERR_BAD_ARG.  The planes are the fields of
+ * ugsm_submit_full_checked, bit for bit; its refusals, counts and memory, plus one device field per pair (two for a pair that takes its back
+ * planes) of result staging in the slot.  Asynchronous on `slot`: every buffer stays valid and untouched until ugsm_wait(ctx, slot). */
+int ugsm_submit_full_checked_host(ugsm_ctx *ctx, int slot, int n, const uint8_t *const *rgbL, const uint8_t *const *rgbR,
+                                  int W, int H, int stride, float *const *dispH, float *const *dispV, float *const *dispC,
+                                  float *const *backH, float *const *backV, float *const *backC, float tau);
 /* Blocking, one pair, any host memory in and out, as ugsm_match_full.  backH / backV / backC (the right camera's checked planes): all three
  * or none (NULL); anything else is UGSM_ERR_BAD_ARG. */
 int ugsm_match_full_checked(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride,
@@ -955,6 +968,49 @@ typedef struct ugsm_cloud_result {
 /* The cloud of the pair the last ugsm_next_done reported.  UGSM_ERR_STATE if that pair carried no managed cloud, if its call failed, or if
  * nothing has been reported yet. */
 int ugsm_done_cloud(ugsm_ctx *ctx, ugsm_cloud_result *out);
+
+/* ---- checked pairs through the queue: both directions of the pairs of a call in lockstep, each pair with a tau of its own -----------------
+ *
+ * A plain ugsm_enqueue_full* on a context with ugsm_set_lr_check(ctx, tau, UGSM_LR_FULL) is checked the context's way: its call goes pair by
+ * pair, every pair matched a second time with the images exchanged, the right camera's field thrown away, tau one setting for everything
+ * outstanding.  These forms carry the check with the pair instead: the call a pair goes out in is ONE ugsm_submit_full_checked[_host] of its
+ * pairs -- the pyramids once, 2 n fields in lockstep, one check launch -- and launches nothing that call does not launch.  They neither read
+ * nor change ugsm_set_lr_check; plain pairs on the same context behave exactly as before.
+ *   The contract, bit for bit: d_out, and d_back where given, of a pair are what ugsm_submit_full_checked writes for that pair alone with that
+ * tau (dx and dy the unchecked matches', the confidences zeroed where the check fails), in the input format captured at enqueue, however the
+ * queue grouped the pairs; the managed planes are the same fields.  The cloud forms: byte for byte, count included, what ugsm_point_cloud
+ * writes for the pair's CHECKED forward planes and left image -- a compact cloud with min_conf > 0 leaves the marked pixels out.
+ *   Grouping: pairs of one call are all checked, with one bit-equal tau, or all plain; a pair of another tau, a plain pair, a pair with or
+ * without a cloud ends the group as a pair of another kind does.  Pairs of one call may differ in whether they take the right camera's field.
+ * Call sizes, the stagger, back-pressure and the (slots + 1) x batch limit are those of every other pair (ugsm_queue_plan).
+ *   d_back (device forms): may be NULL -- that pair's right-to-left field then stays in the slot.  want_back (managed forms): nonzero lends the
+ * right camera's checked planes too, through ugsm_done_checked; ugsm_completion.result[0 .. 2] are the checked forward planes (NULL for a cloud
+ * pair without want_planes), result[3] and result[4] NULL.
+ *   Refused with nothing enqueued, after the refusals of ugsm_enqueue_full[_managed] and before those of the cloud spec and of a full queue:
+ * !(tau > 0), NaN included: UGSM_ERR_BAD_ARG; a context with early_exit_threshold > 0 or kernel_path 1: UGSM_ERR_BAD_ARG; a runtime without the
+ * checked call: UGSM_ERR_STATE.  A call that fails -- UGSM_ERR_NOMEM where the level buffers cannot hold 2 n full fields: sixteen fields for a
+ * call of eight, 17 GB at 16 MP -- is reported through each pair's ugsm_completion.status once the slot has drained, as ever.
+ *   Memory of the managed forms: per slot, one device field per pair of a call (two for a pair with want_back) of result staging, and the
+ * page-locked staging of a pair grows by three planes with want_back.
+ *   Out of scope: a page-locked _host kind of these forms; foveated pairs (UGSM_LR_FOVEATED already runs their check in lockstep through the
+ * queue); seeded or coarse / fine pairs. */
+int ugsm_enqueue_full_checked(ugsm_ctx *ctx, const uint8_t *d_rgbL, const uint8_t *d_rgbR, int W, int H, int stride, float *d_out,
+                              float *d_back /* may be NULL */, float tau, uint64_t tag);
+int ugsm_enqueue_full_checked_managed(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, float tau,
+                                      int want_back, uint64_t tag);
+int ugsm_enqueue_full_checked_cloud(ugsm_ctx *ctx, const uint8_t *d_rgbL, const uint8_t *d_rgbR, int W, int H, int stride, float *d_out,
+                                    float *d_back /* may be NULL */, float tau, const ugsm_queue_cloud *spec, void *d_points,
+                                    long long cap_points, long long *d_count, uint64_t tag);
+int ugsm_enqueue_full_checked_cloud_managed(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, float tau,
+                                            int want_back, const ugsm_queue_cloud *spec, uint64_t tag);
+typedef struct ugsm_checked_result {
+    float *back[3];                     /* managed with want_back: page-locked H, V, C planes of the right camera's checked field, valid until the
+                                           NEXT ugsm_next_done on this context; else NULL */
+    long long marked_fwd, marked_back;  /* what ugsm_last_lr_marked_pair answers for the pair */
+} ugsm_checked_result;
+/* For the pair the last ugsm_next_done reported.  UGSM_ERR_STATE if that was no checked pair, if its call failed, or if nothing has been
+ * reported yet. */
+int ugsm_done_checked(ugsm_ctx *ctx, ugsm_checked_result *out);
 
 /* Row f-3: MatchGPULib::hierarchicalDisparity (MatchGPULib.cpp:2589-2701, kernel MatchLib.cu:435-462):
  * one full-resolution (dx, dy, conf) field from the foveated stacks -- the coarsest fovea level (the whole

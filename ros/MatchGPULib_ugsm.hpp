@@ -325,7 +325,7 @@ public:
         const int W = L->image.cols, H = L->image.rows;
         if (R->image.cols != W || R->image.rows != H) return UGSM_ERR_SIZE_MISMATCH;
         int st = ugsm_enqueue_full_managed(ctx_, L->image.data, R->image.data, W, H, (int)L->image.step, tag);
-        if (st == UGSM_OK) { kinds_[tag] = Kind{false, false, W, H, false}; st = ugsm_flush(ctx_); }
+        if (st == UGSM_OK) { kinds_[tag] = Kind{false, false, W, H, false, false}; st = ugsm_flush(ctx_); }
         return report(st);
     }
     template <class ImgPtr>
@@ -335,7 +335,7 @@ public:
         if (R->image.cols != W || R->image.rows != H) return UGSM_ERR_SIZE_MISMATCH;
         if (ugsm_fovea_dims(W, H, 14, foveatelevel, &fovW, &fovH) != UGSM_OK) return UGSM_ERR_BAD_ARG;
         int st = ugsm_enqueue_foveated_managed(ctx_, L->image.data, R->image.data, W, H, (int)L->image.step, 0, 0, want_pyramids ? 1 : 0, tag);
-        if (st == UGSM_OK) { kinds_[tag] = Kind{true, want_pyramids, W, H, false}; st = ugsm_flush(ctx_); }
+        if (st == UGSM_OK) { kinds_[tag] = Kind{true, want_pyramids, W, H, false, false}; st = ugsm_flush(ctx_); }
         return report(st);
     }
     // ... and with the pair's coloured cloud (include/ugsm.h, "the cloud from the queue"): the cloud of doReconstructionRGB /
@@ -347,7 +347,7 @@ public:
         const int W = L->image.cols, H = L->image.rows;
         if (R->image.cols != W || R->image.rows != H) return UGSM_ERR_SIZE_MISMATCH;
         int st = ugsm_enqueue_full_cloud_managed(ctx_, L->image.data, R->image.data, W, H, (int)L->image.step, &spec, tag);
-        if (st == UGSM_OK) { kinds_[tag] = Kind{false, false, W, H, true}; st = ugsm_flush(ctx_); }
+        if (st == UGSM_OK) { kinds_[tag] = Kind{false, false, W, H, true, false}; st = ugsm_flush(ctx_); }
         return report(st);
     }
     template <class ImgPtr>
@@ -357,7 +357,28 @@ public:
         if (R->image.cols != W || R->image.rows != H) return UGSM_ERR_SIZE_MISMATCH;
         if (ugsm_fovea_dims(W, H, 14, foveatelevel, &fovW, &fovH) != UGSM_OK) return UGSM_ERR_BAD_ARG;
         int st = ugsm_enqueue_foveated_cloud_managed(ctx_, L->image.data, R->image.data, W, H, (int)L->image.step, 0, 0, &spec, tag);
-        if (st == UGSM_OK) { kinds_[tag] = Kind{true, false, W, H, true}; st = ugsm_flush(ctx_); }
+        if (st == UGSM_OK) { kinds_[tag] = Kind{true, false, W, H, true, false}; st = ugsm_flush(ctx_); }
+        return report(st);
+    }
+    // ... and checked (include/ugsm.h, "checked pairs through the queue"): both directions of the pairs of a call in lockstep with THIS pair's
+    // tau (> 0), whatever setLRCheck holds; the planes nextDone lends are the checked forward field.  want_back: the right camera's checked
+    // planes too, through Done::checked.back.  Full mode only (the foveated queue forms are checked through setLRCheck's UGSM_LR_FOVEATED).
+    template <class ImgPtr>
+    int enqueueMatchChecked(ImgPtr L, ImgPtr R, float tau, bool want_back, uint64_t tag)
+    {
+        const int W = L->image.cols, H = L->image.rows;
+        if (R->image.cols != W || R->image.rows != H) return UGSM_ERR_SIZE_MISMATCH;
+        int st = ugsm_enqueue_full_checked_managed(ctx_, L->image.data, R->image.data, W, H, (int)L->image.step, tau, want_back ? 1 : 0, tag);
+        if (st == UGSM_OK) { kinds_[tag] = Kind{false, false, W, H, false, true}; st = ugsm_flush(ctx_); }
+        return report(st);
+    }
+    template <class ImgPtr>
+    int enqueueMatchCheckedCloud(ImgPtr L, ImgPtr R, float tau, bool want_back, const ugsm_queue_cloud &spec, uint64_t tag)
+    {
+        const int W = L->image.cols, H = L->image.rows;
+        if (R->image.cols != W || R->image.rows != H) return UGSM_ERR_SIZE_MISMATCH;
+        int st = ugsm_enqueue_full_checked_cloud_managed(ctx_, L->image.data, R->image.data, W, H, (int)L->image.step, tau, want_back ? 1 : 0, &spec, tag);
+        if (st == UGSM_OK) { kinds_[tag] = Kind{false, false, W, H, true, true}; st = ugsm_flush(ctx_); }
         return report(st);
     }
     int outstanding() const { return (int)kinds_.size(); }
@@ -372,6 +393,8 @@ public:
         float *planes[5];
         bool has_cloud;           // the pair was enqueued with enqueueMatchCloud / enqueueStackCloud and its call succeeded: ...
         ugsm_cloud_result cloud;  // ... its cloud (ugsm_done_cloud): page-locked records of the library, valid until the next nextDone
+        bool is_checked;              // the pair was enqueued with enqueueMatchChecked[Cloud] and its call succeeded: ...
+        ugsm_checked_result checked;  // ... the pixels its check marked and, with want_back, the right camera's planes (ugsm_done_checked)
     };
     // true: *out filled -- the oldest pair has been REPORTED and no longer counts as outstanding; out->status says how its call went (a
     // failed call: logged to stderr, planes null; the caller drops whatever it keeps under the tag).  false: nothing outstanding, or
@@ -387,13 +410,15 @@ public:
         for (int i = 0; i < 5; i++) out->planes[i] = c.status == UGSM_OK ? c.result[i] : nullptr;
         out->cloud = ugsm_cloud_result();
         out->has_cloud = k.cloud && c.status == UGSM_OK && report(ugsm_done_cloud(ctx_, &out->cloud)) == UGSM_OK;
+        out->checked = ugsm_checked_result();
+        out->is_checked = k.checked && c.status == UGSM_OK && report(ugsm_done_checked(ctx_, &out->checked)) == UGSM_OK;
         return true;
     }
 
 private:
     ugsm_ctx *ctx_;
     int levels_ = 0;  // the context's pyramid levels (matchCoarse / matchFine size a level's field by them)
-    struct Kind { bool foveated, pyramids; int W, H; bool cloud; };
+    struct Kind { bool foveated, pyramids; int W, H; bool cloud, checked; };
     std::map<uint64_t, Kind> kinds_;
     int report(int st)
     {

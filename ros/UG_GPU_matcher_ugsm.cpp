@@ -22,6 +22,8 @@
 //
 // Nor this: the parameter `lr_check_tau` (default 0 = off).  With tau > 0 the blocking full-mode paths (topic and service) run the LR check for the call:
 // both directions in one lockstep call (ugsm_match_full_checked), the confidence plane zeroed where the match does not point back within tau pixels.
+// With frames_in_flight > 1 the full-mode topic path enqueues the checked queue forms with that tau (the shim's enqueueMatchChecked, and
+// enqueueMatchCheckedCloud with publish_cloud: a compact cloud with cloud_min_conf > 0 then leaves the marked pixels out); tau is read per frame.
 //
 // Nor this: the parameter `seed_level` (default -1 = off).  With a level s >= 0 the blocking full-mode topic path keeps every frame's result and starts the
 // next frame of the same size at level s from it (the shim's matchSeeded: ugsm_match_full_seeded) instead of from the zero seed at the top level; the
@@ -314,7 +316,10 @@ private:
             if (fov == 1) mgpu_->initStack(L, R);
             // (a status other than UGSM_OK = the pair was REJECTED and nothing is outstanding under the tag: include/ugsm.h, ugsm_enqueue_*)
             // (the cloud forms carry no pyramid stacks: with publish_cloud the foveated path publishes the H, V, C stacks and the cloud)
-            const int st = publish_cloud_ ? (fov == 1 ? mgpu_->enqueueStackCloud(L, R, cloud_spec_, tag) : mgpu_->enqueueMatchCloud(L, R, cloud_spec_, tag))
+            // (lr_check_tau > 0, full mode: the checked forms, the pair's own tau; the node publishes the left camera's field only)
+            const float tau = fov == 1 ? 0.0f : lr_check_tau();
+            const int st = tau > 0.0f ? (publish_cloud_ ? mgpu_->enqueueMatchCheckedCloud(L, R, tau, false, cloud_spec_, tag) : mgpu_->enqueueMatchChecked(L, R, tau, false, tag))
+                         : publish_cloud_ ? (fov == 1 ? mgpu_->enqueueStackCloud(L, R, cloud_spec_, tag) : mgpu_->enqueueMatchCloud(L, R, cloud_spec_, tag))
                                           : (fov == 1 ? mgpu_->enqueueStack(L, R, true, tag) : mgpu_->enqueueMatch(L, R, tag));
             if (st != UGSM_OK) { ROS_ERROR("ugsm enqueue failed: %s", ugsm_status_string(st)); return; }
             in_flight_[tag] = InFlight{L->header, R->header};

@@ -3,6 +3,8 @@
 
     python tools/lr_bench.py [--parent-tree DIR] [--rounds 3] [--out profiles/lr_fovea_bench.json]
     python tools/lr_bench.py --full [--parent-tree DIR] [--rounds 3]      # the full-mode calls: full_main below, profiles/lr_full_bench.json
+    python tools/lr_bench.py --queue [--parent-tree DIR] [--rounds 3]     # checked full-mode pairs through the queue: queue_main below,
+                                                                          # profiles/lr_queue_bench.json
 
 At 16 MP (4928 x 3264) and 1080p, 14 / 7 levels, images resident on the device, events off, every measurement a child process of its own
 (one context per process, as tools/ab.py), the configurations of a group taking turns round by round, every child's value kept:
@@ -37,10 +39,13 @@ ap.add_argument("--burst", type=int, default=96)
 ap.add_argument("--tau", type=float, default=1.0)
 ap.add_argument("--sizes", nargs="*", default=list(SIZES))
 ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "lr_fovea_bench.json"))
+ap.add_argument("--out-partial", default=None, help="--queue: also write what has been measured so far to this file after every child")
 ap.add_argument("--full", action="store_true", help="the full-mode table (full_main below) instead of the foveated one; writes profiles/lr_full_bench.json")
+ap.add_argument("--queue", action="store_true", help="checked full-mode pairs through the queue (queue_main below); writes profiles/lr_queue_bench.json")
+ap.add_argument("--arm", choices=["plain", "ctx", "checked", "checked_back", "managed", "managed_back"], default="plain", help="(internal, --child queue)")
 ap.add_argument("--form", choices=["plain", "seq", "new"], default="plain", help="(internal, --child full)")
 ap.add_argument("--n", type=int, default=1, help="(internal, --child full) pairs per call")
-ap.add_argument("--child", choices=["call", "burst", "full"], help="(internal) measure in this process, print one JSON line")
+ap.add_argument("--child", choices=["call", "burst", "full", "queue"], help="(internal) measure in this process, print one JSON line")
 ap.add_argument("--tree", default=ROOT, help="(internal) the tree whose package the child loads")
 ap.add_argument("--checked", type=int, default=0, help="(internal)")
 ap.add_argument("--size", default="16mp", help="(internal)")
@@ -170,9 +175,106 @@ def full_main():
     print(f"wrote {out}")
 
 
-def measure(kind, size, tree, checked, form="plain", n=1):
+def queue_child():
+    """A queue burst of --burst full-mode pairs on four slots with batches of eight (every pair the same two images, a ring of (slots + 1) x batch
+    outputs), completions polled after every enqueue and drained at the end, in pairs per second after a warm-up burst of 2 x slots x batch.  The arms:
+    plain -- ugsm_enqueue_full; ctx -- the same on a context with ugsm_set_lr_check(tau, UGSM_LR_FULL): the context's own check, pair by pair;
+    checked, checked_back -- ugsm_enqueue_full_checked without and with d_back; managed, managed_back -- ugsm_enqueue_full_checked_managed from
+    pageable host images, without and with want_back."""
+    sys.path.insert(0, args.tree)
+    from ug_stereomatcher_amd import _lib, synth
+    assert os.path.dirname(os.path.abspath(_lib.__file__)) == os.path.join(os.path.abspath(args.tree), "ug_stereomatcher_amd")
+    W, H = SIZES[args.size]
+    L, R = synth.make_pair(W, H, synth.BASE_SEED + 2)[:2]
+    slots, B, arm = 4, 8, args.arm
+    with _lib.Context(levels=LEVELS, slots=slots, batch=B) as c:
+        if arm == "ctx":
+            c.set_lr_check(args.tau, _lib.UGSM_LR_FULL)
+        cap = (slots + 1) * B
+        device = not arm.startswith("managed")
+        dL, dR = (c.to_device(L), c.to_device(R)) if device else (None, None)
+        ring = [c.alloc(3 * W * H * 4) for _ in range(cap)] if device else []
+        back = [c.alloc(3 * W * H * 4) for _ in range(cap)] if arm == "checked_back" else [None] * cap
+
+        def enqueue(k):
+            if arm in ("plain", "ctx"):
+                c.enqueue_full(dL, dR, W, H, 3 * W, ring[k % cap], k)
+            elif device:
+                c.enqueue_full_checked(dL, dR, W, H, 3 * W, ring[k % cap], back[k % cap], args.tau, k)
+            else:
+                c.enqueue_full_checked_managed(L, R, args.tau, arm == "managed_back", k)
+
+        def run(m):
+            sizes, last = [], None
+            for k in range(m):
+                enqueue(k)
+                while True:
+                    d = c.next_done(False)
+                    if d is None:
+                        break
+                    if d.call_index != last:
+                        sizes.append(d.call_pairs)
+                        last = d.call_index
+            for d in c.drain():
+                if d.call_index != last:
+                    sizes.append(d.call_pairs)
+                    last = d.call_index
+            return sizes
+        run(2 * slots * B)
+        t0 = time.perf_counter()
+        sizes = run(args.burst)
+        dt = time.perf_counter() - t0
+        out = dict(pairs_per_s=args.burst / dt, calls=sizes, device_bytes=c.device_bytes())
+    print("LRBENCH " + json.dumps(out), flush=True)
+
+
+def queue_main():
+    """--queue: what a checked full-mode pair costs through the queue, at 16 MP and 1080p, 14 levels, four slots, batch 8, a burst of --burst
+    (128) pairs, every measurement a child process, the arms taking turns round by round:
+      a         plain pairs;
+      b         the parent commit's only way (--parent-tree; this build's where none is given): ugsm_enqueue_full on a context with
+                ugsm_set_lr_check(tau, UGSM_LR_FULL);  b_this: the same on this build, where a parent was measured;
+      c, c_back ugsm_enqueue_full_checked without / with d_back;
+      d, d_back ugsm_enqueue_full_checked_managed from host memory, without / with want_back.
+    Medians and ranges of pairs/s are kept; no ratio is fixed in advance (DESIGN.md section 8 quotes the table)."""
+    parent = os.path.abspath(args.parent_tree) if args.parent_tree else None
+    if parent and not os.path.exists(os.path.join(parent, "ug_stereomatcher_amd", "libugsm.so")):
+        raise SystemExit(f"{parent}: no built ug_stereomatcher_amd/libugsm.so")
+    old = parent or ROOT
+    burst = args.burst if args.burst != ap.get_default("burst") else 128
+    result = dict(tool="tools/lr_bench.py --queue", levels=LEVELS, tau=args.tau, rounds=args.rounds, burst=burst, slots=4, batch=8,
+                  parent_measured=bool(parent), sizes={})
+    for size in args.sizes:
+        arms = {"a": (ROOT, "plain"), "b": (old, "ctx"), "c": (ROOT, "checked"), "c_back": (ROOT, "checked_back"), "d": (ROOT, "managed"),
+                "d_back": (ROOT, "managed_back")}
+        if parent:
+            arms["b_this"] = (ROOT, "ctx")
+        kept = {k: [] for k in arms}
+        for rnd in range(args.rounds):
+            names = list(arms)
+            for name in (names if rnd % 2 == 0 else names[::-1]):     # alternating order
+                tree, arm = arms[name]
+                kept[name].append(measure("queue", size, tree, 0, arm=arm, burst=burst))
+                print(size, name, kept[name][-1], flush=True)
+                if args.out_partial:                                  # (every child's value is on disk as soon as it exists)
+                    json.dump(dict(result, sizes=dict(result["sizes"], **{size: dict(children=kept)})), open(args.out_partial, "w"), indent=1, sort_keys=True)
+        med = {k: statistics.median(v["pairs_per_s"] for v in kept[k]) for k in arms}
+        rng = {k: max(v["pairs_per_s"] for v in kept[k]) - min(v["pairs_per_s"] for v in kept[k]) for k in arms}
+        row = dict(W=SIZES[size][0], H=SIZES[size][1], children=kept, median_pairs_per_s=med, range_pairs_per_s=rng, b_range_pairs_per_s=rng["b"],
+                   c_over_b=med["c"] / med["b"], a_over_c=med["a"] / med["c"], a_over_b=med["a"] / med["b"], c_back_over_c=med["c_back"] / med["c"],
+                   d_over_c=med["d"] / med["c"], c_beats_b_by_more_than_b_range=bool(med["c"] - med["b"] > rng["b"]))
+        result["sizes"][size] = row
+        print(json.dumps({k: v for k, v in row.items() if k != "children"}), flush=True)
+    out = args.out if args.out != ap.get_default("out") else os.path.join(ROOT, "profiles", "lr_queue_bench.json")
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    json.dump(result, open(out, "w"), indent=1, sort_keys=True)
+    print(f"wrote {out}")
+
+
+def measure(kind, size, tree, checked, form="plain", n=1, arm="plain", burst=None):
     cmd = [sys.executable, os.path.abspath(__file__), "--child", kind, "--size", size, "--tree", tree, "--checked", str(int(checked)),
-           "--reps", str(args.reps), "--warmup", str(args.warmup), "--burst", str(args.burst), "--tau", str(args.tau), "--form", form, "--n", str(n)]
+           "--reps", str(args.reps), "--warmup", str(args.warmup), "--burst", str(burst or args.burst), "--tau", str(args.tau), "--form", form, "--n", str(n),
+           "--arm", arm]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=240)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("LRBENCH ")]
     if r.returncode != 0 or not lines:
@@ -224,7 +326,11 @@ def main():
 if __name__ == "__main__":
     if args.child == "full":
         full_child()
+    elif args.child == "queue":
+        queue_child()
     elif args.child:
         child()
+    elif args.queue:
+        queue_main()
     else:
         full_main() if args.full else main()

@@ -77,6 +77,9 @@ EXPORTS = [
     "ugsm_submit_foveated_warm", "ugsm_submit_foveated_warm_field", "ugsm_match_foveated_warm", "ugsm_stage_warm_stack", "ugsm_fovea_warm_pixel_iterations",
     # the full-mode call in two halves
     "ugsm_submit_full_coarse", "ugsm_submit_full_fine", "ugsm_match_full_coarse", "ugsm_match_full_fine", "ugsm_stage_prolong", "ugsm_coarse_pixel_iterations",
+    # checked full-mode pairs through the queue
+    "ugsm_submit_full_checked_host", "ugsm_enqueue_full_checked", "ugsm_enqueue_full_checked_managed", "ugsm_enqueue_full_checked_cloud",
+    "ugsm_enqueue_full_checked_cloud_managed", "ugsm_done_checked",
 ]
 # ... and what include/ugsm_dev.h adds (libugsm_dev.so only)
 DEV_EXPORTS = ["ugsm_stage_poly_probe", "ugsm_stage_div3_probe", "ugsm_stage_div_probe", "ugsm_stage_range_words", "ugsm_stage_iterate_rgb8", "ugsm_stage_level0_direct"]
@@ -134,6 +137,11 @@ class CloudResult(C.Structure):
     """ugsm_cloud_result (include/ugsm.h): what ugsm_done_cloud reports."""
     _fields_ = [("points", C.c_void_p), ("count", C.c_longlong), ("stored", C.c_longlong), ("point_step", C.c_int), ("levels", C.c_int),
                 ("level_counts", C.c_longlong * UGSM_MAX_LEVELS)]
+
+
+class CheckedResult(C.Structure):
+    """ugsm_checked_result (include/ugsm.h): what ugsm_done_checked reports."""
+    _fields_ = [("back", C.POINTER(C.c_float) * 3), ("marked_fwd", C.c_longlong), ("marked_back", C.c_longlong)]
 
 
 def queue_cloud(P1, P2, params: CloudParams, max_points: int = 0, want_planes: bool = False) -> QueueCloud:
@@ -290,6 +298,7 @@ def load(dev: bool = False):
     lib.ugsm_match_foveated_multi_checked.argtypes = [vp, vp, vp, i, i, i, i, ip, ip, pp, pp, pp, C.c_float]
     lib.ugsm_submit_full_checked.argtypes = [vp, i, i, pp, pp, i, i, i, pp, pp, C.c_float]
     lib.ugsm_match_full_checked.argtypes = [vp, vp, vp, i, i, i, vp, vp, vp, vp, vp, vp, C.c_float]
+    lib.ugsm_submit_full_checked_host.argtypes = [vp, i, i, pp, pp, i, i, i, pp, pp, pp, pp, pp, pp, C.c_float]
     lib.ugsm_last_lr_marked_pair.argtypes = [vp, i, i, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
     lib.ugsm_submit_full_seeded.argtypes = [vp, i, i, pp, pp, i, i, i, pp, i, pp]
     lib.ugsm_match_full_seeded.argtypes = [vp, vp, vp, i, i, i, vp, vp, vp, i, vp, vp, vp]
@@ -363,6 +372,11 @@ def load(dev: bool = False):
     lib.ugsm_enqueue_full_cloud_managed.argtypes = [vp, vp, vp, i, i, i, C.POINTER(QueueCloud), u64]
     lib.ugsm_enqueue_foveated_cloud_managed.argtypes = [vp, vp, vp, i, i, i, i, i, C.POINTER(QueueCloud), u64]
     lib.ugsm_done_cloud.argtypes = [vp, C.POINTER(CloudResult)]
+    lib.ugsm_enqueue_full_checked.argtypes = [vp, vp, vp, i, i, i, vp, vp, C.c_float, u64]
+    lib.ugsm_enqueue_full_checked_managed.argtypes = [vp, vp, vp, i, i, i, C.c_float, i, u64]
+    lib.ugsm_enqueue_full_checked_cloud.argtypes = [vp, vp, vp, i, i, i, vp, vp, C.c_float, C.POINTER(QueueCloud), vp, C.c_longlong, vp, u64]
+    lib.ugsm_enqueue_full_checked_cloud_managed.argtypes = [vp, vp, vp, i, i, i, C.c_float, i, C.POINTER(QueueCloud), u64]
+    lib.ugsm_done_checked.argtypes = [vp, C.POINTER(CheckedResult)]
     lib.ugsm_flush.argtypes = [vp]
     lib.ugsm_next_done.argtypes = [vp, C.POINTER(Completion), i]
     lib.ugsm_queue_depth.argtypes = [vp, ip, ip, ip]
@@ -1004,6 +1018,17 @@ class Context:
                                                         W, H, stride, self._ptrs([o[0].ctypes.data for o in outs]), self._ptrs([o[1].ctypes.data for o in outs]),
                                                         self._ptrs([o[2].ctypes.data for o in outs])))
 
+    def submit_full_checked_host(self, slot: int, rgbL, rgbR, W: int, H: int, stride: int, outs, backs, tau: float):
+        """submit_full_checked from page-locked memory (ugsm_submit_full_checked_host).  rgbL / rgbR: lists of page-locked uint8 arrays; outs: list
+        of page-locked (3, H, W) float32 arrays for the checked forward fields; backs: None, or a list of such arrays (or None) per pair for the
+        right camera's checked fields."""
+        n = len(rgbL)
+        if len(rgbR) != n or len(outs) != n or (backs is not None and len(backs) != n):
+            raise UgsmError(UGSM_ERR_BAD_ARG, "one entry per pair in every list")
+        bp = [self._ptrs([b[c].ctypes.data if b is not None else None for b in backs]) if backs is not None else None for c in range(3)]
+        self.check(self.lib.ugsm_submit_full_checked_host(self._h, slot, n, self._ptrs([a.ctypes.data for a in rgbL]), self._ptrs([a.ctypes.data for a in rgbR]),
+                                                          W, H, stride, *[self._ptrs([o[c].ctypes.data for o in outs]) for c in range(3)], *bp, tau))
+
     def submit_foveated_batch_host(self, slot: int, rgbL, rgbR, W: int, H: int, stride: int, offsets, stacks):
         """stacks: list of page-locked (3, F, fovH, fovW) float32 arrays."""
         n = len(rgbL)
@@ -1110,6 +1135,39 @@ class Context:
         W, H, stride = self._pair(rgbL, rgbR)
         self.check(self.lib.ugsm_enqueue_foveated_cloud_managed(self._h, rgbL.ctypes.data, rgbR.ctypes.data, W, H, stride, int(off[0]), int(off[1]),
                                                                 C.byref(spec), tag))
+
+    # ... checked (ugsm_enqueue_full_checked*): both directions of a call's pairs in lockstep, each pair with its own tau (> 0), whatever
+    # set_lr_check holds; d_back: the right camera's checked field, or None
+    def enqueue_full_checked(self, d_rgbL: int, d_rgbR: int, W: int, H: int, stride: int, d_out: int, d_back, tau: float, tag: int):
+        self.check(self.lib.ugsm_enqueue_full_checked(self._h, d_rgbL, d_rgbR, W, H, stride, d_out, d_back, tau, tag))
+
+    def enqueue_full_checked_managed(self, rgbL: np.ndarray, rgbR: np.ndarray, tau: float, want_back: bool, tag: int):
+        """Any host memory in; the checked forward planes come back in ugsm_completion.result[0..2], the right camera's (want_back) through
+        done_checked()."""
+        W, H, stride = self._pair(rgbL, rgbR)
+        self.check(self.lib.ugsm_enqueue_full_checked_managed(self._h, rgbL.ctypes.data, rgbR.ctypes.data, W, H, stride, tau, 1 if want_back else 0, tag))
+
+    def enqueue_full_checked_cloud(self, d_rgbL: int, d_rgbR: int, W: int, H: int, stride: int, d_out: int, d_back, tau: float, spec: QueueCloud,
+                                   d_points: int, cap_points: int, d_count: int, tag: int):
+        self.check(self.lib.ugsm_enqueue_full_checked_cloud(self._h, d_rgbL, d_rgbR, W, H, stride, d_out, d_back, tau, C.byref(spec), d_points,
+                                                            int(cap_points), d_count, tag))
+
+    def enqueue_full_checked_cloud_managed(self, rgbL: np.ndarray, rgbR: np.ndarray, tau: float, want_back: bool, spec: QueueCloud, tag: int):
+        W, H, stride = self._pair(rgbL, rgbR)
+        self.check(self.lib.ugsm_enqueue_full_checked_cloud_managed(self._h, rgbL.ctypes.data, rgbR.ctypes.data, W, H, stride, tau,
+                                                                    1 if want_back else 0, C.byref(spec), tag))
+
+    def done_checked(self, shape=None):
+        """For the checked pair the last next_done() reported: (marked_fwd, marked_back, back).  back: None, or -- a managed pair enqueued with
+        want_back, `shape` = (H, W) given -- a (3, H, W) copy of the right camera's checked planes (the library's page-locked staging itself is
+        lent only until the next next_done() on the context)."""
+        r = CheckedResult()
+        self.check(self.lib.ugsm_done_checked(self._h, C.byref(r)))
+        back = None
+        if shape is not None and r.back[0]:
+            H, W = shape
+            back = np.stack([np.ctypeslib.as_array(r.back[c], shape=(H, W)) for c in range(3)])
+        return int(r.marked_fwd), int(r.marked_back), back
 
     def done_cloud(self):
         """The managed cloud of the pair the last next_done() reported: (records, count, level_counts).  records is a numpy view of the library's

@@ -520,7 +520,10 @@ int ugsm_point_cloud_resized_fovea(ugsm_ctx *ctx, int slot, const float *d_stack
 // full-mode LR check, early exit) gets pair b's cloud behind pair b's match: a managed call of that kind reuses the slot's image and plane
 // buffers for every pair.  So does a call whose pairs each evaluate more than kBatchMaxPixels sampled points -- the size above which the
 // matcher's own levels go pair by pair, because one pair's launch fills the chip many times over and a batch index buys nothing.
-int ugsm::queue_cloud_submit(ugsm_ctx *ctx, int slot, const CloudCall *call)
+// chk (a call of checked pairs, ugsm_enqueue_full_checked_cloud*; else null): the match is the checked call's -- both directions of the pairs in
+// lockstep, one pair too, whatever the context's own LR setting --, the clouds read the checked forward fields, and a managed pair that asks
+// for them gets its back planes down beside its forward ones.
+static int cloud_call_submit(ugsm_ctx *ctx, int slot, const CloudCall *call, const CheckedCall *chk)
 {
     Slot *s;
     UCHK(get_slot(ctx, slot, &s));
@@ -535,7 +538,8 @@ int ugsm::queue_cloud_submit(ugsm_ctx *ctx, int slot, const CloudCall *call)
     if (stride < input_row_bytes(ctx, W)) return UGSM_ERR_SIZE_MISMATCH;
     HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
     c.cq_n = 0;
-    const bool by_pair = n == 1 || (fovea ? fovea_batch_runs_pair_by_pair(ctx) : batch_runs_pair_by_pair(ctx));
+    if (chk) UCHK(full_checked_check(ctx, n, W, H, stride, chk->tau));
+    const bool by_pair = n == 1 || (!chk && (fovea ? fovea_batch_runs_pair_by_pair(ctx) : batch_runs_pair_by_pair(ctx)));
     int fw = W, fh = H;
     if (fovea) UCHK(ugsm_fovea_dims(W, H, ctx->cfg.levels, F, &fw, &fh));
     const size_t px = (size_t)W * H, fn = (size_t)fw * fh, stackn = (size_t)F * fn;
@@ -544,10 +548,11 @@ int ugsm::queue_cloud_submit(ugsm_ctx *ctx, int slot, const CloudCall *call)
 
     // 1. where every pair's images, state and result lie on the device
     const uint8_t *dL[UGSM_MAX_BATCH], *dR[UGSM_MAX_BATCH];
-    float *state[UGSM_MAX_BATCH], *res[UGSM_MAX_BATCH];
+    float *state[UGSM_MAX_BATCH], *res[UGSM_MAX_BATCH], *back[UGSM_MAX_BATCH] = {nullptr};  // back: a checked pair's right-to-left field, where it is taken
     const size_t st_per = fovea ? ((3 * fn + 63) & ~(size_t)63) : 0, res_per = (3 * plane + 63) & ~(size_t)63;
     if (managed) {
-        // the slot's uploads and hout: [states][results], one of each for a call that runs pair by pair, n otherwise
+        // the slot's uploads and hout: [states][results], one of each for a call that runs pair by pair, n otherwise; a checked call: [back fields]
+        // behind them
         const int copies = by_pair ? 1 : n;
         const size_t img = ((size_t)stride * H + 255) & ~(size_t)255;
         if (img * copies > s->rgb_cap) {
@@ -555,13 +560,16 @@ int ugsm::queue_cloud_submit(ugsm_ctx *ctx, int slot, const CloudCall *call)
             UCHK(grow(ctx, s->rgbL, c, img * copies));
             UCHK(grow(ctx, s->rgbR, s->rgb_cap, img * copies));
         }
-        UCHK(grow(ctx, s->hout, s->hout_cap, std::max(copies * (st_per + res_per), s->hout_cap)));
+        bool any_back = false;
+        for (int b = 0; chk && b < n; b++) any_back = any_back || chk->job[b].back_planes[0];
+        UCHK(grow(ctx, s->hout, s->hout_cap, std::max(copies * (st_per + (any_back ? 2 : 1) * res_per), s->hout_cap)));
         for (int b = 0; b < n; b++) {
             const int k = by_pair ? 0 : b;
             dL[b] = s->rgbL + k * img;
             dR[b] = s->rgbR + k * img;
             state[b] = s->hout + k * st_per;
             res[b] = s->hout + copies * st_per + k * res_per;
+            if (chk && chk->job[b].back_planes[0]) back[b] = s->hout + copies * (st_per + res_per) + k * res_per;
         }
     } else {
         UCHK(grow(ctx, s->hout, s->hout_cap, std::max(st_per * n, s->hout_cap)));
@@ -571,6 +579,7 @@ int ugsm::queue_cloud_submit(ugsm_ctx *ctx, int slot, const CloudCall *call)
             dR[b] = call->job[b].R;
             state[b] = s->hout + (by_pair ? 0 : b * st_per);
             res[b] = call->job[b].out;
+            if (chk) back[b] = chk->job[b].back;
         }
     }
 
@@ -636,7 +645,19 @@ int ugsm::queue_cloud_submit(ugsm_ctx *ctx, int slot, const CloudCall *call)
             HIPCHK(ctx, hipMemcpyAsync(call->job[b].planes[k], res[b] + k * plane, plane * sizeof(float), hipMemcpyDeviceToHost, s->st));
         return UGSM_OK;
     };
-    auto match = [&](int b, int k) {  // pairs b .. b + k - 1 of the call: one of them, or all in lockstep
+    auto download_back = [&](int b) -> int {  // a managed checked pair's back planes, where they are wanted
+        if (!managed || !back[b]) return UGSM_OK;
+        for (int k = 0; k < 3; k++)
+            HIPCHK(ctx, hipMemcpyAsync(chk->job[b].back_planes[k], back[b] + k * plane, plane * sizeof(float), hipMemcpyDeviceToHost, s->st));
+        return UGSM_OK;
+    };
+    auto match = [&](int b, int k) -> int {  // pairs b .. b + k - 1 of the call: one of them, or all in lockstep
+        if (chk) {
+            int kept = 0;
+            for (int j = b; j < b + k; j++) kept += !back[j];
+            UCHK(full_checked_bufs(ctx, *s, k, kept, W, H));
+            return enqueue_full_checked(ctx, *s, slot, k, dL + b, dR + b, W, H, stride, res + b, back + b, chk->tau);
+        }
         return fovea ? enqueue_match_foveated(ctx, *s, slot, k, dL + b, dR + b, W, H, stride, ox + b, oy + b, state + b, res + b, nullptr, nullptr)
                      : enqueue_match_full(ctx, *s, slot, k, dL + b, dR + b, W, H, stride, res + b);
     };
@@ -646,6 +667,7 @@ int ugsm::queue_cloud_submit(ugsm_ctx *ctx, int slot, const CloudCall *call)
             if (managed) UCHK(stage_in(ctx, *s, call->job[b].L, call->job[b].R, W, H, stride));
             UCHK(match(b, 1));
             UCHK(download(b));
+            UCHK(download_back(b));
             UCHK(queue_cloud_launch(ctx, *s, slot, b, 1, fovea, &spec));
         }
     } else {
@@ -655,7 +677,10 @@ int ugsm::queue_cloud_submit(ugsm_ctx *ctx, int slot, const CloudCall *call)
                 HIPCHK(ctx, hipMemcpyAsync(const_cast<uint8_t *>(dR[b]), call->job[b].R, img_bytes, hipMemcpyHostToDevice, s->st));
             }
         UCHK(match(0, n));
-        for (int b = 0; b < n; b++) UCHK(download(b));
+        for (int b = 0; b < n; b++) {
+            UCHK(download(b));
+            UCHK(download_back(b));
+        }
         if (cloud_by_pair)
             for (int b = 0; b < n; b++) UCHK(queue_cloud_launch(ctx, *s, slot, b, 1, fovea, &spec));
         else
@@ -668,6 +693,21 @@ int ugsm::queue_cloud_submit(ugsm_ctx *ctx, int slot, const CloudCall *call)
         c.cq_levels = fovea ? F : 0;
     }
     return mark_done(ctx, *s);
+}
+
+int ugsm::queue_cloud_submit(ugsm_ctx *ctx, int slot, const CloudCall *call) { return cloud_call_submit(ctx, slot, call, nullptr); }
+
+// The checked call's pairs with a cloud each (CtxHooks::checked_submit hands them on from ugsm_full.cpp): the same call as a cloud call of
+// full-mode pairs, with the checked match in the place of the plain one.
+int ugsm::queue_checked_cloud_submit(ugsm_ctx *ctx, int slot, const CheckedCall *chk)
+{
+    if (!chk || !chk->spec || chk->n < 1 || chk->n > UGSM_MAX_BATCH) return UGSM_ERR_BAD_ARG;
+    CloudCall cc{0, chk->managed, chk->n, chk->W, chk->H, chk->stride, chk->spec, {}};
+    for (int b = 0; b < chk->n; b++) {
+        const CheckedJob &j = chk->job[b];
+        cc.job[b] = CloudJob{j.L, j.R, 0, 0, j.out, {j.planes[0], j.planes[1], j.planes[2]}, j.points, j.cap, j.count, nullptr};
+    }
+    return cloud_call_submit(ctx, slot, &cc, chk);
 }
 
 int ugsm::queue_cloud_finish(ugsm_ctx *ctx, int slot, int n, ugsm_cloud_result *res, void *(*staging)(void *, int, long long), void *user)

@@ -342,6 +342,38 @@ int full_checked_bufs(ugsm_ctx *ctx, Slot &s, int n, int kept, int W, int H)
     return lr_host_ready(ctx, s);
 }
 
+// ---- the queue's checked pairs (ugsm_enqueue_full_checked*; CtxHooks::checked_submit / checked_marked) ------------------------------------
+// A call of n checked pairs is ONE slot-level checked call: ugsm_submit_full_checked on the device kind's buffers, ugsm_submit_full_checked_host
+// on a managed call's page-locked staging; pairs that carry a cloud go through the cloud call's frame (ugsm_cloud.cpp).
+int queue_checked_submit(ugsm_ctx *ctx, int slot, const CheckedCall *call)
+{
+    if (!call || call->n < 1 || call->n > UGSM_MAX_BATCH) return UGSM_ERR_BAD_ARG;
+    if (call->spec) return queue_checked_cloud_submit(ctx, slot, call);
+    const int n = call->n;
+    const uint8_t *L[UGSM_MAX_BATCH], *R[UGSM_MAX_BATCH];
+    float *out[3][UGSM_MAX_BATCH], *back[3][UGSM_MAX_BATCH];
+    bool any_back = false;
+    for (int b = 0; b < n; b++) {
+        const CheckedJob &j = call->job[b];
+        L[b] = j.L;
+        R[b] = j.R;
+        for (int k = 0; k < 3; k++) {
+            out[k][b] = call->managed ? j.planes[k] : (k == 0 ? j.out : nullptr);
+            back[k][b] = call->managed ? j.back_planes[k] : (k == 0 ? j.back : nullptr);
+        }
+        any_back = any_back || back[0][b];
+    }
+    if (!call->managed)
+        return ugsm_submit_full_checked(ctx, slot, n, L, R, call->W, call->H, call->stride, out[0], any_back ? back[0] : nullptr, call->tau);
+    return ugsm_submit_full_checked_host(ctx, slot, n, L, R, call->W, call->H, call->stride, out[0], out[1], out[2], any_back ? back[0] : nullptr,
+                                         any_back ? back[1] : nullptr, any_back ? back[2] : nullptr, call->tau);
+}
+int queue_checked_marked(ugsm_ctx *ctx, int slot, int n, long long *fwd, long long *back)
+{
+    for (int b = 0; b < n; b++) UCHK(ugsm_last_lr_marked_pair(ctx, slot, b, fwd + b, back + b));
+    return UGSM_OK;
+}
+
 }  // namespace ugsm
 
 extern "C" {

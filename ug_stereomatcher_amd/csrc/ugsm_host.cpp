@@ -628,6 +628,53 @@ int ugsm_submit_full_batch_host(ugsm_ctx *ctx, int slot, int n, const uint8_t *c
     return mark_done(ctx, *s);
 }
 
+// The checked call from page-locked memory: the uploads of all pairs, both directions in ONE lockstep match (enqueue_full_checked, a lone pair
+// too: the call has no pair-by-pair form), the downloads -- every pair's checked forward planes, and the backward ones of the pairs that ask.
+// The slot's result staging: [n forward fields][the back fields that are taken], field_room floats each.  Every buffer, the staging included,
+// grows before anything is enqueued.
+int ugsm_submit_full_checked_host(ugsm_ctx *ctx, int slot, int n, const uint8_t *const *rgbL, const uint8_t *const *rgbR, int W, int H, int stride,
+                                  float *const *dispH, float *const *dispV, float *const *dispC, float *const *backH, float *const *backV,
+                                  float *const *backC, float tau)
+{
+    Slot *s;
+    UCHK(get_slot(ctx, slot, &s));
+    if (!rgbL || !rgbR || !dispH || !dispV || !dispC) return UGSM_ERR_BAD_ARG;
+    UCHK(full_checked_check(ctx, n, W, H, stride, tau));
+    const bool backs = backH || backV || backC;
+    if (backs && !(backH && backV && backC)) return ctx_fail(ctx, UGSM_ERR_BAD_ARG, "backH, backV and backC: all three arrays or none");
+    bool takes[UGSM_MAX_BATCH];
+    int taken = 0;
+    for (int b = 0; b < n; b++) {
+        const int given = backs ? (backH[b] != nullptr) + (backV[b] != nullptr) + (backC[b] != nullptr) : 0;
+        if (given != 0 && given != 3) return ctx_fail(ctx, UGSM_ERR_BAD_ARG, "backH, backV and backC of a pair: all three or none");
+        takes[b] = given == 3;
+        taken += takes[b];
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
+    UCHK(batch_pinned(ctx, "ugsm_submit_full_checked_host", n, rgbL, rgbR, dispH, dispV, dispC));
+    for (int b = 0; b < n; b++)
+        if (takes[b] && !(is_pinned(backH[b]) && is_pinned(backV[b]) && is_pinned(backC[b]))) return not_pinned(ctx, "ugsm_submit_full_checked_host");
+    const size_t px = (size_t)W * H, per = field_room(px);
+    UCHK(full_checked_bufs(ctx, *s, n, n - taken, W, H));
+    UCHK(grow(ctx, s->hout, s->hout_cap, per * (n + taken)));
+    const uint8_t *dL[UGSM_MAX_BATCH], *dR[UGSM_MAX_BATCH];
+    UCHK(stage_in_batch(ctx, *s, n, rgbL, rgbR, W, H, stride, dL, dR));
+    float *out[UGSM_MAX_BATCH], *back[UGSM_MAX_BATCH];
+    for (int b = 0, k = 0; b < n; b++) {
+        out[b] = s->hout + b * per;
+        back[b] = takes[b] ? s->hout + (n + k++) * per : nullptr;
+    }
+    UCHK(enqueue_full_checked(ctx, *s, slot, n, dL, dR, W, H, stride, out, taken ? back : nullptr, tau));
+    for (int b = 0; b < n; b++) {
+        float *const dst[3] = {dispH[b], dispV[b], dispC[b]};
+        UCHK(copy_out_planes(ctx, *s, out[b], px, dst));  // (page-locked destinations: three asynchronous copies)
+        if (!takes[b]) continue;
+        float *const bdst[3] = {backH[b], backV[b], backC[b]};
+        UCHK(copy_out_planes(ctx, *s, back[b], px, bdst));
+    }
+    return mark_done(ctx, *s);
+}
+
 int ugsm_submit_foveated_batch_host(ugsm_ctx *ctx, int slot, int n, const uint8_t *const *rgbL, const uint8_t *const *rgbR, int W, int H, int stride,
                                     const int *off_x, const int *off_y, float *const *stackH, float *const *stackV, float *const *stackC)
 {

@@ -29,6 +29,23 @@ struct CloudCall {
     CloudJob job[UGSM_MAX_BATCH];
 };
 
+// A call of n checked full-mode pairs (ugsm_enqueue_full_checked*), as the queue hands it to the runtime through CtxHooks::checked_submit.
+struct CheckedJob {
+    const uint8_t *L, *R;   // device kind: the device images; managed: the page-locked staging
+    float *out, *back;      // device kind: d_out, and d_back or null (the pair does not take the right camera's field)
+    float *planes[3];       // managed: the page-locked planes of the checked forward field (null: a cloud pair without want_planes)
+    float *back_planes[3];  // managed with want_back: those of the right camera's checked field
+    void *points;           // device kind with a cloud: d_points, cap_points, d_count
+    long long cap;
+    long long *count;
+};
+struct CheckedCall {
+    int managed, n, W, H, stride;
+    float tau;                     // the call's (every pair's) threshold
+    const ugsm_queue_cloud *spec;  // the call's (every pair's) cloud spec; null: pairs without a cloud
+    CheckedJob job[UGSM_MAX_BATCH];
+};
+
 // State the layers hang on a context; the runtime owns the storage and calls the `free` hooks from ugsm_destroy (before the slots go).
 struct CtxHooks {
     // The queue's way to the cloud work (set by ugsm_create; nullptr in a runtime that has none: tests/fake_runtime.cpp).  cloud_submit:
@@ -38,6 +55,13 @@ struct CtxHooks {
     // of memory) and enqueues the device-to-host copies on the slot's stream: the slot is busy again until they have drained.
     int (*cloud_submit)(ugsm_ctx *, int slot, const CloudCall *call) = nullptr;
     int (*cloud_finish)(ugsm_ctx *, int slot, int n, ugsm_cloud_result *res, void *(*staging)(void *user, int pair, long long bytes), void *user) = nullptr;
+    // The queue's way to the checked full-mode call (set by ugsm_create; nullptr in a runtime that has none).  checked_submit: both directions
+    // of the call's pairs in lockstep with the call's tau, as ugsm_submit_full_checked[_host] enqueues them -- a managed call's images up and
+    // its planes down around the match -- and, with a spec, the clouds of the checked forward fields behind it on the slot's stream, as
+    // cloud_submit puts them there (a managed call then finishes through cloud_finish).  checked_marked (once the slot has drained): the
+    // pixels the check marked in each direction of the call's n pairs.
+    int (*checked_submit)(ugsm_ctx *, int slot, const CheckedCall *call) = nullptr;
+    int (*checked_marked)(ugsm_ctx *, int slot, int n, long long *fwd, long long *back) = nullptr;
     void *queue = nullptr;
     void (*queue_free)(ugsm_ctx *, void *) = nullptr;
     void *shard = nullptr;

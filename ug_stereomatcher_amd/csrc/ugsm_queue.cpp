@@ -5,8 +5,9 @@
 // and 4 from inside bench.py (plan_calls / run / submit), moved behind the C-ABI so that the C++ node's topic path
 // (/root/reference/src/gpu_matcher/UG_GPU_matcher.cpp:126-185,414-494 -- one blocking match() per callback of a single-threaded
 // ros::spin, :749-752) gets the same pipeline from three calls.  Written against the public slot-level entry points only -- and, for the
-// pairs that carry a cloud (ugsm_enqueue_*_cloud*), two function pointers of CtxHooks that the runtime sets in ugsm_create: no symbol of
-// the runtime's cloud work is named here, so the file still links against a runtime that has none (tests/fake_runtime.cpp).
+// pairs that carry a cloud (ugsm_enqueue_*_cloud*) or are checked (ugsm_enqueue_full_checked*), function pointers of CtxHooks that the
+// runtime sets in ugsm_create: no symbol of the runtime's cloud work or of its checked call is named here, so the file still links against a
+// runtime that has none (tests/fake_runtime.cpp).
 #include "ugsm_internal.hpp"
 
 #include <time.h>  // (no HIP header: the queue makes no HIP call -- tests/test_queue_host.py builds this file with g++ against a fake runtime)
@@ -54,13 +55,20 @@ struct Item {
     int fmt = 0;  // the input format the pair was enqueued in (ugsm_set_input_format at the time of its ugsm_enqueue_*)
     unsigned long long seq = 0;
     int managed = -1;  // index into Queue::pool, or -1
+    // a checked pair (ugsm_enqueue_full_checked*): its own threshold, and the right camera's checked field where the pair takes it -- the
+    // device kind: back[0] = d_back; managed with want_back: the three planes, carved from the staging like out[0 .. 2]
+    bool checked = false, want_back = false;
+    float tau = 0.0f;
+    float *back[3] = {nullptr, nullptr, nullptr};
     bool pyr() const { return out[3] != nullptr || out[4] != nullptr; }
     // pairs of one call: one mode, one kind of memory, one geometry, one input format; host calls with pyramid stacks go out alone (the
-    // batched host entry point has none); all with a cloud, of one byte-equal spec, or all without
+    // batched host entry point has none); all with a cloud, of one byte-equal spec, or all without; all checked, with one bit-equal tau, or
+    // none (whether a checked pair takes its back field is the pair's own: the call has an entry per pair for it)
     bool same_kind(const Item &o) const
     {
         return mode == o.mode && mem == o.mem && W == o.W && H == o.H && stride == o.stride && fmt == o.fmt &&
-               !(mem != MEM_DEVICE && (pyr() || o.pyr())) && has_cloud == o.has_cloud && (!has_cloud || memcmp(&spec, &o.spec, sizeof spec) == 0);
+               !(mem != MEM_DEVICE && (pyr() || o.pyr())) && has_cloud == o.has_cloud && (!has_cloud || memcmp(&spec, &o.spec, sizeof spec) == 0) &&
+               checked == o.checked && (!checked || memcmp(&tau, &o.tau, sizeof tau) == 0);
     }
 };
 
@@ -75,6 +83,8 @@ struct Call {
     // submit failed, or whose slot reported an error, has no second step.)  Every other call is in phase 1 from the start.
     int phase = 1;
     std::vector<ugsm_cloud_result> clouds;  // managed cloud calls: what ugsm_done_cloud reports for each pair
+    std::vector<ugsm_checked_result> checked;  // checked calls: what ugsm_done_checked reports for each pair (the counts: read_marks) ...
+    bool marks_read = false;                   // ... once, when the call is retired
 };
 
 struct Done {
@@ -82,6 +92,8 @@ struct Done {
     int managed;  // the managed buffer the completion lends, or -1
     bool has_cloud;  // a managed cloud pair of a call that succeeded: ...
     ugsm_cloud_result cloud;  // ... what ugsm_done_cloud reports after this completion
+    bool checked;  // a checked pair of a call that succeeded: ...
+    ugsm_checked_result chk;  // ... what ugsm_done_checked reports after this completion
 };
 
 struct Queue {
@@ -92,6 +104,8 @@ struct Queue {
     std::vector<int> lent;               // managed buffers the last ugsm_next_done lent to the host
     bool last_has_cloud = false;         // the pair the last ugsm_next_done reported carried a managed cloud: ...
     ugsm_cloud_result last_cloud{};      // ... this one (ugsm_done_cloud)
+    bool last_checked = false;           // ... was a checked pair of a call that succeeded: ...
+    ugsm_checked_result last_chk{};      // ... this is what ugsm_done_checked answers
     unsigned long long seq = 0, flush_upto = 0;
     bool round_restarts = false;  // a flush has closed the burst: the next pair enqueued opens a new staggered round
     long long calls = 0, calls_since_idle = 0;
@@ -158,11 +172,35 @@ Queue *queue_of(ugsm_ctx *ctx)
 
 void update_busy(ugsm_ctx *ctx, Queue *q) { ctx_hooks(ctx).queue_busy = !(q->waiting.empty() && q->flight.empty() && q->done.empty()); }
 
+// A checked call has drained: what its check marked, per pair and direction, from the runtime (the slot still holds the call's counts: it is
+// not used again before the call is retired).  A call that failed has none.
+void read_marks(ugsm_ctx *ctx, Call &c)
+{
+    if (c.marks_read || c.checked.empty()) return;
+    c.marks_read = true;
+    if (c.status != UGSM_OK) return;
+    CtxHooks &h = ctx_hooks(ctx);
+    long long fwd[UGSM_MAX_BATCH] = {0}, back[UGSM_MAX_BATCH] = {0};
+    const int st = h.checked_marked ? h.checked_marked(ctx, c.slot, (int)c.items.size(), fwd, back) : UGSM_ERR_STATE;
+    if (st != UGSM_OK) {
+        c.status = st;
+        return;
+    }
+    for (size_t b = 0; b < c.checked.size(); b++) {
+        const Item &it = c.items[b];
+        ugsm_checked_result &r = c.checked[b];
+        for (int k = 0; k < 3; k++) r.back[k] = it.mem == MEM_MANAGED && it.want_back ? it.back[k] : nullptr;
+        r.marked_fwd = fwd[b];
+        r.marked_back = back[b];
+    }
+}
+
 // the oldest call in flight is complete: its pairs move to the done list
 void retire_front(ugsm_ctx *ctx, Queue *q)
 {
     Call &c = q->flight.front();
     const long long t = now_ns();
+    read_marks(ctx, c);
     for (; c.reported < c.items.size(); c.reported++) {  // (push_back may throw: what has been reported is not reported again)
         const Item &it = c.items[c.reported];
         ugsm_completion d{};
@@ -175,7 +213,8 @@ void retire_front(ugsm_ctx *ctx, Queue *q)
         if (it.mem == MEM_MANAGED)
             for (int k = 0; k < 5; k++) d.result[k] = it.out[k];
         const bool cloud = it.has_cloud && it.mem == MEM_MANAGED && c.status == UGSM_OK && c.reported < c.clouds.size();
-        q->done.push_back(Done{d, it.managed, cloud, cloud ? c.clouds[c.reported] : ugsm_cloud_result{}});
+        const bool chk = it.checked && c.status == UGSM_OK && c.reported < c.checked.size();
+        q->done.push_back(Done{d, it.managed, cloud, cloud ? c.clouds[c.reported] : ugsm_cloud_result{}, chk, chk ? c.checked[c.reported] : ugsm_checked_result{}});
     }
     q->slot_busy[(size_t)c.slot] = 0;
     q->flight.pop_front();
@@ -277,6 +316,15 @@ CloudJob cloud_job(const Item &it)
     return CloudJob{it.L, it.R, it.off_x, it.off_y, it.out[0], {none, none, none}, it.points, it.cap, it.count, it.level_counts};
 }
 
+// a pair's part of the call the checked hook takes
+CheckedJob checked_job(const Item &it)
+{
+    float *const none = nullptr;
+    if (it.mem == MEM_MANAGED)
+        return CheckedJob{it.L, it.R, none, none, {it.out[0], it.out[1], it.out[2]}, {it.back[0], it.back[1], it.back[2]}, nullptr, 0, nullptr};
+    return CheckedJob{it.L, it.R, it.out[0], it.back[0], {none, none, none}, {none, none, none}, it.points, it.cap, it.count};
+}
+
 // One library call for the first n waiting pairs on `slot`.  more: other calls follow this one closely -- pairs wait behind it, or it filled
 // up without a flush (a host that submits faster than the chip matches): the runtime then takes the call to share the chip whatever the
 // other slots are doing at this instant (call_alone, ugsm_policy.cpp).
@@ -289,6 +337,7 @@ void dispatch(ugsm_ctx *ctx, Queue *q, int n, int slot, bool more)
     try {
         c.items.assign(q->waiting.begin(), q->waiting.begin() + n);
         if (c.items[0].has_cloud && c.items[0].mem == MEM_MANAGED) c.clouds.resize((size_t)n);
+        if (c.items[0].checked) c.checked.resize((size_t)n);
     } catch (...) {
         q->flight.pop_back();
         throw;  // (to the entry point's no_throw; the pairs still wait)
@@ -318,7 +367,12 @@ void dispatch(ugsm_ctx *ctx, Queue *q, int n, int slot, bool more)
     const int host_fmt = h.input_format;
     h.input_format = f.fmt;
     int st;
-    if (f.has_cloud) {  // the match and the clouds of the call's pairs: the runtime's hook
+    if (f.checked) {  // both directions of the call's pairs in lockstep, checked with the pairs' tau, and their clouds if they carry one: the runtime's hook
+        CheckedCall kc{f.mem == MEM_MANAGED, n, f.W, f.H, f.stride, f.tau, f.has_cloud ? &f.spec : nullptr, {}};
+        for (int b = 0; b < n; b++) kc.job[b] = checked_job(c.items[(size_t)b]);
+        st = h.checked_submit ? h.checked_submit(ctx, slot, &kc) : UGSM_ERR_STATE;
+        if (f.has_cloud && kc.managed) c.phase = 0;  // (the managed clouds' second step: as below)
+    } else if (f.has_cloud) {  // the match and the clouds of the call's pairs: the runtime's hook
         st = h.cloud_submit ? h.cloud_submit(ctx, slot, &cc) : UGSM_ERR_STATE;
         if (cc.managed) c.phase = 0;  // (a failed submit too: cloud_second_step sees the status once the slot has drained)
     } else if (!fovea && !host) {
@@ -448,7 +502,7 @@ int stage_managed(ugsm_ctx *ctx, Queue *q, Item &it)
     }
     int idx = -1;
     const int grown = no_throw(ctx, "ugsm_enqueue_*_managed: out of host memory", [&]() -> int {
-        idx = managed_get(ctx, q, 2 * img, (planes ? 3 * plane : 0) + (pyr ? 6 * plane : 0));
+        idx = managed_get(ctx, q, 2 * img, (planes ? 3 * plane : 0) + (pyr ? 6 * plane : 0) + (it.want_back ? 3 * plane : 0));
         return UGSM_OK;
     });
     if (grown != UGSM_OK || idx < 0) return UGSM_ERR_NOMEM;  // (ugsm_host_alloc has set the message)
@@ -469,6 +523,7 @@ int stage_managed(ugsm_ctx *ctx, Queue *q, Item &it)
     for (int k = 0; k < 3; k++) it.out[k] = planes ? out + k * plane : nullptr;
     it.out[3] = pyr ? out + 3 * plane : nullptr;
     it.out[4] = pyr ? out + 6 * plane : nullptr;
+    for (int k = 0; k < 3; k++) it.back[k] = it.want_back ? out + ((planes ? 3 : 0) + k) * plane : nullptr;  // (a checked pair is full-mode: no stacks)
     it.managed = idx;
     return UGSM_OK;
 }
@@ -490,6 +545,26 @@ int check_cloud(ugsm_ctx *ctx, const ugsm_queue_cloud *spec, const Item &it)
         return ctx_fail(ctx, UGSM_ERR_BAD_ARG, "ugsm_enqueue_*_cloud: a null or misaligned cloud buffer, or cap_points < 0");
     if (!ctx_hooks(ctx).cloud_submit || !ctx_hooks(ctx).cloud_finish) return ctx_fail(ctx, UGSM_ERR_STATE, "ugsm_enqueue_*_cloud*: this runtime makes no clouds");
     return UGSM_OK;
+}
+// What every ugsm_enqueue_full_checked* checks of its threshold and of the context: what ugsm_submit_full_checked would refuse when the pair's
+// call goes out (full_checked_check, ugsm_full.cpp), made when the pair is enqueued so that a bad pair is rejected and never reported
+int check_checked(ugsm_ctx *ctx, const Item &it)
+{
+    const ugsm_config &cfg = ctx_config(ctx);
+    if (!(it.tau > 0.0f)) return ctx_fail(ctx, UGSM_ERR_BAD_ARG, "ugsm_enqueue_full_checked*: tau must be > 0");
+    if (cfg.early_exit_threshold > 0.0f || cfg.kernel_path == 1)
+        return ctx_fail(ctx, UGSM_ERR_BAD_ARG, "ugsm_enqueue_full_checked*: not with early_exit_threshold > 0 or kernel_path 1");
+    if (!ctx_hooks(ctx).checked_submit || !ctx_hooks(ctx).checked_marked)
+        return ctx_fail(ctx, UGSM_ERR_STATE, "ugsm_enqueue_full_checked*: this runtime has no checked full-mode call");
+    return UGSM_OK;
+}
+Item as_checked(Item it, float tau, float *d_back, bool want_back = false)
+{
+    it.checked = true;
+    it.tau = tau;
+    it.back[0] = d_back;
+    it.want_back = want_back;
+    return it;
 }
 Item with_cloud(Item it, void *points = nullptr, long long cap = 0, long long *count = nullptr, long long *level_counts = nullptr)
 {
@@ -526,6 +601,10 @@ int enqueue_pair(ugsm_ctx *ctx, const char *name, Item it, int required, const u
                      name, it.mode == M_FULL ? "full" : "foveated");
             return ctx_fail(ctx, UGSM_ERR_BAD_ARG, msg);
         }
+    }
+    if (it.checked) {
+        const int ks = check_checked(ctx, it);
+        if (ks != UGSM_OK) return ks;
     }
     if (it.has_cloud) {
         const int cs = check_cloud(ctx, spec, it);
@@ -593,6 +672,8 @@ int next_done(ugsm_ctx *ctx, ugsm_completion *out, int block)
     *out = q->done.front().c;
     q->last_has_cloud = q->done.front().has_cloud;
     q->last_cloud = q->done.front().cloud;
+    q->last_checked = q->done.front().checked;
+    q->last_chk = q->done.front().chk;
     q->done.pop_front();
     // (pairs that waited for room may go out now; the slot-level entry points open up again once nothing is outstanding)
     pump(ctx, q, false);
@@ -695,6 +776,43 @@ int ugsm_enqueue_foveated_cloud_managed(ugsm_ctx *ctx, const uint8_t *rgbL, cons
 {
     const Item it{M_FOVEA, MEM_MANAGED, rgbL, rgbR, W, H, stride, off_x, off_y, {}, tag};
     return enqueue_pair(ctx, "ugsm_enqueue_foveated_cloud_managed", with_cloud(it), 0, spec);
+}
+
+int ugsm_enqueue_full_checked(ugsm_ctx *ctx, const uint8_t *d_rgbL, const uint8_t *d_rgbR, int W, int H, int stride, float *d_out, float *d_back, float tau,
+                              uint64_t tag)
+{
+    const Item it{M_FULL, MEM_DEVICE, d_rgbL, d_rgbR, W, H, stride, 0, 0, {d_out}, tag};
+    return enqueue_pair(ctx, "ugsm_enqueue_full_checked", as_checked(it, tau, d_back), 1);
+}
+
+int ugsm_enqueue_full_checked_managed(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, float tau, int want_back, uint64_t tag)
+{
+    const Item it{M_FULL, MEM_MANAGED, rgbL, rgbR, W, H, stride, 0, 0, {}, tag};
+    return enqueue_pair(ctx, "ugsm_enqueue_full_checked_managed", as_checked(it, tau, nullptr, want_back != 0), 0);
+}
+
+int ugsm_enqueue_full_checked_cloud(ugsm_ctx *ctx, const uint8_t *d_rgbL, const uint8_t *d_rgbR, int W, int H, int stride, float *d_out, float *d_back, float tau,
+                                    const ugsm_queue_cloud *spec, void *d_points, long long cap_points, long long *d_count, uint64_t tag)
+{
+    const Item it{M_FULL, MEM_DEVICE, d_rgbL, d_rgbR, W, H, stride, 0, 0, {d_out}, tag};
+    return enqueue_pair(ctx, "ugsm_enqueue_full_checked_cloud", with_cloud(as_checked(it, tau, d_back), d_points, cap_points, d_count), 1, spec);
+}
+
+int ugsm_enqueue_full_checked_cloud_managed(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, float tau, int want_back,
+                                            const ugsm_queue_cloud *spec, uint64_t tag)
+{
+    const Item it{M_FULL, MEM_MANAGED, rgbL, rgbR, W, H, stride, 0, 0, {}, tag};
+    return enqueue_pair(ctx, "ugsm_enqueue_full_checked_cloud_managed", with_cloud(as_checked(it, tau, nullptr, want_back != 0)), 0, spec);
+}
+
+int ugsm_done_checked(ugsm_ctx *ctx, ugsm_checked_result *out)
+{
+    if (!ctx || !out) return UGSM_ERR_BAD_ARG;
+    Queue *q = queue_of(ctx);
+    if (!q) return ctx_fail(ctx, UGSM_ERR_NOMEM, "ugsm_done_checked: out of host memory");
+    if (!q->last_checked) return ctx_fail(ctx, UGSM_ERR_STATE, "ugsm_done_checked: the last pair ugsm_next_done reported was no checked pair of a call that succeeded");
+    *out = q->last_chk;
+    return UGSM_OK;
 }
 
 int ugsm_done_cloud(ugsm_ctx *ctx, ugsm_cloud_result *out)

@@ -408,6 +408,8 @@ int ugsm_create(const ugsm_config *cfg_in, ugsm_ctx **out)
     ctx->lr_modes = UGSM_LR_FULL;
     ctx->hooks.cloud_submit = queue_cloud_submit;  // (the queue's way to the cloud work: ugsm_internal.hpp)
     ctx->hooks.cloud_finish = queue_cloud_finish;
+    ctx->hooks.checked_submit = queue_checked_submit;  // (... and to the checked full-mode call)
+    ctx->hooks.checked_marked = queue_checked_marked;
     set_policy(ctx, knobs);
     if (dev_env() && getenv("UGSM_MEM_LIMIT_MB")) ctx->mem_limit = atoll(getenv("UGSM_MEM_LIMIT_MB")) << 20;
     // The side stream pays when a pair is alone on the chip (115.6 against 113.9 pairs/s at 16 MP: the right pyramid and the A planes run

@@ -504,5 +504,9 @@ int stage_in(ugsm_ctx *ctx, Slot &s, const uint8_t *rgbL, const uint8_t *rgbR, i
 // ---- ugsm_cloud.cpp, for ugsm_create: the queue's way to the cloud work (CtxHooks, ugsm_internal.hpp) ----------------------------
 int queue_cloud_submit(ugsm_ctx *ctx, int slot, const CloudCall *call);
 int queue_cloud_finish(ugsm_ctx *ctx, int slot, int n, ugsm_cloud_result *res, void *(*staging)(void *, int, long long), void *user);
+// ---- ugsm_full.cpp and ugsm_cloud.cpp, for ugsm_create: the queue's way to the checked full-mode call ----------------------------
+int queue_checked_submit(ugsm_ctx *ctx, int slot, const CheckedCall *call);
+int queue_checked_marked(ugsm_ctx *ctx, int slot, int n, long long *fwd, long long *back);
+int queue_checked_cloud_submit(ugsm_ctx *ctx, int slot, const CheckedCall *call);  // (a call whose pairs carry a cloud)
 
 }  // namespace ugsm

@@ -242,6 +242,16 @@ class MatchGPULib:
         self._tags[tag] = ("full", L.shape[0], L.shape[1], False)
         self._ctx.flush()   # a frame that arrives starts at once if a slot is free; under load the backlog batches itself
 
+    def enqueueMatchChecked(self, cv_ptrL, cv_ptrR, tau: float, tag: int):
+        """enqueueMatch with the LR check of this pair at threshold tau (> 0; ugsm_enqueue_full_checked_managed): both directions of the pairs of a
+        call in lockstep, whatever the context's own setting; nextDone hands out the checked field of the left camera."""
+        L, R = _as_rgb8(cv_ptrL), _as_rgb8(cv_ptrR)
+        if L.shape != R.shape or L.strides[0] != R.strides[0]:
+            raise UgsmError(_lib.UGSM_ERR_SIZE_MISMATCH, "left/right images differ in size")
+        self._ctx.enqueue_full_checked_managed(L, R, float(tau), False, tag)
+        self._tags[tag] = ("full", L.shape[0], L.shape[1], False)
+        self._ctx.flush()
+
     def enqueueStack(self, cv_ptrL, cv_ptrR, tag: int, want_pyr: bool = False, off_x: int = 0, off_y: int = 0):
         """matchStack / matchStackPyramid without the wait."""
         L, R = _as_rgb8(cv_ptrL), _as_rgb8(cv_ptrR)

@@ -128,7 +128,8 @@ class GPUMatcher:
         `frames_in_flight` (opt-in, default 1 = the reference's behaviour: one blocking match() per callback, UG_GPU_matcher.cpp:423):
         with n > 1 the topic path enqueues the synchronised pair into the library's queue and publishes results AS THEY COMPLETE, in
         arrival order, a frame or n - 1 later; a callback blocks only while n pairs are outstanding.  spinOnce() publishes what has
-        finished meanwhile, drain() everything (node shutdown).  The service call stays blocking: a response belongs to its request."""
+        finished meanwhile, drain() everything (node shutdown).  The service call stays blocking: a response belongs to its request.
+        With the parameter `lr_check_tau` > 0 the pipelined full-mode frames go through the checked queue form (enqueueMatchChecked)."""
         self.frames_in_flight = max(1, int(frames_in_flight))
         self._pending = {}   # tag -> (imL header, imR header, image rows, image cols) of the frames in flight
         self._next_tag = 0
@@ -143,6 +144,11 @@ class GPUMatcher:
 
     def _read_foveated(self) -> int:  # :96-102,152-158,522-528 -- re-read on every callback
         return int(self.params.get(FOVEATEDQ, 0))
+
+    def _read_lr_check_tau(self) -> float:
+        """The node's `lr_check_tau` (default 0 = off), re-read on every callback: with frames_in_flight > 1 a full-mode frame is enqueued with
+        the LR check at this threshold and dispC carries the checked confidence."""
+        return float(self.params.get("lr_check_tau", 0.0))
 
     def _matcher(self) -> MatchGPULib:
         # the reference constructs a MatchGPULib per callback (:160,530); the context here persists
@@ -209,6 +215,8 @@ class GPUMatcher:
             if self.foveated == 1:
                 mgpu.initStack(L, R)
                 mgpu.enqueueStack(L, R, tag, want_pyr=True)
+            elif self._read_lr_check_tau() > 0.0:
+                mgpu.enqueueMatchChecked(L, R, self._read_lr_check_tau(), tag)   # (the pair's own tau: the checked queue form)
             else:
                 mgpu.enqueueMatch(L, R, tag)
             self.spinOnce()
