@@ -211,11 +211,30 @@ int ugsm_plan_level(const ugsm_config *cfg, int alone, int W, int H, ugsm_level_
  *   UGSM_INPUT_BGRA8  4 bytes, (b2, b1, b0), alpha ignored
  *   UGSM_INPUT_MONO8  1 byte, (v, v, v)
  * `stride` stays bytes per row and must be at least ugsm_input_bytes_per_pixel(F) * W (UGSM_ERR_SIZE_MISMATCH otherwise; the cloud
- * calls answer UGSM_ERR_BAD_ARG, as for rgb8).  Device pointers need no alignment (the images'; the float buffers: the last paragraph).
+ * calls answer UGSM_ERR_BAD_ARG, as for rgb8).  Device pointers of 8-bit images need no alignment (float images: below; the float buffers:
+ * the last paragraph).
  * The format is a setting of the context that any call may change, and it is CAPTURED WHEN AN IMAGE IS HANDED OVER: by ugsm_match_*,
  * ugsm_submit_* (the pyramids, the shard), ugsm_stage_pyramid and the cloud calls when they are made, and by ugsm_enqueue_* for the pair
  * it enqueues -- the library forms the queue's calls later, each with the format its pairs were enqueued in (pairs of different formats
  * never share a call).
+ *
+ * FLOAT IMAGES.  The matcher's arithmetic is binary32 from its first line (the reference turns every 8-bit sample into a float,
+ * MatchGPULib.cpp:332-338, and never reads a byte again), so an image that is float already -- a 12/16-bit camera scaled by its host
+ * (mono16: v / 256, an exact power-of-two scale that keeps every bit), a pair rectified or normalised on the GPU, a 32FC1 / 32FC3 message --
+ * is read as it stands:
+ *   UGSM_INPUT_RGB32F   12 bytes per pixel: three binary32, (R, G, B)
+ *   UGSM_INPUT_MONO32F   4 bytes per pixel: one binary32 v, read as (v, v, v)
+ * The contract is the algorithm's: level 0 of the pyramid IS the given floats -- the conversion (float)byte is left out, nothing else
+ * changes.  For images whose samples are finite and >= 0 every call that takes an image gives, bit for bit, what it gives on an 8-bit image
+ * with level 0 equal to these floats: a float image whose samples are the integers 0 .. 255 gives the rgb8 (mono8) call's bytes on those
+ * integers.  MONO32F is bit for bit RGB32F of (v, v, v), computed as one channel's passes.  The cloud calls' colour word takes each
+ * channel as: NaN or v <= 0 -> 0, v >= 255 -> 255, else (uint8_t)(v + 0.5f).  Samples that are negative (-0.0 included), NaN or infinite:
+ * every output is written, nothing is read or written out of bounds (a sample never indexes memory), and the values are UNSPECIFIED.
+ * Image pointers stay `const uint8_t *` and `stride` bytes per row.  Beyond the refusals above, a float image whose pointer (device or
+ * host) is not 4-byte aligned, or whose stride is no multiple of 4, is UGSM_ERR_BAD_ARG before anything is enqueued.  A float image is
+ * four times the 8-bit one's bytes in the slots' image buffers and in the staging (16 MP rgb32f: 193 MB an image).
+ * Not built: a planar (CHW) float layout; binary16 or 16-bit integer layouts; K-cost reading level 0 from a float image (a float call
+ * materialises level 0, as bgr8 does); a defined result for negative or non-finite samples.
  *
  * ALIGNMENT OF FLOAT BUFFERS.  Every `float *` device buffer of this header, read or written -- d_out, d_stack, d_pyrL / d_pyrR, d_back,
  * d_prior, d_state, d_full, d_out3, d_xyz, the disparity, confidence and warp planes, the fields of the ugsm_stage_* entry points -- needs
@@ -227,9 +246,12 @@ int ugsm_plan_level(const ugsm_config *cfg, int alone, int W, int H, ugsm_level_
 #define UGSM_INPUT_RGBA8 2
 #define UGSM_INPUT_BGRA8 3
 #define UGSM_INPUT_MONO8 4
-/* 3, 3, 4, 4, 1; -1 for an unknown format.  Host only. */
+#define UGSM_INPUT_RGB32F  8   /* 12 bytes per pixel: three binary32, (R, G, B) */
+#define UGSM_INPUT_MONO32F 9   /*  4 bytes per pixel: one binary32 v, read as (v, v, v) */
+/* 3, 3, 4, 4, 1 for the 8-bit formats, 12 and 4 for the float ones; -1 for an unknown format (5, 6, 7 and 10 among them).  Host only. */
 int ugsm_input_bytes_per_pixel(int format);
-/* The sensor_msgs encoding names "rgb8", "bgr8", "rgba8", "bgra8", "mono8" -> the format; -1 for any other string and for NULL. */
+/* The sensor_msgs encoding names "rgb8", "bgr8", "rgba8", "bgra8", "mono8", "32FC3" (RGB32F), "32FC1" (MONO32F) -> the format; -1 for any
+ * other string and for NULL. */
 int ugsm_input_format_from_encoding(const char *encoding);
 /* UGSM_ERR_BAD_ARG for an unknown format (the format is left as it was).  Takes effect for the images handed over afterwards. */
 int ugsm_set_input_format(ugsm_ctx *ctx, int format);

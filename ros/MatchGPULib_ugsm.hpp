@@ -74,7 +74,9 @@ public:
     void setFoveated(int fov) { foveatedmatching = fov; }
 
     // (not in the reference) the byte layout of the images the next calls hand over: UGSM_INPUT_RGB8 (what cv_bridge's toCvCopy(.., RGB8)
-    // gives), or ugsm_input_format_from_encoding(msg.encoding) for a message read in place (view() below).  UGSM_ERR_BAD_ARG for an unknown one.
+    // gives), or ugsm_input_format_from_encoding(msg.encoding) for a message read in place (view() below): the 8-bit encodings rgb8, bgr8,
+    // rgba8, bgra8, mono8, and 32FC3 / 32FC1 (UGSM_INPUT_RGB32F / UGSM_INPUT_MONO32F: data 4-byte aligned, step a multiple of 4).
+    // UGSM_ERR_BAD_ARG for an unknown one.
     int setInputFormat(int format) { return ugsm_set_input_format(ctx_, format); }
     // (not in the reference) the LR check of a live node: the threshold (0 = off) and the calls that apply it (UGSM_LR_FULL | UGSM_LR_FOVEATED).
     // UGSM_ERR_STATE while pipelined pairs are outstanding.

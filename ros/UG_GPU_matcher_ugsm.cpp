@@ -241,12 +241,17 @@ private:
         free(st);
     }
 
-    // The input format of a pair of messages when the library reads their encoding as it is (rgb8, bgr8, rgba8, bgra8, mono8: the payloads
-    // go to the library in place, no cv_bridge copy); -1: convert with cv_bridge::toCvCopy(.., RGB8) as the reference does
+    // The input format of a pair of messages when the library reads their encoding as it is (rgb8, bgr8, rgba8, bgra8, mono8, and the float
+    // images 32FC3 / 32FC1, whose samples become level 0 of the pyramid without a rounding to bytes: the payloads go to the library in
+    // place, no cv_bridge copy); -1: convert with cv_bridge::toCvCopy(.., RGB8) as the reference does.  A float payload the library would
+    // refuse -- a step that is no multiple of 4, data that is not 4-byte aligned -- takes the conversion too.
+    static bool float_rows_ok(const sensor_msgs::Image &m) { return m.step % 4 == 0 && reinterpret_cast<uintptr_t>(m.data.data()) % 4 == 0; }
     static int in_place_format(const sensor_msgs::Image &l, const sensor_msgs::Image &r)
     {
         const int fmt = ugsm_input_format_from_encoding(l.encoding.c_str());
-        return (fmt >= 0 && r.encoding == l.encoding) ? fmt : -1;
+        if (fmt < 0 || r.encoding != l.encoding) return -1;
+        if ((fmt == UGSM_INPUT_RGB32F || fmt == UGSM_INPUT_MONO32F) && !(float_rows_ok(l) && float_rows_ok(r))) return -1;
+        return fmt;
     }
 
     bool disparitySrv(ug_stereomatcher::GetDisparitiesGPU::Request &req, ug_stereomatcher::GetDisparitiesGPU::Response &rsp)

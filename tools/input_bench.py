@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """The input formats (ugsm_set_input_format, UGSM_INPUT_*) on the device: what reading bgr8, rgba8, bgra8 or mono8 in place costs or saves
-against rgb8.
+against rgb8, and what the float formats rgb32f and mono32f (four times the input bytes) cost.
 
     python tools/input_bench.py [--rounds 2] [--pairs 32] [--reps 8] [--out profiles/input_format_bench.json]
+    python tools/input_bench.py --formats rgb8 rgb32f mono32f --out profiles/input_format_float_bench.json
 
 For 16 MP (4928 x 3264) and 1080p, per format, in child processes that take turns format by format (the order reversed every round, as
 tools/ab.py alternates its configurations; every child under `timeout -k 10`), one context per process:
@@ -30,18 +31,24 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 SIZES = {"16mp": (4928, 3264), "1080p": (1920, 1080)}
-NAMES = ["rgb8", "bgr8", "rgba8", "bgra8", "mono8"]
+NAMES = ["rgb8", "bgr8", "rgba8", "bgra8", "mono8"]  # the default run: the 8-bit formats, name -> UGSM_INPUT_* by position
+FLOAT = {"rgb32f": 8, "mono32f": 9}                   # integer-valued float images of the same pair: the same match, four times the input bytes
 
 
 def child(args):
     import encode_np as en
+    import float_np as fl
     from ug_stereomatcher_amd import _lib, synth
     W, H = SIZES[args.size]
-    fmt = NAMES.index(args.fmt)
     L, R, _, _ = synth.make_pair(W, H, synth.BASE_SEED + 3)
-    a, b = en.encode(L, fmt), en.encode(R, fmt)
+    if args.fmt in FLOAT:
+        fmt = FLOAT[args.fmt]
+        a, b = fl.encode(L, fmt), fl.encode(R, fmt)
+    else:
+        fmt = NAMES.index(args.fmt)
+        a, b = en.encode(L, fmt), en.encode(R, fmt)
     row = a[0].nbytes
-    out = dict(size=args.size, W=W, H=H, format=args.fmt, bytes_per_pixel=en.BPP[fmt], image_MB=row * H / 1e6)
+    out = dict(size=args.size, W=W, H=H, format=args.fmt, bytes_per_pixel=_lib.input_bytes_per_pixel(fmt), image_MB=row * H / 1e6)
 
     # K-pyr-base per image, both forms (slot 0 carries the events)
     with _lib.Context(levels=14, fovea_levels=7, slots=1, profile_events=2) as c:
@@ -70,7 +77,7 @@ def child(args):
         c.set_input_format(fmt)
         dl, dr = c.to_device(a), c.to_device(b)
         douts = [c.alloc(3 * W * H * 4) for _ in range(5)]
-        hl, hr = c.host_array(a.shape, np.uint8), c.host_array(b.shape, np.uint8)
+        hl, hr = c.host_array(a.shape, a.dtype), c.host_array(b.shape, b.dtype)
         hl[...], hr[...] = a, b
         houts = [c.host_array((3, H, W), np.float32) for _ in range(5)]
 
@@ -113,7 +120,7 @@ def main():
     ap.add_argument("--pairs", type=int, default=32)
     ap.add_argument("--reps", type=int, default=8)
     ap.add_argument("--sizes", nargs="*", default=list(SIZES))
-    ap.add_argument("--formats", nargs="*", default=NAMES)
+    ap.add_argument("--formats", nargs="*", default=NAMES, choices=NAMES + list(FLOAT))
     ap.add_argument("--timeout", type=int, default=300, help="seconds per child process")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "input_format_bench.json"))
     ap.add_argument("--child", action="store_true", help="(internal) measure one size and format, print one ROW line")
@@ -135,6 +142,8 @@ def main():
                     sys.stderr.write(p.stdout[-2000:] + p.stderr[-2000:])
                     raise SystemExit(f"child {size} {f} failed with status {p.returncode}; stopping")
                 runs.setdefault((size, f), []).append(json.loads(rows[0]))
+                sys.stderr.write(f"[input_bench] round {r + 1} of {args.rounds}: {size} {f} done\n")
+                sys.stderr.flush()
     keys = ["pyr_base_tiled_us", "pyr_base_stream_us", "device_pairs_s", "managed_pairs_s", "host_pairs_s", "service_ms"]
     table = []
     for (size, f), rs in runs.items():

@@ -92,6 +92,13 @@ UGSM_INPUT_BGR8 = 1
 UGSM_INPUT_RGBA8 = 2
 UGSM_INPUT_BGRA8 = 3
 UGSM_INPUT_MONO8 = 4
+# binary32 images, read as they stand: level 0 of the pyramid is the given floats (finite, >= 0; ugsm.h "FLOAT IMAGES")
+UGSM_INPUT_RGB32F = 8
+UGSM_INPUT_MONO32F = 9
+INPUT_BYTES_PER_PIXEL = {UGSM_INPUT_RGB8: 3, UGSM_INPUT_BGR8: 3, UGSM_INPUT_RGBA8: 4, UGSM_INPUT_BGRA8: 4, UGSM_INPUT_MONO8: 1,
+                         UGSM_INPUT_RGB32F: 12, UGSM_INPUT_MONO32F: 4}
+INPUT_ENCODINGS = {"rgb8": UGSM_INPUT_RGB8, "bgr8": UGSM_INPUT_BGR8, "rgba8": UGSM_INPUT_RGBA8, "bgra8": UGSM_INPUT_BGRA8,
+                   "mono8": UGSM_INPUT_MONO8, "32FC3": UGSM_INPUT_RGB32F, "32FC1": UGSM_INPUT_MONO32F}
 
 # which calls apply the LR check (ugsm_set_lr_check); ugsm_create leaves a context at (lr_check_threshold, UGSM_LR_FULL)
 UGSM_LR_FULL = 1
@@ -534,12 +541,14 @@ def fovea_multi_cloud_points(W: int, H: int, levels: int, fovea_levels: int, off
 
 
 def input_bytes_per_pixel(format: int) -> int:
-    """3, 3, 4, 4, 1 for UGSM_INPUT_RGB8 .. UGSM_INPUT_MONO8; -1 for an unknown format."""
+    """3, 3, 4, 4, 1 for UGSM_INPUT_RGB8 .. UGSM_INPUT_MONO8, 12 and 4 for UGSM_INPUT_RGB32F and UGSM_INPUT_MONO32F (INPUT_BYTES_PER_PIXEL);
+    -1 for an unknown format."""
     return int(load().ugsm_input_bytes_per_pixel(int(format)))
 
 
 def input_format_from_encoding(encoding) -> int:
-    """The UGSM_INPUT_* of a sensor_msgs encoding name ("rgb8", "bgr8", "rgba8", "bgra8", "mono8"); -1 for any other (and None)."""
+    """The UGSM_INPUT_* of a sensor_msgs encoding name (INPUT_ENCODINGS: "rgb8", "bgr8", "rgba8", "bgra8", "mono8", "32FC3", "32FC1"); -1 for any
+    other (and None)."""
     if isinstance(encoding, str):
         encoding = encoding.encode()
     return int(load().ugsm_input_format_from_encoding(encoding))
@@ -640,13 +649,15 @@ class Context:
         return [int(v) for v in out[:self.cfg.fovea_levels]]
 
     def check_image(self, a: np.ndarray):
-        """(H, W) uint8 for mono8, (H, W, 3) for rgb8 / bgr8, (H, W, 4) for rgba8 / bgra8, matching the context's input format; rows may be padded
-        (a view of a wider array), pixels must be contiguous.  Returns (W, H, stride)."""
+        """(H, W) uint8 for mono8, (H, W, 3) for rgb8 / bgr8, (H, W, 4) for rgba8 / bgra8, (H, W, 3) float32 for rgb32f, (H, W) float32 for mono32f,
+        matching the context's input format; rows may be padded (a view of a wider array), pixels must be contiguous.  Returns (W, H, stride)."""
         bpp = input_bytes_per_pixel(self.input_format)
-        if a.dtype != np.uint8 or not ((a.ndim == 2 and bpp == 1) or (a.ndim == 3 and a.shape[2] == bpp and bpp > 1)):
+        size = 4 if self.input_format in (UGSM_INPUT_RGB32F, UGSM_INPUT_MONO32F) else 1  # bytes per sample
+        ch = bpp // size
+        if a.dtype != (np.float32 if size == 4 else np.uint8) or not ((a.ndim == 2 and ch == 1) or (a.ndim == 3 and a.shape[2] == ch and ch > 1)):
             raise UgsmError(UGSM_ERR_SIZE_MISMATCH, f"image of shape {a.shape} and dtype {a.dtype} does not match the input format "
                                                     f"{self.input_format} ({bpp} bytes per pixel)")
-        if (a.ndim == 3 and a.strides[1:] != (bpp, 1)) or (a.ndim == 2 and a.strides[1] != 1):
+        if (a.ndim == 3 and a.strides[1:] != (bpp, size)) or (a.ndim == 2 and a.strides[1] != size):
             raise UgsmError(UGSM_ERR_BAD_ARG, "image pixels must be contiguous")
         return a.shape[1], a.shape[0], a.strides[0]
 

@@ -179,7 +179,7 @@ int cloud_args_ok(const ugsm_ctx *ctx, const float *dx, const float *dy, const f
 {
     if (!ctx || !dx || !dy || !rgb || !P1 || !P2 || !p || !points || !count) return UGSM_ERR_BAD_ARG;
     if (W < 1 || H < 1 || pw < 1 || ph < 1 || (long long)W * H > kMaxPixels || (long long)pw * ph > kMaxPixels) return UGSM_ERR_BAD_ARG;
-    if (stride < input_row_bytes(ctx, W) || p->sampling < 1 || (p->format != UGSM_CLOUD_PCL32 && p->format != UGSM_CLOUD_XYZRGB16)) return UGSM_ERR_BAD_ARG;
+    if (input_status(ctx, W, stride, rgb) != UGSM_OK || p->sampling < 1 || (p->format != UGSM_CLOUD_PCL32 && p->format != UGSM_CLOUD_XYZRGB16)) return UGSM_ERR_BAD_ARG;
     if (std::isnan(p->min_conf) || std::isnan(p->z_min) || std::isnan(p->z_max) || p->z_min > p->z_max) return UGSM_ERR_BAD_ARG;
     if (!conf && p->min_conf > -INFINITY) return UGSM_ERR_BAD_ARG;  // (a confidence test without a confidence plane)
     if (cap < 0 || ((uintptr_t)points & 15) || ((uintptr_t)count & 7)) return UGSM_ERR_BAD_ARG;
@@ -535,7 +535,7 @@ static int cloud_call_submit(ugsm_ctx *ctx, int slot, const CloudCall *call, con
     const bool fovea = call->fovea != 0, managed = call->managed != 0, planes = managed && spec.want_planes != 0;
     if (fovea && F < 2) return UGSM_ERR_BAD_ARG;
     if (W < 1 || H < 1) return UGSM_ERR_BAD_ARG;
-    if (stride < input_row_bytes(ctx, W)) return UGSM_ERR_SIZE_MISMATCH;
+    for (int b = 0; b < n; b++) UCHK(input_status(ctx, W, stride, call->job[b].L, call->job[b].R));
     HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
     c.cq_n = 0;
     if (chk) UCHK(full_checked_check(ctx, n, W, H, stride, chk->tau));

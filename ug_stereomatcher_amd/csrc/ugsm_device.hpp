@@ -40,8 +40,12 @@ static inline dim3 grid2(int W, int H, int z = 1) { return dim3((W + 255) / 256,
 // The byte layouts of an input image the image-reading kernels are instantiated for: the public formats (ugsm.h UGSM_INPUT_*, same
 // numbers) and, for the two four-byte formats, a form that reads a pixel with one 32-bit load -- the host picks it when the image's base
 // pointer and its stride are 4-byte aligned (a caller's device pointer need not be).  Every layout reads as its conversion to rgb8 would:
-// (R, G, B) = bytes (0, 1, 2) or, swapped, (2, 1, 0); mono8 (v, v, v).
-enum InLayout : int { kInRGB8 = 0, kInBGR8 = 1, kInRGBA8 = 2, kInBGRA8 = 3, kInMono8 = 4, kInRGBA8Word = 5, kInBGRA8Word = 6 };
+// (R, G, B) = bytes (0, 1, 2) or, swapped, (2, 1, 0); mono8 (v, v, v).  The two binary32 formats (rgb32f: three floats R, G, B; mono32f: one
+// float v, read as (v, v, v)) are level 0 of the pyramid as they stand: no conversion, one or three aligned dword loads per pixel (the
+// runtime refuses a float image whose base or stride is not 4-byte aligned, input_image_status).
+enum InLayout : int {
+    kInRGB8 = 0, kInBGR8 = 1, kInRGBA8 = 2, kInBGRA8 = 3, kInMono8 = 4, kInRGBA8Word = 5, kInBGRA8Word = 6, kInRGB32F = 8, kInMono32F = 9
+};
 // the layout a launch of format fmt (UGSM_INPUT_*) reads with; words: every image of the launch and the stride are 4-byte aligned
 constexpr int input_layout(int fmt, bool words) { return (words && (fmt == kInRGBA8 || fmt == kInBGRA8)) ? fmt + 3 : fmt; }
 // a launcher's one launch body for the layout it reads with: f(std::integral_constant<int, L>()) (host)
@@ -55,20 +59,30 @@ void with_layout(int layout, F &&f)
     case kInMono8: return f(std::integral_constant<int, kInMono8>());
     case kInRGBA8Word: return f(std::integral_constant<int, kInRGBA8Word>());
     case kInBGRA8Word: return f(std::integral_constant<int, kInBGRA8Word>());
+    case kInRGB32F: return f(std::integral_constant<int, kInRGB32F>());
+    case kInMono32F: return f(std::integral_constant<int, kInMono32F>());
     default: return f(std::integral_constant<int, kInRGB8>());
     }
 }
 template <int L>
 struct InPix {
-    static constexpr int bpp = L == kInMono8 ? 1 : ((L == kInRGB8 || L == kInBGR8) ? 3 : 4);
-    static constexpr bool mono = L == kInMono8;
+    static constexpr bool f32 = L == kInRGB32F || L == kInMono32F;  // samples are binary32: level 0 as given, and range-checked as it is read
+    static constexpr int bpp = L == kInRGB32F ? 12 : (L == kInMono8 ? 1 : ((L == kInRGB8 || L == kInBGR8) ? 3 : 4));
+    static constexpr bool mono = L == kInMono8 || L == kInMono32F;
     static constexpr bool swap = L == kInBGR8 || L == kInBGRA8 || L == kInBGRA8Word;
     static constexpr bool word = L == kInRGBA8Word || L == kInBGRA8Word;
-    static constexpr int channels = mono ? 1 : 3;  // distinct planes: mono8's three are one
-    // R, G, B (mono8: v in b[0] only) of the pixel at p
+    static constexpr int channels = mono ? 1 : 3;  // distinct planes: a mono image's three are one
+    // R, G, B (mono: v in b[0] only) of the pixel at p, as loaded: the 8-bit values, or a float format's bit patterns; tof() makes the sample
     __device__ static __forceinline__ void load(const uint8_t *p, unsigned (&b)[3])
     {
-        if (mono) {
+        if (f32) {
+            const unsigned *const q = reinterpret_cast<const unsigned *>(p);
+            b[0] = q[0];
+            if (!mono) {
+                b[1] = q[1];
+                b[2] = q[2];
+            }
+        } else if (mono) {
             b[0] = p[0];
         } else if (word) {
             const unsigned w = *reinterpret_cast<const unsigned *>(p);
@@ -81,10 +95,18 @@ struct InPix {
             b[2] = p[swap ? 0 : 2];
         }
     }
+    __device__ static __forceinline__ float tof(unsigned b) { return f32 ? __uint_as_float(b) : (float)b; }
     // the same as floats
     __device__ static __forceinline__ void loadf(const uint8_t *p, float (&f)[3])
     {
-        if (mono) {
+        if (f32) {
+            const float *const q = reinterpret_cast<const float *>(p);
+            f[0] = q[0];
+            if (!mono) {
+                f[1] = q[1];
+                f[2] = q[2];
+            }
+        } else if (mono) {
             f[0] = (float)p[0];
         } else if (word) {
             unsigned b[3];

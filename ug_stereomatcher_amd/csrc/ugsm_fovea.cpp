@@ -429,7 +429,7 @@ int multi_check(ugsm_ctx *ctx, int n, int W, int H, int stride, const int *&off_
         return ctx_fail(ctx, UGSM_ERR_BAD_ARG, "the checked multi-window call: not with early_exit_threshold > 0 or kernel_path 1");
     if (!tau && lr_fovea_on(ctx)) return ctx_fail(ctx, UGSM_ERR_STATE, "the foveated LR check is on: the checked multi-window call is ugsm_submit_foveated_multi_checked (ugsm_set_lr_check)");
     UCHK(ugsm_fovea_dims(W, H, ctx->cfg.levels, F, fw, fh));
-    if (stride < input_row_bytes(ctx, W)) return UGSM_ERR_SIZE_MISMATCH;
+    UCHK(input_status(ctx, W, stride));
     return UGSM_OK;
 }
 // the level buffers for n fields of fw x fh in lockstep (contexts that run window by window need one pair's alone)

@@ -329,7 +329,7 @@ int full_checked_check(ugsm_ctx *ctx, int n, int W, int H, int stride, float tau
         return ctx_fail(ctx, UGSM_ERR_BAD_ARG, "the checked full-mode call: not with early_exit_threshold > 0 or kernel_path 1");
     int w[UGSM_MAX_LEVELS], h[UGSM_MAX_LEVELS];
     UCHK(level_dims(W, H, ctx->cfg.levels, w, h));
-    if (stride < input_row_bytes(ctx, W)) return UGSM_ERR_SIZE_MISMATCH;
+    UCHK(input_status(ctx, W, stride));
     return UGSM_OK;
 }
 // ... and its buffers: A, d0 and d1 for 2 n full fields, the LR buffer for the `kept` right-to-left fields the caller does not take and the

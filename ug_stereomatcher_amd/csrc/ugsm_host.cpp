@@ -101,7 +101,7 @@ namespace ugsm {
 int stage_in(ugsm_ctx *ctx, Slot &s, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride)
 {
     if (!rgbL || !rgbR || W < 1 || H < 1) return UGSM_ERR_BAD_ARG;
-    if (stride < input_row_bytes(ctx, W)) return UGSM_ERR_SIZE_MISMATCH;
+    UCHK(input_status(ctx, W, stride, rgbL, rgbR));
     const size_t bytes = (size_t)stride * H;
     if (bytes > s.rgb_cap) {
         size_t c = s.rgb_cap;
@@ -586,7 +586,7 @@ static int stage_in_batch(ugsm_ctx *ctx, Slot &s, int n, const uint8_t *const *r
                           const uint8_t **dL, const uint8_t **dR)
 {
     if (W < 1 || H < 1) return UGSM_ERR_BAD_ARG;
-    if (stride < input_row_bytes(ctx, W)) return UGSM_ERR_SIZE_MISMATCH;
+    for (int b = 0; b < n; b++) UCHK(input_status(ctx, W, stride, rgbL[b], rgbR[b]));
     const size_t bytes = ((size_t)stride * H + 255) & ~(size_t)255;
     if (bytes * n > s.rgb_cap) {
         size_t c = s.rgb_cap;

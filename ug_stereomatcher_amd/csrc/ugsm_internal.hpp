@@ -86,8 +86,21 @@ inline int input_bpp(int format)
     case UGSM_INPUT_RGBA8:
     case UGSM_INPUT_BGRA8: return 4;
     case UGSM_INPUT_MONO8: return 1;
+    case UGSM_INPUT_RGB32F: return 12;
+    case UGSM_INPUT_MONO32F: return 4;
     default: return -1;
     }
+}
+inline bool input_float(int format) { return format == UGSM_INPUT_RGB32F || format == UGSM_INPUT_MONO32F; }
+// The one check of an image's rows and base pointers against the input format, which every entry point that takes an image passes
+// through before it enqueues anything: UGSM_ERR_SIZE_MISMATCH for stride < bytes per pixel * W; for a float format UGSM_ERR_BAD_ARG for a
+// stride that is no multiple of 4 or an image pointer (a or b; null: not looked at) that is not 4-byte aligned -- the kernels read a
+// float pixel with dword loads.
+inline int input_image_status(int format, int W, int stride, const void *a = nullptr, const void *b = nullptr)
+{
+    if ((long long)stride < (long long)input_bpp(format) * W) return UGSM_ERR_SIZE_MISMATCH;
+    if (!input_float(format)) return UGSM_OK;
+    return ((stride & 3) || (reinterpret_cast<uintptr_t>(a) & 3) || (reinterpret_cast<uintptr_t>(b) & 3)) ? UGSM_ERR_BAD_ARG : UGSM_OK;
 }
 CtxHooks &ctx_hooks(ugsm_ctx *ctx);
 const ugsm_config &ctx_config(const ugsm_ctx *ctx);
@@ -152,7 +165,7 @@ inline int refuse_common(ugsm_ctx *ctx, const char *what, int lr_mode, int n, co
     if (ugsm_get_lr_check(ctx, &tau, &modes) == UGSM_OK && tau > 0.0f && (modes & lr_mode)) return ctx_fail(ctx, UGSM_ERR_STATE, msg);
     const int st = ugsm_level_dims(W, H, cfg.levels, w, h);
     if (st != UGSM_OK) return st;
-    return stride < input_bpp(hooks.input_format) * W ? UGSM_ERR_SIZE_MISMATCH : UGSM_OK;
+    return input_image_status(hooks.input_format, W, stride);
 }
 // two buffers of abytes and bbytes share a byte
 inline bool overlap(const void *a, size_t abytes, const void *b, size_t bbytes)

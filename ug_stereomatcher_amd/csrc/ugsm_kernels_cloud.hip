@@ -175,8 +175,16 @@ __device__ __forceinline__ void tri_at(const CloudArgs &a, const Proj &P1q, cons
 // conversion to rgb8.  The three- and four-byte formats read bytes 0, 1, 2 at fixed offsets (two loads) and select the channel order.
 // Not a switch over the formats: that puts the colour loads and their waits ahead of the arithmetic, and the resized clouds' short
 // launches take up to a sixth longer.
+// A float sample as the byte of the colour word: NaN or v <= 0 -> 0, v >= 255 -> 255, else (uint8_t)(v + 0.5f) -- an integer-valued sample gives
+// the byte an 8-bit image would hold.
+__device__ __forceinline__ unsigned colour_byte(float v) { return !(v > 0.0f) ? 0u : (v >= 255.0f ? 255u : (unsigned)(v + 0.5f)); }
 __device__ __forceinline__ unsigned colour_word(const uint8_t *row, int cx, int fmt)
 {
+    if (fmt == kInMono32F) return colour_byte(reinterpret_cast<const float *>(row)[cx]) * 0x010101u;
+    if (fmt == kInRGB32F) {
+        const float *const q = reinterpret_cast<const float *>(row) + (size_t)3 * cx;
+        return colour_byte(q[0]) << 16 | colour_byte(q[1]) << 8 | colour_byte(q[2]);
+    }
     if (fmt == kInMono8) return (unsigned)row[cx] * 0x010101u;
     const bool swap = fmt == kInBGR8 || fmt == kInBGRA8;
     const uint8_t *p = row + (size_t)((fmt == kInRGBA8 || fmt == kInBGRA8) ? 4 : 3) * cx;

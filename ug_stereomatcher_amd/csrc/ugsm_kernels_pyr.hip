@@ -295,6 +295,14 @@ __global__ __launch_bounds__(256) void k_pyr_base(const uint8_t *__restrict__ rg
 #pragma unroll
             for (int k = 0; k < NC; k++) v[u][k] = in ? f[k] : 0.0f;
         }
+        if constexpr (InPix<L>::f32) {  // a float level 0 is whatever the caller sent: every in-image sample loaded is checked (zeros pass)
+            bool bad0 = false;
+#pragma unroll
+            for (int u = 0; u < NLD; u++)
+#pragma unroll
+                for (int k = 0; k < NC; k++) bad0 |= !range_ok(v[u][k]);
+            if (bad0 && range_bad) *range_bad = 1u;
+        }
 #pragma unroll
         for (int u = 0; u < NLD; u++) {
             const int it = tid + u * 256;
@@ -483,7 +491,8 @@ __global__ __launch_bounds__(256) void k_pyr_base_march(const uint8_t *__restric
         const int j2 = (cr >= y0 && cr < y1 && (cr & 1) && (cr >> 1) < H2) ? (cr >> 1) : -1;
 #pragma unroll
         for (int k = 0; k < NC; k++) {
-            const float v = (cin && yin) ? (float)bcur[k] : 0.0f;  // zero padding (U2/U3)
+            const float v = (cin && yin) ? InPix<L>::tof(bcur[k]) : 0.0f;  // zero padding (U2/U3)
+            if constexpr (InPix<L>::f32) bad |= !range_ok(v);  // (a float level 0 is the caller's: checked as it is read; the padding's zeros pass)
 #pragma unroll
             for (int e = k; e < k + NP; e++)
                 if (store0 && own && y >= y0 && y < y1) lvl0[e * n0 + (size_t)y * W + pc] = v;

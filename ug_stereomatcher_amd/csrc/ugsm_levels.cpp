@@ -80,6 +80,9 @@ int build_pyramids(ugsm_ctx *ctx, Slot &s, int si, const uint8_t *const *rgb, in
         for (int b = 0; b < nb; b++) {
             Timer t(ctx, &s, si, KC_MISC, (double)s.W * s.H);
             launch_rgb_planes(pst, rgb[b], stride, s.W, s.H, pyr + b * s.pyr_stride + s.off[0], ctx->hooks.input_format);
+            // (a float level 0 is the caller's: k_pyr_base checks it as it reads it, this path once it is written)
+            if (input_float(ctx->hooks.input_format) && s.range_known)
+                launch_range_scan(pst, pyr + b * s.pyr_stride + s.off[0], 3 * (size_t)s.W * s.H, s.range_bad + b);
         }
     }
     // CreatePyramidFromImage, MatchGPULib.cpp:1063-1106: level 1 from level 0 (sf=(float)SCALE),
@@ -353,7 +356,7 @@ int enqueue_pyramids(ugsm_ctx *ctx, Slot &s, int si, const uint8_t *const *d_rgb
     if (!d_rgbL || !d_rgbR || nb < 1 || nb > kMaxBatch) return UGSM_ERR_BAD_ARG;
     for (int b = 0; b < nb; b++)
         if (!d_rgbL[b] || !d_rgbR[b]) return UGSM_ERR_BAD_ARG;
-    if (stride < input_row_bytes(ctx, W)) return UGSM_ERR_SIZE_MISMATCH;
+    for (int b = 0; b < nb; b++) UCHK(input_status(ctx, W, stride, d_rgbL[b], d_rgbR[b]));
     UCHK(prepare_slot(ctx, s, W, H, nb));
     // the pyramid kernels of the fused path check every value they write (level 0 holds the integers 0..255)
     s.range_known = ctx->cfg.kernel_path != 1 && s.range_bad != nullptr;

@@ -447,14 +447,15 @@ void pump(ugsm_ctx *ctx, Queue *q, bool may_block)
     update_busy(ctx, q);
 }
 
-int check_geometry(ugsm_ctx *ctx, int W, int H, int stride, bool fovea)
+int check_geometry(ugsm_ctx *ctx, int W, int H, int stride, bool fovea, const void *L, const void *R)
 {
     const ugsm_config &cfg = ctx_config(ctx);
     int w[UGSM_MAX_LEVELS], h[UGSM_MAX_LEVELS];
     const int st = ugsm_level_dims(W, H, cfg.levels, w, h);
     if (st != UGSM_OK) return ctx_fail(ctx, st, "ugsm_enqueue_*: bad image size for the context's pyramid");
-    if (stride < input_bpp(ctx_hooks(ctx).input_format) * W)
-        return ctx_fail(ctx, UGSM_ERR_SIZE_MISMATCH, "ugsm_enqueue_*: stride < bytes per pixel of the input format * W");
+    const int is = input_image_status(ctx_hooks(ctx).input_format, W, stride, L, R);
+    if (is == UGSM_ERR_SIZE_MISMATCH) return ctx_fail(ctx, is, "ugsm_enqueue_*: stride < bytes per pixel of the input format * W");
+    if (is != UGSM_OK) return ctx_fail(ctx, is, "ugsm_enqueue_*: a float image's pointers and stride must be 4-byte aligned");
     if (fovea && cfg.fovea_levels < 2) return ctx_fail(ctx, UGSM_ERR_BAD_ARG, "ugsm_enqueue_foveated*: the context has no fovea levels");
     return UGSM_OK;
 }
@@ -591,7 +592,7 @@ int enqueue_pair(ugsm_ctx *ctx, const char *name, Item it, int required, const u
         snprintf(msg, sizeof msg, "%s: null buffer", name);
         return ctx_fail(ctx, UGSM_ERR_BAD_ARG, it.mem == MEM_MANAGED ? "ugsm_enqueue_*_managed: null image" : msg);
     }
-    const int g = check_geometry(ctx, it.W, it.H, it.stride, it.mode == M_FOVEA);
+    const int g = check_geometry(ctx, it.W, it.H, it.stride, it.mode == M_FOVEA, it.L, it.R);
     if (g != UGSM_OK) return g;
     if (it.mem == MEM_PINNED) {
         bool pinned = host_pinned(it.L) && host_pinned(it.R);

@@ -339,6 +339,8 @@ int ugsm_input_format_from_encoding(const char *enc)
     static const char *const names[] = {"rgb8", "bgr8", "rgba8", "bgra8", "mono8"};  // sensor_msgs/image_encodings.h, index = UGSM_INPUT_*
     for (int f = 0; f < 5; f++)
         if (strcmp(enc, names[f]) == 0) return f;
+    if (strcmp(enc, "32FC3") == 0) return UGSM_INPUT_RGB32F;  // (TYPE_32FC3, TYPE_32FC1: the channels of a 32FC3 image read as R, G, B)
+    if (strcmp(enc, "32FC1") == 0) return UGSM_INPUT_MONO32F;
     return -1;
 }
 

@@ -386,8 +386,9 @@ int ugsm_submit_fovea_shard(ugsm_ctx *ctx, int slot, const uint8_t *d_rgbL, cons
     if (cfg.fovea_levels < 2) return ctx_fail(ctx, UGSM_ERR_BAD_ARG, "ugsm_submit_fovea_shard: the context has no fovea levels");
     int fw = 0, fh = 0;
     if ((st = ugsm_fovea_dims(W, H, cfg.levels, cfg.fovea_levels, &fw, &fh)) != UGSM_OK) return st;
-    if (stride < input_bpp(ctx_hooks(ctx).input_format) * W)
-        return ctx_fail(ctx, UGSM_ERR_SIZE_MISMATCH, "ugsm_submit_fovea_shard: stride < bytes per pixel of the input format * W");
+    if ((st = input_image_status(ctx_hooks(ctx).input_format, W, stride, d_rgbL, d_rgbR)) != UGSM_OK)
+        return ctx_fail(ctx, st, st == UGSM_ERR_SIZE_MISMATCH ? "ugsm_submit_fovea_shard: stride < bytes per pixel of the input format * W"
+                                                              : "ugsm_submit_fovea_shard: a float image's pointers and stride must be 4-byte aligned");
     if (ctx_hooks(ctx).queue_busy) return ctx_fail(ctx, UGSM_ERR_STATE, "ugsm_submit_fovea_shard: pairs enqueued with ugsm_enqueue_* are outstanding");
     hipStream_t stream;
     if ((st = slot_stream(ctx, slot, &stream)) != UGSM_OK) return st;

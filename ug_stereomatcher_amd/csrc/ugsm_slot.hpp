@@ -388,6 +388,11 @@ void threshold_schedule(int mi, float *out);
 void fovea_geometry(const int *w, const int *h, int F, int off_x, int off_y, FoveaGeom &g);
 // the least stride of a W-pixel row in the context's input format
 inline int input_row_bytes(const ugsm_ctx *ctx, int W) { return input_bpp(ctx->hooks.input_format) * W; }
+// input_image_status (ugsm_internal.hpp) in the context's input format: a stride too small, or a float image that is not 4-byte aligned
+inline int input_status(const ugsm_ctx *ctx, int W, int stride, const void *a = nullptr, const void *b = nullptr)
+{
+    return input_image_status(ctx->hooks.input_format, W, stride, a, b);
+}
 int ensure_level_bufs(ugsm_ctx *ctx, Slot &s, size_t lvl);
 int lr_host_ready(ugsm_ctx *ctx, Slot &s);
 int prepare_slot(ugsm_ctx *ctx, Slot &s, int W, int H, int nb = 1);

@@ -17,7 +17,7 @@ int ugsm_stage_pyramid(ugsm_ctx *ctx, const uint8_t *d_rgb, int W, int H, int st
     Slot *s;
     UCHK(get_slot(ctx, 0, &s));
     if (!d_rgb || !d_out3 || level < 0 || level >= ctx->cfg.levels) return UGSM_ERR_BAD_ARG;
-    if (stride < input_row_bytes(ctx, W)) return UGSM_ERR_SIZE_MISMATCH;
+    UCHK(input_status(ctx, W, stride, d_rgb));
     HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
     UCHK(prepare_slot(ctx, *s, W, H));
     UCHK(build_pyramids(ctx, *s, 0, &d_rgb, stride, s->pyrL));

@@ -69,7 +69,7 @@ int ugsm_warp_planes(ugsm_ctx *ctx, int slot, const float *d_src, int channels, 
 int ugsm_warp_right(ugsm_ctx *ctx, int slot, const uint8_t *d_rgbR, int W, int H, int stride, const float *d_dispx, const float *d_dispy,
                     float *d_warp3)
 {
-    if (!ctx || !d_rgbR || !d_dispx || !d_dispy || !d_warp3 || !shape_ok(W, H) || stride < input_row_bytes(ctx, W)) return UGSM_ERR_BAD_ARG;
+    if (!ctx || !d_rgbR || !d_dispx || !d_dispy || !d_warp3 || !shape_ok(W, H) || input_status(ctx, W, stride, d_rgbR) != UGSM_OK) return UGSM_ERR_BAD_ARG;
     return warp(ctx, slot, WarpArgs{d_rgbR, stride, W, H, 3, 3, d_dispx, d_dispy, d_warp3}, ctx->hooks.input_format);
 }
 
@@ -85,7 +85,7 @@ int ugsm_photometric_residual(ugsm_ctx *ctx, int slot, const uint8_t *d_rgbL, co
                               const float *d_dispx, const float *d_dispy, const float *d_conf, double *d_sums4)
 {
     if (!ctx || !d_rgbL || !d_rgbR || !d_dispx || !d_dispy || !d_sums4 || ((uintptr_t)d_sums4 & 7) || !shape_ok(W, H) ||
-        stride < input_row_bytes(ctx, W))
+        input_status(ctx, W, stride, d_rgbL, d_rgbR) != UGSM_OK)
         return UGSM_ERR_BAD_ARG;
     ResidualArgs a{d_rgbL, d_rgbR, stride, W, H, 1, d_dispx, d_dispy, d_conf, nullptr};
     return residual(ctx, slot, a, ctx->hooks.input_format, d_sums4);

@@ -4,7 +4,9 @@ Same method names, argument meaning and results as
 /root/reference/src/gpu_matcher/MatchGPULib.h:6-47, so call sites written against the
 reference (UG_GPU_matcher.cpp:160-181,423,530-535,645) read the same.  Images are numpy
 `uint8` arrays of shape (rows, cols, 3) in rgb8 order -- what `cv_bridge::toCvCopy(msg,
-RGB8)->image` holds.  Differences, all deliberate:
+RGB8)->image` holds -- or `float32` arrays, (rows, cols, 3) or (rows, cols), which the library
+reads as they stand (UGSM_INPUT_RGB32F / UGSM_INPUT_MONO32F: a 32FC3 / 32FC1 image, a 16-bit
+camera's v / 256).  Differences, all deliberate:
   * results are returned as numpy arrays owned by the caller (the reference mallocs and
     expects the caller to free, UG_GPU_matcher.cpp:487-489);
   * one persistent context per object, no cudaDeviceReset per call (MatchGPULib.cpp:400);
@@ -36,17 +38,26 @@ def _parse_argv(argv):
     return device, fovea_levels
 
 
-def _as_rgb8(img) -> np.ndarray:
+def _as_image(img):
+    """(array, UGSM_INPUT_*): a uint8 (rows, cols, 3) rgb8 image, or a float32 image read as it stands -- (rows, cols, 3) as rgb32f,
+    (rows, cols) as mono32f (level 0 of the pyramid is these floats; samples finite and >= 0).  Rows may be padded, pixels are contiguous."""
     a = np.asarray(img)
-    if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3:
-        raise UgsmError(_lib.UGSM_ERR_BAD_ARG, "image must be uint8 (rows, cols, 3) rgb8")
-    if a.strides[2] != 1 or a.strides[1] != 3:
+    if a.dtype == np.uint8 and a.ndim == 3 and a.shape[2] == 3:
+        fmt, pixel = _lib.UGSM_INPUT_RGB8, (3, 1)
+    elif a.dtype == np.float32 and a.ndim == 3 and a.shape[2] == 3:
+        fmt, pixel = _lib.UGSM_INPUT_RGB32F, (12, 4)
+    elif a.dtype == np.float32 and a.ndim == 2:
+        fmt, pixel = _lib.UGSM_INPUT_MONO32F, (4,)
+    else:
+        raise UgsmError(_lib.UGSM_ERR_BAD_ARG, "image must be uint8 (rows, cols, 3) rgb8, or float32 (rows, cols, 3) / (rows, cols)")
+    if a.strides[1:] != pixel or a.strides[0] % a.itemsize:
         a = np.ascontiguousarray(a)
-    return a
+    return a, fmt
 
 
 class MatchGPULib:
     MAX_LEVEL = 14  # MatchLib_common.h:13
+    float_images = True  # float32 images are read as they stand (_as_image): the service hands 32FC3 / 32FC1 payloads over in place
 
     def __init__(self, argc: int = 0, argv=None, *, levels: int = MAX_LEVEL, kernel_path: int = 0, frames_in_flight: int = 1):
         """frames_in_flight > 1 (not in the reference): the context gets min(frames_in_flight, 4) slots and the pipelined calls below
@@ -62,6 +73,16 @@ class MatchGPULib:
         batch = min(8, -(-self.frames_in_flight // slots))
         self._ctx = Context(device=device, levels=levels, fovea_levels=fl, slots=slots, kernel_path=kernel_path, batch=batch)
         self._tags = {}     # tag -> (kind, rows, cols, want_pyr) of the pairs outstanding in the queue
+
+    def _take(self, cv_ptrL, cv_ptrR):
+        """The pair as the library reads it, in place, and the context's input format set to match (ugsm_set_input_format: captured by the
+        call that follows)."""
+        (L, fl), (R, fr) = _as_image(cv_ptrL), _as_image(cv_ptrR)
+        if fl != fr or L.shape != R.shape or L.strides[0] != R.strides[0]:
+            raise UgsmError(_lib.UGSM_ERR_SIZE_MISMATCH, "left/right images differ in size or format")
+        if self._ctx.input_format != fl:
+            self._ctx.set_input_format(fl)
+        return L, R
 
     # -- getters / setters, MatchGPULib.cpp:268-301 --
     def getFoveaWidth(self) -> int:
@@ -95,9 +116,7 @@ class MatchGPULib:
         """Returns finDisp: float32 (3, rows, cols) = horizontal, vertical disparity and confidence.
         tau (> 0, fov == 0; not in the reference): the LR check for this call alone, both directions in one lockstep call
         (ugsm_match_full_checked) -- returns (finDisp, backDisp): the checked fields of the left and of the right camera."""
-        L, R = _as_rgb8(cv_ptrL), _as_rgb8(cv_ptrR)
-        if L.shape != R.shape or L.strides[0] != R.strides[0]:
-            raise UgsmError(_lib.UGSM_ERR_SIZE_MISMATCH, "left/right images differ in size")
+        L, R = self._take(cv_ptrL, cv_ptrR)
         self.foveatedmatching = fov
         if tau is not None:
             if fov != 0:
@@ -120,27 +139,21 @@ class MatchGPULib:
     def matchSeeded(self, cv_ptrL, cv_ptrR, prior, start_level: int) -> np.ndarray:
         """(not in the reference) match(L, R, 0) started at level start_level from `prior`, a finDisp of the images' size -- the previous
         frame's, say -- instead of from the zero seed at the top level (ugsm_match_full_seeded).  Returns finDisp."""
-        L, R = _as_rgb8(cv_ptrL), _as_rgb8(cv_ptrR)
-        if L.shape != R.shape or L.strides[0] != R.strides[0]:
-            raise UgsmError(_lib.UGSM_ERR_SIZE_MISMATCH, "left/right images differ in size")
+        L, R = self._take(cv_ptrL, cv_ptrR)
         self.foveatedmatching = 0
         return self._ctx.match_full_seeded(L, R, np.asarray(prior, np.float32), start_level)
 
     def matchCoarse(self, cv_ptrL, cv_ptrR, stop_level: int, want_full: bool = False):
         """(not in the reference) match(L, R, 0) stopped when level stop_level has finished (ugsm_match_full_coarse): that level's field,
         (3, h, w) of the level's size; with want_full, (state, its prolongation to the images' size, a finDisp)."""
-        L, R = _as_rgb8(cv_ptrL), _as_rgb8(cv_ptrR)
-        if L.shape != R.shape or L.strides[0] != R.strides[0]:
-            raise UgsmError(_lib.UGSM_ERR_SIZE_MISMATCH, "left/right images differ in size")
+        L, R = self._take(cv_ptrL, cv_ptrR)
         self.foveatedmatching = 0
         return self._ctx.match_full_coarse(L, R, stop_level, want_full)
 
     def matchFine(self, cv_ptrL, cv_ptrR, state, state_level: int) -> np.ndarray:
         """(not in the reference) the rest of match(L, R, 0) from `state`, the field of level state_level that matchCoarse returned
         (ugsm_match_full_fine): with the same pair, match(L, R, 0)'s finDisp bit for bit.  Returns finDisp."""
-        L, R = _as_rgb8(cv_ptrL), _as_rgb8(cv_ptrR)
-        if L.shape != R.shape or L.strides[0] != R.strides[0]:
-            raise UgsmError(_lib.UGSM_ERR_SIZE_MISMATCH, "left/right images differ in size")
+        L, R = self._take(cv_ptrL, cv_ptrR)
         self.foveatedmatching = 0
         return self._ctx.match_full_fine(L, R, np.asarray(state, np.float32), state_level)
 
@@ -175,9 +188,7 @@ class MatchGPULib:
                 c.free(p)
 
     def _stack(self, cv_ptrL, cv_ptrR, want_pyr: bool, off_x: int = 0, off_y: int = 0):
-        L, R = _as_rgb8(cv_ptrL), _as_rgb8(cv_ptrR)
-        if L.shape != R.shape or L.strides[0] != R.strides[0]:
-            raise UgsmError(_lib.UGSM_ERR_SIZE_MISMATCH, "left/right images differ in size")
+        L, R = self._take(cv_ptrL, cv_ptrR)
         rows, cols = L.shape[:2]
         F = self.foveatelevel
         fw, fh = _lib.fovea_dims(cols, rows, self._levels, F)
@@ -201,9 +212,7 @@ class MatchGPULib:
         """(not in the reference) matchStack(L, R, *off) started at fovea level start_level from `prior_stack` -- what matchStack returned for
         the previous frame at the offsets `prior_off`, which may differ from `off` -- instead of from the zero seed at the top level
         (ugsm_match_foveated_warm).  Returns float32 (foveatelevel, 3, fovH, fovW); the levels above start_level are the prior carried over."""
-        L, R = _as_rgb8(cv_ptrL), _as_rgb8(cv_ptrR)
-        if L.shape != R.shape or L.strides[0] != R.strides[0]:
-            raise UgsmError(_lib.UGSM_ERR_SIZE_MISMATCH, "left/right images differ in size")
+        L, R = self._take(cv_ptrL, cv_ptrR)
         rows, cols = L.shape[:2]
         F = self.foveatelevel
         fw, fh = _lib.fovea_dims(cols, rows, self._levels, F)
@@ -219,9 +228,7 @@ class MatchGPULib:
         """matchStack for every (off_x, off_y) of `offsets` (1 .. 16) in one call -- pyramids and the coarse levels once, the windows' fine
         levels in lockstep.  Returns one float32 (foveatelevel, 3, fovH, fovW) per window, each what matchStack returns for its offset.
         tau (> 0): the checked call -- both directions in lockstep, each stack what matchStack returns under setLRCheck(tau, 2)."""
-        L, R = _as_rgb8(cv_ptrL), _as_rgb8(cv_ptrR)
-        if L.shape != R.shape or L.strides[0] != R.strides[0]:
-            raise UgsmError(_lib.UGSM_ERR_SIZE_MISMATCH, "left/right images differ in size")
+        L, R = self._take(cv_ptrL, cv_ptrR)
         rows, cols = L.shape[:2]
         self.fovW, self.fovH = _lib.fovea_dims(cols, rows, self._levels, self.foveatelevel)
         stacks = self._ctx.match_foveated_multi(L, R, [(int(x), int(y)) for x, y in offsets], tau)
@@ -235,9 +242,7 @@ class MatchGPULib:
     # -- the pipelined twin of match / matchStack / matchStackPyramid (not in the reference; include/ugsm.h "the queue") --
     def enqueueMatch(self, cv_ptrL, cv_ptrR, tag: int):
         """match(L, R, 0) without the wait: the images are copied before the call returns; the result comes out of nextDone."""
-        L, R = _as_rgb8(cv_ptrL), _as_rgb8(cv_ptrR)
-        if L.shape != R.shape or L.strides[0] != R.strides[0]:
-            raise UgsmError(_lib.UGSM_ERR_SIZE_MISMATCH, "left/right images differ in size")
+        L, R = self._take(cv_ptrL, cv_ptrR)
         self._ctx.enqueue_full_managed(L, R, tag)
         self._tags[tag] = ("full", L.shape[0], L.shape[1], False)
         self._ctx.flush()   # a frame that arrives starts at once if a slot is free; under load the backlog batches itself
@@ -245,18 +250,14 @@ class MatchGPULib:
     def enqueueMatchChecked(self, cv_ptrL, cv_ptrR, tau: float, tag: int):
         """enqueueMatch with the LR check of this pair at threshold tau (> 0; ugsm_enqueue_full_checked_managed): both directions of the pairs of a
         call in lockstep, whatever the context's own setting; nextDone hands out the checked field of the left camera."""
-        L, R = _as_rgb8(cv_ptrL), _as_rgb8(cv_ptrR)
-        if L.shape != R.shape or L.strides[0] != R.strides[0]:
-            raise UgsmError(_lib.UGSM_ERR_SIZE_MISMATCH, "left/right images differ in size")
+        L, R = self._take(cv_ptrL, cv_ptrR)
         self._ctx.enqueue_full_checked_managed(L, R, float(tau), False, tag)
         self._tags[tag] = ("full", L.shape[0], L.shape[1], False)
         self._ctx.flush()
 
     def enqueueStack(self, cv_ptrL, cv_ptrR, tag: int, want_pyr: bool = False, off_x: int = 0, off_y: int = 0):
         """matchStack / matchStackPyramid without the wait."""
-        L, R = _as_rgb8(cv_ptrL), _as_rgb8(cv_ptrR)
-        if L.shape != R.shape or L.strides[0] != R.strides[0]:
-            raise UgsmError(_lib.UGSM_ERR_SIZE_MISMATCH, "left/right images differ in size")
+        L, R = self._take(cv_ptrL, cv_ptrR)
         rows, cols = L.shape[:2]
         self.fovW, self.fovH = _lib.fovea_dims(cols, rows, self._levels, self.foveatelevel)
         self._ctx.enqueue_foveated_managed(L, R, (off_x, off_y), want_pyr, tag)

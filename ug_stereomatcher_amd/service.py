@@ -60,6 +60,9 @@ class Image:  # sensor_msgs/Image
     def to_array(self) -> np.ndarray:
         if self.encoding == "32FC1":
             return np.frombuffer(self.data, np.float32).reshape(self.height, self.step // 4)[:, : self.width]
+        if self.encoding == "32FC3":
+            return np.frombuffer(self.data, np.float32).reshape(self.height, self.step // 4)[:, : 3 * self.width].reshape(
+                self.height, self.width, 3)
         if self.encoding in ("rgb8", "bgr8"):
             return np.frombuffer(self.data, np.uint8).reshape(self.height, self.step)[:, : 3 * self.width].reshape(
                 self.height, self.width, 3)
@@ -119,6 +122,15 @@ def to_cv_copy_rgb8(msg: Image) -> np.ndarray:
     raise ValueError(f"Could not convert from '{msg.encoding}' to 'rgb8'.")
 
 
+def to_matcher_image(msg: Image, float_images: bool = True) -> np.ndarray:
+    """The image the matcher is handed: a 32FC3 / 32FC1 message's payload in place (float32 (rows, cols, 3) / (rows, cols), rows as
+    padded as the message's step: the library reads it as UGSM_INPUT_RGB32F / UGSM_INPUT_MONO32F, no rounding to bytes), any other
+    encoding through to_cv_copy_rgb8 -- as is every encoding for a matcher that takes rgb8 alone (float_images False)."""
+    if float_images and msg.encoding in ("32FC3", "32FC1") and msg.step % 4 == 0:
+        return msg.to_array()
+    return to_cv_copy_rgb8(msg)
+
+
 class GPUMatcher:
     """class GPU_matcher, UG_GPU_matcher.cpp:66-738, minus the ROS transport."""
 
@@ -159,6 +171,11 @@ class GPUMatcher:
             self._mgpu = MatchGPULib(self.cmd_argc, self.cmd_argv, **kw)
         return self._mgpu
 
+    def _image(self, msg: Image) -> np.ndarray:
+        """to_matcher_image for this node's matcher (asked only for a float message: a conversion that fails needs no matcher)."""
+        floats = msg.encoding in ("32FC3", "32FC1") and getattr(self._matcher(), "float_images", False)
+        return to_matcher_image(msg, floats)
+
     @staticmethod
     def _stack_msg(planes: np.ndarray, header: Header, L: np.ndarray, fw: int, fh: int, F: int, fill_dims: bool):
         """(F, fovH, fovW) -> (F*fovH) x fovW 32FC1, finest level first (:293-320)."""
@@ -171,8 +188,8 @@ class GPUMatcher:
     def disparitySrv(self, req: GetDisparitiesGPURequest, rsp: GetDisparitiesGPUResponse) -> bool:
         """GPU_matcher::disparitySrv, :497-694."""
         try:
-            L = to_cv_copy_rgb8(req.imL)
-            R = to_cv_copy_rgb8(req.imR)
+            L = self._image(req.imL)
+            R = self._image(req.imR)
         except ValueError:
             return False  # :516-520
         self.foveated = self._read_foveated()
@@ -200,8 +217,8 @@ class GPUMatcher:
     def mainRoutine(self, imL: Image, imR: Image) -> None:
         """GPU_matcher::mainRoutine, :126-494 (synchronised input_left_image/input_right_image)."""
         try:
-            L = to_cv_copy_rgb8(imL)
-            R = to_cv_copy_rgb8(imR)
+            L = self._image(imL)
+            R = self._image(imR)
         except ValueError:
             return  # :146-150
         self.foveated = self._read_foveated()
