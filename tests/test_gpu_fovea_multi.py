@@ -219,6 +219,30 @@ def test_level_buffers_that_cannot_grow(lib, orc, monkeypatch):
             c.free(p)
 
 
+def test_windows_are_refused_when_the_slot_fell_back_to_one_pair(lib, orc, monkeypatch):
+    """A context created for batches of sixteen whose buffers cannot be had (UGSM_MEM_LIMIT_MB: sixteen pairs' pyramids need 64 MB): building
+    the pyramids gives the slot's buffers back and sizes them for the call's one pair -- AFTER the call has grown the level buffers for its
+    windows.  Five windows at F = 2 no longer fit there (7.5 MB against one pair's 3 MB): the call answers UGSM_ERR_STATE with its message
+    before any level is enqueued, and the slot serves a call that fits."""
+    W, H, lv, F = 333, 251, 8, 2
+    L, R = _pair(W, H)
+    fw, fh = lib.fovea_dims(W, H, lv, F)
+    monkeypatch.setenv("UGSM_MEM_LIMIT_MB", "30")
+    with lib.Context(levels=lv, fovea_levels=F, batch=16) as c:
+        dL, dR = c.to_device(L), c.to_device(R)
+        dS = c.alloc(3 * F * fh * fw * 4)
+        five = (C.c_void_p * 5)(*([dS] * 5))
+        st = c.lib.ugsm_submit_foveated_multi(c.handle, 0, dL, dR, W, H, 3 * W, 5, None, None, five)
+        assert st == lib.UGSM_ERR_STATE, st
+        assert b"the level buffers do not hold the windows' fields" in c.lib.ugsm_last_error(c.handle)
+        c.check(c.lib.ugsm_wait(c.handle, 0))
+        got = _multi(c, lib, dL, dR, W, H, 3 * W, lv, F, OFFS[:2])         # n = 2 = 2^(F-1): one pair's buffers hold it
+        for k, off in enumerate(OFFS[:2]):
+            assert_bit_equal(got[k], _answer(orc, L, R, lv, F, off), f"after the refused call, window {k}")
+        for p in (dL, dR, dS):
+            c.free(p)
+
+
 # ---- 5. level 0 only where a window lies -----------------------------------------------------------------------------------------------------
 
 def test_level0_is_stored_in_the_windows_alone(lib):

@@ -540,20 +540,21 @@ static int cloud_call_submit(ugsm_ctx *ctx, int slot, const CloudCall *call, con
     c.cq_n = 0;
     if (chk) UCHK(full_checked_check(ctx, n, W, H, stride, chk->tau));
     const bool by_pair = n == 1 || (!chk && (fovea ? fovea_batch_runs_pair_by_pair(ctx) : batch_runs_pair_by_pair(ctx)));
-    int fw = W, fh = H;
-    if (fovea) UCHK(ugsm_fovea_dims(W, H, ctx->cfg.levels, F, &fw, &fh));
-    const size_t px = (size_t)W * H, fn = (size_t)fw * fh, stackn = (size_t)F * fn;
-    const size_t plane = fovea ? stackn : px;  // floats per result plane: the pair's result is three of them
+    // a foveated call's states lie at the front of hout (FoveaRoom): one for a managed call that runs pair by pair, n otherwise
+    const int copies = managed && by_pair ? 1 : n;
+    FoveaRoom room;
+    if (fovea) UCHK(fovea_room(ctx, W, H, FoveaCall::Pairs, copies, room));
+    const int fw = fovea ? room.fw : W, fh = fovea ? room.fh : H;
+    const size_t plane = fovea ? room.plane : (size_t)W * H;  // floats per result plane: the pair's result is three of them
     const int step = p.format == UGSM_CLOUD_PCL32 ? 32 : 16;
 
-    // 1. where every pair's images, state and result lie on the device
+    // 1. where every pair's images and result lie on the device
     const uint8_t *dL[UGSM_MAX_BATCH], *dR[UGSM_MAX_BATCH];
-    float *state[UGSM_MAX_BATCH], *res[UGSM_MAX_BATCH], *back[UGSM_MAX_BATCH] = {nullptr};  // back: a checked pair's right-to-left field, where it is taken
-    const size_t st_per = fovea ? ((3 * fn + 63) & ~(size_t)63) : 0, res_per = (3 * plane + 63) & ~(size_t)63;
+    float *res[UGSM_MAX_BATCH], *back[UGSM_MAX_BATCH] = {nullptr};  // back: a checked pair's right-to-left field, where it is taken
+    const size_t res_per = (3 * plane + 63) & ~(size_t)63;
     if (managed) {
-        // the slot's uploads and hout: [states][results], one of each for a call that runs pair by pair, n otherwise; a checked call: [back fields]
+        // the slot's uploads and hout: [states][results], one result for a call that runs pair by pair, n otherwise; a checked call: [back fields]
         // behind them
-        const int copies = by_pair ? 1 : n;
         const size_t img = ((size_t)stride * H + 255) & ~(size_t)255;
         if (img * copies > s->rgb_cap) {
             size_t c = s->rgb_cap;
@@ -562,22 +563,21 @@ static int cloud_call_submit(ugsm_ctx *ctx, int slot, const CloudCall *call, con
         }
         bool any_back = false;
         for (int b = 0; chk && b < n; b++) any_back = any_back || chk->job[b].back_planes[0];
-        UCHK(grow(ctx, s->hout, s->hout_cap, std::max(copies * (st_per + (any_back ? 2 : 1) * res_per), s->hout_cap)));
+        const size_t at_res = room.part(copies * res_per), at_back = room.part(any_back ? copies * res_per : 0);
+        UCHK(grow(ctx, s->hout, s->hout_cap, room.total));
         for (int b = 0; b < n; b++) {
             const int k = by_pair ? 0 : b;
             dL[b] = s->rgbL + k * img;
             dR[b] = s->rgbR + k * img;
-            state[b] = s->hout + k * st_per;
-            res[b] = s->hout + copies * st_per + k * res_per;
-            if (chk && chk->job[b].back_planes[0]) back[b] = s->hout + copies * (st_per + res_per) + k * res_per;
+            res[b] = s->hout + at_res + k * res_per;
+            if (chk && chk->job[b].back_planes[0]) back[b] = s->hout + at_back + k * res_per;
         }
     } else {
-        UCHK(grow(ctx, s->hout, s->hout_cap, std::max(st_per * n, s->hout_cap)));
+        UCHK(grow(ctx, s->hout, s->hout_cap, room.total));
         for (int b = 0; b < n; b++) {
             if (!call->job[b].L || !call->job[b].R || !call->job[b].out) return UGSM_ERR_BAD_ARG;
             dL[b] = call->job[b].L;
             dR[b] = call->job[b].R;
-            state[b] = s->hout + (by_pair ? 0 : b * st_per);
             res[b] = call->job[b].out;
             if (chk) back[b] = chk->job[b].back;
         }
@@ -658,7 +658,7 @@ static int cloud_call_submit(ugsm_ctx *ctx, int slot, const CloudCall *call, con
             UCHK(full_checked_bufs(ctx, *s, k, kept, W, H));
             return enqueue_full_checked(ctx, *s, slot, k, dL + b, dR + b, W, H, stride, res + b, back + b, chk->tau);
         }
-        return fovea ? enqueue_match_foveated(ctx, *s, slot, k, dL + b, dR + b, W, H, stride, ox + b, oy + b, state + b, res + b, nullptr, nullptr)
+        return fovea ? enqueue_foveated(ctx, *s, slot, dL + b, dR + b, W, H, stride, FoveaCall::pairs(k, ox + b, oy + b, res + b))
                      : enqueue_match_full(ctx, *s, slot, k, dL + b, dR + b, W, H, stride, res + b);
     };
     const bool cloud_by_pair = by_pair || !batch_level(ctx, (fovea ? F : 1) * wc, hc);  // (a pair's sampled points against kBatchMaxPixels)

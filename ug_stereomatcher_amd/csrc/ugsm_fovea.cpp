@@ -1,7 +1,9 @@
-// ugsm_fovea.cpp -- the foveated calls: the windows of a call's pairs, the fine phase (matching() with foveatedmatching == 1 below level
-// F-1), the call with its LR check in lockstep, the warm call from a prior stack, several windows on one pair and their checked form, and
-// hierarchicalDisparity over the stacks.  The coarse phase is the full-frame descent stopped at level F-1 (enqueue_fovea_coarse,
-// ugsm_full.cpp); the levels' own work is ugsm_levels.cpp.  At the end the ugsm_submit_* entry points of the family.
+// ugsm_fovea.cpp -- the foveated calls.  First the steps: the windows of a call's pairs, the fine phase (matching() with foveatedmatching == 1
+// below level F-1), the stack check, the restriction from priors, level 0 inside several windows.  Then the one sequence made of them
+// (enqueue_foveated), which every kind of call -- pairs, with the LR check in lockstep, several windows on one pair and their checked form, warm
+// from a prior -- goes through as a FoveaCall, with the one function that grows its buffers (fovea_grow).  The coarse phase is the full-frame
+// descent stopped at level F-1 (enqueue_fovea_coarse, ugsm_full.cpp); the levels' own work is ugsm_levels.cpp.  At the end the ugsm_submit_*
+// entry points of the family, and hierarchicalDisparity over the stacks.
 #include "ugsm_slot.hpp"
 
 #include <algorithm>
@@ -102,14 +104,6 @@ int enqueue_fovea_fine(ugsm_ctx *ctx, Slot &s, int si, const Shape &sh, const fl
     return UGSM_OK;
 }
 
-// pair 0's range word into the entries 1 .. m - 1 (windows of one pair run under its word), doubling what is already there
-int spread_range_word(ugsm_ctx *ctx, Slot &s, int m)
-{
-    for (int c = 1; s.range_known && c < m; c *= 2)
-        HIPCHK(ctx, hipMemcpyAsync(s.range_bad + c, s.range_bad, sizeof(unsigned) * std::min(c, m - c), hipMemcpyDeviceToDevice, s.st));
-    return UGSM_OK;
-}
-
 // The room a checked foveated call takes in the slot's LR buffer, in floats.  Entry k's right-to-left stack lies at k * per; the count words (one
 // of 8 bytes per (entry, level); at a multiple of 64 floats: aligned) at cnt.  The right-to-left level-F-1 state: n pairs keep one each behind
 // their stack, at k * per + state; n windows of one pair (one_state) share one behind the last stack, at state.
@@ -160,51 +154,6 @@ int enqueue_fovea_fine(ugsm_ctx *ctx, Slot &s, int si, const float *d_state, int
 }
 
 }  // namespace
-
-// One foveated call of n pairs on device buffers: the pyramids, the coarse levels, the fine levels into the pairs' stacks.  state: n buffers
-// of 3 fovW fovH floats for level F-1's field between the two phases; d_pyrL / d_pyrR as for enqueue_fovea_fine.
-// With the foveated LR check on (ugsm_set_lr_check) the call matches both directions in lockstep and checks the stacks against each other:
-//   - the pyramids are built once; entry n + b of the shape reads pair b's with the L and R views exchanged (pair_pyr), through pair b's windows
-//     and seed maps, under pair b's range word (it covers both images' pyramids: build_pyramids reports either image into range_bad[pair]);
-//     every kernel of a level takes the 2 n entries in one launch except K-cost, which takes each direction in one (run_level);
-//   - every field of a foveated call is at most fovW x fovH, so the 2 n fields lie in the slot's level buffers at a stride of one such field
-//     (n pairs hold n x 3 W H floats per buffer and need 2 n x 3 fovW fovH, fovW fovH <= W H / 2 for every F >= 2: it fits, for F = 2 just);
-//   - what does NOT fit there for F = 2 is the right-to-left STACK, which has to outlive the fine levels: A, d0 and d1 are then full.  It goes,
-//     with the right-to-left state, into the slot's LR buffer (Slot::lr, what the full-mode check keeps its second field in; lr_room): 3 (F + 1)
-//     fovW fovH floats per pair, 24 MB at 16 MP beside the pair's 1.35 GB, counted by ugsm_context_device_bytes;
-//   - one launch checks every level of every pair's stack after the last level (enqueue_lr_stack_check).
-int enqueue_match_foveated(ugsm_ctx *ctx, Slot &s, int si, int n, const uint8_t *const *d_rgbL, const uint8_t *const *d_rgbR, int W, int H, int stride,
-                                 const int *off_x, const int *off_y, float *const *state, float *const *d_stack, float *const *d_pyrL, float *const *d_pyrR)
-{
-    const int F = ctx->cfg.fovea_levels;
-    FoveaWin win;
-    UCHK(fovea_windows(ctx, W, H, n, off_x, off_y, win));
-    if (!lr_fovea_on(ctx)) {
-        // (a single pair alone on the chip gets level F-1 .. top's A planes from the side stream; a batch computes A in line)
-        UCHK(enqueue_pyramids(ctx, s, si, d_rgbL, d_rgbR, n, W, H, stride, n == 1 ? F - 1 : -1, &win));
-        const Shape sh = Shape::pairs(s);
-        UCHK(enqueue_fovea_coarse(ctx, s, si, sh, state));
-        return enqueue_fovea_fine(ctx, s, si, sh, state, off_x, off_y, d_stack, d_pyrL, d_pyrR);
-    }
-    UCHK(enqueue_pyramids(ctx, s, si, d_rgbL, d_rgbR, n, W, H, stride, -1, &win));
-    const int fw = s.w[F - 1], fh = s.h[F - 1];
-    const Shape sh = Shape::both_directions(n, field_room((size_t)fw * fh));
-    const LrRoom room = lr_room(n, F, fw, fh, false);
-    UCHK(ensure_level_bufs(ctx, s, sh.nb * sh.stride));  // (holds already: see above)
-    UCHK(grow(ctx, s.lr, s.lr_cap, room.total));
-    UCHK(lr_host_ready(ctx, s));
-    if (s.range_known) HIPCHK(ctx, hipMemcpyAsync(s.range_bad + n, s.range_bad, sizeof(unsigned) * n, hipMemcpyDeviceToDevice, s.st));
-    float *vstate[2 * kMaxBatch], *vstack[2 * kMaxBatch];
-    for (int b = 0; b < n; b++) {
-        vstate[b] = state[b];
-        vstack[b] = d_stack[b];
-        vstack[n + b] = s.lr + (size_t)b * room.per;
-        vstate[n + b] = vstack[n + b] + room.state;
-    }
-    UCHK(enqueue_fovea_coarse(ctx, s, si, sh, vstate));
-    UCHK(enqueue_fovea_fine(ctx, s, si, sh, vstate, off_x, off_y, vstack, d_pyrL, d_pyrR));
-    return enqueue_lr_stack_check(ctx, s, si, n, F, fw, fh, ctx->lr_tau, d_stack, room.per, reinterpret_cast<unsigned long long *>(s.lr + room.cnt));
-}
 
 // The starting fields of the fovea levels start .. F-1 of n entries from their priors, one launch (launch_restrict_stack): the rows from the
 // two windows' geometries; up to kRestrictStackByValue of them in the launch's arguments, more through the slot's table.  Level `start` goes
@@ -271,35 +220,6 @@ int enqueue_restrict_stack(ugsm_ctx *ctx, Slot &s, int si, int n, const int *w, 
     return UGSM_OK;
 }
 
-// The warm foveated call (ugsm_submit_foveated_warm[_field]; its refusals: ugsm_fovea_seeded.cpp): n pairs in lockstep from fovea level `start`
-// of their priors.  The pyramids stop at level max(start, 2), level 0 inside the new windows; A is computed in line at every level (level F-1,
-// where it is matched, included: the side stream's A planes serve the coarse phase, which does not run).  One launch writes every starting
-// field: level `start`'s into the level buffer the fine phase starts in, the levels above into the stacks' row blocks.
-int enqueue_match_foveated_warm(ugsm_ctx *ctx, Slot &s, int si, int n, const uint8_t *const *d_rgbL, const uint8_t *const *d_rgbR, int W, int H, int stride,
-                                const int *off_x, const int *off_y, const float *const *d_prior, const int *poff_x, const int *poff_y, bool field, int start,
-                                float *const *d_stack)
-{
-    const int F = ctx->cfg.fovea_levels;
-    FoveaWin win;
-    UCHK(fovea_windows(ctx, W, H, n, off_x, off_y, win));
-    UCHK(enqueue_pyramids(ctx, s, si, d_rgbL, d_rgbR, n, W, H, stride, -1, &win, false, 0, start));
-    const Shape sh = Shape::pairs(s);
-    UCHK(enqueue_restrict_stack(ctx, s, si, n, s.w, s.h, F, d_prior, poff_x, poff_y, field, off_x, off_y, start, d_stack, s.d0, sh.stride));
-    return enqueue_fovea_fine(ctx, s, si, sh, nullptr, off_x, off_y, d_stack, nullptr, nullptr, start);
-}
-int fovea_warm_submit(ugsm_ctx *ctx, int slot, int n, const uint8_t *const *d_rgbL, const uint8_t *const *d_rgbR, int W, int H, int stride, const int *off_x,
-                            const int *off_y, const float *const *d_prior, const int *prior_off_x, const int *prior_off_y, int field, int start_level,
-                            float *const *d_stack)
-{
-    const int zeros[UGSM_MAX_BATCH] = {0};
-    const int *ox = off_x ? off_x : zeros, *oy = off_y ? off_y : zeros, *px = prior_off_x ? prior_off_x : zeros, *py = prior_off_y ? prior_off_y : zeros;
-    const int per = (n == 1 || fovea_batch_runs_pair_by_pair(ctx)) ? 1 : n;  // (kernel_path 1: the pairs one after the other, as ugsm_submit_foveated_batch)
-    return submit_pairs(ctx, slot, n, per, [&](Slot &s, int b, int k) {
-        return enqueue_match_foveated_warm(ctx, s, slot, k, d_rgbL + b, d_rgbR + b, W, H, stride, ox + b, oy + b, d_prior + b, px + b, py + b, field != 0,
-                                           start_level, d_stack + b);
-    });
-}
-
 // Level 0 of both images inside the n windows of a multi-window call (k_pyr_base stored none: FoveaWin::later), one launch.
 static int enqueue_level0_windows(ugsm_ctx *ctx, Slot &s, int si, const uint8_t *d_rgbL, const uint8_t *d_rgbR, int stride, int n, const FoveaWin &win)
 {
@@ -328,123 +248,150 @@ static int enqueue_level0_windows(ugsm_ctx *ctx, Slot &s, int si, const uint8_t 
     return UGSM_OK;
 }
 
-// n fovea windows on ONE pair (ugsm_submit_foveated_multi): what does not depend on the window runs once, the rest in lockstep.
-//   - the pyramids of one pair, as a lone foveated call builds them (side stream and A planes of levels F-1 .. top included), but with no
-//     level 0 (FoveaWin::later); one launch then writes level 0 of both images inside the n windows (k_level0_windows).  Pyramids
-//     that k_pyr_base does not build (fewer than three levels, kernel_path 1) hold level 0 whole and skip that launch;
-//   - the coarse phase once, its field into `state`;
-//   - the fine phase on a shape of n windows that all read pair 0's pyramids (Shape::one_pair, pair_pyr), start from the one state and
-//     run under pair 0's range word; their fields lie in the level buffers at a stride of one fovea field, as a checked call's do.  The
-//     caller has made the buffers hold n such fields (n x 3 fovW fovH floats exceed one pair's 3 W H as soon as n > 2^(F-1));
-//   - contexts that run pair by pair (early exit, kernel_path 1) and n == 1: the fine phase window after window, as single pairs.
-// Afterwards the slot holds no whole pyramids (have_pyr, have_coarse false).
-int enqueue_foveated_multi(ugsm_ctx *ctx, Slot &s, int si, const uint8_t *d_rgbL, const uint8_t *d_rgbR, int W, int H, int stride, int n,
-                           const int *off_x, const int *off_y, float *state, float *const *d_stack)
+// ---- the foveated call ------------------------------------------------------------------------------------------------------------------
+// A call runs checked -- both directions in lockstep, the stacks checked against their right-to-left twins -- with the threshold it brings, and a
+// call of pairs under the context's own setting (ugsm_set_lr_check) too.
+static float checked_tau(const ugsm_ctx *ctx, const FoveaCall &call)
 {
-    const int F = ctx->cfg.fovea_levels;
-    FoveaWin win;
-    UCHK(fovea_windows(ctx, W, H, n, off_x, off_y, win));
-    win.later = true;
-    UCHK(enqueue_pyramids(ctx, s, si, d_rgbL, d_rgbR, W, H, stride, F - 1, &win));
-    UCHK(enqueue_level0_windows(ctx, s, si, d_rgbL, d_rgbR, stride, n, win));
-    int st = enqueue_fovea_coarse(ctx, s, si, state);
-    if (st == UGSM_OK) {
-        if (n == 1 || ctx->cfg.kernel_path == 1 || ctx->cfg.early_exit_threshold > 0.0f) {
-            for (int k = 0; k < n && st == UGSM_OK; k++) st = enqueue_fovea_fine(ctx, s, si, state, off_x[k], off_y[k], d_stack[k], nullptr, nullptr);
-        } else {
-            const Shape sh = Shape::windows(n, field_room((size_t)win.w * win.h));
-            if (sh.nb * sh.stride > s.lvl_cap) {
-                ctx->err = "the level buffers do not hold the windows' fields";
-                return UGSM_ERR_STATE;
-            }
-            UCHK(spread_range_word(ctx, s, n));
-            const float *vstate[kMaxBatch];
-            for (int k = 0; k < n; k++) vstate[k] = state;
-            st = enqueue_fovea_fine(ctx, s, si, sh, vstate, off_x, off_y, d_stack, nullptr, nullptr);
-        }
-    }
-    s.have_pyr = false;
-    s.have_coarse = false;
-    return st;
+    return call.tau > 0.0f ? call.tau : (call.kind == FoveaCall::Pairs && lr_fovea_on(ctx)) ? ctx->lr_tau : 0.0f;
 }
 
-// ugsm_submit_foveated_multi_checked: n windows of one pair, both directions in lockstep, the n stacks checked against their right-to-left twins.
-// enqueue_foveated_multi and the checked enqueue_match_foveated composed:
-//   - one pair's pyramids with no level 0 and the one k_level0_windows launch, as the plain multi call (no A planes from the side stream: the
-//     coarse phase runs on two entries and computes A in line, as every batch does).  The right-to-left direction reads the same two
-//     pyramids, so nothing more is stored;
-//   - pair 0's range word into the entries 1 .. 2 n - 1;
-//   - the coarse phase once for the two directions (Shape::coarse_both_directions: entry 1 = pair 0 exchanged, pair_pyr), level F-1's two
-//     fields into `state` and into the LR buffer;
-//   - the fine phase on Shape::windows_both_directions: entry k is window k left-to-right from the first state, entry n + k window k
-//     right-to-left from the second, its stack in the LR buffer.  K-cost runs one launch per direction and level (cost_groups); more than
-//     kMaxBatch entries go through launches of equal size (group_pairs);
-//   - one launch of k_lr_check's stack form over the n (window, level) entries with the call's own tau (enqueue_lr_stack_check).
-// The caller has made the level buffers hold 2 n fovea fields and the LR buffer lr_room(.., true).total floats.
-int enqueue_foveated_multi_checked(ugsm_ctx *ctx, Slot &s, int si, const uint8_t *d_rgbL, const uint8_t *d_rgbR, int W, int H, int stride, int n,
-                                   const int *off_x, const int *off_y, float *state, float *const *d_stack, float tau)
+// The sizes of a foveated call of the context on W x H images, and the states of n pairs / n windows of one pair at the front of hout.
+int fovea_room(const ugsm_ctx *ctx, int W, int H, FoveaCall::Kind kind, int n, FoveaRoom &room)
 {
     const int F = ctx->cfg.fovea_levels;
+    room = FoveaRoom{};
+    UCHK(ugsm_fovea_dims(W, H, ctx->cfg.levels, F, &room.fw, &room.fh));
+    room.px = (size_t)room.fw * room.fh;
+    room.field = field_room(room.px);
+    room.plane = (size_t)F * room.px;
+    room.stack = 3 * room.plane;
+    room.total = (kind == FoveaCall::Pairs ? n : kind == FoveaCall::Windows ? 1 : 0) * room.field;
+    return UGSM_OK;
+}
+
+// Everything the call needs beyond its pairs' own buffers (prepare_slot), grown before anything is enqueued: a refused call has enqueued nothing.
+//   - the level buffers for the windows of one pair, whose fields run in lockstep at a stride of one fovea field: n of them (2 n checked) exceed the
+//     one pair's 3 W H floats as soon as n > 2^(F-1).  Never less than 3 W H, so that prepare_slot need not grow them again.  (Both directions of n
+//     PAIRS fit into what prepare_slot gives n pairs -- fovW fovH <= W H / 2 for every F >= 2, for F = 2 just --: enqueue_foveated sees to the
+//     rounding behind the pyramids, where the slot has its size);
+//   - a checked call's LR buffer (lr_room) and the page-locked words its counts come back in.  What does NOT fit into the level buffers for F = 2 is
+//     the right-to-left STACK, which has to outlive the fine levels: it goes there, with the right-to-left state -- 3 (F + 1) fovW fovH floats per
+//     pair, 24 MB at 16 MP beside the pair's 1.35 GB, counted by ugsm_context_device_bytes;
+//   - hout, for the states and what the entry point has asked for behind them.
+int fovea_grow(ugsm_ctx *ctx, Slot &s, int W, int H, const FoveaCall &call, const FoveaRoom &room)
+{
+    const bool windows = call.kind == FoveaCall::Windows, checked = checked_tau(ctx, call) > 0.0f;
+    if (windows && (checked || !fovea_windows_run_one_by_one(ctx, call.n)))
+        UCHK(ensure_level_bufs(ctx, s, std::max((checked ? 2 : 1) * call.n * room.field, 3 * (size_t)W * H)));
+    if (checked) {
+        UCHK(grow(ctx, s.lr, s.lr_cap, lr_room(call.n, ctx->cfg.fovea_levels, room.fw, room.fh, windows).total));
+        UCHK(lr_host_ready(ctx, s));
+    }
+    return grow(ctx, s.hout, s.hout_cap, room.total);
+}
+
+// One foveated call on device buffers, every kind of it (FoveaCall; d_rgbL / d_rgbR: the n pairs' images, or the one pair's).  The steps are the
+// same for all; what differs is data -- kind: A planes from the side stream | level 0 | coarse phase on | fine phase on | range word | level-F-1 states:
+//   pairs:            F-1 .. top if n == 1 (a batch computes A in line) | k_pyr_base, inside the windows | Shape::pairs | Shape::pairs | -- | n
+//   pairs, checked:   none | same | Shape::both_directions | the same shape | words 0 .. n-1 copied to n .. 2n-1 | n, and n behind the twins' stacks in the LR buffer
+//   windows:          F-1 .. top | none from k_pyr_base (FoveaWin::later), then one k_level0_windows launch | one pair | Shape::windows in lockstep, or window
+//                     by window (fovea_windows_run_one_by_one) | word 0 doubled out to n entries | 1
+//   windows, checked: none | as windows | Shape::coarse_both_directions | Shape::windows_both_directions | word 0 doubled out to 2n | 1, and 1 behind the last twin stack
+//   warm:             none; the pyramids stop at max(start, 2) | inside the windows | not run: one k_restrict_stack launch | Shape::pairs, from level `start` | -- | none
+//   - an exchanged entry (n + b of a checked call) reads its pair's pyramids with the L and R views exchanged (pair_pyr), through entry b's windows
+//     and seed maps, under its pair's range word (it covers both images' pyramids: build_pyramids reports either image into range_bad[pair]), so
+//     nothing more is stored for the second direction.  Every kernel of a level takes the entries in one launch except K-cost, which takes each
+//     direction in one (run_level); more than kMaxBatch entries go through launches of equal size (group_pairs);
+//   - the windows of one pair share what does not depend on the window: the pyramids, the coarse phase and its state.  Pyramids that k_pyr_base does
+//     not build (fewer than three levels, kernel_path 1) hold level 0 whole and skip the k_level0_windows launch;
+//   - a warm call (its refusals: ugsm_fovea_seeded.cpp) computes A in line at every level, level F-1 included, where it is matched: the side stream's
+//     A planes serve the coarse phase.  The one launch writes level `start`'s fields into the level buffer the fine phase starts in, the levels
+//     above into the stacks' row blocks;
+// Afterwards the slot holds no whole pyramids (have_pyr false: every foveated call builds them through its windows).
+int enqueue_foveated(ugsm_ctx *ctx, Slot &s, int si, const uint8_t *const *d_rgbL, const uint8_t *const *d_rgbR, int W, int H, int stride, const FoveaCall &call)
+{
+    const int F = ctx->cfg.fovea_levels, n = call.n;
+    const bool windows = call.kind == FoveaCall::Windows, warm = call.kind == FoveaCall::Warm;
+    const float tau = checked_tau(ctx, call);
+    const bool checked = tau > 0.0f;
     FoveaWin win;
-    UCHK(fovea_windows(ctx, W, H, n, off_x, off_y, win));
-    win.later = true;
-    UCHK(enqueue_pyramids(ctx, s, si, d_rgbL, d_rgbR, W, H, stride, -1, &win));
-    UCHK(enqueue_level0_windows(ctx, s, si, d_rgbL, d_rgbR, stride, n, win));
-    const size_t field = field_room((size_t)win.w * win.h);
-    const Shape sh = Shape::windows_both_directions(n, field);
-    const LrRoom room = lr_room(n, F, win.w, win.h, true);
-    if (sh.nb * sh.stride > s.lvl_cap || room.total > s.lr_cap || !s.lr_host) {
-        ctx->err = "the slot's buffers do not hold the checked windows' fields";
-        return UGSM_ERR_STATE;
+    UCHK(fovea_windows(ctx, W, H, n, call.off_x, call.off_y, win));
+    win.later = windows;
+    FoveaRoom room;
+    UCHK(fovea_room(ctx, W, H, call.kind, n, room));
+    UCHK(fovea_grow(ctx, s, W, H, call, room));
+
+    const bool side_A = !checked && !warm && (windows || n == 1);
+    UCHK(enqueue_pyramids(ctx, s, si, d_rgbL, d_rgbR, windows ? 1 : n, W, H, stride, side_A ? F - 1 : -1, &win, false, 0, warm ? call.start : -1));
+    if (windows) UCHK(enqueue_level0_windows(ctx, s, si, d_rgbL[0], d_rgbR[0], stride, n, win));
+
+    // what runs in lockstep: the real pairs, unless the call is checked or its windows run together
+    const bool one_by_one = windows && !checked && fovea_windows_run_one_by_one(ctx, n);
+    const Shape real = Shape::pairs(s);
+    Shape coarse = real, fine = real;
+    if (checked && !windows) coarse = fine = Shape::both_directions(n, room.field);
+    if (checked && windows) { coarse = Shape::coarse_both_directions(room.field); fine = Shape::windows_both_directions(n, room.field); }
+    if (!checked && windows && !one_by_one) fine = Shape::windows(n, room.field);
+    // The slot has its size now, and prepare_slot may have given the level buffers back and sized them for this call's pairs alone (the
+    // configured batch did not fit): checked pairs grow them to their 2 n fields where the rounding asks for it, the windows' fields are refused
+    const LrRoom lr = lr_room(n, F, room.fw, room.fh, windows);
+    if (checked && !windows) UCHK(ensure_level_bufs(ctx, s, fine.nb * fine.stride));
+    if (windows && !one_by_one && (fine.nb * fine.stride > s.lvl_cap || (checked && (lr.total > s.lr_cap || !s.lr_host))))
+        return ctx_fail(ctx, UGSM_ERR_STATE, checked ? "the slot's buffers do not hold the checked windows' fields" : "the level buffers do not hold the windows' fields");
+    // the range words of the real pairs (the one pair of n windows) out to the entries that run under them, doubling what is already there
+    for (int c = windows ? 1 : n; s.range_known && c < fine.nb; c *= 2)
+        HIPCHK(ctx, hipMemcpyAsync(s.range_bad + c, s.range_bad, sizeof(unsigned) * std::min(c, fine.nb - c), hipMemcpyDeviceToDevice, s.st));
+
+    // entry b's state and stack, and its twin's (entry n + b) in the LR buffer: n pairs keep a state each, n windows share one
+    float *state[2 * kMaxBatch] = {}, *stack[2 * kMaxBatch] = {};
+    for (int b = 0; b < n; b++) {
+        if (!warm) state[b] = s.hout + (windows ? 0 : b * room.field);
+        stack[b] = call.d_stack[b];
+        if (!checked) continue;
+        stack[n + b] = s.lr + b * lr.per;
+        state[n + b] = s.lr + lr.state + (windows ? 0 : b * lr.per);
     }
-    UCHK(spread_range_word(ctx, s, 2 * n));
-    float *vstate[2 * kMaxBatch], *vstack[2 * kMaxBatch];
-    for (int k = 0; k < n; k++) {
-        vstate[k] = state;
-        vstate[n + k] = s.lr + room.state;
-        vstack[k] = d_stack[k];
-        vstack[n + k] = s.lr + (size_t)k * room.per;
+    if (warm) {
+        UCHK(enqueue_restrict_stack(ctx, s, si, n, s.w, s.h, F, call.d_prior, call.prior_off_x, call.prior_off_y, call.field, call.off_x, call.off_y,
+                                    call.start, call.d_stack, s.d0, real.stride));
+    } else {
+        float *const both[2] = {state[0], state[n]};  // (the windows' coarse phase: the one pair, and its twin)
+        UCHK(enqueue_fovea_coarse(ctx, s, si, coarse, windows ? both : state));
     }
-    float *const cstate[2] = {state, s.lr + room.state};
-    s.have_pyr = false;
-    UCHK(enqueue_fovea_coarse(ctx, s, si, Shape::coarse_both_directions(field), cstate));
-    UCHK(enqueue_fovea_fine(ctx, s, si, sh, vstate, off_x, off_y, vstack, nullptr, nullptr));
-    return enqueue_lr_stack_check(ctx, s, si, n, F, win.w, win.h, tau, d_stack, room.per, reinterpret_cast<unsigned long long *>(s.lr + room.cnt));
+    // (windows that run one by one: `fine` is the one real pair, window k after window k - 1 from the one state)
+    for (int k = 0; k < (one_by_one ? n : 1); k++)
+        UCHK(enqueue_fovea_fine(ctx, s, si, fine, warm ? nullptr : state, call.off_x + k, call.off_y + k, stack + k, call.d_pyrL, call.d_pyrR, warm ? call.start : -1));
+    if (!checked) return UGSM_OK;
+    return enqueue_lr_stack_check(ctx, s, si, n, F, room.fw, room.fh, tau, call.d_stack, lr.per, reinterpret_cast<unsigned long long *>(s.lr + lr.cnt));
+}
+
+int fovea_warm_submit(ugsm_ctx *ctx, int slot, int n, const uint8_t *const *d_rgbL, const uint8_t *const *d_rgbR, int W, int H, int stride, const int *off_x,
+                      const int *off_y, const float *const *d_prior, const int *prior_off_x, const int *prior_off_y, int field, int start_level,
+                      float *const *d_stack)
+{
+    const FoveaCall call = FoveaCall::warm(n, off_x, off_y, d_prior, prior_off_x, prior_off_y, field != 0, start_level, d_stack);
+    const int per = (n == 1 || fovea_batch_runs_pair_by_pair(ctx)) ? 1 : n;  // (kernel_path 1: the pairs one after the other, as ugsm_submit_foveated_batch)
+    return submit_pairs(ctx, slot, n, per, [&](Slot &s, int b, int k) { return enqueue_foveated(ctx, s, slot, d_rgbL + b, d_rgbR + b, W, H, stride, call.sub(b, k)); });
 }
 
 // ---- n windows on one pair ----------------------------------------------------------------------------------------------------
-// What ugsm_submit_foveated_multi and ugsm_match_foveated_multi refuse before anything is enqueued; the windows' field size on success.
+// What ugsm_submit_foveated_multi and ugsm_match_foveated_multi refuse before anything is enqueued.
 // tau: null = the plain call; else the checked call's threshold (ugsm_submit_foveated_multi_checked), which has refusals of its own and does
 // not look at the context's setting.
-int multi_check(ugsm_ctx *ctx, int n, int W, int H, int stride, const int *&off_x, const int *&off_y, const int *zeros, int *fw, int *fh,
-                const float *tau)
+int multi_check(ugsm_ctx *ctx, int n, int W, int H, int stride, const float *tau)
 {
     const int F = ctx->cfg.fovea_levels;
     if (n < 1 || n > UGSM_MAX_BATCH || F < 2) return UGSM_ERR_BAD_ARG;
-    if (!off_x) off_x = zeros;
-    if (!off_y) off_y = zeros;
     if (tau && !(*tau > 0.0f)) return ctx_fail(ctx, UGSM_ERR_BAD_ARG, "the checked multi-window call needs tau > 0");
     // (ugsm_set_lr_check's rule: these contexts run every level pair by pair and have no batch dimension to carry the second direction in)
     if (tau && (ctx->cfg.early_exit_threshold > 0.0f || ctx->cfg.kernel_path == 1))
         return ctx_fail(ctx, UGSM_ERR_BAD_ARG, "the checked multi-window call: not with early_exit_threshold > 0 or kernel_path 1");
     if (!tau && lr_fovea_on(ctx)) return ctx_fail(ctx, UGSM_ERR_STATE, "the foveated LR check is on: the checked multi-window call is ugsm_submit_foveated_multi_checked (ugsm_set_lr_check)");
-    UCHK(ugsm_fovea_dims(W, H, ctx->cfg.levels, F, fw, fh));
+    int fw, fh;
+    UCHK(ugsm_fovea_dims(W, H, ctx->cfg.levels, F, &fw, &fh));
     UCHK(input_status(ctx, W, stride));
     return UGSM_OK;
-}
-// the level buffers for n fields of fw x fh in lockstep (contexts that run window by window need one pair's alone)
-int multi_level_bufs(ugsm_ctx *ctx, Slot &s, int n, int W, int H, int fw, int fh)
-{
-    if (n == 1 || ctx->cfg.kernel_path == 1 || ctx->cfg.early_exit_threshold > 0.0f) return UGSM_OK;
-    return ensure_level_bufs(ctx, s, std::max((size_t)n * field_room((size_t)fw * fh), 3 * (size_t)W * H));
-}
-
-// ... and of the checked call: 2 n fields in the level buffers, the right-to-left stacks, state and count words in the LR buffer
-int multi_checked_bufs(ugsm_ctx *ctx, Slot &s, int n, int W, int H, int fw, int fh)
-{
-    UCHK(ensure_level_bufs(ctx, s, std::max(2 * (size_t)n * field_room((size_t)fw * fh), 3 * (size_t)W * H)));
-    UCHK(grow(ctx, s.lr, s.lr_cap, lr_room(n, ctx->cfg.fovea_levels, fw, fh, true).total));
-    return lr_host_ready(ctx, s);
 }
 
 }  // namespace ugsm
@@ -492,15 +439,8 @@ int ugsm_submit_foveated(ugsm_ctx *ctx, int slot, const uint8_t *d_rgbL, const u
     UCHK(get_slot(ctx, slot, &s));
     if (!d_stack) return UGSM_ERR_BAD_ARG;
     HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
-    const int F = ctx->cfg.fovea_levels;
-    if (F < 2) return UGSM_ERR_BAD_ARG;
-    // level F-1's state is staged in the slot's hout
-    int fw, fh;
-    UCHK(ugsm_fovea_dims(W, H, ctx->cfg.levels, F, &fw, &fh));
-    const size_t fn3 = 3 * (size_t)fw * fh;
-    UCHK(grow(ctx, s->hout, s->hout_cap, std::max(fn3, s->hout_cap)));
-    UCHK(enqueue_match_foveated(ctx, *s, slot, 1, &d_rgbL, &d_rgbR, W, H, stride, &off_x, &off_y, &s->hout, &d_stack, d_pyrL ? &d_pyrL : nullptr,
-                          d_pyrR ? &d_pyrR : nullptr));
+    if (ctx->cfg.fovea_levels < 2) return UGSM_ERR_BAD_ARG;
+    UCHK(enqueue_foveated(ctx, *s, slot, &d_rgbL, &d_rgbR, W, H, stride, FoveaCall::pairs(1, &off_x, &off_y, &d_stack, &d_pyrL, &d_pyrR)));
     return mark_done(ctx, *s);
 }
 
@@ -512,24 +452,14 @@ int ugsm_submit_foveated_batch(ugsm_ctx *ctx, int slot, int n, const uint8_t *co
     if (n < 1 || n > UGSM_MAX_BATCH || !d_rgbL || !d_rgbR || !d_stack) return UGSM_ERR_BAD_ARG;
     for (int b = 0; b < n; b++)
         if (!d_rgbL[b] || !d_rgbR[b] || !d_stack[b]) return UGSM_ERR_BAD_ARG;
-    const int F = ctx->cfg.fovea_levels;
-    if (F < 2) return UGSM_ERR_BAD_ARG;
+    if (ctx->cfg.fovea_levels < 2) return UGSM_ERR_BAD_ARG;
     HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
-    int zeros[UGSM_MAX_BATCH] = {0};
-    const int *ox = off_x ? off_x : zeros, *oy = off_y ? off_y : zeros;
-    int fw, fh;
-    UCHK(ugsm_fovea_dims(W, H, ctx->cfg.levels, F, &fw, &fh));
-    const size_t fn3 = field_room((size_t)fw * fh);  // level F-1's state of every pair, staged in the slot's hout
-    UCHK(grow(ctx, s->hout, s->hout_cap, std::max(fn3 * n, s->hout_cap)));
-    if (n == 1 || fovea_batch_runs_pair_by_pair(ctx)) {
-        for (int b = 0; b < n; b++)
-            UCHK(enqueue_match_foveated(ctx, *s, slot, 1, d_rgbL + b, d_rgbR + b, W, H, stride, ox + b, oy + b, &s->hout, d_stack + b,
-                                  (d_pyrL && d_pyrL[b]) ? d_pyrL + b : nullptr, (d_pyrR && d_pyrR[b]) ? d_pyrR + b : nullptr));
-        return mark_done(ctx, *s);
-    }
-    float *state[UGSM_MAX_BATCH];
-    for (int b = 0; b < n; b++) state[b] = s->hout + b * fn3;
-    UCHK(enqueue_match_foveated(ctx, *s, slot, n, d_rgbL, d_rgbR, W, H, stride, ox, oy, state, d_stack, d_pyrL, d_pyrR));
+    const FoveaCall call = FoveaCall::pairs(n, off_x, off_y, d_stack, d_pyrL, d_pyrR);
+    FoveaRoom room;
+    UCHK(fovea_room(ctx, W, H, call.kind, n, room));
+    UCHK(fovea_grow(ctx, *s, W, H, call, room));  // (the whole call's, whichever way it runs)
+    const int per = (n == 1 || fovea_batch_runs_pair_by_pair(ctx)) ? 1 : n;
+    for (int b = 0; b < n; b += per) UCHK(enqueue_foveated(ctx, *s, slot, d_rgbL + b, d_rgbR + b, W, H, stride, call.sub(b, per)));
     return mark_done(ctx, *s);
 }
 
@@ -542,15 +472,10 @@ static int submit_foveated_multi(ugsm_ctx *ctx, int slot, const uint8_t *d_rgbL,
     if (!d_rgbL || !d_rgbR || !d_stack) return UGSM_ERR_BAD_ARG;
     for (int k = 0; k < n && k < UGSM_MAX_BATCH; k++)
         if (!d_stack[k]) return UGSM_ERR_BAD_ARG;
-    const int zeros[UGSM_MAX_BATCH] = {0};
-    int fw, fh;
-    UCHK(multi_check(ctx, n, W, H, stride, off_x, off_y, zeros, &fw, &fh, tau));
+    UCHK(multi_check(ctx, n, W, H, stride, tau));
     HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
-    UCHK(tau ? multi_checked_bufs(ctx, *s, n, W, H, fw, fh) : multi_level_bufs(ctx, *s, n, W, H, fw, fh));
-    const size_t fn3 = 3 * (size_t)fw * fh;  // the (left-to-right) level-F-1 state, staged in the slot's hout as ugsm_submit_foveated stages it
-    UCHK(grow(ctx, s->hout, s->hout_cap, std::max(fn3, s->hout_cap)));
-    if (tau) UCHK(enqueue_foveated_multi_checked(ctx, *s, slot, d_rgbL, d_rgbR, W, H, stride, n, off_x, off_y, s->hout, d_stack, *tau));
-    else UCHK(enqueue_foveated_multi(ctx, *s, slot, d_rgbL, d_rgbR, W, H, stride, n, off_x, off_y, s->hout, d_stack));
+    const FoveaCall call = FoveaCall::windows(n, off_x, off_y, d_stack);
+    UCHK(enqueue_foveated(ctx, *s, slot, &d_rgbL, &d_rgbR, W, H, stride, tau ? call.checked(*tau) : call));
     return mark_done(ctx, *s);
 }
 

@@ -268,7 +268,6 @@ int enqueue_fovea_coarse(ugsm_ctx *ctx, Slot &s, int si, const Shape &sh, float 
             launch_copy_view(s.st, Img3{cur + g.b0 * sh.stride, s.w[F - 1], fn}, s.w[F - 1], s.h[F - 1], d_state[g.b0], fn, s.w[F - 1], &bt);
         });
     }
-    s.have_coarse = sh.nb == 1;
     return UGSM_OK;
 }
 

@@ -362,22 +362,22 @@ int fine_match(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int W, i
 }
 
 // The warm foveated service call (ugsm_match_foveated_warm) on slot 0: images and the prior stack's three planes up, the match into a second
-// stack beside it in the slot's result staging (the call is not in place: [prior 3 stackn][stack 3 stackn]), that stack's planes down.
+// stack beside it in the slot's result staging (the call is not in place: [prior stack][stack]), that stack's planes down.
 int fovea_warm_match(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, int off_x, int off_y, const float *const prior[3],
                      int prior_off_x, int prior_off_y, int start_level, float *const stack[3])
 {
-    int fw, fh;
-    UCHK(ugsm_fovea_dims(W, H, ctx->cfg.levels, ctx->cfg.fovea_levels, &fw, &fh));
-    const size_t stackn = (size_t)ctx->cfg.fovea_levels * fw * fh;
+    FoveaRoom room;
+    UCHK(fovea_room(ctx, W, H, FoveaCall::Warm, 1, room));
+    const size_t at_prior = room.part(room.stack), at_stack = room.part(room.stack);
     auto match = [&](Slot &s) -> int {
-        UCHK(upload_planes(ctx, s, s.hout, stackn, prior));
-        const float *const d_prior = s.hout;
-        float *const d_stack = s.hout + 3 * stackn;
-        return enqueue_match_foveated_warm(ctx, s, 0, 1, &s.rgbL, &s.rgbR, W, H, stride, &off_x, &off_y, &d_prior, &prior_off_x, &prior_off_y, false,
-                                           start_level, &d_stack);
+        UCHK(upload_planes(ctx, s, s.hout + at_prior, room.plane, prior));
+        const float *const d_prior = s.hout + at_prior;
+        float *const d_stack = s.hout + at_stack;
+        return enqueue_foveated(ctx, s, 0, &s.rgbL, &s.rgbR, W, H, stride,
+                                FoveaCall::warm(1, &off_x, &off_y, &d_prior, &prior_off_x, &prior_off_y, false, start_level, &d_stack));
     };
-    return host_call(ctx, rgbL, rgbR, W, H, stride, 6 * stackn, match,
-                     [&](Slot &s) -> int { return download_stack(ctx, s, s.hout + 3 * stackn, stackn, stack[0], stack[1], stack[2]); });
+    return host_call(ctx, rgbL, rgbR, W, H, stride, room.total, match,
+                     [&](Slot &s) -> int { return download_stack(ctx, s, s.hout + at_stack, room.plane, stack[0], stack[1], stack[2]); });
 }
 
 void ctx_host_copy(ugsm_ctx *ctx, void *dst, const void *src, size_t bytes) { team_copy(ctx, dst, src, bytes); }
@@ -445,38 +445,36 @@ int ugsm_match_full_checked(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *r
     });
 }
 
-// One foveated pair from host memory.  The slot's result staging: [state 3*fn][stack 3*stackn][pyrL 3*stackn][pyrR 3*stackn], the pyramid
-// stacks where they are asked for.
+// One foveated pair from host memory.  Behind the state in the slot's result staging: [stack][pyrL][pyrR], the pyramid stacks where they are
+// asked for.
 static int match_foveated_host(ugsm_ctx *ctx, int slot, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, int off_x, int off_y,
                                float *stackH, float *stackV, float *stackC, float *pyrL, float *pyrR, bool sync)
 {
-    const int F = ctx ? ctx->cfg.fovea_levels : 0;
-    size_t fn = 0, stackn = 0;
+    FoveaRoom room;
+    size_t at_stack = 0, at_pl = 0, at_pr = 0;
     float *d_stack = nullptr, *d_pl = nullptr, *d_pr = nullptr;
     auto check = [&](Slot &, size_t &hout) -> int {
-        if (!stackH || !stackV || !stackC || F < 2) return UGSM_ERR_BAD_ARG;
+        if (!stackH || !stackV || !stackC || ctx->cfg.fovea_levels < 2) return UGSM_ERR_BAD_ARG;
         if (!sync && !(is_pinned(rgbL) && is_pinned(rgbR) && is_pinned(stackH) && is_pinned(stackV) && is_pinned(stackC) && (!pyrL || is_pinned(pyrL)) &&
                        (!pyrR || is_pinned(pyrR))))
             return not_pinned(ctx, "ugsm_submit_foveated_host");
-        int fw, fh;
-        UCHK(ugsm_fovea_dims(W, H, ctx->cfg.levels, F, &fw, &fh));
-        fn = (size_t)fw * fh;
-        stackn = (size_t)F * fn;
-        hout = 3 * fn + 3 * stackn + (pyrL ? 3 * stackn : 0) + (pyrR ? 3 * stackn : 0);
+        UCHK(fovea_room(ctx, W, H, FoveaCall::Pairs, 1, room));
+        at_stack = room.part(room.stack);
+        if (pyrL) at_pl = room.part(room.stack);
+        if (pyrR) at_pr = room.part(room.stack);
+        hout = room.total;
         return UGSM_OK;
     };
     auto match = [&](Slot &s) -> int {
-        float *d_state = s.hout;
-        d_stack = d_state + 3 * fn;
-        d_pl = pyrL ? d_stack + 3 * stackn : nullptr;
-        d_pr = pyrR ? d_stack + 3 * stackn + (pyrL ? 3 * stackn : 0) : nullptr;
-        return enqueue_match_foveated(ctx, s, slot, 1, &s.rgbL, &s.rgbR, W, H, stride, &off_x, &off_y, &d_state, &d_stack, d_pl ? &d_pl : nullptr,
-                                      d_pr ? &d_pr : nullptr);
+        d_stack = s.hout + at_stack;
+        d_pl = pyrL ? s.hout + at_pl : nullptr;
+        d_pr = pyrR ? s.hout + at_pr : nullptr;
+        return enqueue_foveated(ctx, s, slot, &s.rgbL, &s.rgbR, W, H, stride, FoveaCall::pairs(1, &off_x, &off_y, &d_stack, &d_pl, &d_pr));
     };
     return host_call(ctx, slot, sync, rgbL, rgbR, W, H, stride, check, match, [&](Slot &s) -> int {
-        UCHK(download_stack(ctx, s, d_stack, stackn, stackH, stackV, stackC));
-        if (pyrL) HIPCHK(ctx, hipMemcpyAsync(pyrL, d_pl, 3 * stackn * sizeof(float), hipMemcpyDeviceToHost, s.st));
-        if (pyrR) HIPCHK(ctx, hipMemcpyAsync(pyrR, d_pr, 3 * stackn * sizeof(float), hipMemcpyDeviceToHost, s.st));
+        UCHK(download_stack(ctx, s, d_stack, room.plane, stackH, stackV, stackC));
+        if (pyrL) HIPCHK(ctx, hipMemcpyAsync(pyrL, d_pl, room.stack * sizeof(float), hipMemcpyDeviceToHost, s.st));
+        if (pyrR) HIPCHK(ctx, hipMemcpyAsync(pyrR, d_pr, room.stack * sizeof(float), hipMemcpyDeviceToHost, s.st));
         return UGSM_OK;
     });
 }
@@ -493,34 +491,29 @@ int ugsm_submit_foveated_host(ugsm_ctx *ctx, int slot, const uint8_t *rgbL, cons
     return match_foveated_host(ctx, slot, rgbL, rgbR, W, H, stride, off_x, off_y, stackH, stackV, stackC, pyrL, pyrR, false);
 }
 
-// n windows of one pair from host memory, on slot 0 (tau: null = the plain call, else the checked one's threshold).  The slot's result staging:
-// [state 3 fn][n stacks of 3 stackn]; the call's buffers, the staging included, grow before the images go up.
+// n windows of one pair from host memory, on slot 0 (tau: null = the plain call, else the checked one's threshold).  Behind the state in the
+// slot's result staging: the n stacks; the call's buffers, the staging included, grow before the images go up.
 static int match_foveated_multi_host(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, int n, const int *off_x,
                                      const int *off_y, float *const *stackH, float *const *stackV, float *const *stackC, const float *tau)
 {
-    const int zeros[UGSM_MAX_BATCH] = {0};
-    size_t stackn = 0;
+    FoveaRoom room;
     float *d_stack[UGSM_MAX_BATCH];
+    const FoveaCall plain = FoveaCall::windows(n, off_x, off_y, d_stack), call = tau ? plain.checked(*tau) : plain;
     auto check = [&](Slot &s, size_t &hout) -> int {
         if (!rgbL || !rgbR || !stackH || !stackV || !stackC) return UGSM_ERR_BAD_ARG;
         for (int k = 0; k < n && k < UGSM_MAX_BATCH; k++)
             if (!stackH[k] || !stackV[k] || !stackC[k]) return UGSM_ERR_BAD_ARG;
-        int fw, fh;
-        UCHK(multi_check(ctx, n, W, H, stride, off_x, off_y, zeros, &fw, &fh, tau));
-        UCHK(tau ? multi_checked_bufs(ctx, s, n, W, H, fw, fh) : multi_level_bufs(ctx, s, n, W, H, fw, fh));
-        const size_t fn = (size_t)fw * fh;
-        stackn = (size_t)ctx->cfg.fovea_levels * fn;
-        hout = 3 * fn + (size_t)n * 3 * stackn;
-        UCHK(grow(ctx, s.hout, s.hout_cap, hout));
-        for (int k = 0; k < n; k++) d_stack[k] = s.hout + 3 * fn + (size_t)k * 3 * stackn;
+        UCHK(multi_check(ctx, n, W, H, stride, tau));
+        UCHK(fovea_room(ctx, W, H, call.kind, n, room));
+        const size_t at_stacks = room.part(n * room.stack);
+        UCHK(fovea_grow(ctx, s, W, H, call, room));
+        for (int k = 0; k < n; k++) d_stack[k] = s.hout + at_stacks + k * room.stack;
+        hout = room.total;
         return UGSM_OK;
     };
-    auto match = [&](Slot &s) -> int {
-        return tau ? enqueue_foveated_multi_checked(ctx, s, 0, s.rgbL, s.rgbR, W, H, stride, n, off_x, off_y, s.hout, d_stack, *tau)
-                   : enqueue_foveated_multi(ctx, s, 0, s.rgbL, s.rgbR, W, H, stride, n, off_x, off_y, s.hout, d_stack);
-    };
+    auto match = [&](Slot &s) -> int { return enqueue_foveated(ctx, s, 0, &s.rgbL, &s.rgbR, W, H, stride, call); };
     return host_call(ctx, 0, true, rgbL, rgbR, W, H, stride, check, match, [&](Slot &s) -> int {
-        for (int k = 0; k < n; k++) UCHK(download_stack(ctx, s, d_stack[k], stackn, stackH[k], stackV[k], stackC[k]));
+        for (int k = 0; k < n; k++) UCHK(download_stack(ctx, s, d_stack[k], room.plane, stackH[k], stackV[k], stackC[k]));
         return UGSM_OK;
     });
 }
@@ -537,32 +530,31 @@ int ugsm_match_foveated_multi_checked(ugsm_ctx *ctx, const uint8_t *rgbL, const 
     return match_foveated_multi_host(ctx, rgbL, rgbR, W, H, stride, n, off_x, off_y, stackH, stackV, stackC, &tau);
 }
 
-// match(L, R, fov == 1), MatchGPULib.cpp:354-360: foveated matching, then hierarchicalDisparity on the stacks.  The slot's result staging:
-// [state][stack][full field]
+// match(L, R, fov == 1), MatchGPULib.cpp:354-360: foveated matching, then hierarchicalDisparity on the stacks.  Behind the state in the slot's
+// result staging: [stack][full field]
 int ugsm_match_foveated_full(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, int off_x, int off_y,
                              float *outH, float *outV, float *outC)
 {
     float *const dst[3] = {outH, outV, outC};
-    const int F = ctx ? ctx->cfg.fovea_levels : 0;
     const size_t n = (size_t)W * H;
-    size_t fn = 0, stackn = 0;
+    FoveaRoom room;
+    size_t at_stack = 0, at_full = 0;
     auto check = [&](Slot &, size_t &hout) -> int {
-        if (!outH || !outV || !outC || F < 2) return UGSM_ERR_BAD_ARG;
-        int fw, fh;
-        UCHK(ugsm_fovea_dims(W, H, ctx->cfg.levels, F, &fw, &fh));
-        fn = (size_t)fw * fh;
-        stackn = (size_t)F * fn;
-        hout = 3 * fn + 3 * stackn + 3 * n;
+        if (!outH || !outV || !outC || ctx->cfg.fovea_levels < 2) return UGSM_ERR_BAD_ARG;
+        UCHK(fovea_room(ctx, W, H, FoveaCall::Pairs, 1, room));
+        at_stack = room.part(room.stack);
+        at_full = room.part(3 * n);
+        hout = room.total;
         return UGSM_OK;
     };
     auto match = [&](Slot &s) -> int {
-        float *d_state = s.hout, *d_stack = d_state + 3 * fn;
-        UCHK(enqueue_match_foveated(ctx, s, 0, 1, &s.rgbL, &s.rgbR, W, H, stride, &off_x, &off_y, &d_state, &d_stack, nullptr, nullptr));
-        return ugsm_reconstruct_full(ctx, 0, d_stack, d_stack + stackn, d_stack + 2 * stackn, W, H, off_x, off_y, d_stack + 3 * stackn);
+        float *d_stack = s.hout + at_stack;
+        UCHK(enqueue_foveated(ctx, s, 0, &s.rgbL, &s.rgbR, W, H, stride, FoveaCall::pairs(1, &off_x, &off_y, &d_stack)));
+        return ugsm_reconstruct_full(ctx, 0, d_stack, d_stack + room.plane, d_stack + 2 * room.plane, W, H, off_x, off_y, s.hout + at_full);
     };
     return host_call(ctx, 0, true, rgbL, rgbR, W, H, stride, check, match, [&](Slot &s) -> int {
         prefault_planes(ctx, dst, n);
-        return copy_out_planes(ctx, s, s.hout + 3 * fn + 3 * stackn, n, dst);
+        return copy_out_planes(ctx, s, s.hout + at_full, n, dst);
     });
 }
 
@@ -685,27 +677,24 @@ int ugsm_submit_foveated_batch_host(ugsm_ctx *ctx, int slot, int n, const uint8_
     if (F < 2) return UGSM_ERR_BAD_ARG;
     HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
     UCHK(batch_pinned(ctx, "ugsm_submit_foveated_batch_host", n, rgbL, rgbR, stackH, stackV, stackC));
-    int zeros[UGSM_MAX_BATCH] = {0};
-    const int *ox = off_x ? off_x : zeros, *oy = off_y ? off_y : zeros;
+    float *stack[UGSM_MAX_BATCH];
+    const FoveaCall call = FoveaCall::pairs(n, off_x, off_y, stack);
     if (n == 1 || fovea_batch_runs_pair_by_pair(ctx)) {
         for (int b = 0; b < n; b++)
-            UCHK(match_foveated_host(ctx, slot, rgbL[b], rgbR[b], W, H, stride, ox[b], oy[b], stackH[b], stackV[b], stackC[b], nullptr, nullptr, false));
+            UCHK(match_foveated_host(ctx, slot, rgbL[b], rgbR[b], W, H, stride, call.off_x[b], call.off_y[b], stackH[b], stackV[b], stackC[b], nullptr,
+                                     nullptr, false));
         return UGSM_OK;
     }
-    int fw, fh;
-    UCHK(ugsm_fovea_dims(W, H, ctx->cfg.levels, F, &fw, &fh));
+    FoveaRoom room;
+    UCHK(fovea_room(ctx, W, H, call.kind, n, room));
     const uint8_t *dL[UGSM_MAX_BATCH], *dR[UGSM_MAX_BATCH];
     UCHK(stage_in_batch(ctx, *s, n, rgbL, rgbR, W, H, stride, dL, dR));
-    const size_t fn = (size_t)fw * fh, stackn = (size_t)F * fn;
-    const size_t st_per = field_room((size_t)fw * fh), sk_per = (3 * stackn + 63) & ~(size_t)63;  // hout: [states n x st_per][stacks n x sk_per]
-    UCHK(grow(ctx, s->hout, s->hout_cap, n * (st_per + sk_per)));
-    float *state[UGSM_MAX_BATCH], *stack[UGSM_MAX_BATCH];
-    for (int b = 0; b < n; b++) {
-        state[b] = s->hout + b * st_per;
-        stack[b] = s->hout + n * st_per + b * sk_per;
-    }
-    UCHK(enqueue_match_foveated(ctx, *s, slot, n, dL, dR, W, H, stride, ox, oy, state, stack, nullptr, nullptr));
-    for (int b = 0; b < n; b++) UCHK(download_stack(ctx, *s, stack[b], stackn, stackH[b], stackV[b], stackC[b]));
+    size_t at[UGSM_MAX_BATCH];  // (behind the states: the n stacks)
+    for (int b = 0; b < n; b++) at[b] = room.part(room.stack);
+    UCHK(fovea_grow(ctx, *s, W, H, call, room));
+    for (int b = 0; b < n; b++) stack[b] = s->hout + at[b];
+    UCHK(enqueue_foveated(ctx, *s, slot, dL, dR, W, H, stride, call));
+    for (int b = 0; b < n; b++) UCHK(download_stack(ctx, *s, stack[b], room.plane, stackH[b], stackV[b], stackC[b]));
     return mark_done(ctx, *s);
 }
 

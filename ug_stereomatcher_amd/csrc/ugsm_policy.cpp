@@ -173,9 +173,12 @@ bool lr_full_on(const ugsm_ctx *ctx) { return ctx->lr_tau > 0.0f && (ctx->lr_mod
 bool lr_fovea_on(const ugsm_ctx *ctx) { return ctx->lr_tau > 0.0f && (ctx->lr_modes & UGSM_LR_FOVEATED); }
 // Contexts whose options need a host round trip per iteration, a second match, or the one-kernel-per-stage path run their batches pair by pair.
 bool batch_runs_pair_by_pair(const ugsm_ctx *ctx) { return ctx->cfg.kernel_path == 1 || ctx->cfg.early_exit_threshold > 0.0f || lr_full_on(ctx); }
-// ... and the foveated batches: the foveated check runs in lockstep (enqueue_match_foveated; ugsm_set_lr_check refuses it to the contexts of the
+// ... and the foveated batches: the foveated check runs in lockstep (enqueue_foveated; ugsm_set_lr_check refuses it to the contexts of the
 // first two kinds).  A context with the full-mode check alone sends its foveated batches through pair by pair as it always has.
 bool fovea_batch_runs_pair_by_pair(const ugsm_ctx *ctx) { return batch_runs_pair_by_pair(ctx) && !lr_fovea_on(ctx); }
+// ... and the n windows of one pair (ugsm_submit_foveated_multi): their fine phase runs window after window, as single pairs, in the contexts of the
+// first two kinds; a lone window is a single pair.  (The checked form is refused to those contexts and runs a lone window in lockstep with its twin.)
+bool fovea_windows_run_one_by_one(const ugsm_ctx *ctx, int n) { return n == 1 || ctx->cfg.kernel_path == 1 || ctx->cfg.early_exit_threshold > 0.0f; }
 
 // ---- development overrides ---------------------------------------------------------------
 // tools/ and tests/ steer the per-level kernel choice through environment variables.  They are read ONLY when UGSM_DEV=1 is set

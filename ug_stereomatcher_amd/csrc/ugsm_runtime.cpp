@@ -212,21 +212,19 @@ int prepare_slot(ugsm_ctx *ctx, Slot &s, int W, int H, int nb)
     //   lr_ran        set by enqueue_full_lr and enqueue_full_checked behind their check;
     //   lr_full_pairs set by enqueue_full_checked alone and read only under lr_ran (ugsm_last_lr_marked, ugsm_last_lr_marked_pair): the calls that
     //                 used to leave it standing beside lr_ran == false left nothing that could be seen;
-    //   lr_fov_pairs  set by enqueue_lr_stack_check behind a checked foveated call's check;
-    //   have_coarse   set by enqueue_fovea_coarse alone, which runs after the pyramids (nothing reads it today).
+    //   lr_fov_pairs  set by enqueue_lr_stack_check behind a checked foveated call's check.
     // Every one of these setters runs after its call's prepare_slot, so nothing a call sets is undone here.  (ugsm_submit_pyramids and
     // ugsm_stage_pyramid, which set none, used to leave the LR words of the call before them standing: after them ugsm_last_lr_marked* now
     // answer what include/ugsm.h says of a last call that ran no check.)  Who does not come through here:
     //   ugsm_submit_fovea_coarse / _fine work on the pyramids of a ugsm_submit_pyramids and touch no LR word, as ever: they run no check
-    //   (include/ugsm.h), and ugsm_last_lr_marked* answer as after that ugsm_submit_pyramids; _coarse sets have_coarse;
-    //   ugsm_stage_iterate[_rgb8] bring planes of their own: they clear have_pyr and have_coarse themselves (a ugsm_submit_fovea_coarse may
-    //   have set it) and touch no LR word; the other ugsm_stage_* calls touch none of the four.
+    //   (include/ugsm.h), and ugsm_last_lr_marked* answer as after that ugsm_submit_pyramids;
+    //   ugsm_stage_iterate[_rgb8] bring planes of their own: they clear have_pyr themselves and touch no LR word; the other ugsm_stage_*
+    //   calls touch none of the three.
     // A call refused before its pyramids (a null image, a stride too small, a size with no pyramid) has enqueued nothing and leaves the slot
     // describing the call before it.
     s.lr_ran = false;
     s.lr_full_pairs = 0;
     s.lr_fov_pairs = 0;
-    s.have_coarse = false;
     const size_t lvl = 3 * (size_t)W * H;
     // (pairs of a batch start on 256-byte boundaries: the kernels' 16-byte accesses stay aligned whatever the level sizes add up to)
     s.pyr_stride = (tot + 63) & ~(size_t)63;

@@ -4,7 +4,7 @@
 //   ugsm_policy.cpp   which kernel and which stream a level gets; the development overrides; ugsm_plan_level
 //   ugsm_levels.cpp   the work of one level: pyramids, A, K-cost and K-smooth (run_level), the seed hand-over
 //   ugsm_full.cpp     the full-frame descent and the calls made of it (whole, checked, seeded, the two halves); a foveated call's coarse phase
-//   ugsm_fovea.cpp    the foveated calls: fine phase, checked, warm, several windows on one pair; hierarchicalDisparity
+//   ugsm_fovea.cpp    the foveated calls: one sequence for every kind of them (FoveaCall), its buffers (FoveaRoom); hierarchicalDisparity
 //   ugsm_host.cpp     everything that touches caller host memory: the host team, staging, the blocking service calls
 //   ugsm_stages.cpp   the stage-level entry points (tests only)
 //   ugsm_cloud.cpp    the clouds;  ugsm_warp.cpp  the warped right image and the photometric residual
@@ -151,7 +151,6 @@ struct Slot {
     bool direct0 = false;
     const uint8_t *img0L[kMaxBatch] = {}, *img0R[kMaxBatch] = {};
     int img0_stride = 0;
-    bool have_coarse = false;
     // The warm foveated call (ugsm_submit_foveated_warm) with more entries than travel in its launch's arguments: their rows in device memory
     // (kMaxBatch of them) and the page-locked copies they are uploaded from on the slot's stream, allocated by the first such call.  The call
     // does not wait for the stream, so kWarmRing copies take turns, each with an event behind its upload, as SlotCloud::mc_tab_h.
@@ -380,6 +379,96 @@ struct LevelRange {
     LevelRange(int f, int t, Start s, const float *const *src, float *const *fl) : from(f), to(t), start(s), source(src), full(fl) {}
 };
 
+// A foveated call, for enqueue_foveated (ugsm_fovea.cpp, where the table of what the kinds differ in is): n pairs with one window each, n windows
+// of one pair, or n pairs from a level of their priors.  Made by the makers alone, so a kind always comes with what belongs to it.  The makers take
+// null offset arrays (every window in the centre) and the call holds the offsets itself; the pointer arrays stay the caller's.
+struct FoveaCall {
+    enum Kind { Pairs, Windows, Warm };
+    Kind kind;
+    int n;
+    int off_x[kMaxBatch] = {}, off_y[kMaxBatch] = {};
+    float *const *d_stack;                                      // the n stacks the call writes
+    float *const *d_pyrL = nullptr, *const *d_pyrR = nullptr;   // Pairs: the pyramid stacks (null, or null entries: none)
+    float tau = 0.0f;                                           // > 0: checked().  (Pairs also run checked under the context's own setting, ugsm_set_lr_check)
+    const float *const *d_prior = nullptr;                      // Warm: the priors -- stacks with window offsets of their own, or full fields --
+    int prior_off_x[kMaxBatch] = {}, prior_off_y[kMaxBatch] = {};
+    bool field = false;
+    int start = -1;                                             // ... and the fovea level the call starts from
+    // ugsm_submit_foveated[_batch]: n pairs, one window each
+    static FoveaCall pairs(int n, const int *off_x, const int *off_y, float *const *d_stack, float *const *d_pyrL = nullptr, float *const *d_pyrR = nullptr)
+    {
+        return FoveaCall(Pairs, n, off_x, off_y, d_stack, d_pyrL, d_pyrR);
+    }
+    // ugsm_submit_foveated_multi: n windows of one pair
+    static FoveaCall windows(int n, const int *off_x, const int *off_y, float *const *d_stack) { return FoveaCall(Windows, n, off_x, off_y, d_stack); }
+    // ugsm_submit_foveated_warm[_field]: n pairs from level `start` of their priors
+    static FoveaCall warm(int n, const int *off_x, const int *off_y, const float *const *d_prior, const int *prior_off_x, const int *prior_off_y, bool field,
+                          int start, float *const *d_stack)
+    {
+        FoveaCall c(Warm, n, off_x, off_y, d_stack);
+        c.d_prior = d_prior;
+        c.hold(c.prior_off_x, prior_off_x);
+        c.hold(c.prior_off_y, prior_off_y);
+        c.field = field;
+        c.start = start;
+        return c;
+    }
+    // both directions in lockstep, the stacks checked against their right-to-left twins
+    FoveaCall checked(float t) const
+    {
+        FoveaCall c = *this;
+        c.tau = t;
+        return c;
+    }
+    // the pairs b .. b + k - 1 of a call of pairs as a call of their own (the contexts that run their batches pair by pair)
+    FoveaCall sub(int b, int k) const
+    {
+        FoveaCall c = *this;
+        c.n = k;
+        for (int j = 0; j < k; j++) {
+            c.off_x[j] = off_x[b + j];
+            c.off_y[j] = off_y[b + j];
+            c.prior_off_x[j] = prior_off_x[b + j];
+            c.prior_off_y[j] = prior_off_y[b + j];
+        }
+        c.d_stack = d_stack + b;
+        c.d_pyrL = d_pyrL ? d_pyrL + b : nullptr;
+        c.d_pyrR = d_pyrR ? d_pyrR + b : nullptr;
+        c.d_prior = d_prior ? d_prior + b : nullptr;
+        return c;
+    }
+
+  private:
+    FoveaCall(Kind k, int n_, const int *ox, const int *oy, float *const *stacks, float *const *pyrL = nullptr, float *const *pyrR = nullptr)
+        : kind(k), n(n_), d_stack(stacks), d_pyrL(pyrL), d_pyrR(pyrR)
+    {
+        hold(off_x, ox);
+        hold(off_y, oy);
+    }
+    // (an n out of range is the sequence's to refuse: nothing of the arrays is read)
+    void hold(int *mine, const int *given)
+    {
+        for (int b = 0; given && n >= 1 && n <= kMaxBatch && b < n; b++) mine[b] = given[b];
+    }
+};
+
+// The sizes of a foveated call, and the layout of the slot's result staging (Slot::hout) for it: [the call's level-F-1 states][what the entry
+// point asks for behind them], every part at a multiple of 64 floats.  The states are the runtime's own: enqueue_foveated takes them from the
+// front -- one per pair, one for the windows of one pair, none for a warm call.  An entry point that stages results there asks for its parts
+// (part), grows (fovea_grow, or host_call with `total`) and finds them at Slot::hout + what part() answered.
+struct FoveaRoom {
+    int fw = 0, fh = 0;
+    size_t px = 0, field = 0;  // the pixels of a field; its room (field_room)
+    size_t plane = 0, stack = 0;  // the floats of a stack plane (F fields' pixels) and of a stack (three of them)
+    size_t total = 0;  // floats of hout: the states, and the parts asked for so far
+    size_t part(size_t floats)
+    {
+        const size_t at = total;
+        total += (floats + 63) & ~(size_t)63;
+        return at;
+    }
+};
+
 // ---- ugsm_runtime.cpp: the context ---------------------------------------------------------------------------------------------------
 int level_dims(int W, int H, int levels, int *w, int *h);
 int level_iterations(int i);
@@ -455,6 +544,7 @@ bool lr_full_on(const ugsm_ctx *ctx);
 bool lr_fovea_on(const ugsm_ctx *ctx);
 bool batch_runs_pair_by_pair(const ugsm_ctx *ctx);
 bool fovea_batch_runs_pair_by_pair(const ugsm_ctx *ctx);
+bool fovea_windows_run_one_by_one(const ugsm_ctx *ctx, int n);
 
 // ---- ugsm_levels.cpp: the work of one level (the comments are with the definitions) --------------------------------------------------------
 Batch copy_batch(const Shape &sh, Grp g, const Img3 *views, float *const *dsts, size_t dst_off);
@@ -487,21 +577,12 @@ int full_checked_bufs(ugsm_ctx *ctx, Slot &s, int n, int kept, int W, int H);
 int enqueue_fovea_coarse(ugsm_ctx *ctx, Slot &s, int si, const Shape &sh, float *const *d_state);
 
 // ---- ugsm_fovea.cpp: the foveated calls ------------------------------------------------------------------------------------------------
-int enqueue_match_foveated(ugsm_ctx *ctx, Slot &s, int si, int n, const uint8_t *const *d_rgbL, const uint8_t *const *d_rgbR, int W, int H, int stride,
-                           const int *off_x, const int *off_y, float *const *state, float *const *d_stack, float *const *d_pyrL, float *const *d_pyrR);
-int enqueue_match_foveated_warm(ugsm_ctx *ctx, Slot &s, int si, int n, const uint8_t *const *d_rgbL, const uint8_t *const *d_rgbR, int W, int H, int stride,
-                                const int *off_x, const int *off_y, const float *const *d_prior, const int *poff_x, const int *poff_y, bool field, int start,
-                                float *const *d_stack);
+int enqueue_foveated(ugsm_ctx *ctx, Slot &s, int si, const uint8_t *const *d_rgbL, const uint8_t *const *d_rgbR, int W, int H, int stride, const FoveaCall &call);
+int fovea_room(const ugsm_ctx *ctx, int W, int H, FoveaCall::Kind kind, int n, FoveaRoom &room);
+int fovea_grow(ugsm_ctx *ctx, Slot &s, int W, int H, const FoveaCall &call, const FoveaRoom &room);
 int enqueue_restrict_stack(ugsm_ctx *ctx, Slot &s, int si, int n, const int *w, const int *h, int F, const float *const *prior, const int *poff_x,
                            const int *poff_y, bool field, const int *off_x, const int *off_y, int start, float *const *d_stack, float *work, size_t work_stride);
-int enqueue_foveated_multi(ugsm_ctx *ctx, Slot &s, int si, const uint8_t *d_rgbL, const uint8_t *d_rgbR, int W, int H, int stride, int n,
-                           const int *off_x, const int *off_y, float *state, float *const *d_stack);
-int enqueue_foveated_multi_checked(ugsm_ctx *ctx, Slot &s, int si, const uint8_t *d_rgbL, const uint8_t *d_rgbR, int W, int H, int stride, int n,
-                                   const int *off_x, const int *off_y, float *state, float *const *d_stack, float tau);
-int multi_check(ugsm_ctx *ctx, int n, int W, int H, int stride, const int *&off_x, const int *&off_y, const int *zeros, int *fw, int *fh,
-                const float *tau = nullptr);
-int multi_level_bufs(ugsm_ctx *ctx, Slot &s, int n, int W, int H, int fw, int fh);
-int multi_checked_bufs(ugsm_ctx *ctx, Slot &s, int n, int W, int H, int fw, int fh);
+int multi_check(ugsm_ctx *ctx, int n, int W, int H, int stride, const float *tau);
 
 // ---- ugsm_host.cpp: caller host memory ------------------------------------------------------------------------------------------------
 int stage_in(ugsm_ctx *ctx, Slot &s, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride);

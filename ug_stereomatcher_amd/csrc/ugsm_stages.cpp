@@ -44,7 +44,6 @@ int ugsm_stage_iterate(ugsm_ctx *ctx, const float *d_L3, const float *d_R3, floa
     // the planes arrive ready-made: check their range here (the pyramid kernels do it for the matcher proper).  The slot's range
     // word then describes THESE planes, no longer the slot's pyramids: a fovea phase submitted afterwards must rebuild them first
     s->have_pyr = false;
-    s->have_coarse = false;
     s->range_known = ctx->cfg.kernel_path != 1;
     if (s->range_known) {
         HIPCHK(ctx, hipMemsetAsync(s->range_bad, 0, sizeof(unsigned), s->st));
@@ -238,7 +237,6 @@ int ugsm_stage_iterate_rgb8(ugsm_ctx *ctx, const uint8_t *d_rgbL, const uint8_t 
     float *cur = s->d0, *other = s->d1;
     HIPCHK(ctx, hipMemcpyAsync(cur, d_d3, lvl * sizeof(float), hipMemcpyDeviceToDevice, s->st));
     s->have_pyr = false;
-    s->have_coarse = false;
     s->range_known = true;  // (the integers 0 .. 255: always inside range_ok)
     HIPCHK(ctx, hipMemsetAsync(s->range_bad, 0, sizeof(unsigned), s->st));
     s->nb = 1;
