@@ -257,6 +257,45 @@ def test_two_calls_back_to_back_alternating_two_stacks(lib, orc):
     assert_bit_equal(got2, f2, "the second of two chained calls, from the first's stack, the window moved")
 
 
+def test_nine_calls_of_three_pairs_back_to_back_take_turns_on_the_upload_ring(lib, orc):
+    """Three pairs are more than travel in the starting-field launch's arguments: their rows go up through the slot's table, from page-locked
+    copies that take turns.  Nine calls on one slot with no wait between them, each into stacks of its own, rotating through three sets of
+    window offsets, so that call k and call k - 4 -- which fill the same copy -- never share a table: a stale copy shows as a wrong stack.
+    From start level 0 (the shortest call).  Every stack is bit-equal to the same call made alone and waited for on that context."""
+    s, pairs = min(STARTS), lc.pairs()
+    priors, poffs = [_prior(orc, j)[0] for j in range(3)], [_prior(orc, j)[1] for j in range(3)]
+    sets = [[NEW[(j + r) % 3] for j in range(3)] for r in range(3)]
+    assert all(sets[k % 3] != sets[(k - 4) % 3] for k in range(4, 9))
+    nf, shape = _stack_floats(lib)
+    with lib.Context(levels=LEVELS, fovea_levels=F, batch=3) as c:
+        d = Dev(c)
+        try:
+            put = [(d.put(L)[0], d.put(R)[0]) for L, R in pairs]
+            stride = pairs[0][0].strides[0]
+            dP = [c.to_device(np.ascontiguousarray(p, np.float32)) for p in priors]
+            d.bufs += dP
+
+            def call(offs):
+                dO = [d.out(nf) for _ in pairs]
+                c.submit_foveated_warm(0, [p[0] for p in put], [p[1] for p in put], W, H, stride, offs, dP, poffs, s, dO)
+                return dO
+            alone = []
+            for offs in sets:
+                dO = call(offs)
+                c.check(c.lib.ugsm_wait(c.handle, 0))
+                alone.append([c.to_host(p, shape) for p in dO])
+            for j in range(3):    # the premise: the three sets give pair j three different stacks
+                assert len({alone[r][j].tobytes() for r in range(3)}) == 3, f"premise: pair {j}"
+            assert_bit_equal(alone[0][0], _warm(orc, 0, s), "the call made alone, against the oracle")
+            queued = [call(sets[k % 3]) for k in range(9)]
+            c.check(c.lib.ugsm_wait(c.handle, 0))
+            for k in range(9):
+                for j in range(3):
+                    assert_bit_equal(c.to_host(queued[k][j], shape), alone[k % 3][j], f"call {k} of nine back to back, pair {j}")
+        finally:
+            d.free()
+
+
 # ---- 7. what runs --------------------------------------------------------------------------------------------------------------------------
 
 def _is_level_work(name):

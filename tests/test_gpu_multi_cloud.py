@@ -295,3 +295,58 @@ def test_bad_arguments_on_a_live_context(lib):
         finally:
             for p in bufs.values():
                 c.free(p)
+
+
+def test_nine_calls_back_to_back_take_turns_on_the_upload_ring(lib):
+    """320 x 240, two windows: nine ugsm_point_cloud_fovea_multi calls on one slot with no wait between them, each into its own poisoned
+    point buffer and count words, rotating through three offset sets (and dense / compact), so that call k and call k - 4 -- which fill the
+    same page-locked copy of the table -- never share a table: a stale copy shows as a wrong cloud.  After one ugsm_wait every call's
+    records (and the poison behind them), count and entry counts equal byte for byte what the same call gave when made alone and waited
+    for on that context."""
+    W, H, F = CASES[2][:3]
+    sets = [[(-60, 40), (0, 0)], [(25, 10), (-30, -20)], [(40, -35), (10, 50)]]
+    n, E, fmt, extra = 2, (F - 1) * 2 + 1, cn.PCL32, 64
+    item = cn.DTYPES[fmt].itemsize
+    rng = np.random.Generator(np.random.PCG64(44))
+    stacks, rgb = _random_stacks(rng, W, H, F, n)
+    dp = C.POINTER(C.c_double)
+    p1, p2 = (np.ascontiguousarray(P, np.float64).reshape(12) for P in (P1, P2A))
+    with lib.Context(levels=LEVELS[F], fovea_levels=F, slots=1) as c:
+        so, h = c.lib, c.handle
+        d_stacks, d_rgb = [c.to_device(t) for t in stacks], c.to_device(rgb)
+        calls = [(sets[k % 3], bool(k % 2)) for k in range(9)]
+        assert all(calls[k][0] != calls[k - 4][0] for k in range(4, 9))
+        caps = [lib.fovea_multi_cloud_points(W, H, LEVELS[F], F, offs, 1) for offs, _ in calls]
+        params = [lib.cloud_params(format=fmt, compact=True, min_conf=0.3) if compact else lib.cloud_params(format=fmt) for _, compact in calls]
+        held = []
+
+        def enqueue(k):
+            bufs = (_poisoned(c, (caps[k] + extra) * item), c.to_device(np.full(1, -7, np.int64)), c.to_device(np.full(E + 1, -7, np.int64)))
+            held.extend(bufs)
+            ox, oy = c._offsets(calls[k][0], n)
+            c.check(so.ugsm_point_cloud_fovea_multi(h, 0, n, c._ptrs(d_stacks), W, H, ox, oy, d_rgb, 3 * W, p1.ctypes.data_as(dp), p2.ctypes.data_as(dp),
+                                                    C.byref(params[k]), bufs[0], caps[k], bufs[1], bufs[2]))
+            return bufs
+
+        def result(k, bufs):
+            return (c.to_host(bufs[0], ((caps[k] + extra) * item,), np.uint8).tobytes(), c.to_host(bufs[1], (1,), np.int64).tobytes(),
+                    c.to_host(bufs[2], (E + 1,), np.int64).tobytes())
+        try:
+            alone = []
+            for k in range(9):
+                bufs = enqueue(k)
+                c.check(so.ugsm_wait(h, 0))
+                alone.append(result(k, bufs))
+            # the premise: per form, the three offset sets give three different clouds (and every call wrote one)
+            for form in ((0, 2, 4), (1, 3, 5)):
+                assert len({alone[k][0] for k in form}) == 3 and len({alone[k][2] for k in form}) == 3
+            assert all(0 < np.frombuffer(a[1], np.int64)[0] <= cap for a, cap in zip(alone, caps))
+            queued = [enqueue(k) for k in range(9)]
+            c.check(so.ugsm_wait(h, 0))
+            for k in range(9):
+                got = result(k, queued[k])
+                assert got[1] == alone[k][1] and got[2] == alone[k][2], f"call {k}: the count or the entry counts"
+                assert got[0] == alone[k][0], f"call {k}: the records"
+        finally:
+            for p in held + d_stacks + [d_rgb]:
+                c.free(p)

@@ -234,9 +234,9 @@ size_t cloud_cnt_words(int entries, int wc, int nchunk) { return (size_t)entries
 
 // What every slot-level cloud does before its launch: it takes the slot and sets the device, fills in the sampled grid (unless the resized
 // forms have: resize_args), its chunks and the input format and, for a compact cloud, makes the slot's count buffer hold `entries`
-// virtual grids and zeroes their totals on the slot's stream.  table_rows (the merged cloud of several windows): before that, room for so
-// many rows in the device table and in the page-locked copies it goes up from.
-int cloud_begin(ugsm_ctx *ctx, int slot, CloudArgs &a, int entries, Slot **out, size_t table_rows = 0)
+// virtual grids and zeroes their totals on the slot's stream.  table (the merged cloud of several windows): before that, the call's turn of the
+// slot's upload ring -- one row per entry, for the caller to fill and upload.
+int cloud_begin(ugsm_ctx *ctx, int slot, CloudArgs &a, int entries, Slot **out, CloudEntry **table = nullptr)
 {
     UCHK(get_slot(ctx, slot, out));
     Slot &s = **out;
@@ -249,22 +249,11 @@ int cloud_begin(ugsm_ctx *ctx, int slot, CloudArgs &a, int entries, Slot **out, 
     a.nchunk = cloud_chunks(a.hc);
     a.fmt = ctx->hooks.input_format;
     a.cnt = nullptr;
-    if (table_rows > c.mc_tab_cap || table_rows > c.mc_tab_h_rows) {  // (an earlier call's kernels may still read the table, its upload the copies)
-        HIPCHK(ctx, hipStreamSynchronize(s.st));
-        UCHK(grow(ctx, c.mc_tab, c.mc_tab_cap, table_rows));
-        if (table_rows > c.mc_tab_h_rows) {
-            if (c.mc_tab_h) HIPCHK(ctx, hipHostFree(c.mc_tab_h));
-            c.mc_tab_h = nullptr;
-            c.mc_tab_h_rows = 0;
-            HIPCHK(ctx, hipHostMalloc((void **)&c.mc_tab_h, SlotCloud::kMcRing * table_rows * sizeof(CloudEntry), hipHostMallocDefault));
-            c.mc_tab_h_rows = table_rows;
-            for (bool &set : c.mc_ev_set) set = false;
-        }
-    }
+    if (table) UCHK(c.mc.begin(ctx, s.st, (size_t)entries, table));
     if (!a.compact) return UGSM_OK;
     const size_t counts = (size_t)entries * a.wc * a.nchunk, need = cloud_cnt_words(entries, a.wc, a.nchunk);
-    if (need > c.cnt_cap) HIPCHK(ctx, hipStreamSynchronize(s.st));  // (the buffer being replaced may still be read by an earlier cloud)
-    UCHK(grow(ctx, c.cnt, c.cnt_cap, need));
+    if (need > c.cnt.cap) HIPCHK(ctx, hipStreamSynchronize(s.st));  // (the buffer being replaced may still be read by an earlier cloud)
+    UCHK(c.cnt.grow(ctx, need));
     a.cnt = c.cnt;
     HIPCHK(ctx, hipMemsetAsync(a.cnt + counts, 0, (need - counts) * sizeof(unsigned), s.st));  // (the totals)
     return UGSM_OK;
@@ -461,13 +450,8 @@ int ugsm_point_cloud_fovea_multi(ugsm_ctx *ctx, int slot, int n, const float *co
     CloudArgs a = cloud_args(nullptr, nullptr, nullptr, d_rgbL, W, H, stride, g.fw, g.fh, p, d_points, cap_points, d_count);
     Slot *s;
     const int E = g.E;
-    UCHK(cloud_begin(ctx, slot, a, E, &s, (size_t)E));
-    SlotCloud &c = s->cloud;
-    const int turn = c.mc_next;
-    c.mc_next = (turn + 1) % SlotCloud::kMcRing;
-    if (!c.mc_ev[turn]) HIPCHK(ctx, hipEventCreateWithFlags(&c.mc_ev[turn], hipEventDisableTiming));
-    if (c.mc_ev_set[turn]) HIPCHK(ctx, hipEventSynchronize(c.mc_ev[turn]));  // (the upload of the call kMcRing back: long done)
-    CloudEntry *const rows = c.mc_tab_h + (size_t)turn * c.mc_tab_h_rows;
+    CloudEntry *rows;
+    UCHK(cloud_begin(ctx, slot, a, E, &s, &rows));
     const bool use_conf = a.compact && p->min_conf > -INFINITY;  // (the confidence planes are read by nothing else)
     long long total = 0;
     for (int e = 0; e < E; e++) {
@@ -478,10 +462,8 @@ int ugsm_point_cloud_fovea_multi(ugsm_ctx *ctx, int slot, int n, const float *co
         rows[e].conf = use_conf ? rows[e].dx + 2 * plane : nullptr;
         total += rows[e].points;
     }
-    HIPCHK(ctx, hipMemcpyAsync(c.mc_tab, rows, (size_t)E * sizeof(CloudEntry), hipMemcpyHostToDevice, s->st));
-    HIPCHK(ctx, hipEventRecord(c.mc_ev[turn], s->st));
-    c.mc_ev_set[turn] = true;
-    const CloudMulti mu{c.mc_tab, E, total, d_entry_counts};
+    UCHK(s->cloud.mc.upload(ctx, s->st, (size_t)E));
+    const CloudMulti mu{s->cloud.mc.tab, E, total, d_entry_counts};
     return timed_launch(ctx, s, slot, (double)E * a.wc * a.hc, [&] { launch_point_cloud_multi(s->st, a, mu, P1, P2); });
 }
 
@@ -556,15 +538,11 @@ static int cloud_call_submit(ugsm_ctx *ctx, int slot, const CloudCall *call, con
         // the slot's uploads and hout: [states][results], one result for a call that runs pair by pair, n otherwise; a checked call: [back fields]
         // behind them
         const size_t img = ((size_t)stride * H + 255) & ~(size_t)255;
-        if (img * copies > s->rgb_cap) {
-            size_t c = s->rgb_cap;
-            UCHK(grow(ctx, s->rgbL, c, img * copies));
-            UCHK(grow(ctx, s->rgbR, s->rgb_cap, img * copies));
-        }
+        UCHK(s->rgb_cap.grow(ctx, img * copies, {&s->rgbL, &s->rgbR}));
         bool any_back = false;
         for (int b = 0; chk && b < n; b++) any_back = any_back || chk->job[b].back_planes[0];
         const size_t at_res = room.part(copies * res_per), at_back = room.part(any_back ? copies * res_per : 0);
-        UCHK(grow(ctx, s->hout, s->hout_cap, room.total));
+        UCHK(s->hout.grow(ctx, room.total));
         for (int b = 0; b < n; b++) {
             const int k = by_pair ? 0 : b;
             dL[b] = s->rgbL + k * img;
@@ -573,7 +551,7 @@ static int cloud_call_submit(ugsm_ctx *ctx, int slot, const CloudCall *call, con
             if (chk && chk->job[b].back_planes[0]) back[b] = s->hout + at_back + k * res_per;
         }
     } else {
-        UCHK(grow(ctx, s->hout, s->hout_cap, room.total));
+        UCHK(s->hout.grow(ctx, room.total));
         for (int b = 0; b < n; b++) {
             if (!call->job[b].L || !call->job[b].R || !call->job[b].out) return UGSM_ERR_BAD_ARG;
             dL[b] = call->job[b].L;
@@ -584,12 +562,8 @@ static int cloud_call_submit(ugsm_ctx *ctx, int slot, const CloudCall *call, con
     }
 
     // 2. the table: every pair's cloud arguments
-    if ((size_t)n > c.cq_tab_cap) {
-        if (c.cq_tab_h) HIPCHK(ctx, hipHostFree(c.cq_tab_h));
-        c.cq_tab_h = nullptr;
-        UCHK(grow(ctx, c.cq_tab, c.cq_tab_cap, (size_t)kMaxBatch));
-        HIPCHK(ctx, hipHostMalloc((void **)&c.cq_tab_h, kMaxBatch * sizeof(CloudPair), hipHostMallocDefault));
-    }
+    UCHK(c.cq_tab.grow(ctx, (size_t)kMaxBatch));
+    UCHK(c.cq_tab_h.grow(ctx, (size_t)kMaxBatch));
     CloudStack sk[UGSM_MAX_BATCH];
     long long dense[UGSM_MAX_BATCH], max_cap = 0;
     int ox[UGSM_MAX_BATCH], oy[UGSM_MAX_BATCH];  // (foveated calls: the pairs' window offsets)
@@ -607,13 +581,13 @@ static int cloud_call_submit(ugsm_ctx *ctx, int slot, const CloudCall *call, con
     }
     if (managed) {
         c.cq_stride = (size_t)max_cap * step;
-        UCHK(grow(ctx, c.cq_pts, c.cq_pts_cap, std::max(c.cq_stride * n, (size_t)16)));
-        UCHK(grow(ctx, c.cq_words, c.cq_words_cap, kMaxBatch * kCqWords));
-        if (!c.cq_words_h) HIPCHK(ctx, hipHostMalloc((void **)&c.cq_words_h, kMaxBatch * kCqWords * sizeof(long long), hipHostMallocDefault));
+        UCHK(c.cq_pts.grow(ctx, std::max(c.cq_stride * n, (size_t)16)));
+        UCHK(c.cq_words.grow(ctx, kMaxBatch * kCqWords));
+        UCHK(c.cq_words_h.grow(ctx, kMaxBatch * kCqWords));
     }
     const int wc = (fw + p.sampling - 1) / p.sampling, hc = (fh + p.sampling - 1) / p.sampling, nchunk = cloud_chunks(hc);
     const size_t cnt_per = cloud_cnt_words(fovea ? F : 1, wc, nchunk);  // a pair's region of the count buffer
-    if (p.compact) UCHK(grow(ctx, c.cnt, c.cnt_cap, cnt_per * n));
+    if (p.compact) UCHK(c.cnt.grow(ctx, cnt_per * n));
     for (int b = 0; b < n; b++) {
         const CloudJob &j = call->job[b];
         void *points = managed ? (void *)(c.cq_pts + b * c.cq_stride) : j.points;

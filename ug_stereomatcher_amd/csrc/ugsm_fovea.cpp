@@ -176,16 +176,7 @@ int enqueue_restrict_stack(ugsm_ctx *ctx, Slot &s, int si, int n, const int *w, 
     }
     RestrictStackRow local[kRestrictStackByValue], *rows = local;
     const bool table = n > kRestrictStackByValue;
-    int turn = 0;
-    if (table) {
-        UCHK(grow(ctx, s.warm_tab, s.warm_tab_cap, (size_t)kMaxBatch));
-        if (!s.warm_tab_h) HIPCHK(ctx, hipHostMalloc((void **)&s.warm_tab_h, Slot::kWarmRing * kMaxBatch * sizeof(RestrictStackRow), hipHostMallocDefault));
-        turn = s.warm_next;
-        s.warm_next = (turn + 1) % Slot::kWarmRing;
-        if (!s.warm_ev[turn]) HIPCHK(ctx, hipEventCreateWithFlags(&s.warm_ev[turn], hipEventDisableTiming));
-        if (s.warm_ev_set[turn]) HIPCHK(ctx, hipEventSynchronize(s.warm_ev[turn]));  // (the upload of the call kWarmRing back: long done)
-        rows = s.warm_tab_h + (size_t)turn * kMaxBatch;
-    }
+    if (table) UCHK(s.warm.begin(ctx, s.st, (size_t)kMaxBatch, &rows));
     for (int b = 0; b < n; b++) {
         FoveaGeom gn, gp;
         fovea_geometry(w, h, F, off_x ? off_x[b] : 0, off_y ? off_y[b] : 0, gn);
@@ -203,10 +194,8 @@ int enqueue_restrict_stack(ugsm_ctx *ctx, Slot &s, int si, int n, const int *w, 
         }
     }
     if (table) {
-        HIPCHK(ctx, hipMemcpyAsync(s.warm_tab, rows, (size_t)n * sizeof(RestrictStackRow), hipMemcpyHostToDevice, s.st));
-        HIPCHK(ctx, hipEventRecord(s.warm_ev[turn], s.st));
-        s.warm_ev_set[turn] = true;
-        rs.table = s.warm_tab;
+        UCHK(s.warm.upload(ctx, s.st, (size_t)n));
+        rs.table = s.warm.tab;
     }
     s.cur_level = start;
     bool ok;
@@ -284,11 +273,8 @@ int fovea_grow(ugsm_ctx *ctx, Slot &s, int W, int H, const FoveaCall &call, cons
     const bool windows = call.kind == FoveaCall::Windows, checked = checked_tau(ctx, call) > 0.0f;
     if (windows && (checked || !fovea_windows_run_one_by_one(ctx, call.n)))
         UCHK(ensure_level_bufs(ctx, s, std::max((checked ? 2 : 1) * call.n * room.field, 3 * (size_t)W * H)));
-    if (checked) {
-        UCHK(grow(ctx, s.lr, s.lr_cap, lr_room(call.n, ctx->cfg.fovea_levels, room.fw, room.fh, windows).total));
-        UCHK(lr_host_ready(ctx, s));
-    }
-    return grow(ctx, s.hout, s.hout_cap, room.total);
+    if (checked) UCHK(lr_ready(ctx, s, lr_room(call.n, ctx->cfg.fovea_levels, room.fw, room.fh, windows).total));
+    return s.hout.grow(ctx, room.total);
 }
 
 // One foveated call on device buffers, every kind of it (FoveaCall; d_rgbL / d_rgbR: the n pairs' images, or the one pair's).  The steps are the
@@ -337,7 +323,7 @@ int enqueue_foveated(ugsm_ctx *ctx, Slot &s, int si, const uint8_t *const *d_rgb
     // configured batch did not fit): checked pairs grow them to their 2 n fields where the rounding asks for it, the windows' fields are refused
     const LrRoom lr = lr_room(n, F, room.fw, room.fh, windows);
     if (checked && !windows) UCHK(ensure_level_bufs(ctx, s, fine.nb * fine.stride));
-    if (windows && !one_by_one && (fine.nb * fine.stride > s.lvl_cap || (checked && (lr.total > s.lr_cap || !s.lr_host))))
+    if (windows && !one_by_one && (fine.nb * fine.stride > s.lvl_cap || (checked && (lr.total > s.lr.cap || !s.lr_host))))
         return ctx_fail(ctx, UGSM_ERR_STATE, checked ? "the slot's buffers do not hold the checked windows' fields" : "the level buffers do not hold the windows' fields");
     // the range words of the real pairs (the one pair of n windows) out to the entries that run under them, doubling what is already there
     for (int c = windows ? 1 : n; s.range_known && c < fine.nb; c *= 2)

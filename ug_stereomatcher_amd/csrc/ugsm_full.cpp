@@ -156,11 +156,10 @@ int enqueue_full_lr(ugsm_ctx *ctx, Slot &s, int si, float *d_out)
 {
     const float tau = ctx->lr_tau;
     const size_t n3 = 3 * (size_t)s.W * s.H;
-    UCHK(grow(ctx, s.lr, s.lr_cap, n3 + 4));
-    UCHK(lr_host_ready(ctx, s));
+    UCHK(lr_ready(ctx, s, n3 + 4));
     unsigned long long *cnt = reinterpret_cast<unsigned long long *>(s.lr + ((n3 + 1) & ~(size_t)1));  // (8-byte aligned)
     HIPCHK(ctx, hipMemsetAsync(cnt, 0, sizeof *cnt, s.st));
-    UCHK(enqueue_full(ctx, s, si, &s.lr, LevelRange::cold(s.levels), true));
+    UCHK(enqueue_full(ctx, s, si, &s.lr.p, LevelRange::cold(s.levels), true));
     {
         Timer t(ctx, &s, si, KC_MISC, (double)s.W * s.H);
         launch_lr_check(s.st, d_out, s.lr, s.W, s.H, tau, cnt);
@@ -202,7 +201,7 @@ int enqueue_full_checked(ugsm_ctx *ctx, Slot &s, int si, int n, const uint8_t *c
     // (holds already, unless prepare_slot ran out of memory for the configured batch and fell back to this call's n pairs: it then freed what the
     // caller had grown)
     UCHK(ensure_level_bufs(ctx, s, sh.nb * sh.stride));
-    if (lr_full_room(s.lvl_stride, kept, n) > s.lr_cap || !s.lr_host) {
+    if (lr_full_room(s.lvl_stride, kept, n) > s.lr.cap || !s.lr_host) {
         ctx->err = "the slot's buffers do not hold both directions' fields";
         return UGSM_ERR_STATE;
     }
@@ -337,8 +336,7 @@ int full_checked_bufs(ugsm_ctx *ctx, Slot &s, int n, int kept, int W, int H)
 {
     const size_t field = field_room((size_t)W * H);  // (Slot::lvl_stride, as prepare_slot sets it for this size)
     UCHK(ensure_level_bufs(ctx, s, 2 * (size_t)n * field));
-    UCHK(grow(ctx, s.lr, s.lr_cap, lr_full_room(field, kept, n)));
-    return lr_host_ready(ctx, s);
+    return lr_ready(ctx, s, lr_full_room(field, kept, n));
 }
 
 // ---- the queue's checked pairs (ugsm_enqueue_full_checked*; CtxHooks::checked_submit / checked_marked) ------------------------------------

@@ -103,11 +103,7 @@ int stage_in(ugsm_ctx *ctx, Slot &s, const uint8_t *rgbL, const uint8_t *rgbR, i
     if (!rgbL || !rgbR || W < 1 || H < 1) return UGSM_ERR_BAD_ARG;
     UCHK(input_status(ctx, W, stride, rgbL, rgbR));
     const size_t bytes = (size_t)stride * H;
-    if (bytes > s.rgb_cap) {
-        size_t c = s.rgb_cap;
-        UCHK(grow(ctx, s.rgbL, c, bytes));
-        UCHK(grow(ctx, s.rgbR, s.rgb_cap, bytes));
-    }
+    UCHK(s.rgb_cap.grow(ctx, bytes, {&s.rgbL, &s.rgbR}));
     HIPCHK(ctx, hipMemcpyAsync(s.rgbL, rgbL, bytes, hipMemcpyHostToDevice, s.st));
     // the right image goes up on the side stream, where its pyramid is built: the transfer (0.9 ms at 16 MP) then runs under the
     // left pyramid instead of in front of it.  The side stream first waits for what the slot did before.
@@ -198,13 +194,7 @@ int copy_out_planes(ugsm_ctx *ctx, Slot &s, const float *d_src, size_t plane_flo
         for (int k = 0; k < 3; k++) HIPCHK(ctx, hipMemcpyAsync(dst[k], d_src + k * plane_floats, pb, hipMemcpyDeviceToHost, s.st));
         return UGSM_OK;
     }
-    if (3 * plane_floats > s.hpin_cap) {
-        if (s.hpin) HIPCHK(ctx, hipHostFree(s.hpin));
-        s.hpin = nullptr;
-        s.hpin_cap = 0;
-        HIPCHK(ctx, hipHostMalloc((void **)&s.hpin, 3 * pb, hipHostMallocDefault));
-        s.hpin_cap = 3 * plane_floats;
-    }
+    UCHK(s.hpin.grow(ctx, 3 * plane_floats));
     // Every plane in PIECES: a piece's copy into the caller's pages runs under the next piece's transfer, so what is left exposed behind
     // the last transfer is one piece's copy, not one plane's (a quarter plane at 16 MP: 0.25 ms instead of 1 ms).
     const int pieces = pb >= 4 * kTeamMinBytes ? 4 : 1;
@@ -287,7 +277,7 @@ int host_call(ugsm_ctx *ctx, int slot, bool sync, const uint8_t *rgbL, const uin
         size_t hout = 0;
         UCHK(check(*s, hout));
         UCHK(stage_in(ctx, *s, rgbL, rgbR, W, H, stride));
-        UCHK(grow(ctx, s->hout, s->hout_cap, hout));
+        UCHK(s->hout.grow(ctx, hout));
         UCHK(match(*s));
         UCHK(down(*s));
         if (!sync) return mark_done(ctx, *s);
@@ -317,8 +307,8 @@ int seeded_match(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int W,
     const size_t n = (size_t)W * H;
     auto match = [&](Slot &s) -> int {
         UCHK(upload_planes(ctx, s, s.hout, n, prior));
-        const LevelRange r = LevelRange::seeded(start_level, &s.hout);
-        return enqueue_match_full(ctx, s, 0, 1, &s.rgbL, &s.rgbR, W, H, stride, &s.hout, &r);
+        const LevelRange r = LevelRange::seeded(start_level, &s.hout.p);
+        return enqueue_match_full(ctx, s, 0, 1, &s.rgbL.p, &s.rgbR.p, W, H, stride, &s.hout.p, &r);
     };
     return host_call(ctx, rgbL, rgbR, W, H, stride, 3 * n, match, [&](Slot &s) -> int {
         prefault_planes(ctx, disp, n);
@@ -336,7 +326,7 @@ int coarse_match(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int W,
     auto match = [&](Slot &s) -> int {
         float *const d_state = s.hout + room, *const d_full = full ? s.hout : nullptr;
         const LevelRange r = LevelRange::coarse(ctx->cfg.levels, e, &d_full);
-        return enqueue_match_full(ctx, s, 0, 1, &s.rgbL, &s.rgbR, W, H, stride, &d_state, &r);
+        return enqueue_match_full(ctx, s, 0, 1, &s.rgbL.p, &s.rgbR.p, W, H, stride, &d_state, &r);
     };
     return host_call(ctx, rgbL, rgbR, W, H, stride, room + 3 * ne, match, [&](Slot &s) -> int {
         if (full) prefault_planes(ctx, full, n);
@@ -353,7 +343,7 @@ int fine_match(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int W, i
         UCHK(upload_planes(ctx, s, s.hout + room, ne, state));
         const float *const d_state = s.hout + room;
         const LevelRange r = LevelRange::fine(e, &d_state);
-        return enqueue_match_full(ctx, s, 0, 1, &s.rgbL, &s.rgbR, W, H, stride, &s.hout, &r);
+        return enqueue_match_full(ctx, s, 0, 1, &s.rgbL.p, &s.rgbR.p, W, H, stride, &s.hout.p, &r);
     };
     return host_call(ctx, rgbL, rgbR, W, H, stride, room + 3 * ne, match, [&](Slot &s) -> int {
         prefault_planes(ctx, disp, n);
@@ -373,7 +363,7 @@ int fovea_warm_match(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, in
         UCHK(upload_planes(ctx, s, s.hout + at_prior, room.plane, prior));
         const float *const d_prior = s.hout + at_prior;
         float *const d_stack = s.hout + at_stack;
-        return enqueue_foveated(ctx, s, 0, &s.rgbL, &s.rgbR, W, H, stride,
+        return enqueue_foveated(ctx, s, 0, &s.rgbL.p, &s.rgbR.p, W, H, stride,
                                 FoveaCall::warm(1, &off_x, &off_y, &d_prior, &prior_off_x, &prior_off_y, false, start_level, &d_stack));
     };
     return host_call(ctx, rgbL, rgbR, W, H, stride, room.total, match,
@@ -398,7 +388,7 @@ static int match_full_host(ugsm_ctx *ctx, int slot, const uint8_t *rgbL, const u
         hout = 3 * n;
         return UGSM_OK;
     };
-    auto match = [&](Slot &s) -> int { return enqueue_match_full(ctx, s, slot, 1, &s.rgbL, &s.rgbR, W, H, stride, &s.hout); };
+    auto match = [&](Slot &s) -> int { return enqueue_match_full(ctx, s, slot, 1, &s.rgbL.p, &s.rgbR.p, W, H, stride, &s.hout.p); };
     return host_call(ctx, slot, sync, rgbL, rgbR, W, H, stride, check, match, [&](Slot &s) -> int {
         if (sync) prefault_planes(ctx, dst, n);  // the GPU is busy for the next ~10 ms: touch the caller's result pages meanwhile
         return copy_out_planes(ctx, s, s.hout, n, dst);
@@ -431,11 +421,11 @@ int ugsm_match_full_checked(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *r
         UCHK(full_checked_check(ctx, 1, W, H, stride, tau));
         UCHK(full_checked_bufs(ctx, s, 1, back ? 0 : 1, W, H));
         hout = (back ? 2 : 1) * room;
-        return grow(ctx, s.hout, s.hout_cap, hout);
+        return s.hout.grow(ctx, hout);
     };
     auto match = [&](Slot &s) -> int {
         float *const d_fwd = s.hout, *const d_bwd = back ? s.hout + room : nullptr;
-        return enqueue_full_checked(ctx, s, 0, 1, &s.rgbL, &s.rgbR, W, H, stride, &d_fwd, back ? &d_bwd : nullptr, tau);
+        return enqueue_full_checked(ctx, s, 0, 1, &s.rgbL.p, &s.rgbR.p, W, H, stride, &d_fwd, back ? &d_bwd : nullptr, tau);
     };
     return host_call(ctx, 0, true, rgbL, rgbR, W, H, stride, check, match, [&](Slot &s) -> int {
         prefault_planes(ctx, dst, n);
@@ -469,7 +459,7 @@ static int match_foveated_host(ugsm_ctx *ctx, int slot, const uint8_t *rgbL, con
         d_stack = s.hout + at_stack;
         d_pl = pyrL ? s.hout + at_pl : nullptr;
         d_pr = pyrR ? s.hout + at_pr : nullptr;
-        return enqueue_foveated(ctx, s, slot, &s.rgbL, &s.rgbR, W, H, stride, FoveaCall::pairs(1, &off_x, &off_y, &d_stack, &d_pl, &d_pr));
+        return enqueue_foveated(ctx, s, slot, &s.rgbL.p, &s.rgbR.p, W, H, stride, FoveaCall::pairs(1, &off_x, &off_y, &d_stack, &d_pl, &d_pr));
     };
     return host_call(ctx, slot, sync, rgbL, rgbR, W, H, stride, check, match, [&](Slot &s) -> int {
         UCHK(download_stack(ctx, s, d_stack, room.plane, stackH, stackV, stackC));
@@ -511,7 +501,7 @@ static int match_foveated_multi_host(ugsm_ctx *ctx, const uint8_t *rgbL, const u
         hout = room.total;
         return UGSM_OK;
     };
-    auto match = [&](Slot &s) -> int { return enqueue_foveated(ctx, s, 0, &s.rgbL, &s.rgbR, W, H, stride, call); };
+    auto match = [&](Slot &s) -> int { return enqueue_foveated(ctx, s, 0, &s.rgbL.p, &s.rgbR.p, W, H, stride, call); };
     return host_call(ctx, 0, true, rgbL, rgbR, W, H, stride, check, match, [&](Slot &s) -> int {
         for (int k = 0; k < n; k++) UCHK(download_stack(ctx, s, d_stack[k], room.plane, stackH[k], stackV[k], stackC[k]));
         return UGSM_OK;
@@ -549,7 +539,7 @@ int ugsm_match_foveated_full(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *
     };
     auto match = [&](Slot &s) -> int {
         float *d_stack = s.hout + at_stack;
-        UCHK(enqueue_foveated(ctx, s, 0, &s.rgbL, &s.rgbR, W, H, stride, FoveaCall::pairs(1, &off_x, &off_y, &d_stack)));
+        UCHK(enqueue_foveated(ctx, s, 0, &s.rgbL.p, &s.rgbR.p, W, H, stride, FoveaCall::pairs(1, &off_x, &off_y, &d_stack)));
         return ugsm_reconstruct_full(ctx, 0, d_stack, d_stack + room.plane, d_stack + 2 * room.plane, W, H, off_x, off_y, s.hout + at_full);
     };
     return host_call(ctx, 0, true, rgbL, rgbR, W, H, stride, check, match, [&](Slot &s) -> int {
@@ -580,11 +570,7 @@ static int stage_in_batch(ugsm_ctx *ctx, Slot &s, int n, const uint8_t *const *r
     if (W < 1 || H < 1) return UGSM_ERR_BAD_ARG;
     for (int b = 0; b < n; b++) UCHK(input_status(ctx, W, stride, rgbL[b], rgbR[b]));
     const size_t bytes = ((size_t)stride * H + 255) & ~(size_t)255;
-    if (bytes * n > s.rgb_cap) {
-        size_t c = s.rgb_cap;
-        UCHK(grow(ctx, s.rgbL, c, bytes * n));
-        UCHK(grow(ctx, s.rgbR, s.rgb_cap, bytes * n));
-    }
+    UCHK(s.rgb_cap.grow(ctx, bytes * n, {&s.rgbL, &s.rgbR}));
     for (int b = 0; b < n; b++) {
         dL[b] = s.rgbL + b * bytes;
         dR[b] = s.rgbR + b * bytes;
@@ -609,7 +595,7 @@ int ugsm_submit_full_batch_host(ugsm_ctx *ctx, int slot, int n, const uint8_t *c
     const uint8_t *dL[UGSM_MAX_BATCH], *dR[UGSM_MAX_BATCH];
     UCHK(stage_in_batch(ctx, *s, n, rgbL, rgbR, W, H, stride, dL, dR));
     const size_t px = (size_t)W * H, per = field_room(px);
-    UCHK(grow(ctx, s->hout, s->hout_cap, per * n));
+    UCHK(s->hout.grow(ctx, per * n));
     float *out[UGSM_MAX_BATCH];
     for (int b = 0; b < n; b++) out[b] = s->hout + b * per;
     UCHK(enqueue_match_full(ctx, *s, slot, n, dL, dR, W, H, stride, out));
@@ -648,7 +634,7 @@ int ugsm_submit_full_checked_host(ugsm_ctx *ctx, int slot, int n, const uint8_t 
         if (takes[b] && !(is_pinned(backH[b]) && is_pinned(backV[b]) && is_pinned(backC[b]))) return not_pinned(ctx, "ugsm_submit_full_checked_host");
     const size_t px = (size_t)W * H, per = field_room(px);
     UCHK(full_checked_bufs(ctx, *s, n, n - taken, W, H));
-    UCHK(grow(ctx, s->hout, s->hout_cap, per * (n + taken)));
+    UCHK(s->hout.grow(ctx, per * (n + taken)));
     const uint8_t *dL[UGSM_MAX_BATCH], *dR[UGSM_MAX_BATCH];
     UCHK(stage_in_batch(ctx, *s, n, rgbL, rgbR, W, H, stride, dL, dR));
     float *out[UGSM_MAX_BATCH], *back[UGSM_MAX_BATCH];

@@ -154,14 +154,8 @@ int enqueue_smooth(ugsm_ctx *ctx, Slot &s, int si, const Shape &sh, float *&a, f
 int weighted_difference(ugsm_ctx *ctx, Slot &s, const float *newd3, const float *oldd3, int W, int H, float out2[2])
 {
     const size_t need = 3 * (size_t)H + 3;
-    if (need > s.wd_cap) {
-        if (s.wd_rows) HIPCHK(ctx, hipFree(s.wd_rows));
-        s.wd_rows = nullptr;
-        s.wd_cap = 0;
-        HIPCHK(ctx, hipMalloc((void **)&s.wd_rows, need * sizeof(double)));
-        s.wd_cap = need;
-    }
-    if (!s.wd_host) HIPCHK(ctx, hipHostMalloc((void **)&s.wd_host, 3 * sizeof(double), hipHostMallocDefault));
+    UCHK(s.wd_rows.grow(ctx, need));
+    UCHK(s.wd_host.grow(ctx, 3));
     double *tot = s.wd_rows + 3 * (size_t)H;
     launch_weighted_difference(s.st, newd3, oldd3, W, H, s.wd_rows, tot);
     HIPCHK(ctx, hipMemcpyAsync(s.wd_host, tot, 3 * sizeof(double), hipMemcpyDeviceToHost, s.st));
@@ -198,7 +192,7 @@ int run_level(ugsm_ctx *ctx, Slot &s, int si, const Shape &sh, const Img3 *Lv, c
     float *third = nullptr;
     if (early) {
         const size_t lvl = 3 * (size_t)W * H;
-        UCHK(grow(ctx, s.d2, s.d2_cap, std::max(lvl, s.lvl_cap)));
+        UCHK(s.d2.grow(ctx, std::max<size_t>(lvl, s.lvl_cap)));
         // the three field buffers rotate through the levels: the spare one is whichever is neither `cur` nor `other` right now
         third = (s.d0 != cur && s.d0 != other) ? s.d0 : ((s.d1 != cur && s.d1 != other) ? s.d1 : s.d2);
         final_out = nullptr;
@@ -329,7 +323,7 @@ int enqueue_side_A(ugsm_ctx *ctx, Slot &s, int a_from, int a_top)
 {
     if (a_from < 0 || ctx->cfg.early_exit_threshold > 0.0f) return UGSM_OK;
     size_t tot = s.off[s.levels - 1] + 3 * (size_t)s.w[s.levels - 1] * s.h[s.levels - 1];
-    UCHK(grow(ctx, s.Apyr, s.apyr_cap, tot));
+    UCHK(s.Apyr.grow(ctx, tot));
     HIPCHK(ctx, hipEventRecord(s.ev_L, s.st));  // (the left pyramid is complete on the main stream)
     s.forked = true;
     HIPCHK(ctx, hipStreamWaitEvent(s.st2, s.ev_L, 0));

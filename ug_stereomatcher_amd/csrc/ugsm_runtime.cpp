@@ -128,63 +128,16 @@ void fovea_geometry(const int *w, const int *h, int F, int off_x, int off_y, Fov
 // for the largest level seen.
 int ensure_level_bufs(ugsm_ctx *ctx, Slot &s, size_t lvl)
 {
-    if (lvl <= s.lvl_cap) return UGSM_OK;
-    // all-or-nothing: a failure part-way (out of memory) leaves every buffer freed and the capacity at zero, never a
-    // capacity that some buffer does not have
-    const size_t old = s.lvl_cap;
-    s.lvl_cap = 0;
-    int st = UGSM_OK;
-    float **bufs[5] = {&s.A, &s.d0, &s.d1, &s.Rw, &s.B};
-    const int nb = ctx->cfg.kernel_path == 1 ? 5 : 3;
-    for (int k = 0; k < nb && st == UGSM_OK; k++) {
-        size_t c = old;
-        st = grow(ctx, *bufs[k], c, lvl);
-    }
-    if (st != UGSM_OK) {
-        for (int k = 0; k < nb; k++) {
-            if (*bufs[k]) {
-                untrack(ctx, *bufs[k]);
-                (void)hipFree(*bufs[k]);
-            }
-            *bufs[k] = nullptr;
-        }
-        return st;
-    }
-    s.lvl_cap = lvl;
-    return UGSM_OK;
+    if (ctx->cfg.kernel_path == 1) return s.lvl_cap.grow(ctx, lvl, {&s.A, &s.d0, &s.d1, &s.Rw, &s.B});
+    return s.lvl_cap.grow(ctx, lvl, {&s.A, &s.d0, &s.d1});
 }
 
-// the page-locked words the LR checks' counts come back in
+// the LR buffer with room for `floats`, and the page-locked words the LR checks' counts come back in
 constexpr size_t kLrHostWords = 1 + (size_t)kMaxBatch * UGSM_MAX_LEVELS;
-int lr_host_ready(ugsm_ctx *ctx, Slot &s)
+int lr_ready(ugsm_ctx *ctx, Slot &s, size_t floats)
 {
-    if (!s.lr_host) HIPCHK(ctx, hipHostMalloc((void **)&s.lr_host, kLrHostWords * sizeof(unsigned long long), hipHostMallocDefault));
-    return UGSM_OK;
-}
-
-// the slot's pyramids and level buffers for `cap_pairs` pairs (both pyramids or neither; level buffers all or nothing)
-static int alloc_slot_buffers(ugsm_ctx *ctx, Slot &s, int cap_pairs, size_t tot, size_t lvl)
-{
-    const size_t pyr_need = cap_pairs > 1 ? s.pyr_stride * cap_pairs : tot;
-    if (pyr_need > s.pyr_cap) {
-        // both or neither: a failure leaves the slot without pyramids and the capacity at zero (never a capacity one of them lacks)
-        size_t capL = s.pyr_cap, capR = s.pyr_cap;
-        s.pyr_cap = 0;
-        int st = grow(ctx, s.pyrL, capL, pyr_need);
-        if (st == UGSM_OK) st = grow(ctx, s.pyrR, capR, pyr_need);
-        if (st != UGSM_OK) {
-            for (float **b : {&s.pyrL, &s.pyrR}) {
-                if (*b) {
-                    untrack(ctx, *b);
-                    (void)hipFree(*b);
-                }
-                *b = nullptr;
-            }
-            return st;
-        }
-        s.pyr_cap = pyr_need;
-    }
-    return ensure_level_bufs(ctx, s, cap_pairs > 1 ? s.lvl_stride * cap_pairs : lvl);
+    UCHK(s.lr.grow(ctx, floats));
+    return s.lr_host.grow(ctx, kLrHostWords);
 }
 
 int prepare_slot(ugsm_ctx *ctx, Slot &s, int W, int H, int nb)
@@ -239,26 +192,18 @@ int prepare_slot(ugsm_ctx *ctx, Slot &s, int W, int H, int nb)
     for (int cap_pairs : {want_pairs, nb}) {
         // (the configured batch did not fit last time, nothing has been released since and this call does not need it: straight to the call's
         // own size -- no hipFree / failing hipMalloc / hipFree / hipMalloc of gigabytes, each a device-wide synchronisation, per call)
-        if (cap_pairs > nb && s.nomem_pairs > 0 && cap_pairs >= s.nomem_pairs && s.nomem_tot == tot && s.nomem_epoch == ctx->release_epoch) continue;
-        st = alloc_slot_buffers(ctx, s, cap_pairs, tot, lvl);
+        if (cap_pairs > nb && s.nomem_pairs > 0 && cap_pairs >= s.nomem_pairs && s.nomem_tot == tot && s.nomem_epoch == ctx->book.release_epoch) continue;
+        // the slot's pyramids and level buffers for `cap_pairs` pairs (both pyramids or neither; level buffers all or nothing)
+        st = s.pyr_cap.grow(ctx, cap_pairs > 1 ? s.pyr_stride * cap_pairs : tot, {&s.pyrL, &s.pyrR});
+        if (st == UGSM_OK) st = ensure_level_bufs(ctx, s, cap_pairs > 1 ? s.lvl_stride * cap_pairs : lvl);
         if (st != UGSM_ERR_NOMEM) break;
         // out of memory: what the attempt (or an earlier, larger call) left in the slot goes back before anything else is tried, so that a
         // refused call never keeps memory it cannot use (the slot's stream has drained its earlier work by then: hipFree waits for it)
-        const std::string why = ctx->err;
-        float **bufs[7] = {&s.pyrL, &s.pyrR, &s.A, &s.d0, &s.d1, &s.Rw, &s.B};
-        for (float **b : bufs) {
-            if (*b) {
-                untrack(ctx, *b);
-                (void)hipFree(*b);
-            }
-            *b = nullptr;
-        }
-        s.pyr_cap = 0;
-        s.lvl_cap = 0;
-        ctx->err = why;
+        s.pyr_cap.release(ctx, {&s.pyrL, &s.pyrR});
+        s.lvl_cap.release(ctx, {&s.A, &s.d0, &s.d1, &s.Rw, &s.B});
         s.nomem_pairs = cap_pairs;
         s.nomem_tot = tot;
-        s.nomem_epoch = ctx->release_epoch;  // (after this attempt's own releases)
+        s.nomem_epoch = ctx->book.release_epoch;  // (after this attempt's own releases)
         if (cap_pairs == nb) break;
     }
     return st;
@@ -411,7 +356,7 @@ int ugsm_create(const ugsm_config *cfg_in, ugsm_ctx **out)
     ctx->hooks.checked_submit = queue_checked_submit;  // (... and to the checked full-mode call)
     ctx->hooks.checked_marked = queue_checked_marked;
     set_policy(ctx, knobs);
-    if (dev_env() && getenv("UGSM_MEM_LIMIT_MB")) ctx->mem_limit = atoll(getenv("UGSM_MEM_LIMIT_MB")) << 20;
+    if (dev_env() && getenv("UGSM_MEM_LIMIT_MB")) ctx->book.mem_limit = atoll(getenv("UGSM_MEM_LIMIT_MB")) << 20;
     // The side stream pays when a pair is alone on the chip (115.6 against 113.9 pairs/s at 16 MP: the right pyramid and the A planes run
     // beside the left pyramid and the coarse levels; profiles/r06_ab_alone.txt).  With four pairs in flight USING theirs it loses 13 % (136
     // against 157 pairs/s): eight streams on the four hardware queues serialise kernels that one stream per pair lets overlap.  So every
@@ -442,7 +387,7 @@ int ugsm_create(const ugsm_config *cfg_in, ugsm_ctx **out)
         const char pc = knobs.stream_prio[0] ? (si < (int)strlen(knobs.stream_prio) ? knobs.stream_prio[si] : 'n') : by_cfg;
         const int prio = pc == 'h' ? prio_greatest : (pc == 'l' ? prio_least : 0);
         bool ok = (!s.owns_st || hipStreamCreateWithPriority(&s.st, hipStreamNonBlocking, prio) == hipSuccess) &&
-                  hipMalloc((void **)&s.range_bad, 2 * kMaxBatch * sizeof(unsigned)) == hipSuccess && hipEventCreateWithFlags(&s.ev_done, hipEventDisableTiming) == hipSuccess;
+                  s.range_bad.grow(ctx, 2 * (size_t)kMaxBatch) == UGSM_OK && hipEventCreateWithFlags(&s.ev_done, hipEventDisableTiming) == hipSuccess;
         s.prio = prio;
         for (hipEvent_t *e : {&s.ev_in, &s.ev_L, &s.ev_R}) ok = ok && hipEventCreateWithFlags(e, hipEventDisableTiming) == hipSuccess;
         for (int i = 0; i < cfg.levels; i++) ok = ok && hipEventCreateWithFlags(&s.ev_A[i], hipEventDisableTiming) == hipSuccess;
@@ -510,29 +455,9 @@ void ugsm_destroy(ugsm_ctx *ctx)
         if (s.st) (void)hipStreamSynchronize(s.st);
         if (s.st2) (void)hipStreamSynchronize(s.st2);
         harvest(ctx, s);
-        for (hipEvent_t e : s.pool) (void)hipEventDestroy(e);
-        for (void *p : {(void *)s.pyrL, (void *)s.pyrR, (void *)s.A, (void *)s.Rw, (void *)s.B, (void *)s.d0, (void *)s.d1,
-                        (void *)s.rgbL, (void *)s.rgbR, (void *)s.hout, (void *)s.range_bad, (void *)s.d2, (void *)s.wd_rows, (void *)s.res_rows})
-            if (p) (void)hipFree(p);
-        if (s.wd_host) (void)hipHostFree(s.wd_host);
-        if (s.hpin) (void)hipHostFree(s.hpin);
-        for (hipEvent_t e : s.out_ev)
-            if (e) (void)hipEventDestroy(e);
-        for (hipEvent_t e : {s.ev_in, s.ev_L, s.ev_R})
-            if (e) (void)hipEventDestroy(e);
-        for (hipEvent_t e : s.ev_A)
-            if (e) (void)hipEventDestroy(e);
-        if (s.Apyr) (void)hipFree(s.Apyr);
-        if (s.lr) (void)hipFree(s.lr);
-        s.cloud.release();
-        if (s.lr_host) (void)hipHostFree(s.lr_host);
-        if (s.warm_tab) (void)hipFree(s.warm_tab);
-        if (s.warm_tab_h) (void)hipHostFree(s.warm_tab_h);
-        for (hipEvent_t e : s.warm_ev)
-            if (e) (void)hipEventDestroy(e);
+        s.release(ctx);
         if (s.st2 && s.owns_st2) (void)hipStreamDestroy(s.st2);
         if (s.st && s.owns_st) (void)hipStreamDestroy(s.st);
-        if (s.ev_done) (void)hipEventDestroy(s.ev_done);
     }
     delete ctx;
 }
@@ -739,7 +664,7 @@ int ugsm_set_profile_events(ugsm_ctx *ctx, int mode)
     return UGSM_OK;
 }
 
-long long ugsm_context_device_bytes(const ugsm_ctx *ctx) { return ctx ? ctx->dev_bytes : -1; }
+long long ugsm_context_device_bytes(const ugsm_ctx *ctx) { return ctx ? ctx->book.dev_bytes : -1; }
 
 int ugsm_dev_alloc(ugsm_ctx *ctx, void **d_ptr, long long bytes)
 {

@@ -8,21 +8,23 @@
 //   ugsm_host.cpp     everything that touches caller host memory: the host team, staging, the blocking service calls
 //   ugsm_stages.cpp   the stage-level entry points (tests only)
 //   ugsm_cloud.cpp    the clouds;  ugsm_warp.cpp  the warped right image and the photometric residual
+//   ugsm_mem.hpp     the slot's memory as owning types (DevBuf, GroupCap, PinnedBuf, UploadRing) and the context's accounting (MemBook): host only
 // (The layers above the slot API -- queue, shard -- and the tests' fake runtimes compile against ugsm_internal.hpp, which needs no HIP.)
 #pragma once
 
 #include "ugsm_internal.hpp"
 #include "ugsm_launch.hpp"
+#include "ugsm_mem.hpp"
 
 #include <algorithm>
 #include <cstdio>
 #include <memory>
 #include <string>
-#include <unordered_map>
 #include <vector>
 
 namespace ugsm {
 
+static_assert(kMemOk == UGSM_OK && kMemErrDevice == UGSM_ERR_DEVICE && kMemErrNoMem == UGSM_ERR_NOMEM, "ugsm_mem.hpp and include/ugsm.h disagree on the status codes");
 constexpr double kScale = 1.41421356;  // MatchLib_common.h:15
 enum KClass { KC_COST = 0, KC_SMOOTH, KC_SQBLUR, KC_PYR, KC_SEED, KC_WARP, KC_BOX, KC_MISC, KC_COST_MARCH, KC_PYR_BASE, KC_COST_SMALL, KC_SMOOTH_SMALL, KC_COST_MARCH4,
               KC_LEVEL0_WIN, KC_RESTRICT, KC_RESTRICT_STACK, KC_PROLONG, KC_COUNT };
@@ -40,39 +42,24 @@ struct EvRec {
 
 // Row f-1, the clouds (ugsm_cloud.cpp)
 struct SlotCloud {
-    unsigned *cnt = nullptr;  // a compact cloud: per (column, chunk) counts + column and strip totals (CloudArgs.cnt)
-    size_t cnt_cap = 0;
+    DevBuf<unsigned> cnt;  // a compact cloud: per (column, chunk) counts + column and strip totals (CloudArgs.cnt)
     // The queue's cloud calls (queue_cloud_submit / queue_cloud_finish): the table of the call's batched cloud launch -- in device memory, and
     // the page-locked copy it is uploaded from on the slot's stream (rewritten only by the slot's next call, i.e. after this one has finished);
     // managed calls: the device clouds of the pairs (pair b at cq_pts + b * cq_stride bytes, cq_cap[b] records of cq_step bytes), their count
     // words (kCqWords per pair: the count, then the level counts) and the page-locked words those come down to with the call
-    CloudPair *cq_tab = nullptr, *cq_tab_h = nullptr;
-    size_t cq_tab_cap = 0;
-    char *cq_pts = nullptr;
-    size_t cq_pts_cap = 0, cq_stride = 0;
-    long long *cq_words = nullptr, *cq_words_h = nullptr;
-    size_t cq_words_cap = 0;
+    DevBuf<CloudPair> cq_tab;
+    PinnedBuf<CloudPair> cq_tab_h;
+    DevBuf<char> cq_pts;
+    size_t cq_stride = 0;
+    DevBuf<long long> cq_words;
+    PinnedBuf<long long> cq_words_h;
     long long cq_cap[kMaxBatch] = {};
     int cq_n = 0, cq_step = 0, cq_levels = 0;  // the managed cloud call in flight: pairs, bytes per record, fovea levels (0: full mode)
-    // The merged cloud of several windows (ugsm_point_cloud_fovea_multi): its table of entries in device memory, and the page-locked copies
-    // it is uploaded from on the slot's stream.  The call does not wait for the stream, so a copy may still be read by an earlier call's
-    // upload when the next call is made: kMcRing copies take turns, each with an event behind its upload, and a call waits only for the
-    // UPLOAD of the call kMcRing before it.
-    static constexpr int kMcRing = 4;
-    CloudEntry *mc_tab = nullptr, *mc_tab_h = nullptr;
-    size_t mc_tab_cap = 0, mc_tab_h_rows = 0;  // rows of the device table; rows of each page-locked copy
-    hipEvent_t mc_ev[kMcRing] = {};
-    bool mc_ev_set[kMcRing] = {};
-    int mc_next = 0;
-    void release()  // everything above goes back (ugsm_destroy: the slot's stream has drained)
-    {
-        for (void *p : {(void *)cnt, (void *)cq_tab, (void *)cq_pts, (void *)cq_words, (void *)mc_tab})
-            if (p) (void)hipFree(p);
-        for (void *p : {(void *)cq_tab_h, (void *)cq_words_h, (void *)mc_tab_h})
-            if (p) (void)hipHostFree(p);
-        for (hipEvent_t e : mc_ev)
-            if (e) (void)hipEventDestroy(e);
-    }
+    // The merged cloud of several windows (ugsm_point_cloud_fovea_multi): its table of entries, sized by the call's entries.  The call does
+    // not wait for the stream: hence the ring.
+    UploadRing<CloudEntry> mc;
+    template <class Ctx>
+    void release(Ctx *ctx) { release_all(ctx, cnt, cq_tab, cq_tab_h, cq_pts, cq_words, cq_words_h, mc); }  // (ugsm_destroy: the slot's stream has drained)
 };
 
 struct Slot {
@@ -80,8 +67,8 @@ struct Slot {
     int W = 0, H = 0, levels = 0;
     int w[UGSM_MAX_LEVELS], h[UGSM_MAX_LEVELS];
     size_t off[UGSM_MAX_LEVELS];  // float offset of level i inside pyrL/pyrR
-    float *pyrL = nullptr, *pyrR = nullptr;
-    size_t pyr_cap = 0;  // floats
+    DevBuf<float> pyrL, pyrR;
+    GroupCap pyr_cap;  // (pyrL, pyrR), floats
     // Batch (round 4): the call in flight matches `nb` pairs of one size in lockstep.  Every per-pair buffer of the slot holds nb copies:
     // pair b's pyramids at pyrL / pyrR + b * pyr_stride, its level buffers (A, d0, d1) at + b * lvl_stride, its range word at range_bad + b.
     // nb and the strides describe the call's REAL pairs and are set by prepare_slot alone (the stage entry points, which bring one field of
@@ -90,7 +77,7 @@ struct Slot {
     // the call's sequence hands down (Shape, below), never written here.
     int nb = 1;
     size_t pyr_stride = 0, lvl_stride = 0;  // floats
-    float *A = nullptr, *Rw = nullptr, *B = nullptr, *d0 = nullptr, *d1 = nullptr;
+    DevBuf<float> A, Rw, B, d0, d1;
     // Side stream of the slot (round 3): the right image's upload and pyramid, and then A = G_clamp * L^2 of every full-frame level
     // (MatchGPULib.cpp:1866-1875, once per level), run there beside the left pyramid and the coarse levels' iterations -- launches
     // that last microseconds and depend on nothing but the left pyramid.  The main stream joins it through events: ev_R before the
@@ -112,32 +99,25 @@ struct Slot {
     bool busy = false;   // a call has been enqueued here and neither ugsm_wait nor ugsm_poll has seen it finish (get_slot / slot_idle)
     bool alone = true;   // the call in flight had the chip to itself when it was submitted (call_alone): what the kernel choices follow
     hipEvent_t ev_in = nullptr, ev_L = nullptr, ev_R = nullptr, ev_A[UGSM_MAX_LEVELS] = {};
-    float *lr = nullptr;     // LR check: the right-to-left field of level 0 (3 planes) + one 8-byte counter behind it
-    size_t lr_cap = 0;
-    unsigned long long *lr_host = nullptr;  // page-locked copies: word 0 the full-mode counter, then one word per (pair, level) of a checked foveated call
+    DevBuf<float> lr;        // LR check: the right-to-left field of level 0 (3 planes) + one 8-byte counter behind it
+    PinnedBuf<unsigned long long> lr_host;  // page-locked copies: word 0 the full-mode counter, then one word per (pair, level) of a checked foveated call
     bool lr_ran = false;
     int lr_full_pairs = 0;  // read with lr_ran: the last call was ugsm_submit_full_checked on this many pairs, word 1 + 2 b + direction of lr_host pair b's count (0: word 0)
     int lr_fov_pairs = 0, lr_fov_F = 0;  // the last call on the slot ran the foveated check on this many pairs of this many levels (0: it did not)
-    float *Apyr = nullptr;   // A of level i at Apyr + off[i] (same layout as the pyramids)
-    size_t apyr_cap = 0;
+    DevBuf<float> Apyr;      // A of level i at Apyr + off[i] (same layout as the pyramids)
     int a_from = -1;         // levels a_from .. top have their A in Apyr (ev_A recorded); -1: none (A is computed in line)
-    size_t lvl_cap = 0;  // floats per 3-plane level buffer
-    uint8_t *rgbL = nullptr, *rgbR = nullptr;
-    size_t rgb_cap = 0;
-    float *d2 = nullptr;            // third (dx,dy,conf) buffer: only with early_exit_threshold > 0 (the previous iteration's field must survive)
-    size_t d2_cap = 0;
-    double *wd_rows = nullptr;      // row f-4 scratch: 3 doubles per row + 3 totals
-    size_t wd_cap = 0;
-    double *wd_host = nullptr;      // page-locked, 3 doubles
+    GroupCap lvl_cap;  // (A, d0, d1[, Rw, B]: the last two under kernel_path 1), floats per 3-plane level buffer
+    DevBuf<uint8_t> rgbL, rgbR;
+    GroupCap rgb_cap;  // (rgbL, rgbR), bytes
+    DevBuf<float> d2;               // third (dx,dy,conf) buffer: only with early_exit_threshold > 0 (the previous iteration's field must survive)
+    DevBuf<double, false> wd_rows;  // row f-4 scratch: 3 doubles per row + 3 totals (not counted)
+    PinnedBuf<double> wd_host;      // 3 doubles
     SlotCloud cloud;                // row f-1, the clouds
-    double *res_rows = nullptr;     // the photometric residual (ugsm_warp.cpp): 4 doubles per row and level, grown on demand (grow: counted)
-    size_t res_cap = 0;
+    DevBuf<double> res_rows;        // the photometric residual (ugsm_warp.cpp): 4 doubles per row and level, grown on demand
     int iters_run[UGSM_MAX_LEVELS];
-    unsigned *range_bad = nullptr;  // device word: 0 while every pyramid value of the pair in this slot passed range_ok (ugsm_exact.hpp)
-    float *hout = nullptr;  // device staging for host-API outputs
-    size_t hout_cap = 0;
-    float *hpin = nullptr;  // page-locked host staging for host-API outputs that land in pageable caller memory
-    size_t hpin_cap = 0;
+    DevBuf<unsigned, false> range_bad;  // (ugsm_create; not counted) device word: 0 while every pyramid value of the pair in this slot passed range_ok (ugsm_exact.hpp)
+    DevBuf<float> hout;     // device staging for host-API outputs
+    PinnedBuf<float> hpin;  // host staging for host-API outputs that land in pageable caller memory
     hipEvent_t out_ev[12] = {};  // one per piece of the pageable copy-out (copy_out_planes)
     // out of memory for the configured batch (prepare_slot): the capacity that failed, for which geometry, and the context's release
     // count then -- the attempt is not repeated until something has been released or a call needs that much
@@ -151,19 +131,27 @@ struct Slot {
     bool direct0 = false;
     const uint8_t *img0L[kMaxBatch] = {}, *img0R[kMaxBatch] = {};
     int img0_stride = 0;
-    // The warm foveated call (ugsm_submit_foveated_warm) with more entries than travel in its launch's arguments: their rows in device memory
-    // (kMaxBatch of them) and the page-locked copies they are uploaded from on the slot's stream, allocated by the first such call.  The call
-    // does not wait for the stream, so kWarmRing copies take turns, each with an event behind its upload, as SlotCloud::mc_tab_h.
-    static constexpr int kWarmRing = 4;
-    RestrictStackRow *warm_tab = nullptr, *warm_tab_h = nullptr;
-    size_t warm_tab_cap = 0;
-    hipEvent_t warm_ev[kWarmRing] = {};
-    bool warm_ev_set[kWarmRing] = {};
-    int warm_next = 0;
+    // The warm foveated call (ugsm_submit_foveated_warm) with more entries than travel in its launch's arguments: their rows, kMaxBatch of
+    // them, made by the first such call.  The call does not wait for the stream: hence the ring.
+    UploadRing<RestrictStackRow> warm;
     bool range_known = false;  // range_bad describes the images the next run_level works on
     int cur_level = kNoLevel;  // pyramid level the launches being enqueued belong to (statistics only)
     std::vector<EvRec> pending;
     std::vector<hipEvent_t> pool;
+    // Every buffer and event above goes back (ugsm_destroy alone: the device set, the streams drained and, afterwards, destroyed there)
+    template <class Ctx>
+    void release(Ctx *ctx)
+    {
+        pyr_cap.release(ctx, {&pyrL, &pyrR});
+        lvl_cap.release(ctx, {&A, &d0, &d1, &Rw, &B});
+        rgb_cap.release(ctx, {&rgbL, &rgbR});
+        release_all(ctx, lr, Apyr, d2, hout, wd_rows, res_rows, range_bad, lr_host, wd_host, hpin, cloud, warm);
+        for (hipEvent_t *e : {&ev_done, &ev_in, &ev_L, &ev_R}) destroy_event(*e);
+        for (hipEvent_t &e : ev_A) destroy_event(e);
+        for (hipEvent_t &e : out_ev) destroy_event(e);
+        for (hipEvent_t &e : pool) destroy_event(e);
+        pool.clear();
+    }
 };
 class HostTeam;  // (ugsm_host.cpp)
 
@@ -188,25 +176,11 @@ struct ugsm_ctx {
     float lr_tau = 0.0f;  // the LR check (ugsm_set_lr_check; ugsm_create: ugsm_config.lr_check_threshold, UGSM_LR_FULL): the threshold ...
     int lr_modes = 0;     // ... and the calls that apply it (UGSM_LR_*)
     ugsm::CtxHooks hooks;  // the queue (ugsm_queue.cpp) and the RCCL shard (ugsm_shard.cpp): layers over the slot API
-    long long dev_bytes = 0;    // device memory held by the slots' growable buffers (grow); ugsm_context_device_bytes
-    std::unordered_map<const void *, size_t> dev_allocs;  // ... buffer by buffer, so that every release is accounted whatever path it takes
-    long long release_epoch = 0;  // counts the releases of tracked device buffers (untrack): "memory may have come free since"
+    ugsm::MemBook book;  // the device memory the slots' counted buffers hold, and the development limit on it (ugsm_mem.hpp)
     bool counted_live = false;  // this context counts in g_live_contexts (ugsm_create got as far as handing it out)
-    long long mem_limit = 0;    // development (UGSM_MEM_LIMIT_MB under UGSM_DEV=1): grow refuses to go past it -- the UGSM_ERR_NOMEM path without exhausting a GPU
     ugsm_ctx();
     ~ugsm_ctx();  // (both in ugsm_host.cpp: where HostTeam is whole)
 };
-
-#define HIPCHK(ctx, call)                                                                             \
-    do {                                                                                              \
-        hipError_t e__ = (call);                                                                      \
-        if (e__ != hipSuccess) {                                                                      \
-            char b__[512];                                                                            \
-            snprintf(b__, sizeof b__, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e__), __FILE__, __LINE__); \
-            (ctx)->err = b__;                                                                         \
-            return UGSM_ERR_DEVICE;                                                                   \
-        }                                                                                             \
-    } while (0)
 
 #define UCHK(call)                       \
     do {                                 \
@@ -222,41 +196,6 @@ struct FoveaGeom {
     int ox[UGSM_MAX_LEVELS], oy[UGSM_MAX_LEVELS];  // crop origin at level lev < F-1
     int cx[UGSM_MAX_LEVELS], cy[UGSM_MAX_LEVELS];  // seed-crop origin for transition lev+1 -> lev
 };
-
-inline void untrack(ugsm_ctx *ctx, const void *p)
-{
-    auto it = ctx->dev_allocs.find(p);
-    if (it == ctx->dev_allocs.end()) return;
-    ctx->dev_bytes -= (long long)it->second;
-    ctx->dev_allocs.erase(it);
-    ctx->release_epoch++;
-}
-
-template <class T>
-int grow(ugsm_ctx *ctx, T *&p, size_t &cap, size_t need)
-{
-    if (need <= cap) return UGSM_OK;
-    if (p) {
-        untrack(ctx, p);
-        HIPCHK(ctx, hipFree(p));
-    }
-    p = nullptr;
-    cap = 0;
-    hipError_t e = (ctx->mem_limit > 0 && ctx->dev_bytes + (long long)(need * sizeof(T)) > ctx->mem_limit) ? hipErrorOutOfMemory
-                                                                                                          : hipMalloc((void **)&p, need * sizeof(T));
-    if (e != hipSuccess) {
-        (void)hipGetLastError();  // (the failed allocation must not poison the next launch check)
-        char b[256];
-        snprintf(b, sizeof b, "hipMalloc of %zu bytes failed: %s (the context holds %lld bytes)", need * sizeof(T), hipGetErrorString(e), ctx->dev_bytes);
-        ctx->err = b;
-        p = nullptr;
-        return UGSM_ERR_NOMEM;
-    }
-    cap = need;
-    ctx->dev_bytes += (long long)(need * sizeof(T));
-    ctx->dev_allocs[p] = need * sizeof(T);
-    return UGSM_OK;
-}
 
 // ---- event bookkeeping -----------------------------------------------------------------
 struct Timer {
@@ -483,7 +422,7 @@ inline int input_status(const ugsm_ctx *ctx, int W, int stride, const void *a = 
     return input_image_status(ctx->hooks.input_format, W, stride, a, b);
 }
 int ensure_level_bufs(ugsm_ctx *ctx, Slot &s, size_t lvl);
-int lr_host_ready(ugsm_ctx *ctx, Slot &s);
+int lr_ready(ugsm_ctx *ctx, Slot &s, size_t floats);
 int prepare_slot(ugsm_ctx *ctx, Slot &s, int W, int H, int nb = 1);
 int check_config(const ugsm_config &cfg);
 int get_slot(ugsm_ctx *ctx, int slot, Slot **out, bool enqueues = true);

@@ -166,9 +166,8 @@ int ugsm_stage_lr_check(ugsm_ctx *ctx, float *d_left3, const float *d_right3, in
     UCHK(get_slot(ctx, 0, &s));
     if (!d_left3 || !d_right3 || W < 1 || H < 1 || H > 65535 || (long long)W * H > kMaxPixels || !(tau >= 0.0f)) return UGSM_ERR_BAD_ARG;
     HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
-    UCHK(grow(ctx, s->lr, s->lr_cap, std::max<size_t>(s->lr_cap, 8)));
-    UCHK(lr_host_ready(ctx, *s));
-    unsigned long long *cnt = reinterpret_cast<unsigned long long *>(s->lr);
+    UCHK(lr_ready(ctx, *s, std::max<size_t>(s->lr.cap, 8)));
+    unsigned long long *cnt = reinterpret_cast<unsigned long long *>(s->lr.p);
     HIPCHK(ctx, hipStreamSynchronize(s->st));  // (the counter shares the slot's LR buffer)
     HIPCHK(ctx, hipMemsetAsync(cnt, 0, sizeof *cnt, s->st));
     launch_lr_check(s->st, d_left3, d_right3, W, H, tau, cnt);

@@ -21,9 +21,9 @@ int warp_begin(ugsm_ctx *ctx, int slot, Slot **out, size_t rows = 0)
     UCHK(get_slot(ctx, slot, out));
     Slot &s = **out;
     HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
-    if (4 * rows > s.res_cap) {
+    if (4 * rows > s.res_rows.cap) {
         HIPCHK(ctx, hipStreamSynchronize(s.st));  // (an earlier residual may still read the buffer being replaced)
-        UCHK(grow(ctx, s.res_rows, s.res_cap, 4 * rows));
+        UCHK(s.res_rows.grow(ctx, 4 * rows));
     }
     return UGSM_OK;
 }
