@@ -46,7 +46,9 @@ extern "C" {
                                the full-mode call in two halves -- ugsm_submit_full_coarse, ugsm_submit_full_fine, ugsm_match_full_coarse,
                                ugsm_match_full_fine, ugsm_stage_prolong, ugsm_coarse_pixel_iterations; checked full-mode pairs through the queue --
                                ugsm_submit_full_checked_host, ugsm_enqueue_full_checked, ugsm_enqueue_full_checked_managed,
-                               ugsm_enqueue_full_checked_cloud, ugsm_enqueue_full_checked_cloud_managed, ugsm_checked_result, ugsm_done_checked
+                               ugsm_enqueue_full_checked_cloud, ugsm_enqueue_full_checked_cloud_managed, ugsm_checked_result, ugsm_done_checked;
+                               the depth image (REP 118 32FC1 / 16UC1) -- ugsm_depth_params, UGSM_DEPTH_32F / UGSM_DEPTH_16U / UGSM_DEPTH_ALL_LEVELS,
+                               ugsm_default_depth_params, ugsm_depth_image_size, ugsm_depth_image, ugsm_depth_image_fovea, ugsm_match_full_depth
                                6: the kernel choices follow what is in flight, not ugsm_config.slots: ugsm_plan_level takes `alone`, ugsm_plan_level_in_frame
                                is gone, ugsm_level_plan.latency_policy is .alone; ugsm_enqueue_* returns UGSM_OK once the pair is accepted (a failed
                                CALL is reported through ugsm_completion.status only); the fovea shard carries a status word (a rank that fails still
@@ -931,6 +933,74 @@ int ugsm_point_cloud_resized_fovea(ugsm_ctx *ctx, int slot, const float *d_stack
                                    int fovW, int fovH, int src_level, int left_margin, int upper_margin, float scale,
                                    const uint8_t *d_rgbL, int W, int H, int stride, const double *P1, const double *P2, float factor,
                                    int colour_mapped, const ugsm_cloud_params *p, void *d_points, long long cap_points, long long *d_count);
+
+/* ---- row f-1, the depth image: REP 118 32FC1 / 16UC1 ----------------------------------------------------------------------------------
+ *
+ * The one intermediate the reference's point-cloud node builds explicitly: doReconstruction_resized / doReconstructionFOV_resized fill a
+ * range_map with the Z of get3DPoint, pixel for pixel and row-major, and cv::resize it to res_range_map (getPointCloud.cpp:730-758,
+ * :813-841, :951-1021).  These calls hand that map out as the depth image REP 118 defines, registered to the left camera: row-major and
+ * contiguous, dw x dh elements of 4 or 2 bytes -- the payload of a sensor_msgs/Image with step = dw * size.
+ *
+ * Per pixel, in this order, every operation in binary32 and rounded on its own:
+ *   Z      factor == 1: the image is pw x ph (W x H; the fovea form: fovW x fovH) and Z is bit for bit the Z that ugsm_triangulate
+ *          (ugsm_triangulate_fovea with ugsm_fovea_level_mapping's numbers) writes for the pixel.  factor < 1: the image is dw x dh =
+ *          (int)((float)pw * factor) x (int)((float)ph * factor), ugsm_depth_image_size, and Z of (ii, jj) is bit for bit the z of record
+ *          (ii, jj) of ugsm_point_cloud_resized[_fovea] -- the same taps, coefficients, sum order and border rule, the same copy at an
+ *          unchanged size; the confidence is read at (xx, yy), xx = (int)((float)ii / factor), yy = (int)((float)jj / factor), as there.
+ *   valid  Z finite, z_min <= Z <= z_max, and (d_conf NULL or conf >= min_conf; a NaN confidence fails).  X and Y play no part.
+ *   32F    m = Z * unit; stored where valid, else the quiet NaN 0x7FC00000.  With the default parameters every finite Z is stored as it is.
+ *   16U    u = (m * 1000.0f) + 0.5f; valid additionally requires u >= 1.0f && u < 65536.0f; (uint16_t)u (truncation) where valid, else 0.
+ * *d_valid (device, 8-byte aligned, may be NULL) receives the number of valid pixels stored; the call zeroes it on the slot's stream.  It is
+ * a sum of integers (ballots and popcounts, one integer atomic per workgroup), the same from run to run.
+ *
+ * unit: metres per unit of Z, that is, of the calibration's translation (P2[0][3] / P2[0][0] is the baseline in that unit).
+ *
+ * Memory: d_depth (device) need only be aligned to its element, the planes to 4 bytes (plane 1 of a d_out starts at 4 W H bytes); nothing is
+ * written outside [d_depth, d_depth + images * dw * dh * size).  d_depth must not overlap d_dispx / d_dispy / d_conf (the stacks).
+ *
+ * ugsm_depth_image_fovea: d_stackx / d_stacky / d_stackc are the (F*fovH) x fovW stacks of a foveated call on a W x H frame with the
+ * window offset (off_x, off_y); levels and fovea_levels are the context's, each level mapped with ugsm_fovea_level_mapping.  level in
+ * 0 .. F-1: that level's image.  UGSM_DEPTH_ALL_LEVELS: every level in ONE launch, the images laid out as stackH is -- (F * dh) x dw,
+ * level 0 first -- and d_valid holds F counts.  A fovea level converts xx + disparity with (int), as the reference does: for a NaN
+ * disparity or one beyond the range of int that conversion is undefined, as it is for ugsm_triangulate_fovea and the fovea clouds.
+ *
+ * ugsm_match_full_depth: the blocking call, ugsm_match_full followed by ugsm_depth_image on the same slot (slot 0).  `depth` (host memory
+ * of any kind) receives the image; each of dispH / dispV / dispC may be NULL and is then not downloaded: with all three NULL only the depth
+ * image crosses the bus.  d_conf is the match's confidence plane.  The images are read in the context's input format.
+ *
+ * ugsm_depth_image[_fovea] are asynchronous on `slot`'s stream, like ugsm_triangulate -- so ordered behind a ugsm_submit_* on the same
+ * slot -- and make no host synchronisation.  UGSM_ERR_STATE: pairs enqueued with ugsm_enqueue_* are outstanding.  UGSM_ERR_BAD_ARG, before
+ * any device work: a null pointer (d_conf / d_stackc / d_valid excepted); d_conf NULL with min_conf above -inf; an unknown format; a unit
+ * that is not finite and > 0; a NaN min_conf / z_min / z_max, or z_min > z_max; a factor that is not finite and in (0, 1] or leaves a side
+ * 0; W or H < 1, or more than 2^28 pixels; a misaligned d_depth / d_valid / plane; d_depth overlapping an input; a bad slot or level; the
+ * fovea form on a context with fovea_levels < 2.
+ *
+ * Out of scope: queue forms (ugsm_enqueue_*_depth*); the depth image of several windows or of a reconstructed stack (compose
+ * ugsm_reconstruct_full[_multi] with ugsm_depth_image); a strided output; depth in the right camera; camera_info handling; undistortion. */
+#define UGSM_DEPTH_32F 0   /* REP 118 32FC1: float, NaN where there is no reading */
+#define UGSM_DEPTH_16U 1   /* REP 118 16UC1: uint16 millimetres, 0 where there is no reading */
+#define UGSM_DEPTH_ALL_LEVELS (-1)
+typedef struct ugsm_depth_params {
+    int   format;        /* UGSM_DEPTH_* */
+    float unit;          /* metres per unit of Z (the calibration's unit); > 0, finite */
+    float min_conf;      /* keep conf >= min_conf; -inf with d_conf NULL: no confidence test (the clouds' rule) */
+    float z_min, z_max;  /* keep z_min <= Z <= z_max, on Z itself (before unit) */
+    float factor;        /* 1.0f: the range map itself; in (0, 1): the reference's res_range_map */
+} ugsm_depth_params;
+/* UGSM_DEPTH_32F, unit 1.0f, min_conf -inf, z_min -inf, z_max +inf, factor 1.0f */
+void ugsm_default_depth_params(ugsm_depth_params *p);
+/* the image's size, the resized clouds' rule: (int)((float)pw * factor) x (int)((float)ph * factor).  Host only.  UGSM_ERR_BAD_ARG: a null
+ * output, pw or ph < 1, a factor that is not in (0, 1] or leaves a side 0. */
+int ugsm_depth_image_size(int pw, int ph, float factor, int *dw, int *dh);
+int ugsm_depth_image(ugsm_ctx *ctx, int slot, const float *d_dispx, const float *d_dispy, const float *d_conf, int W, int H,
+                     const double *P1, const double *P2, const ugsm_depth_params *p, void *d_depth,
+                     unsigned long long *d_valid);
+int ugsm_depth_image_fovea(ugsm_ctx *ctx, int slot, const float *d_stackx, const float *d_stacky, const float *d_stackc,
+                           int W, int H, int off_x, int off_y, int level, const double *P1, const double *P2,
+                           const ugsm_depth_params *p, void *d_depth, unsigned long long *d_valid);
+int ugsm_match_full_depth(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride,
+                          const double *P1, const double *P2, const ugsm_depth_params *p, void *depth, float *dispH,
+                          float *dispV, float *dispC);
 
 /* ---- the cloud from the queue: enqueue a pair, get its cloud back ------------------------------------------------------------------
  *

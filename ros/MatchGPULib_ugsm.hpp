@@ -317,6 +317,67 @@ public:
         return out;
     }
 
+    // (not in the reference's library: its point-cloud node fills range_map on the host, getPointCloud.cpp:730-758)  match(L, R, 0) and its
+    // REP 118 depth image registered to the left camera (ugsm_match_full_depth): p->format UGSM_DEPTH_32F -- float metres, NaN for no reading --
+    // or UGSM_DEPTH_16U -- uint16 millimetres, 0 for no reading; P1, P2 the 3x4 projection matrices, row-major.  Returns the image, malloc'd:
+    // *dw x *dh elements, row-major, the payload of a sensor_msgs::Image with step = *dw * size.  finDisp (may be null): where given, the match's
+    // planes come down too, as match returns them; otherwise only the image crosses the bus.
+    template <class ImgPtr>
+    void *depthImage(ImgPtr L, ImgPtr R, const double *P1, const double *P2, const ugsm_depth_params *p, int *dw, int *dh, float ***finDisp = nullptr)
+    {
+        if (finDisp) *finDisp = nullptr;
+        foveatedmatching = 0;
+        const int W = L->image.cols, H = L->image.rows;
+        if (!p || !dw || !dh || R->image.cols != W || R->image.rows != H || ugsm_depth_image_size(W, H, p->factor, dw, dh) != UGSM_OK) return nullptr;
+        void *img = std::malloc((size_t)*dw * *dh * (p->format == UGSM_DEPTH_16U ? 2 : 4));
+        float **fin = finDisp ? alloc_planes(3, (size_t)W * H) : nullptr;
+        const int st = img ? ugsm_match_full_depth(ctx_, L->image.data, R->image.data, W, H, (int)L->image.step, P1, P2, p, img, fin ? fin[0] : nullptr,
+                                                   fin ? fin[1] : nullptr, fin ? fin[2] : nullptr)
+                           : UGSM_ERR_NOMEM;
+        if (st != UGSM_OK) {
+            std::free(img);
+            if (fin) fail(fin, 3, st);
+            else report(st);
+            return nullptr;
+        }
+        if (finDisp) *finDisp = fin;
+        return img;
+    }
+    // ... and of a fovea stack as matchStack returns it (foveated[k][c] = fovW*fovH floats, c = 0, 1, 2: dx, dy, conf) for a rows x cols frame:
+    // every level's image in one launch (ugsm_depth_image_fovea, UGSM_DEPTH_ALL_LEVELS), laid out level after level, level 0 first --
+    // foveatelevel * *dh rows of *dw elements.  valid (may be null): foveatelevel counts of valid pixels.
+    void *depthImageStack(float ***foveated, int cols, int rows, const double *P1, const double *P2, const ugsm_depth_params *p, int *dw, int *dh,
+                          unsigned long long *valid = nullptr)
+    {
+        const int F = foveatelevel;
+        int fw = 0, fh = 0;
+        if (!foveated || !p || !dw || !dh || ugsm_fovea_dims(cols, rows, 14, F, &fw, &fh) != UGSM_OK ||
+            ugsm_depth_image_size(fw, fh, p->factor, dw, dh) != UGSM_OK)
+            return nullptr;
+        const size_t fn = (size_t)fw * fh, sn = (size_t)F * fn, bytes = (size_t)F * *dw * *dh * (p->format == UGSM_DEPTH_16U ? 2 : 4);
+        void *d_stack = nullptr, *d_img = nullptr, *d_valid = nullptr, *img = std::malloc(bytes);
+        int st = img ? ugsm_dev_alloc(ctx_, &d_stack, (long long)(3 * sn * sizeof(float))) : UGSM_ERR_NOMEM;
+        if (st == UGSM_OK) st = ugsm_dev_alloc(ctx_, &d_img, (long long)bytes);
+        if (st == UGSM_OK) st = ugsm_dev_alloc(ctx_, &d_valid, (long long)(F * sizeof(unsigned long long)));
+        for (int k = 0; k < F && st == UGSM_OK; k++)
+            for (int c = 0; c < 3 && st == UGSM_OK; c++)
+                st = ugsm_copy_to_device(ctx_, (float *)d_stack + c * sn + k * fn, foveated[k][c], (long long)(fn * sizeof(float)));
+        if (st == UGSM_OK)
+            st = ugsm_depth_image_fovea(ctx_, 0, (float *)d_stack, (float *)d_stack + sn, (float *)d_stack + 2 * sn, cols, rows, 0, 0, UGSM_DEPTH_ALL_LEVELS,
+                                        P1, P2, p, d_img, (unsigned long long *)d_valid);
+        if (st == UGSM_OK) st = ugsm_wait(ctx_, 0);
+        if (st == UGSM_OK) st = ugsm_copy_to_host(ctx_, img, d_img, (long long)bytes);
+        if (st == UGSM_OK && valid) st = ugsm_copy_to_host(ctx_, valid, d_valid, (long long)(F * sizeof(unsigned long long)));
+        for (void *q : {d_stack, d_img, d_valid})
+            if (q) ugsm_dev_free(ctx_, q);
+        if (st != UGSM_OK) {
+            std::free(img);
+            report(st);
+            return nullptr;
+        }
+        return img;
+    }
+
     // ---- the pipelined twin of match / matchStack / matchStackPyramid (not in the reference): include/ugsm.h, "the queue" ------------
     // The images are copied into page-locked staging memory of the library before the call returns (the cv_bridge image may be freed);
     // the result comes out of nextDone, in arrival order.  Every call flushes: a frame starts at once if a slot is free, and under load

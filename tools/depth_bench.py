@@ -1,0 +1,214 @@
+#!/usr/bin/env python3
+"""What the depth image costs (ugsm_depth_image, ugsm_match_full_depth), and what a host could do without it -- on ONE box, in one session.
+
+    python tools/depth_bench.py --parent-tree DIR [--rounds 3] [--out profiles/depth_bench.json]
+
+At 16 MP (4928 x 3264) and 1080p, 14 levels, events off.  Every measurement is a fresh child process (one context per process); the children
+of the parent build (DIR: a checkout of the parent commit with its libraries built) and of this build alternate, and the rounds repeat them.
+
+  a_parent / a_this   what a host can do on the parent commit: ugsm_triangulate on resident planes, the download of the Z plane, the 16UC1
+                      conversion in numpy (the rule of include/ugsm.h).  a_this is the same on this build: the X, Y, Z instruction streams
+                      did not move (tools/isa_dump.py --diff), so the two must agree within the spread.
+  b                   ugsm_depth_image 16U on the same planes plus the download of the image.
+  c_parent / c_this   ugsm_match_full from pageable memory: the blocking call, three planes down.
+  d                   ugsm_match_full_depth 16U with no planes: only the image crosses the bus.
+  kernel              the depth launches alone, a REGION as tools/warp_bench.py times it (`reps` calls of ugsm_depth_image through ctypes,
+                      enqueued back to back, and one ugsm_wait): 16U without a confidence plane (8 + 2 bytes a pixel) and 32F with one
+                      (12 + 4), each without d_valid and with it (`_count`: one hipMemsetAsync more per call, and the launch's one integer
+                      atomic per wave on one word), beside the HBM bound W * H * bytes / peak.
+
+Every child's value is kept; a row gives the median and the spread (max - min) of its children.  No number is fixed here: a ratio counts
+as a difference only where it exceeds the spread between children of one configuration."""
+import argparse
+import json
+import os
+import statistics
+import subprocess
+import sys
+import tempfile
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SIZES = {"16mp": (4928, 3264), "1080p": (1920, 1080)}
+LEVELS = 14
+CONFIGS = ["a_parent", "a_this", "b", "c_parent", "c_this", "d", "kernel"]
+HBM_PEAK_SPEC, HBM_PEAK_MEASURED = 8.0e12, 6.29e12   # bytes / s (tools/warp_bench.py)
+UNIT = 0.01                                          # a unit that puts the synthetic pair's depths inside the 16UC1 range
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--parent-tree", default=None, help="a checkout of the parent commit with its libraries built")
+ap.add_argument("--rounds", type=int, default=3)
+ap.add_argument("--reps", type=int, default=15)
+ap.add_argument("--warmup", type=int, default=4)
+ap.add_argument("--region", type=float, default=0.3, help="seconds a timed kernel region should last")
+ap.add_argument("--sizes", nargs="*", default=list(SIZES))
+ap.add_argument("--configs", nargs="*", default=None, help="the configurations to measure (default: all)")
+ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "depth_bench.json"))
+ap.add_argument("--child", default=None, help="(internal) the configuration to measure in this process")
+ap.add_argument("--size", default="16mp", help="(internal)")
+ap.add_argument("--tree", default=ROOT, help="(internal)")
+ap.add_argument("--images", default=None, help="(internal)")
+args = ap.parse_args()
+
+
+def rig():
+    import numpy as np
+    P1 = np.array([[7.3230899280915291e+03, 0., 2.4836974544986647e+03, 0.], [0., 7.3035803715514758e+03, 1.7170248033347561e+03, 0.],
+                   [0., 0., 1., 0.]])
+    P2 = P1.copy()
+    P2[0, 3] = 7.3230899280915291e+03 * 0.12      # (the baseline on the side of the synthetic pairs' positive disparities)
+    return P1, P2
+
+
+def to_16u(np, z, unit):
+    """The 16UC1 rule of include/ugsm.h on a host Z plane."""
+    with np.errstate(invalid="ignore", over="ignore"):
+        u = (z * np.float32(unit)) * np.float32(1000.0) + np.float32(0.5)
+        valid = np.isfinite(z) & (u >= np.float32(1.0)) & (u < np.float32(65536.0))
+        return np.where(valid, u, np.float32(0)).astype(np.uint16)
+
+
+def child():
+    sys.path.insert(0, args.tree)
+    import ctypes as C
+    import numpy as np
+    from ug_stereomatcher_amd import _lib
+    W, H = SIZES[args.size]
+    n = W * H
+    z = np.load(args.images)
+    L, R, field = np.ascontiguousarray(z["L"]), np.ascontiguousarray(z["R"]), np.ascontiguousarray(z["field"])
+    P1, P2 = rig()
+    case = args.child[0]
+    out = {}
+
+    def timed(f):
+        ts = []
+        for _ in range(args.warmup + args.reps):
+            t0 = time.perf_counter()
+            f()
+            ts.append((time.perf_counter() - t0) * 1e3)
+        ts = ts[args.warmup:]
+        return dict(ms=statistics.median(ts), ms_min=min(ts), ms_max=max(ts))
+
+    with _lib.Context(levels=LEVELS, slots=1) as c:
+        if case == "a":
+            dF, dX = c.to_device(field), c.alloc(3 * n * 4)
+
+            def f():
+                c.triangulate(dF, dF + 4 * n, W, H, P1, P2, dX)
+                return to_16u(np, c.to_host(dX + 8 * n, (H, W)), UNIT)
+            out = timed(f)
+            out["valid_share"] = float((f() > 0).mean())
+        elif case == "b":
+            dF, dD, dV = c.to_device(field), c.alloc(2 * n), c.alloc(8)
+            prm = _lib.depth_params(format=_lib.UGSM_DEPTH_16U, unit=UNIT)
+
+            def f():
+                c.depth_image(dF, dF + 4 * n, None, W, H, P1, P2, prm, dD, dV)
+                return c.to_host(dD, (H, W), np.uint16)
+            out = timed(f)
+            out["valid_share"] = float((f() > 0).mean())
+        elif case == "c":
+            planes = np.empty((3, H, W), np.float32)
+            ptr = [planes[k].ctypes.data for k in range(3)]
+            out = timed(lambda: c.check(c.lib.ugsm_match_full(c.handle, L.ctypes.data, R.ctypes.data, W, H, L.strides[0], *ptr)))
+        elif case == "d":
+            prm = _lib.depth_params(format=_lib.UGSM_DEPTH_16U, unit=UNIT)
+            depth = np.empty((H, W), np.uint16)
+            q = [(C.c_double * 12)(*np.asarray(p, np.float64).reshape(12)) for p in (P1, P2)]
+            out = timed(lambda: c.check(c.lib.ugsm_match_full_depth(c.handle, L.ctypes.data, R.ctypes.data, W, H, L.strides[0], q[0], q[1], C.byref(prm),
+                                                                    depth.ctypes.data, None, None, None)))
+            out["valid_share"] = float((depth > 0).mean())
+        else:   # the kernel alone
+            dF, dD, dV = c.to_device(field), c.alloc(4 * n), c.alloc(8)
+
+            def region(f, reps):
+                t0 = time.perf_counter()
+                for _ in range(reps):
+                    f()
+                c.check(c.lib.ugsm_wait(c.handle, 0))
+                return time.perf_counter() - t0
+            # (name: parameters, confidence plane, d_valid, bytes a pixel) -- `_count`: with d_valid, so the region also holds the count's
+            # hipMemsetAsync per call and the launch its one integer atomic per wave on that one word
+            u16, f32 = _lib.depth_params(format=_lib.UGSM_DEPTH_16U, unit=UNIT), _lib.depth_params(min_conf=0.5)
+            forms = {"16u_no_conf": (u16, None, None, 8 + 2), "16u_no_conf_count": (u16, None, dV, 8 + 2),
+                     "32f_conf": (f32, dF + 8 * n, None, 12 + 4), "32f_conf_count": (f32, dF + 8 * n, dV, 12 + 4)}
+            q = [(C.c_double * 12)(*np.asarray(p, np.float64).reshape(12)) for p in (P1, P2)]
+            for name, (prm, conf, valid, per_pixel) in forms.items():
+                ref = C.byref(prm)     # the C call itself: no Python conversion inside the region
+                f = lambda: c.check(c.lib.ugsm_depth_image(c.handle, 0, dF, dF + 4 * n, conf, W, H, q[0], q[1], ref, dD, valid))   # noqa: E731
+                region(f, 10)
+                reps = int(min(max(args.region / (region(f, 30) / 30), 30), 5000))
+                region(f, reps)
+                dt = region(f, reps)
+                out[name] = dict(us_per_call=dt / reps * 1e6, reps=reps, bytes=n * per_pixel)
+    print("DEPTHBENCH " + json.dumps(out), flush=True)
+
+
+def measure(config, size, images, parent):
+    tree = parent if config.endswith("_parent") else ROOT
+    cmd = [sys.executable, os.path.abspath(__file__), "--child", config, "--size", size, "--tree", tree, "--images", images, "--reps", str(args.reps),
+           "--warmup", str(args.warmup), "--region", str(args.region)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("DEPTHBENCH ")]
+    if r.returncode != 0 or not lines:
+        raise SystemExit(f"child failed ({r.returncode}): {' '.join(cmd)}\n{r.stdout[-2000:]}\n{r.stderr[-2000:]}")
+    return json.loads(lines[-1][len("DEPTHBENCH "):])
+
+
+def main():
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    from ug_stereomatcher_amd import synth
+    parent = os.path.abspath(args.parent_tree) if args.parent_tree else None
+    if parent and not os.path.exists(os.path.join(parent, "ug_stereomatcher_amd", "libugsm.so")):
+        raise SystemExit(f"{parent}: no built ug_stereomatcher_amd/libugsm.so")
+    configs = [k for k in (args.configs or CONFIGS) if parent or not k.endswith("_parent")]
+    result = dict(tool="tools/depth_bench.py", levels=LEVELS, rounds=args.rounds, reps=args.reps, parent_measured=bool(parent), unit=UNIT,
+                  hbm_peak_spec_bytes_per_s=HBM_PEAK_SPEC, hbm_peak_measured_bytes_per_s=HBM_PEAK_MEASURED,
+                  timing="a, b, c, d: host clock around one blocking step, the median of `reps` after `warmup`; kernel: region / reps", sizes={})
+    with tempfile.TemporaryDirectory() as tmp:
+        for size in args.sizes:
+            W, H = SIZES[size]
+            L, R, dx, dy = synth.make_pair(W, H, synth.BASE_SEED + 2)
+            images = os.path.join(tmp, f"{size}.npz")
+            np.savez(images, L=L, R=R, field=np.stack([dx, dy, np.full((H, W), 0.75, np.float32)]).astype(np.float32))
+            kept = {k: [] for k in configs}
+            for rnd in range(args.rounds):
+                for k in configs:       # (the parent's children and this build's alternate)
+                    kept[k].append(measure(k, size, images, parent))
+                print(size, rnd, {k: round(v[-1]["ms"], 3) for k, v in kept.items() if k != "kernel"}, flush=True)
+            row = dict(W=W, H=H, configs={}, kernel={})
+            med = {}
+            for k in configs:
+                if k == "kernel":
+                    continue
+                ms = [x["ms"] for x in kept[k]]
+                med[k] = statistics.median(ms)
+                row["configs"][k] = dict(ms=med[k], ms_children=ms, spread_ms=max(ms) - min(ms), children=kept[k])
+            for name in (kept["kernel"][0] if "kernel" in kept else ()):
+                us = [x[name]["us_per_call"] for x in kept["kernel"]]
+                m, nbytes = statistics.median(us), kept["kernel"][0][name]["bytes"]
+                row["kernel"][name] = dict(us_per_call=m, us_per_call_children=us, spread_us=max(us) - min(us), bytes=nbytes,
+                                           reps=[x[name]["reps"] for x in kept["kernel"]],
+                                           hbm_bound_us_spec=nbytes / HBM_PEAK_SPEC * 1e6, hbm_bound_us_measured=nbytes / HBM_PEAK_MEASURED * 1e6,
+                                           bytes_per_s=nbytes / (m * 1e-6))
+            a = "a_parent" if parent else "a_this"
+            cc = "c_parent" if parent else "c_this"
+            if "b" in med and a in med:
+                row["b_over_a"] = med["b"] / med[a]
+            if "d" in med and cc in med:
+                row["d_over_c"] = med["d"] / med[cc]
+                row["c_minus_d_ms"] = med[cc] - med["d"]
+            if parent and all(k in med for k in ("a_this", "a_parent", "c_this", "c_parent")):
+                row["a_this_minus_a_parent_ms"] = med["a_this"] - med["a_parent"]
+                row["c_this_minus_c_parent_ms"] = med["c_this"] - med["c_parent"]
+            result["sizes"][size] = row
+            print(json.dumps({k: v for k, v in row.items() if k not in ("configs",)}), flush=True)
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    json.dump(result, open(args.out, "w"), indent=1, sort_keys=True)
+    print(f"wrote {args.out}")
+
+
+if __name__ == "__main__":
+    child() if args.child else main()

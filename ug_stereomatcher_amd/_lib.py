@@ -80,6 +80,8 @@ EXPORTS = [
     # checked full-mode pairs through the queue
     "ugsm_submit_full_checked_host", "ugsm_enqueue_full_checked", "ugsm_enqueue_full_checked_managed", "ugsm_enqueue_full_checked_cloud",
     "ugsm_enqueue_full_checked_cloud_managed", "ugsm_done_checked",
+    # the depth image (REP 118)
+    "ugsm_default_depth_params", "ugsm_depth_image_size", "ugsm_depth_image", "ugsm_depth_image_fovea", "ugsm_match_full_depth",
 ]
 # ... and what include/ugsm_dev.h adds (libugsm_dev.so only)
 DEV_EXPORTS = ["ugsm_stage_poly_probe", "ugsm_stage_div3_probe", "ugsm_stage_div_probe", "ugsm_stage_range_words", "ugsm_stage_iterate_rgb8", "ugsm_stage_level0_direct"]
@@ -103,6 +105,12 @@ INPUT_ENCODINGS = {"rgb8": UGSM_INPUT_RGB8, "bgr8": UGSM_INPUT_BGR8, "rgba8": UG
 # which calls apply the LR check (ugsm_set_lr_check); ugsm_create leaves a context at (lr_check_threshold, UGSM_LR_FULL)
 UGSM_LR_FULL = 1
 UGSM_LR_FOVEATED = 2
+
+UGSM_DEPTH_32F = 0   # REP 118 32FC1: float32, NaN where there is no reading
+UGSM_DEPTH_16U = 1   # REP 118 16UC1: uint16 millimetres, 0 where there is no reading
+UGSM_DEPTH_ALL_LEVELS = -1
+DEPTH_DTYPES = {UGSM_DEPTH_32F: np.dtype(np.float32), UGSM_DEPTH_16U: np.dtype(np.uint16)}
+DEPTH_ENCODINGS = {"32FC1": UGSM_DEPTH_32F, "16UC1": UGSM_DEPTH_16U}
 
 UGSM_CLOUD_PCL32 = 0     # pcl::PointXYZRGB in memory: x, y, z, 1.0f, rgb word, 12 zero bytes (32 B)
 UGSM_CLOUD_XYZRGB16 = 1  # x, y, z, rgb word (16 B)
@@ -132,6 +140,12 @@ class CloudParams(C.Structure):
     """ugsm_cloud_params (include/ugsm.h)."""
     _fields_ = [("sampling", C.c_int), ("format", C.c_int), ("compact", C.c_int), ("min_conf", C.c_float), ("z_min", C.c_float),
                 ("z_max", C.c_float)]
+
+
+class DepthParams(C.Structure):
+    """ugsm_depth_params (include/ugsm.h)."""
+    _fields_ = [("format", C.c_int), ("unit", C.c_float), ("min_conf", C.c_float), ("z_min", C.c_float), ("z_max", C.c_float),
+                ("factor", C.c_float)]
 
 
 class QueueCloud(C.Structure):
@@ -426,6 +440,12 @@ def load(dev: bool = False):
     lib.ugsm_warp_right_fovea.argtypes = [vp, i, vp, vp, vp, i, i, vp]
     lib.ugsm_photometric_residual.argtypes = [vp, i, vp, vp, i, i, i, vp, vp, vp, vp]
     lib.ugsm_photometric_residual_fovea.argtypes = [vp, i, vp, vp, vp, vp, vp, i, i, vp]
+    lib.ugsm_default_depth_params.argtypes = [C.POINTER(DepthParams)]
+    lib.ugsm_default_depth_params.restype = None
+    lib.ugsm_depth_image_size.argtypes = [i, i, C.c_float, ip, ip]
+    lib.ugsm_depth_image.argtypes = [vp, i, vp, vp, vp, i, i, dpp, dpp, C.POINTER(DepthParams), vp, vp]
+    lib.ugsm_depth_image_fovea.argtypes = [vp, i, vp, vp, vp, i, i, i, i, i, dpp, dpp, C.POINTER(DepthParams), vp, vp]
+    lib.ugsm_match_full_depth.argtypes = [vp, vp, vp, i, i, i, dpp, dpp, C.POINTER(DepthParams), vp, vp, vp, vp]
     if bool(lib.ugsm_is_dev_library()) != bool(dev):
         raise UgsmError(UGSM_ERR_STATE, f"{path} is not the {'development' if dev else 'product'} build")
     _libs[dev] = lib
@@ -500,6 +520,26 @@ def cloud_params(sampling: int = 1, format: int = UGSM_CLOUD_PCL32, compact: boo
         if v is not None:
             setattr(p, name, float(v))
     return p
+
+
+def depth_params(format: int = UGSM_DEPTH_32F, unit: float | None = None, min_conf: float | None = None, z_min: float | None = None,
+                 z_max: float | None = None, factor: float | None = None) -> DepthParams:
+    """ugsm_depth_params from ugsm_default_depth_params with the named fields changed (None: the default)."""
+    p = DepthParams()
+    load().ugsm_default_depth_params(C.byref(p))
+    p.format = int(format)
+    for name, v in (("unit", unit), ("min_conf", min_conf), ("z_min", z_min), ("z_max", z_max), ("factor", factor)):
+        if v is not None:
+            setattr(p, name, float(v))
+    return p
+
+
+def depth_image_size(pw: int, ph: int, factor: float = 1.0):
+    """(dw, dh) of the depth image of pw x ph planes, the resized clouds' rule with f a float32; None on bad arguments."""
+    dw, dh = C.c_int(), C.c_int()
+    if load().ugsm_depth_image_size(pw, ph, C.c_float(float(factor)), C.byref(dw), C.byref(dh)):
+        return None
+    return dw.value, dh.value
 
 
 def cloud_points(W: int, H: int, sampling: int = 1) -> int:
@@ -796,6 +836,54 @@ class Context:
                                                            C.byref(params), d_points, int(cap_points), d_count))
         self.check(self.lib.ugsm_wait(self._h, slot))
         return int(self.to_host(d_count, (1,), np.int64)[0])
+
+    # ---- the depth image, REP 118 32FC1 / 16UC1 (include/ugsm.h) ---------------------------------------------------------------------------
+    @staticmethod
+    def _proj(P1, P2):
+        dp = C.POINTER(C.c_double)
+        p1, p2 = np.ascontiguousarray(P1, np.float64).reshape(12), np.ascontiguousarray(P2, np.float64).reshape(12)
+        return p1, p2, p1.ctypes.data_as(dp), p2.ctypes.data_as(dp)
+
+    def depth_image(self, d_dispx: int, d_dispy: int, d_conf, W: int, H: int, P1, P2, params: DepthParams, d_depth: int, d_valid=None,
+                    slot: int = 0, wait: bool = True):
+        """The depth image of a full-resolution match into d_depth (dw x dh elements, depth_image_size); with d_valid and wait, returns the
+        number of valid pixels stored."""
+        p1, p2, q1, q2 = self._proj(P1, P2)
+        self.check(self.lib.ugsm_depth_image(self._h, slot, d_dispx, d_dispy, d_conf, W, H, q1, q2, C.byref(params), d_depth, d_valid))
+        if wait:
+            self.check(self.lib.ugsm_wait(self._h, slot))
+            if d_valid is not None:
+                return int(self.to_host(d_valid, (1,), np.uint64)[0])
+
+    def depth_image_fovea(self, d_stackx: int, d_stacky: int, d_stackc, W: int, H: int, off, level: int, P1, P2, params: DepthParams,
+                          d_depth: int, d_valid=None, slot: int = 0, wait: bool = True):
+        """The depth image of level `level` of the fovea stacks of a foveated call on a W x H frame at window offset `off`, or with
+        UGSM_DEPTH_ALL_LEVELS of every level (level 0 first) in one launch; with d_valid and wait, returns the list of per-level counts."""
+        p1, p2, q1, q2 = self._proj(P1, P2)
+        self.check(self.lib.ugsm_depth_image_fovea(self._h, slot, d_stackx, d_stacky, d_stackc, W, H, int(off[0]), int(off[1]), int(level), q1,
+                                                   q2, C.byref(params), d_depth, d_valid))
+        if wait:
+            self.check(self.lib.ugsm_wait(self._h, slot))
+            if d_valid is not None:
+                n = self.cfg.fovea_levels if level == UGSM_DEPTH_ALL_LEVELS else 1
+                return self.to_host(d_valid, (n,), np.uint64).astype(np.int64).tolist()
+
+    def match_full_depth(self, L: np.ndarray, R: np.ndarray, P1, P2, params: DepthParams, planes: bool = False):
+        """The blocking call: the match of (L, R) and its depth image, a (dh, dw) float32 or uint16 array; with planes, also the match's
+        (3, H, W) result -- otherwise only the image crosses the bus."""
+        W, H, stride = self.check_image(L)
+        if self.check_image(R) != (W, H, stride):
+            raise UgsmError(UGSM_ERR_SIZE_MISMATCH, "left and right images differ in size or stride")
+        size = depth_image_size(W, H, params.factor)
+        if size is None or params.format not in DEPTH_DTYPES:
+            raise UgsmError(UGSM_ERR_BAD_ARG, "depth parameters")
+        p1, p2, q1, q2 = self._proj(P1, P2)
+        depth = np.empty((size[1], size[0]), DEPTH_DTYPES[params.format])
+        out = np.empty((3, H, W), np.float32) if planes else None
+        ptr = [out[k].ctypes.data for k in range(3)] if planes else [None] * 3
+        self.check(self.lib.ugsm_match_full_depth(self._h, L.ctypes.data, R.ctypes.data, W, H, stride, q1, q2, C.byref(params),
+                                                  depth.ctypes.data, *ptr))
+        return (depth, out) if planes else depth
 
     # ---- the warped right image and the photometric residual of a match (include/ugsm.h) -----------------------------------------------
     def warp_planes(self, d_src: int, channels: int, W: int, H: int, d_dispx: int, d_dispy: int, d_dst: int, slot: int = 0, wait: bool = True):

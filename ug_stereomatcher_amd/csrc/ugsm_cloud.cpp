@@ -8,6 +8,18 @@
 
 using namespace ugsm;
 
+// What the depth calls refuse about their parameters and the planes' size (no device needed), and the image's size.  have_conf: the call has
+// a confidence plane.
+int ugsm::depth_params_ok(const ugsm_depth_params *p, bool have_conf, int pw, int ph, int *dw, int *dh)
+{
+    if (!p || pw < 1 || ph < 1 || (long long)pw * ph > kMaxPixels) return UGSM_ERR_BAD_ARG;
+    if (p->format != UGSM_DEPTH_32F && p->format != UGSM_DEPTH_16U) return UGSM_ERR_BAD_ARG;
+    if (!(std::isfinite(p->unit) && p->unit > 0.0f)) return UGSM_ERR_BAD_ARG;
+    if (std::isnan(p->min_conf) || std::isnan(p->z_min) || std::isnan(p->z_max) || p->z_min > p->z_max) return UGSM_ERR_BAD_ARG;
+    if (!have_conf && p->min_conf > -INFINITY) return UGSM_ERR_BAD_ARG;  // (a confidence test without a confidence plane)
+    return ugsm_depth_image_size(pw, ph, p->factor, dw, dh);
+}
+
 namespace {
 
 // one launch (or a count launch and the cloud's) in the statistics' bracket, and what it reports
@@ -280,6 +292,48 @@ int fovea_cloud_args(CloudArgs &a, const float *stackx, const float *stacky, con
     return UGSM_OK;
 }
 
+// The depth image's checks (no device needed) and its kernel arguments.  dx, dy, conf: `in_levels` levels of pw x ph floats each (a field: 1;
+// the fovea stacks: F); the call writes `levels` images of dw x dh elements behind each other and as many counts.
+int depth_args_ok(const ugsm_ctx *ctx, const float *dx, const float *dy, const float *conf, int in_levels, int pw, int ph, int levels, const double *P1,
+                  const double *P2, const ugsm_depth_params *p, const void *depth, const void *valid, DepthArgs &d)
+{
+    if (!ctx || !dx || !dy || !P1 || !P2 || !depth) return UGSM_ERR_BAD_ARG;
+    int dw, dh;
+    UCHK(depth_params_ok(p, conf != nullptr, pw, ph, &dw, &dh));
+    const size_t size = p->format == UGSM_DEPTH_16U ? 2 : 4;
+    if (((uintptr_t)depth & (size - 1)) || ((uintptr_t)valid & 7)) return UGSM_ERR_BAD_ARG;
+    if (((uintptr_t)dx | (uintptr_t)dy | (uintptr_t)conf) & 3) return UGSM_ERR_BAD_ARG;
+    const uintptr_t o0 = (uintptr_t)depth, o1 = o0 + (size_t)levels * dw * dh * size, in_bytes = (size_t)in_levels * pw * ph * sizeof(float);
+    for (const float *q : {dx, dy, conf})
+        if (q && o0 < (uintptr_t)q + in_bytes && (uintptr_t)q < o1) return UGSM_ERR_BAD_ARG;  // (the image would overwrite what it is made from)
+    d = DepthArgs{};
+    d.conf = conf;
+    d.out = const_cast<void *>(depth);
+    d.valid = static_cast<unsigned long long *>(const_cast<void *>(valid));
+    d.unit = p->unit;
+    d.min_conf = p->min_conf;
+    d.z_min = p->z_min;
+    d.z_max = p->z_max;
+    d.dw = dw;
+    d.dh = dh;
+    d.rz.scale_x = 1. / ((double)dw / pw);  // (as resize_args)
+    d.rz.scale_y = 1. / ((double)dh / ph);
+    d.rz.factor = p->factor;
+    d.rz.same_size = dw == pw && dh == ph;
+    return UGSM_OK;
+}
+
+// the slot, the device, the counts zeroed on the slot's stream, the launch (one for all `levels` images) in the statistics' misc class
+template <class F>
+int depth_image(ugsm_ctx *ctx, int slot, const DepthArgs &d, int levels, F &&launch)
+{
+    Slot *s;
+    UCHK(get_slot(ctx, slot, &s));
+    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
+    if (d.valid) HIPCHK(ctx, hipMemsetAsync(d.valid, 0, (size_t)levels * sizeof(unsigned long long), s->st));
+    return timed_launch(ctx, s, slot, (double)levels * d.dw * d.dh, [&] { launch(s->st); });
+}
+
 constexpr size_t kCqWords = 1 + UGSM_MAX_LEVELS;  // a managed pair's count words: the count, the level counts
 
 int queue_cloud_launch(ugsm_ctx *ctx, Slot &s, int si, int b0, int n, bool stack, const ugsm_queue_cloud *spec)
@@ -491,6 +545,55 @@ int ugsm_point_cloud_resized_fovea(ugsm_ctx *ctx, int slot, const float *d_stack
                           d_points, cap_points, d_count));
     const CloudResize rz = resize_args(a, factor, colour_mapped);
     return point_cloud(ctx, slot, a, true, P1, P2, &rz);
+}
+
+// ---- row f-1, the depth image (REP 118 32FC1 / 16UC1; the reference's range_map and res_range_map, getPointCloud.cpp:730-758, :813-841) ----
+
+void ugsm_default_depth_params(ugsm_depth_params *p)
+{
+    if (!p) return;
+    p->format = UGSM_DEPTH_32F;
+    p->unit = 1.0f;
+    p->min_conf = -INFINITY;
+    p->z_min = -INFINITY;
+    p->z_max = INFINITY;
+    p->factor = 1.0f;
+}
+
+int ugsm_depth_image_size(int pw, int ph, float factor, int *dw, int *dh)
+{
+    if (!dw || !dh || ugsm_resized_cloud_points(pw, ph, factor) < 1) return UGSM_ERR_BAD_ARG;
+    *dw = (int)((float)pw * factor);
+    *dh = (int)((float)ph * factor);
+    return UGSM_OK;
+}
+
+int ugsm_depth_image(ugsm_ctx *ctx, int slot, const float *d_dispx, const float *d_dispy, const float *d_conf, int W, int H, const double *P1,
+                     const double *P2, const ugsm_depth_params *p, void *d_depth, unsigned long long *d_valid)
+{
+    DepthArgs d;
+    UCHK(depth_args_ok(ctx, d_dispx, d_dispy, d_conf, 1, W, H, 1, P1, P2, p, d_depth, d_valid, d));
+    const bool u16 = p->format == UGSM_DEPTH_16U;
+    return depth_image(ctx, slot, d, 1, [&](hipStream_t st) { launch_depth_image(st, d_dispx, d_dispy, W, H, P1, P2, d, u16); });
+}
+
+int ugsm_depth_image_fovea(ugsm_ctx *ctx, int slot, const float *d_stackx, const float *d_stacky, const float *d_stackc, int W, int H, int off_x,
+                           int off_y, int level, const double *P1, const double *P2, const ugsm_depth_params *p, void *d_depth,
+                           unsigned long long *d_valid)
+{
+    if (!ctx || W < 1 || H < 1 || (long long)W * H > kMaxPixels) return UGSM_ERR_BAD_ARG;
+    const int F = ctx->cfg.fovea_levels;
+    const bool all = level == UGSM_DEPTH_ALL_LEVELS;
+    if (F < 2 || (!all && (level < 0 || level >= F))) return UGSM_ERR_BAD_ARG;
+    DepthFoveaArgs f{};
+    int fw, fh;
+    UCHK(fovea_level_mappings(W, H, ctx->cfg.levels, F, off_x, off_y, &fw, &fh, f.lv.left, f.lv.upper, f.lv.scale));
+    f.lv.levels = all ? F : 1;
+    UCHK(depth_args_ok(ctx, d_stackx, d_stacky, d_stackc, F, fw, fh, f.lv.levels, P1, P2, p, d_depth, d_valid, f.d));
+    const bool u16 = p->format == UGSM_DEPTH_16U;
+    const int src_level = all ? 0 : level;
+    return depth_image(ctx, slot, f.d, f.lv.levels,
+                       [&](hipStream_t st) { launch_depth_image_fovea(st, d_stackx, d_stacky, fw, fh, src_level, P1, P2, f, u16); });
 }
 
 }  // extern "C"

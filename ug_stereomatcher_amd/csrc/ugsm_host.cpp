@@ -222,6 +222,24 @@ int copy_out_planes(ugsm_ctx *ctx, Slot &s, const float *d_src, size_t plane_flo
     return UGSM_OK;
 }
 
+// One buffer of any size into caller memory of either kind (the depth image; a single plane): a page-locked destination takes the copy
+// directly, a pageable one takes it through the front of the slot's page-locked staging and the host team -- whatever went through the
+// staging before has been copied out by then (copy_out_planes and this function return with their pageable copies done).
+int copy_out_bytes(ugsm_ctx *ctx, Slot &s, const void *d_src, size_t bytes, void *dst)
+{
+    if (is_pinned(dst)) {
+        HIPCHK(ctx, hipMemcpyAsync(dst, d_src, bytes, hipMemcpyDeviceToHost, s.st));
+        return UGSM_OK;
+    }
+    UCHK(s.hpin.grow(ctx, (bytes + 3) / 4));
+    if (!s.out_ev[0]) HIPCHK(ctx, hipEventCreateWithFlags(&s.out_ev[0], hipEventDisableTiming));
+    HIPCHK(ctx, hipMemcpyAsync(s.hpin, d_src, bytes, hipMemcpyDeviceToHost, s.st));
+    HIPCHK(ctx, hipEventRecord(s.out_ev[0], s.st));
+    HIPCHK(ctx, hipEventSynchronize(s.out_ev[0]));
+    team_copy(ctx, dst, s.hpin, bytes);
+    return UGSM_OK;
+}
+
 // The counterpart of copy_out_planes for what a call reads besides its images (a prior, a state, a prior stack): three host planes of any kind
 // up into d_dst, on the slot's stream.
 int upload_planes(ugsm_ctx *ctx, Slot &s, float *d_dst, size_t plane_floats, const float *const src[3])
@@ -399,6 +417,39 @@ int ugsm_match_full(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int
                     float *dispV, float *dispC)
 {
     return match_full_host(ctx, 0, rgbL, rgbR, W, H, stride, dispH, dispV, dispC, true);
+}
+
+// The service call with the depth image (REP 118) as its result: ugsm_match_full, then ugsm_depth_image on the same slot from the planes
+// in the slot's result staging, the image behind them; the image comes down, and whichever planes are asked for.
+int ugsm_match_full_depth(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, const double *P1, const double *P2,
+                          const ugsm_depth_params *p, void *depth, float *dispH, float *dispV, float *dispC)
+{
+    float *const dst[3] = {dispH, dispV, dispC};
+    const bool all_planes = dispH && dispV && dispC;
+    const size_t n = (size_t)W * H, room = field_room(n);
+    size_t image_bytes = 0;
+    auto check = [&](Slot &, size_t &hout) -> int {
+        int dw, dh;
+        if (!depth || !P1 || !P2) return UGSM_ERR_BAD_ARG;
+        UCHK(depth_params_ok(p, true, W, H, &dw, &dh));
+        image_bytes = (size_t)dw * dh * (p->format == UGSM_DEPTH_16U ? 2 : 4);
+        hout = room + (image_bytes + 3) / 4;
+        return UGSM_OK;
+    };
+    auto match = [&](Slot &s) -> int {
+        UCHK(enqueue_match_full(ctx, s, 0, 1, &s.rgbL.p, &s.rgbR.p, W, H, stride, &s.hout.p));
+        return ugsm_depth_image(ctx, 0, s.hout, s.hout + n, s.hout + 2 * n, W, H, P1, P2, p, s.hout + room, nullptr);
+    };
+    return host_call(ctx, 0, true, rgbL, rgbR, W, H, stride, check, match, [&](Slot &s) -> int {
+        if (all_planes) {
+            prefault_planes(ctx, dst, n);
+            UCHK(copy_out_planes(ctx, s, s.hout, n, dst));
+        } else {
+            for (int k = 0; k < 3; k++)
+                if (dst[k]) UCHK(copy_out_bytes(ctx, s, s.hout + k * n, n * sizeof(float), dst[k]));
+        }
+        return copy_out_bytes(ctx, s, s.hout + room, image_bytes, depth);
+    });
 }
 
 int ugsm_submit_full_host(ugsm_ctx *ctx, int slot, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, float *dispH,

@@ -203,6 +203,33 @@ struct CloudMulti {
 };
 // args.dx / dy / conf are not read (the table's are); args.cnt (compact): (E * wc) * nchunk counts, E * wc column totals, E * strips strip totals
 void launch_point_cloud_multi(hipStream_t st, const CloudArgs &args, const CloudMulti &mu, const double *P1, const double *P2);
+// The depth image (ugsm_depth_image[_fovea]; REP 118): the Z of k_triangulate[_fovea], or the resized clouds' Z, as a row-major image of
+// 32FC1 / 16UC1 elements -- the depth forms of those two kernels.  The image of a level is dw x dh (factor 1: the planes' pw x ph, indexed
+// flat: a thread owns a run of 16 bytes of adjacent pixels, the first run starting where the image is 16-byte aligned; factor < 1:
+// CloudResize's map, a thread a pixel).  The fovea form takes `levels` levels from src_level on in one launch (the grid's y), each mapped by
+// its row of the table (ugsm_fovea_level_mapping), images and counts level after level.
+struct DepthArgs {
+    const float *conf;          // the confidence plane (the fovea form: the stack's, level 0 first); null: no confidence test
+    void *out;                  // dw * dh elements a level: float (32F) or uint16_t (16U), aligned to the element
+    unsigned long long *valid;  // the valid pixels stored, a count a level, zeroed before the launch; may be null
+    float unit, min_conf, z_min, z_max;
+    int dw, dh;
+    CloudResize rz;             // the resized forms (factor < 1)
+};
+struct DepthLevels {
+    int levels;                 // the launch's levels: src_level .. src_level + levels - 1
+    int left[kCloudMaxLevels], upper[kCloudMaxLevels];
+    float scale[kCloudMaxLevels];
+};
+struct DepthFoveaArgs {
+    DepthArgs d;
+    DepthLevels lv;
+};
+// u16: UGSM_DEPTH_16U, else UGSM_DEPTH_32F; d.rz.factor < 1: the resized form
+void launch_depth_image(hipStream_t st, const float *dispx, const float *dispy, int W, int H, const double *P1, const double *P2, const DepthArgs &d,
+                        bool u16);
+void launch_depth_image_fovea(hipStream_t st, const float *stackx, const float *stacky, int fovW, int fovH, int src_level, const double *P1,
+                              const double *P2, const DepthFoveaArgs &d, bool u16);
 void launch_upsample_paste(hipStream_t st, const float *src3, int W, int H, float *dst3, int W2, int H2, const float *fovH_, const float *fovV_,
                            const float *fovC_, int fovW, int fovH, int org_x, int org_y);
 // The same step with the fovea of n stacks of one pair (ugsm_reconstruct_full_multi): window k's crop origin at this level, and its stack's

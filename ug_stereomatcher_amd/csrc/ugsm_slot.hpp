@@ -533,5 +533,7 @@ int queue_cloud_finish(ugsm_ctx *ctx, int slot, int n, ugsm_cloud_result *res, v
 int queue_checked_submit(ugsm_ctx *ctx, int slot, const CheckedCall *call);
 int queue_checked_marked(ugsm_ctx *ctx, int slot, int n, long long *fwd, long long *back);
 int queue_checked_cloud_submit(ugsm_ctx *ctx, int slot, const CheckedCall *call);  // (a call whose pairs carry a cloud)
+// ---- ugsm_cloud.cpp, for ugsm_match_full_depth: the depth image's parameter checks and size, before anything is enqueued -----------
+int depth_params_ok(const ugsm_depth_params *p, bool have_conf, int pw, int ph, int *dw, int *dh);
 
 }  // namespace ugsm

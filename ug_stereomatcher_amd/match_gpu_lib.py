@@ -171,6 +171,19 @@ class MatchGPULib:
             for p in ps + [pout]:
                 c.free(p)
 
+    # -- the depth image (not in the reference's library: its point-cloud node builds range_map on the host) --
+    def depthImage(self, cv_ptrL, cv_ptrR, P1, P2, encoding: str = "32FC1", unit: float = 1.0, min_conf: float = float("-inf"),
+                   z_min: float = float("-inf"), z_max: float = float("inf"), factor: float = 1.0, planes: bool = False):
+        """match(L, R, 0) and its REP 118 depth image registered to the left camera (ugsm_match_full_depth): "32FC1" -- float32 metres, NaN
+        where there is no reading -- or "16UC1" -- uint16 millimetres, 0 where there is none; unit = metres per unit of the calibration.
+        Returns the (dh, dw) image; with planes, (image, finDisp) -- otherwise only the image crosses the bus."""
+        if encoding not in _lib.DEPTH_ENCODINGS:
+            raise UgsmError(_lib.UGSM_ERR_BAD_ARG, f"depth encoding {encoding!r}: 32FC1 or 16UC1")
+        L, R = self._take(cv_ptrL, cv_ptrR)
+        self.foveatedmatching = 0
+        prm = _lib.depth_params(format=_lib.DEPTH_ENCODINGS[encoding], unit=unit, min_conf=min_conf, z_min=z_min, z_max=z_max, factor=factor)
+        return self._ctx.match_full_depth(L, R, P1, P2, prm, planes=planes)
+
     # -- warpRightImage, MatchGPULib.cpp:1445-1518 --
     def warpRightImage(self, right, disparity, channels: int, imageW: int, imageH: int) -> np.ndarray:
         """right: `channels` float planes of imageH x imageW; disparity[0] / disparity[1]: the horizontal / vertical field.  Returns the
