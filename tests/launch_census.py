@@ -9,6 +9,10 @@ census:
     {"launches": [[name, level, launches, pixel_launches], ...] sorted, launches > 0 only,
      "sha256":   [the SHA-256 of each output buffer's bytes, in the order the call was given them]}
 
+CLOUD_CASES does the same for row f-1 (ugsm_cloud.cpp): triangulation, the point clouds, the depth images and the queue's cloud calls, whose
+launches the statistics time under the misc class with points = pairs x entries x sampled grid -- one batched cloud launch and n single ones
+differ in `launches`.
+
 An output buffer is a device buffer (the ugsm_submit_* calls) or a host array (the blocking and host-memory calls, HOST_CASES).  What a call
 reads besides the images -- a prior field, a state, a prior stack -- is filled from numpy.random.default_rng(<a literal seed>): finite, never
 zero (a zero prior would hide a dropped prior) and no other call's output (a case stands alone).
@@ -72,9 +76,9 @@ class _Run:
         self.held += [p for lr in dev for p in lr]
         return [l for l, _ in dev], [r for _, r in dev]
 
-    def out(self, floats):
-        p = self.given(np.zeros(floats, np.float32))
-        self.outs.append(lambda: self.c.to_host(p, (floats,)))
+    def out(self, floats, dtype=np.float32):
+        p = self.given(np.zeros(floats, dtype))
+        self.outs.append(lambda: self.c.to_host(p, (floats,), dtype))
         return p
 
     def given(self, arr):
@@ -329,9 +333,253 @@ HOST_CASES = {
 }
 
 
+# ---- row f-1: triangulation, the point clouds, the depth images (ugsm_cloud.cpp) and the queue's cloud calls ------------------------------------
+# What such a call reads besides the left image is _noise: disparity planes or stacks and a confidence plane in 0.25 .. 2.0, so that min_conf =
+# 1.0 keeps roughly half the points.  With the rig below the noise's Z has its 15th percentile at 210 and its 85th at 589: Z_WINDOW cuts both ends.  Every
+# compact or windowed slot-level case keeps between 10 % and 90 % of its points by tests/cloud_np.py / depth_np.py (the queue's compact case by
+# the CPU oracle's match of its pairs).  Every output is zeroed first and hashed whole: the points buffer (cap records), the count word, level or
+# entry counts, the depth image and its valid counts.
+MIN_CONF = 1.0
+Z_WINDOW = (200.0, 600.0)
+UNIT_16U = 0.05                                                  # 16UC1 holds Z * unit * 1000 below 65536: Z up to 1310 of this noise's 135 .. 866 (5 % .. 95 %)
+Q_MIN_CONF = 0.7                                                 # a match's confidence, not noise: the queue's compact case
+PCL32, XYZRGB16 = 0, 1                                           # UGSM_CLOUD_PCL32, UGSM_CLOUD_XYZRGB16
+DEPTH_32F, DEPTH_16U = 0, 1                                      # UGSM_DEPTH_32F, UGSM_DEPTH_16U
+
+
+def projections():
+    """P1 and P2 of tests/test_gpu_cloud.py: the rectified 16 MP rig with its 0.12 baseline."""
+    P1 = np.array([[7.3230899280915291e+03, 0., 2.4836974544986647e+03, 0.],
+                   [0., 7.3035803715514758e+03, 1.7170248033347561e+03, 0.], [0., 0., 1., 0.]])
+    P2 = P1.copy()
+    P2[0, 3] = -7.3230899280915291e+03 * 0.12
+    return P1, P2
+
+
+def cloud_noise(seed, n):
+    """dx, dy, conf of n values each from _noise; dx negated, so that the points lie in front of the rig (Z > 0: a depth image holds no other)."""
+    a = _noise(seed, 3 * n)
+    a[:n] *= -1
+    return a
+
+
+def _field_in(r, seed):
+    """dx, dy, conf of W x H noise on the device and the left image of pair 0."""
+    n = W * H
+    p = r.given(cloud_noise(seed, n))
+    return [p, p + 4 * n, p + 8 * n], r.images(1)[0][0]
+
+
+def _stack_in(r, seed):
+    """One stack of noise: the F levels of dx, of dy, of conf behind each other."""
+    n = F * r.fw * r.fh
+    p = r.given(cloud_noise(seed, n))
+    return [p, p + 4 * n, p + 8 * n]
+
+
+def _cloud_out(r, cap, fmt, counts=0):
+    """The points buffer of cap records, the count word and `counts` level or entry counts (0: none)."""
+    pts, cnt = r.out(cap * (32 if fmt == PCL32 else 16), np.uint8), r.out(1, np.int64)
+    return (pts, cap, cnt) + ((r.out(counts, np.int64),) if counts else ())
+
+
+def _params(r, fmt, s=1, compact=False, window=False):
+    kw = dict(min_conf=MIN_CONF) if compact else {}
+    if window:
+        kw.update(z_min=Z_WINDOW[0], z_max=Z_WINDOW[1])
+    return r.lib.cloud_params(sampling=s, format=fmt, compact=compact, **kw)
+
+
+def _triangulate(r):
+    (dx, dy, _), _ = _field_in(r, 7501)
+    r.c.triangulate(dx, dy, W, H, *projections(), r.out(3 * W * H))
+
+
+def _triangulate_fovea(r):
+    sx, sy, _ = _stack_in(r, 7502)
+    r.c.triangulate_fovea(sx, sy, r.fw, r.fh, 2, *r.lib.fovea_level_mapping(W, H, LEVELS, F, 2, OFF_CENTRE), *projections(), r.out(3 * r.fw * r.fh))
+
+
+def _cloud(fmt, s=1, compact=False, window=False, cap_div=1, seed=7503):
+    def run(r):
+        planes, rgb = _field_in(r, seed)
+        cap = r.lib.cloud_points(W, H, s) // cap_div
+        r.c.point_cloud(*planes, rgb, W, H, 3 * W, *projections(), _params(r, fmt, s, compact, window), *_cloud_out(r, cap, fmt))
+    return run
+
+
+def _cloud_fovea(level, compact, seed=7504):
+    def run(r):
+        stack, rgb = _stack_in(r, seed), r.images(1)[0][0]
+        r.c.point_cloud_fovea(*stack, r.fw, r.fh, level, *r.lib.fovea_level_mapping(W, H, LEVELS, F, level, OFF_CENTRE), rgb, W, H, 3 * W,
+                              *projections(), _params(r, PCL32, 1, compact), *_cloud_out(r, r.fw * r.fh, PCL32))
+    return run
+
+
+def _cloud_resized(r):
+    planes, rgb = _field_in(r, 7505)
+    r.c.point_cloud_resized(*planes, rgb, W, H, 3 * W, *projections(), 0.2, _params(r, PCL32), *_cloud_out(r, r.lib.resized_cloud_points(W, H, 0.2), PCL32))
+
+
+def _cloud_resized_fovea(r):
+    stack, rgb = _stack_in(r, 7506), r.images(1)[0][0]
+    r.c.point_cloud_resized_fovea(*stack, r.fw, r.fh, 2, *r.lib.fovea_level_mapping(W, H, LEVELS, F, 2, OFF_CENTRE), rgb, W, H, 3 * W, *projections(),
+                                  0.5, _params(r, XYZRGB16, 1, True), *_cloud_out(r, r.lib.resized_cloud_points(r.fw, r.fh, 0.5), XYZRGB16),
+                                  colour_mapped=True)
+
+
+def _cloud_fovea_all(compact, seed=7507):
+    def run(r):
+        stack, rgb = _stack_in(r, seed), r.images(1)[0][0]
+        cap = r.lib.fovea_cloud_points(W, H, LEVELS, F, OFF_CENTRE, 1)
+        r.c.point_cloud_fovea_all(*stack, W, H, OFF_CENTRE, rgb, 3 * W, *projections(), _params(r, PCL32, 1, compact), *_cloud_out(r, cap, PCL32, F))
+    return run
+
+
+def _cloud_fovea_multi(compact, seed=7508):
+    def run(r):
+        stacks, rgb = [_stack_in(r, seed + j)[0] for j in range(len(OFFS3))], r.images(1)[0][0]
+        cap = r.lib.fovea_multi_cloud_points(W, H, LEVELS, F, OFFS3, 1)
+        r.c.point_cloud_fovea_multi(stacks, W, H, OFFS3, rgb, 3 * W, *projections(), _params(r, XYZRGB16, 1, compact),
+                                    *_cloud_out(r, cap, XYZRGB16, (F - 1) * len(OFFS3) + 1))
+    return run
+
+
+def _depth(fmt, factor=1.0, conf=False, seed=7511):
+    def run(r):
+        (dx, dy, c), _ = _field_in(r, seed)
+        p = r.lib.depth_params(format=fmt, unit=UNIT_16U if fmt == DEPTH_16U else None, factor=factor, min_conf=MIN_CONF if conf else None)
+        dw, dh = r.lib.depth_image_size(W, H, factor)
+        r.c.depth_image(dx, dy, c if conf else None, W, H, *projections(), p, r.out(dw * dh, np.uint16 if fmt == DEPTH_16U else np.float32),
+                        r.out(1, np.uint64))
+    return run
+
+
+def _depth_fovea(fmt, level, seed=7512):
+    def run(r):
+        sx, sy, _ = _stack_in(r, seed)
+        n = F if level == r.lib.UGSM_DEPTH_ALL_LEVELS else 1
+        r.c.depth_image_fovea(sx, sy, None, W, H, OFF_CENTRE, level, *projections(), r.lib.depth_params(format=fmt, unit=UNIT_16U if fmt == DEPTH_16U else None),
+                              r.out(n * r.fw * r.fh, np.uint16 if fmt == DEPTH_16U else np.float32), r.out(n, np.uint64))
+    return run
+
+
+def _depth_fovea_all(r):
+    _depth_fovea(DEPTH_16U, r.lib.UGSM_DEPTH_ALL_LEVELS, 7513)(r)
+
+
+def _h_match_full_depth(r):
+    depth, planes = r.c.match_full_depth(*pairs()[0], *projections(), r.lib.depth_params(), planes=True)
+    r.host(depth), r.host(planes)
+
+
+# ... the queue's cloud calls: n pairs enqueued on the one-slot context with batch = 4, flushed, drained with next_done; a managed pair's lent
+# buffers are copied (and hashed in their turn) before the next next_done
+def _spec(r, fmt=PCL32, compact=False, want_planes=False):
+    p = r.lib.cloud_params(format=fmt, compact=compact, min_conf=Q_MIN_CONF if compact else None)
+    return r.lib.queue_cloud(*projections(), p, want_planes=want_planes)
+
+
+def _drain(r, n, each=None):
+    r.c.flush()
+    for tag in range(n):
+        d = r.c.next_done(True)
+        assert d is not None and d.tag == tag, (tag, d and d.tag)
+        if each:
+            each(d)
+    assert r.c.next_done(True) is None
+
+
+def _q_cloud_dev(n, fovea=False, compact=False, lr=False, checked=False):
+    def run(r):
+        if lr:
+            r.c.set_lr_check(TAU, r.lib.UGSM_LR_FULL)
+        dL, dR = r.images(n)
+        spec = _spec(r, PCL32, compact)
+        for b in range(n):
+            if fovea:
+                cap = r.lib.fovea_cloud_points(W, H, LEVELS, F, OFFS3[b], 1)
+                pts, cap, cnt, lvl = _cloud_out(r, cap, PCL32, F)
+                r.c.enqueue_foveated_cloud(dL[b], dR[b], W, H, 3 * W, OFFS3[b], r.stack(), spec, pts, cap, cnt, b, d_level_counts=lvl)
+            elif checked:
+                out, back = r.field(), (r.field() if b == 0 else None)      # (pair 1's right-to-left field stays in the slot)
+                r.c.enqueue_full_checked_cloud(dL[b], dR[b], W, H, 3 * W, out, back, TAU, spec, *_cloud_out(r, W * H, PCL32), b)
+            else:
+                r.c.enqueue_full_cloud(dL[b], dR[b], W, H, 3 * W, r.field(), spec, *_cloud_out(r, W * H, PCL32), b)
+        _drain(r, n)
+    return run
+
+
+def _lent_cloud(r):
+    rec, count, levels = r.c.done_cloud()
+    r.host(rec.view(np.uint8).copy()), r.host(np.array([count] + levels, np.int64))
+
+
+def _q_cloud_managed(n, fovea=False, want_planes=False):
+    def run(r):
+        spec = _spec(r, PCL32, False, want_planes)
+        for b in range(n):
+            L, R = pairs()[b]
+            if fovea:
+                r.c.enqueue_foveated_cloud_managed(L, R, OFF_CENTRE, spec, b)
+            else:
+                r.c.enqueue_full_cloud_managed(L, R, spec, b)
+
+        def each(d):
+            if want_planes:
+                for p in r.c.managed_planes(d, [(H, W)] * 3):
+                    r.host(p.copy())
+            _lent_cloud(r)
+        _drain(r, n, each)
+    return run
+
+
+def _q_checked_cloud_managed_back(r):
+    spec = _spec(r)
+    for b in range(2):
+        r.c.enqueue_full_checked_cloud_managed(*pairs()[b], TAU, True, spec, b)
+
+    def each(d):
+        fwd, bwd, back = r.c.done_checked((H, W))
+        r.host(np.array([fwd, bwd], np.int64)), r.host(back)
+        _lent_cloud(r)
+    _drain(r, 2, each)
+
+
+# (under the default policy only)
+CLOUD_CASES = {
+    "triangulate": (_triangulate, {}),
+    "triangulate_fovea": (_triangulate_fovea, {}),
+    "cloud_dense_pcl32": (_cloud(PCL32), {}),
+    "cloud_compact_xyzrgb16_s3": (_cloud(XYZRGB16, 3, True, True), {}),
+    "cloud_dense_cap_half": (_cloud(PCL32, cap_div=2), {}),                              # the o >= cap path; the count beyond cap
+    "cloud_fovea_l2_dense": (_cloud_fovea(2, False), {}),
+    "cloud_fovea_l2_compact": (_cloud_fovea(2, True), {}),
+    "cloud_resized_f02_dense": (_cloud_resized, {}),
+    "cloud_resized_fovea_f05_compact_mapped": (_cloud_resized_fovea, {}),
+    "cloud_fovea_all_dense": (_cloud_fovea_all(False), {}),
+    "cloud_fovea_all_compact": (_cloud_fovea_all(True), {}),
+    "cloud_fovea_multi_dense": (_cloud_fovea_multi(False), {}),
+    "cloud_fovea_multi_compact": (_cloud_fovea_multi(True), {}),
+    "depth_32f": (_depth(DEPTH_32F), {}),
+    "depth_16u_resized_f05": (_depth(DEPTH_16U, 0.5, True), {}),
+    "depth_fovea_l3_32f": (_depth_fovea(DEPTH_32F, 3), {}),
+    "depth_fovea_all_16u": (_depth_fovea_all, {}),
+    "match_full_depth": (_h_match_full_depth, {}),
+    "q_full_cloud_dev_3": (_q_cloud_dev(3), dict(batch=4)),                              # lockstep: one cloud launch for three pairs
+    "q_fovea_cloud_dev_3_compact": (_q_cloud_dev(3, fovea=True, compact=True), dict(batch=4)),
+    "q_full_cloud_managed_3_planes": (_q_cloud_managed(3, want_planes=True), dict(batch=4)),
+    "q_fovea_cloud_managed_1": (_q_cloud_managed(1, fovea=True), dict(batch=4)),         # pair by pair
+    "q_full_cloud_dev_2_lr": (_q_cloud_dev(2, lr=True), dict(batch=4)),                  # the matcher, so the clouds, pair by pair
+    "q_full_checked_cloud_dev_2": (_q_cloud_dev(2, checked=True), dict(batch=4)),
+    "q_full_checked_cloud_managed_2_back": (_q_checked_cloud_managed_back, dict(batch=4)),
+}
+
+
 def case_ids():
     """(policy, case) of every census, in the order the golden file lists them."""
-    return [(p, k) for p in POLICIES for k in CASES] + [("default", k) for k in HOST_CASES] + [(DEV_POLICY, k) for k in DEV_CASES]
+    return ([(p, k) for p in POLICIES for k in CASES] + [("default", k) for k in HOST_CASES] + [(DEV_POLICY, k) for k in DEV_CASES]
+            + [("default", k) for k in CLOUD_CASES])
 
 
 @contextlib.contextmanager
@@ -350,7 +598,7 @@ def _environ(env):
 
 def census(lib, policy, case):
     """The census of one case under one policy, taken on a fresh one-slot context."""
-    call, case_cfg = CASES[case] if case in CASES else HOST_CASES[case]
+    call, case_cfg = next(t[case] for t in (CASES, HOST_CASES, CLOUD_CASES) if case in t)
     cfg, env = (dict(kernel_path=1, dev=True), {}) if policy == DEV_POLICY else POLICIES[policy]
     with _environ(env):
         c = lib.Context(levels=LEVELS, fovea_levels=F, slots=1, profile_events=2, **dict(cfg, **case_cfg))

@@ -1,6 +1,7 @@
 // ugsm_cloud.cpp -- row f-1 of the runtime: triangulation and the coloured point clouds (getPointCloud.cpp), on the slots of ugsm_runtime.cpp.
-// The fovea forms' geometry and the coverage rule of the merged clouds (host only), the slot-level entry points behind one preamble
-// (cloud_begin), and the queue's cloud calls (CtxHooks::cloud_submit / cloud_finish).  Every cloud kernel is cloud_tile (ugsm_kernels_cloud.hip).
+// The fovea forms' geometry and the coverage rule of the merged clouds (host only), the slot-level entry points behind one description of a
+// cloud call (cloud_call_args) and one preamble (cloud_begin), and the queue's cloud calls (CtxHooks::cloud_submit / cloud_finish), which use
+// both.  Every cloud kernel is cloud_tile (ugsm_kernels_cloud.hip).
 #include "ugsm_slot.hpp"
 
 #include <algorithm>
@@ -15,12 +16,36 @@ int ugsm::depth_params_ok(const ugsm_depth_params *p, bool have_conf, int pw, in
     if (!p || pw < 1 || ph < 1 || (long long)pw * ph > kMaxPixels) return UGSM_ERR_BAD_ARG;
     if (p->format != UGSM_DEPTH_32F && p->format != UGSM_DEPTH_16U) return UGSM_ERR_BAD_ARG;
     if (!(std::isfinite(p->unit) && p->unit > 0.0f)) return UGSM_ERR_BAD_ARG;
-    if (std::isnan(p->min_conf) || std::isnan(p->z_min) || std::isnan(p->z_max) || p->z_min > p->z_max) return UGSM_ERR_BAD_ARG;
-    if (!have_conf && p->min_conf > -INFINITY) return UGSM_ERR_BAD_ARG;  // (a confidence test without a confidence plane)
+    if (!keep_window_ok(p->min_conf, p->z_min, p->z_max, have_conf)) return UGSM_ERR_BAD_ARG;
     return ugsm_depth_image_size(pw, ph, p->factor, dw, dh);
 }
 
 namespace {
+
+// the sampled grid along one side: the pixels 0, s, 2 s, ... below n
+int sampled(int n, int s) { return (n + s - 1) / s; }
+
+// The resized map of pw x ph planes: cv::Size(pw * f, ph * f) -- float products, truncated -- and cv::resize's scales (resize.cpp: inv_scale =
+// (double)dsize / ssize, scale = 1. / inv_scale).  dw = 0: no such map -- a factor outside (0, 1], or one that leaves a side at 0.
+struct ResizedGrid {
+    int dw = 0, dh = 0;
+    CloudResize rz{};
+};
+ResizedGrid resized_grid(int pw, int ph, float factor, int colour_mapped = 0)
+{
+    ResizedGrid g;
+    if (pw < 1 || ph < 1 || !(factor > 0.0f && factor <= 1.0f)) return g;
+    const int dw = (int)((float)pw * factor), dh = (int)((float)ph * factor);
+    if (dw < 1 || dh < 1) return g;
+    g.dw = dw;
+    g.dh = dh;
+    g.rz.scale_x = 1. / ((double)dw / pw);
+    g.rz.scale_y = 1. / ((double)dh / ph);
+    g.rz.factor = factor;
+    g.rz.same_size = dw == pw && dh == ph;
+    g.rz.colour_mapped = colour_mapped;
+    return g;
+}
 
 // one launch (or a count launch and the cloud's) in the statistics' bracket, and what it reports
 template <class F>
@@ -96,8 +121,8 @@ int cloud_multi_geometry(int W, int H, int levels, int F, int n, const int *off_
     g.F = F;
     g.E = (F - 1) * n + 1;
     g.s = sampling;
-    g.wc = (g.fw + sampling - 1) / sampling;
-    g.hc = (g.fh + sampling - 1) / sampling;
+    g.wc = sampled(g.fw, sampling);
+    g.hc = sampled(g.fh, sampling);
     return UGSM_OK;
 }
 
@@ -183,91 +208,104 @@ int cloud_stack_table(int W, int H, int levels, int F, int off_x, int off_y, int
     return UGSM_OK;
 }
 
-// the checks every entry point shares (no device needed); pw x ph: the planes the points come from; resized: the resized forms, which
-// take no sampling (p->sampling 1) and a factor in (0, 1] that leaves both sides at least 1
-int cloud_args_ok(const ugsm_ctx *ctx, const float *dx, const float *dy, const float *conf, const uint8_t *rgb, int W, int H, int stride, int pw,
-                  int ph, const double *P1, const double *P2, const ugsm_cloud_params *p, const void *points, long long cap, const long long *count,
-                  bool resized = false, float factor = 1.0f)
-{
-    if (!ctx || !dx || !dy || !rgb || !P1 || !P2 || !p || !points || !count) return UGSM_ERR_BAD_ARG;
-    if (W < 1 || H < 1 || pw < 1 || ph < 1 || (long long)W * H > kMaxPixels || (long long)pw * ph > kMaxPixels) return UGSM_ERR_BAD_ARG;
-    if (input_status(ctx, W, stride, rgb) != UGSM_OK || p->sampling < 1 || (p->format != UGSM_CLOUD_PCL32 && p->format != UGSM_CLOUD_XYZRGB16)) return UGSM_ERR_BAD_ARG;
-    if (std::isnan(p->min_conf) || std::isnan(p->z_min) || std::isnan(p->z_max) || p->z_min > p->z_max) return UGSM_ERR_BAD_ARG;
-    if (!conf && p->min_conf > -INFINITY) return UGSM_ERR_BAD_ARG;  // (a confidence test without a confidence plane)
-    if (cap < 0 || ((uintptr_t)points & 15) || ((uintptr_t)count & 7)) return UGSM_ERR_BAD_ARG;
-    if (resized && (p->sampling != 1 || ugsm_resized_cloud_points(pw, ph, factor) < 1)) return UGSM_ERR_BAD_ARG;
-    return UGSM_OK;
-}
+// A cloud call, described: what the points come from, the image that colours them, where they go.
+struct CloudFrom {
+    const float *dx, *dy, *conf;  // pw x ph planes, or (fovea) the stacks those are level `level` of; conf may be null
+    int pw, ph;
+    bool fovea = false;           // the fovea forms: the stack level, and its mapping (ugsm_fovea_mapping)
+    int level = 0, left_margin = 0, upper_margin = 0;
+    float scale = 0.0f;
+};
+struct CloudImage {
+    const uint8_t *rgb;
+    int W, H, stride;
+};
+struct CloudTo {
+    void *points;
+    long long cap;
+    long long *count;
+};
 
-// the CloudArgs of a call whose points come from the pw x ph planes dx, dy, conf (conf is only read by a compact cloud)
-CloudArgs cloud_args(const float *dx, const float *dy, const float *conf, const uint8_t *rgb, int W, int H, int stride, int pw, int ph,
-                     const ugsm_cloud_params *p, void *points, long long cap, long long *count)
+// The checks every cloud call shares (no device needed), in the one order they have always had, then the call's CloudArgs (conf is only
+// read by a compact cloud).  resized (the resized forms, which take no sampling: p->sampling 1): the map, whose grid the arguments get.
+int cloud_call_args(const ugsm_ctx *ctx, const CloudFrom &from, const CloudImage &im, const double *P1, const double *P2, const ugsm_cloud_params *p,
+                    const CloudTo &to, CloudArgs &a, const ResizedGrid *resized = nullptr)
 {
-    CloudArgs a{};
-    a.dx = dx;
-    a.dy = dy;
-    a.conf = p->compact ? conf : nullptr;
-    a.pw = pw;
-    a.ph = ph;
-    a.rgb = rgb;
-    a.W = W;
-    a.H = H;
-    a.stride = stride;
+    if (!ctx || !from.dx || !from.dy || !im.rgb || !P1 || !P2 || !p || !to.points || !to.count) return UGSM_ERR_BAD_ARG;
+    if (im.W < 1 || im.H < 1 || from.pw < 1 || from.ph < 1 || (long long)im.W * im.H > kMaxPixels || (long long)from.pw * from.ph > kMaxPixels)
+        return UGSM_ERR_BAD_ARG;
+    if (input_status(ctx, im.W, im.stride, im.rgb) != UGSM_OK || !cloud_records_ok(*p)) return UGSM_ERR_BAD_ARG;
+    if (!keep_window_ok(p->min_conf, p->z_min, p->z_max, from.conf != nullptr)) return UGSM_ERR_BAD_ARG;
+    if (to.cap < 0 || ((uintptr_t)to.points & 15) || ((uintptr_t)to.count & 7)) return UGSM_ERR_BAD_ARG;
+    if (resized && (p->sampling != 1 || resized->dw < 1)) return UGSM_ERR_BAD_ARG;
+    if (from.fovea && (from.level < 0 || from.level >= UGSM_MAX_LEVELS || !std::isfinite(from.scale))) return UGSM_ERR_BAD_ARG;
+    const size_t lvl = from.fovea ? (size_t)from.level * from.pw * from.ph : 0;
+    a = CloudArgs{};
+    a.dx = from.dx + lvl;
+    a.dy = from.dy + lvl;
+    a.conf = p->compact && from.conf ? from.conf + lvl : nullptr;
+    a.pw = from.pw;
+    a.ph = from.ph;
+    a.rgb = im.rgb;
+    a.W = im.W;
+    a.H = im.H;
+    a.stride = im.stride;
     a.s = p->sampling;
     a.format = p->format;
     a.compact = p->compact != 0;
     a.min_conf = p->min_conf;
     a.z_min = p->z_min;
     a.z_max = p->z_max;
-    a.points = points;
-    a.cap = cap;
-    a.count = count;
-    return a;
+    a.left_margin = from.left_margin;
+    a.upper_margin = from.upper_margin;
+    a.scale = from.scale;
+    a.points = to.points;
+    a.cap = to.cap;
+    a.count = to.count;
+    if (resized) {
+        a.wc = resized->dw;
+        a.hc = resized->dh;
+    }
+    return UGSM_OK;
 }
-
-// the resized map: (int)(pw * factor) x (int)(ph * factor) points and cv::resize's scales (resize.cpp: inv_scale = (double)dsize / ssize,
-// scale = 1. / inv_scale)
-CloudResize resize_args(CloudArgs &a, float factor, int colour_mapped)
-{
-    a.wc = (int)((float)a.pw * factor);
-    a.hc = (int)((float)a.ph * factor);
-    CloudResize rz{};
-    rz.scale_x = 1. / ((double)a.wc / a.pw);
-    rz.scale_y = 1. / ((double)a.hc / a.ph);
-    rz.factor = factor;
-    rz.same_size = a.wc == a.pw && a.hc == a.ph;
-    rz.colour_mapped = colour_mapped;
-    return rz;
-}
-
 // The words of a compact cloud's count buffer (CloudArgs.cnt) over `entries` virtual grids of wc columns -- the levels of a stack, the entries
 // of a merged cloud: the entries' (column, chunk) counts, then their column totals and strip totals.
 size_t cloud_cnt_words(int entries, int wc, int nchunk) { return (size_t)entries * ((size_t)wc * nchunk + wc + cloud_strips(wc)); }
 
-// What every slot-level cloud does before its launch: it takes the slot and sets the device, fills in the sampled grid (unless the resized
-// forms have: resize_args), its chunks and the input format and, for a compact cloud, makes the slot's count buffer hold `entries`
-// virtual grids and zeroes their totals on the slot's stream.  table (the merged cloud of several windows): before that, the call's turn of the
-// slot's upload ring -- one row per entry, for the caller to fill and upload.
+// What every cloud derives before its launch and no slot is needed for: the sampled grid (unless the resized forms have theirs), its chunks, the
+// input format, and the region a compact cloud of `entries` virtual grids takes of a count buffer -- its (column, chunk) counts, then the
+// totals, which are zeroed before the launch.
+struct CloudRegion {
+    size_t counts, words;
+};
+CloudRegion cloud_grid(const ugsm_ctx *ctx, CloudArgs &a, int entries)
+{
+    if (!a.wc) {
+        a.wc = sampled(a.pw, a.s);
+        a.hc = sampled(a.ph, a.s);
+    }
+    a.nchunk = cloud_chunks(a.hc);
+    a.fmt = ctx->hooks.input_format;
+    a.cnt = nullptr;
+    return {(size_t)entries * a.wc * a.nchunk, cloud_cnt_words(entries, a.wc, a.nchunk)};
+}
+
+// What every slot-level cloud does before its launch: it takes the slot and sets the device, derives the grid (cloud_grid) and, for a compact
+// cloud, makes the slot's count buffer hold the region and zeroes its totals on the slot's stream.  table (the merged cloud of several
+// windows): before that, the call's turn of the slot's upload ring -- one row per entry, for the caller to fill and upload.
 int cloud_begin(ugsm_ctx *ctx, int slot, CloudArgs &a, int entries, Slot **out, CloudEntry **table = nullptr)
 {
     UCHK(get_slot(ctx, slot, out));
     Slot &s = **out;
     SlotCloud &c = s.cloud;
     HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
-    if (!a.wc) {  // (the resized forms' grid is resize_args')
-        a.wc = (a.pw + a.s - 1) / a.s;
-        a.hc = (a.ph + a.s - 1) / a.s;
-    }
-    a.nchunk = cloud_chunks(a.hc);
-    a.fmt = ctx->hooks.input_format;
-    a.cnt = nullptr;
+    const CloudRegion r = cloud_grid(ctx, a, entries);
     if (table) UCHK(c.mc.begin(ctx, s.st, (size_t)entries, table));
     if (!a.compact) return UGSM_OK;
-    const size_t counts = (size_t)entries * a.wc * a.nchunk, need = cloud_cnt_words(entries, a.wc, a.nchunk);
-    if (need > c.cnt.cap) HIPCHK(ctx, hipStreamSynchronize(s.st));  // (the buffer being replaced may still be read by an earlier cloud)
-    UCHK(c.cnt.grow(ctx, need));
+    if (r.words > c.cnt.cap) HIPCHK(ctx, hipStreamSynchronize(s.st));  // (the buffer being replaced may still be read by an earlier cloud)
+    UCHK(c.cnt.grow(ctx, r.words));
     a.cnt = c.cnt;
-    HIPCHK(ctx, hipMemsetAsync(a.cnt + counts, 0, (need - counts) * sizeof(unsigned), s.st));  // (the totals)
+    HIPCHK(ctx, hipMemsetAsync(a.cnt + r.counts, 0, (r.words - r.counts) * sizeof(unsigned), s.st));  // (the totals)
     return UGSM_OK;
 }
 
@@ -276,20 +314,6 @@ int point_cloud(ugsm_ctx *ctx, int slot, CloudArgs &a, bool fovea, const double 
     Slot *s;
     UCHK(cloud_begin(ctx, slot, a, 1, &s));
     return timed_launch(ctx, s, slot, (double)a.wc * a.hc, [&] { launch_point_cloud(s->st, a, fovea, P1, P2, rz); });
-}
-
-// the foveated forms' planes (level src_level of the stacks) and mapping (ugsm_fovea_mapping)
-int fovea_cloud_args(CloudArgs &a, const float *stackx, const float *stacky, const float *stackc, int fovW, int fovH, int src_level,
-                     int left_margin, int upper_margin, float scale, const uint8_t *rgb, int W, int H, int stride, const ugsm_cloud_params *p,
-                     void *points, long long cap, long long *count)
-{
-    if (src_level < 0 || src_level >= UGSM_MAX_LEVELS || !std::isfinite(scale)) return UGSM_ERR_BAD_ARG;
-    const size_t lvl = (size_t)src_level * fovW * fovH;
-    a = cloud_args(stackx + lvl, stacky + lvl, stackc ? stackc + lvl : nullptr, rgb, W, H, stride, fovW, fovH, p, points, cap, count);
-    a.left_margin = left_margin;
-    a.upper_margin = upper_margin;
-    a.scale = scale;
-    return UGSM_OK;
 }
 
 // The depth image's checks (no device needed) and its kernel arguments.  dx, dy, conf: `in_levels` levels of pw x ph floats each (a field: 1;
@@ -316,10 +340,7 @@ int depth_args_ok(const ugsm_ctx *ctx, const float *dx, const float *dy, const f
     d.z_max = p->z_max;
     d.dw = dw;
     d.dh = dh;
-    d.rz.scale_x = 1. / ((double)dw / pw);  // (as resize_args)
-    d.rz.scale_y = 1. / ((double)dh / ph);
-    d.rz.factor = p->factor;
-    d.rz.same_size = dw == pw && dh == ph;
+    d.rz = resized_grid(pw, ph, p->factor).rz;
     return UGSM_OK;
 }
 
@@ -438,23 +459,21 @@ void ugsm_default_cloud_params(ugsm_cloud_params *p)
 long long ugsm_cloud_points(int W, int H, int sampling)
 {
     if (W < 1 || H < 1 || sampling < 1) return -1;
-    return (long long)((W + sampling - 1) / sampling) * ((H + sampling - 1) / sampling);
+    return (long long)sampled(W, sampling) * sampled(H, sampling);
 }
 
 long long ugsm_resized_cloud_points(int W, int H, float factor)
 {
-    if (W < 1 || H < 1 || !(factor > 0.0f && factor <= 1.0f)) return -1;
-    const int dw = (int)((float)W * factor), dh = (int)((float)H * factor);  // cv::Size(W * f, H * f): float products, truncated
-    if (dw < 1 || dh < 1) return -1;
-    return (long long)dw * dh;
+    const ResizedGrid g = resized_grid(W, H, factor);
+    return g.dw < 1 ? -1 : (long long)g.dw * g.dh;
 }
 
 int ugsm_point_cloud(ugsm_ctx *ctx, int slot, const float *d_dispx, const float *d_dispy, const float *d_conf, const uint8_t *d_rgbL, int W, int H,
                      int stride, const double *P1, const double *P2, const ugsm_cloud_params *p, void *d_points, long long cap_points,
                      long long *d_count)
 {
-    UCHK(cloud_args_ok(ctx, d_dispx, d_dispy, d_conf, d_rgbL, W, H, stride, W, H, P1, P2, p, d_points, cap_points, d_count));
-    CloudArgs a = cloud_args(d_dispx, d_dispy, d_conf, d_rgbL, W, H, stride, W, H, p, d_points, cap_points, d_count);
+    CloudArgs a;
+    UCHK(cloud_call_args(ctx, {d_dispx, d_dispy, d_conf, W, H}, {d_rgbL, W, H, stride}, P1, P2, p, {d_points, cap_points, d_count}, a));
     return point_cloud(ctx, slot, a, false, P1, P2);
 }
 
@@ -462,10 +481,9 @@ int ugsm_point_cloud_fovea(ugsm_ctx *ctx, int slot, const float *d_stackx, const
                            int src_level, int left_margin, int upper_margin, float scale, const uint8_t *d_rgbL, int W, int H, int stride,
                            const double *P1, const double *P2, const ugsm_cloud_params *p, void *d_points, long long cap_points, long long *d_count)
 {
-    UCHK(cloud_args_ok(ctx, d_stackx, d_stacky, d_stackc, d_rgbL, W, H, stride, fovW, fovH, P1, P2, p, d_points, cap_points, d_count));
     CloudArgs a;
-    UCHK(fovea_cloud_args(a, d_stackx, d_stacky, d_stackc, fovW, fovH, src_level, left_margin, upper_margin, scale, d_rgbL, W, H, stride, p,
-                          d_points, cap_points, d_count));
+    UCHK(cloud_call_args(ctx, {d_stackx, d_stacky, d_stackc, fovW, fovH, true, src_level, left_margin, upper_margin, scale}, {d_rgbL, W, H, stride}, P1, P2,
+                         p, {d_points, cap_points, d_count}, a));
     return point_cloud(ctx, slot, a, true, P1, P2);
 }
 
@@ -478,9 +496,9 @@ int ugsm_point_cloud_fovea_all(ugsm_ctx *ctx, int slot, const float *d_stackx, c
     CloudStack sk;
     int fw, fh;
     UCHK(cloud_stack_table(W, H, ctx->cfg.levels, ctx->cfg.fovea_levels, off_x, off_y, p->sampling, sk, &fw, &fh));
-    UCHK(cloud_args_ok(ctx, d_stackx, d_stacky, d_stackc, d_rgbL, W, H, stride, fw, fh, P1, P2, p, d_points, cap_points, d_count));
+    CloudArgs a;
+    UCHK(cloud_call_args(ctx, {d_stackx, d_stacky, d_stackc, fw, fh}, {d_rgbL, W, H, stride}, P1, P2, p, {d_points, cap_points, d_count}, a));
     sk.level_counts = d_level_counts;
-    CloudArgs a = cloud_args(d_stackx, d_stacky, d_stackc, d_rgbL, W, H, stride, fw, fh, p, d_points, cap_points, d_count);
     Slot *s;
     UCHK(cloud_begin(ctx, slot, a, sk.F, &s));
     return timed_launch(ctx, s, slot, (double)sk.F * a.wc * a.hc, [&] { launch_point_cloud_stack(s->st, a, sk, P1, P2); });
@@ -500,8 +518,10 @@ int ugsm_point_cloud_fovea_multi(ugsm_ctx *ctx, int slot, int n, const float *co
     const int F = ctx->cfg.fovea_levels;
     UCHK(cloud_multi_geometry(W, H, ctx->cfg.levels, F, n, off_x, off_y, p->sampling, g));
     const size_t fn = (size_t)g.fw * g.fh, plane = (size_t)F * fn;
-    UCHK(cloud_args_ok(ctx, d_stack[0], d_stack[0] + plane, d_stack[0] + 2 * plane, d_rgbL, W, H, stride, g.fw, g.fh, P1, P2, p, d_points, cap_points, d_count));
-    CloudArgs a = cloud_args(nullptr, nullptr, nullptr, d_rgbL, W, H, stride, g.fw, g.fh, p, d_points, cap_points, d_count);
+    CloudArgs a;
+    UCHK(cloud_call_args(ctx, {d_stack[0], d_stack[0] + plane, d_stack[0] + 2 * plane, g.fw, g.fh}, {d_rgbL, W, H, stride}, P1, P2, p,
+                         {d_points, cap_points, d_count}, a));
+    a.dx = a.dy = a.conf = nullptr;  // (the planes are the table's, entry by entry)
     Slot *s;
     const int E = g.E;
     CloudEntry *rows;
@@ -527,10 +547,10 @@ int ugsm_point_cloud_resized(ugsm_ctx *ctx, int slot, const float *d_dispx, cons
                              int W, int H, int stride, const double *P1, const double *P2, float factor, const ugsm_cloud_params *p,
                              void *d_points, long long cap_points, long long *d_count)
 {
-    UCHK(cloud_args_ok(ctx, d_dispx, d_dispy, d_conf, d_rgbL, W, H, stride, W, H, P1, P2, p, d_points, cap_points, d_count, true, factor));
-    CloudArgs a = cloud_args(d_dispx, d_dispy, d_conf, d_rgbL, W, H, stride, W, H, p, d_points, cap_points, d_count);
-    const CloudResize rz = resize_args(a, factor, 0);
-    return point_cloud(ctx, slot, a, false, P1, P2, &rz);
+    const ResizedGrid g = resized_grid(W, H, factor);
+    CloudArgs a;
+    UCHK(cloud_call_args(ctx, {d_dispx, d_dispy, d_conf, W, H}, {d_rgbL, W, H, stride}, P1, P2, p, {d_points, cap_points, d_count}, a, &g));
+    return point_cloud(ctx, slot, a, false, P1, P2, &g.rz);
 }
 
 int ugsm_point_cloud_resized_fovea(ugsm_ctx *ctx, int slot, const float *d_stackx, const float *d_stacky, const float *d_stackc, int fovW,
@@ -538,13 +558,12 @@ int ugsm_point_cloud_resized_fovea(ugsm_ctx *ctx, int slot, const float *d_stack
                                    int stride, const double *P1, const double *P2, float factor, int colour_mapped, const ugsm_cloud_params *p,
                                    void *d_points, long long cap_points, long long *d_count)
 {
-    UCHK(cloud_args_ok(ctx, d_stackx, d_stacky, d_stackc, d_rgbL, W, H, stride, fovW, fovH, P1, P2, p, d_points, cap_points, d_count, true, factor));
-    if (colour_mapped != 0 && colour_mapped != 1) return UGSM_ERR_BAD_ARG;
+    const ResizedGrid g = resized_grid(fovW, fovH, factor, colour_mapped);
     CloudArgs a;
-    UCHK(fovea_cloud_args(a, d_stackx, d_stacky, d_stackc, fovW, fovH, src_level, left_margin, upper_margin, scale, d_rgbL, W, H, stride, p,
-                          d_points, cap_points, d_count));
-    const CloudResize rz = resize_args(a, factor, colour_mapped);
-    return point_cloud(ctx, slot, a, true, P1, P2, &rz);
+    UCHK(cloud_call_args(ctx, {d_stackx, d_stacky, d_stackc, fovW, fovH, true, src_level, left_margin, upper_margin, scale}, {d_rgbL, W, H, stride}, P1, P2,
+                         p, {d_points, cap_points, d_count}, a, &g));
+    if (colour_mapped != 0 && colour_mapped != 1) return UGSM_ERR_BAD_ARG;
+    return point_cloud(ctx, slot, a, true, P1, P2, &g.rz);
 }
 
 // ---- row f-1, the depth image (REP 118 32FC1 / 16UC1; the reference's range_map and res_range_map, getPointCloud.cpp:730-758, :813-841) ----
@@ -562,9 +581,10 @@ void ugsm_default_depth_params(ugsm_depth_params *p)
 
 int ugsm_depth_image_size(int pw, int ph, float factor, int *dw, int *dh)
 {
-    if (!dw || !dh || ugsm_resized_cloud_points(pw, ph, factor) < 1) return UGSM_ERR_BAD_ARG;
-    *dw = (int)((float)pw * factor);
-    *dh = (int)((float)ph * factor);
+    const ResizedGrid g = resized_grid(pw, ph, factor);
+    if (!dw || !dh || g.dw < 1) return UGSM_ERR_BAD_ARG;
+    *dw = g.dw;
+    *dh = g.dh;
     return UGSM_OK;
 }
 
@@ -608,168 +628,210 @@ int ugsm_depth_image_fovea(ugsm_ctx *ctx, int slot, const float *d_stackx, const
 // chk (a call of checked pairs, ugsm_enqueue_full_checked_cloud*; else null): the match is the checked call's -- both directions of the pairs in
 // lockstep, one pair too, whatever the context's own LR setting --, the clouds read the checked forward fields, and a managed pair that asks
 // for them gets its back planes down beside its forward ones.
-static int cloud_call_submit(ugsm_ctx *ctx, int slot, const CloudCall *call, const CheckedCall *chk)
+// The steps below share the call's plan: what the call is, and what each step has settled for the next.
+namespace {
+struct CloudPlan {
+    const CloudCall *call;
+    const CheckedCall *chk;
+    int n, W, H, stride, F;
+    bool fovea, managed, planes;  // planes: a managed call whose pairs' result planes go down to the host
+    bool by_pair;                 // the matcher takes the call pair by pair
+    int copies;                   // the pairs the slot's buffers hold at once: one for a managed call that runs pair by pair, n otherwise
+    FoveaRoom room;               // a foveated call's states lie at the front of hout
+    int fw, fh;                   // the planes the points come from: the fovea window, or the frame
+    size_t plane;                 // floats per result plane: the pair's result is three of them
+    int step;                     // bytes per record
+    int wc, hc;                   // the sampled grid (step 2)
+    const uint8_t *dL[UGSM_MAX_BATCH], *dR[UGSM_MAX_BATCH];  // step 1: where every pair's images and result lie on the device
+    float *res[UGSM_MAX_BATCH], *back[UGSM_MAX_BATCH];       // back: a checked pair's right-to-left field, where it is taken
+    int ox[UGSM_MAX_BATCH], oy[UGSM_MAX_BATCH];              // (foveated calls: the pairs' window offsets)
+};
+
+// 1. where every pair's images and result lie on the device
+int cloud_call_place(ugsm_ctx *ctx, Slot &s, CloudPlan &q)
 {
-    Slot *s;
-    UCHK(get_slot(ctx, slot, &s));
-    SlotCloud &c = s->cloud;
-    if (!call || !call->spec || call->n < 1 || call->n > UGSM_MAX_BATCH) return UGSM_ERR_BAD_ARG;
-    const ugsm_queue_cloud &spec = *call->spec;
-    const ugsm_cloud_params &p = spec.params;
-    const int n = call->n, W = call->W, H = call->H, stride = call->stride, F = ctx->cfg.fovea_levels;
-    const bool fovea = call->fovea != 0, managed = call->managed != 0, planes = managed && spec.want_planes != 0;
-    if (fovea && F < 2) return UGSM_ERR_BAD_ARG;
-    if (W < 1 || H < 1) return UGSM_ERR_BAD_ARG;
-    for (int b = 0; b < n; b++) UCHK(input_status(ctx, W, stride, call->job[b].L, call->job[b].R));
-    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
-    c.cq_n = 0;
-    if (chk) UCHK(full_checked_check(ctx, n, W, H, stride, chk->tau));
-    const bool by_pair = n == 1 || (!chk && (fovea ? fovea_batch_runs_pair_by_pair(ctx) : batch_runs_pair_by_pair(ctx)));
-    // a foveated call's states lie at the front of hout (FoveaRoom): one for a managed call that runs pair by pair, n otherwise
-    const int copies = managed && by_pair ? 1 : n;
-    FoveaRoom room;
-    if (fovea) UCHK(fovea_room(ctx, W, H, FoveaCall::Pairs, copies, room));
-    const int fw = fovea ? room.fw : W, fh = fovea ? room.fh : H;
-    const size_t plane = fovea ? room.plane : (size_t)W * H;  // floats per result plane: the pair's result is three of them
-    const int step = p.format == UGSM_CLOUD_PCL32 ? 32 : 16;
-
-    // 1. where every pair's images and result lie on the device
-    const uint8_t *dL[UGSM_MAX_BATCH], *dR[UGSM_MAX_BATCH];
-    float *res[UGSM_MAX_BATCH], *back[UGSM_MAX_BATCH] = {nullptr};  // back: a checked pair's right-to-left field, where it is taken
-    const size_t res_per = (3 * plane + 63) & ~(size_t)63;
-    if (managed) {
-        // the slot's uploads and hout: [states][results], one result for a call that runs pair by pair, n otherwise; a checked call: [back fields]
-        // behind them
-        const size_t img = ((size_t)stride * H + 255) & ~(size_t)255;
-        UCHK(s->rgb_cap.grow(ctx, img * copies, {&s->rgbL, &s->rgbR}));
-        bool any_back = false;
-        for (int b = 0; chk && b < n; b++) any_back = any_back || chk->job[b].back_planes[0];
-        const size_t at_res = room.part(copies * res_per), at_back = room.part(any_back ? copies * res_per : 0);
-        UCHK(s->hout.grow(ctx, room.total));
+    const CloudCall &call = *q.call;
+    const CheckedCall *chk = q.chk;
+    const int n = q.n;
+    if (!q.managed) {
+        UCHK(s.hout.grow(ctx, q.room.total));
         for (int b = 0; b < n; b++) {
-            const int k = by_pair ? 0 : b;
-            dL[b] = s->rgbL + k * img;
-            dR[b] = s->rgbR + k * img;
-            res[b] = s->hout + at_res + k * res_per;
-            if (chk && chk->job[b].back_planes[0]) back[b] = s->hout + at_back + k * res_per;
+            if (!call.job[b].L || !call.job[b].R || !call.job[b].out) return UGSM_ERR_BAD_ARG;
+            q.dL[b] = call.job[b].L;
+            q.dR[b] = call.job[b].R;
+            q.res[b] = call.job[b].out;
+            if (chk) q.back[b] = chk->job[b].back;
         }
-    } else {
-        UCHK(s->hout.grow(ctx, room.total));
-        for (int b = 0; b < n; b++) {
-            if (!call->job[b].L || !call->job[b].R || !call->job[b].out) return UGSM_ERR_BAD_ARG;
-            dL[b] = call->job[b].L;
-            dR[b] = call->job[b].R;
-            res[b] = call->job[b].out;
-            if (chk) back[b] = chk->job[b].back;
-        }
+        return UGSM_OK;
     }
+    // the slot's uploads and hout: [states][results], one result for a call that runs pair by pair, n otherwise; a checked call: [back fields]
+    // behind them
+    const size_t res_per = (3 * q.plane + 63) & ~(size_t)63, img = ((size_t)q.stride * q.H + 255) & ~(size_t)255;
+    UCHK(s.rgb_cap.grow(ctx, img * q.copies, {&s.rgbL, &s.rgbR}));
+    bool any_back = false;
+    for (int b = 0; chk && b < n; b++) any_back = any_back || chk->job[b].back_planes[0];
+    const size_t at_res = q.room.part(q.copies * res_per), at_back = q.room.part(any_back ? q.copies * res_per : 0);
+    UCHK(s.hout.grow(ctx, q.room.total));
+    for (int b = 0; b < n; b++) {
+        const int k = q.by_pair ? 0 : b;
+        q.dL[b] = s.rgbL + k * img;
+        q.dR[b] = s.rgbR + k * img;
+        q.res[b] = s.hout + at_res + k * res_per;
+        if (chk && chk->job[b].back_planes[0]) q.back[b] = s.hout + at_back + k * res_per;
+    }
+    return UGSM_OK;
+}
 
-    // 2. the table: every pair's cloud arguments
+// 2. the table: every pair's cloud arguments, uploaded on the slot's stream; a managed call's clouds and count words; the count buffer
+int cloud_call_table(ugsm_ctx *ctx, Slot &s, CloudPlan &q)
+{
+    SlotCloud &c = s.cloud;
+    const ugsm_queue_cloud &spec = *q.call->spec;
+    const ugsm_cloud_params &p = spec.params;
+    const int n = q.n, F = q.F, entries = q.fovea ? F : 1;
     UCHK(c.cq_tab.grow(ctx, (size_t)kMaxBatch));
     UCHK(c.cq_tab_h.grow(ctx, (size_t)kMaxBatch));
-    CloudStack sk[UGSM_MAX_BATCH];
-    long long dense[UGSM_MAX_BATCH], max_cap = 0;
-    int ox[UGSM_MAX_BATCH], oy[UGSM_MAX_BATCH];  // (foveated calls: the pairs' window offsets)
+    long long max_cap = 0;
     for (int b = 0; b < n; b++) {
-        ox[b] = call->job[b].off_x;
-        oy[b] = call->job[b].off_y;
-        if (fovea) {
-            UCHK(cloud_stack_table(W, H, ctx->cfg.levels, F, ox[b], oy[b], p.sampling, sk[b], nullptr, nullptr));
-            dense[b] = sk[b].lv[F - 1].first + sk[b].lv[F - 1].points;
+        CloudStack &sk = c.cq_tab_h[b].sk;
+        q.ox[b] = q.call->job[b].off_x;
+        q.oy[b] = q.call->job[b].off_y;
+        long long dense;
+        if (q.fovea) {  // (the pair's row of the table gets its stack here, the rest below)
+            UCHK(cloud_stack_table(q.W, q.H, ctx->cfg.levels, F, q.ox[b], q.oy[b], p.sampling, sk, nullptr, nullptr));
+            dense = sk.lv[F - 1].first + sk.lv[F - 1].points;
         } else {
-            dense[b] = ugsm_cloud_points(W, H, p.sampling);
+            dense = ugsm_cloud_points(q.W, q.H, p.sampling);
         }
-        c.cq_cap[b] = managed ? (spec.max_points > 0 ? std::min(spec.max_points, dense[b]) : dense[b]) : call->job[b].cap;
+        c.cq_cap[b] = q.managed ? (spec.max_points > 0 ? std::min(spec.max_points, dense) : dense) : q.call->job[b].cap;
         max_cap = std::max(max_cap, c.cq_cap[b]);
     }
-    if (managed) {
-        c.cq_stride = (size_t)max_cap * step;
+    if (q.managed) {
+        c.cq_stride = (size_t)max_cap * q.step;
         UCHK(c.cq_pts.grow(ctx, std::max(c.cq_stride * n, (size_t)16)));
         UCHK(c.cq_words.grow(ctx, kMaxBatch * kCqWords));
         UCHK(c.cq_words_h.grow(ctx, kMaxBatch * kCqWords));
     }
-    const int wc = (fw + p.sampling - 1) / p.sampling, hc = (fh + p.sampling - 1) / p.sampling, nchunk = cloud_chunks(hc);
-    const size_t cnt_per = cloud_cnt_words(fovea ? F : 1, wc, nchunk);  // a pair's region of the count buffer
+    CloudArgs shape{};  // (what every pair's grid comes from)
+    shape.pw = q.fw;
+    shape.ph = q.fh;
+    shape.s = p.sampling;
+    const size_t cnt_per = cloud_grid(ctx, shape, entries).words;  // a pair's region of the count buffer
+    q.wc = shape.wc;
+    q.hc = shape.hc;
     if (p.compact) UCHK(c.cnt.grow(ctx, cnt_per * n));
     for (int b = 0; b < n; b++) {
-        const CloudJob &j = call->job[b];
-        void *points = managed ? (void *)(c.cq_pts + b * c.cq_stride) : j.points;
-        long long *count = managed ? c.cq_words + b * kCqWords : j.count;
-        long long *levels = managed ? c.cq_words + b * kCqWords + 1 : j.level_counts;
-        UCHK(cloud_args_ok(ctx, res[b], res[b] + plane, res[b] + 2 * plane, dL[b], W, H, stride, fw, fh, spec.P1, spec.P2, &p, points, c.cq_cap[b], count));
-        if ((uintptr_t)levels & 7) return UGSM_ERR_BAD_ARG;
+        const CloudJob &j = q.call->job[b];
+        long long *const words = q.managed ? c.cq_words + b * kCqWords : nullptr, *const levels = q.managed ? words + 1 : j.level_counts;
+        const CloudTo to = q.managed ? CloudTo{c.cq_pts + b * c.cq_stride, c.cq_cap[b], words} : CloudTo{j.points, c.cq_cap[b], j.count};
         CloudPair &row = c.cq_tab_h[b];
-        row = CloudPair{};
-        row.a = cloud_args(res[b], res[b] + plane, res[b] + 2 * plane, dL[b], W, H, stride, fw, fh, &p, points, c.cq_cap[b], count);
-        row.a.wc = wc;
-        row.a.hc = hc;
-        row.a.nchunk = nchunk;
-        row.a.fmt = ctx->hooks.input_format;
+        UCHK(cloud_call_args(ctx, {q.res[b], q.res[b] + q.plane, q.res[b] + 2 * q.plane, q.fw, q.fh}, {q.dL[b], q.W, q.H, q.stride}, spec.P1, spec.P2, &p, to,
+                             row.a));
+        if ((uintptr_t)levels & 7) return UGSM_ERR_BAD_ARG;
+        cloud_grid(ctx, row.a, entries);
         row.a.cnt = p.compact ? c.cnt + b * cnt_per : nullptr;
-        if (fovea) {
-            row.sk = sk[b];
-            row.sk.level_counts = levels;
-        }
+        if (q.fovea) row.sk.level_counts = levels;
+        else row.sk = CloudStack{};
     }
-    HIPCHK(ctx, hipMemcpyAsync(c.cq_tab, c.cq_tab_h, n * sizeof(CloudPair), hipMemcpyHostToDevice, s->st));
-    if (p.compact) HIPCHK(ctx, hipMemsetAsync(c.cnt, 0, cnt_per * n * sizeof(unsigned), s->st));  // (the totals of every pair's region)
+    HIPCHK(ctx, hipMemcpyAsync(c.cq_tab, c.cq_tab_h, n * sizeof(CloudPair), hipMemcpyHostToDevice, s.st));
+    if (p.compact) HIPCHK(ctx, hipMemsetAsync(c.cnt, 0, cnt_per * n * sizeof(unsigned), s.st));  // (the totals of every pair's region)
+    return UGSM_OK;
+}
 
-    // 3. the match, and the clouds behind it
-    const size_t img_bytes = (size_t)stride * H;
-    auto download = [&](int b) -> int {  // a managed pair's planes, where they are wanted
-        if (!planes) return UGSM_OK;
-        for (int k = 0; k < 3; k++)
-            HIPCHK(ctx, hipMemcpyAsync(call->job[b].planes[k], res[b] + k * plane, plane * sizeof(float), hipMemcpyDeviceToHost, s->st));
-        return UGSM_OK;
-    };
-    auto download_back = [&](int b) -> int {  // a managed checked pair's back planes, where they are wanted
-        if (!managed || !back[b]) return UGSM_OK;
-        for (int k = 0; k < 3; k++)
-            HIPCHK(ctx, hipMemcpyAsync(chk->job[b].back_planes[k], back[b] + k * plane, plane * sizeof(float), hipMemcpyDeviceToHost, s->st));
-        return UGSM_OK;
-    };
-    auto match = [&](int b, int k) -> int {  // pairs b .. b + k - 1 of the call: one of them, or all in lockstep
-        if (chk) {
-            int kept = 0;
-            for (int j = b; j < b + k; j++) kept += !back[j];
-            UCHK(full_checked_bufs(ctx, *s, k, kept, W, H));
-            return enqueue_full_checked(ctx, *s, slot, k, dL + b, dR + b, W, H, stride, res + b, back + b, chk->tau);
-        }
-        return fovea ? enqueue_foveated(ctx, *s, slot, dL + b, dR + b, W, H, stride, FoveaCall::pairs(k, ox + b, oy + b, res + b))
-                     : enqueue_match_full(ctx, *s, slot, k, dL + b, dR + b, W, H, stride, res + b);
-    };
-    const bool cloud_by_pair = by_pair || !batch_level(ctx, (fovea ? F : 1) * wc, hc);  // (a pair's sampled points against kBatchMaxPixels)
-    if (by_pair) {
+// pairs b .. b + k - 1 of the call: one of them, or all in lockstep
+int cloud_call_match(ugsm_ctx *ctx, Slot &s, int slot, CloudPlan &q, int b, int k)
+{
+    if (q.chk) {
+        int kept = 0;
+        for (int j = b; j < b + k; j++) kept += !q.back[j];
+        UCHK(full_checked_bufs(ctx, s, k, kept, q.W, q.H));
+        return enqueue_full_checked(ctx, s, slot, k, q.dL + b, q.dR + b, q.W, q.H, q.stride, q.res + b, q.back + b, q.chk->tau);
+    }
+    return q.fovea ? enqueue_foveated(ctx, s, slot, q.dL + b, q.dR + b, q.W, q.H, q.stride, FoveaCall::pairs(k, q.ox + b, q.oy + b, q.res + b))
+                   : enqueue_match_full(ctx, s, slot, k, q.dL + b, q.dR + b, q.W, q.H, q.stride, q.res + b);
+}
+
+// a managed pair's planes, and a managed checked pair's back planes, where they are wanted
+int cloud_call_download(ugsm_ctx *ctx, Slot &s, const CloudPlan &q, int b)
+{
+    for (int k = 0; q.planes && k < 3; k++)
+        HIPCHK(ctx, hipMemcpyAsync(q.call->job[b].planes[k], q.res[b] + k * q.plane, q.plane * sizeof(float), hipMemcpyDeviceToHost, s.st));
+    for (int k = 0; q.managed && q.back[b] && k < 3; k++)
+        HIPCHK(ctx, hipMemcpyAsync(q.chk->job[b].back_planes[k], q.back[b] + k * q.plane, q.plane * sizeof(float), hipMemcpyDeviceToHost, s.st));
+    return UGSM_OK;
+}
+
+// 3. the match, and the clouds behind it; a managed call's count words down behind them
+int cloud_call_run(ugsm_ctx *ctx, Slot &s, int slot, CloudPlan &q)
+{
+    SlotCloud &c = s.cloud;
+    const CloudCall &call = *q.call;
+    const ugsm_queue_cloud &spec = *call.spec;
+    const int n = q.n;
+    const size_t img_bytes = (size_t)q.stride * q.H;
+    const bool cloud_by_pair = q.by_pair || !batch_level(ctx, (q.fovea ? q.F : 1) * q.wc, q.hc);  // (a pair's sampled points against kBatchMaxPixels)
+    if (q.by_pair) {
         for (int b = 0; b < n; b++) {
-            if (managed) UCHK(stage_in(ctx, *s, call->job[b].L, call->job[b].R, W, H, stride));
-            UCHK(match(b, 1));
-            UCHK(download(b));
-            UCHK(download_back(b));
-            UCHK(queue_cloud_launch(ctx, *s, slot, b, 1, fovea, &spec));
+            if (q.managed) UCHK(stage_in(ctx, s, call.job[b].L, call.job[b].R, q.W, q.H, q.stride));
+            UCHK(cloud_call_match(ctx, s, slot, q, b, 1));
+            UCHK(cloud_call_download(ctx, s, q, b));
+            UCHK(queue_cloud_launch(ctx, s, slot, b, 1, q.fovea, &spec));
         }
     } else {
-        if (managed)
+        if (q.managed)
             for (int b = 0; b < n; b++) {
-                HIPCHK(ctx, hipMemcpyAsync(const_cast<uint8_t *>(dL[b]), call->job[b].L, img_bytes, hipMemcpyHostToDevice, s->st));
-                HIPCHK(ctx, hipMemcpyAsync(const_cast<uint8_t *>(dR[b]), call->job[b].R, img_bytes, hipMemcpyHostToDevice, s->st));
+                HIPCHK(ctx, hipMemcpyAsync(const_cast<uint8_t *>(q.dL[b]), call.job[b].L, img_bytes, hipMemcpyHostToDevice, s.st));
+                HIPCHK(ctx, hipMemcpyAsync(const_cast<uint8_t *>(q.dR[b]), call.job[b].R, img_bytes, hipMemcpyHostToDevice, s.st));
             }
-        UCHK(match(0, n));
-        for (int b = 0; b < n; b++) {
-            UCHK(download(b));
-            UCHK(download_back(b));
-        }
+        UCHK(cloud_call_match(ctx, s, slot, q, 0, n));
+        for (int b = 0; b < n; b++) UCHK(cloud_call_download(ctx, s, q, b));
         if (cloud_by_pair)
-            for (int b = 0; b < n; b++) UCHK(queue_cloud_launch(ctx, *s, slot, b, 1, fovea, &spec));
+            for (int b = 0; b < n; b++) UCHK(queue_cloud_launch(ctx, s, slot, b, 1, q.fovea, &spec));
         else
-            UCHK(queue_cloud_launch(ctx, *s, slot, 0, n, fovea, &spec));
+            UCHK(queue_cloud_launch(ctx, s, slot, 0, n, q.fovea, &spec));
     }
-    if (managed) {
-        HIPCHK(ctx, hipMemcpyAsync(c.cq_words_h, c.cq_words, n * kCqWords * sizeof(long long), hipMemcpyDeviceToHost, s->st));
+    if (q.managed) {
+        HIPCHK(ctx, hipMemcpyAsync(c.cq_words_h, c.cq_words, n * kCqWords * sizeof(long long), hipMemcpyDeviceToHost, s.st));
         c.cq_n = n;
-        c.cq_step = step;
-        c.cq_levels = fovea ? F : 0;
+        c.cq_step = q.step;
+        c.cq_levels = q.fovea ? q.F : 0;
     }
-    return mark_done(ctx, *s);
+    return mark_done(ctx, s);
+}
+}  // namespace
+
+static int cloud_call_submit(ugsm_ctx *ctx, int slot, const CloudCall *call, const CheckedCall *chk)
+{
+    Slot *s;
+    UCHK(get_slot(ctx, slot, &s));
+    if (!call || !call->spec || call->n < 1 || call->n > UGSM_MAX_BATCH) return UGSM_ERR_BAD_ARG;
+    CloudPlan q{};
+    q.call = call;
+    q.chk = chk;
+    q.n = call->n;
+    q.W = call->W;
+    q.H = call->H;
+    q.stride = call->stride;
+    q.F = ctx->cfg.fovea_levels;
+    q.fovea = call->fovea != 0;
+    q.managed = call->managed != 0;
+    q.planes = q.managed && call->spec->want_planes != 0;
+    if (q.fovea && q.F < 2) return UGSM_ERR_BAD_ARG;
+    if (q.W < 1 || q.H < 1) return UGSM_ERR_BAD_ARG;
+    for (int b = 0; b < q.n; b++) UCHK(input_status(ctx, q.W, q.stride, call->job[b].L, call->job[b].R));
+    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
+    s->cloud.cq_n = 0;
+    if (chk) UCHK(full_checked_check(ctx, q.n, q.W, q.H, q.stride, chk->tau));
+    q.by_pair = q.n == 1 || (!chk && (q.fovea ? fovea_batch_runs_pair_by_pair(ctx) : batch_runs_pair_by_pair(ctx)));
+    q.copies = q.managed && q.by_pair ? 1 : q.n;
+    if (q.fovea) UCHK(fovea_room(ctx, q.W, q.H, FoveaCall::Pairs, q.copies, q.room));
+    q.fw = q.fovea ? q.room.fw : q.W;
+    q.fh = q.fovea ? q.room.fh : q.H;
+    q.plane = q.fovea ? q.room.plane : (size_t)q.W * q.H;
+    q.step = call->spec->params.format == UGSM_CLOUD_PCL32 ? 32 : 16;
+    UCHK(cloud_call_place(ctx, *s, q));
+    UCHK(cloud_call_table(ctx, *s, q));
+    return cloud_call_run(ctx, *s, slot, q);
 }
 
 int ugsm::queue_cloud_submit(ugsm_ctx *ctx, int slot, const CloudCall *call) { return cloud_call_submit(ctx, slot, call, nullptr); }

@@ -9,9 +9,26 @@
 #include <stdint.h>
 #include <stdio.h>
 
+#include <cmath>
 #include <new>
 
 namespace ugsm {
+
+constexpr long long kMaxPixels = 1LL << 28;  // 268 Mpx: 4 B x pixels of one plane stays below 2^31
+
+// Row f-1's rules, stated once for the slot-level calls (ugsm_cloud.cpp) and for the queue, which makes them when a pair is enqueued.
+// The keep window of ugsm_cloud_params / ugsm_depth_params: no NaN among min_conf, z_min and z_max, z_min <= z_max, and no confidence
+// test without a confidence plane (have_conf; the queue's pairs always have one).
+inline bool keep_window_ok(float min_conf, float z_min, float z_max, bool have_conf)
+{
+    if (std::isnan(min_conf) || std::isnan(z_min) || std::isnan(z_max) || z_min > z_max) return false;
+    return have_conf || !(min_conf > -INFINITY);
+}
+// ... and the records of ugsm_cloud_params: the sampling and the format
+inline bool cloud_records_ok(const ugsm_cloud_params &p)
+{
+    return p.sampling >= 1 && (p.format == UGSM_CLOUD_PCL32 || p.format == UGSM_CLOUD_XYZRGB16);
+}
 
 // A call of n pairs with a cloud each (ugsm_enqueue_*_cloud*), as the queue hands it to the runtime through CtxHooks::cloud_submit.
 struct CloudJob {

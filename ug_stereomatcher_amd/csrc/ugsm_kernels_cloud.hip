@@ -496,18 +496,24 @@ __global__ __launch_bounds__(256) void k_triangulate_fovea(const float *__restri
     }
 }
 
+// a 3x4 projection matrix as the kernels take it
+static Proj proj(const double *P)
+{
+    Proj q;
+    for (int k = 0; k < 12; k++) q.m[k] = P[k];
+    return q;
+}
+
 void launch_triangulate(hipStream_t st, const float *dispx, const float *dispy, int W, int H, const double *P1, const double *P2, float *xyz)
 {
-    Proj a, b;
-    for (int k = 0; k < 12; k++) { a.m[k] = P1[k]; b.m[k] = P2[k]; }
+    const Proj a = proj(P1), b = proj(P2);
     UGSM_LAUNCH(k_triangulate<kEmitPlanes>, dim3((W + 255) / 256, H), dim3(256), 0, st, dispx, dispy, W, H, a, b, xyz);
 }
 
 void launch_triangulate_fovea(hipStream_t st, const float *stackx, const float *stacky, int fovW, int fovH, int src_level, int left_margin,
                               int upper_margin, float scale, const double *P1, const double *P2, float *xyz)
 {
-    Proj a, b;
-    for (int k = 0; k < 12; k++) { a.m[k] = P1[k]; b.m[k] = P2[k]; }
+    const Proj a = proj(P1), b = proj(P2);
     UGSM_LAUNCH(k_triangulate_fovea<kEmitPlanes>, dim3((fovW + 255) / 256, fovH), dim3(256), 0, st, stackx, stacky, fovW, fovH, src_level,
                 left_margin, upper_margin, scale, a, b, xyz);
 }
@@ -524,8 +530,7 @@ static unsigned depth_blocks(long long n, bool resized, bool u16)
 void launch_depth_image(hipStream_t st, const float *dispx, const float *dispy, int W, int H, const double *P1, const double *P2, const DepthArgs &d,
                         bool u16)
 {
-    Proj a, b;
-    for (int k = 0; k < 12; k++) { a.m[k] = P1[k]; b.m[k] = P2[k]; }
+    const Proj a = proj(P1), b = proj(P2);
     using Kern = void (*)(const float *, const float *, int, int, Proj, Proj, DepthArgs);
     const bool resized = d.rz.factor < 1.0f;
     const Kern kern = resized ? (u16 ? (Kern)k_triangulate<kEmitResized16U> : (Kern)k_triangulate<kEmitResized32F>)
@@ -536,8 +541,7 @@ void launch_depth_image(hipStream_t st, const float *dispx, const float *dispy, 
 void launch_depth_image_fovea(hipStream_t st, const float *stackx, const float *stacky, int fovW, int fovH, int src_level, const double *P1,
                               const double *P2, const DepthFoveaArgs &d, bool u16)
 {
-    Proj a, b;
-    for (int k = 0; k < 12; k++) { a.m[k] = P1[k]; b.m[k] = P2[k]; }
+    const Proj a = proj(P1), b = proj(P2);
     using Kern = void (*)(const float *, const float *, int, int, int, int, int, float, Proj, Proj, DepthFoveaArgs);
     const bool resized = d.d.rz.factor < 1.0f;
     const Kern kern = resized ? (u16 ? (Kern)k_triangulate_fovea<kEmitResized16U> : (Kern)k_triangulate_fovea<kEmitResized32F>)
@@ -738,20 +742,24 @@ __global__ __launch_bounds__(256) void k_cloud_fovea(CloudArgs a, Proj P1q, Proj
     cloud_tile<true, Form>(a, rz, P1q, P2q);
 }
 
-// the merged cloud of the fovea stack: the workgroup's level from its strip, that level's planes and mapping
-// into its copy of the arguments
-template <int Form>
-__global__ __launch_bounds__(256) void k_cloud_stack(CloudArgs a, Proj P1q, Proj P2q, CloudStack sk)
+// the workgroup's copy of the arguments moved to a level of the stack: the level's planes and mapping
+__device__ __forceinline__ void to_level(CloudArgs &a, const CloudLevel &lv)
 {
-    static_assert(Form == kTriStackCount || Form == kTriStack, "the stack's two launches");
-    const int level = blockIdx.x / sk.strips;
-    const CloudLevel &lv = sk.lv[level];
     a.dx += lv.plane;
     a.dy += lv.plane;
     if (a.conf) a.conf += lv.plane;
     a.left_margin = lv.left_margin;
     a.upper_margin = lv.upper_margin;
     a.scale = lv.scale;
+}
+
+// the merged cloud of the fovea stack: the workgroup's level from its strip, its copy of the arguments moved there
+template <int Form>
+__global__ __launch_bounds__(256) void k_cloud_stack(CloudArgs a, Proj P1q, Proj P2q, CloudStack sk)
+{
+    static_assert(Form == kTriStackCount || Form == kTriStack, "the stack's two launches");
+    const int level = blockIdx.x / sk.strips;
+    to_level(a, sk.lv[level]);
     cloud_tile<true, Form>(a, CloudResize{}, P1q, P2q, &sk, level);
 }
 
@@ -772,13 +780,7 @@ __global__ __launch_bounds__(256) void k_cloud_stack_pairs(const CloudPair *__re
     const CloudPair &row = table[blockIdx.z];
     CloudArgs a = row.a;
     const int level = blockIdx.x / row.sk.strips;
-    const CloudLevel &lv = row.sk.lv[level];
-    a.dx += lv.plane;
-    a.dy += lv.plane;
-    if (a.conf) a.conf += lv.plane;
-    a.left_margin = lv.left_margin;
-    a.upper_margin = lv.upper_margin;
-    a.scale = lv.scale;
+    to_level(a, row.sk.lv[level]);
     cloud_tile<true, Form>(a, CloudResize{}, P1q, P2q, &row.sk, level);
 }
 
@@ -849,10 +851,17 @@ __global__ __launch_bounds__(256) void k_cloud_multi(CloudArgs a, Proj P1q, Proj
 int cloud_strips(int wc) { return (wc + kCloudTC - 1) / kCloudTC; }
 int cloud_chunks(int hc) { return (hc + kCloudTR - 1) / kCloudTR; }
 
+// compact: the count launch, then the cloud launch; dense: the cloud launch
+template <class Kern, class... Args>
+static void launch_cloud(hipStream_t st, bool compact, Kern count, Kern cloud, dim3 grid, const Args &...args)
+{
+    if (compact) UGSM_LAUNCH(count, grid, dim3(256), 0, st, args...);
+    UGSM_LAUNCH(cloud, grid, dim3(256), 0, st, args...);
+}
+
 void launch_point_cloud(hipStream_t st, const CloudArgs &args, bool fovea, const double *P1, const double *P2, const CloudResize *rz)
 {
-    Proj a, b;
-    for (int k = 0; k < 12; k++) { a.m[k] = P1[k]; b.m[k] = P2[k]; }
+    const Proj a = proj(P1), b = proj(P2);
     using Kern = void (*)(CloudArgs, Proj, Proj, CloudResize);
     const Kern count = rz ? (fovea ? (Kern)k_cloud_fovea<kTriResizedCount> : (Kern)k_cloud<kTriResizedCount>)
                           : (fovea ? (Kern)k_cloud_fovea<kTriCloudCount> : (Kern)k_cloud<kTriCloudCount>);
@@ -860,42 +869,35 @@ void launch_point_cloud(hipStream_t st, const CloudArgs &args, bool fovea, const
                           : (fovea ? (Kern)k_cloud_fovea<kTriCloud> : (Kern)k_cloud<kTriCloud>);
     const dim3 grid(cloud_strips(args.wc), args.nchunk);
     const CloudResize r = rz ? *rz : CloudResize{};
-    if (args.compact) UGSM_LAUNCH(count, grid, dim3(256), 0, st, args, a, b, r);
-    UGSM_LAUNCH(cloud, grid, dim3(256), 0, st, args, a, b, r);
+    launch_cloud(st, args.compact != 0, count, cloud, grid, args, a, b, r);
 }
 
 void launch_point_cloud_stack(hipStream_t st, const CloudArgs &args, const CloudStack &sk, const double *P1, const double *P2)
 {
-    Proj a, b;
-    for (int k = 0; k < 12; k++) { a.m[k] = P1[k]; b.m[k] = P2[k]; }
+    const Proj a = proj(P1), b = proj(P2);
     const dim3 grid(sk.F * sk.strips, args.nchunk);
     using Kern = void (*)(CloudArgs, Proj, Proj, CloudStack);
     const Kern count = k_cloud_stack<kTriStackCount>, cloud = k_cloud_stack<kTriStack>;
-    if (args.compact) UGSM_LAUNCH(count, grid, dim3(256), 0, st, args, a, b, sk);
-    UGSM_LAUNCH(cloud, grid, dim3(256), 0, st, args, a, b, sk);
+    launch_cloud(st, args.compact != 0, count, cloud, grid, args, a, b, sk);
 }
 
 void launch_point_cloud_multi(hipStream_t st, const CloudArgs &args, const CloudMulti &mu, const double *P1, const double *P2)
 {
-    Proj a, b;
-    for (int k = 0; k < 12; k++) { a.m[k] = P1[k]; b.m[k] = P2[k]; }
+    const Proj a = proj(P1), b = proj(P2);
     const dim3 grid(mu.E * cloud_strips(args.wc), args.nchunk);
     using Kern = void (*)(CloudArgs, Proj, Proj, CloudMulti);
     const Kern count = k_cloud_multi<kTriMultiCount>, cloud = k_cloud_multi<kTriMulti>;
-    if (args.compact) UGSM_LAUNCH(count, grid, dim3(256), 0, st, args, a, b, mu);
-    UGSM_LAUNCH(cloud, grid, dim3(256), 0, st, args, a, b, mu);
+    launch_cloud(st, args.compact != 0, count, cloud, grid, args, a, b, mu);
 }
 
 void launch_point_cloud_batch(hipStream_t st, const CloudPair *d_table, int n, const CloudPair &shape, bool stack, const double *P1, const double *P2)
 {
-    Proj a, b;
-    for (int k = 0; k < 12; k++) { a.m[k] = P1[k]; b.m[k] = P2[k]; }
+    const Proj a = proj(P1), b = proj(P2);
     using Kern = void (*)(const CloudPair *, Proj, Proj);
     const Kern count = stack ? (Kern)k_cloud_stack_pairs<kTriStackCount> : (Kern)k_cloud_pairs<kTriCloudCount>;
     const Kern cloud = stack ? (Kern)k_cloud_stack_pairs<kTriStack> : (Kern)k_cloud_pairs<kTriCloud>;
     const dim3 grid(stack ? shape.sk.F * shape.sk.strips : cloud_strips(shape.a.wc), shape.a.nchunk, n);
-    if (shape.a.compact) UGSM_LAUNCH(count, grid, dim3(256), 0, st, d_table, a, b);
-    UGSM_LAUNCH(cloud, grid, dim3(256), 0, st, d_table, a, b);
+    launch_cloud(st, shape.a.compact != 0, count, cloud, grid, d_table, a, b);
 }
 
 }  // namespace ugsm

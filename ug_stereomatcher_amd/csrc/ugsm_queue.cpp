@@ -529,17 +529,16 @@ int stage_managed(ugsm_ctx *ctx, Queue *q, Item &it)
     return UGSM_OK;
 }
 
-// What every ugsm_enqueue_*_cloud* checks of its spec and, the device kind, of its cloud buffers: the slot-level cloud calls' own checks
-// (cloud_args_ok, ugsm_cloud.cpp), made when the pair is enqueued so that a bad pair is rejected and never reported
+// What every ugsm_enqueue_*_cloud* checks of its spec and, the device kind, of its cloud buffers: the slot-level cloud calls' own rules
+// (ugsm_internal.hpp), made when the pair is enqueued so that a bad pair is rejected and never reported
 int check_cloud(ugsm_ctx *ctx, const ugsm_queue_cloud *spec, const Item &it)
 {
     const int W = it.W, H = it.H;
     if (!spec) return ctx_fail(ctx, UGSM_ERR_BAD_ARG, "ugsm_enqueue_*_cloud*: null spec");
     const ugsm_cloud_params &p = spec->params;
-    if (W < 1 || H < 1 || (long long)W * H > (1LL << 28)) return ctx_fail(ctx, UGSM_ERR_BAD_ARG, "ugsm_enqueue_*_cloud*: bad image size");
-    if (p.sampling < 1 || (p.format != UGSM_CLOUD_PCL32 && p.format != UGSM_CLOUD_XYZRGB16))
-        return ctx_fail(ctx, UGSM_ERR_BAD_ARG, "ugsm_enqueue_*_cloud*: sampling < 1 or an unknown record format");
-    if (std::isnan(p.min_conf) || std::isnan(p.z_min) || std::isnan(p.z_max) || p.z_min > p.z_max)
+    if (W < 1 || H < 1 || (long long)W * H > kMaxPixels) return ctx_fail(ctx, UGSM_ERR_BAD_ARG, "ugsm_enqueue_*_cloud*: bad image size");
+    if (!cloud_records_ok(p)) return ctx_fail(ctx, UGSM_ERR_BAD_ARG, "ugsm_enqueue_*_cloud*: sampling < 1 or an unknown record format");
+    if (!keep_window_ok(p.min_conf, p.z_min, p.z_max, true))
         return ctx_fail(ctx, UGSM_ERR_BAD_ARG, "ugsm_enqueue_*_cloud*: a NaN min_conf / z_min / z_max, or z_min > z_max");
     if (spec->max_points < 0) return ctx_fail(ctx, UGSM_ERR_BAD_ARG, "ugsm_enqueue_*_cloud*: max_points < 0");
     if (it.mem == MEM_DEVICE && (!it.points || !it.count || it.cap < 0 || ((uintptr_t)it.points & 15) || ((uintptr_t)it.count & 7) || ((uintptr_t)it.level_counts & 7)))

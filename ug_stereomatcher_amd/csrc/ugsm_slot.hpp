@@ -189,7 +189,6 @@ struct ugsm_ctx {
     } while (0)
 
 namespace ugsm {
-constexpr long long kMaxPixels = 1LL << 28;  // 268 Mpx: 4 B x pixels of one plane stays below 2^31
 
 struct FoveaGeom {
     int fw, fh, Wup, Hup;
