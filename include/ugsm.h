@@ -48,7 +48,8 @@ extern "C" {
                                ugsm_submit_full_checked_host, ugsm_enqueue_full_checked, ugsm_enqueue_full_checked_managed,
                                ugsm_enqueue_full_checked_cloud, ugsm_enqueue_full_checked_cloud_managed, ugsm_checked_result, ugsm_done_checked;
                                the depth image (REP 118 32FC1 / 16UC1) -- ugsm_depth_params, UGSM_DEPTH_32F / UGSM_DEPTH_16U / UGSM_DEPTH_ALL_LEVELS,
-                               ugsm_default_depth_params, ugsm_depth_image_size, ugsm_depth_image, ugsm_depth_image_fovea, ugsm_match_full_depth
+                               ugsm_default_depth_params, ugsm_depth_image_size, ugsm_depth_image, ugsm_depth_image_fovea, ugsm_match_full_depth;
+                               lens distortion in triangulation, clouds and depth -- ugsm_set_lens, ugsm_get_lens, ugsm_undistort_points
                                6: the kernel choices follow what is in flight, not ugsm_config.slots: ugsm_plan_level takes `alone`, ugsm_plan_level_in_frame
                                is gone, ugsm_level_plan.latency_policy is .alone; ugsm_enqueue_* returns UGSM_OK once the pair is accepted (a failed
                                CALL is reported through ugsm_completion.status only); the fovea shard carries a status word (a rank that fails still
@@ -976,7 +977,9 @@ int ugsm_point_cloud_resized_fovea(ugsm_ctx *ctx, int slot, const float *d_stack
  * fovea form on a context with fovea_levels < 2.
  *
  * Out of scope: queue forms (ugsm_enqueue_*_depth*); the depth image of several windows or of a reconstructed stack (compose
- * ugsm_reconstruct_full[_multi] with ugsm_depth_image); a strided output; depth in the right camera; camera_info handling; undistortion. */
+ * ugsm_reconstruct_full[_multi] with ugsm_depth_image); a strided output; depth in the right camera; camera_info handling
+ * (a host hands K and D over with ugsm_set_lens, "lens distortion" below); undistortion of the image itself (the lens setting undistorts the
+ * two positions of each correspondence, the image's grid stays the distorted left camera's). */
 #define UGSM_DEPTH_32F 0   /* REP 118 32FC1: float, NaN where there is no reading */
 #define UGSM_DEPTH_16U 1   /* REP 118 16UC1: uint16 millimetres, 0 where there is no reading */
 #define UGSM_DEPTH_ALL_LEVELS (-1)
@@ -1001,6 +1004,50 @@ int ugsm_depth_image_fovea(ugsm_ctx *ctx, int slot, const float *d_stackx, const
 int ugsm_match_full_depth(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride,
                           const double *P1, const double *P2, const ugsm_depth_params *p, void *depth, float *dispH,
                           float *dispV, float *dispC);
+
+/* ---- lens distortion: plumb_bob D in triangulation, clouds and depth -----------------------------------------------------------------
+ *
+ * Every 3-D output above comes from one closed form that takes the two pixel positions (x1, y1), (x2, y2) of a correspondence as ideal
+ * pinhole coordinates under P1 and P2.  With a lens set, (x1, y1) is undistorted by camera 1's K1, D1 and (x2, y2) by camera 2's K2, D2 just
+ * before the closed form.  Images, match and fields stay as they are; nothing is resampled.  (The reference's cloud node reads K and D from
+ * the two CameraInfo messages and never uses them.)
+ *
+ * The definition, for K (3 x 3 row-major: fx = K[0], fy = K[4], cx = K[2], cy = K[5]; skew ignored), D = (k1, k2, p1, p2, k3) and a pixel
+ * coordinate (u, v) held as binary32; every operation binary64 and rounded on its own, division IEEE:
+ *     x0 = ((double)u - cx) / fx;   y0 = ((double)v - cy) / fy;   x = x0; y = y0;
+ *     `iterations` times:
+ *         r2 = x*x + y*y;
+ *         ic = 1.0 / (1.0 + ((k3*r2 + k2)*r2 + k1)*r2);
+ *         dX = 2.0*p1*x*y + p2*(r2 + 2.0*x*x);
+ *         dY = p1*(r2 + 2.0*y*y) + 2.0*p2*x*y;
+ *         x = (x0 - dX)*ic;   y = (y0 - dY)*ic;
+ *     u' = (float)(x*fx + cx);   v' = (float)(y*fy + cy);
+ * -- the fixed-point iteration of OpenCV's undistortPoints with R = I, P = K, restated (not pinned against OpenCV).  With all five
+ * coefficients zero, u' and v' are u and v bit for bit for every coordinate in and around a frame (the binary64 round trip errs by about
+ * 1e-12 px); zero D is not special-cased, and a zero-D lens gives the bytes of no lens.
+ *
+ * Everything else about a point is unchanged: the colour is read at the original pixel; the fovea forms map first and undistort the mapped
+ * positions, and keep (int)x1 of the mapped, distorted x1; the coverage rule of ugsm_point_cloud_fovea_all is a rule about pixels and stays
+ * on the mapped, distorted positions; a compact cloud tests the X, Y, Z that result; record formats, order and counts, and the 16UC1
+ * rounding, are as without a lens.
+ *
+ * ugsm_set_lens: four host arrays (9, 5, 9, 5 doubles) as sensor_msgs/CameraInfo holds them; iterations 1 .. 32, 0 = 5 (OpenCV's count).
+ * All four arrays NULL switches the lens off, the state of a new context.  It is a setting, read when a call is made, as
+ * ugsm_set_input_format: the values travel in the launch's arguments, so a change between two calls enqueued on one slot does not reach the
+ * earlier one.  UGSM_ERR_BAD_ARG -- the setting stays as it was -- for some but not all arrays NULL, a non-finite entry, !(fx > 0) or
+ * !(fy > 0), iterations outside 0 .. 32.
+ * ugsm_get_lens: *set = 1 and the values (any output but `set` may be NULL) while a lens is set, else *set = 0 and nothing else written.
+ * ugsm_undistort_points: the definition on the host for n points, uv_in / uv_out n pairs (u, v) (they may be the same array); needs no
+ * context and no device.  UGSM_ERR_BAD_ARG for a NULL K or D, n < 0, NULL points with n > 0, and the value checks of ugsm_set_lens.
+ *
+ * Honoured by: ugsm_triangulate, ugsm_triangulate_fovea, ugsm_point_cloud, ugsm_point_cloud_fovea, ugsm_point_cloud_fovea_all,
+ * ugsm_point_cloud_resized and ugsm_point_cloud_resized_fovea (every one of the 16 footprint Z), ugsm_depth_image and
+ * ugsm_depth_image_fovea (both formats, any factor, UGSM_DEPTH_ALL_LEVELS), ugsm_match_full_depth.
+ * Refused while a lens is set -- UGSM_ERR_STATE, nothing enqueued, nothing written, ugsm_last_error names the setting --:
+ * ugsm_point_cloud_fovea_multi and every ugsm_enqueue_*_cloud* (the queue's pair records do not capture the lens yet). */
+int ugsm_set_lens(ugsm_ctx *ctx, const double *K1, const double *D1, const double *K2, const double *D2, int iterations);
+int ugsm_get_lens(const ugsm_ctx *ctx, double *K1, double *D1, double *K2, double *D2, int *iterations, int *set);
+int ugsm_undistort_points(const double *K, const double *D, int iterations, const float *uv_in, float *uv_out, long long n);
 
 /* ---- the cloud from the queue: enqueue a pair, get its cloud back ------------------------------------------------------------------
  *

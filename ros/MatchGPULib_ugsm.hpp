@@ -81,6 +81,16 @@ public:
     // (not in the reference) the LR check of a live node: the threshold (0 = off) and the calls that apply it (UGSM_LR_FULL | UGSM_LR_FOVEATED).
     // UGSM_ERR_STATE while pipelined pairs are outstanding.
     int setLRCheck(float tau, int modes) { return ugsm_set_lr_check(ctx_, tau, modes); }
+    // (not in the reference, whose cloud node reads K and D and never uses them) the plumb_bob lens of the two cameras, as the two
+    // sensor_msgs::CameraInfo hold it -- setLens(infoL.K.data(), infoL.D.data(), infoR.K.data(), infoR.D.data()) with D of five entries --:
+    // depthImage, depthImageStack and every cloud taken from context() undistort the two positions of each correspondence before they
+    // triangulate (include/ugsm.h, "lens distortion").  iterations 0 = 5.  The queue's clouds (ugsm_enqueue_*_cloud*) refuse while a lens
+    // is set, so a node that publishes its cloud from the queue leaves it off.
+    int setLens(const double *K1, const double *D1, const double *K2, const double *D2, int iterations = 0)
+    {
+        return ugsm_set_lens(ctx_, K1, D1, K2, D2, iterations);
+    }
+    int clearLens() { return ugsm_set_lens(ctx_, nullptr, nullptr, nullptr, nullptr, 0); }
 
     // (not in the reference) a sensor_msgs::Image -- anything with height, width, step, data and header -- read in place: what the templated
     // calls below take instead of a cv_bridge copy (->image.{rows,cols,step,data}, ->header).  The message must outlive the call.

@@ -54,6 +54,14 @@ own (one context per process), as tools/lr_bench.py does it: this build's child 
 commit with its libraries built -- the parent's child, which times the n calls there, take turns round by round in alternating order;
 every child's value is kept, `spread` is the range between a configuration's own children.  Written beside the numbers: whether the
 merged call takes no longer than the n calls on the parent commit, beyond the spread between those calls' own repeats.
+
+    python tools/cloud_bench.py --lens [--calibration tests/golden/lens_cal.json] [--rig rig16mp] [--rounds 3] [--out profiles/lens_bench.json]
+
+What honouring the lens costs (ugsm_set_lens): at 16 MP with the calibration's K, D and P, from a synthetic field and a random confidence,
+the dense PCL32 cloud, the compact PCL32 cloud (min_conf 0.5) and the dense resized cloud at f = 0.2, each without a lens and with it.
+Every measurement is a child process of its own; the children without and with the lens take turns round by round in alternating order;
+every child's value is kept (device_ms: the median of --reps repeats of the call's in-dispatch kernel time after --warmup).  The result
+goes under "cloud" of --out, beside what tools/depth_bench.py --lens put there.
 """
 import argparse
 import ctypes as C
@@ -501,6 +509,90 @@ def multi_main(args):
         print(f"wrote {args.out}")
 
 
+LENS_CASES = (("dense_pcl32", False, None), ("compact_pcl32", True, None), ("resized_0.2_pcl32", False, 0.2))
+
+
+def lens_rig(path, name):
+    """K1, D1, K2, D2, P1, P2 of rig `name` of a calibration file laid out as tests/golden/lens_cal.json."""
+    r = json.load(open(path))[name]
+    return {k: np.array(r[k], np.float64) for k in ("K1", "D1", "K2", "D2", "P1", "P2")}
+
+
+def lens_child(args):
+    """One size in this process, with the lens or without: prints one line "LENSBENCH <json list of rows>"."""
+    from ug_stereomatcher_amd import _lib, synth
+    rig = lens_rig(args.calibration, args.rig)
+    dp = C.POINTER(C.c_double)
+    P1p, P2p = rig["P1"].ctypes.data_as(dp), rig["P2"].ctypes.data_as(dp)
+    W, H = (int(v) for v in args.size.split("x"))
+    L, _, dx, dy = synth.make_pair(W, H, synth.BASE_SEED + 2)
+    conf = np.random.Generator(np.random.PCG64(7)).uniform(0, 1, (H, W)).astype(np.float32)
+    rows = []
+    with _lib.Context(levels=14, profile_events=2) as c:
+        lib, h = c.lib, c.handle
+        if args.lens_state == "on":
+            c.set_lens(rig["K1"], rig["D1"], rig["K2"], rig["D2"], args.iterations)
+        d = [c.to_device(np.ascontiguousarray(a)) for a in (-dx, dy, conf, L)]     # (the rig's right camera lies on the side of negative disparities)
+        d_pts, d_cnt = c.alloc(W * H * 32), c.alloc(8)
+        for name, compact, factor in LENS_CASES:
+            prm = _lib.cloud_params(compact=compact, min_conf=0.5 if compact else None)
+            if factor is None:
+                call = lambda: c.check(lib.ugsm_point_cloud(h, 0, d[0], d[1], d[2], d[3], W, H, L.strides[0], P1p, P2p, C.byref(prm), d_pts, W * H, d_cnt))
+            else:
+                call = lambda: c.check(lib.ugsm_point_cloud_resized(h, 0, d[0], d[1], d[2], d[3], W, H, L.strides[0], P1p, P2p, C.c_float(factor),
+                                                                    C.byref(prm), d_pts, W * H, d_cnt))
+            t, lo, hi, wall = spread_ms(c, call, args.reps, args.warmup)
+            rows.append(dict(case=name, device_ms=t, device_ms_min=lo, device_ms_max=hi, wall_ms=wall, records=int(c.to_host(d_cnt, (1,), np.int64)[0])))
+        for p in d + [d_pts, d_cnt]:
+            c.free(p)
+    print("LENSBENCH " + json.dumps(rows), flush=True)
+
+
+def lens_merge(out, key, value):
+    """profiles/lens_bench.json holds the cloud tool's and the depth tool's results side by side."""
+    doc = json.load(open(out)) if os.path.exists(out) else {}
+    doc[key] = value
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, "w") as f:
+        json.dump(doc, f, indent=1, sort_keys=True)
+    print(f"wrote {out}")
+
+
+def lens_main(args):
+    import statistics
+    import subprocess
+
+    def measure(state, size):
+        cmd = [sys.executable, os.path.abspath(__file__), "--lens", "--child", "--lens-state", state, "--size", size, "--reps", str(args.reps),
+               "--warmup", str(args.warmup), "--calibration", args.calibration, "--rig", args.rig, "--iterations", str(args.iterations)]
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("LENSBENCH ")]
+        if r.returncode != 0 or not lines:
+            raise SystemExit(f"child failed ({r.returncode}): {' '.join(cmd)}\n{r.stdout[-2000:]}\n{r.stderr[-2000:]}")
+        return json.loads(lines[-1][10:])
+
+    result = dict(tool="tools/cloud_bench.py --lens", rig=args.rig, iterations=args.iterations, rounds=args.rounds, reps=args.reps, warmup=args.warmup,
+                  cases=[])
+    for size in args.sizes.split(","):
+        kept = {"off": [], "on": []}
+        for rnd in range(args.rounds):
+            for state in (("off", "on") if rnd % 2 == 0 else ("on", "off")):     # alternating order
+                kept[state].append(measure(state, size))
+                print(size, "lens", state, "round", rnd, flush=True)
+        for k, first in enumerate(kept["off"][0]):
+            case = dict(size=size, case=first["case"], records=first["records"], records_lens=kept["on"][0][k]["records"])
+            for state, tag in (("off", "no_lens"), ("on", "lens")):
+                ms = [ch[k]["device_ms"] for ch in kept[state]]
+                case[tag + "_device_ms"] = round(statistics.median(ms), 4)
+                case[tag + "_device_ms_children"] = [round(v, 4) for v in ms]
+                case[tag + "_device_ms_spread"] = round(max(ms) - min(ms), 4)
+                case[tag + "_wall_ms"] = round(statistics.median(ch[k]["wall_ms"] for ch in kept[state]), 4)
+            case["lens_over_no_lens"] = round(case["lens_device_ms"] / case["no_lens_device_ms"], 3)
+            result["cases"].append(case)
+            print(json.dumps({a: b for a, b in case.items() if not a.endswith("_children")}), flush=True)
+    lens_merge(args.out or os.path.join(ROOT, "profiles", "lens_bench.json"), "cloud", result)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=25)
@@ -518,10 +610,19 @@ def main():
     ap.add_argument("--child", action="store_true", help="(internal) --multi: measure in this process")
     ap.add_argument("--tree", default=ROOT, help="(internal) the tree whose package the child loads")
     ap.add_argument("--size", default="4928x3264", help="(internal)")
+    ap.add_argument("--lens", action="store_true", help="the dense, compact and resized cloud without a lens and with it instead")
+    ap.add_argument("--calibration", default=os.path.join(ROOT, "tests", "golden", "lens_cal.json"), help="--lens: K, D, P of the two cameras")
+    ap.add_argument("--rig", default="rig16mp", help="--lens: the rig of the calibration file")
+    ap.add_argument("--iterations", type=int, default=5, help="--lens: ugsm_set_lens's iterations")
+    ap.add_argument("--lens-state", choices=("off", "on"), default="off", help="(internal) --lens: the child's setting")
     ap.add_argument("--out")
     args = ap.parse_args()
     if args.multi:
         return multi_child(args) if args.child else multi_main(args)
+    if args.lens:
+        if args.sizes == "4928x3264,1920x1080":
+            args.sizes = "4928x3264"
+        return lens_child(args) if args.child else lens_main(args)
     from ug_stereomatcher_amd import _lib, synth
     import torch
     rows = []

@@ -17,6 +17,12 @@ of the parent build (DIR: a checkout of the parent commit with its libraries bui
                       (12 + 4), each without d_valid and with it (`_count`: one hipMemsetAsync more per call, and the launch's one integer
                       atomic per wave on one word), beside the HBM bound W * H * bytes / peak.
 
+    python tools/depth_bench.py --lens [--calibration tests/golden/lens_cal.json] [--rig rig16mp] [--rounds 3] [--out profiles/lens_bench.json]
+
+What honouring the lens costs (ugsm_set_lens): the `kernel` regions alone, with the calibration's K, D and P, in children without a lens
+(`kernel`) and with it (`kernel_lens`) that take turns round by round; the result goes under "depth" of --out, beside what
+tools/cloud_bench.py --lens put there.
+
 Every child's value is kept; a row gives the median and the spread (max - min) of its children.  No number is fixed here: a ratio counts
 as a difference only where it exceeds the spread between children of one configuration."""
 import argparse
@@ -43,7 +49,11 @@ ap.add_argument("--warmup", type=int, default=4)
 ap.add_argument("--region", type=float, default=0.3, help="seconds a timed kernel region should last")
 ap.add_argument("--sizes", nargs="*", default=list(SIZES))
 ap.add_argument("--configs", nargs="*", default=None, help="the configurations to measure (default: all)")
-ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "depth_bench.json"))
+ap.add_argument("--lens", action="store_true", help="the kernel regions without a lens and with it instead")
+ap.add_argument("--calibration", default=os.path.join(ROOT, "tests", "golden", "lens_cal.json"), help="--lens: K, D, P of the two cameras")
+ap.add_argument("--rig", default="rig16mp", help="--lens: the rig of the calibration file")
+ap.add_argument("--iterations", type=int, default=5, help="--lens: ugsm_set_lens's iterations")
+ap.add_argument("--out", default=None, help="default: profiles/depth_bench.json (--lens: profiles/lens_bench.json)")
 ap.add_argument("--child", default=None, help="(internal) the configuration to measure in this process")
 ap.add_argument("--size", default="16mp", help="(internal)")
 ap.add_argument("--tree", default=ROOT, help="(internal)")
@@ -78,6 +88,11 @@ def child():
     z = np.load(args.images)
     L, R, field = np.ascontiguousarray(z["L"]), np.ascontiguousarray(z["R"]), np.ascontiguousarray(z["field"])
     P1, P2 = rig()
+    cal = None
+    if args.lens:   # the calibration's projections; its right camera lies on the side of negative disparities
+        cal = {k: np.array(v, np.float64) for k, v in json.load(open(args.calibration))[args.rig].items() if isinstance(v, list)}
+        P1, P2 = cal["P1"].reshape(3, 4), cal["P2"].reshape(3, 4)
+        field[0] = -field[0]
     case = args.child[0]
     out = {}
 
@@ -91,6 +106,8 @@ def child():
         return dict(ms=statistics.median(ts), ms_min=min(ts), ms_max=max(ts))
 
     with _lib.Context(levels=LEVELS, slots=1) as c:
+        if args.child.endswith("_lens"):
+            c.set_lens(cal["K1"], cal["D1"], cal["K2"], cal["D2"], args.iterations)
         if case == "a":
             dF, dX = c.to_device(field), c.alloc(3 * n * 4)
 
@@ -149,6 +166,8 @@ def measure(config, size, images, parent):
     tree = parent if config.endswith("_parent") else ROOT
     cmd = [sys.executable, os.path.abspath(__file__), "--child", config, "--size", size, "--tree", tree, "--images", images, "--reps", str(args.reps),
            "--warmup", str(args.warmup), "--region", str(args.region)]
+    if args.lens:
+        cmd += ["--lens", "--calibration", args.calibration, "--rig", args.rig, "--iterations", str(args.iterations)]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("DEPTHBENCH ")]
     if r.returncode != 0 or not lines:
@@ -164,6 +183,9 @@ def main():
     if parent and not os.path.exists(os.path.join(parent, "ug_stereomatcher_amd", "libugsm.so")):
         raise SystemExit(f"{parent}: no built ug_stereomatcher_amd/libugsm.so")
     configs = [k for k in (args.configs or CONFIGS) if parent or not k.endswith("_parent")]
+    if args.lens:
+        configs = ["kernel", "kernel_lens"]
+        args.sizes = [s for s in args.sizes if s == "16mp"] or ["16mp"]
     result = dict(tool="tools/depth_bench.py", levels=LEVELS, rounds=args.rounds, reps=args.reps, parent_measured=bool(parent), unit=UNIT,
                   hbm_peak_spec_bytes_per_s=HBM_PEAK_SPEC, hbm_peak_measured_bytes_per_s=HBM_PEAK_MEASURED,
                   timing="a, b, c, d: host clock around one blocking step, the median of `reps` after `warmup`; kernel: region / reps", sizes={})
@@ -175,22 +197,22 @@ def main():
             np.savez(images, L=L, R=R, field=np.stack([dx, dy, np.full((H, W), 0.75, np.float32)]).astype(np.float32))
             kept = {k: [] for k in configs}
             for rnd in range(args.rounds):
-                for k in configs:       # (the parent's children and this build's alternate)
+                for k in (configs if rnd % 2 == 0 or not args.lens else configs[::-1]):       # (the parent's children and this build's alternate)
                     kept[k].append(measure(k, size, images, parent))
-                print(size, rnd, {k: round(v[-1]["ms"], 3) for k, v in kept.items() if k != "kernel"}, flush=True)
+                print(size, rnd, {k: round(v[-1]["ms"], 3) for k, v in kept.items() if not k.startswith("kernel")}, flush=True)
             row = dict(W=W, H=H, configs={}, kernel={})
             med = {}
             for k in configs:
-                if k == "kernel":
+                if k.startswith("kernel"):
                     continue
                 ms = [x["ms"] for x in kept[k]]
                 med[k] = statistics.median(ms)
                 row["configs"][k] = dict(ms=med[k], ms_children=ms, spread_ms=max(ms) - min(ms), children=kept[k])
-            for name in (kept["kernel"][0] if "kernel" in kept else ()):
-                us = [x[name]["us_per_call"] for x in kept["kernel"]]
-                m, nbytes = statistics.median(us), kept["kernel"][0][name]["bytes"]
-                row["kernel"][name] = dict(us_per_call=m, us_per_call_children=us, spread_us=max(us) - min(us), bytes=nbytes,
-                                           reps=[x[name]["reps"] for x in kept["kernel"]],
+            for cfg, name in [(cfg, name) for cfg in ("kernel", "kernel_lens") if cfg in kept for name in kept[cfg][0]]:
+                us = [x[name]["us_per_call"] for x in kept[cfg]]
+                m, nbytes = statistics.median(us), kept[cfg][0][name]["bytes"]
+                row.setdefault(cfg, {})[name] = dict(us_per_call=m, us_per_call_children=us, spread_us=max(us) - min(us), bytes=nbytes,
+                                           reps=[x[name]["reps"] for x in kept[cfg]],
                                            hbm_bound_us_spec=nbytes / HBM_PEAK_SPEC * 1e6, hbm_bound_us_measured=nbytes / HBM_PEAK_MEASURED * 1e6,
                                            bytes_per_s=nbytes / (m * 1e-6))
             a = "a_parent" if parent else "a_this"
@@ -205,9 +227,15 @@ def main():
                 row["c_this_minus_c_parent_ms"] = med["c_this"] - med["c_parent"]
             result["sizes"][size] = row
             print(json.dumps({k: v for k, v in row.items() if k not in ("configs",)}), flush=True)
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    json.dump(result, open(args.out, "w"), indent=1, sort_keys=True)
-    print(f"wrote {args.out}")
+    out = args.out or os.path.join(ROOT, "profiles", "lens_bench.json" if args.lens else "depth_bench.json")
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    if args.lens:   # beside the cloud tool's result
+        result.update(tool="tools/depth_bench.py --lens", rig=args.rig, iterations=args.iterations)
+        doc = json.load(open(out)) if os.path.exists(out) else {}
+        doc["depth"] = result
+        result = doc
+    json.dump(result, open(out, "w"), indent=1, sort_keys=True)
+    print(f"wrote {out}")
 
 
 if __name__ == "__main__":

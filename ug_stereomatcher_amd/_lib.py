@@ -82,6 +82,8 @@ EXPORTS = [
     "ugsm_enqueue_full_checked_cloud_managed", "ugsm_done_checked",
     # the depth image (REP 118)
     "ugsm_default_depth_params", "ugsm_depth_image_size", "ugsm_depth_image", "ugsm_depth_image_fovea", "ugsm_match_full_depth",
+    # lens distortion in triangulation, clouds and depth
+    "ugsm_set_lens", "ugsm_get_lens", "ugsm_undistort_points",
 ]
 # ... and what include/ugsm_dev.h adds (libugsm_dev.so only)
 DEV_EXPORTS = ["ugsm_stage_poly_probe", "ugsm_stage_div3_probe", "ugsm_stage_div_probe", "ugsm_stage_range_words", "ugsm_stage_iterate_rgb8", "ugsm_stage_level0_direct"]
@@ -446,6 +448,9 @@ def load(dev: bool = False):
     lib.ugsm_depth_image.argtypes = [vp, i, vp, vp, vp, i, i, dpp, dpp, C.POINTER(DepthParams), vp, vp]
     lib.ugsm_depth_image_fovea.argtypes = [vp, i, vp, vp, vp, i, i, i, i, i, dpp, dpp, C.POINTER(DepthParams), vp, vp]
     lib.ugsm_match_full_depth.argtypes = [vp, vp, vp, i, i, i, dpp, dpp, C.POINTER(DepthParams), vp, vp, vp, vp]
+    lib.ugsm_set_lens.argtypes = [vp, dpp, dpp, dpp, dpp, i]
+    lib.ugsm_get_lens.argtypes = [vp, dpp, dpp, dpp, dpp, ip, ip]
+    lib.ugsm_undistort_points.argtypes = [dpp, dpp, i, vp, vp, C.c_longlong]
     if bool(lib.ugsm_is_dev_library()) != bool(dev):
         raise UgsmError(UGSM_ERR_STATE, f"{path} is not the {'development' if dev else 'product'} build")
     _libs[dev] = lib
@@ -532,6 +537,26 @@ def depth_params(format: int = UGSM_DEPTH_32F, unit: float | None = None, min_co
         if v is not None:
             setattr(p, name, float(v))
     return p
+
+
+def _doubles(a, n: int, what: str):
+    a = np.ascontiguousarray(a, np.float64).reshape(-1)
+    if a.size != n:
+        raise UgsmError(UGSM_ERR_BAD_ARG, f"{what}: {n} values")
+    return (C.c_double * n)(*a)
+
+
+def undistort_points(K, D, uv, iterations: int = 5) -> np.ndarray:
+    """The lens definition of include/ugsm.h on the host (ugsm_undistort_points; no context, no device): uv of shape (..., 2), float32 pixel
+    coordinates (u, v) under K (3 x 3) and D = (k1, k2, p1, p2, k3); returns the undistorted coordinates in the same shape."""
+    src = np.ascontiguousarray(uv, np.float32)
+    if src.ndim < 1 or src.shape[-1] != 2:
+        raise UgsmError(UGSM_ERR_BAD_ARG, "undistort_points: uv of shape (..., 2)")
+    dst = np.empty_like(src)
+    st = load().ugsm_undistort_points(_doubles(K, 9, "K"), _doubles(D, 5, "D"), int(iterations), src.ctypes.data, dst.ctypes.data, src.size // 2)
+    if st != UGSM_OK:
+        raise UgsmError(st, "ugsm_undistort_points")
+    return dst
 
 
 def depth_image_size(pw: int, ph: int, factor: float = 1.0):
@@ -678,6 +703,24 @@ class Context:
         tau, modes = C.c_float(), C.c_int()
         self.check(self.lib.ugsm_get_lr_check(self._h, C.byref(tau), C.byref(modes)))
         return tau.value, modes.value
+
+    # ---- lens distortion (ugsm_set_lens): read by every triangulation, cloud and depth call when it is made ------------------------------
+    def set_lens(self, K1, D1, K2, D2, iterations: int = 5):
+        """K (3 x 3) and D = (k1, k2, p1, p2, k3) of the left and the right camera, as sensor_msgs/CameraInfo holds them."""
+        self.check(self.lib.ugsm_set_lens(self._h, _doubles(K1, 9, "K1"), _doubles(D1, 5, "D1"), _doubles(K2, 9, "K2"), _doubles(D2, 5, "D2"),
+                                          int(iterations)))
+
+    def clear_lens(self):
+        self.check(self.lib.ugsm_set_lens(self._h, None, None, None, None, 0))
+
+    def get_lens(self):
+        """None while no lens is set, else (K1, D1, K2, D2, iterations) with K of shape (3, 3)."""
+        K1, K2, D1, D2 = (C.c_double * 9)(), (C.c_double * 9)(), (C.c_double * 5)(), (C.c_double * 5)()
+        it, on = C.c_int(), C.c_int()
+        self.check(self.lib.ugsm_get_lens(self._h, K1, D1, K2, D2, C.byref(it), C.byref(on)))
+        if not on.value:
+            return None
+        return np.array(K1).reshape(3, 3), np.array(D1), np.array(K2).reshape(3, 3), np.array(D2), it.value
 
     def last_lr_marked(self, slot: int = 0) -> int:
         return int(self.lib.ugsm_last_lr_marked(self._h, slot))

@@ -313,7 +313,7 @@ int point_cloud(ugsm_ctx *ctx, int slot, CloudArgs &a, bool fovea, const double 
 {
     Slot *s;
     UCHK(cloud_begin(ctx, slot, a, 1, &s));
-    return timed_launch(ctx, s, slot, (double)a.wc * a.hc, [&] { launch_point_cloud(s->st, a, fovea, P1, P2, rz); });
+    return timed_launch(ctx, s, slot, (double)a.wc * a.hc, [&] { launch_point_cloud(s->st, a, fovea, P1, P2, rz, ctx_lens(ctx)); });
 }
 
 // The depth image's checks (no device needed) and its kernel arguments.  dx, dy, conf: `in_levels` levels of pw x ph floats each (a field: 1;
@@ -375,7 +375,7 @@ int ugsm_triangulate(ugsm_ctx *ctx, int slot, const float *d_dispx, const float 
     UCHK(get_slot(ctx, slot, &s));
     if (!d_dispx || !d_dispy || !P1 || !P2 || !d_xyz || W < 1 || H < 1) return UGSM_ERR_BAD_ARG;
     HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
-    return timed_launch(ctx, s, slot, (double)W * H, [&] { launch_triangulate(s->st, d_dispx, d_dispy, W, H, P1, P2, d_xyz); });
+    return timed_launch(ctx, s, slot, (double)W * H, [&] { launch_triangulate(s->st, d_dispx, d_dispy, W, H, P1, P2, d_xyz, ctx_lens(ctx)); });
 }
 
 // CdynamicCalibration::left_marginOf_in / upper_marginOf_in / mapXcoord (getPointCloud.cpp:387-484)
@@ -440,7 +440,7 @@ int ugsm_triangulate_fovea(ugsm_ctx *ctx, int slot, const float *d_stackx, const
     if (!d_stackx || !d_stacky || !P1 || !P2 || !d_xyz || fovW < 1 || fovH < 1 || src_level < 0) return UGSM_ERR_BAD_ARG;
     HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
     return timed_launch(ctx, s, slot, (double)fovW * fovH,
-                        [&] { launch_triangulate_fovea(s->st, d_stackx, d_stacky, fovW, fovH, src_level, left_margin, upper_margin, scale, P1, P2, d_xyz); });
+                        [&] { launch_triangulate_fovea(s->st, d_stackx, d_stacky, fovW, fovH, src_level, left_margin, upper_margin, scale, P1, P2, d_xyz, ctx_lens(ctx)); });
 }
 
 // ---- row f-1, the coloured point cloud (getPointCloud.cpp doReconstructionRGB[_FOV], :615-722) ----------------------------------------
@@ -501,7 +501,7 @@ int ugsm_point_cloud_fovea_all(ugsm_ctx *ctx, int slot, const float *d_stackx, c
     sk.level_counts = d_level_counts;
     Slot *s;
     UCHK(cloud_begin(ctx, slot, a, sk.F, &s));
-    return timed_launch(ctx, s, slot, (double)sk.F * a.wc * a.hc, [&] { launch_point_cloud_stack(s->st, a, sk, P1, P2); });
+    return timed_launch(ctx, s, slot, (double)sk.F * a.wc * a.hc, [&] { launch_point_cloud_stack(s->st, a, sk, P1, P2, ctx_lens(ctx)); });
 }
 
 // The stacks of n windows of one pair as one cloud: the entries level-major, each without what the rule across windows leaves out
@@ -512,6 +512,8 @@ int ugsm_point_cloud_fovea_multi(ugsm_ctx *ctx, int slot, int n, const float *co
                                  long long cap_points, long long *d_count, long long *d_entry_counts)
 {
     if (!ctx || !p || !d_stack || n < 1 || n > UGSM_MAX_BATCH || ((uintptr_t)d_entry_counts & 7)) return UGSM_ERR_BAD_ARG;
+    if (ctx->hooks.lens_set)
+        return ctx_fail(ctx, UGSM_ERR_STATE, "ugsm_point_cloud_fovea_multi: a lens is set (ugsm_set_lens) and the merged cloud of several windows does not honour it");
     for (int j = 0; j < n; j++)
         if (!d_stack[j]) return UGSM_ERR_BAD_ARG;
     MultiCloud g;
@@ -594,7 +596,7 @@ int ugsm_depth_image(ugsm_ctx *ctx, int slot, const float *d_dispx, const float 
     DepthArgs d;
     UCHK(depth_args_ok(ctx, d_dispx, d_dispy, d_conf, 1, W, H, 1, P1, P2, p, d_depth, d_valid, d));
     const bool u16 = p->format == UGSM_DEPTH_16U;
-    return depth_image(ctx, slot, d, 1, [&](hipStream_t st) { launch_depth_image(st, d_dispx, d_dispy, W, H, P1, P2, d, u16); });
+    return depth_image(ctx, slot, d, 1, [&](hipStream_t st) { launch_depth_image(st, d_dispx, d_dispy, W, H, P1, P2, d, u16, ctx_lens(ctx)); });
 }
 
 int ugsm_depth_image_fovea(ugsm_ctx *ctx, int slot, const float *d_stackx, const float *d_stacky, const float *d_stackc, int W, int H, int off_x,
@@ -613,7 +615,71 @@ int ugsm_depth_image_fovea(ugsm_ctx *ctx, int slot, const float *d_stackx, const
     const bool u16 = p->format == UGSM_DEPTH_16U;
     const int src_level = all ? 0 : level;
     return depth_image(ctx, slot, f.d, f.lv.levels,
-                       [&](hipStream_t st) { launch_depth_image_fovea(st, d_stackx, d_stacky, fw, fh, src_level, P1, P2, f, u16); });
+                       [&](hipStream_t st) { launch_depth_image_fovea(st, d_stackx, d_stacky, fw, fh, src_level, P1, P2, f, u16, ctx_lens(ctx)); });
+}
+
+// ---- lens distortion (include/ugsm.h): the setting, and the definition on the host --------------------------------------------------
+
+// one camera's K (3 x 3, row-major) and D (k1, k2, p1, p2, k3) as the kernels take them; false: a non-finite entry, !(fx > 0) or !(fy > 0)
+static bool lens_cam(const double *K, const double *D, LensCam &c)
+{
+    for (int k = 0; k < 9; k++)
+        if (!std::isfinite(K[k])) return false;
+    for (int k = 0; k < 5; k++)
+        if (!std::isfinite(D[k])) return false;
+    if (!(K[0] > 0.0) || !(K[4] > 0.0)) return false;
+    c = LensCam{K[0], K[4], K[2], K[5], D[0], D[1], D[2], D[3], D[4]};
+    return true;
+}
+// 0 means the default; false: outside 1 .. 32
+static bool lens_iterations(int &iterations)
+{
+    if (iterations == 0) iterations = 5;
+    return iterations >= 1 && iterations <= 32;
+}
+
+int ugsm_set_lens(ugsm_ctx *ctx, const double *K1, const double *D1, const double *K2, const double *D2, int iterations)
+{
+    if (!ctx) return UGSM_ERR_BAD_ARG;
+    const int given = (K1 != nullptr) + (D1 != nullptr) + (K2 != nullptr) + (D2 != nullptr);
+    if (given == 0) {  // off
+        ctx->hooks.lens_set = false;
+        return UGSM_OK;
+    }
+    if (given != 4) return ctx_fail(ctx, UGSM_ERR_BAD_ARG, "ugsm_set_lens: K1, D1, K2 and D2 are all set or all null");
+    Lens ln{};
+    if (!lens_cam(K1, D1, ln.cam[0]) || !lens_cam(K2, D2, ln.cam[1]))
+        return ctx_fail(ctx, UGSM_ERR_BAD_ARG, "ugsm_set_lens: every entry of K and D finite, fx > 0 and fy > 0");
+    if (!lens_iterations(iterations)) return ctx_fail(ctx, UGSM_ERR_BAD_ARG, "ugsm_set_lens: iterations 1 .. 32 (0: the default, 5)");
+    ln.iterations = iterations;
+    ctx->lens = ln;
+    std::copy(K1, K1 + 9, ctx->lens_K[0]);
+    std::copy(K2, K2 + 9, ctx->lens_K[1]);
+    ctx->hooks.lens_set = true;
+    return UGSM_OK;
+}
+
+int ugsm_get_lens(const ugsm_ctx *ctx, double *K1, double *D1, double *K2, double *D2, int *iterations, int *set)
+{
+    if (!ctx || !set) return UGSM_ERR_BAD_ARG;
+    *set = ctx->hooks.lens_set ? 1 : 0;
+    if (!ctx->hooks.lens_set) return UGSM_OK;
+    double *const K[2] = {K1, K2}, *const D[2] = {D1, D2};
+    for (int c = 0; c < 2; c++) {
+        const LensCam &m = ctx->lens.cam[c];
+        if (K[c]) std::copy(ctx->lens_K[c], ctx->lens_K[c] + 9, K[c]);
+        if (D[c]) D[c][0] = m.k1, D[c][1] = m.k2, D[c][2] = m.p1, D[c][3] = m.p2, D[c][4] = m.k3;
+    }
+    if (iterations) *iterations = ctx->lens.iterations;
+    return UGSM_OK;
+}
+
+int ugsm_undistort_points(const double *K, const double *D, int iterations, const float *uv_in, float *uv_out, long long n)
+{
+    LensCam c;
+    if (!K || !D || n < 0 || (n > 0 && (!uv_in || !uv_out)) || !lens_cam(K, D, c) || !lens_iterations(iterations)) return UGSM_ERR_BAD_ARG;
+    for (long long i = 0; i < n; i++) undistort_point(c, iterations, uv_in[2 * i], uv_in[2 * i + 1], uv_out[2 * i], uv_out[2 * i + 1]);
+    return UGSM_OK;
 }
 
 }  // extern "C"

@@ -93,6 +93,9 @@ struct CtxHooks {
     // ugsm_set_input_format: the format of the images the next calls hand over (the queue stores it with each pair and sets it back while
     // it sends the pair's call)
     int input_format = UGSM_INPUT_RGB8;
+    // ugsm_set_lens: a lens is set.  The queue's cloud pairs and the merged cloud of several windows refuse then (include/ugsm.h, "lens
+    // distortion"); the values themselves are the runtime's.
+    bool lens_set = false;
 };
 // ugsm_input_bytes_per_pixel: 3, 3, 4, 4, 1 for UGSM_INPUT_RGB8 .. UGSM_INPUT_MONO8, -1 otherwise
 inline int input_bpp(int format)

@@ -7,6 +7,7 @@
 // Citations: /root/reference/src/gpu_matcher/<file>:<line> unless a path is given.
 #include "ugsm_device.hpp"
 #include "ugsm_launch.hpp"
+#include "ugsm_lens.hpp"
 
 namespace ugsm {
 
@@ -62,6 +63,22 @@ __device__ __forceinline__ void tri_point(float x1, float y1, float x2, float y2
     Z = ZUp / divisor;
 }
 
+// ... under a lens (ugsm_set_lens; ugsm_lens.hpp): the two positions undistorted, each by its own camera, just before the closed form.  The
+// caller keeps the distorted (x1, y1): the colour, the fovea forms' (int)x1 and the coverage rule are about pixels.
+__device__ __forceinline__ void tri_point_lens(const Lens &ln, float x1, float y1, float x2, float y2, const double *P1, const double *P2, float &X,
+                                               float &Y, float &Z)
+{
+    float u1, v1, u2, v2;
+    undistort_point(ln.cam[0], ln.iterations, x1, y1, u1, v1);
+    undistort_point(ln.cam[1], ln.iterations, x2, y2, u2, v2);
+    tri_point(u1, v1, u2, v2, P1, P2, X, Y, Z);
+}
+// A kernel that honours the lens is the same kernel with one more argument, the Lens by value behind its last (template parameter pack
+// LensArg: empty, or Lens); the instances without it keep the argument list and the code they had.  L below: the launch has a lens, and ln
+// points at it (else null and not read).
+__device__ __forceinline__ const Lens *lens_of() { return nullptr; }
+__device__ __forceinline__ const Lens *lens_of(const Lens &ln) { return &ln; }
+
 // =========================================================================================
 // SURVEY 8f row f-1, second half: the coloured point cloud, getPointCloud.cpp doReconstructionRGB (:675-722) and
 // doReconstructionRGB_FOV (:615-673) -- the node's scalar double loop over the pixels with one push_back per pixel.
@@ -89,9 +106,9 @@ constexpr int kCloudPad = kCloudTR + 1;  // records per column in LDS: column c 
 
 // X, Y, Z of pixel (ii, jj) of the planes, from the same operands as the plane kernels (bit-identical to them); (x1, y1) the pixel in the
 // full-resolution frame.
-template <bool Fovea>
+template <bool Fovea, bool L = false>
 __device__ __forceinline__ void tri_at(const CloudArgs &a, const Proj &P1q, const Proj &P2q, int ii, int jj, float &x1, float &y1, float &X,
-                                       float &Y, float &Z)
+                                       float &Y, float &Z, const Lens *ln = nullptr)
 {
     const size_t at = (size_t)jj * a.pw + ii;
     float x2, y2;
@@ -108,15 +125,16 @@ __device__ __forceinline__ void tri_at(const CloudArgs &a, const Proj &P1q, cons
         x2 = ii + a.dx[at];
         y2 = jj + a.dy[at];
     }
-    tri_point(x1, y1, x2, y2, P1q.m, P2q.m, X, Y, Z);
+    if constexpr (L) tri_point_lens(*ln, x1, y1, x2, y2, P1q.m, P2q.m, X, Y, Z);
+    else tri_point(x1, y1, x2, y2, P1q.m, P2q.m, X, Y, Z);
 }
 // ... from the pixel's disparity (ddx, ddy), for a caller that has loaded it already: the depth image's runs, which read eight pixels'
 // disparities with 16-byte loads.  The operands are tri_at's, line for line, with the loaded value where tri_at reads the plane; the two stay
 // apart because tri_at written as a call of this one moved the register allocation of k_cloud_fovea<kTriResized> (tools/isa_dump.py --diff),
 // and tests/test_gpu_depth.py holds them to the same bits.
-template <bool Fovea>
+template <bool Fovea, bool L = false>
 __device__ __forceinline__ void tri_of(const CloudArgs &a, const Proj &P1q, const Proj &P2q, int ii, int jj, float ddx, float ddy, float &x1, float &y1,
-                                       float &X, float &Y, float &Z)
+                                       float &X, float &Y, float &Z, const Lens *ln = nullptr)
 {
     float x2, y2;
     if (Fovea) {  // as k_triangulate_fovea
@@ -132,7 +150,8 @@ __device__ __forceinline__ void tri_of(const CloudArgs &a, const Proj &P1q, cons
         x2 = ii + ddx;
         y2 = jj + ddy;
     }
-    tri_point(x1, y1, x2, y2, P1q.m, P2q.m, X, Y, Z);
+    if constexpr (L) tri_point_lens(*ln, x1, y1, x2, y2, P1q.m, P2q.m, X, Y, Z);
+    else tri_point(x1, y1, x2, y2, P1q.m, P2q.m, X, Y, Z);
 }
 
 // The colour word of pixel cx of an image row in any input format (UGSM_INPUT_*; fmt is uniform): R << 16 | G << 8 | B of the pixel's
@@ -179,11 +198,11 @@ __device__ __forceinline__ bool cloud_keep(const CloudArgs &a, size_t at, float 
 }
 
 // one sampled point: its record (x, y, z, rgb word as float bits) and whether a compact cloud keeps it
-template <bool Fovea, bool Colour>
-__device__ __forceinline__ bool cloud_point(const CloudArgs &a, const Proj &P1q, const Proj &P2q, int ii, int jj, float4 &rec)
+template <bool Fovea, bool Colour, bool L = false>
+__device__ __forceinline__ bool cloud_point(const CloudArgs &a, const Proj &P1q, const Proj &P2q, int ii, int jj, float4 &rec, const Lens *ln = nullptr)
 {
     float x1, y1, X, Y, Z;
-    tri_at<Fovea>(a, P1q, P2q, ii, jj, x1, y1, X, Y, Z);
+    tri_at<Fovea, L>(a, P1q, P2q, ii, jj, x1, y1, X, Y, Z, ln);
     if (Colour) {  // the foveated kernels: at ((int)mapXcoord(ii), (int)mapYcoord(jj)) of the full-resolution image (:630-640), clamped (colour_at)
         const int cx = Fovea ? min(max((int)x1, 0), a.W - 1) : ii, cy = Fovea ? min(max((int)y1, 0), a.H - 1) : jj;
         rec = make_float4(X, Y, Z, __uint_as_float(colour_word(a.rgb + (size_t)cy * a.stride, cx, a.fmt)));
@@ -221,15 +240,15 @@ __device__ __forceinline__ void cubic_tap(int d, double scale, int n, int &s, fl
 
 // Rec (the depth image's use): the record is written whether or not there is a colour to read -- (X, Y, Z, 0) -- so that rec.z hands the
 // resized map's Z to a caller that keeps nothing else
-template <bool Fovea, bool Colour, bool Rec = Colour>
+template <bool Fovea, bool Colour, bool Rec = Colour, bool L = false>
 __device__ __forceinline__ bool resized_point(const CloudArgs &a, const CloudResize &rz, const Proj &P1q, const Proj &P2q, int ii, int jj,
-                                              float4 &rec)
+                                              float4 &rec, const Lens *ln = nullptr)
 {
     // (ii < (int)(pw * f) keeps ii / f below pw; the clamp never acts)
     const int xx = min((int)((float)ii / rz.factor), a.pw - 1);
     const int yy = min((int)((float)jj / rz.factor), a.ph - 1);
     float x1, y1, X, Y, Z;
-    tri_at<Fovea>(a, P1q, P2q, xx, yy, x1, y1, X, Y, Z);
+    tri_at<Fovea, L>(a, P1q, P2q, xx, yy, x1, y1, X, Y, Z, ln);
     // the colour is read before the taps: its loads go out with the centre pixel's dx, dy, not one round trip after the taps
     const bool mapped = Fovea && rz.colour_mapped;
     const unsigned word = Colour ? colour_at<Fovea>(a, mapped ? (int)x1 : xx, mapped ? (int)y1 : yy) : 0u;
@@ -247,7 +266,7 @@ __device__ __forceinline__ bool resized_point(const CloudArgs &a, const CloudRes
 #pragma unroll
             for (int k = 0; k < 4; k++) {
                 float u1, u2, u3, u4;
-                tri_at<Fovea>(a, P1q, P2q, min(max(sx - 1 + k, 0), a.pw - 1), ty, u1, u2, u3, u4, s[k]);
+                tri_at<Fovea, L>(a, P1q, P2q, min(max(sx - 1 + k, 0), a.pw - 1), ty, u1, u2, u3, u4, s[k], ln);
             }
             const float p0 = s[0] * cx[0];
             const float h = (((border ? 0.0f + p0 : p0) + s[1] * cx[1]) + s[2] * cx[2]) + s[3] * cx[3];
@@ -306,8 +325,8 @@ __device__ __forceinline__ void depth_count(const DepthArgs &d, int level, unsig
 // (0 .. Run-1): run 0 is the head, the last run the tail, and both go element by element; every run between them is stored with one 16-byte
 // store, and loaded with 16-byte loads where dx, dy and conf are 16-byte aligned at pixel `head` too (else with 4-byte loads).  Nothing but a
 // pixel's own bytes is written.  A workgroup takes 256 runs at a time and walks on by the grid's width.
-template <bool Fovea, bool U16>
-__device__ __forceinline__ void depth_run(const CloudArgs &a, const DepthArgs &d, const Proj &P1q, const Proj &P2q, int level)
+template <bool Fovea, bool U16, bool L>
+__device__ __forceinline__ void depth_run(const CloudArgs &a, const DepthArgs &d, const Proj &P1q, const Proj &P2q, int level, const Lens *ln)
 {
     constexpr int Size = U16 ? 2 : 4, Run = 16 / Size;
     const int n = a.pw * a.ph;
@@ -350,7 +369,7 @@ __device__ __forceinline__ void depth_run(const CloudArgs &a, const DepthArgs &d
             bits[e] = 0;
             if (full || (i >= 0 && i < n)) {
                 float x1, y1, X, Y, Z;
-                tri_of<Fovea>(a, P1q, P2q, xx, yy, ddx[e], ddy[e], x1, y1, X, Y, Z);
+                tri_of<Fovea, L>(a, P1q, P2q, xx, yy, ddx[e], ddy[e], x1, y1, X, Y, Z, ln);
                 valid = depth_element<U16>(d, Z, cf[e], bits[e]);
                 if (++xx == a.pw) {
                     xx = 0;
@@ -381,8 +400,8 @@ __device__ __forceinline__ void depth_run(const CloudArgs &a, const DepthArgs &d
 // tri_at).  Z is the z of resized_point's record -- the resized clouds' own routine, with no colour to read and nothing to keep (`a` is a
 // dense cloud's: compact 0) --; the confidence is read where that routine registers the pixel, (xx, yy) = ((int)((float)ii / factor),
 // (int)((float)jj / factor)), inside the plane as there.
-template <bool Fovea, bool U16>
-__device__ __forceinline__ void depth_resized(const CloudArgs &a, const DepthArgs &d, const Proj &P1q, const Proj &P2q, int level)
+template <bool Fovea, bool U16, bool L>
+__device__ __forceinline__ void depth_resized(const CloudArgs &a, const DepthArgs &d, const Proj &P1q, const Proj &P2q, int level, const Lens *ln)
 {
     const int n = d.dw * d.dh;
     unsigned count = 0;
@@ -394,7 +413,7 @@ __device__ __forceinline__ void depth_resized(const CloudArgs &a, const DepthArg
             const int xx = min((int)((float)ii / d.rz.factor), a.pw - 1), yy = min((int)((float)jj / d.rz.factor), a.ph - 1);
             const float cf = a.conf ? a.conf[(size_t)yy * a.pw + xx] : 0.0f;
             float4 rec;
-            resized_point<Fovea, false, true>(a, d.rz, P1q, P2q, ii, jj, rec);
+            resized_point<Fovea, false, true, L>(a, d.rz, P1q, P2q, ii, jj, rec, ln);
             unsigned bits;
             valid = depth_element<U16>(d, rec.z, cf, bits);
             const size_t o = (size_t)level * n + i;
@@ -420,10 +439,12 @@ struct TriOut<kEmitPlanes> {
     using fovea = float *__restrict__;
 };
 
-template <int Emit>
+template <int Emit, class... LensArg>
 __global__ __launch_bounds__(256) void k_triangulate(const float *__restrict__ dispx, const float *__restrict__ dispy, int W, int H, Proj P1q, Proj P2q,
-                                                     typename TriOut<Emit>::field out)
+                                                     typename TriOut<Emit>::field out, LensArg... lens)
 {
+    constexpr bool L = sizeof...(LensArg) != 0;
+    [[maybe_unused]] const Lens *const ln = lens_of(lens...);
     if constexpr (Emit == kEmitPlanes) {
         float *__restrict__ xyz = out;
         const int xx = blockIdx.x * blockDim.x + threadIdx.x;
@@ -436,7 +457,8 @@ __global__ __launch_bounds__(256) void k_triangulate(const float *__restrict__ d
         x2 = xx + dispx[at];
         y2 = yy + dispy[at];
         float X, Y, Z;
-        tri_point(x1, y1, x2, y2, P1q.m, P2q.m, X, Y, Z);
+        if constexpr (L) tri_point_lens(*ln, x1, y1, x2, y2, P1q.m, P2q.m, X, Y, Z);
+        else tri_point(x1, y1, x2, y2, P1q.m, P2q.m, X, Y, Z);
         xyz[at] = X;
         xyz[n + at] = Y;
         xyz[2 * n + at] = Z;
@@ -447,8 +469,8 @@ __global__ __launch_bounds__(256) void k_triangulate(const float *__restrict__ d
         a.conf = out.conf;
         a.pw = W;
         a.ph = H;
-        if constexpr (Emit == kEmitDepth32F || Emit == kEmitDepth16U) depth_run<false, Emit == kEmitDepth16U>(a, out, P1q, P2q, 0);
-        else depth_resized<false, Emit == kEmitResized16U>(a, out, P1q, P2q, 0);
+        if constexpr (Emit == kEmitDepth32F || Emit == kEmitDepth16U) depth_run<false, Emit == kEmitDepth16U, L>(a, out, P1q, P2q, 0, ln);
+        else depth_resized<false, Emit == kEmitResized16U, L>(a, out, P1q, P2q, 0, ln);
     }
 }
 
@@ -456,11 +478,13 @@ __global__ __launch_bounds__(256) void k_triangulate(const float *__restrict__ d
 // coordinates mapped into the full-resolution frame by mapXcoord / mapYcoord (:387-421).  Those take an int, so the
 // right-image coordinate xx + disparity is truncated toward zero before scaling -- kept as in the reference.
 // The depth forms: blockIdx.y = the level among the launch's (src_level the first), its mapping from the table.
-template <int Emit>
+template <int Emit, class... LensArg>
 __global__ __launch_bounds__(256) void k_triangulate_fovea(const float *__restrict__ stackx, const float *__restrict__ stacky, int fovW, int fovH,
                                                            int src_level, int left_margin, int upper_margin, float scale, Proj P1q, Proj P2q,
-                                                           typename TriOut<Emit>::fovea out)
+                                                           typename TriOut<Emit>::fovea out, LensArg... lens)
 {
+    constexpr bool L = sizeof...(LensArg) != 0;
+    [[maybe_unused]] const Lens *const ln = lens_of(lens...);
     if constexpr (Emit == kEmitPlanes) {
         float *__restrict__ xyz = out;
         const int xx = blockIdx.x * blockDim.x + threadIdx.x;
@@ -475,7 +499,8 @@ __global__ __launch_bounds__(256) void k_triangulate_fovea(const float *__restri
         const float x2 = (float)left_margin + (float)sx * scale;
         const float y2 = (float)upper_margin + (float)sy * scale;
         float X, Y, Z;
-        tri_point(x1, y1, x2, y2, P1q.m, P2q.m, X, Y, Z);
+        if constexpr (L) tri_point_lens(*ln, x1, y1, x2, y2, P1q.m, P2q.m, X, Y, Z);
+        else tri_point(x1, y1, x2, y2, P1q.m, P2q.m, X, Y, Z);
         xyz[at] = X;
         xyz[n + at] = Y;
         xyz[2 * n + at] = Z;
@@ -491,8 +516,8 @@ __global__ __launch_bounds__(256) void k_triangulate_fovea(const float *__restri
         a.left_margin = out.lv.left[level];
         a.upper_margin = out.lv.upper[level];
         a.scale = out.lv.scale[level];
-        if constexpr (Emit == kEmitDepth32F || Emit == kEmitDepth16U) depth_run<true, Emit == kEmitDepth16U>(a, out.d, P1q, P2q, k);
-        else depth_resized<true, Emit == kEmitResized16U>(a, out.d, P1q, P2q, k);
+        if constexpr (Emit == kEmitDepth32F || Emit == kEmitDepth16U) depth_run<true, Emit == kEmitDepth16U, L>(a, out.d, P1q, P2q, k, ln);
+        else depth_resized<true, Emit == kEmitResized16U, L>(a, out.d, P1q, P2q, k, ln);
     }
 }
 
@@ -504,18 +529,26 @@ static Proj proj(const double *P)
     return q;
 }
 
-void launch_triangulate(hipStream_t st, const float *dispx, const float *dispy, int W, int H, const double *P1, const double *P2, float *xyz)
+// Every launcher below picks the instance from its `lens` (null: none): the same grid and arguments, the Lens by value behind them.
+#define UGSM_LAUNCH_LENS(lens, plain, with_lens, grid, st, ...)                                  \
+    do {                                                                                       \
+        if (lens) UGSM_LAUNCH(with_lens, grid, dim3(256), 0, st, __VA_ARGS__, *(lens));        \
+        else UGSM_LAUNCH(plain, grid, dim3(256), 0, st, __VA_ARGS__);                          \
+    } while (0)
+
+void launch_triangulate(hipStream_t st, const float *dispx, const float *dispy, int W, int H, const double *P1, const double *P2, float *xyz,
+                        const Lens *lens)
 {
     const Proj a = proj(P1), b = proj(P2);
-    UGSM_LAUNCH(k_triangulate<kEmitPlanes>, dim3((W + 255) / 256, H), dim3(256), 0, st, dispx, dispy, W, H, a, b, xyz);
+    UGSM_LAUNCH_LENS(lens, (k_triangulate<kEmitPlanes>), (k_triangulate<kEmitPlanes, Lens>), dim3((W + 255) / 256, H), st, dispx, dispy, W, H, a, b, xyz);
 }
 
 void launch_triangulate_fovea(hipStream_t st, const float *stackx, const float *stacky, int fovW, int fovH, int src_level, int left_margin,
-                              int upper_margin, float scale, const double *P1, const double *P2, float *xyz)
+                              int upper_margin, float scale, const double *P1, const double *P2, float *xyz, const Lens *lens)
 {
     const Proj a = proj(P1), b = proj(P2);
-    UGSM_LAUNCH(k_triangulate_fovea<kEmitPlanes>, dim3((fovW + 255) / 256, fovH), dim3(256), 0, st, stackx, stacky, fovW, fovH, src_level,
-                left_margin, upper_margin, scale, a, b, xyz);
+    UGSM_LAUNCH_LENS(lens, (k_triangulate_fovea<kEmitPlanes>), (k_triangulate_fovea<kEmitPlanes, Lens>), dim3((fovW + 255) / 256, fovH), st, stackx, stacky,
+                     fovW, fovH, src_level, left_margin, upper_margin, scale, a, b, xyz);
 }
 
 // workgroups of a depth launch over one level of n pixels: the plain forms' runs (n / Run whole ones, the head's and the tail's), the
@@ -528,26 +561,32 @@ static unsigned depth_blocks(long long n, bool resized, bool u16)
 }
 
 void launch_depth_image(hipStream_t st, const float *dispx, const float *dispy, int W, int H, const double *P1, const double *P2, const DepthArgs &d,
-                        bool u16)
+                        bool u16, const Lens *lens)
 {
     const Proj a = proj(P1), b = proj(P2);
     using Kern = void (*)(const float *, const float *, int, int, Proj, Proj, DepthArgs);
+    using KernLens = void (*)(const float *, const float *, int, int, Proj, Proj, DepthArgs, Lens);
     const bool resized = d.rz.factor < 1.0f;
     const Kern kern = resized ? (u16 ? (Kern)k_triangulate<kEmitResized16U> : (Kern)k_triangulate<kEmitResized32F>)
                               : (u16 ? (Kern)k_triangulate<kEmitDepth16U> : (Kern)k_triangulate<kEmitDepth32F>);
-    UGSM_LAUNCH(kern, dim3(depth_blocks((long long)d.dw * d.dh, resized, u16)), dim3(256), 0, st, dispx, dispy, W, H, a, b, d);
+    const KernLens kern_lens = resized ? (u16 ? (KernLens)k_triangulate<kEmitResized16U, Lens> : (KernLens)k_triangulate<kEmitResized32F, Lens>)
+                                       : (u16 ? (KernLens)k_triangulate<kEmitDepth16U, Lens> : (KernLens)k_triangulate<kEmitDepth32F, Lens>);
+    UGSM_LAUNCH_LENS(lens, kern, kern_lens, dim3(depth_blocks((long long)d.dw * d.dh, resized, u16)), st, dispx, dispy, W, H, a, b, d);
 }
 
 void launch_depth_image_fovea(hipStream_t st, const float *stackx, const float *stacky, int fovW, int fovH, int src_level, const double *P1,
-                              const double *P2, const DepthFoveaArgs &d, bool u16)
+                              const double *P2, const DepthFoveaArgs &d, bool u16, const Lens *lens)
 {
     const Proj a = proj(P1), b = proj(P2);
     using Kern = void (*)(const float *, const float *, int, int, int, int, int, float, Proj, Proj, DepthFoveaArgs);
+    using KernLens = void (*)(const float *, const float *, int, int, int, int, int, float, Proj, Proj, DepthFoveaArgs, Lens);
     const bool resized = d.d.rz.factor < 1.0f;
     const Kern kern = resized ? (u16 ? (Kern)k_triangulate_fovea<kEmitResized16U> : (Kern)k_triangulate_fovea<kEmitResized32F>)
                               : (u16 ? (Kern)k_triangulate_fovea<kEmitDepth16U> : (Kern)k_triangulate_fovea<kEmitDepth32F>);
-    UGSM_LAUNCH(kern, dim3(depth_blocks((long long)d.d.dw * d.d.dh, resized, u16), d.lv.levels), dim3(256), 0, st, stackx, stacky, fovW, fovH,
-                src_level, 0, 0, 0.0f, a, b, d);
+    const KernLens kern_lens = resized ? (u16 ? (KernLens)k_triangulate_fovea<kEmitResized16U, Lens> : (KernLens)k_triangulate_fovea<kEmitResized32F, Lens>)
+                                       : (u16 ? (KernLens)k_triangulate_fovea<kEmitDepth16U, Lens> : (KernLens)k_triangulate_fovea<kEmitDepth32F, Lens>);
+    UGSM_LAUNCH_LENS(lens, kern, kern_lens, dim3(depth_blocks((long long)d.d.dw * d.d.dh, resized, u16), d.lv.levels), st, stackx, stacky, fovW, fovH,
+                     src_level, 0, 0, 0.0f, a, b, d);
 }
 
 // The merged cloud of the whole fovea stack (ugsm_point_cloud_fovea_all; kTriStackCount / kTriStack): the same tile over F * strips
@@ -593,9 +632,9 @@ enum TriForm : int {
     kTriCloudCount = 1, kTriCloud = 2, kTriResizedCount = 3, kTriResized = 4, kTriStackCount = 5, kTriStack = 6, kTriMultiCount = 7, kTriMulti = 8
 };
 
-template <bool Fovea, int Form>
+template <bool Fovea, int Form, bool L = false>
 __device__ __forceinline__ void cloud_tile(const CloudArgs &a, const CloudResize &rz, const Proj &P1q, const Proj &P2q, const CloudStack *sk = nullptr,
-                                           int level = 0, const CloudMulti *mu = nullptr, const MultiTile *mt = nullptr)
+                                           int level = 0, const CloudMulti *mu = nullptr, const MultiTile *mt = nullptr, const Lens *ln = nullptr)
 {
     constexpr bool Stack = Form == kTriStackCount || Form == kTriStack;
     constexpr bool Multi = Form == kTriMultiCount || Form == kTriMulti;  // (level: the entry; its early return is the kernel's)
@@ -631,9 +670,9 @@ __device__ __forceinline__ void cloud_tile(const CloudArgs &a, const CloudResize
         if (ci < a.wc && cj < a.hc && !covered) {
             float4 v;
             if constexpr (Form == kTriResizedCount || Form == kTriResized)
-                k = resized_point<Fovea, Write>(a, rz, P1q, P2q, ci, cj, v);
+                k = resized_point<Fovea, Write, Write, L>(a, rz, P1q, P2q, ci, cj, v, ln);
             else
-                k = cloud_point<Fovea, Write>(a, P1q, P2q, ci * a.s, cj * a.s, v);
+                k = cloud_point<Fovea, Write, L>(a, P1q, P2q, ci * a.s, cj * a.s, v, ln);
             if (Write) rec[c * kCloudPad + r] = v;
         }
         kept[c * kCloudTR + r] = k;
@@ -731,15 +770,15 @@ __device__ __forceinline__ void cloud_tile(const CloudArgs &a, const CloudResize
 }
 
 // the cloud of one field / of one fovea level; rz: the resized cloud's (unused by the others)
-template <int Form>
-__global__ __launch_bounds__(256) void k_cloud(CloudArgs a, Proj P1q, Proj P2q, CloudResize rz)
+template <int Form, class... LensArg>
+__global__ __launch_bounds__(256) void k_cloud(CloudArgs a, Proj P1q, Proj P2q, CloudResize rz, LensArg... lens)
 {
-    cloud_tile<false, Form>(a, rz, P1q, P2q);
+    cloud_tile<false, Form, sizeof...(LensArg) != 0>(a, rz, P1q, P2q, nullptr, 0, nullptr, nullptr, lens_of(lens...));
 }
-template <int Form>
-__global__ __launch_bounds__(256) void k_cloud_fovea(CloudArgs a, Proj P1q, Proj P2q, CloudResize rz)
+template <int Form, class... LensArg>
+__global__ __launch_bounds__(256) void k_cloud_fovea(CloudArgs a, Proj P1q, Proj P2q, CloudResize rz, LensArg... lens)
 {
-    cloud_tile<true, Form>(a, rz, P1q, P2q);
+    cloud_tile<true, Form, sizeof...(LensArg) != 0>(a, rz, P1q, P2q, nullptr, 0, nullptr, nullptr, lens_of(lens...));
 }
 
 // the workgroup's copy of the arguments moved to a level of the stack: the level's planes and mapping
@@ -754,13 +793,13 @@ __device__ __forceinline__ void to_level(CloudArgs &a, const CloudLevel &lv)
 }
 
 // the merged cloud of the fovea stack: the workgroup's level from its strip, its copy of the arguments moved there
-template <int Form>
-__global__ __launch_bounds__(256) void k_cloud_stack(CloudArgs a, Proj P1q, Proj P2q, CloudStack sk)
+template <int Form, class... LensArg>
+__global__ __launch_bounds__(256) void k_cloud_stack(CloudArgs a, Proj P1q, Proj P2q, CloudStack sk, LensArg... lens)
 {
     static_assert(Form == kTriStackCount || Form == kTriStack, "the stack's two launches");
     const int level = blockIdx.x / sk.strips;
     to_level(a, sk.lv[level]);
-    cloud_tile<true, Form>(a, CloudResize{}, P1q, P2q, &sk, level);
+    cloud_tile<true, Form, sizeof...(LensArg) != 0>(a, CloudResize{}, P1q, P2q, &sk, level, nullptr, nullptr, lens_of(lens...));
 }
 
 // The same clouds for the pairs of a queue call in one launch: blockIdx.z = the pair, whose row of the table in
@@ -859,23 +898,38 @@ static void launch_cloud(hipStream_t st, bool compact, Kern count, Kern cloud, d
     UGSM_LAUNCH(cloud, grid, dim3(256), 0, st, args...);
 }
 
-void launch_point_cloud(hipStream_t st, const CloudArgs &args, bool fovea, const double *P1, const double *P2, const CloudResize *rz)
+void launch_point_cloud(hipStream_t st, const CloudArgs &args, bool fovea, const double *P1, const double *P2, const CloudResize *rz, const Lens *lens)
 {
     const Proj a = proj(P1), b = proj(P2);
+    const dim3 grid(cloud_strips(args.wc), args.nchunk);
+    const CloudResize r = rz ? *rz : CloudResize{};
+    if (lens) {
+        using Kern = void (*)(CloudArgs, Proj, Proj, CloudResize, Lens);
+        const Kern count = rz ? (fovea ? (Kern)k_cloud_fovea<kTriResizedCount, Lens> : (Kern)k_cloud<kTriResizedCount, Lens>)
+                              : (fovea ? (Kern)k_cloud_fovea<kTriCloudCount, Lens> : (Kern)k_cloud<kTriCloudCount, Lens>);
+        const Kern cloud = rz ? (fovea ? (Kern)k_cloud_fovea<kTriResized, Lens> : (Kern)k_cloud<kTriResized, Lens>)
+                              : (fovea ? (Kern)k_cloud_fovea<kTriCloud, Lens> : (Kern)k_cloud<kTriCloud, Lens>);
+        launch_cloud(st, args.compact != 0, count, cloud, grid, args, a, b, r, *lens);
+        return;
+    }
     using Kern = void (*)(CloudArgs, Proj, Proj, CloudResize);
     const Kern count = rz ? (fovea ? (Kern)k_cloud_fovea<kTriResizedCount> : (Kern)k_cloud<kTriResizedCount>)
                           : (fovea ? (Kern)k_cloud_fovea<kTriCloudCount> : (Kern)k_cloud<kTriCloudCount>);
     const Kern cloud = rz ? (fovea ? (Kern)k_cloud_fovea<kTriResized> : (Kern)k_cloud<kTriResized>)
                           : (fovea ? (Kern)k_cloud_fovea<kTriCloud> : (Kern)k_cloud<kTriCloud>);
-    const dim3 grid(cloud_strips(args.wc), args.nchunk);
-    const CloudResize r = rz ? *rz : CloudResize{};
     launch_cloud(st, args.compact != 0, count, cloud, grid, args, a, b, r);
 }
 
-void launch_point_cloud_stack(hipStream_t st, const CloudArgs &args, const CloudStack &sk, const double *P1, const double *P2)
+void launch_point_cloud_stack(hipStream_t st, const CloudArgs &args, const CloudStack &sk, const double *P1, const double *P2, const Lens *lens)
 {
     const Proj a = proj(P1), b = proj(P2);
     const dim3 grid(sk.F * sk.strips, args.nchunk);
+    if (lens) {
+        using Kern = void (*)(CloudArgs, Proj, Proj, CloudStack, Lens);
+        const Kern count = k_cloud_stack<kTriStackCount, Lens>, cloud = k_cloud_stack<kTriStack, Lens>;
+        launch_cloud(st, args.compact != 0, count, cloud, grid, args, a, b, sk, *lens);
+        return;
+    }
     using Kern = void (*)(CloudArgs, Proj, Proj, CloudStack);
     const Kern count = k_cloud_stack<kTriStackCount>, cloud = k_cloud_stack<kTriStack>;
     launch_cloud(st, args.compact != 0, count, cloud, grid, args, a, b, sk);

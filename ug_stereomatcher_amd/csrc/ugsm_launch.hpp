@@ -109,9 +109,14 @@ void launch_lr_check(hipStream_t st, float *stack0, const float *back0, int fovW
 // (F = 1: a stack is one full-frame field.  A checked full-mode call, ugsm_submit_full_checked, checks both directions of its pairs so: entry
 // 2 b = pair b's left-to-right field against its right-to-left one, entry 2 b + 1 the two exchanged, both pointers relative to one base.)
 // X, Y, Z planes from the full-resolution (dx, dy) and the two 3x4 projection matrices
-void launch_triangulate(hipStream_t st, const float *dispx, const float *dispy, int W, int H, const double *P1, const double *P2, float *xyz);
+// lens (here and in every launcher below that takes one; ugsm_lens.hpp): null -- the pixel positions are pinhole coordinates, the instances
+// that have always been launched; else the launch's lens form, which takes the Lens by value behind the same arguments and undistorts both
+// positions of every correspondence just before the closed form.
+struct Lens;
+void launch_triangulate(hipStream_t st, const float *dispx, const float *dispy, int W, int H, const double *P1, const double *P2, float *xyz,
+                        const Lens *lens = nullptr);
 void launch_triangulate_fovea(hipStream_t st, const float *stackx, const float *stacky, int fovW, int fovH, int src_level, int left_margin,
-                              int upper_margin, float scale, const double *P1, const double *P2, float *xyz);
+                              int upper_margin, float scale, const double *P1, const double *P2, float *xyz, const Lens *lens = nullptr);
 // SURVEY 8f row f-1, the coloured point cloud (ugsm_point_cloud[_fovea]): k_cloud[_fovea]<kTriCloudCount / kTriCloud>.
 // The sampled grid is wc x hc points (point (ci, cj) = pixel (ci * s, cj * s) of the planes); tiles of 32 columns x 64 rows of it.
 struct CloudArgs {
@@ -160,9 +165,11 @@ struct CloudStack {
 int cloud_strips(int wc);
 int cloud_chunks(int hc);
 // compact: a count launch, then the cloud launch; dense: the cloud launch.  rz: the resized forms
-void launch_point_cloud(hipStream_t st, const CloudArgs &args, bool fovea, const double *P1, const double *P2, const CloudResize *rz = nullptr);
+void launch_point_cloud(hipStream_t st, const CloudArgs &args, bool fovea, const double *P1, const double *P2, const CloudResize *rz = nullptr,
+                        const Lens *lens = nullptr);
 // the same for the merged cloud of the stack; args.cnt (compact): (F * wc) * nchunk counts, F * wc column totals, F * strips strip totals
-void launch_point_cloud_stack(hipStream_t st, const CloudArgs &args, const CloudStack &sk, const double *P1, const double *P2);
+void launch_point_cloud_stack(hipStream_t st, const CloudArgs &args, const CloudStack &sk, const double *P1, const double *P2,
+                              const Lens *lens = nullptr);
 // The clouds of the n pairs of a queue call in ONE launch (compact: two), the pair = blockIdx.z: k_cloud_pairs / k_cloud_stack_pairs read their
 // pair's row of a table in DEVICE memory instead of kernel arguments (sixteen CloudStacks do not fit there).  Every row holds the pair's
 // whole CloudArgs -- its planes or stack, image, its own region of the count buffer (zeroed before the launch), points, cap and count --
@@ -227,9 +234,9 @@ struct DepthFoveaArgs {
 };
 // u16: UGSM_DEPTH_16U, else UGSM_DEPTH_32F; d.rz.factor < 1: the resized form
 void launch_depth_image(hipStream_t st, const float *dispx, const float *dispy, int W, int H, const double *P1, const double *P2, const DepthArgs &d,
-                        bool u16);
+                        bool u16, const Lens *lens = nullptr);
 void launch_depth_image_fovea(hipStream_t st, const float *stackx, const float *stacky, int fovW, int fovH, int src_level, const double *P1,
-                              const double *P2, const DepthFoveaArgs &d, bool u16);
+                              const double *P2, const DepthFoveaArgs &d, bool u16, const Lens *lens = nullptr);
 void launch_upsample_paste(hipStream_t st, const float *src3, int W, int H, float *dst3, int W2, int H2, const float *fovH_, const float *fovV_,
                            const float *fovC_, int fovW, int fovH, int org_x, int org_y);
 // The same step with the fovea of n stacks of one pair (ugsm_reconstruct_full_multi): window k's crop origin at this level, and its stack's

@@ -607,6 +607,10 @@ int enqueue_pair(ugsm_ctx *ctx, const char *name, Item it, int required, const u
         if (ks != UGSM_OK) return ks;
     }
     if (it.has_cloud) {
+        if (ctx_hooks(ctx).lens_set) {  // (the queue's pair records do not capture the lens: include/ugsm.h, "lens distortion")
+            snprintf(msg, sizeof msg, "%s: a lens is set (ugsm_set_lens) and the queue's clouds do not honour it; switch it off or take the cloud with ugsm_point_cloud*", name);
+            return ctx_fail(ctx, UGSM_ERR_STATE, msg);
+        }
         const int cs = check_cloud(ctx, spec, it);
         if (cs != UGSM_OK) return cs;
         it.spec = *spec;  // (copied now: the call is formed later)

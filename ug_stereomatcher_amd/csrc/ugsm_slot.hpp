@@ -14,6 +14,7 @@
 
 #include "ugsm_internal.hpp"
 #include "ugsm_launch.hpp"
+#include "ugsm_lens.hpp"
 #include "ugsm_mem.hpp"
 
 #include <algorithm>
@@ -175,6 +176,8 @@ struct ugsm_ctx {
     long long batch_max_px = 0;  // development override of kBatchMaxPixels (batch_level): levels up to this size go through a batched call as one launch; < 0 = none
     float lr_tau = 0.0f;  // the LR check (ugsm_set_lr_check; ugsm_create: ugsm_config.lr_check_threshold, UGSM_LR_FULL): the threshold ...
     int lr_modes = 0;     // ... and the calls that apply it (UGSM_LR_*)
+    ugsm::Lens lens{};    // the lens (ugsm_set_lens), read when hooks.lens_set: a call takes a copy into its launch's arguments
+    double lens_K[2][9] = {};  // ... and the two K as they were handed over (ugsm_get_lens gives them back whole)
     ugsm::CtxHooks hooks;  // the queue (ugsm_queue.cpp) and the RCCL shard (ugsm_shard.cpp): layers over the slot API
     ugsm::MemBook book;  // the device memory the slots' counted buffers hold, and the development limit on it (ugsm_mem.hpp)
     bool counted_live = false;  // this context counts in g_live_contexts (ugsm_create got as far as handing it out)
@@ -534,5 +537,7 @@ int queue_checked_marked(ugsm_ctx *ctx, int slot, int n, long long *fwd, long lo
 int queue_checked_cloud_submit(ugsm_ctx *ctx, int slot, const CheckedCall *call);  // (a call whose pairs carry a cloud)
 // ---- ugsm_cloud.cpp, for ugsm_match_full_depth: the depth image's parameter checks and size, before anything is enqueued -----------
 int depth_params_ok(const ugsm_depth_params *p, bool have_conf, int pw, int ph, int *dw, int *dh);
+// the lens of the calls made now (ugsm_set_lens), as the launchers take it: null while none is set
+inline const Lens *ctx_lens(const ugsm_ctx *ctx) { return ctx->hooks.lens_set ? &ctx->lens : nullptr; }
 
 }  // namespace ugsm

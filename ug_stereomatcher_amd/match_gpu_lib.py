@@ -184,6 +184,15 @@ class MatchGPULib:
         prm = _lib.depth_params(format=_lib.DEPTH_ENCODINGS[encoding], unit=unit, min_conf=min_conf, z_min=z_min, z_max=z_max, factor=factor)
         return self._ctx.match_full_depth(L, R, P1, P2, prm, planes=planes)
 
+    # -- lens distortion (not in the reference: its cloud node reads K and D and never uses them) --
+    def setLens(self, K1, D1, K2, D2, iterations: int = 5):
+        """The plumb_bob K and D of the two CameraInfo messages: depthImage and every cloud taken from this matcher's context undistort the two
+        pixel positions of each correspondence before they triangulate (ugsm_set_lens)."""
+        self._ctx.set_lens(K1, D1, K2, D2, iterations)
+
+    def clearLens(self):
+        self._ctx.clear_lens()
+
     # -- warpRightImage, MatchGPULib.cpp:1445-1518 --
     def warpRightImage(self, right, disparity, channels: int, imageW: int, imageH: int) -> np.ndarray:
         """right: `channels` float planes of imageH x imageW; disparity[0] / disparity[1]: the horizontal / vertical field.  Returns the
