@@ -48,7 +48,8 @@ extern "C" {
                                ugsm_submit_full_checked_host, ugsm_enqueue_full_checked, ugsm_enqueue_full_checked_managed,
                                ugsm_enqueue_full_checked_cloud, ugsm_enqueue_full_checked_cloud_managed, ugsm_checked_result, ugsm_done_checked;
                                the depth image (REP 118 32FC1 / 16UC1) -- ugsm_depth_params, UGSM_DEPTH_32F / UGSM_DEPTH_16U / UGSM_DEPTH_ALL_LEVELS,
-                               ugsm_default_depth_params, ugsm_depth_image_size, ugsm_depth_image, ugsm_depth_image_fovea, ugsm_match_full_depth;
+                               ugsm_default_depth_params, ugsm_depth_image_size, ugsm_depth_image, ugsm_depth_image_fovea, ugsm_match_full_depth,
+                               ugsm_depth_image_fovea_full, ugsm_depth_image_fovea_multi, ugsm_match_foveated_depth;
                                lens distortion in triangulation, clouds and depth -- ugsm_set_lens, ugsm_get_lens, ugsm_undistort_points
                                6: the kernel choices follow what is in flight, not ugsm_config.slots: ugsm_plan_level takes `alone`, ugsm_plan_level_in_frame
                                is gone, ugsm_level_plan.latency_policy is .alone; ugsm_enqueue_* returns UGSM_OK once the pair is accepted (a failed
@@ -976,8 +977,36 @@ int ugsm_point_cloud_resized_fovea(ugsm_ctx *ctx, int slot, const float *d_stack
  * 0; W or H < 1, or more than 2^28 pixels; a misaligned d_depth / d_valid / plane; d_depth overlapping an input; a bad slot or level; the
  * fovea form on a context with fovea_levels < 2.
  *
- * Out of scope: queue forms (ugsm_enqueue_*_depth*); the depth image of several windows or of a reconstructed stack (compose
- * ugsm_reconstruct_full[_multi] with ugsm_depth_image); a strided output; depth in the right camera; camera_info handling
+ * THE WHOLE FRAME FROM A FOVEA STACK -- ugsm_depth_image_fovea_full, ugsm_depth_image_fovea_multi, ugsm_match_foveated_depth.  One W x H (or
+ * resized) image registered to the left camera from the stack of a foveated call (_multi: from the n stacks of
+ * ugsm_submit_foveated_multi[_checked]).  The contract is one sentence: the image and *d_valid are byte for byte what
+ * ugsm_reconstruct_full (_multi: ugsm_reconstruct_full_multi) into a 3 W H field, followed by ugsm_depth_image on that field's three planes
+ * with the same P1, P2, p and the same lens setting, would give.  The full-resolution field is never formed: one launch (and the zeroing of
+ * *d_valid), no level buffers, no slot memory beyond a table of n > 1 windows.  What the sentence implies:
+ *   value     of frame pixel (x, y): descend from level 0.  At level l < F-1 the site is inside the window when 0 <= x - ox[l] < fovW &&
+ *             0 <= y - oy[l] < fovH, ox / oy the window's origin at level l as the foveated call places it (off_x, off_y clamped to the
+ *             level).  _multi: every window is tested and the HIGHEST-numbered window that holds the site supplies the value.  Otherwise
+ *             move to x = tex(((float)x + 0.5f) / s, w[l+1]), the same in y (s = (float)1.41421356; tex: floor, clamped to 0 .. n-1).
+ *             Level F-1 holds every site; _multi reads it from stack 0.
+ *   scaling   the three values read (dx, dy, conf) are multiplied by s once per level descended, each product rounded on its own -- the
+ *             confidence too, as hierarchicalDisparity scales every channel: min_conf tests conf * s^depth, as it does in the composition.
+ *   Z         the FIELD form, not the fovea form: x1 = x, y1 = y, x2 = x + dx, y2 = y + dy, no (int) conversion and no level mapping; then
+ *             the lens if one is set and the rule above, exactly as ugsm_depth_image applies them.  A disparity never indexes memory, so NaN,
+ *             infinite and huge values are defined here, unlike in the per-level fovea form.
+ *   factor    < 1: the image is ugsm_depth_image_size(W, H, factor), Z the resized clouds' cubic resize of the 16 footprint Z, each from
+ *             its own descent, the confidence read by descent at (xx, yy) = ((int)((float)ii / factor), (int)((float)jj / factor)).
+ * d_stackc NULL (with min_conf -inf): no confidence test, as ugsm_depth_image with d_conf NULL; _multi takes each stack as 3 planes of F
+ * levels (d_stack: a HOST array of n DEVICE stacks; off_x / off_y NULL = centred) and always tests the confidence (a NaN fails).
+ * Both are asynchronous on `slot`, ordered behind a ugsm_submit_foveated* on the same slot, and make no host synchronisation (the table of
+ * n > 1 windows goes up on the slot's stream; only its first growth waits for the stream).  Refused before any device work, nothing written,
+ * ugsm_last_error naming the call: everything ugsm_depth_image refuses (the planes being the stacks); fovea_levels < 2; n outside
+ * 1 .. UGSM_MAX_BATCH or a null stack entry; d_depth overlapping any stack; UGSM_ERR_STATE while pairs enqueued with ugsm_enqueue_* are
+ * outstanding.  ugsm_match_foveated_depth: the blocking call, ugsm_match_foveated followed by ugsm_depth_image_fovea_full on slot 0; each of
+ * stackH / stackV / stackC may be NULL and is then not downloaded (the sibling of ugsm_match_full_depth).
+ *
+ * Out of scope: queue forms (ugsm_enqueue_*_depth*), also of the whole-frame image; the whole frame's X, Y, Z planes or cloud without the
+ * field (compose ugsm_reconstruct_full[_multi] with ugsm_triangulate / ugsm_point_cloud); a strided output; depth in the right camera;
+ * camera_info handling
  * (a host hands K and D over with ugsm_set_lens, "lens distortion" below); undistortion of the image itself (the lens setting undistorts the
  * two positions of each correspondence, the image's grid stays the distorted left camera's). */
 #define UGSM_DEPTH_32F 0   /* REP 118 32FC1: float, NaN where there is no reading */
@@ -1004,6 +1033,20 @@ int ugsm_depth_image_fovea(ugsm_ctx *ctx, int slot, const float *d_stackx, const
 int ugsm_match_full_depth(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride,
                           const double *P1, const double *P2, const ugsm_depth_params *p, void *depth, float *dispH,
                           float *dispV, float *dispC);
+/* one W x H (or resized) depth image registered to the left camera, from the stack of a foveated call */
+int ugsm_depth_image_fovea_full(ugsm_ctx *ctx, int slot, const float *d_stackx, const float *d_stacky, const float *d_stackc,
+                                int W, int H, int off_x, int off_y, const double *P1, const double *P2,
+                                const ugsm_depth_params *p, void *d_depth, unsigned long long *d_valid);
+/* the same from the n stacks of ugsm_submit_foveated_multi[_checked] (HOST array of n DEVICE stacks, 3 planes of F levels each;
+ * off_x / off_y NULL = centred) */
+int ugsm_depth_image_fovea_multi(ugsm_ctx *ctx, int slot, int n, const float *const *d_stack, int W, int H,
+                                 const int *off_x, const int *off_y, const double *P1, const double *P2,
+                                 const ugsm_depth_params *p, void *d_depth, unsigned long long *d_valid);
+/* blocking: ugsm_match_foveated, then ugsm_depth_image_fovea_full on slot 0; each of stackH / stackV / stackC may be NULL and is then
+ * not downloaded (the sibling of ugsm_match_full_depth) */
+int ugsm_match_foveated_depth(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, int off_x, int off_y,
+                              const double *P1, const double *P2, const ugsm_depth_params *p, void *depth,
+                              float *stackH, float *stackV, float *stackC);
 
 /* ---- lens distortion: plumb_bob D in triangulation, clouds and depth -----------------------------------------------------------------
  *
@@ -1042,7 +1085,8 @@ int ugsm_match_full_depth(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgb
  *
  * Honoured by: ugsm_triangulate, ugsm_triangulate_fovea, ugsm_point_cloud, ugsm_point_cloud_fovea, ugsm_point_cloud_fovea_all,
  * ugsm_point_cloud_resized and ugsm_point_cloud_resized_fovea (every one of the 16 footprint Z), ugsm_depth_image and
- * ugsm_depth_image_fovea (both formats, any factor, UGSM_DEPTH_ALL_LEVELS), ugsm_match_full_depth.
+ * ugsm_depth_image_fovea (both formats, any factor, UGSM_DEPTH_ALL_LEVELS), ugsm_match_full_depth, ugsm_depth_image_fovea_full,
+ * ugsm_depth_image_fovea_multi and ugsm_match_foveated_depth.
  * Refused while a lens is set -- UGSM_ERR_STATE, nothing enqueued, nothing written, ugsm_last_error names the setting --:
  * ugsm_point_cloud_fovea_multi and every ugsm_enqueue_*_cloud* (the queue's pair records do not capture the lens yet). */
 int ugsm_set_lens(ugsm_ctx *ctx, const double *K1, const double *D1, const double *K2, const double *D2, int iterations);

@@ -388,6 +388,27 @@ public:
         return img;
     }
 
+    // ... and of the WHOLE frame from a foveated match (ugsm_match_foveated_depth): matchStack's match at window offset (off_x, off_y) and one
+    // *dw x *dh image of the rows x cols frame from its stack -- what hierarchicalDisparity followed by the depth image of that field gives,
+    // without the field.  Only the image crosses the bus.  (depthImageStack keeps its per-level meaning.)
+    template <class ImgPtr>
+    void *depthImageFrame(ImgPtr L, ImgPtr R, const double *P1, const double *P2, const ugsm_depth_params *p, int *dw, int *dh, int off_x = 0, int off_y = 0)
+    {
+        foveatedmatching = 1;
+        const int W = L->image.cols, H = L->image.rows;
+        if (!p || !dw || !dh || R->image.cols != W || R->image.rows != H || ugsm_depth_image_size(W, H, p->factor, dw, dh) != UGSM_OK) return nullptr;
+        void *img = std::malloc((size_t)*dw * *dh * (p->format == UGSM_DEPTH_16U ? 2 : 4));
+        const int st = img ? ugsm_match_foveated_depth(ctx_, L->image.data, R->image.data, W, H, (int)L->image.step, off_x, off_y, P1, P2, p, img, nullptr,
+                                                       nullptr, nullptr)
+                           : UGSM_ERR_NOMEM;
+        if (st != UGSM_OK) {
+            std::free(img);
+            report(st);
+            return nullptr;
+        }
+        return img;
+    }
+
     // ---- the pipelined twin of match / matchStack / matchStackPyramid (not in the reference): include/ugsm.h, "the queue" ------------
     // The images are copied into page-locked staging memory of the library before the call returns (the cv_bridge image may be freed);
     // the result comes out of nextDone, in arrival order.  Every call flushes: a frame starts at once if a slot is free, and under load

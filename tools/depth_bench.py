@@ -23,6 +23,14 @@ What honouring the lens costs (ugsm_set_lens): the `kernel` regions alone, with 
 (`kernel`) and with it (`kernel_lens`) that take turns round by round; the result goes under "depth" of --out, beside what
 tools/cloud_bench.py --lens put there.
 
+    python tools/depth_bench.py --frame --parent-tree DIR [--rounds 3] [--out profiles/depth_frame_bench.json]
+
+The depth image of the whole frame from a fovea stack: (a) the composition ugsm_reconstruct_full[_multi] + ugsm_depth_image on a build of the
+parent commit against (b) the fused call ugsm_depth_image_fovea_full / _multi on this build.  4928 x 3264 (14 levels, 7 fovea levels) and
+1920 x 1080 (the same), 32F and 16U, factor 1 and 0.2, one window and four scattered windows; device-resident synthetic stacks, events off.
+A child is one (size, windows, build): it times every form as a region (calls enqueued back to back, one ugsm_wait) and reports what
+the context's slot memory grew by (ugsm_context_device_bytes).  The children of the two builds take turns, `rounds` children each.
+
 Every child's value is kept; a row gives the median and the spread (max - min) of its children.  No number is fixed here: a ratio counts
 as a difference only where it exceeds the spread between children of one configuration."""
 import argparse
@@ -50,6 +58,8 @@ ap.add_argument("--region", type=float, default=0.3, help="seconds a timed kerne
 ap.add_argument("--sizes", nargs="*", default=list(SIZES))
 ap.add_argument("--configs", nargs="*", default=None, help="the configurations to measure (default: all)")
 ap.add_argument("--lens", action="store_true", help="the kernel regions without a lens and with it instead")
+ap.add_argument("--frame", action="store_true", help="the whole frame's image from a fovea stack: the parent's composition against the fused call")
+ap.add_argument("--windows", type=int, default=1, help="(internal) --frame: the windows of the child's stacks")
 ap.add_argument("--calibration", default=os.path.join(ROOT, "tests", "golden", "lens_cal.json"), help="--lens: K, D, P of the two cameras")
 ap.add_argument("--rig", default="rig16mp", help="--lens: the rig of the calibration file")
 ap.add_argument("--iterations", type=int, default=5, help="--lens: ugsm_set_lens's iterations")
@@ -76,6 +86,113 @@ def to_16u(np, z, unit):
         u = (z * np.float32(unit)) * np.float32(1000.0) + np.float32(0.5)
         valid = np.isfinite(z) & (u >= np.float32(1.0)) & (u < np.float32(65536.0))
         return np.where(valid, u, np.float32(0)).astype(np.uint16)
+
+
+FRAME_LEVELS, FRAME_FOVEA = 14, 7
+FRAME_OFFSETS = {1: [(150, -90)], 4: [(-700, -400), (650, -350), (-600, 420), (720, 380)]}   # (level-0 pixels; clamped to the frame where they leave it)
+FRAME_FORMS = [("32f", 0, 1.0), ("16u", 1, 1.0), ("32f_0.2", 0, 0.2), ("16u_0.2", 1, 0.2)]
+
+
+def frame_child():
+    """One (size, windows, build): `fused` on this build, `composed` on whichever tree args.tree names (only calls the parent has)."""
+    sys.path.insert(0, args.tree)
+    import ctypes as C
+    import numpy as np
+    from ug_stereomatcher_amd import _lib
+    W, H = SIZES[args.size]
+    n, nw, fused = W * H, args.windows, args.child == "fused"
+    P1, P2 = rig()
+    q = [(C.c_double * 12)(*np.asarray(p, np.float64).reshape(12)) for p in (P1, P2)]
+    offs = FRAME_OFFSETS[nw]
+    out = {}
+    with _lib.Context(levels=FRAME_LEVELS, fovea_levels=FRAME_FOVEA, slots=1) as c:
+        fw, fh = _lib.fovea_dims(W, H, FRAME_LEVELS, FRAME_FOVEA)
+        plane = FRAME_FOVEA * fw * fh
+        rng = np.random.Generator(np.random.PCG64(17))
+        stacks = []
+        for _ in range(nw):
+            st = np.empty((3, FRAME_FOVEA, fh, fw), np.float32)
+            for l in range(FRAME_FOVEA):
+                k = np.float32(1.41421356) ** np.float32(l)
+                st[0, l] = rng.normal(40, 12, (fh, fw)).astype(np.float32) / k
+                st[1, l] = rng.normal(0, 2, (fh, fw)).astype(np.float32) / k
+                st[2, l] = rng.uniform(0, 1, (fh, fw)).astype(np.float32) / k
+            stacks.append(c.to_device(st))
+        arr = (C.c_void_p * nw)(*stacks)
+        ox, oy = (C.c_int * nw)(*[o[0] for o in offs]), (C.c_int * nw)(*[o[1] for o in offs])
+        dF = None if fused else c.alloc(3 * n * 4)
+        dD, dV = c.alloc(4 * n), c.alloc(8)
+        bytes0 = c.device_bytes()
+
+        def region(f, reps):
+            t0 = time.perf_counter()
+            for _ in range(reps):
+                f()
+            c.check(c.lib.ugsm_wait(c.handle, 0))
+            return time.perf_counter() - t0
+        lib, h, s0 = c.lib, c.handle, stacks[0]
+        for name, fmt, factor in FRAME_FORMS:
+            prm = _lib.depth_params(format=fmt, unit=UNIT, min_conf=0.25, factor=factor)
+            ref = C.byref(prm)
+            if fused and nw == 1:
+                f = lambda: c.check(lib.ugsm_depth_image_fovea_full(h, 0, s0, s0 + 4 * plane, s0 + 8 * plane, W, H, offs[0][0], offs[0][1], q[0], q[1], ref, dD, dV))   # noqa: E731
+            elif fused:
+                f = lambda: c.check(lib.ugsm_depth_image_fovea_multi(h, 0, nw, arr, W, H, ox, oy, q[0], q[1], ref, dD, dV))   # noqa: E731
+            elif nw == 1:
+                def f():
+                    c.check(lib.ugsm_reconstruct_full(h, 0, s0, s0 + 4 * plane, s0 + 8 * plane, W, H, offs[0][0], offs[0][1], dF))
+                    c.check(lib.ugsm_depth_image(h, 0, dF, dF + 4 * n, dF + 8 * n, W, H, q[0], q[1], ref, dD, dV))
+            else:
+                def f():
+                    c.check(lib.ugsm_reconstruct_full_multi(h, 0, nw, arr, W, H, ox, oy, dF))
+                    c.check(lib.ugsm_depth_image(h, 0, dF, dF + 4 * n, dF + 8 * n, W, H, q[0], q[1], ref, dD, dV))
+            region(f, 5)
+            reps = int(min(max(args.region / (region(f, 10) / 10), 10), 2000))
+            region(f, reps)
+            dt = region(f, reps)
+            out[name] = dict(us_per_call=dt / reps * 1e6, reps=reps, valid=int(c.to_host(dV, (1,), np.uint64)[0]))
+        # the slot's growth, and what the caller must hold besides the stacks and the image
+        out["slot_bytes"] = c.device_bytes() - bytes0
+        out["caller_field_bytes"] = 0 if fused else 3 * n * 4
+    print("DEPTHBENCH " + json.dumps(out), flush=True)
+
+
+def frame_main():
+    parent = os.path.abspath(args.parent_tree) if args.parent_tree else None
+    if not parent or not os.path.exists(os.path.join(parent, "ug_stereomatcher_amd", "libugsm.so")):
+        raise SystemExit("--frame needs --parent-tree DIR, a checkout of the parent commit with its libraries built")
+    result = dict(tool="tools/depth_bench.py --frame", levels=FRAME_LEVELS, fovea_levels=FRAME_FOVEA, rounds=args.rounds, unit=UNIT, offsets=FRAME_OFFSETS,
+                  timing="region / reps: calls enqueued back to back and one ugsm_wait; a: ugsm_reconstruct_full[_multi] + ugsm_depth_image on the parent "
+                         "build, b: the fused call on this build; min_conf 0.25 and d_valid in every call", rows=[])
+    for size in args.sizes:
+        for nw in (1, 4):
+            kept = {"composed": [], "fused": []}
+            for rnd in range(args.rounds):
+                for k in (("composed", "fused") if rnd % 2 == 0 else ("fused", "composed")):     # (the two builds' children take turns)
+                    cmd = [sys.executable, os.path.abspath(__file__), "--frame", "--child", k, "--size", size, "--windows", str(nw), "--tree",
+                           parent if k == "composed" else ROOT, "--region", str(args.region)]
+                    r = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
+                    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("DEPTHBENCH ")]
+                    if r.returncode != 0 or not lines:
+                        raise SystemExit(f"child failed ({r.returncode}): {' '.join(cmd)}\n{r.stdout[-2000:]}\n{r.stderr[-2000:]}")
+                    kept[k].append(json.loads(lines[-1][len("DEPTHBENCH "):]))
+            for name, _, _ in FRAME_FORMS:
+                a = [x[name]["us_per_call"] for x in kept["composed"]]
+                b = [x[name]["us_per_call"] for x in kept["fused"]]
+                ma, mb = statistics.median(a), statistics.median(b)
+                spread = max(max(a) - min(a), max(b) - min(b))
+                assert kept["composed"][0][name]["valid"] == kept["fused"][0][name]["valid"], (size, nw, name)
+                row = dict(size=size, W=SIZES[size][0], H=SIZES[size][1], windows=nw, form=name, a_us=ma, a_us_children=a, b_us=mb, b_us_children=b,
+                           b_over_a=mb / ma, spread_us=spread, spread_over_a=spread / ma, b_beats_a_by_more_than_the_spread=bool(ma - mb > spread),
+                           valid=kept["fused"][0][name]["valid"],
+                           a_slot_bytes=kept["composed"][0]["slot_bytes"], a_caller_field_bytes=kept["composed"][0]["caller_field_bytes"],
+                           b_slot_bytes=kept["fused"][0]["slot_bytes"], b_caller_field_bytes=0)
+                result["rows"].append(row)
+                print(json.dumps({k: v for k, v in row.items() if not k.endswith("_children")}), flush=True)
+    out = args.out or os.path.join(ROOT, "profiles", "depth_frame_bench.json")
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    json.dump(result, open(out, "w"), indent=1, sort_keys=True)
+    print(f"wrote {out}")
 
 
 def child():
@@ -239,4 +356,7 @@ def main():
 
 
 if __name__ == "__main__":
-    child() if args.child else main()
+    if args.frame:
+        frame_child() if args.child else frame_main()
+    else:
+        child() if args.child else main()

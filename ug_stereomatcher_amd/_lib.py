@@ -82,6 +82,7 @@ EXPORTS = [
     "ugsm_enqueue_full_checked_cloud_managed", "ugsm_done_checked",
     # the depth image (REP 118)
     "ugsm_default_depth_params", "ugsm_depth_image_size", "ugsm_depth_image", "ugsm_depth_image_fovea", "ugsm_match_full_depth",
+    "ugsm_depth_image_fovea_full", "ugsm_depth_image_fovea_multi", "ugsm_match_foveated_depth",
     # lens distortion in triangulation, clouds and depth
     "ugsm_set_lens", "ugsm_get_lens", "ugsm_undistort_points",
 ]
@@ -448,6 +449,9 @@ def load(dev: bool = False):
     lib.ugsm_depth_image.argtypes = [vp, i, vp, vp, vp, i, i, dpp, dpp, C.POINTER(DepthParams), vp, vp]
     lib.ugsm_depth_image_fovea.argtypes = [vp, i, vp, vp, vp, i, i, i, i, i, dpp, dpp, C.POINTER(DepthParams), vp, vp]
     lib.ugsm_match_full_depth.argtypes = [vp, vp, vp, i, i, i, dpp, dpp, C.POINTER(DepthParams), vp, vp, vp, vp]
+    lib.ugsm_depth_image_fovea_full.argtypes = [vp, i, vp, vp, vp, i, i, i, i, dpp, dpp, C.POINTER(DepthParams), vp, vp]
+    lib.ugsm_depth_image_fovea_multi.argtypes = [vp, i, i, C.POINTER(vp), i, i, C.POINTER(i), C.POINTER(i), dpp, dpp, C.POINTER(DepthParams), vp, vp]
+    lib.ugsm_match_foveated_depth.argtypes = [vp, vp, vp, i, i, i, i, i, dpp, dpp, C.POINTER(DepthParams), vp, vp, vp, vp]
     lib.ugsm_set_lens.argtypes = [vp, dpp, dpp, dpp, dpp, i]
     lib.ugsm_get_lens.argtypes = [vp, dpp, dpp, dpp, dpp, ip, ip]
     lib.ugsm_undistort_points.argtypes = [dpp, dpp, i, vp, vp, C.c_longlong]
@@ -927,6 +931,52 @@ class Context:
         self.check(self.lib.ugsm_match_full_depth(self._h, L.ctypes.data, R.ctypes.data, W, H, stride, q1, q2, C.byref(params),
                                                   depth.ctypes.data, *ptr))
         return (depth, out) if planes else depth
+
+    def depth_image_fovea_full(self, d_stackx: int, d_stacky: int, d_stackc, W: int, H: int, off, P1, P2, params: DepthParams, d_depth: int,
+                               d_valid=None, slot: int = 0, wait: bool = True):
+        """The depth image of the WHOLE W x H frame from the fovea stacks of a foveated call at window offset `off` -- what reconstruct_full
+        followed by depth_image gives, in one launch and without the field; with d_valid and wait, returns the number of valid pixels."""
+        p1, p2, q1, q2 = self._proj(P1, P2)
+        self.check(self.lib.ugsm_depth_image_fovea_full(self._h, slot, d_stackx, d_stacky, d_stackc, W, H, int(off[0]), int(off[1]), q1, q2,
+                                                        C.byref(params), d_depth, d_valid))
+        if wait:
+            self.check(self.lib.ugsm_wait(self._h, slot))
+            if d_valid is not None:
+                return int(self.to_host(d_valid, (1,), np.uint64)[0])
+
+    def depth_image_fovea_multi(self, d_stack, W: int, H: int, offsets, P1, P2, params: DepthParams, d_depth: int, d_valid=None, slot: int = 0,
+                                wait: bool = True):
+        """The same from the stacks of several windows of one pair (d_stack: their device addresses; offsets None: centred) -- what
+        reconstruct_full_multi followed by depth_image gives: where windows overlap the highest index wins."""
+        n = len(d_stack)
+        ox, oy = self._offsets(offsets, n)
+        p1, p2, q1, q2 = self._proj(P1, P2)
+        self.check(self.lib.ugsm_depth_image_fovea_multi(self._h, slot, n, self._ptrs(d_stack), W, H, ox, oy, q1, q2, C.byref(params), d_depth,
+                                                         d_valid))
+        if wait:
+            self.check(self.lib.ugsm_wait(self._h, slot))
+            if d_valid is not None:
+                return int(self.to_host(d_valid, (1,), np.uint64)[0])
+
+    def match_foveated_depth(self, L: np.ndarray, R: np.ndarray, P1, P2, params: DepthParams, off=(0, 0), stack: bool = False):
+        """The blocking call: the foveated match of (L, R) at window offset `off` and the depth image of the whole frame from its stack, a
+        (dh, dw) float32 or uint16 array; with stack, also the (3, F, fovH, fovW) stack -- otherwise only the image crosses the bus."""
+        W, H, stride = self.check_image(L)
+        if self.check_image(R) != (W, H, stride):
+            raise UgsmError(UGSM_ERR_SIZE_MISMATCH, "left and right images differ in size or stride")
+        size = depth_image_size(W, H, params.factor)
+        if size is None or params.format not in DEPTH_DTYPES:
+            raise UgsmError(UGSM_ERR_BAD_ARG, "depth parameters")
+        p1, p2, q1, q2 = self._proj(P1, P2)
+        depth = np.empty((size[1], size[0]), DEPTH_DTYPES[params.format])
+        out = None
+        if stack:
+            fw, fh = fovea_dims(W, H, self.cfg.levels, self.cfg.fovea_levels)
+            out = np.empty((3, self.cfg.fovea_levels, fh, fw), np.float32)
+        ptr = [out[k].ctypes.data for k in range(3)] if stack else [None] * 3
+        self.check(self.lib.ugsm_match_foveated_depth(self._h, L.ctypes.data, R.ctypes.data, W, H, stride, int(off[0]), int(off[1]), q1, q2,
+                                                      C.byref(params), depth.ctypes.data, *ptr))
+        return (depth, out) if stack else depth
 
     # ---- the warped right image and the photometric residual of a match (include/ugsm.h) -----------------------------------------------
     def warp_planes(self, d_src: int, channels: int, W: int, H: int, d_dispx: int, d_dispy: int, d_dst: int, slot: int = 0, wait: bool = True):

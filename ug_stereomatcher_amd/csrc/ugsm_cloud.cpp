@@ -6,6 +6,9 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstring>
+#include <string>
+#include <type_traits>
 
 using namespace ugsm;
 
@@ -318,8 +321,9 @@ int point_cloud(ugsm_ctx *ctx, int slot, CloudArgs &a, bool fovea, const double 
 
 // The depth image's checks (no device needed) and its kernel arguments.  dx, dy, conf: `in_levels` levels of pw x ph floats each (a field: 1;
 // the fovea stacks: F); the call writes `levels` images of dw x dh elements behind each other and as many counts.
+// in_floats (the whole-frame forms, whose inputs are not the image's size): the floats behind each of dx, dy, conf, else in_levels * pw * ph.
 int depth_args_ok(const ugsm_ctx *ctx, const float *dx, const float *dy, const float *conf, int in_levels, int pw, int ph, int levels, const double *P1,
-                  const double *P2, const ugsm_depth_params *p, const void *depth, const void *valid, DepthArgs &d)
+                  const double *P2, const ugsm_depth_params *p, const void *depth, const void *valid, DepthArgs &d, size_t in_floats = 0)
 {
     if (!ctx || !dx || !dy || !P1 || !P2 || !depth) return UGSM_ERR_BAD_ARG;
     int dw, dh;
@@ -327,7 +331,7 @@ int depth_args_ok(const ugsm_ctx *ctx, const float *dx, const float *dy, const f
     const size_t size = p->format == UGSM_DEPTH_16U ? 2 : 4;
     if (((uintptr_t)depth & (size - 1)) || ((uintptr_t)valid & 7)) return UGSM_ERR_BAD_ARG;
     if (((uintptr_t)dx | (uintptr_t)dy | (uintptr_t)conf) & 3) return UGSM_ERR_BAD_ARG;
-    const uintptr_t o0 = (uintptr_t)depth, o1 = o0 + (size_t)levels * dw * dh * size, in_bytes = (size_t)in_levels * pw * ph * sizeof(float);
+    const uintptr_t o0 = (uintptr_t)depth, o1 = o0 + (size_t)levels * dw * dh * size, in_bytes = (in_floats ? in_floats : (size_t)in_levels * pw * ph) * sizeof(float);
     for (const float *q : {dx, dy, conf})
         if (q && o0 < (uintptr_t)q + in_bytes && (uintptr_t)q < o1) return UGSM_ERR_BAD_ARG;  // (the image would overwrite what it is made from)
     d = DepthArgs{};
@@ -353,6 +357,97 @@ int depth_image(ugsm_ctx *ctx, int slot, const DepthArgs &d, int levels, F &&lau
     HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
     if (d.valid) HIPCHK(ctx, hipMemsetAsync(d.valid, 0, (size_t)levels * sizeof(unsigned long long), s->st));
     return timed_launch(ctx, s, slot, (double)levels * d.dw * d.dh, [&] { launch(s->st); });
+}
+
+// ---- the depth image of the whole frame from a fovea stack (ugsm_depth_image_fovea_full / _multi) ------------------------------------------
+// The call's table goes up on the turns of the slot's one upload ring (SlotCloud::mc, the merged cloud's): its rows are raw memory to this
+// call, as many CloudEntry rows as hold the n windows.
+static_assert(alignof(CloudEntry) >= alignof(FrameWindow) && std::is_trivially_copyable<FrameWindow>::value, "FrameWindow rows in the ring's rows");
+size_t frame_table_rows(int n) { return ((size_t)n * sizeof(FrameWindow) + sizeof(CloudEntry) - 1) / sizeof(CloudEntry); }
+
+// What both forms derive and refuse before any device work: the levels' sizes and the n windows' origins (fovea_geometry, as
+// ugsm_reconstruct_full[_multi] place them), the depth image's own checks on the W x H frame against stack 0's planes (depth_args_ok; sx, sy,
+// sc: F x fh x fw floats each), and every further stack's overlap with the image.  stack: null (one window, the three planes apart), or the n
+// stacks of three planes each.
+int depth_frame_args(const ugsm_ctx *ctx, int n, const float *const *stack, const float *sx, const float *sy, const float *sc, int W, int H,
+                     const int *off_x, const int *off_y, const double *P1, const double *P2, const ugsm_depth_params *p, const void *depth,
+                     const void *valid, DepthArgs &d, DepthFrame &fr, FrameWindow *win)
+{
+    if (!ctx || n < 1 || n > UGSM_MAX_BATCH || W < 1 || H < 1 || (long long)W * H > kMaxPixels) return UGSM_ERR_BAD_ARG;
+    const int levels = ctx->cfg.levels, F = ctx->cfg.fovea_levels;
+    if (F < 2 || F > levels || levels > UGSM_MAX_LEVELS) return UGSM_ERR_BAD_ARG;
+    int w[UGSM_MAX_LEVELS], h[UGSM_MAX_LEVELS];
+    UCHK(level_dims(W, H, levels, w, h));  // (as ugsm_reconstruct_full: the context's whole pyramid must exist at this size)
+    fr = DepthFrame{};
+    fr.n = n;
+    fr.F = F;
+    for (int l = 0; l < F; l++) {
+        fr.w[l] = w[l];
+        fr.h[l] = h[l];
+    }
+    for (int j = 0; j < n; j++) {
+        FoveaGeom g;
+        fovea_geometry(w, h, F, off_x ? off_x[j] : 0, off_y ? off_y[j] : 0, g);
+        fr.fw = g.fw;
+        fr.fh = g.fh;
+        win[j] = FrameWindow{};
+        for (int l = 0; l < F - 1; l++) {
+            win[j].ox[l] = g.ox[l];
+            win[j].oy[l] = g.oy[l];
+        }
+        if (stack) {
+            if (!stack[j]) return UGSM_ERR_BAD_ARG;
+            win[j].stack = byte_diff(stack[j], stack[0]);
+        }
+    }
+    const size_t plane = (size_t)F * fr.fw * fr.fh;
+    if (stack) {
+        sx = stack[0];
+        sy = sx + plane;
+        sc = sx + 2 * plane;
+    }
+    UCHK(depth_args_ok(ctx, sx, sy, sc, 1, W, H, 1, P1, P2, p, depth, valid, d, plane));
+    const size_t image = (size_t)d.dw * d.dh * (p->format == UGSM_DEPTH_16U ? 2 : 4);
+    for (int j = 1; stack && j < n; j++) {
+        if ((uintptr_t)stack[j] & 3) return UGSM_ERR_BAD_ARG;
+        if (overlap(depth, image, stack[j], 3 * plane * sizeof(float))) return UGSM_ERR_BAD_ARG;
+    }
+    return UGSM_OK;
+}
+
+// the slot, the table of n > 1 windows up on the slot's stream (nothing waits for the stream unless the ring has to grow), the count zeroed, the one launch
+int depth_frame(ugsm_ctx *ctx, int slot, const float *sx, const float *sy, const double *P1, const double *P2, const DepthArgs &d, DepthFrame &fr,
+                const FrameWindow *win, bool u16)
+{
+    Slot *s;
+    UCHK(get_slot(ctx, slot, &s));
+    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
+    if (fr.n > 1) {
+        CloudEntry *rows;
+        const size_t nrows = frame_table_rows(fr.n);
+        UCHK(s->cloud.mc.begin(ctx, s->st, nrows, &rows));
+        memcpy(static_cast<void *>(rows), win, (size_t)fr.n * sizeof(FrameWindow));
+        UCHK(s->cloud.mc.upload(ctx, s->st, nrows));
+        fr.table = reinterpret_cast<const FrameWindow *>(static_cast<const CloudEntry *>(s->cloud.mc.tab));
+    }
+    if (d.valid) HIPCHK(ctx, hipMemsetAsync(d.valid, 0, sizeof(unsigned long long), s->st));
+    bool fits = true;
+    UCHK(timed_launch(ctx, s, slot, (double)d.dw * d.dh,
+                      [&] { fits = launch_depth_image_frame(s->st, sx, sy, P1, P2, d, fr, win, u16, ctx_lens(ctx)); }));
+    return fits ? UGSM_OK : ctx_fail(ctx, UGSM_ERR_STATE, "a window of the stack leaves its level");
+}
+
+// A refusal of `call` names it in ugsm_last_error, in front of what the check itself had to say.
+template <class F>
+int named(ugsm_ctx *ctx, const char *call, F &&body)
+{
+    if (!ctx) return body();
+    const std::string before = ctx->err;
+    ctx->err.clear();
+    const int st = body();
+    if (st == UGSM_OK) ctx->err = before;
+    else ctx->err = std::string(call) + ": " + (ctx->err.empty() ? ugsm_status_string(st) : ctx->err);
+    return st;
 }
 
 constexpr size_t kCqWords = 1 + UGSM_MAX_LEVELS;  // a managed pair's count words: the count, the level counts
@@ -616,6 +711,35 @@ int ugsm_depth_image_fovea(ugsm_ctx *ctx, int slot, const float *d_stackx, const
     const int src_level = all ? 0 : level;
     return depth_image(ctx, slot, f.d, f.lv.levels,
                        [&](hipStream_t st) { launch_depth_image_fovea(st, d_stackx, d_stacky, fw, fh, src_level, P1, P2, f, u16, ctx_lens(ctx)); });
+}
+
+// The whole frame's image from the stack of a foveated call: what ugsm_reconstruct_full followed by ugsm_depth_image gives, in one launch and
+// without the field (k_triangulate's frame forms).
+int ugsm_depth_image_fovea_full(ugsm_ctx *ctx, int slot, const float *d_stackx, const float *d_stacky, const float *d_stackc, int W, int H, int off_x,
+                                int off_y, const double *P1, const double *P2, const ugsm_depth_params *p, void *d_depth, unsigned long long *d_valid)
+{
+    return named(ctx, "ugsm_depth_image_fovea_full", [&]() -> int {
+        DepthArgs d;
+        DepthFrame fr;
+        FrameWindow win;
+        UCHK(depth_frame_args(ctx, 1, nullptr, d_stackx, d_stacky, d_stackc, W, H, &off_x, &off_y, P1, P2, p, d_depth, d_valid, d, fr, &win));
+        return depth_frame(ctx, slot, d_stackx, d_stacky, P1, P2, d, fr, &win, p->format == UGSM_DEPTH_16U);
+    });
+}
+
+// ... from the stacks of n windows of one pair: what ugsm_reconstruct_full_multi followed by ugsm_depth_image gives
+int ugsm_depth_image_fovea_multi(ugsm_ctx *ctx, int slot, int n, const float *const *d_stack, int W, int H, const int *off_x, const int *off_y,
+                                 const double *P1, const double *P2, const ugsm_depth_params *p, void *d_depth, unsigned long long *d_valid)
+{
+    return named(ctx, "ugsm_depth_image_fovea_multi", [&]() -> int {
+        if (!d_stack) return UGSM_ERR_BAD_ARG;
+        DepthArgs d;
+        DepthFrame fr;
+        FrameWindow win[UGSM_MAX_BATCH];
+        UCHK(depth_frame_args(ctx, n, d_stack, nullptr, nullptr, nullptr, W, H, off_x, off_y, P1, P2, p, d_depth, d_valid, d, fr, win));
+        const size_t plane = (size_t)fr.F * fr.fw * fr.fh;
+        return depth_frame(ctx, slot, d_stack[0], d_stack[0] + plane, P1, P2, d, fr, win, p->format == UGSM_DEPTH_16U);
+    });
 }
 
 // ---- lens distortion (include/ugsm.h): the setting, and the definition on the host --------------------------------------------------

@@ -526,6 +526,39 @@ int ugsm_match_foveated(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR,
     return match_foveated_host(ctx, 0, rgbL, rgbR, W, H, stride, off_x, off_y, stackH, stackV, stackC, pyrL, pyrR, true);
 }
 
+// The foveated service call with the whole frame's depth image (REP 118) as its result: ugsm_match_foveated, then
+// ugsm_depth_image_fovea_full on the same slot from the stack in the slot's result staging, the image behind it; the image comes down, and
+// whichever stack planes are asked for.  The sibling of ugsm_match_full_depth.
+int ugsm_match_foveated_depth(ugsm_ctx *ctx, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, int off_x, int off_y,
+                              const double *P1, const double *P2, const ugsm_depth_params *p, void *depth, float *stackH, float *stackV, float *stackC)
+{
+    float *const dst[3] = {stackH, stackV, stackC};
+    FoveaRoom room;
+    size_t at_stack = 0, at_image = 0, image_bytes = 0;
+    auto check = [&](Slot &, size_t &hout) -> int {
+        int dw, dh;
+        if (!depth || !P1 || !P2 || ctx->cfg.fovea_levels < 2) return ctx_fail(ctx, UGSM_ERR_BAD_ARG, "ugsm_match_foveated_depth: a null pointer, or fovea_levels < 2");
+        if (depth_params_ok(p, true, W, H, &dw, &dh) != UGSM_OK) return ctx_fail(ctx, UGSM_ERR_BAD_ARG, "ugsm_match_foveated_depth: the depth parameters");
+        image_bytes = (size_t)dw * dh * (p->format == UGSM_DEPTH_16U ? 2 : 4);
+        UCHK(fovea_room(ctx, W, H, FoveaCall::Pairs, 1, room));
+        at_stack = room.part(room.stack);
+        at_image = room.part((image_bytes + 3) / 4);
+        hout = room.total;
+        return UGSM_OK;
+    };
+    auto match = [&](Slot &s) -> int {
+        float *d_stack = s.hout + at_stack, *d_none = nullptr;
+        UCHK(enqueue_foveated(ctx, s, 0, &s.rgbL.p, &s.rgbR.p, W, H, stride, FoveaCall::pairs(1, &off_x, &off_y, &d_stack, &d_none, &d_none)));
+        return ugsm_depth_image_fovea_full(ctx, 0, d_stack, d_stack + room.plane, d_stack + 2 * room.plane, W, H, off_x, off_y, P1, P2, p,
+                                           s.hout + at_image, nullptr);
+    };
+    return host_call(ctx, 0, true, rgbL, rgbR, W, H, stride, check, match, [&](Slot &s) -> int {
+        for (int k = 0; k < 3; k++)
+            if (dst[k]) UCHK(copy_out_bytes(ctx, s, s.hout + at_stack + k * room.plane, room.plane * sizeof(float), dst[k]));
+        return copy_out_bytes(ctx, s, s.hout + at_image, image_bytes, depth);
+    });
+}
+
 int ugsm_submit_foveated_host(ugsm_ctx *ctx, int slot, const uint8_t *rgbL, const uint8_t *rgbR, int W, int H, int stride, int off_x,
                               int off_y, float *stackH, float *stackV, float *stackC, float *pyrL, float *pyrR)
 {

@@ -1,6 +1,7 @@
 // ugsm_kernels_cloud.hip -- SURVEY 8f row f-1: triangulation of a match into X, Y, Z planes and into coloured point clouds.
 //
-// k_triangulate / k_triangulate_fovea (the X, Y, Z planes and, as their depth forms, the REP 118 depth image), k_cloud / k_cloud_fovea (the coloured cloud and the resized cloud of one field
+// k_triangulate / k_triangulate_fovea (the X, Y, Z planes and, as their depth forms, the REP 118 depth image -- k_triangulate's frame forms: the
+// depth image of the whole frame from a fovea stack), k_cloud / k_cloud_fovea (the coloured cloud and the resized cloud of one field
 // or one fovea level), k_cloud_stack (the merged cloud of a whole fovea stack), k_cloud_pairs / k_cloud_stack_pairs (the clouds of the pairs
 // of a queue call in one launch), k_cloud_multi (the merged cloud of several windows' stacks).  Every cloud kernel is one tile routine,
 // cloud_tile, under a preamble of its own.  HBM-bound.
@@ -104,15 +105,143 @@ constexpr int kCloudTC = 32;             // sampled columns per tile
 constexpr int kCloudTR = 64;             // sampled rows per tile = lanes of a wave (phase B)
 constexpr int kCloudPad = kCloudTR + 1;  // records per column in LDS: column c starts 4c banks further on (phase A stores 32 columns at once)
 
+// Where a pixel's (dx, dy, conf) comes from -- template parameter Src of tri_at, resized_point, depth_run and depth_resized.  PlaneSrc, the
+// default: the planes of CloudArgs, read where each routine has always read them; its instances are the code they were (tools/isa_dump.py
+// --diff).  FrameSrc (k_triangulate's frame forms): the value ugsm_reconstruct_full[_multi] would have put at frame pixel (x, y), by descent through the
+// fovea stack as k_restrict_stack walks it.  At level l < F-1 the site lies inside a window when 0 <= x - ox[l] < fw && 0 <= y - oy[l] < fh
+// (Table: every window is tried and the highest-numbered one that holds the site supplies the value); else it moves to
+// tex_index(((float)x + 0.5f) / s, w[l + 1]), the same in y; level F-1 holds every site and is stack 0's.  The level's sizes and the windows'
+// origins are uniform (scalar loads by a uniform index); a lane that has found its level stops moving, and the wave leaves the loop when every
+// lane has.  Then one multiplication by s per level descended, every channel, each product rounded on its own.  A thread walks the N pixels of
+// its run side by side, so that their loads go out together.  Nothing is read outside the stacks: a window test precedes every read of a
+// level below F-1 and tex_index clamps to level F-1's own size (the launcher checks that every window lies inside its level).  A disparity
+// never indexes anything here: NaN, infinite and huge values pass through.
+struct PlaneSrc {
+    static constexpr bool kPlanes = true;
+};
+// tex_index(((float)c + 0.5f) / s, n) for c >= 0, s = (float)1.41421356: a descent's step, two of them per pixel and level, and the IEEE
+// division is what the step costs.  q = a * RN(1 / s) lies within 1.5 q 2^-23 of the quotient's exact value and of its rounded one, so
+// wherever q is further than q 2^-21 from both neighbouring integers, floor(q) IS floor(RN(a / s)); elsewhere (3 columns in a thousand of a
+// 16 MP frame; every q from 2^21 on) the division itself is made, behind a branch a wave skips when no lane needs it.  Every operation is a
+// binary32 one with the same result on the host: the equality has been checked there for every c below 2^28.
+__device__ __forceinline__ int frame_down(int c, int n)
+{
+    const float s = (float)1.41421356, rs = 1.0f / s;
+    const float a = (float)c + 0.5f;
+    const float q = a * rs;
+    float f = floorf(q);
+    const float fr = q - f, m = q * 0x1p-21f;
+    if (!(fr > m && fr < 1.0f - m)) f = floorf(a / s);
+    return f > (float)(n - 1) ? n - 1 : (int)f;  // (f >= 0: tex_index's other clamp never acts)
+}
+template <bool Table>
+struct FrameSrc {
+    static constexpr bool kPlanes = false;
+    const float *sx, *sy, *sc;  // stack 0's planes; sc null: no confidence (0.0f)
+    const DepthFrame *f;
+    template <int N>
+    __device__ __forceinline__ void fetch(const int (&px)[N], const int (&py)[N], float (&dx)[N], float (&dy)[N], float (&cf)[N]) const
+    {
+        const float s = (float)1.41421356;
+        const DepthFrame &fr = *f;
+        const int fn = fr.fw * fr.fh, last = fr.F - 1;
+        int x[N], y[N], depth[N], at[N];
+        long long sh[N];
+        bool found[N];
+#pragma unroll
+        for (int e = 0; e < N; e++) {
+            x[e] = px[e];
+            y[e] = py[e];
+            depth[e] = last;
+            at[e] = 0;
+            sh[e] = 0;
+            found[e] = false;
+        }
+        for (int l = 0; l < last; l++) {  // (uniform)
+            bool hit[N];
+#pragma unroll
+            for (int e = 0; e < N; e++) hit[e] = false;
+            const int nw = Table ? fr.n : 1;
+            for (int j = 0; j < nw; j++) {
+                const FrameWindow &w = Table ? fr.table[j] : fr.win;
+                const int ox = w.ox[l], oy = w.oy[l];
+                const long long st = w.stack;
+#pragma unroll
+                for (int e = 0; e < N; e++) {
+                    const int fx = x[e] - ox, fy = y[e] - oy;
+                    if (!found[e] && fx >= 0 && fx < fr.fw && fy >= 0 && fy < fr.fh) {
+                        hit[e] = true;
+                        at[e] = l * fn + fy * fr.fw + fx;
+                        sh[e] = st;
+                    }
+                }
+            }
+            bool open = false;
+#pragma unroll
+            for (int e = 0; e < N; e++) {
+                if (hit[e]) {
+                    found[e] = true;
+                    depth[e] = l;
+                } else if (!found[e]) {
+                    x[e] = frame_down(x[e], fr.w[l + 1]);
+                    open = true;
+                }
+            }
+            // rows move whether found or not (a found lane no longer reads its row), so that a pixel in its left neighbour's row takes that
+            // neighbour's: a run lies in one row or two
+#pragma unroll
+            for (int e = 0; e < N; e++) {
+                if (e > 0 && py[e] == py[e - 1]) y[e] = y[e - 1];
+                else y[e] = frame_down(y[e], fr.h[l + 1]);
+            }
+            if (__ballot(open) == 0) break;
+        }
+#pragma unroll
+        for (int e = 0; e < N; e++) {
+            if (!found[e]) at[e] = last * fn + y[e] * fr.fw + x[e];
+            dx[e] = shifted(sx, sh[e])[at[e]];
+            dy[e] = shifted(sy, sh[e])[at[e]];
+            cf[e] = sc ? shifted(sc, sh[e])[at[e]] : 0.0f;
+        }
+        for (int j = 0; j < last; j++) {  // (uniform; a lane multiplies while j < its depth)
+#pragma unroll
+            for (int e = 0; e < N; e++) {
+                if (j < depth[e]) {
+                    dx[e] = s * dx[e];
+                    dy[e] = s * dy[e];
+                    cf[e] = s * cf[e];
+                }
+            }
+        }
+    }
+    __device__ __forceinline__ void fetch1(int x, int y, float &dx, float &dy, float &cf) const
+    {
+        const int px[1] = {x}, py[1] = {y};
+        float vx[1], vy[1], vc[1];
+        fetch<1>(px, py, vx, vy, vc);
+        dx = vx[0];
+        dy = vy[0];
+        cf = vc[0];
+    }
+};
+
 // X, Y, Z of pixel (ii, jj) of the planes, from the same operands as the plane kernels (bit-identical to them); (x1, y1) the pixel in the
 // full-resolution frame.
-template <bool Fovea, bool L = false>
+template <bool Fovea, bool L = false, class Src = PlaneSrc>
 __device__ __forceinline__ void tri_at(const CloudArgs &a, const Proj &P1q, const Proj &P2q, int ii, int jj, float &x1, float &y1, float &X,
-                                       float &Y, float &Z, const Lens *ln = nullptr)
+                                       float &Y, float &Z, const Lens *ln = nullptr, const Src *src = nullptr)
 {
     const size_t at = (size_t)jj * a.pw + ii;
     float x2, y2;
-    if (Fovea) {  // as k_triangulate_fovea
+    if constexpr (!Src::kPlanes) {  // the field form on the source's value
+        static_assert(!Fovea, "a source other than the planes gives a full-resolution field");
+        float ddx, ddy, unused;
+        src->fetch1(ii, jj, ddx, ddy, unused);
+        x1 = ii;
+        y1 = jj;
+        x2 = ii + ddx;
+        y2 = jj + ddy;
+    } else if (Fovea) {  // as k_triangulate_fovea
         x1 = (float)a.left_margin + (float)ii * a.scale;
         y1 = (float)a.upper_margin + (float)jj * a.scale;
         const int sx = (int)(ii + a.dx[at]);
@@ -240,15 +369,15 @@ __device__ __forceinline__ void cubic_tap(int d, double scale, int n, int &s, fl
 
 // Rec (the depth image's use): the record is written whether or not there is a colour to read -- (X, Y, Z, 0) -- so that rec.z hands the
 // resized map's Z to a caller that keeps nothing else
-template <bool Fovea, bool Colour, bool Rec = Colour, bool L = false>
+template <bool Fovea, bool Colour, bool Rec = Colour, bool L = false, class Src = PlaneSrc>
 __device__ __forceinline__ bool resized_point(const CloudArgs &a, const CloudResize &rz, const Proj &P1q, const Proj &P2q, int ii, int jj,
-                                              float4 &rec, const Lens *ln = nullptr)
+                                              float4 &rec, const Lens *ln = nullptr, const Src *src = nullptr)
 {
     // (ii < (int)(pw * f) keeps ii / f below pw; the clamp never acts)
     const int xx = min((int)((float)ii / rz.factor), a.pw - 1);
     const int yy = min((int)((float)jj / rz.factor), a.ph - 1);
     float x1, y1, X, Y, Z;
-    tri_at<Fovea, L>(a, P1q, P2q, xx, yy, x1, y1, X, Y, Z, ln);
+    tri_at<Fovea, L, Src>(a, P1q, P2q, xx, yy, x1, y1, X, Y, Z, ln, src);
     // the colour is read before the taps: its loads go out with the centre pixel's dx, dy, not one round trip after the taps
     const bool mapped = Fovea && rz.colour_mapped;
     const unsigned word = Colour ? colour_at<Fovea>(a, mapped ? (int)x1 : xx, mapped ? (int)y1 : yy) : 0u;
@@ -266,7 +395,7 @@ __device__ __forceinline__ bool resized_point(const CloudArgs &a, const CloudRes
 #pragma unroll
             for (int k = 0; k < 4; k++) {
                 float u1, u2, u3, u4;
-                tri_at<Fovea, L>(a, P1q, P2q, min(max(sx - 1 + k, 0), a.pw - 1), ty, u1, u2, u3, u4, s[k], ln);
+                tri_at<Fovea, L, Src>(a, P1q, P2q, min(max(sx - 1 + k, 0), a.pw - 1), ty, u1, u2, u3, u4, s[k], ln, src);
             }
             const float p0 = s[0] * cx[0];
             const float h = (((border ? 0.0f + p0 : p0) + s[1] * cx[1]) + s[2] * cx[2]) + s[3] * cx[3];
@@ -325,8 +454,9 @@ __device__ __forceinline__ void depth_count(const DepthArgs &d, int level, unsig
 // (0 .. Run-1): run 0 is the head, the last run the tail, and both go element by element; every run between them is stored with one 16-byte
 // store, and loaded with 16-byte loads where dx, dy and conf are 16-byte aligned at pixel `head` too (else with 4-byte loads).  Nothing but a
 // pixel's own bytes is written.  A workgroup takes 256 runs at a time and walks on by the grid's width.
-template <bool Fovea, bool U16, bool L>
-__device__ __forceinline__ void depth_run(const CloudArgs &a, const DepthArgs &d, const Proj &P1q, const Proj &P2q, int level, const Lens *ln)
+template <bool Fovea, bool U16, bool L, class Src = PlaneSrc>
+__device__ __forceinline__ void depth_run(const CloudArgs &a, const DepthArgs &d, const Proj &P1q, const Proj &P2q, int level, const Lens *ln,
+                                          const Src *src = nullptr)
 {
     constexpr int Size = U16 ? 2 : 4, Run = 16 / Size;
     const int n = a.pw * a.ph;
@@ -340,7 +470,23 @@ __device__ __forceinline__ void depth_run(const CloudArgs &a, const DepthArgs &d
         const int i0 = head - Run + (r0 + (int)threadIdx.x) * Run;
         const bool full = i0 >= 0 && i0 + Run <= n;
         float ddx[Run], ddy[Run], cf[Run];
-        if (full && wide) {
+        if constexpr (!Src::kPlanes) {  // the run's pixels side by side through the source (a pixel outside the image: pixel (0, 0)'s, unused)
+            int px[Run], py[Run];
+            const int first = max(i0, 0);
+            int fy = first / a.pw, fx = first - fy * a.pw;
+#pragma unroll
+            for (int e = 0; e < Run; e++) {
+                const int i = i0 + e;
+                const bool in = i >= 0 && i < n;
+                px[e] = in ? fx : 0;
+                py[e] = in ? fy : 0;
+                if (in && ++fx == a.pw) {
+                    fx = 0;
+                    fy++;
+                }
+            }
+            src->template fetch<Run>(px, py, ddx, ddy, cf);
+        } else if (full && wide) {
 #pragma unroll
             for (int q = 0; q < Run / 4; q++) {
                 const float4 vx = reinterpret_cast<const float4 *>(a.dx + i0)[q], vy = reinterpret_cast<const float4 *>(a.dy + i0)[q];
@@ -400,8 +546,9 @@ __device__ __forceinline__ void depth_run(const CloudArgs &a, const DepthArgs &d
 // tri_at).  Z is the z of resized_point's record -- the resized clouds' own routine, with no colour to read and nothing to keep (`a` is a
 // dense cloud's: compact 0) --; the confidence is read where that routine registers the pixel, (xx, yy) = ((int)((float)ii / factor),
 // (int)((float)jj / factor)), inside the plane as there.
-template <bool Fovea, bool U16, bool L>
-__device__ __forceinline__ void depth_resized(const CloudArgs &a, const DepthArgs &d, const Proj &P1q, const Proj &P2q, int level, const Lens *ln)
+template <bool Fovea, bool U16, bool L, class Src = PlaneSrc>
+__device__ __forceinline__ void depth_resized(const CloudArgs &a, const DepthArgs &d, const Proj &P1q, const Proj &P2q, int level, const Lens *ln,
+                                              const Src *src = nullptr)
 {
     const int n = d.dw * d.dh;
     unsigned count = 0;
@@ -411,9 +558,15 @@ __device__ __forceinline__ void depth_resized(const CloudArgs &a, const DepthArg
         if (i < n) {
             const int jj = i / d.dw, ii = i - jj * d.dw;
             const int xx = min((int)((float)ii / d.rz.factor), a.pw - 1), yy = min((int)((float)jj / d.rz.factor), a.ph - 1);
-            const float cf = a.conf ? a.conf[(size_t)yy * a.pw + xx] : 0.0f;
+            float cf;
+            if constexpr (!Src::kPlanes) {
+                float ux, uy;
+                src->fetch1(xx, yy, ux, uy, cf);
+            } else {
+                cf = a.conf ? a.conf[(size_t)yy * a.pw + xx] : 0.0f;
+            }
             float4 rec;
-            resized_point<Fovea, false, true, L>(a, d.rz, P1q, P2q, ii, jj, rec, ln);
+            resized_point<Fovea, false, true, L, Src>(a, d.rz, P1q, P2q, ii, jj, rec, ln, src);
             unsigned bits;
             valid = depth_element<U16>(d, rec.z, cf, bits);
             const size_t o = (size_t)level * n + i;
@@ -427,10 +580,21 @@ __device__ __forceinline__ void depth_resized(const CloudArgs &a, const DepthArg
 
 // What k_triangulate / k_triangulate_fovea emit (template parameter): the X, Y, Z planes, or the depth image in its four forms.  The planes'
 // instances keep the argument list and the body they had as plain kernels; a depth instance takes its DepthArgs where they take the planes.
-enum TriEmit : int { kEmitPlanes = 0, kEmitDepth32F = 1, kEmitDepth16U = 2, kEmitResized32F = 3, kEmitResized16U = 4 };
+// k_triangulate alone has the frame forms: the depth image of the WHOLE frame from a fovea stack (ugsm_depth_image_fovea_full / _multi;
+// DepthFrame, ugsm_launch.hpp) -- the four depth forms over the W x H frame, the same runs, stores, grid and count, every (dx, dy, conf) a
+// FrameSrc descent instead of a plane read; dispx / dispy are then stack 0's dx and dy planes.  kEmitFrame + a depth form: the window in the
+// arguments; kEmitFrameTable + a depth form: the n > 1 windows read from the table.
+enum TriEmit : int { kEmitPlanes = 0, kEmitDepth32F = 1, kEmitDepth16U = 2, kEmitResized32F = 3, kEmitResized16U = 4, kEmitFrame = 4, kEmitFrameTable = 8 };
+constexpr bool emit_frame(int emit) { return emit > kEmitFrame; }
+constexpr bool emit_table(int emit) { return emit > kEmitFrameTable; }
+constexpr int emit_depth(int emit) { return emit > kEmitFrameTable ? emit - kEmitFrameTable : emit > kEmitFrame ? emit - kEmitFrame : emit; }
+struct DepthFrameArgs {
+    DepthArgs d;
+    DepthFrame fr;
+};
 template <int Emit>
 struct TriOut {
-    using field = DepthArgs;
+    using field = std::conditional_t<emit_frame(Emit), DepthFrameArgs, DepthArgs>;
     using fovea = DepthFoveaArgs;
 };
 template <>
@@ -462,6 +626,15 @@ __global__ __launch_bounds__(256) void k_triangulate(const float *__restrict__ d
         xyz[at] = X;
         xyz[n + at] = Y;
         xyz[2 * n + at] = Z;
+    } else if constexpr (emit_frame(Emit)) {
+        constexpr int Form = emit_depth(Emit);
+        CloudArgs a{};
+        a.conf = out.d.conf;
+        a.pw = W;
+        a.ph = H;
+        const FrameSrc<emit_table(Emit)> src{dispx, dispy, out.d.conf, &out.fr};
+        if constexpr (Form == kEmitDepth32F || Form == kEmitDepth16U) depth_run<false, Form == kEmitDepth16U, L>(a, out.d, P1q, P2q, 0, ln, &src);
+        else depth_resized<false, Form == kEmitResized16U, L>(a, out.d, P1q, P2q, 0, ln, &src);
     } else {
         CloudArgs a{};
         a.dx = dispx;
@@ -587,6 +760,40 @@ void launch_depth_image_fovea(hipStream_t st, const float *stackx, const float *
                                        : (u16 ? (KernLens)k_triangulate_fovea<kEmitDepth16U, Lens> : (KernLens)k_triangulate_fovea<kEmitDepth32F, Lens>);
     UGSM_LAUNCH_LENS(lens, kern, kern_lens, dim3(depth_blocks((long long)d.d.dw * d.d.dh, resized, u16), d.lv.levels), st, stackx, stacky, fovW, fovH,
                      src_level, 0, 0, 0.0f, a, b, d);
+}
+
+template <int Base>
+static void launch_depth_frame(hipStream_t st, const float *stackx, const float *stacky, const Proj &a, const Proj &b, const DepthFrameArgs &d, bool u16,
+                               const Lens *lens)
+{
+    using Kern = void (*)(const float *, const float *, int, int, Proj, Proj, DepthFrameArgs);
+    using KernLens = void (*)(const float *, const float *, int, int, Proj, Proj, DepthFrameArgs, Lens);
+    const bool resized = d.d.rz.factor < 1.0f;
+    const Kern kern = resized ? (u16 ? (Kern)k_triangulate<Base + kEmitResized16U> : (Kern)k_triangulate<Base + kEmitResized32F>)
+                              : (u16 ? (Kern)k_triangulate<Base + kEmitDepth16U> : (Kern)k_triangulate<Base + kEmitDepth32F>);
+    const KernLens kern_lens = resized ? (u16 ? (KernLens)k_triangulate<Base + kEmitResized16U, Lens> : (KernLens)k_triangulate<Base + kEmitResized32F, Lens>)
+                                       : (u16 ? (KernLens)k_triangulate<Base + kEmitDepth16U, Lens> : (KernLens)k_triangulate<Base + kEmitDepth32F, Lens>);
+    UGSM_LAUNCH_LENS(lens, kern, kern_lens, dim3(depth_blocks((long long)d.d.dw * d.d.dh, resized, u16)), st, stackx, stacky, d.fr.w[0], d.fr.h[0], a, b, d);
+}
+
+bool launch_depth_image_frame(hipStream_t st, const float *stackx, const float *stacky, const double *P1, const double *P2, const DepthArgs &d,
+                              DepthFrame fr, const FrameWindow *win, bool u16, const Lens *lens)
+{
+    if (!win || fr.n < 1 || fr.n > kMaxBatch || fr.F < 2 || fr.F > kCloudMaxLevels || (fr.n > 1) != (fr.table != nullptr)) return false;
+    if (fr.fw < 1 || fr.fh < 1 || fr.w[fr.F - 1] != fr.fw || fr.h[fr.F - 1] != fr.fh || (long long)fr.F * fr.fw * fr.fh > 0x7fffffffll) return false;
+    if ((long long)fr.w[0] * fr.h[0] > (1ll << 28) || d.dw < 1 || d.dh < 1 || d.dw > fr.w[0] || d.dh > fr.h[0]) return false;
+    if (!(d.rz.factor < 1.0f) && (d.dw != fr.w[0] || d.dh != fr.h[0])) return false;
+    for (int l = 0; l < fr.F; l++)
+        if (fr.w[l] < 1 || fr.h[l] < 1) return false;  // (tex_index clamps to n - 1: every read lies inside its level)
+    for (int j = 0; j < fr.n; j++)
+        for (int l = 0; l < fr.F - 1; l++)
+            if (win[j].ox[l] < 0 || win[j].oy[l] < 0 || win[j].ox[l] + fr.fw > fr.w[l] || win[j].oy[l] + fr.fh > fr.h[l]) return false;
+    const Proj a = proj(P1), b = proj(P2);
+    if (!fr.table) fr.win = win[0];
+    const DepthFrameArgs args{d, fr};
+    if (fr.table) launch_depth_frame<kEmitFrameTable>(st, stackx, stacky, a, b, args, u16, lens);
+    else launch_depth_frame<kEmitFrame>(st, stackx, stacky, a, b, args, u16, lens);
+    return true;
 }
 
 // The merged cloud of the whole fovea stack (ugsm_point_cloud_fovea_all; kTriStackCount / kTriStack): the same tile over F * strips

@@ -237,6 +237,29 @@ void launch_depth_image(hipStream_t st, const float *dispx, const float *dispy, 
                         bool u16, const Lens *lens = nullptr);
 void launch_depth_image_fovea(hipStream_t st, const float *stackx, const float *stacky, int fovW, int fovH, int src_level, const double *P1,
                               const double *P2, const DepthFoveaArgs &d, bool u16, const Lens *lens = nullptr);
+// The depth image of the WHOLE frame from a fovea stack (ugsm_depth_image_fovea_full / _multi): the frame forms of k_triangulate, the depth forms above over the
+// W x H frame (DepthArgs.dw x dh its image) with another source of a pixel's (dx, dy, conf) -- not a read of a full-resolution plane but the
+// value ugsm_reconstruct_full[_multi] would have put there, found per pixel as k_restrict_stack finds it: descend from level 0 until a
+// level's window holds the site (several windows: the highest-numbered one that does; level F-1 holds every site and is stack 0's), then as
+// many multiplications by (float)1.41421356 as levels were descended, every channel.  The field is never formed.
+// A window = its origin at every level l < F-1 and its stack's distance from stack 0 in BYTES (the three plane pointers of the launch are
+// stack 0's and every window's planes lie the same distance behind them).  One window travels in the kernel arguments; n > 1 are read from
+// `table`, n rows in DEVICE memory (sixteen do not fit among the arguments: kRestrictStackByValue, below).
+struct FrameWindow {
+    long long stack;
+    int ox[kCloudMaxLevels], oy[kCloudMaxLevels];
+};
+struct DepthFrame {
+    int n, F, fw, fh;                            // windows; fovea levels; a level's window (w[F-1] x h[F-1] = fw x fh)
+    int w[kCloudMaxLevels], h[kCloudMaxLevels];  // the sizes of the levels 0 .. F-1 (w[0] x h[0] = the frame)
+    const FrameWindow *table;                    // n > 1: the windows, in device memory; else null and `win` is the window
+    FrameWindow win;
+};
+// stackx / stacky: the dx and dy planes of stack 0 (F x fh x fw floats each), d.conf its confidence plane or null.  win: the n windows in HOST
+// memory -- checked here (n = 1: copied into the arguments; n > 1: they must be what fr.table holds).  False (nothing launched): a shape the
+// kernel's bounds do not cover -- a window that leaves its level, sizes that do not fit together, n > 1 without a table.
+bool launch_depth_image_frame(hipStream_t st, const float *stackx, const float *stacky, const double *P1, const double *P2, const DepthArgs &d,
+                              DepthFrame fr, const FrameWindow *win, bool u16, const Lens *lens = nullptr);
 void launch_upsample_paste(hipStream_t st, const float *src3, int W, int H, float *dst3, int W2, int H2, const float *fovH_, const float *fovV_,
                            const float *fovC_, int fovW, int fovH, int org_x, int org_y);
 // The same step with the fovea of n stacks of one pair (ugsm_reconstruct_full_multi): window k's crop origin at this level, and its stack's

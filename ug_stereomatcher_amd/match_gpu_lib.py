@@ -184,6 +184,22 @@ class MatchGPULib:
         prm = _lib.depth_params(format=_lib.DEPTH_ENCODINGS[encoding], unit=unit, min_conf=min_conf, z_min=z_min, z_max=z_max, factor=factor)
         return self._ctx.match_full_depth(L, R, P1, P2, prm, planes=planes)
 
+    def depthImageFrame(self, cv_ptrL, cv_ptrR, P1, P2, encoding: str = "32FC1", unit: float = 1.0, min_conf: float = float("-inf"),
+                        z_min: float = float("-inf"), z_max: float = float("inf"), factor: float = 1.0, off_x: int = 0, off_y: int = 0,
+                        stack: bool = False):
+        """The foveated match of (L, R) at window offset (off_x, off_y) and the REP 118 depth image of the WHOLE frame from its stack
+        (ugsm_match_foveated_depth): what hierarchicalDisparity of matchStack's result followed by the depth image of that field gives, without
+        the field.  Encodings and unit as depthImage.  Returns the (dh, dw) image; with stack, (image, stack as matchStack returns it)."""
+        if encoding not in _lib.DEPTH_ENCODINGS:
+            raise UgsmError(_lib.UGSM_ERR_BAD_ARG, f"depth encoding {encoding!r}: 32FC1 or 16UC1")
+        L, R = self._take(cv_ptrL, cv_ptrR)
+        self.foveatedmatching = 1
+        prm = _lib.depth_params(format=_lib.DEPTH_ENCODINGS[encoding], unit=unit, min_conf=min_conf, z_min=z_min, z_max=z_max, factor=factor)
+        if not stack:
+            return self._ctx.match_foveated_depth(L, R, P1, P2, prm, off=(off_x, off_y))
+        img, st = self._ctx.match_foveated_depth(L, R, P1, P2, prm, off=(off_x, off_y), stack=True)
+        return img, np.ascontiguousarray(np.transpose(st, (1, 0, 2, 3)))
+
     # -- lens distortion (not in the reference: its cloud node reads K and D and never uses them) --
     def setLens(self, K1, D1, K2, D2, iterations: int = 5):
         """The plumb_bob K and D of the two CameraInfo messages: depthImage and every cloud taken from this matcher's context undistort the two
