@@ -15,7 +15,7 @@ PRODUCT_KERNELS = {"k_cost_march", "k_cost_march4", "k_cost_small", "k_smooth_sm
                    "k_triangulate_fovea", "k_upsample_paste", "k_wdiff_rows", "k_wdiff_total",
                    "k_restrict", "k_prolong", "k_level0_windows", "k_warp_right", "k_residual_rows", "k_residual_total", "k_upsample_paste_multi",
                    "k_restrict_stack", "k_cloud", "k_cloud_fovea", "k_cloud_stack", "k_cloud_pairs", "k_cloud_stack_pairs", "k_cloud_multi"}
-SHIPPED_HIP = ["ugsm_kernels_aux.hip", "ugsm_kernels_cloud.hip", "ugsm_kernels_fields.hip", "ugsm_kernels_march.hip", "ugsm_kernels_march4.hip",
+SHIPPED_HIP = ["ugsm_kernels_aux.hip", "ugsm_kernels_cloud.hip", "ugsm_kernels_depth.hip", "ugsm_kernels_fields.hip", "ugsm_kernels_march.hip", "ugsm_kernels_march4.hip",
                "ugsm_kernels_pyr.hip", "ugsm_kernels_small.hip", "ugsm_kernels_smooth.hip", "ugsm_kernels_warp.hip"]
 
 
@@ -105,16 +105,47 @@ def test_a_kernel_name_is_one_operation(lib):
 
 def test_product_kernel_sources_hold_no_development_switch():
     """the shipped .hip files compile with no -D probe macro recognised -- no preprocessor conditional at all -- and libugsm_dev.so
-    is those same files plus csrc/dev/."""
+    is those same files plus csrc/dev/.  The same OBJECTS: what make would run (a dry run: nothing is compiled) compiles every source once,
+    with no -D, and the two libraries are two links that differ only in the objects they name."""
+    import shutil
+    import subprocess
     csrc = os.path.join(ROOT, "ug_stereomatcher_amd", "csrc")
     files = sorted(f for f in os.listdir(csrc) if f.endswith(".hip"))
     assert files == SHIPPED_HIP
     for f in files:
         src = open(os.path.join(csrc, f)).read()
         assert not re.search(r"^\s*#\s*(if|ifdef|ifndef|elif|else|endif)\b", src, re.M), f
-        assert "UGSM_DEV_LIB" not in src and "UGSM_DEV_KERNELS" not in src, f
-    mk = open(os.path.join(csrc, "Makefile")).read()
-    assert re.search(r"\$\(OUT\): \$\(SRCS\) \$\(HDRS\)\n\t\$\(HIPCC\) \$\(FLAGS\) \$\(SRCS\) -o", mk) and "dev/ugsm_dev_" not in mk.split("DEV_SRCS")[0]
+    every = [os.path.join(d, f) for d in (csrc, os.path.join(csrc, "dev")) for f in sorted(os.listdir(d)) if os.path.isfile(os.path.join(d, f))]
+    assert len(every) > 30
+    for f in every:
+        src = open(f).read()
+        assert not re.search(r"UGSM_DEV_(LIB|KERNELS)", src), f   # (the two macros that once told the libraries apart)
+    make = shutil.which("make")
+    assert make, "make: the build's own tool"
+    plan = subprocess.run([make, "-n", "-B", "-C", csrc, "all"], capture_output=True, text=True, check=True).stdout
+    cmds = [line.split() for line in plan.splitlines() if "hipcc" in line.split(" ")[0]]
+    compiles, links = [c for c in cmds if "-c" in c], [c for c in cmds if "-shared" in c]
+    assert len(compiles) + len(links) == len(cmds) and not [c for c in compiles if "-shared" in c]
+    assert not [a for c in cmds for a in c if a.startswith("-D")]
+    srcs = lambda c: [os.path.relpath(a, csrc) for a in c if a.endswith((".hip", ".cpp"))]
+    assert all(len(srcs(c)) == 1 for c in compiles)
+    compiled = sorted(srcs(c)[0] for c in compiles)
+    # every source file of csrc/ and csrc/dev/ is compiled, and exactly once
+    assert compiled == sorted(os.path.relpath(f, csrc) for f in every if f.endswith((".hip", ".cpp"))), compiled
+    shared = [s for s in compiled if not s.startswith("dev" + os.sep) and s != "ugsm_no_dev.cpp"]
+    assert set(SHIPPED_HIP) <= set(shared) and len(shared) >= 24
+    obj_of = {s: os.path.join("build", os.path.splitext(s)[0] + ".o") for s in compiled}
+    for c in compiles:   # ... into the object the links name
+        assert os.path.relpath(c[c.index("-o") + 1], csrc) == obj_of[srcs(c)[0]], c
+    objs = lambda c: sorted(os.path.relpath(a, csrc) for a in c if a.endswith(".o"))
+    out = lambda c: os.path.basename(c[c.index("-o") + 1])
+    by_out = {out(c): c for c in links}
+    assert sorted(by_out) == ["libugsm.so", "libugsm_dev.so"] and len(links) == 2
+    assert not srcs(by_out["libugsm.so"]) and not srcs(by_out["libugsm_dev.so"]) and "hip" not in by_out["libugsm.so"] + by_out["libugsm_dev.so"]  # (-x hip)
+    # libugsm.so: the shared objects + ugsm_no_dev, nothing from dev/; libugsm_dev.so: the shared objects + dev/, not ugsm_no_dev
+    assert objs(by_out["libugsm.so"]) == sorted(obj_of[s] for s in shared + ["ugsm_no_dev.cpp"])
+    assert objs(by_out["libugsm_dev.so"]) == sorted(obj_of[s] for s in compiled if s != "ugsm_no_dev.cpp")
+    assert len([s for s in compiled if s.startswith("dev" + os.sep)]) >= 4
 
 
 def test_product_refuses_the_configurations_of_the_development_library(lib):

@@ -16,7 +16,6 @@
 //   15  tile heights of the 112-column K-smooth tile: bits against 36 rows, timing
 //   18  two kernels on two streams: alone and side by side
 //   20  level 0 from the 8-bit image: K-cost and A on the float planes against their rgb8 instances -- bits, then timing, alternating
-#define UGSM_DEV_LIB 1  // (the launch header's declarations of the dev kernels)
 #include "../ug_stereomatcher_amd/csrc/ugsm_kernels_aux.hip"
 #include "../ug_stereomatcher_amd/csrc/ugsm_kernels_pyr.hip"
 #include "../ug_stereomatcher_amd/csrc/ugsm_kernels_smooth.hip"

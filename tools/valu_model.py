@@ -21,7 +21,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "ug_stereomatcher_amd", "csrc")
-FLAGS = ["-O3", "-std=c++17", "-DUGSM_DEV_LIB", "--offload-arch=gfx950", "-ffp-contract=off", "-fno-fast-math", "-fno-slp-vectorize", "-x", "hip", "-S",
+FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off", "-fno-fast-math", "-fno-slp-vectorize", "-x", "hip", "-S",
          "--cuda-device-only"]
 
 # valubench kernel -> cost class

@@ -1,7 +1,7 @@
 // ugsm_cloud.cpp -- row f-1 of the runtime: triangulation and the coloured point clouds (getPointCloud.cpp), on the slots of ugsm_runtime.cpp.
 // The fovea forms' geometry and the coverage rule of the merged clouds (host only), the slot-level entry points behind one description of a
 // cloud call (cloud_call_args) and one preamble (cloud_begin), and the queue's cloud calls (CtxHooks::cloud_submit / cloud_finish), which use
-// both.  Every cloud kernel is cloud_tile (ugsm_kernels_cloud.hip).
+// both.  Every cloud kernel is cloud_tile (ugsm_kernels_cloud.hip); the planes and the depth images are k_triangulate[_fovea]'s (ugsm_kernels_depth.hip).
 #include "ugsm_slot.hpp"
 
 #include <algorithm>

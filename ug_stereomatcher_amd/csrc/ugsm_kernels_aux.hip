@@ -3,8 +3,8 @@
 // k_seed (a level's starting field where the next level's K-cost does not seed itself), k_copy_view (the fovea / pyramid stacks),
 // k_lr_check (the opt-in LR-consistency check, on a field and on a stack), k_rgb_planes (level 0 of a pyramid of fewer than three levels:
 // BASELINE configs[0]), k_level0_windows (level 0 inside the windows of a multi-window foveated call), k_wdiff_rows / k_wdiff_total
-// (SURVEY 8f row f-4).  All HBM- or launch-bound.  Fields between levels and stacks: ugsm_kernels_fields.hip; the point clouds:
-// ugsm_kernels_cloud.hip; the warp and the photometric residual: ugsm_kernels_warp.hip.
+// (SURVEY 8f row f-4).  All HBM- or launch-bound.  Fields between levels and stacks: ugsm_kernels_fields.hip; the X, Y, Z planes and
+// the depth images: ugsm_kernels_depth.hip; the point clouds: ugsm_kernels_cloud.hip; the warp and the photometric residual: ugsm_kernels_warp.hip.
 // Citations: /root/reference/src/gpu_matcher/<file>:<line> unless a path is given.
 #include "ugsm_device.hpp"
 #include "ugsm_launch.hpp"

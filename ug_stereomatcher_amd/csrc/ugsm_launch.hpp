@@ -62,7 +62,7 @@ struct Batch {
     long long out[kMaxBatch];  // pair b's output: nd3 / o3 / dst (a slot buffer, or the caller's)
 };
 
-// ---- plain per-pixel kernels (ugsm_kernels_aux.hip, _fields.hip, _cloud.hip, _warp.hip) ----
+// ---- plain per-pixel kernels (ugsm_kernels_aux.hip, _fields.hip, _depth.hip, _cloud.hip, _warp.hip) ----
 void launch_seed(hipStream_t st, const float *src3, int Ws, int Hs, float *dst3, int Wd, int Hd, int cx, int cy, const Batch *bt = nullptr);
 // The restriction, k_restrict (ugsm_submit_full_seeded): level `level`'s starting field dst3 (w x h, the level's size) from the
 // full-resolution field src3 (W x H).  Batched: pair b reads src3 + bt->in[b] bytes and writes dst3 + bt->out[b] bytes.
@@ -325,12 +325,12 @@ struct ResidualArgs {
 };
 void launch_residual(hipStream_t st, const ResidualArgs &a, int in, double *sums);
 
-// ---- libugsm_dev.so only (UGSM_DEV_LIB; csrc/dev/): kernel_path 1 (one kernel per reference stage), round 1's LDS-tiled K-cost
-// (ugsm_config.march_min_pixels < 0) and the probe kernels.  The product build has no-op stand-ins so that the runtime reads the same;
-// ugsm_create refuses the configurations that would reach them, the kernel-choice policy gives every other level a shipped K-cost form
-// (run_level answers UGSM_ERR_STATE rather than reach launch_cost_fused here) and the probe entry points are not compiled in.
-#ifdef UGSM_DEV_LIB
-constexpr bool kDevLib = true;
+// ---- libugsm_dev.so only (csrc/dev/): kernel_path 1 (one kernel per reference stage), round 1's LDS-tiled K-cost
+// (ugsm_config.march_min_pixels < 0) and the probe kernels.  The product links no-op stand-ins (ugsm_no_dev.cpp) so that the runtime is the
+// same objects in both libraries; ugsm_create refuses the configurations that would reach them, the kernel-choice policy gives every other level
+// a shipped K-cost form (run_level answers UGSM_ERR_STATE rather than reach launch_cost_fused here) and the probe entry points
+// (dev/ugsm_dev_entries.cpp) are not linked in.  kDevLib: which of the two a library is, defined by the file only it links.
+extern const bool kDevLib;
 void launch_blur_decimate_ref(hipStream_t st, const float *src3, int W, int H, float *dst3, int W2, int H2, float sf);
 void launch_sqblur_clamp_ref(hipStream_t st, Img3 src, int W, int H, float *dst3);
 void launch_warp_ref(hipStream_t st, Img3 R, const float *d3, int W, int H, float *Rw3);
@@ -344,16 +344,6 @@ void launch_cost_fused(hipStream_t st, Img3 L, Img3 R, const float *A3, const fl
 void launch_div_probe(hipStream_t st, const float *n, const float *d, float *q, int count);
 void launch_div3_probe(hipStream_t st, const float *a0, const float *a1, const float *a2, const float *s, float *q0, float *q1, float *q2, int n);
 void launch_poly_probe(hipStream_t st, const float *c, const float *l, const float *r, const float *thr, float *delta, float *corr, float *third, int n);
-#else
-constexpr bool kDevLib = false;
-inline void launch_blur_decimate_ref(hipStream_t, const float *, int, int, float *, int, int, float) {}
-inline void launch_sqblur_clamp_ref(hipStream_t, Img3, int, int, float *) {}
-inline void launch_warp_ref(hipStream_t, Img3, const float *, int, int, float *) {}
-inline void launch_cost_ref(hipStream_t, Img3, const float *, const float *, const float *, const float *, float *, int, int, float, int, float *) {}
-inline void launch_smooth_pass_ref(hipStream_t, const float *, float *, int, int) {}
-inline void launch_box_ref(hipStream_t, const float *, float *, int, int) {}
-inline void launch_cost_fused(hipStream_t, Img3, Img3, const float *, const float *, float *, int, int, float, int) {}
-#endif
 
 // ---- K-cost ----------------------------------------------------------------------------------
 // One iteration's warp + cost + parabola + update as a marching kernel (ugsm_kernels_march.hip): one wave per strip of columns, no LDS.

@@ -1,5 +1,5 @@
 // ugsm_lens.hpp -- lens distortion (plumb_bob D) of a correspondence's two pixel positions, stated once for the kernels of
-// ugsm_kernels_cloud.hip and for the host entry point ugsm_undistort_points (include/ugsm.h, "lens distortion").
+// ugsm_kernels_depth.hip and ugsm_kernels_cloud.hip (through ugsm_tri.hpp) and for the host entry point ugsm_undistort_points (include/ugsm.h, "lens distortion").
 //
 // The fixed-point iteration of OpenCV's undistortPoints with R = I, P = K for a camera K (fx, fy, cx, cy; skew ignored) and
 // D = (k1, k2, p1, p2, k3): the pixel coordinate is binary32, every operation below is binary64 and rounded on its own (the library builds
